@@ -24,6 +24,9 @@ mtb-sized indexes, sketch_wave_kernel for the 500-locus one) against HBM bandwid
 algorithmic bytes of SURVEY.md section 8d, with its duration measured live with HIP events on the
 launch stream; `cpu_baseline` times the CPU oracle (oracle/oracle.c + oracle_index.c, a scalar port) on a
 bounded sample of the same workload, on one thread and on the host's cores (up to 64 threads).
+
+`--dump-outputs DIR` writes the vector the last timed step left (coverage per k-mer node and strand, reads per PRG) as .npy files;
+the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -264,6 +267,27 @@ def full_size_checks(torch, ctx, opts, bases, offsets, n_reads, covg, prg_reads,
     return shard_invariant, kernels_agree
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """DIR/<name>.npy of every device array (u32 words held in int32 tensors) as float64, which holds every u32 exactly.  An array
+    that would take the files past DUMP_CAP_BYTES is written as a fixed, seeded sample of its entries (ascending positions, the same
+    on every run), beside <name>_index.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_CAP_BYTES
+    for name, t in arrays.items():
+        a = t.cpu().numpy().view(np.uint32).astype(np.float64)
+        if a.nbytes > left:
+            keep = left // 2 // 16  # (half of what is left: sample + index, 16 bytes per entry)
+            idx = np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))
+            a = a[idx]
+            np.save(os.path.join(out_dir, f"{name}_index.npy"), idx.astype(np.float64))
+            left -= idx.size * 8
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        left -= a.nbytes
+
+
 def write_bgzf(path, data, block=65280, level=1):
     """bgzip's container (gzip members of <= 64 KB with a 'BC' extra field), written with zlib only"""
     import struct
@@ -384,10 +408,15 @@ def main():
     ap.add_argument("--no-checks", action="store_true",
                     help="skip the full-size property checks after the timed region (profiling runs: every launch is then a "
                          "timed full-size one, so rocprofv3 per-kernel averages compare directly with avg_launch_ms)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0's reduced vector: coverage.npy, "
+                         "prg_reads.npy) as float64 .npy files into DIR, to compare two builds output for output")
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be at least 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
     rank = int(os.environ.get("RANK", "0"))
@@ -664,6 +693,8 @@ def main():
         elapsed = float(t.item())
 
     checksum = int(covg.to(torch.int64).sum().item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"coverage": covg, "prg_reads": prg_reads})
     counters = ctx.counters()
     # N > 1: the vector every rank holds must be the sum of the ranks' own vectors (one more, untimed, pass + reduce)
     reduce_consistent = None
