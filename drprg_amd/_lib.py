@@ -120,6 +120,7 @@ SIGNATURES = {
                                         C.c_size_t]),
     "drprg_hip_kernel_timing": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "drprg_hip_filter_schedule": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "drprg_hip_buffer_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
 }
 
 

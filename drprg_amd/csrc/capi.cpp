@@ -1213,6 +1213,21 @@ int drprg_hip_filter_schedule(drprg_hip_ctx* ctx, uint64_t out[20])
     API_END(ctx)
 }
 
+int drprg_hip_buffer_info(drprg_hip_ctx* ctx, uint64_t out[6])
+{
+    API_BEGIN(ctx)
+    if (!out) throw Error(DRPRG_EINVAL, "null pointer");
+    need_mapper(ctx);
+    std::memset(out, 0, 6 * sizeof(uint64_t));
+    for (Mapper* m : mappers_of(ctx)) { // (several devices: the counts summed, the capacities the largest)
+        uint64_t v[6];
+        m->buffer_info(v);
+        for (int i = 0; i < 3; ++i) out[i] += v[i];
+        for (int i = 3; i < 5; ++i) out[i] = std::max(out[i], v[i]);
+    }
+    API_END(ctx)
+}
+
 } // extern "C"
 
 // ---- post-VCF stage ------------------------------------------------------------------------------------

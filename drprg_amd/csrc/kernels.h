@@ -220,7 +220,10 @@ struct FilterWork {
     // entries from b * slice_budget; chunk k of it, tiles [first, end) of the workgroup's range [lo, ..), starts (first - lo) * slice_cpt +
     // k * slice_slack entries in and holds (end - first) * slice_cpt + slice_slack -- room in proportion to its tiles plus a floor for the
     // small ones (a 4-tile chunk that meets five reads from the panel).  The filter kernel leaves start and room next to the count.
+    // The chunks of a dynamic schedule's last round (tickets from slice_extra_from on) hold slice_extra entries more each and start
+    // (k - slice_extra_from) * slice_extra further in: a long read from the panel lying wholly inside one of those small chunks fits it.
     uint32_t slice_budget, slice_cpt, slice_slack;
+    uint32_t slice_extra, slice_extra_from;
     uint64_t* raw_pos;       // global base position of a candidate k-mer, ascending per slice
     uint32_t* slice_count;   // [n_slices], clamped to the slice's room (more: overflow bit 2, the host runs the batch again)
     uint32_t* slice_base;    // [n_slices]: first entry of the slice in raw_pos (/ raw_grp)

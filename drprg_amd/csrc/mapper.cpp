@@ -37,6 +37,9 @@ template <typename T> static void dfree(T*& p)
 enum { C_HITS = 0, C_MINIMIZERS = 1, C_CLUSTERS_KEPT = 2, C_HITS_KEPT = 3, C_OVERFLOW = 4, C_MAXLEN = 5, C_UNSORTED = 6, C_COMPLEX = 7, C_CHUNK = 8, C_N = 16 };
 // reads up to this length get their hits reordered per read (read_sort_kernel); longer ones take the radix sort
 constexpr uint64_t READ_SORT_MAX_LEN = 512;
+// candidate buffers of the filtered sequence: one entry per this many bases of the batch.  One per 64 is laid out by the tile; the quarter
+// added on top is kept for the small chunks of a dynamic schedule's last round (sketch_filter.hip launch_sketch_filter)
+constexpr uint64_t FILTER_BASES_PER_ENTRY = 48;
 
 Mapper::Mapper(const FlatIndex& idx, const MapParams& p, int device) : device_(device)
 {
@@ -167,6 +170,8 @@ Mapper::Mapper(const FlatIndex& idx, const MapParams& p, int device) : device_(d
 #endif
     if (const char* e = std::getenv("DRPRG_HIP_LANES")) max_lanes_ = std::min(4, std::max(1, std::atoi(e)));
     if (const char* e = std::getenv("DRPRG_HIP_LANES_MIN_BASES")) lanes_min_bases_ = std::strtoull(e, nullptr, 10); // (tests: 0)
+    if (const char* e = std::getenv("DRPRG_HIP_MIN_CAPACITY")) // (tests: small batches at the production ratio, or below it to force regrows)
+        min_capacity_ = std::max<uint64_t>(MIN_CAPACITY_CLAMP, std::min<uint64_t>(std::strtoull(e, nullptr, 10), 1ull << 30));
     // ONE allocation [coverage | reads per PRG]: the sample's whole additive state is one contiguous u32 vector, so the
     // collective of the path is a single ncclAllReduce / ncclReduce over it (capi.cpp)
     dmalloc(d_covg_, 2 * (size_t)n_knodes_ + (size_t)n_prgs_);
@@ -588,7 +593,7 @@ void Mapper::leftovers(Lane& lane, const uint8_t* d_bases, const uint64_t* d_off
     wait_stream(stream);
     const uint64_t n_left = lane.h_scratch[L_HITS];
     if (n_left == 0) return;
-    ensure_workspace(std::max<uint64_t>(1u << 20, n_left + n_left / 8));
+    ensure_workspace(std::max<uint64_t>(min_capacity_, n_left + n_left / 8));
     a.hit_key = d_key_a_; // the hit buffers may have moved
     a.hit_val = d_val_a_;
     a.hit_capacity = hit_capacity_;
@@ -642,7 +647,7 @@ void Mapper::direct_launch(int set, const uint8_t* d_bases, const uint64_t* d_of
     }
     ensure_lanes(set + 1, 0); // (the lanes exist; only this set's lane may grow: the other one may belong to a batch in flight)
     Lane& lane = lanes_[(size_t)set];
-    grow_lane(lane, std::min<uint64_t>(std::max<uint64_t>(1u << 20, n_bases / 16), (1ull << 31) - 1));
+    grow_lane(lane, std::min<uint64_t>(std::max<uint64_t>(min_capacity_, n_bases / 16), (1ull << 31) - 1));
     // read_cluster_kernel takes the candidates straight from the tile slices (no gathered list unless reads are left over); what it
     // handled is marked in the dense cand_pos1 array with a value no other batch used (DRPRG_RC_SLICES=0: gather first, as before)
     static const bool from_slices = [] {
@@ -776,6 +781,7 @@ bool Mapper::direct_finish(int set, const uint8_t* d_bases, const uint64_t* d_of
             HIPCHK(hipStreamSynchronize(stream));
         }
         HIPCHK(hipStreamSynchronize(stream)); // (the buffers are about to be freed)
+        ++reruns_direct_;
         t.slice_cap = std::min<uint32_t>(t.slice_cap * 2, 4096);
         grow_lane(lane, std::min<uint64_t>(lane.raw_capacity * 2, (1ull << 31) - 1));
         return false;
@@ -816,6 +822,7 @@ void Mapper::finish_lane(Lane& lane, const uint8_t* d_bases, const uint64_t* d_o
         // (hit_scan_kernel / read_cluster_kernel check the flag); grow the lane and run the range again, alone
         if (attempt > 8) throw Error(DRPRG_EOVERFLOW, "candidate buffer overflow after regrow");
         grow_lane(lane, lane.raw_capacity * 4);
+        ++reruns_filter_;
         launch_lane(lane, stream, d_bases, d_offsets, n_reads, n_bases, covg, prg_reads, pk);
         wait_stream(stream);
     }
@@ -833,6 +840,20 @@ void Mapper::filter_schedule(uint64_t out[20])
 {
     sync();
     for (int i = 0; i < 20; ++i) out[i] = ft_last_[i];
+}
+
+void Mapper::buffer_info(uint64_t out[6])
+{
+    sync(); // (a deferred batch that overflowed is run again when it is completed)
+    uint64_t raw = 0;
+    for (const std::vector<Lane>* v : { &lanes_, &pipe_lanes_ })
+        for (const Lane& lane : *v) raw = std::max(raw, lane.raw_capacity);
+    out[0] = reruns_filter_;
+    out[1] = reruns_direct_;
+    out[2] = regrows_hits_;
+    out[3] = raw;
+    out[4] = hit_capacity_;
+    out[5] = 0;
 }
 
 void Mapper::tune_filter_shares(const Lane& lane, bool packed, uint64_t n_bases)
@@ -960,7 +981,7 @@ void Mapper::map_device_async_impl(const uint8_t* d_bases, const uint64_t* d_off
     }
     Lane& lane = pipe_lanes_[(size_t)pipe_next_];
     // (this lane's previous batch was completed by the call before this one; growing frees its buffers, which waits for the device)
-    grow_lane(lane, std::max<uint64_t>(1u << 20, n_bases / 64));
+    grow_lane(lane, std::max<uint64_t>(min_capacity_, n_bases / FILTER_BASES_PER_ENTRY));
     lane.r0 = 0;
     lane.r1 = (uint32_t)n_reads;
     launch_lane(lane, stream, d_bases, d_offsets, (uint32_t)n_reads, n_bases, covg, prg_reads, pk);
@@ -1077,7 +1098,7 @@ void Mapper::run_batch(const uint8_t* d_bases, const uint64_t* d_offsets, uint32
         // ---- filtered sequences: the hits of short reads never leave the chip (read_cluster_kernel).  The batch is cut into
         // one read range per lane; the ranges run concurrently (lane 0 on the caller's stream), one host wait at the end ----
         const int n_lanes = (n_bases >= lanes_min_bases_ && n_reads >= 64) ? max_lanes_ : 1;
-        const uint64_t lane_cap = std::max<uint64_t>(1u << 20, n_bases / 64 / (uint64_t)n_lanes * (n_lanes > 1 ? 3 : 2) / 2);
+        const uint64_t lane_cap = std::max<uint64_t>(min_capacity_, n_bases / FILTER_BASES_PER_ENTRY / (uint64_t)n_lanes * (n_lanes > 1 ? 3 : 2) / 2);
         ensure_lanes(n_lanes, lane_cap);
         if (n_lanes > 1) HIPCHK(hipEventRecord(ev_begin_, stream));
         for (int j = n_lanes - 1; j >= 0; --j) { // (lane 0 last: its stream is the one the host then waits on)
@@ -1107,7 +1128,7 @@ void Mapper::run_batch(const uint8_t* d_bases, const uint64_t* d_offsets, uint32
         return;
     }
     // ---- direct sequence, generic form: every k-mer hashed, hits in tile order, global radix sort ----
-    ensure_workspace(std::max<uint64_t>(1u << 20, n_bases / 64));
+    ensure_workspace(std::max<uint64_t>(min_capacity_, n_bases / 64));
     const uint32_t n_tiles = dev::sketch_n_tiles(n_bases, halo_);
     ts_ = &tsets_[0];
     if (n_tiles > ts_->first_cap) { // first read of every tile
@@ -1128,6 +1149,7 @@ void Mapper::run_batch(const uint8_t* d_bases, const uint64_t* d_offsets, uint32
         if (h_counters_[C_HITS] > hit_capacity_) {
             if (attempt > 6) throw Error(DRPRG_EOVERFLOW, "hit buffer overflow after regrow");
             ensure_workspace(h_counters_[C_HITS] + h_counters_[C_HITS] / 8 + 1024);
+            ++regrows_hits_;
             continue;
         }
         break;

@@ -131,6 +131,10 @@ public:
     // [1] slices = tickets, [2] tiles per wave of round 0 (even share), [3..6] shares of the four wave classes in 1/256 of an even one,
     // [7..10] when the classes were through in 10 ns from the kernel's first wave (0: not clocked), [11] slices per workgroup, [12..19] chunk size per round
     void filter_schedule(uint64_t out[20]);
+    // the buffers that grow when a batch does not fit them (drprg_hip_buffer_info; counts since the Mapper was made, reset() keeps them):
+    // out[0] read ranges of the filtered sequence run again after a candidate slice overflowed, [1] the same for the direct sequence's
+    // candidate form, [2] regrows of the generic hit buffer, [3] largest raw_capacity of any lane (entries), [4] hit_capacity_, [5] 0.  Synchronises.
+    void buffer_info(uint64_t out[6]);
     void enable_kernel_timing(bool on) { timing_ = on; }
     double sketch_ms_total() const { return sketch_ms_; }
     uint64_t sketch_launches() const { return sketch_launches_; }
@@ -272,6 +276,11 @@ private:
                                     // and read_cluster of the other range wait for it, and what does overlap (verify) competes for the
                                     // same VALU issue slots -- every kernel stretches by about what the overlap saves
     uint64_t lanes_min_bases_ = 64ull << 20; // smaller batches always take one lane
+    // smallest capacity of the candidate / hit buffers, in entries (DRPRG_HIP_MIN_CAPACITY, read here at construction; tests lower it so that
+    // small batches run at the production ratio -- n_bases / 48 for the filtered sequence --, or below it to make the buffers regrow)
+    static constexpr uint64_t MIN_CAPACITY_CLAMP = 4096;
+    uint64_t min_capacity_ = 1u << 20;
+    uint64_t reruns_filter_ = 0, reruns_direct_ = 0, regrows_hits_ = 0; // buffer_info
     hipEvent_t ev_begin_ = nullptr; // recorded on the caller's stream: the other lanes start behind it
     void* d_temp_ = nullptr;
     // candidate form of the direct sequence: one slice of `cap` records per tile.  Two sets of the workspace: the synchronous calls use

@@ -248,6 +248,10 @@ __global__ __launch_bounds__(FT_THREADS) void sketch_filter_kernel(SketchArgs a,
     auto slice_geometry = [&](uint32_t kt, uint32_t b, uint32_t e, uint32_t& base, uint32_t& cap) {
         base = blockIdx.x * fw.slice_budget + (b - wg_lo) * fw.slice_cpt + kt * fw.slice_slack;
         cap = (e - b) * fw.slice_cpt + fw.slice_slack;
+        if (kt >= fw.slice_extra_from) { // (the last round's chunks)
+            base += (kt - fw.slice_extra_from) * fw.slice_extra;
+            cap += fw.slice_extra;
+        }
     };
     uint32_t base_cur, cap_cur;
     slice_geometry(wv, tile, c_all, base_cur, cap_cur);
@@ -952,8 +956,28 @@ hipError_t launch_sketch_filter(const SketchArgs& a, uint32_t read_begin, uint32
         const uint64_t budget = std::min<uint64_t>(b.raw_capacity, 0x7FFFFFFFull) / grid;
         const uint64_t wg_tiles = fw.sched.per_wg > (uint32_t)FT_WAVES ? (n_tiles + grid - 1) / grid : (uint64_t)FT_WAVES * ((n_tiles + grid * FT_WAVES - 1) / (grid * FT_WAVES));
         fw.slice_budget = (uint32_t)budget;
-        fw.slice_slack = (uint32_t)std::min<uint64_t>(256, budget / (4ull * fw.sched.per_wg));
-        fw.slice_cpt = (uint32_t)((budget - (uint64_t)fw.slice_slack * fw.sched.per_wg) / std::max<uint64_t>(wg_tiles, 1));
+        fw.slice_extra = 0;
+        fw.slice_extra_from = 0xFFFFFFFFu;
+        // A dynamic schedule's last round hands out chunks of a few tiles: room by the tile gives them ~4 x slice_cpt + slice_slack, which a
+        // 4 kb read from the panel (~8000 / (w + 1) candidates) overflows -- and the whole batch ran again with every buffer x4, or x16
+        // (ADVICE r06).  A quarter of the workgroup's budget is kept for them: room for tiles wholly inside the panel (2 / (w + 1) of the
+        // positions), as far as the quarter goes -- about one long read per chunk.  The other three quarters are laid out as before, so
+        // that every chunk keeps the room per tile it had when the capacity was a third smaller (mapper.cpp FILTER_BASES_PER_ENTRY).
+        const bool last_round = fw.sched.n_rounds > 1;
+        const uint64_t reserve = last_round ? budget / 4 : 0, main = budget - reserve;
+        fw.slice_slack = (uint32_t)std::min<uint64_t>(256, main / (4ull * fw.sched.per_wg));
+        const uint64_t tiles = std::max<uint64_t>(wg_tiles, 1);
+        fw.slice_cpt = (uint32_t)((main - (uint64_t)fw.slice_slack * fw.sched.per_wg) / tiles);
+        if (last_round) {
+            const uint32_t last = fw.sched.n_rounds - 1, from = fw.sched.first_ticket[last], n_last = fw.sched.per_wg - from;
+            const uint64_t tile_pos = 63ull * (uint64_t)filter_positions_per_lane(level0, a.packed != 0);
+            const uint64_t sz = fw.sched.size[last], want = sz * tile_pos * 2 / (uint64_t)(a.w + 1);
+            const uint64_t have = sz * fw.slice_cpt + fw.slice_slack;
+            if (n_last && want > have) {
+                fw.slice_extra = (uint32_t)std::min<uint64_t>(want - have, reserve / n_last);
+                fw.slice_extra_from = from;
+            }
+        }
     }
     fw.raw_pos = b.raw_pos;
     fw.cand_info = b.cand_info;

@@ -298,6 +298,13 @@ class Context:
                 "round0_class_shares_per_256": v[3:7], "chunk_tiles_per_round": [x for x in v[13:20] if x],
                 "class_end_us": [round(x / 100.0, 1) for x in v[7:11]]}
 
+    def buffer_info(self):
+        """how often the candidate / hit buffers overflowed and the batch ran again, and their capacities in entries (include/drprg_hip.h)"""
+        out = (C.c_uint64 * 6)()
+        _check(lib.drprg_hip_buffer_info(self._h, out), self._h)
+        return dict(filter_reruns=int(out[0]), direct_reruns=int(out[1]), hit_regrows=int(out[2]), lane_capacity=int(out[3]),
+                    hit_capacity=int(out[4]))
+
     def kernel_timing(self, enable=True, reset=False):
         ms, n = C.c_double(), C.c_uint64()
         _check(lib.drprg_hip_kernel_timing(self._h, 1 if enable else 0, 1 if reset else 0, C.byref(ms), C.byref(n)), self._h)

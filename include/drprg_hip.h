@@ -328,6 +328,13 @@ int drprg_hip_kernel_timing(drprg_hip_ctx* ctx, int enable, int reset, double* m
  * [2] tiles per wave of round 0, [3..6] the classes' shares of round 0 in 1/256 of an even one, [7..10] the classes' end times in 10 ns from
  * the kernel's first wave (0: not clocked), [11] chunks per workgroup, [12..19] chunk size of every round in tiles.  Synchronises. */
 int drprg_hip_filter_schedule(drprg_hip_ctx* ctx, uint64_t out[20]);
+/* The device buffers that grow when a batch does not fit them, and how often they had to (tests: the paths that run a batch again).
+ * out[0] read ranges of the filtered sequence run again after a candidate slice overflowed, [1] the same for the direct sequence's
+ * candidate form, [2] regrows of the generic pipeline's hit buffer, [3] largest candidate capacity of any lane in entries, [4] hit
+ * buffer capacity in entries, [5] 0 (reserved).  Counted from drprg_hip_open like the buffers themselves: drprg_hip_reset keeps them.
+ * A multi-device context sums [0..2] and takes the largest [3..4].  The smallest capacity is DRPRG_HIP_MIN_CAPACITY entries (default
+ * 2^20, at least 4096; read when the context opens).  Synchronises. */
+int drprg_hip_buffer_info(drprg_hip_ctx* ctx, uint64_t out[6]);
 
 #ifdef __cplusplus
 }

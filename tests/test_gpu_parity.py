@@ -534,7 +534,7 @@ def test_cli_map_end_to_end(tmp_path, oracle):
 # 50k-variant index.  Two mtb-like indexes: synth.mtb_like_panel() (random backbone, the bench's alternative workload) and
 # the SURVEY 8d index (backbone = the reference's genes.fa, sites = its panel.bcf records + seeded bubbles; bench.py's headline).  Oracle parity on read counts the
 # oracle maps in seconds on the host's cores; the full BASELINE sizes through size-independent properties.
-ORACLE_THREADS = max(1, min(os.cpu_count() or 1, 32))
+ORACLE_THREADS = max(1, min(16, len(os.sched_getaffinity(0))))  # (a GPU box gives a command 16 CPUs of many)
 GOLDEN_INDEX_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "downstream")
 _PANELS = {}
 
@@ -790,7 +790,7 @@ def test_wave_tile_geometry_edges(tmp_path, oracle, monkeypatch, fuse):
 
 
 @pytest.mark.parametrize("kernel", [0, 1, 3])
-def test_deferred_batches_equal_synchronous_ones(tmp_path, oracle, kernel):
+def test_deferred_batches_equal_synchronous_ones(tmp_path, oracle, monkeypatch, kernel):
     """drprg_hip_map_device_async: a batch is queued and its read-back is looked at while the next one runs.  Batches that need the
     host afterwards -- dense reads that overflow the candidate slices (run again with larger buffers), reads of a 70-copy locus
     that read_cluster_kernel leaves to the generic pipeline -- come out exactly as through the synchronous call and as the oracle
@@ -815,16 +815,25 @@ def test_deferred_batches_equal_synchronous_ones(tmp_path, oracle, kernel):
     tens = [(torch.from_numpy(np.ascontiguousarray(b)).to(dev), torch.from_numpy(o.astype(np.int64)).to(dev), len(o) - 1, int(o[-1]))
             for b, o in batches]
     torch.cuda.synchronize()
+    # the buffers at their production size (n_bases / 48; the direct sequence's n_bases / 16, the generic one's n_bases / 64) instead of the 2^20-entry floor, which
+    # batches this small never outgrow: the dense ones do outgrow them (drprg_hip_buffer_info counts the reruns)
+    monkeypatch.setenv("DRPRG_HIP_MIN_CAPACITY", "0")
     ctx = _ctx(tmp_path, panel, 11, 15, True, kernel=kernel)
     for tb, to, n, nb in tens:
         ctx.map_device(tb.data_ptr(), to.data_ptr(), n, nb)
     want, want_prg = ctx.coverage()
     want_cnt = ctx.counters()
+    reran = ctx.buffer_info()
     ctx.reset()
     for tb, to, n, nb in tens:
         ctx.map_device_async(tb.data_ptr(), to.data_ptr(), n, nb)
     got, got_prg = ctx.coverage()  # (reading results completes the batch in flight)
     cnt = ctx.counters()
+    info = ctx.buffer_info()
+    which = {0: "filter_reruns", 1: "hit_regrows", 3: "direct_reruns"}[kernel]
+    assert reran[which] >= 1, reran  # the synchronous pass ran a batch again ...
+    if kernel != 1:  # ... and so did the deferred one, on the lanes of its own (kernel 1 has none: its hit buffer had grown already)
+        assert info[which] > reran[which], (reran, info)
     assert np.array_equal(got, want) and np.array_equal(got_prg, want_prg)
     for key in ("reads", "bases", "minimizers", "hits", "clusters_kept", "hits_kept", "leftover_reads"):
         assert cnt[key] == want_cnt[key], key
