@@ -1,6 +1,6 @@
 // candidates.hip -- the candidate stage of the filtered launch sequence (see the overview at the top of
-// sketch_filter.hip): slices of candidate positions -> one dense list ordered by (read, position) -> exact lookup and
-// window-minimizer test per candidate (verify_count_kernel) -> batch totals; and, for the reads that
+// sketch_filter.hip): slices of candidate positions -> exact lookup and window-minimizer test per candidate, written as one dense
+// list ordered by (read, position) (verify_scan_kernel) -> batch totals; and, for the reads that
 // read_cluster_kernel leaves over, the hit list for the generic cluster pipeline (recount / expand / per-read reorder).
 #include "filter_common.h"
 #include "verify_lane.h"
@@ -13,106 +13,23 @@ namespace drprg {
 namespace dev {
 
 // ---------------------------------------------------------------------------------------------
-// scans
-// ---------------------------------------------------------------------------------------------
-// one workgroup: cand_prefix = exclusive scan of slice_count (the gathered form: DRPRG_VERIFY_FORM=gather, read_verify_kernel)
-__global__ __launch_bounds__(SCAN_THREADS) void cand_scan_kernel(FilterWork fw)
-{
-    __shared__ uint32_t s_w[SCAN_THREADS / 64 + 1];
-    constexpr int PER = MAX_CHUNKS / SCAN_THREADS;
-    const int tid = threadIdx.x;
-    // two passes over this thread's PER consecutive slices: their sum, then -- behind the block scan -- their prefixes
-    uint32_t run = 0;
-    for (int i = 0; i < PER; ++i) {
-        const uint32_t s = (uint32_t)tid * PER + i;
-        if (s >= fw.n_slices) break;
-        const uint32_t n = fw.slice_count[s];
-        run += n;
-    }
-    uint32_t total;
-    uint32_t acc = block_exclusive_scan<SCAN_THREADS / 64>(run, s_w, &total);
-    for (int i = 0; i < PER; ++i) {
-        const uint32_t s = (uint32_t)tid * PER + i;
-        if (s >= fw.n_slices) break;
-        const uint32_t n = fw.slice_count[s];
-        fw.cand_prefix[s] = acc;
-        acc += n;
-    }
-    if (tid == 0) fw.cand_prefix[fw.n_slices] = total;
-}
-
-// ---------------------------------------------------------------------------------------------
 // verification (the per-candidate device functions: verify_lane.h)
 // ---------------------------------------------------------------------------------------------
-// slices -> one dense, ordered list of candidate positions (cand_gp; the verification kernel writes cand_info / cand_pos1 / cand_rec
-// at the same indices.  Until round 5 the positions went to cand_info and were replaced there: read_verify_kernel's workgroups read
-// positions their neighbours own, so the list has to stay as it is)
-__global__ __launch_bounds__(64) void cand_gather_kernel(FilterWork fw)
-{
-    const uint32_t s = blockIdx.x;
-    const uint32_t n = fw.cand_prefix[s + 1] - fw.cand_prefix[s];
-    const uint64_t* __restrict__ src = fw.raw_pos + fw.slice_base[s];
-    uint64_t* __restrict__ dst = fw.cand_gp + fw.cand_prefix[s];
-    for (uint32_t i = threadIdx.x; i < n; i += 64) dst[i] = src[i];
-}
-
-template <int KC, bool PACKED>
-__global__ __launch_bounds__(EX_THREADS) void verify_count_kernel(SketchArgs a, FilterWork fw, ReadClusterArgs rc)
-{
-    __shared__ uint32_t s_red[3][EX_THREADS / 64];
-    const int tid = threadIdx.x;
-    uint32_t t_begin, t_end;
-    candidate_range(fw, blockIdx.x, gridDim.x, t_begin, t_end);
-    const VerifyConsts c(a, fw);
-    uint32_t my_hits = 0, my_nmin = 0, my_maxlen = 0;
-    // (the position of this thread's next candidate is requested one round early: one round trip less in the chain of each)
-    int64_t gp_next = t_begin + tid < t_end ? (int64_t)fw.cand_gp[t_begin + tid] : 0;
-    for (uint32_t t = t_begin + tid; t < t_end; t += EX_THREADS) {
-        const int64_t gp = gp_next;
-        if (t + EX_THREADS < t_end) gp_next = (int64_t)fw.cand_gp[t + EX_THREADS];
-        VerifyOut o;
-        verify_one_lane<KC, PACKED>(a, fw, rc, c, gp, o, my_hits, my_nmin, my_maxlen);
-        fw.cand_pos1[t] = o.pos1;
-        fw.cand_info[t] = ((uint64_t)o.slot << 32) | ((uint64_t)o.strand << 31) | (uint64_t)o.read;
-        fw.cand_rec[t] = o.crec;
-    }
-    // ---- per-workgroup totals (the only barrier of the kernel) ----
-    const uint32_t wh = wave_inclusive_scan(my_hits), wn = wave_inclusive_scan(my_nmin), wm = wave_max(my_maxlen);
-    if ((tid & 63) == 63) {
-        s_red[0][tid >> 6] = wh;
-        s_red[1][tid >> 6] = wn;
-        s_red[2][tid >> 6] = wm;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        uint32_t h = 0, n = 0, mx = 0;
-        for (int i = 0; i < EX_THREADS / 64; ++i) {
-            h += s_red[0][i];
-            n += s_red[1][i];
-            mx = s_red[2][i] > mx ? s_red[2][i] : mx;
-        }
-        fw.wg_hits[blockIdx.x] = h;
-        fw.wg_nmin[blockIdx.x] = n;
-        fw.wg_maxlen[blockIdx.x] = mx;
-    }
-}
-
-// The same kernel WITHOUT cand_scan_kernel and cand_gather_kernel in front of it (round 5: 10 + 12 us of a 0.59 ms step, one workgroup's
-// latency and a copy of 14 MB).  Every workgroup scans the counts itself -- since round 6 those of the SUPERBLOCKS, FT_SUPER slices each, which
-// the filter kernel keeps next to the slice counts: 8192 words at most, 16 per thread, one coalesced round trip and a block scan: 16 MB of L2
-// reads over the whole grid --, leaves the exclusive prefix of every superblock in LDS (32 KB), takes its share [t_begin, t_end) of the
-// ordered list from the total, and reads the positions of its candidates straight from the filter kernel's slices: entry t lives in the
-// superblock s with prefix[s] <= t < prefix[s + 1] (a candidate bisects the superblocks of its workgroup's share, a handful of a full batch),
-// there in the slice the eight slice counts of the superblock say (one more round trip to the L2, requested a candidate ahead like the
-// position itself), at raw_pos[start of the slice + rest].  Workgroup 0 leaves the total where read_cluster_kernel and the generic pipeline
-// look for it (*fw.cand_total).  The dense list of positions (fw.cand_gp) is not made: only the experimental read-by-read form wants it,
-// and gets the old sequence.
+// One kernel scans the slice counts, gathers the positions and verifies (until round 5 a scan kernel and a gather kernel ran in front of a
+// verification kernel: 10 + 12 us of a 0.59 ms step, one workgroup's latency and a copy of 14 MB).  Every workgroup scans
+// the counts itself -- since round 6 those of the SUPERBLOCKS, FT_SUPER slices each, which the filter kernel keeps next to the slice counts:
+// 8192 words at most, 16 per thread, one coalesced round trip and a block scan: 16 MB of L2 reads over the whole grid --, leaves the exclusive
+// prefix of every superblock in LDS (32 KB), takes its share [t_begin, t_end) of the ordered list from the total, and reads the positions of
+// its candidates straight from the filter kernel's slices: entry t lives in the superblock s with prefix[s] <= t < prefix[s + 1] (a candidate
+// bisects the superblocks of its workgroup's share, a handful of a full batch), there in the slice the eight slice counts of the superblock
+// say (one more round trip to the L2, requested a candidate ahead like the position itself), at raw_pos[start of the slice + rest].  Workgroup
+// 0 leaves the total where read_cluster_kernel and the generic pipeline look for it (*fw.cand_total).
 #ifndef DRPRG_VS_THREADS // (measurement builds)
 #define DRPRG_VS_THREADS 512
 #endif
-// threads per workgroup: every workgroup pays the slice scan once, so fewer and larger ones pay less of it -- 256 (as verify_count_kernel, 8 per
-// CU) measured 0.516 ms per step on the 8d index (packed 0.452), 512 (4 per CU) 0.503-0.512 (0.445), 1024 (2 per CU) 0.507-0.514 (0.447);
-// the larger indexes do not care (profiles/r05/verify_scan.txt)
+// threads per workgroup: every workgroup pays the slice scan once, so fewer and larger ones pay less of it -- 256 (8 per CU) measured 0.516 ms
+// per step on the 8d index (packed 0.452), 512 (4 per CU) 0.503-0.512 (0.445), 1024 (2 per CU) 0.507-0.514 (0.447); the larger indexes do
+// not care (profiles/r05/verify_scan.txt)
 constexpr int VS_THREADS = DRPRG_VS_THREADS;
 constexpr int VS_PER = MAX_SLICES / VS_THREADS; // superblocks per thread of the scan
 template <int KC, bool PACKED>
@@ -121,7 +38,6 @@ __global__ __launch_bounds__(VS_THREADS, 8) void verify_scan_kernel(SketchArgs a
     __shared__ uint32_t s_red[3][VS_THREADS / 64];
     __shared__ uint32_t s_w[VS_THREADS / 64 + 1];
     __shared__ uint32_t s_share[2];
-    __shared__ uint32_t s_ticket; // (interleaved order: the workgroup's round counter)
     __shared__ __attribute__((aligned(16))) uint32_t s_pre[MAX_SLICES + 4]; // exclusive prefix of ALL superblocks (32 KB; one past the last: the total)
     const int tid = threadIdx.x;
     // ---- the scan: my VS_PER consecutive superblocks (FT_SUPER slices each; the filter kernel summed their clamped counts) ----
@@ -137,7 +53,7 @@ __global__ __launch_bounds__(VS_THREADS, 8) void verify_scan_kernel(SketchArgs a
     for (int i = 0; i < VS_PER / 4; ++i) run += v[i].x + v[i].y + v[i].z + v[i].w;
     uint32_t total;
     const uint32_t before = block_exclusive_scan<VS_THREADS / 64>(run, s_w, &total);
-    if (blockIdx.x == 0 && tid == 0) fw.cand_prefix[fw.n_slices] = total; // = *fw.cand_total
+    if (blockIdx.x == 0 && tid == 0) *fw.cand_count = total; // = *fw.cand_total
     if (fw.debug & 2048u) return; // (DRPRG_FT_DEBUG=2048: measurement only, the slice scan alone)
     // Every thread leaves the prefixes of its own slices in LDS, out of the counts it still holds: entry t of the list then lives in the
     // slice s with s_pre[s] <= t < s_pre[s + 1], for every t, and no workgroup reads a count twice.  (Until late in round 5 a window of 64
@@ -166,7 +82,6 @@ __global__ __launch_bounds__(VS_THREADS, 8) void verify_scan_kernel(SketchArgs a
             n1 += (p.y <= x1 ? 1u : 0u) + (p.z <= x1 ? 1u : 0u) + (p.w <= x1 ? 1u : 0u) + (acc <= x1 ? 1u : 0u);
         }
         if (tid == VS_THREADS - 1) s_pre[MAX_SLICES] = acc; // (= total)
-        if (tid == 0) s_ticket = 0;
         if (own0) s_share[0] = (uint32_t)tid * VS_PER + n0;
         if (own1) s_share[1] = (uint32_t)tid * VS_PER + n1;
     }
@@ -195,36 +110,13 @@ __global__ __launch_bounds__(VS_THREADS, 8) void verify_scan_kernel(SketchArgs a
         }
         return (int64_t)fw.raw_pos[(size_t)at + (rest - before)];
     };
-    if (fw.verify_interleave) {
-        // Interleaved order (round 6): the list is cut into rounds of 64 consecutive candidates; round r belongs to workgroup r mod grid, whose
-        // waves take its rounds by ticket (an LDS counter; a wave's first is its own number).  A workgroup samples the whole list instead
-        // of owning one stretch of it -- stretches differ: reads off the panel end at the table probe, reads on it walk their windows --
-        // and a wave that drew cheap rounds draws more of them.
-        const uint32_t n_rounds = (total + 63u) >> 6;
-        const uint32_t lane = (uint32_t)tid & 63u;
-        uint32_t r = (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)(tid >> 6) * gridDim.x + blockIdx.x));
-        int64_t gp_next = (r < n_rounds && r * 64u + lane < total) ? position_in(r * 64u + lane, 0u, (uint32_t)MAX_SLICES - 1u, (uint32_t)MAX_SLICES / 2u) : 0;
-        while (r < n_rounds) { // (wave-uniform)
-            const uint32_t t = r * 64u + lane;
-            const int64_t gp = gp_next;
-            uint32_t drawn = 0;
-            if (lane == 0) drawn = atomicAdd(&s_ticket, 1u);
-            const uint32_t rn = ((uint32_t)(VS_THREADS / 64) + (uint32_t)__builtin_amdgcn_readfirstlane((int)drawn)) * gridDim.x + blockIdx.x;
-            if (rn < n_rounds && rn * 64u + lane < total) gp_next = position_in(rn * 64u + lane, 0u, (uint32_t)MAX_SLICES - 1u, (uint32_t)MAX_SLICES / 2u);
-            if (t < total) {
-                VerifyOut o;
-                if (!(fw.debug & 512u)) verify_one_lane<KC, PACKED>(a, fw, rc, c, gp, o, my_hits, my_nmin, my_maxlen);
-                fw.cand_pos1[t] = o.pos1;
-                fw.cand_info[t] = ((uint64_t)o.slot << 32) | ((uint64_t)o.strand << 31) | (uint64_t)o.read;
-                fw.cand_rec[t] = o.crec;
-            }
-            r = rn;
-        }
-    } else if (t_begin < t_end) { // (workgroup-uniform)
+    // (No `if (t_begin < t_end)` around this block: a workgroup without a share reads bounds it never uses and skips the loop.  With that
+    // test, and without the second loop this kernel had until the interleaved order was deleted, the compiler reloaded spilled scalar
+    // registers ~20 more times per candidate: +1.8 us per launch on packed mtb.  Keep the loop's shape when touching it.)
+    {
         // the superblocks of this workgroup's share [t_begin, t_end): its candidates bisect only those (a handful of a full batch)
         const uint32_t s_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_share[0]), s_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_share[1]);
-        uint32_t span_step = 1;
-        while (2 * span_step <= s_hi - s_lo) span_step *= 2; // (largest power of two <= the span, at least 1)
+        const uint32_t span_step = s_hi > s_lo ? 1u << (31 - __builtin_clz(s_hi - s_lo)) : 1u; // (largest power of two <= the span, at least 1)
         auto position_of = [&](uint32_t t) -> int64_t { return position_in(t, s_lo, s_hi, span_step); }; // t_begin <= t < t_end
         // (the position of this thread's next candidate is requested one round early: one round trip less in the chain of each)
         int64_t gp_next = t_begin + tid < t_end ? position_of(t_begin + (uint32_t)tid) : 0;
@@ -282,7 +174,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void hit_scan_kernel(SketchArgs a, Fi
     const int tid = threadIdx.x;
     uint32_t v[PER], h[PER], nm[PER], ml[PER], run = 0, nmin = 0, mx = 0;
 #pragma unroll
-    for (int i = 0; i < PER; ++i) { // (all twelve loads together, as in cand_scan_kernel)
+    for (int i = 0; i < PER; ++i) { // (all twelve loads together)
         const uint32_t g = (uint32_t)tid * PER + i, gc = g < n_wg ? g : 0u;
         h[i] = fw.wg_hits[gc];
         nm[i] = fw.wg_nmin[gc];
@@ -424,7 +316,7 @@ __global__ __launch_bounds__(RS_THREADS) void read_fix_kernel(uint64_t* __restri
     }
 }
 
-// what read_cluster_kernel left behind: hits and longest read per workgroup range (the layout verify_count_kernel wrote)
+// what read_cluster_kernel left behind: hits and longest read per workgroup range (the layout verify_scan_kernel wrote)
 __global__ __launch_bounds__(EX_THREADS) void recount_kernel(SketchArgs a, FilterWork fw)
 {
     __shared__ uint32_t s_red[2][EX_THREADS / 64];
@@ -469,7 +361,7 @@ __device__ __forceinline__ bool tile_overflow(const SketchArgs& a, const uint32_
     return (*reinterpret_cast<volatile uint32_t*>(a.overflow) & 4u) != 0 || (uint64_t)tile_prefix[n_tiles] > dense_capacity;
 }
 
-// The batch counters: hits and minimizers of all tiles (and what sketch_wave_kernel clustered itself), summed by a small grid --
+// The batch counters: hits and minimizers of all tiles, summed by a small grid --
 // one atomic per counter and workgroup: as part of the gather (6000 workgroups, four atomics each on the same four addresses) the
 // sums cost 0.3 ms of its 0.8 on the 500-locus index.
 // block_first != nullptr (read_cluster_kernel<SLICES> follows): word m = the slice that holds entry 64 m of the ordered list
@@ -482,7 +374,7 @@ __global__ __launch_bounds__(TG_THREADS) void tile_totals_kernel(SketchArgs a, c
         if (blockIdx.x == 0 && tid == 0) atomicOr(a.overflow, 4u);
         return;
     }
-    uint32_t my_hits = 0, my_nmin = 0, my_fc = 0, my_fh = 0;
+    uint32_t my_hits = 0, my_nmin = 0;
     for (uint32_t t = blockIdx.x * TG_THREADS + (uint32_t)tid; t < n_tiles; t += gridDim.x * TG_THREADS) {
         my_hits += a.tile_hits[t];
         my_nmin += a.tile_nmin[t];
@@ -490,28 +382,19 @@ __global__ __launch_bounds__(TG_THREADS) void tile_totals_kernel(SketchArgs a, c
             const uint32_t lo = tile_prefix[t], hi = tile_prefix[t + 1];
             for (uint32_t m = (lo + 63u) >> 6; lo < hi && (uint64_t)m << 6 < hi; ++m) block_first[m] = t;
         }
-        if (a.fuse > 0) { // what sketch_wave_kernel clustered itself
-            const uint32_t f = a.tile_fast[t];
-            my_fc += f & 0xFFFFu;
-            my_fh += f >> 16;
-        }
     }
     // (sums of 32-bit partials per workgroup: a workgroup covers at most n_tiles / gridDim.x + 1024 tiles of <= 2^16 hits each)
-    uint32_t hits, nmin, fc, fh;
+    uint32_t hits, nmin;
     (void)block_exclusive_scan<TG_THREADS / 64>(my_hits, s_w, &hits);
     (void)block_exclusive_scan<TG_THREADS / 64>(my_nmin, s_w, &nmin);
-    (void)block_exclusive_scan<TG_THREADS / 64>(my_fc, s_w, &fc);
-    (void)block_exclusive_scan<TG_THREADS / 64>(my_fh, s_w, &fh);
     if (tid == 0) {
         if (hits) atomicAdd(a.n_hits, (unsigned long long)hits);
         if (nmin) atomicAdd(a.n_minimizers, (unsigned long long)nmin);
-        if (fc) atomicAdd(a.n_clusters_kept, (unsigned long long)fc);
-        if (fh) atomicAdd(a.n_hits_kept, (unsigned long long)fh);
     }
 }
 
-// The slices copied into the dense, ordered candidate list.  mark != 0 (a copy after read_cluster_kernel has read the candidates
-// from the slices): a candidate whose dense cand_pos1 holds the mark was handled there and gets position 0.
+// The slices copied into the dense, ordered candidate list after read_cluster_kernel has read the candidates from the slices: a
+// candidate whose dense cand_pos1 holds the mark was handled there and gets position 0.
 __global__ __launch_bounds__(TG_THREADS) void tile_gather_kernel(SketchArgs a, FilterWork fw, const uint32_t* __restrict__ tile_prefix,
     uint32_t n_tiles, uint64_t dense_capacity, uint32_t mark)
 {
@@ -540,7 +423,7 @@ __global__ __launch_bounds__(TG_THREADS) void tile_gather_kernel(SketchArgs a, F
                 const uint32_t i = i0 + 64u * (uint32_t)u + (uint32_t)lane;
                 if (i < n) {
                     fw.cand_info[dst + i] = ci[u];
-                    fw.cand_pos1[dst + i] = (mark && fw.cand_pos1[dst + i] == mark) ? 0u : cp[u];
+                    fw.cand_pos1[dst + i] = fw.cand_pos1[dst + i] == mark ? 0u : cp[u];
                     fw.cand_rec[dst + i] = cr[u];
                 }
             }
@@ -551,68 +434,20 @@ __global__ __launch_bounds__(TG_THREADS) void tile_gather_kernel(SketchArgs a, F
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-// (Round 3 tried to do without the two single-workgroup scans of this sequence, cand_scan_kernel and hit_scan_kernel, 10 + 6 us:
-// every workgroup of cand_gather_kernel summing the slice counts before its own, and every workgroup of verify_count_kernel adding
-// its totals to the batch counters with three atomics.  Measured: cand_gather 11 -> 38 us (8192 workgroups x up to 8192 loads),
-// verify_count 116 -> 231 us (12 k atomics on one 64-byte line take their turn in the L2), step 0.59 -> 0.72 ms.  Round 4: the totals of
-// hit_scan_kernel are summed by workgroup 0 of read_cluster_kernel when that kernel follows (with_totals = false); scan + gather in one
-// launch -- a workgroup summing what lies before its 64 slices -- took 19.4 us against 9.1 + 11.8: cand_scan_kernel stays.)
-// DRPRG_VERIFY_FORM=gather keeps the three-kernel sequence of rounds 1-4 (A/B runs, a second way through the parity tests); the
-// experimental read-by-read form (make EXPERIMENTAL=1 + DRPRG_VERIFY_FORM=read: read_verify.hip, bit-exact and 8 % slower,
-// profiles/r05/read_verify.txt) needs the gathered list of positions as well.  Read at every launch (the tests switch it); the host
-// allocates FilterBuffers::cand_gp only for a launch that will gather (8 bytes per candidate slot the default sequence never touches: ADVICE r05).
-bool gathered_list_requested()
-{
-    const char* form = std::getenv("DRPRG_VERIFY_FORM");
-    if (!form) return false;
-    const std::string f(form);
-#ifdef DRPRG_EXPERIMENTAL
-    return f == "gather" || f == "read";
-#else
-    return f == "gather";
-#endif
-}
-
+// (the three-kernel sequence of rounds 1-4 -- cand_scan, cand_gather, verify_count -- and a read-by-read verification lost to this one
+// launch: DESIGN.md section 6, profiles/r05/verify_scan.txt and read_verify.txt)
 hipError_t launch_candidate_stage(const SketchArgs& a, FilterWork& fw, const ReadClusterArgs& rc, int n_cus, hipStream_t stream, bool with_totals)
 {
-    fw.verify_grid = fw.ex_grid;
-    const char* form = std::getenv("DRPRG_VERIFY_FORM");
-    bool gathered = form && std::string(form) == "gather";
-    {   // DRPRG_VERIFY_ORDER=contiguous | interleave (read at every launch): which candidates a workgroup of verify_scan_kernel takes
-        const char* order = std::getenv("DRPRG_VERIFY_ORDER");
-        fw.verify_interleave = order && std::string(order) == "interleave" ? 1u : 0u;
-    }
-#ifdef DRPRG_EXPERIMENTAL
-    const bool by_read = read_verify_applies(a, fw);
-    gathered = gathered || by_read;
-#endif
-    if (gathered && !fw.cand_gp) return hipErrorInvalidValue; // (the caller allocates it when gathered_list_requested())
-    if (!gathered) { // one launch: verify_scan_kernel scans the slice counts itself and reads the slices
-        // (DRPRG_VERIFY_WG_PER_CU: measurements.  The grid is what fills the CUs' 2048 thread slots: fewer or more workgroups per CU measured
-        // within the noise or worse; profiles/r05/verify_scan.txt)
-        static const int per_cu = [] { const char* e = std::getenv("DRPRG_VERIFY_WG_PER_CU"); return e ? std::max(1, std::atoi(e)) : 0; }();
-        fw.verify_grid = std::min<uint32_t>((uint32_t)n_cus * (uint32_t)(per_cu ? per_cu : 2048 / VS_THREADS), MAX_EX_WG); // (2048 threads per CU)
-        const dim3 grid(fw.verify_grid);
-        if (a.packed) {
-            if (a.k == 15) hipLaunchKernelGGL((verify_scan_kernel<15, true>), grid, dim3(VS_THREADS), 0, stream, a, fw, rc);
-            else hipLaunchKernelGGL((verify_scan_kernel<0, true>), grid, dim3(VS_THREADS), 0, stream, a, fw, rc);
-        } else if (a.k == 15) hipLaunchKernelGGL((verify_scan_kernel<15, false>), grid, dim3(VS_THREADS), 0, stream, a, fw, rc);
-        else hipLaunchKernelGGL((verify_scan_kernel<0, false>), grid, dim3(VS_THREADS), 0, stream, a, fw, rc);
-    } else {
-        hipLaunchKernelGGL(cand_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, stream, fw);
-        hipLaunchKernelGGL(cand_gather_kernel, dim3(fw.n_slices), dim3(64), 0, stream, fw);
-#ifdef DRPRG_EXPERIMENTAL
-        if (by_read) {
-            fw.verify_grid = std::min<uint32_t>(read_verify_grid(n_cus), MAX_EX_WG);
-            HIP_TRY(launch_read_verify(a, fw, rc, fw.verify_grid, stream));
-        } else
-#endif
-        if (a.packed) {
-            if (a.k == 15) hipLaunchKernelGGL((verify_count_kernel<15, true>), dim3(fw.ex_grid), dim3(EX_THREADS), 0, stream, a, fw, rc);
-            else hipLaunchKernelGGL((verify_count_kernel<0, true>), dim3(fw.ex_grid), dim3(EX_THREADS), 0, stream, a, fw, rc);
-        } else if (a.k == 15) hipLaunchKernelGGL((verify_count_kernel<15, false>), dim3(fw.ex_grid), dim3(EX_THREADS), 0, stream, a, fw, rc);
-        else hipLaunchKernelGGL((verify_count_kernel<0, false>), dim3(fw.ex_grid), dim3(EX_THREADS), 0, stream, a, fw, rc);
-    }
+    // (DRPRG_VERIFY_WG_PER_CU: measurements.  The grid is what fills the CUs' 2048 thread slots: fewer or more workgroups per CU measured
+    // within the noise or worse; profiles/r05/verify_scan.txt)
+    static const int per_cu = [] { const char* e = std::getenv("DRPRG_VERIFY_WG_PER_CU"); return e ? std::max(1, std::atoi(e)) : 0; }();
+    fw.verify_grid = std::min<uint32_t>((uint32_t)n_cus * (uint32_t)(per_cu ? per_cu : 2048 / VS_THREADS), MAX_EX_WG); // (2048 threads per CU)
+    const dim3 grid(fw.verify_grid);
+    if (a.packed) {
+        if (a.k == 15) hipLaunchKernelGGL((verify_scan_kernel<15, true>), grid, dim3(VS_THREADS), 0, stream, a, fw, rc);
+        else hipLaunchKernelGGL((verify_scan_kernel<0, true>), grid, dim3(VS_THREADS), 0, stream, a, fw, rc);
+    } else if (a.k == 15) hipLaunchKernelGGL((verify_scan_kernel<15, false>), grid, dim3(VS_THREADS), 0, stream, a, fw, rc);
+    else hipLaunchKernelGGL((verify_scan_kernel<0, false>), grid, dim3(VS_THREADS), 0, stream, a, fw, rc);
     if (with_totals) hipLaunchKernelGGL(hit_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, stream, a, fw, 0, fw.verify_grid); // (else: read_cluster_kernel's workgroup 0)
     return hipGetLastError();
 }
@@ -642,30 +477,25 @@ uint32_t direct_first_read_tiles(uint64_t n_bases, int halo, int k, int w, bool 
 hipError_t launch_direct_candidates(const SketchArgs& a, bool wide_hash, uint32_t* tile_prefix, void* temp, size_t temp_bytes,
     uint64_t dense_capacity, const ReadClusterArgs& rc, int n_cus, FilterWork& fw, hipStream_t stream, KernelTimer timer, uint32_t slices_mark)
 {
-    if (a.n_bases == 0 || !a.tile_cap) return hipErrorInvalidValue;
+    if (a.n_bases == 0 || !a.tile_cap || !slices_mark) return hipErrorInvalidValue;
     const uint32_t n_tiles = direct_candidate_tiles(a.n_bases, a.halo, a.k, a.w, wide_hash);
     if (use_wave_form(a.k, a.w, wide_hash)) HIP_TRY(launch_sketch_wave(a, stream, timer));
     else HIP_TRY(launch_sketch_probe(a, wide_hash, stream, timer));
     // tile_count[n_tiles] is a zero the caller keeps there: the exclusive scan of n_tiles + 1 counts ends with the total
     HIP_TRY(exclusive_scan_u32(temp, temp_bytes, a.tile_count, tile_prefix, n_tiles + 1, stream));
     fw.cand_total = tile_prefix + n_tiles;
-    const dim3 grid((n_tiles + TG_TILES - 1) / TG_TILES);
-    // (the block table of the slices form lives in the dense cand_info array: two words per entry of capacity, one per 64 needed)
-    uint32_t* const block_first = slices_mark && dense_capacity ? reinterpret_cast<uint32_t*>(fw.cand_info) : nullptr;
+    // (the block table lives in the dense cand_info array: two words per entry of capacity, one per 64 needed)
+    uint32_t* const block_first = dense_capacity ? reinterpret_cast<uint32_t*>(fw.cand_info) : nullptr;
     hipLaunchKernelGGL(tile_totals_kernel, dim3(std::min<uint32_t>((n_tiles + TG_THREADS - 1) / TG_THREADS, (uint32_t)n_cus)), dim3(TG_THREADS), 0, stream, a,
         tile_prefix, n_tiles, dense_capacity, block_first);
     HIP_TRY(hipGetLastError());
-    if (slices_mark) { // read_cluster_kernel takes the candidates from the slices: a dense list only if reads are left over
-        ReadClusterArgs rcs = rc;
-        rcs.block_first = block_first;
-        rcs.slice_prefix = tile_prefix;
-        rcs.n_slices = n_tiles;
-        rcs.mark_epoch = slices_mark;
-        return launch_read_cluster(a, fw, rcs, n_cus, false, stream);
-    }
-    hipLaunchKernelGGL(tile_gather_kernel, grid, dim3(TG_THREADS), 0, stream, a, fw, tile_prefix, n_tiles, dense_capacity, 0u);
-    HIP_TRY(hipGetLastError());
-    return launch_read_cluster(a, fw, rc, n_cus, false, stream);
+    // read_cluster_kernel takes the candidates from the slices: a dense list only if reads are left over (launch_tile_gather_marked)
+    ReadClusterArgs rcs = rc;
+    rcs.block_first = block_first;
+    rcs.slice_prefix = tile_prefix;
+    rcs.n_slices = n_tiles;
+    rcs.mark_epoch = slices_mark;
+    return launch_read_cluster(a, fw, rcs, n_cus, false, stream);
 }
 
 // the dense list after all, for the reads read_cluster_kernel<SLICES> left over: the slices copied, handled candidates (dense

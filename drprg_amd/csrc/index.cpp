@@ -159,7 +159,7 @@ void PrgIndex::flatten()
                 const uint32_t hr = code * BLOOM_CR;
                 f.bloomr[hr >> (32 - BLOOMR_WBITS)] |= (1u << (hr & 31)) | (1u << ((hr >> 5) & 31)) | (1u << ((hr >> 10) & 31)) | (1u << ((hr >> 15) & 31));
                 // the same stage inside the level-0 array: word = top 15 bits of the hash, three bits from its low 15, three from a
-                // second hash (six bits: the array is a third full, and every false positive is a candidate verify_count_kernel pays for)
+                // second hash (six bits: the array is a third full, and every false positive is a candidate verify_scan_kernel pays for)
                 const uint32_t hs = code * BLOOM_C2;
                 f.bloom0f[hr >> (32 - L0_WBITS)] |= (1u << (hr & 31)) | (1u << ((hr >> 5) & 31)) | (1u << ((hr >> 10) & 31)) | (1u << (hs >> 27))
                     | (1u << ((hs >> 22) & 31)) | (1u << ((hs >> 17) & 31));

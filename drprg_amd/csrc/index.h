@@ -38,7 +38,7 @@ struct FlatIndex {
     uint32_t bloom0_wbits = 0;
     std::vector<uint32_t> bloom0;
     std::vector<uint32_t> bloom0f; // bloom0 plus the second-stage bits of every code (four per code, in the word its BLOOM_CR hash selects)
-    // with level 0: the second stage (refine_kernel), 2^14 words keyed on the whole k-mer code, four bits per code
+    // with level 0: a second stage of its own (the retired two-kernel form), 2^14 words keyed on the whole k-mer code, four bits per code
     std::vector<uint32_t> bloomr;
     // middle tier (k = 15, too many index k-mers for the forms above; common.h MID_*): level 0 keyed on CANONICAL 12-mers (its own
     // array `mid0`, 2^15 words, `mid0_bits` = 3 or 1 bits per 12-mer), the exact bitmap of those canonical 12-mers, and the

@@ -82,15 +82,6 @@ struct SketchArgs {
     uint32_t *tile_count, *tile_hits, *tile_nmin;
     const uint32_t* prg_min_path_len; // for the size threshold stored in the records
     const uint32_t* prg_thr;          // per PRG: floor(shortest k-mer path * fraction) (sketch_wave_kernel)
-    // in-kernel clustering of the reads that lie inside one tile (sketch_wave_kernel stage C1): 0 off, 1 on, -1 undo
-    int fuse;
-    int max_diff;
-    uint32_t* covg;      // the batch's accumulators (stage C1 adds to them directly)
-    uint32_t* prg_reads;
-    uint32_t* tile_fast; // per slice: hits kept << 16 | clusters kept by stage C1
-    unsigned long long* n_clusters_kept;
-    unsigned long long* n_hits_kept;
-    unsigned long long* dbg; // 8 words, DRPRG_WAVE_DEBUG only: why stage C1 left entries behind
     double fraction;
     uint32_t min_cluster_size;
 };
@@ -148,7 +139,7 @@ struct BloomTables {
     uint32_t bloom_wbits;
     const uint32_t* bloom0;
     uint32_t bloom0_wbits;
-    const uint32_t* bloomr; // second stage of the level-0 form (2^BLOOMR_WBITS words)
+    const uint32_t* bloomr; // FlatIndex::bloomr (2^BLOOMR_WBITS words): the second stage of the retired two-kernel level-0 form; no kernel reads it
     const uint32_t* bloom0f; // level 0 and the second-stage bits in one array (the form with the second stage inside the streaming kernel)
     // middle tier (FlatIndex::mid0 / mid_bitmap / midc; nullptr: absent)
     const uint32_t* mid0 = nullptr;
@@ -165,8 +156,6 @@ struct BloomTables {
 // was too small.  The hits are written ordered by (read, position); a.n_hits receives their number.
 struct FilterBuffers {
     uint64_t* raw_pos;
-    uint4* raw_grp; // raw_capacity entries: level-0 survivors (groups of four positions) on their way to refine_kernel; nullptr unless group_records_requested()
-    uint64_t* cand_gp; // raw_capacity entries: the dense, ordered list of candidate positions (cand_gather_kernel); nullptr unless gathered_list_requested()
     uint64_t* cand_info;
     uint32_t* cand_pos1;
     uint4* cand_rec; // raw_capacity entries
@@ -207,14 +196,13 @@ struct FilterWork {
     uint32_t bloom_wbits;
     const uint32_t* bloom0;  // level 0 (nullptr / 0: absent)
     uint32_t bloom0_wbits;
-    const uint32_t* bloomr;  // second stage of the level-0 form
     const uint32_t* mid_bitmap; // middle tier: exact bitmap of the canonical index 12-mers (2^24 bits, global memory)
     const uint32_t* midc;       // middle tier: split-block Bloom filter of the index k-mer codes (2^midc_wbits blocks of 16 bytes, global memory)
     uint32_t midc_wbits;
     unsigned long long* stat;   // DRPRG_FT_STATS=1 (middle tier): groups tested, past level 0, past the bitmap, candidate positions
     uint32_t read_begin, read_end; // this launch sequence maps reads [read_begin, read_end) of the batch: the filter kernel
                              // streams the wave tiles (FT_WPOS positions each) that cover their bases, candidates
-                             // outside [offsets[read_begin], offsets[read_end]) are dropped by verify_count_kernel
+                             // outside [offsets[read_begin], offsets[read_end]) are dropped by verify_scan_kernel
     uint32_t n_slices;       // slices of the candidate buffers (= chunks of the filter kernel's schedule: its workgroups x sched.per_wg)
     // Where a slice lives (round 6: the chunks are not of one size, so neither are their slices): workgroup b's slices share slice_budget
     // entries from b * slice_budget; chunk k of it, tiles [first, end) of the workgroup's range [lo, ..), starts (first - lo) * slice_cpt +
@@ -226,36 +214,28 @@ struct FilterWork {
     uint32_t slice_extra, slice_extra_from;
     uint64_t* raw_pos;       // global base position of a candidate k-mer, ascending per slice
     uint32_t* slice_count;   // [n_slices], clamped to the slice's room (more: overflow bit 2, the host runs the batch again)
-    uint32_t* slice_base;    // [n_slices]: first entry of the slice in raw_pos (/ raw_grp)
+    uint32_t* slice_base;    // [n_slices]: first entry of the slice in raw_pos
     uint32_t* slice_cap;     // [n_slices]: its room
     uint32_t* super_count;   // [MAX_SLICES], zero before the launch (counters_home_kernel clears it behind every sequence): the candidates of
                              // slices 8 s .. 8 s + 7 (what verify_scan_kernel scans)
     FilterSched sched;       // sketch_filter_kernel's chunk schedule
-    uint4* raw_grp;          // level-0 form only, the slices' geometry: {position of a surviving group of four k-mers (lo, hi),
-                             // its 16 bases, the 2 after them}, ascending per slice; refine_kernel turns them into raw_pos
-    uint32_t* grp_count;     // [n_slices], clamped like slice_count
-    uint32_t* cand_prefix;   // [n_slices + 1]: exclusive scan of the clamped counts
-    const uint32_t* cand_total; // the number of candidates (filtered sequence: &cand_prefix[n_slices])
-    uint64_t* cand_gp;       // [candidates]: global base position of the candidate k-mer, ascending (the slices gathered; nothing writes
-                             // it after cand_gather_kernel: read_verify_kernel's workgroups read their neighbours' entries)
+    uint32_t* cand_count;    // one word: verify_scan_kernel's workgroup 0 leaves the number of candidates here (the filtered sequence's
+                             // writable alias of *cand_total; the direct sequence aims cand_total at its tile prefix instead)
+    const uint32_t* cand_total; // the number of candidates (filtered sequence: cand_count)
     uint64_t* cand_info;     // [candidates]: slot << 32 | strand << 31 | read
     uint32_t* cand_pos1;     // [candidates]: read position + 1 of a minimizer, 0 = not a minimizer
     uint4* cand_rec;         // [candidates]: what read_cluster_kernel needs of a minimizer: first index record, number of
                              // records, group << 16 | size threshold, coverage index of the first record (0,0,.. = not a minimizer)
-    uint32_t ex_grid;        // workgroups of verify_count_kernel / expand_kernel
-    uint32_t verify_grid;    // workgroups of the verification kernel of this batch (verify_count_kernel: ex_grid; read_verify_kernel: its
-                             // persistent grid): as many words of wg_hits / wg_nmin / wg_maxlen hold its totals
+    uint32_t ex_grid;        // workgroups of recount_kernel / expand_kernel
+    uint32_t verify_grid;    // workgroups of verify_scan_kernel: as many words of wg_hits / wg_nmin / wg_maxlen hold its totals
     uint32_t *wg_hits, *wg_nmin, *wg_maxlen, *wg_base; // [ex_grid]
     unsigned long long* max_len; // longest read that holds a minimizer hit (this batch)
     unsigned long long* class_clock; // FilterBuffers::class_clock (may be null)
     uint32_t wave_share[4];  // sketch_filter_kernel: tiles of the waves 4c .. 4c + 3 of a workgroup, in 1/256 of an even share (sum 1024); see its launch
-    uint32_t verify_interleave; // verify_scan_kernel: rounds of 64 candidates dealt out over the workgroups instead of one stretch of the list each
     uint32_t debug;          // ablation switches for profiling (DRPRG_FT_DEBUG): 1 = skip the Bloom test, 8 = every read through the
-                             // generic pipeline, 16 / 32 = verify_count_kernel without its window scan / table probe and
+                             // generic pipeline, 16 / 32 = verify_scan_kernel without its window scan / table probe and
                              // everything after it (wrong results: timing only, tools/dbg16.sh)
 };
-constexpr uint32_t RC_WAVE_MAX_WG = 1024; // workgroups of read_cluster_wave_kernel at most
-constexpr uint32_t RC_CHUNK_OWN = 1536; // candidates a chunk of read_cluster_kernel owns (read_cluster.hip RC_OWN)
 constexpr uint32_t READ_NONE = 0x7FFFFFFFu; // "read" of a candidate that lies past the last whole k-mer of the buffer
 
 // per-read clustering straight from the candidate list (read_cluster_kernel)
@@ -278,17 +258,8 @@ struct ReadClusterArgs {
     uint32_t n_slices, mark_epoch;
     const uint32_t* block_first;  // [total / 64 + 1]: the slice that holds entry 64 m of the ordered list (tile_totals_kernel writes it into the
                                   // -- until a dense list is gathered -- unused fw.cand_info)
-    // the wave form (read_cluster_wave.hip) runs first and counts in *n_unfit the reads it leaves untouched (long reads, minimizers with many
-    // index records); read_cluster_kernel then runs as a SECOND PASS over what is left: second_pass != 0 makes it return at once when
-    // *n_unfit == 0 and skip the candidates that are handled already
-    unsigned long long* n_unfit;
-    int second_pass;
-    uint32_t* wg_partials; // [RC_WAVE_MAX_WG][n_prgs + 4]: per-workgroup histogram and counters of the wave form (summed by its last workgroup)
-    uint32_t* wg_done;     // zero before the launch: workgroups of the wave form that have finished
-    uint32_t* chunk_flags; // [candidate capacity / RC_CHUNK_OWN + 2], zero before the launch: the wave form sets word c when it leaves a read whose first
-                           // candidate lies in read_cluster_kernel's chunk c; the second pass takes only those chunks
     // the batch totals of the candidate stage (hits, minimizers, longest read with a hit) summed by workgroup 0 of read_cluster_kernel
-    // from verify_count_kernel's per-workgroup words instead of by a kernel of their own (hit_scan_kernel: 6 us of launch + one round
+    // from verify_scan_kernel's per-workgroup words instead of by a kernel of their own (hit_scan_kernel: 6 us of launch + one round
     // trip; it still runs when the hits are counted again for the generic pipeline, which also needs its prefix sums)
     const uint32_t *wg_hits, *wg_nmin, *wg_maxlen;
     uint32_t n_wg;                 // 0: the totals are somebody else's business
@@ -297,15 +268,11 @@ struct ReadClusterArgs {
     unsigned long long* phase_clock; // DRPRG_RC_DEBUG=1: 12 counters, clock cycles thread 0 of every workgroup spent per phase (else null)
     uint32_t minpath_in_lds;         // set by launch_read_cluster: the dynamic LDS holds [n_prgs] u16 shortest paths behind the histogram
 };
-// DRPRG_RC_FORM=wave (read at every call): launch_read_cluster runs the wave form first; its flag words must be zero before the launch
-bool read_cluster_wave_form_requested();
 // from[0 .. n) -> to[0 .. n) (the device address of pinned host memory), then from[0 .. n) = 0; n <= 64.  zero != nullptr: zero[0 .. n_zero)
 // = 0 as well (n_zero a multiple of 4, zero 16-byte aligned: the superblock counts of the filtered sequence)
 hipError_t launch_counters_home(unsigned long long* from, unsigned long long* to, uint32_t n, hipStream_t stream, uint32_t* zero = nullptr, uint32_t n_zero = 0);
 uint32_t* filter_super_counts(uint32_t* small); // the superblock counts inside a FilterBuffers::small block ...
 uint32_t filter_super_words();                  // ... and how many words they are
-bool group_records_requested();  // ... will want FilterBuffers::raw_grp (DRPRG_FILTER_FORM=refine, experimental library)
-bool gathered_list_requested(); // this launch of the filtered sequence will want FilterBuffers::cand_gp (DRPRG_VERIFY_FORM=gather / read)
 size_t filter_small_words();
 // the fields of fw that the consumers of a dense candidate list use (candidates.hip, read_cluster.hip)
 void init_candidate_work(FilterWork& fw, const FilterBuffers& b, int n_cus);
@@ -320,13 +287,12 @@ hipError_t launch_sketch_filter(const SketchArgs& a, uint32_t read_begin, uint32
 hipError_t launch_filter_recount(const SketchArgs& a, const FilterWork& fw, hipStream_t stream);
 // ... and their hits are written to a.hit_key / a.hit_val ordered by (read, position)
 hipError_t launch_filter_expand(const SketchArgs& a, const FilterWork& fw, hipStream_t stream);
-// Candidate form of the direct sequence: launch_sketch_probe with a.tile_cap != 0, then the tile slices -> one dense
-// ordered candidate list (fw.cand_info / cand_pos1 / cand_rec, *fw.cand_total) -> read_cluster_kernel.  tile_prefix:
-// n_tiles + 1 words; temp: scan_temp_bytes(n_tiles + 1) bytes.  a.n_hits receives the hits of the batch; overflow bit 2:
-// a tile slice or the dense list (dense_capacity entries) was too small (nothing was counted then).
+// Candidate form of the direct sequence: launch_sketch_probe / launch_sketch_wave with a.tile_cap != 0, then read_cluster_kernel
+// straight from the tile slices (*fw.cand_total: their total); it marks the candidates it handled with slices_mark (!= 0) in the dense
+// fw.cand_pos1.  tile_prefix: n_tiles + 1 words; temp: scan_temp_bytes(n_tiles + 1) bytes.  a.n_hits receives the hits of the batch;
+// overflow bit 2: a tile slice was too small, or the total exceeds dense_capacity (nothing was counted then).
 hipError_t launch_direct_candidates(const SketchArgs& a, bool wide_hash, uint32_t* tile_prefix, void* temp, size_t temp_bytes,
-    uint64_t dense_capacity, const ReadClusterArgs& rc, int n_cus, FilterWork& fw, hipStream_t stream, KernelTimer timer = {},
-    uint32_t slices_mark = 0); // slices_mark != 0: no gathered list, read_cluster_kernel reads the slices and marks handled candidates with it
+    uint64_t dense_capacity, const ReadClusterArgs& rc, int n_cus, FilterWork& fw, hipStream_t stream, KernelTimer timer, uint32_t slices_mark);
 // the gathered list after such a batch, for the reads that were left over (handled candidates get position 0)
 hipError_t launch_tile_gather_marked(const SketchArgs& a, const FilterWork& fw, const uint32_t* tile_prefix, uint32_t n_tiles, uint64_t dense_capacity,
     uint32_t mark, hipStream_t stream);

@@ -34,7 +34,7 @@ template <typename T> static void dfree(T*& p)
 }
 
 // counter slots
-enum { C_HITS = 0, C_MINIMIZERS = 1, C_CLUSTERS_KEPT = 2, C_HITS_KEPT = 3, C_OVERFLOW = 4, C_MAXLEN = 5, C_UNSORTED = 6, C_COMPLEX = 7, C_CHUNK = 8, C_N = 16 };
+enum { C_HITS = 0, C_MINIMIZERS = 1, C_CLUSTERS_KEPT = 2, C_HITS_KEPT = 3, C_OVERFLOW = 4, C_MAXLEN = 5, C_UNSORTED = 6, C_COMPLEX = 7, C_N = 8 };
 // reads up to this length get their hits reordered per read (read_sort_kernel); longer ones take the radix sort
 constexpr uint64_t READ_SORT_MAX_LEN = 512;
 // candidate buffers of the filtered sequence: one entry per this many bases of the batch.  One per 64 is laid out by the tile; the quarter
@@ -157,17 +157,6 @@ Mapper::Mapper(const FlatIndex& idx, const MapParams& p, int device) : device_(d
     HIPCHK(hipDeviceGetAttribute(&n_cus_, hipDeviceAttributeMultiprocessorCount, device_));
     HIPCHK(hipStreamSynchronize(nullptr)); // every table is on the device before a kernel of a non-blocking stream can ask for it
     set_params(p); // again: the kernel choice depends on the filter being available
-#ifdef DRPRG_EXPERIMENTAL // (make EXPERIMENTAL=1; the default build has no such instantiation of sketch_wave_kernel)
-    {
-        const char* f = std::getenv("DRPRG_WAVE_FUSE");
-        const char* d = std::getenv("DRPRG_FT_DEBUG");
-        // opt-in (DRPRG_WAVE_FUSE=1; 2 = single-record minimizers only): measured on the 500-locus workload the in-kernel
-        // clustering takes 84 % of the candidates away from gather + read_cluster_kernel (2.7 -> 2.1 ms) but costs
-        // sketch_wave_kernel 1.65 ms (3.84 -> 5.50 ms): 7.6 ms per 10 M reads against 6.9 ms without it
-        fuse_in_kernel_ = f && std::atoi(f) != 0 && !(d && (std::atoi(d) & 8));
-        fuse_mode_ = f && std::atoi(f) == 2 ? 2 : 1;
-    }
-#endif
     if (const char* e = std::getenv("DRPRG_HIP_LANES")) max_lanes_ = std::min(4, std::max(1, std::atoi(e)));
     if (const char* e = std::getenv("DRPRG_HIP_LANES_MIN_BASES")) lanes_min_bases_ = std::strtoull(e, nullptr, 10); // (tests: 0)
     if (const char* e = std::getenv("DRPRG_HIP_MIN_CAPACITY")) // (tests: small batches at the production ratio, or below it to force regrows)
@@ -224,7 +213,7 @@ Mapper::~Mapper()
 
 // Zeroes device memory and returns when it IS zero.  hipMemset on device memory runs on the null stream and may return before it
 // has run; this class's streams are non-blocking, so nothing they do waits for the null stream -- a freshly allocated cand_pos1
-// was zeroed AFTER verify_count_kernel had written the first batch into it (cold start, several contexts busy on one device:
+// was zeroed AFTER the verification kernel had written the first batch into it (cold start, several contexts busy on one device:
 // one run in ten lost 5 % of its clusters; tools/stress_multi.py).
 void Mapper::zero_now(void* p, int value, size_t bytes)
 {
@@ -343,7 +332,7 @@ void Mapper::ensure_workspace(uint64_t cap)
 
 void Mapper::free_lane(Lane& lane)
 {
-    dfree(lane.raw_pos); dfree(lane.raw_grp); dfree(lane.cand_gp); dfree(lane.cand_info); dfree(lane.cand_pos1); dfree(lane.cand_rec); dfree(lane.small); dfree(lane.rc_flags); dfree(lane.rc_partials);
+    dfree(lane.raw_pos); dfree(lane.cand_info); dfree(lane.cand_pos1); dfree(lane.cand_rec); dfree(lane.small);
     dfree(lane.d_scratch);
     if (lane.h_scratch) (void)hipHostFree(lane.h_scratch);
     lane.h_scratch = nullptr;
@@ -358,11 +347,9 @@ void Mapper::grow_lane(Lane& lane, uint64_t cap)
 {
     if (cap <= lane.raw_capacity) return;
     if (cap >= (1ull << 31)) throw Error(DRPRG_EOVERFLOW, "more than 2^31 candidate k-mers in one read range; map smaller batches");
-    dfree(lane.raw_pos); dfree(lane.raw_grp); dfree(lane.cand_gp); dfree(lane.cand_info); dfree(lane.cand_pos1); dfree(lane.cand_rec); dfree(lane.rc_flags);
+    dfree(lane.raw_pos); dfree(lane.cand_info); dfree(lane.cand_pos1); dfree(lane.cand_rec);
     lane.raw_capacity = cap;
-    dmalloc(lane.raw_pos, cap); dmalloc(lane.cand_info, cap); dmalloc(lane.cand_pos1, cap); dmalloc(lane.cand_rec, cap); // (cand_gp: launch_lane, on demand)
-    dmalloc(lane.rc_flags, (size_t)(cap / dev::RC_CHUNK_OWN + 3));
-    if (!lane.rc_partials) dmalloc(lane.rc_partials, (size_t)dev::RC_WAVE_MAX_WG * ((size_t)n_prgs_ + 4));
+    dmalloc(lane.raw_pos, cap); dmalloc(lane.cand_info, cap); dmalloc(lane.cand_pos1, cap); dmalloc(lane.cand_rec, cap);
     // the slices form of the direct sequence uses cand_pos1 as an array of "handled" marks (mark = a batch's epoch): fresh device
     // memory may hold anything, including a value some later epoch of this or an earlier Mapper takes
     zero_now(lane.cand_pos1, 0, cap * sizeof(uint32_t));
@@ -396,14 +383,11 @@ void Mapper::launch_lane(Lane& lane, hipStream_t stream, const uint8_t* d_bases,
 {
     if (!lane.scratch_zero) HIPCHK(hipMemsetAsync(lane.d_scratch, 0, L_N * sizeof(unsigned long long), stream));
     lane.scratch_zero = false;
-    if (!lane.cand_gp && dev::gathered_list_requested()) dmalloc(lane.cand_gp, lane.raw_capacity); // (grow_lane frees it with the rest)
-    if (!lane.raw_grp && bloom0_wbits_ && dev::group_records_requested()) dmalloc(lane.raw_grp, lane.raw_capacity);
     dev::SketchArgs a = sketch_args(d_bases, d_offsets, n_reads, n_bases, pk);
     a.n_hits = &lane.d_scratch[L_HITS];
     a.n_minimizers = &lane.d_scratch[L_MINIMIZERS];
     a.overflow = reinterpret_cast<uint32_t*>(&lane.d_scratch[L_OVERFLOW]);
-    dev::FilterBuffers fb { lane.raw_pos, lane.raw_grp, lane.cand_gp, lane.cand_info, lane.cand_pos1, lane.cand_rec, lane.raw_capacity, lane.small,
-        &lane.d_scratch[L_MAXLEN] };
+    dev::FilterBuffers fb { lane.raw_pos, lane.cand_info, lane.cand_pos1, lane.cand_rec, lane.raw_capacity, lane.small, &lane.d_scratch[L_MAXLEN] };
     fb.stat = d_ft_stat_;
     {
         static const bool adapt = [] { const char* e = std::getenv("DRPRG_FT_ADAPT"); return !e || std::atoi(e) != 0; }();
@@ -436,12 +420,6 @@ void Mapper::launch_lane(Lane& lane, hipStream_t stream, const uint8_t* d_bases,
     rc.n_clusters_kept = &d_counters_[C_CLUSTERS_KEPT];
     rc.n_hits_kept = &d_counters_[C_HITS_KEPT];
     rc.n_complex = &lane.d_scratch[L_COMPLEX];
-    rc.n_unfit = &lane.d_scratch[L_UNFIT];
-    rc.chunk_flags = lane.rc_flags;
-    rc.wg_partials = lane.rc_partials;
-    rc.wg_done = lane.rc_flags + (lane.raw_capacity / dev::RC_CHUNK_OWN + 2); // (one word behind the flags, cleared with them)
-    if (dev::read_cluster_wave_form_requested()) // (only the opt-in wave form reads them)
-        HIPCHK(hipMemsetAsync(lane.rc_flags, 0, (lane.raw_capacity / dev::RC_CHUNK_OWN + 3) * sizeof(uint32_t), stream));
     rc.chunk_counter = reinterpret_cast<uint32_t*>(&lane.d_scratch[L_CHUNK]);
     dev::KernelTimer timer;
     if (timing_) { // events bracket the dominant kernel only
@@ -449,16 +427,9 @@ void Mapper::launch_lane(Lane& lane, hipStream_t stream, const uint8_t* d_bases,
         timer.end = lane.t1;
     }
     HIPCHK(dev::launch_sketch_filter(a, lane.r0, lane.r1, bt, n_cus_, fb, rc, lane.fw, stream, timer));
-    // the counters to the pinned mirror and zero again behind it: one small kernel (DRPRG_HIP_COUNTERS_HOME=0: a copy and a memset, rounds 1-4)
-    static const bool one_launch = [] { const char* e = std::getenv("DRPRG_HIP_COUNTERS_HOME"); return !e || std::atoi(e) != 0; }();
-    if (one_launch) {
-        if (!lane.h_scratch_dev) HIPCHK(hipHostGetDevicePointer((void**)&lane.h_scratch_dev, lane.h_scratch, 0));
-        HIPCHK(dev::launch_counters_home(lane.d_scratch, lane.h_scratch_dev, L_N, stream, dev::filter_super_counts(lane.small), dev::filter_super_words()));
-    } else {
-        HIPCHK(hipMemcpyAsync(lane.h_scratch, lane.d_scratch, L_N * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipMemsetAsync(lane.d_scratch, 0, L_N * sizeof(unsigned long long), stream));
-        HIPCHK(hipMemsetAsync(dev::filter_super_counts(lane.small), 0, dev::filter_super_words() * sizeof(uint32_t), stream));
-    }
+    // the counters to the pinned mirror and zero again behind it: one small kernel (rounds 1-4: a copy and two memsets)
+    if (!lane.h_scratch_dev) HIPCHK(hipHostGetDevicePointer((void**)&lane.h_scratch_dev, lane.h_scratch, 0));
+    HIPCHK(dev::launch_counters_home(lane.d_scratch, lane.h_scratch_dev, L_N, stream, dev::filter_super_counts(lane.small), dev::filter_super_words()));
     lane.scratch_zero = true;
 }
 
@@ -603,7 +574,7 @@ void Mapper::leftovers(Lane& lane, const uint8_t* d_bases, const uint64_t* d_off
 
 void Mapper::free_tile_set(TileSet& t)
 {
-    dfree(t.d_tile_info); dfree(t.d_tile_pos1); dfree(t.d_tile_count); dfree(t.d_tile_hits); dfree(t.d_tile_nmin); dfree(t.d_tile_prefix); dfree(t.d_tile_fast);
+    dfree(t.d_tile_info); dfree(t.d_tile_pos1); dfree(t.d_tile_count); dfree(t.d_tile_hits); dfree(t.d_tile_nmin); dfree(t.d_tile_prefix);
     dfree(t.d_nbits);
     t.nbits_cap = 0;
     dfree(t.d_tile_rec); dfree(t.d_tile_first);
@@ -617,21 +588,21 @@ void Mapper::free_tile_set(TileSet& t)
 void Mapper::ensure_tile_workspace(TileSet& t, uint32_t n_tiles, uint32_t tile_cap)
 {
     if (n_tiles <= t.ws_tiles && tile_cap <= t.ws_cap) return;
-    dfree(t.d_tile_info); dfree(t.d_tile_pos1); dfree(t.d_tile_count); dfree(t.d_tile_hits); dfree(t.d_tile_nmin); dfree(t.d_tile_prefix); dfree(t.d_tile_fast); dfree(t.d_tile_rec);
+    dfree(t.d_tile_info); dfree(t.d_tile_pos1); dfree(t.d_tile_count); dfree(t.d_tile_hits); dfree(t.d_tile_nmin); dfree(t.d_tile_prefix); dfree(t.d_tile_rec);
     if (t.d_tile_temp) (void)hipFree(t.d_tile_temp);
     t.d_tile_temp = nullptr;
     t.ws_tiles = std::max(t.ws_tiles, n_tiles + n_tiles / 8 + 32);
     t.ws_cap = std::max(t.ws_cap, tile_cap);
     const size_t n = (size_t)t.ws_tiles * t.ws_cap;
     dmalloc(t.d_tile_info, n); dmalloc(t.d_tile_pos1, n); dmalloc(t.d_tile_rec, n);
-    dmalloc(t.d_tile_count, (size_t)t.ws_tiles + 1); dmalloc(t.d_tile_hits, (size_t)t.ws_tiles + 1); dmalloc(t.d_tile_nmin, (size_t)t.ws_tiles + 1); dmalloc(t.d_tile_prefix, (size_t)t.ws_tiles + 1); dmalloc(t.d_tile_fast, (size_t)t.ws_tiles + 1);
+    dmalloc(t.d_tile_count, (size_t)t.ws_tiles + 1); dmalloc(t.d_tile_hits, (size_t)t.ws_tiles + 1); dmalloc(t.d_tile_nmin, (size_t)t.ws_tiles + 1); dmalloc(t.d_tile_prefix, (size_t)t.ws_tiles + 1);
     t.tile_temp_bytes = dev::scan_temp_bytes(t.ws_tiles + 1);
     HIPCHK(hipMalloc(&t.d_tile_temp, t.tile_temp_bytes ? t.tile_temp_bytes : 1));
 }
 
 // Direct sequence, candidate form: every k-mer hashed (any k, any w, any index size); each tile leaves its index minimizers
-// as candidate records in position order, a scan + gather makes the dense ordered list and read_cluster_kernel takes it from
-// there -- no hit list, no radix sort, no cluster kernels for the reads that fit it.
+// as candidate records in position order, a scan orders the slices and read_cluster_kernel takes the candidates from them -- no hit
+// list, no radix sort, no cluster kernels for the reads that fit it.
 // One attempt, asynchronous on `stream`: the launches, the lane's counters to their pinned mirror, the counters cleared behind the copy.
 void Mapper::direct_launch(int set, const uint8_t* d_bases, const uint64_t* d_offsets, uint32_t n_reads, uint64_t n_bases, uint32_t* covg,
     uint32_t* prg_reads, hipStream_t stream, bool timed_by_set_events, const PackedInfo* pk)
@@ -649,24 +620,17 @@ void Mapper::direct_launch(int set, const uint8_t* d_bases, const uint64_t* d_of
     Lane& lane = lanes_[(size_t)set];
     grow_lane(lane, std::min<uint64_t>(std::max<uint64_t>(min_capacity_, n_bases / 16), (1ull << 31) - 1));
     // read_cluster_kernel takes the candidates straight from the tile slices (no gathered list unless reads are left over); what it
-    // handled is marked in the dense cand_pos1 array with a value no other batch used (DRPRG_RC_SLICES=0: gather first, as before)
-    static const bool from_slices = [] {
-        const char* e = std::getenv("DRPRG_RC_SLICES");
-        return !(e && std::atoi(e) == 0);
-    }();
-    uint32_t mark = 0;
-    if (from_slices && !fuse_in_kernel_) {
-        // (never a value a position + 1 can have, never 0; one sequence of epochs per process, so that no two Mappers that follow
-        // each other in recycled device memory ever use the same mark)
-        static std::atomic<uint32_t> process_epoch { 0x80000000u };
-        slices_epoch_ = process_epoch.fetch_add(1) + 1;
-        if (slices_epoch_ < 0x80000000u) { // wrapped after 2^31 batches: marks of old batches may still be around, clear them
-            HIPCHK(hipMemsetAsync(lane.cand_pos1, 0, lane.raw_capacity * sizeof(uint32_t), stream));
-            process_epoch.store(0x80000001u);
-            slices_epoch_ = 0x80000001u;
-        }
-        mark = slices_epoch_;
+    // handled is marked in the dense cand_pos1 array with a value no other batch used (the gather-first sequence of rounds 1-3 lost to
+    // this one: DESIGN.md section 6).  The mark is never a value a position + 1 can have, never 0; one sequence of epochs per process,
+    // so that no two Mappers that follow each other in recycled device memory ever use the same mark.
+    static std::atomic<uint32_t> process_epoch { 0x80000000u };
+    slices_epoch_ = process_epoch.fetch_add(1) + 1;
+    if (slices_epoch_ < 0x80000000u) { // wrapped after 2^31 batches: marks of old batches may still be around, clear them
+        HIPCHK(hipMemsetAsync(lane.cand_pos1, 0, lane.raw_capacity * sizeof(uint32_t), stream));
+        process_epoch.store(0x80000001u);
+        slices_epoch_ = 0x80000001u;
     }
+    const uint32_t mark = slices_epoch_;
     ensure_tile_workspace(t, n_tiles, t.slice_cap);
     if (!lane.scratch_zero) HIPCHK(hipMemsetAsync(lane.d_scratch, 0, L_N * sizeof(unsigned long long), stream));
     lane.scratch_zero = false;
@@ -699,22 +663,11 @@ void Mapper::direct_launch(int set, const uint8_t* d_bases, const uint64_t* d_of
     a.tile_count = t.d_tile_count;
     a.tile_hits = t.d_tile_hits;
     a.tile_nmin = t.d_tile_nmin;
-    a.tile_fast = t.d_tile_fast;
     a.prg_min_path_len = d_min_path_len_;
     a.prg_thr = d_prg_thr_;
-    // sketch_wave_kernel can cluster the reads that lie inside one tile itself and add their coverage on the spot
-    // (opt-in: DRPRG_WAVE_FUSE=1; never with DRPRG_FT_DEBUG=8, "every read through the generic pipeline")
-    a.fuse = fuse_in_kernel_ && dev::direct_uses_wave_form(params_.k, params_.w, wide_hash_) ? fuse_mode_ : 0;
-    a.max_diff = params_.max_diff;
-    a.covg = covg;
-    a.prg_reads = prg_reads;
-    a.n_clusters_kept = &d_counters_[C_CLUSTERS_KEPT];
-    a.n_hits_kept = &d_counters_[C_HITS_KEPT];
-    a.dbg = std::getenv("DRPRG_WAVE_DEBUG") ? &d_counters_[C_CHUNK] : nullptr; // (words C_CHUNK.. are unused by this sequence)
     a.fraction = params_.cluster_fraction();
     a.min_cluster_size = params_.min_cluster_size;
-    dev::FilterBuffers fb { lane.raw_pos, lane.raw_grp, lane.cand_gp, lane.cand_info, lane.cand_pos1, lane.cand_rec, lane.raw_capacity, lane.small,
-        &lane.d_scratch[L_MAXLEN] };
+    dev::FilterBuffers fb { lane.raw_pos, lane.cand_info, lane.cand_pos1, lane.cand_rec, lane.raw_capacity, lane.small, &lane.d_scratch[L_MAXLEN] };
     dev::ReadClusterArgs rc {};
     rc.prg_min_path_len = d_min_path_len_;
     rc.fraction = params_.cluster_fraction();
@@ -726,12 +679,6 @@ void Mapper::direct_launch(int set, const uint8_t* d_bases, const uint64_t* d_of
     rc.n_clusters_kept = &d_counters_[C_CLUSTERS_KEPT];
     rc.n_hits_kept = &d_counters_[C_HITS_KEPT];
     rc.n_complex = &lane.d_scratch[L_COMPLEX];
-    rc.n_unfit = &lane.d_scratch[L_UNFIT];
-    rc.chunk_flags = lane.rc_flags;
-    rc.wg_partials = lane.rc_partials;
-    rc.wg_done = lane.rc_flags + (lane.raw_capacity / dev::RC_CHUNK_OWN + 2); // (one word behind the flags, cleared with them)
-    if (dev::read_cluster_wave_form_requested()) // (only the opt-in wave form reads them)
-        HIPCHK(hipMemsetAsync(lane.rc_flags, 0, (lane.raw_capacity / dev::RC_CHUNK_OWN + 3) * sizeof(uint32_t), stream));
     rc.chunk_counter = reinterpret_cast<uint32_t*>(&lane.d_scratch[L_CHUNK]);
     lane.fw = dev::FilterWork {};
     lane.fw.read_begin = 0;
@@ -761,8 +708,6 @@ void Mapper::direct_launch(int set, const uint8_t* d_bases, const uint64_t* d_of
 
 // The read-back of such an attempt has arrived.  false: a tile slice or the dense list was too small -- nothing was counted except the
 // minimizers, and those only in this attempt's scratch block --, the buffers have been grown and the caller runs the batch again.
-// What sketch_wave_kernel already added to the coverage vector for the reads it clusters itself is taken back first: the same launch
-// with fuse = -1 repeats exactly those additions as subtractions (same input, same slice capacity, so the same reads take that path).
 // true: totals taken, reads left to the generic pipeline queued on `stream`.
 bool Mapper::direct_finish(int set, const uint8_t* d_bases, const uint64_t* d_offsets, uint32_t n_reads, uint64_t n_bases, uint32_t* covg,
     uint32_t* prg_reads, hipStream_t stream, int attempt, const PackedInfo* pk)
@@ -774,12 +719,6 @@ bool Mapper::direct_finish(int set, const uint8_t* d_bases, const uint64_t* d_of
     if (ovf & 2u) throw Error(DRPRG_EOVERFLOW, "a read is longer than 2^" + std::to_string(dev::HIT_POS_BITS) + " bases");
     if (ovf & 4u) {
         if (attempt > 6) throw Error(DRPRG_EOVERFLOW, "candidate buffer overflow after regrow");
-        if (t.a_done.fuse > 0) {
-            dev::SketchArgs undo = t.a_done;
-            undo.fuse = -t.a_done.fuse;
-            HIPCHK(dev::launch_sketch_wave(undo, stream));
-            HIPCHK(hipStreamSynchronize(stream));
-        }
         HIPCHK(hipStreamSynchronize(stream)); // (the buffers are about to be freed)
         ++reruns_direct_;
         t.slice_cap = std::min<uint32_t>(t.slice_cap * 2, 4096);
@@ -789,7 +728,7 @@ bool Mapper::direct_finish(int set, const uint8_t* d_bases, const uint64_t* d_of
     tot_minimizers_ += lane.h_scratch[L_MINIMIZERS];
     tot_hits_ += lane.h_scratch[L_HITS];
     tot_leftover_ += lane.h_scratch[L_COMPLEX];
-    if (t.mark && lane.h_scratch[L_COMPLEX]) // reads were left over: the generic pipeline wants the gathered list after all
+    if (lane.h_scratch[L_COMPLEX]) // reads were left over: the generic pipeline wants the gathered list after all
         HIPCHK(dev::launch_tile_gather_marked(t.a_done, lane.fw, t.d_tile_prefix, t.n_tiles, lane.raw_capacity, t.mark, stream));
     leftovers(lane, d_bases, d_offsets, n_reads, n_bases, covg, prg_reads, stream, pk);
     return true;
@@ -918,7 +857,7 @@ void Mapper::map_device_async_impl(const uint8_t* d_bases, const uint64_t* d_off
 {
     if (n_reads == 0) return;
     const bool deferred_filter = use_filter_ && max_lanes_ == 1;
-    const bool deferred_direct = !use_filter_ && use_direct_cands_ && !fuse_in_kernel_;
+    const bool deferred_direct = !use_filter_ && use_direct_cands_;
     if ((!deferred_filter && !deferred_direct) || n_bases == 0) { // (no deferred form of the other sequences: the batch is complete on return,
         map_device_impl(d_bases, d_offsets, n_reads, n_bases, covg, prg_reads, stream, pk); // including what its tail queued for the leftover reads)
         HIPCHK(hipSetDevice(device_));
@@ -1607,9 +1546,6 @@ MapCounters Mapper::counters()
     HIPCHK(hipStreamSynchronize(stream_));
     unsigned long long c[C_N];
     HIPCHK(hipMemcpy(c, d_counters_, sizeof(c), hipMemcpyDeviceToHost));
-    if (std::getenv("DRPRG_WAVE_DEBUG"))
-        std::fprintf(stderr, "[sketch_wave] entries %llu: several records out of group %llu, other group than the read's first %llu, read not inside the tile %llu, "
-                             "more than 64 entries %llu; entries left to the records path %llu\n", c[C_CHUNK], c[C_CHUNK + 1], c[C_CHUNK + 2], c[C_CHUNK + 3], c[C_CHUNK + 4], c[C_CHUNK + 5]);
     if (d_ft_stat_) {
         unsigned long long st[4];
         HIPCHK(hipMemcpy(st, d_ft_stat_, sizeof(st), hipMemcpyDeviceToHost));

@@ -150,11 +150,9 @@ private:
         hipStream_t stream = nullptr; // lanes >= 1 (lane 0 uses the stream of the call)
         hipEvent_t done = nullptr, t0 = nullptr, t1 = nullptr;
         uint64_t raw_capacity = 0;
-        uint64_t *raw_pos = nullptr, *cand_gp = nullptr, *cand_info = nullptr;
-        uint4 *raw_grp = nullptr, *cand_rec = nullptr;
+        uint64_t *raw_pos = nullptr, *cand_info = nullptr;
+        uint4* cand_rec = nullptr;
         uint32_t *cand_pos1 = nullptr, *small = nullptr;
-        uint32_t* rc_partials = nullptr; // RC_WAVE_MAX_WG x (n_prgs + 4) words: per-workgroup sums of read_cluster_wave_kernel
-        uint32_t* rc_flags = nullptr; // raw_capacity / RC_CHUNK_OWN + 2 words: chunks in which read_cluster_wave_kernel left a read (zeroed per batch)
         unsigned long long* d_scratch = nullptr; // L_N x u64 per-sequence counters (below)
         unsigned long long* h_scratch = nullptr; // pinned mirror
         unsigned long long* h_scratch_dev = nullptr; // its device address
@@ -163,7 +161,7 @@ private:
         dev::FilterWork fw {};
         uint32_t r0 = 0, r1 = 0;                 // read range of the current batch
     };
-    enum { L_HITS = 0, L_OVERFLOW = 1, L_MAXLEN = 2, L_UNSORTED = 3, L_COMPLEX = 4, L_CHUNK = 5, L_MINIMIZERS = 6, L_UNFIT = 7, L_FT_CLOCK = 8 /* five words: FilterBuffers::class_clock */, L_N = 13 };
+    enum { L_HITS = 0, L_OVERFLOW = 1, L_MAXLEN = 2, L_UNSORTED = 3, L_COMPLEX = 4, L_CHUNK = 5, L_MINIMIZERS = 6, L_FT_CLOCK = 7 /* five words: FilterBuffers::class_clock */, L_N = 12 };
     // What makes a device batch a packed one (2-bit words instead of bytes): where its non-ACGT positions are.  Passed along with the batch
     // pointer to everything that touches the batch (nullptr: ASCII) and kept in Pending for the deferred completion -- until round 5 the
     // batch's ADDRESS was looked up in a map, which every free and every recycled address had to keep honest.
@@ -252,8 +250,6 @@ private:
     unsigned long long* d_ft_stat_ = nullptr; // DRPRG_FT_STATS=1: groups tested / past level 0 / past the bitmap, candidate positions
     int n_cus_ = 256;
     bool use_filter_ = false;
-    bool fuse_in_kernel_ = false; // sketch_wave_kernel clusters the reads inside one tile itself (DRPRG_WAVE_FUSE=1)
-    int fuse_mode_ = 1;          // 2: only reads whose minimizers all have one index record (DRPRG_WAVE_FUSE=2)
     bool use_direct_cands_ = false; // direct sketch kernel in its candidate form (read_cluster_kernel instead of sort + cluster kernels)
     // accumulators
     uint32_t* d_covg_ = nullptr;
@@ -289,7 +285,7 @@ private:
     struct TileSet {
         uint32_t slice_cap = 256, ws_tiles = 0, ws_cap = 0, first_cap = 0;
         uint64_t* d_tile_info = nullptr;
-        uint32_t *d_tile_pos1 = nullptr, *d_tile_count = nullptr, *d_tile_hits = nullptr, *d_tile_nmin = nullptr, *d_tile_prefix = nullptr, *d_tile_fast = nullptr;
+        uint32_t *d_tile_pos1 = nullptr, *d_tile_count = nullptr, *d_tile_hits = nullptr, *d_tile_nmin = nullptr, *d_tile_prefix = nullptr;
         uint4* d_tile_rec = nullptr;
         void* d_tile_temp = nullptr;
         size_t tile_temp_bytes = 0;

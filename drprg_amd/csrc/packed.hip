@@ -2,7 +2,7 @@
 // conversions between the packed form and ASCII on the device.
 //
 // The packed form is what crosses PCIe and what stays in HBM (a quarter of the bytes); the kernels of the filtered launch sequence
-// (sketch_filter.hip, candidates.hip verify_count_kernel) read it directly.  The direct sketch kernels (sketch_wave.hip,
+// (sketch_filter.hip, candidates.hip verify_scan_kernel) read it directly.  The direct sketch kernels (sketch_wave.hip,
 // sketch_probe.hip: indexes beyond the filter's reach, 5 ms per 10 M reads and VALU-bound on their hashes) and the anchor scan of
 // `discover` (anchor_scan.hip) keep their ASCII input: a packed batch is expanded once for them, 0.3 ms per 1.5 G bases at the
 // bandwidth of the copy.  HBM-bound: n / 4 bytes read, n bytes written.

@@ -13,7 +13,7 @@ namespace dev {
 // ---------------------------------------------------------------------------------------------
 // per-read clustering straight from the candidate list
 // ---------------------------------------------------------------------------------------------
-// The candidates arrive ordered by (read, position) -- from verify_count_kernel, or from the direct sketch kernel in its
+// The candidates arrive ordered by (read, position) -- from verify_scan_kernel, or from the direct sketch kernel in its
 // candidate form -- so all minimizers of a read sit next to each other, and a short read has a few dozen hits, nearly
 // always in ONE cluster.  read_cluster_kernel therefore never materialises the hit list.  A workgroup stages RC_SLOTS
 // consecutive candidates and their index records (the hits) in LDS.  A position gap > max_diff between two consecutive
@@ -46,7 +46,7 @@ constexpr int RC_SLOTS = RC_THREADS * RC_PER; // staged candidates
 // 128 slots of look-ahead mean 1920 owned candidates per chunk instead of 1536, a fifth fewer chunks -- and a chunk costs ~21 us whatever
 // is in it (round 4).  A read that does not fit its chunk's look-ahead goes through the generic pipeline as before.
 constexpr int RC_HCAP = DRPRG_RC_HCAP;         // staged hits
-constexpr int RC_POOL = 512;                  // reads per chunk that may take the wave path (sketch_wave_kernel clusters the plain reads itself: what is left is rich in these)
+constexpr int RC_POOL = 512;                  // reads per chunk that may take the wave path
 constexpr uint32_t RC_IRREGULAR = 2u, RC_COMPLEX = 1u;
 
 // later (read start << 16 | segment start) pair: the read start decides, then the segment start.  A gap inside a read
@@ -69,7 +69,6 @@ template <bool SLICES, int AHEAD>
 __global__ __launch_bounds__(RC_THREADS, 4 * DRPRG_RC_WG_PER_CU) void read_cluster_kernel(SketchArgs a, FilterWork fw, ReadClusterArgs rc)
 {
     constexpr int RC_AHEAD = AHEAD, RC_OWN = RC_SLOTS - AHEAD;
-    static_assert(RC_PER != 2 || AHEAD != 512 || RC_OWN == (int)RC_CHUNK_OWN, "kernels.h RC_CHUNK_OWN: the chunk numbering the wave form's flags use");
     static_assert(RC_OWN % 64 == 0, "the slices form locates 64 entries from a multiple of 64 per wave");
     (void)RC_AHEAD;
     extern __shared__ uint32_t s_hist[]; // clusters kept per PRG
@@ -133,8 +132,6 @@ __global__ __launch_bounds__(RC_THREADS, 4 * DRPRG_RC_WG_PER_CU) void read_clust
         __syncthreads();
     }
     if (*reinterpret_cast<volatile uint32_t*>(a.overflow) & 4u) return; // a candidate slice overflowed: the host re-runs the batch
-    // second pass behind read_cluster_wave_kernel: only if that kernel left reads untouched (long reads, mostly)
-    if (rc.second_pass && *reinterpret_cast<volatile unsigned long long*>(rc.n_unfit) == 0ull) return;
     const uint32_t total = SLICES ? rc.slice_prefix[rc.n_slices] : *fw.cand_total;
     const uint32_t handled_mark = SLICES ? rc.mark_epoch : 0u; // what a handled candidate's cand_pos1 becomes
     // (the shortest path of every PRG sits behind the histogram when two workgroups per CU still fit with it -- launch_read_cluster decides:
@@ -243,13 +240,10 @@ __global__ __launch_bounds__(RC_THREADS, 4 * DRPRG_RC_WG_PER_CU) void read_clust
             };
 #pragma unroll
             for (int q = 0; q < RC_PER; ++q) {
-                const uint32_t i = (uint32_t)tid + (uint32_t)q * RC_THREADS;
                 const size_t src = some[q] ? locate(q, d_last) : 0; // (a wave past the end reads entry 0 of slice 0 and drops it)
                 st.info[q] = live ? (uint32_t)a.tile_info[src] : 0u;
                 st.pos1[q] = live ? a.tile_pos1[src] : 0u;
                 st.rec[q] = live ? a.tile_rec[src] : make_uint4(0, 0, 0, 0);
-                // (second pass: what the wave form handled carries this batch's mark in the dense array)
-                if (rc.second_pass && live && i < n_in && fw.cand_pos1[b + i] == rc.mark_epoch) st.pos1[q] = 0u;
             }
             // the two neighbours of the staged range (thread 0 alone looks at them)
             st.edge_prev = 0u;
@@ -264,22 +258,11 @@ __global__ __launch_bounds__(RC_THREADS, 4 * DRPRG_RC_WG_PER_CU) void read_clust
         }
         return st;
     };
-    // (second pass: only the chunks in which the wave form left a read)
     // Chunks 0 .. gridDim.x - 1 belong to the workgroups by number, the counter hands out the ones after them: every workgroup's first
     // ticket used to be a returning atomic on one address, 512 of them at the same moment -- microseconds in which nothing else of the
     // workgroup could start (round 5; the fixed cost of a launch went from 21 to 17 us)
-    auto take_ticket = [&]() -> uint32_t {
-        uint32_t t;
-        do t = atomicAdd(rc.chunk_counter, 1u) + gridDim.x;
-        while (rc.second_pass && (uint64_t)t * RC_OWN < total && !rc.chunk_flags[t]);
-        return t;
-    };
+    auto take_ticket = [&]() -> uint32_t { return atomicAdd(rc.chunk_counter, 1u) + gridDim.x; };
     uint32_t cur = blockIdx.x;
-    if (rc.second_pass) { // (experimental wave form first: a chunk of its own only if that form left a read in it)
-        if (tid == 0) s_chunk = ((uint64_t)cur * RC_OWN < total && !rc.chunk_flags[cur]) ? take_ticket() : cur;
-        lds_barrier(tid);
-        cur = s_chunk;
-    }
     Staged nx = request(cur);
     for (;;) {
         RC_MARK(9); // (what ran since mark 8: the wave path of thread 0's wave)
@@ -709,16 +692,6 @@ __global__ void flag_complex_kernel(const unsigned long long* n_hits, unsigned l
     if (*n_hits) *n_complex = 1;
 }
 
-bool read_cluster_wave_form_requested()
-{
-#ifdef DRPRG_EXPERIMENTAL
-    const char* form = std::getenv("DRPRG_RC_FORM");
-    return form && std::string(form) == "wave";
-#else
-    return false; // (the wave form is part of `make EXPERIMENTAL=1` only)
-#endif
-}
-
 hipError_t launch_read_cluster(const SketchArgs& a, const FilterWork& fw, const ReadClusterArgs& rc, int n_cus, bool skip, hipStream_t stream)
 {
     if (skip) {
@@ -726,21 +699,7 @@ hipError_t launch_read_cluster(const SketchArgs& a, const FilterWork& fw, const 
         return hipGetLastError();
     }
     ReadClusterArgs rcd = rc;
-    // make EXPERIMENTAL=1 + DRPRG_RC_FORM=wave (read per launch; tests switch it): the wave form first (read_cluster_wave.hip: no workgroup barriers;
-    // everything a 150-base read needs) and this kernel behind it for what that leaves.  NOT the default: measured on MI355X
-    // (profiles/r04/rc_forms.txt) the wave form takes 61 us where this kernel takes 68 us on configs[1], and then still needs this
-    // kernel for the reads it left (37 us) and a 8 us kernel for the totals; on configs[4] 2.2 ms against 1.3 ms.  DESIGN.md section 6.
-    const bool wave_first = read_cluster_wave_form_requested();
-    rcd.second_pass = 0;
-    // (long reads do not fit a wave's 128 staged candidates: a batch of them goes straight to the workgroup form)
-#ifdef DRPRG_EXPERIMENTAL
-    if (wave_first && rc.n_unfit && rc.chunk_flags && a.n_bases / (a.n_reads ? a.n_reads : 1u) <= 600) {
-        HIP_TRY(launch_read_cluster_wave(a, fw, rc, n_cus, stream));
-        rcd.second_pass = 1;
-    }
-#else
-    (void)wave_first;
-#endif
+    // (a wave form without workgroup barriers lost to this kernel: 61 + 37 + 8 us against 68 us on configs[1]; profiles/r04/rc_forms.txt)
     static unsigned long long* d_phase = nullptr;
     const bool debug = std::getenv("DRPRG_RC_DEBUG") != nullptr;
     if (debug) {
@@ -767,15 +726,13 @@ hipError_t launch_read_cluster(const SketchArgs& a, const FilterWork& fw, const 
         rcd.minpath_in_lds = fit_with == fit_without ? 1u : 0u;
         if (rcd.minpath_in_lds) dyn = with;
     }
-    // look-ahead by the batch's mean read length (DRPRG_RC_AHEAD=128 / 256 / 512 forces one; the second pass behind the wave form shares
-    // that form's chunk numbering: 512)
+    // look-ahead by the batch's mean read length (DRPRG_RC_AHEAD=128 / 256 / 512 forces one)
     const uint64_t mean_len = a.n_bases / (a.n_reads ? a.n_reads : 1u);
     int ahead = mean_len <= 300 ? 128 : mean_len <= 600 ? 256 : 512;
     if (const char* e = std::getenv("DRPRG_RC_AHEAD")) {
         const int v = std::atoi(e);
         if (v == 128 || v == 256 || v == 512) ahead = v;
     }
-    if (rcd.second_pass) ahead = 512;
     static size_t configured[6][MAX_HIP_DEVICES] = {};
     auto launch = [&](auto kernel, size_t (&conf)[MAX_HIP_DEVICES]) -> hipError_t {
         HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), dyn, conf));

@@ -1,5 +1,5 @@
-// sketch_block.h -- the register-resident (w,k)-minimizer block shared by sketch_wave_kernel (sketch_wave.hip: every k-mer of a
-// batch) and read_verify_kernel (read_verify.hip: every k-mer of the reads that hold index k-mers).  A lane owns 16 consecutive k-mer
+// sketch_block.h -- the register-resident (w,k)-minimizer block of sketch_wave_kernel (sketch_wave.hip: every k-mer of a
+// batch).  A lane owns 16 consecutive k-mer
 // start positions = 16 bases, packed to 2 bits twice (first base in the low bits: `le`; first base in the high bits: `be`); the right
 // neighbour's two words arrive by a DPP wave shift; k-mer j is one v_alignbit_b32 out of each stream; the hash is mix_k<K>
 // (device_common.h); the W-1 hash values either side of a lane's 16 come from the neighbouring lanes by DPP wave shifts and the

@@ -13,11 +13,9 @@
 //                          in position order to the chunk's own slice (cursor in a scalar register: no atomics, no barriers;
 //                          the slices in chunk order are the candidates in position order).  Three tiles of bases are in flight
 //                          per wave in a register ring, the right neighbour's packed word arrives through a DPP wave shift.
-//                          Level-0 form, default: the groups that pass wait in the wave's 2 KB of LDS
-//                          and go through the second-stage filter -- its bits share the level-0 array -- 64 at a time,
-//                          one lane per group; only surviving positions leave the kernel.
-//   refine_kernel          level-0 form with DRPRG_FILTER_FORM=refine: the groups leave sketch_filter_kernel as 16-byte
-//                          records; one lane per group, second-stage filter in LDS, ordered compaction per slice.
+//                          Level-0 form: the groups that pass wait in the wave's 2 KB of LDS and go through the second-stage
+//                          filter -- its bits share the level-0 array -- 64 at a time, one lane per group; only surviving
+//                          positions leave the kernel.
 //   candidates.hip
 //   verify_scan_kernel     (round 5) every workgroup scans the slice counts itself (round 6: the counts of superblocks of eight slices),
 //                          takes its share of the ordered candidate list and reads the positions from the slices; then one lane per candidate, start to finish, no
@@ -25,8 +23,7 @@
 //                          positives end here) -> read lookup -> window-minimizer test, walked outward from the candidate
 //                          (verify_lane.h).  Leaves one record per candidate and the totals per workgroup, which workgroup 0
 //                          of read_cluster_kernel sums.
-//   cand_scan_kernel, cand_gather_kernel, verify_count_kernel, hit_scan_kernel: the same stage as four launches over a gathered
-//                          list (rounds 1-4; DRPRG_VERIFY_FORM=gather, and the generic pipeline's recount).
+//   hit_scan_kernel        the batch totals when read_cluster_kernel does not sum them (the generic pipeline's recount).
 //   read_cluster.hip
 //   read_cluster_kernel    clusters, size / overlap filters and coverage per read, out of LDS-staged chunks of the
 //                          candidate list: no hit list, no sort.
@@ -51,7 +48,7 @@ namespace dev {
 
 // 16 ASCII bases -> 32 bits, 2 per base, first base in the lowest bits.  The 2-bit letter is bits 2:1 of the ASCII code
 // (A 0, C 1, T 2, G 3, either case; anything else aliases one of them: it can only create a false candidate, which
-// verify_count_kernel rejects from the raw bases).
+// verify_scan_kernel rejects from the raw bases).
 __device__ inline uint32_t pack16le(const uint4& in)
 {
     // v_dot4_u32_u8 with the byte weights 1, 4, 16, 64 gathers the four 2-bit fields of a dword (they sit at bits 2:1 of
@@ -104,15 +101,12 @@ __device__ __forceinline__ uint32_t canon12_dev(uint32_t x)
 }
 
 // SHORT_K: k < 12, the level-1 key must be masked to 2k bits.  LEVEL0: the level-0 array is present (k = 15).
-// FUSED (with LEVEL0): the second stage runs in this kernel as well.  The groups that pass level 0 are staged in the wave's own
-// 2 KB of LDS and, 64 at a time, put through the second-stage filter one lane per group -- dense lanes, as in refine_kernel --
-// so that only surviving POSITIONS leave for global memory.  Why: the 16-byte group records of the
-// two-kernel form are 104 MB of scattered writes per 10 M reads, and those writes -- not their instructions: staging them in
-// LDS and copying them out coalesced once in twelve tiles changed nothing, sending them nowhere saved 65 us -- slow the
-// streaming reads down.  LDS: level 0 128 KB + stage 32 KB.  A second-stage array of its own (64 KB) does
-// not fit, and read from global memory (26 M four-byte loads per batch) it made this form slower than the two kernels, whether
-// the words were waited for at once or a tile later; so the second-stage bits share the level-0 array (FlatIndex::bloom0f): both
-// tests see a fuller array and let more through, which costs less than the records did.
+// FUSED (= LEVEL0): the second stage runs in this kernel as well.  The groups that pass level 0 are staged in the wave's own 2 KB of
+// LDS and, 64 at a time, put through the second-stage filter one lane per group, so that only surviving POSITIONS leave for global
+// memory (a second kernel behind this one, fed 16-byte group records, lost: 0.69 against 0.64 ms per 10 M reads).
+// LDS: level 0 128 KB + stage 32 KB.  A second-stage array of its own (64 KB) does not fit, and read from global memory (26 M
+// four-byte loads per batch) it was slower, whether the words were waited for at once or a tile later; so the second-stage bits
+// share the level-0 array (FlatIndex::bloom0f): both tests see a fuller array and let more through.
 // MID (with LEVEL0 and FUSED; 3 or 1 = bits per 12-mer in the level-0 array): the middle tier for indexes whose k-mers do not fit an
 // LDS-resident filter.  Level 0 is keyed on the canonical 12-mer; a group that passes it is looked up in the exact bitmap of the
 // canonical index 12-mers in global memory (2 MB: L2-resident; one exec-masked four-byte load per surviving group, all of a tile's
@@ -136,7 +130,7 @@ __device__ __forceinline__ uint32_t canon12_dev(uint32_t x)
 template <bool SHORT_K, bool LEVEL0, bool FUSED = false, int MID = 0, bool PACKED = false>
 __global__ __launch_bounds__(FT_THREADS) void sketch_filter_kernel(SketchArgs a, FilterWork fw)
 {
-    static_assert(!FUSED || LEVEL0, "the fused second stage belongs to the level-0 form");
+    static_assert(FUSED == LEVEL0, "the level-0 form runs its second stage in this kernel");
     static_assert(MID == 0 || (LEVEL0 && FUSED), "the middle tier is a variant of the level-0 form with the second stage inside");
     extern __shared__ uint32_t s_dyn[]; // [level 0: FT_L0_WORDS] then [levels 1+2: 2^bloom_wbits words] or, FUSED, [stage: 2 KB per wave]
     // positions per lane and tile: 32 (two packed words), or -- packed input with level 0 -- 64: one 16-byte load per lane and tile, and
@@ -184,7 +178,7 @@ __global__ __launch_bounds__(FT_THREADS) void sketch_filter_kernel(SketchArgs a,
 #pragma unroll
         for (int r = 0; r < ROUNDS; ++r) dst[tid + r * FT_THREADS] = v[r];
     }
-    if (!LEVEL0) fill(L12_BASE / 4, fw.bloom, n_words);    // (the level-0 form leaves levels 1+2 to refine_kernel)
+    if (!LEVEL0) fill(L12_BASE / 4, fw.bloom, n_words);    // (the level-0 form has no levels 1+2: its second-stage bits share the level-0 array)
     if (tid == 0 && (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t*)s_dyn != 0u) atomicOr(a.overflow, 8u);
 
     // ---- the schedule (FilterSched, kernels.h).  Every workgroup owns a contiguous range of the window's tiles.  Round 0: wave i of the
@@ -294,22 +288,18 @@ __global__ __launch_bounds__(FT_THREADS) void sketch_filter_kernel(SketchArgs a,
             p = *reinterpret_cast<const Pair*>(words + (int64_t)t * (WPOS / 16) + (int64_t)lane * NW);
         } else {
             const uint8_t* g = a.bases + (int64_t)t * WPOS + (int64_t)lane * G;
-            // (plain loads: non-temporal ones were measured on 10 M x 150 bp -- this kernel 382 -> 409 us, refine_kernel 45 -> 38 us
-            // because the group records then survive in the L2, the step 0.720 -> 0.746 ms)
+            // (plain loads: non-temporal ones were measured slower on 10 M x 150 bp in round 2, step 0.720 -> 0.746 ms)
             p.a = *reinterpret_cast<const uint4*>(g);
             p.b = *reinterpret_cast<const uint4*>(g + 16);
         }
     };
     uint64_t* out = fw.raw_pos + base_cur;
-    uint4* grp_out = LEVEL0 ? fw.raw_grp + base_cur : nullptr;
-    (void)grp_out;
     uint32_t lane_keep = (lane == 63 || (fw.debug & 1u)) ? 0u : 0xFFFFFFFFu;
     asm volatile("" : "+v"(lane_keep)); // (a value the compiler knows nothing about: it turns a known per-lane condition back into a branch)
     uint32_t wcur = 0; // candidates in the current slice so far (wave-uniform)
     // FUSED: the groups that passed level 0 wait in the wave's 2 KB of LDS; when the next tile might not fit, they go through the
     // second stage, 64 at a time and one lane each, and the surviving positions are appended in order.  The second-stage bits live
-    // in the same 128 KB array as level 0 (FlatIndex::bloom0f: there is no room for an array of their own, and reading one from
-    // global memory is what made this form lose).  (A macro, not a closure or a function taking the counters by reference: those
+    // in the same 128 KB array as level 0 (FlatIndex::bloom0f: there is no room for an array of their own).  (A macro, not a closure or a function taking the counters by reference: those
     // kept the counters in scratch memory, whose accesses count on vmcnt like every other VMEM instruction.)
     uint4* const stage = FUSED ? reinterpret_cast<uint4*>(s_dyn + STAGE_BASE_WORDS) + (tid >> 6) * STAGE_RECORDS : nullptr;
     uint32_t lcnt = 0; // groups staged (wave-uniform)
@@ -402,11 +392,11 @@ __global__ __launch_bounds__(FT_THREADS) void sketch_filter_kernel(SketchArgs a,
         if constexpr (FUSED) DRPRG_SECOND_STAGE(); // everything staged leaves now
         if (lane == 0) {
             const uint32_t kept = wcur < cap_cur ? wcur : cap_cur;
-            (LEVEL0 && !FUSED ? fw.grp_count : fw.slice_count)[slice] = kept;
+            fw.slice_count[slice] = kept;
             fw.slice_base[slice] = base_cur;
             fw.slice_cap[slice] = cap_cur;
             if (wcur > cap_cur) atomicOr(a.overflow, 4u);
-            if (!(LEVEL0 && !FUSED) && kept) atomicAdd(&fw.super_count[slice / FT_SUPER], kept); // (the two-kernel form: refine_kernel adds)
+            if (kept) atomicAdd(&fw.super_count[slice / FT_SUPER], kept);
         }
     };
 
@@ -429,9 +419,8 @@ __global__ __launch_bounds__(FT_THREADS) void sketch_filter_kernel(SketchArgs a,
         (void)wa; (void)wb; (void)wc;
         if constexpr (LEVEL0) {
             // ---- level 0: one 12-mer per four positions (the one at 4g+3 lies inside every 15-mer starting at 4g..4g+3); group g
-            // ends up in bit g of grp.  The ~2 % of the groups that pass leave the kernel as they are, with their bases: levels 1+2
-            // run in refine_kernel, one lane per group (here they would run for the whole wave as often as its busiest lane
-            // needs: a third of this kernel's instructions) ----
+            // ends up in bit g of grp.  The ~2 % of the groups that pass are staged with their bases for the second stage, which runs one
+            // lane per group (lane by lane it would run for the whole wave as often as its busiest lane needs: a third of the instructions) ----
             uint32_t grp = 0, xs[NG], hs[NG], ws[NG];
 #pragma unroll
             for (int g = 0; g < NG; ++g) { // all the LDS reads in flight before the first test
@@ -470,7 +459,7 @@ __global__ __launch_bounds__(FT_THREADS) void sketch_filter_kernel(SketchArgs a,
             if (b0 | b1 | b2 | b3 | b4) {
                 auto below = [&](uint64_t m) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); };
                 auto lanes_below = [&]() { return below(b0) + 2u * below(b1) + 4u * below(b2) + 8u * below(b3) + (NG > 8 ? 16u * below(b4) : 0u); };
-                const uint32_t wave_total = (uint32_t)(__popcll(b0) + 2 * __popcll(b1) + 4 * __popcll(b2) + 8 * __popcll(b3) + (NG > 8 ? 16 * __popcll(b4) : 0));
+                const uint32_t total = (uint32_t)(__popcll(b0) + 2 * __popcll(b1) + 4 * __popcll(b2) + 8 * __popcll(b3) + (NG > 8 ? 16 * __popcll(b4) : 0));
                 const uint64_t base = (uint64_t)t * WPOS + (uint64_t)lane * G;
                 auto record = [&](int g) {
                     const int q = g >> 2; // the word the group's sixteen bases start in (a select chain: no dynamic register index)
@@ -484,45 +473,33 @@ __global__ __launch_bounds__(FT_THREADS) void sketch_filter_kernel(SketchArgs a,
                     const uint64_t pos = base + 4u * (uint32_t)g;
                     return make_uint4((uint32_t)pos, (uint32_t)(pos >> 32), __funnelshift_r(lo, hi, sh), hi >> sh);
                 };
-                if constexpr (FUSED) {
-                    const uint32_t total = wave_total;
-                    // (running only the full rounds of 64 here and keeping the remainder staged was measured: 159.8 -> 156.7 M VALU
-                    // wave-instructions per 10 M reads and no change in the kernel's time, 318 against 321 us)
-                    if (lcnt + total > STAGE_CAP) DRPRG_SECOND_STAGE(); // wave-uniform
-                    if (total <= STAGE_CAP) {
-                        uint32_t at = lcnt + lanes_below();
-                        while (grp) {
-                            const int g = __ffs(grp) - 1;
-                            grp &= grp - 1;
-                            stage[at++] = record(g);
-                        }
-                        lcnt += total;
-                    } else { // a tile dense with index k-mers (amplicon reads): as many lanes at a time as the stage surely holds, in lane order
-                        constexpr int PART_LANES = (int)STAGE_CAP / NG;
-                        for (int part = 0; part < (64 + PART_LANES - 1) / PART_LANES; ++part) {
-                            uint32_t gq = (lane / PART_LANES) == part ? grp : 0u;
-                            const uint32_t cq = (uint32_t)__popc(gq);
-                            const uint64_t q0 = __ballot(cq & 1u), q1 = __ballot(cq & 2u), q2 = __ballot(cq & 4u), q3 = __ballot(cq & 8u);
-                            const uint64_t q4 = NG > 8 ? __ballot(cq & 16u) : 0ull;
-                            uint32_t at = below(q0) + 2u * below(q1) + 4u * below(q2) + 8u * below(q3) + (NG > 8 ? 16u * below(q4) : 0u);
-                            while (gq) {
-                                const int g = __ffs(gq) - 1;
-                                gq &= gq - 1;
-                                stage[at++] = record(g);
-                            }
-                            lcnt = (uint32_t)(__popcll(q0) + 2 * __popcll(q1) + 4 * __popcll(q2) + 8 * __popcll(q3) + (NG > 8 ? 16 * __popcll(q4) : 0));
-                            DRPRG_SECOND_STAGE();
-                        }
-                    }
-                } else {
-                    uint32_t at = wcur + lanes_below();
+                // (running only the full rounds of 64 here and keeping the remainder staged was measured: 159.8 -> 156.7 M VALU
+                // wave-instructions per 10 M reads and no change in the kernel's time, 318 against 321 us)
+                if (lcnt + total > STAGE_CAP) DRPRG_SECOND_STAGE(); // wave-uniform
+                if (total <= STAGE_CAP) {
+                    uint32_t at = lcnt + lanes_below();
                     while (grp) {
                         const int g = __ffs(grp) - 1;
                         grp &= grp - 1;
-                        if (at < cap_cur) grp_out[at] = record(g);
-                        ++at;
+                        stage[at++] = record(g);
                     }
-                    wcur += wave_total;
+                    lcnt += total;
+                } else { // a tile dense with index k-mers (amplicon reads): as many lanes at a time as the stage surely holds, in lane order
+                    constexpr int PART_LANES = (int)STAGE_CAP / NG;
+                    for (int part = 0; part < (64 + PART_LANES - 1) / PART_LANES; ++part) {
+                        uint32_t gq = (lane / PART_LANES) == part ? grp : 0u;
+                        const uint32_t cq = (uint32_t)__popc(gq);
+                        const uint64_t q0 = __ballot(cq & 1u), q1 = __ballot(cq & 2u), q2 = __ballot(cq & 4u), q3 = __ballot(cq & 8u);
+                        const uint64_t q4 = NG > 8 ? __ballot(cq & 16u) : 0ull;
+                        uint32_t at = below(q0) + 2u * below(q1) + 4u * below(q2) + 8u * below(q3) + (NG > 8 ? 16u * below(q4) : 0u);
+                        while (gq) {
+                            const int g = __ffs(gq) - 1;
+                            gq &= gq - 1;
+                            stage[at++] = record(g);
+                        }
+                        lcnt = (uint32_t)(__popcll(q0) + 2 * __popcll(q1) + 4 * __popcll(q2) + 8 * __popcll(q3) + (NG > 8 ? 16 * __popcll(q4) : 0));
+                        DRPRG_SECOND_STAGE();
+                    }
                 }
             }
             return;
@@ -610,7 +587,6 @@ __global__ __launch_bounds__(FT_THREADS) void sketch_filter_kernel(SketchArgs a,
             slice = slice0 + n_k;
             slice_geometry(n_k, n_begin, n_all, base_cur, cap_cur);
             out = fw.raw_pos + base_cur;
-            if (LEVEL0) grp_out = fw.raw_grp + base_cur;
             wcur = 0;
             tile = n_begin;
             c_all = n_all;
@@ -671,7 +647,7 @@ __global__ __launch_bounds__(FT_THREADS) void sketch_filter_kernel(SketchArgs a,
         const int64_t g = (int64_t)tile * WPOS + (int64_t)lane * G;
         Pair p;
         if constexpr (PACKED) {
-            const int64_t wi = g >> 4; // (words past the end read as 'A's: candidates there fail verify_count_kernel's bounds)
+            const int64_t wi = g >> 4; // (words past the end read as 'A's: candidates there fail verify_scan_kernel's bounds)
             p.x = wi < n_pwords ? words[wi] : 0u;
             p.y = wi + 1 < n_pwords ? words[wi + 1] : 0u;
             if constexpr (NW == 4) {
@@ -699,82 +675,9 @@ __global__ __launch_bounds__(FT_THREADS) void sketch_filter_kernel(SketchArgs a,
 #undef DRPRG_BLOCK_TEST
 #undef DRPRG_STAGE2_APPEND
 
-#ifdef DRPRG_EXPERIMENTAL
-// Second stage of the filter for the groups that passed level 0 (level-0 form of sketch_filter_kernel): one lane per
-// group tests its four k-mer codes against a 64 KB LDS-resident filter (four bits per code, < 15 % full); every wave
-// works through whole slices and compacts the surviving positions, in order, into the slice of raw_pos that
-// cand_scan_kernel / cand_gather_kernel expect.
-constexpr int RF_THREADS = 1024;
-__global__ __launch_bounds__(RF_THREADS) void refine_kernel(SketchArgs a, FilterWork fw)
-{
-    extern __shared__ uint32_t s_bloom[]; // the second-stage filter: 2^BLOOMR_WBITS words
-    const int tid = threadIdx.x, lane = tid & 63;
-    const uint32_t kmask = (1u << (2 * a.k)) - 1; // k = 15
-    for (uint32_t i = tid; i < (1u << BLOOMR_WBITS); i += RF_THREADS) s_bloom[i] = fw.bloomr[i];
-    __syncthreads(); // the only barrier: from here on every wave works through its own slices
-    auto below = [&](uint64_t m) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); };
-    const uint32_t n_waves = gridDim.x * (RF_THREADS / 64);
-    for (uint32_t s = blockIdx.x * (RF_THREADS / 64) + (uint32_t)(tid >> 6); s < fw.n_slices; s += n_waves) {
-        const uint32_t n = fw.grp_count[s], cap = fw.slice_cap[s];
-        const uint4* __restrict__ in = fw.raw_grp + fw.slice_base[s];
-        uint64_t* __restrict__ out = fw.raw_pos + fw.slice_base[s];
-        uint32_t written = 0; // wave-uniform
-        uint4 nxt = (uint32_t)lane < n ? in[lane] : make_uint4(0, 0, 0, 0);
-        for (uint32_t c0 = 0; c0 < n; c0 += 64) {
-            const uint4 r = nxt;
-            const uint32_t i = c0 + (uint32_t)lane;
-            if (i + 64 < n) nxt = in[i + 64]; // in flight while this chunk is tested
-            uint32_t cand = 0;
-            if (i < n) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) { // four bits of one word, keyed on the whole code of the k-mer at position q
-                    const uint32_t f = (q ? __funnelshift_r(r.z, r.w, 2 * q) : r.z) & kmask;
-                    const uint32_t h = f * BLOOM_CR;
-                    const uint32_t word = s_bloom[h >> (32 - BLOOMR_WBITS)];
-                    cand |= ((word >> (h & 31)) & (word >> ((h >> 5) & 31)) & (word >> ((h >> 10) & 31)) & (word >> ((h >> 15) & 31)) & 1u) << q;
-                }
-            }
-            // ordered append: exclusive prefix of the per-lane counts (0..4) from three ballots
-            const uint32_t cnt = (uint32_t)__popc(cand);
-            const uint64_t b0 = __ballot(cnt & 1u), b1 = __ballot(cnt & 2u), b2 = __ballot(cnt & 4u);
-            if (b0 | b1 | b2) {
-                uint32_t at = written + below(b0) + 2u * below(b1) + 4u * below(b2);
-                const uint64_t pos = ((uint64_t)r.y << 32) | r.x;
-                while (cand) {
-                    const int q = __ffs(cand) - 1;
-                    cand &= cand - 1;
-                    if (at < cap) out[at] = pos + (uint64_t)q;
-                    ++at;
-                }
-                written += (uint32_t)(__popcll(b0) + 2 * __popcll(b1) + 4 * __popcll(b2));
-            }
-        }
-        if (lane == 0) {
-            const uint32_t kept = written < cap ? written : cap;
-            fw.slice_count[s] = kept;
-            if (written > cap) atomicOr(a.overflow, 4u);
-            if (kept) atomicAdd(&fw.super_count[s / FT_SUPER], kept);
-        }
-    }
-}
-#endif // DRPRG_EXPERIMENTAL
-
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-// DRPRG_FILTER_FORM=refine with the library of `make EXPERIMENTAL=1`: the level-0 survivors leave sketch_filter_kernel as 16-byte group
-// records (FilterBuffers::raw_grp) for refine_kernel.  Read at every launch; the host allocates raw_grp only then (16 bytes per
-// candidate slot that the default sequence never touches).
-bool group_records_requested()
-{
-#ifdef DRPRG_EXPERIMENTAL
-    const char* form = std::getenv("DRPRG_FILTER_FORM");
-    return form && std::string(form) == "refine";
-#else
-    return false;
-#endif
-}
-
 uint32_t filter_n_tiles(uint64_t n_bases, int positions_per_lane)
 {
     const uint64_t wpos = 63ull * (uint64_t)positions_per_lane;
@@ -796,11 +699,10 @@ uint32_t filter_grid(bool level0, int n_cus, uint32_t n_tiles)
     return grid ? grid : 1;
 }
 
-// FilterBuffers::small: [slice counts: MAX_CHUNKS][superblock counts: MAX_SLICES][slice starts: MAX_CHUNKS][slice rooms: MAX_CHUNKS][prefix of the
-// slices: MAX_CHUNKS + 4 (gathered form only; the word behind the last slice's is the batch's candidate total)][group counts: MAX_CHUNKS (two-kernel
-// form)][per-workgroup totals: 4 x MAX_EX_WG].  The superblock counts are zero between two sequences (counters_home_kernel).
+// FilterBuffers::small: [slice counts: MAX_CHUNKS][superblock counts: MAX_SLICES][slice starts: MAX_CHUNKS][slice rooms: MAX_CHUNKS][the batch's
+// candidate total: 4 (one used)][per-workgroup totals: 4 x MAX_EX_WG].  The superblock counts are zero between two sequences (counters_home_kernel).
 constexpr size_t FT_SMALL_HEAD = (size_t)MAX_CHUNKS * 3 + MAX_SLICES;
-size_t filter_small_words() { return FT_SMALL_HEAD + (size_t)MAX_CHUNKS * 2 + 4 + 4 * (size_t)MAX_EX_WG; }
+size_t filter_small_words() { return FT_SMALL_HEAD + 4 + 4 * (size_t)MAX_EX_WG; }
 uint32_t* filter_super_counts(uint32_t* small) { return small + MAX_CHUNKS; }
 uint32_t filter_super_words() { return (uint32_t)MAX_SLICES; }
 
@@ -871,11 +773,10 @@ FilterSched make_filter_sched(uint32_t n_tiles, uint32_t n_wg, bool window_known
 
 void init_candidate_work(FilterWork& fw, const FilterBuffers& b, int n_cus)
 {
-    fw.cand_gp = b.cand_gp;
     fw.cand_info = b.cand_info;
     fw.cand_pos1 = b.cand_pos1;
     fw.cand_rec = b.cand_rec;
-    fw.wg_hits = b.small + FT_SMALL_HEAD + 2 * MAX_CHUNKS + 4;
+    fw.wg_hits = b.small + FT_SMALL_HEAD + 4;
     fw.wg_nmin = fw.wg_hits + MAX_EX_WG;
     fw.wg_maxlen = fw.wg_nmin + MAX_EX_WG;
     fw.wg_base = fw.wg_maxlen + MAX_EX_WG;
@@ -900,20 +801,15 @@ hipError_t launch_sketch_filter(const SketchArgs& a, uint32_t read_begin, uint32
     if (const char* dbg = std::getenv("DRPRG_FT_DEBUG")) fw.debug = (uint32_t)std::atoi(dbg); // 1 no filter test, 4 no level 0, 8 no read_cluster_kernel
     const bool level0 = mid || (bt.bloom0 != nullptr && a.k == 15 && ((size_t)4 << bt.bloom_wbits) + (size_t)FT_L0_WORDS * 4 <= 160 * 1024
         && !(fw.debug & 4u));
-    // the second stage inside the streaming kernel (default; its bits share the level-0 array) or as refine_kernel behind it
-    // (DRPRG_FILTER_FORM=refine): 0.64 against 0.69 ms per 10 M reads, DESIGN.md section 6
-    const bool fused = mid || (level0 && !group_records_requested()); // (the two-kernel form is part of `make EXPERIMENTAL=1` only)
     // Small tier: the second stage against a block filter in the L2 (sketch_filter_kernel<.., MID = 2>: the level-0 array then holds level 0 alone and
     // lets fewer groups through -- 11 M per 10 M x 150 bp) for packed batches, round 2-5's all-LDS form for ASCII ones; DRPRG_FILTER_STAGE2=l2|lds asks for one of
     // the two whatever the format (read at every launch: A/B runs, tests).  Both leave the same candidates behind verify: the tests map with both.
     const char* const stage2 = std::getenv("DRPRG_FILTER_STAGE2");
     const bool want_l2 = stage2 && *stage2 ? std::string(stage2) == "l2" : a.packed != 0; // (the kernel's header comment: packed batches have the L2 probes to spare)
-    const bool blk = !mid && level0 && fused && want_l2 && bt.blkc != nullptr && bt.blkc_wbits >= 1 && bt.blkc_wbits <= MID_C_MAX_WBITS;
-    if (level0 && !fused && !b.raw_grp) return hipErrorInvalidValue; // (the caller allocates the group records when group_records_requested())
+    const bool blk = !mid && level0 && want_l2 && bt.blkc != nullptr && bt.blkc_wbits >= 1 && bt.blkc_wbits <= MID_C_MAX_WBITS;
     fw.bloom = bt.bloom;
     fw.bloom_wbits = bt.bloom_wbits;
-    fw.bloomr = bt.bloomr;
-    fw.bloom0 = mid ? bt.mid0 : (level0 ? (fused && !blk ? bt.bloom0f : bt.bloom0) : nullptr);
+    fw.bloom0 = mid ? bt.mid0 : (level0 ? (blk ? bt.bloom0 : bt.bloom0f) : nullptr);
     fw.bloom0_wbits = mid ? 15 : (level0 ? bt.bloom0_wbits : 0);
     fw.mid_bitmap = bt.mid_bitmap;
     fw.midc = blk ? bt.blkc : bt.midc;
@@ -988,45 +884,32 @@ hipError_t launch_sketch_filter(const SketchArgs& a, uint32_t read_begin, uint32
     fw.super_count = filter_super_counts(b.small);
     fw.slice_base = b.small + MAX_CHUNKS + MAX_SLICES;
     fw.slice_cap = fw.slice_base + MAX_CHUNKS;
-    fw.cand_prefix = b.small + FT_SMALL_HEAD;
-    fw.cand_total = fw.cand_prefix + fw.n_slices;
-    fw.grp_count = b.small + FT_SMALL_HEAD + MAX_CHUNKS + 4;
-    fw.raw_grp = b.raw_grp;
+    fw.cand_count = b.small + FT_SMALL_HEAD;
+    fw.cand_total = fw.cand_count;
     {
         using Kernel = void (*)(SketchArgs, FilterWork);
-        const int which = mid ? (bt.mid0_bits == 3 ? 4 : 5) : blk ? 6 : level0 ? (fused ? 3 : 2) : (a.k < 12 ? 1 : 0);
-        const Kernel ascii = which == 6 ? &sketch_filter_kernel<false, true, true, 2>
-            : which == 5                ? &sketch_filter_kernel<false, true, true, 1>
-            : which == 4                ? &sketch_filter_kernel<false, true, true, 3>
-            : which == 3                ? &sketch_filter_kernel<false, true, true>
-            : which == 2                ? &sketch_filter_kernel<false, true>
+        const int which = mid ? (bt.mid0_bits == 3 ? 3 : 4) : blk ? 5 : level0 ? 2 : (a.k < 12 ? 1 : 0);
+        const Kernel ascii = which == 5 ? &sketch_filter_kernel<false, true, true, 2>
+            : which == 4                ? &sketch_filter_kernel<false, true, true, 1>
+            : which == 3                ? &sketch_filter_kernel<false, true, true, 3>
+            : which == 2                ? &sketch_filter_kernel<false, true, true>
             : which == 1                ? &sketch_filter_kernel<true, false>
                                         : &sketch_filter_kernel<false, false>;
-        const Kernel packed = which == 6 ? &sketch_filter_kernel<false, true, true, 2, true>
-            : which == 5                 ? &sketch_filter_kernel<false, true, true, 1, true>
-            : which == 4                 ? &sketch_filter_kernel<false, true, true, 3, true>
-            : which == 3                 ? &sketch_filter_kernel<false, true, true, 0, true>
-            : which == 2                 ? &sketch_filter_kernel<false, true, false, 0, true>
+        const Kernel packed = which == 5 ? &sketch_filter_kernel<false, true, true, 2, true>
+            : which == 4                 ? &sketch_filter_kernel<false, true, true, 1, true>
+            : which == 3                 ? &sketch_filter_kernel<false, true, true, 3, true>
+            : which == 2                 ? &sketch_filter_kernel<false, true, true, 0, true>
             : which == 1                 ? &sketch_filter_kernel<true, false, false, 0, true>
                                          : &sketch_filter_kernel<false, false, false, 0, true>;
         const Kernel kernel = a.packed ? packed : ascii;
-        // (+ the chunk counter: 16 bytes of their own, or -- the level-0 form with the second stage inside fills the 160 KB -- the last record of the last wave's stage)
-        const size_t dyn = level0 ? (size_t)FT_L0_WORDS * 4 + (fused ? (size_t)FT_WAVES * 2048 : 16) : ((size_t)4 << bt.bloom_wbits) + 16;
+        // (+ the chunk counter: 16 bytes of their own, or -- the level-0 form fills the 160 KB with its stage -- the last record of the last wave's stage)
+        const size_t dyn = level0 ? (size_t)FT_L0_WORDS * 4 + (size_t)FT_WAVES * 2048 : ((size_t)4 << bt.bloom_wbits) + 16;
         fw.sched.lds_word = (uint32_t)(dyn / 4 - 4);
-        static size_t configured[14][MAX_HIP_DEVICES] = {};
-        HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), dyn, configured[which + (a.packed ? 7 : 0)]));
+        static size_t configured[12][MAX_HIP_DEVICES] = {};
+        HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), dyn, configured[which + (a.packed ? 6 : 0)]));
         launch_timed(timer, kernel, dim3(grid), dim3(FT_THREADS), dyn, stream, a, fw);
     }
     HIP_TRY(hipGetLastError());
-#ifdef DRPRG_EXPERIMENTAL
-    if (level0 && !fused) {
-        static size_t refine_configured[MAX_HIP_DEVICES] = {};
-        const size_t dyn = (size_t)4 << BLOOMR_WBITS;
-        HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(&refine_kernel), dyn, refine_configured));
-        hipLaunchKernelGGL(refine_kernel, dim3(std::min<uint32_t>((fw.n_slices + RF_THREADS / 64 - 1) / (RF_THREADS / 64), (uint32_t)n_cus * 2)), dim3(RF_THREADS), dyn, stream, a, fw);
-        HIP_TRY(hipGetLastError());
-    }
-#endif
     const bool skip_rc = (fw.debug & 8u) != 0; // debug 8: every read with a hit goes the generic way
     HIP_TRY(launch_candidate_stage(a, fw, rc, n_cus, stream, skip_rc));
     ReadClusterArgs rct = rc;

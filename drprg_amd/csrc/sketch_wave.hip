@@ -19,8 +19,7 @@
 //   * read boundaries and non-ACGT bases become a per-lane mask of invalid k-mer starts (a 64-word LDS array per wave, touched
 //     only by that wave);
 //   * the minimizers of the tile are compacted per wave (prefix over lanes with wave scans) and thinned in passes with all
-//     lanes busy: Bloom tier -> exact table lookup -> reads that lie inside the tile are clustered on the spot and their
-//     coverage added (stage C1) -> a record for what is left; the four tiles of a workgroup share one slice.
+//     lanes busy: Bloom tier -> exact table lookup -> a record per index minimizer; the four tiles of a workgroup share one slice.
 #include "sketch_block.h"
 
 namespace drprg {
@@ -68,7 +67,7 @@ struct alignas(16) WaveLds {
     uint32_t rcnt[64];      // per lane: reads that start in its 16 positions; later the read before its first position
 };
 
-template <int K, int W, bool FUSE, bool PACKED>
+template <int K, int W, bool PACKED>
 __device__ __forceinline__ void sketch_wave_tile(const SketchArgs& a, uint32_t tile, bool active, WaveLds& lds, uint32_t* s_nb, uint32_t* s_sum, int lane, int wave)
 {
     if (!active) { // a wave past the last tile still meets the workgroup's two barriers
@@ -252,7 +251,7 @@ __device__ __forceinline__ void sketch_wave_tile(const SketchArgs& a, uint32_t t
         n_b += (uint32_t)__popcll(fm);
     }
     wave_lds_fence();
-    // everything a record, or a hit of the in-kernel clustering, needs of list entry i
+    // everything a record needs of list entry i
     struct Entry {
         uint32_t p, slot, read, strand, kn, prg, rev, thr;
         uint4 sf; // record offset, count, the first record's node << 1 | strand, its prg | shortest path << 12
@@ -261,7 +260,7 @@ __device__ __forceinline__ void sketch_wave_tile(const SketchArgs& a, uint32_t t
     const uint32_t w1_magic = w1_reciprocal(W);
     auto decode = [&](uint32_t i) -> Entry {
         Entry e;
-        e.p = list[i] & 0x7FFFu;
+        e.p = list[i];
         e.slot = hvs[e.p];
         const uint64_t gp = (uint64_t)(origin + (int64_t)e.p);
         const uint32_t rb = *LDS_U32(&lds.rbits[e.p >> 4]);
@@ -293,110 +292,10 @@ __device__ __forceinline__ void sketch_wave_tile(const SketchArgs& a, uint32_t t
         return e;
     };
 
-    // ---- stage C1: reads that lie inside this tile are clustered here (pandora define_clusters / filter_clusters /
-    // add_hits_to_kmergraphs, as read_cluster_kernel's segment path does them).  Such a read has every one of its index
-    // minimizers in this wave's list, next to each other and in position order.  If each has exactly one index record and
-    // all of them fall into ONE (prg, strand) group, its clusters are the runs without a position gap > max_diff, a cluster is
-    // kept iff it has more hits than the size threshold, and the overlap sweep cannot drop a kept one (same group, disjoint
-    // ranges): every hit of a kept cluster adds 1 to its k-mer node's coverage right here.  Every other read -- it crosses the
-    // tile's edge, a minimizer with several records, hits in two groups, more than 64 index minimizers -- keeps its entries
-    // for stage C2 (records -> gather -> read_cluster_kernel).  a.fuse: 0 off (the default: see Mapper), 1 on, -1 take the same
-    // additions back (the host's undo pass before it re-runs a batch whose record slices overflowed).
-    uint32_t n_f = n_b, fast_clusters = 0, fast_hits = 0, my_hits = 0;
-    if constexpr (FUSE) {
-        n_f = 0;
-        uint32_t cont_read = 0xFFFFFFFFu; // a read with more entries than one pass holds: never clustered here
-        for (uint32_t c = 0; c < n_b;) {
-            const uint32_t i = c + (uint32_t)lane;
-            const bool valid = i < n_b;
-            Entry e {};
-            if (valid) e = decode(i);
-            const uint32_t r_prev = from_prev_lane(e.read), pos_prev = from_prev_lane((uint32_t)e.pos);
-            const bool head = valid && (lane == 0 || e.read != r_prev);
-            const uint64_t hm = __ballot(head);
-            uint32_t take = n_b - c < 64u ? n_b - c : 64u;
-            bool oversized = false;
-            if (c + 64 < n_b) { // entries follow: the last read of this pass may run on -- leave it to the next pass
-                const int last_head = 63 - __clzll((long long)hm);
-                if (last_head > 0) take = (uint32_t)last_head;
-                else oversized = true; // one read fills the pass
-            }
-            const bool active = valid && (uint32_t)lane < take;
-            const uint64_t upto = lane == 63 ? ~0ull : ((2ull << lane) - 1ull); // bits 0 .. lane
-            // my read: entries [rs, re)
-            const int rs = 63 - __clzll((long long)((hm & upto) | 1ull));
-            const uint64_t h_after = lane == 63 ? 0ull : (hm >> (lane + 1));
-            uint32_t re = h_after ? (uint32_t)lane + (uint32_t)__ffsll((long long)h_after) : 64u;
-            if (re > take) re = take;
-            const uint32_t g = (e.prg << 1) | e.rev;
-            const uint32_t g0 = (uint32_t)__shfl((int)g, rs);
-            const int64_t s_loc = (int64_t)e.o0 - origin, e_loc = (int64_t)e.o1 - origin;
-            const bool owned = s_loc >= SW_FIRST * SW_G && e_loc <= (SW_LAST + 1) * SW_G - 1 + K; // every k-mer of the read starts in an evaluated lane
-            // a minimizer with several index records (the same k-mer on several paths of a PRG): all of them must be in the group
-            bool records_ok = e.sf.y >= 1u && e.sf.y <= ((a.fuse == 2 || a.fuse == -2) ? 1u : 8u); // (fuse +-2: single-record minimizers only, for A/B runs)
-            if (active && records_ok)
-                for (uint32_t q = 1; q < e.sf.y; ++q) {
-                    const uint32_t kq = a.rec_knode[e.sf.x + q], pq = a.rec_prg[e.sf.x + q];
-                    records_ok &= pq == e.prg && (((kq & 1u) == e.strand) ? 0u : 1u) == e.rev;
-                }
-            const bool bad = active && (!records_ok || g != g0 || !owned || e.read == cont_read || oversized);
-            if (a.dbg && a.fuse > 0) { // why entries stay behind (DRPRG_WAVE_DEBUG)
-                const uint64_t b0 = __ballot(active), b1 = __ballot(active && !records_ok), b2 = __ballot(active && records_ok && g != g0),
-                               b3 = __ballot(active && !owned), b4 = __ballot(active && (e.read == cont_read || oversized));
-                if (lane == 0) {
-                    atomicAdd(&a.dbg[0], (unsigned long long)__popcll(b0));
-                    atomicAdd(&a.dbg[1], (unsigned long long)__popcll(b1));
-                    atomicAdd(&a.dbg[2], (unsigned long long)__popcll(b2));
-                    atomicAdd(&a.dbg[3], (unsigned long long)__popcll(b3));
-                    atomicAdd(&a.dbg[4], (unsigned long long)__popcll(b4));
-                }
-            }
-            const uint64_t bm = __ballot(bad);
-            const uint64_t seg = (re >= 64u ? ~0ull : ((1ull << re) - 1ull)) & ~((1ull << rs) - 1ull);
-            const bool read_bad = (bm & seg) != 0;
-            // my cluster: entries [cs, ce)
-            const bool chead = active && (head || (uint32_t)e.pos - pos_prev > (uint32_t)a.max_diff);
-            const uint64_t cm = __ballot(chead);
-            const int cs = 63 - __clzll((long long)((cm & upto) | 1ull));
-            const uint64_t c_after = lane == 63 ? 0ull : (cm >> (lane + 1));
-            uint32_t ce = c_after ? (uint32_t)lane + (uint32_t)__ffsll((long long)c_after) : 64u;
-            if (ce > take) ce = take;
-            const bool fast = active && !read_bad;
-            // hits of my cluster = sum of the record counts of its entries (differences of an inclusive scan over the lanes)
-            const uint32_t cnt_incl = wave_inclusive_scan(active ? e.sf.y : 0u);
-            // (both shuffles by every lane: a lane that sits out a shuffle reads as 0 to the lanes that ask for its value)
-            const uint32_t upto_end = (uint32_t)__shfl((int)cnt_incl, ce > 0 ? (int)ce - 1 : 0);
-            const uint32_t at_prev = (uint32_t)__shfl((int)cnt_incl, cs > 0 ? cs - 1 : 0);
-            const uint32_t before = cs > 0 ? at_prev : 0u;
-            const bool kept = fast && (upto_end - before) > e.thr;
-            if (kept) {
-                for (uint32_t q = 0; q < e.sf.y; ++q) {
-                    const uint32_t kq = q ? a.rec_knode[e.sf.x + q] : e.kn;
-                    if (a.fuse > 0) atomicAdd(&a.covg[(kq >> 1) * 2u + e.rev], 1u);
-                    else atomicSub(&a.covg[(kq >> 1) * 2u + e.rev], 1u);
-                }
-                if (lane == cs) {
-                    if (a.fuse > 0) atomicAdd(&a.prg_reads[e.prg], 1u);
-                    else atomicSub(&a.prg_reads[e.prg], 1u);
-                }
-            }
-            fast_hits += wave_sum(kept ? e.sf.y : 0u);
-            fast_clusters += (uint32_t)__popcll(__ballot(kept && lane == cs));
-            if (active) my_hits += e.sf.y;
-            if (fast) list[i] = (uint16_t)(e.p | 0x8000u); // done
-            n_f += (uint32_t)__popcll(__ballot(active && read_bad));
-            if (a.dbg && a.fuse > 0) {
-                const uint64_t left = __ballot(active && read_bad);
-                if (lane == 0) atomicAdd(&a.dbg[5], (unsigned long long)__popcll(left));
-            }
-            if (oversized) cont_read = (uint32_t)__builtin_amdgcn_readfirstlane((int)e.read);
-            c += take;
-        }
-        wave_lds_fence();
-    }
+    uint32_t my_hits = 0;
 
     // ---- where this tile's records go: the workgroup's four tiles share one slice, in tile order ----
-    if (lane == 0) s_nb[wave] = n_f;
+    if (lane == 0) s_nb[wave] = n_b;
     __syncthreads();
     uint32_t base = 0, wg_total = 0;
 #pragma unroll
@@ -406,15 +305,15 @@ __device__ __forceinline__ void sketch_wave_tile(const SketchArgs& a, uint32_t t
         wg_total += x;
     }
     const size_t slice = (size_t)blockIdx.x * a.tile_cap;
-    // ---- stage C2: one record per index minimizer that stage C1 left ----
+    // ---- stage C: one record per index minimizer ----
     uint32_t written = 0;
-    for (uint32_t i0 = 0; i0 < n_b && (!FUSE || a.fuse >= 0); i0 += 64) {
+    for (uint32_t i0 = 0; i0 < n_b; i0 += 64) {
         const uint32_t i = i0 + (uint32_t)lane;
-        const bool todo = i < n_b && (!FUSE || !(list[i] & 0x8000u));
+        const bool todo = i < n_b;
         const uint64_t tm = __ballot(todo);
         if (todo) {
             const Entry e = decode(i);
-            if (!FUSE) my_hits += e.sf.y;
+            my_hits += e.sf.y;
             const uint32_t at = base + written + lanes_below(tm);
             if (e.pos >= (1ull << HIT_POS_BITS)) atomicOr(a.overflow, 2u);
             else if (at < a.tile_cap) {
@@ -430,15 +329,12 @@ __device__ __forceinline__ void sketch_wave_tile(const SketchArgs& a, uint32_t t
     if (lane == 0) {
         atomicAdd(&s_sum[0], tile_hits);
         atomicAdd(&s_sum[1], nmin);
-        atomicAdd(&s_sum[2], fast_clusters);
-        atomicAdd(&s_sum[3], fast_hits);
     }
     __syncthreads();
-    if (wave == 0 && lane == 0 && (!FUSE || a.fuse >= 0)) {
+    if (wave == 0 && lane == 0) {
         a.tile_count[blockIdx.x] = wg_total < a.tile_cap ? wg_total : a.tile_cap;
         a.tile_hits[blockIdx.x] = s_sum[0];
         a.tile_nmin[blockIdx.x] = s_sum[1];
-        a.tile_fast[blockIdx.x] = (s_sum[3] << 16) | s_sum[2]; // hits and clusters kept by stage C1 (<= 3904 each)
         if (wg_total > a.tile_cap) atomicOr(a.overflow, 4u);
     }
 }
@@ -452,15 +348,15 @@ __device__ __forceinline__ void sketch_wave_tile(const SketchArgs& a, uint32_t t
 // A ticket per workgroup of 16 waves / 112 KB of LDS: 10 ms, 5.3 ms even without the scan (4 waves per SIMD).  No tickets,
 // tile = blockIdx order, two-level scan (64 tiles per group, look-back over groups): 13 ms against 3.8 ms without the scan --
 // a tile waited 48 us for its 63 group neighbours and 40 us for the previous group, four times its own 12 us.
-template <int K, int W, bool FUSE, bool PACKED>
+template <int K, int W, bool PACKED>
 __global__ __launch_bounds__(SW_WAVES * 64) void sketch_wave_kernel(SketchArgs a, uint32_t n_tiles)
 {
     __shared__ WaveLds s_lds[SW_WAVES];
-    __shared__ uint32_t s_nb[SW_WAVES], s_sum[4];
+    __shared__ uint32_t s_nb[SW_WAVES], s_sum[2];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x < 4) s_sum[threadIdx.x] = 0; // (added to after the first barrier at the earliest)
+    if (threadIdx.x < 2) s_sum[threadIdx.x] = 0; // (added to after the first barrier at the earliest)
     const uint32_t tile = blockIdx.x * SW_WAVES + (uint32_t)wave;
-    sketch_wave_tile<K, W, FUSE, PACKED>(a, tile, tile < n_tiles, s_lds[wave], s_nb, s_sum, lane, wave);
+    sketch_wave_tile<K, W, PACKED>(a, tile, tile < n_tiles, s_lds[wave], s_nb, s_sum, lane, wave);
 }
 
 hipError_t launch_sketch_wave(const SketchArgs& a, hipStream_t stream, KernelTimer timer)
@@ -470,18 +366,12 @@ hipError_t launch_sketch_wave(const SketchArgs& a, hipStream_t stream, KernelTim
     HIP_TRY(launch_tile_first_read(a.offsets, a.n_reads, SW_EVAL, SW_G, n_tiles, a.tile_first_read, stream));
     const dim3 g(wave_n_slices(a.n_bases)), b(SW_WAVES * 64);
     auto go = [&](auto kernel) { launch_timed(timer, kernel, g, b, 0, stream, a, n_tiles); };
-    const int which = (a.w == 11 ? 0 : 4) | (a.fuse ? 2 : 0) | (a.packed ? 1 : 0);
+    const int which = (a.w == 11 ? 0 : 2) | (a.packed ? 1 : 0);
     switch (which) {
-    case 0: go(sketch_wave_kernel<15, 11, false, false>); break;
-    case 1: go(sketch_wave_kernel<15, 11, false, true>); break;
-    case 4: go(sketch_wave_kernel<15, 14, false, false>); break;
-    case 5: go(sketch_wave_kernel<15, 14, false, true>); break;
-#ifdef DRPRG_EXPERIMENTAL // stage C1 (a.fuse != 0: DRPRG_WAVE_FUSE) exists in `make EXPERIMENTAL=1` only
-    case 2: go(sketch_wave_kernel<15, 11, true, false>); break;
-    case 3: go(sketch_wave_kernel<15, 11, true, true>); break;
-    case 6: go(sketch_wave_kernel<15, 14, true, false>); break;
-    case 7: go(sketch_wave_kernel<15, 14, true, true>); break;
-#endif
+    case 0: go(sketch_wave_kernel<15, 11, false>); break;
+    case 1: go(sketch_wave_kernel<15, 11, true>); break;
+    case 2: go(sketch_wave_kernel<15, 14, false>); break;
+    case 3: go(sketch_wave_kernel<15, 14, true>); break;
     default: return hipErrorInvalidValue;
     }
     HIP_TRY(hipGetLastError());

@@ -16,14 +16,6 @@ import os
 FORCED_GENERIC = bool(int(os.environ.get("DRPRG_FT_DEBUG", "0") or 0) & 8)
 
 
-def _experimental():
-    from drprg_amd import _lib
-    return bool(_lib.lib.drprg_hip_experimental())
-
-
-EXPERIMENTAL = _experimental()  # the library holds the opt-in kernel forms (make EXPERIMENTAL=1, DRPRG_HIP_LIB)
-
-
 def _ctx(tmp_path, panel, w, k, illumina, genome_size=20000, kernel=0, min_cluster_size=10):
     from drprg_amd import Context
     prg = str(tmp_path / "dr.prg")
@@ -97,24 +89,10 @@ def _compare(ctx, oracle, bases, offsets, w, k, illumina, kernel, min_cluster_si
     pcnt = ctx.counters()
     assert np.array_equal(pcov, ocov) and np.array_equal(pprg, oprg)
     # (not leftover_reads: a non-ACGT byte reads as a letter in the words, so the packed filter can pass a position the ASCII filter
-    # does not; verify_count_kernel rejects it, but it holds a slot of the ordered candidate list, the chunks of read_cluster_kernel shift
+    # does not; verify_scan_kernel rejects it, but it holds a slot of the ordered candidate list, the chunks of read_cluster_kernel shift
     # by it, and WHICH reads straddle a chunk's look-ahead and go through the generic pipeline instead can differ -- the results cannot)
     for key in ("reads", "bases", "minimizers", "hits", "clusters_kept", "hits_kept"):
         assert pcnt[key] == gcnt[key], key
-    # ... and, with the library of `make EXPERIMENTAL=1`, through the wave form of the last filtered stage (read_cluster_wave.hip; the
-    # switch is read at every launch).  The default suite maps every case in the two input formats only.
-    if EXPERIMENTAL and len(offsets) > 1 and int(offsets[-1]) // (len(offsets) - 1) <= 600:
-        os.environ["DRPRG_RC_FORM"] = "wave"
-        try:
-            ctx.reset()
-            ctx.map_host(bases, offsets)
-            wcov, wprg = ctx.coverage()
-            wcnt = ctx.counters()
-        finally:
-            del os.environ["DRPRG_RC_FORM"]
-        assert np.array_equal(wcov, ocov) and np.array_equal(wprg, oprg)
-        for key in ("reads", "bases", "minimizers", "hits", "clusters_kept", "hits_kept"):  # (which reads are left to the generic
-            assert wcnt[key] == gcnt[key], key                                               # pipeline is the form's own business)
     return ocnt
 
 
@@ -233,62 +211,10 @@ def _reads_from(rng, seqs, n, length, sub_rate=0.002):
     return np.concatenate(reads), offs
 
 
-@pytest.mark.experimental
-@pytest.mark.parametrize("w", [11, 14])
-def test_read_by_read_verification(tmp_path, oracle, w):
-    """read_verify_kernel (short-read batches at k = 15: every read with several candidates is sketched once) on everything its
-    chunk logic distinguishes: 150-base panel reads (sketched), genome reads with a stray index k-mer (the lane path's queue), panel
-    reads of 280 / 900 bases (more candidates than a chunk's look-ahead: the overhang goes through the queue of another chunk),
-    reads over 1024 bases (never sketched), reads shorter than k, empty reads, N runs, lower case -- mean length below 300, the batches
-    the kernel serves when DRPRG_VERIFY_FORM=read asks for it; and the default lane form must count the same"""
-    from drprg_amd import synth
-    rng = np.random.default_rng(40 + w)
-    loci = [synth.make_locus(rng, 2500, site_every=45) for _ in range(3)]
-    panel = synth.Panel(["a", "b", "c"], loci)
-    haps = [synth.sample_haplotype(rng, t).encode() for t in loci for _ in range(3)]
-    genome = synth.random_seq(rng, 60000).encode()
-    parts = [_reads_from(rng, haps, 5000, 150), _reads_from(rng, [genome], 9000, 150), _reads_from(rng, haps, 600, 280),
-             _reads_from(rng, haps, 60, 900, sub_rate=0.01), _reads_from(rng, haps, 12, 1500), _reads_from(rng, haps + [genome], 800, 40),
-             _reads_from(rng, haps, 300, 14), _reads_from(rng, haps, 300, 15), _reads_from(rng, haps, 300, 16)]
-    reads = []
-    for b, o in parts:
-        reads += [b[int(o[i]):int(o[i + 1])].copy() for i in range(len(o) - 1)]
-    reads += [np.zeros(0, np.uint8)] * 200
-    order = rng.permutation(len(reads))
-    reads = [reads[i] for i in order]
-    for r in reads:
-        if len(r) and rng.random() < 0.05:
-            r[rng.integers(0, len(r), size=max(1, len(r) // 60))] = ord("N")
-    reads = [np.frombuffer(r.tobytes().lower(), np.uint8) if len(r) and rng.random() < 0.1 else r for r in reads]
-    offs = np.zeros(len(reads) + 1, np.uint64)
-    offs[1:] = np.cumsum([len(r) for r in reads])
-    bases = np.concatenate(reads)
-    assert int(offs[-1]) // len(reads) <= 300
-    ctx = _ctx(tmp_path, panel, w, 15, True, genome_size=60000, kernel=2)
-    os.environ["DRPRG_VERIFY_FORM"] = "read"
-    try:
-        cnt = _compare(ctx, oracle, bases, offs, w, 15, True, 2)
-        assert cnt["clusters_kept"] > 4000
-        ctx.reset()
-        ctx.map_host(bases, offs)
-        got = ctx.counters()
-        cov, prg = ctx.coverage()
-    finally:
-        del os.environ["DRPRG_VERIFY_FORM"]
-    ctx.reset()
-    ctx.map_host(bases, offs)
-    lane = ctx.counters()
-    lcov, lprg = ctx.coverage()
-    assert np.array_equal(cov, lcov) and np.array_equal(prg, lprg)
-    for key in ("reads", "bases", "minimizers", "hits", "clusters_kept", "hits_kept", "leftover_reads"):
-        assert lane[key] == got[key], key
-
-
 def test_candidates_at_both_ends_of_the_batch(tmp_path, oracle):
     """verify_scan_kernel reads the candidates from the filter kernel's slices through the prefix of the superblock counts it keeps
     in LDS: a batch whose candidates sit in its first and its last slices, with half a million reads that leave no candidate between
-    them, makes the workgroup whose share straddles the gap bisect across thousands of empty superblocks -- and the three-kernel
-    sequence (DRPRG_VERIFY_FORM=gather) must count the same"""
+    them, makes the workgroup whose share straddles the gap bisect across thousands of empty superblocks"""
     from drprg_amd import synth
     rng = np.random.default_rng(77)
     panel = synth.small_panel(seed=31, n_loci=3, length=900)
@@ -302,21 +228,6 @@ def test_candidates_at_both_ends_of_the_batch(tmp_path, oracle):
     ctx = _ctx(tmp_path, panel, 11, 15, True, kernel=2)
     cnt = _compare(ctx, oracle, bases, offs, 11, 15, True, 2, threads=ORACLE_THREADS)
     assert cnt["clusters_kept"] > 200
-    got = ctx.counters()
-    os.environ["DRPRG_VERIFY_FORM"] = "gather"
-    try:
-        ctx.reset()
-        ctx.map_host(bases, offs)
-        old = ctx.counters()
-        ocov, oprg = ctx.coverage()
-    finally:
-        del os.environ["DRPRG_VERIFY_FORM"]
-    ctx.reset()
-    ctx.map_host(bases, offs)
-    cov, prg = ctx.coverage()
-    assert np.array_equal(cov, ocov) and np.array_equal(prg, oprg)
-    for key in ("reads", "bases", "minimizers", "hits", "clusters_kept", "hits_kept", "leftover_reads"):
-        assert old[key] == got[key] or key == "leftover_reads", key
 
 
 @pytest.mark.parametrize("illumina", [True, False])
@@ -722,43 +633,11 @@ def test_multi_device_context_equals_single(tmp_path, oracle):
     assert outs[0] == outs[1] and len(outs[0]) > 30
 
 
-@pytest.mark.experimental
-def test_in_kernel_clustering_of_sketch_wave_kernel(tmp_path, oracle, monkeypatch):
-    """DRPRG_WAVE_FUSE=1 (opt-in): sketch_wave_kernel clusters the reads that lie inside one of its tiles itself -- single
-    (prg, strand) group, minimizers with up to eight index records -- and only the others (reads across a tile edge, hits in
-    several groups, more than 64 index minimizers) leave records for gather + read_cluster_kernel.  Same coverage vector and
-    counters as the oracle on the 500-locus index and on a nested / indel panel with duplicated loci; a tiny record slice
-    forces the overflow + undo + regrow path."""
+def test_wave_tile_geometry_edges(tmp_path, oracle):
+    """sketch_wave_kernel evaluates 61 lanes x 16 positions per tile (976) and loads 1024 bases: reads whose lengths sit on those
+    edges (15, 16, 17, 31, 960 ... 1007, 1024, 1952), runs of empty reads (several reads starting at one position), N runs that
+    cross lane and tile borders, all drawn from loci so that they carry hits"""
     from drprg_amd import synth
-    monkeypatch.setenv("DRPRG_WAVE_FUSE", "1")
-    panel, genomes = _baseline_panel("big")
-    bases, offs = _baseline_reads("big", False, 600_000)
-    ctx = _ctx(tmp_path, panel, 11, 15, True, genome_size=synth.MTB_GENOME_SIZE, kernel=3)
-    cnt = _compare(ctx, oracle, bases, offs, 11, 15, True, 3, threads=ORACLE_THREADS)
-    assert cnt["clusters_kept"] > 50_000 and ctx.counters()["leftover_reads"] == 0
-    ctx.close()
-    rng = np.random.default_rng(23)
-    a = synth.make_locus(rng, 900, site_every=35, nested_frac=0.3, indel_frac=0.2)
-    b = synth.make_locus(rng, 700, site_every=35, nested_frac=0.3, indel_frac=0.2)
-    small = synth.Panel(["a", "a_copy", "b"], [a, a, b])
-    seqs = [synth.sample_haplotype(rng, t).encode() for t in (a, b) for _ in range(4)] + [synth.random_seq(rng, 3000).encode()]
-    parts = [_reads_from(rng, seqs, 6000, 150), _reads_from(rng, seqs, 500, 400), _reads_from(rng, seqs, 60, 2500)]
-    sb = np.concatenate([p[0] for p in parts])
-    so = np.concatenate([np.zeros(1, np.uint64)] + [p[1][1:] + sum(int(q[1][-1]) for q in parts[:i]) for i, p in enumerate(parts)])
-    for illumina in (True, False):
-        ctx = _ctx(tmp_path, small, 11, 15, illumina, kernel=3)
-        _compare(ctx, oracle, sb, so, 11, 15, illumina, 3)
-        ctx.close()
-
-
-@pytest.mark.parametrize("fuse", ["0", pytest.param("1", marks=pytest.mark.experimental)])
-def test_wave_tile_geometry_edges(tmp_path, oracle, monkeypatch, fuse):
-    """sketch_wave_kernel evaluates 61 lanes x 16 positions per tile (976), loads 1024 bases, and a read is clustered in-kernel
-    (DRPRG_WAVE_FUSE=1) only if all its k-mers start inside one tile: reads whose lengths sit on those edges (15, 16, 17, 31,
-    960 ... 1007, 1024, 1952), runs of empty reads (several reads starting at one position), N runs that cross lane and tile
-    borders, all drawn from loci so that they carry hits"""
-    from drprg_amd import synth
-    monkeypatch.setenv("DRPRG_WAVE_FUSE", fuse)
     rng = np.random.default_rng(41)
     loci = [synth.make_locus(rng, 2600, site_every=45, nested_frac=0.2, indel_frac=0.1) for _ in range(3)]
     panel = synth.Panel(["x", "y", "z"], loci)
@@ -862,12 +741,11 @@ def test_deferred_batches_equal_synchronous_ones(tmp_path, oracle, monkeypatch, 
     assert np.array_equal(sums.astype(np.uint32), want)
 
 
-def test_second_stage_inside_the_streaming_kernel(tmp_path, oracle, monkeypatch):
-    """sketch_filter_kernel stages the level-0 survivors in LDS and runs the second-stage filter itself, 64 groups at a time
-    (no refine_kernel, no group records in global memory: the default; DRPRG_FILTER_FORM=refine is the two-kernel form).  Both
-    give the oracle's vector: sparse reads, dense reads whose tiles hold more groups than the stage, reads across slice ends."""
+def test_second_stage_inside_the_streaming_kernel(tmp_path, oracle):
+    """sketch_filter_kernel stages the level-0 survivors in LDS and runs the second-stage filter itself, 64 groups at a time (no group
+    records in global memory).  It gives the oracle's vector: sparse reads, dense reads whose tiles hold more groups than the stage,
+    reads across slice ends."""
     from drprg_amd import synth
-    monkeypatch.setenv("DRPRG_FILTER_FORM", "fused")
     panel = synth.small_panel(seed=6, n_loci=3, length=900)
     rng = np.random.default_rng(5)
     haps = [synth.sample_haplotype(rng, t).encode() for t in panel.trees]
@@ -877,10 +755,6 @@ def test_second_stage_inside_the_streaming_kernel(tmp_path, oracle, monkeypatch)
         ctx = _ctx(tmp_path, panel, 11, 15, True, kernel=2)
         cnt = _compare(ctx, oracle, bases, offs, 11, 15, True, 2)
         assert cnt["clusters_kept"] > 3000
-    if EXPERIMENTAL:  # (the two-kernel form: make EXPERIMENTAL=1)
-        monkeypatch.setenv("DRPRG_FILTER_FORM", "refine")
-        ctx = _ctx(tmp_path, panel, 11, 15, True, kernel=2)
-        _compare(ctx, oracle, sparse[0], sparse[1], 11, 15, True, 2)
 
 
 @pytest.mark.parametrize("sched,grid", [("static", None), ("100,20,4,8", "3")])

@@ -280,12 +280,11 @@ def test_read_ranges_rerun_on_their_own(tmp_path, oracle, monkeypatch, lanes):
 
 
 # ---- 4. direct tile sequence and the generic hit buffer ------------------------------------------------------------------------------
-def _direct_case(tmp_path, oracle, monkeypatch, w, k, read_len=150):
+def _direct_case(tmp_path, oracle, monkeypatch, w, k):
     """The tile slices start at 256 entries whatever the smallest capacity: a context that did not regrow is the same one mapping the
     batch a second time, on the buffers the first pass left"""
     panel = _dense_panel()[0]
-    _, haps, _ = _dense_panel()
-    bases, offs = _dense() if read_len == 150 else _reads_from(np.random.default_rng(read_len), haps, 4000, read_len)
+    bases, offs = _dense()
     n_bases = int(offs[-1])
     ocov, oprg, ocnt = _Oracle.of(oracle, panel.prgs, bases, offs, w, k)
     for packed in (False, True):
@@ -306,15 +305,6 @@ def test_direct_sequence_reruns_a_batch_that_overflowed(tmp_path, oracle, monkey
     """kernel 3 (sketch_wave_kernel's candidate form) on dense reads at its production ratio: the tile slices and the dense list double
     until the batch fits; the aborted attempts count nothing"""
     _direct_case(tmp_path, oracle, monkeypatch, 11, 15)
-
-
-@pytest.mark.experimental
-def test_direct_sequence_rerun_undoes_the_in_kernel_clustering(tmp_path, oracle, monkeypatch):
-    """DRPRG_WAVE_FUSE=1: sketch_wave_kernel adds the coverage of the reads it clusters itself before the host knows the slices overflowed;
-    the undo launch takes exactly that back before the rerun.  (Reads of 600 bases: the 150-base ones lie inside one tile, the kernel
-    clusters them itself and the slices never fill.)"""
-    monkeypatch.setenv("DRPRG_WAVE_FUSE", "1")
-    _direct_case(tmp_path, oracle, monkeypatch, 11, 15, read_len=600)
 
 
 _LDS_CHILD = r"""

@@ -1,6 +1,6 @@
 #!/bin/bash
 # kernel resource usage of one .hip file (gfx950): name, SGPRs, VGPRs, scratch, occupancy, LDS, code size
-# usage: tools/kres.sh drprg_amd/csrc/read_verify.hip [extra hipcc flags]
+# usage: tools/kres.sh drprg_amd/csrc/read_cluster.hip [extra hipcc flags]
 f=$1; shift
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -Iinclude --offload-arch=gfx950 -c "$f" -o /tmp/kres.o -Rpass-analysis=kernel-resource-usage "$@" 2>&1 \
   | grep -E "Function Name|TotalSGPRs|VGPRs:|ScratchSize|Occupancy|LDS Size" \
