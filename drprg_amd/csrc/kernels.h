@@ -180,16 +180,16 @@ struct FilterBuffers {
 // chunk at most); per_wg == 16: static only, one chunk per wave as until round 5.
 constexpr int FT_MAX_ROUNDS = 8;
 struct FilterSched {
-    uint32_t tpw0;       // round 0: tiles per wave of an even split (0: the kernel divides its window itself -- a read range the host has no tile numbers for)
+    uint32_t tpw0;       // round 0: tiles per wave of an even split (0, which the host no longer makes: the kernel divides its window itself)
     uint32_t per_wg;     // chunks = slices per workgroup
     uint32_t n_tiles;    // the tiles the schedule was made for (a dynamic one: the kernel's window must be exactly tiles [0, n_tiles))
     uint32_t first_ticket[FT_MAX_ROUNDS], first_tile[FT_MAX_ROUNDS], size[FT_MAX_ROUNDS]; // [0] unused; first_ticket[r] = 0xFFFFFFFF for r >= n_rounds
     uint32_t n_rounds;
     uint32_t lds_word;   // the workgroup's ticket counter: this word of the kernel's dynamic LDS (set by the launcher; next ticket = 16 + its value)
 };
-// the schedule of one workgroup for n_tiles wave tiles on n_wg workgroups (window_known: the host knows that the window is tiles [0, n_tiles));
+// the schedule of one workgroup for the n_tiles wave tiles of a whole batch on n_wg workgroups;
 // DRPRG_FT_SCHED=static | f,d,m: share of round 0 in 1/256 of the tiles, divisor of the dynamic rounds (x 16), smallest chunk -- measurements
-FilterSched make_filter_sched(uint32_t n_tiles, uint32_t n_wg, bool window_known, const uint32_t share[4]);
+FilterSched make_filter_sched(uint32_t n_tiles, uint32_t n_wg, const uint32_t share[4]);
 // device view of the workspace of one filtered launch sequence (filled by launch_sketch_filter)
 struct FilterWork {
     const uint32_t* bloom;
@@ -200,8 +200,8 @@ struct FilterWork {
     const uint32_t* midc;       // middle tier: split-block Bloom filter of the index k-mer codes (2^midc_wbits blocks of 16 bytes, global memory)
     uint32_t midc_wbits;
     unsigned long long* stat;   // DRPRG_FT_STATS=1 (middle tier): groups tested, past level 0, past the bitmap, candidate positions
-    uint32_t read_begin, read_end; // this launch sequence maps reads [read_begin, read_end) of the batch: the filter kernel
-                             // streams the wave tiles (FT_WPOS positions each) that cover their bases, candidates
+    uint32_t read_begin, read_end; // the reads the launch sequence maps: the whole batch, [0, n_reads) (launch_sketch_filter).  The
+                             // filter kernel streams the wave tiles (FT_WPOS positions each) that cover their bases, candidates
                              // outside [offsets[read_begin], offsets[read_end]) are dropped by verify_scan_kernel
     uint32_t n_slices;       // slices of the candidate buffers (= chunks of the filter kernel's schedule: its workgroups x sched.per_wg)
     // Where a slice lives (round 6: the chunks are not of one size, so neither are their slices): workgroup b's slices share slice_budget
@@ -279,10 +279,8 @@ void init_candidate_work(FilterWork& fw, const FilterBuffers& b, int n_cus);
 // filter -> candidates -> verify -> per-read clustering of the reads that fit read_cluster_kernel (coverage, PRG read
 // counts and the kept-cluster counters are updated); a.n_hits receives the number of hits of the whole batch,
 // rc.n_complex the number of reads left over.  fw is filled for the two follow-up calls.
-// Reads [read_begin, read_end) of the batch only (their bases are located on the device): the host can run several such
-// sequences, each with its own FilterBuffers and scratch counters, on different streams.
-hipError_t launch_sketch_filter(const SketchArgs& a, uint32_t read_begin, uint32_t read_end, const BloomTables& bt, int n_cus,
-    const FilterBuffers& b, const ReadClusterArgs& rc, FilterWork& fw, hipStream_t stream, KernelTimer timer = {});
+hipError_t launch_sketch_filter(const SketchArgs& a, const BloomTables& bt, int n_cus, const FilterBuffers& b, const ReadClusterArgs& rc, FilterWork& fw,
+    hipStream_t stream, KernelTimer timer = {});
 // leftover reads: a.n_hits receives the number of their hits, b.max_len their longest read ...
 hipError_t launch_filter_recount(const SketchArgs& a, const FilterWork& fw, hipStream_t stream);
 // ... and their hits are written to a.hit_key / a.hit_val ordered by (read, position)

@@ -157,8 +157,6 @@ Mapper::Mapper(const FlatIndex& idx, const MapParams& p, int device) : device_(d
     HIPCHK(hipDeviceGetAttribute(&n_cus_, hipDeviceAttributeMultiprocessorCount, device_));
     HIPCHK(hipStreamSynchronize(nullptr)); // every table is on the device before a kernel of a non-blocking stream can ask for it
     set_params(p); // again: the kernel choice depends on the filter being available
-    if (const char* e = std::getenv("DRPRG_HIP_LANES")) max_lanes_ = std::min(4, std::max(1, std::atoi(e)));
-    if (const char* e = std::getenv("DRPRG_HIP_LANES_MIN_BASES")) lanes_min_bases_ = std::strtoull(e, nullptr, 10); // (tests: 0)
     if (const char* e = std::getenv("DRPRG_HIP_MIN_CAPACITY")) // (tests: small batches at the production ratio, or below it to force regrows)
         min_capacity_ = std::max<uint64_t>(MIN_CAPACITY_CLAMP, std::min<uint64_t>(std::strtoull(e, nullptr, 10), 1ull << 30));
     // ONE allocation [coverage | reads per PRG]: the sample's whole additive state is one contiguous u32 vector, so the
@@ -180,7 +178,7 @@ Mapper::~Mapper()
     } catch (...) { // (nothing to report to from a destructor)
     }
     (void)hipDeviceSynchronize();
-    for (Lane& lane : pipe_lanes_) free_lane(lane);
+    for (Lane& lane : lanes_) free_lane(lane);
     if (stream_) (void)hipStreamSynchronize(stream_);
     dfree(d_slot_rec_); dfree(d_slot_first_); dfree(d_rec_knode_); dfree(d_rec_prg_); dfree(d_min_path_len_); dfree(d_prg_thr_);
     if (d_slot_key_) (void)hipFree(d_slot_key_);
@@ -193,7 +191,6 @@ Mapper::~Mapper()
     if (d_temp_) (void)hipFree(d_temp_);
     for (TileSet& t : tsets_) free_tile_set(t);
     dfree(d_bases_); dfree(d_offsets_); dfree(d_bloom_); dfree(d_bloom0_); dfree(d_bloom0f_); dfree(d_bloomr_); dfree(d_pbloom_); dfree(d_mid0_); dfree(d_mid_bitmap_); dfree(d_midc_); dfree(d_blkc_); dfree(d_ft_stat_);
-    for (Lane& lane : lanes_) free_lane(lane);
     for (Stage& st : stage_) {
         dfree(st.d_bases); dfree(st.d_offsets); dfree(st.d_npos);
         if (st.copied) (void)hipEventDestroy(st.copied);
@@ -202,7 +199,6 @@ Mapper::~Mapper()
     for (auto& a : kept_arenas_) (void)hipFree(a.first);
     if (kept_copied_) (void)hipEventDestroy(kept_copied_);
     if (copy_stream_) (void)hipStreamDestroy(copy_stream_);
-    if (ev_begin_) (void)hipEventDestroy(ev_begin_);
     if (h_counters_) (void)hipHostFree(h_counters_);
     if (h_bases_) (void)hipHostFree(h_bases_);
     if (h_offsets_) (void)hipHostFree(h_offsets_);
@@ -337,7 +333,6 @@ void Mapper::free_lane(Lane& lane)
     if (lane.h_scratch) (void)hipHostFree(lane.h_scratch);
     lane.h_scratch = nullptr;
     lane.h_scratch_dev = nullptr;
-    if (lane.stream) (void)hipStreamDestroy(lane.stream);
     for (hipEvent_t* e : { &lane.done, &lane.t0, &lane.t1 })
         if (*e) (void)hipEventDestroy(*e);
     lane = Lane();
@@ -346,7 +341,7 @@ void Mapper::free_lane(Lane& lane)
 void Mapper::grow_lane(Lane& lane, uint64_t cap)
 {
     if (cap <= lane.raw_capacity) return;
-    if (cap >= (1ull << 31)) throw Error(DRPRG_EOVERFLOW, "more than 2^31 candidate k-mers in one read range; map smaller batches");
+    if (cap >= (1ull << 31)) throw Error(DRPRG_EOVERFLOW, "more than 2^31 candidate k-mers in one batch; map smaller batches");
     dfree(lane.raw_pos); dfree(lane.cand_info); dfree(lane.cand_pos1); dfree(lane.cand_rec);
     lane.raw_capacity = cap;
     dmalloc(lane.raw_pos, cap); dmalloc(lane.cand_info, cap); dmalloc(lane.cand_pos1, cap); dmalloc(lane.cand_rec, cap);
@@ -355,13 +350,11 @@ void Mapper::grow_lane(Lane& lane, uint64_t cap)
     zero_now(lane.cand_pos1, 0, cap * sizeof(uint32_t));
 }
 
-void Mapper::ensure_lanes(int n, uint64_t cap)
+// Both lanes' events, counters and their pinned mirror; the candidate buffers grow with the batches (grow_lane).
+void Mapper::ensure_lanes()
 {
-    if (!ev_begin_) HIPCHK(hipEventCreateWithFlags(&ev_begin_, hipEventDisableTiming));
-    while ((int)lanes_.size() < n) {
-        lanes_.emplace_back();
-        Lane& lane = lanes_.back();
-        if (lanes_.size() > 1) HIPCHK(hipStreamCreateWithFlags(&lane.stream, hipStreamNonBlocking));
+    for (Lane& lane : lanes_) {
+        if (lane.h_scratch_dev) continue; // (the last thing a lane gets)
         HIPCHK(hipEventCreateWithFlags(&lane.done, hipEventDisableTiming));
         HIPCHK(hipEventCreate(&lane.t0));
         HIPCHK(hipEventCreate(&lane.t1));
@@ -371,19 +364,47 @@ void Mapper::ensure_lanes(int n, uint64_t cap)
         HIPCHK(hipHostMalloc((void**)&lane.h_scratch, L_N * sizeof(unsigned long long), hipHostMallocDefault));
         zero_now(lane.d_scratch, 0, L_N * sizeof(unsigned long long));
         lane.scratch_zero = true;
+        HIPCHK(hipHostGetDevicePointer((void**)&lane.h_scratch_dev, lane.h_scratch, 0));
     }
-    for (int j = 0; j < n; ++j) grow_lane(lanes_[j], cap);
 }
 
-// One filtered sequence for reads [lane.r0, lane.r1) of the batch, asynchronous on `stream`: kernels, then the lane's
-// counters to its pinned mirror, then the counters cleared again behind the copy (so that the next batch starts with its
-// first kernel instead of a memset).
-void Mapper::launch_lane(Lane& lane, hipStream_t stream, const uint8_t* d_bases, const uint64_t* d_offsets, uint32_t n_reads,
-    uint64_t n_bases, uint32_t* covg, uint32_t* prg_reads, const PackedInfo* pk)
+Mapper::Batch Mapper::make_batch(int lane, const uint8_t* d_bases, const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases, uint32_t* covg,
+    uint32_t* prg_reads, hipStream_t stream, const PackedInfo* pk) const
 {
-    if (!lane.scratch_zero) HIPCHK(hipMemsetAsync(lane.d_scratch, 0, L_N * sizeof(unsigned long long), stream));
+    Batch b;
+    b.active = true;
+    b.direct = !use_filter_; // (the callers run only the two candidate sequences)
+    b.lane = lane;
+    b.d_bases = d_bases;
+    b.d_offsets = d_offsets;
+    b.n_reads = (uint32_t)n_reads;
+    b.n_bases = n_bases;
+    b.covg = covg;
+    b.prg_reads = prg_reads;
+    b.stream = stream;
+    b.packed = pk != nullptr; // (the batch's own description: a re-run or its leftover reads see the format it came in)
+    if (pk) b.pk = *pk;
+    return b;
+}
+
+void Mapper::launch(const Batch& b)
+{
+    ensure_lanes();
+    if (b.direct) direct_launch(b);
+    else filter_launch(b);
+    HIPCHK(hipEventRecord(lanes_[b.lane].done, b.stream));
+}
+
+// One filtered sequence, asynchronous on the batch's stream: kernels, then the lane's counters to its pinned mirror, then the counters
+// cleared again behind the copy (so that the next batch starts with its first kernel instead of a memset).
+void Mapper::filter_launch(const Batch& b)
+{
+    Lane& lane = lanes_[b.lane];
+    // (a deferred batch: this lane's previous batch was completed by the call before this one; growing frees its buffers, which waits for the device)
+    grow_lane(lane, std::max<uint64_t>(min_capacity_, b.n_bases / FILTER_BASES_PER_ENTRY));
+    if (!lane.scratch_zero) HIPCHK(hipMemsetAsync(lane.d_scratch, 0, L_N * sizeof(unsigned long long), b.stream));
     lane.scratch_zero = false;
-    dev::SketchArgs a = sketch_args(d_bases, d_offsets, n_reads, n_bases, pk);
+    dev::SketchArgs a = sketch_args(b.d_bases, b.d_offsets, b.n_reads, b.n_bases, b.pkp());
     a.n_hits = &lane.d_scratch[L_HITS];
     a.n_minimizers = &lane.d_scratch[L_MINIMIZERS];
     a.overflow = reinterpret_cast<uint32_t*>(&lane.d_scratch[L_OVERFLOW]);
@@ -392,8 +413,7 @@ void Mapper::launch_lane(Lane& lane, hipStream_t stream, const uint8_t* d_bases,
     {
         static const bool adapt = [] { const char* e = std::getenv("DRPRG_FT_ADAPT"); return !e || std::atoi(e) != 0; }();
         ft_adapt_ = adapt;
-        const int pi = pk ? 1 : 0;
-        lane.ft_packed = pi != 0;
+        const int pi = b.packed ? 1 : 0;
         if (adapt) {
             fb.class_clock = &lane.d_scratch[L_FT_CLOCK];
             if (ft_share_[pi][0]) fb.wave_share = ft_share_[pi];
@@ -415,8 +435,8 @@ void Mapper::launch_lane(Lane& lane, hipStream_t stream, const uint8_t* d_bases,
     rc.min_cluster_size = params_.min_cluster_size;
     rc.max_diff = params_.max_diff;
     rc.n_prgs = n_prgs_;
-    rc.covg = covg;
-    rc.prg_reads = prg_reads;
+    rc.covg = b.covg;
+    rc.prg_reads = b.prg_reads;
     rc.n_clusters_kept = &d_counters_[C_CLUSTERS_KEPT];
     rc.n_hits_kept = &d_counters_[C_HITS_KEPT];
     rc.n_complex = &lane.d_scratch[L_COMPLEX];
@@ -426,29 +446,28 @@ void Mapper::launch_lane(Lane& lane, hipStream_t stream, const uint8_t* d_bases,
         timer.begin = lane.t0;
         timer.end = lane.t1;
     }
-    HIPCHK(dev::launch_sketch_filter(a, lane.r0, lane.r1, bt, n_cus_, fb, rc, lane.fw, stream, timer));
+    HIPCHK(dev::launch_sketch_filter(a, bt, n_cus_, fb, rc, lane.fw, b.stream, timer));
     // the counters to the pinned mirror and zero again behind it: one small kernel (rounds 1-4: a copy and two memsets)
-    if (!lane.h_scratch_dev) HIPCHK(hipHostGetDevicePointer((void**)&lane.h_scratch_dev, lane.h_scratch, 0));
-    HIPCHK(dev::launch_counters_home(lane.d_scratch, lane.h_scratch_dev, L_N, stream, dev::filter_super_counts(lane.small), dev::filter_super_words()));
+    HIPCHK(dev::launch_counters_home(lane.d_scratch, lane.h_scratch_dev, L_N, b.stream, dev::filter_super_counts(lane.small), dev::filter_super_words()));
     lane.scratch_zero = true;
 }
 
-// The wait polls the stream for a short while first: an interrupt-driven hipStreamSynchronize wakes up tens of microseconds late,
-// which is visible at 0.7 ms per batch.  Only for a short while (~2 ms of polls): a longer batch does not notice the late wake-up,
-// and a host core that spins for it is a core the FASTQ parser threads (or the other ranks of a node) do not have.
-// DRPRG_HIP_SPIN=0: never poll.
-void Mapper::wait_stream(hipStream_t stream)
+// Waits for `event` (recorded on `stream`), or -- event null -- for everything queued on `stream`.  The wait polls for a short while first:
+// an interrupt-driven synchronise wakes up tens of microseconds late, which is visible at 0.7 ms per batch.  Only for a short while (~2 ms
+// of polls): a longer batch does not notice the late wake-up, and a host core that spins for it is a core the FASTQ parser threads (or the
+// other ranks of a node) do not have.  DRPRG_HIP_SPIN=0: never poll.
+static void wait_stream(hipStream_t stream, hipEvent_t event = nullptr)
 {
     static const bool spin = [] {
         const char* e = std::getenv("DRPRG_HIP_SPIN");
         return !(e && std::atoi(e) == 0);
     }();
     for (int spins = 0; spin && spins < 2048; ++spins) {
-        const hipError_t e = hipStreamQuery(stream);
+        const hipError_t e = event ? hipEventQuery(event) : hipStreamQuery(stream);
         if (e == hipSuccess) return;
         if (e != hipErrorNotReady) HIPCHK(e);
     }
-    HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(event ? hipEventSynchronize(event) : hipStreamSynchronize(stream));
 }
 
 // hits in d_key_a_/d_val_a_ -> clusters -> coverage (the generic pipeline).  ordered: the hits are ordered by
@@ -540,21 +559,22 @@ void Mapper::read_counters(hipStream_t stream)
     wait_stream(stream);
 }
 
-void Mapper::note_kernel_time()
+void Mapper::note_kernel_time(hipEvent_t t0, hipEvent_t t1)
 {
     if (!timing_) return;
     float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, ev0_, ev1_));
+    HIPCHK(hipEventElapsedTime(&ms, t0, t1));
     sketch_ms_ += ms;
     sketch_launches_ += 1;
 }
 
-// The reads read_cluster_kernel left over in this lane's candidate list: their hits -> the generic cluster pipeline.
-void Mapper::leftovers(Lane& lane, const uint8_t* d_bases, const uint64_t* d_offsets, uint32_t n_reads, uint64_t n_bases, uint32_t* covg,
-    uint32_t* prg_reads, hipStream_t stream, const PackedInfo* pk)
+// The reads read_cluster_kernel left over in the batch's candidate list: their hits -> the generic cluster pipeline.
+void Mapper::leftovers(const Batch& b)
 {
+    Lane& lane = lanes_[b.lane];
     if (lane.h_scratch[L_COMPLEX] == 0) return;
-    dev::SketchArgs a = sketch_args(d_bases, d_offsets, n_reads, n_bases, pk);
+    const hipStream_t stream = b.stream;
+    dev::SketchArgs a = sketch_args(b.d_bases, b.d_offsets, b.n_reads, b.n_bases, b.pkp());
     a.n_hits = &lane.d_scratch[L_HITS];
     a.n_minimizers = &lane.d_scratch[L_MINIMIZERS]; // (the recount pass does not count minimizers again)
     a.overflow = reinterpret_cast<uint32_t*>(&lane.d_scratch[L_OVERFLOW]);
@@ -569,7 +589,7 @@ void Mapper::leftovers(Lane& lane, const uint8_t* d_bases, const uint64_t* d_off
     a.hit_val = d_val_a_;
     a.hit_capacity = hit_capacity_;
     HIPCHK(dev::launch_filter_expand(a, lane.fw, stream));
-    cluster_hits(d_offsets, (uint32_t)n_left, lane.h_scratch[L_MAXLEN] <= READ_SORT_MAX_LEN, &lane.d_scratch[L_UNSORTED], covg, prg_reads, stream);
+    cluster_hits(b.d_offsets, (uint32_t)n_left, lane.h_scratch[L_MAXLEN] <= READ_SORT_MAX_LEN, &lane.d_scratch[L_UNSORTED], b.covg, b.prg_reads, stream);
 }
 
 void Mapper::free_tile_set(TileSet& t)
@@ -580,8 +600,6 @@ void Mapper::free_tile_set(TileSet& t)
     dfree(t.d_tile_rec); dfree(t.d_tile_first);
     if (t.d_tile_temp) (void)hipFree(t.d_tile_temp);
     t.d_tile_temp = nullptr;
-    for (hipEvent_t* e : { &t.done, &t.t0, &t.t1 })
-        if (*e) (void)hipEventDestroy(*e);
     t = TileSet();
 }
 
@@ -604,9 +622,13 @@ void Mapper::ensure_tile_workspace(TileSet& t, uint32_t n_tiles, uint32_t tile_c
 // as candidate records in position order, a scan orders the slices and read_cluster_kernel takes the candidates from them -- no hit
 // list, no radix sort, no cluster kernels for the reads that fit it.
 // One attempt, asynchronous on `stream`: the launches, the lane's counters to their pinned mirror, the counters cleared behind the copy.
-void Mapper::direct_launch(int set, const uint8_t* d_bases, const uint64_t* d_offsets, uint32_t n_reads, uint64_t n_bases, uint32_t* covg,
-    uint32_t* prg_reads, hipStream_t stream, bool timed_by_set_events, const PackedInfo* pk)
+void Mapper::direct_launch(const Batch& b)
 {
+    const int set = b.lane;
+    const uint8_t* const d_bases = b.d_bases;
+    const uint64_t n_bases = b.n_bases;
+    const hipStream_t stream = b.stream;
+    const PackedInfo* const pk = b.pkp();
     TileSet& t = tsets_[set];
     ts_ = &t;
     const uint32_t n_tiles = dev::direct_candidate_tiles(n_bases, halo_, params_.k, params_.w, wide_hash_); // = slices
@@ -616,8 +638,7 @@ void Mapper::direct_launch(int set, const uint8_t* d_bases, const uint64_t* d_of
         t.first_cap = n_first + n_first / 4 + 16;
         dmalloc(t.d_tile_first, (size_t)t.first_cap);
     }
-    ensure_lanes(set + 1, 0); // (the lanes exist; only this set's lane may grow: the other one may belong to a batch in flight)
-    Lane& lane = lanes_[(size_t)set];
+    Lane& lane = lanes_[set]; // (only this set's lane may grow: the other one may belong to a batch in flight)
     grow_lane(lane, std::min<uint64_t>(std::max<uint64_t>(min_capacity_, n_bases / 16), (1ull << 31) - 1));
     // read_cluster_kernel takes the candidates straight from the tile slices (no gathered list unless reads are left over); what it
     // handled is marked in the dense cand_pos1 array with a value no other batch used (the gather-first sequence of rounds 1-3 lost to
@@ -638,7 +659,7 @@ void Mapper::direct_launch(int set, const uint8_t* d_bases, const uint64_t* d_of
     // a packed batch: sketch_wave_kernel reads the words themselves (round 4; the positions of its npos as one bit per base, set here);
     // the general direct kernel reads an ASCII expansion made on the same stream (packed.hip)
     const bool native_packed = pk != nullptr && dev::direct_uses_wave_form(params_.k, params_.w, wide_hash_);
-    dev::SketchArgs a = sketch_args(native_packed ? d_bases : ascii_view(set, d_bases, n_bases, stream, pk), d_offsets, n_reads, n_bases, native_packed ? pk : nullptr);
+    dev::SketchArgs a = sketch_args(native_packed ? d_bases : ascii_view(set, d_bases, n_bases, stream, pk), b.d_offsets, b.n_reads, n_bases, native_packed ? pk : nullptr);
     if (native_packed && a.n_npos) {
         const uint64_t words16 = ((n_bases + 15) / 16 + 1) & ~1ull; // (an even number of u16 words: the marks are 32-bit atomics)
         if (words16 > t.nbits_cap) {
@@ -674,27 +695,20 @@ void Mapper::direct_launch(int set, const uint8_t* d_bases, const uint64_t* d_of
     rc.min_cluster_size = params_.min_cluster_size;
     rc.max_diff = params_.max_diff;
     rc.n_prgs = n_prgs_;
-    rc.covg = covg;
-    rc.prg_reads = prg_reads;
+    rc.covg = b.covg;
+    rc.prg_reads = b.prg_reads;
     rc.n_clusters_kept = &d_counters_[C_CLUSTERS_KEPT];
     rc.n_hits_kept = &d_counters_[C_HITS_KEPT];
     rc.n_complex = &lane.d_scratch[L_COMPLEX];
     rc.chunk_counter = reinterpret_cast<uint32_t*>(&lane.d_scratch[L_CHUNK]);
     lane.fw = dev::FilterWork {};
     lane.fw.read_begin = 0;
-    lane.fw.read_end = n_reads;
+    lane.fw.read_end = b.n_reads;
     dev::init_candidate_work(lane.fw, fb, n_cus_);
     dev::KernelTimer timer;
     if (timing_) {
-        if (timed_by_set_events) {
-            if (!t.t0) HIPCHK(hipEventCreate(&t.t0));
-            if (!t.t1) HIPCHK(hipEventCreate(&t.t1));
-            timer.begin = t.t0;
-            timer.end = t.t1;
-        } else {
-            timer.begin = ev0_;
-            timer.end = ev1_;
-        }
+        timer.begin = lane.t0;
+        timer.end = lane.t1;
     }
     HIPCHK(dev::launch_direct_candidates(a, wide_hash_, t.d_tile_prefix, t.d_tile_temp, t.tile_temp_bytes, lane.raw_capacity, rc, n_cus_, lane.fw,
         stream, timer, mark));
@@ -708,18 +722,17 @@ void Mapper::direct_launch(int set, const uint8_t* d_bases, const uint64_t* d_of
 
 // The read-back of such an attempt has arrived.  false: a tile slice or the dense list was too small -- nothing was counted except the
 // minimizers, and those only in this attempt's scratch block --, the buffers have been grown and the caller runs the batch again.
-// true: totals taken, reads left to the generic pipeline queued on `stream`.
-bool Mapper::direct_finish(int set, const uint8_t* d_bases, const uint64_t* d_offsets, uint32_t n_reads, uint64_t n_bases, uint32_t* covg,
-    uint32_t* prg_reads, hipStream_t stream, int attempt, const PackedInfo* pk)
+// true: totals taken, reads left to the generic pipeline queued on the batch's stream.
+bool Mapper::direct_finish(const Batch& b, int attempt)
 {
-    TileSet& t = tsets_[set];
+    TileSet& t = tsets_[b.lane];
     ts_ = &t;
-    Lane& lane = lanes_[(size_t)set];
+    Lane& lane = lanes_[b.lane];
     const uint32_t ovf = (uint32_t)lane.h_scratch[L_OVERFLOW];
     if (ovf & 2u) throw Error(DRPRG_EOVERFLOW, "a read is longer than 2^" + std::to_string(dev::HIT_POS_BITS) + " bases");
     if (ovf & 4u) {
         if (attempt > 6) throw Error(DRPRG_EOVERFLOW, "candidate buffer overflow after regrow");
-        HIPCHK(hipStreamSynchronize(stream)); // (the buffers are about to be freed)
+        HIPCHK(hipStreamSynchronize(b.stream)); // (the buffers are about to be freed)
         ++reruns_direct_;
         t.slice_cap = std::min<uint32_t>(t.slice_cap * 2, 4096);
         grow_lane(lane, std::min<uint64_t>(lane.raw_capacity * 2, (1ull << 31) - 1));
@@ -729,52 +742,37 @@ bool Mapper::direct_finish(int set, const uint8_t* d_bases, const uint64_t* d_of
     tot_hits_ += lane.h_scratch[L_HITS];
     tot_leftover_ += lane.h_scratch[L_COMPLEX];
     if (lane.h_scratch[L_COMPLEX]) // reads were left over: the generic pipeline wants the gathered list after all
-        HIPCHK(dev::launch_tile_gather_marked(t.a_done, lane.fw, t.d_tile_prefix, t.n_tiles, lane.raw_capacity, t.mark, stream));
-    leftovers(lane, d_bases, d_offsets, n_reads, n_bases, covg, prg_reads, stream, pk);
+        HIPCHK(dev::launch_tile_gather_marked(t.a_done, lane.fw, t.d_tile_prefix, t.n_tiles, lane.raw_capacity, t.mark, b.stream));
+    leftovers(b);
     return true;
 }
 
-void Mapper::run_batch_direct_candidates(const uint8_t* d_bases, const uint64_t* d_offsets, uint32_t n_reads, uint64_t n_bases,
-    uint32_t* covg, uint32_t* prg_reads, hipStream_t stream, const PackedInfo* pk)
+// The same for the filtered sequence: a candidate slice that was too small -> false, the lane grown; else the totals, and the reads
+// read_cluster_kernel left over -> the generic pipeline on their hits.
+bool Mapper::filter_finish(const Batch& b, int attempt)
 {
-    for (int attempt = 0;; ++attempt) {
-        direct_launch(0, d_bases, d_offsets, n_reads, n_bases, covg, prg_reads, stream, false, pk);
-        wait_stream(stream);
-        note_kernel_time();
-        if (direct_finish(0, d_bases, d_offsets, n_reads, n_bases, covg, prg_reads, stream, attempt, pk)) break;
-    }
-}
-
-// What the host does with a lane's read-back once its sequence has finished: a candidate slice that was too small -> the range
-// again with larger buffers; the totals; the reads read_cluster_kernel left over -> the generic pipeline on their hits.
-void Mapper::finish_lane(Lane& lane, const uint8_t* d_bases, const uint64_t* d_offsets, uint32_t n_reads, uint64_t n_bases, uint32_t* covg,
-    uint32_t* prg_reads, hipStream_t stream, const PackedInfo* pk)
-{
-    for (int attempt = 0;; ++attempt) {
-        const uint32_t ovf = (uint32_t)lane.h_scratch[L_OVERFLOW];
-        if (ovf & 8u) throw Error(DRPRG_EIO, "sketch_filter_kernel: dynamic LDS does not start at address 0");
-        if (ovf & 16u) throw Error(DRPRG_EIO, "sketch_filter_kernel: a chunk of its schedule holds too few whole tiles");
-        if (ovf & 32u) throw Error(DRPRG_EINVAL, "the batch's read offsets do not span its bases: offsets[0] must be 0 and offsets[n_reads] must be n_bases");
-        if (ovf & 2u) throw Error(DRPRG_EOVERFLOW, "a read is longer than 2^" + std::to_string(dev::HIT_POS_BITS) + " bases");
-        if (!(ovf & 4u)) break;
-        // a candidate slice of this range was too small: its sequence counted nothing and touched no coverage
-        // (hit_scan_kernel / read_cluster_kernel check the flag); grow the lane and run the range again, alone
+    Lane& lane = lanes_[b.lane];
+    const uint32_t ovf = (uint32_t)lane.h_scratch[L_OVERFLOW];
+    if (ovf & 8u) throw Error(DRPRG_EIO, "sketch_filter_kernel: dynamic LDS does not start at address 0");
+    if (ovf & 16u) throw Error(DRPRG_EIO, "sketch_filter_kernel: a chunk of its schedule holds too few whole tiles");
+    if (ovf & 32u) throw Error(DRPRG_EINVAL, "the batch's read offsets do not span its bases: offsets[0] must be 0 and offsets[n_reads] must be n_bases");
+    if (ovf & 2u) throw Error(DRPRG_EOVERFLOW, "a read is longer than 2^" + std::to_string(dev::HIT_POS_BITS) + " bases");
+    if (ovf & 4u) {
+        // a candidate slice was too small: the sequence counted nothing and touched no coverage (hit_scan_kernel / read_cluster_kernel
+        // check the flag)
         if (attempt > 8) throw Error(DRPRG_EOVERFLOW, "candidate buffer overflow after regrow");
         grow_lane(lane, lane.raw_capacity * 4);
         ++reruns_filter_;
-        launch_lane(lane, stream, d_bases, d_offsets, n_reads, n_bases, covg, prg_reads, pk);
-        wait_stream(stream);
+        return false;
     }
     tot_minimizers_ += lane.h_scratch[L_MINIMIZERS];
     tot_hits_ += lane.h_scratch[L_HITS];
     tot_leftover_ += lane.h_scratch[L_COMPLEX];
-    tune_filter_shares(lane, lane.ft_packed, n_bases);
-    leftovers(lane, d_bases, d_offsets, n_reads, n_bases, covg, prg_reads, stream, pk);
+    tune_filter_shares(lane, b.packed, b.n_bases);
+    leftovers(b);
+    return true;
 }
 
-// sketch_filter_kernel's four wave classes should end together (sketch_filter.hip: a SIMD issues for its oldest wave first).  How far apart they
-// ended in the batch just read back moves the next batch's shares: share_c *= (mean end / end_c)^0.6, every share kept within 0.35 .. 2.2 of an
-// even one, the sum at 1024.  Any shares give the same candidates; batches too small to time (under 64 M bases) change nothing.
 void Mapper::filter_schedule(uint64_t out[20])
 {
     sync();
@@ -785,8 +783,7 @@ void Mapper::buffer_info(uint64_t out[6])
 {
     sync(); // (a deferred batch that overflowed is run again when it is completed)
     uint64_t raw = 0;
-    for (const std::vector<Lane>* v : { &lanes_, &pipe_lanes_ })
-        for (const Lane& lane : *v) raw = std::max(raw, lane.raw_capacity);
+    for (const Lane& lane : lanes_) raw = std::max(raw, lane.raw_capacity);
     out[0] = reruns_filter_;
     out[1] = reruns_direct_;
     out[2] = regrows_hits_;
@@ -795,6 +792,9 @@ void Mapper::buffer_info(uint64_t out[6])
     out[5] = 0;
 }
 
+// sketch_filter_kernel's four wave classes should end together (sketch_filter.hip: a SIMD issues for its oldest wave first).  How far apart they
+// ended in the batch just read back moves the next batch's shares: share_c *= (mean end / end_c)^0.6, every share kept within 0.35 .. 2.2 of an
+// even one, the sum at 1024.  Any shares give the same candidates; batches too small to time (under 64 M bases) change nothing.
 void Mapper::tune_filter_shares(const Lane& lane, bool packed, uint64_t n_bases)
 {
     {   // what the batch just completed ran with (whatever its size)
@@ -817,7 +817,6 @@ void Mapper::tune_filter_shares(const Lane& lane, bool packed, uint64_t n_bases)
     }
     if (lane.fw.sched.n_rounds > 1) return; // a dynamic schedule balances itself: the shares of round 0 stay what they are
     if (!ft_adapt_ || n_bases < (64ull << 20)) return;
-    if (max_lanes_ > 1) return; // (read ranges on concurrent streams: the classes' clocks measure the overlap, not the shares -- ADVICE r05)
     const unsigned long long* ck = &lane.h_scratch[L_FT_CLOCK];
     if (!ck[0] || !ck[1] || !ck[2] || !ck[3] || !ck[4]) return; // (a launch without the level-0 form, or with DRPRG_FT_SHARE)
     const unsigned long long t0 = ~ck[0];
@@ -856,9 +855,7 @@ void Mapper::map_device_async_impl(const uint8_t* d_bases, const uint64_t* d_off
     uint32_t* prg_reads, hipStream_t stream, const PackedInfo* pk)
 {
     if (n_reads == 0) return;
-    const bool deferred_filter = use_filter_ && max_lanes_ == 1;
-    const bool deferred_direct = !use_filter_ && use_direct_cands_;
-    if ((!deferred_filter && !deferred_direct) || n_bases == 0) { // (no deferred form of the other sequences: the batch is complete on return,
+    if ((!use_filter_ && !use_direct_cands_) || n_bases == 0) { // (no deferred form of the other sequences: the batch is complete on return,
         map_device_impl(d_bases, d_offsets, n_reads, n_bases, covg, prg_reads, stream, pk); // including what its tail queued for the leftover reads)
         HIPCHK(hipSetDevice(device_));
         wait_stream(stream ? stream : stream_);
@@ -870,76 +867,14 @@ void Mapper::map_device_async_impl(const uint8_t* d_bases, const uint64_t* d_off
         throw Error(DRPRG_EOVERFLOW, "at most " + std::to_string(dev::MAX_BATCH_READS) + " reads per batch");
     HIPCHK(hipSetDevice(device_));
     if (kept_cap_ && !in_keep_call_) kept_broken_ = true;
-    if (!stream) stream = stream_;
-    if (!covg) covg = d_covg_;
-    if (!prg_reads) prg_reads = d_prg_reads_;
-    if (deferred_direct) {
-        // the direct sequence in its candidate form, deferred the same way: two sets of the tile workspace taken in turn, the batch's
-        // read-back looked at while the next batch runs (a batch whose slices overflowed, or that left reads to the generic pipeline,
-        // is finished then -- from its own set, which the batch in flight does not touch)
-        const int set = pipe_next_;
-        direct_launch(set, d_bases, d_offsets, (uint32_t)n_reads, n_bases, covg, prg_reads, stream, true, pk);
-        TileSet& t = tsets_[set];
-        if (!t.done) HIPCHK(hipEventCreateWithFlags(&t.done, hipEventDisableTiming));
-        HIPCHK(hipEventRecord(t.done, stream));
-        Pending cur;
-        cur.active = true;
-        cur.direct = true;
-        cur.lane = set;
-        cur.packed = pk != nullptr;
-        if (pk) cur.pk = *pk;
-        cur.d_bases = d_bases;
-        cur.d_offsets = d_offsets;
-        cur.n_reads = (uint32_t)n_reads;
-        cur.n_bases = n_bases;
-        cur.covg = covg;
-        cur.prg_reads = prg_reads;
-        cur.stream = stream;
-        const Pending prev = pending_;
-        pending_ = cur;
-        pipe_next_ ^= 1;
-        tot_reads_ += n_reads;
-        tot_bases_ += n_bases;
-        if (prev.active) complete_batch(prev);
-        return;
-    }
-    if (pipe_lanes_.empty()) {
-        for (int j = 0; j < 2; ++j) {
-            pipe_lanes_.emplace_back();
-            Lane& lane = pipe_lanes_.back();
-            HIPCHK(hipEventCreateWithFlags(&lane.done, hipEventDisableTiming));
-            HIPCHK(hipEventCreate(&lane.t0));
-            HIPCHK(hipEventCreate(&lane.t1));
-            dmalloc(lane.small, dev::filter_small_words());
-            zero_now(lane.small, 0, dev::filter_small_words() * sizeof(uint32_t));
-            dmalloc(lane.d_scratch, (size_t)L_N);
-            HIPCHK(hipHostMalloc((void**)&lane.h_scratch, L_N * sizeof(unsigned long long), hipHostMallocDefault));
-            zero_now(lane.d_scratch, 0, L_N * sizeof(unsigned long long));
-            lane.scratch_zero = true;
-        }
-    }
-    Lane& lane = pipe_lanes_[(size_t)pipe_next_];
-    // (this lane's previous batch was completed by the call before this one; growing frees its buffers, which waits for the device)
-    grow_lane(lane, std::max<uint64_t>(min_capacity_, n_bases / FILTER_BASES_PER_ENTRY));
-    lane.r0 = 0;
-    lane.r1 = (uint32_t)n_reads;
-    launch_lane(lane, stream, d_bases, d_offsets, (uint32_t)n_reads, n_bases, covg, prg_reads, pk);
-    HIPCHK(hipEventRecord(lane.done, stream));
-    Pending cur;
-    cur.active = true;
-    cur.lane = pipe_next_;
-    cur.packed = pk != nullptr;
-    if (pk) cur.pk = *pk;
-    cur.d_bases = d_bases;
-    cur.d_offsets = d_offsets;
-    cur.n_reads = (uint32_t)n_reads;
-    cur.n_bases = n_bases;
-    cur.covg = covg;
-    cur.prg_reads = prg_reads;
-    cur.stream = stream;
+    // the two lanes take the batches in turn: a batch's read-back is looked at while the next batch runs (a batch whose candidate buffers
+    // overflowed, or that left reads to the generic pipeline, is finished then -- from its own lane, which the batch in flight does not touch)
+    const Batch cur = make_batch(pipe_next_, d_bases, d_offsets, n_reads, n_bases, covg ? covg : d_covg_, prg_reads ? prg_reads : d_prg_reads_,
+        stream ? stream : stream_, pk);
+    launch(cur);
     // the batch just queued is registered before the previous one is completed: if completing that one throws (a read too long,
     // an overflow that does not go away, a HIP error) the queued batch is still known to sync() and to the next call
-    const Pending prev = pending_;
+    const Batch prev = pending_;
     pending_ = cur;
     pipe_next_ ^= 1;
     tot_reads_ += n_reads;
@@ -950,71 +885,29 @@ void Mapper::map_device_async_impl(const uint8_t* d_bases, const uint64_t* d_off
 void Mapper::complete_pending()
 {
     if (!pending_.active) return;
-    const Pending p = pending_;
+    const Batch b = pending_;
     pending_.active = false;
-    complete_batch(p);
+    complete_batch(b);
 }
 
-void Mapper::complete_batch(const Pending& p)
+// The batch's first attempt has been launched.  Wait for its read-back, then finish -> (buffers grown) launch again -> wait ... until it
+// fit.  Only the first attempt's kernel time is counted (sketch_ms_total).  A batch that needed the host afterwards (run again, reads left
+// to the generic pipeline) has just had more work queued for its accumulators: "completed" means that work is done too -- the caller may
+// touch the buffers of a completed batch from any stream.
+void Mapper::complete_batch(const Batch& b)
 {
     HIPCHK(hipSetDevice(device_));
-    const PackedInfo* const ppk = p.packed ? &p.pk : nullptr; // (the batch's own description: a re-run or its leftover reads see the format it came in)
-    if (p.direct) {
-        TileSet& t = tsets_[p.lane];
-        static const bool spin_d = [] {
-            const char* e = std::getenv("DRPRG_HIP_SPIN");
-            return !(e && std::atoi(e) == 0);
-        }();
-        bool ready = false;
-        for (int spins = 0; spin_d && spins < 2048 && !ready; ++spins) {
-            const hipError_t e = hipEventQuery(t.done);
-            if (e == hipSuccess) ready = true;
-            else if (e != hipErrorNotReady) HIPCHK(e);
-        }
-        if (!ready) HIPCHK(hipEventSynchronize(t.done));
-        if (timing_ && t.t0 && t.t1) {
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, t.t0, t.t1) == hipSuccess) {
-                sketch_ms_ += ms;
-                sketch_launches_ += 1;
-            }
-        }
-        const uint64_t leftover_before = tot_leftover_;
-        bool reran = false;
-        for (int attempt = 0; !direct_finish(p.lane, p.d_bases, p.d_offsets, p.n_reads, p.n_bases, p.covg, p.prg_reads, p.stream, attempt, ppk); ++attempt) {
-            // its slices were too small: nothing of it was counted; again, alone, behind whatever is queued on its stream
-            direct_launch(p.lane, p.d_bases, p.d_offsets, p.n_reads, p.n_bases, p.covg, p.prg_reads, p.stream, false, ppk);
-            wait_stream(p.stream);
-            reran = true;
-        }
-        if (reran || tot_leftover_ != leftover_before) wait_stream(p.stream);
-        return;
-    }
-    Lane& lane = pipe_lanes_[(size_t)p.lane];
-    static const bool spin = [] {
-        const char* e = std::getenv("DRPRG_HIP_SPIN");
-        return !(e && std::atoi(e) == 0);
-    }();
-    bool ready = false;
-    for (int spins = 0; spin && spins < 2048 && !ready; ++spins) {
-        const hipError_t e = hipEventQuery(lane.done);
-        if (e == hipSuccess) ready = true;
-        else if (e != hipErrorNotReady) HIPCHK(e);
-    }
-    if (!ready) HIPCHK(hipEventSynchronize(lane.done));
-    if (timing_) {
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, lane.t0, lane.t1));
-        sketch_ms_ += ms;
-        sketch_launches_ += 1;
-    }
-    // a batch that needed the host afterwards (run again with larger buffers, reads left to the generic pipeline) has just had
-    // more work queued for its accumulators: "completed" means that work is done too -- the caller may touch the buffers of a
-    // completed batch from any stream
+    const Lane& lane = lanes_[b.lane];
     const uint64_t leftover_before = tot_leftover_;
-    const bool overflowed = ((uint32_t)lane.h_scratch[L_OVERFLOW] & 4u) != 0;
-    finish_lane(lane, p.d_bases, p.d_offsets, p.n_reads, p.n_bases, p.covg, p.prg_reads, p.stream, ppk);
-    if (overflowed || tot_leftover_ != leftover_before) wait_stream(p.stream);
+    for (int attempt = 0;; ++attempt) {
+        if (attempt) launch(b); // (nothing of the last attempt was counted: again, alone, behind whatever is queued on its stream)
+        wait_stream(b.stream, lane.done);
+        if (attempt == 0) note_kernel_time(lane.t0, lane.t1);
+        if (b.direct ? direct_finish(b, attempt) : filter_finish(b, attempt)) {
+            if (attempt || tot_leftover_ != leftover_before) wait_stream(b.stream);
+            return;
+        }
+    }
 }
 
 void Mapper::sync()
@@ -1028,45 +921,20 @@ void Mapper::run_batch(const uint8_t* d_bases, const uint64_t* d_offsets, uint32
     uint32_t* covg, uint32_t* prg_reads, hipStream_t stream, const PackedInfo* pk)
 {
     if (n_bases == 0) return; // only empty reads: no k-mers, no hits
-    dev::KernelTimer timer;
-    if (timing_) { // events bracket the dominant kernel only (sketch_filter_kernel / sketch_probe_kernel)
-        timer.begin = ev0_;
-        timer.end = ev1_;
-    }
-    if (use_filter_) {
-        // ---- filtered sequences: the hits of short reads never leave the chip (read_cluster_kernel).  The batch is cut into
-        // one read range per lane; the ranges run concurrently (lane 0 on the caller's stream), one host wait at the end ----
-        const int n_lanes = (n_bases >= lanes_min_bases_ && n_reads >= 64) ? max_lanes_ : 1;
-        const uint64_t lane_cap = std::max<uint64_t>(min_capacity_, n_bases / FILTER_BASES_PER_ENTRY / (uint64_t)n_lanes * (n_lanes > 1 ? 3 : 2) / 2);
-        ensure_lanes(n_lanes, lane_cap);
-        if (n_lanes > 1) HIPCHK(hipEventRecord(ev_begin_, stream));
-        for (int j = n_lanes - 1; j >= 0; --j) { // (lane 0 last: its stream is the one the host then waits on)
-            Lane& lane = lanes_[j];
-            lane.r0 = (uint32_t)((uint64_t)n_reads * (uint64_t)j / (uint64_t)n_lanes);
-            lane.r1 = (uint32_t)((uint64_t)n_reads * (uint64_t)(j + 1) / (uint64_t)n_lanes);
-            hipStream_t ls = j == 0 ? stream : lane.stream;
-            if (j > 0) HIPCHK(hipStreamWaitEvent(ls, ev_begin_, 0));
-            launch_lane(lane, ls, d_bases, d_offsets, n_reads, n_bases, covg, prg_reads, pk);
-            if (j > 0) HIPCHK(hipEventRecord(lane.done, ls));
-        }
-        for (int j = 1; j < n_lanes; ++j) HIPCHK(hipStreamWaitEvent(stream, lanes_[j].done, 0));
-        wait_stream(stream);
-        if (timing_) {
-            for (int j = 0; j < n_lanes; ++j) {
-                float ms = 0;
-                HIPCHK(hipEventElapsedTime(&ms, lanes_[j].t0, lanes_[j].t1));
-                sketch_ms_ += ms;
-                sketch_launches_ += 1;
-            }
-        }
-        for (int j = 0; j < n_lanes; ++j) finish_lane(lanes_[j], d_bases, d_offsets, n_reads, n_bases, covg, prg_reads, stream, pk);
-        return;
-    }
-    if (use_direct_cands_) {
-        run_batch_direct_candidates(d_bases, d_offsets, n_reads, n_bases, covg, prg_reads, stream, pk);
+    if (use_filter_ || use_direct_cands_) {
+        // ---- the candidate sequences (filtered; direct in its candidate form): the hits of short reads never leave the chip
+        // (read_cluster_kernel).  Lane 0: complete_pending() has left nothing in flight on it ----
+        const Batch b = make_batch(0, d_bases, d_offsets, n_reads, n_bases, covg, prg_reads, stream, pk);
+        launch(b);
+        complete_batch(b);
         return;
     }
     // ---- direct sequence, generic form: every k-mer hashed, hits in tile order, global radix sort ----
+    dev::KernelTimer timer;
+    if (timing_) { // events bracket the dominant kernel only
+        timer.begin = ev0_;
+        timer.end = ev1_;
+    }
     ensure_workspace(std::max<uint64_t>(min_capacity_, n_bases / 64));
     const uint32_t n_tiles = dev::sketch_n_tiles(n_bases, halo_);
     ts_ = &tsets_[0];
@@ -1082,7 +950,7 @@ void Mapper::run_batch(const uint8_t* d_bases, const uint64_t* d_offsets, uint32
         const dev::SketchArgs a = sketch_args(ascii, d_offsets, n_reads, n_bases, nullptr); // (the expansion is ASCII)
         HIPCHK(dev::launch_sketch_probe(a, wide_hash_, stream, timer));
         read_counters(stream);
-        note_kernel_time();
+        if (attempt == 0) note_kernel_time(ev0_, ev1_); // (as complete_batch: a batch's first attempt)
         if ((uint32_t)h_counters_[C_OVERFLOW] & 2u)
             throw Error(DRPRG_EOVERFLOW, "a read is longer than 2^" + std::to_string(dev::HIT_POS_BITS) + " bases");
         if (h_counters_[C_HITS] > hit_capacity_) {
@@ -1113,7 +981,7 @@ void Mapper::map_device_packed(const uint32_t* d_words, const uint64_t* d_offset
     if (!d_words || !d_offsets) throw Error(DRPRG_EINVAL, "null device pointer");
     if ((reinterpret_cast<uintptr_t>(d_words) & 15u) != 0) throw Error(DRPRG_EINVAL, "d_words must be 16-byte aligned");
     const uint8_t* key = reinterpret_cast<const uint8_t*>(d_words);
-    const PackedInfo info { d_npos, n_npos }; // (travels with the batch through every function that touches it, and into Pending)
+    const PackedInfo info { d_npos, n_npos }; // (travels with the batch through every function that touches it, and into Batch)
     if (deferred) map_device_async_impl(key, d_offsets, n_reads, n_bases, covg, prg_reads, stream, &info);
     else map_device_impl(key, d_offsets, n_reads, n_bases, covg, prg_reads, stream, &info);
 }
@@ -1439,7 +1307,7 @@ void Mapper::map_host_async(const HostBatch& hb)
         std::fprintf(stderr, "[drprg-hip] the sample is larger than the %.1f GB of device memory set aside for resident reads (device %d): reads are "
                              "not kept, later passes read the file again (DRPRG_HIP_KEEP_READS_GB raises the limit)\n", (double)cap / 1e9, device_);
     }
-    if (!use_filter_ || max_lanes_ > 1) { // no deferred form of this sequence
+    if (!use_filter_) { // no deferred form of this sequence
         map_host(hb);
         return;
     }

@@ -31,8 +31,8 @@ public:
 
     // Map one batch that is already resident in HBM.  d_bases must be 16-byte aligned.  Coverage is
     // accumulated into d_covg (u32[2*n_knodes]) and d_prg_reads (u32[n_prgs]); nullptr selects the
-    // context's own accumulators.  Asynchronous on `stream` except for one 16-byte read-back of the
-    // hit count between the sketch and the sort.
+    // context's own accumulators.  The candidate sequences return once the batch is complete; the generic one is asynchronous on
+    // `stream` except for one 16-byte read-back of the hit count between the sketch and the sort.
     void map_device(const uint8_t* d_bases, const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases,
         uint32_t* d_covg, uint32_t* d_prg_reads, hipStream_t stream);
 
@@ -42,8 +42,7 @@ public:
     // back-to-back batches leave no gap on the device (measured on 10 M x 150 bp: ~50 us of host round trip per 0.7 ms
     // batch).  The caller keeps d_bases / d_offsets / the accumulators of a batch valid and unchanged until the call after
     // the next one returns, or sync() does (a batch whose candidate buffers overflowed is run again from them).
-    // Filtered sequence with one lane, and the direct sequence in its candidate form (two tile workspaces in turn); everything else
-    // falls back to map_device.
+    // The filtered sequence and the direct sequence in its candidate form (two lanes in turn); everything else falls back to map_device.
     void map_device_async(const uint8_t* d_bases, const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases,
         uint32_t* d_covg, uint32_t* d_prg_reads, hipStream_t stream);
     void sync(); // completes the batch map_device_async left in flight and waits for its stream
@@ -132,7 +131,7 @@ public:
     // [7..10] when the classes were through in 10 ns from the kernel's first wave (0: not clocked), [11] slices per workgroup, [12..19] chunk size per round
     void filter_schedule(uint64_t out[20]);
     // the buffers that grow when a batch does not fit them (drprg_hip_buffer_info; counts since the Mapper was made, reset() keeps them):
-    // out[0] read ranges of the filtered sequence run again after a candidate slice overflowed, [1] the same for the direct sequence's
+    // out[0] batches of the filtered sequence run again after a candidate slice overflowed, [1] the same for the direct sequence's
     // candidate form, [2] regrows of the generic hit buffer, [3] largest raw_capacity of any lane (entries), [4] hit_capacity_, [5] 0.  Synchronises.
     void buffer_info(uint64_t out[6]);
     void enable_kernel_timing(bool on) { timing_ = on; }
@@ -143,11 +142,10 @@ public:
 private:
     void zero_now(void* p, int value, size_t bytes);
     void ensure_workspace(uint64_t hit_capacity);
-    // One filtered launch sequence (sketch_filter -> refine -> candidates -> read_cluster) and everything private to it.
-    // A batch is cut into as many read ranges as there are lanes (default: one); lane 0 runs on the caller's stream, the
-    // others on their own, so that the candidate / cluster kernels of one range can overlap the filter kernel of the next.
+    // What one batch of a candidate sequence (filtered: sketch_filter -> verify -> read_cluster; direct: sketch -> read_cluster from the
+    // tile slices) keeps to itself: candidate buffers, per-sequence counters, and events on the batch's stream (done: behind the batch's
+    // read-back; t0 / t1 around the dominant kernel).  Two lanes: map_device_async takes them in turn, the synchronous calls use lane 0.
     struct Lane {
-        hipStream_t stream = nullptr; // lanes >= 1 (lane 0 uses the stream of the call)
         hipEvent_t done = nullptr, t0 = nullptr, t1 = nullptr;
         uint64_t raw_capacity = 0;
         uint64_t *raw_pos = nullptr, *cand_info = nullptr;
@@ -157,28 +155,44 @@ private:
         unsigned long long* h_scratch = nullptr; // pinned mirror
         unsigned long long* h_scratch_dev = nullptr; // its device address
         bool scratch_zero = false;               // d_scratch is known to be zero on the device
-        bool ft_packed = false;                  // the batch of the sequence in flight is a packed one (tune_filter_shares)
         dev::FilterWork fw {};
-        uint32_t r0 = 0, r1 = 0;                 // read range of the current batch
     };
     enum { L_HITS = 0, L_OVERFLOW = 1, L_MAXLEN = 2, L_UNSORTED = 3, L_COMPLEX = 4, L_CHUNK = 5, L_MINIMIZERS = 6, L_FT_CLOCK = 7 /* five words: FilterBuffers::class_clock */, L_N = 12 };
     // What makes a device batch a packed one (2-bit words instead of bytes): where its non-ACGT positions are.  Passed along with the batch
-    // pointer to everything that touches the batch (nullptr: ASCII) and kept in Pending for the deferred completion -- until round 5 the
+    // pointer to everything that touches the batch (nullptr: ASCII) and kept in Batch for the deferred completion -- until round 5 the
     // batch's ADDRESS was looked up in a map, which every free and every recycled address had to keep honest.
     struct PackedInfo {
         const uint64_t* d_npos = nullptr;
         uint64_t n_npos = 0;
     };
-    void ensure_lanes(int n, uint64_t raw_capacity);
+    // A batch of one of the two candidate sequences, as its launch and finish functions see it
+    struct Batch {
+        bool active = false;
+        bool direct = false; // the direct sequence's candidate form (else the filtered sequence)
+        int lane = 0;        // lanes_[lane] (direct: and tsets_[lane])
+        const uint8_t* d_bases = nullptr;
+        const uint64_t* d_offsets = nullptr;
+        uint32_t n_reads = 0;
+        uint64_t n_bases = 0;
+        uint32_t *covg = nullptr, *prg_reads = nullptr;
+        hipStream_t stream = nullptr;
+        bool packed = false; // the batch is 2-bit words ...
+        PackedInfo pk {};    // ... with these non-ACGT positions
+        const PackedInfo* pkp() const { return packed ? &pk : nullptr; }
+    };
+    Batch make_batch(int lane, const uint8_t* d_bases, const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases, uint32_t* covg, uint32_t* prg_reads,
+        hipStream_t stream, const PackedInfo* pk) const;
+    void ensure_lanes();
     void grow_lane(Lane& lane, uint64_t raw_capacity);
     void free_lane(Lane& lane);
-    void launch_lane(Lane& lane, hipStream_t stream, const uint8_t* d_bases, const uint64_t* d_offsets, uint32_t n_reads,
-        uint64_t n_bases, uint32_t* covg, uint32_t* prg_reads, const PackedInfo* pk);
-    void wait_stream(hipStream_t stream);
-    void leftovers(Lane& lane, const uint8_t* d_bases, const uint64_t* d_offsets, uint32_t n_reads, uint64_t n_bases, uint32_t* covg,
-        uint32_t* prg_reads, hipStream_t stream, const PackedInfo* pk);
-    void run_batch_direct_candidates(const uint8_t* d_bases, const uint64_t* d_offsets, uint32_t n_reads, uint64_t n_bases,
-        uint32_t* covg, uint32_t* prg_reads, hipStream_t stream, const PackedInfo* pk);
+    // One attempt of a batch, queued on its stream with the lane's `done` recorded behind it; finish: the attempt's read-back has arrived
+    // -- false: a candidate buffer was too small, nothing was counted, the buffers have grown and the batch must run again.
+    void launch(const Batch& b);
+    void filter_launch(const Batch& b);
+    bool filter_finish(const Batch& b, int attempt);
+    void direct_launch(const Batch& b);
+    bool direct_finish(const Batch& b, int attempt);
+    void leftovers(const Batch& b);
     void run_batch(const uint8_t* d_bases, const uint64_t* d_offsets, uint32_t n_reads, uint64_t n_bases,
         uint32_t* d_covg, uint32_t* d_prg_reads, hipStream_t stream, const PackedInfo* pk);
     void cluster_hits(const uint64_t* d_offsets, uint32_t n_hits, bool ordered, unsigned long long* d_unsorted, uint32_t* d_covg,
@@ -195,27 +209,11 @@ private:
     void map_device_async_impl(const uint8_t* d_bases, const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases, uint32_t* d_covg, uint32_t* d_prg_reads,
         hipStream_t stream, const PackedInfo* pk);
     void read_counters(hipStream_t stream);
-    void note_kernel_time();
-    // deferred completion: two lanes take the batches in turn; `pending_` is the batch whose read-back nobody has looked at yet
-    struct Pending {
-        bool active = false;
-        int lane = 0;
-        const uint8_t* d_bases = nullptr;
-        const uint64_t* d_offsets = nullptr;
-        uint32_t n_reads = 0;
-        uint64_t n_bases = 0;
-        uint32_t *covg = nullptr, *prg_reads = nullptr;
-        hipStream_t stream = nullptr;
-        bool direct = false; // a batch of the direct sequence's candidate form (lane = its tile set)
-        bool packed = false; // the batch is 2-bit words ...
-        PackedInfo pk {};    // ... with these non-ACGT positions
-    };
+    void note_kernel_time(hipEvent_t t0, hipEvent_t t1);
+    // deferred completion: the batches take the two lanes in turn; `pending_` is the batch whose read-back nobody has looked at yet
     void complete_pending();
-    void complete_batch(const Pending& p);
-    void finish_lane(Lane& lane, const uint8_t* d_bases, const uint64_t* d_offsets, uint32_t n_reads, uint64_t n_bases, uint32_t* covg,
-        uint32_t* prg_reads, hipStream_t stream, const PackedInfo* pk);
-    Pending pending_;
-    std::vector<Lane> pipe_lanes_;
+    void complete_batch(const Batch& b);
+    Batch pending_;
     int pipe_next_ = 0;
 
     int device_ = 0;
@@ -265,23 +263,15 @@ private:
     uint32_t *d_val_a_ = nullptr, *d_val_b_ = nullptr;
     uint32_t *d_head_ = nullptr, *d_scan_ = nullptr, *d_cstart_ = nullptr, *d_order_ = nullptr;
     dev::ClusterRec* d_clusters_ = nullptr;
-    // candidate workspace of the filtered sequence
-    std::vector<Lane> lanes_;
-    int max_lanes_ = 1;             // DRPRG_HIP_LANES (1..4).  Measured on configs[1] (10 M x 150 bp): 0.66 ms with one lane, 0.73 / 0.83 ms
-                                    // with two / four: a resident sketch_filter_kernel workgroup holds 128 KB of a CU's LDS, so refine
-                                    // and read_cluster of the other range wait for it, and what does overlap (verify) competes for the
-                                    // same VALU issue slots -- every kernel stretches by about what the overlap saves
-    uint64_t lanes_min_bases_ = 64ull << 20; // smaller batches always take one lane
+    Lane lanes_[2];
     // smallest capacity of the candidate / hit buffers, in entries (DRPRG_HIP_MIN_CAPACITY, read here at construction; tests lower it so that
     // small batches run at the production ratio -- n_bases / 48 for the filtered sequence --, or below it to make the buffers regrow)
     static constexpr uint64_t MIN_CAPACITY_CLAMP = 4096;
     uint64_t min_capacity_ = 1u << 20;
     uint64_t reruns_filter_ = 0, reruns_direct_ = 0, regrows_hits_ = 0; // buffer_info
-    hipEvent_t ev_begin_ = nullptr; // recorded on the caller's stream: the other lanes start behind it
     void* d_temp_ = nullptr;
-    // candidate form of the direct sequence: one slice of `cap` records per tile.  Two sets of the workspace: the synchronous calls use
-    // the first; map_device_async takes them in turn (a batch's slices must survive until its read-back has been looked at: reads left
-    // to the generic pipeline are gathered from them)
+    // candidate form of the direct sequence: one slice of `cap` records per tile.  One set of the workspace per lane (a batch's slices must
+    // survive until its read-back has been looked at: reads left to the generic pipeline are gathered from them)
     struct TileSet {
         uint32_t slice_cap = 256, ws_tiles = 0, ws_cap = 0, first_cap = 0;
         uint64_t* d_tile_info = nullptr;
@@ -295,7 +285,6 @@ private:
         uint16_t* d_nbits = nullptr;
         uint64_t nbits_cap = 0; // u16 words
         bool nbits_dirty = false;
-        hipEvent_t done = nullptr, t0 = nullptr, t1 = nullptr;
         uint32_t mark = 0, n_tiles = 0;   // of the batch in flight
         dev::SketchArgs a_done {};
     };
@@ -304,10 +293,6 @@ private:
     uint32_t slices_epoch_ = 0x80000000u; // mark of the last batch whose candidates read_cluster_kernel took from the slices
     void free_tile_set(TileSet& t);
     void ensure_tile_workspace(TileSet& t, uint32_t n_tiles, uint32_t tile_cap);
-    void direct_launch(int set, const uint8_t* d_bases, const uint64_t* d_offsets, uint32_t n_reads, uint64_t n_bases, uint32_t* covg, uint32_t* prg_reads,
-        hipStream_t stream, bool timed_by_set_events, const PackedInfo* pk);
-    bool direct_finish(int set, const uint8_t* d_bases, const uint64_t* d_offsets, uint32_t n_reads, uint64_t n_bases, uint32_t* covg, uint32_t* prg_reads,
-        hipStream_t stream, int attempt, const PackedInfo* pk);
     size_t temp_bytes_ = 0;
     // host staging
     uint8_t* h_bases_ = nullptr;

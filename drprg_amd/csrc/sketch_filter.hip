@@ -706,14 +706,14 @@ size_t filter_small_words() { return FT_SMALL_HEAD + 4 + 4 * (size_t)MAX_EX_WG; 
 uint32_t* filter_super_counts(uint32_t* small) { return small + MAX_CHUNKS; }
 uint32_t filter_super_words() { return (uint32_t)MAX_SLICES; }
 
-FilterSched make_filter_sched(uint32_t n_tiles, uint32_t n_wg, bool window_known, const uint32_t share[4])
+FilterSched make_filter_sched(uint32_t n_tiles, uint32_t n_wg, const uint32_t share[4])
 {
     FilterSched s {};
     for (int r = 0; r < FT_MAX_ROUNDS; ++r) s.first_ticket[r] = 0xFFFFFFFFu;
     s.n_rounds = 1;
     s.per_wg = FT_WAVES;
     s.n_tiles = n_tiles;
-    s.tpw0 = window_known ? (n_tiles + n_wg * FT_WAVES - 1) / (n_wg * FT_WAVES) : 0u;
+    s.tpw0 = (n_tiles + n_wg * FT_WAVES - 1) / (n_wg * FT_WAVES);
     // DRPRG_FT_SCHED (read at every launch: tests switch it): "static", or "f,d,m[,a]" = round 0's part of the tiles in 1/256, the divisor of
     // the dynamic rounds x 16 (a round hands every wave 16 / d of an even share of what is left), the smallest chunk in tiles, and the
     // fewest tiles per wave a batch must have for a dynamic schedule at all (64: below that the static split is as good, and cheaper)
@@ -742,7 +742,7 @@ FilterSched make_filter_sched(uint32_t n_tiles, uint32_t n_wg, bool window_known
     const uint32_t tpw0 = (uint32_t)(avg * knobs.f / 256);
     // every chunk of a dynamic schedule must hold two tiles that lie wholly inside the buffer (the last two tiles of a batch may not): the
     // smallest share of round 0 -- the class split rounds down by up to a tile -- and the smallest chunk say whether this batch can have one
-    if (!window_known || knobs.is_static || avg < knobs.min_avg || (uint64_t)tpw0 * min_share / 256 < FT_DEPTH + 2) return s;
+    if (knobs.is_static || avg < knobs.min_avg || (uint64_t)tpw0 * min_share / 256 < FT_DEPTH + 2) return s;
     const uint32_t max_per_wg = (uint32_t)MAX_CHUNKS / n_wg;
     uint64_t done = (uint64_t)FT_WAVES * tpw0, rest = wg_tiles - done;
     if (rest < FT_DEPTH + 2) return s; // (the last chunk -- the whole dynamic part here -- must hold FT_DEPTH whole tiles: the batch's last two may be partial)
@@ -785,12 +785,12 @@ void init_candidate_work(FilterWork& fw, const FilterBuffers& b, int n_cus)
     fw.max_len = b.max_len;
 }
 
-hipError_t launch_sketch_filter(const SketchArgs& a, uint32_t read_begin, uint32_t read_end, const BloomTables& bt, int n_cus,
-    const FilterBuffers& b, const ReadClusterArgs& rc, FilterWork& fw, hipStream_t stream, KernelTimer timer)
+hipError_t launch_sketch_filter(const SketchArgs& a, const BloomTables& bt, int n_cus, const FilterBuffers& b, const ReadClusterArgs& rc, FilterWork& fw,
+    hipStream_t stream, KernelTimer timer)
 {
     fw = FilterWork {};
-    fw.read_begin = read_begin;
-    fw.read_end = read_end;
+    fw.read_begin = 0;
+    fw.read_end = a.n_reads;
     if (a.n_bases == 0) return hipSuccess;
     const bool mid = bt.mid_bitmap != nullptr; // middle tier: level 0 (canonical 12-mers) in LDS, bitmap + code filter in global memory
     if (mid && (a.k != 15 || !bt.mid0 || !bt.midc || bt.midc_wbits < 1 || bt.midc_wbits > MID_C_MAX_WBITS || (bt.mid0_bits != 1 && bt.mid0_bits != 3)))
@@ -841,10 +841,8 @@ hipError_t launch_sketch_filter(const SketchArgs& a, uint32_t read_begin, uint32
         fw.class_clock = level0 && !from_env ? b.class_clock : nullptr;
         for (int c = 0; c < 4; ++c) fw.wave_share[c] = share[c];
     }
-    {   // the chunk schedule: dynamic when this sequence covers the whole batch (the host then knows the tile numbers) and the batch is large enough
-        const bool whole = read_begin == 0 && read_end == a.n_reads;
-        fw.sched = make_filter_sched(filter_n_tiles(a.n_bases, filter_positions_per_lane(level0, a.packed != 0)), grid, whole, fw.wave_share);
-    }
+    // the chunk schedule: dynamic when the batch is large enough
+    fw.sched = make_filter_sched(filter_n_tiles(a.n_bases, filter_positions_per_lane(level0, a.packed != 0)), grid, fw.wave_share);
     fw.n_slices = grid * fw.sched.per_wg;
     {   // the slices' geometry (FilterWork::slice_budget): a floor of up to 256 entries per slice -- a quarter of the workgroup's budget at most --
         // and the rest by the tile.  (A workgroup's range: an even split to the tile, or -- static schedule -- 16 waves x tiles per wave.)

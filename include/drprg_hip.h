@@ -318,7 +318,7 @@ int drprg_hip_report_json(const char* index_dir, const char* annotated_vcf, cons
     int padding, const char* index_version, char* err, size_t err_len);
 
 /* HIP-event timing of the dominant kernel (sketch_filter_kernel / sketch_probe_kernel) on its launch stream (bench.py roofline);
- * launches = launches of that kernel (a batch cut into several read ranges counts one per range).
+ * launches = launches of that kernel, one per batch (a batch run again with larger buffers counts its first attempt only).
  * enable != 0 starts/keeps timing; ms_total / launches may be NULL; reset != 0 clears the sums. */
 int drprg_hip_kernel_timing(drprg_hip_ctx* ctx, int enable, int reset, double* ms_total, uint64_t* launches);
 /* How sketch_filter_kernel handed its tiles out in the batch completed last, and when its four wave classes were through (bench.py prints
@@ -327,7 +327,7 @@ int drprg_hip_kernel_timing(drprg_hip_ctx* ctx, int enable, int reset, double* m
  * the kernel's first wave (0: not clocked), [11] chunks per workgroup, [12..19] chunk size of every round in tiles.  Synchronises. */
 int drprg_hip_filter_schedule(drprg_hip_ctx* ctx, uint64_t out[20]);
 /* The device buffers that grow when a batch does not fit them, and how often they had to (tests: the paths that run a batch again).
- * out[0] read ranges of the filtered sequence run again after a candidate slice overflowed, [1] the same for the direct sequence's
+ * out[0] batches of the filtered sequence run again after a candidate slice overflowed, [1] the same for the direct sequence's
  * candidate form, [2] regrows of the generic pipeline's hit buffer, [3] largest candidate capacity of any lane in entries, [4] hit
  * buffer capacity in entries, [5] 0 (reserved).  Counted from drprg_hip_open like the buffers themselves: drprg_hip_reset keeps them.
  * A multi-device context sums [0..2] and takes the largest [3..4].  The smallest capacity is DRPRG_HIP_MIN_CAPACITY entries (default

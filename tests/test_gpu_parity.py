@@ -711,7 +711,7 @@ def test_deferred_batches_equal_synchronous_ones(tmp_path, oracle, monkeypatch, 
     info = ctx.buffer_info()
     which = {0: "filter_reruns", 1: "hit_regrows", 3: "direct_reruns"}[kernel]
     assert reran[which] >= 1, reran  # the synchronous pass ran a batch again ...
-    if kernel != 1:  # ... and so did the deferred one, on the lanes of its own (kernel 1 has none: its hit buffer had grown already)
+    if kernel != 1:  # ... and so did the deferred one, on its second lane (kernel 1 has no lanes: its hit buffer had grown already)
         assert info[which] > reran[which], (reran, info)
     assert np.array_equal(got, want) and np.array_equal(got_prg, want_prg)
     for key in ("reads", "bases", "minimizers", "hits", "clusters_kept", "hits_kept", "leftover_reads"):
@@ -1080,8 +1080,8 @@ def test_filter_schedule_follows_the_batches(tmp_path, oracle, monkeypatch, sche
     info = ctx.filter_schedule()
     assert ctx.counters()["kernel"] == 2 and ctx.counters()["hits"] == 8 * ocnt["hits"]
     if sched == "static":
-        assert info["form"] == "static" and (not ONE_LANE or len(set(seen)) > 1), seen  # the shares did move
-    elif ONE_LANE:
+        assert info["form"] == "static" and len(set(seen)) > 1, seen  # the shares did move
+    else:
         assert info["form"] == "dynamic" and info["slices_per_workgroup"] > 16 and len(set(seen)) == 1, (info, seen)
     ctx.reset()
     ctx.map_device(tb.data_ptr(), to.data_ptr(), len(offs) - 1, int(offs[-1]))
@@ -1095,10 +1095,6 @@ def test_filter_schedule_follows_the_batches(tmp_path, oracle, monkeypatch, sche
         ctx.map_host_packed(words, offs, npos)
     cov, prg = ctx.coverage()
     assert np.array_equal(cov.astype(np.uint64), 3 * ocov.astype(np.uint64)) and np.array_equal(prg.astype(np.uint64), 3 * oprg.astype(np.uint64))
-
-
-ONE_LANE = int(os.environ.get("DRPRG_HIP_LANES", "1") or 1) == 1  # (a batch cut into read ranges on concurrent streams keeps one chunk per
-# wave: the host has no tile numbers for a range -- the suite still runs that way, tools/flaky_record.sh, without the assertions on the form)
 
 
 def _schedule_forms(ctx, bases, offs):
@@ -1131,13 +1127,13 @@ def test_extreme_tile_shares(tmp_path, oracle, monkeypatch, share, sched, grid):
     ctx = _ctx(tmp_path, panel, 11, 15, True, kernel=2)
     bases, offs = _ragged_reads(panel)
     _compare(ctx, oracle, bases, offs, 11, 15, True, 2)
-    assert not ONE_LANE or _schedule_forms(ctx, bases, offs) == want
+    assert _schedule_forms(ctx, bases, offs) == want
     panel = synth.small_panel(seed=11, n_loci=6, length=1500)
     ctx = _ctx(tmp_path, panel, 11, 15, False, kernel=2)
     gen = synth.HaplotypeGenomes(panel, genome_size=60000, n_hap=4, seed=3)
     bases, offs = synth.sample_long_reads(gen, 3000, seed=3)
     cnt = _compare(ctx, oracle, bases, offs, 11, 15, False, 2)
-    assert cnt["clusters_kept"] > 0 and (not ONE_LANE or _schedule_forms(ctx, bases, offs) == want)
+    assert cnt["clusters_kept"] > 0 and _schedule_forms(ctx, bases, offs) == want
 
 
 @pytest.mark.parametrize("grid,sched", [("1", "100,20,4,8"), ("3", "100,20,4,8"), ("7", "200,17,4,8"), ("5", "60,64,5,8"), ("2", "250,1024,4,8")])
@@ -1159,19 +1155,19 @@ def test_chunk_schedule_edges(tmp_path, oracle, monkeypatch, grid, sched):
         cnt = _compare(ctx, oracle, bases, offs, 11, 15, True, 2)
         assert cnt["clusters_kept"] > 3000
         forms.append(_schedule_forms(ctx, bases, offs))
-    assert not ONE_LANE or all(f[0] == "dynamic" for f in forms), forms
-    if ONE_LANE and sched != "60,64,5,8":  # (a quarter of the tiles in round 0: the packed form's 64 positions per lane leave too few tiles per wave for it)
+    assert all(f[0] == "dynamic" for f in forms), forms
+    if sched != "60,64,5,8":  # (a quarter of the tiles in round 0: the packed form's 64 positions per lane leave too few tiles per wave for it)
         assert all(f[1] == "dynamic" for f in forms), forms
     # the middle tier (its own instantiation of the kernel) and w = 14 (another window) through the same schedule
     monkeypatch.setenv("DRPRG_FORCE_MID_TIER", "1")
     ctx = _ctx(tmp_path, panel, 14, 15, True, kernel=2)
     _compare(ctx, oracle, sparse[0], sparse[1], 14, 15, True, 2)
-    assert not ONE_LANE or _schedule_forms(ctx, sparse[0], sparse[1])[0] == "dynamic"
+    assert _schedule_forms(ctx, sparse[0], sparse[1])[0] == "dynamic"
     monkeypatch.delenv("DRPRG_FORCE_MID_TIER")
     # k = 13 (the forms without level 0: two workgroups per CU, another LDS layout for the counter)
     ctx = _ctx(tmp_path, panel, 16, 13, True, kernel=2)
     _compare(ctx, oracle, sparse[0], sparse[1], 16, 13, True, 2)
-    assert not ONE_LANE or _schedule_forms(ctx, sparse[0], sparse[1])[0] == "dynamic"
+    assert _schedule_forms(ctx, sparse[0], sparse[1])[0] == "dynamic"
 
 
 def test_offsets_must_span_the_batch_under_a_chunk_schedule(tmp_path, oracle, monkeypatch):
@@ -1180,8 +1176,6 @@ def test_offsets_must_span_the_batch_under_a_chunk_schedule(tmp_path, oracle, mo
     nothing had happened.  (One chunk per wave, the schedule of small batches, takes its window from the offsets and does not care.)"""
     import torch
     from drprg_amd import DependencyError, synth
-    if not ONE_LANE:
-        pytest.skip("read ranges on concurrent streams keep one chunk per wave")
     monkeypatch.setenv("DRPRG_FT_GRID", "2")
     monkeypatch.setenv("DRPRG_FT_SCHED", "128,32,4,8")
     panel = synth.small_panel(seed=4)
@@ -1201,7 +1195,7 @@ def test_offsets_must_span_the_batch_under_a_chunk_schedule(tmp_path, oracle, mo
     ctx.reset()
     ctx.map_device(tb.data_ptr(), tgood.data_ptr(), len(offs) - 1, int(offs[-1]))
     cov, prg = ctx.coverage()
-    assert ctx.filter_schedule()["form"] == ("dynamic" if ONE_LANE else "static")
+    assert ctx.filter_schedule()["form"] == "dynamic"
     idx = _oracle_index(oracle, ctx.prg_strings, 11, 15)
     ocov, oprg, _ = _oracle_map(oracle, idx, bases, offs, 11, 15, True)
     assert np.array_equal(cov, ocov) and np.array_equal(prg, oprg)

@@ -233,53 +233,7 @@ def test_deferred_rerun_lands_in_its_own_accumulator(tmp_path, oracle, monkeypat
         assert cnt[key] == sum(w_[2][key] for w_ in want), key
 
 
-# ---- 3. several lanes ----------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("lanes", [2, 4])
-def test_read_ranges_rerun_on_their_own(tmp_path, oracle, monkeypatch, lanes):
-    """DRPRG_HIP_LANES: the batch is cut into read ranges on concurrent streams; one range holds dense reads, the others reads from off
-    the panel.  The ranges that overflow run again on their own, each lane grows by 4 per rerun of its own, and the totals stay exact.
-    (Measured: a second range reruns once beside the dense one, while the control -- the dense range replaced by off-panel reads -- never
-    does; why is still open.  This case pins that the reruns, however many, count nothing twice.)"""
-    monkeypatch.setenv("DRPRG_HIP_LANES", str(lanes))
-    monkeypatch.setenv("DRPRG_HIP_LANES_MIN_BASES", "0")
-    panel = _dense_panel()[0]
-    n, m = 12000 * lanes, 12000  # (reads [m, 2m): range 1 of `lanes`, the dense one)
-    _, _, background = _dense_panel()
-    sb, so = _reads_from(np.random.default_rng(20 + lanes), [background], n - m, 150)
-    bases, offs = _concat((sb[:int(so[m])], so[:m + 1]), _dense(m, 30 + lanes), (sb[int(so[m]):], so[m:] - so[m]))
-    assert len(offs) - 1 == n
-    n_bases = int(offs[-1])
-    ocov, oprg, ocnt = _Oracle.of(oracle, panel.prgs, bases, offs, 11, 15)
-    ref = _open(monkeypatch, tmp_path, panel, 11, 15, 2, _no_regrow_cap(n_bases))
-    rcov, rprg, rcnt, rb, ra = _map(ref, bases, offs, False)
-    assert _delta(rb, ra) == dict.fromkeys(RERUNS, 0)
-    ref.close()
-    # control: the same batch with the dense range replaced by reads from off the panel never reruns at this floor
-    ob, oo = _reads_from(np.random.default_rng(40 + lanes), [background], m, 150)
-    cb, co = _concat((sb[:int(so[m])], so[:m + 1]), (ob, oo), (sb[int(so[m]):], so[m:] - so[m]))
-    cocov, coprg, _ = _Oracle.of(oracle, panel.prgs, cb, co, 11, 15)
-    ctl = _open(monkeypatch, tmp_path, panel, 11, 15, 2, 160 * int(co[-1]) // 2016)
-    ccov, cprg, _, cb0, ca0 = _map(ctl, cb, co, False)
-    assert _delta(cb0, ca0) == dict.fromkeys(RERUNS, 0), ca0
-    assert np.array_equal(ccov, cocov) and np.array_equal(cprg, coprg)
-    ctl.close()
-    # (every lane's slices span the tiles of the whole batch: ~160 entries per tile is room for the sparse ranges, half of what the dense one needs)
-    floor = 160 * n_bases // 2016
-    lane_cap = max(floor, n_bases // 48 // lanes * 3 // 2)
-    ctx = _open(monkeypatch, tmp_path, panel, 11, 15, 2, floor)
-    for packed in (False, True):
-        if packed:
-            ctx.close()
-            ctx = _open(monkeypatch, tmp_path, panel, 11, 15, 2, floor)
-        cov, prg, cnt, b, a = _map(ctx, bases, offs, packed)
-        d = _delta(b, a)
-        assert 1 <= d["filter_reruns"] <= lanes and d["direct_reruns"] == 0 and d["hit_regrows"] == 0, d
-        assert a["lane_capacity"] in [lane_cap * 4 ** i for i in range(1, d["filter_reruns"] + 1)], (a, lane_cap)
-        _assert_exact((cov, prg, cnt), rcnt, ocov, oprg, ocnt, 2, f"packed={packed}")
-    ctx.close()
-
-
-# ---- 4. direct tile sequence and the generic hit buffer ------------------------------------------------------------------------------
+# ---- 3. direct tile sequence and the generic hit buffer ------------------------------------------------------------------------------
 def _direct_case(tmp_path, oracle, monkeypatch, w, k):
     """The tile slices start at 256 entries whatever the smallest capacity: a context that did not regrow is the same one mapping the
     batch a second time, on the buffers the first pass left"""
@@ -348,7 +302,7 @@ def test_generic_hit_buffer_regrows_once(tmp_path, oracle, monkeypatch, packed):
     ctx.close()
 
 
-# ---- 5. the filter's geometry changing under one context ---------------------------------------------------------------------------
+# ---- 4. the filter's geometry changing under one context ---------------------------------------------------------------------------
 def test_geometry_changes_between_batches_on_one_context(tmp_path, oracle, monkeypatch):
     """One context, one batch after the other with DRPRG_FT_GRID 7 -> 3 -> 5 -> unset and the schedule switching with it, the third batch
     overflowing in the middle: every batch exact into an accumulator of its own.  (A launch with fewer slices than the one before finds
@@ -383,7 +337,7 @@ def test_geometry_changes_between_batches_on_one_context(tmp_path, oracle, monke
     ctx.close()
 
 
-# ---- 6. a bench-like batch at the production ratio under the dynamic schedule ------------------------------------------------------------
+# ---- 5. a bench-like batch at the production ratio under the dynamic schedule ------------------------------------------------------------
 def _bench_like(pairs=False):
     """~20 M bases of off-panel 150 bp reads with error-free 4 kb reads from inside a panel locus placed in front of every workgroup's end
     (DRPRG_FT_GRID=4), where the last round of the chunk schedule hands out its smallest chunks: 2, 12, 22 and 32 ASCII tiles in front
