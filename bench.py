@@ -22,8 +22,16 @@ while the next batch runs); DRPRG_BENCH_SYNC=1 makes the host wait for every bat
 Prints ONE JSON line (rank 0).  `roofline` prices the dominant kernel (sketch_filter_kernel for the
 mtb-sized indexes, sketch_wave_kernel for the 500-locus one) against HBM bandwidth using the
 algorithmic bytes of SURVEY.md section 8d, with its duration measured live with HIP events on the
-launch stream; `cpu_baseline` times the CPU oracle (oracle/oracle.c + oracle_index.c, a scalar port) on a
-bounded sample of the same workload, on one thread and on the host's cores (up to 64 threads).
+launch stream.
+
+A plain run does only what the headline needs: it builds the batch, brings the device to its clocks (W + K
+untimed steps, then --spinup-ms of mapping), warms up, times the steps, writes --dump-outputs and prints the
+line.  `--full` adds everything else the line can carry, all of it outside the timed region: `cold_start` (those
+first W + K steps timed, on the device as the preparation leaves it), the full-size property checks, the
+`packed_input` and `other_batches_in_rotation` legs, `cpu_baseline` (the CPU oracle, oracle/oracle.c +
+oracle_index.c, a scalar port, on a bounded sample of the same workload, on one thread and on the host's cores,
+up to 64 threads) and `e2e`; with N > 1, one more untimed pass + reduce that checks that every rank holds the
+sum of the ranks' vectors.  Without --full those fields are null or absent.
 
 `--dump-outputs DIR` writes the vector the last timed step left (coverage per k-mer node and strand, reads per PRG) as .npy files;
 the inputs are seeded, so two builds run with the same arguments can be compared output for output.
@@ -399,15 +407,20 @@ def main():
                          "ncclAllReduce of [coverage | reads per PRG]); torch = torch.distributed.all_reduce on the same buffer; "
                          "auto = native with the nccl backend, torch otherwise")
     ap.add_argument("--read-len", type=int, default=150)
-    ap.add_argument("--cpu-sample", type=int, default=-1, help="reads timed on the CPU oracle (0 = skip, -1 = ~10 s worth)")
-    ap.add_argument("--e2e", type=int, default=1, help="1: add the end-to-end leg (FASTQ text in /dev/shm -> coverage through map_fastx, "
-                                                       "plain and gzip) to the JSON line at N=1; 0: skip")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run every other leg and check of the line (cold_start, the full-size checks, packed_input, "
+                         "other_batches_in_rotation, cpu_baseline, e2e; N > 1: the reduce-consistency pass), all outside the timed region.  "
+                         "Without it: set up, warm up, time the steps, dump, print")
+    ap.add_argument("--cpu-sample", type=int, default=-1, help="with --full: reads timed on the CPU oracle (0 = skip, -1 = ~10 s worth)")
+    ap.add_argument("--e2e", type=int, default=1, help="with --full, 1: add the end-to-end leg (FASTQ text in /dev/shm -> coverage through "
+                                                       "map_fastx, plain and gzip) to the JSON line at N=1; 0: skip")
     ap.add_argument("--spinup-ms", type=float, default=float(os.environ.get("DRPRG_BENCH_SPINUP_MS", "600")),
                     help="untimed mapping of the same batch for this long BEFORE the warm-up steps, so that the timed region runs on a device at "
-                         "its clocks (0: none; the line's cold_start leg is the same command on the device as the preparation leaves it)")
+                         "its clocks (0: none; the cold_start leg of --full is the same command on the device as the preparation leaves it)")
     ap.add_argument("--no-checks", action="store_true",
-                    help="skip the full-size property checks after the timed region (profiling runs: every launch is then a "
-                         "timed full-size one, so rocprofv3 per-kernel averages compare directly with avg_launch_ms)")
+                    help="skip the W + K untimed steps before the spin-up and, with --full, cold_start, the full-size property checks, the "
+                         "packed / rotation legs and e2e (profiling runs: every launch is then a timed full-size one, so rocprofv3 per-kernel "
+                         "averages compare directly with avg_launch_ms)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed (rank 0's reduced vector: coverage.npy, "
                          "prg_reads.npy) as float64 .npy files into DIR, to compare two builds output for output")
@@ -424,6 +437,7 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but the launcher started WORLD_SIZE={world} ranks")
+    checks = args.full and not args.no_checks  # the legs and checks around the headline (a plain run: none of them)
 
     import torch
     import torch.distributed as dist
@@ -623,28 +637,34 @@ def main():
     acc = accs[0]
     # ---- the device's state (round 6).  A MI355X that has idled while the host built the batch (seconds) takes hundreds of milliseconds of
     # work to reach the clocks it then holds: the same 20 steps take 0.49 ms each right after the preparation, 0.465 after 50 ms of mapping
-    # and 0.445 after half a second (profiles/r06/spinup.txt) -- and W = 5 warm-up steps are 2.5 ms.  So the line carries both: "cold_start",
+    # and 0.445 after half a second (profiles/r06/spinup.txt) -- and W = 5 warm-up steps are 2.5 ms.  So a --full line carries both: "cold_start",
     # the W + K steps of this very command measured first, on the device as the preparation leaves it; and the headline, the same W + K steps
-    # after --spinup-ms (600) of untimed mapping of the same batch -- what a process that maps sample after sample runs at. ----
+    # after --spinup-ms (600) of untimed mapping of the same batch -- what a process that maps sample after sample runs at.  A plain run maps
+    # those first W + K steps too, untimed (~15 ms): the first calls of a context set up what it keeps, and without these steps that set-up
+    # ate into the clock-driven spin-up -- 2-3 % fewer spin-up steps, and a headline 0.2-3.5 % slower in six runs alternating with the line
+    # that still timed them. ----
     cold_start = None
     if world == 1 and not args.no_checks and args.spinup_ms > 0:
         for _ in range(args.warmup):
             step()
         drain()
         torch.cuda.synchronize()
-        ctx.kernel_timing(enable=True, reset=True)
-        c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        c0.record(stream)
+        if checks:
+            ctx.kernel_timing(enable=True, reset=True)
+            c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            c0.record(stream)
         for _ in range(args.steps):
             step()
-        c1.record(stream)
+        if checks:
+            c1.record(stream)
         drain()
         torch.cuda.synchronize()
-        c_ms, c_n = ctx.kernel_timing(enable=False)
-        cold_ms = c0.elapsed_time(c1) / args.steps
-        cold_start = {"ms_per_step": cold_ms, "value": n_reads / (cold_ms * 1e-3), "unit": "reads/s", "dominant_kernel_avg_launch_ms": c_ms / max(c_n, 1),
-                      "how": f"{args.warmup} warm-up + {args.steps} timed steps (device time between two events) FIRST, before anything else ran on the "
-                             "device since the batch was built: a device that has idled for seconds"}
+        if checks:
+            c_ms, c_n = ctx.kernel_timing(enable=False)
+            cold_ms = c0.elapsed_time(c1) / args.steps
+            cold_start = {"ms_per_step": cold_ms, "value": n_reads / (cold_ms * 1e-3), "unit": "reads/s", "dominant_kernel_avg_launch_ms": c_ms / max(c_n, 1),
+                          "how": f"{args.warmup} warm-up + {args.steps} timed steps (device time between two events) FIRST, before anything else ran on "
+                                 "the device since the batch was built: a device that has idled for seconds"}
     spinup_steps = 0
     if args.spinup_ms > 0:
         # (mapping only, no reduce: the loop runs by the clock, so the ranks of a job do not run it equally often -- and collectives are matched
@@ -698,7 +718,7 @@ def main():
     counters = ctx.counters()
     # N > 1: the vector every rank holds must be the sum of the ranks' own vectors (one more, untimed, pass + reduce)
     reduce_consistent = None
-    if world > 1:
+    if world > 1 and args.full:
         own = torch.zeros_like(acc)
         with torch.cuda.stream(stream):
             ctx.map_device(bases.data_ptr(), offsets.data_ptr(), n_reads, n_bases, own.data_ptr(), own.data_ptr() + 8 * ctx.n_knodes,
@@ -711,7 +731,7 @@ def main():
         dist.all_reduce(ok, op=dist.ReduceOp.MIN)
         reduce_consistent = bool(ok.item())
     shard_invariant = kernels_agree = packed_equals_ascii = None
-    if world == 1 and not args.no_checks:
+    if world == 1 and checks:
         if packed:  # the packed batch must give what the ASCII batch gives, at full size
             ref = torch.zeros_like(acc)
             map_range(ctx, bases, offsets, 0, n_reads, ref[: 2 * ctx.n_knodes], ref[2 * ctx.n_knodes:], stream, torch)
@@ -720,7 +740,7 @@ def main():
     # The same batch in the OTHER input format, outside the timed region: the headline is the ASCII batch (B(L) = L + 8 bytes per read are
     # really read); the executables' ingest hands over 2-bit packed words, so the line carries that step as well ("packed_input").
     packed_leg = None
-    if world == 1 and not args.no_checks and not packed and os.environ.get("DRPRG_BENCH_PACKED_LEG", "1") != "0":
+    if world == 1 and checks and not packed and os.environ.get("DRPRG_BENCH_PACKED_LEG", "1") != "0":
         pw = torch.zeros((n_bases + 15) // 16 + 4, dtype=torch.int32, device=device)
         pn = torch.zeros(1 << 16, dtype=torch.int64, device=device)
         torch.cuda.synchronize()  # (as above)
@@ -771,7 +791,7 @@ def main():
     # again finds a little of itself in the memory-side cache (256 MB).  What a stream of different batches runs at ("other_batches_in_rotation";
     # profiles/r06/schedule.txt section 11: 1.3-2.8 % below the repeated batch for ASCII input, nothing for packed).
     rotation_leg = None
-    if world == 1 and not args.no_checks and not packed and os.environ.get("DRPRG_BENCH_ROTATION_LEG", "1") != "0":
+    if world == 1 and checks and not packed and os.environ.get("DRPRG_BENCH_ROTATION_LEG", "1") != "0":
         hp = torch.from_numpy(genomes.padded()).to(device)
         rot = [(bases, offsets, n_bases)]
         for sd in (101, 102):
@@ -935,7 +955,7 @@ def main():
         # once on one thread and once with the reads split over the host's cores (threads calling the same C function on
         # disjoint read ranges; integer coverage sums commute).  The multi-thread sample is as large as ~10 s allow -- with
         # enough cores the whole batch -- and the HIP path must give the identical vector on it.
-        if args.cpu_sample != 0 and world == 1:  # (rank 0 at N=1 only)
+        if args.full and args.cpu_sample != 0 and world == 1:  # (rank 0 at N=1 only)
             from concurrent.futures import ThreadPoolExecutor
             from util import Oracle, cluster_fraction, map_params
             orc = Oracle()
@@ -992,7 +1012,7 @@ def main():
                                    "single_thread_value": ns1 / cpu1_s, "single_thread_sample": f"first {ns1} reads, {cpu1_s:.1f}s",
                                    "host_cores_available": os.cpu_count(), "cpu_model": cpu_model(), "parity_vs_hip_on_sample": parity,
                                    "genotyped_vcf_identical_to_oracle_on_sample": vcf_parity}
-        if args.e2e and world == 1 and args.workload != "nanopore" and not args.no_checks:
+        if checks and args.e2e and world == 1 and args.workload != "nanopore":
             try:
                 out["e2e"] = e2e_leg(torch, ctx, synth, bases, n_reads, args.read_len, covg)
             except Exception as exc:  # (no room in /dev/shm, ...: the bench line must not depend on this leg)

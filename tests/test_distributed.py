@@ -133,7 +133,7 @@ def test_bench_ranks_whose_spin_ups_differ(comm):
     import json
     env = dict(os.environ, DRPRG_BENCH_BACKEND="gloo", DRPRG_BENCH_SPINUP_SKEW_MS="120", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--reads-per-gpu", "300000", "--steps", "3", "--warmup", "2", "--spinup-ms", "60",
-           "--cpu-sample", "0", "--e2e", "0", "--comm", comm]
+           "--cpu-sample", "0", "--e2e", "0", "--comm", comm, "--full"]
     p = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=280)
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads([x for x in p.stdout.splitlines() if x.startswith("{")][-1])

@@ -569,6 +569,35 @@ def test_full_size_properties(tmp_path, name, illumina, n_reads):
     assert torch.equal(twice, 2 * covg)
 
 
+def test_bench_plain_and_full_lines():
+    """bench.py on one GPU, small batch: a plain run carries the headline and nothing that needs work outside the timed steps;
+    --full adds cold_start, the full-size checks, the packed leg, cpu_baseline and e2e, and every check among them holds."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--reads-per-gpu", "200000", "--steps", "3", "--warmup", "2",
+           "--spinup-ms", "50"]
+    lines = {}
+    for name, extra in (("plain", []), ("full", ["--full", "--cpu-sample", "2000"])):
+        p = subprocess.run(cmd + extra, cwd=root, capture_output=True, text=True, timeout=280)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines[name] = json.loads([x for x in p.stdout.splitlines() if x.startswith("{")][-1])
+    plain, full = lines["plain"], lines["full"]
+    for line in (plain, full):
+        assert line["unit"] == "reads/s" and line["higher_is_better"] is True and line["dtype"] == "u32"
+        assert line["value"] > 0 and line["ms_per_step"] > 0 and line["steps"] == 3 and line["warmup"] == 2
+    assert plain["cold_start"] is None and plain["config"]["full_size_shard_invariance"] is None
+    assert not {"cpu_baseline", "e2e", "packed_input", "other_batches_in_rotation"} & set(plain)
+    assert full["cold_start"]["ms_per_step"] > 0
+    assert full["config"]["full_size_shard_invariance"] is True and full["config"]["full_size_direct_vs_filtered_kernel_identical"] is not False
+    assert full["packed_input"]["coverage_equals_the_ascii_run"] is True
+    assert full["other_batches_in_rotation"]["ms_per_step"] > 0
+    assert full["cpu_baseline"]["parity_vs_hip_on_sample"] is True
+    assert full["e2e"]["plain"]["coverage_equals_hbm_resident_run"] is True
+    assert full["config"]["coverage_checksum"] == plain["config"]["coverage_checksum"]
+
+
 def test_multi_device_context_equals_single(tmp_path, oracle):
     """drprg_hip_open_multi (native host path): map_fastx shards the ingest blocks over the listed devices and sums
     their coverage vectors into the first.  On a one-GPU box the list names device 0 twice -- two mappers, two streams, the

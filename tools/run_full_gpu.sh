@@ -3,7 +3,7 @@
 tag=${1:-full}
 out=gpurun_out/r03; mkdir -p $out
 timeout 1500 python -m pytest tests -x -q -m gpu > $out/${tag}_gputests.txt 2>&1; tail -5 $out/${tag}_gputests.txt
-timeout 300 python bench.py --steps 20 --warmup 5 > $out/${tag}_bench_mtb.json 2> $out/${tag}_bench_mtb.err; tail -2 $out/${tag}_bench_mtb.err
+timeout 300 python bench.py --full --steps 20 --warmup 5 > $out/${tag}_bench_mtb.json 2> $out/${tag}_bench_mtb.err; tail -2 $out/${tag}_bench_mtb.err
 python - <<PY
 import json
 d = json.loads(open("$out/${tag}_bench_mtb.json").read().strip().splitlines()[-1])

@@ -6,12 +6,12 @@
 tag=${1:-h}
 O=gpurun_out/r03/$tag; mkdir -p $O
 R=${GRAFT_REPO_ROOT:-$PWD}
-timeout 400 python bench.py --steps 20 --warmup 5 > $O/bench_mtb.json 2> $O/bench_mtb.err
-timeout 400 python bench.py --workload nanopore --steps 5 > $O/bench_nanopore.json 2> $O/bench_nanopore.err
-timeout 400 python bench.py --workload big --steps 5 > $O/bench_big.json 2> $O/bench_big.err
-DRPRG_BENCH_BACKEND=gloo timeout 300 python bench.py --gpus 2 --steps 5 --warmup 1 --cpu-sample 0 2> $O/bench_gloo2.err | grep '^{' > $O/bench_gloo_2ranks_one_gpu.json
+timeout 400 python bench.py --full --steps 20 --warmup 5 > $O/bench_mtb.json 2> $O/bench_mtb.err
+timeout 400 python bench.py --full --workload nanopore --steps 5 > $O/bench_nanopore.json 2> $O/bench_nanopore.err
+timeout 400 python bench.py --full --workload big --steps 5 > $O/bench_big.json 2> $O/bench_big.err
+DRPRG_BENCH_BACKEND=gloo timeout 300 python bench.py --full --gpus 2 --steps 5 --warmup 1 --cpu-sample 0 2> $O/bench_gloo2.err | grep '^{' > $O/bench_gloo_2ranks_one_gpu.json
 for wl in mtb-dense mtb-x2 mtb-x4 mtb-x8 mtb-x16 mtb-x32; do
-  timeout 300 python bench.py --workload $wl --steps 10 --warmup 3 --cpu-sample 0 --e2e 0 > $O/bench_$wl.json 2> $O/bench_$wl.err
+  timeout 300 python bench.py --full --workload $wl --steps 10 --warmup 3 --cpu-sample 0 --e2e 0 > $O/bench_$wl.json 2> $O/bench_$wl.err
 done
 DRPRG_BENCH_KERNEL=3 timeout 300 python bench.py --workload mtb-x8 --steps 10 --warmup 3 --cpu-sample 0 --e2e 0 --no-checks > $O/bench_mtb-x8_direct.json 2> /dev/null
 DRPRG_MID_MAX_RECORDS=1000000 timeout 300 python bench.py --workload mtb-x16 --steps 10 --warmup 3 --cpu-sample 0 --e2e 0 --no-checks > $O/bench_mtb-x16_middle_tier.json 2> /dev/null

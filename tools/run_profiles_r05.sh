@@ -7,15 +7,15 @@
 tag=${1:-z}
 O=gpurun_out/r05/$tag; mkdir -p $O
 R=${GRAFT_REPO_ROOT:-$PWD}
-timeout 400 python bench.py > $O/bench_mtb.json 2> $O/bench_mtb.err
-timeout 400 python bench.py --input packed > $O/bench_mtb_packed.json 2> $O/bench_mtb_packed.err
-timeout 400 python bench.py --workload nanopore --steps 5 > $O/bench_nanopore.json 2> $O/bench_nanopore.err
-timeout 400 python bench.py --workload big --steps 5 > $O/bench_big.json 2> $O/bench_big.err
+timeout 400 python bench.py --full > $O/bench_mtb.json 2> $O/bench_mtb.err
+timeout 400 python bench.py --full --input packed > $O/bench_mtb_packed.json 2> $O/bench_mtb_packed.err
+timeout 400 python bench.py --full --workload nanopore --steps 5 > $O/bench_nanopore.json 2> $O/bench_nanopore.err
+timeout 400 python bench.py --full --workload big --steps 5 > $O/bench_big.json 2> $O/bench_big.err
 for comm in native torch; do for n in 2 8; do
-  DRPRG_BENCH_BACKEND=gloo timeout 600 python bench.py --gpus $n --steps 5 --warmup 1 --cpu-sample 0 --comm $comm 2> $O/bench_gloo${n}_$comm.err | grep '^{' > $O/bench_${comm}_gloo_${n}ranks_one_gpu.json
+  DRPRG_BENCH_BACKEND=gloo timeout 600 python bench.py --full --gpus $n --steps 5 --warmup 1 --cpu-sample 0 --comm $comm 2> $O/bench_gloo${n}_$comm.err | grep '^{' > $O/bench_${comm}_gloo_${n}ranks_one_gpu.json
 done; done
 for wl in mtb-dense mtb-x2 mtb-x4 mtb-x8 mtb-x16 mtb-x32; do
-  timeout 300 python bench.py --workload $wl --steps 10 --warmup 3 --cpu-sample 0 --e2e 0 > $O/bench_$wl.json 2> $O/bench_$wl.err
+  timeout 300 python bench.py --full --workload $wl --steps 10 --warmup 3 --cpu-sample 0 --e2e 0 > $O/bench_$wl.json 2> $O/bench_$wl.err
 done
 cd /tmp && export TMPDIR=/tmp
 for wl in mtb mtb-dense mtb-x2 mtb-x4 mtb-x8 mtb-x16 mtb-x32 nanopore big; do

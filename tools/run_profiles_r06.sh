@@ -17,24 +17,24 @@ O=gpurun_out/r06/$tag; mkdir -p $O
 R=${GRAFT_REPO_ROOT:-$PWD}
 SERIES="mtb-dense mtb-x2 mtb-x4 mtb-x8 mtb-x16 mtb-x32"
 if has bench; then
-  timeout 500 python bench.py > $O/bench_mtb.json 2> $O/bench_mtb.err
+  timeout 500 python bench.py --full > $O/bench_mtb.json 2> $O/bench_mtb.err
   timeout 400 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_mtb_driver_command.json 2> $O/bench_mtb_driver_command.err
-  timeout 400 python bench.py --input packed --cpu-sample 0 --e2e 0 > $O/bench_mtb_packed.json 2> $O/bench_mtb_packed.err
-  timeout 400 python bench.py --workload nanopore --steps 10 --warmup 3 --e2e 0 > $O/bench_nanopore.json 2> $O/bench_nanopore.err
-  timeout 400 python bench.py --workload nanopore --input packed --steps 10 --warmup 3 --cpu-sample 0 --e2e 0 > $O/bench_nanopore_packed.json 2> $O/bench_nanopore_packed.err
-  DRPRG_FILTER_STAGE2=lds timeout 400 python bench.py --input packed --steps 20 --warmup 5 --cpu-sample 0 --e2e 0 > $O/bench_mtb_packed_all_lds_second_stage.json 2> /dev/null
-  DRPRG_FILTER_STAGE2=l2 timeout 400 python bench.py --steps 20 --warmup 5 --cpu-sample 0 --e2e 0 > $O/bench_mtb_l2_second_stage.json 2> /dev/null
-  timeout 400 python bench.py --workload big --steps 10 --warmup 3 --e2e 0 > $O/bench_big.json 2> $O/bench_big.err
-  DRPRG_FT_SCHED=static timeout 400 python bench.py --gpus 1 --steps 20 --warmup 5 --cpu-sample 0 --e2e 0 > $O/bench_mtb_static_schedule.json 2> $O/bench_mtb_static_schedule.err
+  timeout 400 python bench.py --full --input packed --cpu-sample 0 --e2e 0 > $O/bench_mtb_packed.json 2> $O/bench_mtb_packed.err
+  timeout 400 python bench.py --full --workload nanopore --steps 10 --warmup 3 --e2e 0 > $O/bench_nanopore.json 2> $O/bench_nanopore.err
+  timeout 400 python bench.py --full --workload nanopore --input packed --steps 10 --warmup 3 --cpu-sample 0 --e2e 0 > $O/bench_nanopore_packed.json 2> $O/bench_nanopore_packed.err
+  DRPRG_FILTER_STAGE2=lds timeout 400 python bench.py --full --input packed --steps 20 --warmup 5 --cpu-sample 0 --e2e 0 > $O/bench_mtb_packed_all_lds_second_stage.json 2> /dev/null
+  DRPRG_FILTER_STAGE2=l2 timeout 400 python bench.py --full --steps 20 --warmup 5 --cpu-sample 0 --e2e 0 > $O/bench_mtb_l2_second_stage.json 2> /dev/null
+  timeout 400 python bench.py --full --workload big --steps 10 --warmup 3 --e2e 0 > $O/bench_big.json 2> $O/bench_big.err
+  DRPRG_FT_SCHED=static timeout 400 python bench.py --full --gpus 1 --steps 20 --warmup 5 --cpu-sample 0 --e2e 0 > $O/bench_mtb_static_schedule.json 2> $O/bench_mtb_static_schedule.err
 fi
 if has ranks; then
   for comm in native torch; do for n in 2 8; do
-    DRPRG_BENCH_BACKEND=gloo timeout 600 python bench.py --gpus $n --steps 5 --warmup 1 --cpu-sample 0 --comm $comm 2> $O/bench_gloo${n}_$comm.err | grep '^{' > $O/bench_${comm}_gloo_${n}ranks_one_gpu.json
+    DRPRG_BENCH_BACKEND=gloo timeout 600 python bench.py --full --gpus $n --steps 5 --warmup 1 --cpu-sample 0 --comm $comm 2> $O/bench_gloo${n}_$comm.err | grep '^{' > $O/bench_${comm}_gloo_${n}ranks_one_gpu.json
   done; done
 fi
 if has series; then
   for wl in $SERIES; do
-    timeout 300 python bench.py --workload $wl --steps 20 --warmup 5 --cpu-sample 0 --e2e 0 > $O/bench_$wl.json 2> $O/bench_$wl.err
+    timeout 300 python bench.py --full --workload $wl --steps 20 --warmup 5 --cpu-sample 0 --e2e 0 > $O/bench_$wl.json 2> $O/bench_$wl.err
     DRPRG_FT_SCHED=static timeout 300 python bench.py --workload $wl --steps 20 --warmup 5 --cpu-sample 0 --e2e 0 --no-checks > $O/bench_${wl}_static_schedule.json 2> /dev/null
   done
 fi

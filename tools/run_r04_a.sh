@@ -5,9 +5,9 @@ tag=${1:-a}
 O=gpurun_out/r04/$tag; mkdir -p $O
 timeout 1500 python -m pytest tests -x -q -m gpu > $O/gputests.txt 2>&1; tail -5 $O/gputests.txt
 timeout 300 build/tools/mb_issue > $O/mb_issue.txt 2>&1; head -30 $O/mb_issue.txt
-timeout 400 python bench.py --steps 20 --warmup 5 > $O/bench_mtb.json 2> $O/bench_mtb.err; tail -2 $O/bench_mtb.err
+timeout 400 python bench.py --full --steps 20 --warmup 5 > $O/bench_mtb.json 2> $O/bench_mtb.err; tail -2 $O/bench_mtb.err
 for comm in native torch; do
-  DRPRG_BENCH_BACKEND=gloo timeout 300 python bench.py --gpus 2 --steps 5 --warmup 1 --cpu-sample 0 --comm $comm 2> $O/bench_gloo2_$comm.err | grep '^{' > $O/bench_${comm}_gloo_2ranks_one_gpu.json
+  DRPRG_BENCH_BACKEND=gloo timeout 300 python bench.py --full --gpus 2 --steps 5 --warmup 1 --cpu-sample 0 --comm $comm 2> $O/bench_gloo2_$comm.err | grep '^{' > $O/bench_${comm}_gloo_2ranks_one_gpu.json
   tail -3 $O/bench_gloo2_$comm.err
 done
 python - <<PY

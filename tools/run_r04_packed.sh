@@ -4,8 +4,8 @@
 tag=${1:-p}
 O=gpurun_out/r04/$tag; mkdir -p $O
 R=${GRAFT_REPO_ROOT:-$PWD}
-timeout 400 python bench.py --steps 20 --warmup 5 > $O/bench_mtb.json 2> $O/bench_mtb.err
-timeout 400 python bench.py --steps 20 --warmup 5 --input packed > $O/bench_mtb_packed.json 2> $O/bench_mtb_packed.err
+timeout 400 python bench.py --full --steps 20 --warmup 5 > $O/bench_mtb.json 2> $O/bench_mtb.err
+timeout 400 python bench.py --full --steps 20 --warmup 5 --input packed > $O/bench_mtb_packed.json 2> $O/bench_mtb_packed.err
 tail -3 $O/bench_mtb_packed.err
 cd /tmp && export TMPDIR=/tmp
 for inp in ascii packed; do

@@ -5,7 +5,7 @@ O=gpurun_out/r04/$tag; mkdir -p $O
 R=${GRAFT_REPO_ROOT:-$PWD}
 timeout 1200 python -m pytest tests -x -q -m gpu -k "$sel" > $O/gputests.txt 2>&1; tail -4 $O/gputests.txt
 for inp in ascii packed; do
-  timeout 300 python bench.py --steps 20 --warmup 5 --input $inp --cpu-sample 0 --e2e 0 > $O/bench_$inp.json 2> $O/bench_$inp.err
+  timeout 300 python bench.py --full --steps 20 --warmup 5 --input $inp --cpu-sample 0 --e2e 0 > $O/bench_$inp.json 2> $O/bench_$inp.err
 done
 cd /tmp && export TMPDIR=/tmp
 for inp in ascii packed; do

@@ -16,7 +16,7 @@ for wl in $wls; do for inp in $inputs; do
   for v in "${VARS[@]}"; do
     name=${v%%:*}; envs=${v#*:}
     ( IFS="@"; for e in $envs; do [ -n "$e" ] && export "$e"; done; unset IFS
-      timeout 400 python bench.py --workload $wl --steps ${STEPS:-20} --warmup ${WARMUP:-5} --input $inp --cpu-sample 0 --e2e 0 > $O/bench_${wl}_${name}_$inp.json 2> $O/bench_${wl}_${name}_$inp.err
+      timeout 400 python bench.py --full --workload $wl --steps ${STEPS:-20} --warmup ${WARMUP:-5} --input $inp --cpu-sample 0 --e2e 0 > $O/bench_${wl}_${name}_$inp.json 2> $O/bench_${wl}_${name}_$inp.err
       if [ -z "$NOPROF" ]; then
         ( cd /tmp && export TMPDIR=/tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof -o k -- python3 $R/bench.py --workload $wl --input $inp --steps 20 --warmup 5 --cpu-sample 0 --e2e 0 --no-checks > /dev/null 2>&1 )
         echo "== $wl $name $inp"; python tools/kstats.py $O/prof/k_kernel_stats.csv | grep -v rocclr
