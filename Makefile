@@ -9,13 +9,9 @@ HIPFLAGS := $(CXXFLAGS) --offload-arch=$(ARCH)
 
 SRC  := drprg_amd/csrc
 OBJD := build/obj
-HOST_SRCS := prg.cpp kmergraph.cpp index.cpp fastx.cpp genotype.cpp params.cpp denovo.cpp mapper.cpp capi.cpp vcfio.cpp bcfout.cpp annotate.cpp report_json.cpp ingest.cpp pgunzip.cpp rccl_dyn.cpp pack.cpp
+HOST_SRCS := prg.cpp kmergraph.cpp index.cpp fastx.cpp genotype.cpp params.cpp denovo.cpp mapper.cpp capi.cpp vcfio.cpp bcfout.cpp annotate.cpp report_json.cpp ingest.cpp pgunzip.cpp rccl_dyn.cpp pack.cpp switches.cpp
 HIP_SRCS := sketch_probe.hip sketch_wave.hip sketch_filter.hip candidates.hip read_cluster.hip cluster.hip anchor_scan.hip packed.hip
 LIB  := drprg_amd/lib/libdrprg_hip.so
-# EXTRA_DEFS: build-time knobs for measurement builds (tools/rc_variants.sh), e.g. make OBJD=build/obj_x LIB=build/x/libdrprg_hip.so EXTRA_DEFS=-DDRPRG_RC_PER=4
-EXTRA_DEFS ?=
-CXXFLAGS += $(EXTRA_DEFS)
-HIPFLAGS += $(EXTRA_DEFS)
 OBJS := $(addprefix $(OBJD)/,$(HOST_SRCS:.cpp=.o)) $(addprefix $(OBJD)/,$(HIP_SRCS:.hip=.o))
 BIN  := drprg_amd/bin/pandora
 ORACLE := oracle/liboracle.so

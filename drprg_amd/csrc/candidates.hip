@@ -5,8 +5,6 @@
 #include "filter_common.h"
 #include "verify_lane.h"
 #include <algorithm>
-#include <cstdlib>
-#include <string>
 #include <cstdint>
 
 namespace drprg {
@@ -24,13 +22,10 @@ namespace dev {
 // bisects the superblocks of its workgroup's share, a handful of a full batch), there in the slice the eight slice counts of the superblock
 // say (one more round trip to the L2, requested a candidate ahead like the position itself), at raw_pos[start of the slice + rest].  Workgroup
 // 0 leaves the total where read_cluster_kernel and the generic pipeline look for it (*fw.cand_total).
-#ifndef DRPRG_VS_THREADS // (measurement builds)
-#define DRPRG_VS_THREADS 512
-#endif
 // threads per workgroup: every workgroup pays the slice scan once, so fewer and larger ones pay less of it -- 256 (8 per CU) measured 0.516 ms
 // per step on the 8d index (packed 0.452), 512 (4 per CU) 0.503-0.512 (0.445), 1024 (2 per CU) 0.507-0.514 (0.447); the larger indexes do
 // not care (profiles/r05/verify_scan.txt)
-constexpr int VS_THREADS = DRPRG_VS_THREADS;
+constexpr int VS_THREADS = 512;
 constexpr int VS_PER = MAX_SLICES / VS_THREADS; // superblocks per thread of the scan
 template <int KC, bool PACKED>
 __global__ __launch_bounds__(VS_THREADS, 8) void verify_scan_kernel(SketchArgs a, FilterWork fw, ReadClusterArgs rc) // (8 waves per SIMD = 64 VGPRs: the ASCII form wants 74 and spills 28 bytes per lane, and is still faster for the eighth wave: 102 -> 97 us, nanopore 424 -> 383 us)
@@ -54,7 +49,6 @@ __global__ __launch_bounds__(VS_THREADS, 8) void verify_scan_kernel(SketchArgs a
     uint32_t total;
     const uint32_t before = block_exclusive_scan<VS_THREADS / 64>(run, s_w, &total);
     if (blockIdx.x == 0 && tid == 0) *fw.cand_count = total; // = *fw.cand_total
-    if (fw.debug & 2048u) return; // (DRPRG_FT_DEBUG=2048: measurement only, the slice scan alone)
     // Every thread leaves the prefixes of its own slices in LDS, out of the counts it still holds: entry t of the list then lives in the
     // slice s with s_pre[s] <= t < s_pre[s + 1], for every t, and no workgroup reads a count twice.  (Until late in round 5 a window of 64
     // prefixes was rebuilt -- one more dependent load, a wave scan and two barriers: 3-4.5 us per workgroup -- every 64 slices of its share.)
@@ -124,7 +118,7 @@ __global__ __launch_bounds__(VS_THREADS, 8) void verify_scan_kernel(SketchArgs a
             const int64_t gp = gp_next;
             if (t + VS_THREADS < t_end) gp_next = position_of(t + VS_THREADS);
             VerifyOut o;
-            if (!(fw.debug & 512u)) verify_one_lane<KC, PACKED>(a, fw, rc, c, gp, o, my_hits, my_nmin, my_maxlen); // (DRPRG_FT_DEBUG=512: measurement only, the scan and the positions alone)
+            verify_one_lane<KC, PACKED>(a, rc, c, gp, o, my_hits, my_nmin, my_maxlen);
             fw.cand_pos1[t] = o.pos1;
             fw.cand_info[t] = ((uint64_t)o.slot << 32) | ((uint64_t)o.strand << 31) | (uint64_t)o.read;
             fw.cand_rec[t] = o.crec;
@@ -438,10 +432,9 @@ __global__ __launch_bounds__(TG_THREADS) void tile_gather_kernel(SketchArgs a, F
 // launch: DESIGN.md section 6, profiles/r05/verify_scan.txt and read_verify.txt)
 hipError_t launch_candidate_stage(const SketchArgs& a, FilterWork& fw, const ReadClusterArgs& rc, int n_cus, hipStream_t stream, bool with_totals)
 {
-    // (DRPRG_VERIFY_WG_PER_CU: measurements.  The grid is what fills the CUs' 2048 thread slots: fewer or more workgroups per CU measured
-    // within the noise or worse; profiles/r05/verify_scan.txt)
-    static const int per_cu = [] { const char* e = std::getenv("DRPRG_VERIFY_WG_PER_CU"); return e ? std::max(1, std::atoi(e)) : 0; }();
-    fw.verify_grid = std::min<uint32_t>((uint32_t)n_cus * (uint32_t)(per_cu ? per_cu : 2048 / VS_THREADS), MAX_EX_WG); // (2048 threads per CU)
+    // (the grid is what fills the CUs' 2048 thread slots: fewer or more workgroups per CU measured within the noise or worse;
+    // profiles/r05/verify_scan.txt)
+    fw.verify_grid = std::min<uint32_t>((uint32_t)n_cus * (uint32_t)(2048 / VS_THREADS), MAX_EX_WG);
     const dim3 grid(fw.verify_grid);
     if (a.packed) {
         if (a.k == 15) hipLaunchKernelGGL((verify_scan_kernel<15, true>), grid, dim3(VS_THREADS), 0, stream, a, fw, rc);
@@ -452,34 +445,25 @@ hipError_t launch_candidate_stage(const SketchArgs& a, FilterWork& fw, const Rea
     return hipGetLastError();
 }
 
-// DRPRG_DIRECT_FORM=lds keeps sketch_probe_kernel for every (k, w) (A/B runs, and a second way through the parity tests)
-static bool use_wave_form(int k, int w, bool wide_hash)
+// force_lds (DRPRG_DIRECT_FORM=lds) keeps sketch_probe_kernel for every (k, w) (A/B runs, and a second way through the parity tests)
+bool direct_uses_wave_form(int k, int w, bool wide_hash, bool force_lds) { return !wide_hash && !force_lds && wave_kernel_applies(k, w); }
+
+uint32_t direct_candidate_tiles(uint64_t n_bases, int halo, int k, int w, bool wide_hash, bool force_lds)
 {
-    static const bool forced_lds = [] {
-        const char* e = std::getenv("DRPRG_DIRECT_FORM");
-        return e && std::string(e) == "lds";
-    }();
-    return !wide_hash && !forced_lds && wave_kernel_applies(k, w);
+    return direct_uses_wave_form(k, w, wide_hash, force_lds) ? wave_n_slices(n_bases) : sketch_n_tiles(n_bases, halo);
 }
 
-bool direct_uses_wave_form(int k, int w, bool wide_hash) { return use_wave_form(k, w, wide_hash); }
-
-uint32_t direct_candidate_tiles(uint64_t n_bases, int halo, int k, int w, bool wide_hash)
+uint32_t direct_first_read_tiles(uint64_t n_bases, int halo, int k, int w, bool wide_hash, bool force_lds)
 {
-    return use_wave_form(k, w, wide_hash) ? wave_n_slices(n_bases) : sketch_n_tiles(n_bases, halo);
+    return direct_uses_wave_form(k, w, wide_hash, force_lds) ? wave_n_tiles(n_bases) : sketch_n_tiles(n_bases, halo);
 }
 
-uint32_t direct_first_read_tiles(uint64_t n_bases, int halo, int k, int w, bool wide_hash)
-{
-    return use_wave_form(k, w, wide_hash) ? wave_n_tiles(n_bases) : sketch_n_tiles(n_bases, halo);
-}
-
-hipError_t launch_direct_candidates(const SketchArgs& a, bool wide_hash, uint32_t* tile_prefix, void* temp, size_t temp_bytes,
+hipError_t launch_direct_candidates(const SketchArgs& a, bool wide_hash, bool force_lds, uint32_t* tile_prefix, void* temp, size_t temp_bytes,
     uint64_t dense_capacity, const ReadClusterArgs& rc, int n_cus, FilterWork& fw, hipStream_t stream, KernelTimer timer, uint32_t slices_mark)
 {
     if (a.n_bases == 0 || !a.tile_cap || !slices_mark) return hipErrorInvalidValue;
-    const uint32_t n_tiles = direct_candidate_tiles(a.n_bases, a.halo, a.k, a.w, wide_hash);
-    if (use_wave_form(a.k, a.w, wide_hash)) HIP_TRY(launch_sketch_wave(a, stream, timer));
+    const uint32_t n_tiles = direct_candidate_tiles(a.n_bases, a.halo, a.k, a.w, wide_hash, force_lds);
+    if (direct_uses_wave_form(a.k, a.w, wide_hash, force_lds)) HIP_TRY(launch_sketch_wave(a, stream, timer));
     else HIP_TRY(launch_sketch_probe(a, wide_hash, stream, timer));
     // tile_count[n_tiles] is a zero the caller keeps there: the exclusive scan of n_tiles + 1 counts ends with the total
     HIP_TRY(exclusive_scan_u32(temp, temp_bytes, a.tile_count, tile_prefix, n_tiles + 1, stream));

@@ -245,7 +245,7 @@ int drprg_hip_index(const char* prg_file, int w, int k, int threads)
 {
     if (!prg_file) return DRPRG_EINVAL;
     try {
-        PrgIndex::build_and_save(prg_file, w, k, threads > 0 ? threads : 1);
+        PrgIndex::build_and_save(prg_file, w, k, threads > 0 ? threads : 1, read_switches());
     } catch (const Error& e) {
         g_last_error = e.what();
         return e.code;
@@ -277,20 +277,21 @@ static drprg_hip_ctx* open_impl(const char* prg_file, int w, int k, int device, 
     } join_warm { warm };
     try {
         ctx->prg_file = prg_file;
+        const Switches sw = read_switches(); // (the filter tier's; every Mapper reads its own)
         if (from_files) {
             // The k-mer graphs and the .idx beside the PRG are this build's own files.  An index directory made by the real
             // pandora holds files of the same names in pandora's private format: they are not parsed, the graphs are rebuilt
             // from the PRG string (tens of milliseconds for an mtb-sized panel), unless DRPRG_HIP_STRICT_INDEX is set.
             try {
-                ctx->index.load(prg_file, w, k);
+                ctx->index.load(prg_file, w, k, sw);
             } catch (const Error& e) {
                 const char* strict = std::getenv("DRPRG_HIP_STRICT_INDEX");
                 if ((e.code != DRPRG_EFORMAT && e.code != DRPRG_ENOENT) || (strict && *strict && *strict != '0')) throw;
                 std::fprintf(stderr, "drprg-hip: warning: %s; rebuilding the k-mer graphs from %s\n", e.what(), prg_file);
                 ctx->index = PrgIndex();
-                ctx->index.build(prg_file, w, k, threads > 0 ? threads : 1);
+                ctx->index.build(prg_file, w, k, threads > 0 ? threads : 1, sw);
             }
-        } else ctx->index.build(prg_file, w, k, threads > 0 ? threads : 1);
+        } else ctx->index.build(prg_file, w, k, threads > 0 ? threads : 1, sw);
         ctx->params.w = w;
         ctx->params.k = k;
         apply_defaults(ctx->params, nullptr);

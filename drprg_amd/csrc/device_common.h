@@ -128,14 +128,6 @@ __device__ inline uint32_t table_slot_dev(uint64_t key, uint32_t bits)
 __device__ __forceinline__ bool table_find4(const uint32_t* __restrict__ slot_key, uint32_t tmask, uint32_t h, uint32_t& sl)
 {
     constexpr uint32_t EMPTY = HashTraits<uint32_t>::EMPTY;
-#ifdef DRPRG_PROBE_LINEAR // (measurement builds: one slot per round trip, rounds 1-4)
-    while (true) {
-        const uint32_t key = slot_key[sl];
-        if (key == h) return true;
-        if (key == EMPTY) return false;
-        sl = (sl + 1) & tmask;
-    }
-#endif
     uint32_t base = sl & ~3u, from = 0xFu << (sl & 3u);
     while (true) {
         const uint4 q = *reinterpret_cast<const uint4*>(slot_key + base);

@@ -28,7 +28,7 @@ std::string PrgIndex::gfa_path(const std::string& prg_file, const std::string& n
     return dir_of(prg_file) + "/kmer_prgs/" + name + ".k" + std::to_string(k) + ".w" + std::to_string(w) + ".gfa";
 }
 
-void PrgIndex::build(const std::string& prg_file, int w_, int k_, int threads)
+void PrgIndex::build(const std::string& prg_file, int w_, int k_, int threads, const Switches& sw)
 {
     if (k_ < 1 || k_ > 32 || w_ < 1) throw Error(DRPRG_EINVAL, "need 1 <= k <= 32 and w >= 1");
     w = w_;
@@ -53,10 +53,10 @@ void PrgIndex::build(const std::string& prg_file, int w_, int k_, int threads)
     work();
     for (auto& t : pool) t.join();
     if (failed) throw Error(DRPRG_EFORMAT, err);
-    flatten();
+    flatten(sw);
 }
 
-void PrgIndex::flatten()
+void PrgIndex::flatten(const Switches& sw)
 {
     FlatIndex& f = flat;
     f = FlatIndex();
@@ -129,8 +129,8 @@ void PrgIndex::flatten()
     constexpr uint32_t L0_WBITS = 15;
     const bool small_tier = k <= 15 && entries > 0 && entries <= 3 * (size_t(1) << MAX_WBITS);
     const bool level0 = small_tier && k == 15 && 4 * entries * 3 <= (size_t(32) << L0_WBITS) / 2;
-    const bool force_mid = k == 15 && std::getenv("DRPRG_FORCE_MID_TIER") != nullptr; // (tests: small panels through the middle tier)
-    if (small_tier && !force_mid && (level0 || k < 15 || std::getenv("DRPRG_NO_MID_TIER"))) {
+    const bool force_mid = k == 15 && sw.force_mid_tier; // (tests: small panels through the middle tier)
+    if (small_tier && !force_mid && (level0 || k < 15)) {
         // level 0 (k = 15 and a small index only): a second array of 2^15 words keyed on the 12-mers at offsets 0..3 of
         // every index k-mer, so that the kernel probes one 12-mer per four read positions (the 12-mer at 4g+3 lies
         // inside every 15-mer that starts at 4g..4g+3).  Levels 1+2 then get 32 KB: 160 KB of LDS in all.
@@ -191,22 +191,7 @@ void PrgIndex::flatten()
                 }
             });
         }
-        if (level0 && std::getenv("DRPRG_FT_STATS")) { // how full the level-0 array is, alone and with the second stage's bits in it, and what
-            // a random 12-mer's three-bit test passes at in each (mean over the words of (bits / 32)^3: the third bit's position comes from the key itself)
-            auto stat = [](const std::vector<uint32_t>& a, const char* name) {
-                double bits = 0, p3 = 0;
-                for (uint32_t wd : a) {
-                    const double b = (double)__builtin_popcount(wd);
-                    bits += b;
-                    p3 += (b / 32) * (b / 32) * (b / 32);
-                }
-                std::fprintf(stderr, "[filter] %s: %.1f %% of %zu bits set, a random key passes the three-bit test at %.2f %%\n", name, 100 * bits / (32.0 * a.size()),
-                    32 * a.size(), 100 * p3 / a.size());
-            };
-            stat(f.bloom0, "level 0 alone");
-            stat(f.bloom0f, "level 0 + second-stage bits");
-        }
-    } else if (k == 15 && entries > 0 && !std::getenv("DRPRG_NO_MID_TIER") && recs.size() <= mid_tier_max_records()) {
+    } else if (k == 15 && entries > 0 && recs.size() <= sw.mid_max_records) {
         // Middle tier (round 3): too many index k-mers for an LDS-resident filter of the whole codes.  Level 0 stays in LDS but
         // is keyed on the CANONICAL 12-mer (half the entries); what passes it is looked up in the exact bitmap of the canonical
         // index 12-mers (2 MB, in the L2: ~267 G four-byte probes per second chip-wide, measured -- tools/mb_l2probe.hip), and
@@ -408,21 +393,21 @@ void PrgIndex::save(const std::string& prg_file) const
     if (!out) throw Error(DRPRG_EIO, "short write to " + idx_path(prg_file, w, k));
 }
 
-void PrgIndex::build_and_save(const std::string& prg_file, int w, int k, int threads)
+void PrgIndex::build_and_save(const std::string& prg_file, int w, int k, int threads, const Switches& sw)
 {
     PrgIndex idx;
-    idx.build(prg_file, w, k, threads);
+    idx.build(prg_file, w, k, threads, sw);
     idx.save(prg_file);
 }
 
-void PrgIndex::load(const std::string& prg_file, int w_, int k_)
+void PrgIndex::load(const std::string& prg_file, int w_, int k_, const Switches& sw)
 {
     w = w_;
     k = k_;
     prgs = load_prg_file(prg_file);
     kgs.assign(prgs.size(), KmerGraph());
     for (size_t p = 0; p < prgs.size(); ++p) kgs[p].load_gfa(gfa_path(prg_file, prgs[p].name, w, k), prgs[p], w, k);
-    flatten();
+    flatten(sw);
     // the .idx file must agree with what the k-mer graphs imply
     std::ifstream in(idx_path(prg_file, w, k));
     if (!in) throw Error(DRPRG_ENOENT, "cannot open " + idx_path(prg_file, w, k));

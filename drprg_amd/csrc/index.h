@@ -6,6 +6,7 @@
 // `<prg>.k<K>.w<W>.idx` and `kmer_prgs/`).
 #pragma once
 #include "kmergraph.h"
+#include "switches.h"
 
 namespace drprg {
 
@@ -64,19 +65,19 @@ struct PrgIndex {
     void filter_selfcheck(uint64_t out[8]) const;
 
     // `pandora index`: sketch every PRG of prg_file, write <prg_file>.k<k>.w<w>.idx and
-    // <dir>/kmer_prgs/<name>.k<k>.w<w>.gfa
-    static void build_and_save(const std::string& prg_file, int w, int k, int threads);
+    // <dir>/kmer_prgs/<name>.k<k>.w<w>.gfa.  sw: the filter tier's switches (force_mid_tier, mid_max_records) for the flattened tables
+    static void build_and_save(const std::string& prg_file, int w, int k, int threads, const Switches& sw);
     // in-memory build (no files touched)
-    void build(const std::string& prg_file, int w, int k, int threads);
+    void build(const std::string& prg_file, int w, int k, int threads, const Switches& sw);
     // load what build_and_save wrote
-    void load(const std::string& prg_file, int w, int k);
+    void load(const std::string& prg_file, int w, int k, const Switches& sw);
     void save(const std::string& prg_file) const;
 
     static std::string idx_path(const std::string& prg_file, int w, int k);
     static std::string gfa_path(const std::string& prg_file, const std::string& name, int w, int k);
 
 private:
-    void flatten();
+    void flatten(const Switches& sw);
 };
 
 // slot index of `key` in a table of 2^bits slots (multiplicative hash; same function on the device).  narrow: the keys are

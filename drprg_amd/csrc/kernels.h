@@ -3,6 +3,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <hip/hip_runtime_api.h>
+#include "switches.h"
 
 #if defined(__HIPCC__)
 #define DRPRG_HD __host__ __device__
@@ -126,13 +127,13 @@ uint32_t wave_tile_eval();
 uint32_t wave_n_tiles(uint64_t n_bases);
 uint32_t wave_n_slices(uint64_t n_bases); // one slice of tile_cap records per workgroup of four tiles
 hipError_t launch_sketch_wave(const SketchArgs& a, hipStream_t stream, KernelTimer timer = {});
-// tiles of the candidate form of the direct sequence for these parameters (whichever kernel serves them)
-uint32_t direct_candidate_tiles(uint64_t n_bases, int halo, int k, int w, bool wide_hash); // = slices
-bool direct_uses_wave_form(int k, int w, bool wide_hash); // sketch_wave_kernel serves these parameters
-uint32_t direct_first_read_tiles(uint64_t n_bases, int halo, int k, int w, bool wide_hash); // entries of tile_first_read
+// tiles of the candidate form of the direct sequence for these parameters (whichever kernel serves them; force_lds: Switches::direct_lds)
+uint32_t direct_candidate_tiles(uint64_t n_bases, int halo, int k, int w, bool wide_hash, bool force_lds); // = slices
+bool direct_uses_wave_form(int k, int w, bool wide_hash, bool force_lds); // sketch_wave_kernel serves these parameters
+uint32_t direct_first_read_tiles(uint64_t n_bases, int halo, int k, int w, bool wide_hash, bool force_lds); // entries of tile_first_read
 // filtered form (k <= 15, w <= 16): bloom = 2^bloom_wbits words of index k-mer codes
 uint32_t filter_n_tiles(uint64_t n_bases, int positions_per_lane = 32);
-uint32_t filter_grid(bool level0, int n_cus, uint32_t n_tiles);
+uint32_t filter_grid(bool level0, int n_cus, uint32_t n_tiles, uint32_t cap); // cap: Switches::ft_grid (0: none)
 // device copies of FlatIndex::bloom / bloom0 (bloom0 == nullptr: no level 0)
 struct BloomTables {
     const uint32_t* bloom;
@@ -162,7 +163,6 @@ struct FilterBuffers {
     uint64_t raw_capacity;
     uint32_t* small;
     unsigned long long* max_len;
-    unsigned long long* stat = nullptr; // middle tier, DRPRG_FT_STATS=1: four device counters (FilterWork::stat)
     // sketch_filter_kernel's tile shares (FilterWork::wave_share) for this launch, or nullptr: its built-in ones; and five zeroed device words that
     // receive ~(earliest start) and the latest end of each of the four wave classes on the 100 MHz wall clock (reported by bench.py; with the
     // static schedule the host sets the next batch's shares by them: mapper.cpp tune_filter_shares)
@@ -188,8 +188,10 @@ struct FilterSched {
     uint32_t lds_word;   // the workgroup's ticket counter: this word of the kernel's dynamic LDS (set by the launcher; next ticket = 16 + its value)
 };
 // the schedule of one workgroup for the n_tiles wave tiles of a whole batch on n_wg workgroups;
-// DRPRG_FT_SCHED=static | f,d,m: share of round 0 in 1/256 of the tiles, divisor of the dynamic rounds (x 16), smallest chunk -- measurements
-FilterSched make_filter_sched(uint32_t n_tiles, uint32_t n_wg, const uint32_t share[4]);
+// (knobs: DRPRG_FT_SCHED, switches.h)
+FilterSched make_filter_sched(uint32_t n_tiles, uint32_t n_wg, const uint32_t share[4], const FilterSchedKnobs& knobs);
+// sketch_filter_kernel's built-in tile shares of the four wave classes in the level-0 forms (what Mapper::tune_filter_shares starts from)
+const uint32_t* filter_builtin_shares(bool mid, bool packed);
 // device view of the workspace of one filtered launch sequence (filled by launch_sketch_filter)
 struct FilterWork {
     const uint32_t* bloom;
@@ -199,7 +201,6 @@ struct FilterWork {
     const uint32_t* mid_bitmap; // middle tier: exact bitmap of the canonical index 12-mers (2^24 bits, global memory)
     const uint32_t* midc;       // middle tier: split-block Bloom filter of the index k-mer codes (2^midc_wbits blocks of 16 bytes, global memory)
     uint32_t midc_wbits;
-    unsigned long long* stat;   // DRPRG_FT_STATS=1 (middle tier): groups tested, past level 0, past the bitmap, candidate positions
     uint32_t read_begin, read_end; // the reads the launch sequence maps: the whole batch, [0, n_reads) (launch_sketch_filter).  The
                              // filter kernel streams the wave tiles (FT_WPOS positions each) that cover their bases, candidates
                              // outside [offsets[read_begin], offsets[read_end]) are dropped by verify_scan_kernel
@@ -232,9 +233,6 @@ struct FilterWork {
     unsigned long long* max_len; // longest read that holds a minimizer hit (this batch)
     unsigned long long* class_clock; // FilterBuffers::class_clock (may be null)
     uint32_t wave_share[4];  // sketch_filter_kernel: tiles of the waves 4c .. 4c + 3 of a workgroup, in 1/256 of an even share (sum 1024); see its launch
-    uint32_t debug;          // ablation switches for profiling (DRPRG_FT_DEBUG): 1 = skip the Bloom test, 8 = every read through the
-                             // generic pipeline, 16 / 32 = verify_scan_kernel without its window scan / table probe and
-                             // everything after it (wrong results: timing only, tools/dbg16.sh)
 };
 constexpr uint32_t READ_NONE = 0x7FFFFFFFu; // "read" of a candidate that lies past the last whole k-mer of the buffer
 
@@ -265,7 +263,6 @@ struct ReadClusterArgs {
     uint32_t n_wg;                 // 0: the totals are somebody else's business
     unsigned long long *tot_hits, *tot_minimizers, *tot_max_len;
     const uint32_t* overflow_word; // bit 2: a candidate slice overflowed (the host runs the batch again: minimizers must not count twice)
-    unsigned long long* phase_clock; // DRPRG_RC_DEBUG=1: 12 counters, clock cycles thread 0 of every workgroup spent per phase (else null)
     uint32_t minpath_in_lds;         // set by launch_read_cluster: the dynamic LDS holds [n_prgs] u16 shortest paths behind the histogram
 };
 // from[0 .. n) -> to[0 .. n) (the device address of pinned host memory), then from[0 .. n) = 0; n <= 64.  zero != nullptr: zero[0 .. n_zero)
@@ -278,9 +275,10 @@ size_t filter_small_words();
 void init_candidate_work(FilterWork& fw, const FilterBuffers& b, int n_cus);
 // filter -> candidates -> verify -> per-read clustering of the reads that fit read_cluster_kernel (coverage, PRG read
 // counts and the kept-cluster counters are updated); a.n_hits receives the number of hits of the whole batch,
-// rc.n_complex the number of reads left over.  fw is filled for the two follow-up calls.
+// rc.n_complex the number of reads left over.  fw is filled for the two follow-up calls.  sw: the grid cap, schedule, tile shares, second
+// stage and read_cluster_kernel switches
 hipError_t launch_sketch_filter(const SketchArgs& a, const BloomTables& bt, int n_cus, const FilterBuffers& b, const ReadClusterArgs& rc, FilterWork& fw,
-    hipStream_t stream, KernelTimer timer = {});
+    const Switches& sw, hipStream_t stream, KernelTimer timer = {});
 // leftover reads: a.n_hits receives the number of their hits, b.max_len their longest read ...
 hipError_t launch_filter_recount(const SketchArgs& a, const FilterWork& fw, hipStream_t stream);
 // ... and their hits are written to a.hit_key / a.hit_val ordered by (read, position)
@@ -289,7 +287,7 @@ hipError_t launch_filter_expand(const SketchArgs& a, const FilterWork& fw, hipSt
 // straight from the tile slices (*fw.cand_total: their total); it marks the candidates it handled with slices_mark (!= 0) in the dense
 // fw.cand_pos1.  tile_prefix: n_tiles + 1 words; temp: scan_temp_bytes(n_tiles + 1) bytes.  a.n_hits receives the hits of the batch;
 // overflow bit 2: a tile slice was too small, or the total exceeds dense_capacity (nothing was counted then).
-hipError_t launch_direct_candidates(const SketchArgs& a, bool wide_hash, uint32_t* tile_prefix, void* temp, size_t temp_bytes,
+hipError_t launch_direct_candidates(const SketchArgs& a, bool wide_hash, bool force_lds, uint32_t* tile_prefix, void* temp, size_t temp_bytes,
     uint64_t dense_capacity, const ReadClusterArgs& rc, int n_cus, FilterWork& fw, hipStream_t stream, KernelTimer timer, uint32_t slices_mark);
 // the gathered list after such a batch, for the reads that were left over (handled candidates get position 0)
 hipError_t launch_tile_gather_marked(const SketchArgs& a, const FilterWork& fw, const uint32_t* tile_prefix, uint32_t n_tiles, uint64_t dense_capacity,

@@ -138,8 +138,7 @@ Mapper::Mapper(const FlatIndex& idx, const MapParams& p, int device) : device_(d
         }
     }
     if (idx.midc_wbits) {
-        const size_t max_records = mid_tier_max_records(); // (common.h: where the direct sequence takes over)
-        if (idx.rec_prg.size() <= max_records) {
+        if (idx.rec_prg.size() <= sw_.mid_max_records) { // (switches.h: where the direct sequence takes over)
             midc_wbits_ = idx.midc_wbits;
             mid0_bits_ = idx.mid0_bits;
             dmalloc(d_mid0_, idx.mid0.size());
@@ -148,17 +147,13 @@ Mapper::Mapper(const FlatIndex& idx, const MapParams& p, int device) : device_(d
             HIPCHK(hipMemcpy(d_mid_bitmap_, idx.mid_bitmap.data(), idx.mid_bitmap.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
             dmalloc(d_midc_, idx.midc.size());
             HIPCHK(hipMemcpy(d_midc_, idx.midc.data(), idx.midc.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-            if (const char* e = std::getenv("DRPRG_FT_STATS"); e && std::atoi(e)) {
-                dmalloc(d_ft_stat_, (size_t)4);
-                zero_now(d_ft_stat_, 0, 4 * sizeof(unsigned long long));
-            }
         }
     }
     HIPCHK(hipDeviceGetAttribute(&n_cus_, hipDeviceAttributeMultiprocessorCount, device_));
     HIPCHK(hipStreamSynchronize(nullptr)); // every table is on the device before a kernel of a non-blocking stream can ask for it
     set_params(p); // again: the kernel choice depends on the filter being available
-    if (const char* e = std::getenv("DRPRG_HIP_MIN_CAPACITY")) // (tests: small batches at the production ratio, or below it to force regrows)
-        min_capacity_ = std::max<uint64_t>(MIN_CAPACITY_CLAMP, std::min<uint64_t>(std::strtoull(e, nullptr, 10), 1ull << 30));
+    if (sw_.min_capacity) // (tests: small batches at the production ratio, or below it to force regrows)
+        min_capacity_ = std::max<uint64_t>(MIN_CAPACITY_CLAMP, std::min<uint64_t>(*sw_.min_capacity, 1ull << 30));
     // ONE allocation [coverage | reads per PRG]: the sample's whole additive state is one contiguous u32 vector, so the
     // collective of the path is a single ncclAllReduce / ncclReduce over it (capi.cpp)
     dmalloc(d_covg_, 2 * (size_t)n_knodes_ + (size_t)n_prgs_);
@@ -190,7 +185,7 @@ Mapper::~Mapper()
     dfree(d_head_); dfree(d_scan_); dfree(d_cstart_); dfree(d_order_); dfree(d_clusters_);
     if (d_temp_) (void)hipFree(d_temp_);
     for (TileSet& t : tsets_) free_tile_set(t);
-    dfree(d_bases_); dfree(d_offsets_); dfree(d_bloom_); dfree(d_bloom0_); dfree(d_bloom0f_); dfree(d_bloomr_); dfree(d_pbloom_); dfree(d_mid0_); dfree(d_mid_bitmap_); dfree(d_midc_); dfree(d_blkc_); dfree(d_ft_stat_);
+    dfree(d_bases_); dfree(d_offsets_); dfree(d_bloom_); dfree(d_bloom0_); dfree(d_bloom0f_); dfree(d_bloomr_); dfree(d_pbloom_); dfree(d_mid0_); dfree(d_mid_bitmap_); dfree(d_midc_); dfree(d_blkc_);
     for (Stage& st : stage_) {
         dfree(st.d_bases); dfree(st.d_offsets); dfree(st.d_npos);
         if (st.copied) (void)hipEventDestroy(st.copied);
@@ -307,6 +302,7 @@ void Mapper::reset_coverage(bool new_sample)
     tot_reads_ = tot_bases_ = tot_hits_ = tot_leftover_ = tot_minimizers_ = 0;
     for (auto& sh : ft_share_) // (a reset context starts from the launcher's built-in tile shares again: ADVICE r05)
         for (uint32_t& v : sh) v = 0;
+    sw_ = read_switches(); // (those that only shape construction keep their effect from the open)
     if (new_sample) drop_kept();
 }
 
@@ -409,16 +405,8 @@ void Mapper::filter_launch(const Batch& b)
     a.n_minimizers = &lane.d_scratch[L_MINIMIZERS];
     a.overflow = reinterpret_cast<uint32_t*>(&lane.d_scratch[L_OVERFLOW]);
     dev::FilterBuffers fb { lane.raw_pos, lane.cand_info, lane.cand_pos1, lane.cand_rec, lane.raw_capacity, lane.small, &lane.d_scratch[L_MAXLEN] };
-    fb.stat = d_ft_stat_;
-    {
-        static const bool adapt = [] { const char* e = std::getenv("DRPRG_FT_ADAPT"); return !e || std::atoi(e) != 0; }();
-        ft_adapt_ = adapt;
-        const int pi = b.packed ? 1 : 0;
-        if (adapt) {
-            fb.class_clock = &lane.d_scratch[L_FT_CLOCK];
-            if (ft_share_[pi][0]) fb.wave_share = ft_share_[pi];
-        }
-    }
+    fb.class_clock = &lane.d_scratch[L_FT_CLOCK]; // (unused when DRPRG_FT_SHARE pins the shares: then nothing adapts them)
+    if (ft_share_[b.packed ? 1 : 0][0]) fb.wave_share = ft_share_[b.packed ? 1 : 0];
     dev::BloomTables bt { d_bloom_, bloom_wbits_, d_bloom0_, bloom0_wbits_, d_bloomr_, d_bloom0f_ };
     bt.blkc = d_blkc_;
     bt.blkc_wbits = blkc_wbits_;
@@ -446,7 +434,7 @@ void Mapper::filter_launch(const Batch& b)
         timer.begin = lane.t0;
         timer.end = lane.t1;
     }
-    HIPCHK(dev::launch_sketch_filter(a, bt, n_cus_, fb, rc, lane.fw, b.stream, timer));
+    HIPCHK(dev::launch_sketch_filter(a, bt, n_cus_, fb, rc, lane.fw, sw_, b.stream, timer));
     // the counters to the pinned mirror and zero again behind it: one small kernel (rounds 1-4: a copy and two memsets)
     HIPCHK(dev::launch_counters_home(lane.d_scratch, lane.h_scratch_dev, L_N, b.stream, dev::filter_super_counts(lane.small), dev::filter_super_words()));
     lane.scratch_zero = true;
@@ -455,14 +443,10 @@ void Mapper::filter_launch(const Batch& b)
 // Waits for `event` (recorded on `stream`), or -- event null -- for everything queued on `stream`.  The wait polls for a short while first:
 // an interrupt-driven synchronise wakes up tens of microseconds late, which is visible at 0.7 ms per batch.  Only for a short while (~2 ms
 // of polls): a longer batch does not notice the late wake-up, and a host core that spins for it is a core the FASTQ parser threads (or the
-// other ranks of a node) do not have.  DRPRG_HIP_SPIN=0: never poll.
+// other ranks of a node) do not have.
 static void wait_stream(hipStream_t stream, hipEvent_t event = nullptr)
 {
-    static const bool spin = [] {
-        const char* e = std::getenv("DRPRG_HIP_SPIN");
-        return !(e && std::atoi(e) == 0);
-    }();
-    for (int spins = 0; spin && spins < 2048; ++spins) {
+    for (int spins = 0; spins < 2048; ++spins) {
         const hipError_t e = event ? hipEventQuery(event) : hipStreamQuery(stream);
         if (e == hipSuccess) return;
         if (e != hipErrorNotReady) HIPCHK(e);
@@ -631,8 +615,8 @@ void Mapper::direct_launch(const Batch& b)
     const PackedInfo* const pk = b.pkp();
     TileSet& t = tsets_[set];
     ts_ = &t;
-    const uint32_t n_tiles = dev::direct_candidate_tiles(n_bases, halo_, params_.k, params_.w, wide_hash_); // = slices
-    const uint32_t n_first = dev::direct_first_read_tiles(n_bases, halo_, params_.k, params_.w, wide_hash_);
+    const uint32_t n_tiles = dev::direct_candidate_tiles(n_bases, halo_, params_.k, params_.w, wide_hash_, sw_.direct_lds); // = slices
+    const uint32_t n_first = dev::direct_first_read_tiles(n_bases, halo_, params_.k, params_.w, wide_hash_, sw_.direct_lds);
     if (n_first > t.first_cap) { // first read of every tile
         dfree(t.d_tile_first);
         t.first_cap = n_first + n_first / 4 + 16;
@@ -658,7 +642,7 @@ void Mapper::direct_launch(const Batch& b)
     HIPCHK(hipMemsetAsync(t.d_tile_count + n_tiles, 0, sizeof(uint32_t), stream)); // the scan's closing zero
     // a packed batch: sketch_wave_kernel reads the words themselves (round 4; the positions of its npos as one bit per base, set here);
     // the general direct kernel reads an ASCII expansion made on the same stream (packed.hip)
-    const bool native_packed = pk != nullptr && dev::direct_uses_wave_form(params_.k, params_.w, wide_hash_);
+    const bool native_packed = pk != nullptr && dev::direct_uses_wave_form(params_.k, params_.w, wide_hash_, sw_.direct_lds);
     dev::SketchArgs a = sketch_args(native_packed ? d_bases : ascii_view(set, d_bases, n_bases, stream, pk), b.d_offsets, b.n_reads, n_bases, native_packed ? pk : nullptr);
     if (native_packed && a.n_npos) {
         const uint64_t words16 = ((n_bases + 15) / 16 + 1) & ~1ull; // (an even number of u16 words: the marks are 32-bit atomics)
@@ -710,7 +694,7 @@ void Mapper::direct_launch(const Batch& b)
         timer.begin = lane.t0;
         timer.end = lane.t1;
     }
-    HIPCHK(dev::launch_direct_candidates(a, wide_hash_, t.d_tile_prefix, t.d_tile_temp, t.tile_temp_bytes, lane.raw_capacity, rc, n_cus_, lane.fw,
+    HIPCHK(dev::launch_direct_candidates(a, wide_hash_, sw_.direct_lds, t.d_tile_prefix, t.d_tile_temp, t.tile_temp_bytes, lane.raw_capacity, rc, n_cus_, lane.fw,
         stream, timer, mark));
     t.a_done = a;
     t.mark = mark;
@@ -810,13 +794,8 @@ void Mapper::tune_filter_shares(const Lane& lane, bool packed, uint64_t n_bases)
         ft_last_[11] = sc.per_wg;
         for (int r = 0; r < dev::FT_MAX_ROUNDS; ++r) ft_last_[12 + r] = r && r < (int)sc.n_rounds ? sc.size[r] : 0;
     }
-    if (lane.fw.cand_total && std::getenv("DRPRG_FT_STATS")) { // what the filter left for verify_scan_kernel (measurements; the batch is complete)
-        uint32_t total = 0;
-        if (hipMemcpy(&total, lane.fw.cand_total, sizeof(total), hipMemcpyDeviceToHost) == hipSuccess)
-            std::fprintf(stderr, "[sketch_filter] candidate positions of the batch: %u\n", total);
-    }
     if (lane.fw.sched.n_rounds > 1) return; // a dynamic schedule balances itself: the shares of round 0 stay what they are
-    if (!ft_adapt_ || n_bases < (64ull << 20)) return;
+    if (n_bases < (64ull << 20)) return;
     const unsigned long long* ck = &lane.h_scratch[L_FT_CLOCK];
     if (!ck[0] || !ck[1] || !ck[2] || !ck[3] || !ck[4]) return; // (a launch without the level-0 form, or with DRPRG_FT_SHARE)
     const unsigned long long t0 = ~ck[0];
@@ -827,9 +806,8 @@ void Mapper::tune_filter_shares(const Lane& lane, bool packed, uint64_t n_bases)
         mean += end[c] / 4;
     }
     uint32_t* s = ft_share_[packed ? 1 : 0];
-    if (!s[0]) { // the launcher's built-in shares were in use: the same numbers (sketch_filter.hip)
-        static const uint32_t ascii_l0[4] = { 397, 294, 200, 133 }, packed_l0[4] = { 422, 292, 184, 126 }, mid_l0[4] = { 356, 292, 220, 156 };
-        const uint32_t* from = use_mid_ ? mid_l0 : packed ? packed_l0 : ascii_l0;
+    if (!s[0]) { // the launcher's built-in shares were in use
+        const uint32_t* from = dev::filter_builtin_shares(use_mid_, packed);
         for (int c = 0; c < 4; ++c) s[c] = from[c];
     }
     double v[4], sum = 0;
@@ -841,8 +819,6 @@ void Mapper::tune_filter_shares(const Lane& lane, bool packed, uint64_t n_bases)
     uint32_t acc = 0;
     for (int c = 0; c < 3; ++c) acc += s[c] = (uint32_t)(1024.0 * v[c] / sum + 0.5);
     s[3] = 1024u - acc;
-    static const bool verbose = [] { const char* e = std::getenv("DRPRG_FT_ADAPT"); return e && std::atoi(e) == 2; }();
-    if (verbose) std::fprintf(stderr, "[ft shares] classes ended at %.0f %.0f %.0f %.0f (10 ns) -> %u %u %u %u\n", end[0], end[1], end[2], end[3], s[0], s[1], s[2], s[3]);
 }
 
 void Mapper::map_device_async(const uint8_t* d_bases, const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases, uint32_t* covg,
@@ -1414,12 +1390,6 @@ MapCounters Mapper::counters()
     HIPCHK(hipStreamSynchronize(stream_));
     unsigned long long c[C_N];
     HIPCHK(hipMemcpy(c, d_counters_, sizeof(c), hipMemcpyDeviceToHost));
-    if (d_ft_stat_) {
-        unsigned long long st[4];
-        HIPCHK(hipMemcpy(st, d_ft_stat_, sizeof(st), hipMemcpyDeviceToHost));
-        std::fprintf(stderr, "[sketch_filter middle tier] groups %llu, past level 0 %llu (%.2f %%), past the bitmap %llu (%.2f %%), candidate positions %llu\n", st[0],
-            st[1], st[0] ? 100.0 * (double)st[1] / (double)st[0] : 0.0, st[2], st[0] ? 100.0 * (double)st[2] / (double)st[0] : 0.0, st[3]);
-    }
     MapCounters m;
     m.reads = tot_reads_;
     m.bases = tot_bases_;

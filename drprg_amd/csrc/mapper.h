@@ -109,7 +109,9 @@ public:
     static void pinned_free(void* p);
     static void warm_device(int device);
 
-    void reset_coverage(bool new_sample = true); // new_sample: the reads kept in HBM (keep_reads) go as well
+    // new_sample: the reads kept in HBM (keep_reads) go as well.  The switches are read again: a context maps with those it was opened or last
+    // reset with (DRPRG_HIP_MIN_CAPACITY, DRPRG_FORCE_MID_TIER and DRPRG_MID_MAX_RECORDS shape construction: they take effect at open only)
+    void reset_coverage(bool new_sample = true);
     // own accumulators
     uint32_t* d_covg() const { return d_covg_; }
     uint32_t* d_prg_reads() const { return d_prg_reads_; }
@@ -217,6 +219,7 @@ private:
     int pipe_next_ = 0;
 
     int device_ = 0;
+    Switches sw_ = read_switches(); // the hot path's switches (switches.h): read at construction and again by reset_coverage
     MapParams params_;
     bool wide_hash_ = false;
     int halo_ = 16;
@@ -245,7 +248,6 @@ private:
     uint32_t* d_blkc_ = nullptr; // small tier: the second stage as a split-block filter in global memory (FlatIndex::blkc)
     uint32_t blkc_wbits_ = 0;
     bool use_mid_ = false;                   // the filtered sequence runs in its middle-tier form
-    unsigned long long* d_ft_stat_ = nullptr; // DRPRG_FT_STATS=1: groups tested / past level 0 / past the bitmap, candidate positions
     int n_cus_ = 256;
     bool use_filter_ = false;
     bool use_direct_cands_ = false; // direct sketch kernel in its candidate form (read_cluster_kernel instead of sort + cluster kernels)
@@ -264,7 +266,7 @@ private:
     uint32_t *d_head_ = nullptr, *d_scan_ = nullptr, *d_cstart_ = nullptr, *d_order_ = nullptr;
     dev::ClusterRec* d_clusters_ = nullptr;
     Lane lanes_[2];
-    // smallest capacity of the candidate / hit buffers, in entries (DRPRG_HIP_MIN_CAPACITY, read here at construction; tests lower it so that
+    // smallest capacity of the candidate / hit buffers, in entries (DRPRG_HIP_MIN_CAPACITY, taken at construction; tests lower it so that
     // small batches run at the production ratio -- n_bases / 48 for the filtered sequence --, or below it to make the buffers regrow)
     static constexpr uint64_t MIN_CAPACITY_CLAMP = 4096;
     uint64_t min_capacity_ = 1u << 20;
@@ -314,7 +316,6 @@ private:
     hipStream_t copy_stream_ = nullptr;
     // sketch_filter_kernel's tile shares, followed from batch to batch ([0] ASCII, [1] packed input; {0}: the launcher's built-in ones so far)
     uint32_t ft_share_[2][4] = { { 0, 0, 0, 0 }, { 0, 0, 0, 0 } };
-    bool ft_adapt_ = true;
     uint64_t ft_last_[20] = {};
     void tune_filter_shares(const Lane& lane, bool packed, uint64_t n_bases);
     // keep_reads: device memory in large pieces, handed out front to back

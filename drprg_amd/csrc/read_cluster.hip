@@ -3,9 +3,6 @@
 #include "filter_common.h"
 #include <algorithm>
 #include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <string>
 
 namespace drprg {
 namespace dev {
@@ -33,19 +30,15 @@ namespace dev {
 // nothing else.)  Chunks are handed out through a global counter.
 constexpr int RC_THREADS = 1024;
 constexpr int RC_WAVES = RC_THREADS / 64;
-#ifndef DRPRG_RC_PER // (build-time knobs of tools/rc_variants.sh: slots per thread, staged hits, workgroups per CU)
-#define DRPRG_RC_PER 2
-#define DRPRG_RC_HCAP 3072
-#define DRPRG_RC_WG_PER_CU 2
-#endif
-constexpr int RC_PER = DRPRG_RC_PER;
+constexpr int RC_PER = 2;        // staged candidates per thread
+constexpr int RC_WG_PER_CU = 2;  // workgroups per CU
 constexpr int RC_SLOTS = RC_THREADS * RC_PER; // staged candidates
 // Look-ahead (template parameter AHEAD; RC_AHEAD / RC_OWN are defined at the top of the kernel): a read belongs to the chunk that owns its
 // first candidate, so the last AHEAD of the staged slots are there for reads that begin in the owned range and run on.  512 slots serve
 // a 4 kb Nanopore read (~250 candidates); a 150-base read has a few dozen at most, and every slot not spent on look-ahead is owned:
 // 128 slots of look-ahead mean 1920 owned candidates per chunk instead of 1536, a fifth fewer chunks -- and a chunk costs ~21 us whatever
 // is in it (round 4).  A read that does not fit its chunk's look-ahead goes through the generic pipeline as before.
-constexpr int RC_HCAP = DRPRG_RC_HCAP;         // staged hits
+constexpr int RC_HCAP = 3072;                 // staged hits
 constexpr int RC_POOL = 512;                  // reads per chunk that may take the wave path
 constexpr uint32_t RC_IRREGULAR = 2u, RC_COMPLEX = 1u;
 
@@ -66,7 +59,7 @@ __device__ __forceinline__ void lds_barrier(int& t) { asm volatile("s_waitcnt lg
 
 // SLICES: the candidates are read from the tile slices of the direct sketch kernel (rc.slice_prefix), not from a gathered list
 template <bool SLICES, int AHEAD>
-__global__ __launch_bounds__(RC_THREADS, 4 * DRPRG_RC_WG_PER_CU) void read_cluster_kernel(SketchArgs a, FilterWork fw, ReadClusterArgs rc)
+__global__ __launch_bounds__(RC_THREADS, 4 * RC_WG_PER_CU) void read_cluster_kernel(SketchArgs a, FilterWork fw, ReadClusterArgs rc)
 {
     constexpr int RC_AHEAD = AHEAD, RC_OWN = RC_SLOTS - AHEAD;
     static_assert(RC_OWN % 64 == 0, "the slices form locates 64 entries from a multiple of 64 per wave");
@@ -92,16 +85,6 @@ __global__ __launch_bounds__(RC_THREADS, 4 * DRPRG_RC_WG_PER_CU) void read_clust
     int tid = threadIdx.x;
 #define lane (tid & 63)
 #define wave (tid >> 6)
-    // (DRPRG_RC_DEBUG=1: thread 0 of every workgroup adds the clock cycles between two marks to counter `ph`)
-    unsigned long long pc_last = rc.phase_clock ? clock64() : 0;
-#define RC_MARK(ph)                                                  \
-    do {                                                             \
-        if (rc.phase_clock && tid == 0) {                            \
-            const unsigned long long pc_now = clock64();             \
-            atomicAdd(&rc.phase_clock[ph], pc_now - pc_last);        \
-            pc_last = pc_now;                                        \
-        }                                                            \
-    } while (0)
     if (rc.n_wg && blockIdx.x == 0) { // the candidate stage's totals (kernels.h): before any of the early returns below
         uint32_t h = 0, nm = 0, ml = 0;
         for (uint32_t g = (uint32_t)tid; g < rc.n_wg; g += RC_THREADS) {
@@ -265,15 +248,12 @@ __global__ __launch_bounds__(RC_THREADS, 4 * DRPRG_RC_WG_PER_CU) void read_clust
     uint32_t cur = blockIdx.x;
     Staged nx = request(cur);
     for (;;) {
-        RC_MARK(9); // (what ran since mark 8: the wave path of thread 0's wave)
         lds_barrier(tid); // LDS of the previous chunk is free, everybody holds the chunk number in a register
-        RC_MARK(0);
         const uint64_t base64 = (uint64_t)cur * RC_OWN;
         if (base64 >= total) break;
         const uint32_t base = (uint32_t)base64;
         const uint32_t n_loaded = total - base < (uint32_t)RC_SLOTS ? total - base : (uint32_t)RC_SLOTS;
         const uint32_t n_own = total - base < (uint32_t)RC_OWN ? total - base : (uint32_t)RC_OWN;
-        RC_MARK(1);
         // (the ticket of the next chunk: a device-wide atomic that returns a value takes microseconds; it is asked for here and put
         // into LDS two phases later, so that nobody waits for it at the barrier that closes stage A)
         uint32_t ticket = 0;
@@ -316,7 +296,6 @@ __global__ __launch_bounds__(RC_THREADS, 4 * DRPRG_RC_WG_PER_CU) void read_clust
             s_n_irr = 0;
         }
         lds_barrier(tid);
-        RC_MARK(2);
         // ---- B: exclusive sum scan of the hit counts and ONE inclusive max scan of (read start << 16 | segment start), in slot
         // order: both starts only grow along the slots and a read start is a segment start, so the packed maximum is the pair ----
         {
@@ -356,7 +335,6 @@ __global__ __launch_bounds__(RC_THREADS, 4 * DRPRG_RC_WG_PER_CU) void read_clust
             }
             const uint32_t excl_mx_in_wave = __shfl_up(imx, 1);
             lds_barrier(tid);
-            RC_MARK(3);
             uint32_t before = incl - run, mx_before = lane ? excl_mx_in_wave : 0u, sum = 0;
 #pragma unroll
             for (int i = 0; i < RC_WAVES; ++i) {
@@ -379,7 +357,6 @@ __global__ __launch_bounds__(RC_THREADS, 4 * DRPRG_RC_WG_PER_CU) void read_clust
         }
         if (tid == 0) s_chunk = ticket;
         lds_barrier(tid);
-        RC_MARK(4);
         // ---- C: the hits (one per index record of every minimizer); every segment start closes the segment before it; a
         // minimizer whose group differs from the previous one of its read makes the read irregular; the first minimizer of a
         // segment names the segment's group and threshold ----
@@ -405,13 +382,7 @@ __global__ __launch_bounds__(RC_THREADS, 4 * DRPRG_RC_WG_PER_CU) void read_clust
             // a k-mer that several k-mer nodes share (a quarter of the minimizers of a PRG index): its further records, four at a
             // time with their eight loads requested together (one after the other they were up to three round trips that the
             // whole workgroup waited for at the barrier)
-            if (fw.debug & 4096u) // (DRPRG_FT_DEBUG=4096: timing only, wrong results -- what fetching the further records costs: they repeat the first)
-                for (uint32_t r = 1; r < cnt; ++r) {
-                    s_grp[h0 + r] = (uint16_t)g;
-                    s_hpos[h0 + r] = (uint16_t)pos;
-                    s_cov[h0 + r] = crec[q].w;
-                }
-            for (uint32_t r0 = 1; r0 < cnt && !(fw.debug & 4096u); r0 += 4) {
+            for (uint32_t r0 = 1; r0 < cnt; r0 += 4) {
                 uint32_t kn4[4], prg4[4];
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
@@ -443,7 +414,6 @@ __global__ __launch_bounds__(RC_THREADS, 4 * DRPRG_RC_WG_PER_CU) void read_clust
             if (lead && lead <= n_own) s_cplx[lead - 1] = 1;
         }
         lds_barrier(tid);
-        RC_MARK(5);
         // ---- E: the first slot of every segment decides for the segment; reads with several groups queue for the wave path ----
 #pragma unroll
         for (int q = 0; q < RC_PER; ++q) {
@@ -483,7 +453,6 @@ __global__ __launch_bounds__(RC_THREADS, 4 * DRPRG_RC_WG_PER_CU) void read_clust
             s_dec[i] = (uint8_t)dec;
         }
         lds_barrier(tid);
-        RC_MARK(6);
         // ---- F: the minimizers of the kept segments ----
         {
 #pragma unroll
@@ -501,17 +470,11 @@ __global__ __launch_bounds__(RC_THREADS, 4 * DRPRG_RC_WG_PER_CU) void read_clust
                 }
             }
         }
-        RC_MARK(8);
         cur = s_chunk; // (written by thread 0 before the barrier that closed phase B)
         nx = request(cur);
-        RC_MARK(12); // (asking for the next chunk's candidates; what follows until mark 9 is the wave path of thread 0's wave)
         // ---- G: reads with hits in several groups, one wave per read: lane j holds cluster j, the hits are broadcast one by one
         // (clusters per group split at gaps, size threshold, the overlap sweep of cluster_filter_kernel) ----
         const uint32_t n_irr = s_n_irr < (uint32_t)RC_POOL ? s_n_irr : (uint32_t)RC_POOL;
-        if (rc.phase_clock && tid == 0) { // (counters 10, 11 of the debug block: reads that took the wave path, chunks)
-            atomicAdd(&rc.phase_clock[10], (unsigned long long)n_irr);
-            atomicAdd(&rc.phase_clock[11], 1ull);
-        }
         for (uint32_t r = wave; r < n_irr; r += RC_WAVES) {
             const uint32_t i = s_irr[r] & 0xFFFFu, e = s_irr[r] >> 16;
             const uint32_t read = s_read[i], hb = s_hstart[i], he = s_hstart[e];
@@ -648,7 +611,6 @@ __global__ __launch_bounds__(RC_THREADS, 4 * DRPRG_RC_WG_PER_CU) void read_clust
                 if (s_pos1[c]) fw.cand_pos1[base + c] = handled_mark; // handled
         }
     }
-    RC_MARK(7);
     // ---- workgroup totals ----
     if (my_kept) atomicAdd(&s_tot[0], (unsigned long long)my_kept);
     if (my_kept_hits) atomicAdd(&s_tot[1], my_kept_hits);
@@ -664,7 +626,6 @@ __global__ __launch_bounds__(RC_THREADS, 4 * DRPRG_RC_WG_PER_CU) void read_clust
 }
 #undef lane
 #undef wave
-#undef RC_MARK
 
 // The counters of a launch sequence to their pinned mirror on the host, and zero again on the device for the next batch: one small launch
 // where a copy and a memset were two (mapper.cpp launch_lane; to: the device address of the mirror).  Round 6: the superblock counts of the
@@ -700,13 +661,6 @@ hipError_t launch_read_cluster(const SketchArgs& a, const FilterWork& fw, const 
     }
     ReadClusterArgs rcd = rc;
     // (a wave form without workgroup barriers lost to this kernel: 61 + 37 + 8 us against 68 us on configs[1]; profiles/r04/rc_forms.txt)
-    static unsigned long long* d_phase = nullptr;
-    const bool debug = std::getenv("DRPRG_RC_DEBUG") != nullptr;
-    if (debug) {
-        if (!d_phase) HIP_TRY(hipMalloc(&d_phase, 14 * sizeof(unsigned long long)));
-        HIP_TRY(hipMemsetAsync(d_phase, 0, 14 * sizeof(unsigned long long), stream));
-        rcd.phase_clock = d_phase;
-    }
     size_t dyn = (size_t)rc.n_prgs * sizeof(uint32_t); // the per-PRG histogram, behind ~77 KB of static LDS
     {   // + the shortest paths, 16 bits each, if the same number of workgroups per CU still fits (configs[4]: 500 PRGs, 88 bytes to spare)
         static size_t static_lds = 0;
@@ -722,21 +676,17 @@ hipError_t launch_read_cluster(const SketchArgs& a, const FilterWork& fw, const 
             static_lds = most;
         }
         const size_t lds_cu = 160 * 1024, with = dyn + (size_t)rc.n_prgs * sizeof(uint16_t);
-        const size_t fit_without = std::min<size_t>(lds_cu / (static_lds + dyn), DRPRG_RC_WG_PER_CU), fit_with = std::min<size_t>(lds_cu / (static_lds + with), DRPRG_RC_WG_PER_CU);
+        const size_t fit_without = std::min<size_t>(lds_cu / (static_lds + dyn), RC_WG_PER_CU), fit_with = std::min<size_t>(lds_cu / (static_lds + with), RC_WG_PER_CU);
         rcd.minpath_in_lds = fit_with == fit_without ? 1u : 0u;
         if (rcd.minpath_in_lds) dyn = with;
     }
-    // look-ahead by the batch's mean read length (DRPRG_RC_AHEAD=128 / 256 / 512 forces one)
+    // look-ahead by the batch's mean read length
     const uint64_t mean_len = a.n_bases / (a.n_reads ? a.n_reads : 1u);
-    int ahead = mean_len <= 300 ? 128 : mean_len <= 600 ? 256 : 512;
-    if (const char* e = std::getenv("DRPRG_RC_AHEAD")) {
-        const int v = std::atoi(e);
-        if (v == 128 || v == 256 || v == 512) ahead = v;
-    }
+    const int ahead = mean_len <= 300 ? 128 : mean_len <= 600 ? 256 : 512;
     static size_t configured[6][MAX_HIP_DEVICES] = {};
     auto launch = [&](auto kernel, size_t (&conf)[MAX_HIP_DEVICES]) -> hipError_t {
         HIP_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), dyn, conf));
-        hipLaunchKernelGGL(kernel, dim3((uint32_t)n_cus * DRPRG_RC_WG_PER_CU), dim3(RC_THREADS), dyn, stream, a, fw, rcd);
+        hipLaunchKernelGGL(kernel, dim3((uint32_t)n_cus * RC_WG_PER_CU), dim3(RC_THREADS), dyn, stream, a, fw, rcd);
         return hipGetLastError();
     };
     if (rcd.slice_prefix) {
@@ -747,18 +697,6 @@ hipError_t launch_read_cluster(const SketchArgs& a, const FilterWork& fw, const 
         if (ahead == 128) HIP_TRY(launch(&read_cluster_kernel<false, 128>, configured[3]));
         else if (ahead == 256) HIP_TRY(launch(&read_cluster_kernel<false, 256>, configured[4]));
         else HIP_TRY(launch(&read_cluster_kernel<false, 512>, configured[5]));
-    }
-    if (debug) { // cycles of thread 0, summed over the workgroups, per phase (the marks follow the barriers of the chunk loop)
-        unsigned long long h[14];
-        HIP_TRY(hipStreamSynchronize(stream));
-        HIP_TRY(hipMemcpy(h, d_phase, sizeof h, hipMemcpyDeviceToHost));
-        unsigned long long sum = 0;
-        for (int i = 0; i < 10; ++i) sum += h[i];
-        sum += h[12];
-        std::fprintf(stderr, "[read_cluster phases, %% of %llu Mcycles]", sum / 1000000);
-        for (int i = 0; i < 10; ++i) std::fprintf(stderr, " %d:%.1f", i, sum ? 100.0 * (double)h[i] / (double)sum : 0.0);
-        std::fprintf(stderr, " request:%.1f", sum ? 100.0 * (double)h[12] / (double)sum : 0.0);
-        std::fprintf(stderr, " | %llu reads on the wave path in %llu chunks\n", h[10], h[11]);
     }
     return hipGetLastError();
 }

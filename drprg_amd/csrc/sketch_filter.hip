@@ -36,11 +36,7 @@
 // whose filter fits the LDS of a CU; everything else takes the direct kernel.
 #include "filter_common.h"
 #include <algorithm>
-#include <array>
 #include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <string>
 #include <type_traits>
 
 namespace drprg {
@@ -157,8 +153,6 @@ __global__ __launch_bounds__(FT_THREADS) void sketch_filter_kernel(SketchArgs a,
     const int sh_w = 32 - (int)fw.bloom_wbits;
     const uint32_t sh_c = 32u - fw.midc_wbits; // (middle tier)
     (void)sh_c;
-    uint32_t st_a = 0, st_b = 0, st_c = 0; // DRPRG_FT_STATS (middle tier): groups past level 0 / past the bitmap, candidate positions, per lane
-    (void)st_a; (void)st_b; (void)st_c;
 
     // The filter arrays into LDS, 16 bytes per load and store (all of them powers of two >= 256 words, 16-byte aligned on both sides): 8 rounds
     // for the 128 KB of level 0 where word by word it was 32 -- and 8 us of every launch (round 5: step 0.511 -> 0.503 ms, packed 0.444 -> 0.437)
@@ -252,8 +246,6 @@ __global__ __launch_bounds__(FT_THREADS) void sketch_filter_kernel(SketchArgs a,
     base_cur = (uint32_t)__builtin_amdgcn_readfirstlane((int)base_cur);
     cap_cur = (uint32_t)__builtin_amdgcn_readfirstlane((int)cap_cur);
     if (tid == 0) s_dyn[fw.sched.lds_word] = 0; // (before the one barrier below; a word no filter array and no wave's stage uses)
-    uint32_t tiles_done = 0;
-    (void)tiles_done;
 
     auto load16 = [&](int64_t g) -> uint4 { // 16 bases at global position g (a multiple of 16)
         if (g + 16 <= n_bases) return *reinterpret_cast<const uint4*>(a.bases + g);
@@ -294,7 +286,7 @@ __global__ __launch_bounds__(FT_THREADS) void sketch_filter_kernel(SketchArgs a,
         }
     };
     uint64_t* out = fw.raw_pos + base_cur;
-    uint32_t lane_keep = (lane == 63 || (fw.debug & 1u)) ? 0u : 0xFFFFFFFFu;
+    uint32_t lane_keep = lane == 63 ? 0u : 0xFFFFFFFFu;
     asm volatile("" : "+v"(lane_keep)); // (a value the compiler knows nothing about: it turns a known per-lane condition back into a branch)
     uint32_t wcur = 0; // candidates in the current slice so far (wave-uniform)
     // FUSED: the groups that passed level 0 wait in the wave's 2 KB of LDS; when the next tile might not fit, they go through the
@@ -312,7 +304,6 @@ __global__ __launch_bounds__(FT_THREADS) void sketch_filter_kernel(SketchArgs a,
         uint32_t cand2 = (cand2_in);                                                                                                  \
         /* ordered append: exclusive prefix of the per-lane counts (0..4) from three ballots */                                       \
         const uint32_t c2 = (uint32_t)__popc(cand2);                                                                                  \
-        if constexpr (MID != 0) st_c += c2;                                                                                           \
         const uint64_t e0 = __ballot(c2 & 1u), e1 = __ballot(c2 & 2u), e2 = __ballot(c2 & 4u);                                        \
         if (e0 | e1 | e2) {                                                                                                           \
             uint32_t at2 = wcur + mb_below(e0) + 2u * mb_below(e1) + 4u * mb_below(e2);                                               \
@@ -439,7 +430,6 @@ __global__ __launch_bounds__(FT_THREADS) void sketch_filter_kernel(SketchArgs a,
                 // ---- the exact bitmap of the canonical index 12-mers, only for the groups that passed level 0: one exec-masked load
                 // each, all in flight before the first test (the L2 serves ~267 G such probes per second chip-wide whatever their
                 // width, so every group level 0 rejects is 3.7 ps saved) ----
-                st_a += (uint32_t)__popc(grp);
                 uint32_t bw[NG];
 #pragma unroll
                 for (int g = 0; g < NG; ++g) {
@@ -450,7 +440,6 @@ __global__ __launch_bounds__(FT_THREADS) void sketch_filter_kernel(SketchArgs a,
 #pragma unroll
                 for (int g = 0; g < NG; ++g) keep |= ((bw[g] >> (xs[g] & 31)) & 1u) << g;
                 grp &= keep;
-                st_b += (uint32_t)__popc(grp);
             }
             // ---- append in (lane, group) = position order: exclusive prefix of the per-lane counts (0..NG) from four or five ballots ----
             const uint32_t cnt = (uint32_t)__popc(grp);
@@ -505,30 +494,28 @@ __global__ __launch_bounds__(FT_THREADS) void sketch_filter_kernel(SketchArgs a,
             return;
         }
         uint32_t cand = 0;
-        if (!(fw.debug & 1u)) {
-            uint32_t c1 = 0; // level-1 survivors, position j in bit j
-            {
-                // ---- level 1 over my 32 positions ----
+        uint32_t c1 = 0; // level-1 survivors, position j in bit j
+        {
+            // ---- level 1 over my 32 positions ----
 #pragma unroll
-                for (int j = FT_G - 1; j >= 0; --j) {
-                    const uint32_t lo = j < 16 ? wa : wb, hi = j < 16 ? wb : wc;
-                    uint32_t x = (j & 15) ? __builtin_amdgcn_alignbit(hi, lo, 2 * (j & 15)) : lo; // code in the low bits, later bases above
-                    if (SHORT_K) x &= kmask24;
-                    const uint32_t h = __umul24(x, BLOOM_C1);
-                    c1 = __builtin_amdgcn_alignbit(c1, bloom_test(lds_at(L12_BASE + ((h >> 16) & amask)), h, x), 31); // c1 = c1 << 1 | bit
-                }
-                if (lane == 63) c1 = 0;
-            }
-            // ---- level 2, only for the survivors: three more bits in a second word, keyed on the whole code ----
-            while (c1) {
-                const int j = __ffs(c1) - 1;
-                c1 &= c1 - 1;
+            for (int j = FT_G - 1; j >= 0; --j) {
                 const uint32_t lo = j < 16 ? wa : wb, hi = j < 16 ? wb : wc;
-                const uint32_t f = __funnelshift_r(lo, hi, 2 * (j & 15)) & kmask;
-                const uint32_t h2 = f * BLOOM_C2;
-                const uint32_t word = lds_at(L12_BASE + ((h2 >> sh_w) << 2));
-                cand |= ((word >> (h2 & 31)) & (word >> ((h2 >> 5) & 31)) & (word >> ((h2 >> 10) & 31)) & 1u) << j;
+                uint32_t x = (j & 15) ? __builtin_amdgcn_alignbit(hi, lo, 2 * (j & 15)) : lo; // code in the low bits, later bases above
+                if (SHORT_K) x &= kmask24;
+                const uint32_t h = __umul24(x, BLOOM_C1);
+                c1 = __builtin_amdgcn_alignbit(c1, bloom_test(lds_at(L12_BASE + ((h >> 16) & amask)), h, x), 31); // c1 = c1 << 1 | bit
             }
+            if (lane == 63) c1 = 0;
+        }
+        // ---- level 2, only for the survivors: three more bits in a second word, keyed on the whole code ----
+        while (c1) {
+            const int j = __ffs(c1) - 1;
+            c1 &= c1 - 1;
+            const uint32_t lo = j < 16 ? wa : wb, hi = j < 16 ? wb : wc;
+            const uint32_t f = __funnelshift_r(lo, hi, 2 * (j & 15)) & kmask;
+            const uint32_t h2 = f * BLOOM_C2;
+            const uint32_t word = lds_at(L12_BASE + ((h2 >> sh_w) << 2));
+            cand |= ((word >> (h2 & 31)) & (word >> ((h2 >> 5) & 31)) & (word >> ((h2 >> 10) & 31)) & 1u) << j;
         }
         // ---- append in (lane, bit) = position order; about two candidates per tile survive ----
         uint64_t m = __ballot(cand != 0);
@@ -581,7 +568,6 @@ __global__ __launch_bounds__(FT_THREADS) void sketch_filter_kernel(SketchArgs a,
     // of this kernel are not free -- 2.4 cycles each where a vector instruction costs 3.7, fitted on the SQ counters of two builds.)
     auto advance = [&]() {
         ++tile;
-        if constexpr (MID != 0) ++tiles_done;
         if (tile >= c_end && has_next) { // wave-uniform
             close_slice();
             slice = slice0 + n_k;
@@ -595,23 +581,19 @@ __global__ __launch_bounds__(FT_THREADS) void sketch_filter_kernel(SketchArgs a,
             decoded = false;
         }
     };
-    Pair r0 {}, r1 {}, r2 {};
+    Pair r0 {}, r1 {}, r2 {}, r3 {};
     const bool pipelined = tile < c_end; // wave-uniform
-    if (pipelined) {
+    if (pipelined) { // (a dynamic schedule's chunks hold FT_DEPTH full tiles at least)
         fetch(tile, r0);
-        fetch(tile + 1 < c_end ? tile + 1 : tile, r1); // (a dynamic schedule's chunks hold FT_DEPTH full tiles at least)
+        fetch(tile + 1 < c_end ? tile + 1 : tile, r1);
+        fetch(tile + 2 < c_end ? tile + 2 : tile, r2);
     }
-#if DRPRG_FT_DEPTH == 3
-    Pair r3 {};
-    if (pipelined) fetch(tile + 2 < c_end ? tile + 2 : tile, r2);
-#endif
     __syncthreads(); // Bloom filter in place; the only barrier
     // (middle tier: a tile's bitmap probes are waited for inside process() together with every load the wave has issued, the freshly
     // requested tile included; requesting that tile BEHIND process() instead was measured and changed nothing -- 522 / 534 / 1254 us
     // against 520 / 530 / 1234 on the dense, 2-fold and 8-fold indexes: the other three waves of the SIMD cover the wait)
     if (pipelined)
         for (;;) {
-#if DRPRG_FT_DEPTH == 3
             fetch(ahead2(), r3);
             process(tile, r0);
             advance();
@@ -628,20 +610,6 @@ __global__ __launch_bounds__(FT_THREADS) void sketch_filter_kernel(SketchArgs a,
             process(tile, r3);
             advance();
             if (tile >= c_end) break;
-#else
-            fetch(ahead2(), r2);
-            process(tile, r0);
-            advance();
-            if (tile >= c_end) break;
-            fetch(ahead2(), r0);
-            process(tile, r1);
-            advance();
-            if (tile >= c_end) break;
-            fetch(ahead2(), r1);
-            process(tile, r2);
-            advance();
-            if (tile >= c_end) break;
-#endif
         }
     for (; tile < c_all; ++tile) { // the end of the buffer (the last chunk of the window only), guarded loads
         const int64_t g = (int64_t)tile * WPOS + (int64_t)lane * G;
@@ -659,17 +627,9 @@ __global__ __launch_bounds__(FT_THREADS) void sketch_filter_kernel(SketchArgs a,
             p.b = load16(g + 16);
         }
         process(tile, p);
-        if constexpr (MID != 0) ++tiles_done;
     }
     close_slice();
     if (fw.class_clock && (tid & 255) == 0) atomicMax(&fw.class_clock[1 + (tid >> 8)], (unsigned long long)wall_clock64()); // (waves 4c: when class c was through)
-    if constexpr (MID != 0)
-        if (fw.stat) {
-            atomicAdd(&fw.stat[1], (unsigned long long)st_a);
-            atomicAdd(&fw.stat[2], (unsigned long long)st_b);
-            atomicAdd(&fw.stat[3], (unsigned long long)st_c);
-            if (lane == 0) atomicAdd(&fw.stat[0], (unsigned long long)tiles_done * 63ull * (G / 4));
-        }
 }
 #undef DRPRG_SECOND_STAGE
 #undef DRPRG_BLOCK_TEST
@@ -684,7 +644,7 @@ uint32_t filter_n_tiles(uint64_t n_bases, int positions_per_lane)
     return (uint32_t)((n_bases + wpos - 1) / wpos);
 }
 
-uint32_t filter_grid(bool level0, int n_cus, uint32_t n_tiles)
+uint32_t filter_grid(bool level0, int n_cus, uint32_t n_tiles, uint32_t cap)
 {
     // persistent grid: the workgroups that stay resident (1024 threads each; 64 KB of LDS: two per CU, 128 KB with
     // level 0: one per CU), never more waves than there are wave tiles
@@ -692,10 +652,7 @@ uint32_t filter_grid(bool level0, int n_cus, uint32_t n_tiles)
     const uint32_t need = (n_tiles + FT_WAVES - 1) / FT_WAVES;
     if (grid > need) grid = need;
     if (grid > (uint32_t)(MAX_SLICES / FT_WAVES)) grid = MAX_SLICES / FT_WAVES;
-    if (const char* e = std::getenv("DRPRG_FT_GRID")) { // (tests: few workgroups, so that a small batch gives every wave a chunk schedule)
-        const int cap = std::atoi(e);
-        if (cap >= 1 && grid > (uint32_t)cap) grid = (uint32_t)cap;
-    }
+    if (cap && grid > cap) grid = cap; // (tests: few workgroups, so that a small batch gives every wave a chunk schedule)
     return grid ? grid : 1;
 }
 
@@ -706,7 +663,7 @@ size_t filter_small_words() { return FT_SMALL_HEAD + 4 + 4 * (size_t)MAX_EX_WG; 
 uint32_t* filter_super_counts(uint32_t* small) { return small + MAX_CHUNKS; }
 uint32_t filter_super_words() { return (uint32_t)MAX_SLICES; }
 
-FilterSched make_filter_sched(uint32_t n_tiles, uint32_t n_wg, const uint32_t share[4])
+FilterSched make_filter_sched(uint32_t n_tiles, uint32_t n_wg, const uint32_t share[4], const FilterSchedKnobs& knobs)
 {
     FilterSched s {};
     for (int r = 0; r < FT_MAX_ROUNDS; ++r) s.first_ticket[r] = 0xFFFFFFFFu;
@@ -714,26 +671,6 @@ FilterSched make_filter_sched(uint32_t n_tiles, uint32_t n_wg, const uint32_t sh
     s.per_wg = FT_WAVES;
     s.n_tiles = n_tiles;
     s.tpw0 = (n_tiles + n_wg * FT_WAVES - 1) / (n_wg * FT_WAVES);
-    // DRPRG_FT_SCHED (read at every launch: tests switch it): "static", or "f,d,m[,a]" = round 0's part of the tiles in 1/256, the divisor of
-    // the dynamic rounds x 16 (a round hands every wave 16 / d of an even share of what is left), the smallest chunk in tiles, and the
-    // fewest tiles per wave a batch must have for a dynamic schedule at all (64: below that the static split is as good, and cheaper)
-    struct Knobs {
-        bool is_static = false;
-        uint32_t f = 180, d = 32, m = 4, min_avg = 64;
-    } knobs;
-    if (const char* e = std::getenv("DRPRG_FT_SCHED")) {
-        if (std::string(e) == "static") knobs.is_static = true;
-        else {
-            unsigned a = 0, b = 0, c = 0, g = 64;
-            const int got = std::sscanf(e, "%u,%u,%u,%u", &a, &b, &c, &g);
-            if (got >= 3 && a >= 1 && a <= 250 && b >= 17 && b <= 1024 && c >= 4 && c <= 4096 && g >= 8) {
-                knobs.f = a;
-                knobs.d = b;
-                knobs.m = c;
-                knobs.min_avg = g;
-            }
-        }
-    }
     uint32_t min_share = share[0];
     for (int c = 1; c < 4; ++c) min_share = std::min(min_share, share[c]);
     // the schedule of ONE workgroup, for the smaller of the two sizes an even split of the window gives (the kernel's workgroups find their
@@ -785,8 +722,21 @@ void init_candidate_work(FilterWork& fw, const FilterBuffers& b, int n_cus)
     fw.max_len = b.max_len;
 }
 
+// The shares of the four wave classes of a workgroup (sketch_filter_kernel: a SIMD issues for its oldest wave first).  Measured where the
+// classes of the level-0 forms (one workgroup per CU, four waves per SIMD) end with even shares -- 8d index 208 / 243 / 291 / 351 us of a 366 us
+// launch, packed 139 / 184 / 237 / 292 of 309 -- and set so that they end together there: 306 / 288 / 286 / 304 of 320 us, packed 219 / 226 /
+// 240 / 257 of 270.  The other workloads of the level-0 forms gain less from the same shares (middle tier, dense 8d genes 501 -> 479 us,
+// 8-fold index 1252 -> 1219; 4 kb reads 1966 -> 1801) and none loses; the forms with two workgroups per CU keep even shares.
+// (the middle tier's waves wait for the L2 more and for each other less: its classes end at 1 : 1.13 : 1.30 : 1.49 with even shares)
+// Any shares give the same candidates: the ranges stay in wave order.
+const uint32_t* filter_builtin_shares(bool mid, bool packed)
+{
+    static const uint32_t ascii_l0[4] = { 397, 294, 200, 133 }, packed_l0[4] = { 422, 292, 184, 126 }, mid_l0[4] = { 356, 292, 220, 156 };
+    return mid ? mid_l0 : packed ? packed_l0 : ascii_l0;
+}
+
 hipError_t launch_sketch_filter(const SketchArgs& a, const BloomTables& bt, int n_cus, const FilterBuffers& b, const ReadClusterArgs& rc, FilterWork& fw,
-    hipStream_t stream, KernelTimer timer)
+    const Switches& sw, hipStream_t stream, KernelTimer timer)
 {
     fw = FilterWork {};
     fw.read_begin = 0;
@@ -798,14 +748,11 @@ hipError_t launch_sketch_filter(const SketchArgs& a, const BloomTables& bt, int 
     if (!mid && (1u << bt.bloom_wbits) > (uint32_t)FT_BLOOM_WORDS) return hipErrorInvalidValue;
     if (!mid && bt.bloom0 && (1u << bt.bloom0_wbits) != (uint32_t)FT_L0_WORDS) return hipErrorInvalidValue;
     if (!mid && bt.bloom0 && (!bt.bloomr || !bt.bloom0f)) return hipErrorInvalidValue;
-    if (const char* dbg = std::getenv("DRPRG_FT_DEBUG")) fw.debug = (uint32_t)std::atoi(dbg); // 1 no filter test, 4 no level 0, 8 no read_cluster_kernel
-    const bool level0 = mid || (bt.bloom0 != nullptr && a.k == 15 && ((size_t)4 << bt.bloom_wbits) + (size_t)FT_L0_WORDS * 4 <= 160 * 1024
-        && !(fw.debug & 4u));
+    const bool level0 = mid || (bt.bloom0 != nullptr && a.k == 15 && ((size_t)4 << bt.bloom_wbits) + (size_t)FT_L0_WORDS * 4 <= 160 * 1024);
     // Small tier: the second stage against a block filter in the L2 (sketch_filter_kernel<.., MID = 2>: the level-0 array then holds level 0 alone and
     // lets fewer groups through -- 11 M per 10 M x 150 bp) for packed batches, round 2-5's all-LDS form for ASCII ones; DRPRG_FILTER_STAGE2=l2|lds asks for one of
-    // the two whatever the format (read at every launch: A/B runs, tests).  Both leave the same candidates behind verify: the tests map with both.
-    const char* const stage2 = std::getenv("DRPRG_FILTER_STAGE2");
-    const bool want_l2 = stage2 && *stage2 ? std::string(stage2) == "l2" : a.packed != 0; // (the kernel's header comment: packed batches have the L2 probes to spare)
+    // the two whatever the format (A/B runs, tests).  Both leave the same candidates behind verify: the tests map with both.
+    const bool want_l2 = sw.stage2 == Stage2::by_format ? a.packed != 0 : sw.stage2 == Stage2::l2; // (the kernel's header comment: packed batches have the L2 probes to spare)
     const bool blk = !mid && level0 && want_l2 && bt.blkc != nullptr && bt.blkc_wbits >= 1 && bt.blkc_wbits <= MID_C_MAX_WBITS;
     fw.bloom = bt.bloom;
     fw.bloom_wbits = bt.bloom_wbits;
@@ -814,35 +761,15 @@ hipError_t launch_sketch_filter(const SketchArgs& a, const BloomTables& bt, int 
     fw.mid_bitmap = bt.mid_bitmap;
     fw.midc = blk ? bt.blkc : bt.midc;
     fw.midc_wbits = blk ? bt.blkc_wbits : bt.midc_wbits;
-    fw.stat = mid ? b.stat : nullptr;
-    const uint32_t grid = filter_grid(level0, n_cus, filter_n_tiles(a.n_bases, filter_positions_per_lane(level0, a.packed != 0)));
-    {   // The shares of the four wave classes of a workgroup (sketch_filter_kernel: a SIMD issues for its oldest wave first).  Measured where the
-        // classes of the level-0 forms (one workgroup per CU, four waves per SIMD) end with even shares -- 8d index 208 / 243 / 291 / 351 us of a 366 us
-        // launch, packed 139 / 184 / 237 / 292 of 309 -- and set so that they end together there: 306 / 288 / 286 / 304 of 320 us, packed 219 / 226 /
-        // 240 / 257 of 270.  The other workloads of the level-0 forms gain less from the same shares (middle tier, dense 8d genes 501 -> 479 us,
-        // 8-fold index 1252 -> 1219; 4 kb reads 1966 -> 1801) and none loses; the forms with two workgroups per CU keep even shares.
-        // DRPRG_FT_SHARE=a,b,c,d (any scale): measurements.  Any shares give the same candidates: the ranges stay in wave order.
-        // (read at every launch: the tests map one batch with several)
-        const char* const share_env = std::getenv("DRPRG_FT_SHARE");
-        const bool from_env = share_env != nullptr;
-        std::array<uint32_t, 4> env_share { 256, 256, 256, 256 };
-        if (share_env) {
-            double v[4] = { 1, 1, 1, 1 };
-            if (std::sscanf(share_env, "%lf,%lf,%lf,%lf", &v[0], &v[1], &v[2], &v[3]) == 4 && v[0] > 0 && v[1] > 0 && v[2] > 0 && v[3] > 0) {
-                const double sum = v[0] + v[1] + v[2] + v[3];
-                uint32_t acc = 0;
-                for (int c = 0; c < 3; ++c) acc += env_share[c] = (uint32_t)(1024.0 * v[c] / sum + 0.5);
-                env_share[3] = 1024u - acc;
-            }
-        }
-        // (the middle tier's waves wait for the L2 more and for each other less: its classes end at 1 : 1.13 : 1.30 : 1.49 with even shares)
-        static const uint32_t even[4] = { 256, 256, 256, 256 }, ascii_l0[4] = { 397, 294, 200, 133 }, packed_l0[4] = { 422, 292, 184, 126 }, mid_l0[4] = { 356, 292, 220, 156 };
-        const uint32_t* share = from_env ? env_share.data() : !level0 ? even : b.wave_share ? b.wave_share : mid ? mid_l0 : a.packed ? packed_l0 : ascii_l0;
-        fw.class_clock = level0 && !from_env ? b.class_clock : nullptr;
+    const uint32_t grid = filter_grid(level0, n_cus, filter_n_tiles(a.n_bases, filter_positions_per_lane(level0, a.packed != 0)), sw.ft_grid);
+    {   // the shares of the four wave classes of a workgroup (filter_builtin_shares); DRPRG_FT_SHARE pins them (the tests map one batch with several)
+        static const uint32_t even[4] = { 256, 256, 256, 256 };
+        const uint32_t* share = sw.ft_share_pinned ? sw.ft_share : !level0 ? even : b.wave_share ? b.wave_share : filter_builtin_shares(mid, a.packed != 0);
+        fw.class_clock = level0 && !sw.ft_share_pinned ? b.class_clock : nullptr;
         for (int c = 0; c < 4; ++c) fw.wave_share[c] = share[c];
     }
     // the chunk schedule: dynamic when the batch is large enough
-    fw.sched = make_filter_sched(filter_n_tiles(a.n_bases, filter_positions_per_lane(level0, a.packed != 0)), grid, fw.wave_share);
+    fw.sched = make_filter_sched(filter_n_tiles(a.n_bases, filter_positions_per_lane(level0, a.packed != 0)), grid, fw.wave_share, sw.ft_sched);
     fw.n_slices = grid * fw.sched.per_wg;
     {   // the slices' geometry (FilterWork::slice_budget): a floor of up to 256 entries per slice -- a quarter of the workgroup's budget at most --
         // and the rest by the tile.  (A workgroup's range: an even split to the tile, or -- static schedule -- 16 waves x tiles per wave.)
@@ -908,7 +835,7 @@ hipError_t launch_sketch_filter(const SketchArgs& a, const BloomTables& bt, int 
         launch_timed(timer, kernel, dim3(grid), dim3(FT_THREADS), dyn, stream, a, fw);
     }
     HIP_TRY(hipGetLastError());
-    const bool skip_rc = (fw.debug & 8u) != 0; // debug 8: every read with a hit goes the generic way
+    const bool skip_rc = sw.skip_read_cluster; // (DRPRG_FT_DEBUG bit 8: every read with a hit goes the generic way)
     HIP_TRY(launch_candidate_stage(a, fw, rc, n_cus, stream, skip_rc));
     ReadClusterArgs rct = rc;
     if (!skip_rc) { // the batch totals come out of read_cluster_kernel's workgroup 0

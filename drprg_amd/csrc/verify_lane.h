@@ -3,9 +3,6 @@
 // inside the external `pandora map` process of /root/reference/src/lib.rs:580-642.
 #pragma once
 #include "filter_common.h"
-#ifndef DRPRG_VERIFY_OUTWARD
-#define DRPRG_VERIFY_OUTWARD 1
-#endif
 
 namespace drprg {
 namespace dev {
@@ -153,7 +150,7 @@ __device__ __forceinline__ void verify_emit(const SketchArgs& a, const ReadClust
 
 // One candidate, start to finish, by one lane
 template <int KC, bool PACKED>
-__device__ __forceinline__ void verify_one_lane(const SketchArgs& a, const FilterWork& fw, const ReadClusterArgs& rc, const VerifyConsts& c, int64_t gp, VerifyOut& o,
+__device__ __forceinline__ void verify_one_lane(const SketchArgs& a, const ReadClusterArgs& rc, const VerifyConsts& c, int64_t gp, VerifyOut& o,
     uint32_t& my_hits, uint32_t& my_nmin, uint32_t& my_maxlen)
 {
     const uint32_t* __restrict__ slot_key = c.slot_key;
@@ -241,7 +238,7 @@ __device__ __forceinline__ void verify_one_lane(const SketchArgs& a, const Filte
             g = (hf < hr ? hf : hr) + 1;
         }
         bool found = false;
-        if (g && !(fw.debug & 32u)) { // (DRPRG_FT_DEBUG=32: timing only, no table probe and nothing after it)
+        if (g) {
             const uint32_t h = g - 1;
             uint32_t sl = table_slot_dev(h, a.table_bits);
             found = table_find4(slot_key, tmask, h, sl);
@@ -266,7 +263,6 @@ __device__ __forceinline__ void verify_one_lane(const SketchArgs& a, const Filte
                 r2w = __funnelshift_l(r3w, r2w, s2);
                 // steps that can count at all: inside the read and the window, no N in the k-mer (bit i = step i)
                 const uint32_t valid = ((2u << i_hi) - 1u) & ~((1u << i_lo) - 1u) & ~(uint32_t)(bad >> of);
-#if DRPRG_VERIFY_OUTWARD
                 // The candidate is a minimizer iff the neighbours with hash >= its own form a run of w-1 around it: L on its left, then
                 // w-1-L on its right.  Walked outward from the candidate -- left until the first smaller hash (or enough), then right
                 // exactly as far as still needed -- that is at most w hashes per lane, whatever L is, where every step q_first ..
@@ -279,8 +275,8 @@ __device__ __forceinline__ void verify_one_lane(const SketchArgs& a, const Filte
                 const int need = w - 1;
                 const int l_lim = l_cap < need ? l_cap : need;
                 int dir = l_lim > 0 ? -1 : 1, j = ic + dir, remaining = need; // remaining: neighbours still to be shown >= the candidate
-                bool going = l_cap + r_cap >= need && need > 0 && (dir < 0 || need <= r_cap) && !(fw.debug & 16u);
-                bool is_min = need == 0 || (fw.debug & 16u) != 0; // (DRPRG_FT_DEBUG=16: measurement only, no window test)
+                bool going = l_cap + r_cap >= need && need > 0 && (dir < 0 || need <= r_cap);
+                bool is_min = need == 0;
                 // (the three words one bit to the right: step j then starts at the odd bit 2j + 1, and the funnel shift that extracts it is
                 // never one by zero -- which v_alignbit_b32 cannot do and the compiler guards with a branch)
                 const uint32_t q0 = r0w >> 1, q1 = __builtin_amdgcn_alignbit(r0w, r1w, 1), q2 = __builtin_amdgcn_alignbit(r1w, r2w, 1);
@@ -299,28 +295,7 @@ __device__ __forceinline__ void verify_one_lane(const SketchArgs& a, const Filte
                     dir = turn ? 1 : dir;
                     j = turn ? ic + 1 : j + dir;
                 }
-                const uint32_t streak = is_min ? (uint32_t)need : 0u, right = 0;
-#else
-                uint32_t streak = 0, right = 0, alive = 1;
-                uint32_t rcw = revcomp_code(r0w >> sh_k, k) << 2; // the reverse complement rolls along: one base in, one out
-                const int n_steps = (fw.debug & 16u) ? 0 : 2 * w - 1; // (DRPRG_FT_DEBUG=16: measurement only, no window test)
-                for (int i = 0; i < n_steps; ++i) {
-                    const uint32_t f = r0w >> sh_k;
-                    rcw = (rcw >> 2) | ((~f & 3u) << (2 * k - 2));
-                    r0w = __funnelshift_l(r1w, r0w, 2);
-                    r1w = __funnelshift_l(r2w, r1w, 2);
-                    r2w <<= 2;
-                    const uint32_t hf = verify_mix<KC>(f, kmask), hr = verify_mix<KC>(rcw, kmask);
-                    const uint32_t x = (hf < hr ? hf : hr) + 1;
-                    const bool ok = ((valid >> i) & 1u) && x >= g;
-                    if (i < ic) streak = ok ? streak + 1 : 0;
-                    else if (i > ic) {
-                        alive = ok ? alive : 0u;
-                        right += alive;
-                    }
-                }
-#endif
-                if ((int)(streak + right) >= w - 1) verify_emit(a, rc, c, gp, r0, r1, strand, sf, o, my_hits, my_nmin, my_maxlen);
+                if (is_min) verify_emit(a, rc, c, gp, r0, r1, strand, sf, o, my_hits, my_nmin, my_maxlen);
             }
         }
     }

@@ -6,10 +6,6 @@ capacity lowered through DRPRG_HIP_MIN_CAPACITY, which is read when a context op
 (drprg_hip_buffer_info) and that the results are the oracle's and those of the same batch on a context whose buffers did not have to
 grow: nothing of an aborted attempt may be counted twice.  Buffer capacity only grows and survives reset(), so every case opens a
 fresh context per input format."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
@@ -261,24 +257,10 @@ def test_direct_sequence_reruns_a_batch_that_overflowed(tmp_path, oracle, monkey
     _direct_case(tmp_path, oracle, monkeypatch, 11, 15)
 
 
-_LDS_CHILD = r"""
-import sys
-sys.path[:0] = [sys.argv[1], sys.argv[1] + "/tests"]
-import pytest
-sys.exit(pytest.main(["-q", "-p", "no:cacheprovider", "-m", "gpu", sys.argv[1] + "/tests/test_gpu_regrow.py::test_direct_sequence_reruns_a_batch_that_overflowed"]))
-"""
-
-
-def test_direct_sequence_lds_form_reruns(tmp_path):
-    """The same with DRPRG_DIRECT_FORM=lds (sketch_probe_kernel for every (k, w)): the switch is read once per process, so the case runs
-    in a child process of its own"""
-    if os.environ.get("DRPRG_DIRECT_FORM") == "lds":
-        pytest.skip("this process runs the lds form already")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, DRPRG_DIRECT_FORM="lds")
-    r = subprocess.run([sys.executable, "-c", _LDS_CHILD, root], env=env, cwd=str(tmp_path), capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    assert "1 passed" in r.stdout, r.stdout[-3000:]
+def test_direct_sequence_lds_form_reruns(tmp_path, oracle, monkeypatch):
+    """The same with DRPRG_DIRECT_FORM=lds (sketch_probe_kernel for every (k, w)), which a context reads when it opens"""
+    monkeypatch.setenv("DRPRG_DIRECT_FORM", "lds")
+    _direct_case(tmp_path, oracle, monkeypatch, 11, 15)
 
 
 @pytest.mark.parametrize("packed", [False, True], ids=["ascii", "packed"])
@@ -303,10 +285,11 @@ def test_generic_hit_buffer_regrows_once(tmp_path, oracle, monkeypatch, packed):
 
 
 # ---- 4. the filter's geometry changing under one context ---------------------------------------------------------------------------
-def test_geometry_changes_between_batches_on_one_context(tmp_path, oracle, monkeypatch):
-    """One context, one batch after the other with DRPRG_FT_GRID 7 -> 3 -> 5 -> unset and the schedule switching with it, the third batch
-    overflowing in the middle: every batch exact into an accumulator of its own.  (A launch with fewer slices than the one before finds
-    that launch's slice counts behind its own: they must not be read as its own.)"""
+def test_geometry_changes_across_resets_on_one_context(tmp_path, oracle, monkeypatch):
+    """One context, one batch after the other with DRPRG_FT_GRID 7 -> 3 -> 5 -> unset and the schedule switching with it -- taken up by the
+    reset() in front of each batch, since a context maps with the switches it was opened or last reset with --, the third batch overflowing
+    in the middle: every batch exact into an accumulator of its own.  (A launch with fewer slices than the one before finds that launch's
+    slice counts behind its own: they must not be read as its own; reset() keeps the lanes' buffers as they are.)"""
     import torch
     panel = _dense_panel()[0]
     steps = [("7", "100,20,4,8", _sparse(30000, 41)), ("3", "static", _sparse(26000, 42)), ("5", "60,64,5,8", _dense(24000, 43)),
@@ -319,6 +302,7 @@ def test_geometry_changes_between_batches_on_one_context(tmp_path, oracle, monke
                 monkeypatch.delenv(name, raising=False)
             else:
                 monkeypatch.setenv(name, v)
+        ctx.reset()
         ocov, oprg, ocnt = _Oracle.of(oracle, panel.prgs, bases, offs, 11, 15)
         tb, to, _, _ = _to_device(torch, bases, offs, False)
         acc = torch.zeros(2 * ctx.n_knodes + ctx.n_prgs, dtype=torch.int32, device=dev)

@@ -12,7 +12,7 @@ if [ -z "$SKIP_TESTS" ]; then
   grep -q " passed" $out/${tag}_tests.txt && ! grep -q "failed\|error" $out/${tag}_tests.txt || { echo "tests not green: stopping"; tail -30 $out/${tag}_tests.txt; exit 1; }
 fi
 for wl in $wls; do
-  DRPRG_FT_STATS=1 timeout 200 python bench.py --full --workload $wl --steps 10 --warmup 3 --cpu-sample 0 --e2e 0 > $out/${tag}_bench_${wl}.json 2> $out/${tag}_bench_${wl}.err
+  timeout 200 python bench.py --full --workload $wl --steps 10 --warmup 3 --cpu-sample 0 --e2e 0 > $out/${tag}_bench_${wl}.json 2> $out/${tag}_bench_${wl}.err
   tail -2 $out/${tag}_bench_${wl}.err
   python - <<PY
 import json
