@@ -297,8 +297,14 @@ __global__ __launch_bounds__(SK_THREADS) void sketch_probe_kernel(SketchArgs a)
                 const uint64_t r0 = o0, r1 = o1, pos = gp - r0;
                 const uint32_t strand = (s_strand[j / SK_G] >> (j % SK_G)) & 1u;
                 my_hits += rec.y;
-                if (pos >= (1ull << HIT_POS_BITS)) atomicOr(a.overflow, 2u);
-                else if (at < a.tile_cap) {
+                if (pos >= (1ull << HIT_POS_BITS)) {
+                    atomicOr(a.overflow, 2u);
+                    if (at < a.tile_cap) { // (the entry is counted: it must not stay whatever the slice held before -- read_cluster_kernel runs before the host looks at the flag)
+                        a.tile_info[slice + at] = (uint64_t)read;
+                        a.tile_pos1[slice + at] = 0u;
+                        a.tile_rec[slice + at] = make_uint4(0, 0, 0, 0);
+                    }
+                } else if (at < a.tile_cap) {
                     const uint32_t kn = sf.z, prg = sf.w & 0xFFFu;
                     const uint32_t rev = ((kn & 1u) == strand) ? 0u : 1u;
                     // size threshold of a cluster of this read on that PRG (cluster_eval_kernel)

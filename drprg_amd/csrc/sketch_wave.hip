@@ -315,8 +315,14 @@ __device__ __forceinline__ void sketch_wave_tile(const SketchArgs& a, uint32_t t
             const Entry e = decode(i);
             my_hits += e.sf.y;
             const uint32_t at = base + written + lanes_below(tm);
-            if (e.pos >= (1ull << HIT_POS_BITS)) atomicOr(a.overflow, 2u);
-            else if (at < a.tile_cap) {
+            if (e.pos >= (1ull << HIT_POS_BITS)) {
+                atomicOr(a.overflow, 2u);
+                if (at < a.tile_cap) { // (the entry is counted: it must not stay whatever the slice held before -- read_cluster_kernel runs before the host looks at the flag)
+                    a.tile_info[slice + at] = (uint64_t)e.read;
+                    a.tile_pos1[slice + at] = 0u;
+                    a.tile_rec[slice + at] = make_uint4(0, 0, 0, 0);
+                }
+            } else if (at < a.tile_cap) {
                 a.tile_info[slice + at] = ((uint64_t)e.slot << 32) | ((uint64_t)e.strand << 31) | (uint64_t)e.read;
                 a.tile_pos1[slice + at] = (uint32_t)e.pos + 1;
                 a.tile_rec[slice + at] = make_uint4(e.sf.x, e.sf.y, (e.strand << 31) | (((e.prg << 1) | e.rev) << 16) | e.thr, (e.kn >> 1) * 2u + e.rev);

@@ -26,6 +26,15 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+# oracle.c's orc_hit and orc_cluster, as the compiler lays them out
+HIT_DTYPE = np.dtype([("prg", "<u4"), ("knode", "<u4"), ("pos", "<u4"), ("fwd", "u1")], align=True)
+CLUSTER_DTYPE = np.dtype([("first", "<i4"), ("n", "<i4"), ("prg", "<u4"), ("first_pos", "<u4"), ("last_pos", "<u4"), ("fwd", "u1"), ("alive", "u1")],
+                         align=True)
+TRACED_DTYPE = np.dtype(dict(names=list(CLUSTER_DTYPE.names) + ["thr"], formats=[CLUSTER_DTYPE[n] for n in CLUSTER_DTYPE.names] + ["<u4"],
+                             offsets=[CLUSTER_DTYPE.fields[n][1] for n in CLUSTER_DTYPE.names] + [CLUSTER_DTYPE.itemsize],
+                             itemsize=CLUSTER_DTYPE.itemsize + 4))  # oracle.c's struct orc_traced
+
+
 class Oracle:
     def __init__(self):
         ensure_built()
@@ -39,6 +48,21 @@ class Oracle:
         L.orc_map_reads.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_double, C.c_uint32,
                                     C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]
+        L.orc_trace_new.restype = C.c_void_p
+        L.orc_trace_new.argtypes = []
+        L.orc_trace_free.restype = None
+        L.orc_trace_free.argtypes = [C.c_void_p]
+        L.orc_read_clusters.restype = C.c_int64
+        L.orc_read_clusters.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_double, C.c_uint32, C.c_void_p, C.c_int64,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        for name in ("orc_trace_hits", "orc_trace_runs", "orc_trace_clusters"):
+            getattr(L, name).restype = C.c_void_p
+            getattr(L, name).argtypes = [C.c_void_p]
+        L.orc_trace_counts.restype = None
+        L.orc_trace_counts.argtypes = [C.c_void_p, C.c_void_p]
+        L.orc_cluster_threshold.restype = C.c_uint32
+        L.orc_cluster_threshold.argtypes = [C.c_uint64, C.c_int, C.c_double, C.c_uint32, C.c_uint32]
+        self._trace = None
         L.orc_allele_stats.restype = None
         L.orc_allele_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.POINTER(C.c_double)]
         L.orc_likelihood.restype = C.c_double
@@ -196,6 +220,33 @@ class Oracle:
         assert rc == 0
         return covg, prg_reads, dict(zip(("reads", "bases", "minimizers", "hits", "clusters_kept", "hits_kept"),
                                          (int(x) for x in counters)))
+
+    def read_clusters(self, seq, idx, w, k, max_diff, fraction, min_cluster_size):
+        """One read traced by orc_read_clusters (the body of orc_map_reads' loop).  Returns a dict: hits (HIT_DTYPE, orc_sort_hits order), runs
+        (every run define_clusters cuts, hit order; `alive` = passed the size threshold; `thr`), clusters (the runs that passed, after
+        filter_clusters, clusterComp order; `alive` = survived the sweep; `thr`), minimizers, keyed (minimizers whose hash is an index key)."""
+        L = self.lib
+        if self._trace is None:
+            self._trace = L.orc_trace_new()
+        seq = np.frombuffer(seq, np.uint8) if isinstance(seq, (bytes, bytearray)) else np.ascontiguousarray(seq, np.uint8)
+        L.orc_read_clusters(self._trace, _p(seq) if seq.size else None, seq.size, w, k, max_diff, fraction, min_cluster_size, _p(idx["keys"]),
+                            len(idx["keys"]), _p(idx["rec_off"]), _p(idx["rec_prg"]), _p(idx["rec_knode"]), _p(idx["rec_strand"]),
+                            _p(idx["min_path_len"]))
+        cnt = np.zeros(5, np.int64)
+        L.orc_trace_counts(self._trace, _p(cnt))
+        nm, keyed, nh, nruns, nc = (int(x) for x in cnt)
+
+        def take(fn, n, dtype):
+            if n == 0:
+                return np.zeros(0, dtype)
+            return np.frombuffer(C.string_at(getattr(L, fn)(self._trace), n * dtype.itemsize), dtype)
+
+        return dict(hits=take("orc_trace_hits", nh, HIT_DTYPE), runs=take("orc_trace_runs", nruns, TRACED_DTYPE),
+                    clusters=take("orc_trace_clusters", nc, TRACED_DTYPE), minimizers=nm, keyed=keyed, length=int(seq.size))
+
+    def cluster_threshold(self, read_len, w, fraction, min_cluster_size, min_path_len):
+        """the size threshold orc_define_clusters measures a run against"""
+        return int(self.lib.orc_cluster_threshold(int(read_len), w, fraction, min_cluster_size, int(min_path_len)))
 
     def allele_stats(self, fwd, rev, min_kmer_covg):
         fwd = np.ascontiguousarray(fwd, np.uint32)
