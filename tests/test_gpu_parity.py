@@ -545,7 +545,9 @@ def _device_reads(torch, genomes, n_reads, seed, long_reads=False):
 @pytest.mark.parametrize("name,illumina,n_reads", [("mtb_8d", True, 10_000_000), ("mtb_8d", False, 2_000_000), ("big", True, 10_000_000)],
                          ids=["config1_10M_illumina", "config2_2M_nanopore", "config4_10M_500_loci"])
 def test_full_size_properties(tmp_path, name, illumina, n_reads):
-    """BASELINE.json's full sizes, where the oracle cannot follow in seconds: (1) sharding invariance -- coverage(whole batch)
+    """BASELINE.json's full sizes through size-independent properties, HIP against HIP (the oracle's side of batches this large and larger
+    is in tests/test_gpu_wide_batches.py: the 10 M-read batch mapped whole by the oracle, 2^32-base batches with hits planted across 2^31 and
+    2^32, 2^28 reads): (1) sharding invariance -- coverage(whole batch)
     == coverage(first half) + coverage(second half), bit for bit (what makes the multi-GPU reduce exact); (2) the sequence
     `auto` picks and the direct kernel + generic cluster pipeline (radix sort, cluster kernels) give the identical vector;
     (3) a second pass over the same batch doubles every counter (accumulation, no lost or duplicated atomics)."""
