@@ -14,6 +14,7 @@
 #include "mapper.h"
 #include "rccl_dyn.h"
 #include "pack.h"
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <fcntl.h>
@@ -97,6 +98,11 @@ struct drprg_hip_ctx {
     std::vector<uint32_t> covg, prg_reads;
     bool host_coverage_valid = false;
     uint64_t total_bases = 0;
+    // depth cap (drprg_hip_set_max_covg; the rule is in include/drprg_hip.h): total_bases above is the running total B
+    uint64_t max_covg = ~0ull; // off
+    bool cap_reached = false;
+    uint64_t accepted_reads = 0, dropped_reads = 0;
+    bool bases_without_reads = false; // total_bases holds bases that came with a coverage vector (set_coverage, load_coverage): accepted_reads does not stand for them
     int threads = 4; // parser threads of drprg_hip_map_fastx
     bool packed_input = false; // drprg_hip_set_input_format: map_fastx packs the reads to 2 bits on the parser threads
     uint32_t ginfo[4] = { 0, 0, 0, 0 };
@@ -354,6 +360,75 @@ int drprg_hip_set_opts_sized(drprg_hip_ctx* ctx, const drprg_hip_map_opts* opts,
     return drprg_hip_set_opts(ctx, opts);
 }
 
+// ---- depth cap -------------------------------------------------------------------------------------------------------------
+// T = (max_covg + 1) * genome_size, the bases at which the context stops accepting reads; false: no cap (off, or beyond what a
+// 64-bit count of bases can reach)
+static bool cap_target(const drprg_hip_ctx* ctx, uint64_t& T)
+{
+    if (ctx->max_covg >= 0xFFFFFFFFull) return false;
+    const unsigned __int128 t = (unsigned __int128)(ctx->max_covg + 1) * ctx->params.genome_size;
+    if (t > (unsigned __int128)~0ull) return false;
+    T = (uint64_t)t;
+    return true;
+}
+
+// false: the cap has been reached (by an earlier call, or by a cap set below what is mapped already) -- the n_reads offered are dropped
+static bool cap_open(drprg_hip_ctx* ctx, uint64_t n_reads)
+{
+    uint64_t T;
+    if (!ctx->cap_reached && cap_target(ctx, T) && ctx->total_bases >= T) ctx->cap_reached = true;
+    if (ctx->cap_reached) ctx->dropped_reads += n_reads;
+    return !ctx->cap_reached;
+}
+
+// What accepting a batch does to the cap's state.  Worked out before the batch is mapped, committed after the map call has succeeded: a
+// call that is refused (bad pointers, a read too long, ...) leaves the context as it was.
+struct CapCut {
+    bool reached = false;
+    uint64_t dropped = 0;
+};
+
+static void cap_commit(drprg_hip_ctx* ctx, const CapCut& c, uint64_t n_reads, uint64_t n_bases)
+{
+    ctx->total_bases += n_bases;
+    ctx->accepted_reads += n_reads;
+    if (c.reached) {
+        ctx->cap_reached = true;
+        ctx->dropped_reads += c.dropped;
+    }
+}
+
+// The reads of a host batch the cap accepts: the first `return value` (>= 1; cap_open has said yes).  offsets[0] == 0.
+static uint64_t cap_host_prefix(const drprg_hip_ctx* ctx, const uint64_t* offsets, uint64_t n_reads, CapCut& c)
+{
+    uint64_t T;
+    if (!cap_target(ctx, T)) return n_reads;
+    const uint64_t need = T - ctx->total_bases; // >= 1
+    if (offsets[n_reads] < need) return n_reads;
+    const uint64_t i = (uint64_t)(std::lower_bound(offsets + 1, offsets + n_reads + 1, need) - offsets);
+    c.reached = true;
+    c.dropped = n_reads - i;
+    return i;
+}
+
+// The same for a device batch, whose offsets only the device can read: a batch below the cap is accepted as it is, without a look
+// at the device; the one that crosses it is cut by covg_cut_kernel (Mapper::find_cut) -- after the checks the map call itself makes.
+static void cap_device_prefix(const drprg_hip_ctx* ctx, Mapper& m, const void* d_bases, const void* d_offsets, uint64_t& n_reads, uint64_t& n_bases,
+    const void* d_npos, uint64_t& n_npos, bool packed, void* hip_stream, CapCut& c)
+{
+    uint64_t T;
+    if (n_reads == 0 || !cap_target(ctx, T) || n_bases < T - ctx->total_bases) return;
+    Mapper::check_device_batch(d_bases, d_offsets, n_reads, d_npos, n_npos, packed);
+    const Mapper::CutPoint cut = m.find_cut((const uint64_t*)d_offsets, n_reads, T - ctx->total_bases, (const uint64_t*)d_npos, n_npos, (hipStream_t)hip_stream);
+    c.reached = true;
+    c.dropped = n_reads - cut.n_reads;
+    n_reads = cut.n_reads;
+    n_bases = cut.n_bases;
+    n_npos = cut.n_npos;
+}
+
+static std::vector<Mapper*> mappers_of(drprg_hip_ctx* ctx);
+
 static Mapper& need_mapper(drprg_hip_ctx* ctx)
 {
     if (!ctx->mapper) throw Error(DRPRG_ENODEV, "host-only context: the hot path runs on a HIP device only (no CPU fallback)");
@@ -365,6 +440,7 @@ int drprg_hip_map_fastx(drprg_hip_ctx* ctx, const char* reads_path)
     API_BEGIN(ctx)
     if (!reads_path) throw Error(DRPRG_EINVAL, "null reads path");
     Mapper& m = need_mapper(ctx);
+    if (!cap_open(ctx, 0)) return DRPRG_OK; // the depth cap was reached before this call: the file is not opened
     ctx->host_coverage_valid = false;
     ctx->mapped_paths.push_back(reads_path);
     // multi-threaded ingest into pinned blocks (ingest.cpp); multi-line FASTQ falls back to the serial reader
@@ -380,6 +456,8 @@ int drprg_hip_map_fastx(drprg_hip_ctx* ctx, const char* reads_path)
         hb.n_npos = b.n_npos;
         return hb;
     };
+    uint64_t cap_T = 0;
+    const bool capped = cap_target(ctx, cap_T);
     // page-locked ingest blocks are kept by the process between calls and contexts (PinPool)
     hooks.alloc = [](size_t n) -> void* { return PinPool::get().take(n); };
     hooks.release = [](void* p) { PinPool::get().give_back(p); };
@@ -408,6 +486,21 @@ int drprg_hip_map_fastx(drprg_hip_ctx* ctx, const char* reads_path)
             mapper_of(first).map_host_async(host_batch(b));
         };
     }
+    // Under a depth cap the blocks come in file order, one at a time (IngestHooks::submit_in_order), and are counted HERE, where they
+    // are handed to the devices -- round robin --: the block that crosses the cap goes to its device cut to the accepted reads (so a
+    // device that keeps its blocks resident keeps exactly those), nothing after it is copied anywhere and the ingest takes no new piece of the file.
+    size_t rr = 0;
+    if (capped)
+        hooks.submit_in_order = [&](const PinnedBatch& b) -> bool {
+            if (b.offsets[0] != 0) throw Error(DRPRG_EINVAL, "offsets[0] must be 0");
+            Mapper::HostBatch hb = host_batch(b);
+            CapCut c;
+            hb.n_reads = cap_host_prefix(ctx, b.offsets, b.n_reads, c);
+            if (hb.packed) hb.n_npos = (uint64_t)(std::lower_bound(b.npos, b.npos + b.n_npos, b.offsets[hb.n_reads]) - b.npos);
+            mapper_of(rr++ % ndev).map_host_async(hb);
+            cap_commit(ctx, c, hb.n_reads, b.offsets[hb.n_reads]);
+            return !ctx->cap_reached;
+        };
     // the coverage vectors of the other devices are summed into device 0 ON THE DEVICE (drprg_hip_reduce: one RCCL reduce over
     // the devices of the context, or a peer copy + add kernel per device); unsigned sums commute, so the result does not depend
     // on which device mapped which block
@@ -418,17 +511,45 @@ int drprg_hip_map_fastx(drprg_hip_ctx* ctx, const char* reads_path)
     };
     try {
         IngestStats st = ingest_fastx(reads_path, ctx->threads, hooks);
-        ctx->total_bases += st.bases;
+        if (capped) ctx->dropped_reads += st.discarded_reads; // (the accepted ones were counted block by block)
+        else {
+            ctx->total_bases += st.bases;
+            ctx->accepted_reads += st.reads;
+        }
         fold();
     } catch (const Error& e) {
         if (e.code != DRPRG_EAGAIN_SERIAL) throw; // (a failed multi-device pass leaves partial vectors on the devices: reset before reuse)
         FastxReader rd(reads_path);
         ReadBatch batch;
         while (rd.next_batch(batch, 8u << 20, 1ull << 30)) {
-            m.map_host(batch.bases.data(), batch.offsets.data(), batch.n_reads());
-            ctx->total_bases += batch.bases.size();
+            if (!batch.n_reads()) continue;
+            CapCut c;
+            const uint64_t n = cap_host_prefix(ctx, batch.offsets.data(), batch.n_reads(), c);
+            m.map_host(batch.bases.data(), batch.offsets.data(), n);
+            cap_commit(ctx, c, n, batch.offsets[n]);
+            if (ctx->cap_reached) break;
         }
     }
+    API_END(ctx)
+}
+
+int drprg_hip_set_max_covg(drprg_hip_ctx* ctx, uint64_t max_covg)
+{
+    if (!ctx) return DRPRG_EINVAL;
+    ctx->max_covg = max_covg; // (>= 2^32 - 1: off; what is mapped already counts -- cap_open looks at the running total)
+    return DRPRG_OK;
+}
+
+int drprg_hip_max_covg_info(drprg_hip_ctx* ctx, uint64_t out[4])
+{
+    API_BEGIN(ctx)
+    if (!out) throw Error(DRPRG_EINVAL, "null output");
+    for (Mapper* m : mappers_of(ctx)) m->sync();
+    (void)cap_open(ctx, 0);
+    out[0] = ctx->cap_reached ? 1 : 0;
+    out[1] = ctx->accepted_reads;
+    out[2] = ctx->total_bases;
+    out[3] = ctx->dropped_reads;
     API_END(ctx)
 }
 
@@ -444,9 +565,12 @@ int drprg_hip_map_host(drprg_hip_ctx* ctx, const uint8_t* bases, const uint64_t*
     API_BEGIN(ctx)
     if (n_reads && (!bases || !offsets)) throw Error(DRPRG_EINVAL, "null buffer");
     Mapper& m = need_mapper(ctx);
-    if (n_reads) {
+    if (n_reads && cap_open(ctx, n_reads)) {
+        if (offsets[0] != 0) throw Error(DRPRG_EINVAL, "offsets[0] must be 0");
+        CapCut c;
+        n_reads = cap_host_prefix(ctx, offsets, n_reads, c); // (the offsets are here: a batch that crosses the depth cap is cut on the host)
         m.map_host(bases, offsets, n_reads);
-        ctx->total_bases += offsets[n_reads];
+        cap_commit(ctx, c, n_reads, offsets[n_reads]);
     }
     ctx->host_coverage_valid = false;
     API_END(ctx)
@@ -488,16 +612,19 @@ int drprg_hip_map_host_packed(drprg_hip_ctx* ctx, const uint32_t* words, const u
     if (n_reads && (!words || !offsets)) throw Error(DRPRG_EINVAL, "null buffer");
     if (n_npos && !npos) throw Error(DRPRG_EINVAL, "n_npos > 0 without the positions");
     Mapper& m = need_mapper(ctx);
-    if (n_reads) {
+    if (n_reads && cap_open(ctx, n_reads)) {
+        if (offsets[0] != 0) throw Error(DRPRG_EINVAL, "offsets[0] must be 0");
+        CapCut c;
+        n_reads = cap_host_prefix(ctx, offsets, n_reads, c);
         Mapper::HostBatch hb;
         hb.bases = reinterpret_cast<const uint8_t*>(words);
         hb.offsets = offsets;
         hb.n_reads = n_reads;
         hb.packed = true;
         hb.npos = npos;
-        hb.n_npos = n_npos;
+        hb.n_npos = (uint64_t)(std::lower_bound(npos, npos + n_npos, offsets[n_reads]) - npos); // (all of them unless the batch was cut)
         m.map_host(hb);
-        ctx->total_bases += offsets[n_reads];
+        cap_commit(ctx, c, n_reads, offsets[n_reads]);
     }
     ctx->host_coverage_valid = false;
     API_END(ctx)
@@ -508,9 +635,13 @@ static int map_device_packed(drprg_hip_ctx* ctx, const void* d_words, const void
 {
     API_BEGIN(ctx)
     Mapper& m = need_mapper(ctx);
-    m.map_device_packed((const uint32_t*)d_words, (const uint64_t*)d_offsets, n_reads, n_bases, (const uint64_t*)d_npos, n_npos, (uint32_t*)d_covg,
-        (uint32_t*)d_prg_reads, (hipStream_t)hip_stream, deferred);
-    ctx->total_bases += n_bases;
+    if (n_reads == 0 || cap_open(ctx, n_reads)) { // (an empty batch still goes through the mapper's argument checks)
+        CapCut c;
+        cap_device_prefix(ctx, m, d_words, d_offsets, n_reads, n_bases, d_npos, n_npos, true, hip_stream, c);
+        m.map_device_packed((const uint32_t*)d_words, (const uint64_t*)d_offsets, n_reads, n_bases, (const uint64_t*)d_npos, n_npos, (uint32_t*)d_covg,
+            (uint32_t*)d_prg_reads, (hipStream_t)hip_stream, deferred);
+        cap_commit(ctx, c, n_reads, n_bases);
+    }
     ctx->host_coverage_valid = false;
     API_END(ctx)
 }
@@ -543,9 +674,14 @@ int drprg_hip_map_device(drprg_hip_ctx* ctx, const void* d_bases, const void* d_
 {
     API_BEGIN(ctx)
     Mapper& m = need_mapper(ctx);
-    m.map_device((const uint8_t*)d_bases, (const uint64_t*)d_offsets, n_reads, n_bases, (uint32_t*)d_covg,
-        (uint32_t*)d_prg_reads, (hipStream_t)hip_stream);
-    ctx->total_bases += n_bases;
+    if (n_reads == 0 || cap_open(ctx, n_reads)) {
+        CapCut c;
+        uint64_t no_npos = 0;
+        cap_device_prefix(ctx, m, d_bases, d_offsets, n_reads, n_bases, nullptr, no_npos, false, hip_stream, c);
+        m.map_device((const uint8_t*)d_bases, (const uint64_t*)d_offsets, n_reads, n_bases, (uint32_t*)d_covg,
+            (uint32_t*)d_prg_reads, (hipStream_t)hip_stream);
+        cap_commit(ctx, c, n_reads, n_bases);
+    }
     ctx->host_coverage_valid = false;
     API_END(ctx)
 }
@@ -555,9 +691,14 @@ int drprg_hip_map_device_async(drprg_hip_ctx* ctx, const void* d_bases, const vo
 {
     API_BEGIN(ctx)
     Mapper& m = need_mapper(ctx);
-    m.map_device_async((const uint8_t*)d_bases, (const uint64_t*)d_offsets, n_reads, n_bases, (uint32_t*)d_covg,
-        (uint32_t*)d_prg_reads, (hipStream_t)hip_stream);
-    ctx->total_bases += n_bases;
+    if (n_reads == 0 || cap_open(ctx, n_reads)) {
+        CapCut c;
+        uint64_t no_npos = 0;
+        cap_device_prefix(ctx, m, d_bases, d_offsets, n_reads, n_bases, nullptr, no_npos, false, hip_stream, c);
+        m.map_device_async((const uint8_t*)d_bases, (const uint64_t*)d_offsets, n_reads, n_bases, (uint32_t*)d_covg,
+            (uint32_t*)d_prg_reads, (hipStream_t)hip_stream);
+        cap_commit(ctx, c, n_reads, n_bases);
+    }
     ctx->host_coverage_valid = false;
     API_END(ctx)
 }
@@ -723,6 +864,7 @@ int drprg_hip_set_coverage(drprg_hip_ctx* ctx, const uint32_t* covg, uint64_t n_
     ctx->prg_reads.assign(prg_reads, prg_reads + n_prgs);
     ctx->host_coverage_valid = true;
     ctx->total_bases = total_bases;
+    ctx->bases_without_reads = true;
     if (ctx->mapper) ctx->mapper->upload(ctx->covg, ctx->prg_reads);
     API_END(ctx)
 }
@@ -746,6 +888,9 @@ int drprg_hip_reset(drprg_hip_ctx* ctx)
     ctx->prg_reads.clear();
     ctx->host_coverage_valid = false;
     ctx->total_bases = 0;
+    ctx->cap_reached = false; // (the cap itself stays)
+    ctx->accepted_reads = ctx->dropped_reads = 0;
+    ctx->bases_without_reads = false;
     ctx->mapped_paths.clear();
     ctx->needs_reset = false;
     API_END(ctx)
@@ -791,7 +936,7 @@ int drprg_hip_map_resident(drprg_hip_ctx* ctx, drprg_hip_ctx* from)
     for (size_t i = 0; i < dst.size(); ++i)
         if (dst[i]->device() != src[i]->device()) throw Error(DRPRG_EINVAL, "the two contexts list different devices");
     ctx->host_coverage_valid = false;
-    for (size_t i = 0; i < dst.size(); ++i) dst[i]->map_kept_from(*src[i]);
+    for (size_t i = 0; i < dst.size(); ++i) ctx->accepted_reads += dst[i]->map_kept_from(*src[i]); // (what `from` accepted under ITS cap: exactly those reads)
     ctx->total_bases += from->total_bases;
     ctx->mapped_paths.insert(ctx->mapped_paths.end(), from->mapped_paths.begin(), from->mapped_paths.end());
     reduce_devices(ctx);
@@ -900,7 +1045,11 @@ int drprg_hip_discover_reads(drprg_hip_ctx* ctx, const char* reads_path, const c
         resident = [ctx](const std::vector<uint64_t>& anchors, uint32_t A, std::vector<uint8_t>& bases, std::vector<uint64_t>& offsets) {
             for (Mapper* m : mappers_of(ctx)) m->select_reads_with_anchors(anchors, A, bases, offsets);
         };
-    std::vector<NovelVariant> variants = assemble_candidate_regions(r, reads_path, ctx->threads, adp, ctx->params.illumina, resident);
+    // a depth cap that was reached: the file pass stops after the reads that were mapped (the resident ones are those already)
+    // (only when every base of the running total came with its reads through this context: a total taken over with a coverage vector
+    // says nothing about how many reads of the file stand behind it)
+    const uint64_t max_reads = ctx->cap_reached && !ctx->bases_without_reads ? ctx->accepted_reads : ~0ull;
+    std::vector<NovelVariant> variants = assemble_candidate_regions(r, reads_path, ctx->threads, adp, ctx->params.illumina, resident, max_reads);
     write_denovo_paths(dir, smp, r, variants, list_loci != 0);
     if (out) {
         out[0] = (uint32_t)r.candidates.size();
@@ -1009,6 +1158,7 @@ int drprg_hip_load_coverage(drprg_hip_ctx* ctx, const char* path, const char* ta
     ctx->prg_reads.swap(prg_reads);
     ctx->host_coverage_valid = true;
     ctx->total_bases = hdr[3];
+    ctx->bases_without_reads = true;
     if (ctx->mapper) ctx->mapper->upload(ctx->covg, ctx->prg_reads);
     if (counters) std::memcpy(counters, cnt, sizeof cnt);
     API_END(ctx)
@@ -1328,6 +1478,29 @@ extern "C" int drprg_hip_gunzip_file(const char* gz_path, int threads, uint64_t 
         out[0] = total;
         out[1] = pg.chunks_accepted();
         out[2] = pg.chunks_redone();
+    });
+}
+
+extern "C" int drprg_hip_parse_fastx_ordered(const char* reads_path, int threads, uint64_t max_reads, uint64_t out[6], char* err, size_t err_len)
+{
+    if (!reads_path || !out) return DRPRG_EINVAL;
+    return report_guard(err, err_len, [&]() {
+        uint64_t sum = 0, n_reads = 0, n_bases = 0, batches = 0;
+        IngestHooks hooks;
+        hooks.submit_in_order = [&](const PinnedBatch& b) -> bool {
+            const uint64_t n = std::min<uint64_t>(b.n_reads, max_reads - n_reads);
+            for (uint64_t i = 0; i < n; ++i) {
+                uint64_t h = 1469598103934665603ull;
+                for (uint64_t j = b.offsets[i]; j < b.offsets[i + 1]; ++j) h = (h ^ b.bases[j]) * 1099511628211ull;
+                sum += (n_reads + i + 1) * h;
+            }
+            n_reads += n;
+            n_bases += b.offsets[n];
+            ++batches;
+            return n_reads < max_reads;
+        };
+        const IngestStats st = ingest_fastx(reads_path, threads, hooks);
+        out[0] = n_reads; out[1] = n_bases; out[2] = sum; out[3] = batches; out[4] = (uint64_t)st.gz_mode; out[5] = st.discarded_reads;
     });
 }
 

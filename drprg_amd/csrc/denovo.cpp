@@ -303,7 +303,7 @@ std::vector<AssembledAllele> assemble_region(const std::string& slice, uint32_t 
 } // namespace
 
 std::vector<NovelVariant> assemble_candidate_regions(const GenotypeResult& gr, const std::string& reads_path, int threads, const DiscoverParams& dp,
-    bool accurate_reads, const ResidentReads& resident)
+    bool accurate_reads, const ResidentReads& resident, uint64_t max_reads)
 {
     std::vector<NovelVariant> out;
     const uint32_t A = dp.anchor_len;
@@ -466,6 +466,16 @@ std::vector<NovelVariant> assemble_candidate_regions(const GenotypeResult& gr, c
         IngestHooks hooks;
         hooks.concurrent_submit = true;
         hooks.submit = scan_batch;
+        // max_reads (the mapping pass stopped at a depth cap): only the first max_reads reads of the file are looked at -- the blocks
+        // come in file order then, and the ingest stops reading once they are through
+        uint64_t seen = 0;
+        auto scan_prefix = [&](PinnedBatch b) {
+            b.n_reads = std::min<uint64_t>(b.n_reads, max_reads - seen);
+            seen += b.n_reads;
+            if (b.n_reads) scan_batch(b);
+            return seen < max_reads;
+        };
+        if (max_reads != ~0ull) hooks.submit_in_order = scan_prefix;
         try {
             ingest_fastx(reads_path, threads, hooks);
         } catch (const Error& e) {
@@ -479,7 +489,7 @@ std::vector<NovelVariant> assemble_candidate_regions(const GenotypeResult& gr, c
                 if (!rb.n_reads()) continue;
                 rb.bases.resize(rb.bases.size() + 64); // (what an ingest block has after its last base)
                 PinnedBatch b { rb.bases.data(), rb.offsets.data(), rb.n_reads(), rb.offsets.back() };
-                scan_batch(b);
+                if (!scan_prefix(b)) break;
             }
         }
     }

@@ -20,7 +20,7 @@ struct NovelVariant {
 // read that holds one of them (more reads do no harm) to bases / offsets -- Mapper::select_reads_with_anchors.
 using ResidentReads = std::function<void(const std::vector<uint64_t>& anchors, uint32_t anchor_len, std::vector<uint8_t>& bases, std::vector<uint64_t>& offsets)>;
 std::vector<NovelVariant> assemble_candidate_regions(const GenotypeResult& gr, const std::string& reads_path, int threads, const DiscoverParams& dp,
-    bool accurate_reads, const ResidentReads& resident = ResidentReads());
+    bool accurate_reads, const ResidentReads& resident = ResidentReads(), uint64_t max_reads = ~0ull);
 
 // <dir>/denovo_paths.txt (+ denovo_sequences.fa, denovo_variants.tsv).  list_loci = false keeps the "0 loci" line: the
 // variants are then reported in denovo_variants.tsv only and the caller's make_prg step is not triggered.

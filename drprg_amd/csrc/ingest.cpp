@@ -76,6 +76,7 @@ struct Block {
     // early and at a different fill for every worker -- otherwise all workers fill their first block at the same moment, the
     // copy engine idles until then and works through a burst afterwards (measured: 10 M x 150 bp, first copies at 67 of 95 ms)
     size_t flush_at = 0;
+    uint64_t seq = 0; // ordered hand-over: the slice its reads come from
 };
 
 struct Shared {
@@ -89,20 +90,88 @@ struct Shared {
     std::atomic<int64_t> ns_first_submit { -1 }, ns_submit_wait { 0 }, ns_submit_run { 0 }, ns_parse { 0 }, ns_alloc { 0 }, ns_read { 0 };
     int64_t now_ns() const { return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_start).count(); }
     std::atomic<bool> failed { false };
+    // ordered hand-over (IngestHooks::submit_in_order): the slice whose blocks are handed over now; stop: the hook wants no more
+    const bool ordered;
+    std::mutex turn_mu;
+    std::condition_variable turn_cv;
+    uint64_t turn = 0;
+    std::atomic<bool> stop { false };
+    std::atomic<uint64_t> discarded { 0 };
+    struct StopParse {}; // thrown out of parse_slice once the hook has said stop
     std::string error;
     int error_code = DRPRG_EFORMAT;
 
-    explicit Shared(const IngestHooks& h) : hooks(h) {}
+    explicit Shared(const IngestHooks& h) : hooks(h), ordered((bool)h.submit_in_order) {}
     void fail(int code, const std::string& m)
     {
-        std::lock_guard<std::mutex> g(err_mu);
-        if (!failed.exchange(true)) {
-            error = m;
-            error_code = code;
+        {
+            std::lock_guard<std::mutex> g(err_mu);
+            if (!failed.exchange(true)) {
+                error = m;
+                error_code = code;
+            }
         }
+        std::lock_guard<std::mutex> g(turn_mu); // (threads that wait for their turn look at `failed`)
+        turn_cv.notify_all();
+    }
+    void clear(Block& b)
+    {
+        b.n_reads = 0;
+        b.n_bases = 0;
+        b.npos.clear();
+        if (b.packed) reinterpret_cast<uint64_t*>(b.bases)[0] = 0; // (pack_append: a fresh stream)
+        b.flush_at = BLOCK_BASES;
+    }
+    // Ordered hand-over: the block's reads are the next ones of slice b.seq.  Waits until every slice before that one is through, hands
+    // the block over, and -- end_of_slice -- lets the next slice in.  Slices are taken from the queue in file order, so the slice whose
+    // turn it is is always in the hands of a thread that is parsing it or standing here.
+    void submit_ordered(Block& b, bool end_of_slice)
+    {
+        if (b.n_reads == 0 && !end_of_slice) return;
+        std::unique_lock<std::mutex> l(turn_mu);
+        turn_cv.wait(l, [&] { return turn == b.seq || stop || failed; });
+        if (failed) {
+            // (the caller asked for room in a FULL block and appends as soon as this returns: the block is emptied and the rest of the
+            // slice is not parsed -- nothing of it will be handed over)
+            clear(b);
+            if (!end_of_slice) throw StopParse {};
+            return;
+        }
+        if (stop) {
+            discarded += b.n_reads;
+            clear(b);
+            if (!end_of_slice) throw StopParse {};
+            return;
+        }
+        if (b.n_reads) {
+            PinnedBatch pb { b.bases, b.offsets, b.n_reads, b.n_bases };
+            pb.packed = b.packed;
+            pb.npos = b.npos.data();
+            pb.n_npos = b.npos.size();
+            struct Wake { // (a hook that throws: the thread reports the failure, the others must not wait for this turn)
+                std::condition_variable& cv;
+                ~Wake() { cv.notify_all(); }
+            } wake { turn_cv };
+            const bool go_on = hooks.submit_in_order(pb);
+            reads += b.n_reads;
+            bases += b.n_bases;
+            batches += 1;
+            clear(b);
+            if (!go_on) {
+                stop = true;
+                if (!end_of_slice) throw StopParse {};
+                return;
+            }
+        }
+        if (end_of_slice) ++turn;
+        turn_cv.notify_all();
     }
     void submit(Block& b)
     {
+        if (ordered) {
+            submit_ordered(b, false);
+            return;
+        }
         if (b.n_reads == 0) return;
         PinnedBatch pb { b.bases, b.offsets, b.n_reads, b.n_bases };
         pb.packed = b.packed;
@@ -126,11 +195,7 @@ struct Shared {
         reads += b.n_reads;
         bases += b.n_bases;
         batches += 1;
-        b.n_reads = 0;
-        b.n_bases = 0;
-        b.npos.clear();
-        if (b.packed) reinterpret_cast<uint64_t*>(b.bases)[0] = 0; // (pack_append: a fresh stream)
-        b.flush_at = BLOCK_BASES;
+        clear(b);
     }
     Block new_block()
     {
@@ -311,6 +376,7 @@ struct Slice {
     std::shared_ptr<TextBuffer> owner; // inflated gzip text; null for a memory-mapped file
     std::shared_ptr<void> mapping;     // plain file: the slice's own mapping, unmapped by the parser thread when it is done with it
     uint64_t file_off = 0, file_len = 0; // plain file, begin == nullptr: the parser thread reads these bytes into a buffer of its own
+    uint64_t seq = 0;                    // its place in the file (given by the queue)
 };
 
 class SliceQueue {
@@ -321,6 +387,7 @@ public:
         std::unique_lock<std::mutex> l(mu_);
         not_full_.wait(l, [&] { return q_.size() < cap_ || closed_; });
         if (closed_) return;
+        s.seq = pushed_++;
         q_.push_back(std::move(s));
         not_empty_.notify_one();
     }
@@ -347,6 +414,7 @@ private:
     std::condition_variable not_empty_, not_full_;
     std::deque<Slice> q_;
     size_t cap_;
+    uint64_t pushed_ = 0;
     bool closed_ = false;
 };
 
@@ -523,28 +591,33 @@ IngestStats ingest_fastx(const std::string& path, int threads, const IngestHooks
         try {
             Slice s;
             while (queue.pop(s)) {
-                if (sh.failed) continue; // drain
+                if (sh.failed || sh.stop) continue; // drain
                 if (!blk.bases) {
                     const int64_t t0 = sh.debug ? sh.now_ns() : 0;
                     blk = sh.new_block();
                     if (sh.debug) sh.ns_alloc += sh.now_ns() - t0;
                 }
                 const int64_t t0 = sh.debug ? sh.now_ns() : 0;
-                if (!s.begin && s.file_len) { // plain file: this thread reads the slice into its own (recycled, huge-page) buffer
-                    if (!own_text || own_text->size() < s.file_len + 64) own_text = plain_pool().acquire(std::max<size_t>(s.file_len + 64, plain_slice_bytes() + (plain_slice_bytes() >> 1)));
-                    size_t have = 0;
-                    while (have < s.file_len) {
-                        const ssize_t r = pread(fd, own_text->data() + have, s.file_len - have, (off_t)(s.file_off + have));
-                        if (r <= 0) throw Error(DRPRG_EIO, "cannot read " + path);
-                        have += (size_t)r;
-                    }
-                    if (sh.debug) sh.ns_read += sh.now_ns() - t0;
-                    parse_slice(own_text->data(), own_text->data() + s.file_len, fastq, blk, sh);
-                } else parse_slice(s.begin, s.end, fastq, blk, sh);
+                blk.seq = s.seq;
+                try {
+                    if (!s.begin && s.file_len) { // plain file: this thread reads the slice into its own (recycled, huge-page) buffer
+                        if (!own_text || own_text->size() < s.file_len + 64) own_text = plain_pool().acquire(std::max<size_t>(s.file_len + 64, plain_slice_bytes() + (plain_slice_bytes() >> 1)));
+                        size_t have = 0;
+                        while (have < s.file_len) {
+                            const ssize_t r = pread(fd, own_text->data() + have, s.file_len - have, (off_t)(s.file_off + have));
+                            if (r <= 0) throw Error(DRPRG_EIO, "cannot read " + path);
+                            have += (size_t)r;
+                        }
+                        if (sh.debug) sh.ns_read += sh.now_ns() - t0;
+                        parse_slice(own_text->data(), own_text->data() + s.file_len, fastq, blk, sh);
+                    } else parse_slice(s.begin, s.end, fastq, blk, sh);
+                    if (sh.ordered) sh.submit_ordered(blk, true); // (a block never spans two slices: the next slice may be far away in the file)
+                } catch (const Shared::StopParse&) { // the hook has what it wanted: the rest of the slice is not parsed
+                }
                 s = Slice(); // (a mapped slice: its mapping goes now, on this thread)
                 if (sh.debug) sh.ns_parse += sh.now_ns() - t0;
             }
-            if (!sh.failed) sh.submit(blk);
+            if (!sh.failed && !sh.ordered) sh.submit(blk);
         } catch (const Error& e) {
             sh.fail(e.code, e.what());
             queue.close();
@@ -608,7 +681,7 @@ IngestStats ingest_fastx(const std::string& path, int threads, const IngestHooks
                 return e && std::atoi(e) != 0;
             }();
             std::vector<char> win;
-            while (!use_mmap && cur < map_len && !sh.failed) {
+            while (!use_mmap && cur < map_len && !sh.failed && !sh.stop) {
                 size_t cut = map_len;
                 const size_t slice = plain_slice_bytes();
                 if (map_len - cur > slice + (slice >> 2)) {
@@ -639,7 +712,7 @@ IngestStats ingest_fastx(const std::string& path, int threads, const IngestHooks
                 cur = cut;
                 queue.push(std::move(sl));
             }
-            while (cur < map_len && !sh.failed) {
+            while (cur < map_len && !sh.failed && !sh.stop) {
                 size_t want = SLICE_BYTES + (SLICE_BYTES >> 2);
                 for (;;) {
                     const size_t lo = cur / page * page;
@@ -803,7 +876,7 @@ IngestStats ingest_fastx(const std::string& path, int threads, const IngestHooks
                                              "handing windows to the parser threads %.1f ms\n", sh.now_ns() / 1e6, text / 1e6, acquire / 1e6, push / 1e6);
                 }
             } loop_times { sh, ns_text, ns_acquire, ns_push };
-            while (!eof && !sh.failed) {
+            while (!eof && !sh.failed && !sh.stop) {
                 // (one size for every window -- the carry is at most the 1 MB the cut is looked for in --, so a recycled buffer always fits)
                 t_mark = sh.debug ? sh.now_ns() : 0;
                 auto buf = gz_pool.acquire(std::max(carry.size(), size_t(1) << 20) + SLICE_BYTES);
@@ -853,6 +926,7 @@ IngestStats ingest_fastx(const std::string& path, int threads, const IngestHooks
     st.reads = sh.reads;
     st.bases = sh.bases;
     st.batches = sh.batches;
+    st.discarded_reads = sh.discarded;
     st.parallel = threads > 1;
     if (sh.debug)
         std::fprintf(stderr, "[ingest] wall %.1f ms, %llu batches, first hand-over at %.1f ms; summed over the %zu parser threads: parse (hand-overs included) %.1f ms, "

@@ -26,10 +26,16 @@ struct IngestHooks {
     bool concurrent_submit = false;                 // ... unless set: then by any parser thread, and submit does its own locking
     bool packed = false;                            // the parser threads pack the bases to 2 bits as they copy them (pack.h): a block is a
                                                     // quarter of the bytes to page-lock and to move over PCIe
+    // When set, it replaces submit: the blocks are handed over one at a time IN FILE ORDER (a block then never spans two slices of the
+    // text, and a parser thread waits with a full block until the slices before its own are through).  false: stop -- nothing more is
+    // handed over, the parser threads take no new slices and the rest of the file is not read.  For callers whose result depends on
+    // which reads come first (the depth cap, drprg_hip_set_max_covg); everything else keeps the unordered hand-over.
+    std::function<bool(const PinnedBatch&)> submit_in_order;
 };
 
 struct IngestStats {
     uint64_t reads = 0, bases = 0, batches = 0;
+    uint64_t discarded_reads = 0; // submit_in_order said stop: reads the parser threads had in blocks that were never handed over
     bool parallel = false;
     int gz_mode = 0; // 0 plain text, 1 BGZF (members inflated in parallel), 2 one gzip member in one libdeflate call, 3 zlib streaming,
                      // 4 one plain gzip stream inflated by all threads (pgunzip.h)

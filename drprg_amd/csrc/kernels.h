@@ -317,6 +317,12 @@ hipError_t launch_mark_npos(const uint64_t* npos, uint64_t n_npos, uint64_t n_ba
 hipError_t launch_pack(const uint8_t* bases, uint64_t n_bases, uint32_t* words, uint64_t* npos, uint64_t npos_cap, unsigned long long* n_npos,
     hipStream_t stream);
 
+// covg_cut.hip: the read at which a device batch crosses the depth cap.  out (page-locked host memory, device address): out[0] = the smallest
+// i in [1, n_reads] with offsets[i] >= target (n_reads if none), out[1] = offsets[i], out[2] = how many of the n_npos ascending positions
+// in npos lie below offsets[i].  One wave; n_reads >= 1.
+hipError_t launch_covg_cut(const uint64_t* offsets, uint64_t n_reads, uint64_t target, const uint64_t* npos, uint64_t n_npos, unsigned long long* out,
+    hipStream_t stream);
+
 // anchor_scan.hip: reads of a resident batch that hold one of the (sorted) anchor k-mers of length A -- every such read once,
 // in any order, appended to `list` (count keeps counting past list_cap).  prefilter: 2^16 bits, bit (kmer & 0xFFFF) set for every
 // anchor; flags: n_reads words, zero before the launch.

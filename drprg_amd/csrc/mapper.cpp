@@ -195,6 +195,7 @@ Mapper::~Mapper()
     if (kept_copied_) (void)hipEventDestroy(kept_copied_);
     if (copy_stream_) (void)hipStreamDestroy(copy_stream_);
     if (h_counters_) (void)hipHostFree(h_counters_);
+    if (h_cut_) (void)hipHostFree(h_cut_);
     if (h_bases_) (void)hipHostFree(h_bases_);
     if (h_offsets_) (void)hipHostFree(h_offsets_);
     if (ev0_) (void)hipEventDestroy(ev0_);
@@ -977,6 +978,31 @@ void Mapper::map_device_impl(const uint8_t* d_bases, const uint64_t* d_offsets, 
         stream ? stream : stream_, pk);
     tot_reads_ += n_reads;
     tot_bases_ += n_bases;
+}
+
+void Mapper::check_device_batch(const void* d_bases, const void* d_offsets, uint64_t n_reads, const void* d_npos, uint64_t n_npos, bool packed)
+{
+    if (n_npos && !d_npos) throw Error(DRPRG_EINVAL, "n_npos > 0 without the positions");
+    if (n_reads == 0) return;
+    if (!d_bases || !d_offsets) throw Error(DRPRG_EINVAL, "null device pointer");
+    if ((reinterpret_cast<uintptr_t>(d_bases) & 15u) != 0) throw Error(DRPRG_EINVAL, packed ? "d_words must be 16-byte aligned" : "d_bases must be 16-byte aligned");
+    if (n_reads > dev::MAX_BATCH_READS) throw Error(DRPRG_EOVERFLOW, "at most " + std::to_string(dev::MAX_BATCH_READS) + " reads per batch");
+}
+
+Mapper::CutPoint Mapper::find_cut(const uint64_t* d_offsets, uint64_t n_reads, uint64_t target, const uint64_t* d_npos, uint64_t n_npos, hipStream_t stream)
+{
+    if (!d_offsets || n_reads == 0) throw Error(DRPRG_EINVAL, "null device pointer");
+    if (n_npos && !d_npos) throw Error(DRPRG_EINVAL, "n_npos > 0 without the positions");
+    sync(); // (a batch in flight comes before this one in the running total: it is complete before this one is cut)
+    HIPCHK(hipSetDevice(device_));
+    if (!stream) stream = stream_;
+    if (!h_cut_) {
+        HIPCHK(hipHostMalloc((void**)&h_cut_, 4 * sizeof(unsigned long long), hipHostMallocDefault));
+        HIPCHK(hipHostGetDevicePointer((void**)&h_cut_dev_, h_cut_, 0));
+    }
+    HIPCHK(dev::launch_covg_cut(d_offsets, n_reads, target, d_npos, n_npos, h_cut_dev_, stream));
+    wait_stream(stream);
+    return CutPoint { h_cut_[0], h_cut_[1], h_cut_[2] };
 }
 
 void Mapper::map_host(const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads)

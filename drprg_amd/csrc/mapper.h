@@ -52,6 +52,17 @@ public:
     void map_device_packed(const uint32_t* d_words, const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases, const uint64_t* d_npos, uint64_t n_npos,
         uint32_t* d_covg, uint32_t* d_prg_reads, hipStream_t stream, bool deferred);
 
+    // Depth cap (drprg_hip_set_max_covg; the running total is kept by the context, capi.cpp): where a device batch reaches `target` bases.
+    // n_reads = the smallest i in [1, n_reads] with d_offsets[i] >= target (n_reads if there is none), n_bases = d_offsets[i], n_npos = how
+    // many of the batch's listed positions lie below that.  Completes the batch map_device_async left in flight, runs covg_cut_kernel on
+    // `stream` and waits for it: called for the one batch that crosses the cap, never for a batch that cannot reach it.
+    // what map_device* refuses a batch for, checked without touching anything (throws the same errors)
+    static void check_device_batch(const void* d_bases, const void* d_offsets, uint64_t n_reads, const void* d_npos, uint64_t n_npos, bool packed);
+    struct CutPoint {
+        uint64_t n_reads, n_bases, n_npos;
+    };
+    CutPoint find_cut(const uint64_t* d_offsets, uint64_t n_reads, uint64_t target, const uint64_t* d_npos, uint64_t n_npos, hipStream_t stream);
+
     // Map a host batch (copies through pinned staging buffers, then map_device on the own accumulators).
     void map_host(const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads);
     // The same without waiting for the kernels: the copy to the device runs on a copy stream into one of two staging sets, the
@@ -205,6 +216,7 @@ private:
     const uint8_t* ascii_view(int slot, const uint8_t* d_bases, uint64_t n_bases, hipStream_t stream, const PackedInfo* pk);
     uint8_t* d_unpacked_[3] = { nullptr, nullptr, nullptr };
     unsigned long long* d_pack_count_ = nullptr; // pack_on_device's counter word
+    unsigned long long *h_cut_ = nullptr, *h_cut_dev_ = nullptr; // find_cut's three result words: pinned, and their device address
     uint64_t unpacked_cap_[3] = { 0, 0, 0 };
     void map_device_impl(const uint8_t* d_bases, const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases, uint32_t* d_covg, uint32_t* d_prg_reads,
         hipStream_t stream, const PackedInfo* pk);

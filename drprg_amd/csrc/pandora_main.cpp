@@ -60,6 +60,8 @@ void usage()
         "  pandora map      [--genotype] [--local] [--gt-conf X] [-v] [-o DIR] [-g SIZE] [--max-covg N]\n"
         "                   [--vcf-refs FASTA] [-t N] [-w W] [-k K] [-c N] [-I] [-K] [-e RATE] [--max-diff N] <prg> <reads>\n"
         "  pandora discover [same mapping options] <prg> <query.tsv>\n"
+        "  --max-covg N: reads are taken in file order up to and including the first one at which (N + 1) x SIZE bases are reached;\n"
+        "                the rest is not mapped (default 300; 4294967295 = no cap)\n"
         "environment: DRPRG_HIP_DEVICE selects the GPU (default 0); DRPRG_HIP_DEVICES=0,1,.. maps on several GPUs of the node\n");
 }
 
@@ -143,6 +145,7 @@ drprg_hip_ctx* open_ctx(const Args& a)
     o.min_cluster_size = a.min_cluster_size;
     o.genome_size = a.genome_size;
     if (int rc = drprg_hip_set_opts(ctx, &o)) die(drprg_hip_last_error(ctx), -rc);
+    if (int rc = drprg_hip_set_max_covg(ctx, a.max_covg)) die(drprg_hip_last_error(ctx), -rc);
     drprg_hip_set_threads(ctx, a.threads);
     drprg_hip_set_input_format(ctx, packed_input()); // the parser threads pack the reads to 2 bits (DRPRG_HIP_INPUT=ascii: one byte per base)
     return ctx;
@@ -182,7 +185,16 @@ std::string run_tag(const Args& a, const std::string& reads)
     };
     return stamp(a.positional[0]) + "|" + stamp(reads) + "|w" + std::to_string(a.w) + "|k" + std::to_string(a.k) + "|c"
         + std::to_string(a.min_cluster_size) + "|I" + std::to_string((int)a.illumina) + "|e" + std::to_string(a.error_rate) + "|m"
-        + std::to_string(a.max_diff) + "|g" + std::to_string((unsigned long long)a.genome_size);
+        + std::to_string(a.max_diff) + "|g" + std::to_string((unsigned long long)a.genome_size) + "|M" + std::to_string((unsigned long long)a.max_covg);
+}
+
+// -v: says where the depth cap stopped the pass, if it did
+void report_cap(drprg_hip_ctx* ctx, const Args& a)
+{
+    uint64_t ci[4] = { 0, 0, 0, 0 };
+    if (!a.verbose || drprg_hip_max_covg_info(ctx, ci) != 0 || !ci[0]) return;
+    std::printf("[pandora-hip] stopped reading at %llu reads: max coverage reached (--max-covg %llu x -g %llu: %llu bases mapped)\n", (unsigned long long)ci[1],
+        (unsigned long long)a.max_covg, (unsigned long long)a.genome_size, (unsigned long long)ci[2]);
 }
 
 const char* COVERAGE_CACHE = ".drprg_hip_coverage";
@@ -203,6 +215,7 @@ int cmd_map(const Args& a)
     } else {
         if (int rc = drprg_hip_map_fastx(ctx, a.positional[1].c_str())) die(drprg_hip_last_error(ctx), -rc);
         report_counters(ctx, now_s() - t0);
+        report_cap(ctx, a);
     }
     const std::string vcf = a.outdir + "/pandora_genotyped.vcf";
     if (int rc = drprg_hip_genotype(ctx, a.vcf_refs.empty() ? nullptr : a.vcf_refs.c_str(), vcf.c_str(), "sample"))
@@ -236,6 +249,7 @@ int cmd_discover(const Args& a)
     double t0 = now_s();
     if (int rc = drprg_hip_map_fastx(ctx, reads.c_str())) die(drprg_hip_last_error(ctx), -rc);
     report_counters(ctx, now_s() - t0);
+    report_cap(ctx, a);
     // The mapping half of discover is the same kernels as `map`; its products are (1) the candidate regions -- stretches of each
     // locus' called consensus that the reads do not support --, (2) the novel variants a host-side pile-up of
     // the reads finds in them, and (3) the coverage vector, kept for the `map` call drprg issues next on the unchanged PRG.

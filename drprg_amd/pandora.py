@@ -152,6 +152,17 @@ class Context:
     def reset(self):
         _check(lib.drprg_hip_reset(self._h), self._h)
 
+    # ---- depth cap (include/drprg_hip.h: drprg_hip_set_max_covg) -------------------------------
+    def set_max_covg(self, max_covg):
+        """`pandora --max-covg`: reads are accepted in order until (max_covg + 1) * genome_size bases have been mapped since the last
+        reset; None, or anything from 2**32 - 1 up, switches the cap off (the default)"""
+        _check(lib.drprg_hip_set_max_covg(self._h, 2 ** 64 - 1 if max_covg is None else int(max_covg)), self._h)
+
+    def max_covg_info(self):
+        out = (C.c_uint64 * 4)()
+        _check(lib.drprg_hip_max_covg_info(self._h, out), self._h)
+        return dict(reached=bool(out[0]), reads=int(out[1]), bases=int(out[2]), dropped=int(out[3]))
+
     # ---- reads that stay in HBM (include/drprg_hip.h: drprg_hip_keep_reads) --------------------
     def keep_reads(self, max_bytes):
         """map_fastx leaves the blocks it copies on the device (up to max_bytes per device; 0 switches it off)"""
@@ -340,8 +351,9 @@ class Pandora:
 
     @staticmethod
     def _parse_args(args):
-        """The argv drprg passes: -t T -w W -k K -c C [-I] [-K] (/root/reference/src/predict.rs:236-245)."""
-        o = dict(threads=1, w=14, k=15, c=10, illumina=False)
+        """The argv drprg passes: -t T -w W -k K -c C [-I] [-K] (/root/reference/src/predict.rs:236-245), and --max-covg M (pandora's own
+        default, 300, when it is not given; 4294967295 = no cap, what the reference passes in front of these)."""
+        o = dict(threads=1, w=14, k=15, c=10, illumina=False, max_covg=300)
         it = iter([str(a) for a in args])
         for a in it:
             if a == "-t":
@@ -354,11 +366,21 @@ class Pandora:
                 o["c"] = int(next(it))
             elif a == "-I":
                 o["illumina"] = True
+            elif a == "--max-covg":
+                o["max_covg"] = int(next(it))
             elif a == "-K":
                 pass
             else:
                 raise DependencyError("ProcessError", f"unknown pandora option {a}", code=2)
         return o
+
+    @staticmethod
+    def _struct_args(args):
+        """what struct Pandora puts in front of the caller's arguments before it spawns `pandora discover` / `pandora map`
+        (/root/reference/src/lib.rs:533-534, :605-606): no depth cap.  A --max-covg among `args` comes later and wins, as on pandora's
+        command line; without one discover_with / genotype_with map every read, like the struct they stand in for -- _parse_args' own
+        default (300) is that of the bare `pandora` command, which these two never run bare."""
+        return ["--max-covg", "4294967295"] + [str(a) for a in args]
 
     def index_with(self, prg_path, args=()):
         """Pandora::index_with, /root/reference/src/lib.rs:479-510."""
@@ -369,6 +391,7 @@ class Pandora:
         o = self._parse_args(args)
         ctx = Context(prg, o["w"], o["k"], device=self.device)
         ctx.set_opts(illumina=o["illumina"], min_cluster_size=o["c"], genome_size=MTB_GENOME_SIZE)
+        ctx.set_max_covg(o["max_covg"])
         ctx.map_fastx(reads)
         return ctx
 
@@ -378,7 +401,14 @@ class Pandora:
         def stamp(p):
             st = os.stat(p)
             return f"{os.path.realpath(p)}:{st.st_size}:{st.st_mtime_ns}"
-        return "|".join([stamp(prg), stamp(reads)] + [str(a) for a in args if str(a) != "-K"])
+        # (the depth cap by its value, given or not: a vector mapped under one cap is not another cap's)
+        rest, it = [], iter(str(a) for a in args)
+        for a in it:
+            if a == "--max-covg":
+                next(it, None)
+            elif a != "-K":
+                rest.append(a)
+        return "|".join([stamp(prg), stamp(reads)] + rest + [f"M{Pandora._parse_args(args)['max_covg']}"])
 
     COVERAGE_CACHE = ".drprg_hip_coverage"
 
@@ -392,6 +422,7 @@ class Pandora:
         "0 loci with denovo variants"."""
         import warnings
         os.makedirs(outdir, exist_ok=True)
+        args = self._struct_args(args)
         with open(query_idx) as fh:
             sample, reads = fh.readline().split()[:2]
         with self._mapped_context(prg, reads, args) as ctx:
@@ -410,11 +441,13 @@ class Pandora:
         """Pandora::genotype_with, /root/reference/src/lib.rs:580-642.  If discover_with left this run's coverage vector
         under <outdir>/discover (where drprg puts it, /root/reference/src/predict.rs:248), the reads are not mapped again."""
         os.makedirs(outdir, exist_ok=True)
+        args = self._struct_args(args)
         o = self._parse_args(args)
         cache = os.path.join(outdir, "discover", self.COVERAGE_CACHE)
         ctx = Context(prg, o["w"], o["k"], device=self.device)
         with ctx:
             ctx.set_opts(illumina=o["illumina"], min_cluster_size=o["c"], genome_size=MTB_GENOME_SIZE)
+            ctx.set_max_covg(o["max_covg"])
             self.reused_discover_coverage = os.path.exists(cache) and ctx.load_coverage(cache, self._run_tag(prg, reads, args))
             if not self.reused_discover_coverage:
                 ctx.map_fastx(reads)

@@ -110,11 +110,42 @@ int drprg_hip_map_fastx(drprg_hip_ctx* ctx, const char* reads_path); /* fasta/fa
 /* Parser threads used by drprg_hip_map_fastx (the -t that drprg forwards to pandora, /root/reference/src/predict.rs:236-245);
  * default 4.  The file is cut at record boundaries and parsed in parallel into pinned blocks. */
 int drprg_hip_set_threads(drprg_hip_ctx* ctx, int threads);
+
+/* Depth cap: `pandora map --max-covg`.  pandora takes the reads in file order, adds each read's length to a running total and stops
+ * after the first read for which total / genome_size > max_covg (integer division) [UPSTREAM-MEMORY: pandora's source is not under
+ * /root/reference and drprg always passes 4294967295, so nothing there pins this rule].  Restated: with T = (max_covg + 1) * genome_size
+ * and B(i) the bases of the first i reads mapped on this context since the last drprg_hip_reset -- over all calls and all entry points,
+ * host, device, packed and map_fastx --, the accepted reads are the first n, n the smallest i with B(i) >= T (all reads if there is no
+ * such i).  What follows read n is neither mapped nor counted: not in the counters' reads and bases, not in the total the genotyper's
+ * expected depth is taken from.  Zero-length reads follow the same rule (they can never be the cut themselves).  Once the cap has been
+ * reached every further map call returns 0 and maps nothing, until drprg_hip_reset: that clears the running total and keeps the cap.
+ *   drprg_hip_set_max_covg: the default is off, and so is any max_covg >= 4294967295 (what drprg passes).  genome_size is the one of
+ *     the map options in force.  Set after reads were mapped, it applies from the current running total.
+ *   A device batch that cannot reach the cap (running total + n_bases < T) costs nothing extra: no launch, no synchronisation.  The one
+ *     batch that crosses it is cut on the device (covg_cut.hip): the call completes a batch still in flight from the async form, waits
+ *     for that one small kernel and maps the prefix.  drprg_hip_map_fastx hands its blocks over in file order while a cap is set; at the
+ *     cut it copies nothing further to a device and its parser and inflate threads take no new piece of the file -- a plain file, a BGZF
+ *     file and a gzip stream are not read to their end (up to one 8 MB / 32 MB piece per parser thread is already under way and is
+ *     dropped); only a small single-member .gz, which is inflated by one library call before the first read is parsed, is still inflated
+ *     whole.  Only the accepted reads stay resident (drprg_hip_keep_reads); drprg_hip_discover_reads then sees exactly the reads that
+ *     were mapped, from HBM or from the file.  A call that is refused (bad pointers, ...) changes nothing of the cap's state.  A context over several devices counts where the blocks are handed
+ *     to the devices: the summed vector does not depend on which device mapped what.
+ *   drprg_hip_max_covg_info: out[0] = 1 if the cap was reached, out[1] = reads accepted, out[2] = bases accepted, out[3] = reads that
+ *     were offered and dropped (map_fastx: the reads parsed before the ingest stopped, not the rest of the file).  Synchronises.
+ *   The cap is per context.  Nothing coordinates it across the one-process-per-GPU layout: a caller who shards the reads of a sample
+ *     over ranks shards the cap, and each rank stops at its own T. */
+int drprg_hip_set_max_covg(drprg_hip_ctx* ctx, uint64_t max_covg);
+int drprg_hip_max_covg_info(drprg_hip_ctx* ctx, uint64_t out[4]);
 /* Host-only self-check of that ingest: parses the file with `threads` parser threads and returns
  * out[0..4] = reads, bases, order-independent digest (sum of the FNV-1a hashes of the reads), batches, and how gzip input
  * was inflated (0 plain text, 1 BGZF members in parallel, 2 one member in one libdeflate call, 3 zlib streaming, 4 one plain
  * gzip stream inflated by all threads: chunks entered at block boundaries found in the compressed data, csrc/pgunzip.h). */
 int drprg_hip_parse_fastx(const char* reads_path, int threads, uint64_t out[5], char* err, size_t err_len);
+/* The same for the hand-over in file order that the depth cap uses: the blocks are taken one at a time, in file order, until max_reads
+ * reads have been seen (the last block is cut there), then the ingest is told to stop.  out[0..5] = reads seen, their bases, an
+ * order-DEPENDENT digest (sum over the reads of (index + 1) x FNV-1a of the read, index counted from 0 in file order), blocks handed
+ * over, how gzip input was inflated (as above), reads the parser threads had in blocks that were never handed over. */
+int drprg_hip_parse_fastx_ordered(const char* reads_path, int threads, uint64_t max_reads, uint64_t out[6], char* err, size_t err_len);
 /* Host-only self-check of way 4 on any gzip file (not only FASTQ): inflates gz_path with `threads` threads and chunks of
  * chunk_bytes compressed bytes (0 = automatic) into out_path; out[0..2] = bytes written, chunks accepted as their threads
  * inflated them, chunks inflated again from the known position.  Member CRC-32s and lengths are checked as gzip does. */
