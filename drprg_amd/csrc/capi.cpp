@@ -411,20 +411,25 @@ static uint64_t cap_host_prefix(const drprg_hip_ctx* ctx, const uint64_t* offset
     return i;
 }
 
+// The host batch cut to those reads (a packed one: and to the positions listed for them).
+static void cap_host_cut(const drprg_hip_ctx* ctx, Mapper::HostBatch& hb, CapCut& c)
+{
+    hb.n_reads = cap_host_prefix(ctx, hb.offsets, hb.n_reads, c);
+    if (hb.packed) hb.n_npos = (uint64_t)(std::lower_bound(hb.npos, hb.npos + hb.n_npos, hb.n_bases()) - hb.npos); // (all of them unless the batch was cut)
+}
+
 // The same for a device batch, whose offsets only the device can read: a batch below the cap is accepted as it is, without a look
-// at the device; the one that crosses it is cut by covg_cut_kernel (Mapper::find_cut) -- after the checks the map call itself makes.
-static void cap_device_prefix(const drprg_hip_ctx* ctx, Mapper& m, const void* d_bases, const void* d_offsets, uint64_t& n_reads, uint64_t& n_bases,
-    const void* d_npos, uint64_t& n_npos, bool packed, void* hip_stream, CapCut& c)
+// at the device; the one that crosses it is cut by covg_cut_kernel (Mapper::find_cut, which first makes the checks the map call itself makes: Mapper::check).
+static void cap_device_prefix(const drprg_hip_ctx* ctx, Mapper& m, Mapper::DeviceBatch& b, void* hip_stream, CapCut& c)
 {
     uint64_t T;
-    if (n_reads == 0 || !cap_target(ctx, T) || n_bases < T - ctx->total_bases) return;
-    Mapper::check_device_batch(d_bases, d_offsets, n_reads, d_npos, n_npos, packed);
-    const Mapper::CutPoint cut = m.find_cut((const uint64_t*)d_offsets, n_reads, T - ctx->total_bases, (const uint64_t*)d_npos, n_npos, (hipStream_t)hip_stream);
+    if (b.n_reads == 0 || !cap_target(ctx, T) || b.n_bases < T - ctx->total_bases) return;
+    const Mapper::CutPoint cut = m.find_cut(b, T - ctx->total_bases, (hipStream_t)hip_stream);
     c.reached = true;
-    c.dropped = n_reads - cut.n_reads;
-    n_reads = cut.n_reads;
-    n_bases = cut.n_bases;
-    n_npos = cut.n_npos;
+    c.dropped = b.n_reads - cut.n_reads;
+    b.n_reads = cut.n_reads;
+    b.n_bases = cut.n_bases;
+    b.n_npos = cut.n_npos;
 }
 
 static std::vector<Mapper*> mappers_of(drprg_hip_ctx* ctx);
@@ -446,16 +451,7 @@ int drprg_hip_map_fastx(drprg_hip_ctx* ctx, const char* reads_path)
     // multi-threaded ingest into pinned blocks (ingest.cpp); multi-line FASTQ falls back to the serial reader
     IngestHooks hooks;
     hooks.packed = ctx->packed_input;
-    auto host_batch = [](const PinnedBatch& b) {
-        Mapper::HostBatch hb;
-        hb.bases = b.bases;
-        hb.offsets = b.offsets;
-        hb.n_reads = b.n_reads;
-        hb.packed = b.packed;
-        hb.npos = b.npos;
-        hb.n_npos = b.n_npos;
-        return hb;
-    };
+    auto host_batch = [](const PinnedBatch& b) { return Mapper::HostBatch { b.bases, b.offsets, b.n_reads, b.packed, b.npos, b.n_npos }; };
     uint64_t cap_T = 0;
     const bool capped = cap_target(ctx, cap_T);
     // page-locked ingest blocks are kept by the process between calls and contexts (PinPool)
@@ -495,10 +491,9 @@ int drprg_hip_map_fastx(drprg_hip_ctx* ctx, const char* reads_path)
             if (b.offsets[0] != 0) throw Error(DRPRG_EINVAL, "offsets[0] must be 0");
             Mapper::HostBatch hb = host_batch(b);
             CapCut c;
-            hb.n_reads = cap_host_prefix(ctx, b.offsets, b.n_reads, c);
-            if (hb.packed) hb.n_npos = (uint64_t)(std::lower_bound(b.npos, b.npos + b.n_npos, b.offsets[hb.n_reads]) - b.npos);
+            cap_host_cut(ctx, hb, c);
             mapper_of(rr++ % ndev).map_host_async(hb);
-            cap_commit(ctx, c, hb.n_reads, b.offsets[hb.n_reads]);
+            cap_commit(ctx, c, hb.n_reads, hb.n_bases());
             return !ctx->cap_reached;
         };
     // the coverage vectors of the other devices are summed into device 0 ON THE DEVICE (drprg_hip_reduce: one RCCL reduce over
@@ -523,10 +518,11 @@ int drprg_hip_map_fastx(drprg_hip_ctx* ctx, const char* reads_path)
         ReadBatch batch;
         while (rd.next_batch(batch, 8u << 20, 1ull << 30)) {
             if (!batch.n_reads()) continue;
+            Mapper::HostBatch hb { batch.bases.data(), batch.offsets.data(), batch.n_reads() };
             CapCut c;
-            const uint64_t n = cap_host_prefix(ctx, batch.offsets.data(), batch.n_reads(), c);
-            m.map_host(batch.bases.data(), batch.offsets.data(), n);
-            cap_commit(ctx, c, n, batch.offsets[n]);
+            cap_host_cut(ctx, hb, c);
+            m.map_host(hb);
+            cap_commit(ctx, c, hb.n_reads, hb.n_bases());
             if (ctx->cap_reached) break;
         }
     }
@@ -560,19 +556,25 @@ int drprg_hip_set_threads(drprg_hip_ctx* ctx, int threads)
     return DRPRG_OK;
 }
 
+// A host batch in either form: cut at the depth cap (the offsets are here), mapped, counted.  The entry points have refused null buffers.
+static void map_host_batch(drprg_hip_ctx* ctx, Mapper::HostBatch hb)
+{
+    Mapper& m = need_mapper(ctx);
+    if (hb.n_reads && cap_open(ctx, hb.n_reads)) {
+        if (hb.offsets[0] != 0) throw Error(DRPRG_EINVAL, "offsets[0] must be 0");
+        CapCut c;
+        cap_host_cut(ctx, hb, c);
+        m.map_host(hb);
+        cap_commit(ctx, c, hb.n_reads, hb.n_bases());
+    }
+    ctx->host_coverage_valid = false;
+}
+
 int drprg_hip_map_host(drprg_hip_ctx* ctx, const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads)
 {
     API_BEGIN(ctx)
     if (n_reads && (!bases || !offsets)) throw Error(DRPRG_EINVAL, "null buffer");
-    Mapper& m = need_mapper(ctx);
-    if (n_reads && cap_open(ctx, n_reads)) {
-        if (offsets[0] != 0) throw Error(DRPRG_EINVAL, "offsets[0] must be 0");
-        CapCut c;
-        n_reads = cap_host_prefix(ctx, offsets, n_reads, c); // (the offsets are here: a batch that crosses the depth cap is cut on the host)
-        m.map_host(bases, offsets, n_reads);
-        cap_commit(ctx, c, n_reads, offsets[n_reads]);
-    }
-    ctx->host_coverage_valid = false;
+    map_host_batch(ctx, Mapper::HostBatch { bases, offsets, n_reads });
     API_END(ctx)
 }
 
@@ -611,51 +613,41 @@ int drprg_hip_map_host_packed(drprg_hip_ctx* ctx, const uint32_t* words, const u
     API_BEGIN(ctx)
     if (n_reads && (!words || !offsets)) throw Error(DRPRG_EINVAL, "null buffer");
     if (n_npos && !npos) throw Error(DRPRG_EINVAL, "n_npos > 0 without the positions");
+    map_host_batch(ctx, Mapper::HostBatch { reinterpret_cast<const uint8_t*>(words), offsets, n_reads, true, npos, n_npos });
+    API_END(ctx)
+}
+
+// Behind the four device entry points: a batch that crosses the depth cap is cut to the accepted reads, then mapped, then counted.
+static int map_device_batch(drprg_hip_ctx* ctx, Mapper::DeviceBatch b, void* d_covg, void* d_prg_reads, void* hip_stream, bool deferred)
+{
+    API_BEGIN(ctx)
     Mapper& m = need_mapper(ctx);
-    if (n_reads && cap_open(ctx, n_reads)) {
-        if (offsets[0] != 0) throw Error(DRPRG_EINVAL, "offsets[0] must be 0");
+    if (b.n_reads == 0 || cap_open(ctx, b.n_reads)) { // (an empty batch still goes through the mapper's argument checks)
         CapCut c;
-        n_reads = cap_host_prefix(ctx, offsets, n_reads, c);
-        Mapper::HostBatch hb;
-        hb.bases = reinterpret_cast<const uint8_t*>(words);
-        hb.offsets = offsets;
-        hb.n_reads = n_reads;
-        hb.packed = true;
-        hb.npos = npos;
-        hb.n_npos = (uint64_t)(std::lower_bound(npos, npos + n_npos, offsets[n_reads]) - npos); // (all of them unless the batch was cut)
-        m.map_host(hb);
-        cap_commit(ctx, c, n_reads, offsets[n_reads]);
+        cap_device_prefix(ctx, m, b, hip_stream, c);
+        m.map(b, (uint32_t*)d_covg, (uint32_t*)d_prg_reads, (hipStream_t)hip_stream, deferred);
+        cap_commit(ctx, c, b.n_reads, b.n_bases);
     }
     ctx->host_coverage_valid = false;
     API_END(ctx)
 }
 
-static int map_device_packed(drprg_hip_ctx* ctx, const void* d_words, const void* d_offsets, uint64_t n_reads, uint64_t n_bases, const void* d_npos,
-    uint64_t n_npos, void* d_covg, void* d_prg_reads, void* hip_stream, bool deferred)
+static Mapper::DeviceBatch device_batch(const void* d_bases, const void* d_offsets, uint64_t n_reads, uint64_t n_bases, bool packed = false,
+    const void* d_npos = nullptr, uint64_t n_npos = 0)
 {
-    API_BEGIN(ctx)
-    Mapper& m = need_mapper(ctx);
-    if (n_reads == 0 || cap_open(ctx, n_reads)) { // (an empty batch still goes through the mapper's argument checks)
-        CapCut c;
-        cap_device_prefix(ctx, m, d_words, d_offsets, n_reads, n_bases, d_npos, n_npos, true, hip_stream, c);
-        m.map_device_packed((const uint32_t*)d_words, (const uint64_t*)d_offsets, n_reads, n_bases, (const uint64_t*)d_npos, n_npos, (uint32_t*)d_covg,
-            (uint32_t*)d_prg_reads, (hipStream_t)hip_stream, deferred);
-        cap_commit(ctx, c, n_reads, n_bases);
-    }
-    ctx->host_coverage_valid = false;
-    API_END(ctx)
+    return Mapper::DeviceBatch { (const uint8_t*)d_bases, (const uint64_t*)d_offsets, n_reads, n_bases, packed, (const uint64_t*)d_npos, n_npos };
 }
 
 int drprg_hip_map_device_packed(drprg_hip_ctx* ctx, const void* d_words, const void* d_offsets, uint64_t n_reads, uint64_t n_bases, const void* d_npos,
     uint64_t n_npos, void* d_covg, void* d_prg_reads, void* hip_stream)
 {
-    return map_device_packed(ctx, d_words, d_offsets, n_reads, n_bases, d_npos, n_npos, d_covg, d_prg_reads, hip_stream, false);
+    return map_device_batch(ctx, device_batch(d_words, d_offsets, n_reads, n_bases, true, d_npos, n_npos), d_covg, d_prg_reads, hip_stream, false);
 }
 
 int drprg_hip_map_device_packed_async(drprg_hip_ctx* ctx, const void* d_words, const void* d_offsets, uint64_t n_reads, uint64_t n_bases, const void* d_npos,
     uint64_t n_npos, void* d_covg, void* d_prg_reads, void* hip_stream)
 {
-    return map_device_packed(ctx, d_words, d_offsets, n_reads, n_bases, d_npos, n_npos, d_covg, d_prg_reads, hip_stream, true);
+    return map_device_batch(ctx, device_batch(d_words, d_offsets, n_reads, n_bases, true, d_npos, n_npos), d_covg, d_prg_reads, hip_stream, true);
 }
 
 int drprg_hip_pack_device(drprg_hip_ctx* ctx, const void* d_bases, uint64_t n_bases, void* d_words, void* d_npos, uint64_t npos_cap, uint64_t* n_npos,
@@ -672,35 +664,13 @@ int drprg_hip_pack_device(drprg_hip_ctx* ctx, const void* d_bases, uint64_t n_ba
 int drprg_hip_map_device(drprg_hip_ctx* ctx, const void* d_bases, const void* d_offsets, uint64_t n_reads, uint64_t n_bases,
     void* d_covg, void* d_prg_reads, void* hip_stream)
 {
-    API_BEGIN(ctx)
-    Mapper& m = need_mapper(ctx);
-    if (n_reads == 0 || cap_open(ctx, n_reads)) {
-        CapCut c;
-        uint64_t no_npos = 0;
-        cap_device_prefix(ctx, m, d_bases, d_offsets, n_reads, n_bases, nullptr, no_npos, false, hip_stream, c);
-        m.map_device((const uint8_t*)d_bases, (const uint64_t*)d_offsets, n_reads, n_bases, (uint32_t*)d_covg,
-            (uint32_t*)d_prg_reads, (hipStream_t)hip_stream);
-        cap_commit(ctx, c, n_reads, n_bases);
-    }
-    ctx->host_coverage_valid = false;
-    API_END(ctx)
+    return map_device_batch(ctx, device_batch(d_bases, d_offsets, n_reads, n_bases), d_covg, d_prg_reads, hip_stream, false);
 }
 
 int drprg_hip_map_device_async(drprg_hip_ctx* ctx, const void* d_bases, const void* d_offsets, uint64_t n_reads, uint64_t n_bases,
     void* d_covg, void* d_prg_reads, void* hip_stream)
 {
-    API_BEGIN(ctx)
-    Mapper& m = need_mapper(ctx);
-    if (n_reads == 0 || cap_open(ctx, n_reads)) {
-        CapCut c;
-        uint64_t no_npos = 0;
-        cap_device_prefix(ctx, m, d_bases, d_offsets, n_reads, n_bases, nullptr, no_npos, false, hip_stream, c);
-        m.map_device_async((const uint8_t*)d_bases, (const uint64_t*)d_offsets, n_reads, n_bases, (uint32_t*)d_covg,
-            (uint32_t*)d_prg_reads, (hipStream_t)hip_stream);
-        cap_commit(ctx, c, n_reads, n_bases);
-    }
-    ctx->host_coverage_valid = false;
-    API_END(ctx)
+    return map_device_batch(ctx, device_batch(d_bases, d_offsets, n_reads, n_bases), d_covg, d_prg_reads, hip_stream, true);
 }
 
 int drprg_hip_sync(drprg_hip_ctx* ctx)

@@ -180,15 +180,14 @@ Mapper::~Mapper()
     dfree(d_covg_); d_prg_reads_ = nullptr; dfree(d_counters_);
     for (int i = 0; i < 3; ++i) dfree(d_unpacked_[i]);
     dfree(d_pack_count_);
-    dfree(d_npos_);
     dfree(d_key_a_); dfree(d_key_b_); dfree(d_val_a_); dfree(d_val_b_);
     dfree(d_head_); dfree(d_scan_); dfree(d_cstart_); dfree(d_order_); dfree(d_clusters_);
     if (d_temp_) (void)hipFree(d_temp_);
     for (TileSet& t : tsets_) free_tile_set(t);
-    dfree(d_bases_); dfree(d_offsets_); dfree(d_bloom_); dfree(d_bloom0_); dfree(d_bloom0f_); dfree(d_bloomr_); dfree(d_pbloom_); dfree(d_mid0_); dfree(d_mid_bitmap_); dfree(d_midc_); dfree(d_blkc_);
-    for (Stage& st : stage_) {
-        dfree(st.d_bases); dfree(st.d_offsets); dfree(st.d_npos);
-        if (st.copied) (void)hipEventDestroy(st.copied);
+    dfree(d_bloom_); dfree(d_bloom0_); dfree(d_bloom0f_); dfree(d_bloomr_); dfree(d_pbloom_); dfree(d_mid0_); dfree(d_mid_bitmap_); dfree(d_midc_); dfree(d_blkc_);
+    for (Stage* st : { &stage_[0], &stage_[1], &stage_sync_ }) {
+        dfree(st->d_bases); dfree(st->d_offsets); dfree(st->d_npos);
+        if (st->copied) (void)hipEventDestroy(st->copied);
     }
     dfree(d_peer_tmp_);
     for (auto& a : kept_arenas_) (void)hipFree(a.first);
@@ -196,8 +195,6 @@ Mapper::~Mapper()
     if (copy_stream_) (void)hipStreamDestroy(copy_stream_);
     if (h_counters_) (void)hipHostFree(h_counters_);
     if (h_cut_) (void)hipHostFree(h_cut_);
-    if (h_bases_) (void)hipHostFree(h_bases_);
-    if (h_offsets_) (void)hipHostFree(h_offsets_);
     if (ev0_) (void)hipEventDestroy(ev0_);
     if (ev1_) (void)hipEventDestroy(ev1_);
     if (stream_) (void)hipStreamDestroy(stream_);
@@ -365,22 +362,16 @@ void Mapper::ensure_lanes()
     }
 }
 
-Mapper::Batch Mapper::make_batch(int lane, const uint8_t* d_bases, const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases, uint32_t* covg,
-    uint32_t* prg_reads, hipStream_t stream, const PackedInfo* pk) const
+Mapper::Batch Mapper::make_batch(int lane, const DeviceBatch& batch, uint32_t* covg, uint32_t* prg_reads, hipStream_t stream) const
 {
     Batch b;
+    b.batch = batch;
     b.active = true;
     b.direct = !use_filter_; // (the callers run only the two candidate sequences)
     b.lane = lane;
-    b.d_bases = d_bases;
-    b.d_offsets = d_offsets;
-    b.n_reads = (uint32_t)n_reads;
-    b.n_bases = n_bases;
     b.covg = covg;
     b.prg_reads = prg_reads;
     b.stream = stream;
-    b.packed = pk != nullptr; // (the batch's own description: a re-run or its leftover reads see the format it came in)
-    if (pk) b.pk = *pk;
     return b;
 }
 
@@ -398,16 +389,16 @@ void Mapper::filter_launch(const Batch& b)
 {
     Lane& lane = lanes_[b.lane];
     // (a deferred batch: this lane's previous batch was completed by the call before this one; growing frees its buffers, which waits for the device)
-    grow_lane(lane, std::max<uint64_t>(min_capacity_, b.n_bases / FILTER_BASES_PER_ENTRY));
+    grow_lane(lane, std::max<uint64_t>(min_capacity_, b.batch.n_bases / FILTER_BASES_PER_ENTRY));
     if (!lane.scratch_zero) HIPCHK(hipMemsetAsync(lane.d_scratch, 0, L_N * sizeof(unsigned long long), b.stream));
     lane.scratch_zero = false;
-    dev::SketchArgs a = sketch_args(b.d_bases, b.d_offsets, b.n_reads, b.n_bases, b.pkp());
+    dev::SketchArgs a = sketch_args(b.batch);
     a.n_hits = &lane.d_scratch[L_HITS];
     a.n_minimizers = &lane.d_scratch[L_MINIMIZERS];
     a.overflow = reinterpret_cast<uint32_t*>(&lane.d_scratch[L_OVERFLOW]);
     dev::FilterBuffers fb { lane.raw_pos, lane.cand_info, lane.cand_pos1, lane.cand_rec, lane.raw_capacity, lane.small, &lane.d_scratch[L_MAXLEN] };
     fb.class_clock = &lane.d_scratch[L_FT_CLOCK]; // (unused when DRPRG_FT_SHARE pins the shares: then nothing adapts them)
-    if (ft_share_[b.packed ? 1 : 0][0]) fb.wave_share = ft_share_[b.packed ? 1 : 0];
+    if (ft_share_[b.batch.packed ? 1 : 0][0]) fb.wave_share = ft_share_[b.batch.packed ? 1 : 0];
     dev::BloomTables bt { d_bloom_, bloom_wbits_, d_bloom0_, bloom0_wbits_, d_bloomr_, d_bloom0f_ };
     bt.blkc = d_blkc_;
     bt.blkc_wbits = blkc_wbits_;
@@ -490,13 +481,13 @@ void Mapper::cluster_hits(const uint64_t* d_offsets, uint32_t n_hits, bool order
     HIPCHK(dev::launch_cluster_pipeline(c, n_hits, n_prgs_, stream));
 }
 
-dev::SketchArgs Mapper::sketch_args(const uint8_t* d_bases, const uint64_t* d_offsets, uint32_t n_reads, uint64_t n_bases, const PackedInfo* pk) const
+dev::SketchArgs Mapper::sketch_args(const DeviceBatch& batch) const
 {
     dev::SketchArgs a {};
-    a.bases = d_bases;
-    a.offsets = d_offsets;
-    a.n_bases = n_bases;
-    a.n_reads = n_reads;
+    a.bases = batch.d_bases;
+    a.offsets = batch.d_offsets;
+    a.n_bases = batch.n_bases;
+    a.n_reads = (uint32_t)batch.n_reads; // (check: at most 2^28)
     a.w = params_.w;
     a.k = params_.k;
     a.halo = halo_;
@@ -515,18 +506,16 @@ dev::SketchArgs Mapper::sketch_args(const uint8_t* d_bases, const uint64_t* d_of
     a.n_hits = &d_counters_[C_HITS];
     a.n_minimizers = &d_counters_[C_MINIMIZERS];
     a.overflow = reinterpret_cast<uint32_t*>(&d_counters_[C_OVERFLOW]);
-    if (pk) { // (a batch of 2-bit words: said by the caller, carried with the batch -- not looked up by its address)
-        a.packed = 1;
-        a.npos = pk->d_npos;
-        a.n_npos = pk->n_npos;
-    }
+    a.packed = batch.packed ? 1 : 0; // (said by the caller, carried with the batch -- not looked up by its address)
+    a.npos = batch.d_npos;
+    a.n_npos = batch.n_npos;
     return a;
 }
 
-const uint8_t* Mapper::ascii_view(int slot, const uint8_t* d_bases, uint64_t n_bases, hipStream_t stream, const PackedInfo* pk)
+Mapper::DeviceBatch Mapper::ascii_view(int slot, const DeviceBatch& batch, hipStream_t stream)
 {
-    if (!pk) return d_bases;
-    const uint64_t need = (n_bases + 15) / 16 * 16 + 64;
+    if (!batch.packed) return batch;
+    const uint64_t need = (batch.n_bases + 15) / 16 * 16 + 64;
     if (need > unpacked_cap_[slot]) {
         sync(); // (a batch in flight may still read the old buffer)
         HIPCHK(hipStreamSynchronize(stream));
@@ -534,8 +523,13 @@ const uint8_t* Mapper::ascii_view(int slot, const uint8_t* d_bases, uint64_t n_b
         unpacked_cap_[slot] = need + need / 4;
         dmalloc(d_unpacked_[slot], unpacked_cap_[slot]);
     }
-    HIPCHK(dev::launch_unpack(reinterpret_cast<const uint32_t*>(d_bases), n_bases, pk->d_npos, pk->n_npos, d_unpacked_[slot], stream));
-    return d_unpacked_[slot];
+    HIPCHK(dev::launch_unpack(reinterpret_cast<const uint32_t*>(batch.d_bases), batch.n_bases, batch.d_npos, batch.n_npos, d_unpacked_[slot], stream));
+    DeviceBatch ascii;
+    ascii.d_bases = d_unpacked_[slot];
+    ascii.d_offsets = batch.d_offsets;
+    ascii.n_reads = batch.n_reads;
+    ascii.n_bases = batch.n_bases;
+    return ascii;
 }
 
 void Mapper::read_counters(hipStream_t stream)
@@ -559,7 +553,7 @@ void Mapper::leftovers(const Batch& b)
     Lane& lane = lanes_[b.lane];
     if (lane.h_scratch[L_COMPLEX] == 0) return;
     const hipStream_t stream = b.stream;
-    dev::SketchArgs a = sketch_args(b.d_bases, b.d_offsets, b.n_reads, b.n_bases, b.pkp());
+    dev::SketchArgs a = sketch_args(b.batch);
     a.n_hits = &lane.d_scratch[L_HITS];
     a.n_minimizers = &lane.d_scratch[L_MINIMIZERS]; // (the recount pass does not count minimizers again)
     a.overflow = reinterpret_cast<uint32_t*>(&lane.d_scratch[L_OVERFLOW]);
@@ -574,7 +568,7 @@ void Mapper::leftovers(const Batch& b)
     a.hit_val = d_val_a_;
     a.hit_capacity = hit_capacity_;
     HIPCHK(dev::launch_filter_expand(a, lane.fw, stream));
-    cluster_hits(b.d_offsets, (uint32_t)n_left, lane.h_scratch[L_MAXLEN] <= READ_SORT_MAX_LEN, &lane.d_scratch[L_UNSORTED], b.covg, b.prg_reads, stream);
+    cluster_hits(b.batch.d_offsets, (uint32_t)n_left, lane.h_scratch[L_MAXLEN] <= READ_SORT_MAX_LEN, &lane.d_scratch[L_UNSORTED], b.covg, b.prg_reads, stream);
 }
 
 void Mapper::free_tile_set(TileSet& t)
@@ -610,10 +604,8 @@ void Mapper::ensure_tile_workspace(TileSet& t, uint32_t n_tiles, uint32_t tile_c
 void Mapper::direct_launch(const Batch& b)
 {
     const int set = b.lane;
-    const uint8_t* const d_bases = b.d_bases;
-    const uint64_t n_bases = b.n_bases;
+    const uint64_t n_bases = b.batch.n_bases;
     const hipStream_t stream = b.stream;
-    const PackedInfo* const pk = b.pkp();
     TileSet& t = tsets_[set];
     ts_ = &t;
     const uint32_t n_tiles = dev::direct_candidate_tiles(n_bases, halo_, params_.k, params_.w, wide_hash_, sw_.direct_lds); // = slices
@@ -643,8 +635,8 @@ void Mapper::direct_launch(const Batch& b)
     HIPCHK(hipMemsetAsync(t.d_tile_count + n_tiles, 0, sizeof(uint32_t), stream)); // the scan's closing zero
     // a packed batch: sketch_wave_kernel reads the words themselves (round 4; the positions of its npos as one bit per base, set here);
     // the general direct kernel reads an ASCII expansion made on the same stream (packed.hip)
-    const bool native_packed = pk != nullptr && dev::direct_uses_wave_form(params_.k, params_.w, wide_hash_, sw_.direct_lds);
-    dev::SketchArgs a = sketch_args(native_packed ? d_bases : ascii_view(set, d_bases, n_bases, stream, pk), b.d_offsets, b.n_reads, n_bases, native_packed ? pk : nullptr);
+    const bool native_packed = b.batch.packed && dev::direct_uses_wave_form(params_.k, params_.w, wide_hash_, sw_.direct_lds);
+    dev::SketchArgs a = sketch_args(native_packed ? b.batch : ascii_view(set, b.batch, stream));
     if (native_packed && a.n_npos) {
         const uint64_t words16 = ((n_bases + 15) / 16 + 1) & ~1ull; // (an even number of u16 words: the marks are 32-bit atomics)
         if (words16 > t.nbits_cap) {
@@ -688,7 +680,7 @@ void Mapper::direct_launch(const Batch& b)
     rc.chunk_counter = reinterpret_cast<uint32_t*>(&lane.d_scratch[L_CHUNK]);
     lane.fw = dev::FilterWork {};
     lane.fw.read_begin = 0;
-    lane.fw.read_end = b.n_reads;
+    lane.fw.read_end = (uint32_t)b.batch.n_reads;
     dev::init_candidate_work(lane.fw, fb, n_cus_);
     dev::KernelTimer timer;
     if (timing_) {
@@ -753,7 +745,7 @@ bool Mapper::filter_finish(const Batch& b, int attempt)
     tot_minimizers_ += lane.h_scratch[L_MINIMIZERS];
     tot_hits_ += lane.h_scratch[L_HITS];
     tot_leftover_ += lane.h_scratch[L_COMPLEX];
-    tune_filter_shares(lane, b.packed, b.n_bases);
+    tune_filter_shares(lane, b.batch.packed, b.batch.n_bases);
     leftovers(b);
     return true;
 }
@@ -822,40 +814,46 @@ void Mapper::tune_filter_shares(const Lane& lane, bool packed, uint64_t n_bases)
     s[3] = 1024u - acc;
 }
 
-void Mapper::map_device_async(const uint8_t* d_bases, const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases, uint32_t* covg,
-    uint32_t* prg_reads, hipStream_t stream)
+void Mapper::check(const DeviceBatch& b)
 {
-    map_device_async_impl(d_bases, d_offsets, n_reads, n_bases, covg, prg_reads, stream, nullptr);
+    if (b.n_npos && !b.d_npos) throw Error(DRPRG_EINVAL, "n_npos > 0 without the positions");
+    if (b.n_reads == 0) return;
+    if (!b.d_bases || !b.d_offsets) throw Error(DRPRG_EINVAL, "null device pointer");
+    if ((reinterpret_cast<uintptr_t>(b.d_bases) & 15u) != 0)
+        throw Error(DRPRG_EINVAL, std::string(b.packed ? "d_words" : "d_bases") + " must be 16-byte aligned");
+    if (b.n_reads > dev::MAX_BATCH_READS) throw Error(DRPRG_EOVERFLOW, "at most " + std::to_string(dev::MAX_BATCH_READS) + " reads per batch");
 }
 
-void Mapper::map_device_async_impl(const uint8_t* d_bases, const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases, uint32_t* covg,
-    uint32_t* prg_reads, hipStream_t stream, const PackedInfo* pk)
+void Mapper::map(const DeviceBatch& batch, uint32_t* covg, uint32_t* prg_reads, hipStream_t stream, bool deferred)
 {
-    if (n_reads == 0) return;
-    if ((!use_filter_ && !use_direct_cands_) || n_bases == 0) { // (no deferred form of the other sequences: the batch is complete on return,
-        map_device_impl(d_bases, d_offsets, n_reads, n_bases, covg, prg_reads, stream, pk); // including what its tail queued for the leftover reads)
-        HIPCHK(hipSetDevice(device_));
-        wait_stream(stream ? stream : stream_);
+    check(batch);
+    if (batch.n_reads == 0) return;
+    HIPCHK(hipSetDevice(device_));
+    if (kept_cap_ && !in_keep_call_) kept_broken_ = true; // reads of the caller's own buffers: not among the kept ones
+    if (!covg) covg = d_covg_;
+    if (!prg_reads) prg_reads = d_prg_reads_;
+    if (!stream) stream = stream_;
+    if (!deferred || (!use_filter_ && !use_direct_cands_) || batch.n_bases == 0) {
+        complete_pending();
+        run_batch(batch, covg, prg_reads, stream);
+        tot_reads_ += batch.n_reads;
+        tot_bases_ += batch.n_bases;
+        // (no deferred form of the other sequences, or of a batch of empty reads: the batch is complete on return, including what its tail
+        // queued for the leftover reads)
+        if (deferred) wait_stream(stream);
         return;
     }
-    if (!d_bases || !d_offsets) throw Error(DRPRG_EINVAL, "null device pointer");
-    if ((reinterpret_cast<uintptr_t>(d_bases) & 15u) != 0) throw Error(DRPRG_EINVAL, "d_bases must be 16-byte aligned");
-    if (n_reads > dev::MAX_BATCH_READS)
-        throw Error(DRPRG_EOVERFLOW, "at most " + std::to_string(dev::MAX_BATCH_READS) + " reads per batch");
-    HIPCHK(hipSetDevice(device_));
-    if (kept_cap_ && !in_keep_call_) kept_broken_ = true;
     // the two lanes take the batches in turn: a batch's read-back is looked at while the next batch runs (a batch whose candidate buffers
     // overflowed, or that left reads to the generic pipeline, is finished then -- from its own lane, which the batch in flight does not touch)
-    const Batch cur = make_batch(pipe_next_, d_bases, d_offsets, n_reads, n_bases, covg ? covg : d_covg_, prg_reads ? prg_reads : d_prg_reads_,
-        stream ? stream : stream_, pk);
+    const Batch cur = make_batch(pipe_next_, batch, covg, prg_reads, stream);
     launch(cur);
     // the batch just queued is registered before the previous one is completed: if completing that one throws (a read too long,
     // an overflow that does not go away, a HIP error) the queued batch is still known to sync() and to the next call
     const Batch prev = pending_;
     pending_ = cur;
     pipe_next_ ^= 1;
-    tot_reads_ += n_reads;
-    tot_bases_ += n_bases;
+    tot_reads_ += batch.n_reads;
+    tot_bases_ += batch.n_bases;
     if (prev.active) complete_batch(prev); // the batch before this one, while this one runs
 }
 
@@ -894,14 +892,14 @@ void Mapper::sync()
     if (last) HIPCHK(hipStreamSynchronize(last));
 }
 
-void Mapper::run_batch(const uint8_t* d_bases, const uint64_t* d_offsets, uint32_t n_reads, uint64_t n_bases,
-    uint32_t* covg, uint32_t* prg_reads, hipStream_t stream, const PackedInfo* pk)
+void Mapper::run_batch(const DeviceBatch& batch, uint32_t* covg, uint32_t* prg_reads, hipStream_t stream)
 {
+    const uint64_t n_bases = batch.n_bases;
     if (n_bases == 0) return; // only empty reads: no k-mers, no hits
     if (use_filter_ || use_direct_cands_) {
         // ---- the candidate sequences (filtered; direct in its candidate form): the hits of short reads never leave the chip
         // (read_cluster_kernel).  Lane 0: complete_pending() has left nothing in flight on it ----
-        const Batch b = make_batch(0, d_bases, d_offsets, n_reads, n_bases, covg, prg_reads, stream, pk);
+        const Batch b = make_batch(0, batch, covg, prg_reads, stream);
         launch(b);
         complete_batch(b);
         return;
@@ -920,11 +918,11 @@ void Mapper::run_batch(const uint8_t* d_bases, const uint64_t* d_offsets, uint32
         ts_->first_cap = n_tiles + n_tiles / 4 + 16;
         dmalloc(ts_->d_tile_first, (size_t)ts_->first_cap);
     }
-    const uint8_t* const ascii = ascii_view(2, d_bases, n_bases, stream, pk); // (a packed batch: expanded on the device for this kernel)
+    const DeviceBatch ascii = ascii_view(2, batch, stream); // (a packed batch: expanded on the device for this kernel)
     for (int attempt = 0;; ++attempt) {
         HIPCHK(hipMemsetAsync(&d_counters_[C_HITS], 0, 2 * sizeof(unsigned long long), stream)); // hits + minimizers of this attempt
         HIPCHK(hipMemsetAsync(&d_counters_[C_OVERFLOW], 0, sizeof(unsigned long long), stream));
-        const dev::SketchArgs a = sketch_args(ascii, d_offsets, n_reads, n_bases, nullptr); // (the expansion is ASCII)
+        const dev::SketchArgs a = sketch_args(ascii);
         HIPCHK(dev::launch_sketch_probe(a, wide_hash_, stream, timer));
         read_counters(stream);
         if (attempt == 0) note_kernel_time(ev0_, ev1_); // (as complete_batch: a batch's first attempt)
@@ -940,59 +938,13 @@ void Mapper::run_batch(const uint8_t* d_bases, const uint64_t* d_offsets, uint32
     }
     tot_minimizers_ += h_counters_[C_MINIMIZERS];
     tot_hits_ += h_counters_[C_HITS];
-    cluster_hits(d_offsets, (uint32_t)h_counters_[C_HITS], false, nullptr, covg, prg_reads, stream);
+    cluster_hits(batch.d_offsets, (uint32_t)h_counters_[C_HITS], false, nullptr, covg, prg_reads, stream);
 }
 
-void Mapper::map_device(const uint8_t* d_bases, const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases,
-    uint32_t* covg, uint32_t* prg_reads, hipStream_t stream)
+Mapper::CutPoint Mapper::find_cut(const DeviceBatch& b, uint64_t target, hipStream_t stream)
 {
-    map_device_impl(d_bases, d_offsets, n_reads, n_bases, covg, prg_reads, stream, nullptr);
-}
-
-void Mapper::map_device_packed(const uint32_t* d_words, const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases, const uint64_t* d_npos, uint64_t n_npos,
-    uint32_t* covg, uint32_t* prg_reads, hipStream_t stream, bool deferred)
-{
-    if (n_npos && !d_npos) throw Error(DRPRG_EINVAL, "n_npos > 0 without the positions");
-    if (n_reads == 0) return;
-    // (everything that can refuse the batch is checked before the batch is known as packed; a batch that fails later is forgotten again)
-    if (!d_words || !d_offsets) throw Error(DRPRG_EINVAL, "null device pointer");
-    if ((reinterpret_cast<uintptr_t>(d_words) & 15u) != 0) throw Error(DRPRG_EINVAL, "d_words must be 16-byte aligned");
-    const uint8_t* key = reinterpret_cast<const uint8_t*>(d_words);
-    const PackedInfo info { d_npos, n_npos }; // (travels with the batch through every function that touches it, and into Batch)
-    if (deferred) map_device_async_impl(key, d_offsets, n_reads, n_bases, covg, prg_reads, stream, &info);
-    else map_device_impl(key, d_offsets, n_reads, n_bases, covg, prg_reads, stream, &info);
-}
-
-void Mapper::map_device_impl(const uint8_t* d_bases, const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases,
-    uint32_t* covg, uint32_t* prg_reads, hipStream_t stream, const PackedInfo* pk)
-{
-    if (n_reads == 0) return;
-    if (!d_bases || !d_offsets) throw Error(DRPRG_EINVAL, "null device pointer");
-    if ((reinterpret_cast<uintptr_t>(d_bases) & 15u) != 0) throw Error(DRPRG_EINVAL, "d_bases must be 16-byte aligned");
-    if (n_reads > dev::MAX_BATCH_READS)
-        throw Error(DRPRG_EOVERFLOW, "at most " + std::to_string(dev::MAX_BATCH_READS) + " reads per batch");
-    HIPCHK(hipSetDevice(device_));
-    if (kept_cap_ && !in_keep_call_) kept_broken_ = true; // reads of the caller's own buffers: not among the kept ones
-    complete_pending();
-    run_batch(d_bases, d_offsets, (uint32_t)n_reads, n_bases, covg ? covg : d_covg_, prg_reads ? prg_reads : d_prg_reads_,
-        stream ? stream : stream_, pk);
-    tot_reads_ += n_reads;
-    tot_bases_ += n_bases;
-}
-
-void Mapper::check_device_batch(const void* d_bases, const void* d_offsets, uint64_t n_reads, const void* d_npos, uint64_t n_npos, bool packed)
-{
-    if (n_npos && !d_npos) throw Error(DRPRG_EINVAL, "n_npos > 0 without the positions");
-    if (n_reads == 0) return;
-    if (!d_bases || !d_offsets) throw Error(DRPRG_EINVAL, "null device pointer");
-    if ((reinterpret_cast<uintptr_t>(d_bases) & 15u) != 0) throw Error(DRPRG_EINVAL, packed ? "d_words must be 16-byte aligned" : "d_bases must be 16-byte aligned");
-    if (n_reads > dev::MAX_BATCH_READS) throw Error(DRPRG_EOVERFLOW, "at most " + std::to_string(dev::MAX_BATCH_READS) + " reads per batch");
-}
-
-Mapper::CutPoint Mapper::find_cut(const uint64_t* d_offsets, uint64_t n_reads, uint64_t target, const uint64_t* d_npos, uint64_t n_npos, hipStream_t stream)
-{
-    if (!d_offsets || n_reads == 0) throw Error(DRPRG_EINVAL, "null device pointer");
-    if (n_npos && !d_npos) throw Error(DRPRG_EINVAL, "n_npos > 0 without the positions");
+    check(b);
+    if (b.n_reads == 0) return CutPoint { 0, 0, 0 };
     sync(); // (a batch in flight comes before this one in the running total: it is complete before this one is cut)
     HIPCHK(hipSetDevice(device_));
     if (!stream) stream = stream_;
@@ -1000,52 +952,57 @@ Mapper::CutPoint Mapper::find_cut(const uint64_t* d_offsets, uint64_t n_reads, u
         HIPCHK(hipHostMalloc((void**)&h_cut_, 4 * sizeof(unsigned long long), hipHostMallocDefault));
         HIPCHK(hipHostGetDevicePointer((void**)&h_cut_dev_, h_cut_, 0));
     }
-    HIPCHK(dev::launch_covg_cut(d_offsets, n_reads, target, d_npos, n_npos, h_cut_dev_, stream));
+    HIPCHK(dev::launch_covg_cut(b.d_offsets, b.n_reads, target, b.d_npos, b.n_npos, h_cut_dev_, stream));
     wait_stream(stream);
     return CutPoint { h_cut_[0], h_cut_[1], h_cut_[2] };
 }
 
-void Mapper::map_host(const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads)
+void Mapper::ensure_stage(Stage& st, uint64_t payload_bytes, uint64_t n_reads, uint64_t n_npos)
 {
-    HostBatch b;
-    b.bases = bases;
-    b.offsets = offsets;
-    b.n_reads = n_reads;
-    map_host(b);
+    const bool grow_bases = payload_bytes + 64 > st.bases_cap, grow_reads = n_reads + 1 > st.reads_cap, grow_npos = n_npos > st.npos_cap;
+    if (grow_bases || grow_reads || grow_npos) sync(); // (freeing device memory waits for the device; be explicit about the batch in flight)
+    if (grow_bases) {
+        dfree(st.d_bases);
+        st.bases_cap = payload_bytes + payload_bytes / 4 + 64;
+        dmalloc(st.d_bases, st.bases_cap);
+    }
+    if (grow_reads) {
+        dfree(st.d_offsets);
+        st.reads_cap = n_reads + n_reads / 4 + 1;
+        dmalloc(st.d_offsets, st.reads_cap);
+    }
+    if (grow_npos) {
+        dfree(st.d_npos);
+        st.npos_cap = n_npos + n_npos / 4 + 16;
+        dmalloc(st.d_npos, st.npos_cap);
+    }
 }
 
-void Mapper::map_host(const HostBatch& b)
+Mapper::DeviceBatch Mapper::copy_in(const HostBatch& hb, uint8_t* d_bases, uint64_t* d_offsets, uint64_t* d_npos, hipStream_t stream)
 {
-    const uint64_t n_reads = b.n_reads;
-    if (n_reads == 0) return;
+    DeviceBatch b;
+    b.d_bases = d_bases;
+    b.d_offsets = d_offsets;
+    b.n_reads = hb.n_reads;
+    b.n_bases = hb.n_bases();
+    b.packed = hb.packed;
+    b.n_npos = hb.packed ? hb.n_npos : 0;
+    b.d_npos = b.n_npos ? d_npos : nullptr;
+    HIPCHK(hipMemcpyAsync(d_bases, hb.bases, hb.payload_bytes(), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(d_offsets, hb.offsets, (hb.n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+    if (b.n_npos) HIPCHK(hipMemcpyAsync(d_npos, hb.npos, b.n_npos * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+    return b;
+}
+
+void Mapper::map_host(const HostBatch& hb)
+{
+    if (hb.n_reads == 0) return;
     sync();
     HIPCHK(hipSetDevice(device_));
-    if (b.offsets[0] != 0) throw Error(DRPRG_EINVAL, "offsets[0] must be 0");
-    const uint64_t n_bases = b.n_bases(), bytes = b.payload_bytes();
-    if (bytes + 64 > stage_bases_cap_) {
-        dfree(d_bases_);
-        stage_bases_cap_ = bytes + bytes / 4 + 64;
-        dmalloc(d_bases_, stage_bases_cap_);
-    }
-    if (n_reads + 1 > stage_reads_cap_) {
-        dfree(d_offsets_);
-        stage_reads_cap_ = n_reads + n_reads / 4 + 1;
-        dmalloc(d_offsets_, stage_reads_cap_);
-    }
-    if (b.packed && b.n_npos > stage_npos_cap_) {
-        dfree(d_npos_);
-        stage_npos_cap_ = b.n_npos + b.n_npos / 4 + 16;
-        dmalloc(d_npos_, stage_npos_cap_);
-    }
-    HIPCHK(hipMemcpyAsync(d_bases_, b.bases, bytes, hipMemcpyHostToDevice, stream_));
-    HIPCHK(hipMemcpyAsync(d_offsets_, b.offsets, (n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream_));
-    if (b.packed) {
-        if (b.n_npos) HIPCHK(hipMemcpyAsync(d_npos_, b.npos, b.n_npos * sizeof(uint64_t), hipMemcpyHostToDevice, stream_));
-        map_device_packed(reinterpret_cast<const uint32_t*>(d_bases_), d_offsets_, n_reads, n_bases, b.n_npos ? d_npos_ : nullptr, b.n_npos, nullptr, nullptr, stream_,
-            false);
-    } else {
-        map_device(d_bases_, d_offsets_, n_reads, n_bases, nullptr, nullptr, stream_);
-    }
+    if (hb.offsets[0] != 0) throw Error(DRPRG_EINVAL, "offsets[0] must be 0");
+    Stage& st = stage_sync_;
+    ensure_stage(st, hb.payload_bytes(), hb.n_reads, hb.packed ? hb.n_npos : 0);
+    map(copy_in(hb, st.d_bases, st.d_offsets, st.d_npos, stream_), nullptr, nullptr, stream_, false);
     HIPCHK(hipStreamSynchronize(stream_)); // the staging buffers are reused by the next call
 }
 
@@ -1123,9 +1080,8 @@ uint64_t Mapper::map_kept_from(const Mapper& other)
     if (other.device_ != device_) throw Error(DRPRG_EINVAL, "the kept reads live on another device");
     if (!other.kept_complete()) throw Error(DRPRG_ENODATA, "the other context does not hold all of its reads");
     uint64_t n = 0;
-    for (const KeptBatch& b : other.kept_) {
-        if (b.packed) map_device_packed(reinterpret_cast<const uint32_t*>(b.d_bases), b.d_offsets, b.n_reads, b.n_bases, b.d_npos, b.n_npos, nullptr, nullptr, stream_, true);
-        else map_device_async(b.d_bases, b.d_offsets, b.n_reads, b.n_bases, nullptr, nullptr, stream_);
+    for (const DeviceBatch& b : other.kept_) {
+        map(b, nullptr, nullptr, stream_, true);
         n += b.n_reads;
     }
     sync();
@@ -1146,7 +1102,7 @@ void Mapper::select_reads_with_anchors(std::vector<uint64_t> anchors, uint32_t A
     std::vector<uint32_t> pf(2048, 0);
     for (uint64_t a : anchors) pf[(a & 0xFFFF) >> 5] |= 1u << (a & 31);
     uint64_t total_reads = 0, max_reads = 0;
-    for (const KeptBatch& b : kept_) {
+    for (const DeviceBatch& b : kept_) {
         total_reads += b.n_reads;
         max_reads = std::max(max_reads, b.n_reads);
     }
@@ -1177,7 +1133,7 @@ void Mapper::select_reads_with_anchors(std::vector<uint64_t> anchors, uint32_t A
     // many consecutive batches as expand into <= 1 GB (a larger batch alone) --, scanned, and its selected reads gathered before the next
     // window's expansion takes the scratch: the scratch is the largest window, not the sample (up to 128 Gbases can stay
     // resident packed; expanding all of them at once needed that much memory again, with no way back to the file pass).
-    auto expanded = [](const KeptBatch& kb) -> uint64_t { return kb.packed ? (kb.n_bases + 15) / 16 * 16 + 64 : 0; };
+    auto expanded = [](const DeviceBatch& kb) -> uint64_t { return kb.packed ? (kb.n_bases + 15) / 16 * 16 + 64 : 0; };
     constexpr uint64_t WINDOW_BYTES = 1ull << 30;
     std::vector<std::pair<size_t, size_t>> windows; // [first batch, one past the last)
     uint64_t scratch_need = 0;
@@ -1196,7 +1152,7 @@ void Mapper::select_reads_with_anchors(std::vector<uint64_t> anchors, uint32_t A
     for (const auto& win : windows) {
         uint64_t at = 0;
         for (size_t b = win.first; b < win.second; ++b) {
-            const KeptBatch& kb = kept_[b];
+            const DeviceBatch& kb = kept_[b];
             if (!kb.packed) {
                 ascii[b] = kb.d_bases;
                 continue;
@@ -1206,7 +1162,7 @@ void Mapper::select_reads_with_anchors(std::vector<uint64_t> anchors, uint32_t A
             at += expanded(kb);
         }
         for (size_t b = win.first; b < win.second; ++b) {
-            const KeptBatch& kb = kept_[b];
+            const DeviceBatch& kb = kept_[b];
             HIPCHK(hipMemsetAsync(d_flags, 0, kb.n_reads * sizeof(uint32_t), stream_));
             HIPCHK(dev::launch_anchor_scan(ascii[b], kb.d_offsets, (uint32_t)kb.n_reads, kb.n_bases, d_anchors, (uint32_t)anchors.size(), A, d_pf, (uint32_t)b,
                 d_flags, d_count, d_list, total_reads, n_cus_, stream_));
@@ -1249,49 +1205,32 @@ void Mapper::select_reads_with_anchors(std::vector<uint64_t> anchors, uint32_t A
     }
 }
 
-void Mapper::map_host_async(const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads)
-{
-    HostBatch b;
-    b.bases = bases;
-    b.offsets = offsets;
-    b.n_reads = n_reads;
-    map_host_async(b);
-}
-
 void Mapper::map_host_async(const HostBatch& hb)
 {
     const uint64_t n_reads = hb.n_reads;
-    const uint64_t* offsets = hb.offsets;
     if (n_reads == 0) return;
     if (kept_cap_ && !kept_broken_) {
         // the block goes into device memory of its own and stays there
         HIPCHK(hipSetDevice(device_));
-        if (offsets[0] != 0) throw Error(DRPRG_EINVAL, "offsets[0] must be 0");
-        const uint64_t n_bases = hb.n_bases(), bytes = hb.payload_bytes();
-        uint8_t* db = n_bases ? static_cast<uint8_t*>(arena_take(bytes + 64)) : nullptr;
-        uint64_t* doff = n_bases && db ? static_cast<uint64_t*>(arena_take((n_reads + 1) * sizeof(uint64_t))) : nullptr;
-        uint64_t* dnp = n_bases && doff && hb.packed && hb.n_npos ? static_cast<uint64_t*>(arena_take(hb.n_npos * sizeof(uint64_t))) : nullptr;
-        if (n_bases == 0) {
+        if (hb.offsets[0] != 0) throw Error(DRPRG_EINVAL, "offsets[0] must be 0");
+        if (hb.n_bases() == 0) {
             tot_reads_ += n_reads; // (only empty reads: nothing to keep)
             return;
         }
-        if (db && doff && (dnp || !(hb.packed && hb.n_npos))) {
+        const uint64_t n_npos = hb.packed ? hb.n_npos : 0;
+        uint8_t* db = static_cast<uint8_t*>(arena_take(hb.payload_bytes() + 64));
+        uint64_t* doff = db ? static_cast<uint64_t*>(arena_take((n_reads + 1) * sizeof(uint64_t))) : nullptr;
+        uint64_t* dnp = doff && n_npos ? static_cast<uint64_t*>(arena_take(n_npos * sizeof(uint64_t))) : nullptr;
+        if (db && doff && (dnp || !n_npos)) {
             if (!copy_stream_) HIPCHK(hipStreamCreateWithFlags(&copy_stream_, hipStreamNonBlocking));
             if (!kept_copied_) HIPCHK(hipEventCreateWithFlags(&kept_copied_, hipEventDisableTiming));
-            HIPCHK(hipMemcpyAsync(db, hb.bases, bytes, hipMemcpyHostToDevice, copy_stream_));
-            HIPCHK(hipMemcpyAsync(doff, offsets, (n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, copy_stream_));
-            if (dnp) HIPCHK(hipMemcpyAsync(dnp, hb.npos, hb.n_npos * sizeof(uint64_t), hipMemcpyHostToDevice, copy_stream_));
+            const DeviceBatch kb = copy_in(hb, db, doff, dnp, copy_stream_);
             HIPCHK(hipEventRecord(kept_copied_, copy_stream_));
             HIPCHK(hipStreamWaitEvent(stream_, kept_copied_, 0));
-            KeptBatch kb { db, doff, n_reads, n_bases };
-            kb.packed = hb.packed;
-            kb.d_npos = dnp;
-            kb.n_npos = hb.packed ? hb.n_npos : 0;
             kept_.push_back(kb);
             in_keep_call_ = true;
             try {
-                if (hb.packed) map_device_packed(reinterpret_cast<const uint32_t*>(db), doff, n_reads, n_bases, dnp, kb.n_npos, nullptr, nullptr, stream_, true);
-                else map_device_async(db, doff, n_reads, n_bases, nullptr, nullptr, stream_);
+                map(kb, nullptr, nullptr, stream_, true);
             } catch (...) {
                 in_keep_call_ = false;
                 throw;
@@ -1314,44 +1253,22 @@ void Mapper::map_host_async(const HostBatch& hb)
         return;
     }
     HIPCHK(hipSetDevice(device_));
-    if (offsets[0] != 0) throw Error(DRPRG_EINVAL, "offsets[0] must be 0");
-    const uint64_t n_bases = hb.n_bases(), bytes = hb.payload_bytes();
-    if (n_bases == 0) { // only empty reads: nothing to copy, nothing to map (the counters still see them)
+    if (hb.offsets[0] != 0) throw Error(DRPRG_EINVAL, "offsets[0] must be 0");
+    if (hb.n_bases() == 0) { // only empty reads: nothing to copy, nothing to map (the counters still see them)
         tot_reads_ += n_reads;
         return;
     }
     if (!copy_stream_) HIPCHK(hipStreamCreateWithFlags(&copy_stream_, hipStreamNonBlocking));
-    // the batch that used this staging set two calls ago was completed by the previous call (map_device_async completes the batch
+    // the batch that used this staging set two calls ago was completed by the previous call (a deferred map completes the batch
     // before the one it queues), so the set is free
     Stage& st = stage_[stage_next_];
     stage_next_ ^= 1;
     if (!st.copied) HIPCHK(hipEventCreateWithFlags(&st.copied, hipEventDisableTiming));
-    if (bytes + 64 > st.bases_cap) {
-        sync(); // (freeing device memory waits for the device; be explicit about the batch in flight)
-        dfree(st.d_bases);
-        st.bases_cap = bytes + bytes / 4 + 64;
-        dmalloc(st.d_bases, st.bases_cap);
-    }
-    if (n_reads + 1 > st.reads_cap) {
-        sync();
-        dfree(st.d_offsets);
-        st.reads_cap = n_reads + n_reads / 4 + 1;
-        dmalloc(st.d_offsets, st.reads_cap);
-    }
-    if (hb.packed && hb.n_npos > st.npos_cap) {
-        sync();
-        dfree(st.d_npos);
-        st.npos_cap = hb.n_npos + hb.n_npos / 4 + 16;
-        dmalloc(st.d_npos, st.npos_cap);
-    }
-    HIPCHK(hipMemcpyAsync(st.d_bases, hb.bases, bytes, hipMemcpyHostToDevice, copy_stream_));
-    HIPCHK(hipMemcpyAsync(st.d_offsets, offsets, (n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, copy_stream_));
-    if (hb.packed && hb.n_npos) HIPCHK(hipMemcpyAsync(st.d_npos, hb.npos, hb.n_npos * sizeof(uint64_t), hipMemcpyHostToDevice, copy_stream_));
+    ensure_stage(st, hb.payload_bytes(), n_reads, hb.packed ? hb.n_npos : 0);
+    const DeviceBatch b = copy_in(hb, st.d_bases, st.d_offsets, st.d_npos, copy_stream_);
     HIPCHK(hipEventRecord(st.copied, copy_stream_));
     HIPCHK(hipStreamWaitEvent(stream_, st.copied, 0));
-    if (hb.packed) map_device_packed(reinterpret_cast<const uint32_t*>(st.d_bases), st.d_offsets, n_reads, n_bases, hb.n_npos ? st.d_npos : nullptr, hb.n_npos, nullptr,
-        nullptr, stream_, true);
-    else map_device_async(st.d_bases, st.d_offsets, n_reads, n_bases, nullptr, nullptr, stream_);
+    map(b, nullptr, nullptr, stream_, true);
     HIPCHK(hipEventSynchronize(st.copied)); // the caller's block is free again; the kernels run on
 }
 

@@ -29,47 +29,44 @@ public:
     hipStream_t stream() const { return stream_; }
     void set_params(const MapParams& p);
 
-    // Map one batch that is already resident in HBM.  d_bases must be 16-byte aligned.  Coverage is
-    // accumulated into d_covg (u32[2*n_knodes]) and d_prg_reads (u32[n_prgs]); nullptr selects the
-    // context's own accumulators.  The candidate sequences return once the batch is complete; the generic one is asynchronous on
-    // `stream` except for one 16-byte read-back of the hit count between the sketch and the sort.
-    void map_device(const uint8_t* d_bases, const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases,
-        uint32_t* d_covg, uint32_t* d_prg_reads, hipStream_t stream);
-
-    // The same batch without the host waiting for it: the launch sequence is queued on `stream` and the call returns; the
-    // read-back the sequence ends with (buffer overflow flags, reads left to the generic pipeline, counters) is looked at
-    // while the NEXT batch runs -- by the next map_device_async, or by sync() and everything that reads results -- so that
-    // back-to-back batches leave no gap on the device (measured on 10 M x 150 bp: ~50 us of host round trip per 0.7 ms
-    // batch).  The caller keeps d_bases / d_offsets / the accumulators of a batch valid and unchanged until the call after
-    // the next one returns, or sync() does (a batch whose candidate buffers overflowed is run again from them).
-    // The filtered sequence and the direct sequence in its candidate form (two lanes in turn); everything else falls back to map_device.
-    void map_device_async(const uint8_t* d_bases, const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases,
-        uint32_t* d_covg, uint32_t* d_prg_reads, hipStream_t stream);
-    void sync(); // completes the batch map_device_async left in flight and waits for its stream
-    // The same two entries for a batch in the 2-bit packed form (kernels.h SketchArgs::packed): d_words = u32[ceil(n_bases / 16)], 8-byte
-    // aligned; d_npos = the n_npos ascending positions of the bases that are not ACGTacgt (may be null when n_npos == 0).  The filtered
-    // sequence reads the words directly; the direct sequences get an ASCII expansion made on the device (packed.hip).
-    void map_device_packed(const uint32_t* d_words, const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases, const uint64_t* d_npos, uint64_t n_npos,
-        uint32_t* d_covg, uint32_t* d_prg_reads, hipStream_t stream, bool deferred);
+    // One batch that is resident in HBM, in either form.  packed: d_bases points at the 2-bit words (kernels.h SketchArgs::packed), u32[ceil(n_bases / 16)],
+    // and d_npos at the n_npos ascending positions of the bases that are not ACGTacgt (may be null when n_npos == 0).  What a host batch becomes
+    // once it is copied, what keep_reads keeps, and what every launch function is told about its input.
+    struct DeviceBatch {
+        const uint8_t* d_bases = nullptr;
+        const uint64_t* d_offsets = nullptr;
+        uint64_t n_reads = 0, n_bases = 0;
+        bool packed = false;
+        const uint64_t* d_npos = nullptr;
+        uint64_t n_npos = 0;
+    };
+    // Map such a batch.  d_bases must be 16-byte aligned.  Coverage is accumulated into d_covg (u32[2*n_knodes]) and d_prg_reads (u32[n_prgs]);
+    // nullptr selects the context's own accumulators, a null stream its own stream.  The filtered sequence reads packed words directly; the
+    // direct sequences get an ASCII expansion made on the device (packed.hip).
+    // deferred == false: the candidate sequences return once the batch is complete; the generic one is asynchronous on `stream` except for
+    // one 16-byte read-back of the hit count between the sketch and the sort.
+    // deferred == true: the launch sequence is queued on `stream` and the call returns; the read-back the sequence ends with (buffer overflow
+    // flags, reads left to the generic pipeline, counters) is looked at while the NEXT batch runs -- by the next deferred map, or by sync() and
+    // everything that reads results -- so that back-to-back batches leave no gap on the device (measured on 10 M x 150 bp: ~50 us of host
+    // round trip per 0.7 ms batch).  The caller keeps the batch's buffers and the accumulators valid and unchanged until the call after the
+    // next one returns, or sync() does (a batch whose candidate buffers overflowed is run again from them).  The filtered sequence and the
+    // direct sequence in its candidate form (two lanes in turn) have this form; everything else, and a batch of empty reads, runs as if
+    // deferred were false and then waits for the stream.
+    void map(const DeviceBatch& b, uint32_t* d_covg, uint32_t* d_prg_reads, hipStream_t stream, bool deferred);
+    void sync(); // completes the batch a deferred map left in flight and waits for its stream
+    // what map refuses a batch for, checked without touching anything: the only place that throws these errors
+    static void check(const DeviceBatch& b);
 
     // Depth cap (drprg_hip_set_max_covg; the running total is kept by the context, capi.cpp): where a device batch reaches `target` bases.
     // n_reads = the smallest i in [1, n_reads] with d_offsets[i] >= target (n_reads if there is none), n_bases = d_offsets[i], n_npos = how
-    // many of the batch's listed positions lie below that.  Completes the batch map_device_async left in flight, runs covg_cut_kernel on
-    // `stream` and waits for it: called for the one batch that crosses the cap, never for a batch that cannot reach it.
-    // what map_device* refuses a batch for, checked without touching anything (throws the same errors)
-    static void check_device_batch(const void* d_bases, const void* d_offsets, uint64_t n_reads, const void* d_npos, uint64_t n_npos, bool packed);
+    // many of the batch's listed positions lie below that.  Completes the batch a deferred map left in flight, runs covg_cut_kernel on
+    // `stream` and waits for it: called for the one batch that crosses the cap, never for a batch that cannot reach it.  Refuses what
+    // check() refuses; a batch without reads has no cut (all zero).
     struct CutPoint {
         uint64_t n_reads, n_bases, n_npos;
     };
-    CutPoint find_cut(const uint64_t* d_offsets, uint64_t n_reads, uint64_t target, const uint64_t* d_npos, uint64_t n_npos, hipStream_t stream);
+    CutPoint find_cut(const DeviceBatch& b, uint64_t target, hipStream_t stream);
 
-    // Map a host batch (copies through pinned staging buffers, then map_device on the own accumulators).
-    void map_host(const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads);
-    // The same without waiting for the kernels: the copy to the device runs on a copy stream into one of two staging sets, the
-    // launch sequence is queued behind it (map_device_async) and the call returns as soon as the COPY is done -- the host block
-    // may be reused then -- so that the next block's copy overlaps this block's kernels.  sync() (or anything that reads
-    // results) completes what is in flight.  Sequences without a deferred form fall back to map_host.
-    void map_host_async(const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads);
     // ASCII -> packed on the device (harnesses: bench.py packs its synthetic batch; tests).  Returns the number of non-ACGT bases; their
     // positions are in d_npos, ascending, if there are at most npos_cap of them.  Synchronises `stream`.
     uint64_t pack_on_device(const uint8_t* d_bases, uint64_t n_bases, uint32_t* d_words, uint64_t* d_npos, uint64_t npos_cap, hipStream_t stream);
@@ -84,24 +81,21 @@ public:
         uint64_t n_bases() const { return offsets[n_reads]; }
         uint64_t payload_bytes() const { return packed ? ((n_bases() + 15) / 16) * 4 : n_bases(); }
     };
+    // Map a host batch (copied into a staging set, then map on the own accumulators).
     void map_host(const HostBatch& b);
+    // The same without waiting for the kernels: the copy to the device runs on a copy stream into one of two staging sets, the
+    // launch sequence is queued behind it (a deferred map) and the call returns as soon as the COPY is done -- the host block
+    // may be reused then -- so that the next block's copy overlaps this block's kernels.  sync() (or anything that reads
+    // results) completes what is in flight.  Sequences without a deferred form fall back to map_host.
     void map_host_async(const HostBatch& b);
     // Reads that stay in HBM (off by default).  keep_reads(max_bytes > 0): from now on map_host_async copies every block into
     // device memory of its own instead of a staging set and leaves it there -- at most max_bytes of it; one byte more and
     // everything kept is dropped and the staging sets are back.  kept_complete(): every read mapped since keep_reads() /
     // reset_coverage() is among kept().  What they are for: select_reads_with_anchors below (the pile-up of `discover` without a
     // second pass over the file) and mapping the same reads again against another index (map_kept_from).
-    struct KeptBatch {
-        const uint8_t* d_bases; // (packed: the words)
-        const uint64_t* d_offsets;
-        uint64_t n_reads, n_bases;
-        bool packed = false;
-        const uint64_t* d_npos = nullptr;
-        uint64_t n_npos = 0;
-    };
     void keep_reads(uint64_t max_bytes);
     bool kept_complete() const { return kept_cap_ > 0 && !kept_broken_; }
-    const std::vector<KeptBatch>& kept() const { return kept_; }
+    const std::vector<DeviceBatch>& kept() const { return kept_; }
     uint64_t kept_bytes() const { return kept_bytes_; }
     void drop_kept();
     // Every kept read that holds one of `anchors` (k-mers of length A <= 31 packed 2 bits per base, A=0 .. T=3, first base in the
@@ -134,7 +128,7 @@ public:
     void device_tables(uint64_t out[6]) const;
 
     // timing of the dominant kernel (HIP events on the launch stream), for bench.py
-    // is the batch queued by map_device_async (not yet completed) accumulating into these buffers?
+    // is the batch queued by a deferred map (not yet completed) accumulating into these buffers?
     bool pending_writes_to(const uint32_t* covg, const uint32_t* prg_reads) const
     {
         return pending_.active && ((covg && pending_.covg == covg) || (prg_reads && pending_.prg_reads == prg_reads));
@@ -157,7 +151,7 @@ private:
     void ensure_workspace(uint64_t hit_capacity);
     // What one batch of a candidate sequence (filtered: sketch_filter -> verify -> read_cluster; direct: sketch -> read_cluster from the
     // tile slices) keeps to itself: candidate buffers, per-sequence counters, and events on the batch's stream (done: behind the batch's
-    // read-back; t0 / t1 around the dominant kernel).  Two lanes: map_device_async takes them in turn, the synchronous calls use lane 0.
+    // read-back; t0 / t1 around the dominant kernel).  Two lanes: deferred maps take them in turn, the synchronous calls use lane 0.
     struct Lane {
         hipEvent_t done = nullptr, t0 = nullptr, t1 = nullptr;
         uint64_t raw_capacity = 0;
@@ -171,30 +165,18 @@ private:
         dev::FilterWork fw {};
     };
     enum { L_HITS = 0, L_OVERFLOW = 1, L_MAXLEN = 2, L_UNSORTED = 3, L_COMPLEX = 4, L_CHUNK = 5, L_MINIMIZERS = 6, L_FT_CLOCK = 7 /* five words: FilterBuffers::class_clock */, L_N = 12 };
-    // What makes a device batch a packed one (2-bit words instead of bytes): where its non-ACGT positions are.  Passed along with the batch
-    // pointer to everything that touches the batch (nullptr: ASCII) and kept in Batch for the deferred completion -- until round 5 the
-    // batch's ADDRESS was looked up in a map, which every free and every recycled address had to keep honest.
-    struct PackedInfo {
-        const uint64_t* d_npos = nullptr;
-        uint64_t n_npos = 0;
-    };
-    // A batch of one of the two candidate sequences, as its launch and finish functions see it
+    // A batch of one of the two candidate sequences, as its launch and finish functions see it.  The description travels with the batch (a
+    // re-run or its leftover reads see the format it came in) -- until round 5 the batch's ADDRESS was looked up in a map, which every free
+    // and every recycled address had to keep honest.
     struct Batch {
+        DeviceBatch batch;
         bool active = false;
         bool direct = false; // the direct sequence's candidate form (else the filtered sequence)
         int lane = 0;        // lanes_[lane] (direct: and tsets_[lane])
-        const uint8_t* d_bases = nullptr;
-        const uint64_t* d_offsets = nullptr;
-        uint32_t n_reads = 0;
-        uint64_t n_bases = 0;
         uint32_t *covg = nullptr, *prg_reads = nullptr;
         hipStream_t stream = nullptr;
-        bool packed = false; // the batch is 2-bit words ...
-        PackedInfo pk {};    // ... with these non-ACGT positions
-        const PackedInfo* pkp() const { return packed ? &pk : nullptr; }
     };
-    Batch make_batch(int lane, const uint8_t* d_bases, const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases, uint32_t* covg, uint32_t* prg_reads,
-        hipStream_t stream, const PackedInfo* pk) const;
+    Batch make_batch(int lane, const DeviceBatch& batch, uint32_t* covg, uint32_t* prg_reads, hipStream_t stream) const;
     void ensure_lanes();
     void grow_lane(Lane& lane, uint64_t raw_capacity);
     void free_lane(Lane& lane);
@@ -206,22 +188,17 @@ private:
     void direct_launch(const Batch& b);
     bool direct_finish(const Batch& b, int attempt);
     void leftovers(const Batch& b);
-    void run_batch(const uint8_t* d_bases, const uint64_t* d_offsets, uint32_t n_reads, uint64_t n_bases,
-        uint32_t* d_covg, uint32_t* d_prg_reads, hipStream_t stream, const PackedInfo* pk);
+    void run_batch(const DeviceBatch& batch, uint32_t* d_covg, uint32_t* d_prg_reads, hipStream_t stream);
     void cluster_hits(const uint64_t* d_offsets, uint32_t n_hits, bool ordered, unsigned long long* d_unsorted, uint32_t* d_covg,
         uint32_t* d_prg_reads, hipStream_t stream);
-    dev::SketchArgs sketch_args(const uint8_t* d_bases, const uint64_t* d_offsets, uint32_t n_reads, uint64_t n_bases, const PackedInfo* pk) const;
-    // d_bases itself, or -- for a packed batch -- its ASCII expansion in scratch buffer `slot` (0 / 1: the two tile sets of the direct
+    dev::SketchArgs sketch_args(const DeviceBatch& batch) const;
+    // the batch itself, or -- for a packed batch -- its ASCII expansion in scratch buffer `slot` (0 / 1: the two tile sets of the direct
     // sequence's candidate form, 2: the generic sequence), made on `stream`
-    const uint8_t* ascii_view(int slot, const uint8_t* d_bases, uint64_t n_bases, hipStream_t stream, const PackedInfo* pk);
+    DeviceBatch ascii_view(int slot, const DeviceBatch& batch, hipStream_t stream);
     uint8_t* d_unpacked_[3] = { nullptr, nullptr, nullptr };
     unsigned long long* d_pack_count_ = nullptr; // pack_on_device's counter word
     unsigned long long *h_cut_ = nullptr, *h_cut_dev_ = nullptr; // find_cut's three result words: pinned, and their device address
     uint64_t unpacked_cap_[3] = { 0, 0, 0 };
-    void map_device_impl(const uint8_t* d_bases, const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases, uint32_t* d_covg, uint32_t* d_prg_reads,
-        hipStream_t stream, const PackedInfo* pk);
-    void map_device_async_impl(const uint8_t* d_bases, const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases, uint32_t* d_covg, uint32_t* d_prg_reads,
-        hipStream_t stream, const PackedInfo* pk);
     void read_counters(hipStream_t stream);
     void note_kernel_time(hipEvent_t t0, hipEvent_t t1);
     // deferred completion: the batches take the two lanes in turn; `pending_` is the batch whose read-back nobody has looked at yet
@@ -308,14 +285,8 @@ private:
     void free_tile_set(TileSet& t);
     void ensure_tile_workspace(TileSet& t, uint32_t n_tiles, uint32_t tile_cap);
     size_t temp_bytes_ = 0;
-    // host staging
-    uint8_t* h_bases_ = nullptr;
-    uint64_t* h_offsets_ = nullptr;
-    uint8_t* d_bases_ = nullptr;
-    uint64_t* d_offsets_ = nullptr;
-    uint64_t* d_npos_ = nullptr;
-    uint64_t stage_bases_cap_ = 0, stage_reads_cap_ = 0, stage_npos_cap_ = 0;
-    // map_host_async: two staging sets taken in turn, their copies on a stream of their own
+    // host staging: device buffers a host batch is copied into.  map_host has one set; map_host_async takes two in turn, their copies on
+    // a stream of their own
     struct Stage {
         uint8_t* d_bases = nullptr;
         uint64_t* d_offsets = nullptr;
@@ -323,7 +294,12 @@ private:
         uint64_t bases_cap = 0, reads_cap = 0, npos_cap = 0;
         hipEvent_t copied = nullptr;
     };
-    Stage stage_[2];
+    // room in `st` for a batch of these sizes (n_npos: 0 for an ASCII batch); a buffer that is too small is replaced by one a quarter larger
+    void ensure_stage(Stage& st, uint64_t payload_bytes, uint64_t n_reads, uint64_t n_npos);
+    Stage stage_[2], stage_sync_;
+    // queues the copies of a host batch to these device addresses (d_npos: used when the batch lists positions) on `stream`; returns the
+    // batch they will hold
+    DeviceBatch copy_in(const HostBatch& hb, uint8_t* d_bases, uint64_t* d_offsets, uint64_t* d_npos, hipStream_t stream);
     int stage_next_ = 0;
     hipStream_t copy_stream_ = nullptr;
     // sketch_filter_kernel's tile shares, followed from batch to batch ([0] ASCII, [1] packed input; {0}: the launcher's built-in ones so far)
@@ -334,7 +310,7 @@ private:
     std::vector<std::pair<void*, size_t>> kept_arenas_;
     uint8_t* arena_at_ = nullptr;
     size_t arena_left_ = 0;
-    std::vector<KeptBatch> kept_;
+    std::vector<DeviceBatch> kept_;
     uint64_t kept_cap_ = 0, kept_bytes_ = 0;
     bool kept_broken_ = false, in_keep_call_ = false;
     hipEvent_t kept_copied_ = nullptr;
