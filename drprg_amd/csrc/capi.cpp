@@ -1033,6 +1033,33 @@ int drprg_hip_discover_reads(drprg_hip_ctx* ctx, const char* reads_path, const c
     API_END(ctx)
 }
 
+int drprg_hip_select_reads(drprg_hip_ctx* ctx, const uint64_t* anchors, uint64_t n_anchors, uint32_t A, uint64_t window_bytes, uint8_t* bases,
+    uint64_t bases_cap, uint64_t* offsets, uint64_t* ids, uint64_t reads_cap, uint64_t out[2])
+{
+    API_BEGIN(ctx)
+    if (!out || (n_anchors && !anchors)) throw Error(DRPRG_EINVAL, "null argument");
+    if (A == 0 || A > 31) throw Error(DRPRG_EINVAL, "anchor length must be 1..31");
+    if (!reads_resident(ctx, nullptr)) throw Error(DRPRG_ENODATA, "not every read of the sample is resident");
+    const std::vector<uint64_t> kmers(anchors, anchors + n_anchors);
+    std::vector<uint8_t> sel_bases;
+    std::vector<uint64_t> sel_offsets(1, 0), sel_ids;
+    uint64_t first_block = 0; // (ids count the kept blocks through all the mappers, like drprg_hip_resident_info)
+    for (Mapper* m : mappers_of(ctx)) {
+        const size_t had = sel_ids.size();
+        m->select_reads_with_anchors(kmers, A, sel_bases, sel_offsets, &sel_ids, window_bytes);
+        for (size_t i = had; i < sel_ids.size(); ++i) sel_ids[i] += first_block << 32;
+        first_block += m->kept().size();
+    }
+    out[0] = sel_ids.size();
+    out[1] = sel_bases.size();
+    if (sel_ids.size() > reads_cap || sel_bases.size() > bases_cap) throw Error(DRPRG_EOVERFLOW, "the selected reads do not fit the caller's buffers");
+    if ((!sel_bases.empty() && !bases) || !offsets || (!sel_ids.empty() && !ids)) throw Error(DRPRG_EINVAL, "null output buffer");
+    if (!sel_bases.empty()) std::memcpy(bases, sel_bases.data(), sel_bases.size());
+    std::memcpy(offsets, sel_offsets.data(), sel_offsets.size() * sizeof(uint64_t));
+    if (!sel_ids.empty()) std::memcpy(ids, sel_ids.data(), sel_ids.size() * sizeof(uint64_t));
+    API_END(ctx)
+}
+
 int drprg_hip_update_prg(drprg_hip_ctx* ctx, const char* out_prg, uint32_t* n_applied)
 {
     API_BEGIN(ctx)

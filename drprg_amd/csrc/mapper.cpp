@@ -1089,7 +1089,8 @@ uint64_t Mapper::map_kept_from(const Mapper& other)
     return n;
 }
 
-void Mapper::select_reads_with_anchors(std::vector<uint64_t> anchors, uint32_t A, std::vector<uint8_t>& bases, std::vector<uint64_t>& offsets)
+void Mapper::select_reads_with_anchors(std::vector<uint64_t> anchors, uint32_t A, std::vector<uint8_t>& bases, std::vector<uint64_t>& offsets,
+    std::vector<uint64_t>* ids, uint64_t window_bytes)
 {
     if (!kept_complete()) throw Error(DRPRG_ENODATA, "not every read of the sample is resident");
     if (A == 0 || A > 31) throw Error(DRPRG_EINVAL, "anchor length must be 1..31");
@@ -1134,7 +1135,7 @@ void Mapper::select_reads_with_anchors(std::vector<uint64_t> anchors, uint32_t A
     // window's expansion takes the scratch: the scratch is the largest window, not the sample (up to 128 Gbases can stay
     // resident packed; expanding all of them at once needed that much memory again, with no way back to the file pass).
     auto expanded = [](const DeviceBatch& kb) -> uint64_t { return kb.packed ? (kb.n_bases + 15) / 16 * 16 + 64 : 0; };
-    constexpr uint64_t WINDOW_BYTES = 1ull << 30;
+    const uint64_t WINDOW_BYTES = window_bytes ? window_bytes : SELECT_WINDOW_BYTES;
     std::vector<std::pair<size_t, size_t>> windows; // [first batch, one past the last)
     uint64_t scratch_need = 0;
     for (size_t b = 0; b < kept_.size();) {
@@ -1202,6 +1203,8 @@ void Mapper::select_reads_with_anchors(std::vector<uint64_t> anchors, uint32_t A
         (void)hipFree(d_out);
         HIPCHK(e);
         for (size_t i = 0; i < list.size(); ++i) offsets.push_back(offsets.back() + list[i].len);
+        if (ids)
+            for (size_t i = 0; i < list.size(); ++i) ids->push_back((uint64_t)list[i].batch << 32 | list[i].read);
     }
 }
 

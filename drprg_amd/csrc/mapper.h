@@ -100,8 +100,11 @@ public:
     void drop_kept();
     // Every kept read that holds one of `anchors` (k-mers of length A <= 31 packed 2 bits per base, A=0 .. T=3, first base in the
     // high bits) -- and possibly a few that do not -- appended to bases / offsets (offsets[0] = 0 is written when offsets is
-    // empty), in batch and read order.  anchor_scan.hip.
-    void select_reads_with_anchors(std::vector<uint64_t> anchors, uint32_t A, std::vector<uint8_t>& bases, std::vector<uint64_t>& offsets);
+    // empty), in batch and read order.  anchor_scan.hip.  ids (may be null): kept batch << 32 | read in the batch of every read appended.
+    // window_bytes: how much ASCII expansion of packed batches one window holds (0: SELECT_WINDOW_BYTES).
+    static constexpr uint64_t SELECT_WINDOW_BYTES = 1ull << 30;
+    void select_reads_with_anchors(std::vector<uint64_t> anchors, uint32_t A, std::vector<uint8_t>& bases, std::vector<uint64_t>& offsets,
+        std::vector<uint64_t>* ids = nullptr, uint64_t window_bytes = 0);
     // maps the batches another Mapper of the same device keeps (it must outlive the call); returns the reads mapped
     uint64_t map_kept_from(const Mapper& other);
 

@@ -177,6 +177,24 @@ class Context:
         _check(lib.drprg_hip_resident_info(self._h, out), self._h)
         return dict(complete=bool(out[0]), bytes=int(out[1]), blocks=int(out[2]), last_discover_from_hbm=bool(out[3]))
 
+    def select_reads(self, anchors, A, window_bytes=0):
+        """the resident reads in which one of `anchors` (k-mers of A bases as integers, 2 bits per base, A 0 C 1 G 2 T 3, first base high)
+        starts -- the selection discover_reads runs on the device (drprg_hip_select_reads); returns (bases u8, offsets u64, ids u64 =
+        kept block << 32 | read in the block)"""
+        anchors = np.ascontiguousarray(anchors, dtype=np.uint64)
+        out = (C.c_uint64 * 2)()
+        offsets = np.zeros(1, np.uint64)
+        rc = lib.drprg_hip_select_reads(self._h, _ptr(anchors), anchors.size, int(A), int(window_bytes), None, 0, _ptr(offsets), None, 0, out)
+        if rc == 0:  # nothing selected
+            return np.zeros(0, np.uint8), offsets, np.zeros(0, np.uint64)
+        if rc != -75:  # -EOVERFLOW: out holds the sizes needed
+            _check(rc, self._h)
+        n_reads, n_bases = int(out[0]), int(out[1])
+        bases, offsets, ids = np.zeros(n_bases, np.uint8), np.zeros(n_reads + 1, np.uint64), np.zeros(n_reads, np.uint64)
+        _check(lib.drprg_hip_select_reads(self._h, _ptr(anchors), anchors.size, int(A), int(window_bytes), _ptr(bases), n_bases, _ptr(offsets),
+                                          _ptr(ids), n_reads, out), self._h)
+        return bases, offsets, ids
+
     def counters(self):
         out = (C.c_uint64 * 8)()
         _check(lib.drprg_hip_counters(self._h, out), self._h)

@@ -244,6 +244,21 @@ int drprg_hip_discover_reads(drprg_hip_ctx* ctx, const char* reads_path, const c
 int drprg_hip_keep_reads(drprg_hip_ctx* ctx, uint64_t max_bytes);
 int drprg_hip_map_resident(drprg_hip_ctx* ctx, drprg_hip_ctx* from);
 int drprg_hip_resident_info(drprg_hip_ctx* ctx, uint64_t out[4]);
+/* The read selection drprg_hip_discover_reads uses when the reads are resident, on its own: for every device of the context, in order,
+ * every kept read in which a k-mer of `anchors` STARTS (anchors: n_anchors k-mers of A bases, 2 bits per base, A 0 C 1 G 2 T 3, first base
+ * in the high bits; any order, duplicates allowed).  A block's reads are one base stream: read r of a block is returned iff for some p with
+ * offsets[r] <= p < offsets[r + 1] and p + A <= the block's bases, stream[p .. p + A) is all ACGTacgt and, upper-cased, an anchor -- the
+ * k-mer may run on into the reads behind r (the caller's own scan of the returned reads decides; no read that holds an anchor is lost).
+ *   A read is returned once.  Reads come in block order, then read order, device after device.  A block kept in the packed form returns
+ *   upper case (non-ACGT bytes as N), an ASCII block the bytes of the file.
+ *   bases[bases_cap], offsets[reads_cap + 1] (offsets[0] = 0), ids[reads_cap]: ids[i] = kept block << 32 | read in that block, the blocks
+ *   counted through the devices as drprg_hip_resident_info counts them.  out[0] = reads, out[1] = bases selected, always; -EOVERFLOW
+ *   (-75) with nothing copied when either buffer is too small -- call with both caps 0 for the sizes.
+ *   window_bytes: packed blocks are expanded to ASCII for the scan a window of consecutive blocks at a time, as many as expand into
+ *   window_bytes (a larger block alone); 0 = the built-in 1 GB, what discover uses.  The result does not depend on it.
+ *   -ENODATA (-61) unless every read mapped since the last reset is resident; -EINVAL for A outside 1..31. */
+int drprg_hip_select_reads(drprg_hip_ctx* ctx, const uint64_t* anchors, uint64_t n_anchors, uint32_t A, uint64_t window_bytes, uint8_t* bases,
+    uint64_t bases_cap, uint64_t* offsets, uint64_t* ids, uint64_t reads_cap, uint64_t out[2]);
 
 /* What MakePrg::update does in the reference (/root/reference/src/lib.rs:279-456: mafft --add of the consensus with the novel
  * variants, then make_prg from_msa) for a host without make_prg / mafft: writes the context's PRG file again with every novel variant
