@@ -118,6 +118,7 @@ struct KernelTimer {
 uint32_t sketch_tile_eval(int halo);
 uint32_t sketch_n_tiles(uint64_t n_bases, int halo);
 hipError_t launch_sketch_probe(const SketchArgs& a, bool wide_hash, hipStream_t stream, KernelTimer timer = {});
+bool probe_compile_time_window(int k, int w); // 32-bit keys: sketch_probe_kernel<uint32_t, k, w> serves these, the sequential scan the rest
 // first read that starts at or after the first staged base (tile * t_eval - halo) of every tile
 hipError_t launch_tile_first_read(const uint64_t* offsets, uint32_t n_reads, int t_eval, int halo, uint32_t n_tiles, uint32_t* out,
     hipStream_t stream);

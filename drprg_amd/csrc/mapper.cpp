@@ -766,7 +766,11 @@ void Mapper::buffer_info(uint64_t out[6])
     out[2] = regrows_hits_;
     out[3] = raw;
     out[4] = hit_capacity_;
-    out[5] = 0;
+    // which sketch form serves this context: 1 sketch_wave_kernel, 2 / 3 / 4 sketch_probe_kernel with its compile-time window / its sequential
+    // scan on u32 / u64 keys; the filtered sequence: 10 small tier (level 0 on 12-mers), 11 levels 1+2 alone (k < 15), 12 middle tier
+    if (use_filter_) out[5] = use_mid_ ? 12 : (bloom0_wbits_ ? 10 : 11);
+    else if (use_direct_cands_ && dev::direct_uses_wave_form(params_.k, params_.w, wide_hash_, sw_.direct_lds)) out[5] = 1;
+    else out[5] = wide_hash_ ? 4 : (dev::probe_compile_time_window(params_.k, params_.w) ? 2 : 3);
 }
 
 // sketch_filter_kernel's four wave classes should end together (sketch_filter.hip: a SIMD issues for its oldest wave first).  How far apart they
@@ -1321,7 +1325,11 @@ void Mapper::device_tables(uint64_t out[6]) const
 {
     out[4] = use_mid_ ? (uint64_t)MID_BITMAP_WORDS * 4 + ((uint64_t)16 << midc_wbits_) : 0; // global-memory (L2) tiers of the filter
     if (!use_mid_ && use_filter_ && d_blkc_) out[4] = (uint64_t)16 << blkc_wbits_; // (small tier: the second stage's block filter, what packed batches are tested against)
-    out[5] = 0;
+    // which sketch form serves this context: 1 sketch_wave_kernel, 2 / 3 / 4 sketch_probe_kernel with its compile-time window / its sequential
+    // scan on u32 / u64 keys; the filtered sequence: 10 small tier (level 0 on 12-mers), 11 levels 1+2 alone (k < 15), 12 middle tier
+    if (use_filter_) out[5] = use_mid_ ? 12 : (bloom0_wbits_ ? 10 : 11);
+    else if (use_direct_cands_ && dev::direct_uses_wave_form(params_.k, params_.w, wide_hash_, sw_.direct_lds)) out[5] = 1;
+    else out[5] = wide_hash_ ? 4 : (dev::probe_compile_time_window(params_.k, params_.w) ? 2 : 3);
     out[0] = d_pbloom_ ? (uint64_t)1 << pbloom_wbits_ : 0;
     out[1] = ((uint64_t)1 << table_bits_) * (wide_hash_ ? 16 : 12);
     out[2] = bloom_wbits_ ? ((uint64_t)4 << bloom_wbits_) + (bloom0_wbits_ ? ((uint64_t)4 << bloom0_wbits_) + ((uint64_t)4 << BLOOMR_WBITS) : 0) : 0;

@@ -401,6 +401,8 @@ uint32_t sketch_n_tiles(uint64_t n_bases, int halo)
     return (uint32_t)((n_bases + t_eval - 1) / t_eval);
 }
 
+bool probe_compile_time_window(int k, int w) { return k == 15 && (w == 11 || w == 14); }
+
 hipError_t launch_sketch_probe(const SketchArgs& a, bool wide_hash, hipStream_t stream, KernelTimer timer)
 {
     if (a.n_bases == 0) return hipSuccess;
@@ -409,9 +411,9 @@ hipError_t launch_sketch_probe(const SketchArgs& a, bool wide_hash, hipStream_t 
     const dim3 g(grid), b(SK_THREADS);
     if (wide_hash)
         launch_timed(timer, sketch_probe_kernel<uint64_t, 0, 0>, g, b, 0, stream, a);
-    else if (a.k == 15 && a.w == 11)
+    else if (probe_compile_time_window(a.k, a.w) && a.w == 11)
         launch_timed(timer, sketch_probe_kernel<uint32_t, 15, 11>, g, b, 0, stream, a);
-    else if (a.k == 15 && a.w == 14)
+    else if (probe_compile_time_window(a.k, a.w))
         launch_timed(timer, sketch_probe_kernel<uint32_t, 15, 14>, g, b, 0, stream, a);
     else
         launch_timed(timer, sketch_probe_kernel<uint32_t, 0, 0>, g, b, 0, stream, a);

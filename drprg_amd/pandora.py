@@ -293,7 +293,7 @@ class Context:
         out = (C.c_uint64 * 6)()
         _check(lib.drprg_hip_device_tables(self._h, out), self._h)
         return dict(pbloom_words=int(out[0]), table_bytes=int(out[1]), lds_filter_bytes=int(out[2]), kernel=int(out[3]),
-                    l2_filter_bytes=int(out[4]))
+                    l2_filter_bytes=int(out[4]), sketch_form=int(out[5]))
 
     def export_index(self):
         """Flat index (sorted keys + CSR records) in the layout oracle/oracle.c consumes."""

@@ -326,7 +326,9 @@ int drprg_hip_index_export(const drprg_hip_ctx* ctx, uint64_t* keys, uint32_t* r
  * (0: the table fits the L2, no tier), out[1] = bytes of the open-addressed probe table (keys + slot records), out[2] = bytes
  * of the LDS-resident filter arrays of the prefiltered sequence (0: index too large / k > 15), out[3] = sequence in use,
  * out[4] = bytes of the filter tiers of that sequence that live in global memory (L2-resident: the middle tier's bitmap and
- * code filter; the small tier's block filter, which is the second stage for packed batches; 0 otherwise), out[5] = 0 (reserved). */
+ * code filter; the small tier's block filter, which is the second stage for packed batches; 0 otherwise), out[5] = the sketch
+ * form that serves the context: 1 sketch_wave_kernel; sketch_probe_kernel with 2 its compile-time window, 3 its sequential scan on
+ * 32-bit keys, 4 on 64-bit keys; of the prefiltered sequence 10 the small tier, 11 levels 1+2 alone (k < 15), 12 the middle tier. */
 int drprg_hip_device_tables(drprg_hip_ctx* ctx, uint64_t out[6]);
 
 /* Local-graph introspection of PRG `prg` (node intervals are offsets into the PRG string, markers and their

@@ -54,6 +54,36 @@ EDGE_PRGS = {
     "lower_case": "acgtacgtttgaccagtaggaccattagaccagattacaggatc 5 g 6 t 5 aggtaccagatagacagat",
 }
 WK = [(11, 15), (14, 15), (3, 5), (1, 7), (5, 9), (19, 21), (11, 31)]
+EVEN_WK = [(11, 14), (5, 8), (7, 12), (11, 20), (11, 30), (1, 14)]  # even k: a k-mer can be its own reverse complement
+
+# Repeats: strings on which two k-mers of one window share a canonical hash, so that "ties kept, each reported once" and
+# strand = (fwd <= rc) decide which k-mers are nodes.  _F1 .. _F3 are fixed random flanks, _X a fixed random 30-mer.
+_F1, _F2, _F3 = "GTCAGCATTGACCGTAGGCTTACGATCCGATAGCTAGGCATCAGTCCGATTGACA", "TGGACTCATTCGAGCGTATTCAGGACGATCTTGACGCATGCTAGTTCAGGCATACG", \
+    "CCTAGATCGGACTTAGCATGCCATAGGCTTAACGTGCATCAGTAGCTTGCAGGA"
+_X = "GATTACCGTTAGCACGGATTCAGGCTTACA"
+_REVCOMP = str.maketrans("ACGT", "TGCA")
+_rc = lambda s: s.translate(_REVCOMP)[::-1]
+_UNITS = "CAGTTGACCATGG"  # the tandem repeat of period d is its first d bases, repeated (each prefix has full period: no shorter one)
+REPEAT_PRGS = {
+    "homopolymer": _F1 + "A" * 40 + _F2,
+    "ac_repeat": _F1 + "AC" * 30 + _F2,
+    "cgg_repeat_with_a_site_inside": _F1 + "CGG" * 12 + " 5 CGG 6 CGA 5 " + "CGG" * 12 + _F2,
+    "period_7": _F1 + "GACTTCA" * 9 + _F2,
+    "perfect_palindrome": _F1 + _X + _rc(_X) + _F2,
+    "hairpin_with_a_3_base_loop": _F1 + _X + "ACG" + _rc(_X) + _F2,
+    "direct_repeat": _F1 + _X + _F2[:20] + _X + _F3,
+    "a_120": "A" * 120,
+    "site_inside_a_t_run": _F1 + "T" * 20 + " 5 T 6 C 5 " + "T" * 20 + _F2,
+    "alleles_differ_by_one_repeat_unit": _F1 + "GACCT" * 5 + " 5 GACCT 6 GACCTGACCT 5 " + "GACCT" * 5 + _F2,
+    "empty_allele_inside_a_homopolymer": _F1 + "G" * 20 + " 5 G 6  5 " + "G" * 20 + _F2,
+    "at_repeat_then_cg_repeat": _F1 + "AT" * 20 + _F2 + "CG" * 20 + _F3,
+}
+REPEAT_PRGS.update({f"tandem_period_{d}": _F1 + (_UNITS[:d] * (60 // d + 1)) + _F2 for d in range(1, 13)})  # every period 1 .. w + 1, w = 11
+
+
+def run_prgs(w, k):
+    """a run of exactly k + w - 2, k + w - 1 and k + w identical bases (w - 1, w and w + 1 tied k-mers) between the flanks"""
+    return {f"run_of_{n}": _F1 + "C" * n + _F2 for n in (k + w - 2, k + w - 1, k + w)}
 
 
 @pytest.mark.parametrize("name", sorted(EDGE_PRGS))
@@ -166,6 +196,28 @@ def test_written_kmer_graphs_equal_the_oracle_graphs(tmp_path, oracle):
             assert p == idx["rec_prg"][lo + j] and strand == idx["rec_strand"][lo + j]
             assert node == idx["rec_knode"][lo + j] - idx["knode_base"][p]
             assert [(int(a), int(b)) for a, b in re.findall(r"\[(\d+), (\d+)\)", m.group(2))] == graph_paths[p][node - 1]
+
+
+@pytest.mark.parametrize("w,k", WK + EVEN_WK)
+def test_repeat_prgs(tmp_path, oracle, w, k):
+    """product index == oracle index on every repeat; on the strings without sites the k-mer nodes are exactly the read sketch's
+    minimizers; every minimum of every window of every walk is a node"""
+    prgs = dict(REPEAT_PRGS, **run_prgs(w, k))
+    names = list(prgs)
+    ctx, _ = _product_index(tmp_path, names, [prgs[n] for n in names], w, k)
+    _assert_same_index(ctx.export_index(), oracle.build_index([prgs[n] for n in names], w, k))
+    ctx.close()
+    tied = 0
+    for name in names:
+        g = oracle.sketch_prg(prgs[name], w, k, paths=True, walk_check=True)
+        assert g["walk"]["missing"] == 0, name
+        tied += len(g["hash"]) - len(set(g["hash"].tolist()))
+        if " " not in prgs[name]:
+            h, p, s = oracle.sketch(prgs[name], w, k)
+            assert [pp[0][0] for pp in g["paths"]] == p.tolist(), name
+            assert np.array_equal(g["hash"], h) and np.array_equal(g["strand"], s), name
+            assert g["min_path_len"] == len(h) + 1, name
+    assert tied > 100  # (the nodes that share their hash with another node of the same PRG: what random sequence never has)
 
 
 def test_every_read_side_minimizer_of_a_prg_walk_is_a_node(oracle):
