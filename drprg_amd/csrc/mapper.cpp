@@ -13,26 +13,6 @@
 
 namespace drprg {
 
-#define HIPCHK(x)                                                                                              \
-    do {                                                                                                       \
-        hipError_t e_ = (x);                                                                                   \
-        if (e_ != hipSuccess)                                                                                  \
-            throw Error(e_ == hipErrorOutOfMemory ? DRPRG_ENOMEM : DRPRG_EIO,                                  \
-                std::string("HIP error: ") + hipGetErrorString(e_) + " at " + __FILE__ + ":" + std::to_string(__LINE__)); \
-    } while (0)
-
-template <typename T> static void dmalloc(T*& p, size_t n)
-{
-    p = nullptr;
-    if (n == 0) n = 1;
-    HIPCHK(hipMalloc((void**)&p, n * sizeof(T)));
-}
-template <typename T> static void dfree(T*& p)
-{
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
-
 // counter slots
 enum { C_HITS = 0, C_MINIMIZERS = 1, C_CLUSTERS_KEPT = 2, C_HITS_KEPT = 3, C_OVERFLOW = 4, C_MAXLEN = 5, C_UNSORTED = 6, C_COMPLEX = 7, C_N = 8 };
 // reads up to this length get their hits reordered per read (read_sort_kernel); longer ones take the radix sort
@@ -41,6 +21,97 @@ constexpr uint64_t READ_SORT_MAX_LEN = 512;
 // added on top is kept for the small chunks of a dynamic schedule's last round (sketch_filter.hip launch_sketch_filter)
 constexpr uint64_t FILTER_BASES_PER_ENTRY = 48;
 
+void Mapper::IndexTables::fill(const FlatIndex& idx, bool wide_hash, uint64_t mid_max_records)
+{
+    const size_t nslot = idx.slot_key.size(), nrec = idx.rec_prg.size();
+    // what the kernels cannot address is refused here, on the host index, before the first allocation
+    if (idx.min_path_len.size() > dev::MAX_PRGS) throw Error(DRPRG_EOVERFLOW, "more than " + std::to_string(dev::MAX_PRGS) + " PRGs");
+    for (size_t i = 0; i < nslot; ++i)
+        if (idx.slot_cnt[i] && idx.min_path_len[idx.rec_prg[idx.slot_off[i]]] >= (1u << 20))
+            throw Error(DRPRG_EOVERFLOW, "a PRG's shortest k-mer path has 2^20 nodes or more");
+    if (idx.total_knodes() >= (1u << 31)) throw Error(DRPRG_EOVERFLOW, "too many k-mer nodes");
+    table_bits = idx.table_bits;
+    if (wide_hash) {
+        std::vector<uint64_t> k64(nslot);
+        for (size_t i = 0; i < nslot; ++i) k64[i] = idx.slot_cnt[i] ? idx.slot_key[i] : ~0ULL; // empty-slot sentinel
+        slot_key.upload(reinterpret_cast<const unsigned char*>(k64.data()), nslot * sizeof(uint64_t));
+    } else {
+        std::vector<uint32_t> k32(nslot);
+        for (size_t i = 0; i < nslot; ++i) k32[i] = idx.slot_cnt[i] ? (uint32_t)idx.slot_key[i] : 0xFFFFFFFFu; // empty-slot sentinel
+        slot_key.upload(reinterpret_cast<const unsigned char*>(k32.data()), nslot * sizeof(uint32_t));
+    }
+    std::vector<uint2> rec(nslot);
+    std::vector<uint4> first(nslot);
+    for (size_t i = 0; i < nslot; ++i) {
+        rec[i] = make_uint2(idx.slot_off[i], idx.slot_cnt[i]);
+        first[i] = make_uint4(idx.slot_off[i], idx.slot_cnt[i], 0u, 0u);
+        if (idx.slot_cnt[i]) {
+            const uint32_t r = idx.slot_off[i], prg = idx.rec_prg[r];
+            first[i].z = (idx.rec_knode_global[r] << 1) | idx.rec_strand[r];
+            first[i].w = prg | (idx.min_path_len[prg] << 12);
+        }
+    }
+    slot_rec.upload(rec);
+    slot_first.upload(first);
+    std::vector<uint32_t> rk(nrec);
+    std::vector<uint16_t> rp(nrec);
+    for (size_t i = 0; i < nrec; ++i) {
+        rk[i] = (idx.rec_knode_global[i] << 1) | idx.rec_strand[i];
+        rp[i] = (uint16_t)idx.rec_prg[i];
+    }
+    rec_knode.upload(rk);
+    rec_prg.upload(rp);
+    min_path_len.upload(idx.min_path_len);
+    h_min_path_len = idx.min_path_len;
+    prg_thr.alloc(idx.min_path_len.size()); // (filled by set_params)
+    // Bloom tier of the direct kernel: only when keys + slot records outgrow an XCD's 4 MB L2 (<= ~4 keys per 32-bit word)
+    if (nslot * (size_t)(wide_hash ? 16 : 12) > ((size_t)2 << 20)) {
+        pbloom_wbits = 10;
+        while (((size_t)4 << pbloom_wbits) < idx.keys.size()) ++pbloom_wbits;
+        std::vector<uint32_t> pb((size_t)1 << pbloom_wbits, 0);
+        for (uint64_t key : idx.keys) {
+            const uint32_t m = dev::pbloom_mix(key);
+            pb[dev::pbloom_word(m, pbloom_wbits)] |= dev::pbloom_bits(m);
+        }
+        pbloom.upload(pb);
+    }
+    bloom_wbits = idx.bloom_wbits;
+    if (bloom_wbits) bloom.upload(idx.bloom);
+    bloom0_wbits = bloom_wbits ? idx.bloom0_wbits : 0;
+    if (bloom0_wbits) {
+        bloom0.upload(idx.bloom0);
+        bloom0f.upload(idx.bloom0f);
+        bloomr.upload(idx.bloomr);
+        if (idx.blkc_wbits) { // the second stage for the L2 (round 6)
+            blkc_wbits = idx.blkc_wbits;
+            blkc.upload(idx.blkc);
+        }
+    }
+    if (idx.midc_wbits && nrec <= mid_max_records) { // (switches.h: where the direct sequence takes over)
+        midc_wbits = idx.midc_wbits;
+        mid0_bits = idx.mid0_bits;
+        mid0.upload(idx.mid0);
+        mid_bitmap.upload(idx.mid_bitmap);
+        midc.upload(idx.midc);
+    }
+    HIPCHK(hipStreamSynchronize(nullptr)); // every table is on the device before a kernel of a non-blocking stream can ask for it
+}
+
+dev::BloomTables Mapper::IndexTables::bloom_tables(bool mid) const
+{
+    dev::BloomTables bt { bloom.data(), bloom_wbits, bloom0.data(), bloom0_wbits, bloomr.data(), bloom0f.data() };
+    bt.blkc = blkc.data();
+    bt.blkc_wbits = blkc_wbits;
+    if (mid) {
+        bt.mid0 = mid0.data();
+        bt.mid_bitmap = mid_bitmap.data();
+        bt.midc = midc.data();
+        bt.midc_wbits = midc_wbits;
+        bt.mid0_bits = mid0_bits;
+    }
+    return bt;
+}
+
 Mapper::Mapper(const FlatIndex& idx, const MapParams& p, int device) : device_(device)
 {
     int ndev = 0;
@@ -48,123 +119,25 @@ Mapper::Mapper(const FlatIndex& idx, const MapParams& p, int device) : device_(d
         throw Error(DRPRG_ENODEV, "no HIP device is visible: the drprg hot path has no CPU fallback");
     if (device < 0 || device >= ndev) throw Error(DRPRG_ENODEV, "HIP device " + std::to_string(device) + " does not exist");
     HIPCHK(hipSetDevice(device_));
-    HIPCHK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
     n_prgs_ = (uint32_t)idx.min_path_len.size();
     n_knodes_ = idx.total_knodes();
-    table_bits_ = idx.table_bits;
-    bloom_wbits_ = idx.bloom_wbits;
-    if (n_prgs_ > dev::MAX_PRGS) throw Error(DRPRG_EOVERFLOW, "more than " + std::to_string(dev::MAX_PRGS) + " PRGs");
-    set_params(p);
-
-    const size_t nslot = idx.slot_key.size();
-    if (wide_hash_) {
-        std::vector<uint64_t> k64(nslot);
-        for (size_t i = 0; i < nslot; ++i) k64[i] = idx.slot_cnt[i] ? idx.slot_key[i] : ~0ULL; // empty-slot sentinel
-        uint64_t* k = nullptr;
-        dmalloc(k, nslot);
-        HIPCHK(hipMemcpy(k, k64.data(), nslot * sizeof(uint64_t), hipMemcpyHostToDevice));
-        d_slot_key_ = k;
-    } else {
-        std::vector<uint32_t> k32(nslot);
-        for (size_t i = 0; i < nslot; ++i) k32[i] = idx.slot_cnt[i] ? (uint32_t)idx.slot_key[i] : 0xFFFFFFFFu; // empty-slot sentinel
-        uint32_t* k = nullptr;
-        dmalloc(k, nslot);
-        HIPCHK(hipMemcpy(k, k32.data(), nslot * sizeof(uint32_t), hipMemcpyHostToDevice));
-        d_slot_key_ = k;
-    }
-    std::vector<uint2> rec(nslot);
-    for (size_t i = 0; i < nslot; ++i) rec[i] = make_uint2(idx.slot_off[i], idx.slot_cnt[i]);
-    dmalloc(d_slot_rec_, nslot);
-    HIPCHK(hipMemcpy(d_slot_rec_, rec.data(), nslot * sizeof(uint2), hipMemcpyHostToDevice));
-    {
-        std::vector<uint4> first(nslot);
-        for (size_t i = 0; i < nslot; ++i) {
-            first[i] = make_uint4(idx.slot_off[i], idx.slot_cnt[i], 0u, 0u);
-            if (idx.slot_cnt[i]) {
-                const uint32_t r = idx.slot_off[i], prg = idx.rec_prg[r];
-                if (idx.min_path_len[prg] >= (1u << 20)) throw Error(DRPRG_EOVERFLOW, "a PRG's shortest k-mer path has 2^20 nodes or more");
-                first[i].z = (idx.rec_knode_global[r] << 1) | idx.rec_strand[r];
-                first[i].w = prg | (idx.min_path_len[prg] << 12);
-            }
-        }
-        dmalloc(d_slot_first_, nslot);
-        HIPCHK(hipMemcpy(d_slot_first_, first.data(), nslot * sizeof(uint4), hipMemcpyHostToDevice));
-    }
-    const size_t nrec = idx.rec_prg.size();
-    std::vector<uint32_t> rk(nrec);
-    std::vector<uint16_t> rp(nrec);
-    for (size_t i = 0; i < nrec; ++i) {
-        rk[i] = (idx.rec_knode_global[i] << 1) | idx.rec_strand[i];
-        rp[i] = (uint16_t)idx.rec_prg[i];
-    }
-    if (n_knodes_ >= (1u << 31)) throw Error(DRPRG_EOVERFLOW, "too many k-mer nodes");
-    dmalloc(d_rec_knode_, nrec);
-    dmalloc(d_rec_prg_, nrec);
-    HIPCHK(hipMemcpy(d_rec_knode_, rk.data(), nrec * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_rec_prg_, rp.data(), nrec * sizeof(uint16_t), hipMemcpyHostToDevice));
-    dmalloc(d_min_path_len_, (size_t)n_prgs_);
-    HIPCHK(hipMemcpy(d_min_path_len_, idx.min_path_len.data(), n_prgs_ * sizeof(uint32_t), hipMemcpyHostToDevice));
-    h_min_path_len_ = idx.min_path_len;
-    dmalloc(d_prg_thr_, (size_t)n_prgs_);
-    // Bloom tier of the direct kernel: only when keys + slot records outgrow an XCD's 4 MB L2 (<= ~4 keys per 32-bit word)
-    if (nslot * (size_t)(wide_hash_ ? 16 : 12) > ((size_t)2 << 20)) {
-        pbloom_wbits_ = 10;
-        while (((size_t)4 << pbloom_wbits_) < idx.keys.size()) ++pbloom_wbits_;
-        std::vector<uint32_t> pb((size_t)1 << pbloom_wbits_, 0);
-        for (uint64_t key : idx.keys) {
-            const uint32_t m = dev::pbloom_mix(key);
-            pb[dev::pbloom_word(m, pbloom_wbits_)] |= dev::pbloom_bits(m);
-        }
-        dmalloc(d_pbloom_, pb.size());
-        HIPCHK(hipMemcpy(d_pbloom_, pb.data(), pb.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
-    bloom_wbits_ = idx.bloom_wbits;
-    if (bloom_wbits_) {
-        dmalloc(d_bloom_, idx.bloom.size());
-        HIPCHK(hipMemcpy(d_bloom_, idx.bloom.data(), idx.bloom.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
-    bloom0_wbits_ = bloom_wbits_ ? idx.bloom0_wbits : 0;
-    if (bloom0_wbits_) {
-        dmalloc(d_bloom0_, idx.bloom0.size());
-        HIPCHK(hipMemcpy(d_bloom0_, idx.bloom0.data(), idx.bloom0.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        dmalloc(d_bloom0f_, idx.bloom0f.size());
-        HIPCHK(hipMemcpy(d_bloom0f_, idx.bloom0f.data(), idx.bloom0f.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        dmalloc(d_bloomr_, idx.bloomr.size());
-        HIPCHK(hipMemcpy(d_bloomr_, idx.bloomr.data(), idx.bloomr.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        if (idx.blkc_wbits) { // the second stage for the L2 (round 6)
-            blkc_wbits_ = idx.blkc_wbits;
-            dmalloc(d_blkc_, idx.blkc.size());
-            HIPCHK(hipMemcpy(d_blkc_, idx.blkc.data(), idx.blkc.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        }
-    }
-    if (idx.midc_wbits) {
-        if (idx.rec_prg.size() <= sw_.mid_max_records) { // (switches.h: where the direct sequence takes over)
-            midc_wbits_ = idx.midc_wbits;
-            mid0_bits_ = idx.mid0_bits;
-            dmalloc(d_mid0_, idx.mid0.size());
-            HIPCHK(hipMemcpy(d_mid0_, idx.mid0.data(), idx.mid0.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-            dmalloc(d_mid_bitmap_, idx.mid_bitmap.size());
-            HIPCHK(hipMemcpy(d_mid_bitmap_, idx.mid_bitmap.data(), idx.mid_bitmap.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-            dmalloc(d_midc_, idx.midc.size());
-            HIPCHK(hipMemcpy(d_midc_, idx.midc.data(), idx.midc.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        }
-    }
+    tables_.fill(idx, p.k > 15, sw_.mid_max_records);
+    stream_.create();
     HIPCHK(hipDeviceGetAttribute(&n_cus_, hipDeviceAttributeMultiprocessorCount, device_));
-    HIPCHK(hipStreamSynchronize(nullptr)); // every table is on the device before a kernel of a non-blocking stream can ask for it
-    set_params(p); // again: the kernel choice depends on the filter being available
+    set_params(p); // (behind the tables: the kernel choice depends on the filter being available)
     if (sw_.min_capacity) // (tests: small batches at the production ratio, or below it to force regrows)
         min_capacity_ = std::max<uint64_t>(MIN_CAPACITY_CLAMP, std::min<uint64_t>(*sw_.min_capacity, 1ull << 30));
     // ONE allocation [coverage | reads per PRG]: the sample's whole additive state is one contiguous u32 vector, so the
     // collective of the path is a single ncclAllReduce / ncclReduce over it (capi.cpp)
-    dmalloc(d_covg_, 2 * (size_t)n_knodes_ + (size_t)n_prgs_);
-    d_prg_reads_ = d_covg_ + 2 * (size_t)n_knodes_;
-    dmalloc(d_counters_, (size_t)C_N);
-    HIPCHK(hipHostMalloc((void**)&h_counters_, C_N * sizeof(unsigned long long), hipHostMallocDefault));
-    HIPCHK(hipEventCreate(&ev0_));
-    HIPCHK(hipEventCreate(&ev1_));
+    d_covg_.alloc(2 * (size_t)n_knodes_ + (size_t)n_prgs_);
+    d_counters_.alloc(C_N);
+    h_counters_.alloc(C_N);
+    ev0_.create(true);
+    ev1_.create(true);
     reset_coverage();
 }
 
+// The owners free everything; what is left to say is the order: nothing is in flight when they do.
 Mapper::~Mapper()
 {
     (void)hipSetDevice(device_);
@@ -173,40 +146,14 @@ Mapper::~Mapper()
     } catch (...) { // (nothing to report to from a destructor)
     }
     (void)hipDeviceSynchronize();
-    for (Lane& lane : lanes_) free_lane(lane);
-    if (stream_) (void)hipStreamSynchronize(stream_);
-    dfree(d_slot_rec_); dfree(d_slot_first_); dfree(d_rec_knode_); dfree(d_rec_prg_); dfree(d_min_path_len_); dfree(d_prg_thr_);
-    if (d_slot_key_) (void)hipFree(d_slot_key_);
-    dfree(d_covg_); d_prg_reads_ = nullptr; dfree(d_counters_);
-    for (int i = 0; i < 3; ++i) dfree(d_unpacked_[i]);
-    dfree(d_pack_count_);
-    dfree(d_key_a_); dfree(d_key_b_); dfree(d_val_a_); dfree(d_val_b_);
-    dfree(d_head_); dfree(d_scan_); dfree(d_cstart_); dfree(d_order_); dfree(d_clusters_);
-    if (d_temp_) (void)hipFree(d_temp_);
-    for (TileSet& t : tsets_) free_tile_set(t);
-    dfree(d_bloom_); dfree(d_bloom0_); dfree(d_bloom0f_); dfree(d_bloomr_); dfree(d_pbloom_); dfree(d_mid0_); dfree(d_mid_bitmap_); dfree(d_midc_); dfree(d_blkc_);
-    for (Stage* st : { &stage_[0], &stage_[1], &stage_sync_ }) {
-        dfree(st->d_bases); dfree(st->d_offsets); dfree(st->d_npos);
-        if (st->copied) (void)hipEventDestroy(st->copied);
-    }
-    dfree(d_peer_tmp_);
-    for (auto& a : kept_arenas_) (void)hipFree(a.first);
-    if (kept_copied_) (void)hipEventDestroy(kept_copied_);
-    if (copy_stream_) (void)hipStreamDestroy(copy_stream_);
-    if (h_counters_) (void)hipHostFree(h_counters_);
-    if (h_cut_) (void)hipHostFree(h_cut_);
-    if (ev0_) (void)hipEventDestroy(ev0_);
-    if (ev1_) (void)hipEventDestroy(ev1_);
-    if (stream_) (void)hipStreamDestroy(stream_);
 }
 
 // Zeroes device memory and returns when it IS zero.  hipMemset on device memory runs on the null stream and may return before it
 // has run; this class's streams are non-blocking, so nothing they do waits for the null stream -- a freshly allocated cand_pos1
 // was zeroed AFTER the verification kernel had written the first batch into it (cold start, several contexts busy on one device:
 // one run in ten lost 5 % of its clusters; tools/stress_multi.py).
-void Mapper::zero_now(void* p, int value, size_t bytes)
+void Mapper::zero_now(void* p, size_t bytes)
 {
-    (void)value;
     HIPCHK(hipMemsetAsync(p, 0, bytes, stream_));
     HIPCHK(hipStreamSynchronize(stream_));
 }
@@ -270,23 +217,23 @@ void Mapper::set_params(const MapParams& p)
     // validate everything before any state changes: a refused call leaves the previous parameters in force
     if (p.k < 1 || p.k > 31) throw Error(DRPRG_EINVAL, "k must be in [1,31]");
     if (p.w < 1 || p.w > 1024) throw Error(DRPRG_EINVAL, "w must be in [1,1024]");
-    const bool filter_ok = (bloom_wbits_ != 0 || midc_wbits_ != 0) && p.k <= 15 && p.w <= 16;
+    const bool filter_ok = (tables_.bloom_wbits != 0 || tables_.midc_wbits != 0) && p.k <= 15 && p.w <= 16;
     if (p.kernel_mode < 0 || p.kernel_mode > 3) throw Error(DRPRG_EINVAL, "kernel must be 0 (auto), 1, 2 or 3");
     if (p.kernel_mode == 2 && !filter_ok)
         throw Error(DRPRG_EINVAL, "the Bloom-prefiltered kernel needs k <= 15, w <= 16 and an index small enough for its filter tiers");
     params_ = p;
     wide_hash_ = p.k > 15;
     halo_ = std::max(16, ((p.w - 1 + 15) / 16) * 16);
-    if (d_prg_thr_) { // the PRG's share of the cluster size threshold, in the oracle's own arithmetic
+    { // the PRG's share of the cluster size threshold, in the oracle's own arithmetic
         std::vector<uint32_t> thr(n_prgs_);
         const double fraction = params_.cluster_fraction();
-        for (uint32_t i = 0; i < n_prgs_; ++i) thr[i] = (uint32_t)((double)h_min_path_len_[i] * fraction);
+        for (uint32_t i = 0; i < n_prgs_; ++i) thr[i] = (uint32_t)((double)tables_.h_min_path_len[i] * fraction);
         HIPCHK(hipSetDevice(device_));
-        HIPCHK(hipMemcpy(d_prg_thr_, thr.data(), n_prgs_ * sizeof(uint32_t), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(tables_.prg_thr.data(), thr.data(), n_prgs_ * sizeof(uint32_t), hipMemcpyHostToDevice));
         HIPCHK(hipStreamSynchronize(nullptr)); // (the copies of this file run on the null stream, which the non-blocking streams do not wait for)
     }
     use_filter_ = p.kernel_mode == 2 || (p.kernel_mode == 0 && filter_ok);
-    use_mid_ = use_filter_ && bloom_wbits_ == 0;
+    use_mid_ = use_filter_ && tables_.bloom_wbits == 0;
     use_direct_cands_ = p.kernel_mode == 3 || (p.kernel_mode == 0 && !filter_ok);
 }
 
@@ -294,8 +241,8 @@ void Mapper::reset_coverage(bool new_sample)
 {
     sync();
     HIPCHK(hipSetDevice(device_));
-    HIPCHK(hipMemsetAsync(d_covg_, 0, (2 * (size_t)n_knodes_ + (size_t)n_prgs_) * sizeof(uint32_t), stream_)); // [coverage | reads per PRG]
-    HIPCHK(hipMemsetAsync(d_counters_, 0, C_N * sizeof(unsigned long long), stream_));
+    HIPCHK(hipMemsetAsync(d_covg_.data(), 0, d_covg_.bytes(), stream_)); // [coverage | reads per PRG]
+    HIPCHK(hipMemsetAsync(d_counters_.data(), 0, d_counters_.bytes(), stream_));
     HIPCHK(hipStreamSynchronize(stream_));
     tot_reads_ = tot_bases_ = tot_hits_ = tot_leftover_ = tot_minimizers_ = 0;
     for (auto& sh : ft_share_) // (a reset context starts from the launcher's built-in tile shares again: ADVICE r05)
@@ -306,59 +253,38 @@ void Mapper::reset_coverage(bool new_sample)
 
 void Mapper::ensure_workspace(uint64_t cap)
 {
-    if (cap <= hit_capacity_) return;
+    if (cap <= hit_capacity()) return;
     if (cap >= (1ull << 31)) throw Error(DRPRG_EOVERFLOW, "more than 2^31 minimizer hits in one batch; map smaller batches");
-    dfree(d_key_a_); dfree(d_key_b_); dfree(d_val_a_); dfree(d_val_b_);
-    dfree(d_head_); dfree(d_scan_); dfree(d_cstart_); dfree(d_order_); dfree(d_clusters_);
-    if (d_temp_) (void)hipFree(d_temp_);
-    d_temp_ = nullptr;
-    hit_capacity_ = cap;
-    dmalloc(d_key_a_, cap); dmalloc(d_key_b_, cap); dmalloc(d_val_a_, cap); dmalloc(d_val_b_, cap);
-    dmalloc(d_head_, cap); dmalloc(d_scan_, cap); dmalloc(d_cstart_, cap + 1); dmalloc(d_order_, cap);
-    dmalloc(d_clusters_, cap);
-    temp_bytes_ = std::max(dev::sort_temp_bytes((uint32_t)cap), dev::scan_temp_bytes((uint32_t)cap));
-    HIPCHK(hipMalloc(&d_temp_, temp_bytes_ ? temp_bytes_ : 1));
-}
-
-void Mapper::free_lane(Lane& lane)
-{
-    dfree(lane.raw_pos); dfree(lane.cand_info); dfree(lane.cand_pos1); dfree(lane.cand_rec); dfree(lane.small);
-    dfree(lane.d_scratch);
-    if (lane.h_scratch) (void)hipHostFree(lane.h_scratch);
-    lane.h_scratch = nullptr;
-    lane.h_scratch_dev = nullptr;
-    for (hipEvent_t* e : { &lane.done, &lane.t0, &lane.t1 })
-        if (*e) (void)hipEventDestroy(*e);
-    lane = Lane();
+    d_key_a_.alloc(cap); d_key_b_.alloc(cap); d_val_a_.alloc(cap); d_val_b_.alloc(cap);
+    d_head_.alloc(cap); d_scan_.alloc(cap); d_cstart_.alloc(cap + 1); d_order_.alloc(cap);
+    d_clusters_.alloc(cap);
+    d_temp_.alloc(std::max(dev::sort_temp_bytes((uint32_t)cap), dev::scan_temp_bytes((uint32_t)cap)));
 }
 
 void Mapper::grow_lane(Lane& lane, uint64_t cap)
 {
-    if (cap <= lane.raw_capacity) return;
+    if (cap <= lane.capacity()) return;
     if (cap >= (1ull << 31)) throw Error(DRPRG_EOVERFLOW, "more than 2^31 candidate k-mers in one batch; map smaller batches");
-    dfree(lane.raw_pos); dfree(lane.cand_info); dfree(lane.cand_pos1); dfree(lane.cand_rec);
-    lane.raw_capacity = cap;
-    dmalloc(lane.raw_pos, cap); dmalloc(lane.cand_info, cap); dmalloc(lane.cand_pos1, cap); dmalloc(lane.cand_rec, cap);
+    lane.raw_pos.alloc(cap); lane.cand_info.alloc(cap); lane.cand_pos1.alloc(cap); lane.cand_rec.alloc(cap);
     // the slices form of the direct sequence uses cand_pos1 as an array of "handled" marks (mark = a batch's epoch): fresh device
     // memory may hold anything, including a value some later epoch of this or an earlier Mapper takes
-    zero_now(lane.cand_pos1, 0, cap * sizeof(uint32_t));
+    zero_now(lane.cand_pos1.data(), lane.cand_pos1.bytes());
 }
 
 // Both lanes' events, counters and their pinned mirror; the candidate buffers grow with the batches (grow_lane).
 void Mapper::ensure_lanes()
 {
     for (Lane& lane : lanes_) {
-        if (lane.h_scratch_dev) continue; // (the last thing a lane gets)
-        HIPCHK(hipEventCreateWithFlags(&lane.done, hipEventDisableTiming));
-        HIPCHK(hipEventCreate(&lane.t0));
-        HIPCHK(hipEventCreate(&lane.t1));
-        dmalloc(lane.small, dev::filter_small_words());
-        zero_now(lane.small, 0, dev::filter_small_words() * sizeof(uint32_t)); // (the superblock counts start at zero; every sequence leaves them so)
-        dmalloc(lane.d_scratch, (size_t)L_N);
-        HIPCHK(hipHostMalloc((void**)&lane.h_scratch, L_N * sizeof(unsigned long long), hipHostMallocDefault));
-        zero_now(lane.d_scratch, 0, L_N * sizeof(unsigned long long));
+        if (lane.h_scratch) continue; // (the last thing a lane gets)
+        lane.done.create(false);
+        lane.t0.create(true);
+        lane.t1.create(true);
+        lane.small.alloc(dev::filter_small_words());
+        zero_now(lane.small.data(), lane.small.bytes()); // (the superblock counts start at zero; every sequence leaves them so)
+        lane.d_scratch.alloc(L_N);
+        zero_now(lane.d_scratch.data(), lane.d_scratch.bytes());
         lane.scratch_zero = true;
-        HIPCHK(hipHostGetDevicePointer((void**)&lane.h_scratch_dev, lane.h_scratch, 0));
+        lane.h_scratch.alloc(L_N);
     }
 }
 
@@ -383,6 +309,47 @@ void Mapper::launch(const Batch& b)
     HIPCHK(hipEventRecord(lanes_[b.lane].done, b.stream));
 }
 
+void Mapper::count_on_lane(dev::SketchArgs& a, const Lane& lane) const
+{
+    a.n_hits = lane.d_scratch.data() + L_HITS;
+    a.n_minimizers = lane.d_scratch.data() + L_MINIMIZERS;
+    a.overflow = reinterpret_cast<uint32_t*>(lane.d_scratch.data() + L_OVERFLOW);
+}
+
+dev::FilterBuffers Mapper::filter_buffers(const Lane& lane) const
+{
+    return dev::FilterBuffers { lane.raw_pos.data(), lane.cand_info.data(), lane.cand_pos1.data(), lane.cand_rec.data(), lane.capacity(), lane.small.data(),
+        lane.d_scratch.data() + L_MAXLEN };
+}
+
+dev::ReadClusterArgs Mapper::read_cluster_args(const Batch& b) const
+{
+    const Lane& lane = lanes_[b.lane];
+    dev::ReadClusterArgs rc {};
+    rc.prg_min_path_len = tables_.min_path_len.data();
+    rc.fraction = params_.cluster_fraction();
+    rc.min_cluster_size = params_.min_cluster_size;
+    rc.max_diff = params_.max_diff;
+    rc.n_prgs = n_prgs_;
+    rc.covg = b.covg;
+    rc.prg_reads = b.prg_reads;
+    rc.n_clusters_kept = d_counters_.data() + C_CLUSTERS_KEPT;
+    rc.n_hits_kept = d_counters_.data() + C_HITS_KEPT;
+    rc.n_complex = lane.d_scratch.data() + L_COMPLEX;
+    rc.chunk_counter = reinterpret_cast<uint32_t*>(lane.d_scratch.data() + L_CHUNK);
+    return rc;
+}
+
+dev::KernelTimer Mapper::kernel_timer(hipEvent_t t0, hipEvent_t t1) const
+{
+    dev::KernelTimer timer;
+    if (timing_) { // events bracket the dominant kernel only
+        timer.begin = t0;
+        timer.end = t1;
+    }
+    return timer;
+}
+
 // One filtered sequence, asynchronous on the batch's stream: kernels, then the lane's counters to its pinned mirror, then the counters
 // cleared again behind the copy (so that the next batch starts with its first kernel instead of a memset).
 void Mapper::filter_launch(const Batch& b)
@@ -390,45 +357,16 @@ void Mapper::filter_launch(const Batch& b)
     Lane& lane = lanes_[b.lane];
     // (a deferred batch: this lane's previous batch was completed by the call before this one; growing frees its buffers, which waits for the device)
     grow_lane(lane, std::max<uint64_t>(min_capacity_, b.batch.n_bases / FILTER_BASES_PER_ENTRY));
-    if (!lane.scratch_zero) HIPCHK(hipMemsetAsync(lane.d_scratch, 0, L_N * sizeof(unsigned long long), b.stream));
+    if (!lane.scratch_zero) HIPCHK(hipMemsetAsync(lane.d_scratch.data(), 0, lane.d_scratch.bytes(), b.stream));
     lane.scratch_zero = false;
-    dev::SketchArgs a = sketch_args(b.batch);
-    a.n_hits = &lane.d_scratch[L_HITS];
-    a.n_minimizers = &lane.d_scratch[L_MINIMIZERS];
-    a.overflow = reinterpret_cast<uint32_t*>(&lane.d_scratch[L_OVERFLOW]);
-    dev::FilterBuffers fb { lane.raw_pos, lane.cand_info, lane.cand_pos1, lane.cand_rec, lane.raw_capacity, lane.small, &lane.d_scratch[L_MAXLEN] };
-    fb.class_clock = &lane.d_scratch[L_FT_CLOCK]; // (unused when DRPRG_FT_SHARE pins the shares: then nothing adapts them)
+    dev::SketchArgs a = sketch_args(b.batch, nullptr);
+    count_on_lane(a, lane);
+    dev::FilterBuffers fb = filter_buffers(lane);
+    fb.class_clock = lane.d_scratch.data() + L_FT_CLOCK; // (unused when DRPRG_FT_SHARE pins the shares: then nothing adapts them)
     if (ft_share_[b.batch.packed ? 1 : 0][0]) fb.wave_share = ft_share_[b.batch.packed ? 1 : 0];
-    dev::BloomTables bt { d_bloom_, bloom_wbits_, d_bloom0_, bloom0_wbits_, d_bloomr_, d_bloom0f_ };
-    bt.blkc = d_blkc_;
-    bt.blkc_wbits = blkc_wbits_;
-    if (use_mid_) {
-        bt.mid0 = d_mid0_;
-        bt.mid_bitmap = d_mid_bitmap_;
-        bt.midc = d_midc_;
-        bt.midc_wbits = midc_wbits_;
-        bt.mid0_bits = mid0_bits_;
-    }
-    dev::ReadClusterArgs rc {};
-    rc.prg_min_path_len = d_min_path_len_;
-    rc.fraction = params_.cluster_fraction();
-    rc.min_cluster_size = params_.min_cluster_size;
-    rc.max_diff = params_.max_diff;
-    rc.n_prgs = n_prgs_;
-    rc.covg = b.covg;
-    rc.prg_reads = b.prg_reads;
-    rc.n_clusters_kept = &d_counters_[C_CLUSTERS_KEPT];
-    rc.n_hits_kept = &d_counters_[C_HITS_KEPT];
-    rc.n_complex = &lane.d_scratch[L_COMPLEX];
-    rc.chunk_counter = reinterpret_cast<uint32_t*>(&lane.d_scratch[L_CHUNK]);
-    dev::KernelTimer timer;
-    if (timing_) { // events bracket the dominant kernel only
-        timer.begin = lane.t0;
-        timer.end = lane.t1;
-    }
-    HIPCHK(dev::launch_sketch_filter(a, bt, n_cus_, fb, rc, lane.fw, sw_, b.stream, timer));
+    HIPCHK(dev::launch_sketch_filter(a, tables_.bloom_tables(use_mid_), n_cus_, fb, read_cluster_args(b), lane.fw, sw_, b.stream, kernel_timer(lane.t0, lane.t1)));
     // the counters to the pinned mirror and zero again behind it: one small kernel (rounds 1-4: a copy and two memsets)
-    HIPCHK(dev::launch_counters_home(lane.d_scratch, lane.h_scratch_dev, L_N, b.stream, dev::filter_super_counts(lane.small), dev::filter_super_words()));
+    HIPCHK(dev::launch_counters_home(lane.d_scratch.data(), lane.h_scratch.device_ptr(), L_N, b.stream, dev::filter_super_counts(lane.small.data()), dev::filter_super_words()));
     lane.scratch_zero = true;
 }
 
@@ -452,36 +390,36 @@ void Mapper::cluster_hits(const uint64_t* d_offsets, uint32_t n_hits, bool order
     uint32_t* prg_reads, hipStream_t stream)
 {
     if (n_hits == 0) return;
-    const uint64_t* s_key = d_key_b_;
-    const uint32_t* s_val = d_val_b_;
+    const uint64_t* s_key = d_key_b_.data();
+    const uint32_t* s_val = d_val_b_.data();
     if (ordered) {
-        HIPCHK(dev::launch_read_sort(d_key_a_, d_val_a_, n_hits, d_order_, hit_capacity_, d_unsorted, stream));
-        s_key = d_key_a_;
-        s_val = d_val_a_;
-    } else HIPCHK(dev::sort_hits(d_temp_, temp_bytes_, d_key_a_, d_key_b_, d_val_a_, d_val_b_, n_hits, stream));
-    HIPCHK(dev::launch_cluster_flags(s_key, n_hits, params_.max_diff, d_head_, d_scan_, d_temp_, temp_bytes_, stream));
-    HIPCHK(dev::launch_cluster_starts(d_head_, d_scan_, n_hits, d_cstart_, stream));
+        HIPCHK(dev::launch_read_sort(d_key_a_.data(), d_val_a_.data(), n_hits, d_order_.data(), hit_capacity(), d_unsorted, stream));
+        s_key = d_key_a_.data();
+        s_val = d_val_a_.data();
+    } else HIPCHK(dev::sort_hits(d_temp_.data(), d_temp_.size(), d_key_a_.data(), d_key_b_.data(), d_val_a_.data(), d_val_b_.data(), n_hits, stream));
+    HIPCHK(dev::launch_cluster_flags(s_key, n_hits, params_.max_diff, d_head_.data(), d_scan_.data(), d_temp_.data(), d_temp_.size(), stream));
+    HIPCHK(dev::launch_cluster_starts(d_head_.data(), d_scan_.data(), n_hits, d_cstart_.data(), stream));
     dev::ClusterArgs c {};
     c.key = s_key;
     c.val = s_val;
-    c.scan = d_scan_;
-    c.cstart = d_cstart_;
-    c.d_n_clusters = d_scan_ + (n_hits - 1);
+    c.scan = d_scan_.data();
+    c.cstart = d_cstart_.data();
+    c.d_n_clusters = d_scan_.data() + (n_hits - 1);
     c.offsets = d_offsets;
-    c.prg_min_path_len = d_min_path_len_;
-    c.clusters = d_clusters_;
-    c.order = d_order_;
+    c.prg_min_path_len = tables_.min_path_len.data();
+    c.clusters = d_clusters_.data();
+    c.order = d_order_.data();
     c.w = params_.w;
     c.fraction = params_.cluster_fraction();
     c.min_cluster_size = params_.min_cluster_size;
     c.covg = covg;
     c.prg_reads = prg_reads;
-    c.n_clusters_kept = &d_counters_[C_CLUSTERS_KEPT];
-    c.n_hits_kept = &d_counters_[C_HITS_KEPT];
+    c.n_clusters_kept = d_counters_.data() + C_CLUSTERS_KEPT;
+    c.n_hits_kept = d_counters_.data() + C_HITS_KEPT;
     HIPCHK(dev::launch_cluster_pipeline(c, n_hits, n_prgs_, stream));
 }
 
-dev::SketchArgs Mapper::sketch_args(const DeviceBatch& batch) const
+dev::SketchArgs Mapper::sketch_args(const DeviceBatch& batch, const TileSet* tiles) const
 {
     dev::SketchArgs a {};
     a.bases = batch.d_bases;
@@ -491,21 +429,21 @@ dev::SketchArgs Mapper::sketch_args(const DeviceBatch& batch) const
     a.w = params_.w;
     a.k = params_.k;
     a.halo = halo_;
-    a.slot_key = d_slot_key_;
-    a.slot_rec = d_slot_rec_;
-    a.slot_first = d_slot_first_;
-    a.table_bits = table_bits_;
-    a.rec_knode = d_rec_knode_;
-    a.rec_prg = d_rec_prg_;
-    a.tile_first_read = ts_->d_tile_first;
-    a.pbloom = d_pbloom_;
-    a.pbloom_wbits = pbloom_wbits_;
-    a.hit_key = d_key_a_;
-    a.hit_val = d_val_a_;
-    a.hit_capacity = hit_capacity_;
-    a.n_hits = &d_counters_[C_HITS];
-    a.n_minimizers = &d_counters_[C_MINIMIZERS];
-    a.overflow = reinterpret_cast<uint32_t*>(&d_counters_[C_OVERFLOW]);
+    a.slot_key = tables_.slot_key.data();
+    a.slot_rec = tables_.slot_rec.data();
+    a.slot_first = tables_.slot_first.data();
+    a.table_bits = tables_.table_bits;
+    a.rec_knode = tables_.rec_knode.data();
+    a.rec_prg = tables_.rec_prg.data();
+    a.tile_first_read = tiles ? tiles->d_tile_first.data() : nullptr;
+    a.pbloom = tables_.pbloom.data();
+    a.pbloom_wbits = tables_.pbloom_wbits;
+    a.hit_key = d_key_a_.data();
+    a.hit_val = d_val_a_.data();
+    a.hit_capacity = hit_capacity();
+    a.n_hits = d_counters_.data() + C_HITS;
+    a.n_minimizers = d_counters_.data() + C_MINIMIZERS;
+    a.overflow = reinterpret_cast<uint32_t*>(d_counters_.data() + C_OVERFLOW);
     a.packed = batch.packed ? 1 : 0; // (said by the caller, carried with the batch -- not looked up by its address)
     a.npos = batch.d_npos;
     a.n_npos = batch.n_npos;
@@ -516,16 +454,14 @@ Mapper::DeviceBatch Mapper::ascii_view(int slot, const DeviceBatch& batch, hipSt
 {
     if (!batch.packed) return batch;
     const uint64_t need = (batch.n_bases + 15) / 16 * 16 + 64;
-    if (need > unpacked_cap_[slot]) {
+    if (need > d_unpacked_[slot].size()) {
         sync(); // (a batch in flight may still read the old buffer)
         HIPCHK(hipStreamSynchronize(stream));
-        dfree(d_unpacked_[slot]);
-        unpacked_cap_[slot] = need + need / 4;
-        dmalloc(d_unpacked_[slot], unpacked_cap_[slot]);
+        d_unpacked_[slot].alloc(need + need / 4);
     }
-    HIPCHK(dev::launch_unpack(reinterpret_cast<const uint32_t*>(batch.d_bases), batch.n_bases, batch.d_npos, batch.n_npos, d_unpacked_[slot], stream));
+    HIPCHK(dev::launch_unpack(reinterpret_cast<const uint32_t*>(batch.d_bases), batch.n_bases, batch.d_npos, batch.n_npos, d_unpacked_[slot].data(), stream));
     DeviceBatch ascii;
-    ascii.d_bases = d_unpacked_[slot];
+    ascii.d_bases = d_unpacked_[slot].data();
     ascii.d_offsets = batch.d_offsets;
     ascii.n_reads = batch.n_reads;
     ascii.n_bases = batch.n_bases;
@@ -534,7 +470,7 @@ Mapper::DeviceBatch Mapper::ascii_view(int slot, const DeviceBatch& batch, hipSt
 
 void Mapper::read_counters(hipStream_t stream)
 {
-    HIPCHK(hipMemcpyAsync(h_counters_, d_counters_, C_N * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(h_counters_.data(), d_counters_.data(), d_counters_.bytes(), hipMemcpyDeviceToHost, stream));
     wait_stream(stream);
 }
 
@@ -553,48 +489,38 @@ void Mapper::leftovers(const Batch& b)
     Lane& lane = lanes_[b.lane];
     if (lane.h_scratch[L_COMPLEX] == 0) return;
     const hipStream_t stream = b.stream;
-    dev::SketchArgs a = sketch_args(b.batch);
-    a.n_hits = &lane.d_scratch[L_HITS];
-    a.n_minimizers = &lane.d_scratch[L_MINIMIZERS]; // (the recount pass does not count minimizers again)
-    a.overflow = reinterpret_cast<uint32_t*>(&lane.d_scratch[L_OVERFLOW]);
+    dev::SketchArgs a = sketch_args(b.batch, b.direct ? &tsets_[b.lane] : nullptr);
+    count_on_lane(a, lane); // (the recount pass does not count minimizers again)
     lane.scratch_zero = false; // the leftover pass uses the lane's counters again
     HIPCHK(dev::launch_filter_recount(a, lane.fw, stream));
-    HIPCHK(hipMemcpyAsync(lane.h_scratch, lane.d_scratch, L_N * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(lane.h_scratch.data(), lane.d_scratch.data(), lane.d_scratch.bytes(), hipMemcpyDeviceToHost, stream));
     wait_stream(stream);
     const uint64_t n_left = lane.h_scratch[L_HITS];
     if (n_left == 0) return;
     ensure_workspace(std::max<uint64_t>(min_capacity_, n_left + n_left / 8));
-    a.hit_key = d_key_a_; // the hit buffers may have moved
-    a.hit_val = d_val_a_;
-    a.hit_capacity = hit_capacity_;
+    a.hit_key = d_key_a_.data(); // the hit buffers may have moved
+    a.hit_val = d_val_a_.data();
+    a.hit_capacity = hit_capacity();
     HIPCHK(dev::launch_filter_expand(a, lane.fw, stream));
-    cluster_hits(b.batch.d_offsets, (uint32_t)n_left, lane.h_scratch[L_MAXLEN] <= READ_SORT_MAX_LEN, &lane.d_scratch[L_UNSORTED], b.covg, b.prg_reads, stream);
-}
-
-void Mapper::free_tile_set(TileSet& t)
-{
-    dfree(t.d_tile_info); dfree(t.d_tile_pos1); dfree(t.d_tile_count); dfree(t.d_tile_hits); dfree(t.d_tile_nmin); dfree(t.d_tile_prefix);
-    dfree(t.d_nbits);
-    t.nbits_cap = 0;
-    dfree(t.d_tile_rec); dfree(t.d_tile_first);
-    if (t.d_tile_temp) (void)hipFree(t.d_tile_temp);
-    t.d_tile_temp = nullptr;
-    t = TileSet();
+    cluster_hits(b.batch.d_offsets, (uint32_t)n_left, lane.h_scratch[L_MAXLEN] <= READ_SORT_MAX_LEN, lane.d_scratch.data() + L_UNSORTED, b.covg, b.prg_reads, stream);
 }
 
 void Mapper::ensure_tile_workspace(TileSet& t, uint32_t n_tiles, uint32_t tile_cap)
 {
     if (n_tiles <= t.ws_tiles && tile_cap <= t.ws_cap) return;
-    dfree(t.d_tile_info); dfree(t.d_tile_pos1); dfree(t.d_tile_count); dfree(t.d_tile_hits); dfree(t.d_tile_nmin); dfree(t.d_tile_prefix); dfree(t.d_tile_rec);
-    if (t.d_tile_temp) (void)hipFree(t.d_tile_temp);
-    t.d_tile_temp = nullptr;
-    t.ws_tiles = std::max(t.ws_tiles, n_tiles + n_tiles / 8 + 32);
-    t.ws_cap = std::max(t.ws_cap, tile_cap);
-    const size_t n = (size_t)t.ws_tiles * t.ws_cap;
-    dmalloc(t.d_tile_info, n); dmalloc(t.d_tile_pos1, n); dmalloc(t.d_tile_rec, n);
-    dmalloc(t.d_tile_count, (size_t)t.ws_tiles + 1); dmalloc(t.d_tile_hits, (size_t)t.ws_tiles + 1); dmalloc(t.d_tile_nmin, (size_t)t.ws_tiles + 1); dmalloc(t.d_tile_prefix, (size_t)t.ws_tiles + 1);
-    t.tile_temp_bytes = dev::scan_temp_bytes(t.ws_tiles + 1);
-    HIPCHK(hipMalloc(&t.d_tile_temp, t.tile_temp_bytes ? t.tile_temp_bytes : 1));
+    const uint32_t ws_tiles = std::max(t.ws_tiles, n_tiles + n_tiles / 8 + 32), ws_cap = std::max(t.ws_cap, tile_cap);
+    const size_t n = (size_t)ws_tiles * ws_cap, per_tile = (size_t)ws_tiles + 1;
+    t.d_tile_info.alloc(n); t.d_tile_pos1.alloc(n); t.d_tile_rec.alloc(n);
+    t.d_tile_count.alloc(per_tile); t.d_tile_hits.alloc(per_tile); t.d_tile_nmin.alloc(per_tile); t.d_tile_prefix.alloc(per_tile);
+    t.d_tile_temp.alloc(dev::scan_temp_bytes(ws_tiles + 1));
+    t.ws_tiles = ws_tiles; // (said last: a set whose allocation failed half-way is still known as too small)
+    t.ws_cap = ws_cap;
+}
+
+// the first read of every tile: one entry per tile of the sketch that fills it, a quarter more when it has to grow
+void Mapper::reserve_tile_first(TileSet& t, uint32_t n_tiles)
+{
+    t.d_tile_first.reserve(n_tiles, n_tiles + n_tiles / 4 + 16);
 }
 
 // Direct sequence, candidate form: every k-mer hashed (any k, any w, any index size); each tile leaves its index minimizers
@@ -607,14 +533,8 @@ void Mapper::direct_launch(const Batch& b)
     const uint64_t n_bases = b.batch.n_bases;
     const hipStream_t stream = b.stream;
     TileSet& t = tsets_[set];
-    ts_ = &t;
     const uint32_t n_tiles = dev::direct_candidate_tiles(n_bases, halo_, params_.k, params_.w, wide_hash_, sw_.direct_lds); // = slices
-    const uint32_t n_first = dev::direct_first_read_tiles(n_bases, halo_, params_.k, params_.w, wide_hash_, sw_.direct_lds);
-    if (n_first > t.first_cap) { // first read of every tile
-        dfree(t.d_tile_first);
-        t.first_cap = n_first + n_first / 4 + 16;
-        dmalloc(t.d_tile_first, (size_t)t.first_cap);
-    }
+    reserve_tile_first(t, dev::direct_first_read_tiles(n_bases, halo_, params_.k, params_.w, wide_hash_, sw_.direct_lds));
     Lane& lane = lanes_[set]; // (only this set's lane may grow: the other one may belong to a batch in flight)
     grow_lane(lane, std::min<uint64_t>(std::max<uint64_t>(min_capacity_, n_bases / 16), (1ull << 31) - 1));
     // read_cluster_kernel takes the candidates straight from the tile slices (no gathered list unless reads are left over); what it
@@ -624,76 +544,51 @@ void Mapper::direct_launch(const Batch& b)
     static std::atomic<uint32_t> process_epoch { 0x80000000u };
     slices_epoch_ = process_epoch.fetch_add(1) + 1;
     if (slices_epoch_ < 0x80000000u) { // wrapped after 2^31 batches: marks of old batches may still be around, clear them
-        HIPCHK(hipMemsetAsync(lane.cand_pos1, 0, lane.raw_capacity * sizeof(uint32_t), stream));
+        HIPCHK(hipMemsetAsync(lane.cand_pos1.data(), 0, lane.cand_pos1.bytes(), stream));
         process_epoch.store(0x80000001u);
         slices_epoch_ = 0x80000001u;
     }
     const uint32_t mark = slices_epoch_;
     ensure_tile_workspace(t, n_tiles, t.slice_cap);
-    if (!lane.scratch_zero) HIPCHK(hipMemsetAsync(lane.d_scratch, 0, L_N * sizeof(unsigned long long), stream));
+    if (!lane.scratch_zero) HIPCHK(hipMemsetAsync(lane.d_scratch.data(), 0, lane.d_scratch.bytes(), stream));
     lane.scratch_zero = false;
-    HIPCHK(hipMemsetAsync(t.d_tile_count + n_tiles, 0, sizeof(uint32_t), stream)); // the scan's closing zero
+    HIPCHK(hipMemsetAsync(t.d_tile_count.data() + n_tiles, 0, sizeof(uint32_t), stream)); // the scan's closing zero
     // a packed batch: sketch_wave_kernel reads the words themselves (round 4; the positions of its npos as one bit per base, set here);
     // the general direct kernel reads an ASCII expansion made on the same stream (packed.hip)
     const bool native_packed = b.batch.packed && dev::direct_uses_wave_form(params_.k, params_.w, wide_hash_, sw_.direct_lds);
-    dev::SketchArgs a = sketch_args(native_packed ? b.batch : ascii_view(set, b.batch, stream));
+    dev::SketchArgs a = sketch_args(native_packed ? b.batch : ascii_view(set, b.batch, stream), &t);
     if (native_packed && a.n_npos) {
         const uint64_t words16 = ((n_bases + 15) / 16 + 1) & ~1ull; // (an even number of u16 words: the marks are 32-bit atomics)
-        if (words16 > t.nbits_cap) {
-            dfree(t.d_nbits);
-            t.nbits_cap = words16 + words16 / 4;
-            t.nbits_cap += t.nbits_cap & 1;
-            dmalloc(t.d_nbits, (size_t)t.nbits_cap);
-            t.nbits_dirty = true; // (fresh memory)
-        }
-        if (t.nbits_dirty) HIPCHK(hipMemsetAsync(t.d_nbits, 0, (size_t)t.nbits_cap * sizeof(uint16_t), stream));
-        HIPCHK(dev::launch_mark_npos(a.npos, a.n_npos, n_bases, t.d_nbits, stream));
+        const uint64_t grown = words16 + words16 / 4;
+        if (t.d_nbits.reserve(words16, grown + (grown & 1))) t.nbits_dirty = true; // (fresh memory)
+        if (t.nbits_dirty) HIPCHK(hipMemsetAsync(t.d_nbits.data(), 0, t.d_nbits.bytes(), stream));
+        HIPCHK(dev::launch_mark_npos(a.npos, a.n_npos, n_bases, t.d_nbits.data(), stream));
         t.nbits_dirty = true;
-        a.nbits = t.d_nbits;
+        a.nbits = t.d_nbits.data();
     }
-    a.n_hits = &lane.d_scratch[L_HITS];
-    a.n_minimizers = &lane.d_scratch[L_MINIMIZERS];
-    a.overflow = reinterpret_cast<uint32_t*>(&lane.d_scratch[L_OVERFLOW]);
+    count_on_lane(a, lane);
     a.tile_cap = t.ws_cap;
-    a.tile_info = t.d_tile_info;
-    a.tile_pos1 = t.d_tile_pos1;
-    a.tile_rec = t.d_tile_rec;
-    a.tile_count = t.d_tile_count;
-    a.tile_hits = t.d_tile_hits;
-    a.tile_nmin = t.d_tile_nmin;
-    a.prg_min_path_len = d_min_path_len_;
-    a.prg_thr = d_prg_thr_;
+    a.tile_info = t.d_tile_info.data();
+    a.tile_pos1 = t.d_tile_pos1.data();
+    a.tile_rec = t.d_tile_rec.data();
+    a.tile_count = t.d_tile_count.data();
+    a.tile_hits = t.d_tile_hits.data();
+    a.tile_nmin = t.d_tile_nmin.data();
+    a.prg_min_path_len = tables_.min_path_len.data();
+    a.prg_thr = tables_.prg_thr.data();
     a.fraction = params_.cluster_fraction();
     a.min_cluster_size = params_.min_cluster_size;
-    dev::FilterBuffers fb { lane.raw_pos, lane.cand_info, lane.cand_pos1, lane.cand_rec, lane.raw_capacity, lane.small, &lane.d_scratch[L_MAXLEN] };
-    dev::ReadClusterArgs rc {};
-    rc.prg_min_path_len = d_min_path_len_;
-    rc.fraction = params_.cluster_fraction();
-    rc.min_cluster_size = params_.min_cluster_size;
-    rc.max_diff = params_.max_diff;
-    rc.n_prgs = n_prgs_;
-    rc.covg = b.covg;
-    rc.prg_reads = b.prg_reads;
-    rc.n_clusters_kept = &d_counters_[C_CLUSTERS_KEPT];
-    rc.n_hits_kept = &d_counters_[C_HITS_KEPT];
-    rc.n_complex = &lane.d_scratch[L_COMPLEX];
-    rc.chunk_counter = reinterpret_cast<uint32_t*>(&lane.d_scratch[L_CHUNK]);
     lane.fw = dev::FilterWork {};
     lane.fw.read_begin = 0;
     lane.fw.read_end = (uint32_t)b.batch.n_reads;
-    dev::init_candidate_work(lane.fw, fb, n_cus_);
-    dev::KernelTimer timer;
-    if (timing_) {
-        timer.begin = lane.t0;
-        timer.end = lane.t1;
-    }
-    HIPCHK(dev::launch_direct_candidates(a, wide_hash_, sw_.direct_lds, t.d_tile_prefix, t.d_tile_temp, t.tile_temp_bytes, lane.raw_capacity, rc, n_cus_, lane.fw,
-        stream, timer, mark));
+    dev::init_candidate_work(lane.fw, filter_buffers(lane), n_cus_);
+    HIPCHK(dev::launch_direct_candidates(a, wide_hash_, sw_.direct_lds, t.d_tile_prefix.data(), t.d_tile_temp.data(), t.d_tile_temp.size(), lane.capacity(),
+        read_cluster_args(b), n_cus_, lane.fw, stream, kernel_timer(lane.t0, lane.t1), mark));
     t.a_done = a;
     t.mark = mark;
     t.n_tiles = n_tiles;
-    HIPCHK(hipMemcpyAsync(lane.h_scratch, lane.d_scratch, L_N * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipMemsetAsync(lane.d_scratch, 0, L_N * sizeof(unsigned long long), stream));
+    HIPCHK(hipMemcpyAsync(lane.h_scratch.data(), lane.d_scratch.data(), lane.d_scratch.bytes(), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemsetAsync(lane.d_scratch.data(), 0, lane.d_scratch.bytes(), stream));
     lane.scratch_zero = true;
 }
 
@@ -703,7 +598,6 @@ void Mapper::direct_launch(const Batch& b)
 bool Mapper::direct_finish(const Batch& b, int attempt)
 {
     TileSet& t = tsets_[b.lane];
-    ts_ = &t;
     Lane& lane = lanes_[b.lane];
     const uint32_t ovf = (uint32_t)lane.h_scratch[L_OVERFLOW];
     if (ovf & 2u) throw Error(DRPRG_EOVERFLOW, "a read is longer than 2^" + std::to_string(dev::HIT_POS_BITS) + " bases");
@@ -712,14 +606,14 @@ bool Mapper::direct_finish(const Batch& b, int attempt)
         HIPCHK(hipStreamSynchronize(b.stream)); // (the buffers are about to be freed)
         ++reruns_direct_;
         t.slice_cap = std::min<uint32_t>(t.slice_cap * 2, 4096);
-        grow_lane(lane, std::min<uint64_t>(lane.raw_capacity * 2, (1ull << 31) - 1));
+        grow_lane(lane, std::min<uint64_t>(lane.capacity() * 2, (1ull << 31) - 1));
         return false;
     }
     tot_minimizers_ += lane.h_scratch[L_MINIMIZERS];
     tot_hits_ += lane.h_scratch[L_HITS];
     tot_leftover_ += lane.h_scratch[L_COMPLEX];
     if (lane.h_scratch[L_COMPLEX]) // reads were left over: the generic pipeline wants the gathered list after all
-        HIPCHK(dev::launch_tile_gather_marked(t.a_done, lane.fw, t.d_tile_prefix, t.n_tiles, lane.raw_capacity, t.mark, b.stream));
+        HIPCHK(dev::launch_tile_gather_marked(t.a_done, lane.fw, t.d_tile_prefix.data(), t.n_tiles, lane.capacity(), t.mark, b.stream));
     leftovers(b);
     return true;
 }
@@ -738,7 +632,7 @@ bool Mapper::filter_finish(const Batch& b, int attempt)
         // a candidate slice was too small: the sequence counted nothing and touched no coverage (hit_scan_kernel / read_cluster_kernel
         // check the flag)
         if (attempt > 8) throw Error(DRPRG_EOVERFLOW, "candidate buffer overflow after regrow");
-        grow_lane(lane, lane.raw_capacity * 4);
+        grow_lane(lane, lane.capacity() * 4);
         ++reruns_filter_;
         return false;
     }
@@ -760,17 +654,22 @@ void Mapper::buffer_info(uint64_t out[6])
 {
     sync(); // (a deferred batch that overflowed is run again when it is completed)
     uint64_t raw = 0;
-    for (const Lane& lane : lanes_) raw = std::max(raw, lane.raw_capacity);
+    for (const Lane& lane : lanes_) raw = std::max(raw, lane.capacity());
     out[0] = reruns_filter_;
     out[1] = reruns_direct_;
     out[2] = regrows_hits_;
     out[3] = raw;
-    out[4] = hit_capacity_;
-    // which sketch form serves this context: 1 sketch_wave_kernel, 2 / 3 / 4 sketch_probe_kernel with its compile-time window / its sequential
-    // scan on u32 / u64 keys; the filtered sequence: 10 small tier (level 0 on 12-mers), 11 levels 1+2 alone (k < 15), 12 middle tier
-    if (use_filter_) out[5] = use_mid_ ? 12 : (bloom0_wbits_ ? 10 : 11);
-    else if (use_direct_cands_ && dev::direct_uses_wave_form(params_.k, params_.w, wide_hash_, sw_.direct_lds)) out[5] = 1;
-    else out[5] = wide_hash_ ? 4 : (dev::probe_compile_time_window(params_.k, params_.w) ? 2 : 3);
+    out[4] = hit_capacity();
+    out[5] = sketch_form();
+}
+
+// which sketch form serves this context: 1 sketch_wave_kernel, 2 / 3 / 4 sketch_probe_kernel with its compile-time window / its sequential
+// scan on u32 / u64 keys; the filtered sequence: 10 small tier (level 0 on 12-mers), 11 levels 1+2 alone (k < 15), 12 middle tier
+int Mapper::sketch_form() const
+{
+    if (use_filter_) return use_mid_ ? 12 : (tables_.bloom0_wbits ? 10 : 11);
+    if (use_direct_cands_ && dev::direct_uses_wave_form(params_.k, params_.w, wide_hash_, sw_.direct_lds)) return 1;
+    return wide_hash_ ? 4 : (dev::probe_compile_time_window(params_.k, params_.w) ? 2 : 3);
 }
 
 // sketch_filter_kernel's four wave classes should end together (sketch_filter.hip: a SIMD issues for its oldest wave first).  How far apart they
@@ -834,8 +733,8 @@ void Mapper::map(const DeviceBatch& batch, uint32_t* covg, uint32_t* prg_reads, 
     if (batch.n_reads == 0) return;
     HIPCHK(hipSetDevice(device_));
     if (kept_cap_ && !in_keep_call_) kept_broken_ = true; // reads of the caller's own buffers: not among the kept ones
-    if (!covg) covg = d_covg_;
-    if (!prg_reads) prg_reads = d_prg_reads_;
+    if (!covg) covg = d_covg();
+    if (!prg_reads) prg_reads = d_prg_reads();
     if (!stream) stream = stream_;
     if (!deferred || (!use_filter_ && !use_direct_cands_) || batch.n_bases == 0) {
         complete_pending();
@@ -909,30 +808,19 @@ void Mapper::run_batch(const DeviceBatch& batch, uint32_t* covg, uint32_t* prg_r
         return;
     }
     // ---- direct sequence, generic form: every k-mer hashed, hits in tile order, global radix sort ----
-    dev::KernelTimer timer;
-    if (timing_) { // events bracket the dominant kernel only
-        timer.begin = ev0_;
-        timer.end = ev1_;
-    }
     ensure_workspace(std::max<uint64_t>(min_capacity_, n_bases / 64));
-    const uint32_t n_tiles = dev::sketch_n_tiles(n_bases, halo_);
-    ts_ = &tsets_[0];
-    if (n_tiles > ts_->first_cap) { // first read of every tile
-        dfree(ts_->d_tile_first);
-        ts_->first_cap = n_tiles + n_tiles / 4 + 16;
-        dmalloc(ts_->d_tile_first, (size_t)ts_->first_cap);
-    }
+    reserve_tile_first(tsets_[0], dev::sketch_n_tiles(n_bases, halo_));
     const DeviceBatch ascii = ascii_view(2, batch, stream); // (a packed batch: expanded on the device for this kernel)
     for (int attempt = 0;; ++attempt) {
-        HIPCHK(hipMemsetAsync(&d_counters_[C_HITS], 0, 2 * sizeof(unsigned long long), stream)); // hits + minimizers of this attempt
-        HIPCHK(hipMemsetAsync(&d_counters_[C_OVERFLOW], 0, sizeof(unsigned long long), stream));
-        const dev::SketchArgs a = sketch_args(ascii);
-        HIPCHK(dev::launch_sketch_probe(a, wide_hash_, stream, timer));
+        HIPCHK(hipMemsetAsync(d_counters_.data() + C_HITS, 0, 2 * sizeof(unsigned long long), stream)); // hits + minimizers of this attempt
+        HIPCHK(hipMemsetAsync(d_counters_.data() + C_OVERFLOW, 0, sizeof(unsigned long long), stream));
+        const dev::SketchArgs a = sketch_args(ascii, &tsets_[0]);
+        HIPCHK(dev::launch_sketch_probe(a, wide_hash_, stream, kernel_timer(ev0_, ev1_)));
         read_counters(stream);
         if (attempt == 0) note_kernel_time(ev0_, ev1_); // (as complete_batch: a batch's first attempt)
         if ((uint32_t)h_counters_[C_OVERFLOW] & 2u)
             throw Error(DRPRG_EOVERFLOW, "a read is longer than 2^" + std::to_string(dev::HIT_POS_BITS) + " bases");
-        if (h_counters_[C_HITS] > hit_capacity_) {
+        if (h_counters_[C_HITS] > hit_capacity()) {
             if (attempt > 6) throw Error(DRPRG_EOVERFLOW, "hit buffer overflow after regrow");
             ensure_workspace(h_counters_[C_HITS] + h_counters_[C_HITS] / 8 + 1024);
             ++regrows_hits_;
@@ -952,34 +840,19 @@ Mapper::CutPoint Mapper::find_cut(const DeviceBatch& b, uint64_t target, hipStre
     sync(); // (a batch in flight comes before this one in the running total: it is complete before this one is cut)
     HIPCHK(hipSetDevice(device_));
     if (!stream) stream = stream_;
-    if (!h_cut_) {
-        HIPCHK(hipHostMalloc((void**)&h_cut_, 4 * sizeof(unsigned long long), hipHostMallocDefault));
-        HIPCHK(hipHostGetDevicePointer((void**)&h_cut_dev_, h_cut_, 0));
-    }
-    HIPCHK(dev::launch_covg_cut(b.d_offsets, b.n_reads, target, b.d_npos, b.n_npos, h_cut_dev_, stream));
+    if (!h_cut_) h_cut_.alloc(4);
+    HIPCHK(dev::launch_covg_cut(b.d_offsets, b.n_reads, target, b.d_npos, b.n_npos, h_cut_.device_ptr(), stream));
     wait_stream(stream);
     return CutPoint { h_cut_[0], h_cut_[1], h_cut_[2] };
 }
 
 void Mapper::ensure_stage(Stage& st, uint64_t payload_bytes, uint64_t n_reads, uint64_t n_npos)
 {
-    const bool grow_bases = payload_bytes + 64 > st.bases_cap, grow_reads = n_reads + 1 > st.reads_cap, grow_npos = n_npos > st.npos_cap;
-    if (grow_bases || grow_reads || grow_npos) sync(); // (freeing device memory waits for the device; be explicit about the batch in flight)
-    if (grow_bases) {
-        dfree(st.d_bases);
-        st.bases_cap = payload_bytes + payload_bytes / 4 + 64;
-        dmalloc(st.d_bases, st.bases_cap);
-    }
-    if (grow_reads) {
-        dfree(st.d_offsets);
-        st.reads_cap = n_reads + n_reads / 4 + 1;
-        dmalloc(st.d_offsets, st.reads_cap);
-    }
-    if (grow_npos) {
-        dfree(st.d_npos);
-        st.npos_cap = n_npos + n_npos / 4 + 16;
-        dmalloc(st.d_npos, st.npos_cap);
-    }
+    if (payload_bytes + 64 > st.d_bases.size() || n_reads + 1 > st.d_offsets.size() || n_npos > st.d_npos.size())
+        sync(); // (freeing device memory waits for the device; be explicit about the batch in flight)
+    st.d_bases.reserve(payload_bytes + 64, payload_bytes + payload_bytes / 4 + 64);
+    st.d_offsets.reserve(n_reads + 1, n_reads + n_reads / 4 + 1);
+    st.d_npos.reserve(n_npos, n_npos + n_npos / 4 + 16);
 }
 
 Mapper::DeviceBatch Mapper::copy_in(const HostBatch& hb, uint8_t* d_bases, uint64_t* d_offsets, uint64_t* d_npos, hipStream_t stream)
@@ -1006,7 +879,7 @@ void Mapper::map_host(const HostBatch& hb)
     if (hb.offsets[0] != 0) throw Error(DRPRG_EINVAL, "offsets[0] must be 0");
     Stage& st = stage_sync_;
     ensure_stage(st, hb.payload_bytes(), hb.n_reads, hb.packed ? hb.n_npos : 0);
-    map(copy_in(hb, st.d_bases, st.d_offsets, st.d_npos, stream_), nullptr, nullptr, stream_, false);
+    map(copy_in(hb, st.d_bases.data(), st.d_offsets.data(), st.d_npos.data(), stream_), nullptr, nullptr, stream_, false);
     HIPCHK(hipStreamSynchronize(stream_)); // the staging buffers are reused by the next call
 }
 
@@ -1016,11 +889,11 @@ uint64_t Mapper::pack_on_device(const uint8_t* d_bases, uint64_t n_bases, uint32
     if (!stream) stream = stream_;
     if (n_bases == 0) return 0;
     if (!d_bases || !d_words) throw Error(DRPRG_EINVAL, "null device pointer");
-    if (!d_pack_count_) dmalloc(d_pack_count_, (size_t)1); // (one counter word per Mapper: a hipMalloc / hipFree per call synchronises the device)
+    if (!d_pack_count_) d_pack_count_.alloc(1); // (one counter word per Mapper: an allocation per call synchronises the device)
     unsigned long long n = 0;
-    HIPCHK(hipMemsetAsync(d_pack_count_, 0, sizeof(unsigned long long), stream));
-    HIPCHK(dev::launch_pack(d_bases, n_bases, d_words, d_npos, d_npos ? npos_cap : 0, d_pack_count_, stream));
-    HIPCHK(hipMemcpyAsync(&n, d_pack_count_, sizeof n, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemsetAsync(d_pack_count_.data(), 0, sizeof(unsigned long long), stream));
+    HIPCHK(dev::launch_pack(d_bases, n_bases, d_words, d_npos, d_npos ? npos_cap : 0, d_pack_count_.data(), stream));
+    HIPCHK(hipMemcpyAsync(&n, d_pack_count_.data(), sizeof n, hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
     if (n && !d_npos) throw Error(DRPRG_EINVAL, "the batch holds bases that are not ACGT and no buffer for their positions was given");
     if (d_npos && n > 1 && n <= npos_cap) { // the positions come out in any order: sorted on the host (few; the harness path)
@@ -1039,13 +912,15 @@ void* Mapper::arena_take(size_t bytes)
     if (bytes > arena_left_) {
         // (what is left of the current piece is not used: pieces are 256 MB, blocks ~25 MB)
         const size_t piece = std::max<size_t>(bytes, std::min<uint64_t>(256ull << 20, kept_cap_ - kept_bytes_));
-        void* p = nullptr;
-        if (hipMalloc(&p, piece) != hipSuccess) {
+        DeviceBuffer<uint8_t> arena;
+        try {
+            arena.alloc(piece);
+        } catch (const Error&) { // (the device is full: the caller goes on without resident reads)
             (void)hipGetLastError();
             return nullptr;
         }
-        kept_arenas_.emplace_back(p, piece);
-        arena_at_ = static_cast<uint8_t*>(p);
+        kept_arenas_.push_back(std::move(arena));
+        arena_at_ = kept_arenas_.back().data();
         arena_left_ = piece;
     }
     void* r = arena_at_;
@@ -1069,7 +944,6 @@ void Mapper::drop_kept()
         sync();
         HIPCHK(hipSetDevice(device_));
         HIPCHK(hipStreamSynchronize(stream_));
-        for (auto& a : kept_arenas_) (void)hipFree(a.first);
     }
     kept_arenas_.clear();
     kept_.clear();
@@ -1111,29 +985,16 @@ void Mapper::select_reads_with_anchors(std::vector<uint64_t> anchors, uint32_t A
         total_reads += b.n_reads;
         max_reads = std::max(max_reads, b.n_reads);
     }
-    // device scratch of this call (freed on every way out)
-    struct Scratch {
-        std::vector<void*> p;
-        ~Scratch()
-        {
-            for (void* q : p) (void)hipFree(q);
-        }
-        void* get(size_t bytes)
-        {
-            void* q = nullptr;
-            if (hipMalloc(&q, bytes ? bytes : 16) != hipSuccess) throw Error(DRPRG_ENOMEM, "out of device memory (read selection)");
-            p.push_back(q);
-            return q;
-        }
-    } scratch;
-    uint64_t* d_anchors = static_cast<uint64_t*>(scratch.get(anchors.size() * sizeof(uint64_t)));
-    uint32_t* d_pf = static_cast<uint32_t*>(scratch.get(pf.size() * sizeof(uint32_t)));
-    uint32_t* d_flags = static_cast<uint32_t*>(scratch.get(max_reads * sizeof(uint32_t)));
-    unsigned long long* d_count = static_cast<unsigned long long*>(scratch.get(sizeof(unsigned long long)));
-    dev::SelectedRead* d_list = static_cast<dev::SelectedRead*>(scratch.get(total_reads * sizeof(dev::SelectedRead)));
-    HIPCHK(hipMemcpyAsync(d_anchors, anchors.data(), anchors.size() * sizeof(uint64_t), hipMemcpyHostToDevice, stream_));
-    HIPCHK(hipMemcpyAsync(d_pf, pf.data(), pf.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
-    HIPCHK(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), stream_));
+    // device scratch of this call
+    DeviceBuffer<uint64_t> d_anchors;
+    DeviceBuffer<uint32_t> d_pf, d_flags;
+    DeviceBuffer<unsigned long long> d_count;
+    DeviceBuffer<dev::SelectedRead> d_list;
+    DeviceBuffer<uint8_t> d_ascii;
+    d_anchors.alloc(anchors.size()); d_pf.alloc(pf.size()); d_flags.alloc(max_reads); d_count.alloc(1); d_list.alloc(total_reads);
+    HIPCHK(hipMemcpyAsync(d_anchors.data(), anchors.data(), anchors.size() * sizeof(uint64_t), hipMemcpyHostToDevice, stream_));
+    HIPCHK(hipMemcpyAsync(d_pf.data(), pf.data(), pf.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
+    HIPCHK(hipMemsetAsync(d_count.data(), 0, sizeof(unsigned long long), stream_));
     // Batches kept in the packed form: the scan and the gather read an ASCII expansion.  It is made a WINDOW of batches at a time -- as
     // many consecutive batches as expand into <= 1 GB (a larger batch alone) --, scanned, and its selected reads gathered before the next
     // window's expansion takes the scratch: the scratch is the largest window, not the sample (up to 128 Gbases can stay
@@ -1151,7 +1012,7 @@ void Mapper::select_reads_with_anchors(std::vector<uint64_t> anchors, uint32_t A
         scratch_need = std::max(scratch_need, need);
         b = e;
     }
-    uint8_t* d_ascii = scratch_need ? static_cast<uint8_t*>(scratch.get(scratch_need)) : nullptr;
+    if (scratch_need) d_ascii.alloc(scratch_need);
     std::vector<const uint8_t*> ascii(kept_.size(), nullptr);
     unsigned long long done = 0; // entries of d_list the windows before this one left
     for (const auto& win : windows) {
@@ -1162,23 +1023,23 @@ void Mapper::select_reads_with_anchors(std::vector<uint64_t> anchors, uint32_t A
                 ascii[b] = kb.d_bases;
                 continue;
             }
-            HIPCHK(dev::launch_unpack(reinterpret_cast<const uint32_t*>(kb.d_bases), kb.n_bases, kb.d_npos, kb.n_npos, d_ascii + at, stream_));
-            ascii[b] = d_ascii + at;
+            HIPCHK(dev::launch_unpack(reinterpret_cast<const uint32_t*>(kb.d_bases), kb.n_bases, kb.d_npos, kb.n_npos, d_ascii.data() + at, stream_));
+            ascii[b] = d_ascii.data() + at;
             at += expanded(kb);
         }
         for (size_t b = win.first; b < win.second; ++b) {
             const DeviceBatch& kb = kept_[b];
-            HIPCHK(hipMemsetAsync(d_flags, 0, kb.n_reads * sizeof(uint32_t), stream_));
-            HIPCHK(dev::launch_anchor_scan(ascii[b], kb.d_offsets, (uint32_t)kb.n_reads, kb.n_bases, d_anchors, (uint32_t)anchors.size(), A, d_pf, (uint32_t)b,
-                d_flags, d_count, d_list, total_reads, n_cus_, stream_));
+            HIPCHK(hipMemsetAsync(d_flags.data(), 0, kb.n_reads * sizeof(uint32_t), stream_));
+            HIPCHK(dev::launch_anchor_scan(ascii[b], kb.d_offsets, (uint32_t)kb.n_reads, kb.n_bases, d_anchors.data(), (uint32_t)anchors.size(), A, d_pf.data(),
+                (uint32_t)b, d_flags.data(), d_count.data(), d_list.data(), total_reads, n_cus_, stream_));
         }
         unsigned long long count = 0;
-        HIPCHK(hipMemcpyAsync(&count, d_count, sizeof count, hipMemcpyDeviceToHost, stream_));
+        HIPCHK(hipMemcpyAsync(&count, d_count.data(), sizeof count, hipMemcpyDeviceToHost, stream_));
         HIPCHK(hipStreamSynchronize(stream_));
         if (count > total_reads) throw Error(DRPRG_EIO, "read selection: more reads than the batches hold"); // (each read is appended once)
         if (count == done) continue;
         std::vector<dev::SelectedRead> list(count - done);
-        HIPCHK(hipMemcpy(list.data(), d_list + done, (count - done) * sizeof(dev::SelectedRead), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(list.data(), d_list.data() + done, (count - done) * sizeof(dev::SelectedRead), hipMemcpyDeviceToHost));
         done = count;
         std::sort(list.begin(), list.end(), [](const dev::SelectedRead& x, const dev::SelectedRead& y) { return x.batch != y.batch ? x.batch < y.batch : x.read < y.read; });
         std::vector<dev::GatherEntry> table(list.size());
@@ -1191,21 +1052,16 @@ void Mapper::select_reads_with_anchors(std::vector<uint64_t> anchors, uint32_t A
             out_bytes += list[i].len;
         }
         // (device memory of this window only: freed before the next one)
-        dev::GatherEntry* d_table = nullptr;
-        uint8_t* d_out = nullptr;
-        if (hipMalloc((void**)&d_table, list.size() * sizeof(dev::GatherEntry)) != hipSuccess || hipMalloc((void**)&d_out, out_bytes ? out_bytes : 16) != hipSuccess) {
-            if (d_table) (void)hipFree(d_table);
-            throw Error(DRPRG_ENOMEM, "out of device memory (read selection)");
-        }
+        DeviceBuffer<dev::GatherEntry> d_table;
+        DeviceBuffer<uint8_t> d_out;
+        d_table.alloc(list.size());
+        d_out.alloc(out_bytes);
         const size_t base0 = bases.size();
         bases.resize(base0 + out_bytes);
-        hipError_t e = hipMemcpyAsync(d_table, table.data(), list.size() * sizeof(dev::GatherEntry), hipMemcpyHostToDevice, stream_);
-        if (e == hipSuccess) e = dev::launch_gather_reads(d_table, (uint32_t)list.size(), d_out, stream_);
-        if (e == hipSuccess && out_bytes) e = hipMemcpyAsync(bases.data() + base0, d_out, out_bytes, hipMemcpyDeviceToHost, stream_);
-        if (e == hipSuccess) e = hipStreamSynchronize(stream_);
-        (void)hipFree(d_table);
-        (void)hipFree(d_out);
-        HIPCHK(e);
+        HIPCHK(hipMemcpyAsync(d_table.data(), table.data(), list.size() * sizeof(dev::GatherEntry), hipMemcpyHostToDevice, stream_));
+        HIPCHK(dev::launch_gather_reads(d_table.data(), (uint32_t)list.size(), d_out.data(), stream_));
+        if (out_bytes) HIPCHK(hipMemcpyAsync(bases.data() + base0, d_out.data(), out_bytes, hipMemcpyDeviceToHost, stream_));
+        HIPCHK(hipStreamSynchronize(stream_));
         for (size_t i = 0; i < list.size(); ++i) offsets.push_back(offsets.back() + list[i].len);
         if (ids)
             for (size_t i = 0; i < list.size(); ++i) ids->push_back((uint64_t)list[i].batch << 32 | list[i].read);
@@ -1229,8 +1085,8 @@ void Mapper::map_host_async(const HostBatch& hb)
         uint64_t* doff = db ? static_cast<uint64_t*>(arena_take((n_reads + 1) * sizeof(uint64_t))) : nullptr;
         uint64_t* dnp = doff && n_npos ? static_cast<uint64_t*>(arena_take(n_npos * sizeof(uint64_t))) : nullptr;
         if (db && doff && (dnp || !n_npos)) {
-            if (!copy_stream_) HIPCHK(hipStreamCreateWithFlags(&copy_stream_, hipStreamNonBlocking));
-            if (!kept_copied_) HIPCHK(hipEventCreateWithFlags(&kept_copied_, hipEventDisableTiming));
+            if (!copy_stream_) copy_stream_.create();
+            if (!kept_copied_) kept_copied_.create(false);
             const DeviceBatch kb = copy_in(hb, db, doff, dnp, copy_stream_);
             HIPCHK(hipEventRecord(kept_copied_, copy_stream_));
             HIPCHK(hipStreamWaitEvent(stream_, kept_copied_, 0));
@@ -1265,14 +1121,14 @@ void Mapper::map_host_async(const HostBatch& hb)
         tot_reads_ += n_reads;
         return;
     }
-    if (!copy_stream_) HIPCHK(hipStreamCreateWithFlags(&copy_stream_, hipStreamNonBlocking));
+    if (!copy_stream_) copy_stream_.create();
     // the batch that used this staging set two calls ago was completed by the previous call (a deferred map completes the batch
     // before the one it queues), so the set is free
     Stage& st = stage_[stage_next_];
     stage_next_ ^= 1;
-    if (!st.copied) HIPCHK(hipEventCreateWithFlags(&st.copied, hipEventDisableTiming));
+    if (!st.copied) st.copied.create(false);
     ensure_stage(st, hb.payload_bytes(), n_reads, hb.packed ? hb.n_npos : 0);
-    const DeviceBatch b = copy_in(hb, st.d_bases, st.d_offsets, st.d_npos, copy_stream_);
+    const DeviceBatch b = copy_in(hb, st.d_bases.data(), st.d_offsets.data(), st.d_npos.data(), copy_stream_);
     HIPCHK(hipEventRecord(st.copied, copy_stream_));
     HIPCHK(hipStreamWaitEvent(stream_, st.copied, 0));
     map(b, nullptr, nullptr, stream_, true);
@@ -1288,13 +1144,13 @@ void Mapper::add_vectors_from(Mapper& other)
     sync();
     HIPCHK(hipSetDevice(device_));
     const size_t nc = 2 * (size_t)n_knodes_, np = n_prgs_;
-    const uint32_t* src = other.d_covg_; // [coverage | reads per PRG], one vector on either side
+    const uint32_t* src = other.d_covg(); // [coverage | reads per PRG], one vector on either side
     if (other.device_ != device_) {
-        if (!d_peer_tmp_) dmalloc(d_peer_tmp_, nc + np);
-        HIPCHK(hipMemcpyPeerAsync(d_peer_tmp_, device_, other.d_covg_, other.device_, (nc + np) * sizeof(uint32_t), stream_));
-        src = d_peer_tmp_;
+        if (!d_peer_tmp_) d_peer_tmp_.alloc(nc + np);
+        HIPCHK(hipMemcpyPeerAsync(d_peer_tmp_.data(), device_, other.d_covg(), other.device_, (nc + np) * sizeof(uint32_t), stream_));
+        src = d_peer_tmp_.data();
     }
-    HIPCHK(dev::launch_vector_add_u32(d_covg_, src, nc + np, stream_));
+    HIPCHK(dev::launch_vector_add_u32(d_covg(), src, nc + np, stream_));
     HIPCHK(hipStreamSynchronize(stream_));
 }
 
@@ -1305,8 +1161,8 @@ void Mapper::download(std::vector<uint32_t>& covg, std::vector<uint32_t>& prg_re
     HIPCHK(hipStreamSynchronize(stream_));
     covg.resize(2 * (size_t)n_knodes_);
     prg_reads.resize(n_prgs_);
-    HIPCHK(hipMemcpy(covg.data(), d_covg_, covg.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(prg_reads.data(), d_prg_reads_, prg_reads.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(covg.data(), d_covg(), covg.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(prg_reads.data(), d_prg_reads(), prg_reads.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
 }
 
 void Mapper::upload(const std::vector<uint32_t>& covg, const std::vector<uint32_t>& prg_reads)
@@ -1316,23 +1172,20 @@ void Mapper::upload(const std::vector<uint32_t>& covg, const std::vector<uint32_
     if (covg.size() != 2 * (size_t)n_knodes_ || prg_reads.size() != n_prgs_) throw Error(DRPRG_EINVAL, "coverage size mismatch");
     sync();
     HIPCHK(hipSetDevice(device_));
-    HIPCHK(hipMemcpy(d_covg_, covg.data(), covg.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_prg_reads_, prg_reads.data(), prg_reads.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_covg(), covg.data(), covg.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_prg_reads(), prg_reads.data(), prg_reads.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     HIPCHK(hipStreamSynchronize(nullptr));
 }
 
 void Mapper::device_tables(uint64_t out[6]) const
 {
-    out[4] = use_mid_ ? (uint64_t)MID_BITMAP_WORDS * 4 + ((uint64_t)16 << midc_wbits_) : 0; // global-memory (L2) tiers of the filter
-    if (!use_mid_ && use_filter_ && d_blkc_) out[4] = (uint64_t)16 << blkc_wbits_; // (small tier: the second stage's block filter, what packed batches are tested against)
-    // which sketch form serves this context: 1 sketch_wave_kernel, 2 / 3 / 4 sketch_probe_kernel with its compile-time window / its sequential
-    // scan on u32 / u64 keys; the filtered sequence: 10 small tier (level 0 on 12-mers), 11 levels 1+2 alone (k < 15), 12 middle tier
-    if (use_filter_) out[5] = use_mid_ ? 12 : (bloom0_wbits_ ? 10 : 11);
-    else if (use_direct_cands_ && dev::direct_uses_wave_form(params_.k, params_.w, wide_hash_, sw_.direct_lds)) out[5] = 1;
-    else out[5] = wide_hash_ ? 4 : (dev::probe_compile_time_window(params_.k, params_.w) ? 2 : 3);
-    out[0] = d_pbloom_ ? (uint64_t)1 << pbloom_wbits_ : 0;
-    out[1] = ((uint64_t)1 << table_bits_) * (wide_hash_ ? 16 : 12);
-    out[2] = bloom_wbits_ ? ((uint64_t)4 << bloom_wbits_) + (bloom0_wbits_ ? ((uint64_t)4 << bloom0_wbits_) + ((uint64_t)4 << BLOOMR_WBITS) : 0) : 0;
+    const IndexTables& t = tables_;
+    out[4] = use_mid_ ? (uint64_t)MID_BITMAP_WORDS * 4 + ((uint64_t)16 << t.midc_wbits) : 0; // global-memory (L2) tiers of the filter
+    if (!use_mid_ && use_filter_ && t.blkc) out[4] = (uint64_t)16 << t.blkc_wbits; // (small tier: the second stage's block filter, what packed batches are tested against)
+    out[5] = sketch_form();
+    out[0] = t.pbloom ? (uint64_t)1 << t.pbloom_wbits : 0;
+    out[1] = ((uint64_t)1 << t.table_bits) * (wide_hash_ ? 16 : 12);
+    out[2] = t.bloom_wbits ? ((uint64_t)4 << t.bloom_wbits) + (t.bloom0_wbits ? ((uint64_t)4 << t.bloom0_wbits) + ((uint64_t)4 << BLOOMR_WBITS) : 0) : 0;
     if (use_mid_) out[2] = (uint64_t)4 << 15;
     out[3] = use_filter_ ? 2 : (use_direct_cands_ ? 3 : 1);
 }
@@ -1343,7 +1196,7 @@ MapCounters Mapper::counters()
     HIPCHK(hipSetDevice(device_));
     HIPCHK(hipStreamSynchronize(stream_));
     unsigned long long c[C_N];
-    HIPCHK(hipMemcpy(c, d_counters_, sizeof(c), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(c, d_counters_.data(), sizeof(c), hipMemcpyDeviceToHost));
     MapCounters m;
     m.reads = tot_reads_;
     m.bases = tot_bases_;

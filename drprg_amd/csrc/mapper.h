@@ -4,6 +4,7 @@
 // This is the MI355X replacement for the read loop of `pandora map` (pangraph_from_read_file),
 // spawned by the reference at /root/reference/src/lib.rs:580-642.
 #pragma once
+#include "device_mem.h"
 #include "index.h"
 #include "kernels.h"
 #include <vector>
@@ -121,8 +122,8 @@ public:
     // reset with (DRPRG_HIP_MIN_CAPACITY, DRPRG_FORCE_MID_TIER and DRPRG_MID_MAX_RECORDS shape construction: they take effect at open only)
     void reset_coverage(bool new_sample = true);
     // own accumulators
-    uint32_t* d_covg() const { return d_covg_; }
-    uint32_t* d_prg_reads() const { return d_prg_reads_; }
+    uint32_t* d_covg() const { return d_covg_.data(); }
+    uint32_t* d_prg_reads() const { return d_covg_.data() + 2 * (size_t)n_knodes_; }
     void download(std::vector<uint32_t>& covg, std::vector<uint32_t>& prg_reads);
     void upload(const std::vector<uint32_t>& covg, const std::vector<uint32_t>& prg_reads);
     MapCounters counters(); // synchronises
@@ -142,7 +143,7 @@ public:
     void filter_schedule(uint64_t out[20]);
     // the buffers that grow when a batch does not fit them (drprg_hip_buffer_info; counts since the Mapper was made, reset() keeps them):
     // out[0] batches of the filtered sequence run again after a candidate slice overflowed, [1] the same for the direct sequence's
-    // candidate form, [2] regrows of the generic hit buffer, [3] largest raw_capacity of any lane (entries), [4] hit_capacity_, [5] 0.  Synchronises.
+    // candidate form, [2] regrows of the generic hit buffer, [3] largest capacity of any lane (entries), [4] hit_capacity(), [5] sketch_form().  Synchronises.
     void buffer_info(uint64_t out[6]);
     void enable_kernel_timing(bool on) { timing_ = on; }
     double sketch_ms_total() const { return sketch_ms_; }
@@ -150,22 +151,25 @@ public:
     void reset_kernel_timing() { sketch_ms_ = 0; sketch_launches_ = 0; }
 
 private:
-    void zero_now(void* p, int value, size_t bytes);
+    // Every device allocation, pinned block, event and stream below is held by an owner of device_mem.h: nothing is freed by hand.  The
+    // streams come first, so that they are destroyed last -- after the buffers that work queued on them used.
+    Stream stream_, copy_stream_; // (copy_stream_: the copies of map_host_async, created with the first of them)
+    void zero_now(void* p, size_t bytes);
     void ensure_workspace(uint64_t hit_capacity);
     // What one batch of a candidate sequence (filtered: sketch_filter -> verify -> read_cluster; direct: sketch -> read_cluster from the
-    // tile slices) keeps to itself: candidate buffers, per-sequence counters, and events on the batch's stream (done: behind the batch's
-    // read-back; t0 / t1 around the dominant kernel).  Two lanes: deferred maps take them in turn, the synchronous calls use lane 0.
+    // tile slices) keeps to itself: candidate buffers (all of capacity() entries; grow_lane), per-sequence counters with their pinned
+    // mirror, and events on the batch's stream (done: behind the batch's read-back; t0 / t1 around the dominant kernel) -- the last three
+    // made by ensure_lanes.  Two lanes: deferred maps take them in turn, the synchronous calls use lane 0.
     struct Lane {
-        hipEvent_t done = nullptr, t0 = nullptr, t1 = nullptr;
-        uint64_t raw_capacity = 0;
-        uint64_t *raw_pos = nullptr, *cand_info = nullptr;
-        uint4* cand_rec = nullptr;
-        uint32_t *cand_pos1 = nullptr, *small = nullptr;
-        unsigned long long* d_scratch = nullptr; // L_N x u64 per-sequence counters (below)
-        unsigned long long* h_scratch = nullptr; // pinned mirror
-        unsigned long long* h_scratch_dev = nullptr; // its device address
-        bool scratch_zero = false;               // d_scratch is known to be zero on the device
+        Event done, t0, t1;
+        DeviceBuffer<uint64_t> raw_pos, cand_info;
+        DeviceBuffer<uint4> cand_rec;
+        DeviceBuffer<uint32_t> cand_pos1, small;
+        DeviceBuffer<unsigned long long> d_scratch; // L_N x u64 per-sequence counters (below)
+        PinnedBuffer<unsigned long long> h_scratch; // pinned mirror
+        bool scratch_zero = false;                  // d_scratch is known to be zero on the device
         dev::FilterWork fw {};
+        uint64_t capacity() const { return raw_pos.size(); }
     };
     enum { L_HITS = 0, L_OVERFLOW = 1, L_MAXLEN = 2, L_UNSORTED = 3, L_COMPLEX = 4, L_CHUNK = 5, L_MINIMIZERS = 6, L_FT_CLOCK = 7 /* five words: FilterBuffers::class_clock */, L_N = 12 };
     // A batch of one of the two candidate sequences, as its launch and finish functions see it.  The description travels with the batch (a
@@ -181,8 +185,7 @@ private:
     };
     Batch make_batch(int lane, const DeviceBatch& batch, uint32_t* covg, uint32_t* prg_reads, hipStream_t stream) const;
     void ensure_lanes();
-    void grow_lane(Lane& lane, uint64_t raw_capacity);
-    void free_lane(Lane& lane);
+    void grow_lane(Lane& lane, uint64_t capacity);
     // One attempt of a batch, queued on its stream with the lane's `done` recorded behind it; finish: the attempt's read-back has arrived
     // -- false: a candidate buffer was too small, nothing was counted, the buffers have grown and the batch must run again.
     void launch(const Batch& b);
@@ -194,14 +197,18 @@ private:
     void run_batch(const DeviceBatch& batch, uint32_t* d_covg, uint32_t* d_prg_reads, hipStream_t stream);
     void cluster_hits(const uint64_t* d_offsets, uint32_t n_hits, bool ordered, unsigned long long* d_unsorted, uint32_t* d_covg,
         uint32_t* d_prg_reads, hipStream_t stream);
-    dev::SketchArgs sketch_args(const DeviceBatch& batch) const;
+    // what the launch functions of a batch on a lane say alike: the lane's counters as the sketch's n_hits / n_minimizers / overflow, its
+    // candidate buffers, read_cluster_kernel's arguments, and the events around the dominant kernel (when kernels are timed)
+    void count_on_lane(dev::SketchArgs& a, const Lane& lane) const;
+    dev::FilterBuffers filter_buffers(const Lane& lane) const;
+    dev::ReadClusterArgs read_cluster_args(const Batch& b) const;
+    dev::KernelTimer kernel_timer(hipEvent_t t0, hipEvent_t t1) const;
     // the batch itself, or -- for a packed batch -- its ASCII expansion in scratch buffer `slot` (0 / 1: the two tile sets of the direct
     // sequence's candidate form, 2: the generic sequence), made on `stream`
     DeviceBatch ascii_view(int slot, const DeviceBatch& batch, hipStream_t stream);
-    uint8_t* d_unpacked_[3] = { nullptr, nullptr, nullptr };
-    unsigned long long* d_pack_count_ = nullptr; // pack_on_device's counter word
-    unsigned long long *h_cut_ = nullptr, *h_cut_dev_ = nullptr; // find_cut's three result words: pinned, and their device address
-    uint64_t unpacked_cap_[3] = { 0, 0, 0 };
+    DeviceBuffer<uint8_t> d_unpacked_[3];
+    DeviceBuffer<unsigned long long> d_pack_count_; // pack_on_device's counter word
+    PinnedBuffer<unsigned long long> h_cut_;        // find_cut's three result words
     void read_counters(hipStream_t stream);
     void note_kernel_time(hipEvent_t t0, hipEvent_t t1);
     // deferred completion: the batches take the two lanes in turn; `pending_` is the batch whose read-back nobody has looked at yet
@@ -215,115 +222,117 @@ private:
     MapParams params_;
     bool wide_hash_ = false;
     int halo_ = 16;
-    uint32_t n_knodes_ = 0, n_prgs_ = 0, table_bits_ = 0;
-    hipStream_t stream_ = nullptr;
-    // index tables
-    void* d_slot_key_ = nullptr;
-    uint2* d_slot_rec_ = nullptr;
-    uint4* d_slot_first_ = nullptr;
-    uint32_t* d_rec_knode_ = nullptr;
-    uint16_t* d_rec_prg_ = nullptr;
-    uint32_t* d_min_path_len_ = nullptr;
-    uint32_t* d_prg_thr_ = nullptr;         // per PRG: floor(shortest k-mer path * cluster fraction), follows set_params
-    std::vector<uint32_t> h_min_path_len_;
-    uint32_t* d_bloom_ = nullptr;
-    uint32_t bloom_wbits_ = 0;
-    uint32_t* d_pbloom_ = nullptr; // Bloom tier of the direct kernel (large indexes)
-    uint32_t pbloom_wbits_ = 0;
-    uint32_t* d_bloom0_ = nullptr; // level 0 of the filter (k = 15, small indexes)
-    uint32_t* d_bloom0f_ = nullptr; // level 0 + second-stage bits in one array
-    uint32_t bloom0_wbits_ = 0;
-    uint32_t* d_bloomr_ = nullptr; // second stage of the level-0 form
-    // middle tier of the filter (FlatIndex::mid0 / mid_bitmap / midc): level 0 in LDS, the other two in global memory (L2-resident)
-    uint32_t *d_mid0_ = nullptr, *d_mid_bitmap_ = nullptr, *d_midc_ = nullptr;
-    uint32_t midc_wbits_ = 0, mid0_bits_ = 0;
-    uint32_t* d_blkc_ = nullptr; // small tier: the second stage as a split-block filter in global memory (FlatIndex::blkc)
-    uint32_t blkc_wbits_ = 0;
+    uint32_t n_knodes_ = 0, n_prgs_ = 0;
+    // The index on the device.  fill() refuses an index the kernels cannot address before it allocates anything, then uploads table by table.
+    struct IndexTables {
+        uint32_t table_bits = 0;
+        DeviceBuffer<unsigned char> slot_key; // u32 keys, u64 when wide_hash
+        DeviceBuffer<uint2> slot_rec;
+        DeviceBuffer<uint4> slot_first;
+        DeviceBuffer<uint32_t> rec_knode;
+        DeviceBuffer<uint16_t> rec_prg;
+        DeviceBuffer<uint32_t> min_path_len;
+        DeviceBuffer<uint32_t> prg_thr; // per PRG: floor(shortest k-mer path * cluster fraction), follows set_params
+        std::vector<uint32_t> h_min_path_len;
+        DeviceBuffer<uint32_t> bloom;
+        uint32_t bloom_wbits = 0;
+        DeviceBuffer<uint32_t> pbloom; // Bloom tier of the direct kernel (large indexes)
+        uint32_t pbloom_wbits = 0;
+        DeviceBuffer<uint32_t> bloom0;  // level 0 of the filter (k = 15, small indexes)
+        DeviceBuffer<uint32_t> bloom0f; // level 0 + second-stage bits in one array
+        uint32_t bloom0_wbits = 0;
+        DeviceBuffer<uint32_t> bloomr; // second stage of the level-0 form
+        // middle tier of the filter (FlatIndex::mid0 / mid_bitmap / midc): level 0 in LDS, the other two in global memory (L2-resident)
+        DeviceBuffer<uint32_t> mid0, mid_bitmap, midc;
+        uint32_t midc_wbits = 0, mid0_bits = 0;
+        DeviceBuffer<uint32_t> blkc; // small tier: the second stage as a split-block filter in global memory (FlatIndex::blkc)
+        uint32_t blkc_wbits = 0;
+        void fill(const FlatIndex& idx, bool wide_hash, uint64_t mid_max_records);
+        dev::BloomTables bloom_tables(bool mid) const; // what sketch_filter_kernel tests against (mid: in its middle-tier form)
+    };
+    IndexTables tables_;
     bool use_mid_ = false;                   // the filtered sequence runs in its middle-tier form
     int n_cus_ = 256;
     bool use_filter_ = false;
     bool use_direct_cands_ = false; // direct sketch kernel in its candidate form (read_cluster_kernel instead of sort + cluster kernels)
-    // accumulators
-    uint32_t* d_covg_ = nullptr;
-    uint32_t* d_prg_reads_ = nullptr;
-    unsigned long long* d_counters_ = nullptr; // 8 x u64: hits(batch), minimizers, clusters_kept, hits_kept, overflow, ...
-    unsigned long long* h_counters_ = nullptr; // pinned mirror
+    int sketch_form() const;
+    // accumulators: ONE allocation [coverage | reads per PRG]
+    DeviceBuffer<uint32_t> d_covg_;
+    DeviceBuffer<unsigned long long> d_counters_; // 8 x u64: hits(batch), minimizers, clusters_kept, hits_kept, overflow, ...
+    PinnedBuffer<unsigned long long> h_counters_; // pinned mirror
     // per-batch device counters are read back once per batch and summed here (an aborted attempt -- a buffer that has to
     // grow -- is simply not added, whatever sequence ran before it)
     uint64_t tot_reads_ = 0, tot_bases_ = 0, tot_hits_ = 0, tot_leftover_ = 0, tot_minimizers_ = 0;
-    // workspace
-    uint64_t hit_capacity_ = 0;
-    uint64_t *d_key_a_ = nullptr, *d_key_b_ = nullptr;
-    uint32_t *d_val_a_ = nullptr, *d_val_b_ = nullptr;
-    uint32_t *d_head_ = nullptr, *d_scan_ = nullptr, *d_cstart_ = nullptr, *d_order_ = nullptr;
-    dev::ClusterRec* d_clusters_ = nullptr;
+    // workspace of the generic pipeline: hit_capacity() entries each (d_cstart_ one more), d_temp_ what the sort and the scan ask for
+    DeviceBuffer<uint64_t> d_key_a_, d_key_b_;
+    DeviceBuffer<uint32_t> d_val_a_, d_val_b_;
+    DeviceBuffer<uint32_t> d_head_, d_scan_, d_cstart_, d_order_;
+    DeviceBuffer<dev::ClusterRec> d_clusters_;
+    DeviceBuffer<unsigned char> d_temp_;
+    uint64_t hit_capacity() const { return d_key_a_.size(); }
     Lane lanes_[2];
     // smallest capacity of the candidate / hit buffers, in entries (DRPRG_HIP_MIN_CAPACITY, taken at construction; tests lower it so that
     // small batches run at the production ratio -- n_bases / 48 for the filtered sequence --, or below it to make the buffers regrow)
     static constexpr uint64_t MIN_CAPACITY_CLAMP = 4096;
     uint64_t min_capacity_ = 1u << 20;
     uint64_t reruns_filter_ = 0, reruns_direct_ = 0, regrows_hits_ = 0; // buffer_info
-    void* d_temp_ = nullptr;
-    // candidate form of the direct sequence: one slice of `cap` records per tile.  One set of the workspace per lane (a batch's slices must
-    // survive until its read-back has been looked at: reads left to the generic pipeline are gathered from them)
+    // candidate form of the direct sequence: ws_tiles slices of ws_cap records, one slice per tile, with the per-tile counts and the scan's
+    // scratch (ensure_tile_workspace).  One set of the workspace per lane (a batch's slices must survive until its read-back has been
+    // looked at: reads left to the generic pipeline are gathered from them).  d_tile_first also serves the generic sequence (set 0).
     struct TileSet {
-        uint32_t slice_cap = 256, ws_tiles = 0, ws_cap = 0, first_cap = 0;
-        uint64_t* d_tile_info = nullptr;
-        uint32_t *d_tile_pos1 = nullptr, *d_tile_count = nullptr, *d_tile_hits = nullptr, *d_tile_nmin = nullptr, *d_tile_prefix = nullptr;
-        uint4* d_tile_rec = nullptr;
-        void* d_tile_temp = nullptr;
-        size_t tile_temp_bytes = 0;
-        uint32_t* d_tile_first = nullptr; // first read of every tile
-        // packed batches through sketch_wave_kernel: one bit per base, set for the positions in the batch's npos (allocated with the first
-        // batch that has any; all zero except between a launch and the next launch on this set)
-        uint16_t* d_nbits = nullptr;
-        uint64_t nbits_cap = 0; // u16 words
+        uint32_t slice_cap = 256, ws_tiles = 0, ws_cap = 0;
+        DeviceBuffer<uint64_t> d_tile_info;
+        DeviceBuffer<uint32_t> d_tile_pos1, d_tile_count, d_tile_hits, d_tile_nmin, d_tile_prefix;
+        DeviceBuffer<uint4> d_tile_rec;
+        DeviceBuffer<unsigned char> d_tile_temp;
+        DeviceBuffer<uint32_t> d_tile_first; // first read of every tile (reserve_tile_first)
+        // packed batches through sketch_wave_kernel: one bit per base in u16 words, set for the positions in the batch's npos (allocated
+        // with the first batch that has any; all zero except between a launch and the next launch on this set)
+        DeviceBuffer<uint16_t> d_nbits;
         bool nbits_dirty = false;
         uint32_t mark = 0, n_tiles = 0;   // of the batch in flight
         dev::SketchArgs a_done {};
     };
     TileSet tsets_[2];
-    TileSet* ts_ = &tsets_[0];
+    // the sketch's arguments for a batch; `tiles`: the tile set whose first-read table it fills -- tsets_[lane] for a direct batch,
+    // tsets_[0] for the generic sequence, null for the filtered sequence, whose kernels have no such table
+    dev::SketchArgs sketch_args(const DeviceBatch& batch, const TileSet* tiles) const;
     uint32_t slices_epoch_ = 0x80000000u; // mark of the last batch whose candidates read_cluster_kernel took from the slices
-    void free_tile_set(TileSet& t);
     void ensure_tile_workspace(TileSet& t, uint32_t n_tiles, uint32_t tile_cap);
-    size_t temp_bytes_ = 0;
-    // host staging: device buffers a host batch is copied into.  map_host has one set; map_host_async takes two in turn, their copies on
-    // a stream of their own
+    void reserve_tile_first(TileSet& t, uint32_t n_tiles);
+    // host staging: device buffers a host batch is copied into, each replaced by one a quarter larger when a batch does not fit it
+    // (ensure_stage).  map_host has one set; map_host_async takes two in turn, their copies on copy_stream_ with `copied` behind them
     struct Stage {
-        uint8_t* d_bases = nullptr;
-        uint64_t* d_offsets = nullptr;
-        uint64_t* d_npos = nullptr;
-        uint64_t bases_cap = 0, reads_cap = 0, npos_cap = 0;
-        hipEvent_t copied = nullptr;
+        DeviceBuffer<uint8_t> d_bases;
+        DeviceBuffer<uint64_t> d_offsets, d_npos;
+        Event copied;
     };
-    // room in `st` for a batch of these sizes (n_npos: 0 for an ASCII batch); a buffer that is too small is replaced by one a quarter larger
+    // room in `st` for a batch of these sizes (n_npos: 0 for an ASCII batch)
     void ensure_stage(Stage& st, uint64_t payload_bytes, uint64_t n_reads, uint64_t n_npos);
     Stage stage_[2], stage_sync_;
     // queues the copies of a host batch to these device addresses (d_npos: used when the batch lists positions) on `stream`; returns the
     // batch they will hold
     DeviceBatch copy_in(const HostBatch& hb, uint8_t* d_bases, uint64_t* d_offsets, uint64_t* d_npos, hipStream_t stream);
     int stage_next_ = 0;
-    hipStream_t copy_stream_ = nullptr;
     // sketch_filter_kernel's tile shares, followed from batch to batch ([0] ASCII, [1] packed input; {0}: the launcher's built-in ones so far)
     uint32_t ft_share_[2][4] = { { 0, 0, 0, 0 }, { 0, 0, 0, 0 } };
     uint64_t ft_last_[20] = {};
     void tune_filter_shares(const Lane& lane, bool packed, uint64_t n_bases);
     // keep_reads: device memory in large pieces, handed out front to back
-    std::vector<std::pair<void*, size_t>> kept_arenas_;
+    std::vector<DeviceBuffer<uint8_t>> kept_arenas_;
     uint8_t* arena_at_ = nullptr;
     size_t arena_left_ = 0;
     std::vector<DeviceBatch> kept_;
     uint64_t kept_cap_ = 0, kept_bytes_ = 0;
     bool kept_broken_ = false, in_keep_call_ = false;
-    hipEvent_t kept_copied_ = nullptr;
+    Event kept_copied_;
     void* arena_take(size_t bytes);
-    uint32_t* d_peer_tmp_ = nullptr; // add_vectors_from: the other device's vectors on this device
+    DeviceBuffer<uint32_t> d_peer_tmp_; // add_vectors_from: the other device's vectors on this device
     // timing
     bool timing_ = false;
     double sketch_ms_ = 0;
     uint64_t sketch_launches_ = 0;
-    hipEvent_t ev0_ = nullptr, ev1_ = nullptr;
+    Event ev0_, ev1_;
 };
 
 } // namespace drprg
