@@ -270,27 +270,50 @@ __global__ void read_inversion_kernel(const uint64_t* __restrict__ key, uint32_t
 
 constexpr int RS_THREADS = 256, RS_MAX = 1024;
 __global__ __launch_bounds__(RS_THREADS) void read_fix_kernel(uint64_t* __restrict__ key, uint32_t* __restrict__ val,
-    const uint2* __restrict__ list, const unsigned long long* __restrict__ count)
+    uint64_t* __restrict__ key_tmp, uint32_t* __restrict__ val_tmp, const uint2* __restrict__ list, const unsigned long long* __restrict__ count)
 {
     __shared__ uint64_t s_key[RS_MAX];
     __shared__ uint32_t s_val[RS_MAX];
     const uint32_t n_list = (uint32_t)*count;
     for (uint32_t r = blockIdx.x; r < n_list; r += gridDim.x) {
         const uint32_t start = list[r].x, len = list[r].y;
-        if (len > RS_MAX) { // not expected for short reads; correct but serial
-            if (threadIdx.x == 0)
-                for (uint32_t j = start + 1; j < start + len; ++j) {
-                    const uint64_t kj = key[j];
-                    const uint32_t vj = val[j];
-                    uint32_t p = j;
-                    while (p > start && key[p - 1] > kj) {
-                        key[p] = key[p - 1];
-                        val[p] = val[p - 1];
-                        --p;
+        if (len > RS_MAX) {
+            // More hits than the LDS arrays hold (a tiny k: every key has hundreds of records, a 150-base read 100 000 hits).  The same
+            // ranks, RS_THREADS hits at a time against tiles of the read's keys staged in LDS; the sorted copy is built in the radix sort's
+            // output arrays, which the per-read order leaves unused, and copied back.  (One thread sorting by insertion, as this was until
+            // (w, k) = (1, 1) ran it, moves len^2 / 4 hits through global memory: minutes per read.)
+            for (uint32_t t0 = 0; t0 < len; t0 += RS_THREADS) { // (block-uniform trip counts: the loops hold barriers)
+                const uint32_t t = t0 + threadIdx.x;
+                const bool mine = t < len;
+                const uint64_t kt = mine ? key[start + t] : 0;
+                uint32_t before = 0;
+                for (uint32_t j0 = 0; j0 < len; j0 += RS_MAX) {
+                    const uint32_t nj = len - j0 < (uint32_t)RS_MAX ? len - j0 : (uint32_t)RS_MAX;
+                    __syncthreads();
+                    for (uint32_t j = threadIdx.x; j < nj; j += RS_THREADS) s_key[j] = key[start + j0 + j];
+                    __syncthreads();
+                    if (!mine) continue;
+                    if (j0 + nj <= t) {
+                        for (uint32_t j = 0; j < nj; ++j) before += s_key[j] <= kt ? 1u : 0u; // earlier hits precede on ties
+                    } else if (j0 > t) {
+                        for (uint32_t j = 0; j < nj; ++j) before += s_key[j] < kt ? 1u : 0u;
+                    } else {
+                        const uint32_t tj = t - j0;
+                        for (uint32_t j = 0; j < tj; ++j) before += s_key[j] <= kt ? 1u : 0u;
+                        for (uint32_t j = tj + 1; j < nj; ++j) before += s_key[j] < kt ? 1u : 0u;
                     }
-                    key[p] = kj;
-                    val[p] = vj;
                 }
+                if (mine) {
+                    key_tmp[start + before] = kt;
+                    val_tmp[start + before] = val[start + t];
+                }
+            }
+            __syncthreads();
+            for (uint32_t t = threadIdx.x; t < len; t += RS_THREADS) {
+                key[start + t] = key_tmp[start + t];
+                val[start + t] = val_tmp[start + t];
+            }
+            __syncthreads();
             continue;
         }
         for (uint32_t t = threadIdx.x; t < len; t += RS_THREADS) {
@@ -506,14 +529,15 @@ hipError_t launch_filter_expand(const SketchArgs& a, const FilterWork& fw, hipSt
     return hipGetLastError();
 }
 
-hipError_t launch_read_sort(uint64_t* key, uint32_t* val, uint32_t n, uint32_t* scratch, uint64_t scratch_words, unsigned long long* count,
-    hipStream_t stream)
+hipError_t launch_read_sort(uint64_t* key, uint32_t* val, uint64_t* key_tmp, uint32_t* val_tmp, uint32_t n, uint32_t* scratch, uint64_t scratch_words,
+    unsigned long long* count, hipStream_t stream)
 {
     if (n < 2) return hipSuccess;
     uint2* list = reinterpret_cast<uint2*>(scratch);
     hipLaunchKernelGGL(read_inversion_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, key, n, list, (uint32_t)(scratch_words / 2), count);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(read_fix_kernel, dim3(128), dim3(RS_THREADS), 0, stream, key, val, list, count);
+    // (a grid-stride loop over the listed reads; 1 024 workgroups, so that a batch of hundreds of many-hit reads takes one round of them)
+    hipLaunchKernelGGL(read_fix_kernel, dim3(1024), dim3(RS_THREADS), 0, stream, key, val, key_tmp, val_tmp, list, count);
     return hipGetLastError();
 }
 

@@ -133,6 +133,7 @@ struct drprg_hip_ctx {
 };
 
 static thread_local std::string g_last_error;
+static thread_local int g_open_error = DRPRG_OK; // why the last drprg_hip_open* of this thread returned NULL
 
 #define API_BEGIN(ctx)                                  \
     if (!(ctx)) return DRPRG_EINVAL;                    \
@@ -265,12 +266,18 @@ int drprg_hip_index(const char* prg_file, int w, int k, int threads)
 static drprg_hip_ctx* open_impl(const char* prg_file, int w, int k, int device, bool from_files, int threads, const int* more_devices = nullptr,
     int n_more = 0)
 {
+    g_open_error = DRPRG_OK;
     if (!prg_file) {
         g_last_error = "null PRG path";
+        g_open_error = DRPRG_EINVAL;
         return nullptr;
     }
     std::unique_ptr<drprg_hip_ctx> ctx(new (std::nothrow) drprg_hip_ctx);
-    if (!ctx) return nullptr;
+    if (!ctx) {
+        g_last_error = "out of host memory";
+        g_open_error = DRPRG_ENOMEM;
+        return nullptr;
+    }
     // the HIP runtime starts (first call of the process: 50-250 ms) while the index files are read
     std::thread warm;
     if (device >= 0) warm = std::thread(Mapper::warm_device, device);
@@ -304,8 +311,13 @@ static drprg_hip_ctx* open_impl(const char* prg_file, int w, int k, int device, 
         if (warm.joinable()) warm.join();
         if (device >= 0) ctx->mapper.reset(new Mapper(ctx->index.flat, ctx->params, device));
         for (int i = 0; i < n_more; ++i) ctx->extra.emplace_back(new Mapper(ctx->index.flat, ctx->params, more_devices[i]));
+    } catch (const Error& e) {
+        g_last_error = e.what();
+        g_open_error = e.code;
+        return nullptr;
     } catch (const std::exception& e) {
         g_last_error = e.what();
+        g_open_error = DRPRG_EIO;
         return nullptr;
     }
     return ctx.release();
@@ -336,6 +348,8 @@ drprg_hip_ctx* drprg_hip_open_multi(const char* prg_file, int w, int k, const in
 }
 
 void drprg_hip_close(drprg_hip_ctx* ctx) { delete ctx; }
+
+int drprg_hip_open_error(void) { return g_open_error; }
 
 const char* drprg_hip_last_error(const drprg_hip_ctx* ctx) { return ctx ? ctx->last_error.c_str() : g_last_error.c_str(); }
 

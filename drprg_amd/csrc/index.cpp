@@ -28,9 +28,16 @@ std::string PrgIndex::gfa_path(const std::string& prg_file, const std::string& n
     return dir_of(prg_file) + "/kmer_prgs/" + name + ".k" + std::to_string(k) + ".w" + std::to_string(w) + ".gfa";
 }
 
+// the (w, k) every part of the product serves -- index builder, host-only context, Mapper::set_params -- and the tests hold against the oracle
+void PrgIndex::check_wk(int w, int k)
+{
+    if (k < 1 || k > 31) throw Error(DRPRG_EINVAL, "k must be in [1,31]");
+    if (w < 1 || w > 1024) throw Error(DRPRG_EINVAL, "w must be in [1,1024]");
+}
+
 void PrgIndex::build(const std::string& prg_file, int w_, int k_, int threads, const Switches& sw)
 {
-    if (k_ < 1 || k_ > 32 || w_ < 1) throw Error(DRPRG_EINVAL, "need 1 <= k <= 32 and w >= 1");
+    check_wk(w_, k_);
     w = w_;
     k = k_;
     prgs = load_prg_file(prg_file);
@@ -402,6 +409,7 @@ void PrgIndex::build_and_save(const std::string& prg_file, int w, int k, int thr
 
 void PrgIndex::load(const std::string& prg_file, int w_, int k_, const Switches& sw)
 {
+    check_wk(w_, k_);
     w = w_;
     k = k_;
     prgs = load_prg_file(prg_file);

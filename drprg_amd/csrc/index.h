@@ -66,6 +66,7 @@ struct PrgIndex {
 
     // `pandora index`: sketch every PRG of prg_file, write <prg_file>.k<k>.w<w>.idx and
     // <dir>/kmer_prgs/<name>.k<k>.w<w>.gfa.  sw: the filter tier's switches (force_mid_tier, mid_max_records) for the flattened tables
+    static void check_wk(int w, int k); // throws DRPRG_EINVAL outside 1 <= k <= 31, 1 <= w <= 1024
     static void build_and_save(const std::string& prg_file, int w, int k, int threads, const Switches& sw);
     // in-memory build (no files touched)
     void build(const std::string& prg_file, int w, int k, int threads, const Switches& sw);

@@ -294,10 +294,11 @@ hipError_t launch_direct_candidates(const SketchArgs& a, bool wide_hash, bool fo
 hipError_t launch_tile_gather_marked(const SketchArgs& a, const FilterWork& fw, const uint32_t* tile_prefix, uint32_t n_tiles, uint64_t dense_capacity,
     uint32_t mark, hipStream_t stream);
 hipError_t exclusive_scan_u32(void* temp, size_t temp_bytes, const uint32_t* in, uint32_t* out, uint32_t n, hipStream_t stream);
-// hits ordered by (read, pos) -> ordered by (read, prg, strand, pos), in place; meant for short reads.  scratch: u32
-// words (>= n) for the list of reads that need reordering; count: zeroed device scalar
-hipError_t launch_read_sort(uint64_t* key, uint32_t* val, uint32_t n, uint32_t* scratch, uint64_t scratch_words, unsigned long long* count,
-    hipStream_t stream);
+// hits ordered by (read, pos) -> ordered by (read, prg, strand, pos), in place; meant for short reads.  key_tmp / val_tmp: n entries each,
+// used for the reads with more hits than the kernel sorts in LDS.  scratch: u32 words (>= n) for the list of reads that need reordering;
+// count: zeroed device scalar
+hipError_t launch_read_sort(uint64_t* key, uint32_t* val, uint64_t* key_tmp, uint32_t* val_tmp, uint32_t n, uint32_t* scratch, uint64_t scratch_words,
+    unsigned long long* count, hipStream_t stream);
 size_t sort_temp_bytes(uint32_t n);
 size_t scan_temp_bytes(uint32_t n);
 hipError_t sort_hits(void* temp, size_t temp_bytes, const uint64_t* key_in, uint64_t* key_out, const uint32_t* val_in,

@@ -15,7 +15,7 @@ namespace drprg {
 
 // counter slots
 enum { C_HITS = 0, C_MINIMIZERS = 1, C_CLUSTERS_KEPT = 2, C_HITS_KEPT = 3, C_OVERFLOW = 4, C_MAXLEN = 5, C_UNSORTED = 6, C_COMPLEX = 7, C_N = 8 };
-// reads up to this length get their hits reordered per read (read_sort_kernel); longer ones take the radix sort
+// reads up to this length get their hits reordered per read (read_inversion_kernel, read_fix_kernel); longer ones take the radix sort
 constexpr uint64_t READ_SORT_MAX_LEN = 512;
 // candidate buffers of the filtered sequence: one entry per this many bases of the batch.  One per 64 is laid out by the tile; the quarter
 // added on top is kept for the small chunks of a dynamic schedule's last round (sketch_filter.hip launch_sketch_filter)
@@ -215,8 +215,7 @@ void Mapper::set_params(const MapParams& p)
 {
     sync(); // (a batch in flight was launched with the previous parameters)
     // validate everything before any state changes: a refused call leaves the previous parameters in force
-    if (p.k < 1 || p.k > 31) throw Error(DRPRG_EINVAL, "k must be in [1,31]");
-    if (p.w < 1 || p.w > 1024) throw Error(DRPRG_EINVAL, "w must be in [1,1024]");
+    PrgIndex::check_wk(p.w, p.k);
     const bool filter_ok = (tables_.bloom_wbits != 0 || tables_.midc_wbits != 0) && p.k <= 15 && p.w <= 16;
     if (p.kernel_mode < 0 || p.kernel_mode > 3) throw Error(DRPRG_EINVAL, "kernel must be 0 (auto), 1, 2 or 3");
     if (p.kernel_mode == 2 && !filter_ok)
@@ -393,7 +392,7 @@ void Mapper::cluster_hits(const uint64_t* d_offsets, uint32_t n_hits, bool order
     const uint64_t* s_key = d_key_b_.data();
     const uint32_t* s_val = d_val_b_.data();
     if (ordered) {
-        HIPCHK(dev::launch_read_sort(d_key_a_.data(), d_val_a_.data(), n_hits, d_order_.data(), hit_capacity(), d_unsorted, stream));
+        HIPCHK(dev::launch_read_sort(d_key_a_.data(), d_val_a_.data(), d_key_b_.data(), d_val_b_.data(), n_hits, d_order_.data(), hit_capacity(), d_unsorted, stream));
         s_key = d_key_a_.data();
         s_val = d_val_a_.data();
     } else HIPCHK(dev::sort_hits(d_temp_.data(), d_temp_.size(), d_key_a_.data(), d_key_b_.data(), d_val_a_.data(), d_val_b_.data(), n_hits, stream));

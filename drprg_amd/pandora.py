@@ -50,7 +50,7 @@ class Context:
         else:
             self._h = lib.drprg_hip_open(p, w, k, device) if from_files else lib.drprg_hip_open_prg(p, w, k, device, threads)
         if not self._h:
-            raise DependencyError("ProcessError", lib.drprg_hip_last_error(None).decode())
+            raise DependencyError("ProcessError", lib.drprg_hip_last_error(None).decode(), code=-lib.drprg_hip_open_error())
         self.w, self.k, self.device = w, k, device
         sizes = (C.c_uint64 * 5)()
         lib.drprg_hip_index_sizes(self._h, sizes)

@@ -56,6 +56,10 @@ int drprg_hip_index(const char* prg_file, int w, int k, int threads);
  * device < 0 opens a host-only context: index export and genotyping work, every map call fails with
  * -ENODEV (there is no CPU fallback for the hot path).  Returns NULL on failure. */
 drprg_hip_ctx* drprg_hip_open(const char* prg_file, int w, int k, int device);
+/* Why the last drprg_hip_open / _open_prg / _open_multi of the calling thread returned NULL (a negative errno-style code; 0 if it did
+ * not): -EINVAL for a (w, k) outside 1 <= k <= 31, 1 <= w <= 1024 -- the range every part of the library serves, drprg_hip_index and a
+ * host-only context included.  drprg_hip_last_error(NULL) has the message. */
+int drprg_hip_open_error(void);
 
 /* Same, but sketches the PRG in memory instead of reading .idx / kmer_prgs (no files needed or written). */
 drprg_hip_ctx* drprg_hip_open_prg(const char* prg_file, int w, int k, int device, int threads);

@@ -318,17 +318,41 @@ def _walk_end(tr, cls, pred, make, lo, hi, i):
     return False
 
 
-def _build_size(oracle, term, illumina, n_pairs):
+def _step_lengths(tr, w, lo, hi):
+    """the read lengths in [lo, hi) at which floor(fraction * (2 len / (w + 1))) takes a value for the first time, and the length before each"""
+    out = []
+    for e in range(2 * lo // (w + 1), 2 * hi // (w + 1) + 1):
+        length = (e * (w + 1) + 1) // 2  # the first length with 2 len / (w + 1) == e
+        if lo <= length < hi and tr.thr(length, mcs=0) > tr.thr(length - 1, mcs=0):
+            out += [length - 1, length]
+    return out
+
+
+def _bisect_block(tr, make, lo, hi):
+    """narrows [lo, hi] to a dozen block lengths around the one at which the largest run of make(b) first exceeds its threshold (the hits grow
+    with the block): _walk_end then takes them a base at a time"""
+    over = lambda b: (lambda r: r is not None and r["n"] > r["thr"])(_largest(tr(make(b))))
+    if over(lo) or not over(hi):
+        return lo, lo
+    while hi - lo > 8:
+        mid = (lo + hi) // 2
+        lo, hi = (lo, mid) if over(mid) else (mid, hi)
+    return max(K, lo - 2), hi + 2
+
+
+def _build_size(oracle, term, illumina, n_pairs, w=11, panel="main", mcs=10):
+    """w, panel, mcs: the `len` term at another window, on the long locus of sweep_panel() (tests/wk_range.py)"""
     tech = "illumina" if illumina else "nanopore"
-    cls = EdgeClass(f"size_{term}_{tech}", "size_" + term, illumina, 10)
-    tr = Tracer(oracle, "main", 11, illumina, 10)
-    seqs = main_panel(oracle)[1]["seqs"]
-    rng = np.random.default_rng(10 + 2 * ("mcs", "path", "len").index(term) + illumina)
+    cls = EdgeClass(f"size_{term}_{tech}" + (f"_w{w}" if w != 11 else ""), "size_" + term, illumina, mcs, w=w, panel=panel)
+    tr = Tracer(oracle, panel, w, illumina, mcs)
+    seqs = panel_of(oracle, panel)[1]["seqs"]
+    rng = np.random.default_rng(10 + 2 * ("mcs", "path", "len").index(term) + illumina + (1000 * w if w != 11 else 0))
     pred = lambda t, side: is_size(t, tr, side, term)
     i = 0
+    steps = []
     while len(cls.on) < n_pairs and cls.proposed < 40 * n_pairs:
         cls.proposed += 1
-        fill = _seq(rng, 3000)
+        fill = _seq(rng, 3000 if panel == "main" else 6000)
         if term == "mcs":      # a block that holds about min_cluster_size hits; the read is short (Illumina) or its fraction small (Nanopore)
             src = seqs["b"] if i % 2 else seqs["a"][:1500]
             s = int(rng.integers(0, len(src) - 130))
@@ -341,6 +365,17 @@ def _build_size(oracle, term, illumina, n_pairs):
             s = int(rng.integers(0, 60))
             make = lambda b: fill[:100] + src[s:s + b] + fill[100:100 + total - 100 - b]
             lo, hi = (360, 520) if illumina else (60, 160)
+        elif panel == "sweep":  # the same at a window of hundreds of k-mers: reads of thousands of bases, half of them of a length at which
+            # the threshold steps (or one base short of it)
+            src = seqs["long"][1300:]  # (behind the stretch the panel holds twice)
+            if not steps:
+                steps.extend(_step_lengths(tr, w, 1500, 6000))
+            total = steps[cls.proposed // 2 % len(steps)] if cls.proposed % 2 else int(rng.integers(int((w + 1) / tr.frac) + 200, 6000))
+            s = int(rng.integers(0, len(src) - total))
+            make = lambda b: src[s:s + b] + fill[:total - b]
+            lo, hi = K, min(total, 3 * (w + 1) + (w + 1) * tr.thr(total) // 2 * 3)
+            lo, hi = _bisect_block(tr, make, lo, hi)
+            hi = min(hi, total)
         else:                  # a read shorter than the locus: floor(2 len / (w + 1) * fraction)
             src = seqs["b"] if i % 2 else seqs["a"][:1500]
             total = int(rng.integers(140, 400)) if illumina else int(rng.integers(700, 1400))

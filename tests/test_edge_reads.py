@@ -109,3 +109,15 @@ def test_device_reciprocal_is_the_division():
         x = np.arange(1, ((1 << 24) - 1) // (w + 1) + 1, dtype=np.uint64) * d
         for v in (x, x - np.uint64(1)):
             assert np.array_equal((v * magic) >> np.uint64(32), v // d), w
+    # From w = 200 on the device divides: `return len * 2 / (uint64_t)(w + 1)` -- the oracle's own expression.  What is restated here is why the
+    # switch must stay where it is: past it the product x * M no longer has its quotient in the high word for every 2 len < 2^24
+    # (x * (d * M - 2^32) < 2^32 fails), so a wider `w <` would be wrong at some w in 200 .. 1024 and some length the hit key takes.
+    assert "returnlen*2/(uint64_t)(w+1);" in src and src.count("w<200&&") == 1
+    wrong = 0
+    for w in range(200, 1025):
+        d = np.uint64(w + 1)
+        magic = np.uint64((1 << 32) // (w + 1) + 1)
+        x = np.arange(1, ((1 << 24) - 1) // (w + 1) + 1, dtype=np.uint64) * d
+        for v in (x, x - np.uint64(1)):
+            wrong += int(((v * magic) >> np.uint64(32) != v // d).any())
+    assert wrong > 0, "the reciprocal would serve every w: the device's w < 200 could go"
