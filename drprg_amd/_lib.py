@@ -86,6 +86,9 @@ SIGNATURES = {
     "drprg_hip_device_coverage": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "drprg_hip_reset": (C.c_int, [C.c_void_p]),
     "drprg_hip_set_max_covg": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "drprg_hip_pack_device_bam": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
+                                            C.POINTER(C.c_uint64), C.c_void_p]),
+    "drprg_hip_bam_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "drprg_hip_max_covg_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "drprg_hip_keep_reads": (C.c_int, [C.c_void_p, C.c_uint64]),
     "drprg_hip_map_resident": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -8,6 +8,7 @@
 #include "../../include/drprg_hip.h"
 #include "fastx.h"
 #include "genotype.h"
+#include "bam.h"
 #include "ingest.h"
 #include "pgunzip.h"
 #include "denovo.h"
@@ -102,6 +103,7 @@ struct drprg_hip_ctx {
     uint64_t max_covg = ~0ull; // off
     bool cap_reached = false;
     uint64_t accepted_reads = 0, dropped_reads = 0;
+    uint64_t bam_records = 0, bam_skipped = 0, bam_reversed = 0; // drprg_hip_bam_info: of the BAM files mapped since the last reset
     bool bases_without_reads = false; // total_bases holds bases that came with a coverage vector (set_coverage, load_coverage): accepted_reads does not stand for them
     int threads = 4; // parser threads of drprg_hip_map_fastx
     bool packed_input = false; // drprg_hip_set_input_format: map_fastx packs the reads to 2 bits on the parser threads
@@ -430,6 +432,11 @@ static void cap_host_cut(const drprg_hip_ctx* ctx, Mapper::HostBatch& hb, CapCut
 {
     hb.n_reads = cap_host_prefix(ctx, hb.offsets, hb.n_reads, c);
     if (hb.packed) hb.n_npos = (uint64_t)(std::lower_bound(hb.npos, hb.npos + hb.n_npos, hb.n_bases()) - hb.npos); // (all of them unless the batch was cut)
+    if (hb.bam && c.dropped) { // the cut is made on the offsets, before the conversion: the fields of the accepted reads, their non-ACGT codes counted again
+        hb.seq_bytes = hb.seq_start[hb.n_reads];
+        hb.n_npos = 0;
+        for (uint64_t i = 0; i < hb.n_reads; ++i) hb.n_npos += bam::count_non_acgt(hb.bases + hb.seq_start[i], (uint32_t)(hb.offsets[i + 1] - hb.offsets[i]));
+    }
 }
 
 // The same for a device batch, whose offsets only the device can read: a batch below the cap is accepted as it is, without a look
@@ -465,7 +472,10 @@ int drprg_hip_map_fastx(drprg_hip_ctx* ctx, const char* reads_path)
     // multi-threaded ingest into pinned blocks (ingest.cpp); multi-line FASTQ falls back to the serial reader
     IngestHooks hooks;
     hooks.packed = ctx->packed_input;
-    auto host_batch = [](const PinnedBatch& b) { return Mapper::HostBatch { b.bases, b.offsets, b.n_reads, b.packed, b.npos, b.n_npos }; };
+    hooks.bam_native = true; // a BAM file's reads travel in their 4-bit form and are converted on the device (bam_pack.hip), whatever `packed` says
+    auto host_batch = [](const PinnedBatch& b) {
+        return Mapper::HostBatch { b.bases, b.offsets, b.n_reads, b.packed, b.npos, b.n_npos, b.bam, b.seq_start, b.reverse, b.seq_bytes };
+    };
     uint64_t cap_T = 0;
     const bool capped = cap_target(ctx, cap_T);
     // page-locked ingest blocks are kept by the process between calls and contexts (PinPool)
@@ -520,6 +530,9 @@ int drprg_hip_map_fastx(drprg_hip_ctx* ctx, const char* reads_path)
     };
     try {
         IngestStats st = ingest_fastx(reads_path, ctx->threads, hooks);
+        ctx->bam_records += st.bam_records;
+        ctx->bam_skipped += st.bam_skipped;
+        ctx->bam_reversed += st.bam_reversed;
         if (capped) ctx->dropped_reads += st.discarded_reads; // (the accepted ones were counted block by block)
         else {
             ctx->total_bases += st.bases;
@@ -672,6 +685,30 @@ int drprg_hip_pack_device(drprg_hip_ctx* ctx, const void* d_bases, uint64_t n_ba
     if (!n_npos) throw Error(DRPRG_EINVAL, "null n_npos");
     *n_npos = m.pack_on_device((const uint8_t*)d_bases, n_bases, (uint32_t*)d_words, (uint64_t*)d_npos, npos_cap, (hipStream_t)hip_stream);
     if (*n_npos > npos_cap) throw Error(DRPRG_EOVERFLOW, "more non-ACGT bases than the position buffer holds");
+    API_END(ctx)
+}
+
+int drprg_hip_pack_device_bam(drprg_hip_ctx* ctx, const void* d_seq, const void* d_seq_start, const void* d_offsets, const void* d_reverse, uint64_t n_reads,
+    uint64_t n_bases, void* d_words, void* d_npos, uint64_t npos_cap, uint64_t* n_npos, void* hip_stream)
+{
+    API_BEGIN(ctx)
+    Mapper& m = need_mapper(ctx);
+    if (!n_npos) throw Error(DRPRG_EINVAL, "null n_npos");
+    *n_npos = m.pack_bam_on_device((const uint8_t*)d_seq, (const uint64_t*)d_seq_start, (const uint64_t*)d_offsets, (const uint8_t*)d_reverse, n_reads, n_bases,
+        (uint32_t*)d_words, (uint64_t*)d_npos, npos_cap, (hipStream_t)hip_stream);
+    if (*n_npos > npos_cap) throw Error(DRPRG_EOVERFLOW, "more non-ACGT bases than the position buffer holds");
+    API_END(ctx)
+}
+
+int drprg_hip_bam_info(drprg_hip_ctx* ctx, uint64_t out[4])
+{
+    API_BEGIN(ctx)
+    if (!out) throw Error(DRPRG_EINVAL, "null output");
+    out[0] = ctx->bam_records;
+    out[1] = ctx->bam_skipped;
+    out[2] = ctx->bam_reversed;
+    out[3] = 0;
+    for (Mapper* m : mappers_of(ctx)) out[3] += m->bam_blocks();
     API_END(ctx)
 }
 
@@ -874,6 +911,7 @@ int drprg_hip_reset(drprg_hip_ctx* ctx)
     ctx->total_bases = 0;
     ctx->cap_reached = false; // (the cap itself stays)
     ctx->accepted_reads = ctx->dropped_reads = 0;
+    ctx->bam_records = ctx->bam_skipped = ctx->bam_reversed = 0;
     ctx->bases_without_reads = false;
     ctx->mapped_paths.clear();
     ctx->needs_reset = false;

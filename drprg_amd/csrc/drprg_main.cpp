@@ -105,7 +105,7 @@ std::string file_prefix(const std::string& path) // PathExt::prefix: file name u
 void usage()
 {
     std::fprintf(stderr,
-        "drprg predict -x <index dir | species[@version]> -i <reads.fq[.gz]> [-o DIR] [-s SAMPLE] [-I] [-S]\n"
+        "drprg predict -x <index dir | species[@version]> -i <reads.fq[.gz] | reads.bam> [-o DIR] [-s SAMPLE] [-I] [-S]\n"
         "              [-f MAF] [-d MIN_COVG] [-D MAX_COVG] [-b MIN_STRAND_BIAS] [-g MIN_GT_CONF] [-L MAX_INDEL] [-K MIN_FRS]\n"
         "              [-C MIN_CLUSTER_SIZE] [--debug] [-v] [-t THREADS] [--rebuild-index]\n"
         "MI355X-native hot path; -p/-m/-M (external tools) are accepted and not needed: novel variants update the PRG in process.\n");
@@ -305,6 +305,10 @@ int main(int argc, char** argv)
         drprg_hip_genotype_info(ctx, gi);
         std::fprintf(stderr, "[drprg-hip +%.3fs] reads=%llu hits=%llu clusters=%llu exp_depth_covg=%u loci_present=%u records=%u\n",
             since_start(), (unsigned long long)c[0], (unsigned long long)c[3], (unsigned long long)c[4], gi[0], gi[2], gi[3]);
+        uint64_t bi[4] = { 0, 0, 0, 0 };
+        if (drprg_hip_bam_info(ctx, bi) == 0 && bi[0])
+            std::fprintf(stderr, "[drprg-hip +%.3fs] bam: records=%llu skipped=%llu (secondary / supplementary) reverse-complemented=%llu blocks converted on the device=%llu\n",
+                since_start(), (unsigned long long)bi[0], (unsigned long long)bi[1], (unsigned long long)bi[2], (unsigned long long)bi[3]);
     }
     drprg_hip_close(ctx);
     if (verbose) std::fprintf(stderr, "[drprg-hip +%.3fs] device context closed\n", since_start());

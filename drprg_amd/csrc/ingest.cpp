@@ -1,5 +1,6 @@
 // ingest.cpp -- see ingest.h
 #include "ingest.h"
+#include "bam.h"
 #include "pack.h"
 #include "pgunzip.h"
 #include <atomic>
@@ -62,6 +63,11 @@ struct Block {
     uint64_t n_reads = 0, n_bases = 0;
     bool packed = false;
     std::vector<uint64_t> npos; // packed: positions of the bases that are not ACGTacgt
+    // BAM's own form (PinnedBatch::bam): `bases` holds the 4-bit sequence fields back to back
+    bool bam = false;
+    uint64_t* seq_start = nullptr; // inside the allocation of `offsets`, as is ...
+    uint8_t* reverse = nullptr;    // ... this
+    uint64_t seq_bytes = 0, n_non_acgt = 0;
     // the bases of one read (or one line of a multi-line record) behind what the block holds
     inline void append(const char* seq, size_t len)
     {
@@ -77,6 +83,18 @@ struct Block {
     // copy engine idles until then and works through a burst afterwards (measured: 10 M x 150 bp, first copies at 67 of 95 ms)
     size_t flush_at = 0;
     uint64_t seq = 0; // ordered hand-over: the slice its reads come from
+    PinnedBatch view() const
+    {
+        PinnedBatch pb { bases, offsets, n_reads, n_bases };
+        pb.packed = packed;
+        pb.npos = bam ? nullptr : npos.data();
+        pb.n_npos = bam ? n_non_acgt : npos.size();
+        pb.bam = bam;
+        pb.seq_start = seq_start;
+        pb.reverse = reverse;
+        pb.seq_bytes = seq_bytes;
+        return pb;
+    }
 };
 
 struct Shared {
@@ -100,6 +118,9 @@ struct Shared {
     struct StopParse {}; // thrown out of parse_slice once the hook has said stop
     std::string error;
     int error_code = DRPRG_EFORMAT;
+    // BAM input (set before the first slice is queued): its records seen / skipped / reverse-complemented
+    std::atomic<bool> bam { false };
+    std::atomic<uint64_t> bam_records { 0 }, bam_skipped { 0 }, bam_reversed { 0 };
 
     explicit Shared(const IngestHooks& h) : hooks(h), ordered((bool)h.submit_in_order) {}
     void fail(int code, const std::string& m)
@@ -118,6 +139,8 @@ struct Shared {
     {
         b.n_reads = 0;
         b.n_bases = 0;
+        b.seq_bytes = 0;
+        b.n_non_acgt = 0;
         b.npos.clear();
         if (b.packed) reinterpret_cast<uint64_t*>(b.bases)[0] = 0; // (pack_append: a fresh stream)
         b.flush_at = BLOCK_BASES;
@@ -144,10 +167,7 @@ struct Shared {
             return;
         }
         if (b.n_reads) {
-            PinnedBatch pb { b.bases, b.offsets, b.n_reads, b.n_bases };
-            pb.packed = b.packed;
-            pb.npos = b.npos.data();
-            pb.n_npos = b.npos.size();
+            const PinnedBatch pb = b.view();
             struct Wake { // (a hook that throws: the thread reports the failure, the others must not wait for this turn)
                 std::condition_variable& cv;
                 ~Wake() { cv.notify_all(); }
@@ -173,10 +193,7 @@ struct Shared {
             return;
         }
         if (b.n_reads == 0) return;
-        PinnedBatch pb { b.bases, b.offsets, b.n_reads, b.n_bases };
-        pb.packed = b.packed;
-        pb.npos = b.npos.data();
-        pb.n_npos = b.npos.size();
+        const PinnedBatch pb = b.view();
         const int64_t t0 = debug ? now_ns() : 0;
         if (debug) {
             int64_t none = -1;
@@ -200,12 +217,19 @@ struct Shared {
     Block new_block()
     {
         Block b;
-        b.packed = hooks.packed;
-        const size_t bytes_b = (b.packed ? BLOCK_BASES / 4 + 16 : BLOCK_BASES) + 64, bytes_o = (BLOCK_READS + 2) * sizeof(uint64_t);
+        b.bam = bam && hooks.bam_native;
+        b.packed = hooks.packed && !b.bam;
+        // (BAM's form: a read of n bases takes (n + 1) / 2 bytes; seq_start and reverse live behind the offsets)
+        const size_t bytes_b = (b.bam ? BLOCK_BASES / 2 + BLOCK_READS : b.packed ? BLOCK_BASES / 4 + 16 : BLOCK_BASES) + 64;
+        const size_t bytes_o = (BLOCK_READS + 2) * sizeof(uint64_t) * (b.bam ? 2 : 1) + (b.bam ? BLOCK_READS + 64 : 0);
         b.bases = (uint8_t*)(hooks.alloc ? hooks.alloc(bytes_b) : std::malloc(bytes_b));
         b.offsets = (uint64_t*)(hooks.alloc ? hooks.alloc(bytes_o) : std::malloc(bytes_o));
         if (!b.bases || !b.offsets) throw Error(DRPRG_ENOMEM, "cannot allocate an ingest block");
         b.offsets[0] = 0;
+        if (b.bam) {
+            b.seq_start = b.offsets + BLOCK_READS + 2;
+            b.reverse = reinterpret_cast<uint8_t*>(b.seq_start + BLOCK_READS + 2);
+        }
         if (b.packed) reinterpret_cast<uint64_t*>(b.bases)[0] = 0;
         // first hand-over: between 1/16 and 16/16 of a block, a different sixteenth for consecutive workers
         b.flush_at = BLOCK_BASES / 16 * (1 + (size_t)(first_flush.fetch_add(1) % 16));
@@ -366,6 +390,49 @@ void parse_slice(const char* p, const char* e, bool fastq, Block& blk, Shared& s
             blk.offsets[++blk.n_reads] = blk.n_bases;
             p = rec_end;
         }
+    }
+}
+
+// the records of [p, e) of a BAM stream (whole records only: bam::whole_records) into the block, as parse_slice does for text
+void parse_bam_slice(const uint8_t* p, const uint8_t* e, Block& blk, Shared& sh)
+{
+    struct Tally { // (a hand-over may end the slice by an exception)
+        Shared& sh;
+        uint64_t records = 0, skipped = 0, reversed = 0;
+        ~Tally()
+        {
+            sh.bam_records += records;
+            sh.bam_skipped += skipped;
+            sh.bam_reversed += reversed;
+        }
+    } tally { sh };
+    std::vector<char> text;
+    while (p < e) {
+        const bam::Record r = bam::parse_record(p);
+        p += r.bytes;
+        ++tally.records;
+        if (r.skipped()) {
+            ++tally.skipped;
+            continue;
+        }
+        const size_t len = r.l_seq;
+        if (len > BLOCK_BASES) throw Error(DRPRG_EOVERFLOW, "a read is longer than the ingest block");
+        if (blk.n_bases + len > blk.flush_at || blk.n_reads + 1 > BLOCK_READS) sh.submit(blk);
+        if (blk.bam) {
+            const size_t nb = (len + 1) / 2;
+            std::memcpy(blk.bases + blk.seq_bytes, r.seq, nb);
+            blk.seq_start[blk.n_reads] = blk.seq_bytes;
+            blk.reverse[blk.n_reads] = r.reverse() ? 1 : 0;
+            blk.seq_bytes += nb;
+            blk.n_non_acgt += bam::count_non_acgt(r.seq, r.l_seq); // (the bytes are in the cache now: no read-back from the device later)
+            blk.n_bases += len;
+        } else {
+            text.resize(len);
+            bam::to_text(r.seq, r.l_seq, r.reverse(), text.data());
+            blk.append(text.data(), len);
+        }
+        blk.offsets[++blk.n_reads] = blk.n_bases;
+        if (r.reverse()) ++tally.reversed;
     }
 }
 
@@ -610,7 +677,8 @@ IngestStats ingest_fastx(const std::string& path, int threads, const IngestHooks
                         }
                         if (sh.debug) sh.ns_read += sh.now_ns() - t0;
                         parse_slice(own_text->data(), own_text->data() + s.file_len, fastq, blk, sh);
-                    } else parse_slice(s.begin, s.end, fastq, blk, sh);
+                    } else if (sh.bam) parse_bam_slice((const uint8_t*)s.begin, (const uint8_t*)s.end, blk, sh);
+                    else parse_slice(s.begin, s.end, fastq, blk, sh);
                     if (sh.ordered) sh.submit_ordered(blk, true); // (a block never spans two slices: the next slice may be far away in the file)
                 } catch (const Shared::StopParse&) { // the hook has what it wanted: the rest of the slice is not parsed
                 }
@@ -760,6 +828,11 @@ IngestStats ingest_fastx(const std::string& path, int threads, const IngestHooks
             } unmap { gz_map, gz_len };
             std::vector<BgzfBlock> blocks;
             if (gz_data && ld.ok()) blocks = bgzf_index(gz_data, gz_len);
+            // BAM = BGZF whose inflated stream starts with the BAM magic (bam.h); whichever way inflates it
+            unsigned char head[64];
+            const ssize_t head_n = pread(fd, head, sizeof head, 0);
+            const bool bgzf = !blocks.empty() || (head_n > 0 && bgzf_member_size(head, (size_t)head_n) != 0);
+            bool bam_header_done = false;
             std::unique_ptr<ParallelGunzip> pgz; // way (4)
             if (gz_data && blocks.empty() && par_ok) {
                 const char* chunk_env = std::getenv("DRPRG_GZ_CHUNK");
@@ -894,12 +967,34 @@ IngestStats ingest_fastx(const std::string& path, int threads, const IngestHooks
                 const char* b = buf->data();
                 const char* e = b + have;
                 if (!format_known) {
-                    if (!detect_format(b, e, fastq)) continue;
-                    if (fastq) require_four_line_fastq(b, e);
+                    if (bgzf && bam::is_magic((const uint8_t*)b, have)) sh.bam = true;
+                    else {
+                        if (!detect_format(b, e, fastq)) continue;
+                        if (fastq) require_four_line_fastq(b, e);
+                    }
                     format_known = true;
                 }
                 const char* cut = e;
-                if (!eof) {
+                if (sh.bam) {
+                    // One thread hops the block_size chain: whole records go to a parser thread, a record that runs past the window --
+                    // in any field, the block_size word included -- is carried into the next one.  No sequence byte is touched here.
+                    if (!bam_header_done) {
+                        const size_t hb = bam::header_bytes((const uint8_t*)b, have);
+                        if (!hb) {
+                            if (eof) throw Error(DRPRG_EFORMAT, "the BAM header runs past the end of " + path);
+                            carry.assign(b, e);
+                            continue;
+                        }
+                        bam_header_done = true;
+                        b += hb;
+                    }
+                    cut = b + bam::whole_records((const uint8_t*)b, (size_t)(e - b));
+                    if (cut < e) {
+                        if (eof) throw Error(DRPRG_EFORMAT, "a BAM record runs past the end of " + path);
+                        carry.assign(cut, e);
+                    }
+                    if (cut == b) continue;
+                } else if (!eof) {
                     // last record start in the final MB of the buffer: everything after it is carried over
                     const char* scan = have > (1u << 20) ? e - (1u << 20) : b;
                     const char* last = nullptr;
@@ -928,6 +1023,10 @@ IngestStats ingest_fastx(const std::string& path, int threads, const IngestHooks
     st.batches = sh.batches;
     st.discarded_reads = sh.discarded;
     st.parallel = threads > 1;
+    st.bam = sh.bam;
+    st.bam_records = sh.bam_records;
+    st.bam_skipped = sh.bam_skipped;
+    st.bam_reversed = sh.bam_reversed;
     if (sh.debug)
         std::fprintf(stderr, "[ingest] wall %.1f ms, %llu batches, first hand-over at %.1f ms; summed over the %zu parser threads: parse (hand-overs included) %.1f ms, "
                              "waiting for the submitter %.1f ms, inside the submitter %.1f ms, block allocation %.1f ms, reading the file %.1f ms\n", sh.now_ns() / 1e6,

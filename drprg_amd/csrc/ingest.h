@@ -1,4 +1,4 @@
-// ingest.h -- multi-threaded FASTA/FASTQ ingest for the CLI path (NEXT-4).
+// ingest.h -- multi-threaded FASTA/FASTQ/BAM ingest for the CLI path (NEXT-4).
 //
 // The kernels map 10 M reads in under 2 ms; end to end the path is bound by text parsing and the host->device copy.
 // A plain file is memory-mapped and cut at record boundaries into slices that worker threads parse straight into
@@ -17,6 +17,13 @@ struct PinnedBatch {
     bool packed = false;
     const uint64_t* npos = nullptr; // packed: ascending positions of the bases that are not ACGTacgt (pageable memory)
     uint64_t n_npos = 0;
+    // BAM's own form (IngestHooks::bam_native; bam.h): `bases` holds the concatenated 4-bit sequence fields (seq_bytes of them, high
+    // nibble first), read i starts at byte seq_start[i], is offsets[i + 1] - offsets[i] bases long and is the reverse complement of its
+    // field when reverse[i] != 0.  n_npos counts the codes that are not A, C, G or T; npos is null (the device makes the list).
+    bool bam = false;
+    const uint64_t* seq_start = nullptr;
+    const uint8_t* reverse = nullptr;
+    uint64_t seq_bytes = 0;
 };
 
 struct IngestHooks {
@@ -31,6 +38,9 @@ struct IngestHooks {
     // handed over, the parser threads take no new slices and the rest of the file is not read.  For callers whose result depends on
     // which reads come first (the depth cap, drprg_hip_set_max_covg); everything else keeps the unordered hand-over.
     std::function<bool(const PinnedBatch&)> submit_in_order;
+    // A BAM file's reads are handed over in BAM's 4-bit form (PinnedBatch::bam; `packed` does not apply to them).  false: the parser
+    // threads convert them to upper-case text, and the hooks see the ASCII (or packed) blocks the FASTQ of the same reads would give.
+    bool bam_native = false;
 };
 
 struct IngestStats {
@@ -39,9 +49,12 @@ struct IngestStats {
     bool parallel = false;
     int gz_mode = 0; // 0 plain text, 1 BGZF (members inflated in parallel), 2 one gzip member in one libdeflate call, 3 zlib streaming,
                      // 4 one plain gzip stream inflated by all threads (pgunzip.h)
+    // BAM input (bam.h): records seen, records skipped (secondary / supplementary), reads that were reverse-complemented
+    bool bam = false;
+    uint64_t bam_records = 0, bam_skipped = 0, bam_reversed = 0;
 };
 
-// Parses `path` (fasta/fastq, plain or .gz) with `threads` parser threads and feeds every batch to hooks.submit.
+// Parses `path` (fasta/fastq, plain or .gz; or BAM) with `threads` parser threads and feeds every batch to hooks.submit.
 // Throws Error on malformed input.
 IngestStats ingest_fastx(const std::string& path, int threads, const IngestHooks& hooks);
 

@@ -319,6 +319,19 @@ hipError_t launch_mark_npos(const uint64_t* npos, uint64_t n_npos, uint64_t n_ba
 hipError_t launch_pack(const uint8_t* bases, uint64_t n_bases, uint32_t* words, uint64_t* npos, uint64_t npos_cap, unsigned long long* n_npos,
     hipStream_t stream);
 
+// bam_pack.hip: a batch whose sequences are in BAM's 4-bit form (code i of "=ACMGRSVTWYHKDBN" per base, high nibble first) -> the packed
+// form.  Read i is offsets[i + 1] - offsets[i] bases long, its field starts at byte seq_start[i] of seq (the fields need not be adjacent
+// or in order) and the read is the field's reverse complement when reverse[i] != 0 (reverse == nullptr: none is).  words:
+// ceil(n_bases / 16), tail bits of the last word clear, one 16-byte store per four words when words is 16-byte aligned.  A code other
+// than A, C, G, T gets the letter of its upper-case character and is a non-ACGT position: words and positions are what launch_pack makes
+// of the upper-case text of the same reads.  list: chunk_prefix[bam_pack_chunks(n_bases)] receives the number of those positions (below
+// 2^32) and -- npos != nullptr -- the first npos_cap of them are written to npos, ASCENDING.  chunk_count / chunk_prefix:
+// bam_pack_chunks(n_bases) + 1 words each; temp: scan_temp_bytes(bam_pack_chunks(n_bases) + 1) bytes; none is touched when !list ...
+// except chunk_count, which the first launch always fills.
+uint32_t bam_pack_chunks(uint64_t n_bases);
+hipError_t launch_bam_pack(const uint8_t* seq, const uint64_t* seq_start, const uint64_t* offsets, const uint8_t* reverse, uint64_t n_reads, uint64_t n_bases,
+    uint32_t* words, uint64_t* npos, uint64_t npos_cap, bool list, uint32_t* chunk_count, uint32_t* chunk_prefix, void* temp, size_t temp_bytes, hipStream_t stream);
+
 // covg_cut.hip: the read at which a device batch crosses the depth cap.  out (page-locked host memory, device address): out[0] = the smallest
 // i in [1, n_reads] with offsets[i] >= target (n_reads if none), out[1] = offsets[i], out[2] = how many of the n_npos ascending positions
 // in npos lie below offsets[i].  One wave; n_reads >= 1.

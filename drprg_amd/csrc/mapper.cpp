@@ -244,6 +244,7 @@ void Mapper::reset_coverage(bool new_sample)
     HIPCHK(hipMemsetAsync(d_counters_.data(), 0, d_counters_.bytes(), stream_));
     HIPCHK(hipStreamSynchronize(stream_));
     tot_reads_ = tot_bases_ = tot_hits_ = tot_leftover_ = tot_minimizers_ = 0;
+    bam_blocks_ = 0;
     for (auto& sh : ft_share_) // (a reset context starts from the launcher's built-in tile shares again: ADVICE r05)
         for (uint32_t& v : sh) v = 0;
     sw_ = read_switches(); // (those that only shape construction keep their effect from the open)
@@ -870,6 +871,48 @@ Mapper::DeviceBatch Mapper::copy_in(const HostBatch& hb, uint8_t* d_bases, uint6
     return b;
 }
 
+void Mapper::ensure_bam_scratch(BamScratch& s, uint64_t n_bases)
+{
+    const uint64_t n = (uint64_t)dev::bam_pack_chunks(n_bases) + 1;
+    const size_t temp = dev::scan_temp_bytes((uint32_t)n);
+    if (n > s.d_count.size() || n > s.d_prefix.size() || temp > s.d_temp.size()) sync(); // (as ensure_stage)
+    s.d_count.reserve(n, n + n / 4);
+    s.d_prefix.reserve(n, n + n / 4);
+    s.d_temp.reserve(temp, temp + temp / 4);
+}
+
+Mapper::DeviceBatch Mapper::copy_in_bam(const HostBatch& hb, Stage& st, uint8_t* d_words, uint64_t* d_offsets, uint64_t* d_npos, hipStream_t copy_stream,
+    hipStream_t stream)
+{
+    if (!hb.seq_start || (hb.seq_bytes && !hb.bases)) throw Error(DRPRG_EINVAL, "null buffer");
+    if (hb.seq_bytes + 16 > st.d_seq.size() || hb.n_reads > st.d_seq_start.size() || hb.n_reads > st.d_reverse.size()) sync();
+    st.d_seq.reserve(hb.seq_bytes + 16, hb.seq_bytes + hb.seq_bytes / 4 + 16);
+    st.d_seq_start.reserve(hb.n_reads, hb.n_reads + hb.n_reads / 4);
+    st.d_reverse.reserve(hb.n_reads, hb.n_reads + hb.n_reads / 4);
+    ensure_bam_scratch(st.bam, hb.n_bases());
+    DeviceBatch b;
+    b.d_bases = d_words;
+    b.d_offsets = d_offsets;
+    b.n_reads = hb.n_reads;
+    b.n_bases = hb.n_bases();
+    b.packed = true;
+    b.n_npos = hb.n_npos; // (counted by the parser thread that copied the fields: no read-back, no wait)
+    b.d_npos = b.n_npos ? d_npos : nullptr;
+    if (hb.seq_bytes) HIPCHK(hipMemcpyAsync(st.d_seq.data(), hb.bases, hb.seq_bytes, hipMemcpyHostToDevice, copy_stream));
+    HIPCHK(hipMemcpyAsync(st.d_seq_start.data(), hb.seq_start, hb.n_reads * sizeof(uint64_t), hipMemcpyHostToDevice, copy_stream));
+    if (hb.reverse) HIPCHK(hipMemcpyAsync(st.d_reverse.data(), hb.reverse, hb.n_reads, hipMemcpyHostToDevice, copy_stream));
+    HIPCHK(hipMemcpyAsync(d_offsets, hb.offsets, (hb.n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, copy_stream));
+    if (copy_stream != stream) {
+        HIPCHK(hipEventRecord(st.copied, copy_stream));
+        HIPCHK(hipStreamWaitEvent(stream, st.copied, 0));
+    }
+    HIPCHK(dev::launch_bam_pack(st.d_seq.data(), st.d_seq_start.data(), d_offsets, hb.reverse ? st.d_reverse.data() : nullptr, hb.n_reads, b.n_bases,
+        reinterpret_cast<uint32_t*>(d_words), d_npos, b.n_npos, b.n_npos != 0, st.bam.d_count.data(), st.bam.d_prefix.data(), st.bam.d_temp.data(),
+        st.bam.d_temp.size(), stream));
+    ++bam_blocks_;
+    return b;
+}
+
 void Mapper::map_host(const HostBatch& hb)
 {
     if (hb.n_reads == 0) return;
@@ -877,8 +920,9 @@ void Mapper::map_host(const HostBatch& hb)
     HIPCHK(hipSetDevice(device_));
     if (hb.offsets[0] != 0) throw Error(DRPRG_EINVAL, "offsets[0] must be 0");
     Stage& st = stage_sync_;
-    ensure_stage(st, hb.payload_bytes(), hb.n_reads, hb.packed ? hb.n_npos : 0);
-    map(copy_in(hb, st.d_bases.data(), st.d_offsets.data(), st.d_npos.data(), stream_), nullptr, nullptr, stream_, false);
+    ensure_stage(st, hb.payload_bytes(), hb.n_reads, hb.packed || hb.bam ? hb.n_npos : 0);
+    if (hb.bam) map(copy_in_bam(hb, st, st.d_bases.data(), st.d_offsets.data(), st.d_npos.data(), stream_, stream_), nullptr, nullptr, stream_, false);
+    else map(copy_in(hb, st.d_bases.data(), st.d_offsets.data(), st.d_npos.data(), stream_), nullptr, nullptr, stream_, false);
     HIPCHK(hipStreamSynchronize(stream_)); // the staging buffers are reused by the next call
 }
 
@@ -901,6 +945,26 @@ uint64_t Mapper::pack_on_device(const uint8_t* d_bases, uint64_t n_bases, uint32
         std::sort(h.begin(), h.end());
         HIPCHK(hipMemcpy(d_npos, h.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice));
     }
+    return n;
+}
+
+uint64_t Mapper::pack_bam_on_device(const uint8_t* d_seq, const uint64_t* d_seq_start, const uint64_t* d_offsets, const uint8_t* d_reverse, uint64_t n_reads,
+    uint64_t n_bases, uint32_t* d_words, uint64_t* d_npos, uint64_t npos_cap, hipStream_t stream)
+{
+    HIPCHK(hipSetDevice(device_));
+    if (!stream) stream = stream_;
+    if (n_bases == 0) return 0;
+    if (n_reads == 0) throw Error(DRPRG_EINVAL, "bases without reads");
+    if (!d_seq || !d_seq_start || !d_offsets || !d_words) throw Error(DRPRG_EINVAL, "null device pointer");
+    if (n_reads > dev::MAX_BATCH_READS) throw Error(DRPRG_EOVERFLOW, "at most " + std::to_string(dev::MAX_BATCH_READS) + " reads per batch");
+    ensure_bam_scratch(bam_api_, n_bases);
+    const uint32_t n_chunks = dev::bam_pack_chunks(n_bases);
+    HIPCHK(dev::launch_bam_pack(d_seq, d_seq_start, d_offsets, d_reverse, n_reads, n_bases, d_words, d_npos, d_npos ? npos_cap : 0, true,
+        bam_api_.d_count.data(), bam_api_.d_prefix.data(), bam_api_.d_temp.data(), bam_api_.d_temp.size(), stream));
+    uint32_t n = 0;
+    HIPCHK(hipMemcpyAsync(&n, bam_api_.d_prefix.data() + n_chunks, sizeof n, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    if (n && !d_npos) throw Error(DRPRG_EINVAL, "the batch holds bases that are not ACGT and no buffer for their positions was given");
     return n;
 }
 
@@ -1079,14 +1143,20 @@ void Mapper::map_host_async(const HostBatch& hb)
             tot_reads_ += n_reads; // (only empty reads: nothing to keep)
             return;
         }
-        const uint64_t n_npos = hb.packed ? hb.n_npos : 0;
+        const uint64_t n_npos = hb.packed || hb.bam ? hb.n_npos : 0;
         uint8_t* db = static_cast<uint8_t*>(arena_take(hb.payload_bytes() + 64));
         uint64_t* doff = db ? static_cast<uint64_t*>(arena_take((n_reads + 1) * sizeof(uint64_t))) : nullptr;
         uint64_t* dnp = doff && n_npos ? static_cast<uint64_t*>(arena_take(n_npos * sizeof(uint64_t))) : nullptr;
         if (db && doff && (dnp || !n_npos)) {
             if (!copy_stream_) copy_stream_.create();
             if (!kept_copied_) kept_copied_.create(false);
-            const DeviceBatch kb = copy_in(hb, db, doff, dnp, copy_stream_);
+            // (a BAM block is kept in the packed form: its raw fields go through a staging set, taken in turn as below)
+            Stage* raw = hb.bam ? &stage_[stage_next_] : nullptr;
+            if (raw) {
+                stage_next_ ^= 1;
+                if (!raw->copied) raw->copied.create(false);
+            }
+            const DeviceBatch kb = raw ? copy_in_bam(hb, *raw, db, doff, dnp, copy_stream_, stream_) : copy_in(hb, db, doff, dnp, copy_stream_);
             HIPCHK(hipEventRecord(kept_copied_, copy_stream_));
             HIPCHK(hipStreamWaitEvent(stream_, kept_copied_, 0));
             kept_.push_back(kb);
@@ -1126,8 +1196,9 @@ void Mapper::map_host_async(const HostBatch& hb)
     Stage& st = stage_[stage_next_];
     stage_next_ ^= 1;
     if (!st.copied) st.copied.create(false);
-    ensure_stage(st, hb.payload_bytes(), n_reads, hb.packed ? hb.n_npos : 0);
-    const DeviceBatch b = copy_in(hb, st.d_bases.data(), st.d_offsets.data(), st.d_npos.data(), copy_stream_);
+    ensure_stage(st, hb.payload_bytes(), n_reads, hb.packed || hb.bam ? hb.n_npos : 0);
+    const DeviceBatch b = hb.bam ? copy_in_bam(hb, st, st.d_bases.data(), st.d_offsets.data(), st.d_npos.data(), copy_stream_, stream_)
+                                 : copy_in(hb, st.d_bases.data(), st.d_offsets.data(), st.d_npos.data(), copy_stream_);
     HIPCHK(hipEventRecord(st.copied, copy_stream_));
     HIPCHK(hipStreamWaitEvent(stream_, st.copied, 0));
     map(b, nullptr, nullptr, stream_, true);

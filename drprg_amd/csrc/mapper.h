@@ -71,7 +71,13 @@ public:
     // ASCII -> packed on the device (harnesses: bench.py packs its synthetic batch; tests).  Returns the number of non-ACGT bases; their
     // positions are in d_npos, ascending, if there are at most npos_cap of them.  Synchronises `stream`.
     uint64_t pack_on_device(const uint8_t* d_bases, uint64_t n_bases, uint32_t* d_words, uint64_t* d_npos, uint64_t npos_cap, hipStream_t stream);
-    // a host batch in either form (packed: `bases` points at the words, npos / n_npos as above, in host memory)
+    // BAM's 4-bit form -> packed on the device (bam_pack.hip; kernels.h launch_bam_pack says what the arrays hold).  Returns the number of
+    // non-ACGT positions; they are in d_npos, ascending, if there are at most npos_cap of them.  Synchronises `stream`.
+    uint64_t pack_bam_on_device(const uint8_t* d_seq, const uint64_t* d_seq_start, const uint64_t* d_offsets, const uint8_t* d_reverse, uint64_t n_reads,
+        uint64_t n_bases, uint32_t* d_words, uint64_t* d_npos, uint64_t npos_cap, hipStream_t stream);
+    // a host batch in one of three forms (packed: `bases` points at the words, npos / n_npos as above, in host memory; bam: `bases`
+    // points at seq_bytes bytes of 4-bit sequence fields, read i starting at byte seq_start[i] and reverse-complemented when reverse[i]
+    // != 0, n_npos counts the codes that are not A, C, G or T and npos is null -- ingest.h PinnedBatch)
     struct HostBatch {
         const uint8_t* bases = nullptr;
         const uint64_t* offsets = nullptr;
@@ -79,9 +85,15 @@ public:
         bool packed = false;
         const uint64_t* npos = nullptr;
         uint64_t n_npos = 0;
+        bool bam = false;
+        const uint64_t* seq_start = nullptr;
+        const uint8_t* reverse = nullptr;
+        uint64_t seq_bytes = 0;
         uint64_t n_bases() const { return offsets[n_reads]; }
-        uint64_t payload_bytes() const { return packed ? ((n_bases() + 15) / 16) * 4 : n_bases(); }
+        // what the batch takes on the device once it is there (a BAM batch: converted to the packed form)
+        uint64_t payload_bytes() const { return packed || bam ? ((n_bases() + 15) / 16) * 4 : n_bases(); }
     };
+    uint64_t bam_blocks() const { return bam_blocks_; } // BAM batches converted on this device since the last reset_coverage
     // Map a host batch (copied into a staging set, then map on the own accumulators).
     void map_host(const HostBatch& b);
     // The same without waiting for the kernels: the copy to the device runs on a copy stream into one of two staging sets, the
@@ -302,11 +314,25 @@ private:
     void reserve_tile_first(TileSet& t, uint32_t n_tiles);
     // host staging: device buffers a host batch is copied into, each replaced by one a quarter larger when a batch does not fit it
     // (ensure_stage).  map_host has one set; map_host_async takes two in turn, their copies on copy_stream_ with `copied` behind them
+    struct BamScratch { // launch_bam_pack's per-workgroup counts, their scan and the scan's scratch
+        DeviceBuffer<uint32_t> d_count, d_prefix;
+        DeviceBuffer<unsigned char> d_temp;
+    };
     struct Stage {
         DeviceBuffer<uint8_t> d_bases;
         DeviceBuffer<uint64_t> d_offsets, d_npos;
         Event copied;
+        // a BAM batch as it arrives: converted into d_bases -- or into the block that stays resident -- by launch_bam_pack
+        DeviceBuffer<uint8_t> d_seq, d_reverse;
+        DeviceBuffer<uint64_t> d_seq_start;
+        BamScratch bam;
     };
+    void ensure_bam_scratch(BamScratch& s, uint64_t n_bases);
+    // The copies of a BAM batch into st's raw buffers on copy_stream and, behind them on `stream`, its conversion into the packed batch
+    // at these addresses, which is returned.  st.copied is recorded behind the copies when the two streams differ.
+    DeviceBatch copy_in_bam(const HostBatch& hb, Stage& st, uint8_t* d_words, uint64_t* d_offsets, uint64_t* d_npos, hipStream_t copy_stream, hipStream_t stream);
+    BamScratch bam_api_; // pack_bam_on_device's own (the caller's stream is not ordered with the context's)
+    uint64_t bam_blocks_ = 0;
     // room in `st` for a batch of these sizes (n_npos: 0 for an ASCII batch)
     void ensure_stage(Stage& st, uint64_t payload_bytes, uint64_t n_reads, uint64_t n_npos);
     Stage stage_[2], stage_sync_;

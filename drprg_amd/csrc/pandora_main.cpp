@@ -62,6 +62,8 @@ void usage()
         "  pandora discover [same mapping options] <prg> <query.tsv>\n"
         "  --max-covg N: reads are taken in file order up to and including the first one at which (N + 1) x SIZE bases are reached;\n"
         "                the rest is not mapped (default 300; 4294967295 = no cap)\n"
+        "  <reads>: FASTA or FASTQ, plain or gzip; or BAM (secondary and supplementary records are skipped, reverse-strand records are\n"
+        "           reverse-complemented, qualities and alignments are ignored)\n"
         "environment: DRPRG_HIP_DEVICE selects the GPU (default 0); DRPRG_HIP_DEVICES=0,1,.. maps on several GPUs of the node\n");
 }
 
@@ -197,6 +199,15 @@ void report_cap(drprg_hip_ctx* ctx, const Args& a)
         (unsigned long long)a.max_covg, (unsigned long long)a.genome_size, (unsigned long long)ci[2]);
 }
 
+// -v: what a BAM file held
+void report_bam(drprg_hip_ctx* ctx, const Args& a)
+{
+    uint64_t bi[4] = { 0, 0, 0, 0 };
+    if (!a.verbose || drprg_hip_bam_info(ctx, bi) != 0 || !bi[0]) return;
+    std::printf("[pandora-hip] bam: records=%llu skipped=%llu (secondary / supplementary) reverse-complemented=%llu blocks converted on the device=%llu\n",
+        (unsigned long long)bi[0], (unsigned long long)bi[1], (unsigned long long)bi[2], (unsigned long long)bi[3]);
+}
+
 const char* COVERAGE_CACHE = ".drprg_hip_coverage";
 
 int cmd_map(const Args& a)
@@ -216,6 +227,7 @@ int cmd_map(const Args& a)
         if (int rc = drprg_hip_map_fastx(ctx, a.positional[1].c_str())) die(drprg_hip_last_error(ctx), -rc);
         report_counters(ctx, now_s() - t0);
         report_cap(ctx, a);
+        report_bam(ctx, a);
     }
     const std::string vcf = a.outdir + "/pandora_genotyped.vcf";
     if (int rc = drprg_hip_genotype(ctx, a.vcf_refs.empty() ? nullptr : a.vcf_refs.c_str(), vcf.c_str(), "sample"))
@@ -250,6 +262,7 @@ int cmd_discover(const Args& a)
     if (int rc = drprg_hip_map_fastx(ctx, reads.c_str())) die(drprg_hip_last_error(ctx), -rc);
     report_counters(ctx, now_s() - t0);
     report_cap(ctx, a);
+    report_bam(ctx, a);
     // The mapping half of discover is the same kernels as `map`; its products are (1) the candidate regions -- stretches of each
     // locus' called consensus that the reads do not support --, (2) the novel variants a host-side pile-up of
     // the reads finds in them, and (3) the coverage vector, kept for the `map` call drprg issues next on the unchanged PRG.

@@ -113,6 +113,21 @@ class Context:
         _check(lib.drprg_hip_pack_device(self._h, d_bases, n_bases, d_words, d_npos, npos_cap, C.byref(n), stream), self._h)
         return int(n.value)
 
+    # ---- BAM input (include/drprg_hip.h "BAM input") ----------------------------------------------
+    def pack_device_bam(self, d_seq, d_seq_start, d_offsets, d_reverse, n_reads, n_bases, d_words, d_npos=None, npos_cap=0, stream=None):
+        """BAM's 4-bit sequence fields -> packed on the device (drprg_hip_pack_device_bam); returns the number of non-ACGT positions
+        (ascending in d_npos).  d_reverse may be None: no read is reverse-complemented."""
+        n = C.c_uint64()
+        _check(lib.drprg_hip_pack_device_bam(self._h, d_seq, d_seq_start, d_offsets, d_reverse, n_reads, n_bases, d_words, d_npos, npos_cap,
+                                             C.byref(n), stream), self._h)
+        return int(n.value)
+
+    def bam_info(self):
+        """what map_fastx saw of BAM files since the last reset"""
+        out = (C.c_uint64 * 4)()
+        _check(lib.drprg_hip_bam_info(self._h, out), self._h)
+        return dict(records=int(out[0]), skipped=int(out[1]), reversed=int(out[2]), device_blocks=int(out[3]))
+
     def map_device(self, d_bases, d_offsets, n_reads, n_bases, d_covg=None, d_prg_reads=None, stream=None):
         """Pointers are integer device addresses (e.g. torch.Tensor.data_ptr())."""
         _check(lib.drprg_hip_map_device(self._h, d_bases, d_offsets, n_reads, n_bases, d_covg, d_prg_reads, stream), self._h)

@@ -110,7 +110,7 @@ int drprg_hip_set_opts_sized(drprg_hip_ctx* ctx, const drprg_hip_map_opts* opts,
 /* Read mapping: the loop inside `pandora map` / `pandora discover` that
  * Pandora::genotype_with / discover_with wait on (/root/reference/src/lib.rs:580-642, :513-578).
  * Coverage accumulates in the context until drprg_hip_reset. */
-int drprg_hip_map_fastx(drprg_hip_ctx* ctx, const char* reads_path); /* fasta/fastq, plain or .gz */
+int drprg_hip_map_fastx(drprg_hip_ctx* ctx, const char* reads_path); /* fasta/fastq, plain or .gz; or BAM ("BAM input" below) */
 /* Parser threads used by drprg_hip_map_fastx (the -t that drprg forwards to pandora, /root/reference/src/predict.rs:236-245);
  * default 4.  The file is cut at record boundaries and parsed in parallel into pinned blocks. */
 int drprg_hip_set_threads(drprg_hip_ctx* ctx, int threads);
@@ -143,7 +143,9 @@ int drprg_hip_max_covg_info(drprg_hip_ctx* ctx, uint64_t out[4]);
 /* Host-only self-check of that ingest: parses the file with `threads` parser threads and returns
  * out[0..4] = reads, bases, order-independent digest (sum of the FNV-1a hashes of the reads), batches, and how gzip input
  * was inflated (0 plain text, 1 BGZF members in parallel, 2 one member in one libdeflate call, 3 zlib streaming, 4 one plain
- * gzip stream inflated by all threads: chunks entered at block boundaries found in the compressed data, csrc/pgunzip.h). */
+ * gzip stream inflated by all threads: chunks entered at block boundaries found in the compressed data, csrc/pgunzip.h).
+ * A BAM file ("BAM input" below; its BGZF members are inflated as way 1, or by zlib where libdeflate is missing) is turned into the
+ * upper-case text of its reads on the parser threads: reads, bases and digest are those of the FASTQ of the same reads. */
 int drprg_hip_parse_fastx(const char* reads_path, int threads, uint64_t out[5], char* err, size_t err_len);
 /* The same for the hand-over in file order that the depth cap uses: the blocks are taken one at a time, in file order, until max_reads
  * reads have been seen (the last block is cut there), then the ingest is told to stop.  out[0..5] = reads seen, their bases, an
@@ -195,6 +197,43 @@ int drprg_hip_map_device_packed_async(drprg_hip_ctx* ctx, const void* d_words, c
     uint64_t n_npos, void* d_covg, void* d_prg_reads, void* hip_stream);
 int drprg_hip_pack_device(drprg_hip_ctx* ctx, const void* d_bases, uint64_t n_bases, void* d_words, void* d_npos, uint64_t npos_cap, uint64_t* n_npos,
     void* hip_stream);
+
+/* ---- BAM input.  THIS BUILD'S OWN RULE: the reference's reader (needletail) refuses BAM, so nothing under /root/reference pins what a
+ * BAM file means as reads.  The rule below restates FROM MEMORY what `samtools fastq` does by default; samtools was not at hand to
+ * check it against.  drprg_hip_map_fastx, drprg_hip_parse_fastx, drprg_hip_parse_fastx_ordered and drprg_hip_discover_reads take a BAM
+ * path wherever they take a FASTA / FASTQ path; no other input changes its meaning.
+ *   1. A file is BAM if it is BGZF (gzip members that carry the BC extra subfield) and the inflated stream starts with "BAM\1".  A
+ *      bgzip'd FASTQ stays what it was.  The header text and the reference list are skipped; a missing 28-byte EOF block is accepted.
+ *   2. Records are read in file order.  A record with flag 0x100 (secondary) or 0x800 (supplementary) is skipped and counted as
+ *      skipped; every other record is one read, whatever its paired, QC-fail and duplicate flags say.  l_seq == 0: a read of length 0.
+ *   3. The read's bases are its SEQ field -- code i of "=ACMGRSVTWYHKDBN" per base, high nibble first --, reverse-complemented when
+ *      flag 0x10 is set.  The complement of a code is the code with its four bits reversed (A=1 <-> T=8, C=2 <-> G=4, M <-> K, R <-> Y,
+ *      ...; '=', S, W and N map to themselves).
+ *   4. Codes A, C, G, T are bases.  Every other code is a non-ACGT position: it invalidates every k-mer that holds it, as an N byte of
+ *      a FASTQ does, and its 2-bit letter in the packed form is bits 2:1 of the ASCII code of its upper-case letter.  So the words and
+ *      the position list of a BAM batch are bit-identical to drprg_hip_pack_reads of the upper-case text of the same reads.
+ *   5. Qualities, names, CIGAR, tags and alignment coordinates are ignored.
+ *   6. A read longer than 2^23 bases is refused (-EOVERFLOW), as everywhere else.
+ *   7. Malformed input is an error, never a crash or a silently shorter sample.  -84 (EFORMAT): a block_size smaller than the fixed part
+ *      + name + cigar + seq + qual, a record that runs past the end of the stream, a wrong magic behind BGZF.
+ * A BAM file's reads always travel to the device in their 4-bit form (half the bytes of the text) and are converted there to the packed
+ * form above (csrc/bam_pack.hip): drprg_hip_set_input_format does not apply to them.  Blocks that stay resident (drprg_hip_keep_reads)
+ * are kept packed, so everything behind -- drprg_hip_select_reads, drprg_hip_map_resident, the discover pass from HBM, the depth cap --
+ * sees an ordinary packed batch; drprg_hip_resident_info counts packed bytes.  Multi-line FASTQ's serial reader never sees a BAM file.
+ *   drprg_hip_pack_device_bam: the device counterpart of drprg_hip_pack_device for a batch whose sequences are in that 4-bit form.
+ *     d_seq: the sequence fields; d_seq_start: u64[n_reads], the byte of d_seq at which read i's field starts (the fields need not be
+ *     adjacent or in order); d_offsets: u64[n_reads + 1] in bases, as for every batch; d_reverse: u8[n_reads], != 0: the read is the
+ *     reverse complement of its field (NULL: no read is).  d_words: u32[ceil(n_bases / 16)], written with 16-byte stores when it is
+ *     16-byte aligned (what the map entries ask for anyway); d_npos: room for npos_cap positions.  *n_npos receives the number of non-ACGT
+ *     positions (below 2^32), the positions come out ascending; more than npos_cap: -EOVERFLOW with *n_npos set and the first npos_cap
+ *     positions written; d_npos NULL: -EINVAL if there is any.  Stream rule as above; the call waits for its stream.  The result goes
+ *     to drprg_hip_map_device_packed(_async) as it is.
+ *   drprg_hip_bam_info: out[0] = BAM records seen by drprg_hip_map_fastx, out[1] = of those skipped as secondary / supplementary,
+ *     out[2] = reads that were reverse-complemented, out[3] = blocks converted on the device(s); since the last drprg_hip_reset, all 0
+ *     for a context that never saw a BAM file.  Under a depth cap the first three count what was parsed before the ingest stopped. */
+int drprg_hip_pack_device_bam(drprg_hip_ctx* ctx, const void* d_seq, const void* d_seq_start, const void* d_offsets, const void* d_reverse /* may be NULL */,
+    uint64_t n_reads, uint64_t n_bases, void* d_words, void* d_npos, uint64_t npos_cap, uint64_t* n_npos, void* hip_stream);
+int drprg_hip_bam_info(drprg_hip_ctx* ctx, uint64_t out[4]);
 
 /* The per-k-mer-node coverage vector (what gets sum-reduced across GPUs):
  * covg[2g] forward, covg[2g+1] reverse coverage of global k-mer node g; prg_reads[p] clusters on PRG p. */
