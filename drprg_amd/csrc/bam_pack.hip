@@ -12,7 +12,7 @@
 // The non-ACGT positions come out ascending without a sort: the first launch leaves every workgroup's count, one scan turns the counts
 // into starts, and a second launch -- whose workgroups without such a position return at once, i.e. nearly all of them -- makes the
 // masks of its 16384 bases again and writes the positions in order.  HBM-bound by design: n / 2 bytes read, n / 4 written.
-#include "device_common.h"
+#include "search.h"
 
 namespace drprg {
 namespace dev {
@@ -40,18 +40,8 @@ constexpr uint64_t BP_COMPLEMENT = bp_complements(); // the 4-bit reversal of co
 
 uint32_t bam_pack_chunks(uint64_t n_bases) { return (uint32_t)((((n_bases + 15) >> 4) + BP_CHUNK_WORDS - 1) / BP_CHUNK_WORDS); }
 
-// (the three functions below are host code as well, so that a CPU build can walk the kernel's index arithmetic under a sanitizer)
-// the largest r in [lo, hi] with offsets[r] <= p (offsets[lo] <= p): the read that holds base p when p < offsets[hi + 1]
-DRPRG_HD inline uint64_t bp_read_of(const uint64_t* __restrict__ offsets, uint64_t lo, uint64_t hi, uint64_t p)
-{
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo + 1) / 2;
-        if (offsets[mid] <= p) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-
+// (the two functions below, and read_holding of search.h, are host code as well, so that a CPU build can walk the kernel's index arithmetic
+// under a sanitizer)
 struct BamBatch {
     const uint8_t* seq;
     const uint64_t* seq_start;
@@ -127,13 +117,13 @@ __global__ __launch_bounds__(BP_THREADS) void bam_pack_kernel(BamBatch b, uint32
     if (EMIT && chunk_prefix[blockIdx.x + 1] == chunk_prefix[blockIdx.x]) return; // (uniform) nothing to list here
     if (threadIdx.x == 0 || threadIdx.x == 64) {
         const uint64_t chunk_end = chunk_word + BP_CHUNK_WORDS < n_words ? (chunk_word + BP_CHUNK_WORDS) << 4 : b.n_bases;
-        s_read[threadIdx.x >> 6] = bp_read_of(b.offsets, 0, b.n_reads - 1, threadIdx.x == 0 ? chunk_word << 4 : chunk_end - 1);
+        s_read[threadIdx.x >> 6] = read_holding(b.offsets, 0, b.n_reads - 1, threadIdx.x == 0 ? chunk_word << 4 : chunk_end - 1);
     }
     __syncthreads();
     const uint64_t w0 = chunk_word + (uint64_t)threadIdx.x * BP_LANE_WORDS;
     uint32_t w[BP_LANE_WORDS], mask[BP_LANE_WORDS], n_bad = 0;
     if (w0 < n_words) {
-        uint64_t r = bp_read_of(b.offsets, s_read[0], s_read[1], w0 << 4);
+        uint64_t r = read_holding(b.offsets, s_read[0], s_read[1], w0 << 4);
 #pragma unroll
         for (int j = 0; j < BP_LANE_WORDS; ++j) {
             w[j] = 0;

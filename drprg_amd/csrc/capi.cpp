@@ -118,6 +118,13 @@ struct drprg_hip_ctx {
     // only if they are that file's and nothing else's); whether the last drprg_hip_discover_reads took its reads from HBM
     std::vector<std::string> mapped_paths;
     bool last_discover_resident = false;
+    // the last drprg_hip_subsample: reads of the sample before it, and their keep flags (empty: nothing was dropped)
+    // drprg_hip_set_ordered_ingest; and whether a drprg_hip_map_fastx since the last reset handed more than one block over in no
+    // particular order (the reads of such a sample have no file-order numbers)
+    bool ordered_ingest = false, fastx_unordered = false;
+    bool subsampled = false;
+    uint64_t subsample_n = 0;
+    std::vector<uint8_t> subsample_flags;
     // (the page-locked ingest blocks of drprg_hip_map_fastx are recycled process-wide: PinPool above)
     // multi-device context: RCCL communicators of its devices (created on first use; empty when RCCL is not used)
     std::vector<Rccl::Comm> comms;
@@ -478,6 +485,7 @@ int drprg_hip_map_fastx(drprg_hip_ctx* ctx, const char* reads_path)
     };
     uint64_t cap_T = 0;
     const bool capped = cap_target(ctx, cap_T);
+    const bool ordered = capped || ctx->ordered_ingest; // (drprg_hip_set_ordered_ingest: the same hand-over without a cap -- nothing is ever cut)
     // page-locked ingest blocks are kept by the process between calls and contexts (PinPool)
     hooks.alloc = [](size_t n) -> void* { return PinPool::get().take(n); };
     hooks.release = [](void* p) { PinPool::get().give_back(p); };
@@ -510,7 +518,7 @@ int drprg_hip_map_fastx(drprg_hip_ctx* ctx, const char* reads_path)
     // are handed to the devices -- round robin --: the block that crosses the cap goes to its device cut to the accepted reads (so a
     // device that keeps its blocks resident keeps exactly those), nothing after it is copied anywhere and the ingest takes no new piece of the file.
     size_t rr = 0;
-    if (capped)
+    if (ordered)
         hooks.submit_in_order = [&](const PinnedBatch& b) -> bool {
             if (b.offsets[0] != 0) throw Error(DRPRG_EINVAL, "offsets[0] must be 0");
             Mapper::HostBatch hb = host_batch(b);
@@ -533,10 +541,11 @@ int drprg_hip_map_fastx(drprg_hip_ctx* ctx, const char* reads_path)
         ctx->bam_records += st.bam_records;
         ctx->bam_skipped += st.bam_skipped;
         ctx->bam_reversed += st.bam_reversed;
-        if (capped) ctx->dropped_reads += st.discarded_reads; // (the accepted ones were counted block by block)
+        if (ordered) ctx->dropped_reads += st.discarded_reads; // (the accepted ones were counted block by block)
         else {
             ctx->total_bases += st.bases;
             ctx->accepted_reads += st.reads;
+            if (st.batches > 1) ctx->fastx_unordered = true;
         }
         fold();
     } catch (const Error& e) {
@@ -915,6 +924,10 @@ int drprg_hip_reset(drprg_hip_ctx* ctx)
     ctx->bases_without_reads = false;
     ctx->mapped_paths.clear();
     ctx->needs_reset = false;
+    ctx->fastx_unordered = false;
+    ctx->subsampled = false;
+    ctx->subsample_n = 0;
+    ctx->subsample_flags.clear();
     API_END(ctx)
 }
 
@@ -976,6 +989,53 @@ int drprg_hip_resident_info(drprg_hip_ctx* ctx, uint64_t out[4])
         out[2] += m->kept().size();
     }
     out[3] = ctx->last_discover_resident ? 1 : 0;
+    API_END(ctx)
+}
+
+int drprg_hip_set_ordered_ingest(drprg_hip_ctx* ctx, int on)
+{
+    if (!ctx) return DRPRG_EINVAL;
+    ctx->ordered_ingest = on != 0;
+    return DRPRG_OK;
+}
+
+int drprg_hip_subsample(drprg_hip_ctx* ctx, uint64_t target_bases, uint64_t seed, uint64_t out[4])
+{
+    API_BEGIN(ctx)
+    if (!out) throw Error(DRPRG_EINVAL, "null output");
+    Mapper& m = need_mapper(ctx);
+    if (!ctx->extra.empty()) throw Error(DRPRG_EINVAL, "drprg_hip_subsample: a context over several devices is not served");
+    if (ctx->max_covg < 0xFFFFFFFFull)
+        throw Error(DRPRG_EINVAL, "drprg_hip_subsample: a depth cap is set (drprg_hip_set_max_covg); the prefix cap and the random subsample are alternatives");
+    if (ctx->fastx_unordered && m.kept_complete()) // (a sample that is not resident is refused for that, below)
+        throw Error(DRPRG_EINVAL, "drprg_hip_subsample: drprg_hip_map_fastx handed this sample's blocks over in no particular order, so its reads have no "
+                                  "file-order numbers (drprg_hip_set_ordered_ingest(ctx, 1) before the file is mapped)");
+    std::vector<uint8_t> flags;
+    const Mapper::SubsampleResult r = m.subsample_kept(target_bases, seed, flags);
+    out[0] = r.reads_before;
+    out[1] = r.bases_before;
+    out[2] = r.reads_kept;
+    out[3] = r.bases_kept;
+    ctx->subsampled = true;
+    ctx->subsample_n = r.reads_before;
+    ctx->subsample_flags = std::move(flags);
+    if (r.reads_kept != r.reads_before) { // the context now stands for the kept reads alone
+        ctx->host_coverage_valid = false;
+        ctx->total_bases = r.bases_kept;
+        ctx->accepted_reads = r.reads_kept;
+    }
+    API_END(ctx)
+}
+
+int drprg_hip_subsample_flags(drprg_hip_ctx* ctx, uint8_t* flags, uint64_t n)
+{
+    API_BEGIN(ctx)
+    if (!ctx->subsampled) throw Error(DRPRG_EINVAL, "drprg_hip_subsample_flags: no drprg_hip_subsample call since the last reset");
+    if (n != ctx->subsample_n)
+        throw Error(DRPRG_EINVAL, "drprg_hip_subsample_flags: the sample held " + std::to_string(ctx->subsample_n) + " reads, not " + std::to_string(n));
+    if (n && !flags) throw Error(DRPRG_EINVAL, "null output");
+    if (ctx->subsample_flags.empty()) std::memset(flags, 1, n);
+    else std::memcpy(flags, ctx->subsample_flags.data(), n);
     API_END(ctx)
 }
 

@@ -2,35 +2,13 @@
 //
 // A device batch's read offsets exist only in HBM.  The host knows the batch's n_bases, so it knows WHETHER the batch reaches the cap
 // without asking the device; only the one batch that does is looked at here: the smallest i with offsets[i] >= target, and -- for a
-// packed batch -- how many of its listed non-ACGT positions lie below offsets[i].  One wave, a 64-way search: every round the 64 lanes
-// probe evenly spaced entries of what is left of the range and a ballot keeps the one gap the answer lies in, so the range shrinks
-// 64-fold per round (five rounds for 2^28 reads; a binary search by one lane would be 28 dependent loads).  Latency-bound: <= 5 + 5
+// packed batch -- how many of its listed non-ACGT positions lie below offsets[i].  One wave, a 64-way search (first_at_least, search.h: the
+// range shrinks 64-fold per round, five rounds for 2^28 reads).  Latency-bound: <= 5 + 5
 // rounds of one 8-byte load per lane, no LDS, nothing to tune.  Launched at most once per context between resets.
-#include "device_common.h"
+#include "search.h"
 
 namespace drprg {
 namespace dev {
-
-// smallest i in [0, n) with a[i] >= target, n if there is none; a is ascending.  Wave-uniform result; every lane of the wave calls it.
-__device__ inline uint64_t first_at_least(const uint64_t* __restrict__ a, uint64_t n, uint64_t target, int lane)
-{
-    uint64_t lo = 0, hi = n; // the answer is in [lo, hi]; a[hi] >= target or hi == n
-    while (lo < hi) {
-        const uint64_t step = (hi - lo + 63) >> 6; // >= 1: the probes lo + step * lane cover [lo, hi)
-        const uint64_t p = lo + step * (uint64_t)lane;
-        const bool ge = p < hi && a[p] >= target; // (p < hi <= n: inside the array)
-        const uint64_t m = __ballot(ge);
-        if (!m) { // every probe is below the target, the last one at >= hi - step: what is left lies behind it
-            const uint64_t last = lo + step * (uint64_t)((hi - lo - 1) / step);
-            lo = last + 1;
-            continue;
-        }
-        const int f = __ffsll((long long)m) - 1;
-        hi = lo + step * (uint64_t)f;                 // a[hi] >= target
-        if (f) lo = lo + step * (uint64_t)(f - 1) + 1; // a[probe f - 1] < target
-    }
-    return lo;
-}
 
 // out[0] = i, out[1] = offsets[i], out[2] = positions of npos below offsets[i]  (out: page-locked host memory, written by lane 0 with
 // ordinary vector stores).  No entry reaches the target (the caller's n_bases was not offsets[n_reads]): i = n_reads.

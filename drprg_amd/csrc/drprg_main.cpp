@@ -107,7 +107,10 @@ void usage()
     std::fprintf(stderr,
         "drprg predict -x <index dir | species[@version]> -i <reads.fq[.gz] | reads.bam> [-o DIR] [-s SAMPLE] [-I] [-S]\n"
         "              [-f MAF] [-d MIN_COVG] [-D MAX_COVG] [-b MIN_STRAND_BIAS] [-g MIN_GT_CONF] [-L MAX_INDEL] [-K MIN_FRS]\n"
-        "              [-C MIN_CLUSTER_SIZE] [--debug] [-v] [-t THREADS] [--rebuild-index]\n"
+        "              [-C MIN_CLUSTER_SIZE] [--debug] [-v] [-t THREADS] [--rebuild-index] [--subsample-covg D [--seed S]]\n"
+        "--subsample-covg D: the sample is cut at random to D x 4411532 bases on the device before discover and genotyping (reads in the\n"
+        "              order of a 64-bit key made from the seed, default 1, and the read's number, up to and including the one that reaches\n"
+        "              the target); needs the sample resident in device memory (DRPRG_HIP_KEEP_READS_GB, default 32), fails if it is not.\n"
         "MI355X-native hot path; -p/-m/-M (external tools) are accepted and not needed: novel variants update the PRG in process.\n");
 }
 
@@ -144,6 +147,9 @@ int main(int argc, char** argv)
     std::string index, input, outdir = ".", sample;
     bool illumina = false, verbose = false, maf_given = false, rebuild_index = false;
     int threads = 1;
+    bool subsample = false, seed_given = false;
+    double subsample_covg = 0;
+    uint64_t seed = 1;
     uint32_t min_cluster = 10;
     drprg_hip_annotate_opts ao {};
     ao.min_covg = 3;
@@ -188,9 +194,17 @@ int main(int argc, char** argv)
         else if (a == "-v" || a == "--verbose") verbose = true;
         else if (a == "--debug") verbose = true;
         else if (a == "--rebuild-index") rebuild_index = true;
+        else if (a == "--subsample-covg") {
+            char* end = nullptr;
+            const char* v = need(i);
+            subsample_covg = std::strtod(v, &end);
+            if (end == v || *end || !(subsample_covg >= 0)) die(std::string("--subsample-covg needs a depth >= 0, not ") + v, 2);
+            subsample = true;
+        } else if (a == "--seed") { seed = std::strtoull(need(i), nullptr, 10); seed_given = true; }
         else if (a == "-h" || a == "--help") { usage(); return 0; }
         else die("unknown option " + a, 2);
     }
+    if (seed_given && !subsample) die("--seed belongs to --subsample-covg", 2);
     if (index.empty() || input.empty()) {
         usage();
         return 2;
@@ -248,11 +262,22 @@ int main(int argc, char** argv)
     if (const char* e = std::getenv("DRPRG_HIP_KEEP_READS_GB")) keep_gb = std::atof(e);
     if (keep_gb > 0)
         if (int rc = drprg_hip_keep_reads(ctx, (uint64_t)(keep_gb * 1e9))) die(drprg_hip_last_error(ctx), -rc);
+    if (subsample) drprg_hip_set_ordered_ingest(ctx, 1); // (the subsample numbers the reads in file order)
+    if (subsample && !(keep_gb > 0)) die("--subsample-covg needs the reads resident in device memory: DRPRG_HIP_KEEP_READS_GB=0 switches that off");
     if (verbose && std::getenv("DRPRG_HIP_T0")) std::fprintf(stderr, "[drprg-hip +%.3fs] main() entered\n", at_main);
     if (verbose) std::fprintf(stderr, "[drprg-hip +%.3fs] mapping %s against %s (k=%d w=%d) on device %d\n", since_start(), input.c_str(), index.c_str(), k, w, device);
     // discover + map share ONE pass over the reads (the reference runs two, /root/reference/src/predict.rs:248-302)
     if (int rc = drprg_hip_map_fastx(ctx, input.c_str())) die(drprg_hip_last_error(ctx), -rc);
     if (verbose) std::fprintf(stderr, "[drprg-hip +%.3fs] reads mapped\n", since_start());
+    if (subsample) { // the resident sample cut to the target depth at random (include/drprg_hip.h "random subsample"); never a silent full run
+        const uint64_t target = (uint64_t)(subsample_covg * (double)mo.genome_size);
+        uint64_t out[4] = { 0, 0, 0, 0 };
+        if (int rc = drprg_hip_subsample(ctx, target, seed, out)) die(std::string("--subsample-covg: ") + drprg_hip_last_error(ctx), -rc);
+        if (verbose)
+            std::fprintf(stderr, "[drprg-hip +%.3fs] subsample: reads_before=%llu bases_before=%llu reads_kept=%llu bases_kept=%llu (target %llu bases, seed %llu)\n",
+                since_start(), (unsigned long long)out[0], (unsigned long long)out[1], (unsigned long long)out[2], (unsigned long long)out[3],
+                (unsigned long long)target, (unsigned long long)seed);
+    }
     {
         // discover (/root/reference/src/predict.rs:247-256): candidate regions of every locus' called consensus, then a host-side
         // pile-up of the reads over them (whole strings with -I, column-wise majority of aligned strings without).  Novel variants update the PRG (what MakePrg::update does with

@@ -338,6 +338,53 @@ hipError_t launch_bam_pack(const uint8_t* seq, const uint64_t* seq_start, const 
 hipError_t launch_covg_cut(const uint64_t* offsets, uint64_t n_reads, uint64_t target, const uint64_t* npos, uint64_t n_npos, unsigned long long* out,
     hipStream_t stream);
 
+// subsample.hip: a resident sample cut to a target depth at random (the rule: include/drprg_hip.h "random subsample").
+// Selection over the n reads of the sample (1 <= n < 2^32), numbered through its resident blocks.  len: u64[n], zero, then filled block by
+// block by launch_subsample_lengths (reads of blocks that hold no base keep length 0).  launch_subsample_select leaves flag[i] = 1 for the
+// kept reads, rank[i] = kept reads before i and boff[i] = kept bases before i (n + 1 entries each: entry n holds the totals).  key and idx:
+// n + 1 entries, key_sorted, idx_sorted and csum: n entries, scratch; temp: subsample_scan_temp_bytes(n) bytes; cut: two device words.
+struct SubsampleSelect {
+    uint64_t n, target, seed;
+    uint64_t *len, *key, *key_sorted, *csum, *boff;
+    uint32_t *idx, *idx_sorted, *rank;
+    uint8_t* flag;
+    unsigned long long* cut;
+    void* temp;
+    size_t temp_bytes;
+};
+size_t subsample_scan_temp_bytes(uint64_t n);
+hipError_t launch_subsample_lengths(const uint64_t* offsets, uint64_t n_reads, uint64_t first, uint64_t n, uint64_t* len, hipStream_t stream);
+hipError_t launch_subsample_select(const SubsampleSelect& s, hipStream_t stream);
+// out[2 b] = rank[first[b]], out[2 b + 1] = boff[first[b]] for n_bounds read numbers (<= n) in device memory
+hipError_t launch_subsample_bounds(const uint64_t* first, uint32_t n_bounds, uint64_t n, const uint32_t* rank, const uint64_t* boff, unsigned long long* out,
+    hipStream_t stream);
+// Compaction of one resident block (reads first .. first + n_reads - 1 of the sample; n_reads >= 1) into a block of its new_reads kept
+// reads and new_bases kept bases (what the scans say: launch_subsample_bounds).  bases / offsets / n_bases: the old block.
+struct GatherEntry;
+struct SubsampleBlock {
+    const uint8_t* bases;
+    const uint64_t* offsets;
+    uint64_t n_reads, n_bases, first;
+    const uint8_t* flag;
+    const uint32_t* rank;
+    const uint64_t* boff;
+    uint64_t new_reads, new_bases;
+};
+// new_offsets[new_reads + 1], and per kept read its first base in the old block: src_start[new_reads] (packed blocks) or table[new_reads]
+// for launch_gather_reads (ASCII blocks); either may be null.  *err (zeroed by the caller) is set to 1 by any kernel below that finds the
+// scans, the block's offsets and these sizes at odds; nothing is written out of bounds then.
+hipError_t launch_subsample_tables(const SubsampleBlock& b, uint64_t* new_offsets, uint64_t* src_start, GatherEntry* table, uint32_t* err, hipStream_t stream);
+// words[ceil(new_bases / 16)] of the kept reads, tail bits of the last word clear; one 16-byte store per four words when words is 16-byte aligned
+hipError_t launch_subsample_pack(const SubsampleBlock& b, const uint64_t* new_offsets, const uint64_t* src_start, uint32_t* words, uint32_t* err, hipStream_t stream);
+// The old block's n_npos (>= 1) listed positions that lie in kept reads: chunk_prefix[subsample_npos_chunks(n_npos)] receives their number;
+// then they are written at their new places, ascending.  chunk_count / chunk_prefix: subsample_npos_chunks(n_npos) + 1 words each; temp:
+// scan_temp_bytes of as many.
+uint32_t subsample_npos_chunks(uint64_t n_npos);
+hipError_t launch_subsample_npos_count(const SubsampleBlock& b, const uint64_t* npos, uint64_t n_npos, uint32_t* chunk_count, uint32_t* chunk_prefix, void* temp,
+    size_t temp_bytes, hipStream_t stream);
+hipError_t launch_subsample_npos_emit(const SubsampleBlock& b, const uint64_t* npos, uint64_t n_npos, const uint32_t* chunk_prefix, uint64_t* out, uint64_t out_cap,
+    hipStream_t stream);
+
 // anchor_scan.hip: reads of a resident batch that hold one of the (sorted) anchor k-mers of length A -- every such read once,
 // in any order, appended to `list` (count keeps counting past list_cap).  prefilter: 2^16 bits, bit (kmer & 0xFFFF) set for every
 // anchor; flags: n_reads words, zero before the launch.

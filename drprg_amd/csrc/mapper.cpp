@@ -1010,6 +1010,8 @@ void Mapper::drop_kept()
     }
     kept_arenas_.clear();
     kept_.clear();
+    kept_first_.clear();
+    kept_seen_ = 0;
     arena_at_ = nullptr;
     arena_left_ = 0;
     kept_bytes_ = 0;
@@ -1028,6 +1030,158 @@ uint64_t Mapper::map_kept_from(const Mapper& other)
     sync();
     HIPCHK(hipStreamSynchronize(stream_));
     return n;
+}
+
+Mapper::SubsampleResult Mapper::subsample_kept(uint64_t target_bases, uint64_t seed, std::vector<uint8_t>& flags)
+{
+    if (!kept_complete())
+        throw Error(DRPRG_ENODATA, "random subsample: not every read of the sample is resident in device memory (drprg_hip_keep_reads is off, or the "
+                                   "sample is larger than its limit; the executables take the limit from DRPRG_HIP_KEEP_READS_GB)");
+    sync();
+    HIPCHK(hipSetDevice(device_));
+    HIPCHK(hipStreamSynchronize(stream_));
+    flags.clear();
+    const uint64_t n = kept_seen_;
+    uint64_t bases = 0;
+    for (const DeviceBatch& b : kept_) bases += b.n_bases;
+    SubsampleResult res { n, bases, n, bases };
+    if (bases <= target_bases) return res;
+    if (n >= (1ull << 32)) throw Error(DRPRG_EOVERFLOW, "random subsample: 2^32 reads or more in one sample");
+    // ---- selection (device scratch of this call) ----
+    DeviceBuffer<uint64_t> d_len, d_key, d_key_sorted, d_csum, d_boff, d_first;
+    DeviceBuffer<uint32_t> d_idx, d_idx_sorted, d_rank;
+    DeviceBuffer<uint8_t> d_flag;
+    DeviceBuffer<unsigned long long> d_cut, d_bounds; // d_cut: [0..1] the cut, [2] the compaction's error word
+    DeviceBuffer<unsigned char> d_temp;
+    d_len.alloc(n); d_key.alloc(n + 1); d_key_sorted.alloc(n); d_csum.alloc(n); d_boff.alloc(n + 1);
+    d_idx.alloc(n + 1); d_idx_sorted.alloc(n); d_rank.alloc(n + 1); d_flag.alloc(n); d_cut.alloc(4);
+    d_temp.alloc(dev::subsample_scan_temp_bytes(n));
+    HIPCHK(hipMemsetAsync(d_len.data(), 0, d_len.bytes(), stream_));
+    HIPCHK(hipMemsetAsync(d_cut.data(), 0, d_cut.bytes(), stream_));
+    for (size_t b = 0; b < kept_.size(); ++b)
+        HIPCHK(dev::launch_subsample_lengths(kept_[b].d_offsets, kept_[b].n_reads, kept_first_[b], n, d_len.data(), stream_));
+    dev::SubsampleSelect sel {};
+    sel.n = n; sel.target = target_bases; sel.seed = seed;
+    sel.len = d_len.data(); sel.key = d_key.data(); sel.key_sorted = d_key_sorted.data(); sel.csum = d_csum.data(); sel.boff = d_boff.data();
+    sel.idx = d_idx.data(); sel.idx_sorted = d_idx_sorted.data(); sel.rank = d_rank.data(); sel.flag = d_flag.data(); sel.cut = d_cut.data();
+    sel.temp = d_temp.data(); sel.temp_bytes = d_temp.size();
+    HIPCHK(dev::launch_subsample_select(sel, stream_));
+    // kept reads and bases in front of every block's first read, behind its last one, and in all
+    std::vector<uint64_t> first;
+    for (size_t b = 0; b < kept_.size(); ++b) {
+        first.push_back(kept_first_[b]);
+        first.push_back(kept_first_[b] + kept_[b].n_reads);
+    }
+    first.push_back(n);
+    std::vector<unsigned long long> bounds(2 * first.size());
+    d_first.alloc(first.size());
+    d_bounds.alloc(bounds.size());
+    HIPCHK(hipMemcpyAsync(d_first.data(), first.data(), first.size() * sizeof(uint64_t), hipMemcpyHostToDevice, stream_));
+    HIPCHK(dev::launch_subsample_bounds(d_first.data(), (uint32_t)first.size(), n, d_rank.data(), d_boff.data(), d_bounds.data(), stream_));
+    HIPCHK(hipMemcpyAsync(bounds.data(), d_bounds.data(), bounds.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream_));
+    flags.resize(n);
+    HIPCHK(hipMemcpyAsync(flags.data(), d_flag.data(), n, hipMemcpyDeviceToHost, stream_));
+    HIPCHK(hipStreamSynchronize(stream_));
+    res.reads_kept = bounds[bounds.size() - 2];
+    res.bases_kept = bounds[bounds.size() - 1];
+    // ---- compaction: the new set in arenas of its own; the old ones are released by their owners when this scope is left ----
+    std::vector<DeviceBuffer<uint8_t>> old_arenas = std::move(kept_arenas_);
+    std::vector<DeviceBatch> old_kept = std::move(kept_);
+    std::vector<uint64_t> old_first = std::move(kept_first_);
+    uint8_t* const old_at = arena_at_;
+    const size_t old_left = arena_left_;
+    const uint64_t old_bytes = kept_bytes_;
+    kept_arenas_.clear(); kept_.clear(); kept_first_.clear();
+    arena_at_ = nullptr; arena_left_ = 0; kept_bytes_ = 0;
+    try {
+        uint64_t max_reads = 0, max_npos = 0;
+        for (size_t b = 0; b < old_kept.size(); ++b) {
+            max_reads = std::max<uint64_t>(max_reads, bounds[4 * b + 2] - bounds[4 * b]);
+            max_npos = std::max(max_npos, old_kept[b].n_npos);
+        }
+        DeviceBuffer<uint64_t> d_src;
+        DeviceBuffer<dev::GatherEntry> d_table;
+        DeviceBuffer<uint32_t> d_count, d_prefix;
+        DeviceBuffer<unsigned char> d_ntemp;
+        d_src.alloc(max_reads);
+        d_table.alloc(max_reads);
+        if (max_npos) {
+            const uint64_t chunks = (uint64_t)dev::subsample_npos_chunks(max_npos) + 1;
+            d_count.alloc(chunks); d_prefix.alloc(chunks); d_ntemp.alloc(dev::scan_temp_bytes((uint32_t)chunks));
+        }
+        uint32_t* const d_err = reinterpret_cast<uint32_t*>(d_cut.data() + 2);
+        for (size_t b = 0; b < old_kept.size(); ++b) {
+            const DeviceBatch& ob = old_kept[b];
+            const uint64_t nr = bounds[4 * b + 2] - bounds[4 * b], nb = bounds[4 * b + 3] - bounds[4 * b + 1];
+            if (nb == 0) continue; // (nothing of the block is kept, or empty reads only: they are counted below, as map_host_async counts them)
+            const uint64_t payload = ob.packed ? (nb + 15) / 16 * 4 : nb;
+            uint8_t* db = static_cast<uint8_t*>(arena_take(payload + 64));
+            uint64_t* doff = db ? static_cast<uint64_t*>(arena_take((nr + 1) * sizeof(uint64_t))) : nullptr;
+            if (!db || !doff) throw Error(DRPRG_ENOMEM, "random subsample: no device memory for the kept reads beside the resident sample");
+            HIPCHK(hipMemsetAsync(db + payload, 0, 64, stream_));
+            const dev::SubsampleBlock sb { ob.d_bases, ob.d_offsets, ob.n_reads, ob.n_bases, old_first[b], d_flag.data(), d_rank.data(), d_boff.data(), nr, nb };
+            DeviceBatch kb;
+            kb.d_bases = db; kb.d_offsets = doff; kb.n_reads = nr; kb.n_bases = nb; kb.packed = ob.packed;
+            if (ob.packed) {
+                HIPCHK(dev::launch_subsample_tables(sb, doff, d_src.data(), nullptr, d_err, stream_));
+                HIPCHK(dev::launch_subsample_pack(sb, doff, d_src.data(), reinterpret_cast<uint32_t*>(db), d_err, stream_));
+                if (ob.n_npos) {
+                    const uint32_t chunks = dev::subsample_npos_chunks(ob.n_npos);
+                    HIPCHK(dev::launch_subsample_npos_count(sb, ob.d_npos, ob.n_npos, d_count.data(), d_prefix.data(), d_ntemp.data(), d_ntemp.size(), stream_));
+                    uint32_t cnt = 0;
+                    HIPCHK(hipMemcpyAsync(&cnt, d_prefix.data() + chunks, sizeof cnt, hipMemcpyDeviceToHost, stream_));
+                    HIPCHK(hipStreamSynchronize(stream_));
+                    if (cnt) {
+                        uint64_t* dnp = static_cast<uint64_t*>(arena_take((uint64_t)cnt * sizeof(uint64_t)));
+                        if (!dnp) throw Error(DRPRG_ENOMEM, "random subsample: no device memory for the kept reads beside the resident sample");
+                        HIPCHK(dev::launch_subsample_npos_emit(sb, ob.d_npos, ob.n_npos, d_prefix.data(), dnp, cnt, stream_));
+                        kb.d_npos = dnp;
+                        kb.n_npos = cnt;
+                    }
+                }
+            } else {
+                HIPCHK(hipMemsetAsync(d_table.data(), 0, nr * sizeof(dev::GatherEntry), stream_)); // (an entry the kernel refuses to fill copies nothing)
+                HIPCHK(dev::launch_subsample_tables(sb, doff, nullptr, d_table.data(), d_err, stream_));
+                HIPCHK(dev::launch_gather_reads(d_table.data(), (uint32_t)nr, db, stream_));
+            }
+            kept_.push_back(kb);
+            kept_first_.push_back(bounds[4 * b]);
+        }
+        uint32_t err = 0;
+        HIPCHK(hipMemcpyAsync(&err, d_err, sizeof err, hipMemcpyDeviceToHost, stream_));
+        HIPCHK(hipStreamSynchronize(stream_)); // (nothing reads the old blocks any more)
+        if (err) throw Error(DRPRG_EIO, "random subsample: the resident blocks' offsets and the selection do not fit each other");
+    } catch (...) { // the sample as it was
+        (void)hipStreamSynchronize(stream_);
+        kept_arenas_ = std::move(old_arenas);
+        kept_ = std::move(old_kept);
+        kept_first_ = std::move(old_first);
+        arena_at_ = old_at; arena_left_ = old_left; kept_bytes_ = old_bytes;
+        flags.clear();
+        throw;
+    }
+    kept_seen_ = res.reads_kept;
+    // ---- the kept reads mapped afresh ----
+    HIPCHK(hipMemsetAsync(d_covg_.data(), 0, d_covg_.bytes(), stream_)); // [coverage | reads per PRG]
+    HIPCHK(hipMemsetAsync(d_counters_.data(), 0, d_counters_.bytes(), stream_));
+    HIPCHK(hipStreamSynchronize(stream_));
+    tot_reads_ = tot_bases_ = tot_hits_ = tot_leftover_ = tot_minimizers_ = 0;
+    uint64_t in_blocks = 0;
+    in_keep_call_ = true;
+    try {
+        for (const DeviceBatch& b : kept_) {
+            map(b, nullptr, nullptr, stream_, true);
+            in_blocks += b.n_reads;
+        }
+        sync();
+    } catch (...) {
+        in_keep_call_ = false;
+        throw;
+    }
+    in_keep_call_ = false;
+    HIPCHK(hipStreamSynchronize(stream_));
+    tot_reads_ += res.reads_kept - in_blocks; // (kept empty reads of blocks that hold no base any more)
+    return res;
 }
 
 void Mapper::select_reads_with_anchors(std::vector<uint64_t> anchors, uint32_t A, std::vector<uint8_t>& bases, std::vector<uint64_t>& offsets,
@@ -1141,6 +1295,7 @@ void Mapper::map_host_async(const HostBatch& hb)
         if (hb.offsets[0] != 0) throw Error(DRPRG_EINVAL, "offsets[0] must be 0");
         if (hb.n_bases() == 0) {
             tot_reads_ += n_reads; // (only empty reads: nothing to keep)
+            kept_seen_ += n_reads;
             return;
         }
         const uint64_t n_npos = hb.packed || hb.bam ? hb.n_npos : 0;
@@ -1160,6 +1315,8 @@ void Mapper::map_host_async(const HostBatch& hb)
             HIPCHK(hipEventRecord(kept_copied_, copy_stream_));
             HIPCHK(hipStreamWaitEvent(stream_, kept_copied_, 0));
             kept_.push_back(kb);
+            kept_first_.push_back(kept_seen_);
+            kept_seen_ += n_reads;
             in_keep_call_ = true;
             try {
                 map(kb, nullptr, nullptr, stream_, true);

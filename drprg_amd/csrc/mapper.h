@@ -120,6 +120,16 @@ public:
         std::vector<uint64_t>* ids = nullptr, uint64_t window_bytes = 0);
     // maps the batches another Mapper of the same device keeps (it must outlive the call); returns the reads mapped
     uint64_t map_kept_from(const Mapper& other);
+    // Random subsample of the resident sample to target_bases (the rule: include/drprg_hip.h "random subsample"; subsample.hip).  Needs
+    // kept_complete().  The sum of the lengths is at most target_bases: nothing happens.  Otherwise the kept reads are selected on the device,
+    // every resident block is compacted into a block of its kept reads (arenas of their own: the peak is the old set plus the new one), the
+    // old arenas go back through their owners, coverage, reads per PRG and the counters are cleared and the new set is mapped; kept(),
+    // kept_bytes() and everything that reads them see the kept reads from then on.  flags: one byte per read of the sample as it was,
+    // 1 = kept (left empty when nothing was dropped).
+    struct SubsampleResult {
+        uint64_t reads_before, bases_before, reads_kept, bases_kept;
+    };
+    SubsampleResult subsample_kept(uint64_t target_bases, uint64_t seed, std::vector<uint8_t>& flags);
 
     // this += other, on the device (the other Mapper's vectors are left as they are): peer copy into a scratch buffer + one
     // add kernel, or the add kernel alone when both live on the same device.  Both are synchronised first.
@@ -349,6 +359,10 @@ private:
     uint8_t* arena_at_ = nullptr;
     size_t arena_left_ = 0;
     std::vector<DeviceBatch> kept_;
+    // the reads of the sample are numbered in the order they were kept: kept_first_[b] = number of kept_[b]'s first read, kept_seen_ = reads
+    // numbered so far (a block of empty reads only is not kept, but its reads are numbered)
+    std::vector<uint64_t> kept_first_;
+    uint64_t kept_seen_ = 0;
     uint64_t kept_cap_ = 0, kept_bytes_ = 0;
     bool kept_broken_ = false, in_keep_call_ = false;
     Event kept_copied_;

@@ -5,6 +5,7 @@
 //   pandora discover -g G --max-covg M -v -o <dir> -t T -w W -k K -c C [-I] [-K] <prg> <query.tsv>
 //   pandora map      --genotype --local --gt-conf 0 -v -o <out> -g G --max-covg M --vcf-refs <genes.fa>
 //                    -t T -w W -k K -c C [-I] [-K] <prg> <reads>
+// and, this build's own, --subsample-covg D [--seed S] on map and discover (include/drprg_hip.h "random subsample"),
 // and writes the files drprg then looks for: <prg>.k<K>.w<W>.idx + kmer_prgs/ (index),
 // <dir>/denovo_paths.txt (discover, /root/reference/src/lib.rs:569-577),
 // <out>/pandora_genotyped.vcf (map, /root/reference/src/lib.rs:644-646).
@@ -41,6 +42,11 @@ struct Args {
     int max_diff = -1;
     uint64_t genome_size = 5000000;
     uint64_t max_covg = 300;
+    bool max_covg_given = false;
+    // --subsample-covg D [--seed S]: the resident sample cut to D x genome_size bases at random (include/drprg_hip.h "random subsample")
+    bool subsample = false, seed_given = false;
+    double subsample_covg = 0;
+    uint64_t seed = 1;
     std::string outdir = "pandora", vcf_refs;
     std::vector<std::string> positional;
     int device = 0;
@@ -57,11 +63,18 @@ void usage()
     std::fprintf(stderr,
         "pandora-compatible front end of the MI355X drprg hot path\n"
         "  pandora index    [-t N] [-w W] [-k K] <prg>\n"
-        "  pandora map      [--genotype] [--local] [--gt-conf X] [-v] [-o DIR] [-g SIZE] [--max-covg N]\n"
+        "  pandora map      [--genotype] [--local] [--gt-conf X] [-v] [-o DIR] [-g SIZE] [--max-covg N | --subsample-covg D [--seed S]]\n"
         "                   [--vcf-refs FASTA] [-t N] [-w W] [-k K] [-c N] [-I] [-K] [-e RATE] [--max-diff N] <prg> <reads>\n"
         "  pandora discover [same mapping options] <prg> <query.tsv>\n"
         "  --max-covg N: reads are taken in file order up to and including the first one at which (N + 1) x SIZE bases are reached;\n"
         "                the rest is not mapped (default 300; 4294967295 = no cap)\n"
+        "                A prefix is a fair sample only of a file in random order: of a coordinate-sorted BAM it holds the start of the\n"
+        "                genome alone, and the loci behind it come out absent.  Use --subsample-covg for such a file.\n"
+        "  --subsample-covg D [--seed S]: instead of the prefix cap, map every read, keep them in device memory and cut the sample AT RANDOM\n"
+        "                to D x SIZE bases: reads in the order of a 64-bit key made from S (default 1) and the read's number, up to and\n"
+        "                including the one that reaches the target; the kept reads are mapped afresh.  The default --max-covg gives way\n"
+        "                to it; an explicit --max-covg other than 4294967295 beside it is an error.  Needs the whole sample resident\n"
+        "                (DRPRG_HIP_KEEP_READS_GB, default 32): the run fails if it is not.\n"
         "  <reads>: FASTA or FASTQ, plain or gzip; or BAM (secondary and supplementary records are skipped, reverse-strand records are\n"
         "           reverse-complemented, qualities and alignments are ignored)\n"
         "environment: DRPRG_HIP_DEVICE selects the GPU (default 0); DRPRG_HIP_DEVICES=0,1,.. maps on several GPUs of the node\n");
@@ -86,7 +99,19 @@ Args parse(int argc, char** argv)
         else if (s == "-k") a.k = std::atoi(need(i));
         else if (s == "-c" || s == "--min-cluster-size") a.min_cluster_size = (uint32_t)std::strtoul(need(i), nullptr, 10);
         else if (s == "-g" || s == "--genome-size") a.genome_size = std::strtoull(need(i), nullptr, 10);
-        else if (s == "--max-covg") a.max_covg = std::strtoull(need(i), nullptr, 10);
+        else if (s == "--max-covg") {
+            a.max_covg = std::strtoull(need(i), nullptr, 10);
+            a.max_covg_given = true;
+        } else if (s == "--subsample-covg") {
+            char* end = nullptr;
+            const char* v = need(i);
+            a.subsample_covg = std::strtod(v, &end);
+            if (end == v || *end || !(a.subsample_covg >= 0)) die(std::string("--subsample-covg needs a depth >= 0, not ") + v, 2);
+            a.subsample = true;
+        } else if (s == "--seed") {
+            a.seed = std::strtoull(need(i), nullptr, 10);
+            a.seed_given = true;
+        }
         else if (s == "-o" || s == "--outdir") a.outdir = need(i);
         else if (s == "--vcf-refs") a.vcf_refs = need(i);
         else if (s == "--gt-conf") a.gt_conf = std::atof(need(i));
@@ -104,6 +129,11 @@ Args parse(int argc, char** argv)
         } else if (!s.empty() && s[0] == '-' && s.size() > 1) die("unknown option " + s, 2);
         else a.positional.push_back(s);
     }
+    // (usage errors of the two sampling rules: before anything is opened)
+    if (a.seed_given && !a.subsample) die("--seed belongs to --subsample-covg", 2);
+    if (a.subsample && a.max_covg_given && a.max_covg != 4294967295ull)
+        die("--max-covg and --subsample-covg are alternatives (the prefix cap or the random subsample): give one of them", 2);
+    if (a.subsample) a.max_covg = 4294967295ull; // the default cap gives way
     if (const char* d = std::getenv("DRPRG_HIP_DEVICE")) a.device = std::atoi(d);
     return a;
 }
@@ -187,7 +217,34 @@ std::string run_tag(const Args& a, const std::string& reads)
     };
     return stamp(a.positional[0]) + "|" + stamp(reads) + "|w" + std::to_string(a.w) + "|k" + std::to_string(a.k) + "|c"
         + std::to_string(a.min_cluster_size) + "|I" + std::to_string((int)a.illumina) + "|e" + std::to_string(a.error_rate) + "|m"
-        + std::to_string(a.max_diff) + "|g" + std::to_string((unsigned long long)a.genome_size) + "|M" + std::to_string((unsigned long long)a.max_covg);
+        + std::to_string(a.max_diff) + "|g" + std::to_string((unsigned long long)a.genome_size) + "|M" + std::to_string((unsigned long long)a.max_covg)
+        + (a.subsample ? "|S" + std::to_string(a.subsample_covg) + "/" + std::to_string((unsigned long long)a.seed) : std::string());
+}
+
+// The reads stay in HBM after the mapping pass: up to DRPRG_HIP_KEEP_READS_GB per device, default 32, 0 = off.  --subsample-covg works on
+// the resident sample, so there "off" is an error, not a slower route.
+void keep_reads(drprg_hip_ctx* ctx, const Args& a)
+{
+    double keep_gb = 32;
+    if (const char* e = std::getenv("DRPRG_HIP_KEEP_READS_GB")) keep_gb = std::atof(e);
+    if (a.subsample) drprg_hip_set_ordered_ingest(ctx, 1); // (the subsample numbers the reads in file order)
+    if (keep_gb > 0) {
+        if (int rc = drprg_hip_keep_reads(ctx, (uint64_t)(keep_gb * 1e9))) die(drprg_hip_last_error(ctx), -rc);
+    } else if (a.subsample)
+        die("--subsample-covg needs the reads resident in device memory: DRPRG_HIP_KEEP_READS_GB=0 switches that off");
+}
+
+// --subsample-covg: behind the mapping pass, before anything reads coverage.  Fails loudly when the sample is not resident.
+void subsample(drprg_hip_ctx* ctx, const Args& a)
+{
+    if (!a.subsample) return;
+    const uint64_t target = (uint64_t)(a.subsample_covg * (double)a.genome_size);
+    uint64_t out[4] = { 0, 0, 0, 0 };
+    if (int rc = drprg_hip_subsample(ctx, target, a.seed, out)) die(std::string("--subsample-covg: ") + drprg_hip_last_error(ctx), -rc);
+    if (a.verbose)
+        std::printf("[pandora-hip] subsample: reads_before=%llu bases_before=%llu reads_kept=%llu bases_kept=%llu (target %llu bases, seed %llu)\n",
+            (unsigned long long)out[0], (unsigned long long)out[1], (unsigned long long)out[2], (unsigned long long)out[3], (unsigned long long)target,
+            (unsigned long long)a.seed);
 }
 
 // -v: says where the depth cap stopped the pass, if it did
@@ -224,7 +281,9 @@ int cmd_map(const Args& a)
         std::printf("[pandora-hip] coverage of this PRG and these reads taken from %s (reads=%llu bases=%llu hits=%llu): no second mapping pass\n",
             cache.c_str(), (unsigned long long)cached[0], (unsigned long long)cached[1], (unsigned long long)cached[3]);
     } else {
+        if (a.subsample) keep_reads(ctx, a);
         if (int rc = drprg_hip_map_fastx(ctx, a.positional[1].c_str())) die(drprg_hip_last_error(ctx), -rc);
+        subsample(ctx, a);
         report_counters(ctx, now_s() - t0);
         report_cap(ctx, a);
         report_bam(ctx, a);
@@ -252,14 +311,10 @@ int cmd_discover(const Args& a)
     drprg_hip_ctx* ctx = open_ctx(a);
     // pandora discover walks the reads twice (mapping, then the candidate regions); here the second walk is over the blocks the
     // first one left in HBM (up to DRPRG_HIP_KEEP_READS_GB per device, default 32, 0 = read the file again)
-    {
-        double keep_gb = 32;
-        if (const char* e = std::getenv("DRPRG_HIP_KEEP_READS_GB")) keep_gb = std::atof(e);
-        if (keep_gb > 0)
-            if (int rc = drprg_hip_keep_reads(ctx, (uint64_t)(keep_gb * 1e9))) die(drprg_hip_last_error(ctx), -rc);
-    }
+    keep_reads(ctx, a);
     double t0 = now_s();
     if (int rc = drprg_hip_map_fastx(ctx, reads.c_str())) die(drprg_hip_last_error(ctx), -rc);
+    subsample(ctx, a);
     report_counters(ctx, now_s() - t0);
     report_cap(ctx, a);
     report_bam(ctx, a);

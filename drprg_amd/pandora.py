@@ -192,6 +192,26 @@ class Context:
         _check(lib.drprg_hip_resident_info(self._h, out), self._h)
         return dict(complete=bool(out[0]), bytes=int(out[1]), blocks=int(out[2]), last_discover_from_hbm=bool(out[3]))
 
+    # ---- random subsample of the resident sample (include/drprg_hip.h: drprg_hip_subsample) -----
+    SUBSAMPLE_SEED = 1  # the executables' default --seed
+
+    def subsample(self, target_bases, seed=SUBSAMPLE_SEED):
+        """cuts the resident sample to about target_bases at random and maps the kept reads afresh (nothing happens when the sample holds
+        no more than that); returns what was there and what is left"""
+        out = (C.c_uint64 * 4)()
+        _check(lib.drprg_hip_subsample(self._h, int(target_bases), int(seed) & (2 ** 64 - 1), out), self._h)
+        return dict(reads_before=int(out[0]), bases_before=int(out[1]), reads_kept=int(out[2]), bases_kept=int(out[3]))
+
+    def set_ordered_ingest(self, on):
+        """map_fastx hands its blocks over in file order (what subsample()'s numbering needs of a file of more than one block)"""
+        _check(lib.drprg_hip_set_ordered_ingest(self._h, 1 if on else 0), self._h)
+
+    def subsample_flags(self, n_reads):
+        """one byte per read of the sample as the last subsample() found it, 1 = kept (n_reads: how many it held)"""
+        flags = np.zeros(int(n_reads), dtype=np.uint8)
+        _check(lib.drprg_hip_subsample_flags(self._h, _ptr(flags), flags.size), self._h)
+        return flags
+
     def select_reads(self, anchors, A, window_bytes=0):
         """the resident reads in which one of `anchors` (k-mers of A bases as integers, 2 bits per base, A 0 C 1 G 2 T 3, first base high)
         starts -- the selection discover_reads runs on the device (drprg_hip_select_reads); returns (bases u8, offsets u64, ids u64 =

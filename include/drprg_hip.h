@@ -287,6 +287,40 @@ int drprg_hip_discover_reads(drprg_hip_ctx* ctx, const char* reads_path, const c
 int drprg_hip_keep_reads(drprg_hip_ctx* ctx, uint64_t max_bytes);
 int drprg_hip_map_resident(drprg_hip_ctx* ctx, drprg_hip_ctx* from);
 int drprg_hip_resident_info(drprg_hip_ctx* ctx, uint64_t out[4]);
+/* ---- Random subsample of the resident sample to a target depth.  THIS BUILD'S OWN RULE, not pandora's: pandora knows only the depth cap
+ * above, a prefix of the file, which is a fair sample only of a file in random order (under a cap a coordinate-sorted BAM gives reads
+ * from the start of the genome alone).  Workflows subsample at random before they call drprg; this does it on the reads that are
+ * already in HBM, instead of one more pass over the file on the host.
+ *   The reads of the sample are numbered i = 0 .. n-1 in the order they were mapped since the last drprg_hip_reset: file order, through the
+ *   resident blocks and through several drprg_hip_map_fastx calls.  L_i is the length of read i.  Given T = target_bases and a 64-bit seed:
+ *     1. sum(L_i) <= T: every read is kept and nothing else happens (coverage, counters and the resident set are untouched).
+ *     2. Otherwise key(i) = splitmix64(seed + 0x9E3779B97F4A7C15 * (i + 1)) in 64-bit unsigned arithmetic, where splitmix64(z) is the
+ *        usual finaliser: z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB; return z ^ (z >> 31).
+ *     3. The reads are ordered by (key, i) ascending and kept in that order up to AND INCLUDING the first read at which the running sum
+ *        of lengths reaches T -- the same "up to and including" as the depth cap.  (T = 0: exactly the first read in key order.)
+ *     4. The kept reads stay in file order.  Zero-length reads take part like any other read.
+ *   The result depends on the reads' order and lengths, T and the seed alone: not on how the ingest cut the file into blocks, not on the
+ *   input form (ASCII, packed, BAM), not on the number of parser threads.
+ *   drprg_hip_subsample(ctx, target_bases, seed, out): out[0..3] = reads before, bases before, reads kept, bases kept.  When reads are
+ *     dropped, every resident block is compacted on the device into a block of its kept reads (csrc/subsample.hip; the peak device memory
+ *     of the call is the old set plus the new one), coverage, reads per PRG and the counters are cleared and the kept reads are mapped
+ *     afresh: from then on the context -- drprg_hip_coverage, drprg_hip_counters, drprg_hip_genotype, drprg_hip_discover_reads from HBM,
+ *     drprg_hip_select_reads, drprg_hip_map_resident, drprg_hip_resident_info -- is that of a context that was given the kept reads
+ *     alone, and a second call numbers the kept reads from 0.  Needs every read mapped since the last reset to be resident
+ *     (drprg_hip_keep_reads before the first drprg_hip_map_fastx): -ENODATA (-61) otherwise, and the text names DRPRG_HIP_KEEP_READS_GB, the
+ *     executables' limit.  -EINVAL for a context over several devices (drprg_hip_open_multi) and for a context with a depth cap set
+ *     (drprg_hip_set_max_covg below 4294967295): the two rules are alternatives.  -EOVERFLOW for 2^32 reads or more.  A refused or failed
+ *     call leaves the context as it was.
+ *   drprg_hip_subsample_flags(ctx, flags, n): flags[i] = 1 if read i (numbering before the call) was kept by the last drprg_hip_subsample
+ *     since the last reset, else 0; all ones when nothing was dropped.  -EINVAL unless n is that call's out[0]. */
+int drprg_hip_subsample(drprg_hip_ctx* ctx, uint64_t target_bases, uint64_t seed, uint64_t out[4]);
+/* drprg_hip_map_fastx normally hands its blocks to the device as its parser threads fill them, in no particular order (coverage is a sum).
+ * The numbering above needs them in FILE order: drprg_hip_set_ordered_ingest(ctx, 1) makes drprg_hip_map_fastx hand them over one at a
+ * time in file order, the hand-over the depth cap uses, without a cap (0, the default: as before).  A sample of which some file arrived
+ * as more than one block without it is refused by drprg_hip_subsample (-EINVAL) rather than numbered by chance; a file that fits one
+ * block, and every block under a depth cap, is in order anyway.  The executables switch it on when --subsample-covg is given. */
+int drprg_hip_set_ordered_ingest(drprg_hip_ctx* ctx, int on);
+int drprg_hip_subsample_flags(drprg_hip_ctx* ctx, uint8_t* flags, uint64_t n);
 /* The read selection drprg_hip_discover_reads uses when the reads are resident, on its own: for every device of the context, in order,
  * every kept read in which a k-mer of `anchors` STARTS (anchors: n_anchors k-mers of A bases, 2 bits per base, A 0 C 1 G 2 T 3, first base
  * in the high bits; any order, duplicates allowed).  A block's reads are one base stream: read r of a block is returned iff for some p with
