@@ -15,6 +15,7 @@
 #include "mapper.h"
 #include "rccl_dyn.h"
 #include "pack.h"
+#include "read_qual_piece.h"
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -125,6 +126,11 @@ struct drprg_hip_ctx {
     bool subsampled = false;
     uint64_t subsample_n = 0;
     std::vector<uint8_t> subsample_flags;
+    // drprg_hip_set_read_filter: the settings (a reset keeps them) and what the filter has counted since the last reset -- added to by the
+    // submitters of drprg_hip_map_fastx, one per device, under filter_mu
+    Mapper::ReadFilter read_filter;
+    Mapper::FilterOutcome filter_counts;
+    std::mutex filter_mu;
     // (the page-locked ingest blocks of drprg_hip_map_fastx are recycled process-wide: PinPool above)
     // multi-device context: RCCL communicators of its devices (created on first use; empty when RCCL is not used)
     std::vector<Rccl::Comm> comms;
@@ -481,7 +487,28 @@ int drprg_hip_map_fastx(drprg_hip_ctx* ctx, const char* reads_path)
     hooks.packed = ctx->packed_input;
     hooks.bam_native = true; // a BAM file's reads travel in their 4-bit form and are converted on the device (bam_pack.hip), whatever `packed` says
     auto host_batch = [](const PinnedBatch& b) {
-        return Mapper::HostBatch { b.bases, b.offsets, b.n_reads, b.packed, b.npos, b.n_npos, b.bam, b.seq_start, b.reverse, b.seq_bytes };
+        return Mapper::HostBatch { b.bases, b.offsets, b.n_reads, b.packed, b.npos, b.n_npos, b.bam, b.seq_start, b.reverse, b.seq_bytes, b.qual, b.qual_bias };
+    };
+    // The read filter (drprg_hip_set_read_filter): every block goes through Mapper::map_host_filtered on the device that takes it, and
+    // everything behind it -- the counters, the depth cap's running total, the resident set -- sees the kept reads alone.  Not set: nothing
+    // below differs from a build without it (no quality byte is parsed or copied, no launch, no wait).
+    const Mapper::ReadFilter filter = ctx->read_filter;
+    hooks.want_qual = filter.use_qual();
+    uint64_t kept_reads = 0, kept_bases = 0; // of this call (under filter_mu)
+    auto filtered = [&](Mapper& dev, const Mapper::HostBatch& hb, uint64_t cap_need) {
+        Mapper::FilterOutcome o;
+        dev.map_host_filtered(hb, filter, cap_need, o);
+        std::lock_guard<std::mutex> g(ctx->filter_mu);
+        Mapper::FilterOutcome& t = ctx->filter_counts;
+        t.reads_seen += o.reads_seen; t.bases_seen += o.bases_seen; t.dropped_short += o.dropped_short; t.dropped_long += o.dropped_long;
+        t.dropped_lowq += o.dropped_lowq; t.reads_kept += o.reads_kept; t.bases_kept += o.bases_kept;
+        kept_reads += o.mapped_reads;
+        kept_bases += o.mapped_bases;
+        return o;
+    };
+    auto map_block = [&](Mapper& dev, const Mapper::HostBatch& hb) {
+        if (filter.any()) (void)filtered(dev, hb, 0);
+        else dev.map_host_async(hb);
     };
     uint64_t cap_T = 0;
     const bool capped = cap_target(ctx, cap_T);
@@ -498,7 +525,7 @@ int drprg_hip_map_fastx(drprg_hip_ctx* ctx, const char* reads_path)
     auto mapper_of = [&](size_t d) -> Mapper& { return d == 0 ? m : *ctx->extra[d - 1]; };
     if (ndev == 1) {
         // (the copy of a block overlaps the kernels of the block before it: Mapper::map_host_async)
-        hooks.submit = [&](const PinnedBatch& b) { m.map_host_async(host_batch(b)); };
+        hooks.submit = [&](const PinnedBatch& b) { map_block(m, host_batch(b)); };
     } else {
         hooks.concurrent_submit = true;
         hooks.submit = [&](const PinnedBatch& b) {
@@ -507,11 +534,11 @@ int drprg_hip_map_fastx(drprg_hip_ctx* ctx, const char* reads_path)
                 const size_t d = (first + i) % ndev;
                 std::unique_lock<std::mutex> l(dev_mu[d], std::try_to_lock);
                 if (!l.owns_lock()) continue;
-                mapper_of(d).map_host_async(host_batch(b));
+                map_block(mapper_of(d), host_batch(b));
                 return;
             }
             std::lock_guard<std::mutex> l(dev_mu[first]); // all busy: wait for the round-robin choice
-            mapper_of(first).map_host_async(host_batch(b));
+            map_block(mapper_of(first), host_batch(b));
         };
     }
     // Under a depth cap the blocks come in file order, one at a time (IngestHooks::submit_in_order), and are counted HERE, where they
@@ -523,6 +550,14 @@ int drprg_hip_map_fastx(drprg_hip_ctx* ctx, const char* reads_path)
             if (b.offsets[0] != 0) throw Error(DRPRG_EINVAL, "offsets[0] must be 0");
             Mapper::HostBatch hb = host_batch(b);
             CapCut c;
+            if (filter.any()) { // the cap cuts on the kept reads' running total: the device finds the read (Mapper::map_host_filtered)
+                uint64_t T = 0;
+                const Mapper::FilterOutcome o = filtered(mapper_of(rr++ % ndev), hb, cap_target(ctx, T) ? T - ctx->total_bases : 0);
+                c.reached = o.cut;
+                c.dropped = o.cut_dropped;
+                cap_commit(ctx, c, o.mapped_reads, o.mapped_bases);
+                return !ctx->cap_reached;
+            }
             cap_host_cut(ctx, hb, c);
             mapper_of(rr++ % ndev).map_host_async(hb);
             cap_commit(ctx, c, hb.n_reads, hb.n_bases());
@@ -543,8 +578,8 @@ int drprg_hip_map_fastx(drprg_hip_ctx* ctx, const char* reads_path)
         ctx->bam_reversed += st.bam_reversed;
         if (ordered) ctx->dropped_reads += st.discarded_reads; // (the accepted ones were counted block by block)
         else {
-            ctx->total_bases += st.bases;
-            ctx->accepted_reads += st.reads;
+            ctx->total_bases += filter.any() ? kept_bases : st.bases;
+            ctx->accepted_reads += filter.any() ? kept_reads : st.reads;
             if (st.batches > 1) ctx->fastx_unordered = true;
         }
         fold();
@@ -552,13 +587,26 @@ int drprg_hip_map_fastx(drprg_hip_ctx* ctx, const char* reads_path)
         if (e.code != DRPRG_EAGAIN_SERIAL) throw; // (a failed multi-device pass leaves partial vectors on the devices: reset before reuse)
         FastxReader rd(reads_path);
         ReadBatch batch;
-        while (rd.next_batch(batch, 8u << 20, 1ull << 30)) {
+        while (rd.next_batch(batch, 8u << 20, 1ull << 30, false, filter.use_qual())) {
             if (!batch.n_reads()) continue;
             Mapper::HostBatch hb { batch.bases.data(), batch.offsets.data(), batch.n_reads() };
             CapCut c;
-            cap_host_cut(ctx, hb, c);
-            m.map_host(hb);
-            cap_commit(ctx, c, hb.n_reads, hb.n_bases());
+            if (filter.any()) {
+                if (filter.use_qual() && batch.qual.size() != batch.bases.size())
+                    throw Error(DRPRG_EINVAL, "--min-read-qual: a FASTA record has no base qualities; a read is never kept or dropped by a quality threshold it cannot be held against");
+                hb.qual = batch.qual.data();
+                hb.qual_bias = 33;
+                uint64_t T = 0;
+                const Mapper::FilterOutcome o = filtered(m, hb, cap_target(ctx, T) ? T - ctx->total_bases : 0);
+                m.sync(); // (the batch's buffers go with the next read)
+                c.reached = o.cut;
+                c.dropped = o.cut_dropped;
+                cap_commit(ctx, c, o.mapped_reads, o.mapped_bases);
+            } else {
+                cap_host_cut(ctx, hb, c);
+                m.map_host(hb);
+                cap_commit(ctx, c, hb.n_reads, hb.n_bases());
+            }
             if (ctx->cap_reached) break;
         }
     }
@@ -592,10 +640,64 @@ int drprg_hip_set_threads(drprg_hip_ctx* ctx, int threads)
     return DRPRG_OK;
 }
 
+// ---- read filter -----------------------------------------------------------------------------------------------------------
+// The entry points that carry no qualities: while a filter is set they refuse, rather than map unfiltered reads without saying so.
+static void refuse_unfiltered(const drprg_hip_ctx* ctx, const char* entry)
+{
+    if (ctx->read_filter.any())
+        throw Error(DRPRG_EINVAL, std::string(entry) + ": a read filter is set (drprg_hip_set_read_filter) and this entry carries no qualities; the filter "
+                                                      "runs in drprg_hip_map_fastx (clear it with drprg_hip_set_read_filter(ctx, 0, 0, 0))");
+}
+
+int drprg_hip_set_read_filter(drprg_hip_ctx* ctx, uint64_t min_len, uint64_t max_len, uint32_t min_qual_milli)
+{
+    API_BEGIN(ctx)
+    if (max_len != 0 && max_len < min_len) throw Error(DRPRG_EINVAL, "read filter: the longest read allowed is shorter than the shortest");
+    if (min_qual_milli > dev::RQ_MAX_QUAL_MILLI) throw Error(DRPRG_EINVAL, "read filter: a mean quality above 93 cannot be asked for");
+    Mapper::ReadFilter f;
+    f.min_len = min_len;
+    f.max_len = max_len;
+    f.min_qual_milli = min_qual_milli;
+    f.T = min_qual_milli ? dev::rq_threshold(min_qual_milli) : 0;
+    ctx->read_filter = f;
+    API_END(ctx)
+}
+
+int drprg_hip_read_filter_info(drprg_hip_ctx* ctx, uint64_t out[8])
+{
+    API_BEGIN(ctx)
+    if (!out) throw Error(DRPRG_EINVAL, "null output");
+    std::lock_guard<std::mutex> g(ctx->filter_mu);
+    const Mapper::FilterOutcome& t = ctx->filter_counts;
+    out[0] = t.reads_seen; out[1] = t.bases_seen; out[2] = t.dropped_short; out[3] = t.dropped_long; out[4] = t.dropped_lowq;
+    out[5] = t.reads_kept; out[6] = t.bases_kept; out[7] = ctx->read_filter.T;
+    API_END(ctx)
+}
+
+int drprg_hip_read_filter_device(drprg_hip_ctx* ctx, const void* d_qual, uint32_t qual_bias, const void* d_offsets, uint64_t n_reads, uint64_t n_bases,
+    void* d_sums, void* d_flags, uint64_t out[4], void* hip_stream)
+{
+    API_BEGIN(ctx)
+    Mapper& m = need_mapper(ctx);
+    if (!out) throw Error(DRPRG_EINVAL, "null output");
+    if (qual_bias != 0 && qual_bias != 33) throw Error(DRPRG_EINVAL, "read filter: the quality bias is 33 (FASTQ) or 0 (BAM)");
+    uint64_t res[8];
+    m.read_filter_device(ctx->read_filter, (const uint8_t*)d_qual, qual_bias, (const uint64_t*)d_offsets, n_reads, n_bases, (unsigned long long*)d_sums,
+        (uint8_t*)d_flags, res, (hipStream_t)hip_stream);
+    out[0] = res[dev::RF_KEPT_READS];
+    out[1] = res[dev::RF_KEPT_BASES];
+    out[2] = res[dev::RF_BAD_AT];
+    out[3] = 0;
+    if (res[dev::RF_OFFSETS]) throw Error(DRPRG_EINVAL, "read filter: the offsets do not ascend to n_bases");
+    if (res[dev::RF_BAD_AT]) throw Error(DRPRG_EFORMAT, "a base quality outside 0..93 at quality byte " + std::to_string(res[dev::RF_BAD_AT] - 1));
+    API_END(ctx)
+}
+
 // A host batch in either form: cut at the depth cap (the offsets are here), mapped, counted.  The entry points have refused null buffers.
 static void map_host_batch(drprg_hip_ctx* ctx, Mapper::HostBatch hb)
 {
     Mapper& m = need_mapper(ctx);
+    refuse_unfiltered(ctx, "drprg_hip_map_host*");
     if (hb.n_reads && cap_open(ctx, hb.n_reads)) {
         if (hb.offsets[0] != 0) throw Error(DRPRG_EINVAL, "offsets[0] must be 0");
         CapCut c;
@@ -658,6 +760,7 @@ static int map_device_batch(drprg_hip_ctx* ctx, Mapper::DeviceBatch b, void* d_c
 {
     API_BEGIN(ctx)
     Mapper& m = need_mapper(ctx);
+    refuse_unfiltered(ctx, "drprg_hip_map_device*");
     if (b.n_reads == 0 || cap_open(ctx, b.n_reads)) { // (an empty batch still goes through the mapper's argument checks)
         CapCut c;
         cap_device_prefix(ctx, m, b, hip_stream, c);
@@ -928,6 +1031,7 @@ int drprg_hip_reset(drprg_hip_ctx* ctx)
     ctx->subsampled = false;
     ctx->subsample_n = 0;
     ctx->subsample_flags.clear();
+    ctx->filter_counts = Mapper::FilterOutcome(); // (the settings stay, as the depth cap does)
     API_END(ctx)
 }
 
@@ -1123,6 +1227,11 @@ int drprg_hip_discover_reads(drprg_hip_ctx* ctx, const char* reads_path, const c
     // the reads of this very file are in HBM (drprg_hip_keep_reads): the device picks the few that hold an anchor k-mer
     ResidentReads resident;
     ctx->last_discover_resident = reads_resident(ctx, reads_path);
+    // (the pass over the file knows nothing of the read filter: rather than pile up reads the mapping never saw, say so)
+    if (!ctx->last_discover_resident && ctx->filter_counts.reads_kept != ctx->filter_counts.reads_seen)
+        throw Error(DRPRG_ENODATA, "discover: the read filter dropped reads of this sample and the kept reads are not resident in device memory; a pass over "
+                                   "the file would see the unfiltered reads (drprg_hip_keep_reads before drprg_hip_map_fastx; the executables take the limit "
+                                   "from DRPRG_HIP_KEEP_READS_GB)");
     if (ctx->last_discover_resident)
         resident = [ctx](const std::vector<uint64_t>& anchors, uint32_t A, std::vector<uint8_t>& bases, std::vector<uint64_t>& offsets) {
             for (Mapper* m : mappers_of(ctx)) m->select_reads_with_anchors(anchors, A, bases, offsets);

@@ -108,6 +108,10 @@ void usage()
         "drprg predict -x <index dir | species[@version]> -i <reads.fq[.gz] | reads.bam> [-o DIR] [-s SAMPLE] [-I] [-S]\n"
         "              [-f MAF] [-d MIN_COVG] [-D MAX_COVG] [-b MIN_STRAND_BIAS] [-g MIN_GT_CONF] [-L MAX_INDEL] [-K MIN_FRS]\n"
         "              [-C MIN_CLUSTER_SIZE] [--debug] [-v] [-t THREADS] [--rebuild-index] [--subsample-covg D [--seed S]]\n"
+        "              [--min-read-len L] [--max-read-len L] [--min-read-qual Q]\n"
+        "--min-read-len L, --max-read-len L, --min-read-qual Q: reads shorter than L, longer than L or of a mean quality below Q (a decimal\n"
+        "              Phred value; the mean of the error probabilities, as nanoq and chopper take it) are dropped on the device before\n"
+        "              anything else sees them; --min-read-qual needs qualities (FASTQ, or BAM records that hold them).\n"
         "--subsample-covg D: the sample is cut at random to D x 4411532 bases on the device before discover and genotyping (reads in the\n"
         "              order of a 64-bit key made from the seed, default 1, and the read's number, up to and including the one that reaches\n"
         "              the target); needs the sample resident in device memory (DRPRG_HIP_KEEP_READS_GB, default 32), fails if it is not.\n"
@@ -150,6 +154,8 @@ int main(int argc, char** argv)
     bool subsample = false, seed_given = false;
     double subsample_covg = 0;
     uint64_t seed = 1;
+    uint64_t min_read_len = 0, max_read_len = 0; // the read filter (include/drprg_hip.h "read filter"); 0 = not set
+    uint32_t min_read_qual_milli = 0;
     uint32_t min_cluster = 10;
     drprg_hip_annotate_opts ao {};
     ao.min_covg = 3;
@@ -201,10 +207,24 @@ int main(int argc, char** argv)
             if (end == v || *end || !(subsample_covg >= 0)) die(std::string("--subsample-covg needs a depth >= 0, not ") + v, 2);
             subsample = true;
         } else if (a == "--seed") { seed = std::strtoull(need(i), nullptr, 10); seed_given = true; }
+        else if (a == "--min-read-len" || a == "--max-read-len") {
+            char* end = nullptr;
+            const char* v = need(i);
+            const uint64_t n = std::strtoull(v, &end, 10);
+            if (end == v || *end || *v == '-') die(a + " needs a number of bases, not " + v, 2);
+            (a == "--min-read-len" ? min_read_len : max_read_len) = n;
+        } else if (a == "--min-read-qual") {
+            char* end = nullptr;
+            const char* v = need(i);
+            const double q = std::strtod(v, &end);
+            if (end == v || *end || !(q >= 0) || q > 93) die(std::string("--min-read-qual needs a mean quality between 0 and 93, not ") + v, 2);
+            min_read_qual_milli = (uint32_t)(q * 1000.0 + 0.5);
+        }
         else if (a == "-h" || a == "--help") { usage(); return 0; }
         else die("unknown option " + a, 2);
     }
     if (seed_given && !subsample) die("--seed belongs to --subsample-covg", 2);
+    if (max_read_len && max_read_len < min_read_len) die("--max-read-len is below --min-read-len: no read can pass", 2);
     if (index.empty() || input.empty()) {
         usage();
         return 2;
@@ -256,6 +276,7 @@ int main(int argc, char** argv)
     if (int rc = drprg_hip_set_opts(ctx, &mo)) die(drprg_hip_last_error(ctx), -rc);
     drprg_hip_set_threads(ctx, threads);
     drprg_hip_set_input_format(ctx, packed_input()); // the parser threads pack the reads to 2 bits (DRPRG_HIP_INPUT=ascii: one byte per base)
+    if (int rc = drprg_hip_set_read_filter(ctx, min_read_len, max_read_len, min_read_qual_milli)) die(drprg_hip_last_error(ctx), -rc);
     // The reads stay in HBM after the mapping pass (up to DRPRG_HIP_KEEP_READS_GB per device, default 32, 0 = off): discover takes
     // the few reads it needs from there and a novel variant maps them again from there -- the file is read once.
     double keep_gb = 32;
@@ -269,6 +290,14 @@ int main(int argc, char** argv)
     // discover + map share ONE pass over the reads (the reference runs two, /root/reference/src/predict.rs:248-302)
     if (int rc = drprg_hip_map_fastx(ctx, input.c_str())) die(drprg_hip_last_error(ctx), -rc);
     if (verbose) std::fprintf(stderr, "[drprg-hip +%.3fs] reads mapped\n", since_start());
+    if (verbose && (min_read_len || max_read_len || min_read_qual_milli)) {
+        uint64_t fi[8] = {};
+        if (drprg_hip_read_filter_info(ctx, fi) == 0)
+            std::fprintf(stderr, "[drprg-hip +%.3fs] read filter: reads_seen=%llu bases_seen=%llu dropped_short=%llu dropped_long=%llu dropped_low_qual=%llu "
+                                 "reads_kept=%llu bases_kept=%llu (T=%llu)\n", since_start(), (unsigned long long)fi[0], (unsigned long long)fi[1],
+                (unsigned long long)fi[2], (unsigned long long)fi[3], (unsigned long long)fi[4], (unsigned long long)fi[5], (unsigned long long)fi[6],
+                (unsigned long long)fi[7]);
+    }
     if (subsample) { // the resident sample cut to the target depth at random (include/drprg_hip.h "random subsample"); never a silent full run
         const uint64_t target = (uint64_t)(subsample_covg * (double)mo.genome_size);
         uint64_t out[4] = { 0, 0, 0, 0 };
@@ -308,6 +337,7 @@ int main(int argc, char** argv)
                 if (int rc = drprg_hip_set_opts(next, &mo)) die(drprg_hip_last_error(next), -rc);
                 drprg_hip_set_threads(next, threads);
                 drprg_hip_set_input_format(next, packed_input()); // the parser threads pack the reads to 2 bits (DRPRG_HIP_INPUT=ascii: one byte per base)
+                if (int rc = drprg_hip_set_read_filter(next, min_read_len, max_read_len, min_read_qual_milli)) die(drprg_hip_last_error(next), -rc);
                 // the reads again, against the updated index: from HBM if the first context kept them all, else from the file
                 const int from_hbm = drprg_hip_map_resident(next, ctx);
                 if (from_hbm != 0 && from_hbm != -61 /* ENODATA */) die(drprg_hip_last_error(next), -from_hbm);

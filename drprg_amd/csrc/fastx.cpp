@@ -50,7 +50,7 @@ bool FastxReader::getline_(std::string& s)
     return got;
 }
 
-bool FastxReader::next_batch(ReadBatch& out, uint64_t max_reads, uint64_t max_bases, bool keep_names)
+bool FastxReader::next_batch(ReadBatch& out, uint64_t max_reads, uint64_t max_bases, bool keep_names, bool keep_qual)
 {
     out.clear();
     std::string header, seq, plus, qual;
@@ -72,8 +72,12 @@ bool FastxReader::next_batch(ReadBatch& out, uint64_t max_reads, uint64_t max_ba
                 seq += line_;
             }
             size_t need = seq.size(), gotq = 0;
-            while (gotq < need && getline_(line_)) gotq += line_.size();
+            while (gotq < need && getline_(line_)) {
+                gotq += line_.size();
+                if (keep_qual) out.qual.insert(out.qual.end(), line_.begin(), line_.end());
+            }
             if (gotq < need) throw Error(DRPRG_EFORMAT, "truncated FASTQ record in " + path_);
+            if (keep_qual && gotq != need) throw Error(DRPRG_EFORMAT, "a FASTQ record's quality lines are not as long as its sequence in " + path_);
         } else if (header[0] == '>') {
             seq.clear();
             while (getline_(line_)) {

@@ -11,12 +11,16 @@ struct ReadBatch {
     std::vector<uint8_t> bases;
     std::vector<uint64_t> offsets { 0 };
     std::vector<std::string> names; // filled only when keep_names
+    // filled only when keep_qual: the quality bytes of the FASTQ records as the file holds them (Phred + 33), one per base, in step with
+    // `bases`; a FASTA record adds none, so qual.size() != bases.size() says that a read came without qualities
+    std::vector<uint8_t> qual;
     uint64_t n_reads() const { return offsets.size() - 1; }
     void clear()
     {
         bases.clear();
         offsets.assign(1, 0);
         names.clear();
+        qual.clear();
     }
 };
 
@@ -25,7 +29,7 @@ public:
     explicit FastxReader(const std::string& path);
     ~FastxReader();
     // append up to max_reads / max_bases to `out` (cleared first); false when the file is exhausted
-    bool next_batch(ReadBatch& out, uint64_t max_reads, uint64_t max_bases, bool keep_names = false);
+    bool next_batch(ReadBatch& out, uint64_t max_reads, uint64_t max_bases, bool keep_names = false, bool keep_qual = false);
 
 private:
     bool fill();

@@ -68,6 +68,13 @@ struct Block {
     uint64_t* seq_start = nullptr; // inside the allocation of `offsets`, as is ...
     uint8_t* reverse = nullptr;    // ... this
     uint64_t seq_bytes = 0, n_non_acgt = 0;
+    uint8_t* qual = nullptr; // IngestHooks::want_qual: one byte per base, indexed in bases whatever the form of `bases`
+    uint32_t qual_bias = 0;
+    // the quality bytes of the read whose first base is base `at` of the block
+    inline void put_qual(uint64_t at, const void* q, size_t len)
+    {
+        if (qual) std::memcpy(qual + at, q, len);
+    }
     // the bases of one read (or one line of a multi-line record) behind what the block holds
     inline void append(const char* seq, size_t len)
     {
@@ -93,6 +100,8 @@ struct Block {
         pb.seq_start = seq_start;
         pb.reverse = reverse;
         pb.seq_bytes = seq_bytes;
+        pb.qual = qual;
+        pb.qual_bias = qual_bias;
         return pb;
     }
 };
@@ -231,6 +240,11 @@ struct Shared {
             b.reverse = reinterpret_cast<uint8_t*>(b.seq_start + BLOCK_READS + 2);
         }
         if (b.packed) reinterpret_cast<uint64_t*>(b.bases)[0] = 0;
+        if (hooks.want_qual) {
+            b.qual = (uint8_t*)(hooks.alloc ? hooks.alloc(BLOCK_BASES + 64) : std::malloc(BLOCK_BASES + 64));
+            if (!b.qual) throw Error(DRPRG_ENOMEM, "cannot allocate an ingest block");
+            b.qual_bias = bam ? 0 : 33;
+        }
         // first hand-over: between 1/16 and 16/16 of a block, a different sixteenth for consecutive workers
         b.flush_at = BLOCK_BASES / 16 * (1 + (size_t)(first_flush.fetch_add(1) % 16));
         return b;
@@ -244,9 +258,16 @@ struct Shared {
         };
         rel(b.bases);
         rel(b.offsets);
+        rel(b.qual);
         b = Block();
     }
 };
+
+// IngestHooks::want_qual and a read that has bases but no qualities
+[[noreturn]] void no_qualities(const char* what)
+{
+    throw Error(DRPRG_EINVAL, std::string("--min-read-qual: ") + what + " has no base qualities; a read is never kept or dropped by a quality threshold it cannot be held against");
+}
 
 inline const char* find_nl(const char* p, const char* e) { return p < e ? (const char*)memchr(p, '\n', (size_t)(e - p)) : nullptr; }
 
@@ -326,7 +347,13 @@ __attribute__((target("avx2"))) const char* parse_fastq_avx2(const char* p, cons
         if (s_stop > seq && s_stop[-1] == '\r') --s_stop;
         const size_t len = (size_t)(s_stop - seq);
         if (len > BLOCK_BASES) return p;
+        if (blk.qual) { // (the quality line's end is known already: its bytes are copied, not looked at)
+            const char* q_stop = q_end;
+            if (q_stop > plus_end + 1 && q_stop[-1] == '\r') --q_stop;
+            if ((size_t)(q_stop - (plus_end + 1)) != len) return p; // the general loop says what is wrong
+        }
         if (blk.n_bases + len > blk.flush_at || blk.n_reads + 1 > BLOCK_READS) sh.submit(blk);
+        blk.put_qual(blk.n_bases, plus_end + 1, len);
         if (blk.packed) pack_append_overread_avx2(reinterpret_cast<uint64_t*>(blk.bases), blk.n_bases, seq, len, blk.npos); // (s_end + 64 < e: readable)
         else blk.append(seq, len);
         blk.offsets[++blk.n_reads] = blk.n_bases;
@@ -364,7 +391,13 @@ void parse_slice(const char* p, const char* e, bool fastq, Block& blk, Shared& s
             strip_cr(cursor, s_stop);
             const size_t len = (size_t)(s_stop - cursor);
             if (len > BLOCK_BASES) throw Error(DRPRG_EOVERFLOW, "a read is longer than the ingest block");
+            if (blk.qual) {
+                const char* q_stop = q_end ? q_end : e;
+                strip_cr(plus_end + 1, q_stop);
+                if ((size_t)(q_stop - (plus_end + 1)) != len) throw Error(DRPRG_EFORMAT, "a FASTQ record's quality line is not as long as its sequence");
+            }
             if (blk.n_bases + len > blk.flush_at || blk.n_reads + 1 > BLOCK_READS) sh.submit(blk);
+            blk.put_qual(blk.n_bases, plus_end + 1, len);
             blk.append(cursor, len);
             blk.offsets[++blk.n_reads] = blk.n_bases;
             p = q_end ? q_end + 1 : e;
@@ -379,6 +412,7 @@ void parse_slice(const char* p, const char* e, bool fastq, Block& blk, Shared& s
             const size_t bound = (size_t)(rec_end - cursor);
             if (bound > BLOCK_BASES) throw Error(DRPRG_EOVERFLOW, "a read is longer than the ingest block");
             if (blk.n_bases + bound > blk.flush_at || blk.n_reads + 1 > BLOCK_READS) sh.submit(blk);
+            const uint64_t before = blk.n_bases;
             while (cursor < rec_end) {
                 const char* nl = find_nl(cursor, rec_end);
                 const char* stop = nl ? nl : rec_end;
@@ -387,6 +421,7 @@ void parse_slice(const char* p, const char* e, bool fastq, Block& blk, Shared& s
                 blk.append(cursor, (size_t)(stop - cursor));
                 cursor = next;
             }
+            if (blk.qual && blk.n_bases != before) no_qualities("a FASTA record");
             blk.offsets[++blk.n_reads] = blk.n_bases;
             p = rec_end;
         }
@@ -418,6 +453,11 @@ void parse_bam_slice(const uint8_t* p, const uint8_t* e, Block& blk, Shared& sh)
         const size_t len = r.l_seq;
         if (len > BLOCK_BASES) throw Error(DRPRG_EOVERFLOW, "a read is longer than the ingest block");
         if (blk.n_bases + len > blk.flush_at || blk.n_reads + 1 > BLOCK_READS) sh.submit(blk);
+        if (blk.qual && len) {
+            const uint8_t* q = r.seq + (len + 1) / 2; // (parse_record has checked that the record holds l_seq bytes behind the sequence)
+            if (q[0] == 0xFF) no_qualities("a BAM record (its QUAL field starts with 0xFF)");
+            blk.put_qual(blk.n_bases, q, len);
+        }
         if (blk.bam) {
             const size_t nb = (len + 1) / 2;
             std::memcpy(blk.bases + blk.seq_bytes, r.seq, nb);

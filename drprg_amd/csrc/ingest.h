@@ -24,6 +24,11 @@ struct PinnedBatch {
     const uint64_t* seq_start = nullptr;
     const uint8_t* reverse = nullptr;
     uint64_t seq_bytes = 0;
+    // IngestHooks::want_qual: the reads' quality bytes as the file holds them, n_bases of them, those of read i from byte offsets[i] on --
+    // indexed in bases in all three forms -- and what to take off a byte to get the Phred quality: 33 (FASTQ text) or 0 (BAM's QUAL field,
+    // in the record's order whatever its flag says)
+    const uint8_t* qual = nullptr;
+    uint32_t qual_bias = 0;
 };
 
 struct IngestHooks {
@@ -41,6 +46,10 @@ struct IngestHooks {
     // A BAM file's reads are handed over in BAM's 4-bit form (PinnedBatch::bam; `packed` does not apply to them).  false: the parser
     // threads convert them to upper-case text, and the hooks see the ASCII (or packed) blocks the FASTQ of the same reads would give.
     bool bam_native = false;
+    // The blocks carry the reads' quality bytes (PinnedBatch::qual): the parser threads copy the quality line or the QUAL field beside the
+    // bases without looking at the bytes.  A read of one base or more that has none -- a FASTA record, a BAM record whose QUAL field starts
+    // with 0xFF -- ends the call with DRPRG_EINVAL.  false: nothing about the ingest changes, no quality byte is parsed, copied or moved.
+    bool want_qual = false;
 };
 
 struct IngestStats {

@@ -385,6 +385,33 @@ hipError_t launch_subsample_npos_count(const SubsampleBlock& b, const uint64_t* 
 hipError_t launch_subsample_npos_emit(const SubsampleBlock& b, const uint64_t* npos, uint64_t n_npos, const uint32_t* chunk_prefix, uint64_t* out, uint64_t out_cap,
     hipStream_t stream);
 
+// read_qual.hip: the read filter (the rule: include/drprg_hip.h "read filter").  qsum[i] = sum of E[quality] over read i's n_bases-indexed
+// bytes of qual (qual: n_bases + 64 bytes readable; bias 33 or 0), then flag[i] = 1 for the reads the rule keeps, rank[i] = kept reads
+// before i and boff[i] = kept bases before i (n_reads + 1 entries each, entry n_reads the totals: what launch_subsample_tables and the
+// compaction kernels of subsample.hip read).  use_qual == false: qual and qsum are not touched.  flag32, klen: n_reads + 1 entries of
+// scratch; work: eight device words; out: eight words the device can write (page-locked host memory, or device memory), indexed by RF_*;
+// temp: read_filter_temp_bytes(n_reads) bytes.  1 <= n_reads <= MAX_BATCH_READS.
+enum { RF_KEPT_READS = 0, RF_KEPT_BASES = 1, RF_SHORT = 2, RF_LONG = 3, RF_LOWQ = 4, RF_BAD_AT = 5 /* first bad quality byte + 1, or 0 */, RF_OFFSETS = 6 /* offsets at odds with n_bases */ };
+struct ReadFilterArgs {
+    const uint8_t* qual;
+    uint32_t bias;
+    const uint64_t* offsets;
+    uint64_t n_reads, n_bases;
+    uint64_t min_len, max_len, T;
+    bool use_qual;
+    unsigned long long* qsum;
+    uint8_t* flag;
+    uint32_t *flag32, *rank;
+    uint64_t *klen, *boff;
+    unsigned long long *work, *out;
+    void* temp;
+    size_t temp_bytes;
+};
+size_t read_filter_temp_bytes(uint64_t n_reads);
+uint32_t read_qual_tiles(uint64_t n_bases);
+// timer: around read_qual_kernel alone
+hipError_t launch_read_filter(const ReadFilterArgs& a, hipStream_t stream, KernelTimer timer = {});
+
 // anchor_scan.hip: reads of a resident batch that hold one of the (sorted) anchor k-mers of length A -- every such read once,
 // in any order, appended to `list` (count keeps counting past list_cap).  prefilter: 2^16 bits, bit (kmer & 0xFFFF) set for every
 // anchor; flags: n_reads words, zero before the launch.

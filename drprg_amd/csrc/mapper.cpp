@@ -1285,6 +1285,18 @@ void Mapper::select_reads_with_anchors(std::vector<uint64_t> anchors, uint32_t A
     }
 }
 
+// over the limit (or the device is full): nothing is kept from here on, and what was kept is of no use without the rest
+void Mapper::stop_keeping()
+{
+    const uint64_t cap = kept_cap_;
+    drop_kept();
+    kept_cap_ = cap;
+    kept_broken_ = true;
+    // (said once per context, always: the run takes a different, slower route from here -- results are the same)
+    std::fprintf(stderr, "[drprg-hip] the sample is larger than the %.1f GB of device memory set aside for resident reads (device %d): reads are "
+                         "not kept, later passes read the file again (DRPRG_HIP_KEEP_READS_GB raises the limit)\n", (double)cap / 1e9, device_);
+}
+
 void Mapper::map_host_async(const HostBatch& hb)
 {
     const uint64_t n_reads = hb.n_reads;
@@ -1328,14 +1340,7 @@ void Mapper::map_host_async(const HostBatch& hb)
             HIPCHK(hipEventSynchronize(kept_copied_)); // the caller's block is free again
             return;
         }
-        // over the limit (or the device is full): nothing is kept from here on, and what was kept is of no use without the rest
-        const uint64_t cap = kept_cap_;
-        drop_kept();
-        kept_cap_ = cap;
-        kept_broken_ = true;
-        // (said once per context, always: the run takes a different, slower route from here -- results are the same)
-        std::fprintf(stderr, "[drprg-hip] the sample is larger than the %.1f GB of device memory set aside for resident reads (device %d): reads are "
-                             "not kept, later passes read the file again (DRPRG_HIP_KEEP_READS_GB raises the limit)\n", (double)cap / 1e9, device_);
+        stop_keeping();
     }
     if (!use_filter_) { // no deferred form of this sequence
         map_host(hb);
@@ -1360,6 +1365,218 @@ void Mapper::map_host_async(const HostBatch& hb)
     HIPCHK(hipStreamWaitEvent(stream_, st.copied, 0));
     map(b, nullptr, nullptr, stream_, true);
     HIPCHK(hipEventSynchronize(st.copied)); // the caller's block is free again; the kernels run on
+}
+
+// ---- the read filter ---------------------------------------------------------------------------------------------------------------
+void Mapper::ensure_filter_scratch(FilterScratch& fs, uint64_t n_reads, uint64_t qual_bytes, bool own_flags, bool own_sums)
+{
+    auto room = [&](auto& buf, uint64_t need) {
+        if (need <= buf.size()) return;
+        sync(); // (as ensure_stage: freeing device memory waits for the device)
+        buf.alloc(need + need / 4);
+    };
+    if (qual_bytes) room(fs.d_qual, qual_bytes + 64);
+    if (own_flags) room(fs.d_flag, n_reads);
+    if (own_sums) room(fs.d_qsum, n_reads);
+    room(fs.d_flag32, n_reads + 1);
+    room(fs.d_rank, n_reads + 1);
+    room(fs.d_klen, n_reads + 1);
+    room(fs.d_boff, n_reads + 1);
+    room(fs.d_temp, dev::read_filter_temp_bytes(n_reads));
+    if (!fs.d_work) fs.d_work.alloc(8);
+    if (!fs.h_out) fs.h_out.alloc(8);
+}
+
+void Mapper::run_read_filter(FilterScratch& fs, const ReadFilter& f, const uint8_t* d_qual, uint32_t bias, const uint64_t* d_offsets, uint64_t n_reads,
+    uint64_t n_bases, unsigned long long* d_sums, uint8_t* d_flags, hipStream_t stream)
+{
+    dev::ReadFilterArgs a {};
+    a.qual = d_qual; a.bias = bias; a.offsets = d_offsets; a.n_reads = n_reads; a.n_bases = n_bases;
+    a.min_len = f.min_len; a.max_len = f.max_len; a.T = f.T; a.use_qual = f.use_qual(); // (a batch of empty reads launches no tile, and its sums are still cleared)
+    a.qsum = d_sums; a.flag = d_flags; a.flag32 = fs.d_flag32.data(); a.rank = fs.d_rank.data(); a.klen = fs.d_klen.data(); a.boff = fs.d_boff.data();
+    a.work = fs.d_work.data(); a.out = fs.h_out.device_ptr(); a.temp = fs.d_temp.data(); a.temp_bytes = fs.d_temp.size();
+    HIPCHK(dev::launch_read_filter(a, stream));
+}
+
+void Mapper::read_filter_device(const ReadFilter& f, const uint8_t* d_qual, uint32_t bias, const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases,
+    unsigned long long* d_sums, uint8_t* d_flags, uint64_t res[8], hipStream_t stream)
+{
+    for (int i = 0; i < 8; ++i) res[i] = 0;
+    if (n_reads == 0) return;
+    HIPCHK(hipSetDevice(device_));
+    if (!stream) stream = stream_;
+    if (!d_offsets || !d_flags || (f.use_qual() && n_bases && !d_qual)) throw Error(DRPRG_EINVAL, "null device pointer");
+    if (n_reads > dev::MAX_BATCH_READS) throw Error(DRPRG_EOVERFLOW, "at most " + std::to_string(dev::MAX_BATCH_READS) + " reads per batch");
+    FilterScratch& fs = filter_api_;
+    ensure_filter_scratch(fs, n_reads, 0, false, f.use_qual() && !d_sums);
+    if (f.use_qual() && !d_sums) d_sums = fs.d_qsum.data();
+    run_read_filter(fs, f, d_qual, bias, d_offsets, n_reads, n_bases, d_sums, d_flags, stream);
+    HIPCHK(hipStreamSynchronize(stream));
+    for (int i = 0; i < 8; ++i) res[i] = fs.h_out[i];
+}
+
+void Mapper::map_host_filtered(const HostBatch& hb, const ReadFilter& f, uint64_t cap_need, FilterOutcome& o)
+{
+    o = FilterOutcome {};
+    const uint64_t n_reads = hb.n_reads;
+    if (n_reads == 0) return;
+    HIPCHK(hipSetDevice(device_));
+    if (hb.offsets[0] != 0) throw Error(DRPRG_EINVAL, "offsets[0] must be 0");
+    const uint64_t n_bases = hb.n_bases();
+    o.reads_seen = n_reads;
+    o.bases_seen = n_bases;
+    bool keeping = kept_cap_ && !kept_broken_;
+    if (n_bases == 0) { // only empty reads: the lower bound decides, there is nothing to copy and nothing to map (the counters still see them)
+        o.dropped_short = f.min_len ? n_reads : 0;
+        o.reads_kept = o.mapped_reads = n_reads - o.dropped_short;
+        tot_reads_ += o.reads_kept;
+        if (keeping) kept_seen_ += o.reads_kept;
+        return;
+    }
+    if (f.use_qual() && !hb.qual) throw Error(DRPRG_EINVAL, "--min-read-qual: the reads came without base qualities");
+    if (n_reads > dev::MAX_BATCH_READS) throw Error(DRPRG_EOVERFLOW, "at most " + std::to_string(dev::MAX_BATCH_READS) + " reads per batch");
+    if (!copy_stream_) copy_stream_.create();
+    const hipStream_t cs = copy_stream_;
+    // (the batch that used this staging set two calls ago was completed by the previous call: map_host_async)
+    Stage& st = stage_[stage_next_];
+    stage_next_ ^= 1;
+    if (!st.copied) st.copied.create(false);
+    FilterScratch& fs = st.filt;
+    const uint64_t n_npos = hb.packed || hb.bam ? hb.n_npos : 0;
+    ensure_stage(st, hb.payload_bytes(), n_reads, n_npos);
+    ensure_filter_scratch(fs, n_reads, f.use_qual() ? n_bases : 0, true, f.use_qual());
+    const DeviceBatch src = hb.bam ? copy_in_bam(hb, st, st.d_bases.data(), st.d_offsets.data(), st.d_npos.data(), cs, cs)
+                                   : copy_in(hb, st.d_bases.data(), st.d_offsets.data(), st.d_npos.data(), cs);
+    if (f.use_qual()) {
+        HIPCHK(hipMemcpyAsync(fs.d_qual.data(), hb.qual, n_bases, hipMemcpyHostToDevice, cs));
+        HIPCHK(hipMemsetAsync(fs.d_qual.data() + n_bases, 0, 64, cs));
+    }
+    run_read_filter(fs, f, fs.d_qual.data(), hb.qual_bias, src.d_offsets, n_reads, n_bases, fs.d_qsum.data(), fs.d_flag.data(), cs);
+    HIPCHK(hipStreamSynchronize(cs)); // the caller's block is free again; the filter's read-back is here
+    const unsigned long long* h = fs.h_out.data();
+    if (h[dev::RF_OFFSETS]) throw Error(DRPRG_EINVAL, "read filter: the block's offsets do not ascend to its number of bases");
+    if (h[dev::RF_BAD_AT])
+        throw Error(DRPRG_EFORMAT, "a base quality outside 0..93 (quality byte " + std::to_string(h[dev::RF_BAD_AT] - 1) + " of an ingest block of "
+                + std::to_string(n_bases) + " bases, " + (hb.qual_bias ? "FASTQ: bytes 33..126" : "BAM: bytes 0..93") + ")");
+    o.dropped_short = h[dev::RF_SHORT];
+    o.dropped_long = h[dev::RF_LONG];
+    o.dropped_lowq = h[dev::RF_LOWQ];
+    o.reads_kept = h[dev::RF_KEPT_READS];
+    o.bases_kept = h[dev::RF_KEPT_BASES];
+    uint64_t take = n_reads, nr = o.reads_kept, nb = o.bases_kept; // the block's first `take` reads hold the nr reads and nb bases that go on
+    if (cap_need && nb >= cap_need) {
+        // the cut, in the block's own numbering: boff is the running total of the kept bases (covg_cut.hip on the scan instead of the offsets)
+        if (!h_cut_) h_cut_.alloc(4);
+        HIPCHK(dev::launch_covg_cut(fs.d_boff.data(), n_reads, cap_need, nullptr, 0, h_cut_.device_ptr(), cs));
+        HIPCHK(hipStreamSynchronize(cs));
+        take = h_cut_[0];
+        nb = h_cut_[1];
+        uint32_t rk = 0;
+        HIPCHK(hipMemcpyAsync(&rk, fs.d_rank.data() + take, sizeof rk, hipMemcpyDeviceToHost, cs));
+        HIPCHK(hipStreamSynchronize(cs));
+        o.cut = true;
+        o.cut_dropped = nr - rk;
+        nr = rk;
+    }
+    o.mapped_reads = nr;
+    o.mapped_bases = nb;
+    if (nb == 0) { // nothing of the block is left, or empty reads only
+        // No map call follows, so nothing completes the batch in flight -- whose kernels read the OTHER staging set.  This set is handed back:
+        // the next block takes it again, and the sets keep their rule (the batch that used a set before was completed by the map call
+        // between).  Were the turn kept, the next block's copies would overwrite what the batch in flight is still reading.
+        stage_next_ ^= 1;
+        tot_reads_ += nr;
+        if (keeping) kept_seen_ += nr;
+        return;
+    }
+    const bool compact = nr != n_reads;
+    const uint64_t payload = src.packed ? (nb + 15) / 16 * 4 : nb;
+    const dev::SubsampleBlock sb { src.d_bases, src.d_offsets, take, src.n_bases, 0, fs.d_flag.data(), fs.d_rank.data(), fs.d_boff.data(), nr, nb };
+    // how many of the block's listed positions go on: all of them, or -- counted before any room is taken for them -- those in kept reads
+    uint64_t n_list = n_npos;
+    if (compact && src.n_npos) {
+        const uint64_t chunks = (uint64_t)dev::subsample_npos_chunks(src.n_npos) + 1;
+        const size_t temp = dev::scan_temp_bytes((uint32_t)chunks);
+        if (chunks > fs.d_count.size()) fs.d_count.alloc(chunks + chunks / 4);
+        if (chunks > fs.d_prefix.size()) fs.d_prefix.alloc(chunks + chunks / 4);
+        if (temp > fs.d_ntemp.size()) fs.d_ntemp.alloc(temp + temp / 4);
+        HIPCHK(dev::launch_subsample_npos_count(sb, src.d_npos, src.n_npos, fs.d_count.data(), fs.d_prefix.data(), fs.d_ntemp.data(), fs.d_ntemp.size(), cs));
+        uint32_t cnt = 0;
+        HIPCHK(hipMemcpyAsync(&cnt, fs.d_prefix.data() + (chunks - 1), sizeof cnt, hipMemcpyDeviceToHost, cs));
+        HIPCHK(hipStreamSynchronize(cs));
+        n_list = cnt;
+    } else if (compact) n_list = 0;
+    uint8_t* db = nullptr;
+    uint64_t *doff = nullptr, *dnp = nullptr;
+    if (keeping) {
+        db = static_cast<uint8_t*>(arena_take(payload + 64));
+        doff = db ? static_cast<uint64_t*>(arena_take((nr + 1) * sizeof(uint64_t))) : nullptr;
+        dnp = doff && n_list ? static_cast<uint64_t*>(arena_take(n_list * sizeof(uint64_t))) : nullptr;
+        if (!db || !doff || (n_list && !dnp)) {
+            stop_keeping();
+            keeping = false;
+        }
+    }
+    DeviceBatch cur = src;
+    if (compact || keeping) {
+        if (!keeping) {
+            if (payload + 64 > fs.c_bases.size() || nr + 1 > fs.c_offsets.size() || n_list > fs.c_npos.size()) sync();
+            fs.c_bases.reserve(payload + 64, payload + payload / 4 + 64);
+            fs.c_offsets.reserve(nr + 1, nr + nr / 4 + 1);
+            fs.c_npos.reserve(n_list, n_list + n_list / 4 + 16);
+            db = fs.c_bases.data();
+            doff = fs.c_offsets.data();
+            dnp = fs.c_npos.data();
+        }
+        cur.d_bases = db;
+        cur.d_offsets = doff;
+        cur.n_reads = nr;
+        cur.n_bases = nb;
+        HIPCHK(hipMemsetAsync(db + payload, 0, 64, cs));
+        if (!compact) { // the whole block, copied on the device to where it stays
+            HIPCHK(hipMemcpyAsync(db, src.d_bases, payload, hipMemcpyDeviceToDevice, cs));
+            HIPCHK(hipMemcpyAsync(doff, src.d_offsets, (nr + 1) * sizeof(uint64_t), hipMemcpyDeviceToDevice, cs));
+            if (src.n_npos) HIPCHK(hipMemcpyAsync(dnp, src.d_npos, src.n_npos * sizeof(uint64_t), hipMemcpyDeviceToDevice, cs));
+            cur.d_npos = src.n_npos ? dnp : nullptr;
+            HIPCHK(hipStreamSynchronize(cs)); // (the block is whole before anything on the mapping stream reads it)
+        } else {
+            uint32_t* const d_err = reinterpret_cast<uint32_t*>(fs.d_work.data() + 7); // (zeroed with the filter's words)
+            cur.d_npos = nullptr;
+            cur.n_npos = 0;
+            if (src.packed) {
+                if (nr > fs.d_src.size()) fs.d_src.alloc(nr + nr / 4);
+                HIPCHK(dev::launch_subsample_tables(sb, doff, fs.d_src.data(), nullptr, d_err, cs));
+                HIPCHK(dev::launch_subsample_pack(sb, doff, fs.d_src.data(), reinterpret_cast<uint32_t*>(db), d_err, cs));
+                if (n_list) { // (counted above; the scan of the counts is still in d_prefix)
+                    HIPCHK(dev::launch_subsample_npos_emit(sb, src.d_npos, src.n_npos, fs.d_prefix.data(), dnp, n_list, cs));
+                    cur.d_npos = dnp;
+                    cur.n_npos = n_list;
+                }
+            } else {
+                if (nr > fs.d_table.size()) fs.d_table.alloc(nr + nr / 4);
+                HIPCHK(hipMemsetAsync(fs.d_table.data(), 0, nr * sizeof(dev::GatherEntry), cs)); // (an entry the kernel refuses to fill copies nothing)
+                HIPCHK(dev::launch_subsample_tables(sb, doff, nullptr, fs.d_table.data(), d_err, cs));
+                HIPCHK(dev::launch_gather_reads(fs.d_table.data(), (uint32_t)nr, db, cs));
+            }
+            uint32_t err = 0;
+            HIPCHK(hipMemcpyAsync(&err, d_err, sizeof err, hipMemcpyDeviceToHost, cs));
+            HIPCHK(hipStreamSynchronize(cs));
+            if (err) throw Error(DRPRG_EIO, "read filter: the block's offsets and the filter's scans do not fit each other");
+        }
+    }
+    if (keeping) {
+        kept_.push_back(cur);
+        kept_first_.push_back(kept_seen_);
+        kept_seen_ += nr;
+    }
+    in_keep_call_ = keeping;
+    try {
+        map(cur, nullptr, nullptr, stream_, true);
+    } catch (...) {
+        in_keep_call_ = false;
+        throw;
+    }
+    in_keep_call_ = false;
 }
 
 void Mapper::add_vectors_from(Mapper& other)

@@ -89,6 +89,10 @@ public:
         const uint64_t* seq_start = nullptr;
         const uint8_t* reverse = nullptr;
         uint64_t seq_bytes = 0;
+        // the reads' quality bytes (ingest.h PinnedBatch::qual: n_bases() of them, indexed in bases in every form) and what to take off a
+        // byte to get the Phred quality; looked at by map_host_filtered only, and only under a quality threshold
+        const uint8_t* qual = nullptr;
+        uint32_t qual_bias = 0;
         uint64_t n_bases() const { return offsets[n_reads]; }
         // what the batch takes on the device once it is there (a BAM batch: converted to the packed form)
         uint64_t payload_bytes() const { return packed || bam ? ((n_bases() + 15) / 16) * 4 : n_bases(); }
@@ -101,6 +105,32 @@ public:
     // may be reused then -- so that the next block's copy overlaps this block's kernels.  sync() (or anything that reads
     // results) completes what is in flight.  Sequences without a deferred form fall back to map_host.
     void map_host_async(const HostBatch& b);
+    // The read filter (the rule: include/drprg_hip.h "read filter"; read_qual.hip).  T: the rule's threshold for min_qual_milli
+    // (dev::rq_threshold), 0 when there is no quality test.
+    struct ReadFilter {
+        uint64_t min_len = 0, max_len = 0, T = 0;
+        uint32_t min_qual_milli = 0;
+        bool any() const { return min_len || max_len || min_qual_milli; }
+        bool use_qual() const { return min_qual_milli != 0; }
+    };
+    struct FilterOutcome {
+        uint64_t reads_seen = 0, bases_seen = 0, dropped_short = 0, dropped_long = 0, dropped_lowq = 0, reads_kept = 0, bases_kept = 0;
+        uint64_t mapped_reads = 0, mapped_bases = 0; // what was mapped: the kept reads, or those of them in front of the depth cap
+        uint64_t cut_dropped = 0;                    // kept reads behind the depth cap
+        bool cut = false;
+    };
+    // map_host_async behind the filter: the block is copied into a staging set -- its quality bytes too, under a quality threshold --, the
+    // filter runs on the copy stream, the call waits for its 64-byte read-back (the caller's block is free then) and what is left of the
+    // block is mapped as map_host_async maps a block: a block that lost no read as it lies in the staging set, any other compacted by the
+    // kernels of subsample.hip; under keep_reads the block that stays is the compacted one, carved from the arena at its own size (a block
+    // that lost nothing is copied there on the device).  Quality bytes never stay.  cap_need != 0: the depth cap is reached at the
+    // cap_need-th kept base of this block (counted from 1): the kept reads up to the one that holds it are mapped, as cap_host_cut cuts a block.
+    void map_host_filtered(const HostBatch& b, const ReadFilter& f, uint64_t cap_need, FilterOutcome& out);
+    // The filter alone on the caller's device buffers (drprg_hip_read_filter_device): d_sums (may be null) receives the sums of E, d_flags
+    // one byte per read; res[0..7]: dev::RF_*.  d_qual must be readable for 64 bytes behind n_bases when it is 16-byte aligned (any other
+    // address is read byte by byte).  Synchronises `stream`.
+    void read_filter_device(const ReadFilter& f, const uint8_t* d_qual, uint32_t bias, const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases,
+        unsigned long long* d_sums, uint8_t* d_flags, uint64_t res[8], hipStream_t stream);
     // Reads that stay in HBM (off by default).  keep_reads(max_bytes > 0): from now on map_host_async copies every block into
     // device memory of its own instead of a staging set and leaves it there -- at most max_bytes of it; one byte more and
     // everything kept is dropped and the staging sets are back.  kept_complete(): every read mapped since keep_reads() /
@@ -328,7 +358,24 @@ private:
         DeviceBuffer<uint32_t> d_count, d_prefix;
         DeviceBuffer<unsigned char> d_temp;
     };
+    // what the read filter of one block needs beside the block: the quality bytes, the per-read words of read_qual.hip, and -- for a block
+    // that loses reads and is not kept -- the compacted block with the tables the kernels of subsample.hip make it from
+    struct FilterScratch {
+        DeviceBuffer<uint8_t> d_qual, d_flag;
+        DeviceBuffer<unsigned long long> d_qsum, d_work;
+        DeviceBuffer<uint32_t> d_flag32, d_rank;
+        DeviceBuffer<uint64_t> d_klen, d_boff;
+        DeviceBuffer<unsigned char> d_temp;
+        PinnedBuffer<unsigned long long> h_out;
+        DeviceBuffer<uint64_t> d_src;
+        DeviceBuffer<dev::GatherEntry> d_table;
+        DeviceBuffer<uint32_t> d_count, d_prefix;
+        DeviceBuffer<unsigned char> d_ntemp;
+        DeviceBuffer<uint8_t> c_bases;
+        DeviceBuffer<uint64_t> c_offsets, c_npos;
+    };
     struct Stage {
+        FilterScratch filt;
         DeviceBuffer<uint8_t> d_bases;
         DeviceBuffer<uint64_t> d_offsets, d_npos;
         Event copied;
@@ -341,6 +388,12 @@ private:
     // The copies of a BAM batch into st's raw buffers on copy_stream and, behind them on `stream`, its conversion into the packed batch
     // at these addresses, which is returned.  st.copied is recorded behind the copies when the two streams differ.
     DeviceBatch copy_in_bam(const HostBatch& hb, Stage& st, uint8_t* d_words, uint64_t* d_offsets, uint64_t* d_npos, hipStream_t copy_stream, hipStream_t stream);
+    // room for the filter of n_reads reads (qual_bytes: 0 without a quality threshold); own_flags / own_sums: the caller has none
+    void ensure_filter_scratch(FilterScratch& fs, uint64_t n_reads, uint64_t qual_bytes, bool own_flags, bool own_sums);
+    // queues the filter on `stream`; fs.h_out holds dev::RF_* once the stream has been waited for
+    void run_read_filter(FilterScratch& fs, const ReadFilter& f, const uint8_t* d_qual, uint32_t bias, const uint64_t* d_offsets, uint64_t n_reads,
+        uint64_t n_bases, unsigned long long* d_sums, uint8_t* d_flags, hipStream_t stream);
+    FilterScratch filter_api_; // read_filter_device's own (as bam_api_)
     BamScratch bam_api_; // pack_bam_on_device's own (the caller's stream is not ordered with the context's)
     uint64_t bam_blocks_ = 0;
     // room in `st` for a batch of these sizes (n_npos: 0 for an ASCII batch)
@@ -367,6 +420,7 @@ private:
     bool kept_broken_ = false, in_keep_call_ = false;
     Event kept_copied_;
     void* arena_take(size_t bytes);
+    void stop_keeping(); // the resident set given up (over its limit, or the device is full): what map_host_async and map_host_filtered do alike
     DeviceBuffer<uint32_t> d_peer_tmp_; // add_vectors_from: the other device's vectors on this device
     // timing
     bool timing_ = false;

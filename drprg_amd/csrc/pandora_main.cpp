@@ -6,6 +6,7 @@
 //   pandora map      --genotype --local --gt-conf 0 -v -o <out> -g G --max-covg M --vcf-refs <genes.fa>
 //                    -t T -w W -k K -c C [-I] [-K] <prg> <reads>
 // and, this build's own, --subsample-covg D [--seed S] on map and discover (include/drprg_hip.h "random subsample"),
+// --min-read-len L, --max-read-len L and --min-read-qual Q on both (include/drprg_hip.h "read filter"),
 // and writes the files drprg then looks for: <prg>.k<K>.w<W>.idx + kmer_prgs/ (index),
 // <dir>/denovo_paths.txt (discover, /root/reference/src/lib.rs:569-577),
 // <out>/pandora_genotyped.vcf (map, /root/reference/src/lib.rs:644-646).
@@ -47,6 +48,9 @@ struct Args {
     bool subsample = false, seed_given = false;
     double subsample_covg = 0;
     uint64_t seed = 1;
+    // --min-read-len L, --max-read-len L, --min-read-qual Q: the read filter (include/drprg_hip.h "read filter"); 0 = not set
+    uint64_t min_read_len = 0, max_read_len = 0;
+    uint32_t min_read_qual_milli = 0;
     std::string outdir = "pandora", vcf_refs;
     std::vector<std::string> positional;
     int device = 0;
@@ -64,6 +68,7 @@ void usage()
         "pandora-compatible front end of the MI355X drprg hot path\n"
         "  pandora index    [-t N] [-w W] [-k K] <prg>\n"
         "  pandora map      [--genotype] [--local] [--gt-conf X] [-v] [-o DIR] [-g SIZE] [--max-covg N | --subsample-covg D [--seed S]]\n"
+        "                   [--min-read-len L] [--max-read-len L] [--min-read-qual Q]\n"
         "                   [--vcf-refs FASTA] [-t N] [-w W] [-k K] [-c N] [-I] [-K] [-e RATE] [--max-diff N] <prg> <reads>\n"
         "  pandora discover [same mapping options] <prg> <query.tsv>\n"
         "  --max-covg N: reads are taken in file order up to and including the first one at which (N + 1) x SIZE bases are reached;\n"
@@ -75,8 +80,12 @@ void usage()
         "                including the one that reaches the target; the kept reads are mapped afresh.  The default --max-covg gives way\n"
         "                to it; an explicit --max-covg other than 4294967295 beside it is an error.  Needs the whole sample resident\n"
         "                (DRPRG_HIP_KEEP_READS_GB, default 32): the run fails if it is not.\n"
+        "  --min-read-len L, --max-read-len L, --min-read-qual Q: reads shorter than L, longer than L or of a mean quality below Q (a decimal\n"
+        "                Phred value; the mean is that of the error probabilities, as nanoq and chopper take it) are dropped on the device\n"
+        "                before anything else sees them: the run is that of a file of the kept reads.  --min-read-qual needs qualities:\n"
+        "                FASTA, or a BAM record without them, is an error under it.\n"
         "  <reads>: FASTA or FASTQ, plain or gzip; or BAM (secondary and supplementary records are skipped, reverse-strand records are\n"
-        "           reverse-complemented, qualities and alignments are ignored)\n"
+        "           reverse-complemented, alignments are ignored, qualities are looked at by --min-read-qual alone)\n"
         "environment: DRPRG_HIP_DEVICE selects the GPU (default 0); DRPRG_HIP_DEVICES=0,1,.. maps on several GPUs of the node\n");
 }
 
@@ -111,6 +120,18 @@ Args parse(int argc, char** argv)
         } else if (s == "--seed") {
             a.seed = std::strtoull(need(i), nullptr, 10);
             a.seed_given = true;
+        } else if (s == "--min-read-len" || s == "--max-read-len") {
+            char* end = nullptr;
+            const char* v = need(i);
+            const uint64_t n = std::strtoull(v, &end, 10);
+            if (end == v || *end || *v == '-') die(s + " needs a number of bases, not " + v, 2);
+            (s == "--min-read-len" ? a.min_read_len : a.max_read_len) = n;
+        } else if (s == "--min-read-qual") {
+            char* end = nullptr;
+            const char* v = need(i);
+            const double q = std::strtod(v, &end);
+            if (end == v || *end || !(q >= 0) || q > 93) die(std::string("--min-read-qual needs a mean quality between 0 and 93, not ") + v, 2);
+            a.min_read_qual_milli = (uint32_t)(q * 1000.0 + 0.5);
         }
         else if (s == "-o" || s == "--outdir") a.outdir = need(i);
         else if (s == "--vcf-refs") a.vcf_refs = need(i);
@@ -134,6 +155,7 @@ Args parse(int argc, char** argv)
     if (a.subsample && a.max_covg_given && a.max_covg != 4294967295ull)
         die("--max-covg and --subsample-covg are alternatives (the prefix cap or the random subsample): give one of them", 2);
     if (a.subsample) a.max_covg = 4294967295ull; // the default cap gives way
+    if (a.max_read_len && a.max_read_len < a.min_read_len) die("--max-read-len is below --min-read-len: no read can pass", 2);
     if (const char* d = std::getenv("DRPRG_HIP_DEVICE")) a.device = std::atoi(d);
     return a;
 }
@@ -178,6 +200,7 @@ drprg_hip_ctx* open_ctx(const Args& a)
     o.genome_size = a.genome_size;
     if (int rc = drprg_hip_set_opts(ctx, &o)) die(drprg_hip_last_error(ctx), -rc);
     if (int rc = drprg_hip_set_max_covg(ctx, a.max_covg)) die(drprg_hip_last_error(ctx), -rc);
+    if (int rc = drprg_hip_set_read_filter(ctx, a.min_read_len, a.max_read_len, a.min_read_qual_milli)) die(drprg_hip_last_error(ctx), -rc);
     drprg_hip_set_threads(ctx, a.threads);
     drprg_hip_set_input_format(ctx, packed_input()); // the parser threads pack the reads to 2 bits (DRPRG_HIP_INPUT=ascii: one byte per base)
     return ctx;
@@ -218,7 +241,10 @@ std::string run_tag(const Args& a, const std::string& reads)
     return stamp(a.positional[0]) + "|" + stamp(reads) + "|w" + std::to_string(a.w) + "|k" + std::to_string(a.k) + "|c"
         + std::to_string(a.min_cluster_size) + "|I" + std::to_string((int)a.illumina) + "|e" + std::to_string(a.error_rate) + "|m"
         + std::to_string(a.max_diff) + "|g" + std::to_string((unsigned long long)a.genome_size) + "|M" + std::to_string((unsigned long long)a.max_covg)
-        + (a.subsample ? "|S" + std::to_string(a.subsample_covg) + "/" + std::to_string((unsigned long long)a.seed) : std::string());
+        + (a.subsample ? "|S" + std::to_string(a.subsample_covg) + "/" + std::to_string((unsigned long long)a.seed) : std::string())
+        + (a.min_read_len || a.max_read_len || a.min_read_qual_milli ? "|F" + std::to_string((unsigned long long)a.min_read_len) + "/"
+                  + std::to_string((unsigned long long)a.max_read_len) + "/" + std::to_string(a.min_read_qual_milli)
+                                                                     : std::string());
 }
 
 // The reads stay in HBM after the mapping pass: up to DRPRG_HIP_KEEP_READS_GB per device, default 32, 0 = off.  --subsample-covg works on
@@ -265,6 +291,16 @@ void report_bam(drprg_hip_ctx* ctx, const Args& a)
         (unsigned long long)bi[0], (unsigned long long)bi[1], (unsigned long long)bi[2], (unsigned long long)bi[3]);
 }
 
+// -v: what the read filter dropped
+void report_filter(drprg_hip_ctx* ctx, const Args& a)
+{
+    uint64_t fi[8] = {};
+    if (!a.verbose || !(a.min_read_len || a.max_read_len || a.min_read_qual_milli) || drprg_hip_read_filter_info(ctx, fi) != 0) return;
+    std::printf("[pandora-hip] read filter: reads_seen=%llu bases_seen=%llu dropped_short=%llu dropped_long=%llu dropped_low_qual=%llu reads_kept=%llu "
+                "bases_kept=%llu (T=%llu)\n", (unsigned long long)fi[0], (unsigned long long)fi[1], (unsigned long long)fi[2], (unsigned long long)fi[3],
+        (unsigned long long)fi[4], (unsigned long long)fi[5], (unsigned long long)fi[6], (unsigned long long)fi[7]);
+}
+
 const char* COVERAGE_CACHE = ".drprg_hip_coverage";
 
 int cmd_map(const Args& a)
@@ -287,6 +323,7 @@ int cmd_map(const Args& a)
         report_counters(ctx, now_s() - t0);
         report_cap(ctx, a);
         report_bam(ctx, a);
+        report_filter(ctx, a);
     }
     const std::string vcf = a.outdir + "/pandora_genotyped.vcf";
     if (int rc = drprg_hip_genotype(ctx, a.vcf_refs.empty() ? nullptr : a.vcf_refs.c_str(), vcf.c_str(), "sample"))
@@ -318,6 +355,7 @@ int cmd_discover(const Args& a)
     report_counters(ctx, now_s() - t0);
     report_cap(ctx, a);
     report_bam(ctx, a);
+    report_filter(ctx, a);
     // The mapping half of discover is the same kernels as `map`; its products are (1) the candidate regions -- stretches of each
     // locus' called consensus that the reads do not support --, (2) the novel variants a host-side pile-up of
     // the reads finds in them, and (3) the coverage vector, kept for the `map` call drprg issues next on the unchanged PRG.

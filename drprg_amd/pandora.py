@@ -212,6 +212,33 @@ class Context:
         _check(lib.drprg_hip_subsample_flags(self._h, _ptr(flags), flags.size), self._h)
         return flags
 
+    # ---- read filter (include/drprg_hip.h: drprg_hip_set_read_filter) ---------------------------
+    @staticmethod
+    def qual_milli(min_qual):
+        """a decimal mean quality (number or text, as --min-read-qual takes it) as thousandths"""
+        from decimal import Decimal
+        return int((Decimal(str(min_qual)) * 1000).to_integral_value()) if min_qual else 0
+
+    def set_read_filter(self, min_len=0, max_len=0, min_qual=0):
+        """from the next map_fastx on, reads shorter than min_len, longer than max_len (0: no bound) or of a mean quality below min_qual
+        (a decimal Phred value, 0: no test) are dropped on the device before anything else sees them; all zero clears the filter"""
+        _check(lib.drprg_hip_set_read_filter(self._h, int(min_len), int(max_len), self.qual_milli(min_qual)), self._h)
+
+    def read_filter_info(self):
+        out = (C.c_uint64 * 8)()
+        _check(lib.drprg_hip_read_filter_info(self._h, out), self._h)
+        names = ("reads_seen", "bases_seen", "dropped_short", "dropped_long", "dropped_low_qual", "reads_kept", "bases_kept", "T")
+        return dict(zip(names, (int(x) for x in out)))
+
+    def read_filter_device(self, d_qual, qual_bias, d_offsets, n_reads, n_bases, d_sums, d_flags, stream=None):
+        """the filter alone on device buffers (addresses as integers; d_qual / d_sums may be None): returns (kept reads, kept bases, position
+        + 1 of the first quality byte out of range or 0) -- and raises with code -84 when there is such a byte"""
+        out = (C.c_uint64 * 4)()
+        rc = lib.drprg_hip_read_filter_device(self._h, d_qual, int(qual_bias), d_offsets, int(n_reads), int(n_bases), d_sums, d_flags, out, stream)
+        self.last_filter_out = tuple(int(x) for x in out)
+        _check(rc, self._h)
+        return self.last_filter_out[:3]
+
     def select_reads(self, anchors, A, window_bytes=0):
         """the resident reads in which one of `anchors` (k-mers of A bases as integers, 2 bits per base, A 0 C 1 G 2 T 3, first base high)
         starts -- the selection discover_reads runs on the device (drprg_hip_select_reads); returns (bases u8, offsets u64, ids u64 =

@@ -321,6 +321,45 @@ int drprg_hip_subsample(drprg_hip_ctx* ctx, uint64_t target_bases, uint64_t seed
  * block, and every block under a depth cap, is in order anyway.  The executables switch it on when --subsample-covg is given. */
 int drprg_hip_set_ordered_ingest(drprg_hip_ctx* ctx, int on);
 int drprg_hip_subsample_flags(drprg_hip_ctx* ctx, uint8_t* flags, uint64_t n);
+/* ---- Read filter: reads dropped by length and mean quality on the device, as they arrive.  THIS BUILD'S OWN RULE, stated from memory of
+ * what the filters nanopore workflows run in front of drprg compute (nanoq, chopper -q Q -l L, filtlong); neither pandora nor drprg has one.
+ *   Settings, per context: min_len (0: no lower bound), max_len (0: no upper bound), min_qual_milli = Q * 1000 (0: no quality test).
+ *   A read of L bases with Phred qualities q_0 .. q_{L-1}:
+ *     1. Length.  Dropped as SHORT if L < min_len; otherwise dropped as LONG if max_len != 0 and L > max_len.
+ *     2. Quality, only if min_qual_milli != 0 and only for a read that passed 1.  E[q] = round(2^31 * 10^(-q / 10)) for q = 0 .. 93, a
+ *        literal table of 94 32-bit values (csrc/read_qual_piece.h; E[0] = 2^31, E[93] = 1).  S = sum of E[q_j] in 64 bits (L <= 2^23 keeps
+ *        it at or below 2^54).  The read is kept iff S <= L * T, where T = E[Q] when min_qual_milli is a multiple of 1000 and otherwise
+ *        T = floor(2^31 * 10^(-min_qual_milli / 10000) + 0.5) computed in double.  That is "mean error probability <= 10^(-Q / 10)", the
+ *        mean quality those tools mean, in integer arithmetic: the result does not depend on the order of the sum.  A read of no bases
+ *        passes (0 <= 0); the length test decides its fate.
+ *     3. Kept reads stay in file order.
+ *   Where a base's quality comes from: a FASTQ byte minus 33 (a byte below 33 or above 126 fails the call with -84); a BAM record's QUAL
+ *   byte as it is (bytes 94 .. 254 fail the call with -84), not reversed for flag 0x10 -- the sum does not care.  Under a quality
+ *   threshold a read of one base or more WITHOUT qualities -- a FASTA record, a BAM QUAL field whose first byte is 0xFF -- fails the call
+ *   with -EINVAL (the text names --min-read-qual): such a read is never silently kept or dropped.  Without a threshold no quality byte is
+ *   parsed, copied or moved, whatever the input.
+ *   The filter runs in drprg_hip_map_fastx, per ingest block, on the device that takes the block, before anything else sees the block:
+ *   mapping, drprg_hip_counters' reads / bases and the genotyper's total, the depth cap's running total, the resident set and
+ *   drprg_hip_resident_info, drprg_hip_select_reads and discover from HBM, drprg_hip_map_resident, and the numbering of
+ *   drprg_hip_subsample / drprg_hip_subsample_flags all see the kept reads alone, exactly as if the file had held only them (the pipeline
+ *   chopper | rasusa | drprg).  drprg_hip_map_host* and drprg_hip_map_device* carry no qualities: while any setting is non-zero they
+ *   return -EINVAL rather than map unfiltered reads without saying so.  drprg_hip_map_resident maps what `from` keeps, which is filtered.
+ *   drprg_hip_discover_reads takes its reads from HBM, where only the kept ones are; when the filter dropped reads and the sample is not
+ *   resident it returns -ENODATA (-61) rather than pile up the file's unfiltered reads.
+ *   drprg_hip_set_read_filter: applies from the next drprg_hip_map_fastx; a reset keeps the settings.  -EINVAL for max_len != 0 &&
+ *     max_len < min_len and for min_qual_milli > 93000.
+ *   drprg_hip_read_filter_info: since the last reset, out[0..6] = reads seen, bases seen, dropped short, dropped long, dropped for their
+ *     quality, reads kept, bases kept; out[7] = T.
+ *   drprg_hip_read_filter_device: the filter alone on caller-owned device buffers, under the stream rule of the other device entries
+ *     (NULL: the context's own stream; the call returns when the work is done).  d_qual: n_bases quality bytes, read i's from byte
+ *     d_offsets[i] on (u64[n_reads + 1], [0] = 0); when d_qual is 16-byte aligned the 64 bytes behind n_bases must be readable; may be NULL
+ *     when no quality threshold is set.  qual_bias: 33 or 0.  d_sums (u64[n_reads], may be NULL) receives S, d_flags (u8[n_reads]) 1 for a
+ *     kept read.  out[0..3] = kept reads, kept bases, position + 1 of the first quality byte out of range (0: none; the call returns -84),
+ *     reserved. */
+int drprg_hip_set_read_filter(drprg_hip_ctx* ctx, uint64_t min_len, uint64_t max_len, uint32_t min_qual_milli);
+int drprg_hip_read_filter_info(drprg_hip_ctx* ctx, uint64_t out[8]);
+int drprg_hip_read_filter_device(drprg_hip_ctx* ctx, const void* d_qual, uint32_t qual_bias, const void* d_offsets, uint64_t n_reads, uint64_t n_bases,
+    void* d_sums, void* d_flags, uint64_t out[4], void* hip_stream);
 /* The read selection drprg_hip_discover_reads uses when the reads are resident, on its own: for every device of the context, in order,
  * every kept read in which a k-mer of `anchors` STARTS (anchors: n_anchors k-mers of A bases, 2 bits per base, A 0 C 1 G 2 T 3, first base
  * in the high bits; any order, duplicates allowed).  A block's reads are one base stream: read r of a block is returned iff for some p with
