@@ -96,6 +96,9 @@ SIGNATURES = {
     "drprg_hip_subsample": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]),
     "drprg_hip_set_ordered_ingest": (C.c_int, [C.c_void_p, C.c_int]),
     "drprg_hip_subsample_flags": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "drprg_hip_dedup": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]),
+    "drprg_hip_dedup_flags": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "drprg_hip_dedup_keys_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "drprg_hip_set_read_filter": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32]),
     "drprg_hip_read_filter_info": (C.c_int, [C.c_void_p, C.c_void_p]),
     "drprg_hip_read_filter_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,

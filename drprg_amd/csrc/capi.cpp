@@ -126,6 +126,10 @@ struct drprg_hip_ctx {
     bool subsampled = false;
     uint64_t subsample_n = 0;
     std::vector<uint8_t> subsample_flags;
+    // the last drprg_hip_dedup, in the same form
+    bool deduped = false;
+    uint64_t dedup_n = 0;
+    std::vector<uint8_t> dedup_flags;
     // drprg_hip_set_read_filter: the settings (a reset keeps them) and what the filter has counted since the last reset -- added to by the
     // submitters of drprg_hip_map_fastx, one per device, under filter_mu
     Mapper::ReadFilter read_filter;
@@ -1031,6 +1035,9 @@ int drprg_hip_reset(drprg_hip_ctx* ctx)
     ctx->subsampled = false;
     ctx->subsample_n = 0;
     ctx->subsample_flags.clear();
+    ctx->deduped = false;
+    ctx->dedup_n = 0;
+    ctx->dedup_flags.clear();
     ctx->filter_counts = Mapper::FilterOutcome(); // (the settings stay, as the depth cap does)
     API_END(ctx)
 }
@@ -1140,6 +1147,55 @@ int drprg_hip_subsample_flags(drprg_hip_ctx* ctx, uint8_t* flags, uint64_t n)
     if (n && !flags) throw Error(DRPRG_EINVAL, "null output");
     if (ctx->subsample_flags.empty()) std::memset(flags, 1, n);
     else std::memcpy(flags, ctx->subsample_flags.data(), n);
+    API_END(ctx)
+}
+
+int drprg_hip_dedup(drprg_hip_ctx* ctx, uint32_t key_bits, uint64_t out[4])
+{
+    API_BEGIN(ctx)
+    if (!out) throw Error(DRPRG_EINVAL, "null output");
+    Mapper& m = need_mapper(ctx);
+    if (key_bits < 1 || key_bits > 64) throw Error(DRPRG_EINVAL, "drprg_hip_dedup: key_bits must be 1..64");
+    if (!ctx->extra.empty()) throw Error(DRPRG_EINVAL, "drprg_hip_dedup: a context over several devices is not served");
+    if (ctx->fastx_unordered && m.kept_complete()) // (a sample that is not resident is refused for that, below)
+        throw Error(DRPRG_EINVAL, "drprg_hip_dedup: drprg_hip_map_fastx handed this sample's blocks over in no particular order, so its reads have no "
+                                  "file-order numbers (drprg_hip_set_ordered_ingest(ctx, 1) before the file is mapped)");
+    std::vector<uint8_t> flags;
+    const Mapper::SubsampleResult r = m.dedup_kept(key_bits, flags);
+    out[0] = r.reads_before;
+    out[1] = r.bases_before;
+    out[2] = r.reads_kept;
+    out[3] = r.bases_kept;
+    ctx->deduped = true;
+    ctx->dedup_n = r.reads_before;
+    ctx->dedup_flags = std::move(flags);
+    if (r.reads_kept != r.reads_before) { // the context now stands for the kept reads alone
+        ctx->host_coverage_valid = false;
+        ctx->total_bases = r.bases_kept;
+        ctx->accepted_reads = r.reads_kept;
+    }
+    API_END(ctx)
+}
+
+int drprg_hip_dedup_flags(drprg_hip_ctx* ctx, uint8_t* flags, uint64_t n)
+{
+    API_BEGIN(ctx)
+    if (!ctx->deduped) throw Error(DRPRG_EINVAL, "drprg_hip_dedup_flags: no drprg_hip_dedup call since the last reset");
+    if (n != ctx->dedup_n) throw Error(DRPRG_EINVAL, "drprg_hip_dedup_flags: the sample held " + std::to_string(ctx->dedup_n) + " reads, not " + std::to_string(n));
+    if (n && !flags) throw Error(DRPRG_EINVAL, "null output");
+    if (n == 0) return DRPRG_OK;
+    if (ctx->dedup_flags.empty()) std::memset(flags, 1, n);
+    else std::memcpy(flags, ctx->dedup_flags.data(), n);
+    API_END(ctx)
+}
+
+int drprg_hip_dedup_keys_device(drprg_hip_ctx* ctx, const void* d_words, const void* d_offsets, uint64_t n_reads, uint64_t n_bases, const void* d_npos, uint64_t n_npos,
+    void* d_keys, void* hip_stream)
+{
+    API_BEGIN(ctx)
+    Mapper& m = need_mapper(ctx);
+    m.dedup_keys_device((const uint32_t*)d_words, (const uint64_t*)d_offsets, n_reads, n_bases, (const uint64_t*)d_npos, n_npos, (unsigned long long*)d_keys,
+        (hipStream_t)hip_stream);
     API_END(ctx)
 }
 

@@ -108,13 +108,16 @@ void usage()
         "drprg predict -x <index dir | species[@version]> -i <reads.fq[.gz] | reads.bam> [-o DIR] [-s SAMPLE] [-I] [-S]\n"
         "              [-f MAF] [-d MIN_COVG] [-D MAX_COVG] [-b MIN_STRAND_BIAS] [-g MIN_GT_CONF] [-L MAX_INDEL] [-K MIN_FRS]\n"
         "              [-C MIN_CLUSTER_SIZE] [--debug] [-v] [-t THREADS] [--rebuild-index] [--subsample-covg D [--seed S]]\n"
-        "              [--min-read-len L] [--max-read-len L] [--min-read-qual Q]\n"
+        "              [--dedup] [--min-read-len L] [--max-read-len L] [--min-read-qual Q]\n"
         "--min-read-len L, --max-read-len L, --min-read-qual Q: reads shorter than L, longer than L or of a mean quality below Q (a decimal\n"
         "              Phred value; the mean of the error probabilities, as nanoq and chopper take it) are dropped on the device before\n"
         "              anything else sees them; --min-read-qual needs qualities (FASTQ, or BAM records that hold them).\n"
         "--subsample-covg D: the sample is cut at random to D x 4411532 bases on the device before discover and genotyping (reads in the\n"
         "              order of a 64-bit key made from the seed, default 1, and the read's number, up to and including the one that reaches\n"
         "              the target); needs the sample resident in device memory (DRPRG_HIP_KEEP_READS_GB, default 32), fails if it is not.\n"
+        "--dedup: every read that is identical to a read before it in the file (same length, same bases case-insensitively, non-ACGT bases\n"
+        "              at the same places; forward strand only) is dropped on the device, in front of --subsample-covg, discover and\n"
+        "              genotyping; needs the sample resident in device memory (DRPRG_HIP_KEEP_READS_GB, default 32), fails if it is not.\n"
         "MI355X-native hot path; -p/-m/-M (external tools) are accepted and not needed: novel variants update the PRG in process.\n");
 }
 
@@ -151,7 +154,7 @@ int main(int argc, char** argv)
     std::string index, input, outdir = ".", sample;
     bool illumina = false, verbose = false, maf_given = false, rebuild_index = false;
     int threads = 1;
-    bool subsample = false, seed_given = false;
+    bool subsample = false, seed_given = false, dedup = false;
     double subsample_covg = 0;
     uint64_t seed = 1;
     uint64_t min_read_len = 0, max_read_len = 0; // the read filter (include/drprg_hip.h "read filter"); 0 = not set
@@ -200,6 +203,7 @@ int main(int argc, char** argv)
         else if (a == "-v" || a == "--verbose") verbose = true;
         else if (a == "--debug") verbose = true;
         else if (a == "--rebuild-index") rebuild_index = true;
+        else if (a == "--dedup") dedup = true;
         else if (a == "--subsample-covg") {
             char* end = nullptr;
             const char* v = need(i);
@@ -283,7 +287,8 @@ int main(int argc, char** argv)
     if (const char* e = std::getenv("DRPRG_HIP_KEEP_READS_GB")) keep_gb = std::atof(e);
     if (keep_gb > 0)
         if (int rc = drprg_hip_keep_reads(ctx, (uint64_t)(keep_gb * 1e9))) die(drprg_hip_last_error(ctx), -rc);
-    if (subsample) drprg_hip_set_ordered_ingest(ctx, 1); // (the subsample numbers the reads in file order)
+    if (subsample || dedup) drprg_hip_set_ordered_ingest(ctx, 1); // (both number the reads in file order)
+    if (dedup && !(keep_gb > 0)) die("--dedup needs the reads resident in device memory: DRPRG_HIP_KEEP_READS_GB=0 switches that off");
     if (subsample && !(keep_gb > 0)) die("--subsample-covg needs the reads resident in device memory: DRPRG_HIP_KEEP_READS_GB=0 switches that off");
     if (verbose && std::getenv("DRPRG_HIP_T0")) std::fprintf(stderr, "[drprg-hip +%.3fs] main() entered\n", at_main);
     if (verbose) std::fprintf(stderr, "[drprg-hip +%.3fs] mapping %s against %s (k=%d w=%d) on device %d\n", since_start(), input.c_str(), index.c_str(), k, w, device);
@@ -297,6 +302,13 @@ int main(int argc, char** argv)
                                  "reads_kept=%llu bases_kept=%llu (T=%llu)\n", since_start(), (unsigned long long)fi[0], (unsigned long long)fi[1],
                 (unsigned long long)fi[2], (unsigned long long)fi[3], (unsigned long long)fi[4], (unsigned long long)fi[5], (unsigned long long)fi[6],
                 (unsigned long long)fi[7]);
+    }
+    if (dedup) { // exact duplicates dropped from the resident sample (include/drprg_hip.h "duplicate reads"); never a silent full run
+        uint64_t out[4] = { 0, 0, 0, 0 };
+        if (int rc = drprg_hip_dedup(ctx, 64, out)) die(std::string("--dedup: ") + drprg_hip_last_error(ctx), -rc);
+        if (verbose)
+            std::fprintf(stderr, "[drprg-hip +%.3fs] dedup: reads_before=%llu bases_before=%llu reads_kept=%llu bases_kept=%llu\n", since_start(),
+                (unsigned long long)out[0], (unsigned long long)out[1], (unsigned long long)out[2], (unsigned long long)out[3]);
     }
     if (subsample) { // the resident sample cut to the target depth at random (include/drprg_hip.h "random subsample"); never a silent full run
         const uint64_t target = (uint64_t)(subsample_covg * (double)mo.genome_size);

@@ -10,6 +10,7 @@
 #else
 #define DRPRG_HD
 #endif
+#include "dedup_word.h"
 
 namespace drprg {
 namespace dev {
@@ -384,6 +385,37 @@ hipError_t launch_subsample_npos_count(const SubsampleBlock& b, const uint64_t* 
     size_t temp_bytes, hipStream_t stream);
 hipError_t launch_subsample_npos_emit(const SubsampleBlock& b, const uint64_t* npos, uint64_t n_npos, const uint32_t* chunk_prefix, uint64_t* out, uint64_t out_cap,
     hipStream_t stream);
+
+// dedup.hip: exact duplicate reads (the rule: include/drprg_hip.h "duplicate reads").  DedupBatch (dedup_word.h): one packed batch.
+// launch_dedup_keys ADDS every read's content key to key[read] (u64[n_reads], zeroed by the caller: a read of no bases keeps 0); *err
+// (zeroed by the caller) is set to 1 by any kernel below that finds offsets at odds with n_bases or an index out of range, and nothing is
+// written out of bounds then.  words: ceil(n_bases / 16); 16-byte loads when it is 16-byte aligned.
+// Selection over the n reads of the sample (1 <= n < 2^32), numbered through its resident blocks.  loc: n entries, zero, then filled block
+// by block by launch_dedup_loc (every block's words and bitmap must live until launch_dedup_select is done); key: n + 1 entries, the keys
+// in [0, n).  launch_dedup_select leaves flag[i] = 0 for every read that is identical to a read before it, rank[i] = kept reads before i and
+// boff[i] = kept bases before i (n + 1 entries each, entry n the totals), exactly as launch_subsample_select does.  idx: n + 1 entries,
+// key_sorted and idx_sorted: n entries, scratch; temp: subsample_scan_temp_bytes(n) bytes.  key_bits (1..64): how many low bits of the
+// key the sort sees; the result does not depend on it.
+struct DedupLoc {
+    const uint32_t* words;
+    const uint16_t* bits;
+    uint64_t start, len;
+};
+struct DedupSelect {
+    uint64_t n;
+    uint32_t key_bits;
+    const DedupLoc* loc;
+    uint64_t *key, *key_sorted, *boff;
+    uint32_t *idx, *idx_sorted, *rank;
+    uint8_t* flag;
+    uint32_t* err;
+    void* temp;
+    size_t temp_bytes;
+};
+uint32_t dedup_tiles(uint64_t n_bases);
+hipError_t launch_dedup_keys(const DedupBatch& b, unsigned long long* key, uint32_t* err, hipStream_t stream);
+hipError_t launch_dedup_loc(const DedupBatch& b, uint64_t first, uint64_t n, DedupLoc* loc, uint32_t* err, hipStream_t stream);
+hipError_t launch_dedup_select(const DedupSelect& s, hipStream_t stream);
 
 // read_qual.hip: the read filter (the rule: include/drprg_hip.h "read filter").  qsum[i] = sum of E[quality] over read i's n_bases-indexed
 // bytes of qual (qual: n_bases + 64 bytes readable; bias 33 or 0), then flag[i] = 1 for the reads the rule keeps, rank[i] = kept reads

@@ -1048,10 +1048,10 @@ Mapper::SubsampleResult Mapper::subsample_kept(uint64_t target_bases, uint64_t s
     if (bases <= target_bases) return res;
     if (n >= (1ull << 32)) throw Error(DRPRG_EOVERFLOW, "random subsample: 2^32 reads or more in one sample");
     // ---- selection (device scratch of this call) ----
-    DeviceBuffer<uint64_t> d_len, d_key, d_key_sorted, d_csum, d_boff, d_first;
+    DeviceBuffer<uint64_t> d_len, d_key, d_key_sorted, d_csum, d_boff;
     DeviceBuffer<uint32_t> d_idx, d_idx_sorted, d_rank;
     DeviceBuffer<uint8_t> d_flag;
-    DeviceBuffer<unsigned long long> d_cut, d_bounds; // d_cut: [0..1] the cut, [2] the compaction's error word
+    DeviceBuffer<unsigned long long> d_cut; // d_cut: [0..1] the cut, [2] the compaction's error word
     DeviceBuffer<unsigned char> d_temp;
     d_len.alloc(n); d_key.alloc(n + 1); d_key_sorted.alloc(n); d_csum.alloc(n); d_boff.alloc(n + 1);
     d_idx.alloc(n + 1); d_idx_sorted.alloc(n); d_rank.alloc(n + 1); d_flag.alloc(n); d_cut.alloc(4);
@@ -1066,6 +1066,21 @@ Mapper::SubsampleResult Mapper::subsample_kept(uint64_t target_bases, uint64_t s
     sel.idx = d_idx.data(); sel.idx_sorted = d_idx_sorted.data(); sel.rank = d_rank.data(); sel.flag = d_flag.data(); sel.cut = d_cut.data();
     sel.temp = d_temp.data(); sel.temp_bytes = d_temp.size();
     HIPCHK(dev::launch_subsample_select(sel, stream_));
+    uint32_t* const d_err = reinterpret_cast<uint32_t*>(d_cut.data() + 2);
+    keep_flagged(d_flag.data(), d_rank.data(), d_boff.data(), d_err, "random subsample", res, flags);
+    return res;
+}
+
+// What both selections of resident reads end in (subsample_kept, dedup_kept): flag[i] = 1 for the reads that stay, rank[i] / boff[i] = kept
+// reads / bases before read i (n + 1 entries, n = kept_seen_; device memory).  Every resident block is compacted into a block of its kept
+// reads in arenas of their own, the old set comes back if that fails, coverage and counters are cleared and the new set is mapped.  d_err:
+// a zeroed device word.  res.reads_kept / bases_kept and flags (the device flags, or empty after a failure) are filled here.
+void Mapper::keep_flagged(const uint8_t* d_flag, const uint32_t* d_rank, const uint64_t* d_boff, uint32_t* d_err, const char* what, SubsampleResult& res,
+    std::vector<uint8_t>& flags)
+{
+    const uint64_t n = kept_seen_;
+    DeviceBuffer<uint64_t> d_first;
+    DeviceBuffer<unsigned long long> d_bounds;
     // kept reads and bases in front of every block's first read, behind its last one, and in all
     std::vector<uint64_t> first;
     for (size_t b = 0; b < kept_.size(); ++b) {
@@ -1077,10 +1092,10 @@ Mapper::SubsampleResult Mapper::subsample_kept(uint64_t target_bases, uint64_t s
     d_first.alloc(first.size());
     d_bounds.alloc(bounds.size());
     HIPCHK(hipMemcpyAsync(d_first.data(), first.data(), first.size() * sizeof(uint64_t), hipMemcpyHostToDevice, stream_));
-    HIPCHK(dev::launch_subsample_bounds(d_first.data(), (uint32_t)first.size(), n, d_rank.data(), d_boff.data(), d_bounds.data(), stream_));
+    HIPCHK(dev::launch_subsample_bounds(d_first.data(), (uint32_t)first.size(), n, d_rank, d_boff, d_bounds.data(), stream_));
     HIPCHK(hipMemcpyAsync(bounds.data(), d_bounds.data(), bounds.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream_));
     flags.resize(n);
-    HIPCHK(hipMemcpyAsync(flags.data(), d_flag.data(), n, hipMemcpyDeviceToHost, stream_));
+    HIPCHK(hipMemcpyAsync(flags.data(), d_flag, n, hipMemcpyDeviceToHost, stream_));
     HIPCHK(hipStreamSynchronize(stream_));
     res.reads_kept = bounds[bounds.size() - 2];
     res.bases_kept = bounds[bounds.size() - 1];
@@ -1109,7 +1124,6 @@ Mapper::SubsampleResult Mapper::subsample_kept(uint64_t target_bases, uint64_t s
             const uint64_t chunks = (uint64_t)dev::subsample_npos_chunks(max_npos) + 1;
             d_count.alloc(chunks); d_prefix.alloc(chunks); d_ntemp.alloc(dev::scan_temp_bytes((uint32_t)chunks));
         }
-        uint32_t* const d_err = reinterpret_cast<uint32_t*>(d_cut.data() + 2);
         for (size_t b = 0; b < old_kept.size(); ++b) {
             const DeviceBatch& ob = old_kept[b];
             const uint64_t nr = bounds[4 * b + 2] - bounds[4 * b], nb = bounds[4 * b + 3] - bounds[4 * b + 1];
@@ -1117,9 +1131,9 @@ Mapper::SubsampleResult Mapper::subsample_kept(uint64_t target_bases, uint64_t s
             const uint64_t payload = ob.packed ? (nb + 15) / 16 * 4 : nb;
             uint8_t* db = static_cast<uint8_t*>(arena_take(payload + 64));
             uint64_t* doff = db ? static_cast<uint64_t*>(arena_take((nr + 1) * sizeof(uint64_t))) : nullptr;
-            if (!db || !doff) throw Error(DRPRG_ENOMEM, "random subsample: no device memory for the kept reads beside the resident sample");
+            if (!db || !doff) throw Error(DRPRG_ENOMEM, std::string(what) + ": no device memory for the kept reads beside the resident sample");
             HIPCHK(hipMemsetAsync(db + payload, 0, 64, stream_));
-            const dev::SubsampleBlock sb { ob.d_bases, ob.d_offsets, ob.n_reads, ob.n_bases, old_first[b], d_flag.data(), d_rank.data(), d_boff.data(), nr, nb };
+            const dev::SubsampleBlock sb { ob.d_bases, ob.d_offsets, ob.n_reads, ob.n_bases, old_first[b], d_flag, d_rank, d_boff, nr, nb };
             DeviceBatch kb;
             kb.d_bases = db; kb.d_offsets = doff; kb.n_reads = nr; kb.n_bases = nb; kb.packed = ob.packed;
             if (ob.packed) {
@@ -1133,7 +1147,7 @@ Mapper::SubsampleResult Mapper::subsample_kept(uint64_t target_bases, uint64_t s
                     HIPCHK(hipStreamSynchronize(stream_));
                     if (cnt) {
                         uint64_t* dnp = static_cast<uint64_t*>(arena_take((uint64_t)cnt * sizeof(uint64_t)));
-                        if (!dnp) throw Error(DRPRG_ENOMEM, "random subsample: no device memory for the kept reads beside the resident sample");
+                        if (!dnp) throw Error(DRPRG_ENOMEM, std::string(what) + ": no device memory for the kept reads beside the resident sample");
                         HIPCHK(dev::launch_subsample_npos_emit(sb, ob.d_npos, ob.n_npos, d_prefix.data(), dnp, cnt, stream_));
                         kb.d_npos = dnp;
                         kb.n_npos = cnt;
@@ -1150,7 +1164,7 @@ Mapper::SubsampleResult Mapper::subsample_kept(uint64_t target_bases, uint64_t s
         uint32_t err = 0;
         HIPCHK(hipMemcpyAsync(&err, d_err, sizeof err, hipMemcpyDeviceToHost, stream_));
         HIPCHK(hipStreamSynchronize(stream_)); // (nothing reads the old blocks any more)
-        if (err) throw Error(DRPRG_EIO, "random subsample: the resident blocks' offsets and the selection do not fit each other");
+        if (err) throw Error(DRPRG_EIO, std::string(what) + ": the resident blocks' offsets and the selection do not fit each other");
     } catch (...) { // the sample as it was
         (void)hipStreamSynchronize(stream_);
         kept_arenas_ = std::move(old_arenas);
@@ -1181,7 +1195,132 @@ Mapper::SubsampleResult Mapper::subsample_kept(uint64_t target_bases, uint64_t s
     in_keep_call_ = false;
     HIPCHK(hipStreamSynchronize(stream_));
     tot_reads_ += res.reads_kept - in_blocks; // (kept empty reads of blocks that hold no base any more)
+}
+
+// One resident block as the key kernel reads it: a packed block as it lies there (the bitmap of its listed positions beside it), an ASCII
+// block packed into scratch first.  The scratch lives as long as this object.
+struct Mapper::DedupBlock {
+    DeviceBuffer<uint32_t> words;
+    DeviceBuffer<uint64_t> npos;
+    DeviceBuffer<uint16_t> bits;
+    dev::DedupBatch batch {};
+};
+
+void Mapper::dedup_block(const DeviceBatch& kb, DedupBlock& out, unsigned long long* d_count)
+{
+    const uint64_t n_words = (kb.n_bases + 15) / 16;
+    const uint64_t* d_npos = kb.d_npos;
+    uint64_t n_npos = kb.n_npos;
+    const uint32_t* words = reinterpret_cast<const uint32_t*>(kb.d_bases);
+    if (!kb.packed) {
+        // launch_pack counts every position it meets and writes those below the capacity: one pass with room for a modest number of them,
+        // a second one only for a block that holds more
+        const uint64_t room = std::min<uint64_t>(kb.n_bases, 1u << 16);
+        out.words.alloc(n_words + 4);
+        out.npos.alloc(room);
+        unsigned long long cnt = 0;
+        HIPCHK(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), stream_));
+        HIPCHK(dev::launch_pack(kb.d_bases, kb.n_bases, out.words.data(), out.npos.data(), room, d_count, stream_));
+        HIPCHK(hipMemcpyAsync(&cnt, d_count, sizeof cnt, hipMemcpyDeviceToHost, stream_));
+        HIPCHK(hipStreamSynchronize(stream_));
+        if (cnt > room) {
+            out.npos.alloc(cnt);
+            HIPCHK(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), stream_));
+            HIPCHK(dev::launch_pack(kb.d_bases, kb.n_bases, out.words.data(), out.npos.data(), cnt, d_count, stream_));
+        }
+        words = out.words.data();
+        d_npos = out.npos.data();
+        n_npos = cnt;
+    }
+    if (n_npos) {
+        out.bits.alloc(n_words + 8);
+        HIPCHK(hipMemsetAsync(out.bits.data(), 0, out.bits.bytes(), stream_));
+        HIPCHK(dev::launch_mark_npos(d_npos, n_npos, kb.n_bases, out.bits.data(), stream_));
+    }
+    out.batch = dev::DedupBatch { words, n_npos ? out.bits.data() : nullptr, kb.d_offsets, kb.n_reads, kb.n_bases };
+}
+
+Mapper::SubsampleResult Mapper::dedup_kept(uint32_t key_bits, std::vector<uint8_t>& flags)
+{
+    if (key_bits < 1 || key_bits > 64) throw Error(DRPRG_EINVAL, "duplicate removal: key_bits must be 1..64");
+    if (!kept_complete())
+        throw Error(DRPRG_ENODATA, "duplicate removal: not every read of the sample is resident in device memory (drprg_hip_keep_reads is off, or the "
+                                   "sample is larger than its limit; the executables take the limit from DRPRG_HIP_KEEP_READS_GB)");
+    sync();
+    HIPCHK(hipSetDevice(device_));
+    HIPCHK(hipStreamSynchronize(stream_));
+    flags.clear();
+    const uint64_t n = kept_seen_;
+    uint64_t bases = 0, with_bases = 0;
+    for (const DeviceBatch& b : kept_) {
+        bases += b.n_bases;
+        with_bases += b.n_bases ? b.n_reads : 0; // (an upper bound: two reads with bases need two reads in blocks that hold bases)
+    }
+    SubsampleResult res { n, bases, n, bases };
+    if (n >= (1ull << 32)) throw Error(DRPRG_EOVERFLOW, "duplicate removal: 2^32 reads or more in one sample");
+    if (with_bases < 2) return res;
+    // ---- selection (device scratch of this call) ----
+    DeviceBuffer<uint64_t> d_key, d_key_sorted, d_boff;
+    DeviceBuffer<uint32_t> d_idx, d_idx_sorted, d_rank, d_err;
+    DeviceBuffer<uint8_t> d_flag;
+    DeviceBuffer<dev::DedupLoc> d_loc;
+    DeviceBuffer<unsigned long long> d_count;
+    DeviceBuffer<unsigned char> d_temp;
+    d_key.alloc(n + 1); d_key_sorted.alloc(n); d_boff.alloc(n + 1); d_idx.alloc(n + 1); d_idx_sorted.alloc(n); d_rank.alloc(n + 1);
+    d_flag.alloc(n); d_loc.alloc(n); d_err.alloc(4); d_count.alloc(1);
+    d_temp.alloc(dev::subsample_scan_temp_bytes(n));
+    HIPCHK(hipMemsetAsync(d_key.data(), 0, d_key.bytes(), stream_));
+    HIPCHK(hipMemsetAsync(d_loc.data(), 0, d_loc.bytes(), stream_));
+    HIPCHK(hipMemsetAsync(d_err.data(), 0, d_err.bytes(), stream_));
+    std::vector<DedupBlock> blocks(kept_.size()); // (the exact check reads every block: the scratch of all of them lives until it is done)
+    for (size_t b = 0; b < kept_.size(); ++b) {
+        if (!kept_[b].n_reads || !kept_[b].n_bases) continue;
+        if (kept_first_[b] + kept_[b].n_reads > n) throw Error(DRPRG_EIO, "duplicate removal: the resident blocks hold more reads than the sample");
+        dedup_block(kept_[b], blocks[b], d_count.data());
+        HIPCHK(dev::launch_dedup_keys(blocks[b].batch, reinterpret_cast<unsigned long long*>(d_key.data()) + kept_first_[b], d_err.data(), stream_));
+        HIPCHK(dev::launch_dedup_loc(blocks[b].batch, kept_first_[b], n, d_loc.data(), d_err.data(), stream_));
+    }
+    dev::DedupSelect sel {};
+    sel.n = n; sel.key_bits = key_bits; sel.loc = d_loc.data();
+    sel.key = d_key.data(); sel.key_sorted = d_key_sorted.data(); sel.boff = d_boff.data();
+    sel.idx = d_idx.data(); sel.idx_sorted = d_idx_sorted.data(); sel.rank = d_rank.data(); sel.flag = d_flag.data(); sel.err = d_err.data();
+    sel.temp = d_temp.data(); sel.temp_bytes = d_temp.size();
+    HIPCHK(dev::launch_dedup_select(sel, stream_));
+    uint32_t err = 0, kept = 0;
+    HIPCHK(hipMemcpyAsync(&err, d_err.data(), sizeof err, hipMemcpyDeviceToHost, stream_));
+    HIPCHK(hipMemcpyAsync(&kept, d_rank.data() + n, sizeof kept, hipMemcpyDeviceToHost, stream_));
+    HIPCHK(hipStreamSynchronize(stream_));
+    if (err) throw Error(DRPRG_EIO, "duplicate removal: a resident block's offsets do not fit its bases");
+    if (kept == n) return res; // no read dropped: nothing else happens
+    keep_flagged(d_flag.data(), d_rank.data(), d_boff.data(), d_err.data() + 1, "duplicate removal", res, flags);
     return res;
+}
+
+void Mapper::dedup_keys_device(const uint32_t* d_words, const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases, const uint64_t* d_npos, uint64_t n_npos,
+    unsigned long long* d_keys, hipStream_t stream)
+{
+    if (n_reads == 0) return;
+    HIPCHK(hipSetDevice(device_));
+    if (!stream) stream = stream_;
+    if (!d_offsets || !d_keys || (n_bases && !d_words) || (n_npos && !d_npos)) throw Error(DRPRG_EINVAL, "null device pointer");
+    if (n_reads >= (1ull << 32)) throw Error(DRPRG_EOVERFLOW, "duplicate keys: 2^32 reads or more in one batch");
+    const uint64_t n_words = (n_bases + 15) / 16;
+    DeviceBuffer<uint16_t> d_bits;
+    DeviceBuffer<uint32_t> d_err;
+    d_err.alloc(1);
+    HIPCHK(hipMemsetAsync(d_err.data(), 0, d_err.bytes(), stream));
+    HIPCHK(hipMemsetAsync(d_keys, 0, n_reads * sizeof(unsigned long long), stream));
+    if (n_npos) {
+        d_bits.alloc(n_words + 8);
+        HIPCHK(hipMemsetAsync(d_bits.data(), 0, d_bits.bytes(), stream));
+        HIPCHK(dev::launch_mark_npos(d_npos, n_npos, n_bases, d_bits.data(), stream));
+    }
+    const dev::DedupBatch b { d_words, n_npos ? d_bits.data() : nullptr, d_offsets, n_reads, n_bases };
+    HIPCHK(dev::launch_dedup_keys(b, d_keys, d_err.data(), stream));
+    uint32_t err = 0;
+    HIPCHK(hipMemcpyAsync(&err, d_err.data(), sizeof err, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    if (err) throw Error(DRPRG_EINVAL, "duplicate keys: the offsets do not ascend from 0 to n_bases");
 }
 
 void Mapper::select_reads_with_anchors(std::vector<uint64_t> anchors, uint32_t A, std::vector<uint8_t>& bases, std::vector<uint64_t>& offsets,

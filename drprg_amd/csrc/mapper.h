@@ -160,6 +160,15 @@ public:
         uint64_t reads_before, bases_before, reads_kept, bases_kept;
     };
     SubsampleResult subsample_kept(uint64_t target_bases, uint64_t seed, std::vector<uint8_t>& flags);
+    // Exact duplicate reads dropped from the resident sample (the rule: include/drprg_hip.h "duplicate reads"; dedup.hip).  Needs
+    // kept_complete().  Fewer than two reads with bases, or no read dropped: nothing else happens (no compaction, coverage and counters
+    // untouched, flags left empty).  Otherwise what subsample_kept does with its selection.  key_bits (1..64): how many low bits of the
+    // content key the sort sees; the result does not depend on it.  A call that fails leaves the sample as it was.
+    SubsampleResult dedup_kept(uint32_t key_bits, std::vector<uint8_t>& flags);
+    // The key kernel alone on the caller's packed batch (drprg_hip_dedup_keys_device): d_keys[i] = the content key of read i, 0 for a read
+    // of no bases.  Synchronises `stream`.
+    void dedup_keys_device(const uint32_t* d_words, const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases, const uint64_t* d_npos, uint64_t n_npos,
+        unsigned long long* d_keys, hipStream_t stream);
 
     // this += other, on the device (the other Mapper's vectors are left as they are): peer copy into a scratch buffer + one
     // add kernel, or the add kernel alone when both live on the same device.  Both are synchronised first.
@@ -420,6 +429,11 @@ private:
     bool kept_broken_ = false, in_keep_call_ = false;
     Event kept_copied_;
     void* arena_take(size_t bytes);
+    // the second half of subsample_kept and dedup_kept: compaction by the flags, roll-back on failure, the kept reads mapped afresh
+    void keep_flagged(const uint8_t* d_flag, const uint32_t* d_rank, const uint64_t* d_boff, uint32_t* d_err, const char* what, SubsampleResult& res,
+        std::vector<uint8_t>& flags);
+    struct DedupBlock;
+    void dedup_block(const DeviceBatch& kb, DedupBlock& out, unsigned long long* d_count);
     void stop_keeping(); // the resident set given up (over its limit, or the device is full): what map_host_async and map_host_filtered do alike
     DeviceBuffer<uint32_t> d_peer_tmp_; // add_vectors_from: the other device's vectors on this device
     // timing

@@ -5,7 +5,8 @@
 //   pandora discover -g G --max-covg M -v -o <dir> -t T -w W -k K -c C [-I] [-K] <prg> <query.tsv>
 //   pandora map      --genotype --local --gt-conf 0 -v -o <out> -g G --max-covg M --vcf-refs <genes.fa>
 //                    -t T -w W -k K -c C [-I] [-K] <prg> <reads>
-// and, this build's own, --subsample-covg D [--seed S] on map and discover (include/drprg_hip.h "random subsample"),
+// and, this build's own, --subsample-covg D [--seed S] on map and discover (include/drprg_hip.h "random subsample"), --dedup on both
+// (include/drprg_hip.h "duplicate reads"),
 // --min-read-len L, --max-read-len L and --min-read-qual Q on both (include/drprg_hip.h "read filter"),
 // and writes the files drprg then looks for: <prg>.k<K>.w<W>.idx + kmer_prgs/ (index),
 // <dir>/denovo_paths.txt (discover, /root/reference/src/lib.rs:569-577),
@@ -48,6 +49,8 @@ struct Args {
     bool subsample = false, seed_given = false;
     double subsample_covg = 0;
     uint64_t seed = 1;
+    // --dedup: exact duplicate reads dropped from the resident sample (include/drprg_hip.h "duplicate reads")
+    bool dedup = false;
     // --min-read-len L, --max-read-len L, --min-read-qual Q: the read filter (include/drprg_hip.h "read filter"); 0 = not set
     uint64_t min_read_len = 0, max_read_len = 0;
     uint32_t min_read_qual_milli = 0;
@@ -68,7 +71,7 @@ void usage()
         "pandora-compatible front end of the MI355X drprg hot path\n"
         "  pandora index    [-t N] [-w W] [-k K] <prg>\n"
         "  pandora map      [--genotype] [--local] [--gt-conf X] [-v] [-o DIR] [-g SIZE] [--max-covg N | --subsample-covg D [--seed S]]\n"
-        "                   [--min-read-len L] [--max-read-len L] [--min-read-qual Q]\n"
+        "                   [--dedup] [--min-read-len L] [--max-read-len L] [--min-read-qual Q]\n"
         "                   [--vcf-refs FASTA] [-t N] [-w W] [-k K] [-c N] [-I] [-K] [-e RATE] [--max-diff N] <prg> <reads>\n"
         "  pandora discover [same mapping options] <prg> <query.tsv>\n"
         "  --max-covg N: reads are taken in file order up to and including the first one at which (N + 1) x SIZE bases are reached;\n"
@@ -80,6 +83,10 @@ void usage()
         "                including the one that reaches the target; the kept reads are mapped afresh.  The default --max-covg gives way\n"
         "                to it; an explicit --max-covg other than 4294967295 beside it is an error.  Needs the whole sample resident\n"
         "                (DRPRG_HIP_KEEP_READS_GB, default 32): the run fails if it is not.\n"
+        "  --dedup: behind the mapping pass (and in front of --subsample-covg) every read that is identical to a read before it in the file --\n"
+        "                same length, same bases case-insensitively, non-ACGT bases at the same places; forward strand only -- is dropped on the\n"
+        "                device and the kept reads are mapped afresh: the run is that of a file of the kept reads.  Needs the whole sample\n"
+        "                resident (DRPRG_HIP_KEEP_READS_GB, default 32): the run fails if it is not.\n"
         "  --min-read-len L, --max-read-len L, --min-read-qual Q: reads shorter than L, longer than L or of a mean quality below Q (a decimal\n"
         "                Phred value; the mean is that of the error probabilities, as nanoq and chopper take it) are dropped on the device\n"
         "                before anything else sees them: the run is that of a file of the kept reads.  --min-read-qual needs qualities:\n"
@@ -133,6 +140,7 @@ Args parse(int argc, char** argv)
             if (end == v || *end || !(q >= 0) || q > 93) die(std::string("--min-read-qual needs a mean quality between 0 and 93, not ") + v, 2);
             a.min_read_qual_milli = (uint32_t)(q * 1000.0 + 0.5);
         }
+        else if (s == "--dedup") a.dedup = true;
         else if (s == "-o" || s == "--outdir") a.outdir = need(i);
         else if (s == "--vcf-refs") a.vcf_refs = need(i);
         else if (s == "--gt-conf") a.gt_conf = std::atof(need(i));
@@ -242,22 +250,36 @@ std::string run_tag(const Args& a, const std::string& reads)
         + std::to_string(a.min_cluster_size) + "|I" + std::to_string((int)a.illumina) + "|e" + std::to_string(a.error_rate) + "|m"
         + std::to_string(a.max_diff) + "|g" + std::to_string((unsigned long long)a.genome_size) + "|M" + std::to_string((unsigned long long)a.max_covg)
         + (a.subsample ? "|S" + std::to_string(a.subsample_covg) + "/" + std::to_string((unsigned long long)a.seed) : std::string())
+        + (a.dedup ? std::string("|D") : std::string())
         + (a.min_read_len || a.max_read_len || a.min_read_qual_milli ? "|F" + std::to_string((unsigned long long)a.min_read_len) + "/"
                   + std::to_string((unsigned long long)a.max_read_len) + "/" + std::to_string(a.min_read_qual_milli)
                                                                      : std::string());
 }
 
-// The reads stay in HBM after the mapping pass: up to DRPRG_HIP_KEEP_READS_GB per device, default 32, 0 = off.  --subsample-covg works on
+// The reads stay in HBM after the mapping pass: up to DRPRG_HIP_KEEP_READS_GB per device, default 32, 0 = off.  --subsample-covg and --dedup work on
 // the resident sample, so there "off" is an error, not a slower route.
 void keep_reads(drprg_hip_ctx* ctx, const Args& a)
 {
     double keep_gb = 32;
     if (const char* e = std::getenv("DRPRG_HIP_KEEP_READS_GB")) keep_gb = std::atof(e);
-    if (a.subsample) drprg_hip_set_ordered_ingest(ctx, 1); // (the subsample numbers the reads in file order)
+    if (a.subsample || a.dedup) drprg_hip_set_ordered_ingest(ctx, 1); // (both number the reads in file order)
     if (keep_gb > 0) {
         if (int rc = drprg_hip_keep_reads(ctx, (uint64_t)(keep_gb * 1e9))) die(drprg_hip_last_error(ctx), -rc);
     } else if (a.subsample)
         die("--subsample-covg needs the reads resident in device memory: DRPRG_HIP_KEEP_READS_GB=0 switches that off");
+    else if (a.dedup)
+        die("--dedup needs the reads resident in device memory: DRPRG_HIP_KEEP_READS_GB=0 switches that off");
+}
+
+// --dedup: behind the mapping pass, in front of --subsample-covg.  Fails loudly when the sample is not resident.
+void dedup(drprg_hip_ctx* ctx, const Args& a)
+{
+    if (!a.dedup) return;
+    uint64_t out[4] = { 0, 0, 0, 0 };
+    if (int rc = drprg_hip_dedup(ctx, 64, out)) die(std::string("--dedup: ") + drprg_hip_last_error(ctx), -rc);
+    if (a.verbose)
+        std::printf("[pandora-hip] dedup: reads_before=%llu bases_before=%llu reads_kept=%llu bases_kept=%llu\n", (unsigned long long)out[0],
+            (unsigned long long)out[1], (unsigned long long)out[2], (unsigned long long)out[3]);
 }
 
 // --subsample-covg: behind the mapping pass, before anything reads coverage.  Fails loudly when the sample is not resident.
@@ -317,8 +339,9 @@ int cmd_map(const Args& a)
         std::printf("[pandora-hip] coverage of this PRG and these reads taken from %s (reads=%llu bases=%llu hits=%llu): no second mapping pass\n",
             cache.c_str(), (unsigned long long)cached[0], (unsigned long long)cached[1], (unsigned long long)cached[3]);
     } else {
-        if (a.subsample) keep_reads(ctx, a);
+        if (a.subsample || a.dedup) keep_reads(ctx, a);
         if (int rc = drprg_hip_map_fastx(ctx, a.positional[1].c_str())) die(drprg_hip_last_error(ctx), -rc);
+        dedup(ctx, a);
         subsample(ctx, a);
         report_counters(ctx, now_s() - t0);
         report_cap(ctx, a);
@@ -351,6 +374,7 @@ int cmd_discover(const Args& a)
     keep_reads(ctx, a);
     double t0 = now_s();
     if (int rc = drprg_hip_map_fastx(ctx, reads.c_str())) die(drprg_hip_last_error(ctx), -rc);
+    dedup(ctx, a);
     subsample(ctx, a);
     report_counters(ctx, now_s() - t0);
     report_cap(ctx, a);

@@ -212,6 +212,26 @@ class Context:
         _check(lib.drprg_hip_subsample_flags(self._h, _ptr(flags), flags.size), self._h)
         return flags
 
+    # ---- duplicate reads (include/drprg_hip.h: drprg_hip_dedup) -----------------------------------
+    def dedup(self, key_bits=64):
+        """drops every resident read that is identical to a read before it and maps the kept reads afresh (nothing happens when no read is
+        dropped); returns what was there and what is left.  key_bits: how many low bits of the content key the sort sees (the result does
+        not depend on it)"""
+        out = (C.c_uint64 * 4)()
+        _check(lib.drprg_hip_dedup(self._h, int(key_bits), out), self._h)
+        return dict(reads_before=int(out[0]), bases_before=int(out[1]), reads_kept=int(out[2]), bases_kept=int(out[3]))
+
+    def dedup_flags(self, n_reads):
+        """one byte per read of the sample as the last dedup() found it, 1 = kept (n_reads: how many it held)"""
+        flags = np.zeros(int(n_reads), dtype=np.uint8)
+        _check(lib.drprg_hip_dedup_flags(self._h, _ptr(flags), flags.size), self._h)
+        return flags
+
+    def dedup_keys_device(self, d_words, d_offsets, n_reads, n_bases, d_npos, n_npos, d_keys, stream=None):
+        """the content keys of a packed batch in device memory (addresses as integers; d_npos may be None when n_npos is 0) into
+        d_keys (u64 per read)"""
+        _check(lib.drprg_hip_dedup_keys_device(self._h, d_words, d_offsets, int(n_reads), int(n_bases), d_npos, int(n_npos), d_keys, stream), self._h)
+
     # ---- read filter (include/drprg_hip.h: drprg_hip_set_read_filter) ---------------------------
     @staticmethod
     def qual_milli(min_qual):

@@ -321,6 +321,52 @@ int drprg_hip_subsample(drprg_hip_ctx* ctx, uint64_t target_bases, uint64_t seed
  * block, and every block under a depth cap, is in order anyway.  The executables switch it on when --subsample-covg is given. */
 int drprg_hip_set_ordered_ingest(drprg_hip_ctx* ctx, int on);
 int drprg_hip_subsample_flags(drprg_hip_ctx* ctx, uint8_t* flags, uint64_t n);
+/* ---- Duplicate reads: exact duplicates dropped from the resident sample, on the device.  THIS BUILD'S OWN RULE (what fastp --dedup,
+ * clumpify dedupe and seqkit rmdup -s do in front of drprg, made exact); neither pandora nor drprg has one.  Every copy of a PCR or optical
+ * duplicate counts as depth: in the k-mer coverage, in the total bases the expected depth comes from, under --max-covg and in the target
+ * of --subsample-covg.
+ *   Numbering.  Reads are numbered i = 0 .. n-1 as drprg_hip_subsample numbers them: the order mapped since the last reset, which is file
+ *   order, through the resident blocks and through several drprg_hip_map_fastx calls.  This is after the read filter and after a depth cap,
+ *   which both act at ingest.
+ *   Letters and words.  A base's letter is the packed form's: A/a = 0, C/c = 1, T/t = 2, G/g = 3.  Any other byte, and any BAM code other
+ *   than A, C, G, T, is MASKED: letter 0 and a mask bit.  The packed form cannot tell N from R, so neither does the rule.  For a read of
+ *   L >= 1 bases and j = 0 .. ceil(L/16) - 1:
+ *       v_j = sum over t < 16, 16j+t < L of letter(16j+t) << 2t
+ *       m_j = sum over t < 16, 16j+t < L of masked(16j+t) << t
+ *       x_j = v_j | (uint64)m_j << 32
+ *   Identity.  Two reads are identical iff they have the same L and the same sequence x_0, x_1, ...: the same length, masked bases at the
+ *   same places, and the same letters elsewhere, case-insensitively.  It is forward strand only: a read and its reverse complement are
+ *   different reads, as for fastp and seqkit rmdup -s -P.  A BAM record with flag 0x10 is compared as the read it becomes, which is
+ *   already reverse-complemented.  BAM flag 0x400 stays ignored, as now.
+ *   Selection.  Read i is dropped iff some read h < i is identical to it.  The first copy in file order is kept.  Kept reads stay in file
+ *   order.  A read of no bases is never a duplicate and never makes one: it is always kept.
+ *   The key (not part of the decision, but part of the statement).  fin is the splitmix64 finaliser stated under "random subsample",
+ *   G = 0x9E3779B97F4A7C15, and key = fin(G * L) + sum over j of fin(x_j + G * (j + 1)) in 64-bit unsigned arithmetic.  It is a sum, so
+ *   pieces of a read computed by different lanes, waves and workgroups add up in any order to the same bits.  L is in the key because
+ *   letter 0 is A: without it a read and the same read with a poly-A tail would share a key systematically.  Equal keys never decide
+ *   anything.  Identity does.
+ *   Invariance.  The result depends on the reads and their order alone.  It does not depend on how ingest cut the file into blocks, on the
+ *   input form (ASCII, packed, BAM), on -t, or on key_bits below.
+ *   drprg_hip_dedup(ctx, key_bits, out): out[0..3] = reads before, bases before, reads kept, bases kept.  key_bits is in 1..64: how many
+ *     low bits of the key the sort sees; 64 is what the executables pass.  The result does not depend on it, as drprg_hip_select_reads'
+ *     window_bytes does not change its result; it exists so that the collision path is reachable.  Fewer than two reads with bases, or no
+ *     read dropped: nothing else happens (no compaction, no fresh mapping; coverage and counters are untouched).  Otherwise every resident
+ *     block is compacted into a block of its kept reads and the kept reads are mapped afresh, as drprg_hip_subsample does it (csrc/dedup.hip,
+ *     csrc/subsample.hip): after the call the context is that of one given the kept reads alone, and a following drprg_hip_subsample
+ *     numbers the kept reads from 0 -- the pipeline dedupe | rasusa | drprg.  -EINVAL for key_bits outside 1..64, for a context over
+ *     several devices and for a sample whose drprg_hip_map_fastx blocks arrived unordered (drprg_hip_set_ordered_ingest); -ENODATA (-61)
+ *     unless the sample is resident (the text names DRPRG_HIP_KEEP_READS_GB); -EOVERFLOW for 2^32 reads or more.  A depth cap is NOT
+ *     refused: the cap decides at ingest which reads arrive, dedup sees those.  A refused or failed call leaves the context as it was.
+ *   drprg_hip_dedup_flags(ctx, flags, n): flags[i] = 1 if read i (numbering before the call) was kept by the last drprg_hip_dedup since
+ *     the last reset, else 0; all ones when nothing was dropped.  -EINVAL unless n is that call's out[0].
+ *   drprg_hip_dedup_keys_device: the key kernel alone on a caller-owned packed batch, under the stream rule of the other device entries
+ *     (NULL: the context's own stream; the call returns when the work is done).  d_words: u32[ceil(n_bases / 16)], read with 16-byte loads
+ *     when 16-byte aligned; d_offsets: u64[n_reads + 1] from 0 to n_bases (-EINVAL otherwise); d_npos: the n_npos positions of the masked
+ *     bases, in any order (may be NULL when n_npos is 0); d_keys: u64[n_reads], 0 for a read of no bases.  -EOVERFLOW for 2^32 reads or more. */
+int drprg_hip_dedup(drprg_hip_ctx* ctx, uint32_t key_bits, uint64_t out[4]);
+int drprg_hip_dedup_flags(drprg_hip_ctx* ctx, uint8_t* flags, uint64_t n);
+int drprg_hip_dedup_keys_device(drprg_hip_ctx* ctx, const void* d_words, const void* d_offsets, uint64_t n_reads, uint64_t n_bases, const void* d_npos,
+    uint64_t n_npos, void* d_keys, void* hip_stream);
 /* ---- Read filter: reads dropped by length and mean quality on the device, as they arrive.  THIS BUILD'S OWN RULE, stated from memory of
  * what the filters nanopore workflows run in front of drprg compute (nanoq, chopper -q Q -l L, filtlong); neither pandora nor drprg has one.
  *   Settings, per context: min_len (0: no lower bound), max_len (0: no upper bound), min_qual_milli = Q * 1000 (0: no quality test).
