@@ -16,6 +16,7 @@
 #include "rccl_dyn.h"
 #include "pack.h"
 #include "read_qual_piece.h"
+#include "read_trim_piece.h"
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -134,6 +135,7 @@ struct drprg_hip_ctx {
     // submitters of drprg_hip_map_fastx, one per device, under filter_mu
     Mapper::ReadFilter read_filter;
     Mapper::FilterOutcome filter_counts;
+    Mapper::TrimOutcome trim_counts; // drprg_hip_read_trim_info (the settings ride in read_filter)
     std::mutex filter_mu;
     // (the page-locked ingest blocks of drprg_hip_map_fastx are recycled process-wide: PinPool above)
     // multi-device context: RCCL communicators of its devices (created on first use; empty when RCCL is not used)
@@ -497,7 +499,8 @@ int drprg_hip_map_fastx(drprg_hip_ctx* ctx, const char* reads_path)
     // everything behind it -- the counters, the depth cap's running total, the resident set -- sees the kept reads alone.  Not set: nothing
     // below differs from a build without it (no quality byte is parsed or copied, no launch, no wait).
     const Mapper::ReadFilter filter = ctx->read_filter;
-    hooks.want_qual = filter.use_qual();
+    hooks.want_qual = filter.wants_qual(); // (for the filter's threshold or for --trim-qual; fixed crops alone carry none)
+    if (filter.trim_qual_milli) hooks.qual_flag = "--trim-qual"; // (trimming comes first: it is the first to miss them)
     uint64_t kept_reads = 0, kept_bases = 0; // of this call (under filter_mu)
     auto filtered = [&](Mapper& dev, const Mapper::HostBatch& hb, uint64_t cap_need) {
         Mapper::FilterOutcome o;
@@ -506,6 +509,9 @@ int drprg_hip_map_fastx(drprg_hip_ctx* ctx, const char* reads_path)
         Mapper::FilterOutcome& t = ctx->filter_counts;
         t.reads_seen += o.reads_seen; t.bases_seen += o.bases_seen; t.dropped_short += o.dropped_short; t.dropped_long += o.dropped_long;
         t.dropped_lowq += o.dropped_lowq; t.reads_kept += o.reads_kept; t.bases_kept += o.bases_kept;
+        Mapper::TrimOutcome& tt = ctx->trim_counts;
+        tt.reads_seen += o.trim.reads_seen; tt.bases_seen += o.trim.bases_seen; tt.reads_lost_base += o.trim.reads_lost_base; tt.cut_front += o.trim.cut_front;
+        tt.cut_tail += o.trim.cut_tail; tt.qcut_front += o.trim.qcut_front; tt.qcut_tail += o.trim.qcut_tail; tt.emptied += o.trim.emptied;
         kept_reads += o.mapped_reads;
         kept_bases += o.mapped_bases;
         return o;
@@ -591,14 +597,16 @@ int drprg_hip_map_fastx(drprg_hip_ctx* ctx, const char* reads_path)
         if (e.code != DRPRG_EAGAIN_SERIAL) throw; // (a failed multi-device pass leaves partial vectors on the devices: reset before reuse)
         FastxReader rd(reads_path);
         ReadBatch batch;
-        while (rd.next_batch(batch, 8u << 20, 1ull << 30, false, filter.use_qual())) {
+        while (rd.next_batch(batch, 8u << 20, 1ull << 30, false, filter.wants_qual())) {
             if (!batch.n_reads()) continue;
             Mapper::HostBatch hb { batch.bases.data(), batch.offsets.data(), batch.n_reads() };
             CapCut c;
             if (filter.any()) {
+                if (filter.trim_qual_milli && batch.qual.size() != batch.bases.size())
+                    throw Error(DRPRG_EINVAL, "--trim-qual: a FASTA record has no base qualities; a read is never trimmed by a quality it does not have");
                 if (filter.use_qual() && batch.qual.size() != batch.bases.size())
                     throw Error(DRPRG_EINVAL, "--min-read-qual: a FASTA record has no base qualities; a read is never kept or dropped by a quality threshold it cannot be held against");
-                hb.qual = batch.qual.data();
+                if (filter.wants_qual()) hb.qual = batch.qual.data();
                 hb.qual_bias = 33;
                 uint64_t T = 0;
                 const Mapper::FilterOutcome o = filtered(m, hb, cap_target(ctx, T) ? T - ctx->total_bases : 0);
@@ -648,6 +656,9 @@ int drprg_hip_set_threads(drprg_hip_ctx* ctx, int threads)
 // The entry points that carry no qualities: while a filter is set they refuse, rather than map unfiltered reads without saying so.
 static void refuse_unfiltered(const drprg_hip_ctx* ctx, const char* entry)
 {
+    if (ctx->read_filter.trims())
+        throw Error(DRPRG_EINVAL, std::string(entry) + ": read trimming is set (drprg_hip_set_read_trim) and this entry carries no qualities; trimming "
+                                                      "runs in drprg_hip_map_fastx (clear it with drprg_hip_set_read_trim(ctx, 0, 0, 0, 0))");
     if (ctx->read_filter.any())
         throw Error(DRPRG_EINVAL, std::string(entry) + ": a read filter is set (drprg_hip_set_read_filter) and this entry carries no qualities; the filter "
                                                       "runs in drprg_hip_map_fastx (clear it with drprg_hip_set_read_filter(ctx, 0, 0, 0))");
@@ -658,7 +669,7 @@ int drprg_hip_set_read_filter(drprg_hip_ctx* ctx, uint64_t min_len, uint64_t max
     API_BEGIN(ctx)
     if (max_len != 0 && max_len < min_len) throw Error(DRPRG_EINVAL, "read filter: the longest read allowed is shorter than the shortest");
     if (min_qual_milli > dev::RQ_MAX_QUAL_MILLI) throw Error(DRPRG_EINVAL, "read filter: a mean quality above 93 cannot be asked for");
-    Mapper::ReadFilter f;
+    Mapper::ReadFilter f = ctx->read_filter; // (the trim settings ride along: drprg_hip_set_read_trim)
     f.min_len = min_len;
     f.max_len = max_len;
     f.min_qual_milli = min_qual_milli;
@@ -694,6 +705,51 @@ int drprg_hip_read_filter_device(drprg_hip_ctx* ctx, const void* d_qual, uint32_
     out[3] = 0;
     if (res[dev::RF_OFFSETS]) throw Error(DRPRG_EINVAL, "read filter: the offsets do not ascend to n_bases");
     if (res[dev::RF_BAD_AT]) throw Error(DRPRG_EFORMAT, "a base quality outside 0..93 at quality byte " + std::to_string(res[dev::RF_BAD_AT] - 1));
+    API_END(ctx)
+}
+
+// ---- read trimming (the rule: include/drprg_hip.h "read trimming") ---------------------------------------------------------------
+int drprg_hip_set_read_trim(drprg_hip_ctx* ctx, uint64_t front, uint64_t tail, uint32_t qual_milli, uint32_t window)
+{
+    API_BEGIN(ctx)
+    if (qual_milli > dev::RT_MAX_QUAL_MILLI) throw Error(DRPRG_EINVAL, "read trimming: a quality above 93 cannot be asked for");
+    if (window > dev::RT_MAX_WINDOW) throw Error(DRPRG_EINVAL, "read trimming: the window is 1..32 bases");
+    if (window != 0 && qual_milli == 0) throw Error(DRPRG_EINVAL, "read trimming: a window without a quality (--trim-window without --trim-qual)");
+    ctx->read_filter.trim_front = front;
+    ctx->read_filter.trim_tail = tail;
+    ctx->read_filter.trim_qual_milli = qual_milli;
+    ctx->read_filter.trim_window = qual_milli ? (window ? window : dev::RT_DEFAULT_WINDOW) : 0;
+    API_END(ctx)
+}
+
+int drprg_hip_read_trim_info(drprg_hip_ctx* ctx, uint64_t out[8])
+{
+    API_BEGIN(ctx)
+    if (!out) throw Error(DRPRG_EINVAL, "null output");
+    std::lock_guard<std::mutex> g(ctx->filter_mu);
+    const Mapper::TrimOutcome& t = ctx->trim_counts;
+    out[0] = t.reads_seen; out[1] = t.bases_seen; out[2] = t.reads_lost_base; out[3] = t.cut_front; out[4] = t.cut_tail;
+    out[5] = t.qcut_front; out[6] = t.qcut_tail; out[7] = t.emptied;
+    API_END(ctx)
+}
+
+int drprg_hip_read_trim_device(drprg_hip_ctx* ctx, const void* d_qual, uint32_t qual_bias, const void* d_offsets, const void* d_rev, uint64_t n_reads,
+    uint64_t n_bases, void* d_begin, void* d_end, uint64_t out[4], void* hip_stream)
+{
+    API_BEGIN(ctx)
+    Mapper& m = need_mapper(ctx);
+    if (!out) throw Error(DRPRG_EINVAL, "null output");
+    if (qual_bias != 0 && qual_bias != 33) throw Error(DRPRG_EINVAL, "read trimming: the quality bias is 33 (FASTQ) or 0 (BAM)");
+    uint64_t res[9];
+    m.read_trim_device(ctx->read_filter, (const uint8_t*)d_qual, qual_bias, (const uint64_t*)d_offsets, (const uint8_t*)d_rev, n_reads, n_bases,
+        (uint64_t*)d_begin, (uint64_t*)d_end, res, (hipStream_t)hip_stream);
+    const bool bad_offsets = res[dev::RT_BAD_AT] == ~0ull;
+    out[0] = res[dev::RT_KEPT_BASES];
+    out[1] = res[dev::RT_LOST_READS];
+    out[2] = bad_offsets ? 0 : res[dev::RT_BAD_AT];
+    out[3] = 0;
+    if (bad_offsets) throw Error(DRPRG_EINVAL, "read trimming: the offsets do not ascend to n_bases (or a read is longer than 2^31 bases)");
+    if (res[dev::RT_BAD_AT]) throw Error(DRPRG_EFORMAT, "a base quality outside 0..93 at quality byte " + std::to_string(res[dev::RT_BAD_AT] - 1));
     API_END(ctx)
 }
 
@@ -1039,6 +1095,7 @@ int drprg_hip_reset(drprg_hip_ctx* ctx)
     ctx->dedup_n = 0;
     ctx->dedup_flags.clear();
     ctx->filter_counts = Mapper::FilterOutcome(); // (the settings stay, as the depth cap does)
+    ctx->trim_counts = Mapper::TrimOutcome();
     API_END(ctx)
 }
 
@@ -1284,6 +1341,9 @@ int drprg_hip_discover_reads(drprg_hip_ctx* ctx, const char* reads_path, const c
     ResidentReads resident;
     ctx->last_discover_resident = reads_resident(ctx, reads_path);
     // (the pass over the file knows nothing of the read filter: rather than pile up reads the mapping never saw, say so)
+    if (!ctx->last_discover_resident && ctx->trim_counts.reads_lost_base)
+        throw Error(DRPRG_ENODATA, "discover: read trimming cut bases off reads of this sample and the trimmed reads are not resident in device memory; a pass "
+                                   "over the file would pile up untrimmed reads (raise DRPRG_HIP_KEEP_READS_GB, or trim the file first)");
     if (!ctx->last_discover_resident && ctx->filter_counts.reads_kept != ctx->filter_counts.reads_seen)
         throw Error(DRPRG_ENODATA, "discover: the read filter dropped reads of this sample and the kept reads are not resident in device memory; a pass over "
                                    "the file would see the unfiltered reads (drprg_hip_keep_reads before drprg_hip_map_fastx; the executables take the limit "

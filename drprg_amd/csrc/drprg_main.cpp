@@ -109,6 +109,11 @@ void usage()
         "              [-f MAF] [-d MIN_COVG] [-D MAX_COVG] [-b MIN_STRAND_BIAS] [-g MIN_GT_CONF] [-L MAX_INDEL] [-K MIN_FRS]\n"
         "              [-C MIN_CLUSTER_SIZE] [--debug] [-v] [-t THREADS] [--rebuild-index] [--subsample-covg D [--seed S]]\n"
         "              [--dedup] [--min-read-len L] [--max-read-len L] [--min-read-qual Q]\n"
+        "              [--trim-front N] [--trim-tail N] [--trim-qual Q [--trim-window W]]\n"
+        "--trim-front N, --trim-tail N, --trim-qual Q, --trim-window W: every read loses N bases at its start and N at its end and, under\n"
+        "              --trim-qual (a decimal Phred value in (0, 93]), what lies outside its first and last window of W bases (1..32, default\n"
+        "              4) whose MEAN PHRED VALUE is at least Q, then end bases below Q -- on the device, in front of the read filter and\n"
+        "              everything else; --trim-qual needs qualities (FASTQ, or BAM records that hold them).\n"
         "--min-read-len L, --max-read-len L, --min-read-qual Q: reads shorter than L, longer than L or of a mean quality below Q (a decimal\n"
         "              Phred value; the mean of the error probabilities, as nanoq and chopper take it) are dropped on the device before\n"
         "              anything else sees them; --min-read-qual needs qualities (FASTQ, or BAM records that hold them).\n"
@@ -159,6 +164,8 @@ int main(int argc, char** argv)
     uint64_t seed = 1;
     uint64_t min_read_len = 0, max_read_len = 0; // the read filter (include/drprg_hip.h "read filter"); 0 = not set
     uint32_t min_read_qual_milli = 0;
+    uint64_t trim_front = 0, trim_tail = 0; // read trimming (include/drprg_hip.h "read trimming"); 0 = not set
+    uint32_t trim_qual_milli = 0, trim_window = 0;
     uint32_t min_cluster = 10;
     drprg_hip_annotate_opts ao {};
     ao.min_covg = 3;
@@ -224,11 +231,32 @@ int main(int argc, char** argv)
             if (end == v || *end || !(q >= 0) || q > 93) die(std::string("--min-read-qual needs a mean quality between 0 and 93, not ") + v, 2);
             min_read_qual_milli = (uint32_t)(q * 1000.0 + 0.5);
         }
+        else if (a == "--trim-front" || a == "--trim-tail") {
+            char* end = nullptr;
+            const char* v = need(i);
+            const uint64_t n = std::strtoull(v, &end, 10);
+            if (end == v || *end || *v == '-') die(a + " needs a number of bases, not " + v, 2);
+            (a == "--trim-front" ? trim_front : trim_tail) = n;
+        } else if (a == "--trim-qual") {
+            char* end = nullptr;
+            const char* v = need(i);
+            const double q = std::strtod(v, &end);
+            if (end == v || *end || !(q > 0) || q > 93) die(std::string("--trim-qual needs a quality above 0 and at most 93, not ") + v, 2);
+            trim_qual_milli = (uint32_t)(q * 1000.0 + 0.5);
+            if (!trim_qual_milli) die(std::string("--trim-qual needs a quality of at least 0.001, not ") + v, 2);
+        } else if (a == "--trim-window") {
+            char* end = nullptr;
+            const char* v = need(i);
+            const uint64_t n = std::strtoull(v, &end, 10);
+            if (end == v || *end || n < 1 || n > 32) die(std::string("--trim-window needs a window of 1 to 32 bases, not ") + v, 2);
+            trim_window = (uint32_t)n;
+        }
         else if (a == "-h" || a == "--help") { usage(); return 0; }
         else die("unknown option " + a, 2);
     }
     if (seed_given && !subsample) die("--seed belongs to --subsample-covg", 2);
     if (max_read_len && max_read_len < min_read_len) die("--max-read-len is below --min-read-len: no read can pass", 2);
+    if (trim_window && !trim_qual_milli) die("--trim-window belongs to --trim-qual", 2);
     if (index.empty() || input.empty()) {
         usage();
         return 2;
@@ -281,6 +309,7 @@ int main(int argc, char** argv)
     drprg_hip_set_threads(ctx, threads);
     drprg_hip_set_input_format(ctx, packed_input()); // the parser threads pack the reads to 2 bits (DRPRG_HIP_INPUT=ascii: one byte per base)
     if (int rc = drprg_hip_set_read_filter(ctx, min_read_len, max_read_len, min_read_qual_milli)) die(drprg_hip_last_error(ctx), -rc);
+    if (int rc = drprg_hip_set_read_trim(ctx, trim_front, trim_tail, trim_qual_milli, trim_window)) die(drprg_hip_last_error(ctx), -rc);
     // The reads stay in HBM after the mapping pass (up to DRPRG_HIP_KEEP_READS_GB per device, default 32, 0 = off): discover takes
     // the few reads it needs from there and a novel variant maps them again from there -- the file is read once.
     double keep_gb = 32;
@@ -295,6 +324,14 @@ int main(int argc, char** argv)
     // discover + map share ONE pass over the reads (the reference runs two, /root/reference/src/predict.rs:248-302)
     if (int rc = drprg_hip_map_fastx(ctx, input.c_str())) die(drprg_hip_last_error(ctx), -rc);
     if (verbose) std::fprintf(stderr, "[drprg-hip +%.3fs] reads mapped\n", since_start());
+    if (verbose && (trim_front || trim_tail || trim_qual_milli)) {
+        uint64_t ti[8] = {};
+        if (drprg_hip_read_trim_info(ctx, ti) == 0)
+            std::fprintf(stderr, "[drprg-hip +%.3fs] read trimming: reads_seen=%llu bases_seen=%llu reads_lost_base=%llu cut_front=%llu cut_tail=%llu "
+                                 "qual_cut_front=%llu qual_cut_tail=%llu reads_emptied=%llu\n", since_start(), (unsigned long long)ti[0], (unsigned long long)ti[1],
+                (unsigned long long)ti[2], (unsigned long long)ti[3], (unsigned long long)ti[4], (unsigned long long)ti[5], (unsigned long long)ti[6],
+                (unsigned long long)ti[7]);
+    }
     if (verbose && (min_read_len || max_read_len || min_read_qual_milli)) {
         uint64_t fi[8] = {};
         if (drprg_hip_read_filter_info(ctx, fi) == 0)
@@ -350,6 +387,7 @@ int main(int argc, char** argv)
                 drprg_hip_set_threads(next, threads);
                 drprg_hip_set_input_format(next, packed_input()); // the parser threads pack the reads to 2 bits (DRPRG_HIP_INPUT=ascii: one byte per base)
                 if (int rc = drprg_hip_set_read_filter(next, min_read_len, max_read_len, min_read_qual_milli)) die(drprg_hip_last_error(next), -rc);
+                if (int rc = drprg_hip_set_read_trim(next, trim_front, trim_tail, trim_qual_milli, trim_window)) die(drprg_hip_last_error(next), -rc);
                 // the reads again, against the updated index: from HBM if the first context kept them all, else from the file
                 const int from_hbm = drprg_hip_map_resident(next, ctx);
                 if (from_hbm != 0 && from_hbm != -61 /* ENODATA */) die(drprg_hip_last_error(next), -from_hbm);

@@ -264,9 +264,9 @@ struct Shared {
 };
 
 // IngestHooks::want_qual and a read that has bases but no qualities
-[[noreturn]] void no_qualities(const char* what)
+[[noreturn]] void no_qualities(const char* flag, const char* what)
 {
-    throw Error(DRPRG_EINVAL, std::string("--min-read-qual: ") + what + " has no base qualities; a read is never kept or dropped by a quality threshold it cannot be held against");
+    throw Error(DRPRG_EINVAL, std::string(flag) + ": " + what + " has no base qualities; a read is never kept or dropped by a quality threshold it cannot be held against");
 }
 
 inline const char* find_nl(const char* p, const char* e) { return p < e ? (const char*)memchr(p, '\n', (size_t)(e - p)) : nullptr; }
@@ -421,7 +421,7 @@ void parse_slice(const char* p, const char* e, bool fastq, Block& blk, Shared& s
                 blk.append(cursor, (size_t)(stop - cursor));
                 cursor = next;
             }
-            if (blk.qual && blk.n_bases != before) no_qualities("a FASTA record");
+            if (blk.qual && blk.n_bases != before) no_qualities(sh.hooks.qual_flag, "a FASTA record");
             blk.offsets[++blk.n_reads] = blk.n_bases;
             p = rec_end;
         }
@@ -455,7 +455,7 @@ void parse_bam_slice(const uint8_t* p, const uint8_t* e, Block& blk, Shared& sh)
         if (blk.n_bases + len > blk.flush_at || blk.n_reads + 1 > BLOCK_READS) sh.submit(blk);
         if (blk.qual && len) {
             const uint8_t* q = r.seq + (len + 1) / 2; // (parse_record has checked that the record holds l_seq bytes behind the sequence)
-            if (q[0] == 0xFF) no_qualities("a BAM record (its QUAL field starts with 0xFF)");
+            if (q[0] == 0xFF) no_qualities(sh.hooks.qual_flag, "a BAM record (its QUAL field starts with 0xFF)");
             blk.put_qual(blk.n_bases, q, len);
         }
         if (blk.bam) {

@@ -50,6 +50,7 @@ struct IngestHooks {
     // bases without looking at the bytes.  A read of one base or more that has none -- a FASTA record, a BAM record whose QUAL field starts
     // with 0xFF -- ends the call with DRPRG_EINVAL.  false: nothing about the ingest changes, no quality byte is parsed, copied or moved.
     bool want_qual = false;
+    const char* qual_flag = "--min-read-qual"; // the setting that asked for the qualities: named in that error (the read filter's, or --trim-qual)
 };
 
 struct IngestStats {

@@ -444,6 +444,61 @@ uint32_t read_qual_tiles(uint64_t n_bases);
 // timer: around read_qual_kernel alone
 hipError_t launch_read_filter(const ReadFilterArgs& a, hipStream_t stream, KernelTimer timer = {});
 
+// read_trim.hip: read trimming (the rule: include/drprg_hip.h "read trimming").  begin[i], end[i]: the kept range of read i in read
+// orientation ([0, 0) when empty), klen[i] its length, noff the exclusive scan of klen (n_reads + 1 entries each, entry n_reads of noff
+// the kept bases).  qual (n_bases + 64 bytes readable when 16-byte aligned; bias 33 or 0), first and last (u32[n_reads], scratch) are
+// touched only when qual_milli != 0; window is 1..32 then.  rev: u8[n_reads], non-zero where the quality bytes are stored mirrored, or
+// null.  work: ten device words; out: nine words the device can write, indexed by RT_*; temp: read_trim_temp_bytes(n_reads) bytes.
+// 1 <= n_reads <= MAX_BATCH_READS.
+enum {
+    RT_KEPT_BASES = 0, RT_LOST_READS = 1, RT_CUT_FRONT = 2, RT_CUT_TAIL = 3, RT_QCUT_FRONT = 4, RT_QCUT_TAIL = 5, RT_EMPTIED = 6,
+    RT_BAD_AT = 7 /* first bad quality byte + 1, 0, or ~0: offsets at odds with n_bases */, RT_KEPT_NPOS = 8 /* out only */, RT_OFFSETS = 9 /* work only */
+};
+struct ReadTrimArgs {
+    const uint8_t* qual;
+    uint32_t bias;
+    const uint64_t* offsets;
+    const uint8_t* rev;
+    uint64_t n_reads, n_bases;
+    uint64_t front, tail;
+    uint32_t qual_milli, window;
+    uint32_t *first, *last;
+    uint64_t *begin, *end, *klen, *noff;
+    unsigned long long *work, *out;
+    void* temp;
+    size_t temp_bytes;
+};
+// the block's listed non-ACGT positions (n_npos == 0: none, nothing else is looked at).  chunk_count / chunk_prefix:
+// read_trim_npos_chunks(n_npos) + 1 words each; temp: scan_temp_bytes of as many.  launch_read_trim leaves the number of positions inside
+// kept ranges in out[RT_KEPT_NPOS] and the scan in chunk_prefix, which launch_read_trim_npos_emit reads.
+struct ReadTrimNpos {
+    const uint64_t* npos;
+    uint64_t n_npos;
+    uint32_t *chunk_count, *chunk_prefix;
+    void* temp;
+    size_t temp_bytes;
+};
+// what the compaction kernels take: src_start[n_reads] for launch_subsample_pack, btable[n_reads] (from `bases`) and qtable[n_reads] (from
+// `qual`, stored order) for launch_gather_reads; each may be null.  *err (zeroed by the caller) is set when the ranges, the scan and the
+// offsets do not fit each other; such an entry copies nothing.
+struct ReadTrimFill {
+    const uint64_t* offsets;
+    const uint8_t* rev;
+    const uint64_t *begin, *end, *noff;
+    uint64_t n_reads, n_bases, new_bases;
+    const uint8_t *bases, *qual;
+    uint64_t* src_start;
+    GatherEntry *btable, *qtable;
+    uint32_t* err;
+};
+size_t read_trim_temp_bytes(uint64_t n_reads);
+uint32_t read_trim_tiles(uint64_t n_bases);
+uint32_t read_trim_npos_chunks(uint64_t n_npos);
+// timer: around trim_points_kernel alone
+hipError_t launch_read_trim(const ReadTrimArgs& a, const ReadTrimNpos& np, hipStream_t stream, KernelTimer timer = {});
+hipError_t launch_read_trim_fill(const ReadTrimFill& f, hipStream_t stream);
+hipError_t launch_read_trim_npos_emit(const ReadTrimFill& f, const ReadTrimNpos& np, uint64_t* out, uint64_t out_cap, hipStream_t stream);
+
 // anchor_scan.hip: reads of a resident batch that hold one of the (sorted) anchor k-mers of length A -- every such read once,
 // in any order, appended to `list` (count keeps counting past list_cap).  prefilter: 2^16 bits, bit (kmer & 0xFFFF) set for every
 // anchor; flags: n_reads words, zero before the launch.

@@ -1554,6 +1554,64 @@ void Mapper::read_filter_device(const ReadFilter& f, const uint8_t* d_qual, uint
     for (int i = 0; i < 8; ++i) res[i] = fs.h_out[i];
 }
 
+// ---- read trimming -------------------------------------------------------------------------------------------------------------------
+void Mapper::ensure_trim_scratch(FilterScratch& fs, uint64_t n_reads, uint64_t n_npos, bool use_qual, bool own_ranges)
+{
+    auto room = [&](auto& buf, uint64_t need) {
+        if (need <= buf.size()) return;
+        sync(); // (as ensure_stage: freeing device memory waits for the device)
+        buf.alloc(need + need / 4);
+    };
+    if (use_qual) {
+        room(fs.t_first, n_reads);
+        room(fs.t_last, n_reads);
+    }
+    if (own_ranges) {
+        room(fs.t_begin, n_reads);
+        room(fs.t_end, n_reads);
+    }
+    room(fs.t_klen, n_reads + 1);
+    room(fs.t_offsets, n_reads + 1);
+    room(fs.t_temp, dev::read_trim_temp_bytes(n_reads));
+    if (n_npos) {
+        const uint64_t chunks = (uint64_t)dev::read_trim_npos_chunks(n_npos) + 1;
+        room(fs.t_count, chunks);
+        room(fs.t_prefix, chunks);
+        room(fs.t_ntemp, dev::scan_temp_bytes((uint32_t)chunks));
+    }
+    if (!fs.t_work) fs.t_work.alloc(10);
+    if (!fs.t_out) fs.t_out.alloc(9);
+}
+
+void Mapper::run_read_trim(FilterScratch& fs, const ReadFilter& f, const uint8_t* d_qual, uint32_t bias, const uint64_t* d_offsets, const uint8_t* d_rev,
+    uint64_t n_reads, uint64_t n_bases, uint64_t* d_begin, uint64_t* d_end, const uint64_t* d_npos, uint64_t n_npos, hipStream_t stream)
+{
+    dev::ReadTrimArgs a {};
+    a.qual = d_qual; a.bias = bias; a.offsets = d_offsets; a.rev = d_rev; a.n_reads = n_reads; a.n_bases = n_bases;
+    a.front = f.trim_front; a.tail = f.trim_tail; a.qual_milli = f.trim_qual_milli; a.window = f.trim_window;
+    a.first = fs.t_first.data(); a.last = fs.t_last.data(); a.begin = d_begin; a.end = d_end; a.klen = fs.t_klen.data(); a.noff = fs.t_offsets.data();
+    a.work = fs.t_work.data(); a.out = fs.t_out.device_ptr(); a.temp = fs.t_temp.data(); a.temp_bytes = fs.t_temp.size();
+    dev::ReadTrimNpos np {};
+    if (n_npos) np = dev::ReadTrimNpos { d_npos, n_npos, fs.t_count.data(), fs.t_prefix.data(), fs.t_ntemp.data(), fs.t_ntemp.size() };
+    HIPCHK(dev::launch_read_trim(a, np, stream));
+}
+
+void Mapper::read_trim_device(const ReadFilter& f, const uint8_t* d_qual, uint32_t bias, const uint64_t* d_offsets, const uint8_t* d_rev, uint64_t n_reads,
+    uint64_t n_bases, uint64_t* d_begin, uint64_t* d_end, uint64_t res[9], hipStream_t stream)
+{
+    for (int i = 0; i < 9; ++i) res[i] = 0;
+    if (n_reads == 0) return;
+    HIPCHK(hipSetDevice(device_));
+    if (!stream) stream = stream_;
+    if (!d_offsets || !d_begin || !d_end || (f.trim_qual_milli && n_bases && !d_qual)) throw Error(DRPRG_EINVAL, "null device pointer");
+    if (n_reads > dev::MAX_BATCH_READS) throw Error(DRPRG_EOVERFLOW, "at most " + std::to_string(dev::MAX_BATCH_READS) + " reads per batch");
+    FilterScratch& fs = filter_api_;
+    ensure_trim_scratch(fs, n_reads, 0, f.trim_qual_milli != 0, false);
+    run_read_trim(fs, f, d_qual, bias, d_offsets, d_rev, n_reads, n_bases, d_begin, d_end, nullptr, 0, stream);
+    HIPCHK(hipStreamSynchronize(stream));
+    for (int i = 0; i < 9; ++i) res[i] = fs.t_out[i];
+}
+
 void Mapper::map_host_filtered(const HostBatch& hb, const ReadFilter& f, uint64_t cap_need, FilterOutcome& o)
 {
     o = FilterOutcome {};
@@ -1561,7 +1619,7 @@ void Mapper::map_host_filtered(const HostBatch& hb, const ReadFilter& f, uint64_
     if (n_reads == 0) return;
     HIPCHK(hipSetDevice(device_));
     if (hb.offsets[0] != 0) throw Error(DRPRG_EINVAL, "offsets[0] must be 0");
-    const uint64_t n_bases = hb.n_bases();
+    uint64_t n_bases = hb.n_bases(); // (of the block as it goes on: the trimmed block's, once the trim stage has replaced it)
     o.reads_seen = n_reads;
     o.bases_seen = n_bases;
     bool keeping = kept_cap_ && !kept_broken_;
@@ -1572,6 +1630,7 @@ void Mapper::map_host_filtered(const HostBatch& hb, const ReadFilter& f, uint64_
         if (keeping) kept_seen_ += o.reads_kept;
         return;
     }
+    if (f.trim_qual_milli && !hb.qual) throw Error(DRPRG_EINVAL, "--trim-qual: the reads came without base qualities");
     if (f.use_qual() && !hb.qual) throw Error(DRPRG_EINVAL, "--min-read-qual: the reads came without base qualities");
     if (n_reads > dev::MAX_BATCH_READS) throw Error(DRPRG_EOVERFLOW, "at most " + std::to_string(dev::MAX_BATCH_READS) + " reads per batch");
     if (!copy_stream_) copy_stream_.create();
@@ -1581,17 +1640,85 @@ void Mapper::map_host_filtered(const HostBatch& hb, const ReadFilter& f, uint64_
     stage_next_ ^= 1;
     if (!st.copied) st.copied.create(false);
     FilterScratch& fs = st.filt;
-    const uint64_t n_npos = hb.packed || hb.bam ? hb.n_npos : 0;
+    uint64_t n_npos = hb.packed || hb.bam ? hb.n_npos : 0;
     ensure_stage(st, hb.payload_bytes(), n_reads, n_npos);
-    ensure_filter_scratch(fs, n_reads, f.use_qual() ? n_bases : 0, true, f.use_qual());
-    const DeviceBatch src = hb.bam ? copy_in_bam(hb, st, st.d_bases.data(), st.d_offsets.data(), st.d_npos.data(), cs, cs)
-                                   : copy_in(hb, st.d_bases.data(), st.d_offsets.data(), st.d_npos.data(), cs);
-    if (f.use_qual()) {
+    ensure_filter_scratch(fs, n_reads, f.wants_qual() ? n_bases : 0, true, f.use_qual());
+    if (f.trims()) ensure_trim_scratch(fs, n_reads, n_npos, f.trim_qual_milli != 0, true);
+    DeviceBatch src = hb.bam ? copy_in_bam(hb, st, st.d_bases.data(), st.d_offsets.data(), st.d_npos.data(), cs, cs)
+                             : copy_in(hb, st.d_bases.data(), st.d_offsets.data(), st.d_npos.data(), cs);
+    if (f.wants_qual()) {
         HIPCHK(hipMemcpyAsync(fs.d_qual.data(), hb.qual, n_bases, hipMemcpyHostToDevice, cs));
         HIPCHK(hipMemsetAsync(fs.d_qual.data() + n_bases, 0, 64, cs));
     }
-    run_read_filter(fs, f, fs.d_qual.data(), hb.qual_bias, src.d_offsets, n_reads, n_bases, fs.d_qsum.data(), fs.d_flag.data(), cs);
+    const uint8_t* d_q = fs.d_qual.data();
+    uint32_t trim_err = 0;
+    if (f.trims()) {
+        // The trim stage: the kept range of every read, the new offsets and the counts, one read-back; a block that lost a base is compacted
+        // into the set's t_* buffers (launch_subsample_pack for words, launch_gather_reads for text and for the quality bytes) and `src`
+        // and the quality pointer are REPLACED: the filter, the depth cut, the compaction and keep_reads below see a block of trimmed reads.
+        const uint8_t* d_rev = hb.bam && hb.reverse ? st.d_reverse.data() : nullptr; // (BAM: QUAL stays in stored order; the bases were reversed by bam_pack_kernel)
+        run_read_trim(fs, f, d_q, hb.qual_bias, src.d_offsets, d_rev, n_reads, n_bases, fs.t_begin.data(), fs.t_end.data(), src.d_npos, src.n_npos, cs);
+        HIPCHK(hipStreamSynchronize(cs)); // the trim's read-back: the trimmed sizes are known before the filter is launched
+        const unsigned long long* t = fs.t_out.data();
+        if (t[dev::RT_BAD_AT] == ~0ull) throw Error(DRPRG_EINVAL, "read trimming: the block's offsets do not ascend to its number of bases");
+        if (t[dev::RT_BAD_AT])
+            throw Error(DRPRG_EFORMAT, "a base quality outside 0..93 (quality byte " + std::to_string(t[dev::RT_BAD_AT] - 1) + " of an ingest block of "
+                    + std::to_string(n_bases) + " bases, " + (hb.qual_bias ? "FASTQ: bytes 33..126" : "BAM: bytes 0..93") + ")");
+        o.trim.reads_seen = n_reads; o.trim.bases_seen = n_bases; o.trim.reads_lost_base = t[dev::RT_LOST_READS];
+        o.trim.cut_front = t[dev::RT_CUT_FRONT]; o.trim.cut_tail = t[dev::RT_CUT_TAIL]; o.trim.qcut_front = t[dev::RT_QCUT_FRONT];
+        o.trim.qcut_tail = t[dev::RT_QCUT_TAIL]; o.trim.emptied = t[dev::RT_EMPTIED];
+        if (t[dev::RT_LOST_READS]) {
+            const uint64_t nb = t[dev::RT_KEPT_BASES], n_list = src.n_npos ? t[dev::RT_KEPT_NPOS] : 0;
+            o.bases_seen = nb;
+            if (nb == 0) { // every base of the block is gone: reads of no bases, nothing to map; the set is handed back (see below)
+                stage_next_ ^= 1;
+                o.dropped_short = f.min_len ? n_reads : 0;
+                o.reads_kept = o.mapped_reads = n_reads - o.dropped_short;
+                tot_reads_ += o.reads_kept;
+                if (keeping) kept_seen_ += o.reads_kept;
+                return;
+            }
+            const uint64_t payload = src.packed ? (nb + 15) / 16 * 4 : nb;
+            auto room = [&](auto& buf, uint64_t need) {
+                if (need <= buf.size()) return;
+                sync();
+                buf.alloc(need + need / 4);
+            };
+            room(fs.t_bases, payload + 64);
+            if (n_list) room(fs.t_npos, n_list);
+            if (f.use_qual()) room(fs.t_qual, nb + 64);
+            if (src.packed) room(fs.t_src, n_reads);
+            if (!src.packed) room(fs.t_btable, n_reads);
+            if (f.use_qual()) room(fs.t_qtable, n_reads);
+            uint32_t* const d_err = reinterpret_cast<uint32_t*>(fs.t_work.data() + dev::RT_KEPT_NPOS); // (zeroed with the trim's words, unused on the device)
+            dev::ReadTrimFill tf { src.d_offsets, d_rev, fs.t_begin.data(), fs.t_end.data(), fs.t_offsets.data(), n_reads, n_bases, nb, src.d_bases, d_q,
+                src.packed ? fs.t_src.data() : nullptr, src.packed ? nullptr : fs.t_btable.data(), f.use_qual() ? fs.t_qtable.data() : nullptr, d_err };
+            HIPCHK(dev::launch_read_trim_fill(tf, cs));
+            HIPCHK(hipMemsetAsync(fs.t_bases.data() + payload, 0, 64, cs));
+            if (src.packed) {
+                const dev::SubsampleBlock sb { src.d_bases, src.d_offsets, n_reads, n_bases, 0, nullptr, nullptr, nullptr, n_reads, nb };
+                HIPCHK(dev::launch_subsample_pack(sb, fs.t_offsets.data(), fs.t_src.data(), reinterpret_cast<uint32_t*>(fs.t_bases.data()), d_err, cs));
+                if (n_list) {
+                    const dev::ReadTrimNpos np { src.d_npos, src.n_npos, fs.t_count.data(), fs.t_prefix.data(), fs.t_ntemp.data(), fs.t_ntemp.size() };
+                    HIPCHK(dev::launch_read_trim_npos_emit(tf, np, fs.t_npos.data(), n_list, cs));
+                }
+            } else HIPCHK(dev::launch_gather_reads(fs.t_btable.data(), (uint32_t)n_reads, fs.t_bases.data(), cs));
+            if (f.use_qual()) {
+                HIPCHK(dev::launch_gather_reads(fs.t_qtable.data(), (uint32_t)n_reads, fs.t_qual.data(), cs));
+                HIPCHK(hipMemsetAsync(fs.t_qual.data() + nb, 0, 64, cs));
+                d_q = fs.t_qual.data();
+            }
+            HIPCHK(hipMemcpyAsync(&trim_err, d_err, sizeof trim_err, hipMemcpyDeviceToHost, cs)); // (queued behind the compaction; waited for with the filter's read-back)
+            src.d_bases = fs.t_bases.data();
+            src.d_offsets = fs.t_offsets.data();
+            src.n_bases = n_bases = nb;
+            src.d_npos = n_list ? fs.t_npos.data() : nullptr;
+            src.n_npos = n_npos = n_list;
+        }
+    }
+    run_read_filter(fs, f, d_q, hb.qual_bias, src.d_offsets, n_reads, n_bases, fs.d_qsum.data(), fs.d_flag.data(), cs);
     HIPCHK(hipStreamSynchronize(cs)); // the caller's block is free again; the filter's read-back is here
+    if (trim_err) throw Error(DRPRG_EIO, "read trimming: the block's offsets and the trimmed ranges do not fit each other");
     const unsigned long long* h = fs.h_out.data();
     if (h[dev::RF_OFFSETS]) throw Error(DRPRG_EINVAL, "read filter: the block's offsets do not ascend to its number of bases");
     if (h[dev::RF_BAD_AT])

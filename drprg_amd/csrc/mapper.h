@@ -107,13 +107,24 @@ public:
     void map_host_async(const HostBatch& b);
     // The read filter (the rule: include/drprg_hip.h "read filter"; read_qual.hip).  T: the rule's threshold for min_qual_milli
     // (dev::rq_threshold), 0 when there is no quality test.
+    // Read trimming (the rule: include/drprg_hip.h "read trimming"; read_trim.hip) rides in the same settings: it runs in front of the
+    // filter, on the same block.  trim_window is 1..32 whenever trim_qual_milli != 0.
     struct ReadFilter {
         uint64_t min_len = 0, max_len = 0, T = 0;
         uint32_t min_qual_milli = 0;
-        bool any() const { return min_len || max_len || min_qual_milli; }
+        uint64_t trim_front = 0, trim_tail = 0;
+        uint32_t trim_qual_milli = 0, trim_window = 0;
+        bool filters() const { return min_len || max_len || min_qual_milli; }
+        bool trims() const { return trim_front || trim_tail || trim_qual_milli; }
+        bool any() const { return filters() || trims(); }
         bool use_qual() const { return min_qual_milli != 0; }
+        bool wants_qual() const { return min_qual_milli != 0 || trim_qual_milli != 0; } // the ingest carries quality bytes
+    };
+    struct TrimOutcome { // drprg_hip_read_trim_info
+        uint64_t reads_seen = 0, bases_seen = 0, reads_lost_base = 0, cut_front = 0, cut_tail = 0, qcut_front = 0, qcut_tail = 0, emptied = 0;
     };
     struct FilterOutcome {
+        TrimOutcome trim; // (all zero when nothing trims)
         uint64_t reads_seen = 0, bases_seen = 0, dropped_short = 0, dropped_long = 0, dropped_lowq = 0, reads_kept = 0, bases_kept = 0;
         uint64_t mapped_reads = 0, mapped_bases = 0; // what was mapped: the kept reads, or those of them in front of the depth cap
         uint64_t cut_dropped = 0;                    // kept reads behind the depth cap
@@ -131,6 +142,11 @@ public:
     // address is read byte by byte).  Synchronises `stream`.
     void read_filter_device(const ReadFilter& f, const uint8_t* d_qual, uint32_t bias, const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases,
         unsigned long long* d_sums, uint8_t* d_flags, uint64_t res[8], hipStream_t stream);
+    // The trim kernels alone on the caller's device buffers (drprg_hip_read_trim_device): d_begin / d_end receive every read's kept range in
+    // read orientation; d_rev: one byte per read (non-zero: the quality bytes are stored mirrored) or null; d_qual may be null without a
+    // quality threshold, and must be readable for 64 bytes behind n_bases when it is 16-byte aligned.  res[0..8]: dev::RT_*.  Synchronises `stream`.
+    void read_trim_device(const ReadFilter& f, const uint8_t* d_qual, uint32_t bias, const uint64_t* d_offsets, const uint8_t* d_rev, uint64_t n_reads,
+        uint64_t n_bases, uint64_t* d_begin, uint64_t* d_end, uint64_t res[9], hipStream_t stream);
     // Reads that stay in HBM (off by default).  keep_reads(max_bytes > 0): from now on map_host_async copies every block into
     // device memory of its own instead of a staging set and leaves it there -- at most max_bytes of it; one byte more and
     // everything kept is dropped and the staging sets are back.  kept_complete(): every read mapped since keep_reads() /
@@ -382,6 +398,16 @@ private:
         DeviceBuffer<unsigned char> d_ntemp;
         DeviceBuffer<uint8_t> c_bases;
         DeviceBuffer<uint64_t> c_offsets, c_npos;
+        // read trimming: the per-read words of read_trim.hip, and the trimmed block (bases or words, offsets, positions, qualities) that a
+        // block which lost a base is replaced by before the filter sees it
+        DeviceBuffer<uint32_t> t_first, t_last, t_count, t_prefix;
+        DeviceBuffer<uint64_t> t_begin, t_end, t_klen, t_src;
+        DeviceBuffer<unsigned long long> t_work;
+        DeviceBuffer<unsigned char> t_temp, t_ntemp;
+        DeviceBuffer<dev::GatherEntry> t_btable, t_qtable;
+        PinnedBuffer<unsigned long long> t_out;
+        DeviceBuffer<uint8_t> t_bases, t_qual;
+        DeviceBuffer<uint64_t> t_offsets, t_npos;
     };
     struct Stage {
         FilterScratch filt;
@@ -402,7 +428,12 @@ private:
     // queues the filter on `stream`; fs.h_out holds dev::RF_* once the stream has been waited for
     void run_read_filter(FilterScratch& fs, const ReadFilter& f, const uint8_t* d_qual, uint32_t bias, const uint64_t* d_offsets, uint64_t n_reads,
         uint64_t n_bases, unsigned long long* d_sums, uint8_t* d_flags, hipStream_t stream);
-    FilterScratch filter_api_; // read_filter_device's own (as bam_api_)
+    // room for the trim kernels over n_reads reads (own_ranges: the caller brings no begin / end arrays)
+    void ensure_trim_scratch(FilterScratch& fs, uint64_t n_reads, uint64_t n_npos, bool use_qual, bool own_ranges);
+    // queues the trim kernels on `stream`; fs.t_out holds dev::RT_* once the stream has been waited for, fs.t_offsets the new offsets
+    void run_read_trim(FilterScratch& fs, const ReadFilter& f, const uint8_t* d_qual, uint32_t bias, const uint64_t* d_offsets, const uint8_t* d_rev,
+        uint64_t n_reads, uint64_t n_bases, uint64_t* d_begin, uint64_t* d_end, const uint64_t* d_npos, uint64_t n_npos, hipStream_t stream);
+    FilterScratch filter_api_; // read_filter_device's and read_trim_device's own (as bam_api_)
     BamScratch bam_api_; // pack_bam_on_device's own (the caller's stream is not ordered with the context's)
     uint64_t bam_blocks_ = 0;
     // room in `st` for a batch of these sizes (n_npos: 0 for an ASCII batch)

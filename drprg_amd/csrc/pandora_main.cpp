@@ -8,6 +8,7 @@
 // and, this build's own, --subsample-covg D [--seed S] on map and discover (include/drprg_hip.h "random subsample"), --dedup on both
 // (include/drprg_hip.h "duplicate reads"),
 // --min-read-len L, --max-read-len L and --min-read-qual Q on both (include/drprg_hip.h "read filter"),
+// --trim-front N, --trim-tail N, --trim-qual Q and --trim-window W on both (include/drprg_hip.h "read trimming"),
 // and writes the files drprg then looks for: <prg>.k<K>.w<W>.idx + kmer_prgs/ (index),
 // <dir>/denovo_paths.txt (discover, /root/reference/src/lib.rs:569-577),
 // <out>/pandora_genotyped.vcf (map, /root/reference/src/lib.rs:644-646).
@@ -54,6 +55,9 @@ struct Args {
     // --min-read-len L, --max-read-len L, --min-read-qual Q: the read filter (include/drprg_hip.h "read filter"); 0 = not set
     uint64_t min_read_len = 0, max_read_len = 0;
     uint32_t min_read_qual_milli = 0;
+    // --trim-front N, --trim-tail N, --trim-qual Q, --trim-window W: read trimming (include/drprg_hip.h "read trimming"); 0 = not set
+    uint64_t trim_front = 0, trim_tail = 0;
+    uint32_t trim_qual_milli = 0, trim_window = 0;
     std::string outdir = "pandora", vcf_refs;
     std::vector<std::string> positional;
     int device = 0;
@@ -72,6 +76,7 @@ void usage()
         "  pandora index    [-t N] [-w W] [-k K] <prg>\n"
         "  pandora map      [--genotype] [--local] [--gt-conf X] [-v] [-o DIR] [-g SIZE] [--max-covg N | --subsample-covg D [--seed S]]\n"
         "                   [--dedup] [--min-read-len L] [--max-read-len L] [--min-read-qual Q]\n"
+        "                   [--trim-front N] [--trim-tail N] [--trim-qual Q [--trim-window W]]\n"
         "                   [--vcf-refs FASTA] [-t N] [-w W] [-k K] [-c N] [-I] [-K] [-e RATE] [--max-diff N] <prg> <reads>\n"
         "  pandora discover [same mapping options] <prg> <query.tsv>\n"
         "  --max-covg N: reads are taken in file order up to and including the first one at which (N + 1) x SIZE bases are reached;\n"
@@ -91,8 +96,13 @@ void usage()
         "                Phred value; the mean is that of the error probabilities, as nanoq and chopper take it) are dropped on the device\n"
         "                before anything else sees them: the run is that of a file of the kept reads.  --min-read-qual needs qualities:\n"
         "                FASTA, or a BAM record without them, is an error under it.\n"
+        "  --trim-front N, --trim-tail N, --trim-qual Q, --trim-window W: every read loses N bases at its start and N at its end and, under\n"
+        "                --trim-qual (a decimal Phred value in (0, 93]), what lies outside its first and its last window of W bases (1..32,\n"
+        "                default 4) whose MEAN PHRED VALUE is at least Q, then end bases below Q -- on the device, in front of the read filter\n"
+        "                and everything else: the run is that of a file of the trimmed reads.  A read trimmed to nothing stays a read of no\n"
+        "                bases.  --trim-qual needs qualities: FASTA, or a BAM record without them, is an error under it.\n"
         "  <reads>: FASTA or FASTQ, plain or gzip; or BAM (secondary and supplementary records are skipped, reverse-strand records are\n"
-        "           reverse-complemented, alignments are ignored, qualities are looked at by --min-read-qual alone)\n"
+        "           reverse-complemented, alignments are ignored, qualities are looked at by --min-read-qual and --trim-qual alone)\n"
         "environment: DRPRG_HIP_DEVICE selects the GPU (default 0); DRPRG_HIP_DEVICES=0,1,.. maps on several GPUs of the node\n");
 }
 
@@ -140,6 +150,26 @@ Args parse(int argc, char** argv)
             if (end == v || *end || !(q >= 0) || q > 93) die(std::string("--min-read-qual needs a mean quality between 0 and 93, not ") + v, 2);
             a.min_read_qual_milli = (uint32_t)(q * 1000.0 + 0.5);
         }
+        else if (s == "--trim-front" || s == "--trim-tail") {
+            char* end = nullptr;
+            const char* v = need(i);
+            const uint64_t n = std::strtoull(v, &end, 10);
+            if (end == v || *end || *v == '-') die(s + " needs a number of bases, not " + v, 2);
+            (s == "--trim-front" ? a.trim_front : a.trim_tail) = n;
+        } else if (s == "--trim-qual") {
+            char* end = nullptr;
+            const char* v = need(i);
+            const double q = std::strtod(v, &end);
+            if (end == v || *end || !(q > 0) || q > 93) die(std::string("--trim-qual needs a quality above 0 and at most 93, not ") + v, 2);
+            a.trim_qual_milli = (uint32_t)(q * 1000.0 + 0.5);
+            if (!a.trim_qual_milli) die(std::string("--trim-qual needs a quality of at least 0.001, not ") + v, 2);
+        } else if (s == "--trim-window") {
+            char* end = nullptr;
+            const char* v = need(i);
+            const uint64_t n = std::strtoull(v, &end, 10);
+            if (end == v || *end || n < 1 || n > 32) die(std::string("--trim-window needs a window of 1 to 32 bases, not ") + v, 2);
+            a.trim_window = (uint32_t)n;
+        }
         else if (s == "--dedup") a.dedup = true;
         else if (s == "-o" || s == "--outdir") a.outdir = need(i);
         else if (s == "--vcf-refs") a.vcf_refs = need(i);
@@ -164,6 +194,7 @@ Args parse(int argc, char** argv)
         die("--max-covg and --subsample-covg are alternatives (the prefix cap or the random subsample): give one of them", 2);
     if (a.subsample) a.max_covg = 4294967295ull; // the default cap gives way
     if (a.max_read_len && a.max_read_len < a.min_read_len) die("--max-read-len is below --min-read-len: no read can pass", 2);
+    if (a.trim_window && !a.trim_qual_milli) die("--trim-window belongs to --trim-qual", 2);
     if (const char* d = std::getenv("DRPRG_HIP_DEVICE")) a.device = std::atoi(d);
     return a;
 }
@@ -209,6 +240,7 @@ drprg_hip_ctx* open_ctx(const Args& a)
     if (int rc = drprg_hip_set_opts(ctx, &o)) die(drprg_hip_last_error(ctx), -rc);
     if (int rc = drprg_hip_set_max_covg(ctx, a.max_covg)) die(drprg_hip_last_error(ctx), -rc);
     if (int rc = drprg_hip_set_read_filter(ctx, a.min_read_len, a.max_read_len, a.min_read_qual_milli)) die(drprg_hip_last_error(ctx), -rc);
+    if (int rc = drprg_hip_set_read_trim(ctx, a.trim_front, a.trim_tail, a.trim_qual_milli, a.trim_window)) die(drprg_hip_last_error(ctx), -rc);
     drprg_hip_set_threads(ctx, a.threads);
     drprg_hip_set_input_format(ctx, packed_input()); // the parser threads pack the reads to 2 bits (DRPRG_HIP_INPUT=ascii: one byte per base)
     return ctx;
@@ -253,7 +285,11 @@ std::string run_tag(const Args& a, const std::string& reads)
         + (a.dedup ? std::string("|D") : std::string())
         + (a.min_read_len || a.max_read_len || a.min_read_qual_milli ? "|F" + std::to_string((unsigned long long)a.min_read_len) + "/"
                   + std::to_string((unsigned long long)a.max_read_len) + "/" + std::to_string(a.min_read_qual_milli)
-                                                                     : std::string());
+                                                                     : std::string())
+        + (a.trim_front || a.trim_tail || a.trim_qual_milli ? "|T" + std::to_string((unsigned long long)a.trim_front) + "/"
+                  + std::to_string((unsigned long long)a.trim_tail) + "/" + std::to_string(a.trim_qual_milli) + "/"
+                  + std::to_string(a.trim_qual_milli ? (a.trim_window ? a.trim_window : 4u) : 0u)
+                                                            : std::string());
 }
 
 // The reads stay in HBM after the mapping pass: up to DRPRG_HIP_KEEP_READS_GB per device, default 32, 0 = off.  --subsample-covg and --dedup work on
@@ -313,10 +349,14 @@ void report_bam(drprg_hip_ctx* ctx, const Args& a)
         (unsigned long long)bi[0], (unsigned long long)bi[1], (unsigned long long)bi[2], (unsigned long long)bi[3]);
 }
 
-// -v: what the read filter dropped
+// -v: what the read trimming cut, and what the read filter dropped
 void report_filter(drprg_hip_ctx* ctx, const Args& a)
 {
     uint64_t fi[8] = {};
+    if (a.verbose && (a.trim_front || a.trim_tail || a.trim_qual_milli) && drprg_hip_read_trim_info(ctx, fi) == 0)
+        std::printf("[pandora-hip] read trimming: reads_seen=%llu bases_seen=%llu reads_lost_base=%llu cut_front=%llu cut_tail=%llu qual_cut_front=%llu "
+                    "qual_cut_tail=%llu reads_emptied=%llu\n", (unsigned long long)fi[0], (unsigned long long)fi[1], (unsigned long long)fi[2],
+            (unsigned long long)fi[3], (unsigned long long)fi[4], (unsigned long long)fi[5], (unsigned long long)fi[6], (unsigned long long)fi[7]);
     if (!a.verbose || !(a.min_read_len || a.max_read_len || a.min_read_qual_milli) || drprg_hip_read_filter_info(ctx, fi) != 0) return;
     std::printf("[pandora-hip] read filter: reads_seen=%llu bases_seen=%llu dropped_short=%llu dropped_long=%llu dropped_low_qual=%llu reads_kept=%llu "
                 "bases_kept=%llu (T=%llu)\n", (unsigned long long)fi[0], (unsigned long long)fi[1], (unsigned long long)fi[2], (unsigned long long)fi[3],

@@ -259,6 +259,29 @@ class Context:
         _check(rc, self._h)
         return self.last_filter_out[:3]
 
+    # ---- read trimming (include/drprg_hip.h: drprg_hip_set_read_trim) --------------------------
+    def set_read_trim(self, front=0, tail=0, qual=0, window=0):
+        """from the next map_fastx on, every read loses `front` bases at its start and `tail` at its end, and -- qual != 0, a decimal Phred
+        value -- what lies outside its first and last window of `window` bases (0: 4) with a mean quality of at least qual; the trimmed
+        read is what everything behind the ingest sees; all zero clears the settings"""
+        _check(lib.drprg_hip_set_read_trim(self._h, int(front), int(tail), self.qual_milli(qual), int(window)), self._h)
+
+    def read_trim_info(self):
+        out = (C.c_uint64 * 8)()
+        _check(lib.drprg_hip_read_trim_info(self._h, out), self._h)
+        names = ("reads_seen", "bases_seen", "reads_lost_base", "cut_front", "cut_tail", "qual_cut_front", "qual_cut_tail", "reads_emptied")
+        return dict(zip(names, (int(x) for x in out)))
+
+    def read_trim_device(self, d_qual, qual_bias, d_offsets, d_rev, n_reads, n_bases, d_begin, d_end, stream=None):
+        """the trim kernels alone on device buffers (addresses as integers; d_qual may be None without a quality, d_rev may be None):
+        d_begin / d_end (u64 per read) receive the kept ranges in read orientation; returns (kept bases, reads that lost a base, position + 1
+        of the first quality byte out of range or 0) -- and raises with code -84 when there is such a byte"""
+        out = (C.c_uint64 * 4)()
+        rc = lib.drprg_hip_read_trim_device(self._h, d_qual, int(qual_bias), d_offsets, d_rev, int(n_reads), int(n_bases), d_begin, d_end, out, stream)
+        self.last_trim_out = tuple(int(x) for x in out)
+        _check(rc, self._h)
+        return self.last_trim_out[:3]
+
     def select_reads(self, anchors, A, window_bytes=0):
         """the resident reads in which one of `anchors` (k-mers of A bases as integers, 2 bits per base, A 0 C 1 G 2 T 3, first base high)
         starts -- the selection discover_reads runs on the device (drprg_hip_select_reads); returns (bases u8, offsets u64, ids u64 =

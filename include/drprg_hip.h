@@ -406,6 +406,50 @@ int drprg_hip_set_read_filter(drprg_hip_ctx* ctx, uint64_t min_len, uint64_t max
 int drprg_hip_read_filter_info(drprg_hip_ctx* ctx, uint64_t out[8]);
 int drprg_hip_read_filter_device(drprg_hip_ctx* ctx, const void* d_qual, uint32_t qual_bias, const void* d_offsets, uint64_t n_reads, uint64_t n_bases,
     void* d_sums, void* d_flags, uint64_t out[4], void* hip_stream);
+/* ---- Read trimming: read ends cut by quality and by fixed crops on the device, as the reads arrive.  THIS BUILD'S OWN RULE, stated from
+ * memory of what the trimmers workflows run in front of drprg compute (fastp --cut_front / --cut_tail / -f / -t, Trimmomatic LEADING /
+ * TRAILING / SLIDINGWINDOW, cutadapt -q, chopper --headcrop / --tailcrop); neither pandora nor drprg has one and nothing in them pins it.
+ *   Settings, per context: front, tail = bases cut off the start and the end of every read (0: none); qual_milli = Q * 1000 (0: no quality
+ *   trimming; at most 93000); window = W, 1..32 (4 when qual_milli != 0 and window is given as 0).
+ *   A read of L bases, in the orientation the mapper sees, with Phred qualities q_0 .. q_{L-1}:
+ *     1. Fixed crop.  a0 = min(front, L), b0 = L - min(tail, L - a0).
+ *     2. Quality trimming, only if qual_milli != 0.  A window is a start i with a0 <= i and i + W <= b0; it is GOOD iff
+ *        1000 * (q_i + ... + q_{i+W-1}) >= qual_milli * W -- the MEAN PHRED VALUE of the window, which is what fastp and Trimmomatic
+ *        compare, NOT the mean error probability the read filter holds a read against.  Exact in 32-bit integers.  With i_first the
+ *        smallest and i_last the largest good start, the range is [i_first, i_last + W), then narrowed from either end while the end
+ *        base has 1000 * q < qual_milli (a good window holds a base at or above Q, so the narrowing stays inside the edge windows).  No
+ *        good window -- a cropped read shorter than W among them -- leaves the empty range.
+ *     3. Without quality trimming the range is [a0, b0).  Every empty range is reported as [0, 0).
+ *   W = 1 is Trimmomatic's LEADING:Q TRAILING:Q; W = 4 is the family of fastp --cut_front --cut_tail.
+ *   The read IS its kept range for everything behind the ingest.  A read trimmed to nothing stays a read of no bases, as an empty FASTQ
+ *   record would be, and is counted as a read (--min-read-len 1 drops it); trimming itself never drops or reorders reads.
+ *   Qualities come from where the read filter's come from: a FASTQ byte minus 33, a BAM QUAL byte as it is; a byte out of range fails the
+ *   call with -84.  With qual_milli != 0 a read of one base or more WITHOUT qualities (a FASTA record, a BAM QUAL field that starts with
+ *   0xFF) fails the call with -EINVAL, and the text names --trim-qual.  With fixed crops alone no quality byte is parsed, copied or moved
+ *   and every input is served.  A BAM record with flag 0x10 keeps its QUAL field in stored order; the rule is mirror-symmetric, so such a
+ *   read is trimmed in stored order with front and tail swapped and the range is mirrored.
+ *   Trimming runs in drprg_hip_map_fastx, per ingest block, on the device that takes the block, BEFORE the read filter: length bounds and
+ *   mean quality are those of the trimmed read, and the depth cap, the resident set, drprg_hip_dedup, the numbering of drprg_hip_subsample,
+ *   discover and the genotyper see trimmed reads -- the run is that of a file of the trimmed reads (fastp | chopper | dedupe | rasusa |
+ *   drprg), whatever the thread count, the block boundaries and the input form.  drprg_hip_read_filter_info counts trimmed reads and bases
+ *   as "seen".  drprg_hip_map_host* and drprg_hip_map_device* return -EINVAL while any trim setting is non-zero.  Once a read lost a base,
+ *   drprg_hip_discover_reads takes its reads from HBM and returns -ENODATA (-61) when the sample is not resident.  With no setting nothing
+ *   of this exists: no launch, no wait, no quality copy.
+ *   drprg_hip_set_read_trim: applies from the next drprg_hip_map_fastx; a reset keeps the settings.  -EINVAL for qual_milli > 93000, for
+ *     window > 32 and for window != 0 && qual_milli == 0.
+ *   drprg_hip_read_trim_info: since the last reset, out[0..7] = reads seen, bases seen, reads that lost a base, bases cut by the fixed
+ *     front crop, by the fixed tail crop, by quality at the front, by quality at the tail, reads trimmed to nothing.  Bases kept = out[1] -
+ *     out[3] - out[4] - out[5] - out[6]; a read without a good window counts its cropped bases as cut by quality at the front.
+ *   drprg_hip_read_trim_device: the trim kernels alone on caller-owned device buffers, under the stream rule of the other device entries
+ *     (NULL: the context's own stream; the call returns when the work is done).  d_qual: n_bases quality bytes in stored order, read i's
+ *     from byte d_offsets[i] on (u64[n_reads + 1], [0] = 0); when d_qual is 16-byte aligned the 64 bytes behind n_bases must be readable;
+ *     may be NULL when qual_milli == 0.  qual_bias: 33 or 0.  d_rev: u8[n_reads], non-zero for a read stored mirrored, or NULL.  d_begin,
+ *     d_end: u64[n_reads], the kept range of every read in read orientation.  out[0..3] = kept bases, reads that lost a base, position + 1
+ *     of the first quality byte out of range (0: none; the call returns -84), reserved.  Reads of 2^31 bases or more: -EINVAL. */
+int drprg_hip_set_read_trim(drprg_hip_ctx* ctx, uint64_t front, uint64_t tail, uint32_t qual_milli, uint32_t window);
+int drprg_hip_read_trim_info(drprg_hip_ctx* ctx, uint64_t out[8]);
+int drprg_hip_read_trim_device(drprg_hip_ctx* ctx, const void* d_qual, uint32_t qual_bias, const void* d_offsets, const void* d_rev, uint64_t n_reads,
+    uint64_t n_bases, void* d_begin, void* d_end, uint64_t out[4], void* hip_stream);
 /* The read selection drprg_hip_discover_reads uses when the reads are resident, on its own: for every device of the context, in order,
  * every kept read in which a k-mer of `anchors` STARTS (anchors: n_anchors k-mers of A bases, 2 bits per base, A 0 C 1 G 2 T 3, first base
  * in the high bits; any order, duplicates allowed).  A block's reads are one base stream: read r of a block is returned iff for some p with
