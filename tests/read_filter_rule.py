@@ -107,3 +107,32 @@ def small_sample():
 def big_sample():
     """well over 750 000 bases: several blocks"""
     return sample(1000, 250, seed=32)
+
+
+TILE = 16384   # bytes of the quality buffer per workgroup of read_qual_kernel
+SLOTS = 1024   # per-workgroup sums it keeps in LDS: a tile's reads beyond them go to global memory one by one
+
+
+def overflow_batch(seed=17):
+    """lengths of a batch that sends read_qual_kernel down its overflow route, in three tiles.  The first holds 1 300 reads of 1 to 15 bases
+    (lane pieces of 16 bytes hold up to 16 reads) and is filled to its edge: more read starts than the kernel has slots, so the sums of the
+    reads beyond them go to global memory one by one.  Exactly on that edge a run of 1 100 empty reads starts, followed by a read with bases.
+    That run does NOT overflow the second tile: the kernel takes as a tile's first read the LAST read that starts at or before the tile's
+    first byte, which is the read behind the run (slot 0), and no workgroup touches the empty reads -- what the run holds the kernel to is
+    that search, and sums of 0 for reads nobody visits.  The second tile's last lane piece holds the start of a read that ends in the third.
+    Returns (lengths, index of the read behind the empty run, index of the straddler)"""
+    rng = np.random.default_rng(seed)
+    L = [int(x) for x in rng.integers(1, 16, size=1300)]
+    L[:16] = [1] * 16  # one lane piece of sixteen reads
+    while TILE - sum(L) > 300:
+        L.append(int(rng.integers(20, 300)))
+    L.append(TILE - sum(L))
+    L += [0] * 1100
+    behind = len(L)
+    L.append(40)
+    while 2 * TILE - 8 - sum(L) > 300:
+        L.append(int(rng.integers(1, 300)))
+    L.append(2 * TILE - 8 - sum(L))
+    straddler = len(L)
+    L += [100, 0, 7, 1, 333]
+    return L, behind, straddler

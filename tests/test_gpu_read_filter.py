@@ -117,15 +117,17 @@ def _ragged():
     return L, o
 
 
-def _device_filter(ctx, torch, quals_flat, offs, bias, pad=64):
+def _device_filter(ctx, torch, quals_flat, offs, bias, pad=64, shift=0):
+    """shift: the quality buffer starts that many bytes behind a 16-byte aligned address (it is read byte by byte then)"""
     n_reads, n_bases = len(offs) - 1, int(offs[-1])
-    buf = np.zeros(n_bases + pad, dtype=np.uint8)
-    buf[:n_bases] = quals_flat + bias
+    buf = np.zeros(shift + n_bases + pad, dtype=np.uint8)
+    buf[shift:shift + n_bases] = quals_flat + bias
     d_q = torch.from_numpy(buf).cuda()
+    assert d_q.data_ptr() % 16 == 0
     d_o = torch.from_numpy(offs.astype(np.int64)).cuda()
     d_s = torch.full((max(n_reads, 1),), -1, dtype=torch.int64, device="cuda")  # (stale on purpose)
     d_f = torch.full((max(n_reads, 1),), 7, dtype=torch.uint8, device="cuda")
-    out = ctx.read_filter_device(d_q.data_ptr(), bias, d_o.data_ptr(), n_reads, n_bases, d_s.data_ptr(), d_f.data_ptr())
+    out = ctx.read_filter_device(d_q.data_ptr() + shift, bias, d_o.data_ptr(), n_reads, n_bases, d_s.data_ptr(), d_f.data_ptr())
     torch.cuda.synchronize()
     return out, d_s.cpu().numpy().astype(np.uint64)[:n_reads], d_f.cpu().numpy()[:n_reads]
 
@@ -145,11 +147,11 @@ def test_sums_and_flags_of_the_kernel_equal_the_rule(tmp_path, bias):
     T = ctx.read_filter_info()["T"]
     assert abs(T - rule.threshold(12900)) <= 1
 
-    def check(L, offs, q, what):
+    def check(L, offs, q, what, shift=0):
         per_read = [q[int(offs[i]):int(offs[i + 1])] for i in range(len(L))]
         sums = [qual_sum(x) for x in per_read]
         keep = [w == KEEP for w in fates(L, per_read, 1, 16400, T)]
-        out, got_s, got_f = _device_filter(ctx, torch, q, offs, bias)
+        out, got_s, got_f = _device_filter(ctx, torch, q, offs, bias, shift=shift)
         assert got_s.tolist() == sums, (what, [i for i in range(len(L)) if int(got_s[i]) != sums[i]][:8])
         assert got_f.tolist() == [int(k) for k in keep], what
         assert out == (sum(keep), sum(l for l, k in zip(L, keep) if k), 0), (what, out)
@@ -157,6 +159,14 @@ def test_sums_and_flags_of_the_kernel_equal_the_rule(tmp_path, bias):
 
     keep = check(L, offs, q, "ragged")
     assert 0 < sum(keep) < len(L) - 8  # (the eight empty reads are short; the threshold keeps some of the rest and drops some)
+    # the overflow route: more than 1 024 reads under one tile (tests/read_filter_rule.py: overflow_batch), 16-byte aligned and one byte off
+    L3, behind, straddler = rule.overflow_batch()
+    o3 = np.zeros(len(L3) + 1, dtype=np.uint64)
+    o3[1:] = np.cumsum(L3)
+    q3 = rng.integers(0, 94, size=int(o3[-1])).astype(np.uint8)
+    for shift in (0, 1):
+        keep3 = check(L3, o3, q3, ("overflow", shift), shift)
+        assert 0 < sum(keep3) < len(L3) - 1100 and not any(keep3[behind - 1100:behind])
     # a second launch on the same context with a smaller batch: no sum of the first one is left behind
     L2 = [0, 2, 0, 3, 0]
     o2 = np.array([0, 0, 2, 2, 5, 5], dtype=np.uint64)

@@ -108,6 +108,24 @@ def test_census_of_the_gpu_fixtures(which):
     assert only_len.count(LOWQ) == 0 and only_len.count(SHORT) == c["dropped_short"] and only_len.count(LONG) == c["dropped_long"]
 
 
+def test_the_overflow_batch_overflows():
+    """more read starts under one tile than read_qual_kernel has slots for, counted on the lengths alone"""
+    L, behind, straddler = rule.overflow_batch()
+    o = np.zeros(len(L) + 1, dtype=np.int64)
+    o[1:] = np.cumsum(L)
+    starts = np.bincount(o[:-1] // rule.TILE, minlength=3)
+    assert starts[0] > rule.SLOTS + 64 and o[-1] > 2 * rule.TILE
+    assert min(L[:1300]) == 1 and max(L[:1300]) == 15 and L[:16] == [1] * 16
+    # the run of empty reads starts exactly on the tile edge and the read behind it holds that tile's first byte: the kernel must find that
+    # read, 1 100 reads behind the first that starts there, as the tile's first (it does not count the empty ones against its slots)
+    first_at_edge = int(np.searchsorted(o[:-1], rule.TILE, side="left"))
+    assert o[first_at_edge] == rule.TILE and L[first_at_edge:first_at_edge + 1100] == [0] * 1100 and behind == first_at_edge + 1100
+    assert L[behind] > 0 and o[behind] == rule.TILE and behind - first_at_edge == 1100
+    # a read that starts in the second tile's last lane piece (16 bytes) and ends in the third
+    assert 2 * rule.TILE - 16 <= o[straddler] < 2 * rule.TILE < o[straddler + 1]
+    assert max(L) <= 16400 and 0 < min(x for x in L if x)
+
+
 @pytest.mark.parametrize("exe, head", [("pandora", ["map"]), ("pandora", ["discover"]), ("drprg", ["predict", "-x", "nowhere", "-i", "nothing.fq"])])
 def test_usage_errors_exit_with_status_2(exe, head):
     path = os.path.join(ROOT, "drprg_amd", "bin", exe)
