@@ -136,6 +136,7 @@ struct drprg_hip_ctx {
     Mapper::ReadFilter read_filter;
     Mapper::FilterOutcome filter_counts;
     Mapper::TrimOutcome trim_counts; // drprg_hip_read_trim_info (the settings ride in read_filter)
+    Mapper::AdapterOutcome adapter_counts; // drprg_hip_adapter_trim_info (the settings ride in read_filter too)
     std::mutex filter_mu;
     // (the page-locked ingest blocks of drprg_hip_map_fastx are recycled process-wide: PinPool above)
     // multi-device context: RCCL communicators of its devices (created on first use; empty when RCCL is not used)
@@ -512,6 +513,9 @@ int drprg_hip_map_fastx(drprg_hip_ctx* ctx, const char* reads_path)
         Mapper::TrimOutcome& tt = ctx->trim_counts;
         tt.reads_seen += o.trim.reads_seen; tt.bases_seen += o.trim.bases_seen; tt.reads_lost_base += o.trim.reads_lost_base; tt.cut_front += o.trim.cut_front;
         tt.cut_tail += o.trim.cut_tail; tt.qcut_front += o.trim.qcut_front; tt.qcut_tail += o.trim.qcut_tail; tt.emptied += o.trim.emptied;
+        Mapper::AdapterOutcome& at = ctx->adapter_counts;
+        at.reads_seen += o.adapter.reads_seen; at.bases_seen += o.adapter.bases_seen; at.reads_cut += o.adapter.reads_cut; at.bases_cut += o.adapter.bases_cut;
+        at.reads_emptied += o.adapter.reads_emptied;
         kept_reads += o.mapped_reads;
         kept_bases += o.mapped_bases;
         return o;
@@ -656,6 +660,9 @@ int drprg_hip_set_threads(drprg_hip_ctx* ctx, int threads)
 // The entry points that carry no qualities: while a filter is set they refuse, rather than map unfiltered reads without saying so.
 static void refuse_unfiltered(const drprg_hip_ctx* ctx, const char* entry)
 {
+    if (ctx->read_filter.adapters.n)
+        throw Error(DRPRG_EINVAL, std::string(entry) + ": adapters are set (drprg_hip_set_adapters) and adapter trimming runs in drprg_hip_map_fastx; this entry "
+                                                      "would map the reads with their adapters (clear them with drprg_hip_set_adapters(ctx, NULL, 0, 0, 0))");
     if (ctx->read_filter.trims())
         throw Error(DRPRG_EINVAL, std::string(entry) + ": read trimming is set (drprg_hip_set_read_trim) and this entry carries no qualities; trimming "
                                                       "runs in drprg_hip_map_fastx (clear it with drprg_hip_set_read_trim(ctx, 0, 0, 0, 0))");
@@ -750,6 +757,65 @@ int drprg_hip_read_trim_device(drprg_hip_ctx* ctx, const void* d_qual, uint32_t 
     out[3] = 0;
     if (bad_offsets) throw Error(DRPRG_EINVAL, "read trimming: the offsets do not ascend to n_bases (or a read is longer than 2^31 bases)");
     if (res[dev::RT_BAD_AT]) throw Error(DRPRG_EFORMAT, "a base quality outside 0..93 at quality byte " + std::to_string(res[dev::RT_BAD_AT] - 1));
+    API_END(ctx)
+}
+
+// ---- adapter trimming (the rule: include/drprg_hip.h "adapter trimming") ----------------------------------------------------------
+int drprg_hip_set_adapters(drprg_hip_ctx* ctx, const char* const* seqs, uint32_t n, uint32_t error_milli, uint32_t min_overlap)
+{
+    API_BEGIN(ctx)
+    dev::AdapterSet ad {};
+    if (n == 0) { // cleared
+        ctx->read_filter.adapters = ad;
+        return DRPRG_OK;
+    }
+    if (!seqs) throw Error(DRPRG_EINVAL, "adapter trimming: null adapter list");
+    if (n > dev::AD_MAX_ADAPTERS) throw Error(DRPRG_EINVAL, "adapter trimming: at most 4 adapters");
+    if (error_milli > dev::AD_MAX_ERROR_MILLI) throw Error(DRPRG_EINVAL, "adapter trimming: the error rate is 0..0.5");
+    uint32_t shortest = dev::AD_MAX_LEN;
+    for (uint32_t a = 0; a < n; ++a) {
+        if (!seqs[a]) throw Error(DRPRG_EINVAL, "adapter trimming: null adapter");
+        const size_t m = std::strlen(seqs[a]);
+        if (m < 1 || m > dev::AD_MAX_LEN) throw Error(DRPRG_EINVAL, "adapter trimming: an adapter is 1..64 letters long");
+        for (size_t j = 0; j < m; ++j) {
+            const uint32_t l = dev::ad_letter((uint8_t)seqs[a][j]);
+            if (l > 3) throw Error(DRPRG_EINVAL, "adapter trimming: an adapter holds the letters ACGT (either case) and no other");
+            (j < 32 ? ad.lo[a] : ad.hi[a]) |= (uint64_t)l << (2 * (j & 31));
+        }
+        ad.len[a] = (uint32_t)m;
+        if (m > ad.max_len) ad.max_len = (uint32_t)m;
+        if (m < shortest) shortest = (uint32_t)m;
+    }
+    if (min_overlap > shortest) throw Error(DRPRG_EINVAL, "adapter trimming: the minimum overlap is 1..the length of the shortest adapter");
+    ad.n = n;
+    ad.error_milli = error_milli;
+    ad.min_overlap = min_overlap ? min_overlap : std::min(dev::AD_DEFAULT_MIN_OVERLAP, shortest);
+    ctx->read_filter.adapters = ad;
+    API_END(ctx)
+}
+
+int drprg_hip_adapter_trim_info(drprg_hip_ctx* ctx, uint64_t out[5])
+{
+    API_BEGIN(ctx)
+    if (!out) throw Error(DRPRG_EINVAL, "null output");
+    std::lock_guard<std::mutex> g(ctx->filter_mu);
+    const Mapper::AdapterOutcome& t = ctx->adapter_counts;
+    out[0] = t.reads_seen; out[1] = t.bases_seen; out[2] = t.reads_cut; out[3] = t.bases_cut; out[4] = t.reads_emptied;
+    API_END(ctx)
+}
+
+int drprg_hip_adapter_trim_device(drprg_hip_ctx* ctx, const void* d_text, const void* d_words, const void* d_npos, uint64_t n_npos, const void* d_offsets,
+    uint64_t n_reads, uint64_t n_bases, const void* d_begin, void* d_end, uint64_t out[5], void* hip_stream)
+{
+    API_BEGIN(ctx)
+    Mapper& m = need_mapper(ctx);
+    if (!out) throw Error(DRPRG_EINVAL, "null output");
+    if (d_text && d_words) throw Error(DRPRG_EINVAL, "adapter trimming: the bases come as text or as packed words, not both");
+    uint64_t res[6];
+    m.adapter_trim_device(ctx->read_filter, (const uint8_t*)d_text, (const uint32_t*)d_words, (const uint64_t*)d_npos, n_npos, (const uint64_t*)d_offsets, n_reads,
+        n_bases, (const uint64_t*)d_begin, (uint64_t*)d_end, res, (hipStream_t)hip_stream);
+    for (int i = 0; i < 5; ++i) out[i] = res[i];
+    if (res[5]) throw Error(DRPRG_EINVAL, "adapter trimming: the offsets do not ascend to n_bases, or a range does not lie inside its read");
     API_END(ctx)
 }
 
@@ -1096,6 +1162,7 @@ int drprg_hip_reset(drprg_hip_ctx* ctx)
     ctx->dedup_flags.clear();
     ctx->filter_counts = Mapper::FilterOutcome(); // (the settings stay, as the depth cap does)
     ctx->trim_counts = Mapper::TrimOutcome();
+    ctx->adapter_counts = Mapper::AdapterOutcome();
     API_END(ctx)
 }
 
@@ -1341,6 +1408,9 @@ int drprg_hip_discover_reads(drprg_hip_ctx* ctx, const char* reads_path, const c
     ResidentReads resident;
     ctx->last_discover_resident = reads_resident(ctx, reads_path);
     // (the pass over the file knows nothing of the read filter: rather than pile up reads the mapping never saw, say so)
+    if (!ctx->last_discover_resident && ctx->adapter_counts.reads_cut)
+        throw Error(DRPRG_ENODATA, "discover: adapter trimming cut bases off reads of this sample and the cut reads are not resident in device memory; a pass "
+                                   "over the file would pile up reads with their adapters (raise DRPRG_HIP_KEEP_READS_GB, or cut the file first)");
     if (!ctx->last_discover_resident && ctx->trim_counts.reads_lost_base)
         throw Error(DRPRG_ENODATA, "discover: read trimming cut bases off reads of this sample and the trimmed reads are not resident in device memory; a pass "
                                    "over the file would pile up untrimmed reads (raise DRPRG_HIP_KEEP_READS_GB, or trim the file first)");

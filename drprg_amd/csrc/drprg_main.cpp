@@ -19,6 +19,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 #include <vector>
+#include "adapter_args.h"
 
 namespace {
 
@@ -110,6 +111,11 @@ void usage()
         "              [-C MIN_CLUSTER_SIZE] [--debug] [-v] [-t THREADS] [--rebuild-index] [--subsample-covg D [--seed S]]\n"
         "              [--dedup] [--min-read-len L] [--max-read-len L] [--min-read-qual Q]\n"
         "              [--trim-front N] [--trim-tail N] [--trim-qual Q [--trim-window W]]\n"
+        "              [--adapter SEQ]... [--adapter-error E] [--adapter-min-overlap O]\n"
+        "--adapter SEQ (up to 4 times; 1 to 64 letters ACGT), --adapter-error E (0 to 0.5, default 0.1), --adapter-min-overlap O (default 3):\n"
+        "              every read is cut at the leftmost start at which an adapter matches with at most floor(c * E) substitutions over the\n"
+        "              c = min(adapter, rest of the read) letters compared, c >= O -- on the device, behind --trim-* and in front of\n"
+        "              everything else.  No indels, no 5' adapter, no pair overlap.  Needs no qualities.\n"
         "--trim-front N, --trim-tail N, --trim-qual Q, --trim-window W: every read loses N bases at its start and N at its end and, under\n"
         "              --trim-qual (a decimal Phred value in (0, 93]), what lies outside its first and last window of W bases (1..32, default\n"
         "              4) whose MEAN PHRED VALUE is at least Q, then end bases below Q -- on the device, in front of the read filter and\n"
@@ -166,6 +172,7 @@ int main(int argc, char** argv)
     uint32_t min_read_qual_milli = 0;
     uint64_t trim_front = 0, trim_tail = 0; // read trimming (include/drprg_hip.h "read trimming"); 0 = not set
     uint32_t trim_qual_milli = 0, trim_window = 0;
+    drprg::AdapterArgs adapters; // --adapter SEQ, --adapter-error E, --adapter-min-overlap O (include/drprg_hip.h "adapter trimming")
     uint32_t min_cluster = 10;
     drprg_hip_annotate_opts ao {};
     ao.min_covg = 3;
@@ -251,12 +258,24 @@ int main(int argc, char** argv)
             if (end == v || *end || n < 1 || n > 32) die(std::string("--trim-window needs a window of 1 to 32 bases, not ") + v, 2);
             trim_window = (uint32_t)n;
         }
+        else if (a == "--adapter") {
+            const std::string e = adapters.add(need(i));
+            if (!e.empty()) die(e, 2);
+        } else if (a == "--adapter-error") {
+            const std::string e = adapters.set_error(need(i));
+            if (!e.empty()) die(e, 2);
+        } else if (a == "--adapter-min-overlap") {
+            const std::string e = adapters.set_overlap(need(i));
+            if (!e.empty()) die(e, 2);
+        }
         else if (a == "-h" || a == "--help") { usage(); return 0; }
         else die("unknown option " + a, 2);
     }
     if (seed_given && !subsample) die("--seed belongs to --subsample-covg", 2);
     if (max_read_len && max_read_len < min_read_len) die("--max-read-len is below --min-read-len: no read can pass", 2);
     if (trim_window && !trim_qual_milli) die("--trim-window belongs to --trim-qual", 2);
+    if (const std::string e = adapters.check(); !e.empty()) die(e, 2);
+    const std::vector<const char*> adapter_seqs = adapters.pointers();
     if (index.empty() || input.empty()) {
         usage();
         return 2;
@@ -310,6 +329,8 @@ int main(int argc, char** argv)
     drprg_hip_set_input_format(ctx, packed_input()); // the parser threads pack the reads to 2 bits (DRPRG_HIP_INPUT=ascii: one byte per base)
     if (int rc = drprg_hip_set_read_filter(ctx, min_read_len, max_read_len, min_read_qual_milli)) die(drprg_hip_last_error(ctx), -rc);
     if (int rc = drprg_hip_set_read_trim(ctx, trim_front, trim_tail, trim_qual_milli, trim_window)) die(drprg_hip_last_error(ctx), -rc);
+    if (adapters.any())
+        if (int rc = drprg_hip_set_adapters(ctx, adapter_seqs.data(), (uint32_t)adapter_seqs.size(), adapters.error_milli, adapters.min_overlap)) die(drprg_hip_last_error(ctx), -rc);
     // The reads stay in HBM after the mapping pass (up to DRPRG_HIP_KEEP_READS_GB per device, default 32, 0 = off): discover takes
     // the few reads it needs from there and a novel variant maps them again from there -- the file is read once.
     double keep_gb = 32;
@@ -331,6 +352,12 @@ int main(int argc, char** argv)
                                  "qual_cut_front=%llu qual_cut_tail=%llu reads_emptied=%llu\n", since_start(), (unsigned long long)ti[0], (unsigned long long)ti[1],
                 (unsigned long long)ti[2], (unsigned long long)ti[3], (unsigned long long)ti[4], (unsigned long long)ti[5], (unsigned long long)ti[6],
                 (unsigned long long)ti[7]);
+    }
+    if (verbose && adapters.any()) {
+        uint64_t ai[5] = {};
+        if (drprg_hip_adapter_trim_info(ctx, ai) == 0)
+            std::fprintf(stderr, "[drprg-hip +%.3fs] adapter trimming: reads_seen=%llu bases_seen=%llu reads_cut=%llu bases_cut=%llu reads_emptied=%llu\n", since_start(),
+                (unsigned long long)ai[0], (unsigned long long)ai[1], (unsigned long long)ai[2], (unsigned long long)ai[3], (unsigned long long)ai[4]);
     }
     if (verbose && (min_read_len || max_read_len || min_read_qual_milli)) {
         uint64_t fi[8] = {};
@@ -388,6 +415,9 @@ int main(int argc, char** argv)
                 drprg_hip_set_input_format(next, packed_input()); // the parser threads pack the reads to 2 bits (DRPRG_HIP_INPUT=ascii: one byte per base)
                 if (int rc = drprg_hip_set_read_filter(next, min_read_len, max_read_len, min_read_qual_milli)) die(drprg_hip_last_error(next), -rc);
                 if (int rc = drprg_hip_set_read_trim(next, trim_front, trim_tail, trim_qual_milli, trim_window)) die(drprg_hip_last_error(next), -rc);
+                if (adapters.any())
+                    if (int rc = drprg_hip_set_adapters(next, adapter_seqs.data(), (uint32_t)adapter_seqs.size(), adapters.error_milli, adapters.min_overlap))
+                        die(drprg_hip_last_error(next), -rc);
                 // the reads again, against the updated index: from HBM if the first context kept them all, else from the file
                 const int from_hbm = drprg_hip_map_resident(next, ctx);
                 if (from_hbm != 0 && from_hbm != -61 /* ENODATA */) die(drprg_hip_last_error(next), -from_hbm);

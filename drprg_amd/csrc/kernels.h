@@ -11,6 +11,7 @@
 #define DRPRG_HD
 #endif
 #include "dedup_word.h"
+#include "adapter_piece.h"
 
 namespace drprg {
 namespace dev {
@@ -448,12 +449,35 @@ hipError_t launch_read_filter(const ReadFilterArgs& a, hipStream_t stream, Kerne
 // orientation ([0, 0) when empty), klen[i] its length, noff the exclusive scan of klen (n_reads + 1 entries each, entry n_reads of noff
 // the kept bases).  qual (n_bases + 64 bytes readable when 16-byte aligned; bias 33 or 0), first and last (u32[n_reads], scratch) are
 // touched only when qual_milli != 0; window is 1..32 then.  rev: u8[n_reads], non-zero where the quality bytes are stored mirrored, or
-// null.  work: ten device words; out: nine words the device can write, indexed by RT_*; temp: read_trim_temp_bytes(n_reads) bytes.
-// 1 <= n_reads <= MAX_BATCH_READS.
+// null.  work: RT_WORDS device words; out: RT_WORDS words the device can write, indexed by RT_*; temp: read_trim_temp_bytes(n_reads) bytes.
+// 1 <= n_reads <= MAX_BATCH_READS.  ad.n != 0: adapter trimming behind it on the same ranges (adapter_trim.hip; pts: the bases, its
+// offsets, ranges and sizes are taken from here).
 enum {
     RT_KEPT_BASES = 0, RT_LOST_READS = 1, RT_CUT_FRONT = 2, RT_CUT_TAIL = 3, RT_QCUT_FRONT = 4, RT_QCUT_TAIL = 5, RT_EMPTIED = 6,
-    RT_BAD_AT = 7 /* first bad quality byte + 1, 0, or ~0: offsets at odds with n_bases */, RT_KEPT_NPOS = 8 /* out only */, RT_OFFSETS = 9 /* work only */
+    RT_BAD_AT = 7 /* first bad quality byte + 1, 0, or ~0: offsets at odds with n_bases */, RT_KEPT_NPOS = 8 /* out only */, RT_OFFSETS = 9 /* work only */,
+    // adapter trimming (adapter_trim.hip), all zero without adapters: bases in the ranges the crops and the quality trim left, reads and
+    // bases cut, reads emptied
+    RT_AD_BASES_SEEN = 10, RT_AD_READS_CUT = 11, RT_AD_BASES_CUT = 12, RT_AD_EMPTIED = 13, RT_WORDS = 14 /* words of work and of out */
 };
+// adapter_trim.hip: what adapter_points_kernel searches.  The bases as text (n_bases + 64 bytes readable when 16-byte aligned; any other
+// address is read byte by byte and never behind n_bases) or, when words != null, as a packed batch's words (ceil(n_bases / 16)) with
+// nbits, the bitmap launch_mark_npos makes of its position list (null: none).  begin / end: every read's range, read orientation, counted
+// from its first base; cut: u32[n_reads], the smallest matching start counted from begin, or AD_NONE.
+struct AdapterPoints {
+    const uint8_t* text;
+    const uint32_t* words;
+    const uint16_t* nbits;
+    const uint64_t* offsets;
+    const uint64_t *begin, *end;
+    uint64_t n_reads, n_bases;
+    uint32_t* cut;
+};
+uint32_t adapter_trim_tiles(uint64_t n_bases);
+// cut := AD_NONE, adapter_points_kernel, adapter_apply_kernel: end[i] = begin[i] + cut[i] where there is a match, klen[i] (klen may be null)
+// the new length, the counts ADDED to work[RT_AD_*]; work[RT_OFFSETS] is set when a range does not lie inside its read.  end is a.end.
+// timer: around adapter_points_kernel alone
+hipError_t launch_adapter_trim(const AdapterPoints& a, const AdapterSet& ad, uint64_t* end, uint64_t* klen, unsigned long long* work, hipStream_t stream,
+    KernelTimer timer = {});
 struct ReadTrimArgs {
     const uint8_t* qual;
     uint32_t bias;
@@ -467,6 +491,8 @@ struct ReadTrimArgs {
     unsigned long long *work, *out;
     void* temp;
     size_t temp_bytes;
+    AdapterSet ad;
+    AdapterPoints pts;
 };
 // the block's listed non-ACGT positions (n_npos == 0: none, nothing else is looked at).  chunk_count / chunk_prefix:
 // read_trim_npos_chunks(n_npos) + 1 words each; temp: scan_temp_bytes of as many.  launch_read_trim leaves the number of positions inside

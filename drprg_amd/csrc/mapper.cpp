@@ -1555,7 +1555,7 @@ void Mapper::read_filter_device(const ReadFilter& f, const uint8_t* d_qual, uint
 }
 
 // ---- read trimming -------------------------------------------------------------------------------------------------------------------
-void Mapper::ensure_trim_scratch(FilterScratch& fs, uint64_t n_reads, uint64_t n_npos, bool use_qual, bool own_ranges)
+void Mapper::ensure_trim_scratch(FilterScratch& fs, uint64_t n_reads, uint64_t n_npos, bool use_qual, bool own_ranges, bool adapters, uint64_t bitmap_bases)
 {
     auto room = [&](auto& buf, uint64_t need) {
         if (need <= buf.size()) return;
@@ -1579,14 +1579,42 @@ void Mapper::ensure_trim_scratch(FilterScratch& fs, uint64_t n_reads, uint64_t n
         room(fs.t_prefix, chunks);
         room(fs.t_ntemp, dev::scan_temp_bytes((uint32_t)chunks));
     }
-    if (!fs.t_work) fs.t_work.alloc(10);
-    if (!fs.t_out) fs.t_out.alloc(9);
+    if (adapters) {
+        room(fs.t_cut, n_reads);
+        if (bitmap_bases) room(fs.t_nbits, (bitmap_bases + 15) / 16 + 8); // (launch_mark_npos writes 32-bit words)
+    }
+    if (!fs.t_work) fs.t_work.alloc(dev::RT_WORDS);
+    if (!fs.t_out) fs.t_out.alloc(dev::RT_WORDS);
+}
+
+dev::AdapterPoints Mapper::adapter_points(FilterScratch& fs, const uint8_t* d_bases, bool packed, const uint64_t* d_npos, uint64_t n_npos, uint64_t n_bases,
+    hipStream_t stream)
+{
+    dev::AdapterPoints p {};
+    p.cut = fs.t_cut.data();
+    if (!packed) {
+        p.text = d_bases;
+        return p;
+    }
+    p.words = reinterpret_cast<const uint32_t*>(d_bases);
+    if (n_npos) {
+        const uint64_t n16 = (n_bases + 15) / 16 + 8;
+        HIPCHK(hipMemsetAsync(fs.t_nbits.data(), 0, n16 * sizeof(uint16_t), stream));
+        HIPCHK(dev::launch_mark_npos(d_npos, n_npos, n_bases, fs.t_nbits.data(), stream));
+        p.nbits = fs.t_nbits.data();
+    }
+    return p;
 }
 
 void Mapper::run_read_trim(FilterScratch& fs, const ReadFilter& f, const uint8_t* d_qual, uint32_t bias, const uint64_t* d_offsets, const uint8_t* d_rev,
-    uint64_t n_reads, uint64_t n_bases, uint64_t* d_begin, uint64_t* d_end, const uint64_t* d_npos, uint64_t n_npos, hipStream_t stream)
+    uint64_t n_reads, uint64_t n_bases, uint64_t* d_begin, uint64_t* d_end, const uint64_t* d_npos, uint64_t n_npos, hipStream_t stream,
+    const dev::AdapterPoints* pts)
 {
     dev::ReadTrimArgs a {};
+    if (pts && f.adapters.n) {
+        a.ad = f.adapters;
+        a.pts = *pts;
+    }
     a.qual = d_qual; a.bias = bias; a.offsets = d_offsets; a.rev = d_rev; a.n_reads = n_reads; a.n_bases = n_bases;
     a.front = f.trim_front; a.tail = f.trim_tail; a.qual_milli = f.trim_qual_milli; a.window = f.trim_window;
     a.first = fs.t_first.data(); a.last = fs.t_last.data(); a.begin = d_begin; a.end = d_end; a.klen = fs.t_klen.data(); a.noff = fs.t_offsets.data();
@@ -1610,6 +1638,29 @@ void Mapper::read_trim_device(const ReadFilter& f, const uint8_t* d_qual, uint32
     run_read_trim(fs, f, d_qual, bias, d_offsets, d_rev, n_reads, n_bases, d_begin, d_end, nullptr, 0, stream);
     HIPCHK(hipStreamSynchronize(stream));
     for (int i = 0; i < 9; ++i) res[i] = fs.t_out[i];
+}
+
+void Mapper::adapter_trim_device(const ReadFilter& f, const uint8_t* d_text, const uint32_t* d_words, const uint64_t* d_npos, uint64_t n_npos,
+    const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases, const uint64_t* d_begin, uint64_t* d_end, uint64_t res[6], hipStream_t stream, dev::KernelTimer timer)
+{
+    for (int i = 0; i < 6; ++i) res[i] = 0;
+    if (n_reads == 0) return;
+    HIPCHK(hipSetDevice(device_));
+    if (!stream) stream = stream_;
+    if (!f.adapters.n) throw Error(DRPRG_EINVAL, "adapter trimming: no adapter is set (drprg_hip_set_adapters)");
+    if (!d_offsets || !d_begin || !d_end || (n_bases && !d_text && !d_words) || (n_npos && !d_npos)) throw Error(DRPRG_EINVAL, "null device pointer");
+    if (n_reads > dev::MAX_BATCH_READS) throw Error(DRPRG_EOVERFLOW, "at most " + std::to_string(dev::MAX_BATCH_READS) + " reads per batch");
+    FilterScratch& fs = filter_api_;
+    ensure_trim_scratch(fs, n_reads, 0, false, false, true, d_words && n_npos ? n_bases : 0);
+    dev::AdapterPoints p = adapter_points(fs, d_words ? reinterpret_cast<const uint8_t*>(d_words) : d_text, d_words != nullptr, d_npos, n_npos, n_bases, stream);
+    p.offsets = d_offsets; p.begin = d_begin; p.end = d_end; p.n_reads = n_reads; p.n_bases = n_bases;
+    HIPCHK(hipMemsetAsync(fs.t_work.data(), 0, dev::RT_WORDS * sizeof(unsigned long long), stream));
+    HIPCHK(dev::launch_adapter_trim(p, f.adapters, d_end, nullptr, fs.t_work.data(), stream, timer));
+    HIPCHK(hipMemcpyAsync(fs.t_out.data(), fs.t_work.data(), dev::RT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    res[0] = n_reads;
+    for (int i = 0; i < 4; ++i) res[1 + i] = fs.t_out[dev::RT_AD_BASES_SEEN + i];
+    res[5] = fs.t_out[dev::RT_OFFSETS];
 }
 
 void Mapper::map_host_filtered(const HostBatch& hb, const ReadFilter& f, uint64_t cap_need, FilterOutcome& o)
@@ -1643,7 +1694,7 @@ void Mapper::map_host_filtered(const HostBatch& hb, const ReadFilter& f, uint64_
     uint64_t n_npos = hb.packed || hb.bam ? hb.n_npos : 0;
     ensure_stage(st, hb.payload_bytes(), n_reads, n_npos);
     ensure_filter_scratch(fs, n_reads, f.wants_qual() ? n_bases : 0, true, f.use_qual());
-    if (f.trims()) ensure_trim_scratch(fs, n_reads, n_npos, f.trim_qual_milli != 0, true);
+    if (f.trims()) ensure_trim_scratch(fs, n_reads, n_npos, f.trim_qual_milli != 0, true, f.adapters.n != 0, n_npos ? n_bases : 0);
     DeviceBatch src = hb.bam ? copy_in_bam(hb, st, st.d_bases.data(), st.d_offsets.data(), st.d_npos.data(), cs, cs)
                              : copy_in(hb, st.d_bases.data(), st.d_offsets.data(), st.d_npos.data(), cs);
     if (f.wants_qual()) {
@@ -1657,17 +1708,25 @@ void Mapper::map_host_filtered(const HostBatch& hb, const ReadFilter& f, uint64_
         // into the set's t_* buffers (launch_subsample_pack for words, launch_gather_reads for text and for the quality bytes) and `src`
         // and the quality pointer are REPLACED: the filter, the depth cut, the compaction and keep_reads below see a block of trimmed reads.
         const uint8_t* d_rev = hb.bam && hb.reverse ? st.d_reverse.data() : nullptr; // (BAM: QUAL stays in stored order; the bases were reversed by bam_pack_kernel)
-        run_read_trim(fs, f, d_q, hb.qual_bias, src.d_offsets, d_rev, n_reads, n_bases, fs.t_begin.data(), fs.t_end.data(), src.d_npos, src.n_npos, cs);
+        dev::AdapterPoints pts {}; // (adapters: sought in what the crops and the quality trim leave, bases in read orientation; a packed block's bitmap first)
+        if (f.adapters.n) pts = adapter_points(fs, src.d_bases, src.packed, src.d_npos, src.n_npos, n_bases, cs);
+        run_read_trim(fs, f, d_q, hb.qual_bias, src.d_offsets, d_rev, n_reads, n_bases, fs.t_begin.data(), fs.t_end.data(), src.d_npos, src.n_npos, cs, &pts);
         HIPCHK(hipStreamSynchronize(cs)); // the trim's read-back: the trimmed sizes are known before the filter is launched
         const unsigned long long* t = fs.t_out.data();
         if (t[dev::RT_BAD_AT] == ~0ull) throw Error(DRPRG_EINVAL, "read trimming: the block's offsets do not ascend to its number of bases");
         if (t[dev::RT_BAD_AT])
             throw Error(DRPRG_EFORMAT, "a base quality outside 0..93 (quality byte " + std::to_string(t[dev::RT_BAD_AT] - 1) + " of an ingest block of "
                     + std::to_string(n_bases) + " bases, " + (hb.qual_bias ? "FASTQ: bytes 33..126" : "BAM: bytes 0..93") + ")");
-        o.trim.reads_seen = n_reads; o.trim.bases_seen = n_bases; o.trim.reads_lost_base = t[dev::RT_LOST_READS];
-        o.trim.cut_front = t[dev::RT_CUT_FRONT]; o.trim.cut_tail = t[dev::RT_CUT_TAIL]; o.trim.qcut_front = t[dev::RT_QCUT_FRONT];
-        o.trim.qcut_tail = t[dev::RT_QCUT_TAIL]; o.trim.emptied = t[dev::RT_EMPTIED];
-        if (t[dev::RT_LOST_READS]) {
+        if (f.crops()) {
+            o.trim.reads_seen = n_reads; o.trim.bases_seen = n_bases; o.trim.reads_lost_base = t[dev::RT_LOST_READS];
+            o.trim.cut_front = t[dev::RT_CUT_FRONT]; o.trim.cut_tail = t[dev::RT_CUT_TAIL]; o.trim.qcut_front = t[dev::RT_QCUT_FRONT];
+            o.trim.qcut_tail = t[dev::RT_QCUT_TAIL]; o.trim.emptied = t[dev::RT_EMPTIED];
+        }
+        if (f.adapters.n) {
+            o.adapter.reads_seen = n_reads; o.adapter.bases_seen = t[dev::RT_AD_BASES_SEEN]; o.adapter.reads_cut = t[dev::RT_AD_READS_CUT];
+            o.adapter.bases_cut = t[dev::RT_AD_BASES_CUT]; o.adapter.reads_emptied = t[dev::RT_AD_EMPTIED];
+        }
+        if (t[dev::RT_LOST_READS] || t[dev::RT_AD_READS_CUT]) { // the block lost a base to either cause
             const uint64_t nb = t[dev::RT_KEPT_BASES], n_list = src.n_npos ? t[dev::RT_KEPT_NPOS] : 0;
             o.bases_seen = nb;
             if (nb == 0) { // every base of the block is gone: reads of no bases, nothing to map; the set is handed back (see below)

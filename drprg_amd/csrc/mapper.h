@@ -108,14 +108,17 @@ public:
     // The read filter (the rule: include/drprg_hip.h "read filter"; read_qual.hip).  T: the rule's threshold for min_qual_milli
     // (dev::rq_threshold), 0 when there is no quality test.
     // Read trimming (the rule: include/drprg_hip.h "read trimming"; read_trim.hip) rides in the same settings: it runs in front of the
-    // filter, on the same block.  trim_window is 1..32 whenever trim_qual_milli != 0.
+    // filter, on the same block.  trim_window is 1..32 whenever trim_qual_milli != 0.  Adapter trimming (the rule: include/drprg_hip.h
+    // "adapter trimming"; adapter_trim.hip) runs behind the crops and the quality trim, inside the same stage; it needs no quality byte.
     struct ReadFilter {
         uint64_t min_len = 0, max_len = 0, T = 0;
         uint32_t min_qual_milli = 0;
         uint64_t trim_front = 0, trim_tail = 0;
         uint32_t trim_qual_milli = 0, trim_window = 0;
+        dev::AdapterSet adapters {}; // n == 0: none
+        bool crops() const { return trim_front || trim_tail || trim_qual_milli; } // what drprg_hip_read_trim_info counts
         bool filters() const { return min_len || max_len || min_qual_milli; }
-        bool trims() const { return trim_front || trim_tail || trim_qual_milli; }
+        bool trims() const { return crops() || adapters.n != 0; }
         bool any() const { return filters() || trims(); }
         bool use_qual() const { return min_qual_milli != 0; }
         bool wants_qual() const { return min_qual_milli != 0 || trim_qual_milli != 0; } // the ingest carries quality bytes
@@ -123,8 +126,12 @@ public:
     struct TrimOutcome { // drprg_hip_read_trim_info
         uint64_t reads_seen = 0, bases_seen = 0, reads_lost_base = 0, cut_front = 0, cut_tail = 0, qcut_front = 0, qcut_tail = 0, emptied = 0;
     };
+    struct AdapterOutcome { // drprg_hip_adapter_trim_info
+        uint64_t reads_seen = 0, bases_seen = 0, reads_cut = 0, bases_cut = 0, reads_emptied = 0;
+    };
     struct FilterOutcome {
-        TrimOutcome trim; // (all zero when nothing trims)
+        TrimOutcome trim;       // (all zero without a crop or a quality trim)
+        AdapterOutcome adapter; // (all zero without adapters)
         uint64_t reads_seen = 0, bases_seen = 0, dropped_short = 0, dropped_long = 0, dropped_lowq = 0, reads_kept = 0, bases_kept = 0;
         uint64_t mapped_reads = 0, mapped_bases = 0; // what was mapped: the kept reads, or those of them in front of the depth cap
         uint64_t cut_dropped = 0;                    // kept reads behind the depth cap
@@ -147,6 +154,11 @@ public:
     // quality threshold, and must be readable for 64 bytes behind n_bases when it is 16-byte aligned.  res[0..8]: dev::RT_*.  Synchronises `stream`.
     void read_trim_device(const ReadFilter& f, const uint8_t* d_qual, uint32_t bias, const uint64_t* d_offsets, const uint8_t* d_rev, uint64_t n_reads,
         uint64_t n_bases, uint64_t* d_begin, uint64_t* d_end, uint64_t res[9], hipStream_t stream);
+    // The adapter kernels alone on the caller's device buffers (drprg_hip_adapter_trim_device): the bases as text (d_words == null) or as
+    // packed words with their ascending position list; d_begin / d_end hold every read's range and d_end receives the cut ranges' ends.
+    // res[0..4]: reads seen, bases seen, reads cut, bases cut, reads emptied; res[5]: the ranges do not lie inside the reads.  Synchronises `stream`.
+    void adapter_trim_device(const ReadFilter& f, const uint8_t* d_text, const uint32_t* d_words, const uint64_t* d_npos, uint64_t n_npos, const uint64_t* d_offsets,
+        uint64_t n_reads, uint64_t n_bases, const uint64_t* d_begin, uint64_t* d_end, uint64_t res[6], hipStream_t stream, dev::KernelTimer timer = {});
     // Reads that stay in HBM (off by default).  keep_reads(max_bytes > 0): from now on map_host_async copies every block into
     // device memory of its own instead of a staging set and leaves it there -- at most max_bytes of it; one byte more and
     // everything kept is dropped and the staging sets are back.  kept_complete(): every read mapped since keep_reads() /
@@ -408,6 +420,9 @@ private:
         PinnedBuffer<unsigned long long> t_out;
         DeviceBuffer<uint8_t> t_bases, t_qual;
         DeviceBuffer<uint64_t> t_offsets, t_npos;
+        // adapter trimming: every read's smallest matching start, and a packed block's bitmap of non-ACGT bases
+        DeviceBuffer<uint32_t> t_cut;
+        DeviceBuffer<uint16_t> t_nbits;
     };
     struct Stage {
         FilterScratch filt;
@@ -429,10 +444,14 @@ private:
     void run_read_filter(FilterScratch& fs, const ReadFilter& f, const uint8_t* d_qual, uint32_t bias, const uint64_t* d_offsets, uint64_t n_reads,
         uint64_t n_bases, unsigned long long* d_sums, uint8_t* d_flags, hipStream_t stream);
     // room for the trim kernels over n_reads reads (own_ranges: the caller brings no begin / end arrays)
-    void ensure_trim_scratch(FilterScratch& fs, uint64_t n_reads, uint64_t n_npos, bool use_qual, bool own_ranges);
+    // adapters: room for the cut words too, and for a bitmap over bitmap_bases packed bases (0: text, or no listed position)
+    void ensure_trim_scratch(FilterScratch& fs, uint64_t n_reads, uint64_t n_npos, bool use_qual, bool own_ranges, bool adapters = false, uint64_t bitmap_bases = 0);
+    // the bases of a block for adapter_points_kernel; a packed block's bitmap is made on `stream` first (ensure_trim_scratch gave it room)
+    dev::AdapterPoints adapter_points(FilterScratch& fs, const uint8_t* d_bases, bool packed, const uint64_t* d_npos, uint64_t n_npos, uint64_t n_bases, hipStream_t stream);
     // queues the trim kernels on `stream`; fs.t_out holds dev::RT_* once the stream has been waited for, fs.t_offsets the new offsets
     void run_read_trim(FilterScratch& fs, const ReadFilter& f, const uint8_t* d_qual, uint32_t bias, const uint64_t* d_offsets, const uint8_t* d_rev,
-        uint64_t n_reads, uint64_t n_bases, uint64_t* d_begin, uint64_t* d_end, const uint64_t* d_npos, uint64_t n_npos, hipStream_t stream);
+        uint64_t n_reads, uint64_t n_bases, uint64_t* d_begin, uint64_t* d_end, const uint64_t* d_npos, uint64_t n_npos, hipStream_t stream,
+        const dev::AdapterPoints* pts = nullptr);
     FilterScratch filter_api_; // read_filter_device's and read_trim_device's own (as bam_api_)
     BamScratch bam_api_; // pack_bam_on_device's own (the caller's stream is not ordered with the context's)
     uint64_t bam_blocks_ = 0;

@@ -9,6 +9,7 @@
 // (include/drprg_hip.h "duplicate reads"),
 // --min-read-len L, --max-read-len L and --min-read-qual Q on both (include/drprg_hip.h "read filter"),
 // --trim-front N, --trim-tail N, --trim-qual Q and --trim-window W on both (include/drprg_hip.h "read trimming"),
+// --adapter SEQ (repeatable), --adapter-error E and --adapter-min-overlap O on both (include/drprg_hip.h "adapter trimming"),
 // and writes the files drprg then looks for: <prg>.k<K>.w<W>.idx + kmer_prgs/ (index),
 // <dir>/denovo_paths.txt (discover, /root/reference/src/lib.rs:569-577),
 // <out>/pandora_genotyped.vcf (map, /root/reference/src/lib.rs:644-646).
@@ -24,6 +25,8 @@
 #include <string>
 #include <sys/stat.h>
 #include <vector>
+
+#include "adapter_args.h"
 
 namespace {
 
@@ -58,6 +61,7 @@ struct Args {
     // --trim-front N, --trim-tail N, --trim-qual Q, --trim-window W: read trimming (include/drprg_hip.h "read trimming"); 0 = not set
     uint64_t trim_front = 0, trim_tail = 0;
     uint32_t trim_qual_milli = 0, trim_window = 0;
+    drprg::AdapterArgs adapters; // --adapter SEQ, --adapter-error E, --adapter-min-overlap O (include/drprg_hip.h "adapter trimming")
     std::string outdir = "pandora", vcf_refs;
     std::vector<std::string> positional;
     int device = 0;
@@ -77,6 +81,7 @@ void usage()
         "  pandora map      [--genotype] [--local] [--gt-conf X] [-v] [-o DIR] [-g SIZE] [--max-covg N | --subsample-covg D [--seed S]]\n"
         "                   [--dedup] [--min-read-len L] [--max-read-len L] [--min-read-qual Q]\n"
         "                   [--trim-front N] [--trim-tail N] [--trim-qual Q [--trim-window W]]\n"
+        "                   [--adapter SEQ]... [--adapter-error E] [--adapter-min-overlap O]\n"
         "                   [--vcf-refs FASTA] [-t N] [-w W] [-k K] [-c N] [-I] [-K] [-e RATE] [--max-diff N] <prg> <reads>\n"
         "  pandora discover [same mapping options] <prg> <query.tsv>\n"
         "  --max-covg N: reads are taken in file order up to and including the first one at which (N + 1) x SIZE bases are reached;\n"
@@ -101,6 +106,10 @@ void usage()
         "                default 4) whose MEAN PHRED VALUE is at least Q, then end bases below Q -- on the device, in front of the read filter\n"
         "                and everything else: the run is that of a file of the trimmed reads.  A read trimmed to nothing stays a read of no\n"
         "                bases.  --trim-qual needs qualities: FASTA, or a BAM record without them, is an error under it.\n"
+        "  --adapter SEQ (up to 4 times; 1 to 64 letters ACGT), --adapter-error E (0 to 0.5, default 0.1), --adapter-min-overlap O (default 3):\n"
+        "                every read is cut at the leftmost start at which an adapter matches with at most floor(c * E) substitutions over\n"
+        "                the c = min(adapter, rest of the read) letters compared, c >= O -- on the device, behind --trim-* and in front of\n"
+        "                everything else.  No indels, no 5' adapter, no pair overlap.  Needs no qualities.\n"
         "  <reads>: FASTA or FASTQ, plain or gzip; or BAM (secondary and supplementary records are skipped, reverse-strand records are\n"
         "           reverse-complemented, alignments are ignored, qualities are looked at by --min-read-qual and --trim-qual alone)\n"
         "environment: DRPRG_HIP_DEVICE selects the GPU (default 0); DRPRG_HIP_DEVICES=0,1,.. maps on several GPUs of the node\n");
@@ -170,6 +179,16 @@ Args parse(int argc, char** argv)
             if (end == v || *end || n < 1 || n > 32) die(std::string("--trim-window needs a window of 1 to 32 bases, not ") + v, 2);
             a.trim_window = (uint32_t)n;
         }
+        else if (s == "--adapter") {
+            const std::string e = a.adapters.add(need(i));
+            if (!e.empty()) die(e, 2);
+        } else if (s == "--adapter-error") {
+            const std::string e = a.adapters.set_error(need(i));
+            if (!e.empty()) die(e, 2);
+        } else if (s == "--adapter-min-overlap") {
+            const std::string e = a.adapters.set_overlap(need(i));
+            if (!e.empty()) die(e, 2);
+        }
         else if (s == "--dedup") a.dedup = true;
         else if (s == "-o" || s == "--outdir") a.outdir = need(i);
         else if (s == "--vcf-refs") a.vcf_refs = need(i);
@@ -195,6 +214,7 @@ Args parse(int argc, char** argv)
     if (a.subsample) a.max_covg = 4294967295ull; // the default cap gives way
     if (a.max_read_len && a.max_read_len < a.min_read_len) die("--max-read-len is below --min-read-len: no read can pass", 2);
     if (a.trim_window && !a.trim_qual_milli) die("--trim-window belongs to --trim-qual", 2);
+    if (const std::string e = a.adapters.check(); !e.empty()) die(e, 2);
     if (const char* d = std::getenv("DRPRG_HIP_DEVICE")) a.device = std::atoi(d);
     return a;
 }
@@ -241,6 +261,10 @@ drprg_hip_ctx* open_ctx(const Args& a)
     if (int rc = drprg_hip_set_max_covg(ctx, a.max_covg)) die(drprg_hip_last_error(ctx), -rc);
     if (int rc = drprg_hip_set_read_filter(ctx, a.min_read_len, a.max_read_len, a.min_read_qual_milli)) die(drprg_hip_last_error(ctx), -rc);
     if (int rc = drprg_hip_set_read_trim(ctx, a.trim_front, a.trim_tail, a.trim_qual_milli, a.trim_window)) die(drprg_hip_last_error(ctx), -rc);
+    if (a.adapters.any()) {
+        const std::vector<const char*> seqs = a.adapters.pointers();
+        if (int rc = drprg_hip_set_adapters(ctx, seqs.data(), (uint32_t)seqs.size(), a.adapters.error_milli, a.adapters.min_overlap)) die(drprg_hip_last_error(ctx), -rc);
+    }
     drprg_hip_set_threads(ctx, a.threads);
     drprg_hip_set_input_format(ctx, packed_input()); // the parser threads pack the reads to 2 bits (DRPRG_HIP_INPUT=ascii: one byte per base)
     return ctx;
@@ -289,7 +313,8 @@ std::string run_tag(const Args& a, const std::string& reads)
         + (a.trim_front || a.trim_tail || a.trim_qual_milli ? "|T" + std::to_string((unsigned long long)a.trim_front) + "/"
                   + std::to_string((unsigned long long)a.trim_tail) + "/" + std::to_string(a.trim_qual_milli) + "/"
                   + std::to_string(a.trim_qual_milli ? (a.trim_window ? a.trim_window : 4u) : 0u)
-                                                            : std::string());
+                                                            : std::string())
+        + (a.adapters.any() ? a.adapters.tag() : std::string());
 }
 
 // The reads stay in HBM after the mapping pass: up to DRPRG_HIP_KEEP_READS_GB per device, default 32, 0 = off.  --subsample-covg and --dedup work on
@@ -357,6 +382,9 @@ void report_filter(drprg_hip_ctx* ctx, const Args& a)
         std::printf("[pandora-hip] read trimming: reads_seen=%llu bases_seen=%llu reads_lost_base=%llu cut_front=%llu cut_tail=%llu qual_cut_front=%llu "
                     "qual_cut_tail=%llu reads_emptied=%llu\n", (unsigned long long)fi[0], (unsigned long long)fi[1], (unsigned long long)fi[2],
             (unsigned long long)fi[3], (unsigned long long)fi[4], (unsigned long long)fi[5], (unsigned long long)fi[6], (unsigned long long)fi[7]);
+    if (a.verbose && a.adapters.any() && drprg_hip_adapter_trim_info(ctx, fi) == 0)
+        std::printf("[pandora-hip] adapter trimming: reads_seen=%llu bases_seen=%llu reads_cut=%llu bases_cut=%llu reads_emptied=%llu\n", (unsigned long long)fi[0],
+            (unsigned long long)fi[1], (unsigned long long)fi[2], (unsigned long long)fi[3], (unsigned long long)fi[4]);
     if (!a.verbose || !(a.min_read_len || a.max_read_len || a.min_read_qual_milli) || drprg_hip_read_filter_info(ctx, fi) != 0) return;
     std::printf("[pandora-hip] read filter: reads_seen=%llu bases_seen=%llu dropped_short=%llu dropped_long=%llu dropped_low_qual=%llu reads_kept=%llu "
                 "bases_kept=%llu (T=%llu)\n", (unsigned long long)fi[0], (unsigned long long)fi[1], (unsigned long long)fi[2], (unsigned long long)fi[3],

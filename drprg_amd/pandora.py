@@ -282,6 +282,39 @@ class Context:
         _check(rc, self._h)
         return self.last_trim_out[:3]
 
+    # ---- adapter trimming (include/drprg_hip.h: drprg_hip_set_adapters) -------------------------
+    @staticmethod
+    def error_milli(error):
+        """a decimal error rate with at most three places (number or text, as --adapter-error takes it) as thousandths; ValueError otherwise"""
+        from decimal import Decimal
+        milli = Decimal(str(error)) * 1000
+        if milli != milli.to_integral_value() or milli < 0:
+            raise ValueError(f"an error rate is a decimal in [0, 0.5] with at most three places, not {error!r}")
+        return int(milli)
+
+    def set_adapters(self, seqs, error="0.1", min_overlap=0):
+        """from the next map_fastx on, every read is cut at the leftmost start at which one of `seqs` (1 to 4 sequences of 1 to 64 letters
+        ACGT) matches with at most floor(c * error) substitutions over the c letters compared, c >= min_overlap (0: 3, or the shortest
+        adapter's length); behind the crops and the quality trim; an empty list clears the settings"""
+        seqs = [s.encode() if isinstance(s, str) else bytes(s) for s in (seqs or [])]
+        arr = (C.c_char_p * max(len(seqs), 1))(*seqs)
+        _check(lib.drprg_hip_set_adapters(self._h, arr, len(seqs), self.error_milli(error), int(min_overlap)), self._h)
+
+    def adapter_trim_info(self):
+        out = (C.c_uint64 * 5)()
+        _check(lib.drprg_hip_adapter_trim_info(self._h, out), self._h)
+        names = ("reads_seen", "bases_seen", "reads_cut", "bases_cut", "reads_emptied")
+        return dict(zip(names, (int(x) for x in out)))
+
+    def adapter_trim_device(self, d_text, d_words, d_npos, n_npos, d_offsets, n_reads, n_bases, d_begin, d_end, stream=None):
+        """the adapter kernels alone on device buffers (addresses as integers): the bases as text (d_words None) or as packed words with
+        their ascending position list (d_text None; d_npos may be None when n_npos is 0); d_begin / d_end (u64 per read) hold every read's
+        range and d_end receives the cut ends; returns the call's (reads seen, bases seen, reads cut, bases cut, reads emptied)"""
+        out = (C.c_uint64 * 5)()
+        _check(lib.drprg_hip_adapter_trim_device(self._h, d_text, d_words, d_npos, int(n_npos), d_offsets, int(n_reads), int(n_bases), d_begin, d_end, out,
+                                                 stream), self._h)
+        return tuple(int(x) for x in out)
+
     def select_reads(self, anchors, A, window_bytes=0):
         """the resident reads in which one of `anchors` (k-mers of A bases as integers, 2 bits per base, A 0 C 1 G 2 T 3, first base high)
         starts -- the selection discover_reads runs on the device (drprg_hip_select_reads); returns (bases u8, offsets u64, ids u64 =

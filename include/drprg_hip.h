@@ -450,6 +450,43 @@ int drprg_hip_set_read_trim(drprg_hip_ctx* ctx, uint64_t front, uint64_t tail, u
 int drprg_hip_read_trim_info(drprg_hip_ctx* ctx, uint64_t out[8]);
 int drprg_hip_read_trim_device(drprg_hip_ctx* ctx, const void* d_qual, uint32_t qual_bias, const void* d_offsets, const void* d_rev, uint64_t n_reads,
     uint64_t n_bases, void* d_begin, void* d_end, uint64_t out[4], void* hip_stream);
+/* ---- Adapter trimming: sequencing adapters cut off read ends on the device, as the reads arrive.  THIS BUILD'S OWN RULE, stated from memory
+ * of what fastp and cutadapt -a do with a 3' adapter; neither pandora nor drprg has one and nothing in them pins it.
+ *   Settings, per context: 1 to 4 adapter sequences A_1 .. A_n, each 1 to 64 letters of ACGTacgt and no other; an error rate E in [0, 0.5]
+ *   held as an integer per-mille e (E = 0.1 is e = 100, the executables' default); a minimum overlap O, 1 .. the length of the shortest
+ *   adapter (given as 0: 3, or that length if it is smaller).
+ *   Order.  Adapter trimming runs BEHIND the fixed crops and the quality trim of "read trimming", where fastp and cutadapt put it: it works
+ *   on the range [x, y) those left, in read orientation, n = y - x.  For a BAM record with flag 0x10 that is the read as the device has
+ *   already restored it: the bases need no mirror.
+ *   Match.  For an adapter A of m letters and a start p in 0 .. n - 1: c = min(m, n - p); p is a MATCH iff c >= O and the number of j < c
+ *   with read[x + p + j] != A[j] is at most floor(c * e / 1000).  The comparison is case-insensitive; a read base that is not ACGT differs
+ *   from every adapter letter.  A window never reaches past y, so never into the next read.
+ *   Cut.  The read is cut at the smallest matching p over all adapters: end = x + p.  A read cut to nothing stays a read of no bases, as
+ *   with trimming; nothing is dropped or reordered.  There are NO indels (cutadapt's alignment has them), there is no 5' and no anchored
+ *   adapter, and no pair-overlap detection (fastp's default for paired reads): substitutions at a fixed start only.
+ *   Invariance.  Leftmost is a minimum: the result is bit-identical whatever the launch geometry, the thread count and the input form.
+ *   Adapter trimming runs inside the trim stage of drprg_hip_map_fastx, so everything "read trimming" says about what lies behind it holds:
+ *   the read filter, the depth cap, the resident set, drprg_hip_dedup, drprg_hip_subsample, discover and the genotyper see cut reads.  It
+ *   needs no quality byte: FASTA and BAM records without qualities are served, and no quality byte is parsed, copied or moved unless
+ *   another setting needs them.  drprg_hip_read_trim_info keeps counting crops and quality alone.  drprg_hip_map_host* and
+ *   drprg_hip_map_device* return -EINVAL while adapters are set.  Once an adapter cut a base, drprg_hip_discover_reads takes its reads
+ *   from HBM and returns -ENODATA (-61) when the sample is not resident.  With no adapter set nothing of this exists: no launch, no wait.
+ *   drprg_hip_set_adapters: applies from the next drprg_hip_map_fastx; n == 0 clears (seqs may be NULL then); a reset keeps the settings.
+ *     -EINVAL for n > 4, a NULL or empty sequence, one over 64 letters or with a letter outside ACGTacgt, error_milli > 500 and
+ *     min_overlap above the length of the shortest adapter.
+ *   drprg_hip_adapter_trim_info: since the last reset, out[0..4] = reads seen, bases seen (behind crops and quality), reads cut, bases
+ *     cut, reads emptied by the adapter (they still had a base before it).
+ *   drprg_hip_adapter_trim_device: the two adapter kernels alone on caller-owned device buffers, under the stream rule of the other device
+ *     entries.  The bases as text (d_text: n_bases bytes; when 16-byte aligned the 64 bytes behind them must be readable; any other address
+ *     is read byte by byte and never behind n_bases; d_words NULL) or as packed words (d_words: u32[ceil(n_bases / 16)], the form of
+ *     drprg_hip_pack_device, with d_npos: n_npos ascending positions of the bases that are not ACGT; d_text NULL).  d_offsets: u64[n_reads
+ *     + 1].  d_begin, d_end: u64[n_reads], every read's range [x, y) counted from its first base; d_end[i] becomes x + p for a cut read.
+ *     out[0..4]: the five counts of this call.  -EINVAL when no adapter is set, when the offsets do not ascend to n_bases or a range does
+ *     not lie inside its read. */
+int drprg_hip_set_adapters(drprg_hip_ctx* ctx, const char* const* seqs, uint32_t n, uint32_t error_milli, uint32_t min_overlap);
+int drprg_hip_adapter_trim_info(drprg_hip_ctx* ctx, uint64_t out[5]);
+int drprg_hip_adapter_trim_device(drprg_hip_ctx* ctx, const void* d_text, const void* d_words, const void* d_npos, uint64_t n_npos, const void* d_offsets,
+    uint64_t n_reads, uint64_t n_bases, const void* d_begin, void* d_end, uint64_t out[5], void* hip_stream);
 /* The read selection drprg_hip_discover_reads uses when the reads are resident, on its own: for every device of the context, in order,
  * every kept read in which a k-mer of `anchors` STARTS (anchors: n_anchors k-mers of A bases, 2 bits per base, A 0 C 1 G 2 T 3, first base
  * in the high bits; any order, duplicates allowed).  A block's reads are one base stream: read r of a block is returned iff for some p with
