@@ -137,6 +137,7 @@ struct drprg_hip_ctx {
     Mapper::FilterOutcome filter_counts;
     Mapper::TrimOutcome trim_counts; // drprg_hip_read_trim_info (the settings ride in read_filter)
     Mapper::AdapterOutcome adapter_counts; // drprg_hip_adapter_trim_info (the settings ride in read_filter too)
+    Mapper::AdapterOutcome front_counts;   // drprg_hip_front_adapter_info
     std::mutex filter_mu;
     // (the page-locked ingest blocks of drprg_hip_map_fastx are recycled process-wide: PinPool above)
     // multi-device context: RCCL communicators of its devices (created on first use; empty when RCCL is not used)
@@ -516,6 +517,9 @@ int drprg_hip_map_fastx(drprg_hip_ctx* ctx, const char* reads_path)
         Mapper::AdapterOutcome& at = ctx->adapter_counts;
         at.reads_seen += o.adapter.reads_seen; at.bases_seen += o.adapter.bases_seen; at.reads_cut += o.adapter.reads_cut; at.bases_cut += o.adapter.bases_cut;
         at.reads_emptied += o.adapter.reads_emptied;
+        Mapper::AdapterOutcome& ft = ctx->front_counts;
+        ft.reads_seen += o.front.reads_seen; ft.bases_seen += o.front.bases_seen; ft.reads_cut += o.front.reads_cut; ft.bases_cut += o.front.bases_cut;
+        ft.reads_emptied += o.front.reads_emptied;
         kept_reads += o.mapped_reads;
         kept_bases += o.mapped_bases;
         return o;
@@ -660,7 +664,7 @@ int drprg_hip_set_threads(drprg_hip_ctx* ctx, int threads)
 // The entry points that carry no qualities: while a filter is set they refuse, rather than map unfiltered reads without saying so.
 static void refuse_unfiltered(const drprg_hip_ctx* ctx, const char* entry)
 {
-    if (ctx->read_filter.adapters.n)
+    if (ctx->read_filter.any_adapters())
         throw Error(DRPRG_EINVAL, std::string(entry) + ": adapters are set (drprg_hip_set_adapters) and adapter trimming runs in drprg_hip_map_fastx; this entry "
                                                       "would map the reads with their adapters (clear them with drprg_hip_set_adapters(ctx, NULL, 0, 0, 0))");
     if (ctx->read_filter.trims())
@@ -761,18 +765,13 @@ int drprg_hip_read_trim_device(drprg_hip_ctx* ctx, const void* d_qual, uint32_t 
 }
 
 // ---- adapter trimming (the rule: include/drprg_hip.h "adapter trimming") ----------------------------------------------------------
-int drprg_hip_set_adapters(drprg_hip_ctx* ctx, const char* const* seqs, uint32_t n, uint32_t error_milli, uint32_t min_overlap)
+// one side's list into the kernels' form; shortest: lowered to the shortest adapter's length
+static dev::AdapterSet adapter_list(const char* const* seqs, uint32_t n, uint32_t& shortest)
 {
-    API_BEGIN(ctx)
     dev::AdapterSet ad {};
-    if (n == 0) { // cleared
-        ctx->read_filter.adapters = ad;
-        return DRPRG_OK;
-    }
+    if (n == 0) return ad;
     if (!seqs) throw Error(DRPRG_EINVAL, "adapter trimming: null adapter list");
     if (n > dev::AD_MAX_ADAPTERS) throw Error(DRPRG_EINVAL, "adapter trimming: at most 4 adapters");
-    if (error_milli > dev::AD_MAX_ERROR_MILLI) throw Error(DRPRG_EINVAL, "adapter trimming: the error rate is 0..0.5");
-    uint32_t shortest = dev::AD_MAX_LEN;
     for (uint32_t a = 0; a < n; ++a) {
         if (!seqs[a]) throw Error(DRPRG_EINVAL, "adapter trimming: null adapter");
         const size_t m = std::strlen(seqs[a]);
@@ -786,11 +785,64 @@ int drprg_hip_set_adapters(drprg_hip_ctx* ctx, const char* const* seqs, uint32_t
         if (m > ad.max_len) ad.max_len = (uint32_t)m;
         if (m < shortest) shortest = (uint32_t)m;
     }
-    if (min_overlap > shortest) throw Error(DRPRG_EINVAL, "adapter trimming: the minimum overlap is 1..the length of the shortest adapter");
     ad.n = n;
+    return ad;
+}
+
+static void clear_adapters(drprg_hip_ctx* ctx)
+{
+    Mapper::ReadFilter& f = ctx->read_filter;
+    f.adapters = dev::AdapterSet {};
+    f.front_adapters = dev::AdapterSet {};
+    f.eq3 = f.eq5 = dev::AdapterEq {};
+    f.adapter_indels = false;
+}
+
+int drprg_hip_set_adapters(drprg_hip_ctx* ctx, const char* const* seqs, uint32_t n, uint32_t error_milli, uint32_t min_overlap)
+{
+    API_BEGIN(ctx)
+    if (n == 0) { // cleared
+        clear_adapters(ctx);
+        return DRPRG_OK;
+    }
+    if (error_milli > dev::AD_MAX_ERROR_MILLI) throw Error(DRPRG_EINVAL, "adapter trimming: the error rate is 0..0.5");
+    uint32_t shortest = dev::AD_MAX_LEN;
+    dev::AdapterSet ad = adapter_list(seqs, n, shortest);
+    if (min_overlap > shortest) throw Error(DRPRG_EINVAL, "adapter trimming: the minimum overlap is 1..the length of the shortest adapter");
     ad.error_milli = error_milli;
     ad.min_overlap = min_overlap ? min_overlap : std::min(dev::AD_DEFAULT_MIN_OVERLAP, shortest);
+    clear_adapters(ctx); // (the plain rule: no 5' adapter, no indels)
     ctx->read_filter.adapters = ad;
+    API_END(ctx)
+}
+
+int drprg_hip_set_adapters2(drprg_hip_ctx* ctx, const char* const* seqs3, uint32_t n3, const char* const* seqs5, uint32_t n5, uint32_t error_milli,
+    uint32_t min_overlap, uint32_t flags)
+{
+    API_BEGIN(ctx)
+    if (flags & ~dev::AE_FLAG_INDELS) throw Error(DRPRG_EINVAL, "adapter trimming: unknown flag bits");
+    if (n3 == 0 && n5 == 0) { // cleared
+        clear_adapters(ctx);
+        return DRPRG_OK;
+    }
+    const bool indels = (flags & dev::AE_FLAG_INDELS) != 0;
+    if (n5 && !indels) throw Error(DRPRG_EINVAL, "adapter trimming: 5' adapters exist only under the indel rule (flag bit 0)");
+    if (error_milli > dev::AD_MAX_ERROR_MILLI) throw Error(DRPRG_EINVAL, "adapter trimming: the error rate is 0..0.5");
+    uint32_t shortest = dev::AD_MAX_LEN;
+    dev::AdapterSet ad3 = adapter_list(seqs3, n3, shortest), ad5 = adapter_list(seqs5, n5, shortest);
+    if (min_overlap > shortest) throw Error(DRPRG_EINVAL, "adapter trimming: the minimum overlap is 1..the length of the shortest adapter of either side");
+    const uint32_t O = min_overlap ? min_overlap : std::min(dev::AD_DEFAULT_MIN_OVERLAP, shortest);
+    if (ad3.n) { ad3.error_milli = error_milli; ad3.min_overlap = O; }
+    if (ad5.n) { ad5.error_milli = error_milli; ad5.min_overlap = O; }
+    clear_adapters(ctx);
+    Mapper::ReadFilter& f = ctx->read_filter;
+    f.adapters = ad3;
+    if (indels) {
+        f.adapter_indels = true;
+        f.front_adapters = dev::ae_reversed(ad5);
+        f.eq3 = dev::ae_make_eq(f.adapters);
+        f.eq5 = dev::ae_make_eq(f.front_adapters);
+    }
     API_END(ctx)
 }
 
@@ -816,6 +868,31 @@ int drprg_hip_adapter_trim_device(drprg_hip_ctx* ctx, const void* d_text, const 
         n_bases, (const uint64_t*)d_begin, (uint64_t*)d_end, res, (hipStream_t)hip_stream);
     for (int i = 0; i < 5; ++i) out[i] = res[i];
     if (res[5]) throw Error(DRPRG_EINVAL, "adapter trimming: the offsets do not ascend to n_bases, or a range does not lie inside its read");
+    API_END(ctx)
+}
+
+int drprg_hip_front_adapter_info(drprg_hip_ctx* ctx, uint64_t out[5])
+{
+    API_BEGIN(ctx)
+    if (!out) throw Error(DRPRG_EINVAL, "null output");
+    std::lock_guard<std::mutex> g(ctx->filter_mu);
+    const Mapper::AdapterOutcome& t = ctx->front_counts;
+    out[0] = t.reads_seen; out[1] = t.bases_seen; out[2] = t.reads_cut; out[3] = t.bases_cut; out[4] = t.reads_emptied;
+    API_END(ctx)
+}
+
+int drprg_hip_adapter_trim_device2(drprg_hip_ctx* ctx, const void* d_text, const void* d_words, const void* d_npos, uint64_t n_npos, const void* d_offsets,
+    uint64_t n_reads, uint64_t n_bases, void* d_begin, void* d_end, uint64_t out[10], void* hip_stream)
+{
+    API_BEGIN(ctx)
+    Mapper& m = need_mapper(ctx);
+    if (!out) throw Error(DRPRG_EINVAL, "null output");
+    if (d_text && d_words) throw Error(DRPRG_EINVAL, "adapter trimming: the bases come as text or as packed words, not both");
+    uint64_t res[11];
+    m.adapter_trim_device2(ctx->read_filter, (const uint8_t*)d_text, (const uint32_t*)d_words, (const uint64_t*)d_npos, n_npos, (const uint64_t*)d_offsets, n_reads,
+        n_bases, (uint64_t*)d_begin, (uint64_t*)d_end, res, (hipStream_t)hip_stream);
+    for (int i = 0; i < 10; ++i) out[i] = res[i];
+    if (res[10]) throw Error(DRPRG_EINVAL, "adapter trimming: the offsets do not ascend to n_bases, or a range does not lie inside its read");
     API_END(ctx)
 }
 
@@ -1163,6 +1240,7 @@ int drprg_hip_reset(drprg_hip_ctx* ctx)
     ctx->filter_counts = Mapper::FilterOutcome(); // (the settings stay, as the depth cap does)
     ctx->trim_counts = Mapper::TrimOutcome();
     ctx->adapter_counts = Mapper::AdapterOutcome();
+    ctx->front_counts = Mapper::AdapterOutcome();
     API_END(ctx)
 }
 
@@ -1408,7 +1486,7 @@ int drprg_hip_discover_reads(drprg_hip_ctx* ctx, const char* reads_path, const c
     ResidentReads resident;
     ctx->last_discover_resident = reads_resident(ctx, reads_path);
     // (the pass over the file knows nothing of the read filter: rather than pile up reads the mapping never saw, say so)
-    if (!ctx->last_discover_resident && ctx->adapter_counts.reads_cut)
+    if (!ctx->last_discover_resident && (ctx->adapter_counts.reads_cut || ctx->front_counts.reads_cut))
         throw Error(DRPRG_ENODATA, "discover: adapter trimming cut bases off reads of this sample and the cut reads are not resident in device memory; a pass "
                                    "over the file would pile up reads with their adapters (raise DRPRG_HIP_KEEP_READS_GB, or cut the file first)");
     if (!ctx->last_discover_resident && ctx->trim_counts.reads_lost_base)

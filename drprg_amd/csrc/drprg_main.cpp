@@ -111,11 +111,14 @@ void usage()
         "              [-C MIN_CLUSTER_SIZE] [--debug] [-v] [-t THREADS] [--rebuild-index] [--subsample-covg D [--seed S]]\n"
         "              [--dedup] [--min-read-len L] [--max-read-len L] [--min-read-qual Q]\n"
         "              [--trim-front N] [--trim-tail N] [--trim-qual Q [--trim-window W]]\n"
-        "              [--adapter SEQ]... [--adapter-error E] [--adapter-min-overlap O]\n"
+        "              [--adapter SEQ]... [--adapter-error E] [--adapter-min-overlap O] [--adapter-indels] [--front-adapter SEQ]...\n"
         "--adapter SEQ (up to 4 times; 1 to 64 letters ACGT), --adapter-error E (0 to 0.5, default 0.1), --adapter-min-overlap O (default 3):\n"
         "              every read is cut at the leftmost start at which an adapter matches with at most floor(c * E) substitutions over the\n"
         "              c = min(adapter, rest of the read) letters compared, c >= O -- on the device, behind --trim-* and in front of\n"
-        "              everything else.  No indels, no 5' adapter, no pair overlap.  Needs no qualities.\n"
+        "              everything else.  Needs no qualities.\n"
+        "--adapter-indels: an occurrence may carry insertions and deletions too (edit distance at most floor(m * E) over the whole adapter).\n"
+        "--front-adapter SEQ (up to 4 times; needs --adapter-indels): 5' adapters, cut off the reads' starts behind the 3' cut.\n"
+        "              Still missing: anchored adapters, pair overlap, indels inside an adapter that the read's end cuts short.\n"
         "--trim-front N, --trim-tail N, --trim-qual Q, --trim-window W: every read loses N bases at its start and N at its end and, under\n"
         "              --trim-qual (a decimal Phred value in (0, 93]), what lies outside its first and last window of W bases (1..32, default\n"
         "              4) whose MEAN PHRED VALUE is at least Q, then end bases below Q -- on the device, in front of the read filter and\n"
@@ -261,7 +264,11 @@ int main(int argc, char** argv)
         else if (a == "--adapter") {
             const std::string e = adapters.add(need(i));
             if (!e.empty()) die(e, 2);
-        } else if (a == "--adapter-error") {
+        } else if (a == "--front-adapter") {
+            const std::string e = adapters.add_front(need(i));
+            if (!e.empty()) die(e, 2);
+        } else if (a == "--adapter-indels") adapters.indels = true;
+        else if (a == "--adapter-error") {
             const std::string e = adapters.set_error(need(i));
             if (!e.empty()) die(e, 2);
         } else if (a == "--adapter-min-overlap") {
@@ -275,7 +282,6 @@ int main(int argc, char** argv)
     if (max_read_len && max_read_len < min_read_len) die("--max-read-len is below --min-read-len: no read can pass", 2);
     if (trim_window && !trim_qual_milli) die("--trim-window belongs to --trim-qual", 2);
     if (const std::string e = adapters.check(); !e.empty()) die(e, 2);
-    const std::vector<const char*> adapter_seqs = adapters.pointers();
     if (index.empty() || input.empty()) {
         usage();
         return 2;
@@ -330,7 +336,7 @@ int main(int argc, char** argv)
     if (int rc = drprg_hip_set_read_filter(ctx, min_read_len, max_read_len, min_read_qual_milli)) die(drprg_hip_last_error(ctx), -rc);
     if (int rc = drprg_hip_set_read_trim(ctx, trim_front, trim_tail, trim_qual_milli, trim_window)) die(drprg_hip_last_error(ctx), -rc);
     if (adapters.any())
-        if (int rc = drprg_hip_set_adapters(ctx, adapter_seqs.data(), (uint32_t)adapter_seqs.size(), adapters.error_milli, adapters.min_overlap)) die(drprg_hip_last_error(ctx), -rc);
+        if (int rc = adapters.set_on(ctx, drprg_hip_set_adapters, drprg_hip_set_adapters2)) die(drprg_hip_last_error(ctx), -rc);
     // The reads stay in HBM after the mapping pass (up to DRPRG_HIP_KEEP_READS_GB per device, default 32, 0 = off): discover takes
     // the few reads it needs from there and a novel variant maps them again from there -- the file is read once.
     double keep_gb = 32;
@@ -355,8 +361,11 @@ int main(int argc, char** argv)
     }
     if (verbose && adapters.any()) {
         uint64_t ai[5] = {};
-        if (drprg_hip_adapter_trim_info(ctx, ai) == 0)
+        if (!adapters.seqs.empty() && drprg_hip_adapter_trim_info(ctx, ai) == 0)
             std::fprintf(stderr, "[drprg-hip +%.3fs] adapter trimming: reads_seen=%llu bases_seen=%llu reads_cut=%llu bases_cut=%llu reads_emptied=%llu\n", since_start(),
+                (unsigned long long)ai[0], (unsigned long long)ai[1], (unsigned long long)ai[2], (unsigned long long)ai[3], (unsigned long long)ai[4]);
+        if (!adapters.front.empty() && drprg_hip_front_adapter_info(ctx, ai) == 0)
+            std::fprintf(stderr, "[drprg-hip +%.3fs] front adapter trimming: reads_seen=%llu bases_seen=%llu reads_cut=%llu bases_cut=%llu reads_emptied=%llu\n", since_start(),
                 (unsigned long long)ai[0], (unsigned long long)ai[1], (unsigned long long)ai[2], (unsigned long long)ai[3], (unsigned long long)ai[4]);
     }
     if (verbose && (min_read_len || max_read_len || min_read_qual_milli)) {
@@ -416,8 +425,7 @@ int main(int argc, char** argv)
                 if (int rc = drprg_hip_set_read_filter(next, min_read_len, max_read_len, min_read_qual_milli)) die(drprg_hip_last_error(next), -rc);
                 if (int rc = drprg_hip_set_read_trim(next, trim_front, trim_tail, trim_qual_milli, trim_window)) die(drprg_hip_last_error(next), -rc);
                 if (adapters.any())
-                    if (int rc = drprg_hip_set_adapters(next, adapter_seqs.data(), (uint32_t)adapter_seqs.size(), adapters.error_milli, adapters.min_overlap))
-                        die(drprg_hip_last_error(next), -rc);
+                    if (int rc = adapters.set_on(next, drprg_hip_set_adapters, drprg_hip_set_adapters2)) die(drprg_hip_last_error(next), -rc);
                 // the reads again, against the updated index: from HBM if the first context kept them all, else from the file
                 const int from_hbm = drprg_hip_map_resident(next, ctx);
                 if (from_hbm != 0 && from_hbm != -61 /* ENODATA */) die(drprg_hip_last_error(next), -from_hbm);

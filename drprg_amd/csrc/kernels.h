@@ -12,6 +12,7 @@
 #endif
 #include "dedup_word.h"
 #include "adapter_piece.h"
+#include "adapter_edit.h"
 
 namespace drprg {
 namespace dev {
@@ -457,7 +458,9 @@ enum {
     RT_BAD_AT = 7 /* first bad quality byte + 1, 0, or ~0: offsets at odds with n_bases */, RT_KEPT_NPOS = 8 /* out only */, RT_OFFSETS = 9 /* work only */,
     // adapter trimming (adapter_trim.hip), all zero without adapters: bases in the ranges the crops and the quality trim left, reads and
     // bases cut, reads emptied
-    RT_AD_BASES_SEEN = 10, RT_AD_READS_CUT = 11, RT_AD_BASES_CUT = 12, RT_AD_EMPTIED = 13, RT_WORDS = 14 /* words of work and of out */
+    RT_AD_BASES_SEEN = 10, RT_AD_READS_CUT = 11, RT_AD_BASES_CUT = 12, RT_AD_EMPTIED = 13,
+    // the same four for 5' adapters (adapter_edit.hip): the bases seen are those behind the 3' cut
+    RT_FA_BASES_SEEN = 14, RT_FA_READS_CUT = 15, RT_FA_BASES_CUT = 16, RT_FA_EMPTIED = 17, RT_WORDS = 18 /* words of work and of out */
 };
 // adapter_trim.hip: what adapter_points_kernel searches.  The bases as text (n_bases + 64 bytes readable when 16-byte aligned; any other
 // address is read byte by byte and never behind n_bases) or, when words != null, as a packed batch's words (ceil(n_bases / 16)) with
@@ -478,6 +481,13 @@ uint32_t adapter_trim_tiles(uint64_t n_bases);
 // timer: around adapter_points_kernel alone
 hipError_t launch_adapter_trim(const AdapterPoints& a, const AdapterSet& ad, uint64_t* end, uint64_t* klen, unsigned long long* work, hipStream_t stream,
     KernelTimer timer = {});
+// adapter_edit.hip: the indel rule.  3' side (ad3.n != 0): cut := AD_NONE, adapter_edit_points_kernel<-1>, apply: end[i] = begin[i] + cut[i],
+// counts ADDED to work[RT_AD_*]; then the 5' side (ad5.n != 0, ad5 / eq5: the adapters letter-reversed, ae_reversed) on what is left:
+// cut := 0, adapter_edit_points_kernel<1>, apply: begin[i] += cut[i], counts ADDED to work[RT_FA_*].  begin and end are a.begin and a.end;
+// klen[i] (klen may be null) the new length; work[RT_OFFSETS] as launch_adapter_trim.  timer3 / timer5: around either points kernel alone
+uint32_t adapter_edit_tiles(uint64_t n_bases);
+hipError_t launch_adapter_edit(const AdapterPoints& a, const AdapterSet& ad3, const AdapterEq& eq3, const AdapterSet& ad5, const AdapterEq& eq5, uint64_t* begin,
+    uint64_t* end, uint64_t* klen, unsigned long long* work, hipStream_t stream, KernelTimer timer3 = {}, KernelTimer timer5 = {});
 struct ReadTrimArgs {
     const uint8_t* qual;
     uint32_t bias;
@@ -493,6 +503,12 @@ struct ReadTrimArgs {
     size_t temp_bytes;
     AdapterSet ad;
     AdapterPoints pts;
+};
+// the indel rule (adapter_edit.hip) in place of the plain one: launch_read_trim's last argument, kept out of ReadTrimArgs, which goes to
+// kernels by value.  ad3 and ad5 (letter-reversed; either may be empty) with their match masks; ReadTrimArgs::ad is not looked at then
+struct AdapterEditSets {
+    AdapterSet ad3, ad5;
+    AdapterEq eq3, eq5;
 };
 // the block's listed non-ACGT positions (n_npos == 0: none, nothing else is looked at).  chunk_count / chunk_prefix:
 // read_trim_npos_chunks(n_npos) + 1 words each; temp: scan_temp_bytes of as many.  launch_read_trim leaves the number of positions inside
@@ -521,7 +537,7 @@ size_t read_trim_temp_bytes(uint64_t n_reads);
 uint32_t read_trim_tiles(uint64_t n_bases);
 uint32_t read_trim_npos_chunks(uint64_t n_npos);
 // timer: around trim_points_kernel alone
-hipError_t launch_read_trim(const ReadTrimArgs& a, const ReadTrimNpos& np, hipStream_t stream, KernelTimer timer = {});
+hipError_t launch_read_trim(const ReadTrimArgs& a, const ReadTrimNpos& np, hipStream_t stream, KernelTimer timer = {}, const AdapterEditSets* edit = nullptr);
 hipError_t launch_read_trim_fill(const ReadTrimFill& f, hipStream_t stream);
 hipError_t launch_read_trim_npos_emit(const ReadTrimFill& f, const ReadTrimNpos& np, uint64_t* out, uint64_t out_cap, hipStream_t stream);
 

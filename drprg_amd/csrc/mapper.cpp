@@ -1611,9 +1611,12 @@ void Mapper::run_read_trim(FilterScratch& fs, const ReadFilter& f, const uint8_t
     const dev::AdapterPoints* pts)
 {
     dev::ReadTrimArgs a {};
-    if (pts && f.adapters.n) {
-        a.ad = f.adapters;
+    dev::AdapterEditSets edit {};
+    const bool indels = pts && f.adapter_indels && f.any_adapters();
+    if (pts && f.any_adapters()) {
         a.pts = *pts;
+        if (indels) edit = dev::AdapterEditSets { f.adapters, f.front_adapters, f.eq3, f.eq5 };
+        else a.ad = f.adapters;
     }
     a.qual = d_qual; a.bias = bias; a.offsets = d_offsets; a.rev = d_rev; a.n_reads = n_reads; a.n_bases = n_bases;
     a.front = f.trim_front; a.tail = f.trim_tail; a.qual_milli = f.trim_qual_milli; a.window = f.trim_window;
@@ -1621,7 +1624,7 @@ void Mapper::run_read_trim(FilterScratch& fs, const ReadFilter& f, const uint8_t
     a.work = fs.t_work.data(); a.out = fs.t_out.device_ptr(); a.temp = fs.t_temp.data(); a.temp_bytes = fs.t_temp.size();
     dev::ReadTrimNpos np {};
     if (n_npos) np = dev::ReadTrimNpos { d_npos, n_npos, fs.t_count.data(), fs.t_prefix.data(), fs.t_ntemp.data(), fs.t_ntemp.size() };
-    HIPCHK(dev::launch_read_trim(a, np, stream));
+    HIPCHK(dev::launch_read_trim(a, np, stream, {}, indels ? &edit : nullptr));
 }
 
 void Mapper::read_trim_device(const ReadFilter& f, const uint8_t* d_qual, uint32_t bias, const uint64_t* d_offsets, const uint8_t* d_rev, uint64_t n_reads,
@@ -1648,6 +1651,7 @@ void Mapper::adapter_trim_device(const ReadFilter& f, const uint8_t* d_text, con
     HIPCHK(hipSetDevice(device_));
     if (!stream) stream = stream_;
     if (!f.adapters.n) throw Error(DRPRG_EINVAL, "adapter trimming: no adapter is set (drprg_hip_set_adapters)");
+    if (f.adapter_indels) throw Error(DRPRG_EINVAL, "adapter trimming: the indel rule is set (drprg_hip_set_adapters2); it runs through drprg_hip_adapter_trim_device2");
     if (!d_offsets || !d_begin || !d_end || (n_bases && !d_text && !d_words) || (n_npos && !d_npos)) throw Error(DRPRG_EINVAL, "null device pointer");
     if (n_reads > dev::MAX_BATCH_READS) throw Error(DRPRG_EOVERFLOW, "at most " + std::to_string(dev::MAX_BATCH_READS) + " reads per batch");
     FilterScratch& fs = filter_api_;
@@ -1661,6 +1665,36 @@ void Mapper::adapter_trim_device(const ReadFilter& f, const uint8_t* d_text, con
     res[0] = n_reads;
     for (int i = 0; i < 4; ++i) res[1 + i] = fs.t_out[dev::RT_AD_BASES_SEEN + i];
     res[5] = fs.t_out[dev::RT_OFFSETS];
+}
+
+void Mapper::adapter_trim_device2(const ReadFilter& f, const uint8_t* d_text, const uint32_t* d_words, const uint64_t* d_npos, uint64_t n_npos,
+    const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases, uint64_t* d_begin, uint64_t* d_end, uint64_t res[11], hipStream_t stream, dev::KernelTimer timer3,
+    dev::KernelTimer timer5)
+{
+    for (int i = 0; i < 11; ++i) res[i] = 0;
+    if (n_reads == 0) return;
+    HIPCHK(hipSetDevice(device_));
+    if (!stream) stream = stream_;
+    if (!f.any_adapters()) throw Error(DRPRG_EINVAL, "adapter trimming: no adapter is set (drprg_hip_set_adapters, drprg_hip_set_adapters2)");
+    if (!d_offsets || !d_begin || !d_end || (n_bases && !d_text && !d_words) || (n_npos && !d_npos)) throw Error(DRPRG_EINVAL, "null device pointer");
+    if (n_reads > dev::MAX_BATCH_READS) throw Error(DRPRG_EOVERFLOW, "at most " + std::to_string(dev::MAX_BATCH_READS) + " reads per batch");
+    FilterScratch& fs = filter_api_;
+    ensure_trim_scratch(fs, n_reads, 0, false, false, true, d_words && n_npos ? n_bases : 0);
+    dev::AdapterPoints p = adapter_points(fs, d_words ? reinterpret_cast<const uint8_t*>(d_words) : d_text, d_words != nullptr, d_npos, n_npos, n_bases, stream);
+    p.offsets = d_offsets; p.begin = d_begin; p.end = d_end; p.n_reads = n_reads; p.n_bases = n_bases;
+    HIPCHK(hipMemsetAsync(fs.t_work.data(), 0, dev::RT_WORDS * sizeof(unsigned long long), stream));
+    if (f.adapter_indels)
+        HIPCHK(dev::launch_adapter_edit(p, f.adapters, f.eq3, f.front_adapters, f.eq5, d_begin, d_end, nullptr, fs.t_work.data(), stream, timer3, timer5));
+    else HIPCHK(dev::launch_adapter_trim(p, f.adapters, d_end, nullptr, fs.t_work.data(), stream, timer3));
+    HIPCHK(hipMemcpyAsync(fs.t_out.data(), fs.t_work.data(), dev::RT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    if (f.adapters.n) res[0] = n_reads;
+    if (f.front_adapters.n) res[5] = n_reads;
+    for (int i = 0; i < 4; ++i) {
+        res[1 + i] = fs.t_out[dev::RT_AD_BASES_SEEN + i];
+        res[6 + i] = fs.t_out[dev::RT_FA_BASES_SEEN + i];
+    }
+    res[10] = fs.t_out[dev::RT_OFFSETS];
 }
 
 void Mapper::map_host_filtered(const HostBatch& hb, const ReadFilter& f, uint64_t cap_need, FilterOutcome& o)
@@ -1694,7 +1728,7 @@ void Mapper::map_host_filtered(const HostBatch& hb, const ReadFilter& f, uint64_
     uint64_t n_npos = hb.packed || hb.bam ? hb.n_npos : 0;
     ensure_stage(st, hb.payload_bytes(), n_reads, n_npos);
     ensure_filter_scratch(fs, n_reads, f.wants_qual() ? n_bases : 0, true, f.use_qual());
-    if (f.trims()) ensure_trim_scratch(fs, n_reads, n_npos, f.trim_qual_milli != 0, true, f.adapters.n != 0, n_npos ? n_bases : 0);
+    if (f.trims()) ensure_trim_scratch(fs, n_reads, n_npos, f.trim_qual_milli != 0, true, f.any_adapters(), n_npos ? n_bases : 0);
     DeviceBatch src = hb.bam ? copy_in_bam(hb, st, st.d_bases.data(), st.d_offsets.data(), st.d_npos.data(), cs, cs)
                              : copy_in(hb, st.d_bases.data(), st.d_offsets.data(), st.d_npos.data(), cs);
     if (f.wants_qual()) {
@@ -1709,7 +1743,7 @@ void Mapper::map_host_filtered(const HostBatch& hb, const ReadFilter& f, uint64_
         // and the quality pointer are REPLACED: the filter, the depth cut, the compaction and keep_reads below see a block of trimmed reads.
         const uint8_t* d_rev = hb.bam && hb.reverse ? st.d_reverse.data() : nullptr; // (BAM: QUAL stays in stored order; the bases were reversed by bam_pack_kernel)
         dev::AdapterPoints pts {}; // (adapters: sought in what the crops and the quality trim leave, bases in read orientation; a packed block's bitmap first)
-        if (f.adapters.n) pts = adapter_points(fs, src.d_bases, src.packed, src.d_npos, src.n_npos, n_bases, cs);
+        if (f.any_adapters()) pts = adapter_points(fs, src.d_bases, src.packed, src.d_npos, src.n_npos, n_bases, cs);
         run_read_trim(fs, f, d_q, hb.qual_bias, src.d_offsets, d_rev, n_reads, n_bases, fs.t_begin.data(), fs.t_end.data(), src.d_npos, src.n_npos, cs, &pts);
         HIPCHK(hipStreamSynchronize(cs)); // the trim's read-back: the trimmed sizes are known before the filter is launched
         const unsigned long long* t = fs.t_out.data();
@@ -1726,7 +1760,11 @@ void Mapper::map_host_filtered(const HostBatch& hb, const ReadFilter& f, uint64_
             o.adapter.reads_seen = n_reads; o.adapter.bases_seen = t[dev::RT_AD_BASES_SEEN]; o.adapter.reads_cut = t[dev::RT_AD_READS_CUT];
             o.adapter.bases_cut = t[dev::RT_AD_BASES_CUT]; o.adapter.reads_emptied = t[dev::RT_AD_EMPTIED];
         }
-        if (t[dev::RT_LOST_READS] || t[dev::RT_AD_READS_CUT]) { // the block lost a base to either cause
+        if (f.front_adapters.n) {
+            o.front.reads_seen = n_reads; o.front.bases_seen = t[dev::RT_FA_BASES_SEEN]; o.front.reads_cut = t[dev::RT_FA_READS_CUT];
+            o.front.bases_cut = t[dev::RT_FA_BASES_CUT]; o.front.reads_emptied = t[dev::RT_FA_EMPTIED];
+        }
+        if (t[dev::RT_LOST_READS] || t[dev::RT_AD_READS_CUT] || t[dev::RT_FA_READS_CUT]) { // the block lost a base to any cause
             const uint64_t nb = t[dev::RT_KEPT_BASES], n_list = src.n_npos ? t[dev::RT_KEPT_NPOS] : 0;
             o.bases_seen = nb;
             if (nb == 0) { // every base of the block is gone: reads of no bases, nothing to map; the set is handed back (see below)

@@ -115,10 +115,15 @@ public:
         uint32_t min_qual_milli = 0;
         uint64_t trim_front = 0, trim_tail = 0;
         uint32_t trim_qual_milli = 0, trim_window = 0;
-        dev::AdapterSet adapters {}; // n == 0: none
+        dev::AdapterSet adapters {}; // n == 0: none (3' adapters under the indel rule)
+        // the indel rule (drprg_hip_set_adapters2, adapter_edit.hip): 5' adapters, held letter-reversed, and both sides' match masks
+        bool adapter_indels = false;
+        dev::AdapterSet front_adapters {};
+        dev::AdapterEq eq3 {}, eq5 {};
+        bool any_adapters() const { return adapters.n != 0 || front_adapters.n != 0; }
         bool crops() const { return trim_front || trim_tail || trim_qual_milli; } // what drprg_hip_read_trim_info counts
         bool filters() const { return min_len || max_len || min_qual_milli; }
-        bool trims() const { return crops() || adapters.n != 0; }
+        bool trims() const { return crops() || any_adapters(); }
         bool any() const { return filters() || trims(); }
         bool use_qual() const { return min_qual_milli != 0; }
         bool wants_qual() const { return min_qual_milli != 0 || trim_qual_milli != 0; } // the ingest carries quality bytes
@@ -132,6 +137,7 @@ public:
     struct FilterOutcome {
         TrimOutcome trim;       // (all zero without a crop or a quality trim)
         AdapterOutcome adapter; // (all zero without adapters)
+        AdapterOutcome front;   // drprg_hip_front_adapter_info (all zero without 5' adapters; bases_seen: behind the 3' cut)
         uint64_t reads_seen = 0, bases_seen = 0, dropped_short = 0, dropped_long = 0, dropped_lowq = 0, reads_kept = 0, bases_kept = 0;
         uint64_t mapped_reads = 0, mapped_bases = 0; // what was mapped: the kept reads, or those of them in front of the depth cap
         uint64_t cut_dropped = 0;                    // kept reads behind the depth cap
@@ -159,6 +165,11 @@ public:
     // res[0..4]: reads seen, bases seen, reads cut, bases cut, reads emptied; res[5]: the ranges do not lie inside the reads.  Synchronises `stream`.
     void adapter_trim_device(const ReadFilter& f, const uint8_t* d_text, const uint32_t* d_words, const uint64_t* d_npos, uint64_t n_npos, const uint64_t* d_offsets,
         uint64_t n_reads, uint64_t n_bases, const uint64_t* d_begin, uint64_t* d_end, uint64_t res[6], hipStream_t stream, dev::KernelTimer timer = {});
+    // Whatever adapter rule is set (drprg_hip_adapter_trim_device2): as above, and under 5' adapters d_begin receives the cut ranges' begins.
+    // res[0..4]: the 3' side's counts, res[5..9]: the 5' side's (bases seen: behind the 3' cut), res[10]: the ranges do not lie inside the reads.
+    void adapter_trim_device2(const ReadFilter& f, const uint8_t* d_text, const uint32_t* d_words, const uint64_t* d_npos, uint64_t n_npos, const uint64_t* d_offsets,
+        uint64_t n_reads, uint64_t n_bases, uint64_t* d_begin, uint64_t* d_end, uint64_t res[11], hipStream_t stream, dev::KernelTimer timer3 = {},
+        dev::KernelTimer timer5 = {});
     // Reads that stay in HBM (off by default).  keep_reads(max_bytes > 0): from now on map_host_async copies every block into
     // device memory of its own instead of a staging set and leaves it there -- at most max_bytes of it; one byte more and
     // everything kept is dropped and the staging sets are back.  kept_complete(): every read mapped since keep_reads() /

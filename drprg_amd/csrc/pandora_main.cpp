@@ -81,7 +81,7 @@ void usage()
         "  pandora map      [--genotype] [--local] [--gt-conf X] [-v] [-o DIR] [-g SIZE] [--max-covg N | --subsample-covg D [--seed S]]\n"
         "                   [--dedup] [--min-read-len L] [--max-read-len L] [--min-read-qual Q]\n"
         "                   [--trim-front N] [--trim-tail N] [--trim-qual Q [--trim-window W]]\n"
-        "                   [--adapter SEQ]... [--adapter-error E] [--adapter-min-overlap O]\n"
+        "                   [--adapter SEQ]... [--adapter-error E] [--adapter-min-overlap O] [--adapter-indels] [--front-adapter SEQ]...\n"
         "                   [--vcf-refs FASTA] [-t N] [-w W] [-k K] [-c N] [-I] [-K] [-e RATE] [--max-diff N] <prg> <reads>\n"
         "  pandora discover [same mapping options] <prg> <query.tsv>\n"
         "  --max-covg N: reads are taken in file order up to and including the first one at which (N + 1) x SIZE bases are reached;\n"
@@ -109,7 +109,10 @@ void usage()
         "  --adapter SEQ (up to 4 times; 1 to 64 letters ACGT), --adapter-error E (0 to 0.5, default 0.1), --adapter-min-overlap O (default 3):\n"
         "                every read is cut at the leftmost start at which an adapter matches with at most floor(c * E) substitutions over\n"
         "                the c = min(adapter, rest of the read) letters compared, c >= O -- on the device, behind --trim-* and in front of\n"
-        "                everything else.  No indels, no 5' adapter, no pair overlap.  Needs no qualities.\n"
+        "                everything else.  Needs no qualities.\n"
+        "  --adapter-indels: an occurrence may carry insertions and deletions too (edit distance at most floor(m * E) over the whole adapter).\n"
+        "  --front-adapter SEQ (up to 4 times; needs --adapter-indels): 5' adapters, cut off the reads' starts behind the 3' cut.\n"
+        "                Still missing: anchored adapters, pair overlap, indels inside an adapter that the read's end cuts short.\n"
         "  <reads>: FASTA or FASTQ, plain or gzip; or BAM (secondary and supplementary records are skipped, reverse-strand records are\n"
         "           reverse-complemented, alignments are ignored, qualities are looked at by --min-read-qual and --trim-qual alone)\n"
         "environment: DRPRG_HIP_DEVICE selects the GPU (default 0); DRPRG_HIP_DEVICES=0,1,.. maps on several GPUs of the node\n");
@@ -182,7 +185,11 @@ Args parse(int argc, char** argv)
         else if (s == "--adapter") {
             const std::string e = a.adapters.add(need(i));
             if (!e.empty()) die(e, 2);
-        } else if (s == "--adapter-error") {
+        } else if (s == "--front-adapter") {
+            const std::string e = a.adapters.add_front(need(i));
+            if (!e.empty()) die(e, 2);
+        } else if (s == "--adapter-indels") a.adapters.indels = true;
+        else if (s == "--adapter-error") {
             const std::string e = a.adapters.set_error(need(i));
             if (!e.empty()) die(e, 2);
         } else if (s == "--adapter-min-overlap") {
@@ -262,8 +269,7 @@ drprg_hip_ctx* open_ctx(const Args& a)
     if (int rc = drprg_hip_set_read_filter(ctx, a.min_read_len, a.max_read_len, a.min_read_qual_milli)) die(drprg_hip_last_error(ctx), -rc);
     if (int rc = drprg_hip_set_read_trim(ctx, a.trim_front, a.trim_tail, a.trim_qual_milli, a.trim_window)) die(drprg_hip_last_error(ctx), -rc);
     if (a.adapters.any()) {
-        const std::vector<const char*> seqs = a.adapters.pointers();
-        if (int rc = drprg_hip_set_adapters(ctx, seqs.data(), (uint32_t)seqs.size(), a.adapters.error_milli, a.adapters.min_overlap)) die(drprg_hip_last_error(ctx), -rc);
+        if (int rc = a.adapters.set_on(ctx, drprg_hip_set_adapters, drprg_hip_set_adapters2)) die(drprg_hip_last_error(ctx), -rc);
     }
     drprg_hip_set_threads(ctx, a.threads);
     drprg_hip_set_input_format(ctx, packed_input()); // the parser threads pack the reads to 2 bits (DRPRG_HIP_INPUT=ascii: one byte per base)
@@ -382,8 +388,11 @@ void report_filter(drprg_hip_ctx* ctx, const Args& a)
         std::printf("[pandora-hip] read trimming: reads_seen=%llu bases_seen=%llu reads_lost_base=%llu cut_front=%llu cut_tail=%llu qual_cut_front=%llu "
                     "qual_cut_tail=%llu reads_emptied=%llu\n", (unsigned long long)fi[0], (unsigned long long)fi[1], (unsigned long long)fi[2],
             (unsigned long long)fi[3], (unsigned long long)fi[4], (unsigned long long)fi[5], (unsigned long long)fi[6], (unsigned long long)fi[7]);
-    if (a.verbose && a.adapters.any() && drprg_hip_adapter_trim_info(ctx, fi) == 0)
+    if (a.verbose && !a.adapters.seqs.empty() && drprg_hip_adapter_trim_info(ctx, fi) == 0)
         std::printf("[pandora-hip] adapter trimming: reads_seen=%llu bases_seen=%llu reads_cut=%llu bases_cut=%llu reads_emptied=%llu\n", (unsigned long long)fi[0],
+            (unsigned long long)fi[1], (unsigned long long)fi[2], (unsigned long long)fi[3], (unsigned long long)fi[4]);
+    if (a.verbose && !a.adapters.front.empty() && drprg_hip_front_adapter_info(ctx, fi) == 0)
+        std::printf("[pandora-hip] front adapter trimming: reads_seen=%llu bases_seen=%llu reads_cut=%llu bases_cut=%llu reads_emptied=%llu\n", (unsigned long long)fi[0],
             (unsigned long long)fi[1], (unsigned long long)fi[2], (unsigned long long)fi[3], (unsigned long long)fi[4]);
     if (!a.verbose || !(a.min_read_len || a.max_read_len || a.min_read_qual_milli) || drprg_hip_read_filter_info(ctx, fi) != 0) return;
     std::printf("[pandora-hip] read filter: reads_seen=%llu bases_seen=%llu dropped_short=%llu dropped_long=%llu dropped_low_qual=%llu reads_kept=%llu "

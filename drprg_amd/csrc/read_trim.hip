@@ -21,7 +21,8 @@
 // the read's new length and the counts.  One rocPRIM u64 exclusive scan of the lengths gives the new offsets; trim_fill_kernel then writes
 // where every trimmed read starts in the old block (what launch_subsample_pack and launch_gather_reads take), and trim_npos_kernel moves
 // the listed non-ACGT positions that stay (count, scan, emit: ascending without a sort).  Under adapters (drprg_hip_set_adapters) the two
-// kernels of adapter_trim.hip run between the tables and the scan and shorten the ranges once more.
+// kernels of adapter_trim.hip -- under the indel rule (drprg_hip_set_adapters2) those of adapter_edit.hip, for either end -- run between
+// the tables and the scan and shorten the ranges once more.
 #include "read_trim_piece.h"
 #include "search.h"
 #include <rocprim/device/device_scan.hpp>
@@ -221,7 +222,7 @@ __global__ void read_trim_result_kernel(ReadTrimArgs a, const uint32_t* __restri
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     a.out[RT_KEPT_BASES] = a.noff[a.n_reads];
     for (int k = RT_LOST_READS; k <= RT_EMPTIED; ++k) a.out[k] = a.work[k];
-    for (int k = RT_AD_BASES_SEEN; k <= RT_AD_EMPTIED; ++k) a.out[k] = a.work[k];
+    for (int k = RT_AD_BASES_SEEN; k <= RT_FA_EMPTIED; ++k) a.out[k] = a.work[k];
     a.out[RT_BAD_AT] = a.work[RT_OFFSETS] ? ~0ull : (a.work[RT_BAD_AT] == ~0ull ? 0ull : a.work[RT_BAD_AT]);
     a.out[RT_KEPT_NPOS] = n_kept_npos ? *n_kept_npos : 0;
 }
@@ -289,7 +290,7 @@ size_t read_trim_temp_bytes(uint64_t n_reads)
 
 uint32_t read_trim_npos_chunks(uint64_t n_npos) { return (uint32_t)((n_npos + RT_THREADS - 1) / RT_THREADS); }
 
-hipError_t launch_read_trim(const ReadTrimArgs& a, const ReadTrimNpos& np, hipStream_t stream, KernelTimer timer)
+hipError_t launch_read_trim(const ReadTrimArgs& a, const ReadTrimNpos& np, hipStream_t stream, KernelTimer timer, const AdapterEditSets* edit)
 {
     if (!a.n_reads || a.n_reads > MAX_BATCH_READS) return hipErrorInvalidValue;
     if (a.qual_milli && (a.window < 1 || a.window > RT_MAX_WINDOW || a.qual_milli > RT_MAX_QUAL_MILLI)) return hipErrorInvalidValue;
@@ -308,10 +309,11 @@ hipError_t launch_read_trim(const ReadTrimArgs& a, const ReadTrimNpos& np, hipSt
     }
     hipLaunchKernelGGL(trim_tables_kernel, dim3((uint32_t)((a.n_reads + 1 + RT_THREADS - 1) / RT_THREADS)), dim3(RT_THREADS), 0, stream, a);
     HIP_TRY(hipGetLastError());
-    if (a.ad.n) { // adapter trimming (adapter_trim.hip): on the ranges the tables kernel left, before the new lengths are scanned
+    if (edit || a.ad.n) { // adapter trimming: on the ranges the tables kernel left, before the new lengths are scanned
         AdapterPoints pts = a.pts;
         pts.offsets = a.offsets; pts.begin = a.begin; pts.end = a.end; pts.n_reads = a.n_reads; pts.n_bases = a.n_bases;
-        HIP_TRY(launch_adapter_trim(pts, a.ad, a.end, a.klen, a.work, stream));
+        if (edit) HIP_TRY(launch_adapter_edit(pts, edit->ad3, edit->eq3, edit->ad5, edit->eq5, a.begin, a.end, a.klen, a.work, stream)); // (adapter_edit.hip: 3', then 5')
+        else HIP_TRY(launch_adapter_trim(pts, a.ad, a.end, a.klen, a.work, stream));                                        // (adapter_trim.hip)
     }
     HIP_TRY(rocprim::exclusive_scan(a.temp, temp_bytes, a.klen, a.noff, (uint64_t)0, (size_t)a.n_reads + 1, rocprim::plus<uint64_t>(), stream));
     const uint32_t* kept_npos = nullptr;

@@ -292,13 +292,20 @@ class Context:
             raise ValueError(f"an error rate is a decimal in [0, 0.5] with at most three places, not {error!r}")
         return int(milli)
 
-    def set_adapters(self, seqs, error="0.1", min_overlap=0):
+    def set_adapters(self, seqs, error="0.1", min_overlap=0, front=(), indels=False):
         """from the next map_fastx on, every read is cut at the leftmost start at which one of `seqs` (1 to 4 sequences of 1 to 64 letters
         ACGT) matches with at most floor(c * error) substitutions over the c letters compared, c >= min_overlap (0: 3, or the shortest
-        adapter's length); behind the crops and the quality trim; an empty list clears the settings"""
+        adapter's length); behind the crops and the quality trim; an empty list clears the settings.  indels=True: the indel rule
+        (include/drprg_hip.h) -- an occurrence may carry insertions and deletions too, and `front` (0 to 4 sequences) names 5' adapters,
+        which are cut off the reads' starts behind the 3' cut"""
         seqs = [s.encode() if isinstance(s, str) else bytes(s) for s in (seqs or [])]
         arr = (C.c_char_p * max(len(seqs), 1))(*seqs)
-        _check(lib.drprg_hip_set_adapters(self._h, arr, len(seqs), self.error_milli(error), int(min_overlap)), self._h)
+        front = [s.encode() if isinstance(s, str) else bytes(s) for s in (front or [])]
+        if not front and not indels:
+            _check(lib.drprg_hip_set_adapters(self._h, arr, len(seqs), self.error_milli(error), int(min_overlap)), self._h)
+            return
+        arr5 = (C.c_char_p * max(len(front), 1))(*front)
+        _check(lib.drprg_hip_set_adapters2(self._h, arr, len(seqs), arr5, len(front), self.error_milli(error), int(min_overlap), 1 if indels else 0), self._h)
 
     def adapter_trim_info(self):
         out = (C.c_uint64 * 5)()
@@ -313,6 +320,21 @@ class Context:
         out = (C.c_uint64 * 5)()
         _check(lib.drprg_hip_adapter_trim_device(self._h, d_text, d_words, d_npos, int(n_npos), d_offsets, int(n_reads), int(n_bases), d_begin, d_end, out,
                                                  stream), self._h)
+        return tuple(int(x) for x in out)
+
+    def front_adapter_info(self):
+        """the 5' side's counts since the last reset (bases_seen: behind the 3' cut)"""
+        out = (C.c_uint64 * 5)()
+        _check(lib.drprg_hip_front_adapter_info(self._h, out), self._h)
+        names = ("reads_seen", "bases_seen", "reads_cut", "bases_cut", "reads_emptied")
+        return dict(zip(names, (int(x) for x in out)))
+
+    def adapter_trim_device2(self, d_text, d_words, d_npos, n_npos, d_offsets, n_reads, n_bases, d_begin, d_end, stream=None):
+        """adapter_trim_device under whatever rule is set: d_begin receives the begins a 5' adapter moved; returns the call's ten counts,
+        the 3' side's five and the 5' side's five"""
+        out = (C.c_uint64 * 10)()
+        _check(lib.drprg_hip_adapter_trim_device2(self._h, d_text, d_words, d_npos, int(n_npos), d_offsets, int(n_reads), int(n_bases), d_begin, d_end, out,
+                                                  stream), self._h)
         return tuple(int(x) for x in out)
 
     def select_reads(self, anchors, A, window_bytes=0):

@@ -462,8 +462,9 @@ int drprg_hip_read_trim_device(drprg_hip_ctx* ctx, const void* d_qual, uint32_t 
  *   with read[x + p + j] != A[j] is at most floor(c * e / 1000).  The comparison is case-insensitive; a read base that is not ACGT differs
  *   from every adapter letter.  A window never reaches past y, so never into the next read.
  *   Cut.  The read is cut at the smallest matching p over all adapters: end = x + p.  A read cut to nothing stays a read of no bases, as
- *   with trimming; nothing is dropped or reordered.  There are NO indels (cutadapt's alignment has them), there is no 5' and no anchored
- *   adapter, and no pair-overlap detection (fastp's default for paired reads): substitutions at a fixed start only.
+ *   with trimming; nothing is dropped or reordered.  This plain rule compares at a fixed start with substitutions only; the indel rule below
+ *   (drprg_hip_set_adapters2) adds insertions, deletions and 5' adapters.  Still missing under either: anchored adapters, pair-overlap
+ *   detection (fastp's default for paired reads), and indels inside an adapter that the read's end cuts short.
  *   Invariance.  Leftmost is a minimum: the result is bit-identical whatever the launch geometry, the thread count and the input form.
  *   Adapter trimming runs inside the trim stage of drprg_hip_map_fastx, so everything "read trimming" says about what lies behind it holds:
  *   the read filter, the depth cap, the resident set, drprg_hip_dedup, drprg_hip_subsample, discover and the genotyper see cut reads.  It
@@ -482,11 +483,45 @@ int drprg_hip_read_trim_device(drprg_hip_ctx* ctx, const void* d_qual, uint32_t 
  *     drprg_hip_pack_device, with d_npos: n_npos ascending positions of the bases that are not ACGT; d_text NULL).  d_offsets: u64[n_reads
  *     + 1].  d_begin, d_end: u64[n_reads], every read's range [x, y) counted from its first base; d_end[i] becomes x + p for a cut read.
  *     out[0..4]: the five counts of this call.  -EINVAL when no adapter is set, when the offsets do not ascend to n_bases or a range does
- *     not lie inside its read. */
+ *     not lie inside its read; -EINVAL under the indel rule (drprg_hip_adapter_trim_device2 runs it).
+ *
+ *   THE INDEL RULE (drprg_hip_set_adapters2 with flag bit 0; this build's own as well, what cutadapt -a / -g -e do in spirit).  Settings per
+ *   context: 0 to 4 3' adapters and 0 to 4 5' adapters, each 1 to 64 letters ACGTacgt; e and O as above, shared by both sides, O at most
+ *   the shortest adapter of either side; the flag INDELS, without which there are no 5' adapters.  L(c) = floor(c * e / 1000).  ed(S, T) is
+ *   the Levenshtein distance with unit costs, case-insensitive; a read base that is not ACGT differs from every adapter letter.
+ *   3' side.  In the range [x, y) the crops and the quality trim left, r[0 .. n): for an adapter A of m letters, full(p) = min over p <= q
+ *   <= n of ed(A, r[p .. q)) for p in 0 .. n - 1, and full(n) = m.  A start p is a MATCH of A iff
+ *     (a) the adapter runs off the read's end: c = n - p < m, c >= O, and at most L(c) of the j < c have r[p + j] != A[j] (the plain rule's
+ *         partial overlap, substitutions only), or
+ *     (b) full(p) <= L(m) and full(p + 1) >= full(p).  The second clause takes the slack out of an edit distance: without it every start
+ *         up to L(m) bases left of an occurrence would match by counting genome bases as insertions.  It needs the next start's score only.
+ *   The read is cut at the smallest matching p over all 3' adapters: end = x + p.  Limit: an adapter cut short by the read's end that
+ *   carries an indel in what is left is found only through (b).
+ *   5' side: the exact mirror, behind the 3' cut, on [x, y').  Reverse r and reverse every 5' adapter letter by letter (no complement),
+ *   apply the 3' rule; a cut at p' there gives begin = x + (n' - p').  Directly: g(q) = min over p <= q of ed(A, r[p .. q)), g(0) = m; an
+ *   end q in 1 .. n' matches iff (a) q < m, q >= O and the last q letters of A differ from r[0 .. q) in at most L(q) places, or (b) g(q) <=
+ *   L(m) and g(q - 1) >= g(q); the read is cut at the LARGEST matching q.  A read cut to nothing stays a read of no bases.
+ *   At e = 0 the indel rule is the plain rule.  Scores may be computed in bounded windows: a verdict at p is the same when the scores are
+ *   computed afresh from a window that ends m + L(m) + 2 bases behind p (or at y), which is what lets the kernels tile the buffer.
+ *   Without the flag and without 5' adapters the plain rule runs, byte for byte, with its launches and no other.  Everything said above
+ *   about what sees cut reads holds for both sides: -22 from drprg_hip_map_host* / drprg_hip_map_device* while any adapter is set, -61 from
+ *   drprg_hip_discover_reads once either side cut a base of a sample that is not resident.
+ *   drprg_hip_set_adapters2: flags bit 0 = INDELS.  -EINVAL for what drprg_hip_set_adapters refuses, on either list; for n5 > 0 without
+ *     bit 0; for unknown flag bits.  n3 == n5 == 0 clears.  drprg_hip_set_adapters sets the plain rule: it clears 5' adapters and the flag.
+ *   drprg_hip_front_adapter_info: since the last reset, out[0..4] = reads seen, bases seen (behind the 3' cut), reads cut, bases cut, reads
+ *     emptied by a 5' adapter.  drprg_hip_adapter_trim_info keeps its five counts for the 3' side.
+ *   drprg_hip_adapter_trim_device2: the buffers of drprg_hip_adapter_trim_device with d_begin writable; runs whatever rule is set; d_begin[i]
+ *     becomes x + q for a read cut at its 5' end.  out[0..4]: the 3' side's counts of this call, out[5..9]: the 5' side's. */
 int drprg_hip_set_adapters(drprg_hip_ctx* ctx, const char* const* seqs, uint32_t n, uint32_t error_milli, uint32_t min_overlap);
 int drprg_hip_adapter_trim_info(drprg_hip_ctx* ctx, uint64_t out[5]);
 int drprg_hip_adapter_trim_device(drprg_hip_ctx* ctx, const void* d_text, const void* d_words, const void* d_npos, uint64_t n_npos, const void* d_offsets,
     uint64_t n_reads, uint64_t n_bases, const void* d_begin, void* d_end, uint64_t out[5], void* hip_stream);
+#define DRPRG_HIP_ADAPTER_INDELS 1u
+int drprg_hip_set_adapters2(drprg_hip_ctx* ctx, const char* const* seqs3, uint32_t n3, const char* const* seqs5, uint32_t n5, uint32_t error_milli,
+    uint32_t min_overlap, uint32_t flags);
+int drprg_hip_front_adapter_info(drprg_hip_ctx* ctx, uint64_t out[5]);
+int drprg_hip_adapter_trim_device2(drprg_hip_ctx* ctx, const void* d_text, const void* d_words, const void* d_npos, uint64_t n_npos, const void* d_offsets,
+    uint64_t n_reads, uint64_t n_bases, void* d_begin, void* d_end, uint64_t out[10], void* hip_stream);
 /* The read selection drprg_hip_discover_reads uses when the reads are resident, on its own: for every device of the context, in order,
  * every kept read in which a k-mer of `anchors` STARTS (anchors: n_anchors k-mers of A bases, 2 bits per base, A 0 C 1 G 2 T 3, first base
  * in the high bits; any order, duplicates allowed).  A block's reads are one base stream: read r of a block is returned iff for some p with
