@@ -134,10 +134,9 @@ struct drprg_hip_ctx {
     // drprg_hip_set_read_filter: the settings (a reset keeps them) and what the filter has counted since the last reset -- added to by the
     // submitters of drprg_hip_map_fastx, one per device, under filter_mu
     Mapper::ReadFilter read_filter;
+    // the blocks' outcomes summed: drprg_hip_read_filter_info, and in .trim / .adapter / .front drprg_hip_read_trim_info,
+    // drprg_hip_adapter_trim_info and drprg_hip_front_adapter_info (their settings ride in read_filter too)
     Mapper::FilterOutcome filter_counts;
-    Mapper::TrimOutcome trim_counts; // drprg_hip_read_trim_info (the settings ride in read_filter)
-    Mapper::AdapterOutcome adapter_counts; // drprg_hip_adapter_trim_info (the settings ride in read_filter too)
-    Mapper::AdapterOutcome front_counts;   // drprg_hip_front_adapter_info
     std::mutex filter_mu;
     // (the page-locked ingest blocks of drprg_hip_map_fastx are recycled process-wide: PinPool above)
     // multi-device context: RCCL communicators of its devices (created on first use; empty when RCCL is not used)
@@ -508,18 +507,7 @@ int drprg_hip_map_fastx(drprg_hip_ctx* ctx, const char* reads_path)
         Mapper::FilterOutcome o;
         dev.map_host_filtered(hb, filter, cap_need, o);
         std::lock_guard<std::mutex> g(ctx->filter_mu);
-        Mapper::FilterOutcome& t = ctx->filter_counts;
-        t.reads_seen += o.reads_seen; t.bases_seen += o.bases_seen; t.dropped_short += o.dropped_short; t.dropped_long += o.dropped_long;
-        t.dropped_lowq += o.dropped_lowq; t.reads_kept += o.reads_kept; t.bases_kept += o.bases_kept;
-        Mapper::TrimOutcome& tt = ctx->trim_counts;
-        tt.reads_seen += o.trim.reads_seen; tt.bases_seen += o.trim.bases_seen; tt.reads_lost_base += o.trim.reads_lost_base; tt.cut_front += o.trim.cut_front;
-        tt.cut_tail += o.trim.cut_tail; tt.qcut_front += o.trim.qcut_front; tt.qcut_tail += o.trim.qcut_tail; tt.emptied += o.trim.emptied;
-        Mapper::AdapterOutcome& at = ctx->adapter_counts;
-        at.reads_seen += o.adapter.reads_seen; at.bases_seen += o.adapter.bases_seen; at.reads_cut += o.adapter.reads_cut; at.bases_cut += o.adapter.bases_cut;
-        at.reads_emptied += o.adapter.reads_emptied;
-        Mapper::AdapterOutcome& ft = ctx->front_counts;
-        ft.reads_seen += o.front.reads_seen; ft.bases_seen += o.front.bases_seen; ft.reads_cut += o.front.reads_cut; ft.bases_cut += o.front.bases_cut;
-        ft.reads_emptied += o.front.reads_emptied;
+        ctx->filter_counts += o;
         kept_reads += o.mapped_reads;
         kept_bases += o.mapped_bases;
         return o;
@@ -738,7 +726,7 @@ int drprg_hip_read_trim_info(drprg_hip_ctx* ctx, uint64_t out[8])
     API_BEGIN(ctx)
     if (!out) throw Error(DRPRG_EINVAL, "null output");
     std::lock_guard<std::mutex> g(ctx->filter_mu);
-    const Mapper::TrimOutcome& t = ctx->trim_counts;
+    const Mapper::TrimOutcome& t = ctx->filter_counts.trim;
     out[0] = t.reads_seen; out[1] = t.bases_seen; out[2] = t.reads_lost_base; out[3] = t.cut_front; out[4] = t.cut_tail;
     out[5] = t.qcut_front; out[6] = t.qcut_tail; out[7] = t.emptied;
     API_END(ctx)
@@ -851,7 +839,7 @@ int drprg_hip_adapter_trim_info(drprg_hip_ctx* ctx, uint64_t out[5])
     API_BEGIN(ctx)
     if (!out) throw Error(DRPRG_EINVAL, "null output");
     std::lock_guard<std::mutex> g(ctx->filter_mu);
-    const Mapper::AdapterOutcome& t = ctx->adapter_counts;
+    const Mapper::AdapterOutcome& t = ctx->filter_counts.adapter;
     out[0] = t.reads_seen; out[1] = t.bases_seen; out[2] = t.reads_cut; out[3] = t.bases_cut; out[4] = t.reads_emptied;
     API_END(ctx)
 }
@@ -863,11 +851,15 @@ int drprg_hip_adapter_trim_device(drprg_hip_ctx* ctx, const void* d_text, const 
     Mapper& m = need_mapper(ctx);
     if (!out) throw Error(DRPRG_EINVAL, "null output");
     if (d_text && d_words) throw Error(DRPRG_EINVAL, "adapter trimming: the bases come as text or as packed words, not both");
-    uint64_t res[6];
+    // (this entry knows the mismatch rule's 3' adapters alone: d_begin is left as it is, the 5' side's counts stay zero)
+    if (n_reads && !ctx->read_filter.adapters.n) throw Error(DRPRG_EINVAL, "adapter trimming: no adapter is set (drprg_hip_set_adapters)");
+    if (n_reads && ctx->read_filter.adapter_indels)
+        throw Error(DRPRG_EINVAL, "adapter trimming: the indel rule is set (drprg_hip_set_adapters2); it runs through drprg_hip_adapter_trim_device2");
+    uint64_t res[11];
     m.adapter_trim_device(ctx->read_filter, (const uint8_t*)d_text, (const uint32_t*)d_words, (const uint64_t*)d_npos, n_npos, (const uint64_t*)d_offsets, n_reads,
-        n_bases, (const uint64_t*)d_begin, (uint64_t*)d_end, res, (hipStream_t)hip_stream);
+        n_bases, (uint64_t*)d_begin, (uint64_t*)d_end, res, (hipStream_t)hip_stream);
     for (int i = 0; i < 5; ++i) out[i] = res[i];
-    if (res[5]) throw Error(DRPRG_EINVAL, "adapter trimming: the offsets do not ascend to n_bases, or a range does not lie inside its read");
+    if (res[10]) throw Error(DRPRG_EINVAL, "adapter trimming: the offsets do not ascend to n_bases, or a range does not lie inside its read");
     API_END(ctx)
 }
 
@@ -876,7 +868,7 @@ int drprg_hip_front_adapter_info(drprg_hip_ctx* ctx, uint64_t out[5])
     API_BEGIN(ctx)
     if (!out) throw Error(DRPRG_EINVAL, "null output");
     std::lock_guard<std::mutex> g(ctx->filter_mu);
-    const Mapper::AdapterOutcome& t = ctx->front_counts;
+    const Mapper::AdapterOutcome& t = ctx->filter_counts.front;
     out[0] = t.reads_seen; out[1] = t.bases_seen; out[2] = t.reads_cut; out[3] = t.bases_cut; out[4] = t.reads_emptied;
     API_END(ctx)
 }
@@ -889,7 +881,7 @@ int drprg_hip_adapter_trim_device2(drprg_hip_ctx* ctx, const void* d_text, const
     if (!out) throw Error(DRPRG_EINVAL, "null output");
     if (d_text && d_words) throw Error(DRPRG_EINVAL, "adapter trimming: the bases come as text or as packed words, not both");
     uint64_t res[11];
-    m.adapter_trim_device2(ctx->read_filter, (const uint8_t*)d_text, (const uint32_t*)d_words, (const uint64_t*)d_npos, n_npos, (const uint64_t*)d_offsets, n_reads,
+    m.adapter_trim_device(ctx->read_filter, (const uint8_t*)d_text, (const uint32_t*)d_words, (const uint64_t*)d_npos, n_npos, (const uint64_t*)d_offsets, n_reads,
         n_bases, (uint64_t*)d_begin, (uint64_t*)d_end, res, (hipStream_t)hip_stream);
     for (int i = 0; i < 10; ++i) out[i] = res[i];
     if (res[10]) throw Error(DRPRG_EINVAL, "adapter trimming: the offsets do not ascend to n_bases, or a range does not lie inside its read");
@@ -1238,9 +1230,6 @@ int drprg_hip_reset(drprg_hip_ctx* ctx)
     ctx->dedup_n = 0;
     ctx->dedup_flags.clear();
     ctx->filter_counts = Mapper::FilterOutcome(); // (the settings stay, as the depth cap does)
-    ctx->trim_counts = Mapper::TrimOutcome();
-    ctx->adapter_counts = Mapper::AdapterOutcome();
-    ctx->front_counts = Mapper::AdapterOutcome();
     API_END(ctx)
 }
 
@@ -1486,10 +1475,10 @@ int drprg_hip_discover_reads(drprg_hip_ctx* ctx, const char* reads_path, const c
     ResidentReads resident;
     ctx->last_discover_resident = reads_resident(ctx, reads_path);
     // (the pass over the file knows nothing of the read filter: rather than pile up reads the mapping never saw, say so)
-    if (!ctx->last_discover_resident && (ctx->adapter_counts.reads_cut || ctx->front_counts.reads_cut))
+    if (!ctx->last_discover_resident && (ctx->filter_counts.adapter.reads_cut || ctx->filter_counts.front.reads_cut))
         throw Error(DRPRG_ENODATA, "discover: adapter trimming cut bases off reads of this sample and the cut reads are not resident in device memory; a pass "
                                    "over the file would pile up reads with their adapters (raise DRPRG_HIP_KEEP_READS_GB, or cut the file first)");
-    if (!ctx->last_discover_resident && ctx->trim_counts.reads_lost_base)
+    if (!ctx->last_discover_resident && ctx->filter_counts.trim.reads_lost_base)
         throw Error(DRPRG_ENODATA, "discover: read trimming cut bases off reads of this sample and the trimmed reads are not resident in device memory; a pass "
                                    "over the file would pile up untrimmed reads (raise DRPRG_HIP_KEEP_READS_GB, or trim the file first)");
     if (!ctx->last_discover_resident && ctx->filter_counts.reads_kept != ctx->filter_counts.reads_seen)

@@ -3,9 +3,7 @@
 #include <algorithm>
 #include <cmath>
 #include <atomic>
-#include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <mutex>
 #include <set>
 #include <hip/hip_runtime.h>
@@ -290,15 +288,7 @@ void Mapper::ensure_lanes()
 
 Mapper::Batch Mapper::make_batch(int lane, const DeviceBatch& batch, uint32_t* covg, uint32_t* prg_reads, hipStream_t stream) const
 {
-    Batch b;
-    b.batch = batch;
-    b.active = true;
-    b.direct = !use_filter_; // (the callers run only the two candidate sequences)
-    b.lane = lane;
-    b.covg = covg;
-    b.prg_reads = prg_reads;
-    b.stream = stream;
-    return b;
+    return Batch { batch, true, !use_filter_, lane, covg, prg_reads, stream }; // (direct: the callers run only the two candidate sequences)
 }
 
 void Mapper::launch(const Batch& b)
@@ -460,12 +450,7 @@ Mapper::DeviceBatch Mapper::ascii_view(int slot, const DeviceBatch& batch, hipSt
         d_unpacked_[slot].alloc(need + need / 4);
     }
     HIPCHK(dev::launch_unpack(reinterpret_cast<const uint32_t*>(batch.d_bases), batch.n_bases, batch.d_npos, batch.n_npos, d_unpacked_[slot].data(), stream));
-    DeviceBatch ascii;
-    ascii.d_bases = d_unpacked_[slot].data();
-    ascii.d_offsets = batch.d_offsets;
-    ascii.n_reads = batch.n_reads;
-    ascii.n_bases = batch.n_bases;
-    return ascii;
+    return DeviceBatch { d_unpacked_[slot].data(), batch.d_offsets, batch.n_reads, batch.n_bases };
 }
 
 void Mapper::read_counters(hipStream_t stream)
@@ -732,7 +717,7 @@ void Mapper::map(const DeviceBatch& batch, uint32_t* covg, uint32_t* prg_reads, 
     check(batch);
     if (batch.n_reads == 0) return;
     HIPCHK(hipSetDevice(device_));
-    if (kept_cap_ && !in_keep_call_) kept_broken_ = true; // reads of the caller's own buffers: not among the kept ones
+    if (resident_.cap && !in_keep_call_) resident_.broken = true; // reads of the caller's own buffers: not among the kept ones
     if (!covg) covg = d_covg();
     if (!prg_reads) prg_reads = d_prg_reads();
     if (!stream) stream = stream_;
@@ -846,1102 +831,6 @@ Mapper::CutPoint Mapper::find_cut(const DeviceBatch& b, uint64_t target, hipStre
     return CutPoint { h_cut_[0], h_cut_[1], h_cut_[2] };
 }
 
-void Mapper::ensure_stage(Stage& st, uint64_t payload_bytes, uint64_t n_reads, uint64_t n_npos)
-{
-    if (payload_bytes + 64 > st.d_bases.size() || n_reads + 1 > st.d_offsets.size() || n_npos > st.d_npos.size())
-        sync(); // (freeing device memory waits for the device; be explicit about the batch in flight)
-    st.d_bases.reserve(payload_bytes + 64, payload_bytes + payload_bytes / 4 + 64);
-    st.d_offsets.reserve(n_reads + 1, n_reads + n_reads / 4 + 1);
-    st.d_npos.reserve(n_npos, n_npos + n_npos / 4 + 16);
-}
-
-Mapper::DeviceBatch Mapper::copy_in(const HostBatch& hb, uint8_t* d_bases, uint64_t* d_offsets, uint64_t* d_npos, hipStream_t stream)
-{
-    DeviceBatch b;
-    b.d_bases = d_bases;
-    b.d_offsets = d_offsets;
-    b.n_reads = hb.n_reads;
-    b.n_bases = hb.n_bases();
-    b.packed = hb.packed;
-    b.n_npos = hb.packed ? hb.n_npos : 0;
-    b.d_npos = b.n_npos ? d_npos : nullptr;
-    HIPCHK(hipMemcpyAsync(d_bases, hb.bases, hb.payload_bytes(), hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemcpyAsync(d_offsets, hb.offsets, (hb.n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
-    if (b.n_npos) HIPCHK(hipMemcpyAsync(d_npos, hb.npos, b.n_npos * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
-    return b;
-}
-
-void Mapper::ensure_bam_scratch(BamScratch& s, uint64_t n_bases)
-{
-    const uint64_t n = (uint64_t)dev::bam_pack_chunks(n_bases) + 1;
-    const size_t temp = dev::scan_temp_bytes((uint32_t)n);
-    if (n > s.d_count.size() || n > s.d_prefix.size() || temp > s.d_temp.size()) sync(); // (as ensure_stage)
-    s.d_count.reserve(n, n + n / 4);
-    s.d_prefix.reserve(n, n + n / 4);
-    s.d_temp.reserve(temp, temp + temp / 4);
-}
-
-Mapper::DeviceBatch Mapper::copy_in_bam(const HostBatch& hb, Stage& st, uint8_t* d_words, uint64_t* d_offsets, uint64_t* d_npos, hipStream_t copy_stream,
-    hipStream_t stream)
-{
-    if (!hb.seq_start || (hb.seq_bytes && !hb.bases)) throw Error(DRPRG_EINVAL, "null buffer");
-    if (hb.seq_bytes + 16 > st.d_seq.size() || hb.n_reads > st.d_seq_start.size() || hb.n_reads > st.d_reverse.size()) sync();
-    st.d_seq.reserve(hb.seq_bytes + 16, hb.seq_bytes + hb.seq_bytes / 4 + 16);
-    st.d_seq_start.reserve(hb.n_reads, hb.n_reads + hb.n_reads / 4);
-    st.d_reverse.reserve(hb.n_reads, hb.n_reads + hb.n_reads / 4);
-    ensure_bam_scratch(st.bam, hb.n_bases());
-    DeviceBatch b;
-    b.d_bases = d_words;
-    b.d_offsets = d_offsets;
-    b.n_reads = hb.n_reads;
-    b.n_bases = hb.n_bases();
-    b.packed = true;
-    b.n_npos = hb.n_npos; // (counted by the parser thread that copied the fields: no read-back, no wait)
-    b.d_npos = b.n_npos ? d_npos : nullptr;
-    if (hb.seq_bytes) HIPCHK(hipMemcpyAsync(st.d_seq.data(), hb.bases, hb.seq_bytes, hipMemcpyHostToDevice, copy_stream));
-    HIPCHK(hipMemcpyAsync(st.d_seq_start.data(), hb.seq_start, hb.n_reads * sizeof(uint64_t), hipMemcpyHostToDevice, copy_stream));
-    if (hb.reverse) HIPCHK(hipMemcpyAsync(st.d_reverse.data(), hb.reverse, hb.n_reads, hipMemcpyHostToDevice, copy_stream));
-    HIPCHK(hipMemcpyAsync(d_offsets, hb.offsets, (hb.n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, copy_stream));
-    if (copy_stream != stream) {
-        HIPCHK(hipEventRecord(st.copied, copy_stream));
-        HIPCHK(hipStreamWaitEvent(stream, st.copied, 0));
-    }
-    HIPCHK(dev::launch_bam_pack(st.d_seq.data(), st.d_seq_start.data(), d_offsets, hb.reverse ? st.d_reverse.data() : nullptr, hb.n_reads, b.n_bases,
-        reinterpret_cast<uint32_t*>(d_words), d_npos, b.n_npos, b.n_npos != 0, st.bam.d_count.data(), st.bam.d_prefix.data(), st.bam.d_temp.data(),
-        st.bam.d_temp.size(), stream));
-    ++bam_blocks_;
-    return b;
-}
-
-void Mapper::map_host(const HostBatch& hb)
-{
-    if (hb.n_reads == 0) return;
-    sync();
-    HIPCHK(hipSetDevice(device_));
-    if (hb.offsets[0] != 0) throw Error(DRPRG_EINVAL, "offsets[0] must be 0");
-    Stage& st = stage_sync_;
-    ensure_stage(st, hb.payload_bytes(), hb.n_reads, hb.packed || hb.bam ? hb.n_npos : 0);
-    if (hb.bam) map(copy_in_bam(hb, st, st.d_bases.data(), st.d_offsets.data(), st.d_npos.data(), stream_, stream_), nullptr, nullptr, stream_, false);
-    else map(copy_in(hb, st.d_bases.data(), st.d_offsets.data(), st.d_npos.data(), stream_), nullptr, nullptr, stream_, false);
-    HIPCHK(hipStreamSynchronize(stream_)); // the staging buffers are reused by the next call
-}
-
-uint64_t Mapper::pack_on_device(const uint8_t* d_bases, uint64_t n_bases, uint32_t* d_words, uint64_t* d_npos, uint64_t npos_cap, hipStream_t stream)
-{
-    HIPCHK(hipSetDevice(device_));
-    if (!stream) stream = stream_;
-    if (n_bases == 0) return 0;
-    if (!d_bases || !d_words) throw Error(DRPRG_EINVAL, "null device pointer");
-    if (!d_pack_count_) d_pack_count_.alloc(1); // (one counter word per Mapper: an allocation per call synchronises the device)
-    unsigned long long n = 0;
-    HIPCHK(hipMemsetAsync(d_pack_count_.data(), 0, sizeof(unsigned long long), stream));
-    HIPCHK(dev::launch_pack(d_bases, n_bases, d_words, d_npos, d_npos ? npos_cap : 0, d_pack_count_.data(), stream));
-    HIPCHK(hipMemcpyAsync(&n, d_pack_count_.data(), sizeof n, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    if (n && !d_npos) throw Error(DRPRG_EINVAL, "the batch holds bases that are not ACGT and no buffer for their positions was given");
-    if (d_npos && n > 1 && n <= npos_cap) { // the positions come out in any order: sorted on the host (few; the harness path)
-        std::vector<uint64_t> h(n);
-        HIPCHK(hipMemcpy(h.data(), d_npos, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
-        std::sort(h.begin(), h.end());
-        HIPCHK(hipMemcpy(d_npos, h.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice));
-    }
-    return n;
-}
-
-uint64_t Mapper::pack_bam_on_device(const uint8_t* d_seq, const uint64_t* d_seq_start, const uint64_t* d_offsets, const uint8_t* d_reverse, uint64_t n_reads,
-    uint64_t n_bases, uint32_t* d_words, uint64_t* d_npos, uint64_t npos_cap, hipStream_t stream)
-{
-    HIPCHK(hipSetDevice(device_));
-    if (!stream) stream = stream_;
-    if (n_bases == 0) return 0;
-    if (n_reads == 0) throw Error(DRPRG_EINVAL, "bases without reads");
-    if (!d_seq || !d_seq_start || !d_offsets || !d_words) throw Error(DRPRG_EINVAL, "null device pointer");
-    if (n_reads > dev::MAX_BATCH_READS) throw Error(DRPRG_EOVERFLOW, "at most " + std::to_string(dev::MAX_BATCH_READS) + " reads per batch");
-    ensure_bam_scratch(bam_api_, n_bases);
-    const uint32_t n_chunks = dev::bam_pack_chunks(n_bases);
-    HIPCHK(dev::launch_bam_pack(d_seq, d_seq_start, d_offsets, d_reverse, n_reads, n_bases, d_words, d_npos, d_npos ? npos_cap : 0, true,
-        bam_api_.d_count.data(), bam_api_.d_prefix.data(), bam_api_.d_temp.data(), bam_api_.d_temp.size(), stream));
-    uint32_t n = 0;
-    HIPCHK(hipMemcpyAsync(&n, bam_api_.d_prefix.data() + n_chunks, sizeof n, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    if (n && !d_npos) throw Error(DRPRG_EINVAL, "the batch holds bases that are not ACGT and no buffer for their positions was given");
-    return n;
-}
-
-void* Mapper::arena_take(size_t bytes)
-{
-    bytes = (bytes + 255) / 256 * 256;
-    if (kept_bytes_ + bytes > kept_cap_) return nullptr;
-    if (bytes > arena_left_) {
-        // (what is left of the current piece is not used: pieces are 256 MB, blocks ~25 MB)
-        const size_t piece = std::max<size_t>(bytes, std::min<uint64_t>(256ull << 20, kept_cap_ - kept_bytes_));
-        DeviceBuffer<uint8_t> arena;
-        try {
-            arena.alloc(piece);
-        } catch (const Error&) { // (the device is full: the caller goes on without resident reads)
-            (void)hipGetLastError();
-            return nullptr;
-        }
-        kept_arenas_.push_back(std::move(arena));
-        arena_at_ = kept_arenas_.back().data();
-        arena_left_ = piece;
-    }
-    void* r = arena_at_;
-    arena_at_ += bytes;
-    arena_left_ -= bytes;
-    kept_bytes_ += bytes;
-    return r;
-}
-
-void Mapper::keep_reads(uint64_t max_bytes)
-{
-    drop_kept();
-    kept_cap_ = max_bytes;
-    // reads mapped before this call are not resident: kept_complete() must not claim them (map_resident would map a subset)
-    kept_broken_ = tot_reads_ != 0;
-}
-
-void Mapper::drop_kept()
-{
-    if (!kept_arenas_.empty()) {
-        sync();
-        HIPCHK(hipSetDevice(device_));
-        HIPCHK(hipStreamSynchronize(stream_));
-    }
-    kept_arenas_.clear();
-    kept_.clear();
-    kept_first_.clear();
-    kept_seen_ = 0;
-    arena_at_ = nullptr;
-    arena_left_ = 0;
-    kept_bytes_ = 0;
-    kept_broken_ = false;
-}
-
-uint64_t Mapper::map_kept_from(const Mapper& other)
-{
-    if (other.device_ != device_) throw Error(DRPRG_EINVAL, "the kept reads live on another device");
-    if (!other.kept_complete()) throw Error(DRPRG_ENODATA, "the other context does not hold all of its reads");
-    uint64_t n = 0;
-    for (const DeviceBatch& b : other.kept_) {
-        map(b, nullptr, nullptr, stream_, true);
-        n += b.n_reads;
-    }
-    sync();
-    HIPCHK(hipStreamSynchronize(stream_));
-    return n;
-}
-
-Mapper::SubsampleResult Mapper::subsample_kept(uint64_t target_bases, uint64_t seed, std::vector<uint8_t>& flags)
-{
-    if (!kept_complete())
-        throw Error(DRPRG_ENODATA, "random subsample: not every read of the sample is resident in device memory (drprg_hip_keep_reads is off, or the "
-                                   "sample is larger than its limit; the executables take the limit from DRPRG_HIP_KEEP_READS_GB)");
-    sync();
-    HIPCHK(hipSetDevice(device_));
-    HIPCHK(hipStreamSynchronize(stream_));
-    flags.clear();
-    const uint64_t n = kept_seen_;
-    uint64_t bases = 0;
-    for (const DeviceBatch& b : kept_) bases += b.n_bases;
-    SubsampleResult res { n, bases, n, bases };
-    if (bases <= target_bases) return res;
-    if (n >= (1ull << 32)) throw Error(DRPRG_EOVERFLOW, "random subsample: 2^32 reads or more in one sample");
-    // ---- selection (device scratch of this call) ----
-    DeviceBuffer<uint64_t> d_len, d_key, d_key_sorted, d_csum, d_boff;
-    DeviceBuffer<uint32_t> d_idx, d_idx_sorted, d_rank;
-    DeviceBuffer<uint8_t> d_flag;
-    DeviceBuffer<unsigned long long> d_cut; // d_cut: [0..1] the cut, [2] the compaction's error word
-    DeviceBuffer<unsigned char> d_temp;
-    d_len.alloc(n); d_key.alloc(n + 1); d_key_sorted.alloc(n); d_csum.alloc(n); d_boff.alloc(n + 1);
-    d_idx.alloc(n + 1); d_idx_sorted.alloc(n); d_rank.alloc(n + 1); d_flag.alloc(n); d_cut.alloc(4);
-    d_temp.alloc(dev::subsample_scan_temp_bytes(n));
-    HIPCHK(hipMemsetAsync(d_len.data(), 0, d_len.bytes(), stream_));
-    HIPCHK(hipMemsetAsync(d_cut.data(), 0, d_cut.bytes(), stream_));
-    for (size_t b = 0; b < kept_.size(); ++b)
-        HIPCHK(dev::launch_subsample_lengths(kept_[b].d_offsets, kept_[b].n_reads, kept_first_[b], n, d_len.data(), stream_));
-    dev::SubsampleSelect sel {};
-    sel.n = n; sel.target = target_bases; sel.seed = seed;
-    sel.len = d_len.data(); sel.key = d_key.data(); sel.key_sorted = d_key_sorted.data(); sel.csum = d_csum.data(); sel.boff = d_boff.data();
-    sel.idx = d_idx.data(); sel.idx_sorted = d_idx_sorted.data(); sel.rank = d_rank.data(); sel.flag = d_flag.data(); sel.cut = d_cut.data();
-    sel.temp = d_temp.data(); sel.temp_bytes = d_temp.size();
-    HIPCHK(dev::launch_subsample_select(sel, stream_));
-    uint32_t* const d_err = reinterpret_cast<uint32_t*>(d_cut.data() + 2);
-    keep_flagged(d_flag.data(), d_rank.data(), d_boff.data(), d_err, "random subsample", res, flags);
-    return res;
-}
-
-// What both selections of resident reads end in (subsample_kept, dedup_kept): flag[i] = 1 for the reads that stay, rank[i] / boff[i] = kept
-// reads / bases before read i (n + 1 entries, n = kept_seen_; device memory).  Every resident block is compacted into a block of its kept
-// reads in arenas of their own, the old set comes back if that fails, coverage and counters are cleared and the new set is mapped.  d_err:
-// a zeroed device word.  res.reads_kept / bases_kept and flags (the device flags, or empty after a failure) are filled here.
-void Mapper::keep_flagged(const uint8_t* d_flag, const uint32_t* d_rank, const uint64_t* d_boff, uint32_t* d_err, const char* what, SubsampleResult& res,
-    std::vector<uint8_t>& flags)
-{
-    const uint64_t n = kept_seen_;
-    DeviceBuffer<uint64_t> d_first;
-    DeviceBuffer<unsigned long long> d_bounds;
-    // kept reads and bases in front of every block's first read, behind its last one, and in all
-    std::vector<uint64_t> first;
-    for (size_t b = 0; b < kept_.size(); ++b) {
-        first.push_back(kept_first_[b]);
-        first.push_back(kept_first_[b] + kept_[b].n_reads);
-    }
-    first.push_back(n);
-    std::vector<unsigned long long> bounds(2 * first.size());
-    d_first.alloc(first.size());
-    d_bounds.alloc(bounds.size());
-    HIPCHK(hipMemcpyAsync(d_first.data(), first.data(), first.size() * sizeof(uint64_t), hipMemcpyHostToDevice, stream_));
-    HIPCHK(dev::launch_subsample_bounds(d_first.data(), (uint32_t)first.size(), n, d_rank, d_boff, d_bounds.data(), stream_));
-    HIPCHK(hipMemcpyAsync(bounds.data(), d_bounds.data(), bounds.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream_));
-    flags.resize(n);
-    HIPCHK(hipMemcpyAsync(flags.data(), d_flag, n, hipMemcpyDeviceToHost, stream_));
-    HIPCHK(hipStreamSynchronize(stream_));
-    res.reads_kept = bounds[bounds.size() - 2];
-    res.bases_kept = bounds[bounds.size() - 1];
-    // ---- compaction: the new set in arenas of its own; the old ones are released by their owners when this scope is left ----
-    std::vector<DeviceBuffer<uint8_t>> old_arenas = std::move(kept_arenas_);
-    std::vector<DeviceBatch> old_kept = std::move(kept_);
-    std::vector<uint64_t> old_first = std::move(kept_first_);
-    uint8_t* const old_at = arena_at_;
-    const size_t old_left = arena_left_;
-    const uint64_t old_bytes = kept_bytes_;
-    kept_arenas_.clear(); kept_.clear(); kept_first_.clear();
-    arena_at_ = nullptr; arena_left_ = 0; kept_bytes_ = 0;
-    try {
-        uint64_t max_reads = 0, max_npos = 0;
-        for (size_t b = 0; b < old_kept.size(); ++b) {
-            max_reads = std::max<uint64_t>(max_reads, bounds[4 * b + 2] - bounds[4 * b]);
-            max_npos = std::max(max_npos, old_kept[b].n_npos);
-        }
-        DeviceBuffer<uint64_t> d_src;
-        DeviceBuffer<dev::GatherEntry> d_table;
-        DeviceBuffer<uint32_t> d_count, d_prefix;
-        DeviceBuffer<unsigned char> d_ntemp;
-        d_src.alloc(max_reads);
-        d_table.alloc(max_reads);
-        if (max_npos) {
-            const uint64_t chunks = (uint64_t)dev::subsample_npos_chunks(max_npos) + 1;
-            d_count.alloc(chunks); d_prefix.alloc(chunks); d_ntemp.alloc(dev::scan_temp_bytes((uint32_t)chunks));
-        }
-        for (size_t b = 0; b < old_kept.size(); ++b) {
-            const DeviceBatch& ob = old_kept[b];
-            const uint64_t nr = bounds[4 * b + 2] - bounds[4 * b], nb = bounds[4 * b + 3] - bounds[4 * b + 1];
-            if (nb == 0) continue; // (nothing of the block is kept, or empty reads only: they are counted below, as map_host_async counts them)
-            const uint64_t payload = ob.packed ? (nb + 15) / 16 * 4 : nb;
-            uint8_t* db = static_cast<uint8_t*>(arena_take(payload + 64));
-            uint64_t* doff = db ? static_cast<uint64_t*>(arena_take((nr + 1) * sizeof(uint64_t))) : nullptr;
-            if (!db || !doff) throw Error(DRPRG_ENOMEM, std::string(what) + ": no device memory for the kept reads beside the resident sample");
-            HIPCHK(hipMemsetAsync(db + payload, 0, 64, stream_));
-            const dev::SubsampleBlock sb { ob.d_bases, ob.d_offsets, ob.n_reads, ob.n_bases, old_first[b], d_flag, d_rank, d_boff, nr, nb };
-            DeviceBatch kb;
-            kb.d_bases = db; kb.d_offsets = doff; kb.n_reads = nr; kb.n_bases = nb; kb.packed = ob.packed;
-            if (ob.packed) {
-                HIPCHK(dev::launch_subsample_tables(sb, doff, d_src.data(), nullptr, d_err, stream_));
-                HIPCHK(dev::launch_subsample_pack(sb, doff, d_src.data(), reinterpret_cast<uint32_t*>(db), d_err, stream_));
-                if (ob.n_npos) {
-                    const uint32_t chunks = dev::subsample_npos_chunks(ob.n_npos);
-                    HIPCHK(dev::launch_subsample_npos_count(sb, ob.d_npos, ob.n_npos, d_count.data(), d_prefix.data(), d_ntemp.data(), d_ntemp.size(), stream_));
-                    uint32_t cnt = 0;
-                    HIPCHK(hipMemcpyAsync(&cnt, d_prefix.data() + chunks, sizeof cnt, hipMemcpyDeviceToHost, stream_));
-                    HIPCHK(hipStreamSynchronize(stream_));
-                    if (cnt) {
-                        uint64_t* dnp = static_cast<uint64_t*>(arena_take((uint64_t)cnt * sizeof(uint64_t)));
-                        if (!dnp) throw Error(DRPRG_ENOMEM, std::string(what) + ": no device memory for the kept reads beside the resident sample");
-                        HIPCHK(dev::launch_subsample_npos_emit(sb, ob.d_npos, ob.n_npos, d_prefix.data(), dnp, cnt, stream_));
-                        kb.d_npos = dnp;
-                        kb.n_npos = cnt;
-                    }
-                }
-            } else {
-                HIPCHK(hipMemsetAsync(d_table.data(), 0, nr * sizeof(dev::GatherEntry), stream_)); // (an entry the kernel refuses to fill copies nothing)
-                HIPCHK(dev::launch_subsample_tables(sb, doff, nullptr, d_table.data(), d_err, stream_));
-                HIPCHK(dev::launch_gather_reads(d_table.data(), (uint32_t)nr, db, stream_));
-            }
-            kept_.push_back(kb);
-            kept_first_.push_back(bounds[4 * b]);
-        }
-        uint32_t err = 0;
-        HIPCHK(hipMemcpyAsync(&err, d_err, sizeof err, hipMemcpyDeviceToHost, stream_));
-        HIPCHK(hipStreamSynchronize(stream_)); // (nothing reads the old blocks any more)
-        if (err) throw Error(DRPRG_EIO, std::string(what) + ": the resident blocks' offsets and the selection do not fit each other");
-    } catch (...) { // the sample as it was
-        (void)hipStreamSynchronize(stream_);
-        kept_arenas_ = std::move(old_arenas);
-        kept_ = std::move(old_kept);
-        kept_first_ = std::move(old_first);
-        arena_at_ = old_at; arena_left_ = old_left; kept_bytes_ = old_bytes;
-        flags.clear();
-        throw;
-    }
-    kept_seen_ = res.reads_kept;
-    // ---- the kept reads mapped afresh ----
-    HIPCHK(hipMemsetAsync(d_covg_.data(), 0, d_covg_.bytes(), stream_)); // [coverage | reads per PRG]
-    HIPCHK(hipMemsetAsync(d_counters_.data(), 0, d_counters_.bytes(), stream_));
-    HIPCHK(hipStreamSynchronize(stream_));
-    tot_reads_ = tot_bases_ = tot_hits_ = tot_leftover_ = tot_minimizers_ = 0;
-    uint64_t in_blocks = 0;
-    in_keep_call_ = true;
-    try {
-        for (const DeviceBatch& b : kept_) {
-            map(b, nullptr, nullptr, stream_, true);
-            in_blocks += b.n_reads;
-        }
-        sync();
-    } catch (...) {
-        in_keep_call_ = false;
-        throw;
-    }
-    in_keep_call_ = false;
-    HIPCHK(hipStreamSynchronize(stream_));
-    tot_reads_ += res.reads_kept - in_blocks; // (kept empty reads of blocks that hold no base any more)
-}
-
-// One resident block as the key kernel reads it: a packed block as it lies there (the bitmap of its listed positions beside it), an ASCII
-// block packed into scratch first.  The scratch lives as long as this object.
-struct Mapper::DedupBlock {
-    DeviceBuffer<uint32_t> words;
-    DeviceBuffer<uint64_t> npos;
-    DeviceBuffer<uint16_t> bits;
-    dev::DedupBatch batch {};
-};
-
-void Mapper::dedup_block(const DeviceBatch& kb, DedupBlock& out, unsigned long long* d_count)
-{
-    const uint64_t n_words = (kb.n_bases + 15) / 16;
-    const uint64_t* d_npos = kb.d_npos;
-    uint64_t n_npos = kb.n_npos;
-    const uint32_t* words = reinterpret_cast<const uint32_t*>(kb.d_bases);
-    if (!kb.packed) {
-        // launch_pack counts every position it meets and writes those below the capacity: one pass with room for a modest number of them,
-        // a second one only for a block that holds more
-        const uint64_t room = std::min<uint64_t>(kb.n_bases, 1u << 16);
-        out.words.alloc(n_words + 4);
-        out.npos.alloc(room);
-        unsigned long long cnt = 0;
-        HIPCHK(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), stream_));
-        HIPCHK(dev::launch_pack(kb.d_bases, kb.n_bases, out.words.data(), out.npos.data(), room, d_count, stream_));
-        HIPCHK(hipMemcpyAsync(&cnt, d_count, sizeof cnt, hipMemcpyDeviceToHost, stream_));
-        HIPCHK(hipStreamSynchronize(stream_));
-        if (cnt > room) {
-            out.npos.alloc(cnt);
-            HIPCHK(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), stream_));
-            HIPCHK(dev::launch_pack(kb.d_bases, kb.n_bases, out.words.data(), out.npos.data(), cnt, d_count, stream_));
-        }
-        words = out.words.data();
-        d_npos = out.npos.data();
-        n_npos = cnt;
-    }
-    if (n_npos) {
-        out.bits.alloc(n_words + 8);
-        HIPCHK(hipMemsetAsync(out.bits.data(), 0, out.bits.bytes(), stream_));
-        HIPCHK(dev::launch_mark_npos(d_npos, n_npos, kb.n_bases, out.bits.data(), stream_));
-    }
-    out.batch = dev::DedupBatch { words, n_npos ? out.bits.data() : nullptr, kb.d_offsets, kb.n_reads, kb.n_bases };
-}
-
-Mapper::SubsampleResult Mapper::dedup_kept(uint32_t key_bits, std::vector<uint8_t>& flags)
-{
-    if (key_bits < 1 || key_bits > 64) throw Error(DRPRG_EINVAL, "duplicate removal: key_bits must be 1..64");
-    if (!kept_complete())
-        throw Error(DRPRG_ENODATA, "duplicate removal: not every read of the sample is resident in device memory (drprg_hip_keep_reads is off, or the "
-                                   "sample is larger than its limit; the executables take the limit from DRPRG_HIP_KEEP_READS_GB)");
-    sync();
-    HIPCHK(hipSetDevice(device_));
-    HIPCHK(hipStreamSynchronize(stream_));
-    flags.clear();
-    const uint64_t n = kept_seen_;
-    uint64_t bases = 0, with_bases = 0;
-    for (const DeviceBatch& b : kept_) {
-        bases += b.n_bases;
-        with_bases += b.n_bases ? b.n_reads : 0; // (an upper bound: two reads with bases need two reads in blocks that hold bases)
-    }
-    SubsampleResult res { n, bases, n, bases };
-    if (n >= (1ull << 32)) throw Error(DRPRG_EOVERFLOW, "duplicate removal: 2^32 reads or more in one sample");
-    if (with_bases < 2) return res;
-    // ---- selection (device scratch of this call) ----
-    DeviceBuffer<uint64_t> d_key, d_key_sorted, d_boff;
-    DeviceBuffer<uint32_t> d_idx, d_idx_sorted, d_rank, d_err;
-    DeviceBuffer<uint8_t> d_flag;
-    DeviceBuffer<dev::DedupLoc> d_loc;
-    DeviceBuffer<unsigned long long> d_count;
-    DeviceBuffer<unsigned char> d_temp;
-    d_key.alloc(n + 1); d_key_sorted.alloc(n); d_boff.alloc(n + 1); d_idx.alloc(n + 1); d_idx_sorted.alloc(n); d_rank.alloc(n + 1);
-    d_flag.alloc(n); d_loc.alloc(n); d_err.alloc(4); d_count.alloc(1);
-    d_temp.alloc(dev::subsample_scan_temp_bytes(n));
-    HIPCHK(hipMemsetAsync(d_key.data(), 0, d_key.bytes(), stream_));
-    HIPCHK(hipMemsetAsync(d_loc.data(), 0, d_loc.bytes(), stream_));
-    HIPCHK(hipMemsetAsync(d_err.data(), 0, d_err.bytes(), stream_));
-    std::vector<DedupBlock> blocks(kept_.size()); // (the exact check reads every block: the scratch of all of them lives until it is done)
-    for (size_t b = 0; b < kept_.size(); ++b) {
-        if (!kept_[b].n_reads || !kept_[b].n_bases) continue;
-        if (kept_first_[b] + kept_[b].n_reads > n) throw Error(DRPRG_EIO, "duplicate removal: the resident blocks hold more reads than the sample");
-        dedup_block(kept_[b], blocks[b], d_count.data());
-        HIPCHK(dev::launch_dedup_keys(blocks[b].batch, reinterpret_cast<unsigned long long*>(d_key.data()) + kept_first_[b], d_err.data(), stream_));
-        HIPCHK(dev::launch_dedup_loc(blocks[b].batch, kept_first_[b], n, d_loc.data(), d_err.data(), stream_));
-    }
-    dev::DedupSelect sel {};
-    sel.n = n; sel.key_bits = key_bits; sel.loc = d_loc.data();
-    sel.key = d_key.data(); sel.key_sorted = d_key_sorted.data(); sel.boff = d_boff.data();
-    sel.idx = d_idx.data(); sel.idx_sorted = d_idx_sorted.data(); sel.rank = d_rank.data(); sel.flag = d_flag.data(); sel.err = d_err.data();
-    sel.temp = d_temp.data(); sel.temp_bytes = d_temp.size();
-    HIPCHK(dev::launch_dedup_select(sel, stream_));
-    uint32_t err = 0, kept = 0;
-    HIPCHK(hipMemcpyAsync(&err, d_err.data(), sizeof err, hipMemcpyDeviceToHost, stream_));
-    HIPCHK(hipMemcpyAsync(&kept, d_rank.data() + n, sizeof kept, hipMemcpyDeviceToHost, stream_));
-    HIPCHK(hipStreamSynchronize(stream_));
-    if (err) throw Error(DRPRG_EIO, "duplicate removal: a resident block's offsets do not fit its bases");
-    if (kept == n) return res; // no read dropped: nothing else happens
-    keep_flagged(d_flag.data(), d_rank.data(), d_boff.data(), d_err.data() + 1, "duplicate removal", res, flags);
-    return res;
-}
-
-void Mapper::dedup_keys_device(const uint32_t* d_words, const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases, const uint64_t* d_npos, uint64_t n_npos,
-    unsigned long long* d_keys, hipStream_t stream)
-{
-    if (n_reads == 0) return;
-    HIPCHK(hipSetDevice(device_));
-    if (!stream) stream = stream_;
-    if (!d_offsets || !d_keys || (n_bases && !d_words) || (n_npos && !d_npos)) throw Error(DRPRG_EINVAL, "null device pointer");
-    if (n_reads >= (1ull << 32)) throw Error(DRPRG_EOVERFLOW, "duplicate keys: 2^32 reads or more in one batch");
-    const uint64_t n_words = (n_bases + 15) / 16;
-    DeviceBuffer<uint16_t> d_bits;
-    DeviceBuffer<uint32_t> d_err;
-    d_err.alloc(1);
-    HIPCHK(hipMemsetAsync(d_err.data(), 0, d_err.bytes(), stream));
-    HIPCHK(hipMemsetAsync(d_keys, 0, n_reads * sizeof(unsigned long long), stream));
-    if (n_npos) {
-        d_bits.alloc(n_words + 8);
-        HIPCHK(hipMemsetAsync(d_bits.data(), 0, d_bits.bytes(), stream));
-        HIPCHK(dev::launch_mark_npos(d_npos, n_npos, n_bases, d_bits.data(), stream));
-    }
-    const dev::DedupBatch b { d_words, n_npos ? d_bits.data() : nullptr, d_offsets, n_reads, n_bases };
-    HIPCHK(dev::launch_dedup_keys(b, d_keys, d_err.data(), stream));
-    uint32_t err = 0;
-    HIPCHK(hipMemcpyAsync(&err, d_err.data(), sizeof err, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    if (err) throw Error(DRPRG_EINVAL, "duplicate keys: the offsets do not ascend from 0 to n_bases");
-}
-
-void Mapper::select_reads_with_anchors(std::vector<uint64_t> anchors, uint32_t A, std::vector<uint8_t>& bases, std::vector<uint64_t>& offsets,
-    std::vector<uint64_t>* ids, uint64_t window_bytes)
-{
-    if (!kept_complete()) throw Error(DRPRG_ENODATA, "not every read of the sample is resident");
-    if (A == 0 || A > 31) throw Error(DRPRG_EINVAL, "anchor length must be 1..31");
-    if (offsets.empty()) offsets.push_back(0);
-    std::sort(anchors.begin(), anchors.end());
-    anchors.erase(std::unique(anchors.begin(), anchors.end()), anchors.end());
-    if (anchors.empty() || kept_.empty()) return;
-    sync();
-    HIPCHK(hipSetDevice(device_));
-    std::vector<uint32_t> pf(2048, 0);
-    for (uint64_t a : anchors) pf[(a & 0xFFFF) >> 5] |= 1u << (a & 31);
-    uint64_t total_reads = 0, max_reads = 0;
-    for (const DeviceBatch& b : kept_) {
-        total_reads += b.n_reads;
-        max_reads = std::max(max_reads, b.n_reads);
-    }
-    // device scratch of this call
-    DeviceBuffer<uint64_t> d_anchors;
-    DeviceBuffer<uint32_t> d_pf, d_flags;
-    DeviceBuffer<unsigned long long> d_count;
-    DeviceBuffer<dev::SelectedRead> d_list;
-    DeviceBuffer<uint8_t> d_ascii;
-    d_anchors.alloc(anchors.size()); d_pf.alloc(pf.size()); d_flags.alloc(max_reads); d_count.alloc(1); d_list.alloc(total_reads);
-    HIPCHK(hipMemcpyAsync(d_anchors.data(), anchors.data(), anchors.size() * sizeof(uint64_t), hipMemcpyHostToDevice, stream_));
-    HIPCHK(hipMemcpyAsync(d_pf.data(), pf.data(), pf.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
-    HIPCHK(hipMemsetAsync(d_count.data(), 0, sizeof(unsigned long long), stream_));
-    // Batches kept in the packed form: the scan and the gather read an ASCII expansion.  It is made a WINDOW of batches at a time -- as
-    // many consecutive batches as expand into <= 1 GB (a larger batch alone) --, scanned, and its selected reads gathered before the next
-    // window's expansion takes the scratch: the scratch is the largest window, not the sample (up to 128 Gbases can stay
-    // resident packed; expanding all of them at once needed that much memory again, with no way back to the file pass).
-    auto expanded = [](const DeviceBatch& kb) -> uint64_t { return kb.packed ? (kb.n_bases + 15) / 16 * 16 + 64 : 0; };
-    const uint64_t WINDOW_BYTES = window_bytes ? window_bytes : SELECT_WINDOW_BYTES;
-    std::vector<std::pair<size_t, size_t>> windows; // [first batch, one past the last)
-    uint64_t scratch_need = 0;
-    for (size_t b = 0; b < kept_.size();) {
-        size_t e = b;
-        uint64_t need = 0;
-        do need += expanded(kept_[e++]);
-        while (e < kept_.size() && need + expanded(kept_[e]) <= WINDOW_BYTES);
-        windows.emplace_back(b, e);
-        scratch_need = std::max(scratch_need, need);
-        b = e;
-    }
-    if (scratch_need) d_ascii.alloc(scratch_need);
-    std::vector<const uint8_t*> ascii(kept_.size(), nullptr);
-    unsigned long long done = 0; // entries of d_list the windows before this one left
-    for (const auto& win : windows) {
-        uint64_t at = 0;
-        for (size_t b = win.first; b < win.second; ++b) {
-            const DeviceBatch& kb = kept_[b];
-            if (!kb.packed) {
-                ascii[b] = kb.d_bases;
-                continue;
-            }
-            HIPCHK(dev::launch_unpack(reinterpret_cast<const uint32_t*>(kb.d_bases), kb.n_bases, kb.d_npos, kb.n_npos, d_ascii.data() + at, stream_));
-            ascii[b] = d_ascii.data() + at;
-            at += expanded(kb);
-        }
-        for (size_t b = win.first; b < win.second; ++b) {
-            const DeviceBatch& kb = kept_[b];
-            HIPCHK(hipMemsetAsync(d_flags.data(), 0, kb.n_reads * sizeof(uint32_t), stream_));
-            HIPCHK(dev::launch_anchor_scan(ascii[b], kb.d_offsets, (uint32_t)kb.n_reads, kb.n_bases, d_anchors.data(), (uint32_t)anchors.size(), A, d_pf.data(),
-                (uint32_t)b, d_flags.data(), d_count.data(), d_list.data(), total_reads, n_cus_, stream_));
-        }
-        unsigned long long count = 0;
-        HIPCHK(hipMemcpyAsync(&count, d_count.data(), sizeof count, hipMemcpyDeviceToHost, stream_));
-        HIPCHK(hipStreamSynchronize(stream_));
-        if (count > total_reads) throw Error(DRPRG_EIO, "read selection: more reads than the batches hold"); // (each read is appended once)
-        if (count == done) continue;
-        std::vector<dev::SelectedRead> list(count - done);
-        HIPCHK(hipMemcpy(list.data(), d_list.data() + done, (count - done) * sizeof(dev::SelectedRead), hipMemcpyDeviceToHost));
-        done = count;
-        std::sort(list.begin(), list.end(), [](const dev::SelectedRead& x, const dev::SelectedRead& y) { return x.batch != y.batch ? x.batch < y.batch : x.read < y.read; });
-        std::vector<dev::GatherEntry> table(list.size());
-        uint64_t out_bytes = 0;
-        for (size_t i = 0; i < list.size(); ++i) {
-            table[i].src = ascii[list[i].batch] + list[i].offset;
-            table[i].dst = out_bytes;
-            table[i].len = list[i].len;
-            table[i].pad = 0;
-            out_bytes += list[i].len;
-        }
-        // (device memory of this window only: freed before the next one)
-        DeviceBuffer<dev::GatherEntry> d_table;
-        DeviceBuffer<uint8_t> d_out;
-        d_table.alloc(list.size());
-        d_out.alloc(out_bytes);
-        const size_t base0 = bases.size();
-        bases.resize(base0 + out_bytes);
-        HIPCHK(hipMemcpyAsync(d_table.data(), table.data(), list.size() * sizeof(dev::GatherEntry), hipMemcpyHostToDevice, stream_));
-        HIPCHK(dev::launch_gather_reads(d_table.data(), (uint32_t)list.size(), d_out.data(), stream_));
-        if (out_bytes) HIPCHK(hipMemcpyAsync(bases.data() + base0, d_out.data(), out_bytes, hipMemcpyDeviceToHost, stream_));
-        HIPCHK(hipStreamSynchronize(stream_));
-        for (size_t i = 0; i < list.size(); ++i) offsets.push_back(offsets.back() + list[i].len);
-        if (ids)
-            for (size_t i = 0; i < list.size(); ++i) ids->push_back((uint64_t)list[i].batch << 32 | list[i].read);
-    }
-}
-
-// over the limit (or the device is full): nothing is kept from here on, and what was kept is of no use without the rest
-void Mapper::stop_keeping()
-{
-    const uint64_t cap = kept_cap_;
-    drop_kept();
-    kept_cap_ = cap;
-    kept_broken_ = true;
-    // (said once per context, always: the run takes a different, slower route from here -- results are the same)
-    std::fprintf(stderr, "[drprg-hip] the sample is larger than the %.1f GB of device memory set aside for resident reads (device %d): reads are "
-                         "not kept, later passes read the file again (DRPRG_HIP_KEEP_READS_GB raises the limit)\n", (double)cap / 1e9, device_);
-}
-
-void Mapper::map_host_async(const HostBatch& hb)
-{
-    const uint64_t n_reads = hb.n_reads;
-    if (n_reads == 0) return;
-    if (kept_cap_ && !kept_broken_) {
-        // the block goes into device memory of its own and stays there
-        HIPCHK(hipSetDevice(device_));
-        if (hb.offsets[0] != 0) throw Error(DRPRG_EINVAL, "offsets[0] must be 0");
-        if (hb.n_bases() == 0) {
-            tot_reads_ += n_reads; // (only empty reads: nothing to keep)
-            kept_seen_ += n_reads;
-            return;
-        }
-        const uint64_t n_npos = hb.packed || hb.bam ? hb.n_npos : 0;
-        uint8_t* db = static_cast<uint8_t*>(arena_take(hb.payload_bytes() + 64));
-        uint64_t* doff = db ? static_cast<uint64_t*>(arena_take((n_reads + 1) * sizeof(uint64_t))) : nullptr;
-        uint64_t* dnp = doff && n_npos ? static_cast<uint64_t*>(arena_take(n_npos * sizeof(uint64_t))) : nullptr;
-        if (db && doff && (dnp || !n_npos)) {
-            if (!copy_stream_) copy_stream_.create();
-            if (!kept_copied_) kept_copied_.create(false);
-            // (a BAM block is kept in the packed form: its raw fields go through a staging set, taken in turn as below)
-            Stage* raw = hb.bam ? &stage_[stage_next_] : nullptr;
-            if (raw) {
-                stage_next_ ^= 1;
-                if (!raw->copied) raw->copied.create(false);
-            }
-            const DeviceBatch kb = raw ? copy_in_bam(hb, *raw, db, doff, dnp, copy_stream_, stream_) : copy_in(hb, db, doff, dnp, copy_stream_);
-            HIPCHK(hipEventRecord(kept_copied_, copy_stream_));
-            HIPCHK(hipStreamWaitEvent(stream_, kept_copied_, 0));
-            kept_.push_back(kb);
-            kept_first_.push_back(kept_seen_);
-            kept_seen_ += n_reads;
-            in_keep_call_ = true;
-            try {
-                map(kb, nullptr, nullptr, stream_, true);
-            } catch (...) {
-                in_keep_call_ = false;
-                throw;
-            }
-            in_keep_call_ = false;
-            HIPCHK(hipEventSynchronize(kept_copied_)); // the caller's block is free again
-            return;
-        }
-        stop_keeping();
-    }
-    if (!use_filter_) { // no deferred form of this sequence
-        map_host(hb);
-        return;
-    }
-    HIPCHK(hipSetDevice(device_));
-    if (hb.offsets[0] != 0) throw Error(DRPRG_EINVAL, "offsets[0] must be 0");
-    if (hb.n_bases() == 0) { // only empty reads: nothing to copy, nothing to map (the counters still see them)
-        tot_reads_ += n_reads;
-        return;
-    }
-    if (!copy_stream_) copy_stream_.create();
-    // the batch that used this staging set two calls ago was completed by the previous call (a deferred map completes the batch
-    // before the one it queues), so the set is free
-    Stage& st = stage_[stage_next_];
-    stage_next_ ^= 1;
-    if (!st.copied) st.copied.create(false);
-    ensure_stage(st, hb.payload_bytes(), n_reads, hb.packed || hb.bam ? hb.n_npos : 0);
-    const DeviceBatch b = hb.bam ? copy_in_bam(hb, st, st.d_bases.data(), st.d_offsets.data(), st.d_npos.data(), copy_stream_, stream_)
-                                 : copy_in(hb, st.d_bases.data(), st.d_offsets.data(), st.d_npos.data(), copy_stream_);
-    HIPCHK(hipEventRecord(st.copied, copy_stream_));
-    HIPCHK(hipStreamWaitEvent(stream_, st.copied, 0));
-    map(b, nullptr, nullptr, stream_, true);
-    HIPCHK(hipEventSynchronize(st.copied)); // the caller's block is free again; the kernels run on
-}
-
-// ---- the read filter ---------------------------------------------------------------------------------------------------------------
-void Mapper::ensure_filter_scratch(FilterScratch& fs, uint64_t n_reads, uint64_t qual_bytes, bool own_flags, bool own_sums)
-{
-    auto room = [&](auto& buf, uint64_t need) {
-        if (need <= buf.size()) return;
-        sync(); // (as ensure_stage: freeing device memory waits for the device)
-        buf.alloc(need + need / 4);
-    };
-    if (qual_bytes) room(fs.d_qual, qual_bytes + 64);
-    if (own_flags) room(fs.d_flag, n_reads);
-    if (own_sums) room(fs.d_qsum, n_reads);
-    room(fs.d_flag32, n_reads + 1);
-    room(fs.d_rank, n_reads + 1);
-    room(fs.d_klen, n_reads + 1);
-    room(fs.d_boff, n_reads + 1);
-    room(fs.d_temp, dev::read_filter_temp_bytes(n_reads));
-    if (!fs.d_work) fs.d_work.alloc(8);
-    if (!fs.h_out) fs.h_out.alloc(8);
-}
-
-void Mapper::run_read_filter(FilterScratch& fs, const ReadFilter& f, const uint8_t* d_qual, uint32_t bias, const uint64_t* d_offsets, uint64_t n_reads,
-    uint64_t n_bases, unsigned long long* d_sums, uint8_t* d_flags, hipStream_t stream)
-{
-    dev::ReadFilterArgs a {};
-    a.qual = d_qual; a.bias = bias; a.offsets = d_offsets; a.n_reads = n_reads; a.n_bases = n_bases;
-    a.min_len = f.min_len; a.max_len = f.max_len; a.T = f.T; a.use_qual = f.use_qual(); // (a batch of empty reads launches no tile, and its sums are still cleared)
-    a.qsum = d_sums; a.flag = d_flags; a.flag32 = fs.d_flag32.data(); a.rank = fs.d_rank.data(); a.klen = fs.d_klen.data(); a.boff = fs.d_boff.data();
-    a.work = fs.d_work.data(); a.out = fs.h_out.device_ptr(); a.temp = fs.d_temp.data(); a.temp_bytes = fs.d_temp.size();
-    HIPCHK(dev::launch_read_filter(a, stream));
-}
-
-void Mapper::read_filter_device(const ReadFilter& f, const uint8_t* d_qual, uint32_t bias, const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases,
-    unsigned long long* d_sums, uint8_t* d_flags, uint64_t res[8], hipStream_t stream)
-{
-    for (int i = 0; i < 8; ++i) res[i] = 0;
-    if (n_reads == 0) return;
-    HIPCHK(hipSetDevice(device_));
-    if (!stream) stream = stream_;
-    if (!d_offsets || !d_flags || (f.use_qual() && n_bases && !d_qual)) throw Error(DRPRG_EINVAL, "null device pointer");
-    if (n_reads > dev::MAX_BATCH_READS) throw Error(DRPRG_EOVERFLOW, "at most " + std::to_string(dev::MAX_BATCH_READS) + " reads per batch");
-    FilterScratch& fs = filter_api_;
-    ensure_filter_scratch(fs, n_reads, 0, false, f.use_qual() && !d_sums);
-    if (f.use_qual() && !d_sums) d_sums = fs.d_qsum.data();
-    run_read_filter(fs, f, d_qual, bias, d_offsets, n_reads, n_bases, d_sums, d_flags, stream);
-    HIPCHK(hipStreamSynchronize(stream));
-    for (int i = 0; i < 8; ++i) res[i] = fs.h_out[i];
-}
-
-// ---- read trimming -------------------------------------------------------------------------------------------------------------------
-void Mapper::ensure_trim_scratch(FilterScratch& fs, uint64_t n_reads, uint64_t n_npos, bool use_qual, bool own_ranges, bool adapters, uint64_t bitmap_bases)
-{
-    auto room = [&](auto& buf, uint64_t need) {
-        if (need <= buf.size()) return;
-        sync(); // (as ensure_stage: freeing device memory waits for the device)
-        buf.alloc(need + need / 4);
-    };
-    if (use_qual) {
-        room(fs.t_first, n_reads);
-        room(fs.t_last, n_reads);
-    }
-    if (own_ranges) {
-        room(fs.t_begin, n_reads);
-        room(fs.t_end, n_reads);
-    }
-    room(fs.t_klen, n_reads + 1);
-    room(fs.t_offsets, n_reads + 1);
-    room(fs.t_temp, dev::read_trim_temp_bytes(n_reads));
-    if (n_npos) {
-        const uint64_t chunks = (uint64_t)dev::read_trim_npos_chunks(n_npos) + 1;
-        room(fs.t_count, chunks);
-        room(fs.t_prefix, chunks);
-        room(fs.t_ntemp, dev::scan_temp_bytes((uint32_t)chunks));
-    }
-    if (adapters) {
-        room(fs.t_cut, n_reads);
-        if (bitmap_bases) room(fs.t_nbits, (bitmap_bases + 15) / 16 + 8); // (launch_mark_npos writes 32-bit words)
-    }
-    if (!fs.t_work) fs.t_work.alloc(dev::RT_WORDS);
-    if (!fs.t_out) fs.t_out.alloc(dev::RT_WORDS);
-}
-
-dev::AdapterPoints Mapper::adapter_points(FilterScratch& fs, const uint8_t* d_bases, bool packed, const uint64_t* d_npos, uint64_t n_npos, uint64_t n_bases,
-    hipStream_t stream)
-{
-    dev::AdapterPoints p {};
-    p.cut = fs.t_cut.data();
-    if (!packed) {
-        p.text = d_bases;
-        return p;
-    }
-    p.words = reinterpret_cast<const uint32_t*>(d_bases);
-    if (n_npos) {
-        const uint64_t n16 = (n_bases + 15) / 16 + 8;
-        HIPCHK(hipMemsetAsync(fs.t_nbits.data(), 0, n16 * sizeof(uint16_t), stream));
-        HIPCHK(dev::launch_mark_npos(d_npos, n_npos, n_bases, fs.t_nbits.data(), stream));
-        p.nbits = fs.t_nbits.data();
-    }
-    return p;
-}
-
-void Mapper::run_read_trim(FilterScratch& fs, const ReadFilter& f, const uint8_t* d_qual, uint32_t bias, const uint64_t* d_offsets, const uint8_t* d_rev,
-    uint64_t n_reads, uint64_t n_bases, uint64_t* d_begin, uint64_t* d_end, const uint64_t* d_npos, uint64_t n_npos, hipStream_t stream,
-    const dev::AdapterPoints* pts)
-{
-    dev::ReadTrimArgs a {};
-    dev::AdapterEditSets edit {};
-    const bool indels = pts && f.adapter_indels && f.any_adapters();
-    if (pts && f.any_adapters()) {
-        a.pts = *pts;
-        if (indels) edit = dev::AdapterEditSets { f.adapters, f.front_adapters, f.eq3, f.eq5 };
-        else a.ad = f.adapters;
-    }
-    a.qual = d_qual; a.bias = bias; a.offsets = d_offsets; a.rev = d_rev; a.n_reads = n_reads; a.n_bases = n_bases;
-    a.front = f.trim_front; a.tail = f.trim_tail; a.qual_milli = f.trim_qual_milli; a.window = f.trim_window;
-    a.first = fs.t_first.data(); a.last = fs.t_last.data(); a.begin = d_begin; a.end = d_end; a.klen = fs.t_klen.data(); a.noff = fs.t_offsets.data();
-    a.work = fs.t_work.data(); a.out = fs.t_out.device_ptr(); a.temp = fs.t_temp.data(); a.temp_bytes = fs.t_temp.size();
-    dev::ReadTrimNpos np {};
-    if (n_npos) np = dev::ReadTrimNpos { d_npos, n_npos, fs.t_count.data(), fs.t_prefix.data(), fs.t_ntemp.data(), fs.t_ntemp.size() };
-    HIPCHK(dev::launch_read_trim(a, np, stream, {}, indels ? &edit : nullptr));
-}
-
-void Mapper::read_trim_device(const ReadFilter& f, const uint8_t* d_qual, uint32_t bias, const uint64_t* d_offsets, const uint8_t* d_rev, uint64_t n_reads,
-    uint64_t n_bases, uint64_t* d_begin, uint64_t* d_end, uint64_t res[9], hipStream_t stream)
-{
-    for (int i = 0; i < 9; ++i) res[i] = 0;
-    if (n_reads == 0) return;
-    HIPCHK(hipSetDevice(device_));
-    if (!stream) stream = stream_;
-    if (!d_offsets || !d_begin || !d_end || (f.trim_qual_milli && n_bases && !d_qual)) throw Error(DRPRG_EINVAL, "null device pointer");
-    if (n_reads > dev::MAX_BATCH_READS) throw Error(DRPRG_EOVERFLOW, "at most " + std::to_string(dev::MAX_BATCH_READS) + " reads per batch");
-    FilterScratch& fs = filter_api_;
-    ensure_trim_scratch(fs, n_reads, 0, f.trim_qual_milli != 0, false);
-    run_read_trim(fs, f, d_qual, bias, d_offsets, d_rev, n_reads, n_bases, d_begin, d_end, nullptr, 0, stream);
-    HIPCHK(hipStreamSynchronize(stream));
-    for (int i = 0; i < 9; ++i) res[i] = fs.t_out[i];
-}
-
-void Mapper::adapter_trim_device(const ReadFilter& f, const uint8_t* d_text, const uint32_t* d_words, const uint64_t* d_npos, uint64_t n_npos,
-    const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases, const uint64_t* d_begin, uint64_t* d_end, uint64_t res[6], hipStream_t stream, dev::KernelTimer timer)
-{
-    for (int i = 0; i < 6; ++i) res[i] = 0;
-    if (n_reads == 0) return;
-    HIPCHK(hipSetDevice(device_));
-    if (!stream) stream = stream_;
-    if (!f.adapters.n) throw Error(DRPRG_EINVAL, "adapter trimming: no adapter is set (drprg_hip_set_adapters)");
-    if (f.adapter_indels) throw Error(DRPRG_EINVAL, "adapter trimming: the indel rule is set (drprg_hip_set_adapters2); it runs through drprg_hip_adapter_trim_device2");
-    if (!d_offsets || !d_begin || !d_end || (n_bases && !d_text && !d_words) || (n_npos && !d_npos)) throw Error(DRPRG_EINVAL, "null device pointer");
-    if (n_reads > dev::MAX_BATCH_READS) throw Error(DRPRG_EOVERFLOW, "at most " + std::to_string(dev::MAX_BATCH_READS) + " reads per batch");
-    FilterScratch& fs = filter_api_;
-    ensure_trim_scratch(fs, n_reads, 0, false, false, true, d_words && n_npos ? n_bases : 0);
-    dev::AdapterPoints p = adapter_points(fs, d_words ? reinterpret_cast<const uint8_t*>(d_words) : d_text, d_words != nullptr, d_npos, n_npos, n_bases, stream);
-    p.offsets = d_offsets; p.begin = d_begin; p.end = d_end; p.n_reads = n_reads; p.n_bases = n_bases;
-    HIPCHK(hipMemsetAsync(fs.t_work.data(), 0, dev::RT_WORDS * sizeof(unsigned long long), stream));
-    HIPCHK(dev::launch_adapter_trim(p, f.adapters, d_end, nullptr, fs.t_work.data(), stream, timer));
-    HIPCHK(hipMemcpyAsync(fs.t_out.data(), fs.t_work.data(), dev::RT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    res[0] = n_reads;
-    for (int i = 0; i < 4; ++i) res[1 + i] = fs.t_out[dev::RT_AD_BASES_SEEN + i];
-    res[5] = fs.t_out[dev::RT_OFFSETS];
-}
-
-void Mapper::adapter_trim_device2(const ReadFilter& f, const uint8_t* d_text, const uint32_t* d_words, const uint64_t* d_npos, uint64_t n_npos,
-    const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases, uint64_t* d_begin, uint64_t* d_end, uint64_t res[11], hipStream_t stream, dev::KernelTimer timer3,
-    dev::KernelTimer timer5)
-{
-    for (int i = 0; i < 11; ++i) res[i] = 0;
-    if (n_reads == 0) return;
-    HIPCHK(hipSetDevice(device_));
-    if (!stream) stream = stream_;
-    if (!f.any_adapters()) throw Error(DRPRG_EINVAL, "adapter trimming: no adapter is set (drprg_hip_set_adapters, drprg_hip_set_adapters2)");
-    if (!d_offsets || !d_begin || !d_end || (n_bases && !d_text && !d_words) || (n_npos && !d_npos)) throw Error(DRPRG_EINVAL, "null device pointer");
-    if (n_reads > dev::MAX_BATCH_READS) throw Error(DRPRG_EOVERFLOW, "at most " + std::to_string(dev::MAX_BATCH_READS) + " reads per batch");
-    FilterScratch& fs = filter_api_;
-    ensure_trim_scratch(fs, n_reads, 0, false, false, true, d_words && n_npos ? n_bases : 0);
-    dev::AdapterPoints p = adapter_points(fs, d_words ? reinterpret_cast<const uint8_t*>(d_words) : d_text, d_words != nullptr, d_npos, n_npos, n_bases, stream);
-    p.offsets = d_offsets; p.begin = d_begin; p.end = d_end; p.n_reads = n_reads; p.n_bases = n_bases;
-    HIPCHK(hipMemsetAsync(fs.t_work.data(), 0, dev::RT_WORDS * sizeof(unsigned long long), stream));
-    if (f.adapter_indels)
-        HIPCHK(dev::launch_adapter_edit(p, f.adapters, f.eq3, f.front_adapters, f.eq5, d_begin, d_end, nullptr, fs.t_work.data(), stream, timer3, timer5));
-    else HIPCHK(dev::launch_adapter_trim(p, f.adapters, d_end, nullptr, fs.t_work.data(), stream, timer3));
-    HIPCHK(hipMemcpyAsync(fs.t_out.data(), fs.t_work.data(), dev::RT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    if (f.adapters.n) res[0] = n_reads;
-    if (f.front_adapters.n) res[5] = n_reads;
-    for (int i = 0; i < 4; ++i) {
-        res[1 + i] = fs.t_out[dev::RT_AD_BASES_SEEN + i];
-        res[6 + i] = fs.t_out[dev::RT_FA_BASES_SEEN + i];
-    }
-    res[10] = fs.t_out[dev::RT_OFFSETS];
-}
-
-void Mapper::map_host_filtered(const HostBatch& hb, const ReadFilter& f, uint64_t cap_need, FilterOutcome& o)
-{
-    o = FilterOutcome {};
-    const uint64_t n_reads = hb.n_reads;
-    if (n_reads == 0) return;
-    HIPCHK(hipSetDevice(device_));
-    if (hb.offsets[0] != 0) throw Error(DRPRG_EINVAL, "offsets[0] must be 0");
-    uint64_t n_bases = hb.n_bases(); // (of the block as it goes on: the trimmed block's, once the trim stage has replaced it)
-    o.reads_seen = n_reads;
-    o.bases_seen = n_bases;
-    bool keeping = kept_cap_ && !kept_broken_;
-    if (n_bases == 0) { // only empty reads: the lower bound decides, there is nothing to copy and nothing to map (the counters still see them)
-        o.dropped_short = f.min_len ? n_reads : 0;
-        o.reads_kept = o.mapped_reads = n_reads - o.dropped_short;
-        tot_reads_ += o.reads_kept;
-        if (keeping) kept_seen_ += o.reads_kept;
-        return;
-    }
-    if (f.trim_qual_milli && !hb.qual) throw Error(DRPRG_EINVAL, "--trim-qual: the reads came without base qualities");
-    if (f.use_qual() && !hb.qual) throw Error(DRPRG_EINVAL, "--min-read-qual: the reads came without base qualities");
-    if (n_reads > dev::MAX_BATCH_READS) throw Error(DRPRG_EOVERFLOW, "at most " + std::to_string(dev::MAX_BATCH_READS) + " reads per batch");
-    if (!copy_stream_) copy_stream_.create();
-    const hipStream_t cs = copy_stream_;
-    // (the batch that used this staging set two calls ago was completed by the previous call: map_host_async)
-    Stage& st = stage_[stage_next_];
-    stage_next_ ^= 1;
-    if (!st.copied) st.copied.create(false);
-    FilterScratch& fs = st.filt;
-    uint64_t n_npos = hb.packed || hb.bam ? hb.n_npos : 0;
-    ensure_stage(st, hb.payload_bytes(), n_reads, n_npos);
-    ensure_filter_scratch(fs, n_reads, f.wants_qual() ? n_bases : 0, true, f.use_qual());
-    if (f.trims()) ensure_trim_scratch(fs, n_reads, n_npos, f.trim_qual_milli != 0, true, f.any_adapters(), n_npos ? n_bases : 0);
-    DeviceBatch src = hb.bam ? copy_in_bam(hb, st, st.d_bases.data(), st.d_offsets.data(), st.d_npos.data(), cs, cs)
-                             : copy_in(hb, st.d_bases.data(), st.d_offsets.data(), st.d_npos.data(), cs);
-    if (f.wants_qual()) {
-        HIPCHK(hipMemcpyAsync(fs.d_qual.data(), hb.qual, n_bases, hipMemcpyHostToDevice, cs));
-        HIPCHK(hipMemsetAsync(fs.d_qual.data() + n_bases, 0, 64, cs));
-    }
-    const uint8_t* d_q = fs.d_qual.data();
-    uint32_t trim_err = 0;
-    if (f.trims()) {
-        // The trim stage: the kept range of every read, the new offsets and the counts, one read-back; a block that lost a base is compacted
-        // into the set's t_* buffers (launch_subsample_pack for words, launch_gather_reads for text and for the quality bytes) and `src`
-        // and the quality pointer are REPLACED: the filter, the depth cut, the compaction and keep_reads below see a block of trimmed reads.
-        const uint8_t* d_rev = hb.bam && hb.reverse ? st.d_reverse.data() : nullptr; // (BAM: QUAL stays in stored order; the bases were reversed by bam_pack_kernel)
-        dev::AdapterPoints pts {}; // (adapters: sought in what the crops and the quality trim leave, bases in read orientation; a packed block's bitmap first)
-        if (f.any_adapters()) pts = adapter_points(fs, src.d_bases, src.packed, src.d_npos, src.n_npos, n_bases, cs);
-        run_read_trim(fs, f, d_q, hb.qual_bias, src.d_offsets, d_rev, n_reads, n_bases, fs.t_begin.data(), fs.t_end.data(), src.d_npos, src.n_npos, cs, &pts);
-        HIPCHK(hipStreamSynchronize(cs)); // the trim's read-back: the trimmed sizes are known before the filter is launched
-        const unsigned long long* t = fs.t_out.data();
-        if (t[dev::RT_BAD_AT] == ~0ull) throw Error(DRPRG_EINVAL, "read trimming: the block's offsets do not ascend to its number of bases");
-        if (t[dev::RT_BAD_AT])
-            throw Error(DRPRG_EFORMAT, "a base quality outside 0..93 (quality byte " + std::to_string(t[dev::RT_BAD_AT] - 1) + " of an ingest block of "
-                    + std::to_string(n_bases) + " bases, " + (hb.qual_bias ? "FASTQ: bytes 33..126" : "BAM: bytes 0..93") + ")");
-        if (f.crops()) {
-            o.trim.reads_seen = n_reads; o.trim.bases_seen = n_bases; o.trim.reads_lost_base = t[dev::RT_LOST_READS];
-            o.trim.cut_front = t[dev::RT_CUT_FRONT]; o.trim.cut_tail = t[dev::RT_CUT_TAIL]; o.trim.qcut_front = t[dev::RT_QCUT_FRONT];
-            o.trim.qcut_tail = t[dev::RT_QCUT_TAIL]; o.trim.emptied = t[dev::RT_EMPTIED];
-        }
-        if (f.adapters.n) {
-            o.adapter.reads_seen = n_reads; o.adapter.bases_seen = t[dev::RT_AD_BASES_SEEN]; o.adapter.reads_cut = t[dev::RT_AD_READS_CUT];
-            o.adapter.bases_cut = t[dev::RT_AD_BASES_CUT]; o.adapter.reads_emptied = t[dev::RT_AD_EMPTIED];
-        }
-        if (f.front_adapters.n) {
-            o.front.reads_seen = n_reads; o.front.bases_seen = t[dev::RT_FA_BASES_SEEN]; o.front.reads_cut = t[dev::RT_FA_READS_CUT];
-            o.front.bases_cut = t[dev::RT_FA_BASES_CUT]; o.front.reads_emptied = t[dev::RT_FA_EMPTIED];
-        }
-        if (t[dev::RT_LOST_READS] || t[dev::RT_AD_READS_CUT] || t[dev::RT_FA_READS_CUT]) { // the block lost a base to any cause
-            const uint64_t nb = t[dev::RT_KEPT_BASES], n_list = src.n_npos ? t[dev::RT_KEPT_NPOS] : 0;
-            o.bases_seen = nb;
-            if (nb == 0) { // every base of the block is gone: reads of no bases, nothing to map; the set is handed back (see below)
-                stage_next_ ^= 1;
-                o.dropped_short = f.min_len ? n_reads : 0;
-                o.reads_kept = o.mapped_reads = n_reads - o.dropped_short;
-                tot_reads_ += o.reads_kept;
-                if (keeping) kept_seen_ += o.reads_kept;
-                return;
-            }
-            const uint64_t payload = src.packed ? (nb + 15) / 16 * 4 : nb;
-            auto room = [&](auto& buf, uint64_t need) {
-                if (need <= buf.size()) return;
-                sync();
-                buf.alloc(need + need / 4);
-            };
-            room(fs.t_bases, payload + 64);
-            if (n_list) room(fs.t_npos, n_list);
-            if (f.use_qual()) room(fs.t_qual, nb + 64);
-            if (src.packed) room(fs.t_src, n_reads);
-            if (!src.packed) room(fs.t_btable, n_reads);
-            if (f.use_qual()) room(fs.t_qtable, n_reads);
-            uint32_t* const d_err = reinterpret_cast<uint32_t*>(fs.t_work.data() + dev::RT_KEPT_NPOS); // (zeroed with the trim's words, unused on the device)
-            dev::ReadTrimFill tf { src.d_offsets, d_rev, fs.t_begin.data(), fs.t_end.data(), fs.t_offsets.data(), n_reads, n_bases, nb, src.d_bases, d_q,
-                src.packed ? fs.t_src.data() : nullptr, src.packed ? nullptr : fs.t_btable.data(), f.use_qual() ? fs.t_qtable.data() : nullptr, d_err };
-            HIPCHK(dev::launch_read_trim_fill(tf, cs));
-            HIPCHK(hipMemsetAsync(fs.t_bases.data() + payload, 0, 64, cs));
-            if (src.packed) {
-                const dev::SubsampleBlock sb { src.d_bases, src.d_offsets, n_reads, n_bases, 0, nullptr, nullptr, nullptr, n_reads, nb };
-                HIPCHK(dev::launch_subsample_pack(sb, fs.t_offsets.data(), fs.t_src.data(), reinterpret_cast<uint32_t*>(fs.t_bases.data()), d_err, cs));
-                if (n_list) {
-                    const dev::ReadTrimNpos np { src.d_npos, src.n_npos, fs.t_count.data(), fs.t_prefix.data(), fs.t_ntemp.data(), fs.t_ntemp.size() };
-                    HIPCHK(dev::launch_read_trim_npos_emit(tf, np, fs.t_npos.data(), n_list, cs));
-                }
-            } else HIPCHK(dev::launch_gather_reads(fs.t_btable.data(), (uint32_t)n_reads, fs.t_bases.data(), cs));
-            if (f.use_qual()) {
-                HIPCHK(dev::launch_gather_reads(fs.t_qtable.data(), (uint32_t)n_reads, fs.t_qual.data(), cs));
-                HIPCHK(hipMemsetAsync(fs.t_qual.data() + nb, 0, 64, cs));
-                d_q = fs.t_qual.data();
-            }
-            HIPCHK(hipMemcpyAsync(&trim_err, d_err, sizeof trim_err, hipMemcpyDeviceToHost, cs)); // (queued behind the compaction; waited for with the filter's read-back)
-            src.d_bases = fs.t_bases.data();
-            src.d_offsets = fs.t_offsets.data();
-            src.n_bases = n_bases = nb;
-            src.d_npos = n_list ? fs.t_npos.data() : nullptr;
-            src.n_npos = n_npos = n_list;
-        }
-    }
-    run_read_filter(fs, f, d_q, hb.qual_bias, src.d_offsets, n_reads, n_bases, fs.d_qsum.data(), fs.d_flag.data(), cs);
-    HIPCHK(hipStreamSynchronize(cs)); // the caller's block is free again; the filter's read-back is here
-    if (trim_err) throw Error(DRPRG_EIO, "read trimming: the block's offsets and the trimmed ranges do not fit each other");
-    const unsigned long long* h = fs.h_out.data();
-    if (h[dev::RF_OFFSETS]) throw Error(DRPRG_EINVAL, "read filter: the block's offsets do not ascend to its number of bases");
-    if (h[dev::RF_BAD_AT])
-        throw Error(DRPRG_EFORMAT, "a base quality outside 0..93 (quality byte " + std::to_string(h[dev::RF_BAD_AT] - 1) + " of an ingest block of "
-                + std::to_string(n_bases) + " bases, " + (hb.qual_bias ? "FASTQ: bytes 33..126" : "BAM: bytes 0..93") + ")");
-    o.dropped_short = h[dev::RF_SHORT];
-    o.dropped_long = h[dev::RF_LONG];
-    o.dropped_lowq = h[dev::RF_LOWQ];
-    o.reads_kept = h[dev::RF_KEPT_READS];
-    o.bases_kept = h[dev::RF_KEPT_BASES];
-    uint64_t take = n_reads, nr = o.reads_kept, nb = o.bases_kept; // the block's first `take` reads hold the nr reads and nb bases that go on
-    if (cap_need && nb >= cap_need) {
-        // the cut, in the block's own numbering: boff is the running total of the kept bases (covg_cut.hip on the scan instead of the offsets)
-        if (!h_cut_) h_cut_.alloc(4);
-        HIPCHK(dev::launch_covg_cut(fs.d_boff.data(), n_reads, cap_need, nullptr, 0, h_cut_.device_ptr(), cs));
-        HIPCHK(hipStreamSynchronize(cs));
-        take = h_cut_[0];
-        nb = h_cut_[1];
-        uint32_t rk = 0;
-        HIPCHK(hipMemcpyAsync(&rk, fs.d_rank.data() + take, sizeof rk, hipMemcpyDeviceToHost, cs));
-        HIPCHK(hipStreamSynchronize(cs));
-        o.cut = true;
-        o.cut_dropped = nr - rk;
-        nr = rk;
-    }
-    o.mapped_reads = nr;
-    o.mapped_bases = nb;
-    if (nb == 0) { // nothing of the block is left, or empty reads only
-        // No map call follows, so nothing completes the batch in flight -- whose kernels read the OTHER staging set.  This set is handed back:
-        // the next block takes it again, and the sets keep their rule (the batch that used a set before was completed by the map call
-        // between).  Were the turn kept, the next block's copies would overwrite what the batch in flight is still reading.
-        stage_next_ ^= 1;
-        tot_reads_ += nr;
-        if (keeping) kept_seen_ += nr;
-        return;
-    }
-    const bool compact = nr != n_reads;
-    const uint64_t payload = src.packed ? (nb + 15) / 16 * 4 : nb;
-    const dev::SubsampleBlock sb { src.d_bases, src.d_offsets, take, src.n_bases, 0, fs.d_flag.data(), fs.d_rank.data(), fs.d_boff.data(), nr, nb };
-    // how many of the block's listed positions go on: all of them, or -- counted before any room is taken for them -- those in kept reads
-    uint64_t n_list = n_npos;
-    if (compact && src.n_npos) {
-        const uint64_t chunks = (uint64_t)dev::subsample_npos_chunks(src.n_npos) + 1;
-        const size_t temp = dev::scan_temp_bytes((uint32_t)chunks);
-        if (chunks > fs.d_count.size()) fs.d_count.alloc(chunks + chunks / 4);
-        if (chunks > fs.d_prefix.size()) fs.d_prefix.alloc(chunks + chunks / 4);
-        if (temp > fs.d_ntemp.size()) fs.d_ntemp.alloc(temp + temp / 4);
-        HIPCHK(dev::launch_subsample_npos_count(sb, src.d_npos, src.n_npos, fs.d_count.data(), fs.d_prefix.data(), fs.d_ntemp.data(), fs.d_ntemp.size(), cs));
-        uint32_t cnt = 0;
-        HIPCHK(hipMemcpyAsync(&cnt, fs.d_prefix.data() + (chunks - 1), sizeof cnt, hipMemcpyDeviceToHost, cs));
-        HIPCHK(hipStreamSynchronize(cs));
-        n_list = cnt;
-    } else if (compact) n_list = 0;
-    uint8_t* db = nullptr;
-    uint64_t *doff = nullptr, *dnp = nullptr;
-    if (keeping) {
-        db = static_cast<uint8_t*>(arena_take(payload + 64));
-        doff = db ? static_cast<uint64_t*>(arena_take((nr + 1) * sizeof(uint64_t))) : nullptr;
-        dnp = doff && n_list ? static_cast<uint64_t*>(arena_take(n_list * sizeof(uint64_t))) : nullptr;
-        if (!db || !doff || (n_list && !dnp)) {
-            stop_keeping();
-            keeping = false;
-        }
-    }
-    DeviceBatch cur = src;
-    if (compact || keeping) {
-        if (!keeping) {
-            if (payload + 64 > fs.c_bases.size() || nr + 1 > fs.c_offsets.size() || n_list > fs.c_npos.size()) sync();
-            fs.c_bases.reserve(payload + 64, payload + payload / 4 + 64);
-            fs.c_offsets.reserve(nr + 1, nr + nr / 4 + 1);
-            fs.c_npos.reserve(n_list, n_list + n_list / 4 + 16);
-            db = fs.c_bases.data();
-            doff = fs.c_offsets.data();
-            dnp = fs.c_npos.data();
-        }
-        cur.d_bases = db;
-        cur.d_offsets = doff;
-        cur.n_reads = nr;
-        cur.n_bases = nb;
-        HIPCHK(hipMemsetAsync(db + payload, 0, 64, cs));
-        if (!compact) { // the whole block, copied on the device to where it stays
-            HIPCHK(hipMemcpyAsync(db, src.d_bases, payload, hipMemcpyDeviceToDevice, cs));
-            HIPCHK(hipMemcpyAsync(doff, src.d_offsets, (nr + 1) * sizeof(uint64_t), hipMemcpyDeviceToDevice, cs));
-            if (src.n_npos) HIPCHK(hipMemcpyAsync(dnp, src.d_npos, src.n_npos * sizeof(uint64_t), hipMemcpyDeviceToDevice, cs));
-            cur.d_npos = src.n_npos ? dnp : nullptr;
-            HIPCHK(hipStreamSynchronize(cs)); // (the block is whole before anything on the mapping stream reads it)
-        } else {
-            uint32_t* const d_err = reinterpret_cast<uint32_t*>(fs.d_work.data() + 7); // (zeroed with the filter's words)
-            cur.d_npos = nullptr;
-            cur.n_npos = 0;
-            if (src.packed) {
-                if (nr > fs.d_src.size()) fs.d_src.alloc(nr + nr / 4);
-                HIPCHK(dev::launch_subsample_tables(sb, doff, fs.d_src.data(), nullptr, d_err, cs));
-                HIPCHK(dev::launch_subsample_pack(sb, doff, fs.d_src.data(), reinterpret_cast<uint32_t*>(db), d_err, cs));
-                if (n_list) { // (counted above; the scan of the counts is still in d_prefix)
-                    HIPCHK(dev::launch_subsample_npos_emit(sb, src.d_npos, src.n_npos, fs.d_prefix.data(), dnp, n_list, cs));
-                    cur.d_npos = dnp;
-                    cur.n_npos = n_list;
-                }
-            } else {
-                if (nr > fs.d_table.size()) fs.d_table.alloc(nr + nr / 4);
-                HIPCHK(hipMemsetAsync(fs.d_table.data(), 0, nr * sizeof(dev::GatherEntry), cs)); // (an entry the kernel refuses to fill copies nothing)
-                HIPCHK(dev::launch_subsample_tables(sb, doff, nullptr, fs.d_table.data(), d_err, cs));
-                HIPCHK(dev::launch_gather_reads(fs.d_table.data(), (uint32_t)nr, db, cs));
-            }
-            uint32_t err = 0;
-            HIPCHK(hipMemcpyAsync(&err, d_err, sizeof err, hipMemcpyDeviceToHost, cs));
-            HIPCHK(hipStreamSynchronize(cs));
-            if (err) throw Error(DRPRG_EIO, "read filter: the block's offsets and the filter's scans do not fit each other");
-        }
-    }
-    if (keeping) {
-        kept_.push_back(cur);
-        kept_first_.push_back(kept_seen_);
-        kept_seen_ += nr;
-    }
-    in_keep_call_ = keeping;
-    try {
-        map(cur, nullptr, nullptr, stream_, true);
-    } catch (...) {
-        in_keep_call_ = false;
-        throw;
-    }
-    in_keep_call_ = false;
-}
-
 void Mapper::add_vectors_from(Mapper& other)
 {
     if (other.n_knodes_ != n_knodes_ || other.n_prgs_ != n_prgs_) throw Error(DRPRG_EINVAL, "coverage size mismatch");
@@ -1974,7 +863,7 @@ void Mapper::download(std::vector<uint32_t>& covg, std::vector<uint32_t>& prg_re
 
 void Mapper::upload(const std::vector<uint32_t>& covg, const std::vector<uint32_t>& prg_reads)
 {
-    if (kept_cap_) kept_broken_ = true; // coverage that came without its reads
+    if (resident_.cap) resident_.broken = true; // coverage that came without its reads
 
     if (covg.size() != 2 * (size_t)n_knodes_ || prg_reads.size() != n_prgs_) throw Error(DRPRG_EINVAL, "coverage size mismatch");
     sync();

@@ -7,6 +7,8 @@
 #include "device_mem.h"
 #include "index.h"
 #include "kernels.h"
+#include <functional>
+#include <optional>
 #include <vector>
 
 namespace drprg {
@@ -128,11 +130,14 @@ public:
         bool use_qual() const { return min_qual_milli != 0; }
         bool wants_qual() const { return min_qual_milli != 0 || trim_qual_milli != 0; } // the ingest carries quality bytes
     };
+    // (operator+=: a block's outcome added to a running total, count by count)
     struct TrimOutcome { // drprg_hip_read_trim_info
         uint64_t reads_seen = 0, bases_seen = 0, reads_lost_base = 0, cut_front = 0, cut_tail = 0, qcut_front = 0, qcut_tail = 0, emptied = 0;
+        TrimOutcome& operator+=(const TrimOutcome& o);
     };
     struct AdapterOutcome { // drprg_hip_adapter_trim_info
         uint64_t reads_seen = 0, bases_seen = 0, reads_cut = 0, bases_cut = 0, reads_emptied = 0;
+        AdapterOutcome& operator+=(const AdapterOutcome& o);
     };
     struct FilterOutcome {
         TrimOutcome trim;       // (all zero without a crop or a quality trim)
@@ -141,7 +146,8 @@ public:
         uint64_t reads_seen = 0, bases_seen = 0, dropped_short = 0, dropped_long = 0, dropped_lowq = 0, reads_kept = 0, bases_kept = 0;
         uint64_t mapped_reads = 0, mapped_bases = 0; // what was mapped: the kept reads, or those of them in front of the depth cap
         uint64_t cut_dropped = 0;                    // kept reads behind the depth cap
-        bool cut = false;
+        bool cut = false;                            // (of one block: not summed)
+        FilterOutcome& operator+=(const FilterOutcome& o);
     };
     // map_host_async behind the filter: the block is copied into a staging set -- its quality bytes too, under a quality threshold --, the
     // filter runs on the copy stream, the call waits for its 64-byte read-back (the caller's block is free then) and what is left of the
@@ -160,25 +166,22 @@ public:
     // quality threshold, and must be readable for 64 bytes behind n_bases when it is 16-byte aligned.  res[0..8]: dev::RT_*.  Synchronises `stream`.
     void read_trim_device(const ReadFilter& f, const uint8_t* d_qual, uint32_t bias, const uint64_t* d_offsets, const uint8_t* d_rev, uint64_t n_reads,
         uint64_t n_bases, uint64_t* d_begin, uint64_t* d_end, uint64_t res[9], hipStream_t stream);
-    // The adapter kernels alone on the caller's device buffers (drprg_hip_adapter_trim_device): the bases as text (d_words == null) or as
-    // packed words with their ascending position list; d_begin / d_end hold every read's range and d_end receives the cut ranges' ends.
-    // res[0..4]: reads seen, bases seen, reads cut, bases cut, reads emptied; res[5]: the ranges do not lie inside the reads.  Synchronises `stream`.
+    // The adapter kernels alone on the caller's device buffers, under whatever adapter rule is set (drprg_hip_adapter_trim_device and
+    // drprg_hip_adapter_trim_device2): the bases as text (d_words == null) or as packed words with their ascending position list; d_begin /
+    // d_end hold every read's range, d_end receives the cut ranges' ends and, under 5' adapters, d_begin their begins.  res[0..4]: the 3'
+    // side's reads seen, bases seen, reads cut, bases cut, reads emptied; res[5..9]: the 5' side's (bases seen: behind the 3' cut); res[10]:
+    // the ranges do not lie inside the reads.  Synchronises `stream`.
     void adapter_trim_device(const ReadFilter& f, const uint8_t* d_text, const uint32_t* d_words, const uint64_t* d_npos, uint64_t n_npos, const uint64_t* d_offsets,
-        uint64_t n_reads, uint64_t n_bases, const uint64_t* d_begin, uint64_t* d_end, uint64_t res[6], hipStream_t stream, dev::KernelTimer timer = {});
-    // Whatever adapter rule is set (drprg_hip_adapter_trim_device2): as above, and under 5' adapters d_begin receives the cut ranges' begins.
-    // res[0..4]: the 3' side's counts, res[5..9]: the 5' side's (bases seen: behind the 3' cut), res[10]: the ranges do not lie inside the reads.
-    void adapter_trim_device2(const ReadFilter& f, const uint8_t* d_text, const uint32_t* d_words, const uint64_t* d_npos, uint64_t n_npos, const uint64_t* d_offsets,
-        uint64_t n_reads, uint64_t n_bases, uint64_t* d_begin, uint64_t* d_end, uint64_t res[11], hipStream_t stream, dev::KernelTimer timer3 = {},
-        dev::KernelTimer timer5 = {});
+        uint64_t n_reads, uint64_t n_bases, uint64_t* d_begin, uint64_t* d_end, uint64_t res[11], hipStream_t stream);
     // Reads that stay in HBM (off by default).  keep_reads(max_bytes > 0): from now on map_host_async copies every block into
     // device memory of its own instead of a staging set and leaves it there -- at most max_bytes of it; one byte more and
     // everything kept is dropped and the staging sets are back.  kept_complete(): every read mapped since keep_reads() /
     // reset_coverage() is among kept().  What they are for: select_reads_with_anchors below (the pile-up of `discover` without a
     // second pass over the file) and mapping the same reads again against another index (map_kept_from).
     void keep_reads(uint64_t max_bytes);
-    bool kept_complete() const { return kept_cap_ > 0 && !kept_broken_; }
-    const std::vector<DeviceBatch>& kept() const { return kept_; }
-    uint64_t kept_bytes() const { return kept_bytes_; }
+    bool kept_complete() const { return resident_.active(); }
+    const std::vector<DeviceBatch>& kept() const { return resident_.kept; }
+    uint64_t kept_bytes() const { return resident_.bytes; }
     void drop_kept();
     // Every kept read that holds one of `anchors` (k-mers of length A <= 31 packed 2 bits per base, A=0 .. T=3, first base in the
     // high bits) -- and possibly a few that do not -- appended to bases / offsets (offsets[0] = 0 is written when offsets is
@@ -406,6 +409,33 @@ private:
         DeviceBuffer<uint32_t> d_count, d_prefix;
         DeviceBuffer<unsigned char> d_temp;
     };
+    // a buffer too small for `need` elements is replaced by one of `grown` -- a quarter more, unless the caller has a padding rule of its
+    // own --, behind sync(): freeing device memory waits for the device, and this is explicit about the batch in flight
+    template <typename Buf> void grow(Buf& buf, uint64_t need, uint64_t grown)
+    {
+        if (need <= buf.size()) return;
+        sync();
+        buf.alloc(grown);
+    }
+    template <typename Buf> void grow(Buf& buf, uint64_t need) { grow(buf, need, need + need / 4); }
+    // what the kernels of subsample.hip make a compacted block from: per kept read its first base in the old block (d_src: packed blocks,
+    // d_table: text), and the listed positions' per-chunk counts with their scan
+    struct CompactScratch {
+        DeviceBuffer<uint64_t> d_src;
+        DeviceBuffer<dev::GatherEntry> d_table;
+        DeviceBuffer<uint32_t> d_count, d_prefix;
+        DeviceBuffer<unsigned char> d_ntemp;
+    };
+    void compact_room(CompactScratch& cs, bool packed, uint64_t n_kept, uint64_t n_npos); // room for such a block
+    struct BlockRoom { // where a block goes
+        uint8_t* bases;
+        uint64_t *offsets, *npos;
+    };
+    // The one compaction by flag / rank / boff (resident.cpp): block `sb` of `src`, in either form, to where `room` says once it is told how
+    // many listed positions the kept reads hold (counted first: one 4-byte read-back on `stream`, none for a source without any).  Then
+    // tables, pack or gather, emit on `stream`; *d_err (zeroed by the caller) is the caller's to read back.  Returns the new block.
+    DeviceBatch compact_block(const dev::SubsampleBlock& sb, const DeviceBatch& src, CompactScratch& cs, uint32_t* d_err, hipStream_t stream,
+        const std::function<BlockRoom(uint64_t n_list)>& room);
     // what the read filter of one block needs beside the block: the quality bytes, the per-read words of read_qual.hip, and -- for a block
     // that loses reads and is not kept -- the compacted block with the tables the kernels of subsample.hip make it from
     struct FilterScratch {
@@ -415,10 +445,7 @@ private:
         DeviceBuffer<uint64_t> d_klen, d_boff;
         DeviceBuffer<unsigned char> d_temp;
         PinnedBuffer<unsigned long long> h_out;
-        DeviceBuffer<uint64_t> d_src;
-        DeviceBuffer<dev::GatherEntry> d_table;
-        DeviceBuffer<uint32_t> d_count, d_prefix;
-        DeviceBuffer<unsigned char> d_ntemp;
+        CompactScratch comp;
         DeviceBuffer<uint8_t> c_bases;
         DeviceBuffer<uint64_t> c_offsets, c_npos;
         // read trimming: the per-read words of read_trim.hip, and the trimmed block (bases or words, offsets, positions, qualities) that a
@@ -472,25 +499,68 @@ private:
     // queues the copies of a host batch to these device addresses (d_npos: used when the batch lists positions) on `stream`; returns the
     // batch they will hold
     DeviceBatch copy_in(const HostBatch& hb, uint8_t* d_bases, uint64_t* d_offsets, uint64_t* d_npos, hipStream_t stream);
+    // either of the two: a BAM block through st's raw buffers (copy_in_bam), any other straight to the addresses (st may be null then)
+    DeviceBatch copy_block_in(const HostBatch& hb, Stage* st, uint8_t* d_bases, uint64_t* d_offsets, uint64_t* d_npos, hipStream_t copy_stream, hipStream_t stream);
+    DeviceBatch copy_to_stage(const HostBatch& hb, Stage& st, hipStream_t copy_stream, hipStream_t stream); // into st's own buffers, given room first
+    hipStream_t copy_stream(); // (created with the first call)
+    // The two sets of the asynchronous paths, taken in turn: the batch that used a set two calls ago was completed by the previous call (a
+    // deferred map completes the batch before the one it queues), so the set is free.  A block that took a set and ends without a map call
+    // hands it back: nothing has completed the batch in flight, whose kernels read the OTHER set, so the next block must take this one
+    // again -- were the turn kept, its copies would overwrite what the batch in flight is still reading.
+    Stage& next_stage();
+    void hand_back_stage() { stage_next_ ^= 1; }
     int stage_next_ = 0;
+    // reads that are counted and go nowhere (empty reads only): the counters see them, and under keep_reads they are numbered
+    void count_unmapped(uint64_t n, bool keeping);
+    // a block of such reads in front of the filter: the lower bound decides, there is nothing to copy and nothing to map
+    void only_empty_reads(uint64_t n_reads, const ReadFilter& f, bool keeping, FilterOutcome& o);
+    // what the *_device entries begin with alike: the device made current, the refusals, the stream to use (null: the context's own)
+    hipStream_t device_entry(hipStream_t stream, bool null_pointer, uint64_t n_reads);
+    // the steps of map_host_filtered behind the copy (read_prep.cpp), in their order
+    struct KeptPart { // the block's first `take` reads hold the n_reads reads and n_bases bases that go on
+        uint64_t take, n_reads, n_bases;
+    };
+    bool trim_block(const HostBatch& hb, const ReadFilter& f, Stage& st, DeviceBatch& src, const uint8_t*& d_qual, uint32_t& trim_err, FilterOutcome& o);
+    void filter_block(const HostBatch& hb, const ReadFilter& f, FilterScratch& fs, const DeviceBatch& src, const uint8_t* d_qual, const uint32_t& trim_err,
+        FilterOutcome& o);
+    KeptPart cut_at_cap(FilterScratch& fs, uint64_t n_reads, uint64_t cap_need, FilterOutcome& o);
+    DeviceBatch place_block(FilterScratch& fs, const DeviceBatch& src, const KeptPart& k, bool& keeping);
     // sketch_filter_kernel's tile shares, followed from batch to batch ([0] ASCII, [1] packed input; {0}: the launcher's built-in ones so far)
     uint32_t ft_share_[2][4] = { { 0, 0, 0, 0 }, { 0, 0, 0, 0 } };
     uint64_t ft_last_[20] = {};
     void tune_filter_shares(const Lane& lane, bool packed, uint64_t n_bases);
-    // keep_reads: device memory in large pieces, handed out front to back
-    std::vector<DeviceBuffer<uint8_t>> kept_arenas_;
-    uint8_t* arena_at_ = nullptr;
-    size_t arena_left_ = 0;
-    std::vector<DeviceBatch> kept_;
-    // the reads of the sample are numbered in the order they were kept: kept_first_[b] = number of kept_[b]'s first read, kept_seen_ = reads
-    // numbered so far (a block of empty reads only is not kept, but its reads are numbered)
-    std::vector<uint64_t> kept_first_;
-    uint64_t kept_seen_ = 0;
-    uint64_t kept_cap_ = 0, kept_bytes_ = 0;
-    bool kept_broken_ = false, in_keep_call_ = false;
+    // keep_reads: the resident sample.  Device memory in large pieces (arenas), handed out front to back, at most `cap` bytes of it.
+    struct ResidentSet {
+        std::vector<DeviceBuffer<uint8_t>> arenas;
+        uint8_t* at = nullptr; // the bump pointer into the last arena
+        size_t left = 0;       // what is left behind it
+        uint64_t cap = 0, bytes = 0; // (cap == 0: nothing is kept)
+        std::vector<DeviceBatch> kept;
+        // the reads of the sample are numbered in the order they were kept: first[b] = number of kept[b]'s first read, seen = reads numbered
+        // so far (a block of empty reads only is not kept, but its reads are numbered)
+        std::vector<uint64_t> first;
+        uint64_t seen = 0;
+        bool broken = false; // reads were mapped that are not among kept
+        bool active() const { return cap > 0 && !broken; }
+        // room for a block: payload_bytes (and 64 more, which the caller clears) of bases, n_reads + 1 offsets, n_npos listed positions
+        // (npos null without any) -- or nothing, when the cap or the device says no
+        std::optional<BlockRoom> take_block(uint64_t payload_bytes, uint64_t n_reads, uint64_t n_npos);
+        void add(const DeviceBatch& b, uint64_t n_reads) { kept.push_back(b); first.push_back(seen); seen += n_reads; }
+        void count_empty(uint64_t n) { seen += n; }
+        // everything but the cap goes; the caller has made sure that nothing on the device reads the blocks any more
+        void clear() { *this = ResidentSet { {}, nullptr, 0, cap }; }
+
+    private:
+        void* arena_take(size_t bytes);
+    };
+    ResidentSet resident_;
+    // a map call on a block of the resident set: the only kind that does not break the set
+    bool in_keep_call_ = false;
+    void map_resident_block(const DeviceBatch& b);
     Event kept_copied_;
-    void* arena_take(size_t bytes);
-    // the second half of subsample_kept and dedup_kept: compaction by the flags, roll-back on failure, the kept reads mapped afresh
+    // what subsample_kept and dedup_kept begin with (the sample is resident, nothing is in flight), and their second half: compaction by the
+    // flags into a new set, the kept reads mapped afresh
+    SubsampleResult resident_sample(const char* what, std::vector<uint8_t>& flags);
     void keep_flagged(const uint8_t* d_flag, const uint32_t* d_rank, const uint64_t* d_boff, uint32_t* d_err, const char* what, SubsampleResult& res,
         std::vector<uint8_t>& flags);
     struct DedupBlock;

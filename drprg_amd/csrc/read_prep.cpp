@@ -1,0 +1,565 @@
+// read_prep.cpp -- what happens to a host block before it is mapped: staging sets and the copies into them, the read filter, read
+// trimming and adapter trimming with their drivers, and the packers of the harness path.  See mapper.h.
+#include "mapper.h"
+#include <algorithm>
+#include <hip/hip_runtime.h>
+
+namespace drprg {
+
+void Mapper::ensure_stage(Stage& st, uint64_t payload_bytes, uint64_t n_reads, uint64_t n_npos)
+{
+    grow(st.d_bases, payload_bytes + 64, payload_bytes + payload_bytes / 4 + 64);
+    grow(st.d_offsets, n_reads + 1, n_reads + n_reads / 4 + 1);
+    grow(st.d_npos, n_npos, n_npos + n_npos / 4 + 16);
+}
+
+Mapper::DeviceBatch Mapper::copy_in(const HostBatch& hb, uint8_t* d_bases, uint64_t* d_offsets, uint64_t* d_npos, hipStream_t stream)
+{
+    const uint64_t n_npos = hb.packed ? hb.n_npos : 0;
+    const DeviceBatch b { d_bases, d_offsets, hb.n_reads, hb.n_bases(), hb.packed, n_npos ? d_npos : nullptr, n_npos };
+    HIPCHK(hipMemcpyAsync(d_bases, hb.bases, hb.payload_bytes(), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(d_offsets, hb.offsets, (hb.n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+    if (b.n_npos) HIPCHK(hipMemcpyAsync(d_npos, hb.npos, b.n_npos * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+    return b;
+}
+
+void Mapper::ensure_bam_scratch(BamScratch& s, uint64_t n_bases)
+{
+    const uint64_t n = (uint64_t)dev::bam_pack_chunks(n_bases) + 1;
+    const size_t temp = dev::scan_temp_bytes((uint32_t)n);
+    grow(s.d_count, n);
+    grow(s.d_prefix, n);
+    grow(s.d_temp, temp);
+}
+
+Mapper::DeviceBatch Mapper::copy_in_bam(const HostBatch& hb, Stage& st, uint8_t* d_words, uint64_t* d_offsets, uint64_t* d_npos, hipStream_t copy_stream,
+    hipStream_t stream)
+{
+    if (!hb.seq_start || (hb.seq_bytes && !hb.bases)) throw Error(DRPRG_EINVAL, "null buffer");
+    grow(st.d_seq, hb.seq_bytes + 16, hb.seq_bytes + hb.seq_bytes / 4 + 16);
+    grow(st.d_seq_start, hb.n_reads);
+    grow(st.d_reverse, hb.n_reads);
+    ensure_bam_scratch(st.bam, hb.n_bases());
+    // (n_npos: counted by the parser thread that copied the fields: no read-back, no wait)
+    const DeviceBatch b { d_words, d_offsets, hb.n_reads, hb.n_bases(), true, hb.n_npos ? d_npos : nullptr, hb.n_npos };
+    if (hb.seq_bytes) HIPCHK(hipMemcpyAsync(st.d_seq.data(), hb.bases, hb.seq_bytes, hipMemcpyHostToDevice, copy_stream));
+    HIPCHK(hipMemcpyAsync(st.d_seq_start.data(), hb.seq_start, hb.n_reads * sizeof(uint64_t), hipMemcpyHostToDevice, copy_stream));
+    if (hb.reverse) HIPCHK(hipMemcpyAsync(st.d_reverse.data(), hb.reverse, hb.n_reads, hipMemcpyHostToDevice, copy_stream));
+    HIPCHK(hipMemcpyAsync(d_offsets, hb.offsets, (hb.n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, copy_stream));
+    if (copy_stream != stream) {
+        HIPCHK(hipEventRecord(st.copied, copy_stream));
+        HIPCHK(hipStreamWaitEvent(stream, st.copied, 0));
+    }
+    HIPCHK(dev::launch_bam_pack(st.d_seq.data(), st.d_seq_start.data(), d_offsets, hb.reverse ? st.d_reverse.data() : nullptr, hb.n_reads, b.n_bases,
+        reinterpret_cast<uint32_t*>(d_words), d_npos, b.n_npos, b.n_npos != 0, st.bam.d_count.data(), st.bam.d_prefix.data(), st.bam.d_temp.data(),
+        st.bam.d_temp.size(), stream));
+    ++bam_blocks_;
+    return b;
+}
+
+void Mapper::map_host(const HostBatch& hb)
+{
+    if (hb.n_reads == 0) return;
+    sync();
+    HIPCHK(hipSetDevice(device_));
+    if (hb.offsets[0] != 0) throw Error(DRPRG_EINVAL, "offsets[0] must be 0");
+    map(copy_to_stage(hb, stage_sync_, stream_, stream_), nullptr, nullptr, stream_, false);
+    HIPCHK(hipStreamSynchronize(stream_)); // the staging buffers are reused by the next call
+}
+
+Mapper::DeviceBatch Mapper::copy_block_in(const HostBatch& hb, Stage* st, uint8_t* d_bases, uint64_t* d_offsets, uint64_t* d_npos, hipStream_t copy_stream,
+    hipStream_t stream)
+{
+    return hb.bam ? copy_in_bam(hb, *st, d_bases, d_offsets, d_npos, copy_stream, stream) : copy_in(hb, d_bases, d_offsets, d_npos, copy_stream);
+}
+
+Mapper::DeviceBatch Mapper::copy_to_stage(const HostBatch& hb, Stage& st, hipStream_t copy_stream, hipStream_t stream)
+{
+    ensure_stage(st, hb.payload_bytes(), hb.n_reads, hb.packed || hb.bam ? hb.n_npos : 0);
+    return copy_block_in(hb, &st, st.d_bases.data(), st.d_offsets.data(), st.d_npos.data(), copy_stream, stream);
+}
+
+hipStream_t Mapper::copy_stream()
+{
+    if (!copy_stream_) copy_stream_.create();
+    return copy_stream_;
+}
+
+Mapper::Stage& Mapper::next_stage()
+{
+    Stage& st = stage_[stage_next_];
+    stage_next_ ^= 1;
+    if (!st.copied) st.copied.create(false);
+    return st;
+}
+
+void Mapper::count_unmapped(uint64_t n, bool keeping)
+{
+    tot_reads_ += n;
+    if (keeping) resident_.count_empty(n);
+}
+
+void Mapper::only_empty_reads(uint64_t n_reads, const ReadFilter& f, bool keeping, FilterOutcome& o)
+{
+    o.dropped_short = f.min_len ? n_reads : 0;
+    o.reads_kept = o.mapped_reads = n_reads - o.dropped_short;
+    count_unmapped(o.reads_kept, keeping);
+}
+
+hipStream_t Mapper::device_entry(hipStream_t stream, bool null_pointer, uint64_t n_reads)
+{
+    HIPCHK(hipSetDevice(device_));
+    if (null_pointer) throw Error(DRPRG_EINVAL, "null device pointer");
+    if (n_reads > dev::MAX_BATCH_READS) throw Error(DRPRG_EOVERFLOW, "at most " + std::to_string(dev::MAX_BATCH_READS) + " reads per batch");
+    return stream ? stream : static_cast<hipStream_t>(stream_);
+}
+
+uint64_t Mapper::pack_on_device(const uint8_t* d_bases, uint64_t n_bases, uint32_t* d_words, uint64_t* d_npos, uint64_t npos_cap, hipStream_t stream)
+{
+    HIPCHK(hipSetDevice(device_));
+    if (!stream) stream = stream_;
+    if (n_bases == 0) return 0;
+    if (!d_bases || !d_words) throw Error(DRPRG_EINVAL, "null device pointer");
+    if (!d_pack_count_) d_pack_count_.alloc(1); // (one counter word per Mapper: an allocation per call synchronises the device)
+    unsigned long long n = 0;
+    HIPCHK(hipMemsetAsync(d_pack_count_.data(), 0, sizeof(unsigned long long), stream));
+    HIPCHK(dev::launch_pack(d_bases, n_bases, d_words, d_npos, d_npos ? npos_cap : 0, d_pack_count_.data(), stream));
+    HIPCHK(hipMemcpyAsync(&n, d_pack_count_.data(), sizeof n, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    if (n && !d_npos) throw Error(DRPRG_EINVAL, "the batch holds bases that are not ACGT and no buffer for their positions was given");
+    if (d_npos && n > 1 && n <= npos_cap) { // the positions come out in any order: sorted on the host (few; the harness path)
+        std::vector<uint64_t> h(n);
+        HIPCHK(hipMemcpy(h.data(), d_npos, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        std::sort(h.begin(), h.end());
+        HIPCHK(hipMemcpy(d_npos, h.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice));
+    }
+    return n;
+}
+
+uint64_t Mapper::pack_bam_on_device(const uint8_t* d_seq, const uint64_t* d_seq_start, const uint64_t* d_offsets, const uint8_t* d_reverse, uint64_t n_reads,
+    uint64_t n_bases, uint32_t* d_words, uint64_t* d_npos, uint64_t npos_cap, hipStream_t stream)
+{
+    if (n_bases == 0) return 0;
+    if (n_reads == 0) throw Error(DRPRG_EINVAL, "bases without reads");
+    stream = device_entry(stream, !d_seq || !d_seq_start || !d_offsets || !d_words, n_reads);
+    ensure_bam_scratch(bam_api_, n_bases);
+    const uint32_t n_chunks = dev::bam_pack_chunks(n_bases);
+    HIPCHK(dev::launch_bam_pack(d_seq, d_seq_start, d_offsets, d_reverse, n_reads, n_bases, d_words, d_npos, d_npos ? npos_cap : 0, true,
+        bam_api_.d_count.data(), bam_api_.d_prefix.data(), bam_api_.d_temp.data(), bam_api_.d_temp.size(), stream));
+    uint32_t n = 0;
+    HIPCHK(hipMemcpyAsync(&n, bam_api_.d_prefix.data() + n_chunks, sizeof n, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    if (n && !d_npos) throw Error(DRPRG_EINVAL, "the batch holds bases that are not ACGT and no buffer for their positions was given");
+    return n;
+}
+
+void Mapper::map_host_async(const HostBatch& hb)
+{
+    const uint64_t n_reads = hb.n_reads;
+    if (n_reads == 0) return;
+    const bool keeping = resident_.active();
+    if (!keeping && !use_filter_) return map_host(hb); // no deferred form of this sequence
+    HIPCHK(hipSetDevice(device_));
+    if (hb.offsets[0] != 0) throw Error(DRPRG_EINVAL, "offsets[0] must be 0");
+    if (hb.n_bases() == 0) { // only empty reads: nothing to copy, nothing to keep, nothing to map (the counters still see them)
+        count_unmapped(n_reads, keeping);
+        return;
+    }
+    // under keep_reads the block goes into device memory of its own and stays there; else into a staging set
+    std::optional<BlockRoom> own;
+    if (keeping && !(own = resident_.take_block(hb.payload_bytes(), n_reads, hb.packed || hb.bam ? hb.n_npos : 0))) {
+        stop_keeping();
+        return map_host_async(hb); // (as any block of a context that keeps nothing)
+    }
+    const hipStream_t cs = copy_stream();
+    Stage* st = own && !hb.bam ? nullptr : &next_stage(); // (a BAM block is kept in the packed form: its raw fields go through a staging set)
+    if (own && !kept_copied_) kept_copied_.create(false);
+    const hipEvent_t copied = own ? kept_copied_ : st->copied;
+    const DeviceBatch b = own ? copy_block_in(hb, st, own->bases, own->offsets, own->npos, cs, stream_) : copy_to_stage(hb, *st, cs, stream_);
+    HIPCHK(hipEventRecord(copied, cs));
+    HIPCHK(hipStreamWaitEvent(stream_, copied, 0));
+    if (own) {
+        resident_.add(b, n_reads);
+        map_resident_block(b);
+    } else map(b, nullptr, nullptr, stream_, true);
+    HIPCHK(hipEventSynchronize(copied)); // the caller's block is free again; the kernels run on
+}
+
+// ---- the read filter ---------------------------------------------------------------------------------------------------------------
+void Mapper::ensure_filter_scratch(FilterScratch& fs, uint64_t n_reads, uint64_t qual_bytes, bool own_flags, bool own_sums)
+{
+    if (qual_bytes) grow(fs.d_qual, qual_bytes + 64);
+    if (own_flags) grow(fs.d_flag, n_reads);
+    if (own_sums) grow(fs.d_qsum, n_reads);
+    grow(fs.d_flag32, n_reads + 1);
+    grow(fs.d_rank, n_reads + 1);
+    grow(fs.d_klen, n_reads + 1);
+    grow(fs.d_boff, n_reads + 1);
+    grow(fs.d_temp, dev::read_filter_temp_bytes(n_reads));
+    if (!fs.d_work) fs.d_work.alloc(8);
+    if (!fs.h_out) fs.h_out.alloc(8);
+}
+
+void Mapper::run_read_filter(FilterScratch& fs, const ReadFilter& f, const uint8_t* d_qual, uint32_t bias, const uint64_t* d_offsets, uint64_t n_reads,
+    uint64_t n_bases, unsigned long long* d_sums, uint8_t* d_flags, hipStream_t stream)
+{
+    dev::ReadFilterArgs a {};
+    a.qual = d_qual; a.bias = bias; a.offsets = d_offsets; a.n_reads = n_reads; a.n_bases = n_bases;
+    a.min_len = f.min_len; a.max_len = f.max_len; a.T = f.T; a.use_qual = f.use_qual(); // (a batch of empty reads launches no tile, and its sums are still cleared)
+    a.qsum = d_sums; a.flag = d_flags; a.flag32 = fs.d_flag32.data(); a.rank = fs.d_rank.data(); a.klen = fs.d_klen.data(); a.boff = fs.d_boff.data();
+    a.work = fs.d_work.data(); a.out = fs.h_out.device_ptr(); a.temp = fs.d_temp.data(); a.temp_bytes = fs.d_temp.size();
+    HIPCHK(dev::launch_read_filter(a, stream));
+}
+
+void Mapper::read_filter_device(const ReadFilter& f, const uint8_t* d_qual, uint32_t bias, const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases,
+    unsigned long long* d_sums, uint8_t* d_flags, uint64_t res[8], hipStream_t stream)
+{
+    for (int i = 0; i < 8; ++i) res[i] = 0;
+    if (n_reads == 0) return;
+    stream = device_entry(stream, !d_offsets || !d_flags || (f.use_qual() && n_bases && !d_qual), n_reads);
+    FilterScratch& fs = filter_api_;
+    ensure_filter_scratch(fs, n_reads, 0, false, f.use_qual() && !d_sums);
+    if (f.use_qual() && !d_sums) d_sums = fs.d_qsum.data();
+    run_read_filter(fs, f, d_qual, bias, d_offsets, n_reads, n_bases, d_sums, d_flags, stream);
+    HIPCHK(hipStreamSynchronize(stream));
+    for (int i = 0; i < 8; ++i) res[i] = fs.h_out[i];
+}
+
+// ---- read trimming -------------------------------------------------------------------------------------------------------------------
+void Mapper::ensure_trim_scratch(FilterScratch& fs, uint64_t n_reads, uint64_t n_npos, bool use_qual, bool own_ranges, bool adapters, uint64_t bitmap_bases)
+{
+    if (use_qual) {
+        grow(fs.t_first, n_reads);
+        grow(fs.t_last, n_reads);
+    }
+    if (own_ranges) {
+        grow(fs.t_begin, n_reads);
+        grow(fs.t_end, n_reads);
+    }
+    grow(fs.t_klen, n_reads + 1);
+    grow(fs.t_offsets, n_reads + 1);
+    grow(fs.t_temp, dev::read_trim_temp_bytes(n_reads));
+    if (n_npos) {
+        const uint64_t chunks = (uint64_t)dev::read_trim_npos_chunks(n_npos) + 1;
+        grow(fs.t_count, chunks);
+        grow(fs.t_prefix, chunks);
+        grow(fs.t_ntemp, dev::scan_temp_bytes((uint32_t)chunks));
+    }
+    if (adapters) {
+        grow(fs.t_cut, n_reads);
+        if (bitmap_bases) grow(fs.t_nbits, (bitmap_bases + 15) / 16 + 8); // (launch_mark_npos writes 32-bit words)
+    }
+    if (!fs.t_work) fs.t_work.alloc(dev::RT_WORDS);
+    if (!fs.t_out) fs.t_out.alloc(dev::RT_WORDS);
+}
+
+dev::AdapterPoints Mapper::adapter_points(FilterScratch& fs, const uint8_t* d_bases, bool packed, const uint64_t* d_npos, uint64_t n_npos, uint64_t n_bases,
+    hipStream_t stream)
+{
+    dev::AdapterPoints p {};
+    p.cut = fs.t_cut.data();
+    if (!packed) {
+        p.text = d_bases;
+        return p;
+    }
+    p.words = reinterpret_cast<const uint32_t*>(d_bases);
+    if (n_npos) {
+        const uint64_t n16 = (n_bases + 15) / 16 + 8;
+        HIPCHK(hipMemsetAsync(fs.t_nbits.data(), 0, n16 * sizeof(uint16_t), stream));
+        HIPCHK(dev::launch_mark_npos(d_npos, n_npos, n_bases, fs.t_nbits.data(), stream));
+        p.nbits = fs.t_nbits.data();
+    }
+    return p;
+}
+
+void Mapper::run_read_trim(FilterScratch& fs, const ReadFilter& f, const uint8_t* d_qual, uint32_t bias, const uint64_t* d_offsets, const uint8_t* d_rev,
+    uint64_t n_reads, uint64_t n_bases, uint64_t* d_begin, uint64_t* d_end, const uint64_t* d_npos, uint64_t n_npos, hipStream_t stream,
+    const dev::AdapterPoints* pts)
+{
+    dev::ReadTrimArgs a {};
+    dev::AdapterEditSets edit {};
+    const bool indels = pts && f.adapter_indels && f.any_adapters();
+    if (pts && f.any_adapters()) {
+        a.pts = *pts;
+        if (indels) edit = dev::AdapterEditSets { f.adapters, f.front_adapters, f.eq3, f.eq5 };
+        else a.ad = f.adapters;
+    }
+    a.qual = d_qual; a.bias = bias; a.offsets = d_offsets; a.rev = d_rev; a.n_reads = n_reads; a.n_bases = n_bases;
+    a.front = f.trim_front; a.tail = f.trim_tail; a.qual_milli = f.trim_qual_milli; a.window = f.trim_window;
+    a.first = fs.t_first.data(); a.last = fs.t_last.data(); a.begin = d_begin; a.end = d_end; a.klen = fs.t_klen.data(); a.noff = fs.t_offsets.data();
+    a.work = fs.t_work.data(); a.out = fs.t_out.device_ptr(); a.temp = fs.t_temp.data(); a.temp_bytes = fs.t_temp.size();
+    dev::ReadTrimNpos np {};
+    if (n_npos) np = dev::ReadTrimNpos { d_npos, n_npos, fs.t_count.data(), fs.t_prefix.data(), fs.t_ntemp.data(), fs.t_ntemp.size() };
+    HIPCHK(dev::launch_read_trim(a, np, stream, {}, indels ? &edit : nullptr));
+}
+
+void Mapper::read_trim_device(const ReadFilter& f, const uint8_t* d_qual, uint32_t bias, const uint64_t* d_offsets, const uint8_t* d_rev, uint64_t n_reads,
+    uint64_t n_bases, uint64_t* d_begin, uint64_t* d_end, uint64_t res[9], hipStream_t stream)
+{
+    for (int i = 0; i < 9; ++i) res[i] = 0;
+    if (n_reads == 0) return;
+    stream = device_entry(stream, !d_offsets || !d_begin || !d_end || (f.trim_qual_milli && n_bases && !d_qual), n_reads);
+    FilterScratch& fs = filter_api_;
+    ensure_trim_scratch(fs, n_reads, 0, f.trim_qual_milli != 0, false);
+    run_read_trim(fs, f, d_qual, bias, d_offsets, d_rev, n_reads, n_bases, d_begin, d_end, nullptr, 0, stream);
+    HIPCHK(hipStreamSynchronize(stream));
+    for (int i = 0; i < 9; ++i) res[i] = fs.t_out[i];
+}
+
+void Mapper::adapter_trim_device(const ReadFilter& f, const uint8_t* d_text, const uint32_t* d_words, const uint64_t* d_npos, uint64_t n_npos,
+    const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases, uint64_t* d_begin, uint64_t* d_end, uint64_t res[11], hipStream_t stream)
+{
+    for (int i = 0; i < 11; ++i) res[i] = 0;
+    if (n_reads == 0) return;
+    if (!f.any_adapters()) throw Error(DRPRG_EINVAL, "adapter trimming: no adapter is set (drprg_hip_set_adapters, drprg_hip_set_adapters2)");
+    stream = device_entry(stream, !d_offsets || !d_begin || !d_end || (n_bases && !d_text && !d_words) || (n_npos && !d_npos), n_reads);
+    FilterScratch& fs = filter_api_;
+    ensure_trim_scratch(fs, n_reads, 0, false, false, true, d_words && n_npos ? n_bases : 0);
+    dev::AdapterPoints p = adapter_points(fs, d_words ? reinterpret_cast<const uint8_t*>(d_words) : d_text, d_words != nullptr, d_npos, n_npos, n_bases, stream);
+    p.offsets = d_offsets; p.begin = d_begin; p.end = d_end; p.n_reads = n_reads; p.n_bases = n_bases;
+    HIPCHK(hipMemsetAsync(fs.t_work.data(), 0, dev::RT_WORDS * sizeof(unsigned long long), stream));
+    if (f.adapter_indels)
+        HIPCHK(dev::launch_adapter_edit(p, f.adapters, f.eq3, f.front_adapters, f.eq5, d_begin, d_end, nullptr, fs.t_work.data(), stream));
+    else HIPCHK(dev::launch_adapter_trim(p, f.adapters, d_end, nullptr, fs.t_work.data(), stream));
+    HIPCHK(hipMemcpyAsync(fs.t_out.data(), fs.t_work.data(), dev::RT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    if (f.adapters.n) res[0] = n_reads;
+    if (f.front_adapters.n) res[5] = n_reads;
+    for (int i = 0; i < 4; ++i) {
+        res[1 + i] = fs.t_out[dev::RT_AD_BASES_SEEN + i];
+        res[6 + i] = fs.t_out[dev::RT_FA_BASES_SEEN + i];
+    }
+    res[10] = fs.t_out[dev::RT_OFFSETS];
+}
+
+// ---- a host block behind the filter: map_host_filtered and its steps ---------------------------------------------------------------------
+// what the trim stage and the filter say alike about a quality byte out of range (at: the byte's index + 1)
+static Error bad_quality_error(uint64_t at, uint64_t n_bases, uint32_t bias)
+{
+    return Error(DRPRG_EFORMAT, "a base quality outside 0..93 (quality byte " + std::to_string(at - 1) + " of an ingest block of " + std::to_string(n_bases)
+            + " bases, " + (bias ? "FASTQ: bytes 33..126" : "BAM: bytes 0..93") + ")");
+}
+
+// The trim stage: the kept range of every read, the new offsets and the counts, one read-back; a block that lost a base is compacted by
+// its ranges into the set's t_* buffers (launch_subsample_pack for words, launch_gather_reads for text and for the quality bytes) and
+// `src` and the quality pointer are REPLACED: the filter, the depth cut, the compaction and keep_reads see a block of trimmed reads.
+// trim_err receives that compaction's error word once the stream has been waited for again (with the filter's read-back).  false: every
+// base of the block is gone.
+bool Mapper::trim_block(const HostBatch& hb, const ReadFilter& f, Stage& st, DeviceBatch& src, const uint8_t*& d_qual, uint32_t& trim_err, FilterOutcome& o)
+{
+    FilterScratch& fs = st.filt;
+    const hipStream_t cs = copy_stream_;
+    const uint64_t n_reads = src.n_reads, n_bases = src.n_bases;
+    const uint8_t* d_rev = hb.bam && hb.reverse ? st.d_reverse.data() : nullptr; // (BAM: QUAL stays in stored order; the bases were reversed by bam_pack_kernel)
+    dev::AdapterPoints pts {}; // (adapters: sought in what the crops and the quality trim leave, bases in read orientation; a packed block's bitmap first)
+    if (f.any_adapters()) pts = adapter_points(fs, src.d_bases, src.packed, src.d_npos, src.n_npos, n_bases, cs);
+    run_read_trim(fs, f, d_qual, hb.qual_bias, src.d_offsets, d_rev, n_reads, n_bases, fs.t_begin.data(), fs.t_end.data(), src.d_npos, src.n_npos, cs, &pts);
+    HIPCHK(hipStreamSynchronize(cs)); // the trim's read-back: the trimmed sizes are known before the filter is launched
+    const unsigned long long* t = fs.t_out.data();
+    if (t[dev::RT_BAD_AT] == ~0ull) throw Error(DRPRG_EINVAL, "read trimming: the block's offsets do not ascend to its number of bases");
+    if (t[dev::RT_BAD_AT]) throw bad_quality_error(t[dev::RT_BAD_AT], n_bases, hb.qual_bias);
+    if (f.crops())
+        o.trim = TrimOutcome { n_reads, n_bases, t[dev::RT_LOST_READS], t[dev::RT_CUT_FRONT], t[dev::RT_CUT_TAIL], t[dev::RT_QCUT_FRONT], t[dev::RT_QCUT_TAIL],
+            t[dev::RT_EMPTIED] };
+    if (f.adapters.n)
+        o.adapter = AdapterOutcome { n_reads, t[dev::RT_AD_BASES_SEEN], t[dev::RT_AD_READS_CUT], t[dev::RT_AD_BASES_CUT], t[dev::RT_AD_EMPTIED] };
+    if (f.front_adapters.n)
+        o.front = AdapterOutcome { n_reads, t[dev::RT_FA_BASES_SEEN], t[dev::RT_FA_READS_CUT], t[dev::RT_FA_BASES_CUT], t[dev::RT_FA_EMPTIED] };
+    if (!t[dev::RT_LOST_READS] && !t[dev::RT_AD_READS_CUT] && !t[dev::RT_FA_READS_CUT]) return true; // the block lost no base to any cause
+    const uint64_t nb = t[dev::RT_KEPT_BASES], n_list = src.n_npos ? t[dev::RT_KEPT_NPOS] : 0;
+    o.bases_seen = nb;
+    if (nb == 0) return false;
+    const uint64_t payload = src.packed ? (nb + 15) / 16 * 4 : nb;
+    grow(fs.t_bases, payload + 64);
+    if (n_list) grow(fs.t_npos, n_list);
+    if (f.use_qual()) grow(fs.t_qual, nb + 64);
+    if (src.packed) grow(fs.t_src, n_reads);
+    if (!src.packed) grow(fs.t_btable, n_reads);
+    if (f.use_qual()) grow(fs.t_qtable, n_reads);
+    uint32_t* const d_err = reinterpret_cast<uint32_t*>(fs.t_work.data() + dev::RT_KEPT_NPOS); // (zeroed with the trim's words, unused on the device)
+    dev::ReadTrimFill tf { src.d_offsets, d_rev, fs.t_begin.data(), fs.t_end.data(), fs.t_offsets.data(), n_reads, n_bases, nb, src.d_bases, d_qual,
+        src.packed ? fs.t_src.data() : nullptr, src.packed ? nullptr : fs.t_btable.data(), f.use_qual() ? fs.t_qtable.data() : nullptr, d_err };
+    HIPCHK(dev::launch_read_trim_fill(tf, cs));
+    HIPCHK(hipMemsetAsync(fs.t_bases.data() + payload, 0, 64, cs));
+    if (src.packed) { // (by ranges, not by flags: the one pack launch outside compact_block)
+        const dev::SubsampleBlock sb { src.d_bases, src.d_offsets, n_reads, n_bases, 0, nullptr, nullptr, nullptr, n_reads, nb };
+        HIPCHK(dev::launch_subsample_pack(sb, fs.t_offsets.data(), fs.t_src.data(), reinterpret_cast<uint32_t*>(fs.t_bases.data()), d_err, cs));
+        if (n_list) {
+            const dev::ReadTrimNpos np { src.d_npos, src.n_npos, fs.t_count.data(), fs.t_prefix.data(), fs.t_ntemp.data(), fs.t_ntemp.size() };
+            HIPCHK(dev::launch_read_trim_npos_emit(tf, np, fs.t_npos.data(), n_list, cs));
+        }
+    } else HIPCHK(dev::launch_gather_reads(fs.t_btable.data(), (uint32_t)n_reads, fs.t_bases.data(), cs));
+    if (f.use_qual()) {
+        HIPCHK(dev::launch_gather_reads(fs.t_qtable.data(), (uint32_t)n_reads, fs.t_qual.data(), cs));
+        HIPCHK(hipMemsetAsync(fs.t_qual.data() + nb, 0, 64, cs));
+        d_qual = fs.t_qual.data();
+    }
+    HIPCHK(hipMemcpyAsync(&trim_err, d_err, sizeof trim_err, hipMemcpyDeviceToHost, cs)); // (queued behind the compaction; waited for with the filter's read-back)
+    src.d_bases = fs.t_bases.data();
+    src.d_offsets = fs.t_offsets.data();
+    src.n_bases = nb;
+    src.d_npos = n_list ? fs.t_npos.data() : nullptr;
+    src.n_npos = n_list;
+    return true;
+}
+
+// The filter on the block as the trim stage left it, with its read-back: the caller's block is free again when this returns.
+void Mapper::filter_block(const HostBatch& hb, const ReadFilter& f, FilterScratch& fs, const DeviceBatch& src, const uint8_t* d_qual, const uint32_t& trim_err,
+    FilterOutcome& o)
+{
+    const hipStream_t cs = copy_stream_;
+    run_read_filter(fs, f, d_qual, hb.qual_bias, src.d_offsets, src.n_reads, src.n_bases, fs.d_qsum.data(), fs.d_flag.data(), cs);
+    HIPCHK(hipStreamSynchronize(cs));
+    if (trim_err) throw Error(DRPRG_EIO, "read trimming: the block's offsets and the trimmed ranges do not fit each other");
+    const unsigned long long* h = fs.h_out.data();
+    if (h[dev::RF_OFFSETS]) throw Error(DRPRG_EINVAL, "read filter: the block's offsets do not ascend to its number of bases");
+    if (h[dev::RF_BAD_AT]) throw bad_quality_error(h[dev::RF_BAD_AT], src.n_bases, hb.qual_bias);
+    o.dropped_short = h[dev::RF_SHORT];
+    o.dropped_long = h[dev::RF_LONG];
+    o.dropped_lowq = h[dev::RF_LOWQ];
+    o.reads_kept = h[dev::RF_KEPT_READS];
+    o.bases_kept = h[dev::RF_KEPT_BASES];
+}
+
+// Which of the kept reads go on: all of them, or -- cap_need != 0 and reached in this block -- those up to the one that holds the
+// cap_need-th kept base.
+Mapper::KeptPart Mapper::cut_at_cap(FilterScratch& fs, uint64_t n_reads, uint64_t cap_need, FilterOutcome& o)
+{
+    KeptPart k { n_reads, o.reads_kept, o.bases_kept };
+    if (!cap_need || k.n_bases < cap_need) return k;
+    // the cut, in the block's own numbering: boff is the running total of the kept bases (covg_cut.hip on the scan instead of the offsets)
+    const hipStream_t cs = copy_stream_;
+    if (!h_cut_) h_cut_.alloc(4);
+    HIPCHK(dev::launch_covg_cut(fs.d_boff.data(), n_reads, cap_need, nullptr, 0, h_cut_.device_ptr(), cs));
+    HIPCHK(hipStreamSynchronize(cs));
+    k.take = h_cut_[0];
+    k.n_bases = h_cut_[1];
+    uint32_t rk = 0;
+    HIPCHK(hipMemcpyAsync(&rk, fs.d_rank.data() + k.take, sizeof rk, hipMemcpyDeviceToHost, cs));
+    HIPCHK(hipStreamSynchronize(cs));
+    o.cut = true;
+    o.cut_dropped = k.n_reads - rk;
+    k.n_reads = rk;
+    return k;
+}
+
+// Where the block that goes on lies when it is mapped.  A block that lost reads is compacted by the filter's flags (compact_block): into
+// the resident set under keep_reads, else into the stage's c_* buffers.  A block that lost none stays in the staging set, and under
+// keep_reads is copied on the device to where it stays.  keeping: cleared when the resident set cannot take the block (stop_keeping).
+Mapper::DeviceBatch Mapper::place_block(FilterScratch& fs, const DeviceBatch& src, const KeptPart& k, bool& keeping)
+{
+    const hipStream_t cs = copy_stream_;
+    const uint64_t payload = src.packed ? (k.n_bases + 15) / 16 * 4 : k.n_bases;
+    if (k.n_reads == src.n_reads) { // the whole block
+        if (!keeping) return src;
+        const std::optional<BlockRoom> dst = resident_.take_block(payload, k.n_reads, src.n_npos);
+        if (!dst) {
+            stop_keeping();
+            keeping = false;
+            return src;
+        }
+        HIPCHK(hipMemsetAsync(dst->bases + payload, 0, 64, cs));
+        HIPCHK(hipMemcpyAsync(dst->bases, src.d_bases, payload, hipMemcpyDeviceToDevice, cs));
+        HIPCHK(hipMemcpyAsync(dst->offsets, src.d_offsets, (k.n_reads + 1) * sizeof(uint64_t), hipMemcpyDeviceToDevice, cs));
+        if (src.n_npos) HIPCHK(hipMemcpyAsync(dst->npos, src.d_npos, src.n_npos * sizeof(uint64_t), hipMemcpyDeviceToDevice, cs));
+        HIPCHK(hipStreamSynchronize(cs)); // (the block is whole before anything on the mapping stream reads it)
+        return DeviceBatch { dst->bases, dst->offsets, k.n_reads, k.n_bases, src.packed, src.n_npos ? dst->npos : nullptr, src.n_npos };
+    }
+    const dev::SubsampleBlock sb { src.d_bases, src.d_offsets, k.take, src.n_bases, 0, fs.d_flag.data(), fs.d_rank.data(), fs.d_boff.data(), k.n_reads, k.n_bases };
+    uint32_t* const d_err = reinterpret_cast<uint32_t*>(fs.d_work.data() + 7); // (zeroed with the filter's words)
+    const DeviceBatch cur = compact_block(sb, src, fs.comp, d_err, cs, [&](uint64_t n_list) {
+        if (keeping) {
+            if (const std::optional<BlockRoom> dst = resident_.take_block(payload, k.n_reads, n_list)) return *dst;
+            stop_keeping();
+            keeping = false;
+        }
+        grow(fs.c_bases, payload + 64, payload + payload / 4 + 64); // (the staging sets' padding rule: ensure_stage)
+        grow(fs.c_offsets, k.n_reads + 1, k.n_reads + k.n_reads / 4 + 1);
+        grow(fs.c_npos, n_list, n_list + n_list / 4 + 16);
+        return BlockRoom { fs.c_bases.data(), fs.c_offsets.data(), fs.c_npos.data() };
+    });
+    uint32_t err = 0;
+    HIPCHK(hipMemcpyAsync(&err, d_err, sizeof err, hipMemcpyDeviceToHost, cs));
+    HIPCHK(hipStreamSynchronize(cs));
+    if (err) throw Error(DRPRG_EIO, "read filter: the block's offsets and the filter's scans do not fit each other");
+    return cur;
+}
+
+void Mapper::map_host_filtered(const HostBatch& hb, const ReadFilter& f, uint64_t cap_need, FilterOutcome& o)
+{
+    o = FilterOutcome {};
+    const uint64_t n_reads = hb.n_reads;
+    if (n_reads == 0) return;
+    HIPCHK(hipSetDevice(device_));
+    if (hb.offsets[0] != 0) throw Error(DRPRG_EINVAL, "offsets[0] must be 0");
+    const uint64_t n_bases = hb.n_bases();
+    o.reads_seen = n_reads;
+    o.bases_seen = n_bases;
+    bool keeping = resident_.active();
+    if (n_bases == 0) { // (the counters still see them)
+        only_empty_reads(n_reads, f, keeping, o);
+        return;
+    }
+    if (f.trim_qual_milli && !hb.qual) throw Error(DRPRG_EINVAL, "--trim-qual: the reads came without base qualities");
+    if (f.use_qual() && !hb.qual) throw Error(DRPRG_EINVAL, "--min-read-qual: the reads came without base qualities");
+    if (n_reads > dev::MAX_BATCH_READS) throw Error(DRPRG_EOVERFLOW, "at most " + std::to_string(dev::MAX_BATCH_READS) + " reads per batch");
+    // 1. copy in: the block into a staging set, its quality bytes beside it
+    const hipStream_t cs = copy_stream();
+    Stage& st = next_stage();
+    FilterScratch& fs = st.filt;
+    const uint64_t n_npos = hb.packed || hb.bam ? hb.n_npos : 0;
+    ensure_filter_scratch(fs, n_reads, f.wants_qual() ? n_bases : 0, true, f.use_qual());
+    if (f.trims()) ensure_trim_scratch(fs, n_reads, n_npos, f.trim_qual_milli != 0, true, f.any_adapters(), n_npos ? n_bases : 0);
+    DeviceBatch src = copy_to_stage(hb, st, cs, cs);
+    if (f.wants_qual()) {
+        HIPCHK(hipMemcpyAsync(fs.d_qual.data(), hb.qual, n_bases, hipMemcpyHostToDevice, cs));
+        HIPCHK(hipMemsetAsync(fs.d_qual.data() + n_bases, 0, 64, cs));
+    }
+    const uint8_t* d_qual = fs.d_qual.data();
+    uint32_t trim_err = 0;
+    // 2. trim, 3. filter, 4. the depth cap
+    if (f.trims() && !trim_block(hb, f, st, src, d_qual, trim_err, o)) { // reads of no bases are left: nothing to map
+        hand_back_stage();
+        only_empty_reads(n_reads, f, keeping, o);
+        return;
+    }
+    filter_block(hb, f, fs, src, d_qual, trim_err, o);
+    const KeptPart k = cut_at_cap(fs, n_reads, cap_need, o);
+    o.mapped_reads = k.n_reads;
+    o.mapped_bases = k.n_bases;
+    if (k.n_bases == 0) { // nothing of the block is left, or empty reads only
+        hand_back_stage();
+        count_unmapped(k.n_reads, keeping);
+        return;
+    }
+    // 5. place, 6. map
+    const DeviceBatch cur = place_block(fs, src, k, keeping);
+    if (keeping) {
+        resident_.add(cur, k.n_reads);
+        map_resident_block(cur);
+    } else map(cur, nullptr, nullptr, stream_, true);
+}
+
+Mapper::TrimOutcome& Mapper::TrimOutcome::operator+=(const TrimOutcome& o)
+{
+    reads_seen += o.reads_seen; bases_seen += o.bases_seen; reads_lost_base += o.reads_lost_base; cut_front += o.cut_front;
+    cut_tail += o.cut_tail; qcut_front += o.qcut_front; qcut_tail += o.qcut_tail; emptied += o.emptied;
+    return *this;
+}
+
+Mapper::AdapterOutcome& Mapper::AdapterOutcome::operator+=(const AdapterOutcome& o)
+{
+    reads_seen += o.reads_seen; bases_seen += o.bases_seen; reads_cut += o.reads_cut; bases_cut += o.bases_cut; reads_emptied += o.reads_emptied;
+    return *this;
+}
+
+Mapper::FilterOutcome& Mapper::FilterOutcome::operator+=(const FilterOutcome& o)
+{
+    trim += o.trim; adapter += o.adapter; front += o.front;
+    reads_seen += o.reads_seen; bases_seen += o.bases_seen; dropped_short += o.dropped_short; dropped_long += o.dropped_long;
+    dropped_lowq += o.dropped_lowq; reads_kept += o.reads_kept; bases_kept += o.bases_kept;
+    mapped_reads += o.mapped_reads; mapped_bases += o.mapped_bases; cut_dropped += o.cut_dropped;
+    return *this;
+}
+
+} // namespace drprg

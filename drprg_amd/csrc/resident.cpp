@@ -1,0 +1,473 @@
+// resident.cpp -- the reads that stay in device memory (keep_reads): the arenas, the one compaction by flags, random subsample, duplicate
+// removal and the read selection for discover.  See mapper.h.
+#include "mapper.h"
+#include <algorithm>
+#include <cstdio>
+#include <hip/hip_runtime.h>
+
+namespace drprg {
+
+void* Mapper::ResidentSet::arena_take(size_t n)
+{
+    n = (n + 255) / 256 * 256;
+    if (bytes + n > cap) return nullptr;
+    if (n > left) {
+        // (what is left of the current piece is not used: pieces are 256 MB, blocks ~25 MB)
+        const size_t piece = std::max<size_t>(n, std::min<uint64_t>(256ull << 20, cap - bytes));
+        DeviceBuffer<uint8_t> arena;
+        try {
+            arena.alloc(piece);
+        } catch (const Error&) { // (the device is full: the caller goes on without resident reads)
+            (void)hipGetLastError();
+            return nullptr;
+        }
+        arenas.push_back(std::move(arena));
+        at = arenas.back().data();
+        left = piece;
+    }
+    void* r = at;
+    at += n;
+    left -= n;
+    bytes += n;
+    return r;
+}
+
+std::optional<Mapper::BlockRoom> Mapper::ResidentSet::take_block(uint64_t payload_bytes, uint64_t n_reads, uint64_t n_npos)
+{
+    BlockRoom r {};
+    if (!(r.bases = static_cast<uint8_t*>(arena_take(payload_bytes + 64)))) return std::nullopt;
+    if (!(r.offsets = static_cast<uint64_t*>(arena_take((n_reads + 1) * sizeof(uint64_t))))) return std::nullopt;
+    if (n_npos && !(r.npos = static_cast<uint64_t*>(arena_take(n_npos * sizeof(uint64_t))))) return std::nullopt;
+    return r;
+}
+
+void Mapper::keep_reads(uint64_t max_bytes)
+{
+    drop_kept();
+    resident_.cap = max_bytes;
+    // reads mapped before this call are not resident: kept_complete() must not claim them (map_resident would map a subset)
+    resident_.broken = tot_reads_ != 0;
+}
+
+void Mapper::drop_kept()
+{
+    if (!resident_.arenas.empty()) {
+        sync();
+        HIPCHK(hipSetDevice(device_));
+        HIPCHK(hipStreamSynchronize(stream_));
+    }
+    resident_.clear();
+}
+
+// The map call on a block of the resident set.  in_keep_call_ is set for as long as it runs and on no other path: map() takes every other
+// batch for reads of the caller's own buffers and marks the set broken.
+void Mapper::map_resident_block(const DeviceBatch& b)
+{
+    struct Guard {
+        bool& flag;
+        explicit Guard(bool& f) : flag(f) { flag = true; }
+        ~Guard() { flag = false; }
+    } guard(in_keep_call_);
+    map(b, nullptr, nullptr, stream_, true);
+}
+
+uint64_t Mapper::map_kept_from(const Mapper& other)
+{
+    if (other.device_ != device_) throw Error(DRPRG_EINVAL, "the kept reads live on another device");
+    if (!other.kept_complete()) throw Error(DRPRG_ENODATA, "the other context does not hold all of its reads");
+    uint64_t n = 0;
+    for (const DeviceBatch& b : other.resident_.kept) {
+        map(b, nullptr, nullptr, stream_, true);
+        n += b.n_reads;
+    }
+    sync();
+    HIPCHK(hipStreamSynchronize(stream_));
+    return n;
+}
+
+// over the limit (or the device is full): nothing is kept from here on, and what was kept is of no use without the rest
+void Mapper::stop_keeping()
+{
+    const uint64_t cap = resident_.cap;
+    drop_kept(); // (the cap stays)
+    resident_.broken = true;
+    // (said once per context, always: the run takes a different, slower route from here -- results are the same)
+    std::fprintf(stderr, "[drprg-hip] the sample is larger than the %.1f GB of device memory set aside for resident reads (device %d): reads are "
+                         "not kept, later passes read the file again (DRPRG_HIP_KEEP_READS_GB raises the limit)\n", (double)cap / 1e9, device_);
+}
+
+// What subsample_kept and dedup_kept begin with: the whole sample is resident, nothing is in flight, and what the sample holds.
+Mapper::SubsampleResult Mapper::resident_sample(const char* what, std::vector<uint8_t>& flags)
+{
+    if (!kept_complete())
+        throw Error(DRPRG_ENODATA, std::string(what) + ": not every read of the sample is resident in device memory (drprg_hip_keep_reads is off, or the "
+                                   "sample is larger than its limit; the executables take the limit from DRPRG_HIP_KEEP_READS_GB)");
+    sync();
+    HIPCHK(hipSetDevice(device_));
+    HIPCHK(hipStreamSynchronize(stream_));
+    flags.clear();
+    uint64_t bases = 0;
+    for (const DeviceBatch& b : resident_.kept) bases += b.n_bases;
+    return SubsampleResult { resident_.seen, bases, resident_.seen, bases };
+}
+
+Mapper::SubsampleResult Mapper::subsample_kept(uint64_t target_bases, uint64_t seed, std::vector<uint8_t>& flags)
+{
+    SubsampleResult res = resident_sample("random subsample", flags);
+    const uint64_t n = res.reads_before;
+    if (res.bases_before <= target_bases) return res;
+    if (n >= (1ull << 32)) throw Error(DRPRG_EOVERFLOW, "random subsample: 2^32 reads or more in one sample");
+    // ---- selection (device scratch of this call) ----
+    DeviceBuffer<uint64_t> d_len, d_key, d_key_sorted, d_csum, d_boff;
+    DeviceBuffer<uint32_t> d_idx, d_idx_sorted, d_rank;
+    DeviceBuffer<uint8_t> d_flag;
+    DeviceBuffer<unsigned long long> d_cut; // d_cut: [0..1] the cut, [2] the compaction's error word
+    DeviceBuffer<unsigned char> d_temp;
+    d_len.alloc(n); d_key.alloc(n + 1); d_key_sorted.alloc(n); d_csum.alloc(n); d_boff.alloc(n + 1);
+    d_idx.alloc(n + 1); d_idx_sorted.alloc(n); d_rank.alloc(n + 1); d_flag.alloc(n); d_cut.alloc(4);
+    d_temp.alloc(dev::subsample_scan_temp_bytes(n));
+    HIPCHK(hipMemsetAsync(d_len.data(), 0, d_len.bytes(), stream_));
+    HIPCHK(hipMemsetAsync(d_cut.data(), 0, d_cut.bytes(), stream_));
+    for (size_t b = 0; b < resident_.kept.size(); ++b)
+        HIPCHK(dev::launch_subsample_lengths(resident_.kept[b].d_offsets, resident_.kept[b].n_reads, resident_.first[b], n, d_len.data(), stream_));
+    dev::SubsampleSelect sel {};
+    sel.n = n; sel.target = target_bases; sel.seed = seed;
+    sel.len = d_len.data(); sel.key = d_key.data(); sel.key_sorted = d_key_sorted.data(); sel.csum = d_csum.data(); sel.boff = d_boff.data();
+    sel.idx = d_idx.data(); sel.idx_sorted = d_idx_sorted.data(); sel.rank = d_rank.data(); sel.flag = d_flag.data(); sel.cut = d_cut.data();
+    sel.temp = d_temp.data(); sel.temp_bytes = d_temp.size();
+    HIPCHK(dev::launch_subsample_select(sel, stream_));
+    uint32_t* const d_err = reinterpret_cast<uint32_t*>(d_cut.data() + 2);
+    keep_flagged(d_flag.data(), d_rank.data(), d_boff.data(), d_err, "random subsample", res, flags);
+    return res;
+}
+
+// What both selections of resident reads end in (subsample_kept, dedup_kept): flag[i] = 1 for the reads that stay, rank[i] / boff[i] = kept
+// reads / bases before read i (n + 1 entries, n = resident_.seen; device memory).  Every resident block is compacted into a block of its kept
+// reads in arenas of their own, the old set stays where it is if that fails, coverage and counters are cleared and the new set is mapped.  d_err:
+// a zeroed device word.  res.reads_kept / bases_kept and flags (the device flags, or empty after a failure) are filled here.
+void Mapper::keep_flagged(const uint8_t* d_flag, const uint32_t* d_rank, const uint64_t* d_boff, uint32_t* d_err, const char* what, SubsampleResult& res,
+    std::vector<uint8_t>& flags)
+{
+    const uint64_t n = resident_.seen;
+    DeviceBuffer<uint64_t> d_first;
+    DeviceBuffer<unsigned long long> d_bounds;
+    // kept reads and bases in front of every block's first read, behind its last one, and in all
+    std::vector<uint64_t> first;
+    for (size_t b = 0; b < resident_.kept.size(); ++b) {
+        first.push_back(resident_.first[b]);
+        first.push_back(resident_.first[b] + resident_.kept[b].n_reads);
+    }
+    first.push_back(n);
+    std::vector<unsigned long long> bounds(2 * first.size());
+    d_first.alloc(first.size());
+    d_bounds.alloc(bounds.size());
+    HIPCHK(hipMemcpyAsync(d_first.data(), first.data(), first.size() * sizeof(uint64_t), hipMemcpyHostToDevice, stream_));
+    HIPCHK(dev::launch_subsample_bounds(d_first.data(), (uint32_t)first.size(), n, d_rank, d_boff, d_bounds.data(), stream_));
+    HIPCHK(hipMemcpyAsync(bounds.data(), d_bounds.data(), bounds.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream_));
+    flags.resize(n);
+    HIPCHK(hipMemcpyAsync(flags.data(), d_flag, n, hipMemcpyDeviceToHost, stream_));
+    HIPCHK(hipStreamSynchronize(stream_));
+    res.reads_kept = bounds[bounds.size() - 2];
+    res.bases_kept = bounds[bounds.size() - 1];
+    // ---- compaction: a new set under the same cap, in arenas of its own.  It takes the old one's place only once the error word has read
+    // back clean: a failure before that leaves the sample as it was.  The old arenas are released by their owners when this scope is left ----
+    ResidentSet fresh;
+    fresh.cap = resident_.cap;
+    try {
+        const std::vector<DeviceBatch>& old = resident_.kept;
+        CompactScratch scratch;
+        for (size_t b = 0; b < old.size(); ++b) // (room for the largest block first: no block below waits for a regrow)
+            compact_room(scratch, old[b].packed, bounds[4 * b + 2] - bounds[4 * b], old[b].packed ? old[b].n_npos : 0);
+        for (size_t b = 0; b < old.size(); ++b) {
+            const DeviceBatch& ob = old[b];
+            const uint64_t nr = bounds[4 * b + 2] - bounds[4 * b], nb = bounds[4 * b + 3] - bounds[4 * b + 1];
+            if (nb == 0) continue; // (nothing of the block is kept, or empty reads only: they are numbered below, as map_host_async counts them)
+            const uint64_t payload = ob.packed ? (nb + 15) / 16 * 4 : nb;
+            const dev::SubsampleBlock sb { ob.d_bases, ob.d_offsets, ob.n_reads, ob.n_bases, resident_.first[b], d_flag, d_rank, d_boff, nr, nb };
+            fresh.count_empty(bounds[4 * b] - fresh.seen); // (kept reads in front of the block that lie in no block)
+            const DeviceBatch kb = compact_block(sb, ob, scratch, d_err, stream_, [&](uint64_t n_list) {
+                const std::optional<BlockRoom> room = fresh.take_block(payload, nr, n_list);
+                if (!room) throw Error(DRPRG_ENOMEM, std::string(what) + ": no device memory for the kept reads beside the resident sample");
+                return *room;
+            });
+            fresh.add(kb, nr);
+        }
+        fresh.count_empty(res.reads_kept - fresh.seen);
+        uint32_t err = 0;
+        HIPCHK(hipMemcpyAsync(&err, d_err, sizeof err, hipMemcpyDeviceToHost, stream_));
+        HIPCHK(hipStreamSynchronize(stream_)); // (nothing reads the old blocks any more)
+        if (err) throw Error(DRPRG_EIO, std::string(what) + ": the resident blocks' offsets and the selection do not fit each other");
+    } catch (...) {
+        (void)hipStreamSynchronize(stream_); // (nothing writes the new arenas any more when their owners release them)
+        flags.clear();
+        throw;
+    }
+    std::swap(resident_, fresh);
+    // ---- the kept reads mapped afresh ----
+    HIPCHK(hipMemsetAsync(d_covg_.data(), 0, d_covg_.bytes(), stream_)); // [coverage | reads per PRG]
+    HIPCHK(hipMemsetAsync(d_counters_.data(), 0, d_counters_.bytes(), stream_));
+    HIPCHK(hipStreamSynchronize(stream_));
+    tot_reads_ = tot_bases_ = tot_hits_ = tot_leftover_ = tot_minimizers_ = 0;
+    uint64_t in_blocks = 0;
+    for (const DeviceBatch& b : resident_.kept) {
+        map_resident_block(b);
+        in_blocks += b.n_reads;
+    }
+    sync();
+    HIPCHK(hipStreamSynchronize(stream_));
+    tot_reads_ += res.reads_kept - in_blocks; // (kept empty reads of blocks that hold no base any more)
+}
+
+void Mapper::compact_room(CompactScratch& cs, bool packed, uint64_t n_kept, uint64_t n_npos)
+{
+    if (packed) grow(cs.d_src, n_kept);
+    else grow(cs.d_table, n_kept);
+    if (!n_npos) return;
+    const uint64_t chunks = (uint64_t)dev::subsample_npos_chunks(n_npos) + 1;
+    grow(cs.d_count, chunks);
+    grow(cs.d_prefix, chunks);
+    grow(cs.d_ntemp, dev::scan_temp_bytes((uint32_t)chunks));
+}
+
+Mapper::DeviceBatch Mapper::compact_block(const dev::SubsampleBlock& sb, const DeviceBatch& src, CompactScratch& cs, uint32_t* d_err, hipStream_t stream,
+    const std::function<BlockRoom(uint64_t n_list)>& room)
+{
+    const uint64_t nr = sb.new_reads, nb = sb.new_bases;
+    const uint64_t n_npos = src.packed ? src.n_npos : 0; // (a text block lists none)
+    compact_room(cs, src.packed, nr, n_npos);
+    // how many of the block's listed positions lie in kept reads: counted before any room is taken for them (the scan of the counts stays
+    // in d_prefix for the emit below)
+    uint32_t n_list = 0;
+    if (n_npos) {
+        HIPCHK(dev::launch_subsample_npos_count(sb, src.d_npos, n_npos, cs.d_count.data(), cs.d_prefix.data(), cs.d_ntemp.data(), cs.d_ntemp.size(), stream));
+        HIPCHK(hipMemcpyAsync(&n_list, cs.d_prefix.data() + dev::subsample_npos_chunks(n_npos), sizeof n_list, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+    }
+    const BlockRoom dst = room(n_list);
+    HIPCHK(hipMemsetAsync(dst.bases + (src.packed ? (nb + 15) / 16 * 4 : nb), 0, 64, stream));
+    if (!src.packed) HIPCHK(hipMemsetAsync(cs.d_table.data(), 0, nr * sizeof(dev::GatherEntry), stream)); // (an entry the kernel refuses to fill copies nothing)
+    HIPCHK(dev::launch_subsample_tables(sb, dst.offsets, src.packed ? cs.d_src.data() : nullptr, src.packed ? nullptr : cs.d_table.data(), d_err, stream));
+    if (!src.packed) HIPCHK(dev::launch_gather_reads(cs.d_table.data(), (uint32_t)nr, dst.bases, stream));
+    else HIPCHK(dev::launch_subsample_pack(sb, dst.offsets, cs.d_src.data(), reinterpret_cast<uint32_t*>(dst.bases), d_err, stream));
+    if (n_list) HIPCHK(dev::launch_subsample_npos_emit(sb, src.d_npos, n_npos, cs.d_prefix.data(), dst.npos, n_list, stream));
+    return DeviceBatch { dst.bases, dst.offsets, nr, nb, src.packed, n_list ? dst.npos : nullptr, n_list };
+}
+
+// One resident block as the key kernel reads it: a packed block as it lies there (the bitmap of its listed positions beside it), an ASCII
+// block packed into scratch first.  The scratch lives as long as this object.
+struct Mapper::DedupBlock {
+    DeviceBuffer<uint32_t> words;
+    DeviceBuffer<uint64_t> npos;
+    DeviceBuffer<uint16_t> bits;
+    dev::DedupBatch batch {};
+};
+
+void Mapper::dedup_block(const DeviceBatch& kb, DedupBlock& out, unsigned long long* d_count)
+{
+    const uint64_t n_words = (kb.n_bases + 15) / 16;
+    const uint64_t* d_npos = kb.d_npos;
+    uint64_t n_npos = kb.n_npos;
+    const uint32_t* words = reinterpret_cast<const uint32_t*>(kb.d_bases);
+    if (!kb.packed) {
+        // launch_pack counts every position it meets and writes those below the capacity: one pass with room for a modest number of them,
+        // a second one only for a block that holds more
+        const uint64_t room = std::min<uint64_t>(kb.n_bases, 1u << 16);
+        out.words.alloc(n_words + 4);
+        out.npos.alloc(room);
+        unsigned long long cnt = 0;
+        HIPCHK(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), stream_));
+        HIPCHK(dev::launch_pack(kb.d_bases, kb.n_bases, out.words.data(), out.npos.data(), room, d_count, stream_));
+        HIPCHK(hipMemcpyAsync(&cnt, d_count, sizeof cnt, hipMemcpyDeviceToHost, stream_));
+        HIPCHK(hipStreamSynchronize(stream_));
+        if (cnt > room) {
+            out.npos.alloc(cnt);
+            HIPCHK(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), stream_));
+            HIPCHK(dev::launch_pack(kb.d_bases, kb.n_bases, out.words.data(), out.npos.data(), cnt, d_count, stream_));
+        }
+        words = out.words.data();
+        d_npos = out.npos.data();
+        n_npos = cnt;
+    }
+    if (n_npos) {
+        out.bits.alloc(n_words + 8);
+        HIPCHK(hipMemsetAsync(out.bits.data(), 0, out.bits.bytes(), stream_));
+        HIPCHK(dev::launch_mark_npos(d_npos, n_npos, kb.n_bases, out.bits.data(), stream_));
+    }
+    out.batch = dev::DedupBatch { words, n_npos ? out.bits.data() : nullptr, kb.d_offsets, kb.n_reads, kb.n_bases };
+}
+
+Mapper::SubsampleResult Mapper::dedup_kept(uint32_t key_bits, std::vector<uint8_t>& flags)
+{
+    if (key_bits < 1 || key_bits > 64) throw Error(DRPRG_EINVAL, "duplicate removal: key_bits must be 1..64");
+    SubsampleResult res = resident_sample("duplicate removal", flags);
+    const uint64_t n = res.reads_before;
+    uint64_t with_bases = 0; // (an upper bound: two reads with bases need two reads in blocks that hold bases)
+    for (const DeviceBatch& b : resident_.kept) with_bases += b.n_bases ? b.n_reads : 0;
+    if (n >= (1ull << 32)) throw Error(DRPRG_EOVERFLOW, "duplicate removal: 2^32 reads or more in one sample");
+    if (with_bases < 2) return res;
+    // ---- selection (device scratch of this call) ----
+    DeviceBuffer<uint64_t> d_key, d_key_sorted, d_boff;
+    DeviceBuffer<uint32_t> d_idx, d_idx_sorted, d_rank, d_err;
+    DeviceBuffer<uint8_t> d_flag;
+    DeviceBuffer<dev::DedupLoc> d_loc;
+    DeviceBuffer<unsigned long long> d_count;
+    DeviceBuffer<unsigned char> d_temp;
+    d_key.alloc(n + 1); d_key_sorted.alloc(n); d_boff.alloc(n + 1); d_idx.alloc(n + 1); d_idx_sorted.alloc(n); d_rank.alloc(n + 1);
+    d_flag.alloc(n); d_loc.alloc(n); d_err.alloc(4); d_count.alloc(1);
+    d_temp.alloc(dev::subsample_scan_temp_bytes(n));
+    HIPCHK(hipMemsetAsync(d_key.data(), 0, d_key.bytes(), stream_));
+    HIPCHK(hipMemsetAsync(d_loc.data(), 0, d_loc.bytes(), stream_));
+    HIPCHK(hipMemsetAsync(d_err.data(), 0, d_err.bytes(), stream_));
+    std::vector<DedupBlock> blocks(resident_.kept.size()); // (the exact check reads every block: the scratch of all of them lives until it is done)
+    for (size_t b = 0; b < resident_.kept.size(); ++b) {
+        if (!resident_.kept[b].n_reads || !resident_.kept[b].n_bases) continue;
+        if (resident_.first[b] + resident_.kept[b].n_reads > n) throw Error(DRPRG_EIO, "duplicate removal: the resident blocks hold more reads than the sample");
+        dedup_block(resident_.kept[b], blocks[b], d_count.data());
+        HIPCHK(dev::launch_dedup_keys(blocks[b].batch, reinterpret_cast<unsigned long long*>(d_key.data()) + resident_.first[b], d_err.data(), stream_));
+        HIPCHK(dev::launch_dedup_loc(blocks[b].batch, resident_.first[b], n, d_loc.data(), d_err.data(), stream_));
+    }
+    dev::DedupSelect sel {};
+    sel.n = n; sel.key_bits = key_bits; sel.loc = d_loc.data();
+    sel.key = d_key.data(); sel.key_sorted = d_key_sorted.data(); sel.boff = d_boff.data();
+    sel.idx = d_idx.data(); sel.idx_sorted = d_idx_sorted.data(); sel.rank = d_rank.data(); sel.flag = d_flag.data(); sel.err = d_err.data();
+    sel.temp = d_temp.data(); sel.temp_bytes = d_temp.size();
+    HIPCHK(dev::launch_dedup_select(sel, stream_));
+    uint32_t err = 0, kept = 0;
+    HIPCHK(hipMemcpyAsync(&err, d_err.data(), sizeof err, hipMemcpyDeviceToHost, stream_));
+    HIPCHK(hipMemcpyAsync(&kept, d_rank.data() + n, sizeof kept, hipMemcpyDeviceToHost, stream_));
+    HIPCHK(hipStreamSynchronize(stream_));
+    if (err) throw Error(DRPRG_EIO, "duplicate removal: a resident block's offsets do not fit its bases");
+    if (kept == n) return res; // no read dropped: nothing else happens
+    keep_flagged(d_flag.data(), d_rank.data(), d_boff.data(), d_err.data() + 1, "duplicate removal", res, flags);
+    return res;
+}
+
+void Mapper::dedup_keys_device(const uint32_t* d_words, const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases, const uint64_t* d_npos, uint64_t n_npos,
+    unsigned long long* d_keys, hipStream_t stream)
+{
+    if (n_reads == 0) return;
+    HIPCHK(hipSetDevice(device_));
+    if (!stream) stream = stream_;
+    if (!d_offsets || !d_keys || (n_bases && !d_words) || (n_npos && !d_npos)) throw Error(DRPRG_EINVAL, "null device pointer");
+    if (n_reads >= (1ull << 32)) throw Error(DRPRG_EOVERFLOW, "duplicate keys: 2^32 reads or more in one batch");
+    const uint64_t n_words = (n_bases + 15) / 16;
+    DeviceBuffer<uint16_t> d_bits;
+    DeviceBuffer<uint32_t> d_err;
+    d_err.alloc(1);
+    HIPCHK(hipMemsetAsync(d_err.data(), 0, d_err.bytes(), stream));
+    HIPCHK(hipMemsetAsync(d_keys, 0, n_reads * sizeof(unsigned long long), stream));
+    if (n_npos) {
+        d_bits.alloc(n_words + 8);
+        HIPCHK(hipMemsetAsync(d_bits.data(), 0, d_bits.bytes(), stream));
+        HIPCHK(dev::launch_mark_npos(d_npos, n_npos, n_bases, d_bits.data(), stream));
+    }
+    const dev::DedupBatch b { d_words, n_npos ? d_bits.data() : nullptr, d_offsets, n_reads, n_bases };
+    HIPCHK(dev::launch_dedup_keys(b, d_keys, d_err.data(), stream));
+    uint32_t err = 0;
+    HIPCHK(hipMemcpyAsync(&err, d_err.data(), sizeof err, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    if (err) throw Error(DRPRG_EINVAL, "duplicate keys: the offsets do not ascend from 0 to n_bases");
+}
+
+void Mapper::select_reads_with_anchors(std::vector<uint64_t> anchors, uint32_t A, std::vector<uint8_t>& bases, std::vector<uint64_t>& offsets,
+    std::vector<uint64_t>* ids, uint64_t window_bytes)
+{
+    if (!kept_complete()) throw Error(DRPRG_ENODATA, "not every read of the sample is resident");
+    if (A == 0 || A > 31) throw Error(DRPRG_EINVAL, "anchor length must be 1..31");
+    if (offsets.empty()) offsets.push_back(0);
+    std::sort(anchors.begin(), anchors.end());
+    anchors.erase(std::unique(anchors.begin(), anchors.end()), anchors.end());
+    if (anchors.empty() || resident_.kept.empty()) return;
+    sync();
+    HIPCHK(hipSetDevice(device_));
+    std::vector<uint32_t> pf(2048, 0);
+    for (uint64_t a : anchors) pf[(a & 0xFFFF) >> 5] |= 1u << (a & 31);
+    uint64_t total_reads = 0, max_reads = 0;
+    for (const DeviceBatch& b : resident_.kept) {
+        total_reads += b.n_reads;
+        max_reads = std::max(max_reads, b.n_reads);
+    }
+    // device scratch of this call
+    DeviceBuffer<uint64_t> d_anchors;
+    DeviceBuffer<uint32_t> d_pf, d_flags;
+    DeviceBuffer<unsigned long long> d_count;
+    DeviceBuffer<dev::SelectedRead> d_list;
+    DeviceBuffer<uint8_t> d_ascii;
+    d_anchors.alloc(anchors.size()); d_pf.alloc(pf.size()); d_flags.alloc(max_reads); d_count.alloc(1); d_list.alloc(total_reads);
+    HIPCHK(hipMemcpyAsync(d_anchors.data(), anchors.data(), anchors.size() * sizeof(uint64_t), hipMemcpyHostToDevice, stream_));
+    HIPCHK(hipMemcpyAsync(d_pf.data(), pf.data(), pf.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
+    HIPCHK(hipMemsetAsync(d_count.data(), 0, sizeof(unsigned long long), stream_));
+    // Batches kept in the packed form: the scan and the gather read an ASCII expansion.  It is made a WINDOW of batches at a time -- as
+    // many consecutive batches as expand into <= 1 GB (a larger batch alone) --, scanned, and its selected reads gathered before the next
+    // window's expansion takes the scratch: the scratch is the largest window, not the sample (up to 128 Gbases can stay
+    // resident packed; expanding all of them at once needed that much memory again, with no way back to the file pass).
+    auto expanded = [](const DeviceBatch& kb) -> uint64_t { return kb.packed ? (kb.n_bases + 15) / 16 * 16 + 64 : 0; };
+    const uint64_t WINDOW_BYTES = window_bytes ? window_bytes : SELECT_WINDOW_BYTES;
+    std::vector<std::pair<size_t, size_t>> windows; // [first batch, one past the last)
+    uint64_t scratch_need = 0;
+    for (size_t b = 0; b < resident_.kept.size();) {
+        size_t e = b;
+        uint64_t need = 0;
+        do need += expanded(resident_.kept[e++]);
+        while (e < resident_.kept.size() && need + expanded(resident_.kept[e]) <= WINDOW_BYTES);
+        windows.emplace_back(b, e);
+        scratch_need = std::max(scratch_need, need);
+        b = e;
+    }
+    if (scratch_need) d_ascii.alloc(scratch_need);
+    std::vector<const uint8_t*> ascii(resident_.kept.size(), nullptr);
+    unsigned long long done = 0; // entries of d_list the windows before this one left
+    for (const auto& win : windows) {
+        uint64_t at = 0;
+        for (size_t b = win.first; b < win.second; ++b) {
+            const DeviceBatch& kb = resident_.kept[b];
+            if (!kb.packed) {
+                ascii[b] = kb.d_bases;
+                continue;
+            }
+            HIPCHK(dev::launch_unpack(reinterpret_cast<const uint32_t*>(kb.d_bases), kb.n_bases, kb.d_npos, kb.n_npos, d_ascii.data() + at, stream_));
+            ascii[b] = d_ascii.data() + at;
+            at += expanded(kb);
+        }
+        for (size_t b = win.first; b < win.second; ++b) {
+            const DeviceBatch& kb = resident_.kept[b];
+            HIPCHK(hipMemsetAsync(d_flags.data(), 0, kb.n_reads * sizeof(uint32_t), stream_));
+            HIPCHK(dev::launch_anchor_scan(ascii[b], kb.d_offsets, (uint32_t)kb.n_reads, kb.n_bases, d_anchors.data(), (uint32_t)anchors.size(), A, d_pf.data(),
+                (uint32_t)b, d_flags.data(), d_count.data(), d_list.data(), total_reads, n_cus_, stream_));
+        }
+        unsigned long long count = 0;
+        HIPCHK(hipMemcpyAsync(&count, d_count.data(), sizeof count, hipMemcpyDeviceToHost, stream_));
+        HIPCHK(hipStreamSynchronize(stream_));
+        if (count > total_reads) throw Error(DRPRG_EIO, "read selection: more reads than the batches hold"); // (each read is appended once)
+        if (count == done) continue;
+        std::vector<dev::SelectedRead> list(count - done);
+        HIPCHK(hipMemcpy(list.data(), d_list.data() + done, (count - done) * sizeof(dev::SelectedRead), hipMemcpyDeviceToHost));
+        done = count;
+        std::sort(list.begin(), list.end(), [](const dev::SelectedRead& x, const dev::SelectedRead& y) { return x.batch != y.batch ? x.batch < y.batch : x.read < y.read; });
+        std::vector<dev::GatherEntry> table(list.size());
+        uint64_t out_bytes = 0;
+        for (size_t i = 0; i < list.size(); ++i) {
+            table[i].src = ascii[list[i].batch] + list[i].offset;
+            table[i].dst = out_bytes;
+            table[i].len = list[i].len;
+            table[i].pad = 0;
+            out_bytes += list[i].len;
+        }
+        // (device memory of this window only: freed before the next one)
+        DeviceBuffer<dev::GatherEntry> d_table;
+        DeviceBuffer<uint8_t> d_out;
+        d_table.alloc(list.size());
+        d_out.alloc(out_bytes);
+        const size_t base0 = bases.size();
+        bases.resize(base0 + out_bytes);
+        HIPCHK(hipMemcpyAsync(d_table.data(), table.data(), list.size() * sizeof(dev::GatherEntry), hipMemcpyHostToDevice, stream_));
+        HIPCHK(dev::launch_gather_reads(d_table.data(), (uint32_t)list.size(), d_out.data(), stream_));
+        if (out_bytes) HIPCHK(hipMemcpyAsync(bases.data() + base0, d_out.data(), out_bytes, hipMemcpyDeviceToHost, stream_));
+        HIPCHK(hipStreamSynchronize(stream_));
+        for (size_t i = 0; i < list.size(); ++i) offsets.push_back(offsets.back() + list[i].len);
+        if (ids)
+            for (size_t i = 0; i < list.size(); ++i) ids->push_back((uint64_t)list[i].batch << 32 | list[i].read);
+    }
+}
+
+} // namespace drprg

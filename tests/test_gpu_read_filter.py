@@ -355,6 +355,66 @@ def test_a_middle_block_that_loses_every_read(tmp_path, oracle):
     ctx.close()
 
 
+def test_later_blocks_outgrow_the_buffers_while_a_batch_is_in_flight(tmp_path):
+    """The filtered path without keep_reads, blocks that grow: one parser thread hands over a first block at a sixteenth of the ingest's
+    block size, then a full block, then what is left -- here three times the first.  The two staging sets take the blocks in turn, so the
+    second block allocates its set while the first block's deferred batch is in flight, and the third block, larger than the first by more
+    than the quarter a buffer is given on top, regrows every buffer of the first set -- staging, filter scratch, compaction tables, the
+    compacted block -- while the second block's batch is in flight.  (Blocks of a few hundred reads cannot come about: the ingest hands
+    nothing over below that sixteenth, 786 432 bases.)  Reads of 60 .. 150 bases, packed input, a base that is not ACGT in every tenth
+    read, kept or dropped; the lower bound of 90 drops a third of every block.  Vectors, counters and the filter's counts equal those of a
+    context that was given the kept reads alone and no filter; with the reads resident the same blocks give the same vectors again."""
+    from test_gpu_max_covg import _ingest_block_bases
+    panel, genomes = _panel()
+    block, _ = _ingest_block_bases()
+    first, min_len = block // 16, 90
+    rng = np.random.default_rng(47)
+    lengths = rng.integers(60, 151, size=(first + block + 3 * first) // 105)
+    offs = np.zeros(lengths.size + 1, dtype=np.int64)
+    offs[1:] = np.cumsum(lengths)
+    cut = np.searchsorted(offs, [first, first + block])  # the reads that complete the first and the second block
+    sizes = np.diff(np.concatenate(([0], offs[cut], offs[-1:])))
+    assert sizes[0] >= first and sizes[1] >= block and sizes[2] > sizes[0] * 5 // 4 + 4096, sizes
+    genome = np.concatenate(genomes.haps)
+    starts = rng.integers(0, genome.size - 150, size=lengths.size)  # (a read may run from one haplotype into the next: any text will do)
+    bases = genome[np.repeat(starts - offs[:-1], lengths) + np.arange(offs[-1])]
+    bases[offs[:-1:10] + 5] = ord("N")
+    keep = lengths >= min_len
+    for lo, hi in zip(np.concatenate(([0], cut)), np.concatenate((cut, [lengths.size]))):
+        with_n = keep[lo:hi][np.arange(lo, hi) % 10 == 0]
+        assert 0.25 < 1 - keep[lo:hi].mean() < 0.40 and with_n.any() and not with_n.all()  # a third of the block dropped; N in both kinds
+    files = {}
+    for name, sel in (("all", np.ones_like(keep)), ("kept", keep)):
+        files[name] = str(tmp_path / f"{name}.fq")
+        with open(files[name], "wb") as fh:
+            fh.write(b"".join(b"@r%d\n%s\n+\n%s\n" % (i, bases[offs[i]:offs[i + 1]].tobytes(), b"I" * int(lengths[i])) for i in np.flatnonzero(sel)))
+    n_kept, b_kept = int(keep.sum()), int(lengths[keep].sum())
+    counts = dict(reads_seen=int(lengths.size), bases_seen=int(offs[-1]), dropped_short=int(lengths.size) - n_kept, dropped_long=0, dropped_low_qual=0,
+                  reads_kept=n_kept, bases_kept=b_kept)
+    (tmp_path / "plain").mkdir()
+    plain = _ctx(tmp_path / "plain", panel, W, K, True, genome_size=G)
+    plain.set_threads(1)
+    plain.set_input_format(True)
+    plain.map_fastx(files["kept"])
+    want_cnt, want_cov = plain.counters(), plain.coverage()
+    assert want_cnt["reads"] == n_kept and want_cnt["bases"] == b_kept and want_cnt["clusters_kept"] > 5
+    ctx = _ctx(tmp_path, panel, W, K, True, genome_size=G)
+    ctx.set_threads(1)
+    ctx.set_input_format(True)
+    ctx.set_read_filter(min_len=min_len)
+    for keep_bytes in (0, 1 << 28):
+        ctx.reset()
+        ctx.keep_reads(keep_bytes)
+        ctx.map_fastx(files["all"])
+        assert ctx.counters() == want_cnt, keep_bytes
+        assert all(np.array_equal(x, y) for x, y in zip(ctx.coverage(), want_cov)), keep_bytes
+        assert _info_counts(ctx) == counts
+        if keep_bytes:  # the three blocks were there
+            assert ctx.resident_info()["complete"] and ctx.resident_info()["blocks"] == 3, ctx.resident_info()
+    ctx.close()
+    plain.close()
+
+
 # ---- 4. two devices ------------------------------------------------------------------------------------------------------------------------------
 def test_two_devices_give_the_vectors_of_one(tmp_path, oracle):
     from drprg_amd import Context
