@@ -1,0 +1,392 @@
+// capi_prep.cpp -- read preparation (filter, trimming, adapters: settings, counts, device entries) and the resident sample
+// (keep, map from another context, select, subsample, dedup).
+#include "capi_ctx.h"
+#include "read_qual_piece.h"
+#include "read_trim_piece.h"
+#include <algorithm>
+#include <cstring>
+
+using namespace drprg;
+
+extern "C" {
+
+int drprg_hip_set_read_filter(drprg_hip_ctx* ctx, uint64_t min_len, uint64_t max_len, uint32_t min_qual_milli)
+{
+    API_BEGIN(ctx)
+    if (max_len != 0 && max_len < min_len) throw Error(DRPRG_EINVAL, "read filter: the longest read allowed is shorter than the shortest");
+    if (min_qual_milli > dev::RQ_MAX_QUAL_MILLI) throw Error(DRPRG_EINVAL, "read filter: a mean quality above 93 cannot be asked for");
+    Mapper::ReadFilter f = ctx->read_filter; // (the trim settings ride along: drprg_hip_set_read_trim)
+    f.min_len = min_len; f.max_len = max_len; f.min_qual_milli = min_qual_milli;
+    f.T = min_qual_milli ? dev::rq_threshold(min_qual_milli) : 0;
+    ctx->read_filter = f;
+    API_END(ctx)
+}
+
+int drprg_hip_read_filter_info(drprg_hip_ctx* ctx, uint64_t out[8])
+{
+    API_BEGIN(ctx)
+    if (!out) throw Error(DRPRG_EINVAL, "null output");
+    std::lock_guard<std::mutex> g(ctx->filter_mu);
+    const Mapper::FilterOutcome& t = ctx->sample.filter_counts;
+    out[0] = t.reads_seen; out[1] = t.bases_seen; out[2] = t.dropped_short; out[3] = t.dropped_long; out[4] = t.dropped_lowq;
+    out[5] = t.reads_kept; out[6] = t.bases_kept; out[7] = ctx->read_filter.T;
+    API_END(ctx)
+}
+
+int drprg_hip_read_filter_device(drprg_hip_ctx* ctx, const void* d_qual, uint32_t qual_bias, const void* d_offsets, uint64_t n_reads, uint64_t n_bases,
+    void* d_sums, void* d_flags, uint64_t out[4], void* hip_stream)
+{
+    API_BEGIN(ctx)
+    Mapper& m = need_mapper(ctx);
+    if (!out) throw Error(DRPRG_EINVAL, "null output");
+    if (qual_bias != 0 && qual_bias != 33) throw Error(DRPRG_EINVAL, "read filter: the quality bias is 33 (FASTQ) or 0 (BAM)");
+    uint64_t res[8];
+    m.read_filter_device(ctx->read_filter, (const uint8_t*)d_qual, qual_bias, (const uint64_t*)d_offsets, n_reads, n_bases, (unsigned long long*)d_sums,
+        (uint8_t*)d_flags, res, (hipStream_t)hip_stream);
+    out[0] = res[dev::RF_KEPT_READS]; out[1] = res[dev::RF_KEPT_BASES]; out[2] = res[dev::RF_BAD_AT]; out[3] = 0;
+    if (res[dev::RF_OFFSETS]) throw Error(DRPRG_EINVAL, "read filter: the offsets do not ascend to n_bases");
+    if (res[dev::RF_BAD_AT]) throw Error(DRPRG_EFORMAT, "a base quality outside 0..93 at quality byte " + std::to_string(res[dev::RF_BAD_AT] - 1));
+    API_END(ctx)
+}
+
+// ---- read trimming (the rule: include/drprg_hip.h "read trimming") ---------------------------------------------------------------
+int drprg_hip_set_read_trim(drprg_hip_ctx* ctx, uint64_t front, uint64_t tail, uint32_t qual_milli, uint32_t window)
+{
+    API_BEGIN(ctx)
+    if (qual_milli > dev::RT_MAX_QUAL_MILLI) throw Error(DRPRG_EINVAL, "read trimming: a quality above 93 cannot be asked for");
+    if (window > dev::RT_MAX_WINDOW) throw Error(DRPRG_EINVAL, "read trimming: the window is 1..32 bases");
+    if (window != 0 && qual_milli == 0) throw Error(DRPRG_EINVAL, "read trimming: a window without a quality (--trim-window without --trim-qual)");
+    ctx->read_filter.trim_front = front; ctx->read_filter.trim_tail = tail; ctx->read_filter.trim_qual_milli = qual_milli;
+    ctx->read_filter.trim_window = qual_milli ? (window ? window : dev::RT_DEFAULT_WINDOW) : 0;
+    API_END(ctx)
+}
+
+int drprg_hip_read_trim_info(drprg_hip_ctx* ctx, uint64_t out[8])
+{
+    API_BEGIN(ctx)
+    if (!out) throw Error(DRPRG_EINVAL, "null output");
+    std::lock_guard<std::mutex> g(ctx->filter_mu);
+    const Mapper::TrimOutcome& t = ctx->sample.filter_counts.trim;
+    out[0] = t.reads_seen; out[1] = t.bases_seen; out[2] = t.reads_lost_base; out[3] = t.cut_front; out[4] = t.cut_tail;
+    out[5] = t.qcut_front; out[6] = t.qcut_tail; out[7] = t.emptied;
+    API_END(ctx)
+}
+
+int drprg_hip_read_trim_device(drprg_hip_ctx* ctx, const void* d_qual, uint32_t qual_bias, const void* d_offsets, const void* d_rev, uint64_t n_reads,
+    uint64_t n_bases, void* d_begin, void* d_end, uint64_t out[4], void* hip_stream)
+{
+    API_BEGIN(ctx)
+    Mapper& m = need_mapper(ctx);
+    if (!out) throw Error(DRPRG_EINVAL, "null output");
+    if (qual_bias != 0 && qual_bias != 33) throw Error(DRPRG_EINVAL, "read trimming: the quality bias is 33 (FASTQ) or 0 (BAM)");
+    uint64_t res[9];
+    m.read_trim_device(ctx->read_filter, (const uint8_t*)d_qual, qual_bias, (const uint64_t*)d_offsets, (const uint8_t*)d_rev, n_reads, n_bases,
+        (uint64_t*)d_begin, (uint64_t*)d_end, res, (hipStream_t)hip_stream);
+    const bool bad_offsets = res[dev::RT_BAD_AT] == ~0ull;
+    out[0] = res[dev::RT_KEPT_BASES]; out[1] = res[dev::RT_LOST_READS]; out[2] = bad_offsets ? 0 : res[dev::RT_BAD_AT]; out[3] = 0;
+    if (bad_offsets) throw Error(DRPRG_EINVAL, "read trimming: the offsets do not ascend to n_bases (or a read is longer than 2^31 bases)");
+    if (res[dev::RT_BAD_AT]) throw Error(DRPRG_EFORMAT, "a base quality outside 0..93 at quality byte " + std::to_string(res[dev::RT_BAD_AT] - 1));
+    API_END(ctx)
+}
+
+// ---- adapter trimming (the rule: include/drprg_hip.h "adapter trimming") ----------------------------------------------------------
+// one side's list into the kernels' form; shortest: lowered to the shortest adapter's length
+static dev::AdapterSet adapter_list(const char* const* seqs, uint32_t n, uint32_t& shortest)
+{
+    dev::AdapterSet ad {};
+    if (n == 0) return ad;
+    if (!seqs) throw Error(DRPRG_EINVAL, "adapter trimming: null adapter list");
+    if (n > dev::AD_MAX_ADAPTERS) throw Error(DRPRG_EINVAL, "adapter trimming: at most 4 adapters");
+    for (uint32_t a = 0; a < n; ++a) {
+        if (!seqs[a]) throw Error(DRPRG_EINVAL, "adapter trimming: null adapter");
+        const size_t m = std::strlen(seqs[a]);
+        if (m < 1 || m > dev::AD_MAX_LEN) throw Error(DRPRG_EINVAL, "adapter trimming: an adapter is 1..64 letters long");
+        for (size_t j = 0; j < m; ++j) {
+            const uint32_t l = dev::ad_letter((uint8_t)seqs[a][j]);
+            if (l > 3) throw Error(DRPRG_EINVAL, "adapter trimming: an adapter holds the letters ACGT (either case) and no other");
+            (j < 32 ? ad.lo[a] : ad.hi[a]) |= (uint64_t)l << (2 * (j & 31));
+        }
+        ad.len[a] = (uint32_t)m;
+        if (m > ad.max_len) ad.max_len = (uint32_t)m;
+        if (m < shortest) shortest = (uint32_t)m;
+    }
+    ad.n = n;
+    return ad;
+}
+
+static void clear_adapters(drprg_hip_ctx* ctx)
+{
+    Mapper::ReadFilter& f = ctx->read_filter;
+    f.adapters = dev::AdapterSet {};
+    f.front_adapters = dev::AdapterSet {};
+    f.eq3 = f.eq5 = dev::AdapterEq {};
+    f.adapter_indels = false;
+}
+
+// Behind both settings entries (the plain rule is the second form without a 5' list and without flags).  overlap_refusal: what a
+// minimum overlap above the shortest adapter is refused with, in the entry's own words.
+static int set_adapters(drprg_hip_ctx* ctx, const char* const* seqs3, uint32_t n3, const char* const* seqs5, uint32_t n5, uint32_t error_milli,
+    uint32_t min_overlap, uint32_t flags, const char* overlap_refusal)
+{
+    API_BEGIN(ctx)
+    if (flags & ~dev::AE_FLAG_INDELS) throw Error(DRPRG_EINVAL, "adapter trimming: unknown flag bits");
+    if (n3 == 0 && n5 == 0) { // cleared
+        clear_adapters(ctx);
+        return DRPRG_OK;
+    }
+    const bool indels = (flags & dev::AE_FLAG_INDELS) != 0;
+    if (n5 && !indels) throw Error(DRPRG_EINVAL, "adapter trimming: 5' adapters exist only under the indel rule (flag bit 0)");
+    if (error_milli > dev::AD_MAX_ERROR_MILLI) throw Error(DRPRG_EINVAL, "adapter trimming: the error rate is 0..0.5");
+    uint32_t shortest = dev::AD_MAX_LEN;
+    dev::AdapterSet ad3 = adapter_list(seqs3, n3, shortest), ad5 = adapter_list(seqs5, n5, shortest);
+    if (min_overlap > shortest) throw Error(DRPRG_EINVAL, overlap_refusal);
+    const uint32_t O = min_overlap ? min_overlap : std::min(dev::AD_DEFAULT_MIN_OVERLAP, shortest);
+    if (ad3.n) { ad3.error_milli = error_milli; ad3.min_overlap = O; }
+    if (ad5.n) { ad5.error_milli = error_milli; ad5.min_overlap = O; }
+    clear_adapters(ctx);
+    Mapper::ReadFilter& f = ctx->read_filter;
+    f.adapters = ad3;
+    if (indels) {
+        f.adapter_indels = true;
+        f.front_adapters = dev::ae_reversed(ad5);
+        f.eq3 = dev::ae_make_eq(f.adapters);
+        f.eq5 = dev::ae_make_eq(f.front_adapters);
+    }
+    API_END(ctx)
+}
+
+int drprg_hip_set_adapters(drprg_hip_ctx* ctx, const char* const* seqs, uint32_t n, uint32_t error_milli, uint32_t min_overlap)
+{
+    return set_adapters(ctx, seqs, n, nullptr, 0, error_milli, min_overlap, 0, "adapter trimming: the minimum overlap is 1..the length of the shortest adapter");
+}
+
+int drprg_hip_set_adapters2(drprg_hip_ctx* ctx, const char* const* seqs3, uint32_t n3, const char* const* seqs5, uint32_t n5, uint32_t error_milli,
+    uint32_t min_overlap, uint32_t flags)
+{
+    return set_adapters(ctx, seqs3, n3, seqs5, n5, error_milli, min_overlap, flags,
+        "adapter trimming: the minimum overlap is 1..the length of the shortest adapter of either side");
+}
+
+// behind drprg_hip_adapter_trim_info (the 3' side's counts) and drprg_hip_front_adapter_info (the 5' side's)
+static int adapter_info(drprg_hip_ctx* ctx, bool front, uint64_t out[5])
+{
+    API_BEGIN(ctx)
+    if (!out) throw Error(DRPRG_EINVAL, "null output");
+    std::lock_guard<std::mutex> g(ctx->filter_mu);
+    const Mapper::AdapterOutcome& t = front ? ctx->sample.filter_counts.front : ctx->sample.filter_counts.adapter;
+    out[0] = t.reads_seen; out[1] = t.bases_seen; out[2] = t.reads_cut; out[3] = t.bases_cut; out[4] = t.reads_emptied;
+    API_END(ctx)
+}
+
+int drprg_hip_adapter_trim_info(drprg_hip_ctx* ctx, uint64_t out[5]) { return adapter_info(ctx, false, out); }
+int drprg_hip_front_adapter_info(drprg_hip_ctx* ctx, uint64_t out[5]) { return adapter_info(ctx, true, out); }
+
+// Behind both adapter device entries.  n_out: the words of the result handed out (5: the 3' side's counts; 10: both sides').  plain_only: the
+// first form knows the mismatch rule's 3' adapters alone -- d_begin is left as it is, the 5' side's counts stay zero -- and refuses the rest.
+static int adapter_trim_device(drprg_hip_ctx* ctx, const void* d_text, const void* d_words, const void* d_npos, uint64_t n_npos, const void* d_offsets,
+    uint64_t n_reads, uint64_t n_bases, const void* d_begin, void* d_end, uint64_t* out, int n_out, bool plain_only, void* hip_stream)
+{
+    API_BEGIN(ctx)
+    Mapper& m = need_mapper(ctx);
+    if (!out) throw Error(DRPRG_EINVAL, "null output");
+    if (d_text && d_words) throw Error(DRPRG_EINVAL, "adapter trimming: the bases come as text or as packed words, not both");
+    if (plain_only && n_reads && !ctx->read_filter.adapters.n) throw Error(DRPRG_EINVAL, "adapter trimming: no adapter is set (drprg_hip_set_adapters)");
+    if (plain_only && n_reads && ctx->read_filter.adapter_indels)
+        throw Error(DRPRG_EINVAL, "adapter trimming: the indel rule is set (drprg_hip_set_adapters2); it runs through drprg_hip_adapter_trim_device2");
+    uint64_t res[11];
+    m.adapter_trim_device(ctx->read_filter, (const uint8_t*)d_text, (const uint32_t*)d_words, (const uint64_t*)d_npos, n_npos, (const uint64_t*)d_offsets, n_reads,
+        n_bases, (uint64_t*)d_begin, (uint64_t*)d_end, res, (hipStream_t)hip_stream);
+    for (int i = 0; i < n_out; ++i) out[i] = res[i];
+    if (res[10]) throw Error(DRPRG_EINVAL, "adapter trimming: the offsets do not ascend to n_bases, or a range does not lie inside its read");
+    API_END(ctx)
+}
+
+int drprg_hip_adapter_trim_device(drprg_hip_ctx* ctx, const void* d_text, const void* d_words, const void* d_npos, uint64_t n_npos, const void* d_offsets,
+    uint64_t n_reads, uint64_t n_bases, const void* d_begin, void* d_end, uint64_t out[5], void* hip_stream)
+{
+    return adapter_trim_device(ctx, d_text, d_words, d_npos, n_npos, d_offsets, n_reads, n_bases, d_begin, d_end, out, 5, true, hip_stream);
+}
+
+int drprg_hip_adapter_trim_device2(drprg_hip_ctx* ctx, const void* d_text, const void* d_words, const void* d_npos, uint64_t n_npos, const void* d_offsets,
+    uint64_t n_reads, uint64_t n_bases, void* d_begin, void* d_end, uint64_t out[10], void* hip_stream)
+{
+    return adapter_trim_device(ctx, d_text, d_words, d_npos, n_npos, d_offsets, n_reads, n_bases, d_begin, d_end, out, 10, false, hip_stream);
+}
+
+// ---- the resident sample -----------------------------------------------------------------------------------------------------
+} // extern "C"
+
+bool drprg::reads_resident(drprg_hip_ctx* ctx, const char* path)
+{
+    const std::vector<Mapper*> all = mappers_of(ctx);
+    if (all.empty()) return false;
+    for (Mapper* m : all)
+        if (!m->kept_complete()) return false;
+    const std::vector<std::string>& mapped = ctx->sample.mapped_paths;
+    return !path || (mapped.size() == 1 && mapped[0] == path);
+}
+
+extern "C" {
+
+int drprg_hip_keep_reads(drprg_hip_ctx* ctx, uint64_t max_bytes)
+{
+    API_BEGIN(ctx)
+    need_mapper(ctx);
+    for (Mapper* m : mappers_of(ctx)) m->keep_reads(max_bytes);
+    // (reads mapped before this call are not resident: only a context that has mapped nothing yet can stand for a file)
+    if (ctx->sample.total_bases != 0) ctx->sample.mapped_paths.assign(2, std::string());
+    API_END(ctx)
+}
+
+int drprg_hip_map_resident(drprg_hip_ctx* ctx, drprg_hip_ctx* from)
+{
+    API_BEGIN(ctx)
+    if (!from || from == ctx) throw Error(DRPRG_EINVAL, "drprg_hip_map_resident needs another open context");
+    need_mapper(ctx);
+    const std::vector<Mapper*> dst = mappers_of(ctx), src = mappers_of(from);
+    if (!reads_resident(from, nullptr)) throw Error(DRPRG_ENODATA, "the other context does not hold all of its reads in device memory");
+    if (dst.size() != src.size()) throw Error(DRPRG_EINVAL, "the two contexts span different numbers of devices");
+    for (size_t i = 0; i < dst.size(); ++i)
+        if (dst[i]->device() != src[i]->device()) throw Error(DRPRG_EINVAL, "the two contexts list different devices");
+    ctx->sample.host_coverage_valid = false;
+    for (size_t i = 0; i < dst.size(); ++i) ctx->sample.accepted_reads += dst[i]->map_kept_from(*src[i]); // (what `from` accepted under ITS cap: exactly those reads)
+    ctx->sample.total_bases += from->sample.total_bases;
+    ctx->sample.mapped_paths.insert(ctx->sample.mapped_paths.end(), from->sample.mapped_paths.begin(), from->sample.mapped_paths.end());
+    reduce_devices(ctx);
+    API_END(ctx)
+}
+
+int drprg_hip_resident_info(drprg_hip_ctx* ctx, uint64_t out[4])
+{
+    API_BEGIN(ctx)
+    if (!out) throw Error(DRPRG_EINVAL, "null output");
+    out[0] = reads_resident(ctx, nullptr) ? 1 : 0;
+    out[1] = out[2] = 0;
+    for (Mapper* m : mappers_of(ctx)) {
+        out[1] += m->kept_bytes();
+        out[2] += m->kept().size();
+    }
+    out[3] = ctx->last_discover_resident ? 1 : 0;
+    API_END(ctx)
+}
+
+// ---- subsample and dedup: two selections among the resident reads, recorded alike ---------------------------------------------
+// (each of the two shared refusals stands between refusals of the entry's own, in the order they have always been made)
+static void refuse_several_devices(const drprg_hip_ctx* ctx, const std::string& entry)
+{
+    if (!ctx->extra.empty()) throw Error(DRPRG_EINVAL, entry + ": a context over several devices is not served");
+}
+
+static void refuse_unordered(const drprg_hip_ctx* ctx, const Mapper& m, const std::string& entry)
+{
+    if (ctx->sample.fastx_unordered && m.kept_complete()) // (a sample that is not resident is refused for that, by the mapper)
+        throw Error(DRPRG_EINVAL, entry + ": drprg_hip_map_fastx handed this sample's blocks over in no particular order, so its reads have no "
+                                          "file-order numbers (drprg_hip_set_ordered_ingest(ctx, 1) before the file is mapped)");
+}
+
+// what a selection did: into the entry's four outputs, its record, and the context
+static void record_selection(drprg_hip_ctx* ctx, Selection& sel, const Mapper::SubsampleResult& r, std::vector<uint8_t>& flags, uint64_t out[4])
+{
+    out[0] = r.reads_before; out[1] = r.bases_before; out[2] = r.reads_kept; out[3] = r.bases_kept;
+    sel.done = true;
+    sel.reads_before = r.reads_before;
+    sel.flags = std::move(flags);
+    if (r.reads_kept != r.reads_before) { // the context now stands for the kept reads alone
+        ctx->sample.host_coverage_valid = false;
+        ctx->sample.total_bases = r.bases_kept;
+        ctx->sample.accepted_reads = r.reads_kept;
+    }
+}
+
+// the keep flags of the last `entry` call, one byte per read of the sample before it
+static void copy_selection_flags(const Selection& sel, const std::string& entry, uint8_t* flags, uint64_t n)
+{
+    if (!sel.done) throw Error(DRPRG_EINVAL, entry + "_flags: no " + entry + " call since the last reset");
+    if (n != sel.reads_before) throw Error(DRPRG_EINVAL, entry + "_flags: the sample held " + std::to_string(sel.reads_before) + " reads, not " + std::to_string(n));
+    if (n && !flags) throw Error(DRPRG_EINVAL, "null output");
+    if (n == 0) return; // (`flags` may be null)
+    if (sel.flags.empty()) std::memset(flags, 1, n);
+    else std::memcpy(flags, sel.flags.data(), n);
+}
+
+int drprg_hip_subsample(drprg_hip_ctx* ctx, uint64_t target_bases, uint64_t seed, uint64_t out[4])
+{
+    API_BEGIN(ctx)
+    if (!out) throw Error(DRPRG_EINVAL, "null output");
+    Mapper& m = need_mapper(ctx);
+    refuse_several_devices(ctx, "drprg_hip_subsample");
+    if (ctx->max_covg < 0xFFFFFFFFull)
+        throw Error(DRPRG_EINVAL, "drprg_hip_subsample: a depth cap is set (drprg_hip_set_max_covg); the prefix cap and the random subsample are alternatives");
+    refuse_unordered(ctx, m, "drprg_hip_subsample");
+    std::vector<uint8_t> flags;
+    const Mapper::SubsampleResult r = m.subsample_kept(target_bases, seed, flags);
+    record_selection(ctx, ctx->sample.subsample, r, flags, out);
+    API_END(ctx)
+}
+
+int drprg_hip_subsample_flags(drprg_hip_ctx* ctx, uint8_t* flags, uint64_t n)
+{
+    API_BEGIN(ctx)
+    copy_selection_flags(ctx->sample.subsample, "drprg_hip_subsample", flags, n);
+    API_END(ctx)
+}
+
+int drprg_hip_dedup(drprg_hip_ctx* ctx, uint32_t key_bits, uint64_t out[4])
+{
+    API_BEGIN(ctx)
+    if (!out) throw Error(DRPRG_EINVAL, "null output");
+    Mapper& m = need_mapper(ctx);
+    if (key_bits < 1 || key_bits > 64) throw Error(DRPRG_EINVAL, "drprg_hip_dedup: key_bits must be 1..64");
+    refuse_several_devices(ctx, "drprg_hip_dedup");
+    refuse_unordered(ctx, m, "drprg_hip_dedup");
+    std::vector<uint8_t> flags;
+    const Mapper::SubsampleResult r = m.dedup_kept(key_bits, flags);
+    record_selection(ctx, ctx->sample.dedup, r, flags, out);
+    API_END(ctx)
+}
+
+int drprg_hip_dedup_flags(drprg_hip_ctx* ctx, uint8_t* flags, uint64_t n)
+{
+    API_BEGIN(ctx)
+    copy_selection_flags(ctx->sample.dedup, "drprg_hip_dedup", flags, n);
+    API_END(ctx)
+}
+
+int drprg_hip_dedup_keys_device(drprg_hip_ctx* ctx, const void* d_words, const void* d_offsets, uint64_t n_reads, uint64_t n_bases, const void* d_npos, uint64_t n_npos,
+    void* d_keys, void* hip_stream)
+{
+    API_BEGIN(ctx)
+    Mapper& m = need_mapper(ctx);
+    m.dedup_keys_device((const uint32_t*)d_words, (const uint64_t*)d_offsets, n_reads, n_bases, (const uint64_t*)d_npos, n_npos, (unsigned long long*)d_keys,
+        (hipStream_t)hip_stream);
+    API_END(ctx)
+}
+
+int drprg_hip_select_reads(drprg_hip_ctx* ctx, const uint64_t* anchors, uint64_t n_anchors, uint32_t A, uint64_t window_bytes, uint8_t* bases,
+    uint64_t bases_cap, uint64_t* offsets, uint64_t* ids, uint64_t reads_cap, uint64_t out[2])
+{
+    API_BEGIN(ctx)
+    if (!out || (n_anchors && !anchors)) throw Error(DRPRG_EINVAL, "null argument");
+    if (A == 0 || A > 31) throw Error(DRPRG_EINVAL, "anchor length must be 1..31");
+    if (!reads_resident(ctx, nullptr)) throw Error(DRPRG_ENODATA, "not every read of the sample is resident");
+    const std::vector<uint64_t> kmers(anchors, anchors + n_anchors);
+    std::vector<uint8_t> sel_bases;
+    std::vector<uint64_t> sel_offsets(1, 0), sel_ids;
+    uint64_t first_block = 0; // (ids count the kept blocks through all the mappers, like drprg_hip_resident_info)
+    for (Mapper* m : mappers_of(ctx)) {
+        const size_t had = sel_ids.size();
+        m->select_reads_with_anchors(kmers, A, sel_bases, sel_offsets, &sel_ids, window_bytes);
+        for (size_t i = had; i < sel_ids.size(); ++i) sel_ids[i] += first_block << 32;
+        first_block += m->kept().size();
+    }
+    out[0] = sel_ids.size();
+    out[1] = sel_bases.size();
+    if (sel_ids.size() > reads_cap || sel_bases.size() > bases_cap) throw Error(DRPRG_EOVERFLOW, "the selected reads do not fit the caller's buffers");
+    if ((!sel_bases.empty() && !bases) || !offsets || (!sel_ids.empty() && !ids)) throw Error(DRPRG_EINVAL, "null output buffer");
+    if (!sel_bases.empty()) std::memcpy(bases, sel_bases.data(), sel_bases.size());
+    std::memcpy(offsets, sel_offsets.data(), sel_offsets.size() * sizeof(uint64_t));
+    if (!sel_ids.empty()) std::memcpy(ids, sel_ids.data(), sel_ids.size() * sizeof(uint64_t));
+    API_END(ctx)
+}
+
+} // extern "C"

@@ -208,7 +208,7 @@ hipError_t launch_cluster_pipeline(const ClusterArgs& a, uint32_t n_hits, uint32
     return hipGetLastError();
 }
 
-// dst[i] += src[i]: the device-side sum of two coverage vectors (several devices in one process: capi.cpp drprg_hip_reduce)
+// dst[i] += src[i]: the device-side sum of two coverage vectors (several devices in one process: capi_reduce.cpp drprg_hip_reduce)
 __global__ __launch_bounds__(256) void vector_add_u32_kernel(uint32_t* __restrict__ dst, const uint32_t* __restrict__ src, uint64_t n)
 {
     for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) dst[i] += src[i];

@@ -126,7 +126,7 @@ Mapper::Mapper(const FlatIndex& idx, const MapParams& p, int device) : device_(d
     if (sw_.min_capacity) // (tests: small batches at the production ratio, or below it to force regrows)
         min_capacity_ = std::max<uint64_t>(MIN_CAPACITY_CLAMP, std::min<uint64_t>(*sw_.min_capacity, 1ull << 30));
     // ONE allocation [coverage | reads per PRG]: the sample's whole additive state is one contiguous u32 vector, so the
-    // collective of the path is a single ncclAllReduce / ncclReduce over it (capi.cpp)
+    // collective of the path is a single ncclAllReduce / ncclReduce over it (capi_reduce.cpp)
     d_covg_.alloc(2 * (size_t)n_knodes_ + (size_t)n_prgs_);
     d_counters_.alloc(C_N);
     h_counters_.alloc(C_N);

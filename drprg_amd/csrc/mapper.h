@@ -17,7 +17,21 @@ struct MapCounters {
     uint64_t reads = 0, bases = 0, minimizers = 0, hits = 0, clusters_kept = 0, hits_kept = 0;
     uint64_t kernel = 0; // sketch kernel in use: 1 direct (sketch_probe_kernel), 2 Bloom-prefiltered (sketch_filter_kernel)
     uint64_t leftover_reads = 0; // filtered sequence: reads that read_cluster_kernel left to the generic pipeline
+    // another device's counts added in (`kernel` names a kernel form and is no count: it stays this device's)
+    MapCounters& operator+=(const MapCounters& o)
+    {
+        reads += o.reads; bases += o.bases; minimizers += o.minimizers; hits += o.hits;
+        clusters_kept += o.clusters_kept; hits_kept += o.hits_kept; leftover_reads += o.leftover_reads;
+        return *this;
+    }
 };
+
+// the eight words of drprg_hip_counters and of the coverage cache, in their order
+inline void to_words(const MapCounters& c, uint64_t out[8])
+{
+    const uint64_t v[8] = { c.reads, c.bases, c.minimizers, c.hits, c.clusters_kept, c.hits_kept, c.kernel, c.leftover_reads };
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
+}
 
 class Mapper {
 public:
@@ -60,7 +74,7 @@ public:
     // what map refuses a batch for, checked without touching anything: the only place that throws these errors
     static void check(const DeviceBatch& b);
 
-    // Depth cap (drprg_hip_set_max_covg; the running total is kept by the context, capi.cpp): where a device batch reaches `target` bases.
+    // Depth cap (drprg_hip_set_max_covg; the running total is kept by the context, capi_map.cpp): where a device batch reaches `target` bases.
     // n_reads = the smallest i in [1, n_reads] with d_offsets[i] >= target (n_reads if there is none), n_bases = d_offsets[i], n_npos = how
     // many of the batch's listed positions lie below that.  Completes the batch a deferred map left in flight, runs covg_cut_kernel on
     // `stream` and waits for it: called for the one batch that crosses the cap, never for a batch that cannot reach it.  Refuses what

@@ -191,6 +191,78 @@ def test_map_opts_of_another_size_are_refused(tmp_path):
     assert b"mismatch" in lib.drprg_hip_last_error(ctx._h)
 
 
+def _host_only_context(tmp_path):
+    from drprg_amd import Context, synth
+    panel = synth.small_panel(seed=1, n_loci=2, length=200)
+    prg = str(tmp_path / "dr.prg")
+    panel.write(prg)
+    return Context(prg, 11, 15, device=-1, from_files=False)
+
+
+def test_reset_clears_the_sample_and_keeps_the_settings(tmp_path):
+    """drprg_hip_reset puts everything the context knows of its sample back to nothing -- the coverage, the depth cap's running state, the
+    BAM counts, what the read filter and the trimming counted -- and keeps what was set: the depth cap (seen by crossing it again), the read
+    filter (its threshold T is word 7 of drprg_hip_read_filter_info), and the trim settings and adapters that ride in the same settings."""
+    ctx = _host_only_context(tmp_path)
+    ctx.set_read_filter(min_len=50, min_qual=12.5)
+    ctx.set_read_trim(front=3, tail=2, qual=20, window=8)
+    ctx.set_adapters(["AGATCGGAAGAGC"])
+    ctx.set_max_covg(1)  # T = 2 * 5,000,000 bases (the default genome size)
+    threshold = ctx.read_filter_info()["T"]
+    assert threshold != 0
+    covg = np.arange(2 * ctx.n_knodes, dtype=np.uint32) + 1
+    prg_reads = np.full(ctx.n_prgs, 7, dtype=np.uint32)
+    ctx.set_coverage(covg, prg_reads, 20_000_000)
+    assert ctx.max_covg_info() == dict(reached=True, reads=0, bases=20_000_000, dropped=0)
+    assert np.array_equal(ctx.coverage()[0], covg)
+    ctx.reset()
+    assert ctx.max_covg_info() == dict(reached=False, reads=0, bases=0, dropped=0)
+    assert not any(ctx.bam_info().values())
+    assert ctx.read_filter_info() == dict(reads_seen=0, bases_seen=0, dropped_short=0, dropped_long=0, dropped_low_qual=0, reads_kept=0,
+                                          bases_kept=0, T=threshold)
+    assert not any(ctx.read_trim_info().values()) and not any(ctx.adapter_trim_info().values())
+    got_covg, got_reads = ctx.coverage()
+    assert got_covg.shape == covg.shape and got_reads.shape == prg_reads.shape and not got_covg.any() and not got_reads.any()
+    # the cap is still 1: a total above it is over the cap at once, one below it is not
+    ctx.set_coverage(covg, prg_reads, 9_999_999)
+    assert ctx.max_covg_info() == dict(reached=False, reads=0, bases=9_999_999, dropped=0)
+    ctx.set_coverage(covg, prg_reads, 10_000_000)
+    assert ctx.max_covg_info() == dict(reached=True, reads=0, bases=10_000_000, dropped=0)
+    ctx.set_max_covg(2)
+    ctx.reset()
+    ctx.set_coverage(covg, prg_reads, 10_000_000)
+    assert ctx.max_covg_info()["reached"] is False
+
+
+def _flags_refused(ctx, what, ptr, n):
+    from drprg_amd._lib import lib
+    rc = getattr(lib, f"drprg_hip_{what}_flags")(ctx._h, ptr, n)
+    return rc == -22 and lib.drprg_hip_last_error(ctx._h) == f"drprg_hip_{what}_flags: no drprg_hip_{what} call since the last reset".encode()
+
+
+def test_selection_flags_are_refused_before_any_selection(tmp_path):
+    """drprg_hip_subsample_flags / drprg_hip_dedup_flags with no drprg_hip_subsample / drprg_hip_dedup call before them: refused, each in
+    its own words, and the caller's buffer is left alone."""
+    ctx = _host_only_context(tmp_path)
+    buf = np.zeros(4, dtype=np.uint8)
+    for what in ("subsample", "dedup"):
+        assert _flags_refused(ctx, what, buf.ctypes.data, 4)
+    assert not buf.any()
+
+
+def test_selection_flags_of_no_reads_are_refused_like_any_other(tmp_path):
+    """n == 0 does not get past the refusal, with a buffer or without one: asking for nothing returns DRPRG_OK only once there was a
+    selection to ask about.  Held on a context that was reset after it had refused already."""
+    ctx = _host_only_context(tmp_path)
+    buf = np.zeros(1, dtype=np.uint8)
+    for what in ("subsample", "dedup"):
+        assert _flags_refused(ctx, what, None, 0)
+    ctx.reset()
+    for what in ("subsample", "dedup"):
+        assert _flags_refused(ctx, what, None, 0) and _flags_refused(ctx, what, buf.ctypes.data, 0)
+    assert not buf.any()
+
+
 def _parse_vcf(path):
     recs = []
     for line in open(path):
