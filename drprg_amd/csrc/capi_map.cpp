@@ -335,6 +335,9 @@ int drprg_hip_set_threads(drprg_hip_ctx* ctx, int threads)
 // These entry points carry no qualities: while a filter is set they refuse, rather than map unfiltered reads without saying so.
 static void refuse_unfiltered(const drprg_hip_ctx* ctx, const char* entry)
 {
+    if (ctx->read_filter.decoy())
+        throw Error(DRPRG_EINVAL, std::string(entry) + ": a decoy set is loaded (drprg_hip_set_decoy) and the screen runs in drprg_hip_map_fastx; this entry "
+                                                      "would map the reads unscreened (clear it with drprg_hip_set_decoy(ctx, NULL, 0, 0, 0, 0))");
     if (ctx->read_filter.any_adapters())
         throw Error(DRPRG_EINVAL, std::string(entry) + ": adapters are set (drprg_hip_set_adapters) and adapter trimming runs in drprg_hip_map_fastx; this entry "
                                                       "would map the reads with their adapters (clear them with drprg_hip_set_adapters(ctx, NULL, 0, 0, 0))");

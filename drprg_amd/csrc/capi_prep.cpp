@@ -1,9 +1,11 @@
-// capi_prep.cpp -- read preparation (filter, trimming, adapters: settings, counts, device entries) and the resident sample
+// capi_prep.cpp -- read preparation (filter, trimming, adapters, decoy screen: settings, counts, device entries) and the resident sample
 // (keep, map from another context, select, subsample, dedup).
 #include "capi_ctx.h"
+#include "fastx.h"
 #include "read_qual_piece.h"
 #include "read_trim_piece.h"
 #include <algorithm>
+#include <atomic>
 #include <cstring>
 
 using namespace drprg;
@@ -211,6 +213,107 @@ int drprg_hip_adapter_trim_device2(drprg_hip_ctx* ctx, const void* d_text, const
     uint64_t n_reads, uint64_t n_bases, void* d_begin, void* d_end, uint64_t out[10], void* hip_stream)
 {
     return adapter_trim_device(ctx, d_text, d_words, d_npos, n_npos, d_offsets, n_reads, n_bases, d_begin, d_end, out, 10, false, hip_stream);
+}
+
+// ---- the decoy screen (the rule: include/drprg_hip.h "decoy screen") ----------------------------------------------------------------
+static void clear_decoy(drprg_hip_ctx* ctx)
+{
+    Mapper::ReadFilter& f = ctx->read_filter;
+    f.decoy_k = f.decoy_frac_milli = f.decoy_min_kmers = 0;
+    f.decoy_id = 0;
+    for (Mapper* m : mappers_of(ctx)) m->clear_decoy();
+}
+
+// every record of the files, one 'N' between two records (no window spans it); windows: those of the records, whatever letters they hold
+static std::vector<uint8_t> decoy_text(const char* const* paths, uint32_t n, uint32_t k, uint64_t& windows)
+{
+    std::vector<uint8_t> text;
+    windows = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        FastxReader rd(paths[i]);
+        ReadBatch batch;
+        while (rd.next_batch(batch, 1u << 20, 1ull << 28)) {
+            for (uint64_t r = 0; r < batch.n_reads(); ++r) {
+                const uint64_t len = batch.offsets[r + 1] - batch.offsets[r];
+                if (len < k) continue; // (adds nothing)
+                windows += len - k + 1;
+                if (windows > dev::DC_MAX_WINDOWS) throw Error(DRPRG_EOVERFLOW, "decoy screen: the decoy files hold more than 2^31 - 1 windows");
+                if (!text.empty()) text.push_back('N');
+                text.insert(text.end(), batch.bases.begin() + (long)batch.offsets[r], batch.bases.begin() + (long)batch.offsets[r + 1]);
+            }
+        }
+    }
+    return text;
+}
+
+int drprg_hip_set_decoy(drprg_hip_ctx* ctx, const char* const* fasta_paths, uint32_t n, uint32_t k, uint32_t min_frac_milli, uint32_t min_kmers)
+{
+    API_BEGIN(ctx)
+    static std::atomic<uint64_t> sets { 0 };
+    clear_decoy(ctx); // (whatever happens below, the set that was is gone)
+    if (n == 0) return DRPRG_OK;
+    need_mapper(ctx);
+    if (n > dev::DC_MAX_FILES) throw Error(DRPRG_EINVAL, "decoy screen: at most 8 decoy files");
+    if (!fasta_paths) throw Error(DRPRG_EINVAL, "decoy screen: null list of decoy files");
+    for (uint32_t i = 0; i < n; ++i)
+        if (!fasta_paths[i]) throw Error(DRPRG_EINVAL, "decoy screen: null decoy file name");
+    if (k == 0) k = dev::DC_DEFAULT_K;
+    if (k < dev::DC_MIN_K || k > dev::DC_MAX_K) throw Error(DRPRG_EINVAL, "decoy screen: the k-mer length is 9..31");
+    if (min_frac_milli > 1000) throw Error(DRPRG_EINVAL, "decoy screen: the fraction is at most 1");
+    uint64_t windows = 0;
+    const std::vector<uint8_t> text = decoy_text(fasta_paths, n, k, windows);
+    const uint64_t set = ++sets;
+    try {
+        for (Mapper* m : mappers_of(ctx)) m->set_decoy(text, windows, k, set);
+    } catch (...) {
+        clear_decoy(ctx);
+        throw;
+    }
+    Mapper::ReadFilter& f = ctx->read_filter;
+    f.decoy_k = k;
+    f.decoy_frac_milli = min_frac_milli ? min_frac_milli : dev::DC_DEFAULT_FRAC_MILLI;
+    f.decoy_min_kmers = min_kmers ? min_kmers : dev::DC_DEFAULT_MIN_KMERS;
+    f.decoy_id = set;
+    API_END(ctx)
+}
+
+int drprg_hip_decoy_info(drprg_hip_ctx* ctx, uint64_t out[8])
+{
+    API_BEGIN(ctx)
+    if (!out) throw Error(DRPRG_EINVAL, "null output");
+    out[0] = ctx->mapper ? ctx->mapper->decoy_distinct() : 0;
+    out[1] = ctx->mapper ? ctx->mapper->decoy_slots() : 0;
+    std::lock_guard<std::mutex> g(ctx->filter_mu);
+    const Mapper::DecoyOutcome& t = ctx->sample.filter_counts.decoy;
+    out[2] = t.reads_judged; out[3] = t.bases_judged; out[4] = t.reads_dropped; out[5] = t.bases_dropped; out[6] = t.valid; out[7] = t.hits;
+    API_END(ctx)
+}
+
+int drprg_hip_decoy_lookup(drprg_hip_ctx* ctx, const uint64_t* kmers, uint64_t n, uint8_t* found)
+{
+    API_BEGIN(ctx)
+    Mapper& m = need_mapper(ctx);
+    if (!ctx->read_filter.decoy()) throw Error(DRPRG_EINVAL, "decoy screen: no decoy set is loaded (drprg_hip_set_decoy)");
+    if (n && (!kmers || !found)) throw Error(DRPRG_EINVAL, "null argument");
+    std::vector<uint64_t> canon(n);
+    for (uint64_t i = 0; i < n; ++i) canon[i] = dev::dc_canonical(kmers[i], ctx->read_filter.decoy_k);
+    m.decoy_lookup(canon, found);
+    API_END(ctx)
+}
+
+int drprg_hip_decoy_screen_device(drprg_hip_ctx* ctx, const void* d_text, const void* d_words, const void* d_npos, uint64_t n_npos, const void* d_offsets,
+    uint64_t n_reads, uint64_t n_bases, void* d_valid, void* d_hits, void* d_flags, uint64_t out[4], void* hip_stream)
+{
+    API_BEGIN(ctx)
+    Mapper& m = need_mapper(ctx);
+    if (!out) throw Error(DRPRG_EINVAL, "null output");
+    if (d_text && d_words) throw Error(DRPRG_EINVAL, "decoy screen: the bases come as text or as packed words, not both");
+    uint64_t res[5];
+    m.decoy_screen_device(ctx->read_filter, (const uint8_t*)d_text, (const uint32_t*)d_words, (const uint64_t*)d_npos, n_npos, (const uint64_t*)d_offsets, n_reads,
+        n_bases, (uint32_t*)d_valid, (uint32_t*)d_hits, (uint8_t*)d_flags, res, (hipStream_t)hip_stream);
+    for (int i = 0; i < 4; ++i) out[i] = res[i];
+    if (res[4]) throw Error(DRPRG_EINVAL, "decoy screen: the offsets do not ascend from 0 to n_bases");
+    API_END(ctx)
 }
 
 // ---- the resident sample -----------------------------------------------------------------------------------------------------

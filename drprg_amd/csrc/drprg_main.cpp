@@ -20,6 +20,7 @@
 #include <unistd.h>
 #include <vector>
 #include "adapter_args.h"
+#include "decoy_args.h"
 
 namespace {
 
@@ -112,6 +113,12 @@ void usage()
         "              [--dedup] [--min-read-len L] [--max-read-len L] [--min-read-qual Q]\n"
         "              [--trim-front N] [--trim-tail N] [--trim-qual Q [--trim-window W]]\n"
         "              [--adapter SEQ]... [--adapter-error E] [--adapter-min-overlap O] [--adapter-indels] [--front-adapter SEQ]...\n"
+        "              [--decoy FASTA]... [--decoy-k K] [--decoy-min-frac F] [--decoy-min-kmers M]\n"
+        "--decoy FASTA (up to 8 times; plain or .gz), --decoy-k K (9 to 31, default 31), --decoy-min-frac F (in (0, 1], default 0.5),\n"
+        "              --decoy-min-kmers M (default 1): a read is dropped as a contaminant when at least M of its k-mers, and at least the\n"
+        "              fraction F of its k-mers without a letter other than ACGT, are k-mers of the decoy files in either orientation -- on\n"
+        "              the device, behind --trim-*, --adapter and --min/max-read-*.  This build's own rule (k-mer containment, as bbduk\n"
+        "              ref=); sized for mitochondrion, NTM genomes, phiX, not a human genome.\n"
         "--adapter SEQ (up to 4 times; 1 to 64 letters ACGT), --adapter-error E (0 to 0.5, default 0.1), --adapter-min-overlap O (default 3):\n"
         "              every read is cut at the leftmost start at which an adapter matches with at most floor(c * E) substitutions over the\n"
         "              c = min(adapter, rest of the read) letters compared, c >= O -- on the device, behind --trim-* and in front of\n"
@@ -176,6 +183,7 @@ int main(int argc, char** argv)
     uint64_t trim_front = 0, trim_tail = 0; // read trimming (include/drprg_hip.h "read trimming"); 0 = not set
     uint32_t trim_qual_milli = 0, trim_window = 0;
     drprg::AdapterArgs adapters; // --adapter SEQ, --adapter-error E, --adapter-min-overlap O (include/drprg_hip.h "adapter trimming")
+    drprg::DecoyArgs decoy; // --decoy FASTA, --decoy-k K, --decoy-min-frac F, --decoy-min-kmers M (include/drprg_hip.h "decoy screen")
     uint32_t min_cluster = 10;
     drprg_hip_annotate_opts ao {};
     ao.min_covg = 3;
@@ -275,6 +283,19 @@ int main(int argc, char** argv)
             const std::string e = adapters.set_overlap(need(i));
             if (!e.empty()) die(e, 2);
         }
+        else if (a == "--decoy") {
+            const std::string e = decoy.add(need(i));
+            if (!e.empty()) die(e, 2);
+        } else if (a == "--decoy-k") {
+            const std::string e = decoy.set_k(need(i));
+            if (!e.empty()) die(e, 2);
+        } else if (a == "--decoy-min-frac") {
+            const std::string e = decoy.set_frac(need(i));
+            if (!e.empty()) die(e, 2);
+        } else if (a == "--decoy-min-kmers") {
+            const std::string e = decoy.set_kmers(need(i));
+            if (!e.empty()) die(e, 2);
+        }
         else if (a == "-h" || a == "--help") { usage(); return 0; }
         else die("unknown option " + a, 2);
     }
@@ -282,6 +303,7 @@ int main(int argc, char** argv)
     if (max_read_len && max_read_len < min_read_len) die("--max-read-len is below --min-read-len: no read can pass", 2);
     if (trim_window && !trim_qual_milli) die("--trim-window belongs to --trim-qual", 2);
     if (const std::string e = adapters.check(); !e.empty()) die(e, 2);
+    if (const std::string e = decoy.check(); !e.empty()) die(e, 2);
     if (index.empty() || input.empty()) {
         usage();
         return 2;
@@ -337,6 +359,8 @@ int main(int argc, char** argv)
     if (int rc = drprg_hip_set_read_trim(ctx, trim_front, trim_tail, trim_qual_milli, trim_window)) die(drprg_hip_last_error(ctx), -rc);
     if (adapters.any())
         if (int rc = adapters.set_on(ctx, drprg_hip_set_adapters, drprg_hip_set_adapters2)) die(drprg_hip_last_error(ctx), -rc);
+    if (decoy.any()) // (once per run: the second pass after a PRG update maps the resident reads, which are screened already)
+        if (int rc = decoy.set_on(ctx, drprg_hip_set_decoy)) die(drprg_hip_last_error(ctx), -rc);
     // The reads stay in HBM after the mapping pass (up to DRPRG_HIP_KEEP_READS_GB per device, default 32, 0 = off): discover takes
     // the few reads it needs from there and a novel variant maps them again from there -- the file is read once.
     double keep_gb = 32;
@@ -367,6 +391,12 @@ int main(int argc, char** argv)
         if (!adapters.front.empty() && drprg_hip_front_adapter_info(ctx, ai) == 0)
             std::fprintf(stderr, "[drprg-hip +%.3fs] front adapter trimming: reads_seen=%llu bases_seen=%llu reads_cut=%llu bases_cut=%llu reads_emptied=%llu\n", since_start(),
                 (unsigned long long)ai[0], (unsigned long long)ai[1], (unsigned long long)ai[2], (unsigned long long)ai[3], (unsigned long long)ai[4]);
+    }
+    if (verbose && decoy.any()) {
+        uint64_t di[8] = {};
+        if (drprg_hip_decoy_info(ctx, di) == 0)
+            std::fprintf(stderr, "[drprg-hip +%.3fs] decoy screen: kmers=%llu reads_seen=%llu bases_seen=%llu reads_dropped=%llu bases_dropped=%llu\n", since_start(),
+                (unsigned long long)di[0], (unsigned long long)di[2], (unsigned long long)di[3], (unsigned long long)di[4], (unsigned long long)di[5]);
     }
     if (verbose && (min_read_len || max_read_len || min_read_qual_milli)) {
         uint64_t fi[8] = {};
@@ -431,6 +461,8 @@ int main(int argc, char** argv)
                 if (from_hbm != 0 && from_hbm != -61 /* ENODATA */) die(drprg_hip_last_error(next), -from_hbm);
                 drprg_hip_close(ctx);
                 ctx = next;
+                if (from_hbm != 0 && decoy.any()) // (the file again: it is screened again)
+                    if (int rc = decoy.set_on(ctx, drprg_hip_set_decoy)) die(drprg_hip_last_error(ctx), -rc);
                 if (from_hbm != 0)
                     if (int rc = drprg_hip_map_fastx(ctx, input.c_str())) die(drprg_hip_last_error(ctx), -rc);
                 if (verbose)

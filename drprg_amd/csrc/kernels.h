@@ -13,6 +13,7 @@
 #include "dedup_word.h"
 #include "adapter_piece.h"
 #include "adapter_edit.h"
+#include "decoy_piece.h"
 
 namespace drprg {
 namespace dev {
@@ -423,9 +424,17 @@ hipError_t launch_dedup_select(const DedupSelect& s, hipStream_t stream);
 // bytes of qual (qual: n_bases + 64 bytes readable; bias 33 or 0), then flag[i] = 1 for the reads the rule keeps, rank[i] = kept reads
 // before i and boff[i] = kept bases before i (n_reads + 1 entries each, entry n_reads the totals: what launch_subsample_tables and the
 // compaction kernels of subsample.hip read).  use_qual == false: qual and qsum are not touched.  flag32, klen: n_reads + 1 entries of
-// scratch; work: eight device words; out: eight words the device can write (page-locked host memory, or device memory), indexed by RF_*;
+// scratch; work: RF_WORDS device words; out: RF_WORDS words the device can write (page-locked host memory, or device memory), indexed by RF_*;
 // temp: read_filter_temp_bytes(n_reads) bytes.  1 <= n_reads <= MAX_BATCH_READS.
-enum { RF_KEPT_READS = 0, RF_KEPT_BASES = 1, RF_SHORT = 2, RF_LONG = 3, RF_LOWQ = 4, RF_BAD_AT = 5 /* first bad quality byte + 1, or 0 */, RF_OFFSETS = 6 /* offsets at odds with n_bases */ };
+// decoy_valid != null: the decoy screen's verdict (decoy_screen.hip; the rule: include/drprg_hip.h "decoy screen") on the reads the length
+// and quality tests kept, from the V and H launch_decoy_screen left in decoy_valid / decoy_hits (u32[n_reads]): a read it drops has flag 0
+// like any other, so the scans see one verdict; RF_DECOY_* count the reads judged, their bases, the reads and bases dropped, and the sums of
+// V and H over the judged reads.  Null (no decoy set): nothing of it is read or counted.  work and out: RF_WORDS words each.
+enum {
+    RF_KEPT_READS = 0, RF_KEPT_BASES = 1, RF_SHORT = 2, RF_LONG = 3, RF_LOWQ = 4, RF_BAD_AT = 5 /* first bad quality byte + 1, or 0 */,
+    RF_OFFSETS = 6 /* offsets at odds with n_bases */, RF_ERR = 7 /* work only: the error word of the compaction behind the filter */,
+    RF_DECOY_READS = 8, RF_DECOY_BASES = 9, RF_DECOY_DROPPED = 10, RF_DECOY_DROPPED_BASES = 11, RF_DECOY_VALID = 12, RF_DECOY_HITS = 13, RF_WORDS = 16
+};
 struct ReadFilterArgs {
     const uint8_t* qual;
     uint32_t bias;
@@ -433,6 +442,8 @@ struct ReadFilterArgs {
     uint64_t n_reads, n_bases;
     uint64_t min_len, max_len, T;
     bool use_qual;
+    const uint32_t *decoy_valid, *decoy_hits;
+    uint32_t decoy_frac_milli, decoy_min_kmers;
     unsigned long long* qsum;
     uint8_t* flag;
     uint32_t *flag32, *rank;
@@ -540,6 +551,34 @@ uint32_t read_trim_npos_chunks(uint64_t n_npos);
 hipError_t launch_read_trim(const ReadTrimArgs& a, const ReadTrimNpos& np, hipStream_t stream, KernelTimer timer = {}, const AdapterEditSets* edit = nullptr);
 hipError_t launch_read_trim_fill(const ReadTrimFill& f, hipStream_t stream);
 hipError_t launch_read_trim_npos_emit(const ReadTrimFill& f, const ReadTrimNpos& np, uint64_t* out, uint64_t out_cap, hipStream_t stream);
+
+// decoy_screen.hip: the decoy screen (the rule: include/drprg_hip.h "decoy screen").
+// The table.  text: the decoy records as upper- or lower-case text, one 'N' between two records, n_text bytes and 64 readable bytes behind
+// them, 16-byte aligned.  table: n_slots slots (a power of two >= 2 x the windows of the records, at least DC_MIN_SLOTS), filled with
+// DC_EMPTY here; every canonical k-mer of every all-ACGT window is inserted by a 64-bit compare-and-swap, and *distinct (zeroed here)
+// counts the insertions that took an empty slot.
+hipError_t launch_decoy_build(const uint8_t* text, uint64_t n_text, uint32_t k, unsigned long long* table, uint64_t n_slots, unsigned long long* distinct,
+    hipStream_t stream);
+// found[i] = 1 iff the canonical k-mer kmers[i] is in the table
+hipError_t launch_decoy_lookup(const DecoySet& d, const unsigned long long* kmers, uint64_t n, uint8_t* found, hipStream_t stream);
+// The screen.  The bases in either of adapter_points_kernel's two forms: text (n_bases + 64 bytes readable when 16-byte aligned; any other
+// address is read byte by byte and never behind n_bases) or, when words != null, a packed batch's words with nbits, the bitmap
+// launch_mark_npos makes of its position list (null: none).  valid[r] += V, hits[r] += H of read r (u32[n_reads], zeroed by the caller).
+// 1 <= n_reads <= MAX_BATCH_READS; nothing is indexed out of bounds whatever `offsets` holds.
+struct DecoyScreenArgs {
+    const uint8_t* text;
+    const uint32_t* words;
+    const uint16_t* nbits;
+    const uint64_t* offsets;
+    uint64_t n_reads, n_bases;
+    uint32_t *valid, *hits;
+};
+uint32_t decoy_screen_tiles(uint64_t n_bases);
+// timer: around decoy_screen_kernel
+hipError_t launch_decoy_screen(const DecoyScreenArgs& a, const DecoySet& d, hipStream_t stream, KernelTimer timer = {});
+// The verdict alone, for a batch no filter has seen: flag[r] = 0 for a read the rule drops, else 1; work (four zeroed device words) receives
+// reads dropped, bases dropped, the sum of V and the sum of H; *err (zeroed by the caller) is set when the offsets do not ascend from 0 to n_bases.
+hipError_t launch_decoy_verdict(const DecoyScreenArgs& a, const DecoySet& d, uint8_t* flag, unsigned long long* work, uint32_t* err, hipStream_t stream);
 
 // anchor_scan.hip: reads of a resident batch that hold one of the (sorted) anchor k-mers of length A -- every such read once,
 // in any order, appended to `list` (count keeps counting past list_cap).  prefilter: 2^16 bits, bit (kmer & 0xFFFF) set for every

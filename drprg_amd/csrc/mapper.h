@@ -136,11 +136,17 @@ public:
         bool adapter_indels = false;
         dev::AdapterSet front_adapters {};
         dev::AdapterEq eq3 {}, eq5 {};
+        // The decoy screen (the rule: include/drprg_hip.h "decoy screen"; decoy_screen.hip): K (0: no decoy set), f and M.  The table
+        // itself lives on every device of the context (set_decoy); decoy_id names the set these settings were made for, and a Mapper
+        // refuses to screen against any other.
+        uint32_t decoy_k = 0, decoy_frac_milli = 0, decoy_min_kmers = 0;
+        uint64_t decoy_id = 0;
+        bool decoy() const { return decoy_k != 0; }
         bool any_adapters() const { return adapters.n != 0 || front_adapters.n != 0; }
         bool crops() const { return trim_front || trim_tail || trim_qual_milli; } // what drprg_hip_read_trim_info counts
         bool filters() const { return min_len || max_len || min_qual_milli; }
         bool trims() const { return crops() || any_adapters(); }
-        bool any() const { return filters() || trims(); }
+        bool any() const { return filters() || trims() || decoy(); }
         bool use_qual() const { return min_qual_milli != 0; }
         bool wants_qual() const { return min_qual_milli != 0 || trim_qual_milli != 0; } // the ingest carries quality bytes
     };
@@ -153,7 +159,12 @@ public:
         uint64_t reads_seen = 0, bases_seen = 0, reads_cut = 0, bases_cut = 0, reads_emptied = 0;
         AdapterOutcome& operator+=(const AdapterOutcome& o);
     };
+    struct DecoyOutcome { // drprg_hip_decoy_info: the reads the other tests kept, and what the screen made of them
+        uint64_t reads_judged = 0, bases_judged = 0, reads_dropped = 0, bases_dropped = 0, valid = 0, hits = 0;
+        DecoyOutcome& operator+=(const DecoyOutcome& o);
+    };
     struct FilterOutcome {
+        DecoyOutcome decoy;     // (all zero without a decoy set)
         TrimOutcome trim;       // (all zero without a crop or a quality trim)
         AdapterOutcome adapter; // (all zero without adapters)
         AdapterOutcome front;   // drprg_hip_front_adapter_info (all zero without 5' adapters; bases_seen: behind the 3' cut)
@@ -187,6 +198,20 @@ public:
     // the ranges do not lie inside the reads.  Synchronises `stream`.
     void adapter_trim_device(const ReadFilter& f, const uint8_t* d_text, const uint32_t* d_words, const uint64_t* d_npos, uint64_t n_npos, const uint64_t* d_offsets,
         uint64_t n_reads, uint64_t n_bases, uint64_t* d_begin, uint64_t* d_end, uint64_t res[11], hipStream_t stream);
+    // The decoy set of this device (drprg_hip_set_decoy).  text: the records' letters, one 'N' between two records; windows: the windows
+    // of the records (what the table is sized by); set: the name ReadFilter::decoy_id carries.  The table is built on the device
+    // (decoy_screen.hip) and stays until clear_decoy or the Mapper goes; -EINVAL, and no set, when the text holds no k-mer.
+    void set_decoy(const std::vector<uint8_t>& text, uint64_t windows, uint32_t k, uint64_t set);
+    void clear_decoy();
+    uint64_t decoy_distinct() const { return decoy_.distinct; }
+    uint64_t decoy_slots() const { return decoy_.table.size(); }
+    // found[i] = 1 iff canonical k-mer kmers[i] is in the table.  Synchronises.
+    void decoy_lookup(const std::vector<uint64_t>& kmers, uint8_t* found);
+    // The screen kernels alone on the caller's device buffers (drprg_hip_decoy_screen_device): the bases as for adapter_trim_device;
+    // d_valid / d_hits (either may be null) receive V and H, d_flags 1 for a kept read; res[0..3]: reads dropped, bases dropped, sum of V,
+    // sum of H; res[4]: the offsets do not ascend from 0 to n_bases.  Synchronises `stream`.
+    void decoy_screen_device(const ReadFilter& f, const uint8_t* d_text, const uint32_t* d_words, const uint64_t* d_npos, uint64_t n_npos, const uint64_t* d_offsets,
+        uint64_t n_reads, uint64_t n_bases, uint32_t* d_valid, uint32_t* d_hits, uint8_t* d_flags, uint64_t res[5], hipStream_t stream);
     // Reads that stay in HBM (off by default).  keep_reads(max_bytes > 0): from now on map_host_async copies every block into
     // device memory of its own instead of a staging set and leaves it there -- at most max_bytes of it; one byte more and
     // everything kept is dropped and the staging sets are back.  kept_complete(): every read mapped since keep_reads() /
@@ -475,6 +500,11 @@ private:
         // adapter trimming: every read's smallest matching start, and a packed block's bitmap of non-ACGT bases
         DeviceBuffer<uint32_t> t_cut;
         DeviceBuffer<uint16_t> t_nbits;
+        // the decoy screen: V and H of every read ([0, n_reads) and [n_reads, 2 n_reads)), and -- the device entry -- its four counts and
+        // error word with their pinned mirror
+        DeviceBuffer<uint32_t> k_counts;
+        DeviceBuffer<unsigned long long> k_work;
+        PinnedBuffer<unsigned long long> k_out;
     };
     struct Stage {
         FilterScratch filt;
@@ -493,8 +523,9 @@ private:
     // room for the filter of n_reads reads (qual_bytes: 0 without a quality threshold); own_flags / own_sums: the caller has none
     void ensure_filter_scratch(FilterScratch& fs, uint64_t n_reads, uint64_t qual_bytes, bool own_flags, bool own_sums);
     // queues the filter on `stream`; fs.h_out holds dev::RF_* once the stream has been waited for
+    // decoy: fs.k_counts holds the screen's V and H of these reads (run_decoy_screen, on the same stream), and the flags see its verdict
     void run_read_filter(FilterScratch& fs, const ReadFilter& f, const uint8_t* d_qual, uint32_t bias, const uint64_t* d_offsets, uint64_t n_reads,
-        uint64_t n_bases, unsigned long long* d_sums, uint8_t* d_flags, hipStream_t stream);
+        uint64_t n_bases, unsigned long long* d_sums, uint8_t* d_flags, hipStream_t stream, bool decoy = false);
     // room for the trim kernels over n_reads reads (own_ranges: the caller brings no begin / end arrays)
     // adapters: room for the cut words too, and for a bitmap over bitmap_bases packed bases (0: text, or no listed position)
     void ensure_trim_scratch(FilterScratch& fs, uint64_t n_reads, uint64_t n_npos, bool use_qual, bool own_ranges, bool adapters = false, uint64_t bitmap_bases = 0);
@@ -504,6 +535,17 @@ private:
     void run_read_trim(FilterScratch& fs, const ReadFilter& f, const uint8_t* d_qual, uint32_t bias, const uint64_t* d_offsets, const uint8_t* d_rev,
         uint64_t n_reads, uint64_t n_bases, uint64_t* d_begin, uint64_t* d_end, const uint64_t* d_npos, uint64_t n_npos, hipStream_t stream,
         const dev::AdapterPoints* pts = nullptr);
+    // this device's decoy set: the table, its distinct k-mers and the name of the set (0: none)
+    struct DecoyTable {
+        DeviceBuffer<unsigned long long> table;
+        uint64_t distinct = 0, id = 0;
+        uint32_t k = 0;
+    };
+    DecoyTable decoy_;
+    dev::DecoySet decoy_set(const ReadFilter& f) const; // what the kernels are told; refuses settings made for another set
+    // V and H of every read of the batch into fs.k_counts, queued on `stream`: a packed batch's bitmap (fs.t_nbits) first
+    void run_decoy_screen(FilterScratch& fs, const ReadFilter& f, const uint8_t* d_bases, bool packed, const uint64_t* d_npos, uint64_t n_npos,
+        const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases, hipStream_t stream);
     FilterScratch filter_api_; // read_filter_device's and read_trim_device's own (as bam_api_)
     BamScratch bam_api_; // pack_bam_on_device's own (the caller's stream is not ordered with the context's)
     uint64_t bam_blocks_ = 0;

@@ -10,6 +10,7 @@
 // --min-read-len L, --max-read-len L and --min-read-qual Q on both (include/drprg_hip.h "read filter"),
 // --trim-front N, --trim-tail N, --trim-qual Q and --trim-window W on both (include/drprg_hip.h "read trimming"),
 // --adapter SEQ (repeatable), --adapter-error E and --adapter-min-overlap O on both (include/drprg_hip.h "adapter trimming"),
+// --decoy FASTA (repeatable), --decoy-k K, --decoy-min-frac F and --decoy-min-kmers M on both (include/drprg_hip.h "decoy screen"),
 // and writes the files drprg then looks for: <prg>.k<K>.w<W>.idx + kmer_prgs/ (index),
 // <dir>/denovo_paths.txt (discover, /root/reference/src/lib.rs:569-577),
 // <out>/pandora_genotyped.vcf (map, /root/reference/src/lib.rs:644-646).
@@ -27,6 +28,7 @@
 #include <vector>
 
 #include "adapter_args.h"
+#include "decoy_args.h"
 
 namespace {
 
@@ -62,6 +64,7 @@ struct Args {
     uint64_t trim_front = 0, trim_tail = 0;
     uint32_t trim_qual_milli = 0, trim_window = 0;
     drprg::AdapterArgs adapters; // --adapter SEQ, --adapter-error E, --adapter-min-overlap O (include/drprg_hip.h "adapter trimming")
+    drprg::DecoyArgs decoy; // --decoy FASTA, --decoy-k K, --decoy-min-frac F, --decoy-min-kmers M (include/drprg_hip.h "decoy screen")
     std::string outdir = "pandora", vcf_refs;
     std::vector<std::string> positional;
     int device = 0;
@@ -82,6 +85,7 @@ void usage()
         "                   [--dedup] [--min-read-len L] [--max-read-len L] [--min-read-qual Q]\n"
         "                   [--trim-front N] [--trim-tail N] [--trim-qual Q [--trim-window W]]\n"
         "                   [--adapter SEQ]... [--adapter-error E] [--adapter-min-overlap O] [--adapter-indels] [--front-adapter SEQ]...\n"
+        "                   [--decoy FASTA]... [--decoy-k K] [--decoy-min-frac F] [--decoy-min-kmers M]\n"
         "                   [--vcf-refs FASTA] [-t N] [-w W] [-k K] [-c N] [-I] [-K] [-e RATE] [--max-diff N] <prg> <reads>\n"
         "  pandora discover [same mapping options] <prg> <query.tsv>\n"
         "  --max-covg N: reads are taken in file order up to and including the first one at which (N + 1) x SIZE bases are reached;\n"
@@ -113,6 +117,11 @@ void usage()
         "  --adapter-indels: an occurrence may carry insertions and deletions too (edit distance at most floor(m * E) over the whole adapter).\n"
         "  --front-adapter SEQ (up to 4 times; needs --adapter-indels): 5' adapters, cut off the reads' starts behind the 3' cut.\n"
         "                Still missing: anchored adapters, pair overlap, indels inside an adapter that the read's end cuts short.\n"
+        "  --decoy FASTA (up to 8 times; plain or .gz), --decoy-k K (9 to 31, default 31), --decoy-min-frac F (in (0, 1], default 0.5),\n"
+        "                --decoy-min-kmers M (default 1): a read is dropped as a contaminant when at least M of its k-mers, and at least the\n"
+        "                fraction F of its k-mers without a letter other than ACGT, are k-mers of the decoy files in either orientation -- on\n"
+        "                the device, behind --trim-*, --adapter and --min/max-read-*: the run is that of a file of the kept reads.  This\n"
+        "                build's own rule (k-mer containment, as bbduk ref=); sized for mitochondrion, NTM genomes, phiX, not a human genome.\n"
         "  <reads>: FASTA or FASTQ, plain or gzip; or BAM (secondary and supplementary records are skipped, reverse-strand records are\n"
         "           reverse-complemented, alignments are ignored, qualities are looked at by --min-read-qual and --trim-qual alone)\n"
         "environment: DRPRG_HIP_DEVICE selects the GPU (default 0); DRPRG_HIP_DEVICES=0,1,.. maps on several GPUs of the node\n");
@@ -196,6 +205,19 @@ Args parse(int argc, char** argv)
             const std::string e = a.adapters.set_overlap(need(i));
             if (!e.empty()) die(e, 2);
         }
+        else if (s == "--decoy") {
+            const std::string e = a.decoy.add(need(i));
+            if (!e.empty()) die(e, 2);
+        } else if (s == "--decoy-k") {
+            const std::string e = a.decoy.set_k(need(i));
+            if (!e.empty()) die(e, 2);
+        } else if (s == "--decoy-min-frac") {
+            const std::string e = a.decoy.set_frac(need(i));
+            if (!e.empty()) die(e, 2);
+        } else if (s == "--decoy-min-kmers") {
+            const std::string e = a.decoy.set_kmers(need(i));
+            if (!e.empty()) die(e, 2);
+        }
         else if (s == "--dedup") a.dedup = true;
         else if (s == "-o" || s == "--outdir") a.outdir = need(i);
         else if (s == "--vcf-refs") a.vcf_refs = need(i);
@@ -222,6 +244,7 @@ Args parse(int argc, char** argv)
     if (a.max_read_len && a.max_read_len < a.min_read_len) die("--max-read-len is below --min-read-len: no read can pass", 2);
     if (a.trim_window && !a.trim_qual_milli) die("--trim-window belongs to --trim-qual", 2);
     if (const std::string e = a.adapters.check(); !e.empty()) die(e, 2);
+    if (const std::string e = a.decoy.check(); !e.empty()) die(e, 2);
     if (const char* d = std::getenv("DRPRG_HIP_DEVICE")) a.device = std::atoi(d);
     return a;
 }
@@ -271,6 +294,8 @@ drprg_hip_ctx* open_ctx(const Args& a)
     if (a.adapters.any()) {
         if (int rc = a.adapters.set_on(ctx, drprg_hip_set_adapters, drprg_hip_set_adapters2)) die(drprg_hip_last_error(ctx), -rc);
     }
+    if (a.decoy.any())
+        if (int rc = a.decoy.set_on(ctx, drprg_hip_set_decoy)) die(drprg_hip_last_error(ctx), -rc);
     drprg_hip_set_threads(ctx, a.threads);
     drprg_hip_set_input_format(ctx, packed_input()); // the parser threads pack the reads to 2 bits (DRPRG_HIP_INPUT=ascii: one byte per base)
     return ctx;
@@ -320,7 +345,7 @@ std::string run_tag(const Args& a, const std::string& reads)
                   + std::to_string((unsigned long long)a.trim_tail) + "/" + std::to_string(a.trim_qual_milli) + "/"
                   + std::to_string(a.trim_qual_milli ? (a.trim_window ? a.trim_window : 4u) : 0u)
                                                             : std::string())
-        + (a.adapters.any() ? a.adapters.tag() : std::string());
+        + (a.adapters.any() ? a.adapters.tag() : std::string()) + (a.decoy.any() ? a.decoy.tag() : std::string());
 }
 
 // The reads stay in HBM after the mapping pass: up to DRPRG_HIP_KEEP_READS_GB per device, default 32, 0 = off.  --subsample-covg and --dedup work on
@@ -394,6 +419,9 @@ void report_filter(drprg_hip_ctx* ctx, const Args& a)
     if (a.verbose && !a.adapters.front.empty() && drprg_hip_front_adapter_info(ctx, fi) == 0)
         std::printf("[pandora-hip] front adapter trimming: reads_seen=%llu bases_seen=%llu reads_cut=%llu bases_cut=%llu reads_emptied=%llu\n", (unsigned long long)fi[0],
             (unsigned long long)fi[1], (unsigned long long)fi[2], (unsigned long long)fi[3], (unsigned long long)fi[4]);
+    if (a.verbose && a.decoy.any() && drprg_hip_decoy_info(ctx, fi) == 0)
+        std::printf("[pandora-hip] decoy screen: kmers=%llu reads_seen=%llu bases_seen=%llu reads_dropped=%llu bases_dropped=%llu\n", (unsigned long long)fi[0],
+            (unsigned long long)fi[2], (unsigned long long)fi[3], (unsigned long long)fi[4], (unsigned long long)fi[5]);
     if (!a.verbose || !(a.min_read_len || a.max_read_len || a.min_read_qual_milli) || drprg_hip_read_filter_info(ctx, fi) != 0) return;
     std::printf("[pandora-hip] read filter: reads_seen=%llu bases_seen=%llu dropped_short=%llu dropped_long=%llu dropped_low_qual=%llu reads_kept=%llu "
                 "bases_kept=%llu (T=%llu)\n", (unsigned long long)fi[0], (unsigned long long)fi[1], (unsigned long long)fi[2], (unsigned long long)fi[3],

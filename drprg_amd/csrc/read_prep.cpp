@@ -1,5 +1,5 @@
 // read_prep.cpp -- what happens to a host block before it is mapped: staging sets and the copies into them, the read filter, read
-// trimming and adapter trimming with their drivers, and the packers of the harness path.  See mapper.h.
+// trimming, adapter trimming and the decoy screen with their drivers, and the packers of the harness path.  See mapper.h.
 #include "mapper.h"
 #include <algorithm>
 #include <hip/hip_runtime.h>
@@ -103,6 +103,7 @@ void Mapper::only_empty_reads(uint64_t n_reads, const ReadFilter& f, bool keepin
 {
     o.dropped_short = f.min_len ? n_reads : 0;
     o.reads_kept = o.mapped_reads = n_reads - o.dropped_short;
+    if (f.decoy()) o.decoy.reads_judged = o.reads_kept; // (no window, no hit: the screen keeps them)
     count_unmapped(o.reads_kept, keeping);
 }
 
@@ -196,14 +197,18 @@ void Mapper::ensure_filter_scratch(FilterScratch& fs, uint64_t n_reads, uint64_t
     grow(fs.d_klen, n_reads + 1);
     grow(fs.d_boff, n_reads + 1);
     grow(fs.d_temp, dev::read_filter_temp_bytes(n_reads));
-    if (!fs.d_work) fs.d_work.alloc(8);
-    if (!fs.h_out) fs.h_out.alloc(8);
+    if (!fs.d_work) fs.d_work.alloc(dev::RF_WORDS);
+    if (!fs.h_out) fs.h_out.alloc(dev::RF_WORDS);
 }
 
 void Mapper::run_read_filter(FilterScratch& fs, const ReadFilter& f, const uint8_t* d_qual, uint32_t bias, const uint64_t* d_offsets, uint64_t n_reads,
-    uint64_t n_bases, unsigned long long* d_sums, uint8_t* d_flags, hipStream_t stream)
+    uint64_t n_bases, unsigned long long* d_sums, uint8_t* d_flags, hipStream_t stream, bool decoy)
 {
     dev::ReadFilterArgs a {};
+    if (decoy) {
+        a.decoy_valid = fs.k_counts.data(); a.decoy_hits = fs.k_counts.data() + n_reads;
+        a.decoy_frac_milli = f.decoy_frac_milli; a.decoy_min_kmers = f.decoy_min_kmers;
+    }
     a.qual = d_qual; a.bias = bias; a.offsets = d_offsets; a.n_reads = n_reads; a.n_bases = n_bases;
     a.min_len = f.min_len; a.max_len = f.max_len; a.T = f.T; a.use_qual = f.use_qual(); // (a batch of empty reads launches no tile, and its sums are still cleared)
     a.qsum = d_sums; a.flag = d_flags; a.flag32 = fs.d_flag32.data(); a.rank = fs.d_rank.data(); a.klen = fs.d_klen.data(); a.boff = fs.d_boff.data();
@@ -332,6 +337,101 @@ void Mapper::adapter_trim_device(const ReadFilter& f, const uint8_t* d_text, con
     res[10] = fs.t_out[dev::RT_OFFSETS];
 }
 
+// ---- the decoy screen ----------------------------------------------------------------------------------------------------------------
+void Mapper::set_decoy(const std::vector<uint8_t>& text, uint64_t windows, uint32_t k, uint64_t set)
+{
+    HIPCHK(hipSetDevice(device_));
+    sync();
+    clear_decoy();
+    if (text.empty() || windows == 0) throw Error(DRPRG_EINVAL, "decoy screen: the decoy files hold no k-mer");
+    uint64_t n_slots = dev::DC_MIN_SLOTS;
+    while (n_slots < 2 * windows) n_slots <<= 1;
+    DeviceBuffer<uint8_t> d_text;
+    DeviceBuffer<unsigned long long> d_distinct;
+    d_text.alloc(text.size() + 64);
+    d_distinct.alloc(1);
+    DecoyTable t;
+    t.table.alloc(n_slots);
+    HIPCHK(hipMemcpyAsync(d_text.data(), text.data(), text.size(), hipMemcpyHostToDevice, stream_));
+    HIPCHK(hipMemsetAsync(d_text.data() + text.size(), 0, 64, stream_));
+    HIPCHK(dev::launch_decoy_build(d_text.data(), text.size(), k, t.table.data(), n_slots, d_distinct.data(), stream_));
+    unsigned long long distinct = 0;
+    HIPCHK(hipMemcpyAsync(&distinct, d_distinct.data(), sizeof distinct, hipMemcpyDeviceToHost, stream_));
+    HIPCHK(hipStreamSynchronize(stream_));
+    if (distinct == 0) throw Error(DRPRG_EINVAL, "decoy screen: the decoy files hold no k-mer (no window of " + std::to_string(k) + " letters ACGT)");
+    t.distinct = distinct; t.id = set; t.k = k;
+    decoy_ = std::move(t);
+}
+
+void Mapper::clear_decoy()
+{
+    if (!decoy_.table) return;
+    sync(); // (nothing in flight reads the table: the screen runs on the copy stream and is waited for with the filter's read-back)
+    decoy_ = DecoyTable {};
+}
+
+dev::DecoySet Mapper::decoy_set(const ReadFilter& f) const
+{
+    if (!f.decoy() || !decoy_.table || decoy_.id != f.decoy_id || decoy_.k != f.decoy_k)
+        throw Error(DRPRG_EINVAL, "decoy screen: no decoy set is loaded (drprg_hip_set_decoy)");
+    return dev::DecoySet { decoy_.table.data(), decoy_.table.size(), f.decoy_k, f.decoy_frac_milli, f.decoy_min_kmers };
+}
+
+void Mapper::decoy_lookup(const std::vector<uint64_t>& kmers, uint8_t* found)
+{
+    HIPCHK(hipSetDevice(device_));
+    if (!decoy_.table) throw Error(DRPRG_EINVAL, "decoy screen: no decoy set is loaded (drprg_hip_set_decoy)");
+    if (kmers.empty()) return;
+    DeviceBuffer<unsigned long long> d_kmers;
+    DeviceBuffer<uint8_t> d_found;
+    d_kmers.alloc(kmers.size());
+    d_found.alloc(kmers.size());
+    const dev::DecoySet d { decoy_.table.data(), decoy_.table.size(), decoy_.k, 1, 1 };
+    HIPCHK(hipMemcpyAsync(d_kmers.data(), kmers.data(), kmers.size() * sizeof(uint64_t), hipMemcpyHostToDevice, stream_));
+    HIPCHK(dev::launch_decoy_lookup(d, d_kmers.data(), kmers.size(), d_found.data(), stream_));
+    HIPCHK(hipMemcpyAsync(found, d_found.data(), kmers.size(), hipMemcpyDeviceToHost, stream_));
+    HIPCHK(hipStreamSynchronize(stream_));
+}
+
+void Mapper::run_decoy_screen(FilterScratch& fs, const ReadFilter& f, const uint8_t* d_bases, bool packed, const uint64_t* d_npos, uint64_t n_npos,
+    const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases, hipStream_t stream)
+{
+    const dev::DecoySet d = decoy_set(f);
+    grow(fs.k_counts, 2 * n_reads);
+    dev::DecoyScreenArgs a { packed ? nullptr : d_bases, packed ? reinterpret_cast<const uint32_t*>(d_bases) : nullptr, nullptr, d_offsets, n_reads, n_bases,
+        fs.k_counts.data(), fs.k_counts.data() + n_reads };
+    if (packed && n_npos) { // the position list as a bitmap, as adapter_points makes it
+        const uint64_t n16 = (n_bases + 15) / 16 + 8;
+        grow(fs.t_nbits, n16);
+        HIPCHK(hipMemsetAsync(fs.t_nbits.data(), 0, n16 * sizeof(uint16_t), stream));
+        HIPCHK(dev::launch_mark_npos(d_npos, n_npos, n_bases, fs.t_nbits.data(), stream));
+        a.nbits = fs.t_nbits.data();
+    }
+    HIPCHK(hipMemsetAsync(fs.k_counts.data(), 0, 2 * n_reads * sizeof(uint32_t), stream));
+    HIPCHK(dev::launch_decoy_screen(a, d, stream));
+}
+
+void Mapper::decoy_screen_device(const ReadFilter& f, const uint8_t* d_text, const uint32_t* d_words, const uint64_t* d_npos, uint64_t n_npos, const uint64_t* d_offsets,
+    uint64_t n_reads, uint64_t n_bases, uint32_t* d_valid, uint32_t* d_hits, uint8_t* d_flags, uint64_t res[5], hipStream_t stream)
+{
+    for (int i = 0; i < 5; ++i) res[i] = 0;
+    const dev::DecoySet d = decoy_set(f);
+    if (n_reads == 0) return;
+    stream = device_entry(stream, !d_offsets || !d_flags || (n_bases && !d_text && !d_words) || (n_npos && !d_npos), n_reads);
+    FilterScratch& fs = filter_api_;
+    run_decoy_screen(fs, f, d_words ? reinterpret_cast<const uint8_t*>(d_words) : d_text, d_words != nullptr, d_npos, n_npos, d_offsets, n_reads, n_bases, stream);
+    if (!fs.k_work) fs.k_work.alloc(5);
+    if (!fs.k_out) fs.k_out.alloc(5);
+    const dev::DecoyScreenArgs a { d_text, d_words, nullptr, d_offsets, n_reads, n_bases, fs.k_counts.data(), fs.k_counts.data() + n_reads };
+    HIPCHK(hipMemsetAsync(fs.k_work.data(), 0, 5 * sizeof(unsigned long long), stream));
+    HIPCHK(dev::launch_decoy_verdict(a, d, d_flags, fs.k_work.data(), reinterpret_cast<uint32_t*>(fs.k_work.data() + 4), stream));
+    HIPCHK(hipMemcpyAsync(fs.k_out.data(), fs.k_work.data(), 5 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    if (d_valid) HIPCHK(hipMemcpyAsync(d_valid, fs.k_counts.data(), n_reads * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+    if (d_hits) HIPCHK(hipMemcpyAsync(d_hits, fs.k_counts.data() + n_reads, n_reads * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    for (int i = 0; i < 5; ++i) res[i] = fs.k_out[i];
+}
+
 // ---- a host block behind the filter: map_host_filtered and its steps ---------------------------------------------------------------------
 // what the trim stage and the filter say alike about a quality byte out of range (at: the byte's index + 1)
 static Error bad_quality_error(uint64_t at, uint64_t n_bases, uint32_t bias)
@@ -408,7 +508,9 @@ void Mapper::filter_block(const HostBatch& hb, const ReadFilter& f, FilterScratc
     FilterOutcome& o)
 {
     const hipStream_t cs = copy_stream_;
-    run_read_filter(fs, f, d_qual, hb.qual_bias, src.d_offsets, src.n_reads, src.n_bases, fs.d_qsum.data(), fs.d_flag.data(), cs);
+    // (the screen in front of the filter's scans, which then see one verdict: the block as the trim stage left it, whatever its form)
+    if (f.decoy()) run_decoy_screen(fs, f, src.d_bases, src.packed, src.d_npos, src.n_npos, src.d_offsets, src.n_reads, src.n_bases, cs);
+    run_read_filter(fs, f, d_qual, hb.qual_bias, src.d_offsets, src.n_reads, src.n_bases, fs.d_qsum.data(), fs.d_flag.data(), cs, f.decoy());
     HIPCHK(hipStreamSynchronize(cs));
     if (trim_err) throw Error(DRPRG_EIO, "read trimming: the block's offsets and the trimmed ranges do not fit each other");
     const unsigned long long* h = fs.h_out.data();
@@ -419,6 +521,9 @@ void Mapper::filter_block(const HostBatch& hb, const ReadFilter& f, FilterScratc
     o.dropped_lowq = h[dev::RF_LOWQ];
     o.reads_kept = h[dev::RF_KEPT_READS];
     o.bases_kept = h[dev::RF_KEPT_BASES];
+    if (f.decoy())
+        o.decoy = DecoyOutcome { h[dev::RF_DECOY_READS], h[dev::RF_DECOY_BASES], h[dev::RF_DECOY_DROPPED], h[dev::RF_DECOY_DROPPED_BASES], h[dev::RF_DECOY_VALID],
+            h[dev::RF_DECOY_HITS] };
 }
 
 // Which of the kept reads go on: all of them, or -- cap_need != 0 and reached in this block -- those up to the one that holds the
@@ -466,7 +571,7 @@ Mapper::DeviceBatch Mapper::place_block(FilterScratch& fs, const DeviceBatch& sr
         return DeviceBatch { dst->bases, dst->offsets, k.n_reads, k.n_bases, src.packed, src.n_npos ? dst->npos : nullptr, src.n_npos };
     }
     const dev::SubsampleBlock sb { src.d_bases, src.d_offsets, k.take, src.n_bases, 0, fs.d_flag.data(), fs.d_rank.data(), fs.d_boff.data(), k.n_reads, k.n_bases };
-    uint32_t* const d_err = reinterpret_cast<uint32_t*>(fs.d_work.data() + 7); // (zeroed with the filter's words)
+    uint32_t* const d_err = reinterpret_cast<uint32_t*>(fs.d_work.data() + dev::RF_ERR); // (zeroed with the filter's words)
     const DeviceBatch cur = compact_block(sb, src, fs.comp, d_err, cs, [&](uint64_t n_list) {
         if (keeping) {
             if (const std::optional<BlockRoom> dst = resident_.take_block(payload, k.n_reads, n_list)) return *dst;
@@ -553,8 +658,16 @@ Mapper::AdapterOutcome& Mapper::AdapterOutcome::operator+=(const AdapterOutcome&
     return *this;
 }
 
+Mapper::DecoyOutcome& Mapper::DecoyOutcome::operator+=(const DecoyOutcome& o)
+{
+    reads_judged += o.reads_judged; bases_judged += o.bases_judged; reads_dropped += o.reads_dropped; bases_dropped += o.bases_dropped;
+    valid += o.valid; hits += o.hits;
+    return *this;
+}
+
 Mapper::FilterOutcome& Mapper::FilterOutcome::operator+=(const FilterOutcome& o)
 {
+    decoy += o.decoy;
     trim += o.trim; adapter += o.adapter; front += o.front;
     reads_seen += o.reads_seen; bases_seen += o.bases_seen; dropped_short += o.dropped_short; dropped_long += o.dropped_long;
     dropped_lowq += o.dropped_lowq; reads_kept += o.reads_kept; bases_kept += o.bases_kept;

@@ -140,11 +140,14 @@ __global__ __launch_bounds__(RQ_THREADS) void read_qual_kernel(const uint8_t* __
 
 // flag[i] = read i passes the rule; flag32[i] and klen[i]: the same as a word, and the read's length if it is kept -- what the two
 // exclusive scans read (entry n_reads of both: 0).  work[RF_SHORT .. RF_LOWQ] count the dropped reads, work[RF_OFFSETS] is set when the
-// offsets do not ascend or end at n_bases.
+// offsets do not ascend or end at n_bases.  Under a decoy set (a.decoy_valid != null) a read that passed these tests is held against the
+// decoy screen's verdict (dc_drops) and counted in work[RF_DECOY_*].
 __global__ __launch_bounds__(RQ_THREADS) void read_flags_kernel(ReadFilterArgs a)
 {
     __shared__ uint32_t s_n[3];
+    __shared__ unsigned long long s_d[6];
     if (threadIdx.x < 3) s_n[threadIdx.x] = 0;
+    if (threadIdx.x < 6) s_d[threadIdx.x] = 0;
     __syncthreads();
     const uint64_t i = (uint64_t)blockIdx.x * RQ_THREADS + threadIdx.x;
     if (i == a.n_reads) {
@@ -166,12 +169,25 @@ __global__ __launch_bounds__(RQ_THREADS) void read_flags_kernel(ReadFilterArgs a
             if (__umul64hi(len, a.T) == 0 && S > len * a.T) why = 2;
         }
         if (why >= 0) atomicAdd(&s_n[why], 1u);
+        else if (a.decoy_valid) {
+            const uint32_t V = a.decoy_valid[i], H = a.decoy_hits[i];
+            atomicAdd(&s_d[0], 1ull);
+            atomicAdd(&s_d[1], (unsigned long long)len);
+            if (V) atomicAdd(&s_d[4], (unsigned long long)V);
+            if (H) atomicAdd(&s_d[5], (unsigned long long)H);
+            if (dc_drops(V, H, a.decoy_frac_milli, a.decoy_min_kmers)) {
+                why = 3;
+                atomicAdd(&s_d[2], 1ull);
+                atomicAdd(&s_d[3], (unsigned long long)len);
+            }
+        }
         a.flag[i] = why < 0 ? 1 : 0;
         a.flag32[i] = why < 0 ? 1u : 0u;
         a.klen[i] = why < 0 ? len : 0;
     }
     __syncthreads();
     if (threadIdx.x < 3 && s_n[threadIdx.x]) atomicAdd(&a.work[RF_SHORT + threadIdx.x], (unsigned long long)s_n[threadIdx.x]);
+    if (threadIdx.x < 6 && s_d[threadIdx.x]) atomicAdd(&a.work[RF_DECOY_READS + threadIdx.x], s_d[threadIdx.x]);
 }
 
 // the totals of the two scans beside the counts, and everything into `out` (page-locked host memory, or device memory)
@@ -185,7 +201,8 @@ __global__ void read_filter_result_kernel(ReadFilterArgs a)
     a.out[RF_LOWQ] = a.work[RF_LOWQ];
     a.out[RF_BAD_AT] = a.work[RF_BAD_AT] == ~0ull ? 0ull : a.work[RF_BAD_AT];
     a.out[RF_OFFSETS] = a.work[RF_OFFSETS];
-    a.out[7] = 0;
+    a.out[RF_ERR] = 0;
+    for (int i = RF_DECOY_READS; i < RF_WORDS; ++i) a.out[i] = a.work[i];
 }
 
 size_t read_filter_temp_bytes(uint64_t n_reads)
@@ -209,7 +226,7 @@ hipError_t launch_read_filter(const ReadFilterArgs& a, hipStream_t stream, Kerne
 {
     if (!a.n_reads || a.n_reads > MAX_BATCH_READS) return hipErrorInvalidValue;
     size_t temp_bytes = a.temp_bytes; // (rocPRIM takes it by reference)
-    HIP_TRY(hipMemsetAsync(a.work, 0, 8 * sizeof(unsigned long long), stream));
+    HIP_TRY(hipMemsetAsync(a.work, 0, RF_WORDS * sizeof(unsigned long long), stream));
     HIP_TRY(hipMemsetAsync(a.work + RF_BAD_AT, 0xFF, sizeof(unsigned long long), stream));
     if (a.use_qual) {
         HIP_TRY(hipMemsetAsync(a.qsum, 0, a.n_reads * sizeof(unsigned long long), stream));

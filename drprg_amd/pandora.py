@@ -337,6 +337,50 @@ class Context:
                                                   stream), self._h)
         return tuple(int(x) for x in out)
 
+    # ---- decoy screen (include/drprg_hip.h: drprg_hip_set_decoy) -------------------------------
+    @staticmethod
+    def frac_milli(frac):
+        """a decimal fraction in (0, 1] with at most three places (number or text, as --decoy-min-frac takes it) as thousandths; 0 or None:
+        the default; ValueError otherwise"""
+        from decimal import Decimal
+        if not frac:
+            return 0
+        milli = Decimal(str(frac)) * 1000
+        if milli != milli.to_integral_value() or milli < 1 or milli > 1000:
+            raise ValueError(f"a fraction is a decimal in (0, 1] with at most three places, not {frac!r}")
+        return int(milli)
+
+    def set_decoy(self, fasta_paths, k=0, min_frac=0, min_kmers=0):
+        """from the next map_fastx on, a read is dropped when at least min_kmers (0: 1) of its k-mers (k 9..31, 0: 31) and at least the
+        fraction min_frac (0: 0.5) of its valid k-mers are canonical k-mers of the 1 to 8 FASTA files; behind the trim stage and the length
+        and quality tests; an empty list clears the set and frees the table"""
+        paths = [os.fspath(p).encode() for p in (fasta_paths or [])]
+        arr = (C.c_char_p * max(len(paths), 1))(*paths)
+        _check(lib.drprg_hip_set_decoy(self._h, arr, len(paths), int(k), self.frac_milli(min_frac), int(min_kmers)), self._h)
+
+    def decoy_info(self):
+        out = (C.c_uint64 * 8)()
+        _check(lib.drprg_hip_decoy_info(self._h, out), self._h)
+        names = ("kmers", "slots", "reads_seen", "bases_seen", "reads_dropped", "bases_dropped", "valid", "hits")
+        return dict(zip(names, (int(x) for x in out)))
+
+    def decoy_lookup(self, kmers):
+        """membership of k-mers (integers, 2 bits per base, A 0 C 1 G 2 T 3, first base high; either orientation) in the decoy set, probed
+        on the device: one byte per k-mer"""
+        kmers = np.ascontiguousarray(kmers, dtype=np.uint64)
+        found = np.zeros(kmers.size, dtype=np.uint8)
+        _check(lib.drprg_hip_decoy_lookup(self._h, _ptr(kmers), kmers.size, _ptr(found)), self._h)
+        return found
+
+    def decoy_screen_device(self, d_text, d_words, d_npos, n_npos, d_offsets, n_reads, n_bases, d_valid, d_hits, d_flags, stream=None):
+        """the screen kernels alone on device buffers (addresses as integers): the bases as for adapter_trim_device; d_valid / d_hits (u32
+        per read, either may be None) receive V and H, d_flags (u8 per read) 1 for a kept read; returns the call's (reads dropped, bases
+        dropped, sum of V, sum of H)"""
+        out = (C.c_uint64 * 4)()
+        _check(lib.drprg_hip_decoy_screen_device(self._h, d_text, d_words, d_npos, int(n_npos), d_offsets, int(n_reads), int(n_bases), d_valid, d_hits, d_flags,
+                                                 out, stream), self._h)
+        return tuple(int(x) for x in out)
+
     def select_reads(self, anchors, A, window_bytes=0):
         """the resident reads in which one of `anchors` (k-mers of A bases as integers, 2 bits per base, A 0 C 1 G 2 T 3, first base high)
         starts -- the selection discover_reads runs on the device (drprg_hip_select_reads); returns (bases u8, offsets u64, ids u64 =

@@ -522,6 +522,51 @@ int drprg_hip_set_adapters2(drprg_hip_ctx* ctx, const char* const* seqs3, uint32
 int drprg_hip_front_adapter_info(drprg_hip_ctx* ctx, uint64_t out[5]);
 int drprg_hip_adapter_trim_device2(drprg_hip_ctx* ctx, const void* d_text, const void* d_words, const void* d_npos, uint64_t n_npos, const void* d_offsets,
     uint64_t n_reads, uint64_t n_bases, void* d_begin, void* d_end, uint64_t out[10], void* hip_stream);
+/* ---- Decoy screen: contaminant reads dropped on the device, as the reads arrive.  THIS BUILD'S OWN RULE, stated from memory of what bbduk
+ * ref=... does (k-mer containment against a reference), the step clinical pipelines run as bbduk, kraken2, nohuman or clockwork
+ * remove_contam in front of drprg; neither pandora nor drprg has one and nothing in them pins it.
+ *   Settings, per context: a decoy set D; a k-mer length K in 9..31 (31 when given as 0); a fraction held as an integer per-mille f in
+ *   1..1000 (500 when given as 0); a minimum number of hits M >= 1 (1 when given as 0).
+ *   K-mers.  Bases are coded A 0, C 1, G 2, T 3, case-insensitive, first base in the high bits: the coding drprg_hip_select_reads takes its
+ *   anchors in.  The canonical k-mer of a window of K bases is the smaller of the window's code and its reverse complement's code.  A window
+ *   that holds any other letter yields no k-mer.
+ *   The set.  D is the set of the canonical k-mers of every window of every record of 1 to 8 FASTA files, plain or .gz (the reader that
+ *   reads the sample).  Windows never span two records; a record shorter than K adds nothing.  Limit: at most 2^31 - 1 windows in all
+ *   (-EOVERFLOW beyond): mitochondrion, NTM genomes, phiX and the like.  A whole human genome is out of scope.
+ *   Verdict.  For a read of L bases, as the trim stage left it: V = the number of starts p in 0 .. L - K whose window is all ACGT, H = the
+ *   number of those whose canonical k-mer is in D.  The read is dropped as DECOY iff H >= M and 1000 * H >= f * V.  A read with V == 0 is
+ *   kept (M >= 1).  The sums are integers: the verdict depends on nothing but the read and D.
+ *   Order.  The screen runs in drprg_hip_map_fastx, per ingest block, on the device that takes the block, BEHIND the trim stage (crops,
+ *   quality, 3' and 5' adapters) and behind the length and quality tests of the read filter: it judges only the reads those tests kept, and a
+ *   read whose decoy part a crop or an adapter cut off is judged on what is left.  Everything "read filter" lists as seeing the kept reads
+ *   alone sees the reads that also passed the screen: mapping, drprg_hip_counters' reads / bases and the genotyper's total, the depth cap's
+ *   running total, the resident set and drprg_hip_resident_info, drprg_hip_select_reads and discover from HBM, drprg_hip_map_resident,
+ *   drprg_hip_dedup and the numbering of drprg_hip_subsample -- the run is that of a file of the kept reads, whatever the thread count, the
+ *   block boundaries and the input form (FASTQ, FASTA, .gz, BAM; ASCII or packed transport).  The screen needs no quality byte, and none is
+ *   parsed, copied or moved on its account.  drprg_hip_map_host* and drprg_hip_map_device* return -EINVAL while a decoy set is loaded.  Once
+ *   the screen dropped a read of a sample that is not resident, drprg_hip_discover_reads returns -ENODATA (-61).  With no decoy set nothing of
+ *   this exists: no launch, no wait, no allocation.
+ *   Under a decoy set drprg_hip_read_filter_info's reads kept and bases kept (out[5], out[6]) count what passed every test, the screen
+ *   included: seen = short + long + low quality + decoy + kept, decoy being drprg_hip_decoy_info's out[4].
+ *   The table (csrc/decoy_screen.hip): 64-bit slots in device memory, the smallest power of two >= 2 x the windows and
+ *   at least 8, ~0 for an empty slot, linear probing that wraps.  Its layout depends on the order of insertion; membership does not.
+ *   drprg_hip_set_decoy: builds the table on every device of the context; applies from the next drprg_hip_map_fastx; n == 0 clears the set
+ *     and frees the table (fasta_paths may be NULL then).  A reset keeps the settings and the table; drprg_hip_close frees the table.
+ *     -EINVAL for n > 8, k outside 9..31, min_frac_milli > 1000, a NULL path, and files that yield no k-mer at all; an unreadable file:
+ *     what drprg_hip_map_fastx returns for an unreadable reads file (-ENOENT).  On any failure the context is left with no decoy set.
+ *   drprg_hip_decoy_info: out[0] = distinct canonical k-mers in the set, out[1] = table slots; since the last reset, out[2..7] = reads
+ *     judged, bases judged, reads dropped, bases dropped, sum of V, sum of H (over the judged reads).
+ *   drprg_hip_decoy_lookup: found[i] = 1 iff k-mer kmers[i] (the coding above, either orientation: the entry canonicalises) is in the set;
+ *     probed in the table on the device -- the table's own test hook.  -EINVAL without a decoy set.
+ *   drprg_hip_decoy_screen_device: the screen kernels alone on caller-owned device buffers; the two input forms, the address, padding and
+ *     stream rules of drprg_hip_adapter_trim_device.  d_valid, d_hits: u32[n_reads], receive V and H (either may be NULL); d_flags:
+ *     u8[n_reads], 1 for a kept read.  out[0..3] = reads dropped, bases dropped, sum of V, sum of H.  -EINVAL without a decoy set, or when
+ *     the offsets do not ascend from 0 to n_bases. */
+int drprg_hip_set_decoy(drprg_hip_ctx* ctx, const char* const* fasta_paths, uint32_t n, uint32_t k, uint32_t min_frac_milli, uint32_t min_kmers);
+int drprg_hip_decoy_info(drprg_hip_ctx* ctx, uint64_t out[8]);
+int drprg_hip_decoy_lookup(drprg_hip_ctx* ctx, const uint64_t* kmers, uint64_t n, uint8_t* found);
+int drprg_hip_decoy_screen_device(drprg_hip_ctx* ctx, const void* d_text, const void* d_words, const void* d_npos, uint64_t n_npos, const void* d_offsets,
+    uint64_t n_reads, uint64_t n_bases, void* d_valid, void* d_hits, void* d_flags, uint64_t out[4], void* hip_stream);
 /* The read selection drprg_hip_discover_reads uses when the reads are resident, on its own: for every device of the context, in order,
  * every kept read in which a k-mer of `anchors` STARTS (anchors: n_anchors k-mers of A bases, 2 bits per base, A 0 C 1 G 2 T 3, first base
  * in the high bits; any order, duplicates allowed).  A block's reads are one base stream: read r of a block is returned iff for some p with
