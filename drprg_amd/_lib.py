@@ -115,6 +115,10 @@ SIGNATURES = {
     "drprg_hip_front_adapter_info": (C.c_int, [C.c_void_p, C.c_void_p]),
     "drprg_hip_adapter_trim_device2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.c_void_p]),
+    "drprg_hip_set_base_mask": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "drprg_hip_base_mask_info": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "drprg_hip_base_mask_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "drprg_hip_set_decoy": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     "drprg_hip_decoy_info": (C.c_int, [C.c_void_p, C.c_void_p]),
     "drprg_hip_decoy_lookup": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),

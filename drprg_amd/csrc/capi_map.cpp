@@ -226,8 +226,9 @@ static IngestHooks fastx_hooks(FastxPass& p)
     IngestHooks hooks;
     hooks.packed = p.ctx->packed_input;
     hooks.bam_native = true; // a BAM file's reads travel in their 4-bit form and are converted on the device (bam_pack.hip), whatever `packed` says
-    hooks.want_qual = p.filter.wants_qual(); // (for the filter's threshold or for --trim-qual; fixed crops alone carry none)
-    if (p.filter.trim_qual_milli) hooks.qual_flag = "--trim-qual"; // (trimming comes first: it is the first to miss them)
+    hooks.want_qual = p.filter.wants_qual(); // (for the filter's threshold, --trim-qual or --mask-qual; fixed crops alone carry none)
+    if (p.filter.mask_qual) hooks.qual_flag = "--mask-qual";
+    if (p.filter.trim_qual_milli) hooks.qual_flag = "--trim-qual"; // (trimming comes first, then the mask: the first to miss them is named)
     // page-locked ingest blocks are kept by the process between calls and contexts (PinPool)
     hooks.alloc = [](size_t n) -> void* { return PinPool::get().take(n); };
     hooks.release = [](void* q) { PinPool::get().give_back(q); };
@@ -271,6 +272,8 @@ static void map_fastx_serial(FastxPass& p, const char* reads_path)
         if (filter.any()) {
             if (filter.trim_qual_milli && batch.qual.size() != batch.bases.size())
                 throw Error(DRPRG_EINVAL, "--trim-qual: a FASTA record has no base qualities; a read is never trimmed by a quality it does not have");
+            if (filter.mask_qual && batch.qual.size() != batch.bases.size())
+                throw Error(DRPRG_EINVAL, "--mask-qual: a FASTA record has no base qualities; a base is never masked by a quality it does not have");
             if (filter.use_qual() && batch.qual.size() != batch.bases.size())
                 throw Error(DRPRG_EINVAL, "--min-read-qual: a FASTA record has no base qualities; a read is never kept or dropped by a quality threshold it cannot be held against");
             if (filter.wants_qual()) hb.qual = batch.qual.data();
@@ -344,6 +347,9 @@ static void refuse_unfiltered(const drprg_hip_ctx* ctx, const char* entry)
     if (ctx->read_filter.trims())
         throw Error(DRPRG_EINVAL, std::string(entry) + ": read trimming is set (drprg_hip_set_read_trim) and this entry carries no qualities; trimming "
                                                       "runs in drprg_hip_map_fastx (clear it with drprg_hip_set_read_trim(ctx, 0, 0, 0, 0))");
+    if (ctx->read_filter.mask_qual)
+        throw Error(DRPRG_EINVAL, std::string(entry) + ": a base mask is set (drprg_hip_set_base_mask) and this entry carries no qualities; masking runs in "
+                                                      "drprg_hip_map_fastx (clear it with drprg_hip_set_base_mask(ctx, 0))");
     if (ctx->read_filter.any())
         throw Error(DRPRG_EINVAL, std::string(entry) + ": a read filter is set (drprg_hip_set_read_filter) and this entry carries no qualities; the filter "
                                                       "runs in drprg_hip_map_fastx (clear it with drprg_hip_set_read_filter(ctx, 0, 0, 0))");

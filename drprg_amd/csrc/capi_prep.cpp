@@ -1,4 +1,4 @@
-// capi_prep.cpp -- read preparation (filter, trimming, adapters, decoy screen: settings, counts, device entries) and the resident sample
+// capi_prep.cpp -- read preparation (filter, trimming, adapters, base mask, decoy screen: settings, counts, device entries) and the resident sample
 // (keep, map from another context, select, subsample, dedup).
 #include "capi_ctx.h"
 #include "fastx.h"
@@ -213,6 +213,44 @@ int drprg_hip_adapter_trim_device2(drprg_hip_ctx* ctx, const void* d_text, const
     uint64_t n_reads, uint64_t n_bases, void* d_begin, void* d_end, uint64_t out[10], void* hip_stream)
 {
     return adapter_trim_device(ctx, d_text, d_words, d_npos, n_npos, d_offsets, n_reads, n_bases, d_begin, d_end, out, 10, false, hip_stream);
+}
+
+// ---- base masking (the rule: include/drprg_hip.h "base masking") -------------------------------------------------------------------
+int drprg_hip_set_base_mask(drprg_hip_ctx* ctx, uint32_t min_qual)
+{
+    API_BEGIN(ctx)
+    if (min_qual > 93) throw Error(DRPRG_EINVAL, "base masking: a quality above 93 cannot be asked for");
+    ctx->read_filter.mask_qual = min_qual; // (it rides in the settings every device's blocks are prepared under, like the trim settings)
+    API_END(ctx)
+}
+
+int drprg_hip_base_mask_info(drprg_hip_ctx* ctx, uint64_t out[5])
+{
+    API_BEGIN(ctx)
+    if (!out) throw Error(DRPRG_EINVAL, "null output");
+    std::lock_guard<std::mutex> g(ctx->filter_mu);
+    const Mapper::MaskOutcome& t = ctx->sample.filter_counts.mask;
+    out[0] = t.reads_seen; out[1] = t.bases_seen; out[2] = t.reads_masked; out[3] = t.bases_masked; out[4] = t.bases_already_unknown;
+    API_END(ctx)
+}
+
+int drprg_hip_base_mask_device(drprg_hip_ctx* ctx, const void* d_qual, uint32_t qual_bias, const void* d_offsets, const void* d_rev, uint64_t n_reads,
+    uint64_t n_bases, void* d_text, void* d_words, const void* d_npos, uint64_t n_npos, void* d_npos_out, uint64_t npos_cap, uint64_t out[6], void* hip_stream)
+{
+    API_BEGIN(ctx)
+    Mapper& m = need_mapper(ctx);
+    if (!out) throw Error(DRPRG_EINVAL, "null output");
+    if (qual_bias != 0 && qual_bias != 33) throw Error(DRPRG_EINVAL, "base masking: the quality bias is 33 (FASTQ) or 0 (BAM)");
+    if (d_text && d_words) throw Error(DRPRG_EINVAL, "base masking: the bases come as text or as packed words, not both");
+    uint64_t res[8];
+    m.base_mask_device(ctx->read_filter, (const uint8_t*)d_qual, qual_bias, (const uint64_t*)d_offsets, (const uint8_t*)d_rev, n_reads, n_bases, (uint8_t*)d_text,
+        (uint32_t*)d_words, (const uint64_t*)d_npos, n_npos, (uint64_t*)d_npos_out, npos_cap, res, (hipStream_t)hip_stream);
+    for (int i = 0; i < 6; ++i) out[i] = res[i];
+    if (res[7]) throw Error(DRPRG_EINVAL, "base masking: the offsets do not run from 0 to n_bases");
+    if (res[6]) throw Error(DRPRG_EFORMAT, "a base quality outside 0..93 at quality byte " + std::to_string(res[6] - 1));
+    if (res[5] > npos_cap || (res[5] && !d_npos_out))
+        throw Error(DRPRG_EOVERFLOW, "base masking: the list behind the mask holds " + std::to_string(res[5]) + " positions, the buffer " + std::to_string(d_npos_out ? npos_cap : 0));
+    API_END(ctx)
 }
 
 // ---- the decoy screen (the rule: include/drprg_hip.h "decoy screen") ----------------------------------------------------------------

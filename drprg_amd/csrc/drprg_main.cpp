@@ -21,6 +21,7 @@
 #include <vector>
 #include "adapter_args.h"
 #include "decoy_args.h"
+#include "mask_args.h"
 
 namespace {
 
@@ -113,7 +114,12 @@ void usage()
         "              [--dedup] [--min-read-len L] [--max-read-len L] [--min-read-qual Q]\n"
         "              [--trim-front N] [--trim-tail N] [--trim-qual Q [--trim-window W]]\n"
         "              [--adapter SEQ]... [--adapter-error E] [--adapter-min-overlap O] [--adapter-indels] [--front-adapter SEQ]...\n"
-        "              [--decoy FASTA]... [--decoy-k K] [--decoy-min-frac F] [--decoy-min-kmers M]\n"
+        "              [--mask-qual Q] [--decoy FASTA]... [--decoy-k K] [--decoy-min-frac F] [--decoy-min-kmers M]\n"
+        "--mask-qual Q (a whole Phred value, 1 to 93): every base whose quality is below Q becomes an unknown base -- on the device, behind\n"
+        "              --trim-* and --adapter and in front of everything else: the run is that of a file in which those bases are the letter N.\n"
+        "              The read keeps its length, its place in the depth arithmetic and its mean quality; only the k-mers that hold a masked\n"
+        "              base stop existing.  Needs qualities: FASTA, or a BAM record without them, is an error under it.  A threshold on what the\n"
+        "              basecaller claims: at Nanopore qualities a Q of 10 or more leaves few 15-mers.  Default: off.\n"
         "--decoy FASTA (up to 8 times; plain or .gz), --decoy-k K (9 to 31, default 31), --decoy-min-frac F (in (0, 1], default 0.5),\n"
         "              --decoy-min-kmers M (default 1): a read is dropped as a contaminant when at least M of its k-mers, and at least the\n"
         "              fraction F of its k-mers without a letter other than ACGT, are k-mers of the decoy files in either orientation -- on\n"
@@ -182,6 +188,7 @@ int main(int argc, char** argv)
     uint32_t min_read_qual_milli = 0;
     uint64_t trim_front = 0, trim_tail = 0; // read trimming (include/drprg_hip.h "read trimming"); 0 = not set
     uint32_t trim_qual_milli = 0, trim_window = 0;
+    uint32_t mask_qual = 0; // --mask-qual Q: base masking (include/drprg_hip.h "base masking"); 0 = not set
     drprg::AdapterArgs adapters; // --adapter SEQ, --adapter-error E, --adapter-min-overlap O (include/drprg_hip.h "adapter trimming")
     drprg::DecoyArgs decoy; // --decoy FASTA, --decoy-k K, --decoy-min-frac F, --decoy-min-kmers M (include/drprg_hip.h "decoy screen")
     uint32_t min_cluster = 10;
@@ -283,6 +290,10 @@ int main(int argc, char** argv)
             const std::string e = adapters.set_overlap(need(i));
             if (!e.empty()) die(e, 2);
         }
+        else if (a == "--mask-qual") {
+            const std::string e = drprg::parse_mask_qual(need(i), mask_qual);
+            if (!e.empty()) die(e, 2);
+        }
         else if (a == "--decoy") {
             const std::string e = decoy.add(need(i));
             if (!e.empty()) die(e, 2);
@@ -357,6 +368,7 @@ int main(int argc, char** argv)
     drprg_hip_set_input_format(ctx, packed_input()); // the parser threads pack the reads to 2 bits (DRPRG_HIP_INPUT=ascii: one byte per base)
     if (int rc = drprg_hip_set_read_filter(ctx, min_read_len, max_read_len, min_read_qual_milli)) die(drprg_hip_last_error(ctx), -rc);
     if (int rc = drprg_hip_set_read_trim(ctx, trim_front, trim_tail, trim_qual_milli, trim_window)) die(drprg_hip_last_error(ctx), -rc);
+    if (int rc = drprg_hip_set_base_mask(ctx, mask_qual)) die(drprg_hip_last_error(ctx), -rc);
     if (adapters.any())
         if (int rc = adapters.set_on(ctx, drprg_hip_set_adapters, drprg_hip_set_adapters2)) die(drprg_hip_last_error(ctx), -rc);
     if (decoy.any()) // (once per run: the second pass after a PRG update maps the resident reads, which are screened already)
@@ -391,6 +403,12 @@ int main(int argc, char** argv)
         if (!adapters.front.empty() && drprg_hip_front_adapter_info(ctx, ai) == 0)
             std::fprintf(stderr, "[drprg-hip +%.3fs] front adapter trimming: reads_seen=%llu bases_seen=%llu reads_cut=%llu bases_cut=%llu reads_emptied=%llu\n", since_start(),
                 (unsigned long long)ai[0], (unsigned long long)ai[1], (unsigned long long)ai[2], (unsigned long long)ai[3], (unsigned long long)ai[4]);
+    }
+    if (verbose && mask_qual) { // (of the one pass over the file: a second pass after a PRG update maps the resident reads, which are masked already)
+        uint64_t bm[5] = {};
+        if (drprg_hip_base_mask_info(ctx, bm) == 0)
+            std::fprintf(stderr, "[drprg-hip +%.3fs] base masking: reads_seen=%llu bases_seen=%llu reads_masked=%llu bases_masked=%llu bases_already_unknown=%llu\n",
+                since_start(), (unsigned long long)bm[0], (unsigned long long)bm[1], (unsigned long long)bm[2], (unsigned long long)bm[3], (unsigned long long)bm[4]);
     }
     if (verbose && decoy.any()) {
         uint64_t di[8] = {};
@@ -454,6 +472,7 @@ int main(int argc, char** argv)
                 drprg_hip_set_input_format(next, packed_input()); // the parser threads pack the reads to 2 bits (DRPRG_HIP_INPUT=ascii: one byte per base)
                 if (int rc = drprg_hip_set_read_filter(next, min_read_len, max_read_len, min_read_qual_milli)) die(drprg_hip_last_error(next), -rc);
                 if (int rc = drprg_hip_set_read_trim(next, trim_front, trim_tail, trim_qual_milli, trim_window)) die(drprg_hip_last_error(next), -rc);
+                if (int rc = drprg_hip_set_base_mask(next, mask_qual)) die(drprg_hip_last_error(next), -rc);
                 if (adapters.any())
                     if (int rc = adapters.set_on(next, drprg_hip_set_adapters, drprg_hip_set_adapters2)) die(drprg_hip_last_error(next), -rc);
                 // the reads again, against the updated index: from HBM if the first context kept them all, else from the file

@@ -580,6 +580,39 @@ hipError_t launch_decoy_screen(const DecoyScreenArgs& a, const DecoySet& d, hipS
 // reads dropped, bases dropped, the sum of V and the sum of H; *err (zeroed by the caller) is set when the offsets do not ascend from 0 to n_bases.
 hipError_t launch_decoy_verdict(const DecoyScreenArgs& a, const DecoySet& d, uint8_t* flag, unsigned long long* work, uint32_t* err, hipStream_t stream);
 
+// base_mask.hip: base masking (the rule: include/drprg_hip.h "base masking").  Every base whose quality byte minus bias is below min_qual
+// (1..93) becomes an unknown base, in place.  qual: n_bases bytes, indexed in bases (n_bases + 64 bytes readable when 16-byte aligned; any
+// other address is read byte by byte and never behind n_bases); rev: u8[n_reads], non-zero where the quality bytes are stored mirrored, or
+// null.  The bases as text (the byte becomes 'N'; nothing behind n_bases is written) or, when words != null, as a packed batch's words
+// (the letter becomes 3) with nbits, the bitmap launch_mark_npos made of its position list (zeroed u16[ceil(n_bases / 16) + 8], 8-byte
+// aligned; never null then), into which the masked positions are ORed, and chunk_count (base_mask_tiles(n_bases) + 1 words): the set bits
+// of every workgroup's 16 384 bases.  read_flag: u32[n_reads], scratch.  work: BM_WORDS device words, indexed by BM_*.
+// 1 <= n_reads <= MAX_BATCH_READS; nothing is indexed out of bounds whatever `offsets` holds.
+enum {
+    BM_READS_MASKED = 0, BM_BASES_MASKED = 1 /* below min_qual and one of ACGTacgt */, BM_ALREADY = 2 /* below min_qual and not */,
+    BM_LISTED = 3 /* packed: the length of the position list behind the mask */, BM_BAD_AT = 4 /* first bad quality byte + 1, or ~0: none */,
+    BM_OFFSETS = 5 /* offsets that do not run from 0 to n_bases, or -- where a read was looked up -- do not ascend */, BM_WORDS = 8
+};
+struct BaseMaskArgs {
+    const uint8_t* qual;
+    uint32_t bias, min_qual;
+    const uint64_t* offsets;
+    const uint8_t* rev;
+    uint64_t n_reads, n_bases;
+    uint8_t* text;
+    uint32_t* words;
+    uint16_t* nbits;
+    uint32_t *read_flag, *chunk_count;
+    unsigned long long* work;
+};
+uint32_t base_mask_tiles(uint64_t n_bases);
+// timer: around base_mask_kernel
+hipError_t launch_base_mask(const BaseMaskArgs& a, hipStream_t stream, KernelTimer timer = {});
+// The positions of the bitmap's set bits, ascending, into out (the first out_cap of them): the scan of the chunk_count launch_base_mask
+// left, then the emit.  chunk_count / chunk_prefix: base_mask_tiles(n_bases) + 1 words each; temp: scan_temp_bytes of as many.
+hipError_t launch_base_mask_emit(const uint16_t* nbits, uint64_t n_bases, uint32_t* chunk_count, uint32_t* chunk_prefix, void* temp, size_t temp_bytes, uint64_t* out,
+    uint64_t out_cap, hipStream_t stream);
+
 // anchor_scan.hip: reads of a resident batch that hold one of the (sorted) anchor k-mers of length A -- every such read once,
 // in any order, appended to `list` (count keeps counting past list_cap).  prefilter: 2^16 bits, bit (kmer & 0xFFFF) set for every
 // anchor; flags: n_reads words, zero before the launch.

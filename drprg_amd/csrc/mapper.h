@@ -141,14 +141,18 @@ public:
         // refuses to screen against any other.
         uint32_t decoy_k = 0, decoy_frac_milli = 0, decoy_min_kmers = 0;
         uint64_t decoy_id = 0;
+        // Base masking (the rule: include/drprg_hip.h "base masking"; base_mask.hip): Q, 1..93 (0: off).  Behind the trim stage, in
+        // front of the decoy screen and the filter; it needs the quality bytes.
+        uint32_t mask_qual = 0;
         bool decoy() const { return decoy_k != 0; }
         bool any_adapters() const { return adapters.n != 0 || front_adapters.n != 0; }
         bool crops() const { return trim_front || trim_tail || trim_qual_milli; } // what drprg_hip_read_trim_info counts
         bool filters() const { return min_len || max_len || min_qual_milli; }
         bool trims() const { return crops() || any_adapters(); }
-        bool any() const { return filters() || trims() || decoy(); }
+        bool any() const { return filters() || trims() || decoy() || mask_qual; }
         bool use_qual() const { return min_qual_milli != 0; }
-        bool wants_qual() const { return min_qual_milli != 0 || trim_qual_milli != 0; } // the ingest carries quality bytes
+        bool wants_qual() const { return min_qual_milli != 0 || trim_qual_milli != 0 || mask_qual != 0; } // the ingest carries quality bytes
+        bool qual_behind_trim() const { return use_qual() || mask_qual != 0; } // the trim stage gathers the trimmed reads' quality bytes
     };
     // (operator+=: a block's outcome added to a running total, count by count)
     struct TrimOutcome { // drprg_hip_read_trim_info
@@ -163,7 +167,12 @@ public:
         uint64_t reads_judged = 0, bases_judged = 0, reads_dropped = 0, bases_dropped = 0, valid = 0, hits = 0;
         DecoyOutcome& operator+=(const DecoyOutcome& o);
     };
+    struct MaskOutcome { // drprg_hip_base_mask_info: the reads and bases behind the cuts, and what the mask made of them
+        uint64_t reads_seen = 0, bases_seen = 0, reads_masked = 0, bases_masked = 0, bases_already_unknown = 0;
+        MaskOutcome& operator+=(const MaskOutcome& o);
+    };
     struct FilterOutcome {
+        MaskOutcome mask;       // (all zero without a base mask)
         DecoyOutcome decoy;     // (all zero without a decoy set)
         TrimOutcome trim;       // (all zero without a crop or a quality trim)
         AdapterOutcome adapter; // (all zero without adapters)
@@ -212,6 +221,14 @@ public:
     // sum of H; res[4]: the offsets do not ascend from 0 to n_bases.  Synchronises `stream`.
     void decoy_screen_device(const ReadFilter& f, const uint8_t* d_text, const uint32_t* d_words, const uint64_t* d_npos, uint64_t n_npos, const uint64_t* d_offsets,
         uint64_t n_reads, uint64_t n_bases, uint32_t* d_valid, uint32_t* d_hits, uint8_t* d_flags, uint64_t res[5], hipStream_t stream);
+    // The mask kernels alone on the caller's device buffers (drprg_hip_base_mask_device): the quality bytes as for read_trim_device, the
+    // bases -- changed in place -- as text (d_words == null) or as packed words with their ascending position list, which is left as it is:
+    // the list behind the mask goes to d_npos_out (may be d_npos's own buffer only if it is no longer needed: it is read first), when it
+    // holds at most npos_cap positions.  res[0..4]: reads seen, bases seen, reads masked, bases masked, bases already unknown; res[5]: the
+    // new list's length; res[6]: first bad quality byte + 1, or 0; res[7]: the offsets do not run from 0 to n_bases.  Synchronises `stream`.
+    void base_mask_device(const ReadFilter& f, const uint8_t* d_qual, uint32_t bias, const uint64_t* d_offsets, const uint8_t* d_rev, uint64_t n_reads,
+        uint64_t n_bases, uint8_t* d_text, uint32_t* d_words, const uint64_t* d_npos, uint64_t n_npos, uint64_t* d_npos_out, uint64_t npos_cap, uint64_t res[8],
+        hipStream_t stream);
     // Reads that stay in HBM (off by default).  keep_reads(max_bytes > 0): from now on map_host_async copies every block into
     // device memory of its own instead of a staging set and leaves it there -- at most max_bytes of it; one byte more and
     // everything kept is dropped and the staging sets are back.  kept_complete(): every read mapped since keep_reads() /
@@ -505,6 +522,13 @@ private:
         DeviceBuffer<uint32_t> k_counts;
         DeviceBuffer<unsigned long long> k_work;
         PinnedBuffer<unsigned long long> k_out;
+        // base masking: one claim word per read, the counts with their pinned mirror, and -- packed blocks, whose bitmap is t_nbits -- the
+        // per-chunk counts of listed positions, their scan and the list behind the mask
+        DeviceBuffer<uint32_t> m_rflag, m_count, m_prefix;
+        DeviceBuffer<unsigned char> m_temp;
+        DeviceBuffer<unsigned long long> m_work;
+        PinnedBuffer<unsigned long long> m_out;
+        DeviceBuffer<uint64_t> m_npos;
     };
     struct Stage {
         FilterScratch filt;
@@ -544,8 +568,15 @@ private:
     DecoyTable decoy_;
     dev::DecoySet decoy_set(const ReadFilter& f) const; // what the kernels are told; refuses settings made for another set
     // V and H of every read of the batch into fs.k_counts, queued on `stream`: a packed batch's bitmap (fs.t_nbits) first
+    // nbits_ready: fs.t_nbits already holds the batch's bitmap (the mask stage left it): it is not made again
     void run_decoy_screen(FilterScratch& fs, const ReadFilter& f, const uint8_t* d_bases, bool packed, const uint64_t* d_npos, uint64_t n_npos,
-        const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases, hipStream_t stream);
+        const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases, hipStream_t stream, bool nbits_ready = false);
+    // Queues the mask on `stream`, in place on these bases: a packed batch's bitmap (fs.t_nbits) is made first and holds the masked
+    // positions too afterwards.  fs.m_out holds dev::BM_* once the stream has been waited for.
+    void run_base_mask(FilterScratch& fs, const ReadFilter& f, const uint8_t* d_qual, uint32_t bias, const uint64_t* d_offsets, const uint8_t* d_rev,
+        uint64_t n_reads, uint64_t n_bases, uint8_t* d_bases, bool packed, const uint64_t* d_npos, uint64_t n_npos, hipStream_t stream);
+    // the list of a packed batch behind the mask, n_list positions, into fs.m_npos from the bitmap (queued on `stream`)
+    void emit_mask_list(FilterScratch& fs, uint64_t n_bases, uint64_t n_list, hipStream_t stream);
     FilterScratch filter_api_; // read_filter_device's and read_trim_device's own (as bam_api_)
     BamScratch bam_api_; // pack_bam_on_device's own (the caller's stream is not ordered with the context's)
     uint64_t bam_blocks_ = 0;
@@ -577,6 +608,10 @@ private:
         uint64_t take, n_reads, n_bases;
     };
     bool trim_block(const HostBatch& hb, const ReadFilter& f, Stage& st, DeviceBatch& src, const uint8_t*& d_qual, uint32_t& trim_err, FilterOutcome& o);
+    // mask_block queues the mask in place on the block the trim stage left; its counts come with filter_block's read-back, which hands
+    // them to mask_done: the outcome, the refusals, and -- a packed block whose list changed -- `src`'s list REPLACED by the one behind the mask
+    void mask_block(const HostBatch& hb, const ReadFilter& f, Stage& st, const DeviceBatch& src, const uint8_t* d_qual);
+    void mask_done(const HostBatch& hb, Stage& st, DeviceBatch& src, FilterOutcome& o);
     void filter_block(const HostBatch& hb, const ReadFilter& f, FilterScratch& fs, const DeviceBatch& src, const uint8_t* d_qual, const uint32_t& trim_err,
         FilterOutcome& o);
     KeptPart cut_at_cap(FilterScratch& fs, uint64_t n_reads, uint64_t cap_need, FilterOutcome& o);

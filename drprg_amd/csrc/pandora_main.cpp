@@ -29,6 +29,7 @@
 
 #include "adapter_args.h"
 #include "decoy_args.h"
+#include "mask_args.h"
 
 namespace {
 
@@ -63,6 +64,7 @@ struct Args {
     // --trim-front N, --trim-tail N, --trim-qual Q, --trim-window W: read trimming (include/drprg_hip.h "read trimming"); 0 = not set
     uint64_t trim_front = 0, trim_tail = 0;
     uint32_t trim_qual_milli = 0, trim_window = 0;
+    uint32_t mask_qual = 0; // --mask-qual Q: base masking (include/drprg_hip.h "base masking"); 0 = not set
     drprg::AdapterArgs adapters; // --adapter SEQ, --adapter-error E, --adapter-min-overlap O (include/drprg_hip.h "adapter trimming")
     drprg::DecoyArgs decoy; // --decoy FASTA, --decoy-k K, --decoy-min-frac F, --decoy-min-kmers M (include/drprg_hip.h "decoy screen")
     std::string outdir = "pandora", vcf_refs;
@@ -85,7 +87,7 @@ void usage()
         "                   [--dedup] [--min-read-len L] [--max-read-len L] [--min-read-qual Q]\n"
         "                   [--trim-front N] [--trim-tail N] [--trim-qual Q [--trim-window W]]\n"
         "                   [--adapter SEQ]... [--adapter-error E] [--adapter-min-overlap O] [--adapter-indels] [--front-adapter SEQ]...\n"
-        "                   [--decoy FASTA]... [--decoy-k K] [--decoy-min-frac F] [--decoy-min-kmers M]\n"
+        "                   [--mask-qual Q] [--decoy FASTA]... [--decoy-k K] [--decoy-min-frac F] [--decoy-min-kmers M]\n"
         "                   [--vcf-refs FASTA] [-t N] [-w W] [-k K] [-c N] [-I] [-K] [-e RATE] [--max-diff N] <prg> <reads>\n"
         "  pandora discover [same mapping options] <prg> <query.tsv>\n"
         "  --max-covg N: reads are taken in file order up to and including the first one at which (N + 1) x SIZE bases are reached;\n"
@@ -117,13 +119,18 @@ void usage()
         "  --adapter-indels: an occurrence may carry insertions and deletions too (edit distance at most floor(m * E) over the whole adapter).\n"
         "  --front-adapter SEQ (up to 4 times; needs --adapter-indels): 5' adapters, cut off the reads' starts behind the 3' cut.\n"
         "                Still missing: anchored adapters, pair overlap, indels inside an adapter that the read's end cuts short.\n"
+        "  --mask-qual Q (a whole Phred value, 1 to 93): every base whose quality is below Q becomes an unknown base -- on the device, behind\n"
+        "                --trim-* and --adapter and in front of everything else: the run is that of a file in which those bases are the letter N.\n"
+        "                The read keeps its length, its place in the depth arithmetic and its mean quality; only the k-mers that hold a masked\n"
+        "                base stop existing.  Needs qualities: FASTA, or a BAM record without them, is an error under it.  A threshold on what the\n"
+        "                basecaller claims: at Nanopore qualities a Q of 10 or more leaves few 15-mers.  Default: off.\n"
         "  --decoy FASTA (up to 8 times; plain or .gz), --decoy-k K (9 to 31, default 31), --decoy-min-frac F (in (0, 1], default 0.5),\n"
         "                --decoy-min-kmers M (default 1): a read is dropped as a contaminant when at least M of its k-mers, and at least the\n"
         "                fraction F of its k-mers without a letter other than ACGT, are k-mers of the decoy files in either orientation -- on\n"
         "                the device, behind --trim-*, --adapter and --min/max-read-*: the run is that of a file of the kept reads.  This\n"
         "                build's own rule (k-mer containment, as bbduk ref=); sized for mitochondrion, NTM genomes, phiX, not a human genome.\n"
         "  <reads>: FASTA or FASTQ, plain or gzip; or BAM (secondary and supplementary records are skipped, reverse-strand records are\n"
-        "           reverse-complemented, alignments are ignored, qualities are looked at by --min-read-qual and --trim-qual alone)\n"
+        "           reverse-complemented, alignments are ignored, qualities are looked at by --min-read-qual, --trim-qual and --mask-qual alone)\n"
         "environment: DRPRG_HIP_DEVICE selects the GPU (default 0); DRPRG_HIP_DEVICES=0,1,.. maps on several GPUs of the node\n");
 }
 
@@ -190,6 +197,10 @@ Args parse(int argc, char** argv)
             const uint64_t n = std::strtoull(v, &end, 10);
             if (end == v || *end || n < 1 || n > 32) die(std::string("--trim-window needs a window of 1 to 32 bases, not ") + v, 2);
             a.trim_window = (uint32_t)n;
+        }
+        else if (s == "--mask-qual") {
+            const std::string e = drprg::parse_mask_qual(need(i), a.mask_qual);
+            if (!e.empty()) die(e, 2);
         }
         else if (s == "--adapter") {
             const std::string e = a.adapters.add(need(i));
@@ -291,6 +302,7 @@ drprg_hip_ctx* open_ctx(const Args& a)
     if (int rc = drprg_hip_set_max_covg(ctx, a.max_covg)) die(drprg_hip_last_error(ctx), -rc);
     if (int rc = drprg_hip_set_read_filter(ctx, a.min_read_len, a.max_read_len, a.min_read_qual_milli)) die(drprg_hip_last_error(ctx), -rc);
     if (int rc = drprg_hip_set_read_trim(ctx, a.trim_front, a.trim_tail, a.trim_qual_milli, a.trim_window)) die(drprg_hip_last_error(ctx), -rc);
+    if (int rc = drprg_hip_set_base_mask(ctx, a.mask_qual)) die(drprg_hip_last_error(ctx), -rc);
     if (a.adapters.any()) {
         if (int rc = a.adapters.set_on(ctx, drprg_hip_set_adapters, drprg_hip_set_adapters2)) die(drprg_hip_last_error(ctx), -rc);
     }
@@ -345,7 +357,8 @@ std::string run_tag(const Args& a, const std::string& reads)
                   + std::to_string((unsigned long long)a.trim_tail) + "/" + std::to_string(a.trim_qual_milli) + "/"
                   + std::to_string(a.trim_qual_milli ? (a.trim_window ? a.trim_window : 4u) : 0u)
                                                             : std::string())
-        + (a.adapters.any() ? a.adapters.tag() : std::string()) + (a.decoy.any() ? a.decoy.tag() : std::string());
+        + (a.adapters.any() ? a.adapters.tag() : std::string()) + (a.mask_qual ? "|B" + std::to_string(a.mask_qual) : std::string())
+        + (a.decoy.any() ? a.decoy.tag() : std::string());
 }
 
 // The reads stay in HBM after the mapping pass: up to DRPRG_HIP_KEEP_READS_GB per device, default 32, 0 = off.  --subsample-covg and --dedup work on
@@ -419,6 +432,9 @@ void report_filter(drprg_hip_ctx* ctx, const Args& a)
     if (a.verbose && !a.adapters.front.empty() && drprg_hip_front_adapter_info(ctx, fi) == 0)
         std::printf("[pandora-hip] front adapter trimming: reads_seen=%llu bases_seen=%llu reads_cut=%llu bases_cut=%llu reads_emptied=%llu\n", (unsigned long long)fi[0],
             (unsigned long long)fi[1], (unsigned long long)fi[2], (unsigned long long)fi[3], (unsigned long long)fi[4]);
+    if (a.verbose && a.mask_qual && drprg_hip_base_mask_info(ctx, fi) == 0)
+        std::printf("[pandora-hip] base masking: reads_seen=%llu bases_seen=%llu reads_masked=%llu bases_masked=%llu bases_already_unknown=%llu\n",
+            (unsigned long long)fi[0], (unsigned long long)fi[1], (unsigned long long)fi[2], (unsigned long long)fi[3], (unsigned long long)fi[4]);
     if (a.verbose && a.decoy.any() && drprg_hip_decoy_info(ctx, fi) == 0)
         std::printf("[pandora-hip] decoy screen: kmers=%llu reads_seen=%llu bases_seen=%llu reads_dropped=%llu bases_dropped=%llu\n", (unsigned long long)fi[0],
             (unsigned long long)fi[2], (unsigned long long)fi[3], (unsigned long long)fi[4], (unsigned long long)fi[5]);

@@ -1,5 +1,5 @@
 // read_prep.cpp -- what happens to a host block before it is mapped: staging sets and the copies into them, the read filter, read
-// trimming, adapter trimming and the decoy screen with their drivers, and the packers of the harness path.  See mapper.h.
+// trimming, adapter trimming, base masking and the decoy screen with their drivers, and the packers of the harness path.  See mapper.h.
 #include "mapper.h"
 #include <algorithm>
 #include <hip/hip_runtime.h>
@@ -103,6 +103,7 @@ void Mapper::only_empty_reads(uint64_t n_reads, const ReadFilter& f, bool keepin
 {
     o.dropped_short = f.min_len ? n_reads : 0;
     o.reads_kept = o.mapped_reads = n_reads - o.dropped_short;
+    if (f.mask_qual) o.mask.reads_seen = n_reads; // (no base: nothing to mask)
     if (f.decoy()) o.decoy.reads_judged = o.reads_kept; // (no window, no hit: the screen keeps them)
     count_unmapped(o.reads_kept, keeping);
 }
@@ -394,13 +395,14 @@ void Mapper::decoy_lookup(const std::vector<uint64_t>& kmers, uint8_t* found)
 }
 
 void Mapper::run_decoy_screen(FilterScratch& fs, const ReadFilter& f, const uint8_t* d_bases, bool packed, const uint64_t* d_npos, uint64_t n_npos,
-    const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases, hipStream_t stream)
+    const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases, hipStream_t stream, bool nbits_ready)
 {
     const dev::DecoySet d = decoy_set(f);
     grow(fs.k_counts, 2 * n_reads);
     dev::DecoyScreenArgs a { packed ? nullptr : d_bases, packed ? reinterpret_cast<const uint32_t*>(d_bases) : nullptr, nullptr, d_offsets, n_reads, n_bases,
         fs.k_counts.data(), fs.k_counts.data() + n_reads };
-    if (packed && n_npos) { // the position list as a bitmap, as adapter_points makes it
+    if (packed && nbits_ready) a.nbits = fs.t_nbits.data();
+    else if (packed && n_npos) { // the position list as a bitmap, as adapter_points makes it
         const uint64_t n16 = (n_bases + 15) / 16 + 8;
         grow(fs.t_nbits, n16);
         HIPCHK(hipMemsetAsync(fs.t_nbits.data(), 0, n16 * sizeof(uint16_t), stream));
@@ -430,6 +432,59 @@ void Mapper::decoy_screen_device(const ReadFilter& f, const uint8_t* d_text, con
     if (d_hits) HIPCHK(hipMemcpyAsync(d_hits, fs.k_counts.data() + n_reads, n_reads * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
     HIPCHK(hipStreamSynchronize(stream));
     for (int i = 0; i < 5; ++i) res[i] = fs.k_out[i];
+}
+
+// ---- base masking --------------------------------------------------------------------------------------------------------------------
+void Mapper::run_base_mask(FilterScratch& fs, const ReadFilter& f, const uint8_t* d_qual, uint32_t bias, const uint64_t* d_offsets, const uint8_t* d_rev,
+    uint64_t n_reads, uint64_t n_bases, uint8_t* d_bases, bool packed, const uint64_t* d_npos, uint64_t n_npos, hipStream_t stream)
+{
+    grow(fs.m_rflag, n_reads);
+    if (!fs.m_work) fs.m_work.alloc(dev::BM_WORDS);
+    if (!fs.m_out) fs.m_out.alloc(dev::BM_WORDS);
+    dev::BaseMaskArgs a {};
+    a.qual = d_qual; a.bias = bias; a.min_qual = f.mask_qual; a.offsets = d_offsets; a.rev = d_rev; a.n_reads = n_reads; a.n_bases = n_bases;
+    a.read_flag = fs.m_rflag.data(); a.work = fs.m_work.data();
+    if (packed) { // the position list as a bitmap, as adapter_points makes it: always, because the mask writes into it
+        const uint64_t n16 = (n_bases + 15) / 16 + 8, chunks = (uint64_t)dev::base_mask_tiles(n_bases) + 1;
+        grow(fs.t_nbits, n16);
+        grow(fs.m_count, chunks);
+        grow(fs.m_prefix, chunks);
+        grow(fs.m_temp, dev::scan_temp_bytes((uint32_t)chunks));
+        HIPCHK(hipMemsetAsync(fs.t_nbits.data(), 0, n16 * sizeof(uint16_t), stream));
+        HIPCHK(dev::launch_mark_npos(d_npos, n_npos, n_bases, fs.t_nbits.data(), stream));
+        a.words = reinterpret_cast<uint32_t*>(d_bases); a.nbits = fs.t_nbits.data(); a.chunk_count = fs.m_count.data();
+    } else a.text = d_bases;
+    HIPCHK(dev::launch_base_mask(a, stream));
+    HIPCHK(hipMemcpyAsync(fs.m_out.data(), fs.m_work.data(), dev::BM_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+}
+
+void Mapper::emit_mask_list(FilterScratch& fs, uint64_t n_bases, uint64_t n_list, hipStream_t stream)
+{
+    grow(fs.m_npos, n_list, n_list + n_list / 4 + 16);
+    HIPCHK(dev::launch_base_mask_emit(fs.t_nbits.data(), n_bases, fs.m_count.data(), fs.m_prefix.data(), fs.m_temp.data(), fs.m_temp.size(), fs.m_npos.data(), n_list,
+        stream));
+}
+
+void Mapper::base_mask_device(const ReadFilter& f, const uint8_t* d_qual, uint32_t bias, const uint64_t* d_offsets, const uint8_t* d_rev, uint64_t n_reads,
+    uint64_t n_bases, uint8_t* d_text, uint32_t* d_words, const uint64_t* d_npos, uint64_t n_npos, uint64_t* d_npos_out, uint64_t npos_cap, uint64_t res[8],
+    hipStream_t stream)
+{
+    for (int i = 0; i < 8; ++i) res[i] = 0;
+    if (!f.mask_qual) throw Error(DRPRG_EINVAL, "base masking: no quality is set (drprg_hip_set_base_mask)");
+    if (n_reads == 0) return;
+    stream = device_entry(stream, !d_offsets || (n_bases && (!d_qual || (!d_text && !d_words))) || (n_npos && !d_npos), n_reads);
+    FilterScratch& fs = filter_api_;
+    run_base_mask(fs, f, d_qual, bias, d_offsets, d_rev, n_reads, n_bases, d_words ? reinterpret_cast<uint8_t*>(d_words) : d_text, d_words != nullptr, d_npos, n_npos,
+        stream);
+    HIPCHK(hipStreamSynchronize(stream));
+    const unsigned long long* h = fs.m_out.data();
+    res[0] = n_reads; res[1] = n_bases; res[2] = h[dev::BM_READS_MASKED]; res[3] = h[dev::BM_BASES_MASKED]; res[4] = h[dev::BM_ALREADY];
+    res[5] = d_words ? h[dev::BM_LISTED] : 0;
+    res[6] = h[dev::BM_BAD_AT] == ~0ull ? 0 : h[dev::BM_BAD_AT];
+    res[7] = h[dev::BM_OFFSETS];
+    if (res[6] || res[7] || !res[5] || res[5] > npos_cap || !d_npos_out) return;
+    HIPCHK(dev::launch_base_mask_emit(fs.t_nbits.data(), n_bases, fs.m_count.data(), fs.m_prefix.data(), fs.m_temp.data(), fs.m_temp.size(), d_npos_out, npos_cap, stream));
+    HIPCHK(hipStreamSynchronize(stream));
 }
 
 // ---- a host block behind the filter: map_host_filtered and its steps ---------------------------------------------------------------------
@@ -472,13 +527,13 @@ bool Mapper::trim_block(const HostBatch& hb, const ReadFilter& f, Stage& st, Dev
     const uint64_t payload = src.packed ? (nb + 15) / 16 * 4 : nb;
     grow(fs.t_bases, payload + 64);
     if (n_list) grow(fs.t_npos, n_list);
-    if (f.use_qual()) grow(fs.t_qual, nb + 64);
+    if (f.qual_behind_trim()) grow(fs.t_qual, nb + 64);
     if (src.packed) grow(fs.t_src, n_reads);
     if (!src.packed) grow(fs.t_btable, n_reads);
-    if (f.use_qual()) grow(fs.t_qtable, n_reads);
+    if (f.qual_behind_trim()) grow(fs.t_qtable, n_reads);
     uint32_t* const d_err = reinterpret_cast<uint32_t*>(fs.t_work.data() + dev::RT_KEPT_NPOS); // (zeroed with the trim's words, unused on the device)
     dev::ReadTrimFill tf { src.d_offsets, d_rev, fs.t_begin.data(), fs.t_end.data(), fs.t_offsets.data(), n_reads, n_bases, nb, src.d_bases, d_qual,
-        src.packed ? fs.t_src.data() : nullptr, src.packed ? nullptr : fs.t_btable.data(), f.use_qual() ? fs.t_qtable.data() : nullptr, d_err };
+        src.packed ? fs.t_src.data() : nullptr, src.packed ? nullptr : fs.t_btable.data(), f.qual_behind_trim() ? fs.t_qtable.data() : nullptr, d_err };
     HIPCHK(dev::launch_read_trim_fill(tf, cs));
     HIPCHK(hipMemsetAsync(fs.t_bases.data() + payload, 0, 64, cs));
     if (src.packed) { // (by ranges, not by flags: the one pack launch outside compact_block)
@@ -489,7 +544,7 @@ bool Mapper::trim_block(const HostBatch& hb, const ReadFilter& f, Stage& st, Dev
             HIPCHK(dev::launch_read_trim_npos_emit(tf, np, fs.t_npos.data(), n_list, cs));
         }
     } else HIPCHK(dev::launch_gather_reads(fs.t_btable.data(), (uint32_t)n_reads, fs.t_bases.data(), cs));
-    if (f.use_qual()) {
+    if (f.qual_behind_trim()) { // (the filter's threshold, or the mask: either sees the trimmed reads' bytes, in stored order beside d_rev)
         HIPCHK(dev::launch_gather_reads(fs.t_qtable.data(), (uint32_t)n_reads, fs.t_qual.data(), cs));
         HIPCHK(hipMemsetAsync(fs.t_qual.data() + nb, 0, 64, cs));
         d_qual = fs.t_qual.data();
@@ -503,13 +558,39 @@ bool Mapper::trim_block(const HostBatch& hb, const ReadFilter& f, Stage& st, Dev
     return true;
 }
 
+// The mask, queued in place on the block the trim stage left -- the staging copy or the trim stage's compacted copy, never the caller's
+// memory.  No wait of its own: its eight words arrive with the filter's read-back.
+void Mapper::mask_block(const HostBatch& hb, const ReadFilter& f, Stage& st, const DeviceBatch& src, const uint8_t* d_qual)
+{
+    const uint8_t* d_rev = hb.bam && hb.reverse ? st.d_reverse.data() : nullptr; // (as the trim stage: QUAL stays in stored order)
+    run_base_mask(st.filt, f, d_qual, hb.qual_bias, src.d_offsets, d_rev, src.n_reads, src.n_bases, const_cast<uint8_t*>(src.d_bases), src.packed, src.d_npos, src.n_npos,
+        copy_stream_);
+}
+
+void Mapper::mask_done(const HostBatch& hb, Stage& st, DeviceBatch& src, FilterOutcome& o)
+{
+    FilterScratch& fs = st.filt;
+    const unsigned long long* h = fs.m_out.data();
+    if (h[dev::BM_OFFSETS]) throw Error(DRPRG_EINVAL, "base masking: the block's offsets do not ascend to its number of bases");
+    if (h[dev::BM_BAD_AT] != ~0ull) throw bad_quality_error(h[dev::BM_BAD_AT], src.n_bases, hb.qual_bias);
+    o.mask = MaskOutcome { src.n_reads, src.n_bases, h[dev::BM_READS_MASKED], h[dev::BM_BASES_MASKED], h[dev::BM_ALREADY] };
+    if (!src.packed || !h[dev::BM_BASES_MASKED]) return; // (text, or no position joined the list: a base that was unknown already is listed)
+    emit_mask_list(fs, src.n_bases, h[dev::BM_LISTED], copy_stream_);
+    // (queued behind the filter's wait: a block that is mapped where it lies meets no other wait, so the mapping stream is told)
+    HIPCHK(hipEventRecord(st.copied, copy_stream_));
+    HIPCHK(hipStreamWaitEvent(stream_, st.copied, 0));
+    src.d_npos = fs.m_npos.data();
+    src.n_npos = h[dev::BM_LISTED];
+}
+
 // The filter on the block as the trim stage left it, with its read-back: the caller's block is free again when this returns.
 void Mapper::filter_block(const HostBatch& hb, const ReadFilter& f, FilterScratch& fs, const DeviceBatch& src, const uint8_t* d_qual, const uint32_t& trim_err,
     FilterOutcome& o)
 {
     const hipStream_t cs = copy_stream_;
     // (the screen in front of the filter's scans, which then see one verdict: the block as the trim stage left it, whatever its form)
-    if (f.decoy()) run_decoy_screen(fs, f, src.d_bases, src.packed, src.d_npos, src.n_npos, src.d_offsets, src.n_reads, src.n_bases, cs);
+    // (behind the mask a packed block's bitmap is there already, and holds the masked positions, which the list does not yet)
+    if (f.decoy()) run_decoy_screen(fs, f, src.d_bases, src.packed, src.d_npos, src.n_npos, src.d_offsets, src.n_reads, src.n_bases, cs, f.mask_qual != 0);
     run_read_filter(fs, f, d_qual, hb.qual_bias, src.d_offsets, src.n_reads, src.n_bases, fs.d_qsum.data(), fs.d_flag.data(), cs, f.decoy());
     HIPCHK(hipStreamSynchronize(cs));
     if (trim_err) throw Error(DRPRG_EIO, "read trimming: the block's offsets and the trimmed ranges do not fit each other");
@@ -606,6 +687,7 @@ void Mapper::map_host_filtered(const HostBatch& hb, const ReadFilter& f, uint64_
         return;
     }
     if (f.trim_qual_milli && !hb.qual) throw Error(DRPRG_EINVAL, "--trim-qual: the reads came without base qualities");
+    if (f.mask_qual && !hb.qual) throw Error(DRPRG_EINVAL, "--mask-qual: the reads came without base qualities");
     if (f.use_qual() && !hb.qual) throw Error(DRPRG_EINVAL, "--min-read-qual: the reads came without base qualities");
     if (n_reads > dev::MAX_BATCH_READS) throw Error(DRPRG_EOVERFLOW, "at most " + std::to_string(dev::MAX_BATCH_READS) + " reads per batch");
     // 1. copy in: the block into a staging set, its quality bytes beside it
@@ -622,13 +704,15 @@ void Mapper::map_host_filtered(const HostBatch& hb, const ReadFilter& f, uint64_
     }
     const uint8_t* d_qual = fs.d_qual.data();
     uint32_t trim_err = 0;
-    // 2. trim, 3. filter, 4. the depth cap
+    // 2. trim, 3. mask, 4. filter, 5. the depth cap
     if (f.trims() && !trim_block(hb, f, st, src, d_qual, trim_err, o)) { // reads of no bases are left: nothing to map
         hand_back_stage();
         only_empty_reads(n_reads, f, keeping, o);
         return;
     }
+    if (f.mask_qual) mask_block(hb, f, st, src, d_qual);
     filter_block(hb, f, fs, src, d_qual, trim_err, o);
+    if (f.mask_qual) mask_done(hb, st, src, o); // (the block's list is the one behind the mask before the block is placed)
     const KeptPart k = cut_at_cap(fs, n_reads, cap_need, o);
     o.mapped_reads = k.n_reads;
     o.mapped_bases = k.n_bases;
@@ -637,7 +721,7 @@ void Mapper::map_host_filtered(const HostBatch& hb, const ReadFilter& f, uint64_
         count_unmapped(k.n_reads, keeping);
         return;
     }
-    // 5. place, 6. map
+    // 6. place, 7. map
     const DeviceBatch cur = place_block(fs, src, k, keeping);
     if (keeping) {
         resident_.add(cur, k.n_reads);
@@ -658,6 +742,13 @@ Mapper::AdapterOutcome& Mapper::AdapterOutcome::operator+=(const AdapterOutcome&
     return *this;
 }
 
+Mapper::MaskOutcome& Mapper::MaskOutcome::operator+=(const MaskOutcome& o)
+{
+    reads_seen += o.reads_seen; bases_seen += o.bases_seen; reads_masked += o.reads_masked; bases_masked += o.bases_masked;
+    bases_already_unknown += o.bases_already_unknown;
+    return *this;
+}
+
 Mapper::DecoyOutcome& Mapper::DecoyOutcome::operator+=(const DecoyOutcome& o)
 {
     reads_judged += o.reads_judged; bases_judged += o.bases_judged; reads_dropped += o.reads_dropped; bases_dropped += o.bases_dropped;
@@ -667,6 +758,7 @@ Mapper::DecoyOutcome& Mapper::DecoyOutcome::operator+=(const DecoyOutcome& o)
 
 Mapper::FilterOutcome& Mapper::FilterOutcome::operator+=(const FilterOutcome& o)
 {
+    mask += o.mask;
     decoy += o.decoy;
     trim += o.trim; adapter += o.adapter; front += o.front;
     reads_seen += o.reads_seen; bases_seen += o.bases_seen; dropped_short += o.dropped_short; dropped_long += o.dropped_long;

@@ -337,6 +337,32 @@ class Context:
                                                   stream), self._h)
         return tuple(int(x) for x in out)
 
+    # ---- base masking (include/drprg_hip.h: drprg_hip_set_base_mask) ---------------------------
+    def set_base_mask(self, min_qual=0):
+        """from the next map_fastx on, every base whose Phred quality is below min_qual (a whole number, 1..93) becomes an unknown base on
+        the device, behind the trim stage and in front of everything else: the run is that of a file with N in its place; 0 clears it"""
+        if int(min_qual) != min_qual:
+            raise ValueError(f"a base quality is a whole number from 0 to 93, not {min_qual!r}")
+        _check(lib.drprg_hip_set_base_mask(self._h, int(min_qual)), self._h)
+
+    def base_mask_info(self):
+        out = (C.c_uint64 * 5)()
+        _check(lib.drprg_hip_base_mask_info(self._h, out), self._h)
+        names = ("reads_seen", "bases_seen", "reads_masked", "bases_masked", "bases_already_unknown")
+        return dict(zip(names, (int(x) for x in out)))
+
+    def base_mask_device(self, d_qual, qual_bias, d_offsets, d_rev, n_reads, n_bases, d_text, d_words, d_npos, n_npos, d_npos_out, npos_cap, stream=None):
+        """the mask kernels alone on device buffers (addresses as integers), in place: the bases as text (d_words None) or as packed words
+        (d_text None) with their ascending position list, which is only read; d_npos_out (u64 x npos_cap) receives the list behind the
+        mask; d_rev may be None.  Returns (reads seen, bases seen, reads masked, bases masked, bases already unknown, new list length) --
+        and raises with code -75 when npos_cap is too small, -84 for a quality byte out of range; last_mask_out holds the six words then"""
+        out = (C.c_uint64 * 6)()
+        rc = lib.drprg_hip_base_mask_device(self._h, d_qual, int(qual_bias), d_offsets, d_rev, int(n_reads), int(n_bases), d_text, d_words, d_npos, int(n_npos),
+                                            d_npos_out, int(npos_cap), out, stream)
+        self.last_mask_out = tuple(int(x) for x in out)
+        _check(rc, self._h)
+        return self.last_mask_out
+
     # ---- decoy screen (include/drprg_hip.h: drprg_hip_set_decoy) -------------------------------
     @staticmethod
     def frac_milli(frac):

@@ -567,6 +567,47 @@ int drprg_hip_decoy_info(drprg_hip_ctx* ctx, uint64_t out[8]);
 int drprg_hip_decoy_lookup(drprg_hip_ctx* ctx, const uint64_t* kmers, uint64_t n, uint8_t* found);
 int drprg_hip_decoy_screen_device(drprg_hip_ctx* ctx, const void* d_text, const void* d_words, const void* d_npos, uint64_t n_npos, const void* d_offsets,
     uint64_t n_reads, uint64_t n_bases, void* d_valid, void* d_hits, void* d_flags, uint64_t out[4], void* hip_stream);
+/* ---- Base masking: low-quality bases made unknown on the device, as the reads arrive.  THIS BUILD'S OWN RULE: the switch every pile-up
+ * caller has (samtools mpileup -Q, GATK's minimum base quality) and the k-mer tools have as a quality cut-off (Cortex, mccortex, Jellyfish);
+ * neither pandora nor drprg has one and nothing in them pins it.
+ *   Setting, per context: Q, an integer in 1..93 (0: off, the default).
+ *   The rule.  A base whose Phred quality is below Q becomes an unknown base; a base of quality Q or more is untouched, whatever it is.  The
+ *   run is exactly that of a file in which those bases are the letter N and everything else -- the quality bytes included -- is unchanged.
+ *   The read keeps its length: its bases keep counting towards the expected depth, the depth cap and the random subsample's target, and
+ *   its mean error probability under the read filter is what it was.  Only the k-mers that hold a masked base stop existing.
+ *   Qualities.  The FASTQ line's byte - 33, or BAM's QUAL byte.  A reverse-strand BAM record's QUAL stays in stored order while its bases
+ *   are reversed on the device: base p of a read of L bases is judged by quality byte L - 1 - p.  A byte outside 0..93 fails the run
+ *   (-EFORMAT, -84), as under the other quality settings.
+ *   Order.  Masking runs in drprg_hip_map_fastx, per ingest block, on the device that takes the block, BEHIND the trim stage (crops, quality
+ *   trim, 3' and 5' adapters: adapters are compared as letters, and a masked base would differ from every letter) and IN FRONT OF the decoy
+ *   screen (its V and H are those of the masked read), the read filter and everything behind it: mapping, the resident set,
+ *   drprg_hip_dedup (where any non-ACGT base is one masked base), drprg_hip_select_reads and discover from HBM, drprg_hip_map_resident and
+ *   the genotyper see the masked reads, whatever the thread count, the block boundaries and the input form (FASTQ, .gz, BAM; ASCII or packed
+ *   transport).  The block is changed in its staging copy, or in the trim stage's compacted copy; the caller's memory never is.  A packed
+ *   block's 2-bit letter becomes 3 (bits 2:1 of 'N') and the position joins the block's ascending list of non-ACGT positions, without a
+ *   duplicate where the base was unknown already: word for word and position for position the block the file with N would have given.
+ *   Masking needs qualities: a FASTA record, or a BAM record whose QUAL starts with 0xFF, fails drprg_hip_map_fastx with -EINVAL and a text
+ *   that names --mask-qual (when --trim-qual is set too it is named instead: the first setting to miss them).  drprg_hip_map_host* and
+ *   drprg_hip_map_device* carry no qualities and return -EINVAL while Q != 0.  Once a base of a sample that is not resident was masked,
+ *   drprg_hip_discover_reads returns -ENODATA (-61).  With Q == 0 nothing of this exists: no quality byte is parsed, copied or moved on its
+ *   account, no launch, no wait, no allocation.
+ *   Limits.  Masking is a threshold on what the basecaller claims, no more.  At Nanopore qualities a Q of 10 or more masks so many bases that
+ *   few 15-mers survive.  No claim about real samples is made: none were run.
+ *   drprg_hip_set_base_mask: applies from the next drprg_hip_map_fastx, on every device of the context; a reset keeps it.  -EINVAL above 93.
+ *   drprg_hip_base_mask_info: since the last reset, out[0..4] = reads seen and bases seen by the stage (behind the cuts), reads with at least
+ *     one masked base, bases below Q that were one of ACGTacgt (masked), bases below Q that were not (already unknown).
+ *   drprg_hip_base_mask_device: the mask kernels alone on caller-owned device buffers, under the context's Q (-EINVAL when it is 0).  d_qual,
+ *     qual_bias, d_offsets, d_rev: as drprg_hip_read_trim_device takes them (d_qual readable for 64 bytes behind n_bases when it is 16-byte
+ *     aligned; any other address is read byte by byte).  The bases are changed IN PLACE: d_text (n_bases bytes; nothing behind them is
+ *     written) or d_words (u32[ceil(n_bases / 16)]) with d_npos / n_npos, the ascending list of its non-ACGT positions, which is only
+ *     read.  d_npos_out: u64[npos_cap], receives the list behind the mask, ascending.  out[0..4]: the five counts above; out[5]: the new
+ *     list's length (0 for text).  -EOVERFLOW when npos_cap is smaller than that -- out[5] still says what is needed, the words are masked,
+ *     nothing is written to d_npos_out.  -EFORMAT for a quality byte outside 0..93, the text naming its position; -EINVAL when the offsets do not run from 0 to n_bases.
+ *     Synchronises the stream. */
+int drprg_hip_set_base_mask(drprg_hip_ctx* ctx, uint32_t min_qual);
+int drprg_hip_base_mask_info(drprg_hip_ctx* ctx, uint64_t out[5]);
+int drprg_hip_base_mask_device(drprg_hip_ctx* ctx, const void* d_qual, uint32_t qual_bias, const void* d_offsets, const void* d_rev, uint64_t n_reads,
+    uint64_t n_bases, void* d_text, void* d_words, const void* d_npos, uint64_t n_npos, void* d_npos_out, uint64_t npos_cap, uint64_t out[6], void* hip_stream);
 /* The read selection drprg_hip_discover_reads uses when the reads are resident, on its own: for every device of the context, in order,
  * every kept read in which a k-mer of `anchors` STARTS (anchors: n_anchors k-mers of A bases, 2 bits per base, A 0 C 1 G 2 T 3, first base
  * in the high bits; any order, duplicates allowed).  A block's reads are one base stream: read r of a block is returned iff for some p with
