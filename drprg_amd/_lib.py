@@ -119,7 +119,15 @@ SIGNATURES = {
     "drprg_hip_base_mask_info": (C.c_int, [C.c_void_p, C.c_void_p]),
     "drprg_hip_base_mask_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
-    "drprg_hip_set_decoy": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "drprg_hip_set_poly_trim": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint32]),
+    "drprg_hip_poly_trim_info": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "drprg_hip_poly_trim_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p]),
+    "drprg_hip_set_min_complexity": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "drprg_hip_complexity_info": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "drprg_hip_complexity_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p]),
+    "drprg_hip_set_decoy":(C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     "drprg_hip_decoy_info": (C.c_int, [C.c_void_p, C.c_void_p]),
     "drprg_hip_decoy_lookup": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "drprg_hip_decoy_screen_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,

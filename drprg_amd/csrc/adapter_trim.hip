@@ -6,7 +6,8 @@
 // adapter_points_kernel is a segmented leftmost-match search over the batch's concatenated bases.  The BUFFER is tiled, not the reads --
 // 16 384 bases per workgroup, as trim_points_kernel tiles the quality bytes --, so 150-base reads and 50 kb reads run the same code.  A lane
 // takes 16 starts per round, four rounds: one word of 2-bit letters and a 16-bit mask of the bases that are not ACGT, made of 16 text bytes
-// in registers (ad_text16) or loaded as they lie (a packed block's words, and the bitmap launch_mark_npos makes of its position list).
+// in registers (ad_text16) or loaded as they lie (a packed block's words, and the bitmap launch_mark_npos makes of its position list):
+// load16_common, load16.h.
 // Behind the load there is one code path.  The up to 63 bases behind a lane's own come by shuffle from the next four lanes, on the last
 // lanes of a wave from memory -- never from behind the buffer: a word whose first base is not below n_bases is not loaded, and what a
 // window holds behind its read's range is masked off before it is counted (ad_match, adapter_piece.h: host code as well).  Per start and
@@ -22,6 +23,7 @@
 //
 // adapter_apply_kernel: one thread per read -- end = begin + cut, the new length, and the counts.
 #include "adapter_piece.h"
+#include "load16.h"
 #include "search.h"
 
 namespace drprg {
@@ -46,30 +48,7 @@ __device__ inline void ad_put(AdLds& s, uint32_t* __restrict__ gcut, uint64_t n_
     else atomicMin(&gcut[read], cut);
 }
 
-// The 16 bases from base p on (p a multiple of 16) in the common form.  A word whose first base is not below n_bases is not loaded: it
-// reads as sixteen bases that match nothing.  Text at an address that is not 16-byte aligned is read byte by byte and never behind n_bases
-// (such a buffer promises no padding); aligned text has its 64 bytes, so the 16 bytes at p < n_bases are readable.
-__device__ inline void ad_load16(const AdapterPoints& a, bool aligned, uint64_t p, uint32_t& code, uint32_t& nmask)
-{
-    code = 0;
-    nmask = 0xFFFFu;
-    if (p >= a.n_bases) return;
-    if (a.words) {
-        code = a.words[p >> 4]; // (p < n_bases: below ceil(n_bases / 16))
-        nmask = a.nbits ? a.nbits[p >> 4] : 0u;
-        return;
-    }
-    uint32_t w[4] = { 0, 0, 0, 0 };
-    if (aligned) {
-        const uint4 v = load_once_16(a.text + p);
-        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-    } else {
-        const uint32_t n = (uint32_t)(a.n_bases - p < 16 ? a.n_bases - p : 16);
-        for (uint32_t j = 0; j < n; ++j) w[j >> 2] |= (uint32_t)a.text[p + j] << (8 * (j & 3));
-    }
-    ad_text16(w, code, nmask);
-}
-
+// (the 16 bases from base p on in the common form: load16_common, load16.h)
 __global__ __launch_bounds__(AD_THREADS) void adapter_points_kernel(AdapterPoints a, AdapterSet ad)
 {
     __shared__ AdLds s;
@@ -93,7 +72,7 @@ __global__ __launch_bounds__(AD_THREADS) void adapter_points_kernel(AdapterPoint
         const uint64_t p = tile + ((uint64_t)round * AD_THREADS + threadIdx.x) * AD_LANE_STARTS;
         code[round] = 0;
         nm[round] = 0xFFFFu;
-        if (p < tile_end) ad_load16(a, aligned, p, code[round], nm[round]);
+        if (p < tile_end) load16_common(a.text, a.words, a.nbits, a.n_bases, aligned, p, code[round], nm[round]);
     }
 #pragma unroll
     for (int round = 0; round < AD_ROUNDS; ++round) {
@@ -112,7 +91,7 @@ __global__ __launch_bounds__(AD_THREADS) void adapter_points_kernel(AdapterPoint
                 if (lane + (int)k > 63) {
                     c[k] = 0;
                     n[k] = 0xFFFFu;
-                    if (live) ad_load16(a, aligned, p + (uint64_t)k * AD_LANE_STARTS, c[k], n[k]);
+                    if (live) load16_common(a.text, a.words, a.nbits, a.n_bases, aligned, p + (uint64_t)k * AD_LANE_STARTS, c[k], n[k]);
                 }
             }
         }

@@ -47,7 +47,8 @@ struct SampleState {
     Selection subsample, dedup; // drprg_hip_subsample, drprg_hip_dedup
     // What the read filter has counted: added to by the submitters of drprg_hip_map_fastx, one per device, under filter_mu.  The blocks'
     // outcomes summed: drprg_hip_read_filter_info, and in .trim / .adapter / .front drprg_hip_read_trim_info,
-    // drprg_hip_adapter_trim_info and drprg_hip_front_adapter_info, in .mask drprg_hip_base_mask_info, in .decoy drprg_hip_decoy_info.
+    // drprg_hip_adapter_trim_info and drprg_hip_front_adapter_info, in .mask drprg_hip_base_mask_info, in .decoy drprg_hip_decoy_info, in
+    // .poly drprg_hip_poly_trim_info, in .cplx drprg_hip_complexity_info.
     Mapper::FilterOutcome filter_counts;
     MapCounters extra_counts; // what devices 1 .. ndev-1 counted (reduce_devices folds them in when it folds their coverage)
 };
@@ -66,7 +67,8 @@ struct drprg_hip_ctx {
     int threads = 4; // parser threads of drprg_hip_map_fastx
     bool packed_input = false; // drprg_hip_set_input_format: map_fastx packs the reads to 2 bits on the parser threads
     bool ordered_ingest = false; // drprg_hip_set_ordered_ingest
-    // drprg_hip_set_read_filter; the settings of drprg_hip_set_read_trim, drprg_hip_set_adapters* and drprg_hip_set_base_mask ride in it too
+    // drprg_hip_set_read_filter; the settings of drprg_hip_set_read_trim, drprg_hip_set_adapters*, drprg_hip_set_base_mask,
+    // drprg_hip_set_poly_trim and drprg_hip_set_min_complexity ride in it too
     drprg::Mapper::ReadFilter read_filter;
     std::mutex filter_mu; // guards sample.filter_counts
     // ---- results of the last calls: a reset keeps them ----

@@ -93,6 +93,12 @@ int drprg_hip_discover_reads(drprg_hip_ctx* ctx, const char* reads_path, const c
     if (!ctx->last_discover_resident && ctx->sample.filter_counts.trim.reads_lost_base)
         throw Error(DRPRG_ENODATA, "discover: read trimming cut bases off reads of this sample and the trimmed reads are not resident in device memory; a pass "
                                    "over the file would pile up untrimmed reads (raise DRPRG_HIP_KEEP_READS_GB, or trim the file first)");
+    if (!ctx->last_discover_resident && ctx->sample.filter_counts.poly.reads_cut)
+        throw Error(DRPRG_ENODATA, "discover: poly-tail trimming (--poly-tail) cut tails off reads of this sample and the cut reads are not resident in device memory; "
+                                   "a pass over the file would pile up the reads with their tails (raise DRPRG_HIP_KEEP_READS_GB, or trim the file first)");
+    if (!ctx->last_discover_resident && ctx->sample.filter_counts.cplx.reads_dropped)
+        throw Error(DRPRG_ENODATA, "discover: the complexity filter (--min-complexity) dropped reads of this sample and the kept reads are not resident in device "
+                                   "memory; a pass over the file would pile up the dropped reads too (raise DRPRG_HIP_KEEP_READS_GB, or filter the file first)");
     if (!ctx->last_discover_resident && ctx->sample.filter_counts.mask.reads_masked)
         throw Error(DRPRG_ENODATA, "discover: base masking (--mask-qual) made bases of this sample unknown and the masked reads are not resident in device memory; "
                                    "a pass over the file would pile up the bases as the file holds them (raise DRPRG_HIP_KEEP_READS_GB, or mask the file first)");

@@ -344,6 +344,12 @@ static void refuse_unfiltered(const drprg_hip_ctx* ctx, const char* entry)
     if (ctx->read_filter.any_adapters())
         throw Error(DRPRG_EINVAL, std::string(entry) + ": adapters are set (drprg_hip_set_adapters) and adapter trimming runs in drprg_hip_map_fastx; this entry "
                                                       "would map the reads with their adapters (clear them with drprg_hip_set_adapters(ctx, NULL, 0, 0, 0))");
+    if (ctx->read_filter.poly())
+        throw Error(DRPRG_EINVAL, std::string(entry) + ": poly-tail trimming is set (drprg_hip_set_poly_trim) and runs in drprg_hip_map_fastx; this entry "
+                                                      "would map the reads with their tails (clear it with drprg_hip_set_poly_trim(ctx, NULL, 0))");
+    if (ctx->read_filter.min_complexity)
+        throw Error(DRPRG_EINVAL, std::string(entry) + ": a complexity threshold is set (drprg_hip_set_min_complexity) and the test runs in drprg_hip_map_fastx; "
+                                                      "this entry would map the reads unjudged (clear it with drprg_hip_set_min_complexity(ctx, 0))");
     if (ctx->read_filter.trims())
         throw Error(DRPRG_EINVAL, std::string(entry) + ": read trimming is set (drprg_hip_set_read_trim) and this entry carries no qualities; trimming "
                                                       "runs in drprg_hip_map_fastx (clear it with drprg_hip_set_read_trim(ctx, 0, 0, 0, 0))");

@@ -1,4 +1,5 @@
-// capi_prep.cpp -- read preparation (filter, trimming, adapters, base mask, decoy screen: settings, counts, device entries) and the resident sample
+// capi_prep.cpp -- read preparation (filter, trimming, adapters, poly tails, read complexity, base mask, decoy screen: settings, counts, device
+// entries) and the resident sample
 // (keep, map from another context, select, subsample, dedup).
 #include "capi_ctx.h"
 #include "fastx.h"
@@ -213,6 +214,88 @@ int drprg_hip_adapter_trim_device2(drprg_hip_ctx* ctx, const void* d_text, const
     uint64_t n_reads, uint64_t n_bases, void* d_begin, void* d_end, uint64_t out[10], void* hip_stream)
 {
     return adapter_trim_device(ctx, d_text, d_words, d_npos, n_npos, d_offsets, n_reads, n_bases, d_begin, d_end, out, 10, false, hip_stream);
+}
+
+// ---- poly tails (the rule: include/drprg_hip.h "poly tails") ------------------------------------------------------------------------
+int drprg_hip_set_poly_trim(drprg_hip_ctx* ctx, const char* letters, uint32_t min_len)
+{
+    API_BEGIN(ctx)
+    if (!letters || !*letters) { // cleared
+        ctx->read_filter.poly_letters = ctx->read_filter.poly_min_len = 0;
+        return DRPRG_OK;
+    }
+    static const char acgt[] = "ACGT";
+    uint32_t set = 0;
+    for (const char* c = letters; *c; ++c) {
+        const char* at = (*c & 0x40) ? std::strchr(acgt, *c & 0xDF) : nullptr;
+        if (!at) throw Error(DRPRG_EINVAL, "poly-tail trimming: the letters are ACGT (either case) and no other");
+        const uint32_t bit = 1u << (at - acgt);
+        if (set & bit) throw Error(DRPRG_EINVAL, "poly-tail trimming: a letter is named once");
+        set |= bit;
+    }
+    if (min_len < dev::PT_MIN_LEN_LO || min_len > dev::PT_MIN_LEN_HI) throw Error(DRPRG_EINVAL, "poly-tail trimming: the shortest tail cut is 2..255 bases long");
+    ctx->read_filter.poly_letters = set; // (they ride in the settings every device's blocks are prepared under, like the trim settings)
+    ctx->read_filter.poly_min_len = min_len;
+    API_END(ctx)
+}
+
+int drprg_hip_poly_trim_info(drprg_hip_ctx* ctx, uint64_t out[5])
+{
+    API_BEGIN(ctx)
+    if (!out) throw Error(DRPRG_EINVAL, "null output");
+    std::lock_guard<std::mutex> g(ctx->filter_mu);
+    const Mapper::PolyOutcome& t = ctx->sample.filter_counts.poly;
+    out[0] = t.reads_seen; out[1] = t.bases_seen; out[2] = t.reads_cut; out[3] = t.bases_cut; out[4] = t.reads_emptied;
+    API_END(ctx)
+}
+
+int drprg_hip_poly_trim_device(drprg_hip_ctx* ctx, const void* d_text, const void* d_words, const void* d_npos, uint64_t n_npos, const void* d_offsets,
+    uint64_t n_reads, uint64_t n_bases, const void* d_begin, void* d_end, uint64_t out[5], void* hip_stream)
+{
+    API_BEGIN(ctx)
+    Mapper& m = need_mapper(ctx);
+    if (!out) throw Error(DRPRG_EINVAL, "null output");
+    if (d_text && d_words) throw Error(DRPRG_EINVAL, "poly-tail trimming: the bases come as text or as packed words, not both");
+    uint64_t res[6];
+    m.poly_trim_device(ctx->read_filter, (const uint8_t*)d_text, (const uint32_t*)d_words, (const uint64_t*)d_npos, n_npos, (const uint64_t*)d_offsets, n_reads,
+        n_bases, (const uint64_t*)d_begin, (uint64_t*)d_end, res, (hipStream_t)hip_stream);
+    for (int i = 0; i < 5; ++i) out[i] = res[i];
+    if (res[5]) throw Error(DRPRG_EINVAL, "poly-tail trimming: the offsets do not ascend to n_bases, or a range does not lie inside its read");
+    API_END(ctx)
+}
+
+// ---- the low-complexity filter (the rule: include/drprg_hip.h "read complexity") ----------------------------------------------------
+int drprg_hip_set_min_complexity(drprg_hip_ctx* ctx, uint32_t percent)
+{
+    API_BEGIN(ctx)
+    if (percent > 100) throw Error(DRPRG_EINVAL, "read complexity: the threshold is a percentage, 1..100 (0 clears it)");
+    ctx->read_filter.min_complexity = percent;
+    API_END(ctx)
+}
+
+int drprg_hip_complexity_info(drprg_hip_ctx* ctx, uint64_t out[4])
+{
+    API_BEGIN(ctx)
+    if (!out) throw Error(DRPRG_EINVAL, "null output");
+    std::lock_guard<std::mutex> g(ctx->filter_mu);
+    const Mapper::ComplexityOutcome& t = ctx->sample.filter_counts.cplx;
+    out[0] = t.reads_judged; out[1] = t.bases_judged; out[2] = t.reads_dropped; out[3] = t.bases_dropped;
+    API_END(ctx)
+}
+
+int drprg_hip_complexity_device(drprg_hip_ctx* ctx, const void* d_text, const void* d_words, const void* d_npos, uint64_t n_npos, const void* d_offsets,
+    uint64_t n_reads, uint64_t n_bases, void* d_diff, void* d_flags, uint64_t out[2], void* hip_stream)
+{
+    API_BEGIN(ctx)
+    Mapper& m = need_mapper(ctx);
+    if (!out) throw Error(DRPRG_EINVAL, "null output");
+    if (d_text && d_words) throw Error(DRPRG_EINVAL, "read complexity: the bases come as text or as packed words, not both");
+    uint64_t res[3];
+    m.complexity_device(ctx->read_filter, (const uint8_t*)d_text, (const uint32_t*)d_words, (const uint64_t*)d_npos, n_npos, (const uint64_t*)d_offsets, n_reads,
+        n_bases, (uint32_t*)d_diff, (uint8_t*)d_flags, res, (hipStream_t)hip_stream);
+    out[0] = res[0]; out[1] = res[1];
+    if (res[2]) throw Error(DRPRG_EINVAL, "read complexity: the offsets do not ascend from 0 to n_bases");
+    API_END(ctx)
 }
 
 // ---- base masking (the rule: include/drprg_hip.h "base masking") -------------------------------------------------------------------

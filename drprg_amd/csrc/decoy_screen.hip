@@ -18,6 +18,7 @@
 // slots are taken, and the loop is bounded by the table's size whatever it holds.
 //
 // The build inserts with a 64-bit compare-and-swap: the slot a k-mer ends in depends on who came first, membership does not.
+#include "load16.h"
 #include "search.h"
 
 namespace drprg {
@@ -28,28 +29,6 @@ constexpr uint32_t DC_LANE_STARTS = 64;
 constexpr uint32_t DC_TILE = DC_THREADS * DC_LANE_STARTS; // 16384 starts per workgroup
 
 uint32_t decoy_screen_tiles(uint64_t n_bases) { return (uint32_t)((n_bases + DC_TILE - 1) / DC_TILE); }
-
-// the 16 bases from base p on (p a multiple of 16) in the common form: ad_load16 of adapter_trim.hip for this kernel's arguments
-__device__ inline void dc_load16(const DecoyScreenArgs& a, bool aligned, uint64_t p, uint32_t& code, uint32_t& nmask)
-{
-    code = 0;
-    nmask = 0xFFFFu;
-    if (p >= a.n_bases) return;
-    if (a.words) {
-        code = a.words[p >> 4]; // (p < n_bases: below ceil(n_bases / 16))
-        nmask = a.nbits ? a.nbits[p >> 4] : 0u;
-        return;
-    }
-    uint32_t w[4] = { 0, 0, 0, 0 };
-    if (aligned) {
-        const uint4 v = load_once_16(a.text + p);
-        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-    } else {
-        const uint32_t n = (uint32_t)(a.n_bases - p < 16 ? a.n_bases - p : 16);
-        for (uint32_t j = 0; j < n; ++j) w[j >> 2] |= (uint32_t)a.text[p + j] << (8 * (j & 3));
-    }
-    ad_text16(w, code, nmask);
-}
 
 // The starts p .. p + nst - 1 (p a multiple of 16, 1 <= nst <= DC_LANE_STARTS): visit(j, canon) for every j < nst whose window [p + j,
 // p + j + k) is all ACGT and lies below n_bases of the loader, in ascending order; canon: the window's canonical k-mer.
@@ -62,7 +41,7 @@ __device__ inline void dc_roll(const DecoyScreenArgs& a, bool aligned, uint64_t 
     uint32_t run = 0;
     for (uint32_t w = 0; 16u * w < n_take; ++w) {
         uint32_t code, nm;
-        dc_load16(a, aligned, p + 16ull * w, code, nm);
+        load16_common(a.text, a.words, a.nbits, a.n_bases, aligned, p + 16ull * w, code, nm);
 #pragma unroll
         for (uint32_t j = 0; j < 16u; ++j) {
             const uint32_t l = (code >> (2u * j)) & 3u, c = l ^ (l >> 1);

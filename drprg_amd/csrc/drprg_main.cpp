@@ -22,6 +22,7 @@
 #include "adapter_args.h"
 #include "decoy_args.h"
 #include "mask_args.h"
+#include "poly_args.h"
 
 namespace {
 
@@ -114,7 +115,15 @@ void usage()
         "              [--dedup] [--min-read-len L] [--max-read-len L] [--min-read-qual Q]\n"
         "              [--trim-front N] [--trim-tail N] [--trim-qual Q [--trim-window W]]\n"
         "              [--adapter SEQ]... [--adapter-error E] [--adapter-min-overlap O] [--adapter-indels] [--front-adapter SEQ]...\n"
+        "              [--poly-tail LETTERS [--poly-min-len M]] [--min-complexity P]\n"
         "              [--mask-qual Q] [--decoy FASTA]... [--decoy-k K] [--decoy-min-frac F] [--decoy-min-kmers M]\n"
+        "--poly-tail LETTERS (letters of ACGT, e.g. G or ACGT), --poly-min-len M (2 to 255, default 10): every read loses its longest suffix of\n"
+        "              at least M bases that begins with one of the letters and holds at most min(n / 8, 5) other bases -- the tails two-colour\n"
+        "              instruments (NextSeq, NovaSeq) leave when a cluster goes dark, which carry HIGH qualities.  On the device, behind --trim-*\n"
+        "              and both --adapter sides, in front of everything else: the run is that of a file of the cut reads.  Needs no qualities.\n"
+        "--min-complexity P (a whole percentage, 1 to 100; fastp's default is 30): a read is dropped when fewer than P %% of its neighbouring\n"
+        "              base pairs differ (an unknown base differs from every letter) -- on the device, behind --trim-*, --adapter, --poly-tail,\n"
+        "              --mask-qual and --min/max-read-*, in front of --decoy.  This build's own rules, after fastp.  Default: off.\n"
         "--mask-qual Q (a whole Phred value, 1 to 93): every base whose quality is below Q becomes an unknown base -- on the device, behind\n"
         "              --trim-* and --adapter and in front of everything else: the run is that of a file in which those bases are the letter N.\n"
         "              The read keeps its length, its place in the depth arithmetic and its mean quality; only the k-mers that hold a masked\n"
@@ -190,6 +199,7 @@ int main(int argc, char** argv)
     uint32_t trim_qual_milli = 0, trim_window = 0;
     uint32_t mask_qual = 0; // --mask-qual Q: base masking (include/drprg_hip.h "base masking"); 0 = not set
     drprg::AdapterArgs adapters; // --adapter SEQ, --adapter-error E, --adapter-min-overlap O (include/drprg_hip.h "adapter trimming")
+    drprg::PolyArgs poly; // --poly-tail LETTERS, --poly-min-len M, --min-complexity P (include/drprg_hip.h "poly tails", "read complexity")
     drprg::DecoyArgs decoy; // --decoy FASTA, --decoy-k K, --decoy-min-frac F, --decoy-min-kmers M (include/drprg_hip.h "decoy screen")
     uint32_t min_cluster = 10;
     drprg_hip_annotate_opts ao {};
@@ -294,6 +304,16 @@ int main(int argc, char** argv)
             const std::string e = drprg::parse_mask_qual(need(i), mask_qual);
             if (!e.empty()) die(e, 2);
         }
+        else if (a == "--poly-tail") {
+            const std::string e = poly.set_letters(need(i));
+            if (!e.empty()) die(e, 2);
+        } else if (a == "--poly-min-len") {
+            const std::string e = poly.set_min_len(need(i));
+            if (!e.empty()) die(e, 2);
+        } else if (a == "--min-complexity") {
+            const std::string e = poly.set_complexity(need(i));
+            if (!e.empty()) die(e, 2);
+        }
         else if (a == "--decoy") {
             const std::string e = decoy.add(need(i));
             if (!e.empty()) die(e, 2);
@@ -315,6 +335,7 @@ int main(int argc, char** argv)
     if (trim_window && !trim_qual_milli) die("--trim-window belongs to --trim-qual", 2);
     if (const std::string e = adapters.check(); !e.empty()) die(e, 2);
     if (const std::string e = decoy.check(); !e.empty()) die(e, 2);
+    if (const std::string e = poly.check(); !e.empty()) die(e, 2);
     if (index.empty() || input.empty()) {
         usage();
         return 2;
@@ -369,6 +390,7 @@ int main(int argc, char** argv)
     if (int rc = drprg_hip_set_read_filter(ctx, min_read_len, max_read_len, min_read_qual_milli)) die(drprg_hip_last_error(ctx), -rc);
     if (int rc = drprg_hip_set_read_trim(ctx, trim_front, trim_tail, trim_qual_milli, trim_window)) die(drprg_hip_last_error(ctx), -rc);
     if (int rc = drprg_hip_set_base_mask(ctx, mask_qual)) die(drprg_hip_last_error(ctx), -rc);
+    if (int rc = poly.set_on(ctx, drprg_hip_set_poly_trim, drprg_hip_set_min_complexity)) die(drprg_hip_last_error(ctx), -rc);
     if (adapters.any())
         if (int rc = adapters.set_on(ctx, drprg_hip_set_adapters, drprg_hip_set_adapters2)) die(drprg_hip_last_error(ctx), -rc);
     if (decoy.any()) // (once per run: the second pass after a PRG update maps the resident reads, which are screened already)
@@ -404,11 +426,23 @@ int main(int argc, char** argv)
             std::fprintf(stderr, "[drprg-hip +%.3fs] front adapter trimming: reads_seen=%llu bases_seen=%llu reads_cut=%llu bases_cut=%llu reads_emptied=%llu\n", since_start(),
                 (unsigned long long)ai[0], (unsigned long long)ai[1], (unsigned long long)ai[2], (unsigned long long)ai[3], (unsigned long long)ai[4]);
     }
+    if (verbose && poly.tails()) { // (of the one pass over the file: a second pass after a PRG update maps the resident reads, which are cut already)
+        uint64_t pt[5] = {};
+        if (drprg_hip_poly_trim_info(ctx, pt) == 0)
+            std::fprintf(stderr, "[drprg-hip +%.3fs] poly tail trimming: reads_seen=%llu bases_seen=%llu reads_cut=%llu bases_cut=%llu reads_emptied=%llu\n", since_start(),
+                (unsigned long long)pt[0], (unsigned long long)pt[1], (unsigned long long)pt[2], (unsigned long long)pt[3], (unsigned long long)pt[4]);
+    }
     if (verbose && mask_qual) { // (of the one pass over the file: a second pass after a PRG update maps the resident reads, which are masked already)
         uint64_t bm[5] = {};
         if (drprg_hip_base_mask_info(ctx, bm) == 0)
             std::fprintf(stderr, "[drprg-hip +%.3fs] base masking: reads_seen=%llu bases_seen=%llu reads_masked=%llu bases_masked=%llu bases_already_unknown=%llu\n",
                 since_start(), (unsigned long long)bm[0], (unsigned long long)bm[1], (unsigned long long)bm[2], (unsigned long long)bm[3], (unsigned long long)bm[4]);
+    }
+    if (verbose && poly.min_complexity) { // (of the one pass over the file, like the lines beside it)
+        uint64_t cx[4] = {};
+        if (drprg_hip_complexity_info(ctx, cx) == 0)
+            std::fprintf(stderr, "[drprg-hip +%.3fs] complexity filter: reads_seen=%llu bases_seen=%llu reads_dropped=%llu bases_dropped=%llu\n", since_start(),
+                (unsigned long long)cx[0], (unsigned long long)cx[1], (unsigned long long)cx[2], (unsigned long long)cx[3]);
     }
     if (verbose && decoy.any()) {
         uint64_t di[8] = {};
@@ -473,6 +507,7 @@ int main(int argc, char** argv)
                 if (int rc = drprg_hip_set_read_filter(next, min_read_len, max_read_len, min_read_qual_milli)) die(drprg_hip_last_error(next), -rc);
                 if (int rc = drprg_hip_set_read_trim(next, trim_front, trim_tail, trim_qual_milli, trim_window)) die(drprg_hip_last_error(next), -rc);
                 if (int rc = drprg_hip_set_base_mask(next, mask_qual)) die(drprg_hip_last_error(next), -rc);
+                if (int rc = poly.set_on(next, drprg_hip_set_poly_trim, drprg_hip_set_min_complexity)) die(drprg_hip_last_error(next), -rc);
                 if (adapters.any())
                     if (int rc = adapters.set_on(next, drprg_hip_set_adapters, drprg_hip_set_adapters2)) die(drprg_hip_last_error(next), -rc);
                 // the reads again, against the updated index: from HBM if the first context kept them all, else from the file

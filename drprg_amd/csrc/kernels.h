@@ -14,6 +14,7 @@
 #include "adapter_piece.h"
 #include "adapter_edit.h"
 #include "decoy_piece.h"
+#include "poly_piece.h"
 
 namespace drprg {
 namespace dev {
@@ -430,10 +431,16 @@ hipError_t launch_dedup_select(const DedupSelect& s, hipStream_t stream);
 // and quality tests kept, from the V and H launch_decoy_screen left in decoy_valid / decoy_hits (u32[n_reads]): a read it drops has flag 0
 // like any other, so the scans see one verdict; RF_DECOY_* count the reads judged, their bases, the reads and bases dropped, and the sums of
 // V and H over the judged reads.  Null (no decoy set): nothing of it is read or counted.  work and out: RF_WORDS words each.
+// cplx_diff != null: the low-complexity verdict (the rule: include/drprg_hip.h "read complexity") on the reads the length and quality tests
+// kept, from the D launch_read_diff left in cplx_diff (u32[n_reads]) and cplx_percent (1..100): a read it drops has flag 0 like any other,
+// and the decoy screen's verdict then applies only to the reads it kept as well; RF_CPLX_* count the reads judged, their bases, and the
+// reads and bases dropped.  Null: nothing of it is read or counted.
 enum {
     RF_KEPT_READS = 0, RF_KEPT_BASES = 1, RF_SHORT = 2, RF_LONG = 3, RF_LOWQ = 4, RF_BAD_AT = 5 /* first bad quality byte + 1, or 0 */,
     RF_OFFSETS = 6 /* offsets at odds with n_bases */, RF_ERR = 7 /* work only: the error word of the compaction behind the filter */,
-    RF_DECOY_READS = 8, RF_DECOY_BASES = 9, RF_DECOY_DROPPED = 10, RF_DECOY_DROPPED_BASES = 11, RF_DECOY_VALID = 12, RF_DECOY_HITS = 13, RF_WORDS = 16
+    RF_DECOY_READS = 8, RF_DECOY_BASES = 9, RF_DECOY_DROPPED = 10, RF_DECOY_DROPPED_BASES = 11, RF_DECOY_VALID = 12, RF_DECOY_HITS = 13,
+    // the low-complexity filter (read_complexity.hip), all zero without it: reads judged, their bases, reads and bases dropped
+    RF_CPLX_READS = 14, RF_CPLX_BASES = 15, RF_CPLX_DROPPED = 16, RF_CPLX_DROPPED_BASES = 17, RF_WORDS = 18
 };
 struct ReadFilterArgs {
     const uint8_t* qual;
@@ -444,6 +451,8 @@ struct ReadFilterArgs {
     bool use_qual;
     const uint32_t *decoy_valid, *decoy_hits;
     uint32_t decoy_frac_milli, decoy_min_kmers;
+    const uint32_t* cplx_diff;
+    uint32_t cplx_percent;
     unsigned long long* qsum;
     uint8_t* flag;
     uint32_t *flag32, *rank;
@@ -471,7 +480,9 @@ enum {
     // bases cut, reads emptied
     RT_AD_BASES_SEEN = 10, RT_AD_READS_CUT = 11, RT_AD_BASES_CUT = 12, RT_AD_EMPTIED = 13,
     // the same four for 5' adapters (adapter_edit.hip): the bases seen are those behind the 3' cut
-    RT_FA_BASES_SEEN = 14, RT_FA_READS_CUT = 15, RT_FA_BASES_CUT = 16, RT_FA_EMPTIED = 17, RT_WORDS = 18 /* words of work and of out */
+    RT_FA_BASES_SEEN = 14, RT_FA_READS_CUT = 15, RT_FA_BASES_CUT = 16, RT_FA_EMPTIED = 17,
+    // the same four for poly tails (poly_tail.hip): the bases seen are those behind both adapter cuts
+    RT_PT_BASES_SEEN = 18, RT_PT_READS_CUT = 19, RT_PT_BASES_CUT = 20, RT_PT_EMPTIED = 21, RT_WORDS = 22 /* words of work and of out */
 };
 // adapter_trim.hip: what adapter_points_kernel searches.  The bases as text (n_bases + 64 bytes readable when 16-byte aligned; any other
 // address is read byte by byte and never behind n_bases) or, when words != null, as a packed batch's words (ceil(n_bases / 16)) with
@@ -499,6 +510,12 @@ hipError_t launch_adapter_trim(const AdapterPoints& a, const AdapterSet& ad, uin
 uint32_t adapter_edit_tiles(uint64_t n_bases);
 hipError_t launch_adapter_edit(const AdapterPoints& a, const AdapterSet& ad3, const AdapterEq& eq3, const AdapterSet& ad5, const AdapterEq& eq5, uint64_t* begin,
     uint64_t* end, uint64_t* klen, unsigned long long* work, hipStream_t stream, KernelTimer timer3 = {}, KernelTimer timer5 = {});
+// poly_tail.hip: poly-tail trimming (the rule: include/drprg_hip.h "poly tails") on the same inputs (a.cut is not looked at): end[i] -= the
+// longest qualifying suffix of read i's range over the letters of the set (letters: bit 0 A, 1 C, 2 G, 3 T; min_len: 2..255), klen[i] (klen
+// may be null) the new length, the counts ADDED to work[RT_PT_*]; work[RT_OFFSETS] as launch_adapter_trim.  One launch; a read costs its
+// tail's length plus a few bases, not its own.  end is a.end.  timer: around poly_tail_kernel
+hipError_t launch_poly_tail(const AdapterPoints& a, uint32_t letters, uint32_t min_len, uint64_t* end, uint64_t* klen, unsigned long long* work, hipStream_t stream,
+    KernelTimer timer = {});
 struct ReadTrimArgs {
     const uint8_t* qual;
     uint32_t bias;
@@ -514,6 +531,7 @@ struct ReadTrimArgs {
     size_t temp_bytes;
     AdapterSet ad;
     AdapterPoints pts;
+    uint32_t poly_letters, poly_min_len; // poly tails behind the adapters (poly_tail.hip) on pts; poly_letters == 0: none
 };
 // the indel rule (adapter_edit.hip) in place of the plain one: launch_read_trim's last argument, kept out of ReadTrimArgs, which goes to
 // kernels by value.  ad3 and ad5 (letter-reversed; either may be empty) with their match masks; ReadTrimArgs::ad is not looked at then
@@ -579,6 +597,25 @@ hipError_t launch_decoy_screen(const DecoyScreenArgs& a, const DecoySet& d, hipS
 // The verdict alone, for a batch no filter has seen: flag[r] = 0 for a read the rule drops, else 1; work (four zeroed device words) receives
 // reads dropped, bases dropped, the sum of V and the sum of H; *err (zeroed by the caller) is set when the offsets do not ascend from 0 to n_bases.
 hipError_t launch_decoy_verdict(const DecoyScreenArgs& a, const DecoySet& d, uint8_t* flag, unsigned long long* work, uint32_t* err, hipStream_t stream);
+
+// read_complexity.hip: the low-complexity filter (the rule: include/drprg_hip.h "read complexity").  The bases in either of
+// adapter_points_kernel's two forms, as the decoy screen takes them.  diff[r] = D of read r, the neighbouring pairs inside it that differ
+// (u32[n_reads]; zeroed here).  1 <= n_reads <= MAX_BATCH_READS; a read is shorter than 2^32 bases (the callers refuse a block that is
+// not); nothing is indexed out of bounds whatever `offsets` holds.
+struct ComplexityArgs {
+    const uint8_t* text;
+    const uint32_t* words;
+    const uint16_t* nbits;
+    const uint64_t* offsets;
+    uint64_t n_reads, n_bases;
+    uint32_t* diff;
+};
+uint32_t read_complexity_tiles(uint64_t n_bases);
+// timer: around read_diff_kernel
+hipError_t launch_read_diff(const ComplexityArgs& a, hipStream_t stream, KernelTimer timer = {});
+// The verdict alone, for a batch no filter has seen: flag[r] = 0 for a read the rule drops under percent (1..100), else 1; work (two zeroed
+// device words) receives reads dropped and bases dropped; *err (zeroed by the caller) is set when the offsets do not ascend from 0 to n_bases.
+hipError_t launch_complexity_verdict(const ComplexityArgs& a, uint32_t percent, uint8_t* flag, unsigned long long* work, uint32_t* err, hipStream_t stream);
 
 // base_mask.hip: base masking (the rule: include/drprg_hip.h "base masking").  Every base whose quality byte minus bias is below min_qual
 // (1..93) becomes an unknown base, in place.  qual: n_bases bytes, indexed in bases (n_bases + 64 bytes readable when 16-byte aligned; any

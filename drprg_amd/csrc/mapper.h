@@ -144,12 +144,20 @@ public:
         // Base masking (the rule: include/drprg_hip.h "base masking"; base_mask.hip): Q, 1..93 (0: off).  Behind the trim stage, in
         // front of the decoy screen and the filter; it needs the quality bytes.
         uint32_t mask_qual = 0;
+        // Poly tails (the rule: include/drprg_hip.h "poly tails"; poly_tail.hip): the set S (bit 0 A, 1 C, 2 G, 3 T; 0: off) and M,
+        // 2..255 whenever S is set.  Inside the trim stage, behind both adapter sides; it needs no quality byte.
+        uint32_t poly_letters = 0, poly_min_len = 0;
+        // The low-complexity filter (the rule: include/drprg_hip.h "read complexity"; read_complexity.hip): P, 1..100 (0: off).  Behind
+        // the mask, on the reads the length and quality tests kept, in front of the decoy screen's verdict.
+        uint32_t min_complexity = 0;
         bool decoy() const { return decoy_k != 0; }
+        bool poly() const { return poly_letters != 0; }
         bool any_adapters() const { return adapters.n != 0 || front_adapters.n != 0; }
         bool crops() const { return trim_front || trim_tail || trim_qual_milli; } // what drprg_hip_read_trim_info counts
         bool filters() const { return min_len || max_len || min_qual_milli; }
-        bool trims() const { return crops() || any_adapters(); }
-        bool any() const { return filters() || trims() || decoy() || mask_qual; }
+        bool trims() const { return crops() || any_adapters() || poly(); }
+        bool trim_points() const { return any_adapters() || poly(); } // the trim stage looks at the bases (a packed block's bitmap first)
+        bool any() const { return filters() || trims() || decoy() || mask_qual || min_complexity; }
         bool use_qual() const { return min_qual_milli != 0; }
         bool wants_qual() const { return min_qual_milli != 0 || trim_qual_milli != 0 || mask_qual != 0; } // the ingest carries quality bytes
         bool qual_behind_trim() const { return use_qual() || mask_qual != 0; } // the trim stage gathers the trimmed reads' quality bytes
@@ -171,7 +179,17 @@ public:
         uint64_t reads_seen = 0, bases_seen = 0, reads_masked = 0, bases_masked = 0, bases_already_unknown = 0;
         MaskOutcome& operator+=(const MaskOutcome& o);
     };
+    struct PolyOutcome { // drprg_hip_poly_trim_info: the reads and bases behind both adapter cuts, and what the tail cut took
+        uint64_t reads_seen = 0, bases_seen = 0, reads_cut = 0, bases_cut = 0, reads_emptied = 0;
+        PolyOutcome& operator+=(const PolyOutcome& o);
+    };
+    struct ComplexityOutcome { // drprg_hip_complexity_info: the reads the length and quality tests kept, and what the threshold dropped
+        uint64_t reads_judged = 0, bases_judged = 0, reads_dropped = 0, bases_dropped = 0;
+        ComplexityOutcome& operator+=(const ComplexityOutcome& o);
+    };
     struct FilterOutcome {
+        PolyOutcome poly;       // (all zero without poly-tail trimming)
+        ComplexityOutcome cplx; // (all zero without a complexity threshold)
         MaskOutcome mask;       // (all zero without a base mask)
         DecoyOutcome decoy;     // (all zero without a decoy set)
         TrimOutcome trim;       // (all zero without a crop or a quality trim)
@@ -207,6 +225,16 @@ public:
     // the ranges do not lie inside the reads.  Synchronises `stream`.
     void adapter_trim_device(const ReadFilter& f, const uint8_t* d_text, const uint32_t* d_words, const uint64_t* d_npos, uint64_t n_npos, const uint64_t* d_offsets,
         uint64_t n_reads, uint64_t n_bases, uint64_t* d_begin, uint64_t* d_end, uint64_t res[11], hipStream_t stream);
+    // The tail cut alone on the caller's device buffers (drprg_hip_poly_trim_device): buffers as for adapter_trim_device; d_end receives the
+    // cut ranges' ends.  res[0..4]: reads seen, bases seen, reads cut, bases cut, reads emptied; res[5]: the ranges do not lie inside the
+    // reads.  Synchronises `stream`.
+    void poly_trim_device(const ReadFilter& f, const uint8_t* d_text, const uint32_t* d_words, const uint64_t* d_npos, uint64_t n_npos, const uint64_t* d_offsets,
+        uint64_t n_reads, uint64_t n_bases, const uint64_t* d_begin, uint64_t* d_end, uint64_t res[6], hipStream_t stream);
+    // The complexity kernels alone on the caller's device buffers (drprg_hip_complexity_device): the bases as for adapter_trim_device; d_diff
+    // (may be null) receives D, d_flags 1 for a kept read; res[0..1]: reads dropped, bases dropped; res[2]: the offsets do not ascend from
+    // 0 to n_bases.  Synchronises `stream`.
+    void complexity_device(const ReadFilter& f, const uint8_t* d_text, const uint32_t* d_words, const uint64_t* d_npos, uint64_t n_npos, const uint64_t* d_offsets,
+        uint64_t n_reads, uint64_t n_bases, uint32_t* d_diff, uint8_t* d_flags, uint64_t res[3], hipStream_t stream);
     // The decoy set of this device (drprg_hip_set_decoy).  text: the records' letters, one 'N' between two records; windows: the windows
     // of the records (what the table is sized by); set: the name ReadFilter::decoy_id carries.  The table is built on the device
     // (decoy_screen.hip) and stays until clear_decoy or the Mapper goes; -EINVAL, and no set, when the text holds no k-mer.
@@ -522,6 +550,10 @@ private:
         DeviceBuffer<uint32_t> k_counts;
         DeviceBuffer<unsigned long long> k_work;
         PinnedBuffer<unsigned long long> k_out;
+        // the low-complexity filter: D of every read; complexity_device's three words with their pinned mirror
+        DeviceBuffer<uint32_t> x_diff;
+        DeviceBuffer<unsigned long long> x_work;
+        PinnedBuffer<unsigned long long> x_out;
         // base masking: one claim word per read, the counts with their pinned mirror, and -- packed blocks, whose bitmap is t_nbits -- the
         // per-chunk counts of listed positions, their scan and the list behind the mask
         DeviceBuffer<uint32_t> m_rflag, m_count, m_prefix;
@@ -549,7 +581,11 @@ private:
     // queues the filter on `stream`; fs.h_out holds dev::RF_* once the stream has been waited for
     // decoy: fs.k_counts holds the screen's V and H of these reads (run_decoy_screen, on the same stream), and the flags see its verdict
     void run_read_filter(FilterScratch& fs, const ReadFilter& f, const uint8_t* d_qual, uint32_t bias, const uint64_t* d_offsets, uint64_t n_reads,
-        uint64_t n_bases, unsigned long long* d_sums, uint8_t* d_flags, hipStream_t stream, bool decoy = false);
+        uint64_t n_bases, unsigned long long* d_sums, uint8_t* d_flags, hipStream_t stream, bool decoy = false, bool complexity = false);
+    // D of every read of the batch into fs.x_diff, queued on `stream`, which the flags then hold against f.min_complexity: a packed batch's
+    // bitmap (fs.t_nbits) first, unless nbits_ready.  true: fs.t_nbits holds the batch's bitmap afterwards
+    bool run_read_complexity(FilterScratch& fs, const uint8_t* d_bases, bool packed, const uint64_t* d_npos, uint64_t n_npos, const uint64_t* d_offsets,
+        uint64_t n_reads, uint64_t n_bases, hipStream_t stream, bool nbits_ready = false);
     // room for the trim kernels over n_reads reads (own_ranges: the caller brings no begin / end arrays)
     // adapters: room for the cut words too, and for a bitmap over bitmap_bases packed bases (0: text, or no listed position)
     void ensure_trim_scratch(FilterScratch& fs, uint64_t n_reads, uint64_t n_npos, bool use_qual, bool own_ranges, bool adapters = false, uint64_t bitmap_bases = 0);

@@ -30,6 +30,7 @@
 #include "adapter_args.h"
 #include "decoy_args.h"
 #include "mask_args.h"
+#include "poly_args.h"
 
 namespace {
 
@@ -66,6 +67,7 @@ struct Args {
     uint32_t trim_qual_milli = 0, trim_window = 0;
     uint32_t mask_qual = 0; // --mask-qual Q: base masking (include/drprg_hip.h "base masking"); 0 = not set
     drprg::AdapterArgs adapters; // --adapter SEQ, --adapter-error E, --adapter-min-overlap O (include/drprg_hip.h "adapter trimming")
+    drprg::PolyArgs poly; // --poly-tail LETTERS, --poly-min-len M, --min-complexity P (include/drprg_hip.h "poly tails", "read complexity")
     drprg::DecoyArgs decoy; // --decoy FASTA, --decoy-k K, --decoy-min-frac F, --decoy-min-kmers M (include/drprg_hip.h "decoy screen")
     std::string outdir = "pandora", vcf_refs;
     std::vector<std::string> positional;
@@ -87,6 +89,7 @@ void usage()
         "                   [--dedup] [--min-read-len L] [--max-read-len L] [--min-read-qual Q]\n"
         "                   [--trim-front N] [--trim-tail N] [--trim-qual Q [--trim-window W]]\n"
         "                   [--adapter SEQ]... [--adapter-error E] [--adapter-min-overlap O] [--adapter-indels] [--front-adapter SEQ]...\n"
+        "                   [--poly-tail LETTERS [--poly-min-len M]] [--min-complexity P]\n"
         "                   [--mask-qual Q] [--decoy FASTA]... [--decoy-k K] [--decoy-min-frac F] [--decoy-min-kmers M]\n"
         "                   [--vcf-refs FASTA] [-t N] [-w W] [-k K] [-c N] [-I] [-K] [-e RATE] [--max-diff N] <prg> <reads>\n"
         "  pandora discover [same mapping options] <prg> <query.tsv>\n"
@@ -119,6 +122,13 @@ void usage()
         "  --adapter-indels: an occurrence may carry insertions and deletions too (edit distance at most floor(m * E) over the whole adapter).\n"
         "  --front-adapter SEQ (up to 4 times; needs --adapter-indels): 5' adapters, cut off the reads' starts behind the 3' cut.\n"
         "                Still missing: anchored adapters, pair overlap, indels inside an adapter that the read's end cuts short.\n"
+        "  --poly-tail LETTERS (letters of ACGT, e.g. G or ACGT), --poly-min-len M (2 to 255, default 10): every read loses its longest suffix of\n"
+        "                at least M bases that begins with one of the letters and holds at most min(n / 8, 5) other bases -- the tails two-colour\n"
+        "                instruments (NextSeq, NovaSeq) leave when a cluster goes dark, which carry HIGH qualities.  On the device, behind --trim-*\n"
+        "                and both --adapter sides, in front of everything else: the run is that of a file of the cut reads.  Needs no qualities.\n"
+        "  --min-complexity P (a whole percentage, 1 to 100; fastp's default is 30): a read is dropped when fewer than P %% of its neighbouring\n"
+        "                base pairs differ (an unknown base differs from every letter) -- on the device, behind --trim-*, --adapter, --poly-tail,\n"
+        "                --mask-qual and --min/max-read-*, in front of --decoy.  This build's own rules, after fastp.  Default: off.\n"
         "  --mask-qual Q (a whole Phred value, 1 to 93): every base whose quality is below Q becomes an unknown base -- on the device, behind\n"
         "                --trim-* and --adapter and in front of everything else: the run is that of a file in which those bases are the letter N.\n"
         "                The read keeps its length, its place in the depth arithmetic and its mean quality; only the k-mers that hold a masked\n"
@@ -216,6 +226,16 @@ Args parse(int argc, char** argv)
             const std::string e = a.adapters.set_overlap(need(i));
             if (!e.empty()) die(e, 2);
         }
+        else if (s == "--poly-tail") {
+            const std::string e = a.poly.set_letters(need(i));
+            if (!e.empty()) die(e, 2);
+        } else if (s == "--poly-min-len") {
+            const std::string e = a.poly.set_min_len(need(i));
+            if (!e.empty()) die(e, 2);
+        } else if (s == "--min-complexity") {
+            const std::string e = a.poly.set_complexity(need(i));
+            if (!e.empty()) die(e, 2);
+        }
         else if (s == "--decoy") {
             const std::string e = a.decoy.add(need(i));
             if (!e.empty()) die(e, 2);
@@ -256,6 +276,7 @@ Args parse(int argc, char** argv)
     if (a.trim_window && !a.trim_qual_milli) die("--trim-window belongs to --trim-qual", 2);
     if (const std::string e = a.adapters.check(); !e.empty()) die(e, 2);
     if (const std::string e = a.decoy.check(); !e.empty()) die(e, 2);
+    if (const std::string e = a.poly.check(); !e.empty()) die(e, 2);
     if (const char* d = std::getenv("DRPRG_HIP_DEVICE")) a.device = std::atoi(d);
     return a;
 }
@@ -303,6 +324,7 @@ drprg_hip_ctx* open_ctx(const Args& a)
     if (int rc = drprg_hip_set_read_filter(ctx, a.min_read_len, a.max_read_len, a.min_read_qual_milli)) die(drprg_hip_last_error(ctx), -rc);
     if (int rc = drprg_hip_set_read_trim(ctx, a.trim_front, a.trim_tail, a.trim_qual_milli, a.trim_window)) die(drprg_hip_last_error(ctx), -rc);
     if (int rc = drprg_hip_set_base_mask(ctx, a.mask_qual)) die(drprg_hip_last_error(ctx), -rc);
+    if (int rc = a.poly.set_on(ctx, drprg_hip_set_poly_trim, drprg_hip_set_min_complexity)) die(drprg_hip_last_error(ctx), -rc);
     if (a.adapters.any()) {
         if (int rc = a.adapters.set_on(ctx, drprg_hip_set_adapters, drprg_hip_set_adapters2)) die(drprg_hip_last_error(ctx), -rc);
     }
@@ -357,7 +379,7 @@ std::string run_tag(const Args& a, const std::string& reads)
                   + std::to_string((unsigned long long)a.trim_tail) + "/" + std::to_string(a.trim_qual_milli) + "/"
                   + std::to_string(a.trim_qual_milli ? (a.trim_window ? a.trim_window : 4u) : 0u)
                                                             : std::string())
-        + (a.adapters.any() ? a.adapters.tag() : std::string()) + (a.mask_qual ? "|B" + std::to_string(a.mask_qual) : std::string())
+        + (a.adapters.any() ? a.adapters.tag() : std::string()) + a.poly.tag() + (a.mask_qual ? "|B" + std::to_string(a.mask_qual) : std::string())
         + (a.decoy.any() ? a.decoy.tag() : std::string());
 }
 
@@ -432,9 +454,15 @@ void report_filter(drprg_hip_ctx* ctx, const Args& a)
     if (a.verbose && !a.adapters.front.empty() && drprg_hip_front_adapter_info(ctx, fi) == 0)
         std::printf("[pandora-hip] front adapter trimming: reads_seen=%llu bases_seen=%llu reads_cut=%llu bases_cut=%llu reads_emptied=%llu\n", (unsigned long long)fi[0],
             (unsigned long long)fi[1], (unsigned long long)fi[2], (unsigned long long)fi[3], (unsigned long long)fi[4]);
+    if (a.verbose && a.poly.tails() && drprg_hip_poly_trim_info(ctx, fi) == 0)
+        std::printf("[pandora-hip] poly tail trimming: reads_seen=%llu bases_seen=%llu reads_cut=%llu bases_cut=%llu reads_emptied=%llu\n", (unsigned long long)fi[0],
+            (unsigned long long)fi[1], (unsigned long long)fi[2], (unsigned long long)fi[3], (unsigned long long)fi[4]);
     if (a.verbose && a.mask_qual && drprg_hip_base_mask_info(ctx, fi) == 0)
         std::printf("[pandora-hip] base masking: reads_seen=%llu bases_seen=%llu reads_masked=%llu bases_masked=%llu bases_already_unknown=%llu\n",
             (unsigned long long)fi[0], (unsigned long long)fi[1], (unsigned long long)fi[2], (unsigned long long)fi[3], (unsigned long long)fi[4]);
+    if (a.verbose && a.poly.min_complexity && drprg_hip_complexity_info(ctx, fi) == 0)
+        std::printf("[pandora-hip] complexity filter: reads_seen=%llu bases_seen=%llu reads_dropped=%llu bases_dropped=%llu\n", (unsigned long long)fi[0],
+            (unsigned long long)fi[1], (unsigned long long)fi[2], (unsigned long long)fi[3]);
     if (a.verbose && a.decoy.any() && drprg_hip_decoy_info(ctx, fi) == 0)
         std::printf("[pandora-hip] decoy screen: kmers=%llu reads_seen=%llu bases_seen=%llu reads_dropped=%llu bases_dropped=%llu\n", (unsigned long long)fi[0],
             (unsigned long long)fi[2], (unsigned long long)fi[3], (unsigned long long)fi[4], (unsigned long long)fi[5]);

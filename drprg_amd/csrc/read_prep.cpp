@@ -1,5 +1,5 @@
 // read_prep.cpp -- what happens to a host block before it is mapped: staging sets and the copies into them, the read filter, read
-// trimming, adapter trimming, base masking and the decoy screen with their drivers, and the packers of the harness path.  See mapper.h.
+// trimming, adapter trimming, poly tails, base masking, the low-complexity filter and the decoy screen with their drivers, and the packers of the harness path.  See mapper.h.
 #include "mapper.h"
 #include <algorithm>
 #include <hip/hip_runtime.h>
@@ -103,7 +103,9 @@ void Mapper::only_empty_reads(uint64_t n_reads, const ReadFilter& f, bool keepin
 {
     o.dropped_short = f.min_len ? n_reads : 0;
     o.reads_kept = o.mapped_reads = n_reads - o.dropped_short;
+    if (f.poly()) o.poly.reads_seen = n_reads; // (no base: no tail)
     if (f.mask_qual) o.mask.reads_seen = n_reads; // (no base: nothing to mask)
+    if (f.min_complexity) o.cplx.reads_judged = o.reads_kept; // (no pair: the threshold keeps them)
     if (f.decoy()) o.decoy.reads_judged = o.reads_kept; // (no window, no hit: the screen keeps them)
     count_unmapped(o.reads_kept, keeping);
 }
@@ -203,9 +205,12 @@ void Mapper::ensure_filter_scratch(FilterScratch& fs, uint64_t n_reads, uint64_t
 }
 
 void Mapper::run_read_filter(FilterScratch& fs, const ReadFilter& f, const uint8_t* d_qual, uint32_t bias, const uint64_t* d_offsets, uint64_t n_reads,
-    uint64_t n_bases, unsigned long long* d_sums, uint8_t* d_flags, hipStream_t stream, bool decoy)
+    uint64_t n_bases, unsigned long long* d_sums, uint8_t* d_flags, hipStream_t stream, bool decoy, bool complexity)
 {
     dev::ReadFilterArgs a {};
+    if (complexity) {
+        a.cplx_diff = fs.x_diff.data(); a.cplx_percent = f.min_complexity;
+    }
     if (decoy) {
         a.decoy_valid = fs.k_counts.data(); a.decoy_hits = fs.k_counts.data() + n_reads;
         a.decoy_frac_milli = f.decoy_frac_milli; a.decoy_min_kmers = f.decoy_min_kmers;
@@ -285,11 +290,12 @@ void Mapper::run_read_trim(FilterScratch& fs, const ReadFilter& f, const uint8_t
     dev::ReadTrimArgs a {};
     dev::AdapterEditSets edit {};
     const bool indels = pts && f.adapter_indels && f.any_adapters();
+    if (pts && f.trim_points()) a.pts = *pts;
     if (pts && f.any_adapters()) {
-        a.pts = *pts;
         if (indels) edit = dev::AdapterEditSets { f.adapters, f.front_adapters, f.eq3, f.eq5 };
         else a.ad = f.adapters;
     }
+    if (pts && f.poly()) { a.poly_letters = f.poly_letters; a.poly_min_len = f.poly_min_len; }
     a.qual = d_qual; a.bias = bias; a.offsets = d_offsets; a.rev = d_rev; a.n_reads = n_reads; a.n_bases = n_bases;
     a.front = f.trim_front; a.tail = f.trim_tail; a.qual_milli = f.trim_qual_milli; a.window = f.trim_window;
     a.first = fs.t_first.data(); a.last = fs.t_last.data(); a.begin = d_begin; a.end = d_end; a.klen = fs.t_klen.data(); a.noff = fs.t_offsets.data();
@@ -336,6 +342,68 @@ void Mapper::adapter_trim_device(const ReadFilter& f, const uint8_t* d_text, con
         res[6 + i] = fs.t_out[dev::RT_FA_BASES_SEEN + i];
     }
     res[10] = fs.t_out[dev::RT_OFFSETS];
+}
+
+// ---- poly tails ----------------------------------------------------------------------------------------------------------------------
+void Mapper::poly_trim_device(const ReadFilter& f, const uint8_t* d_text, const uint32_t* d_words, const uint64_t* d_npos, uint64_t n_npos, const uint64_t* d_offsets,
+    uint64_t n_reads, uint64_t n_bases, const uint64_t* d_begin, uint64_t* d_end, uint64_t res[6], hipStream_t stream)
+{
+    for (int i = 0; i < 6; ++i) res[i] = 0;
+    if (!f.poly()) throw Error(DRPRG_EINVAL, "poly-tail trimming: no letter is set (drprg_hip_set_poly_trim)");
+    if (n_reads == 0) return;
+    stream = device_entry(stream, !d_offsets || !d_begin || !d_end || (n_bases && !d_text && !d_words) || (n_npos && !d_npos), n_reads);
+    FilterScratch& fs = filter_api_;
+    ensure_trim_scratch(fs, n_reads, 0, false, false, true, d_words && n_npos ? n_bases : 0);
+    dev::AdapterPoints p = adapter_points(fs, d_words ? reinterpret_cast<const uint8_t*>(d_words) : d_text, d_words != nullptr, d_npos, n_npos, n_bases, stream);
+    p.offsets = d_offsets; p.begin = d_begin; p.end = d_end; p.n_reads = n_reads; p.n_bases = n_bases;
+    HIPCHK(hipMemsetAsync(fs.t_work.data(), 0, dev::RT_WORDS * sizeof(unsigned long long), stream));
+    HIPCHK(dev::launch_poly_tail(p, f.poly_letters, f.poly_min_len, d_end, nullptr, fs.t_work.data(), stream));
+    HIPCHK(hipMemcpyAsync(fs.t_out.data(), fs.t_work.data(), dev::RT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    res[0] = n_reads;
+    for (int i = 0; i < 4; ++i) res[1 + i] = fs.t_out[dev::RT_PT_BASES_SEEN + i];
+    res[5] = fs.t_out[dev::RT_OFFSETS];
+}
+
+// ---- the low-complexity filter -------------------------------------------------------------------------------------------------------
+bool Mapper::run_read_complexity(FilterScratch& fs, const uint8_t* d_bases, bool packed, const uint64_t* d_npos, uint64_t n_npos, const uint64_t* d_offsets,
+    uint64_t n_reads, uint64_t n_bases, hipStream_t stream, bool nbits_ready)
+{
+    if (n_bases >= dev::CX_MAX_READ) // (a read is no longer than its block: D is a 32-bit word)
+        throw Error(DRPRG_EOVERFLOW, "read complexity: a block of 2^32 bases or more; the pairs of a read are counted in a 32-bit word");
+    grow(fs.x_diff, n_reads);
+    dev::ComplexityArgs a { packed ? nullptr : d_bases, packed ? reinterpret_cast<const uint32_t*>(d_bases) : nullptr, nullptr, d_offsets, n_reads, n_bases,
+        fs.x_diff.data() };
+    if (packed && !nbits_ready && n_npos) { // the position list as a bitmap, as adapter_points makes it
+        const uint64_t n16 = (n_bases + 15) / 16 + 8;
+        grow(fs.t_nbits, n16);
+        HIPCHK(hipMemsetAsync(fs.t_nbits.data(), 0, n16 * sizeof(uint16_t), stream));
+        HIPCHK(dev::launch_mark_npos(d_npos, n_npos, n_bases, fs.t_nbits.data(), stream));
+        nbits_ready = true;
+    }
+    if (packed && nbits_ready) a.nbits = fs.t_nbits.data();
+    HIPCHK(dev::launch_read_diff(a, stream));
+    return packed && nbits_ready;
+}
+
+void Mapper::complexity_device(const ReadFilter& f, const uint8_t* d_text, const uint32_t* d_words, const uint64_t* d_npos, uint64_t n_npos, const uint64_t* d_offsets,
+    uint64_t n_reads, uint64_t n_bases, uint32_t* d_diff, uint8_t* d_flags, uint64_t res[3], hipStream_t stream)
+{
+    for (int i = 0; i < 3; ++i) res[i] = 0;
+    if (!f.min_complexity) throw Error(DRPRG_EINVAL, "read complexity: no threshold is set (drprg_hip_set_min_complexity)");
+    if (n_reads == 0) return;
+    stream = device_entry(stream, !d_offsets || !d_flags || (n_bases && !d_text && !d_words) || (n_npos && !d_npos), n_reads);
+    FilterScratch& fs = filter_api_;
+    run_read_complexity(fs, d_words ? reinterpret_cast<const uint8_t*>(d_words) : d_text, d_words != nullptr, d_npos, n_npos, d_offsets, n_reads, n_bases, stream);
+    if (!fs.x_work) fs.x_work.alloc(3);
+    if (!fs.x_out) fs.x_out.alloc(3);
+    const dev::ComplexityArgs a { d_text, d_words, nullptr, d_offsets, n_reads, n_bases, fs.x_diff.data() };
+    HIPCHK(hipMemsetAsync(fs.x_work.data(), 0, 3 * sizeof(unsigned long long), stream));
+    HIPCHK(dev::launch_complexity_verdict(a, f.min_complexity, d_flags, fs.x_work.data(), reinterpret_cast<uint32_t*>(fs.x_work.data() + 2), stream));
+    HIPCHK(hipMemcpyAsync(fs.x_out.data(), fs.x_work.data(), 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    if (d_diff) HIPCHK(hipMemcpyAsync(d_diff, fs.x_diff.data(), n_reads * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    for (int i = 0; i < 3; ++i) res[i] = fs.x_out[i];
 }
 
 // ---- the decoy screen ----------------------------------------------------------------------------------------------------------------
@@ -507,7 +575,7 @@ bool Mapper::trim_block(const HostBatch& hb, const ReadFilter& f, Stage& st, Dev
     const uint64_t n_reads = src.n_reads, n_bases = src.n_bases;
     const uint8_t* d_rev = hb.bam && hb.reverse ? st.d_reverse.data() : nullptr; // (BAM: QUAL stays in stored order; the bases were reversed by bam_pack_kernel)
     dev::AdapterPoints pts {}; // (adapters: sought in what the crops and the quality trim leave, bases in read orientation; a packed block's bitmap first)
-    if (f.any_adapters()) pts = adapter_points(fs, src.d_bases, src.packed, src.d_npos, src.n_npos, n_bases, cs);
+    if (f.trim_points()) pts = adapter_points(fs, src.d_bases, src.packed, src.d_npos, src.n_npos, n_bases, cs); // (poly tails look at the same bases)
     run_read_trim(fs, f, d_qual, hb.qual_bias, src.d_offsets, d_rev, n_reads, n_bases, fs.t_begin.data(), fs.t_end.data(), src.d_npos, src.n_npos, cs, &pts);
     HIPCHK(hipStreamSynchronize(cs)); // the trim's read-back: the trimmed sizes are known before the filter is launched
     const unsigned long long* t = fs.t_out.data();
@@ -520,7 +588,9 @@ bool Mapper::trim_block(const HostBatch& hb, const ReadFilter& f, Stage& st, Dev
         o.adapter = AdapterOutcome { n_reads, t[dev::RT_AD_BASES_SEEN], t[dev::RT_AD_READS_CUT], t[dev::RT_AD_BASES_CUT], t[dev::RT_AD_EMPTIED] };
     if (f.front_adapters.n)
         o.front = AdapterOutcome { n_reads, t[dev::RT_FA_BASES_SEEN], t[dev::RT_FA_READS_CUT], t[dev::RT_FA_BASES_CUT], t[dev::RT_FA_EMPTIED] };
-    if (!t[dev::RT_LOST_READS] && !t[dev::RT_AD_READS_CUT] && !t[dev::RT_FA_READS_CUT]) return true; // the block lost no base to any cause
+    if (f.poly()) o.poly = PolyOutcome { n_reads, t[dev::RT_PT_BASES_SEEN], t[dev::RT_PT_READS_CUT], t[dev::RT_PT_BASES_CUT], t[dev::RT_PT_EMPTIED] };
+    // (a read cut by a tail has lost a base like any other)
+    if (!t[dev::RT_LOST_READS] && !t[dev::RT_AD_READS_CUT] && !t[dev::RT_FA_READS_CUT] && !t[dev::RT_PT_READS_CUT]) return true; // the block lost no base to any cause
     const uint64_t nb = t[dev::RT_KEPT_BASES], n_list = src.n_npos ? t[dev::RT_KEPT_NPOS] : 0;
     o.bases_seen = nb;
     if (nb == 0) return false;
@@ -590,8 +660,12 @@ void Mapper::filter_block(const HostBatch& hb, const ReadFilter& f, FilterScratc
     const hipStream_t cs = copy_stream_;
     // (the screen in front of the filter's scans, which then see one verdict: the block as the trim stage left it, whatever its form)
     // (behind the mask a packed block's bitmap is there already, and holds the masked positions, which the list does not yet)
-    if (f.decoy()) run_decoy_screen(fs, f, src.d_bases, src.packed, src.d_npos, src.n_npos, src.d_offsets, src.n_reads, src.n_bases, cs, f.mask_qual != 0);
-    run_read_filter(fs, f, d_qual, hb.qual_bias, src.d_offsets, src.n_reads, src.n_bases, fs.d_qsum.data(), fs.d_flag.data(), cs, f.decoy());
+    // (the pair count in front of both: the threshold judges the block as the mask left it, and its bitmap serves the screen too)
+    bool nbits_ready = f.mask_qual != 0 && src.packed;
+    if (f.min_complexity)
+        nbits_ready = run_read_complexity(fs, src.d_bases, src.packed, src.d_npos, src.n_npos, src.d_offsets, src.n_reads, src.n_bases, cs, nbits_ready) || nbits_ready;
+    if (f.decoy()) run_decoy_screen(fs, f, src.d_bases, src.packed, src.d_npos, src.n_npos, src.d_offsets, src.n_reads, src.n_bases, cs, nbits_ready);
+    run_read_filter(fs, f, d_qual, hb.qual_bias, src.d_offsets, src.n_reads, src.n_bases, fs.d_qsum.data(), fs.d_flag.data(), cs, f.decoy(), f.min_complexity != 0);
     HIPCHK(hipStreamSynchronize(cs));
     if (trim_err) throw Error(DRPRG_EIO, "read trimming: the block's offsets and the trimmed ranges do not fit each other");
     const unsigned long long* h = fs.h_out.data();
@@ -602,6 +676,8 @@ void Mapper::filter_block(const HostBatch& hb, const ReadFilter& f, FilterScratc
     o.dropped_lowq = h[dev::RF_LOWQ];
     o.reads_kept = h[dev::RF_KEPT_READS];
     o.bases_kept = h[dev::RF_KEPT_BASES];
+    if (f.min_complexity)
+        o.cplx = ComplexityOutcome { h[dev::RF_CPLX_READS], h[dev::RF_CPLX_BASES], h[dev::RF_CPLX_DROPPED], h[dev::RF_CPLX_DROPPED_BASES] };
     if (f.decoy())
         o.decoy = DecoyOutcome { h[dev::RF_DECOY_READS], h[dev::RF_DECOY_BASES], h[dev::RF_DECOY_DROPPED], h[dev::RF_DECOY_DROPPED_BASES], h[dev::RF_DECOY_VALID],
             h[dev::RF_DECOY_HITS] };
@@ -696,7 +772,7 @@ void Mapper::map_host_filtered(const HostBatch& hb, const ReadFilter& f, uint64_
     FilterScratch& fs = st.filt;
     const uint64_t n_npos = hb.packed || hb.bam ? hb.n_npos : 0;
     ensure_filter_scratch(fs, n_reads, f.wants_qual() ? n_bases : 0, true, f.use_qual());
-    if (f.trims()) ensure_trim_scratch(fs, n_reads, n_npos, f.trim_qual_milli != 0, true, f.any_adapters(), n_npos ? n_bases : 0);
+    if (f.trims()) ensure_trim_scratch(fs, n_reads, n_npos, f.trim_qual_milli != 0, true, f.trim_points(), n_npos ? n_bases : 0);
     DeviceBatch src = copy_to_stage(hb, st, cs, cs);
     if (f.wants_qual()) {
         HIPCHK(hipMemcpyAsync(fs.d_qual.data(), hb.qual, n_bases, hipMemcpyHostToDevice, cs));
@@ -742,6 +818,18 @@ Mapper::AdapterOutcome& Mapper::AdapterOutcome::operator+=(const AdapterOutcome&
     return *this;
 }
 
+Mapper::PolyOutcome& Mapper::PolyOutcome::operator+=(const PolyOutcome& o)
+{
+    reads_seen += o.reads_seen; bases_seen += o.bases_seen; reads_cut += o.reads_cut; bases_cut += o.bases_cut; reads_emptied += o.reads_emptied;
+    return *this;
+}
+
+Mapper::ComplexityOutcome& Mapper::ComplexityOutcome::operator+=(const ComplexityOutcome& o)
+{
+    reads_judged += o.reads_judged; bases_judged += o.bases_judged; reads_dropped += o.reads_dropped; bases_dropped += o.bases_dropped;
+    return *this;
+}
+
 Mapper::MaskOutcome& Mapper::MaskOutcome::operator+=(const MaskOutcome& o)
 {
     reads_seen += o.reads_seen; bases_seen += o.bases_seen; reads_masked += o.reads_masked; bases_masked += o.bases_masked;
@@ -758,6 +846,7 @@ Mapper::DecoyOutcome& Mapper::DecoyOutcome::operator+=(const DecoyOutcome& o)
 
 Mapper::FilterOutcome& Mapper::FilterOutcome::operator+=(const FilterOutcome& o)
 {
+    poly += o.poly; cplx += o.cplx;
     mask += o.mask;
     decoy += o.decoy;
     trim += o.trim; adapter += o.adapter; front += o.front;

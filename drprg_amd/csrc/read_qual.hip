@@ -141,13 +141,15 @@ __global__ __launch_bounds__(RQ_THREADS) void read_qual_kernel(const uint8_t* __
 // flag[i] = read i passes the rule; flag32[i] and klen[i]: the same as a word, and the read's length if it is kept -- what the two
 // exclusive scans read (entry n_reads of both: 0).  work[RF_SHORT .. RF_LOWQ] count the dropped reads, work[RF_OFFSETS] is set when the
 // offsets do not ascend or end at n_bases.  Under a decoy set (a.decoy_valid != null) a read that passed these tests is held against the
-// decoy screen's verdict (dc_drops) and counted in work[RF_DECOY_*].
+// decoy screen's verdict (dc_drops) and counted in work[RF_DECOY_*]; under a complexity threshold (a.cplx_diff != null) it is held
+// against that verdict first (cx_drops, poly_piece.h), counted in work[RF_CPLX_*], and the decoy verdict sees only what it kept.
 __global__ __launch_bounds__(RQ_THREADS) void read_flags_kernel(ReadFilterArgs a)
 {
     __shared__ uint32_t s_n[3];
-    __shared__ unsigned long long s_d[6];
+    __shared__ unsigned long long s_d[6], s_c[4];
     if (threadIdx.x < 3) s_n[threadIdx.x] = 0;
     if (threadIdx.x < 6) s_d[threadIdx.x] = 0;
+    if (threadIdx.x < 4) s_c[threadIdx.x] = 0;
     __syncthreads();
     const uint64_t i = (uint64_t)blockIdx.x * RQ_THREADS + threadIdx.x;
     if (i == a.n_reads) {
@@ -169,7 +171,16 @@ __global__ __launch_bounds__(RQ_THREADS) void read_flags_kernel(ReadFilterArgs a
             if (__umul64hi(len, a.T) == 0 && S > len * a.T) why = 2;
         }
         if (why >= 0) atomicAdd(&s_n[why], 1u);
-        else if (a.decoy_valid) {
+        else if (a.cplx_diff) { // the low-complexity verdict, on what the length and quality tests kept
+            atomicAdd(&s_c[0], 1ull);
+            atomicAdd(&s_c[1], (unsigned long long)len);
+            if (cx_drops(a.cplx_diff[i], len, a.cplx_percent)) {
+                why = 4;
+                atomicAdd(&s_c[2], 1ull);
+                atomicAdd(&s_c[3], (unsigned long long)len);
+            }
+        }
+        if (why < 0 && a.decoy_valid) {
             const uint32_t V = a.decoy_valid[i], H = a.decoy_hits[i];
             atomicAdd(&s_d[0], 1ull);
             atomicAdd(&s_d[1], (unsigned long long)len);
@@ -188,6 +199,7 @@ __global__ __launch_bounds__(RQ_THREADS) void read_flags_kernel(ReadFilterArgs a
     __syncthreads();
     if (threadIdx.x < 3 && s_n[threadIdx.x]) atomicAdd(&a.work[RF_SHORT + threadIdx.x], (unsigned long long)s_n[threadIdx.x]);
     if (threadIdx.x < 6 && s_d[threadIdx.x]) atomicAdd(&a.work[RF_DECOY_READS + threadIdx.x], s_d[threadIdx.x]);
+    if (threadIdx.x < 4 && s_c[threadIdx.x]) atomicAdd(&a.work[RF_CPLX_READS + threadIdx.x], s_c[threadIdx.x]);
 }
 
 // the totals of the two scans beside the counts, and everything into `out` (page-locked host memory, or device memory)

@@ -222,7 +222,7 @@ __global__ void read_trim_result_kernel(ReadTrimArgs a, const uint32_t* __restri
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     a.out[RT_KEPT_BASES] = a.noff[a.n_reads];
     for (int k = RT_LOST_READS; k <= RT_EMPTIED; ++k) a.out[k] = a.work[k];
-    for (int k = RT_AD_BASES_SEEN; k <= RT_FA_EMPTIED; ++k) a.out[k] = a.work[k];
+    for (int k = RT_AD_BASES_SEEN; k <= RT_PT_EMPTIED; ++k) a.out[k] = a.work[k];
     a.out[RT_BAD_AT] = a.work[RT_OFFSETS] ? ~0ull : (a.work[RT_BAD_AT] == ~0ull ? 0ull : a.work[RT_BAD_AT]);
     a.out[RT_KEPT_NPOS] = n_kept_npos ? *n_kept_npos : 0;
 }
@@ -309,11 +309,12 @@ hipError_t launch_read_trim(const ReadTrimArgs& a, const ReadTrimNpos& np, hipSt
     }
     hipLaunchKernelGGL(trim_tables_kernel, dim3((uint32_t)((a.n_reads + 1 + RT_THREADS - 1) / RT_THREADS)), dim3(RT_THREADS), 0, stream, a);
     HIP_TRY(hipGetLastError());
-    if (edit || a.ad.n) { // adapter trimming: on the ranges the tables kernel left, before the new lengths are scanned
+    if (edit || a.ad.n || a.poly_letters) { // adapter trimming, then poly tails: on the ranges the tables kernel left, before the new lengths are scanned
         AdapterPoints pts = a.pts;
         pts.offsets = a.offsets; pts.begin = a.begin; pts.end = a.end; pts.n_reads = a.n_reads; pts.n_bases = a.n_bases;
         if (edit) HIP_TRY(launch_adapter_edit(pts, edit->ad3, edit->eq3, edit->ad5, edit->eq5, a.begin, a.end, a.klen, a.work, stream)); // (adapter_edit.hip: 3', then 5')
-        else HIP_TRY(launch_adapter_trim(pts, a.ad, a.end, a.klen, a.work, stream));                                        // (adapter_trim.hip)
+        else if (a.ad.n) HIP_TRY(launch_adapter_trim(pts, a.ad, a.end, a.klen, a.work, stream));                            // (adapter_trim.hip)
+        if (a.poly_letters) HIP_TRY(launch_poly_tail(pts, a.poly_letters, a.poly_min_len, a.end, a.klen, a.work, stream));  // (poly_tail.hip)
     }
     HIP_TRY(rocprim::exclusive_scan(a.temp, temp_bytes, a.klen, a.noff, (uint64_t)0, (size_t)a.n_reads + 1, rocprim::plus<uint64_t>(), stream));
     const uint32_t* kept_npos = nullptr;

@@ -337,6 +337,53 @@ class Context:
                                                   stream), self._h)
         return tuple(int(x) for x in out)
 
+    # ---- poly tails (include/drprg_hip.h: drprg_hip_set_poly_trim) -----------------------------
+    def set_poly_trim(self, letters="", min_len=10):
+        """from the next map_fastx on, every read loses its longest suffix of at least min_len (2..255) bases that begins with one of
+        `letters` (distinct letters of ACGT, e.g. "G") and holds at most min(n // 8, 5) other bases -- on the device, behind the crops, the
+        quality trim and both adapter sides; "" or None clears it"""
+        if letters and int(min_len) != min_len:
+            raise ValueError(f"a tail's shortest length is a whole number from 2 to 255, not {min_len!r}")
+        s = letters.encode() if isinstance(letters, str) else (bytes(letters) if letters else None)
+        _check(lib.drprg_hip_set_poly_trim(self._h, s or None, int(min_len) if s else 0), self._h)
+
+    def poly_trim_info(self):
+        out = (C.c_uint64 * 5)()
+        _check(lib.drprg_hip_poly_trim_info(self._h, out), self._h)
+        names = ("reads_seen", "bases_seen", "reads_cut", "bases_cut", "reads_emptied")
+        return dict(zip(names, (int(x) for x in out)))
+
+    def poly_trim_device(self, d_text, d_words, d_npos, n_npos, d_offsets, n_reads, n_bases, d_begin, d_end, stream=None):
+        """the tail cut alone on device buffers (addresses as integers): the buffers of adapter_trim_device; d_end receives the cut ends;
+        returns the call's (reads seen, bases seen, reads cut, bases cut, reads emptied)"""
+        out = (C.c_uint64 * 5)()
+        _check(lib.drprg_hip_poly_trim_device(self._h, d_text, d_words, d_npos, int(n_npos), d_offsets, int(n_reads), int(n_bases), d_begin, d_end, out,
+                                              stream), self._h)
+        return tuple(int(x) for x in out)
+
+    # ---- read complexity (include/drprg_hip.h: drprg_hip_set_min_complexity) -------------------
+    def set_min_complexity(self, percent=0):
+        """from the next map_fastx on, a read of L >= 2 bases is dropped when fewer than percent % (a whole number, 1..100) of its L - 1
+        neighbouring base pairs differ -- on the device, behind the trim stage and the mask, on the reads the length and quality tests
+        kept, in front of the decoy screen's verdict; 0 clears it"""
+        if int(percent) != percent:
+            raise ValueError(f"a complexity threshold is a whole percentage from 0 to 100, not {percent!r}")
+        _check(lib.drprg_hip_set_min_complexity(self._h, int(percent)), self._h)
+
+    def complexity_info(self):
+        out = (C.c_uint64 * 4)()
+        _check(lib.drprg_hip_complexity_info(self._h, out), self._h)
+        names = ("reads_seen", "bases_seen", "reads_dropped", "bases_dropped")
+        return dict(zip(names, (int(x) for x in out)))
+
+    def complexity_device(self, d_text, d_words, d_npos, n_npos, d_offsets, n_reads, n_bases, d_diff, d_flags, stream=None):
+        """the complexity kernels alone on device buffers (addresses as integers): the bases as for adapter_trim_device; d_diff (u32 per
+        read, may be None) receives D, d_flags (u8 per read) 1 for a kept read; returns the call's (reads dropped, bases dropped)"""
+        out = (C.c_uint64 * 2)()
+        _check(lib.drprg_hip_complexity_device(self._h, d_text, d_words, d_npos, int(n_npos), d_offsets, int(n_reads), int(n_bases), d_diff, d_flags, out,
+                                               stream), self._h)
+        return tuple(int(x) for x in out)
+
     # ---- base masking (include/drprg_hip.h: drprg_hip_set_base_mask) ---------------------------
     def set_base_mask(self, min_qual=0):
         """from the next map_fastx on, every base whose Phred quality is below min_qual (a whole number, 1..93) becomes an unknown base on

@@ -608,6 +608,65 @@ int drprg_hip_set_base_mask(drprg_hip_ctx* ctx, uint32_t min_qual);
 int drprg_hip_base_mask_info(drprg_hip_ctx* ctx, uint64_t out[5]);
 int drprg_hip_base_mask_device(drprg_hip_ctx* ctx, const void* d_qual, uint32_t qual_bias, const void* d_offsets, const void* d_rev, uint64_t n_reads,
     uint64_t n_bases, void* d_text, void* d_words, const void* d_npos, uint64_t n_npos, void* d_npos_out, uint64_t npos_cap, uint64_t out[6], void* hip_stream);
+/* ---- Poly tails: runs of one letter cut off read ends on the device, as the reads arrive.  THIS BUILD'S OWN RULE, stated from memory of
+ * fastp's poly-G / poly-X tail trimming (which fastp turns on by itself for NextSeq and NovaSeq data: on two-colour chemistry "no signal" is
+ * called as G, with HIGH qualities, so neither quality setting touches such a tail); neither pandora nor drprg has one and nothing in them
+ * pins it.
+ *   The comparison, shared with "read complexity" below: case-insensitive; every byte that is not one of ACGTacgt is the one unknown base
+ *   U -- a listed position of a packed block and a base drprg_hip_set_base_mask masked included --; U equals U and differs from every letter.
+ *   Settings, per context: a non-empty set S of letters from ACGT, and M, a whole number in 2..255 (the executables' default: 10).
+ *   The rule.  A read of L bases in read orientation, as the stages in front left it.  For a letter X and n in M..L the suffix of n bases
+ *   QUALIFIES when its first (leftmost) base is X and the number mm of its bases that are not X is at most min(floor(n / 8), 5).  The read
+ *   loses its LONGEST qualifying suffix over all X in S; nothing when none qualifies.  "Longest" is a maximum over independent tests: the
+ *   result is bit-identical whatever the launch geometry, the thread count, the block boundaries and the input form.  mm only grows with n,
+ *   so a scan from the read's end may stop at the sixth base that is not X: the work per read is its tail's length plus a few bases.
+ *   Differences from fastp, on purpose: fastp stops at the first prefix-from-the-end that breaks its allowance; this rule has no running
+ *   condition.  And the rule can take along up to five bases that were not X (e.g. TTTT GACGT G x 40 under S = {G}, M = 10 loses 45 bases).
+ *   Order.  The cut runs in drprg_hip_map_fastx, per ingest block, inside the trim stage BEHIND the crops, the quality trim, the 3' and the
+ *   5' adapters, on what they left, and IN FRONT OF base masking, the decoy screen, the read filter and everything behind them: the run is
+ *   that of a file of the cut reads.  A reverse-strand BAM record is cut in read orientation.  It needs no quality byte and serves FASTA
+ *   and BAM without QUAL.  A read cut to nothing stays, as a read of no bases.  drprg_hip_map_host* and drprg_hip_map_device* return -EINVAL
+ *   while S is set.  Once a tail was cut off a read of a sample that is not resident, drprg_hip_discover_reads returns -ENODATA (-61).  With
+ *   no S nothing of this exists: no launch, no wait, no allocation, no copy.
+ *   drprg_hip_set_poly_trim: letters: a string of distinct letters of ACGTacgt; NULL or "" clears the setting.  Applies from the next
+ *     drprg_hip_map_fastx, on every device of the context; a reset keeps it.  -EINVAL for any other letter, a repeated letter, or min_len
+ *     outside 2..255.
+ *   drprg_hip_poly_trim_info: since the last reset, out[0..4] = reads seen and bases seen by the cut (behind both adapter sides), reads cut,
+ *     bases cut, reads emptied.
+ *   drprg_hip_poly_trim_device: the tail cut alone on caller-owned device buffers, under the context's settings (-EINVAL without): the
+ *     buffers, the two input forms and the stream, alignment and readable-64-bytes rules of drprg_hip_adapter_trim_device.  d_begin / d_end
+ *     hold every read's range; d_end receives the cut ranges' ends.  out[0..4]: this call's five counts.  Synchronises the stream. */
+int drprg_hip_set_poly_trim(drprg_hip_ctx* ctx, const char* letters, uint32_t min_len);
+int drprg_hip_poly_trim_info(drprg_hip_ctx* ctx, uint64_t out[5]);
+int drprg_hip_poly_trim_device(drprg_hip_ctx* ctx, const void* d_text, const void* d_words, const void* d_npos, uint64_t n_npos, const void* d_offsets,
+    uint64_t n_reads, uint64_t n_bases, const void* d_begin, void* d_end, uint64_t out[5], void* hip_stream);
+/* ---- Read complexity: low-complexity reads dropped on the device, as the reads arrive.  THIS BUILD'S OWN RULE, stated from memory of
+ * fastp's low-complexity filter (whose default threshold is 30 %; here the default is off).
+ *   Setting, per context: P, a whole number in 1..100 (0: off).
+ *   The rule, under the comparison of "poly tails".  For a read of L bases, D = the number of i in 0..L - 2 whose bases i and i + 1 differ.
+ *   The read is dropped as LOW COMPLEXITY iff L >= 2 and 100 * D < P * (L - 1), in 64-bit integers.  A read of 0 or 1 bases is kept by this
+ *   test (lengths are the read filter's business).  D is a sum over independent positions: the verdict depends on nothing but the read.
+ *   So a read that is dark from its first cycle (all G), homopolymer and dinucleotide-poor reads, and reads that base masking turned almost
+ *   wholly unknown are dropped.
+ *   Order.  The test runs in drprg_hip_map_fastx, per ingest block, on the read as the trim stage (both adapter sides and the tail cut
+ *   included) and base masking left it.  Only the reads the length and quality tests of the read filter kept are judged, and the decoy
+ *   screen's verdict then applies only to the reads this test kept as well.  Everything "read filter" lists as seeing the kept reads alone
+ *   sees one verdict.  It needs no quality byte.  A read is shorter than 2^32 bases (a block that is not is refused, -EOVERFLOW).
+ *   drprg_hip_map_host* and drprg_hip_map_device* return -EINVAL while P != 0.  Once the test dropped a read of a sample that is not
+ *   resident, drprg_hip_discover_reads returns -ENODATA (-61).  With P == 0 nothing of this exists: no launch, no wait, no allocation.
+ *   drprg_hip_read_filter_info's reads kept and bases kept (out[5], out[6]) count what passed every test: seen = short + long + low quality
+ *   + low complexity + decoy + kept, low complexity being drprg_hip_complexity_info's out[2] and decoy drprg_hip_decoy_info's out[4].
+ *   drprg_hip_set_min_complexity: applies from the next drprg_hip_map_fastx, on every device of the context; a reset keeps it; 0 clears it.
+ *     -EINVAL above 100.
+ *   drprg_hip_complexity_info: since the last reset, out[0..3] = reads judged, their bases, reads dropped, bases dropped.
+ *   drprg_hip_complexity_device: the kernels alone on caller-owned device buffers, under the context's P (-EINVAL when it is 0); the two
+ *     input forms and the address, padding and stream rules of drprg_hip_adapter_trim_device.  d_diff: u32[n_reads], receives D (may be
+ *     NULL); d_flags: u8[n_reads], 1 for a kept read.  out[0..1] = reads dropped, bases dropped.  -EINVAL when the offsets do not ascend
+ *     from 0 to n_bases.  Synchronises the stream. */
+int drprg_hip_set_min_complexity(drprg_hip_ctx* ctx, uint32_t percent);
+int drprg_hip_complexity_info(drprg_hip_ctx* ctx, uint64_t out[4]);
+int drprg_hip_complexity_device(drprg_hip_ctx* ctx, const void* d_text, const void* d_words, const void* d_npos, uint64_t n_npos, const void* d_offsets,
+    uint64_t n_reads, uint64_t n_bases, void* d_diff, void* d_flags, uint64_t out[2], void* hip_stream);
 /* The read selection drprg_hip_discover_reads uses when the reads are resident, on its own: for every device of the context, in order,
  * every kept read in which a k-mer of `anchors` STARTS (anchors: n_anchors k-mers of A bases, 2 bits per base, A 0 C 1 G 2 T 3, first base
  * in the high bits; any order, duplicates allowed).  A block's reads are one base stream: read r of a block is returned iff for some p with
