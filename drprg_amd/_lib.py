@@ -127,6 +127,14 @@ SIGNATURES = {
     "drprg_hip_complexity_info": (C.c_int, [C.c_void_p, C.c_void_p]),
     "drprg_hip_complexity_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p]),
+    "drprg_hip_read_stats_words": (C.c_uint64, []),
+    "drprg_hip_read_stats_layout": (C.c_int, [C.c_void_p]),
+    "drprg_hip_set_read_stats": (C.c_int, [C.c_void_p, C.c_int]),
+    "drprg_hip_read_stats_info": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64]),
+    "drprg_hip_read_stats_prepared_is_raw": (C.c_int, [C.c_void_p]),
+    "drprg_hip_read_stats_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                              C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "drprg_hip_write_qc_json": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p]),
     "drprg_hip_set_decoy":(C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     "drprg_hip_decoy_info": (C.c_int, [C.c_void_p, C.c_void_p]),
     "drprg_hip_decoy_lookup": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),

@@ -24,6 +24,7 @@ struct Selection {
     bool done = false;
     uint64_t reads_before = 0;
     std::vector<uint8_t> flags;
+    uint64_t counts[4] = { 0, 0, 0, 0 }; // the call's four outputs: reads and bases before, reads and bases kept
 };
 
 // What the context knows of the sample it is mapping: all of it, and nothing else, goes back to this with drprg_hip_reset.
@@ -50,6 +51,9 @@ struct SampleState {
     // drprg_hip_adapter_trim_info and drprg_hip_front_adapter_info, in .mask drprg_hip_base_mask_info, in .decoy drprg_hip_decoy_info, in
     // .poly drprg_hip_poly_trim_info, in .cplx drprg_hip_complexity_info.
     Mapper::FilterOutcome filter_counts;
+    // read statistics (drprg_hip_set_read_stats): a pass of drprg_hip_map_fastx ran under a prep setting or a depth cap, so the prepared
+    // snapshot was counted on its own; false: it is the raw snapshot by definition (drprg_hip_read_stats_info says which)
+    bool stats_prepared = false;
     MapCounters extra_counts; // what devices 1 .. ndev-1 counted (reduce_devices folds them in when it folds their coverage)
 };
 } // namespace drprg

@@ -180,7 +180,8 @@ static Mapper::FilterOutcome map_filtered(drprg_hip_ctx* ctx, const Mapper::Read
 // device that keeps its blocks resident keeps exactly those): filtered, the cap cuts on the kept reads' running total and the device finds the
 // read (Mapper::map_host_filtered); unfiltered, the cut is made here.  The cap's state is committed once the map call has succeeded.
 // wait: the caller reuses the block's buffers at once, so the mapper is done with them on return.  Returns whether the ingest goes on.
-static bool map_block_capped(drprg_hip_ctx* ctx, const Mapper::ReadFilter& filter, Mapper& dev, Mapper::HostBatch hb, bool wait)
+// count: read statistics, when they are set (the blocks of drprg_hip_map_fastx: the host entries carry no qualities and are not counted).
+static bool map_block_capped(drprg_hip_ctx* ctx, const Mapper::ReadFilter& filter, Mapper& dev, Mapper::HostBatch hb, bool wait, bool count = false)
 {
     if (filter.any()) {
         uint64_t T = 0;
@@ -189,7 +190,18 @@ static bool map_block_capped(drprg_hip_ctx* ctx, const Mapper::ReadFilter& filte
         cap_commit(ctx, CapCut { o.cut, o.cut_dropped }, o.mapped_reads, o.mapped_bases);
     } else {
         CapCut c;
+        Mapper::HostBatch whole = hb;
         cap_host_cut(ctx, hb, c);
+        if (count && filter.read_stats) { // under a cap the two snapshots differ: raw takes the block as the file held it, prepared what the cap accepts
+            uint64_t T = 0;
+            hb.stats_mode = whole.stats_mode = (uint8_t)filter.read_stats;
+            hb.stats_which = cap_target(ctx, T) ? 3 : 1;
+            if (c.dropped) {
+                whole.stats_which = 1;
+                dev.count_host_block(whole);
+                hb.stats_which = 2;
+            }
+        }
         if (wait) dev.map_host(hb);
         else dev.map_host_async(hb); // (the copy of a block overlaps the kernels of the block before it)
         cap_commit(ctx, c, hb.n_reads, hb.n_bases());
@@ -200,7 +212,12 @@ static bool map_block_capped(drprg_hip_ctx* ctx, const Mapper::ReadFilter& filte
 // A block handed over in no particular order: nothing is cut, and the cap's totals are counted once, after the ingest (count_ingest).
 static void map_block_unordered(FastxPass& p, Mapper& dev, const Mapper::HostBatch& hb)
 {
-    if (!p.filter.any()) return dev.map_host_async(hb);
+    if (!p.filter.any()) {
+        Mapper::HostBatch counted = hb;
+        counted.stats_mode = (uint8_t)p.filter.read_stats; // (nothing is prepared and nothing is cut: the raw snapshot stands for both)
+        counted.stats_which = p.filter.read_stats ? 1 : 0;
+        return dev.map_host_async(counted);
+    }
     const Mapper::FilterOutcome o = map_filtered(p.ctx, p.filter, dev, hb, 0);
     p.kept_reads += o.mapped_reads;
     p.kept_bases += o.mapped_bases;
@@ -226,7 +243,9 @@ static IngestHooks fastx_hooks(FastxPass& p)
     IngestHooks hooks;
     hooks.packed = p.ctx->packed_input;
     hooks.bam_native = true; // a BAM file's reads travel in their 4-bit form and are converted on the device (bam_pack.hip), whatever `packed` says
-    hooks.want_qual = p.filter.wants_qual(); // (for the filter's threshold, --trim-qual or --mask-qual; fixed crops alone carry none)
+    hooks.want_qual = p.filter.wants_qual(); // (for the filter's threshold, --trim-qual, --mask-qual or --qc-json; fixed crops alone carry none)
+    if (p.filter.read_stats == 1) hooks.qual_flag = "--qc-json"; // (any other quality setting is named first)
+    if (p.filter.use_qual()) hooks.qual_flag = "--min-read-qual";
     if (p.filter.mask_qual) hooks.qual_flag = "--mask-qual";
     if (p.filter.trim_qual_milli) hooks.qual_flag = "--trim-qual"; // (trimming comes first, then the mask: the first to miss them is named)
     // page-locked ingest blocks are kept by the process between calls and contexts (PinPool)
@@ -241,7 +260,7 @@ static IngestHooks fastx_hooks(FastxPass& p)
     if (p.ordered)
         hooks.submit_in_order = [&p](const PinnedBatch& b) -> bool {
             if (b.offsets[0] != 0) throw Error(DRPRG_EINVAL, "offsets[0] must be 0");
-            return map_block_capped(p.ctx, p.filter, *p.devs[p.rr++ % p.devs.size()], host_batch(b), false);
+            return map_block_capped(p.ctx, p.filter, *p.devs[p.rr++ % p.devs.size()], host_batch(b), false, true);
         };
     return hooks;
 }
@@ -276,10 +295,12 @@ static void map_fastx_serial(FastxPass& p, const char* reads_path)
                 throw Error(DRPRG_EINVAL, "--mask-qual: a FASTA record has no base qualities; a base is never masked by a quality it does not have");
             if (filter.use_qual() && batch.qual.size() != batch.bases.size())
                 throw Error(DRPRG_EINVAL, "--min-read-qual: a FASTA record has no base qualities; a read is never kept or dropped by a quality threshold it cannot be held against");
-            if (filter.wants_qual()) hb.qual = batch.qual.data();
-            hb.qual_bias = 33;
         }
-        if (!map_block_capped(p.ctx, filter, *p.devs[0], hb, true)) break;
+        if (filter.read_stats == 1 && batch.qual.size() != batch.bases.size())
+            throw Error(DRPRG_EINVAL, "--qc-json: a FASTA record has no base qualities; the read statistics report them (--qc-no-qual reports without them)");
+        if (filter.wants_qual()) hb.qual = batch.qual.data();
+        if (filter.any() || filter.read_stats) hb.qual_bias = 33;
+        if (!map_block_capped(p.ctx, filter, *p.devs[0], hb, true, true)) break;
     }
 }
 
@@ -295,6 +316,7 @@ int drprg_hip_map_fastx(drprg_hip_ctx* ctx, const char* reads_path)
     ctx->sample.mapped_paths.push_back(reads_path);
     uint64_t T = 0;
     FastxPass pass(ctx, cap_target(ctx, T) || ctx->ordered_ingest);
+    if (pass.filter.read_stats && (pass.filter.any() || cap_target(ctx, T))) ctx->sample.stats_prepared = true; // (else the raw snapshot stands for both)
     const IngestHooks hooks = fastx_hooks(pass);
     try {
         count_ingest(pass, ingest_fastx(reads_path, ctx->threads, hooks));
@@ -306,6 +328,8 @@ int drprg_hip_map_fastx(drprg_hip_ctx* ctx, const char* reads_path)
         if (e.code != DRPRG_EAGAIN_SERIAL) throw; // (a failed multi-device pass leaves partial vectors on the devices: reset before reuse)
         map_fastx_serial(pass, reads_path);
     }
+    if (pass.filter.read_stats) // what the statistics kernels refused, once per pass (a block behind a prep stage has said so itself)
+        for (Mapper* m : mappers_of(ctx)) m->check_read_stats();
     API_END(ctx)
 }
 
@@ -356,6 +380,9 @@ static void refuse_unfiltered(const drprg_hip_ctx* ctx, const char* entry)
     if (ctx->read_filter.mask_qual)
         throw Error(DRPRG_EINVAL, std::string(entry) + ": a base mask is set (drprg_hip_set_base_mask) and this entry carries no qualities; masking runs in "
                                                       "drprg_hip_map_fastx (clear it with drprg_hip_set_base_mask(ctx, 0))");
+    if (ctx->read_filter.read_stats == 1)
+        throw Error(DRPRG_EINVAL, std::string(entry) + ": read statistics with qualities are set (drprg_hip_set_read_stats) and this entry carries no qualities; "
+                                                      "the statistics are taken in drprg_hip_map_fastx (clear them with drprg_hip_set_read_stats(ctx, 0))");
     if (ctx->read_filter.any())
         throw Error(DRPRG_EINVAL, std::string(entry) + ": a read filter is set (drprg_hip_set_read_filter) and this entry carries no qualities; the filter "
                                                       "runs in drprg_hip_map_fastx (clear it with drprg_hip_set_read_filter(ctx, 0, 0, 0))");

@@ -3,6 +3,8 @@
 // (keep, map from another context, select, subsample, dedup).
 #include "capi_ctx.h"
 #include "fastx.h"
+#include "read_stats_host.h"
+#include <cstdio>
 #include "read_qual_piece.h"
 #include "read_trim_piece.h"
 #include <algorithm>
@@ -336,6 +338,125 @@ int drprg_hip_base_mask_device(drprg_hip_ctx* ctx, const void* d_qual, uint32_t 
     API_END(ctx)
 }
 
+// ---- read statistics (the rule: include/drprg_hip.h "read statistics"; the layout: read_stats_words.h) ------------------------------------
+uint64_t drprg_hip_read_stats_words(void) { return dev::RS_WORDS; }
+
+int drprg_hip_read_stats_layout(uint64_t out[13])
+{
+    if (!out) return DRPRG_EINVAL;
+    const uint64_t v[13] = { dev::RS_WORDS, dev::RS_LEN_READS, dev::RS_LEN_BASES, dev::RS_CYC_BASE, dev::RS_CYC_QSUM, dev::RS_QUAL_HIST, dev::RS_READQ_HIST,
+        dev::RS_GC_HIST, dev::RS_LEN_BINS, dev::RS_CYCLES, dev::RS_COLS, dev::RS_QUALS, dev::RS_GC_BINS };
+    for (int i = 0; i < 13; ++i) out[i] = v[i];
+    return DRPRG_OK;
+}
+
+int drprg_hip_set_read_stats(drprg_hip_ctx* ctx, int mode)
+{
+    API_BEGIN(ctx)
+    if (mode < 0 || mode > 2) throw Error(DRPRG_EINVAL, "read statistics: the mode is 0 (off), 1 (with qualities) or 2 (without)");
+    ctx->read_filter.read_stats = (uint32_t)mode; // (it rides in the settings every device's blocks are prepared under, like the trim settings)
+    API_END(ctx)
+}
+
+// one snapshot of the context: its devices' folded (which 1 on a sample no prep setting or cap touched: the raw one)
+static void read_stats_snapshot(drprg_hip_ctx* ctx, int which, std::vector<uint64_t>& w)
+{
+    if (which == 1 && !ctx->sample.stats_prepared) which = 0;
+    w.assign(dev::RS_WORDS, 0);
+    w[dev::RS_MIN_LEN] = ~0ull;
+    std::vector<uint64_t> one(dev::RS_WORDS);
+    for (Mapper* m : mappers_of(ctx)) {
+        m->read_stats(which, one.data());
+        rs_fold(w.data(), one.data());
+    }
+    rs_finish(w.data());
+}
+
+int drprg_hip_read_stats_info(drprg_hip_ctx* ctx, int which, uint64_t* out, uint64_t n_words)
+{
+    API_BEGIN(ctx)
+    need_mapper(ctx);
+    if (!out) throw Error(DRPRG_EINVAL, "null output");
+    if (which != 0 && which != 1) throw Error(DRPRG_EINVAL, "read statistics: the snapshot is 0 (raw) or 1 (prepared)");
+    if (n_words < dev::RS_WORDS) throw Error(DRPRG_EINVAL, "read statistics: a snapshot holds " + std::to_string(dev::RS_WORDS) + " words (drprg_hip_read_stats_words), the buffer " + std::to_string(n_words));
+    std::vector<uint64_t> w;
+    read_stats_snapshot(ctx, which, w);
+    std::memcpy(out, w.data(), dev::RS_WORDS * sizeof(uint64_t));
+    API_END(ctx)
+}
+
+int drprg_hip_read_stats_prepared_is_raw(drprg_hip_ctx* ctx)
+{
+    if (!ctx) return DRPRG_EINVAL;
+    return ctx->sample.stats_prepared ? 0 : 1;
+}
+
+int drprg_hip_read_stats_device(drprg_hip_ctx* ctx, const void* d_text, const void* d_words, const void* d_npos, uint64_t n_npos, const void* d_qual, uint32_t qual_bias,
+    const void* d_offsets, const void* d_rev, uint64_t n_reads, uint64_t n_bases, const void* d_flags, uint64_t take, uint64_t* out, uint64_t n_words, void* hip_stream)
+{
+    API_BEGIN(ctx)
+    Mapper& m = need_mapper(ctx);
+    if (!out) throw Error(DRPRG_EINVAL, "null output");
+    if (n_words < dev::RS_WORDS) throw Error(DRPRG_EINVAL, "read statistics: a snapshot holds " + std::to_string(dev::RS_WORDS) + " words (drprg_hip_read_stats_words), the buffer " + std::to_string(n_words));
+    if (qual_bias != 0 && qual_bias != 33) throw Error(DRPRG_EINVAL, "read statistics: the quality bias is 33 (FASTQ) or 0 (BAM)");
+    if (d_text && d_words) throw Error(DRPRG_EINVAL, "read statistics: the bases come as text or as packed words, not both");
+    uint64_t res[2];
+    m.read_stats_device((const uint8_t*)d_text, (const uint32_t*)d_words, (const uint64_t*)d_npos, n_npos, (const uint8_t*)d_qual, qual_bias, (const uint64_t*)d_offsets,
+        (const uint8_t*)d_rev, n_reads, n_bases, (const uint8_t*)d_flags, take, out, res, (hipStream_t)hip_stream);
+    if (res[1]) throw Error(DRPRG_EINVAL, "read statistics: the offsets do not ascend from 0 to n_bases");
+    if (res[0]) throw Error(DRPRG_EFORMAT, "a base quality outside 0..93 at quality byte " + std::to_string(res[0] - 1));
+    API_END(ctx)
+}
+
+int drprg_hip_write_qc_json(drprg_hip_ctx* ctx, const char* path, const char* sample)
+{
+    API_BEGIN(ctx)
+    need_mapper(ctx);
+    if (!path) throw Error(DRPRG_EINVAL, "null path");
+    const Mapper::ReadFilter& f = ctx->read_filter;
+    if (!f.read_stats) throw Error(DRPRG_EINVAL, "read statistics are not set (drprg_hip_set_read_stats)");
+    std::vector<uint64_t> raw, prepared;
+    read_stats_snapshot(ctx, 0, raw);
+    read_stats_snapshot(ctx, 1, prepared);
+    QcReport r;
+    r.sample = sample ? sample : "";
+    r.with_qual = f.read_stats == 1;
+    r.prepared_is_raw = !ctx->sample.stats_prepared;
+    r.raw = raw.data();
+    r.prepared = prepared.data();
+    r.settings = { { "max_covg", ctx->max_covg >= 0xFFFFFFFFull ? 0xFFFFFFFFull : ctx->max_covg } /* 4294967295: off */, { "min_read_len", f.min_len },
+        { "max_read_len", f.max_len }, { "min_read_qual_milli", f.min_qual_milli }, { "trim_front", f.trim_front }, { "trim_tail", f.trim_tail },
+        { "trim_qual_milli", f.trim_qual_milli }, { "trim_window", f.trim_window }, { "adapters", f.adapters.n }, { "front_adapters", f.front_adapters.n },
+        { "adapter_indels", f.adapter_indels ? 1u : 0u }, { "poly_letters", f.poly_letters }, { "poly_min_len", f.poly_min_len }, { "mask_qual", f.mask_qual },
+        { "min_complexity", f.min_complexity }, { "decoy_k", f.decoy_k }, { "decoy_frac_milli", f.decoy_frac_milli }, { "decoy_min_kmers", f.decoy_min_kmers },
+        { "packed_input", ctx->packed_input ? 1u : 0u } };
+    // the counters every stage keeps, as its *_info entry returns them
+    const auto stage = [&](const char* name, int (*info)(drprg_hip_ctx*, uint64_t*), size_t n) {
+        std::vector<uint64_t> v(n, 0);
+        if (int rc = info(ctx, v.data())) throw Error(rc, ctx->last_error);
+        r.stages.emplace_back(name, std::move(v));
+    };
+    stage("read_trim", drprg_hip_read_trim_info, 8);
+    stage("adapter_trim", drprg_hip_adapter_trim_info, 5);
+    stage("front_adapter", drprg_hip_front_adapter_info, 5);
+    stage("poly_trim", drprg_hip_poly_trim_info, 5);
+    stage("base_mask", drprg_hip_base_mask_info, 5);
+    stage("read_filter", drprg_hip_read_filter_info, 8);
+    stage("complexity", drprg_hip_complexity_info, 4);
+    stage("decoy", drprg_hip_decoy_info, 8);
+    stage("max_covg", drprg_hip_max_covg_info, 4);
+    const Selection& dd = ctx->sample.dedup;
+    const Selection& ss = ctx->sample.subsample;
+    r.stages.emplace_back("dedup", dd.done ? std::vector<uint64_t>(dd.counts, dd.counts + 4) : std::vector<uint64_t>());
+    r.stages.emplace_back("subsample", ss.done ? std::vector<uint64_t>(ss.counts, ss.counts + 4) : std::vector<uint64_t>());
+    const std::string text = qc_json(r);
+    FILE* fp = std::fopen(path, "wb");
+    if (!fp) throw Error(DRPRG_EIO, std::string("cannot write ") + path);
+    const bool ok = std::fwrite(text.data(), 1, text.size(), fp) == text.size();
+    if (std::fclose(fp) != 0 || !ok) throw Error(DRPRG_EIO, std::string("cannot write ") + path);
+    API_END(ctx)
+}
+
 // ---- the decoy screen (the rule: include/drprg_hip.h "decoy screen") ----------------------------------------------------------------
 static void clear_decoy(drprg_hip_ctx* ctx)
 {
@@ -514,6 +635,7 @@ static void record_selection(drprg_hip_ctx* ctx, Selection& sel, const Mapper::S
     out[0] = r.reads_before; out[1] = r.bases_before; out[2] = r.reads_kept; out[3] = r.bases_kept;
     sel.done = true;
     sel.reads_before = r.reads_before;
+    for (int i = 0; i < 4; ++i) sel.counts[i] = out[i];
     sel.flags = std::move(flags);
     if (r.reads_kept != r.reads_before) { // the context now stands for the kept reads alone
         ctx->sample.host_coverage_valid = false;

@@ -23,6 +23,7 @@
 #include "decoy_args.h"
 #include "mask_args.h"
 #include "poly_args.h"
+#include "qc_args.h"
 
 namespace {
 
@@ -115,7 +116,7 @@ void usage()
         "              [--dedup] [--min-read-len L] [--max-read-len L] [--min-read-qual Q]\n"
         "              [--trim-front N] [--trim-tail N] [--trim-qual Q [--trim-window W]]\n"
         "              [--adapter SEQ]... [--adapter-error E] [--adapter-min-overlap O] [--adapter-indels] [--front-adapter SEQ]...\n"
-        "              [--poly-tail LETTERS [--poly-min-len M]] [--min-complexity P]\n"
+        "              [--poly-tail LETTERS [--poly-min-len M]] [--min-complexity P] [--qc-json FILE [--qc-no-qual]]\n"
         "              [--mask-qual Q] [--decoy FASTA]... [--decoy-k K] [--decoy-min-frac F] [--decoy-min-kmers M]\n"
         "--poly-tail LETTERS (letters of ACGT, e.g. G or ACGT), --poly-min-len M (2 to 255, default 10): every read loses its longest suffix of\n"
         "              at least M bases that begins with one of the letters and holds at most min(n / 8, 5) other bases -- the tails two-colour\n"
@@ -154,7 +155,9 @@ void usage()
         "--dedup: every read that is identical to a read before it in the file (same length, same bases case-insensitively, non-ACGT bases\n"
         "              at the same places; forward strand only) is dropped on the device, in front of --subsample-covg, discover and\n"
         "              genotyping; needs the sample resident in device memory (DRPRG_HIP_KEEP_READS_GB, default 32), fails if it is not.\n"
-        "MI355X-native hot path; -p/-m/-M (external tools) are accepted and not needed: novel variants update the PRG in process.\n");
+        "%s"
+        "MI355X-native hot path; -p/-m/-M (external tools) are accepted and not needed: novel variants update the PRG in process.\n",
+        drprg::QcArgs::usage());
 }
 
 } // namespace
@@ -199,6 +202,7 @@ int main(int argc, char** argv)
     uint32_t trim_qual_milli = 0, trim_window = 0;
     uint32_t mask_qual = 0; // --mask-qual Q: base masking (include/drprg_hip.h "base masking"); 0 = not set
     drprg::AdapterArgs adapters; // --adapter SEQ, --adapter-error E, --adapter-min-overlap O (include/drprg_hip.h "adapter trimming")
+    drprg::QcArgs qc; // --qc-json FILE, --qc-no-qual (include/drprg_hip.h "read statistics")
     drprg::PolyArgs poly; // --poly-tail LETTERS, --poly-min-len M, --min-complexity P (include/drprg_hip.h "poly tails", "read complexity")
     drprg::DecoyArgs decoy; // --decoy FASTA, --decoy-k K, --decoy-min-frac F, --decoy-min-kmers M (include/drprg_hip.h "decoy screen")
     uint32_t min_cluster = 10;
@@ -245,6 +249,8 @@ int main(int argc, char** argv)
         else if (a == "-v" || a == "--verbose") verbose = true;
         else if (a == "--debug") verbose = true;
         else if (a == "--rebuild-index") rebuild_index = true;
+        else if (a == "--qc-json") qc.json = need(i);
+        else if (a == "--qc-no-qual") qc.no_qual = true;
         else if (a == "--dedup") dedup = true;
         else if (a == "--subsample-covg") {
             char* end = nullptr;
@@ -336,6 +342,7 @@ int main(int argc, char** argv)
     if (const std::string e = adapters.check(); !e.empty()) die(e, 2);
     if (const std::string e = decoy.check(); !e.empty()) die(e, 2);
     if (const std::string e = poly.check(); !e.empty()) die(e, 2);
+    if (const std::string e = qc.check(); !e.empty()) die(e, 2);
     if (index.empty() || input.empty()) {
         usage();
         return 2;
@@ -391,6 +398,7 @@ int main(int argc, char** argv)
     if (int rc = drprg_hip_set_read_trim(ctx, trim_front, trim_tail, trim_qual_milli, trim_window)) die(drprg_hip_last_error(ctx), -rc);
     if (int rc = drprg_hip_set_base_mask(ctx, mask_qual)) die(drprg_hip_last_error(ctx), -rc);
     if (int rc = poly.set_on(ctx, drprg_hip_set_poly_trim, drprg_hip_set_min_complexity)) die(drprg_hip_last_error(ctx), -rc);
+    if (int rc = drprg_hip_set_read_stats(ctx, qc.mode())) die(drprg_hip_last_error(ctx), -rc); // (this context alone: the report is the first mapping pass's)
     if (adapters.any())
         if (int rc = adapters.set_on(ctx, drprg_hip_set_adapters, drprg_hip_set_adapters2)) die(drprg_hip_last_error(ctx), -rc);
     if (decoy.any()) // (once per run: the second pass after a PRG update maps the resident reads, which are screened already)
@@ -473,6 +481,10 @@ int main(int argc, char** argv)
             std::fprintf(stderr, "[drprg-hip +%.3fs] subsample: reads_before=%llu bases_before=%llu reads_kept=%llu bases_kept=%llu (target %llu bases, seed %llu)\n",
                 since_start(), (unsigned long long)out[0], (unsigned long long)out[1], (unsigned long long)out[2], (unsigned long long)out[3],
                 (unsigned long long)target, (unsigned long long)seed);
+    }
+    if (qc.any()) { // the report of the one pass over the file, with the counts of --dedup and --subsample-covg: a second pass maps resident reads
+        if (int rc = drprg_hip_write_qc_json(ctx, qc.json.c_str(), sample.c_str())) die(std::string("--qc-json: ") + drprg_hip_last_error(ctx), -rc);
+        if (verbose) qc.report(ctx, [](const char* line) { std::fprintf(stderr, "[drprg-hip +%.3fs] %s\n", since_start(), line); });
     }
     {
         // discover (/root/reference/src/predict.rs:247-256): candidate regions of every locus' called consensus, then a host-side

@@ -15,6 +15,7 @@
 #include "adapter_edit.h"
 #include "decoy_piece.h"
 #include "poly_piece.h"
+#include "read_stats_words.h"
 
 namespace drprg {
 namespace dev {
@@ -649,6 +650,30 @@ hipError_t launch_base_mask(const BaseMaskArgs& a, hipStream_t stream, KernelTim
 // left, then the emit.  chunk_count / chunk_prefix: base_mask_tiles(n_bases) + 1 words each; temp: scan_temp_bytes of as many.
 hipError_t launch_base_mask_emit(const uint16_t* nbits, uint64_t n_bases, uint32_t* chunk_count, uint32_t* chunk_prefix, void* temp, size_t temp_bytes, uint64_t* out,
     uint64_t out_cap, hipStream_t stream);
+
+// read_stats.hip: read statistics (the rule: include/drprg_hip.h "read statistics"; the layout: read_stats_words.h).  The reads of a batch
+// counted into acc, a snapshot's RS_DEV_WORDS device accumulators (launch_read_stats_clear puts them to their start; every launch adds).
+// The bases in either of adapter_points_kernel's two forms, as the decoy screen takes them (text 16-byte aligned has 64 readable bytes
+// behind n_bases; any other address is read byte by byte).  qual: as base_mask.hip takes it, with rev, or null: the three quality
+// sections are left alone.  flags: u8[n_reads], 0 for a read that does not count, or null; take: only reads below it count.  gcv, esum:
+// u64[n_reads] scratch (esum only with qual), zeroed here.  n_reads <= MAX_BATCH_READS, n_bases < RS_MAX_BASES; nothing is indexed out of
+// bounds whatever `offsets` holds: offsets that do not ascend from 0 to n_bases set acc[RS_DEV_OFFSETS].
+constexpr uint64_t RS_MAX_BASES = 1ull << 32;
+struct ReadStatsArgs {
+    const uint8_t* text;
+    const uint32_t* words;
+    const uint16_t* nbits;
+    const uint8_t* qual;
+    uint32_t bias;
+    const uint64_t* offsets;
+    const uint8_t *rev, *flags;
+    uint64_t n_reads, n_bases, take;
+    unsigned long long *gcv, *esum, *acc;
+};
+uint32_t read_stats_tiles(uint64_t n_bases);
+hipError_t launch_read_stats_clear(unsigned long long* acc, hipStream_t stream);
+// timer: around read_stats_pos_kernel
+hipError_t launch_read_stats(const ReadStatsArgs& a, hipStream_t stream, KernelTimer timer = {});
 
 // anchor_scan.hip: reads of a resident batch that hold one of the (sorted) anchor k-mers of length A -- every such read once,
 // in any order, appended to `list` (count keeps counting past list_cap).  prefilter: 2^16 bits, bit (kmer & 0xFFFF) set for every

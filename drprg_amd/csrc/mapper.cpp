@@ -246,7 +246,14 @@ void Mapper::reset_coverage(bool new_sample)
     for (auto& sh : ft_share_) // (a reset context starts from the launcher's built-in tile shares again: ADVICE r05)
         for (uint32_t& v : sh) v = 0;
     sw_ = read_switches(); // (those that only shape construction keep their effect from the open)
-    if (new_sample) drop_kept();
+    if (new_sample) {
+        drop_kept();
+        for (int w = 0; w < 2; ++w) { // the read statistics are the sample's
+            if (stats_.acc[w]) HIPCHK(dev::launch_read_stats_clear(stats_.acc[w].data(), stream_));
+            stats_.empty_reads[w] = 0;
+        }
+        HIPCHK(hipStreamSynchronize(stream_));
+    }
 }
 
 void Mapper::ensure_workspace(uint64_t cap)

@@ -109,6 +109,10 @@ public:
         // byte to get the Phred quality; looked at by map_host_filtered only, and only under a quality threshold
         const uint8_t* qual = nullptr;
         uint32_t qual_bias = 0;
+        // Read statistics on a block that goes through map_host / map_host_async (no prep setting: capi_map.cpp sets these on the blocks of
+        // drprg_hip_map_fastx; map_host_filtered reads ReadFilter::read_stats instead).  stats_mode: 0 off, 1 with qualities (qual is set
+        // then), 2 without; stats_which: bit STATS_RAW / STATS_PREPARED set for the snapshots the block is counted into.
+        uint8_t stats_mode = 0, stats_which = 0;
         uint64_t n_bases() const { return offsets[n_reads]; }
         // what the batch takes on the device once it is there (a BAM batch: converted to the packed form)
         uint64_t payload_bytes() const { return packed || bam ? ((n_bases() + 15) / 16) * 4 : n_bases(); }
@@ -150,6 +154,9 @@ public:
         // The low-complexity filter (the rule: include/drprg_hip.h "read complexity"; read_complexity.hip): P, 1..100 (0: off).  Behind
         // the mask, on the reads the length and quality tests kept, in front of the decoy screen's verdict.
         uint32_t min_complexity = 0;
+        // Read statistics (the rule: include/drprg_hip.h "read statistics"; read_stats.hip): 0 off, 1 with qualities, 2 without.  No prep
+        // setting -- any() does not see it: a block of a context without one goes through map_host_async and is counted there.
+        uint32_t read_stats = 0;
         bool decoy() const { return decoy_k != 0; }
         bool poly() const { return poly_letters != 0; }
         bool any_adapters() const { return adapters.n != 0 || front_adapters.n != 0; }
@@ -159,8 +166,8 @@ public:
         bool trim_points() const { return any_adapters() || poly(); } // the trim stage looks at the bases (a packed block's bitmap first)
         bool any() const { return filters() || trims() || decoy() || mask_qual || min_complexity; }
         bool use_qual() const { return min_qual_milli != 0; }
-        bool wants_qual() const { return min_qual_milli != 0 || trim_qual_milli != 0 || mask_qual != 0; } // the ingest carries quality bytes
-        bool qual_behind_trim() const { return use_qual() || mask_qual != 0; } // the trim stage gathers the trimmed reads' quality bytes
+        bool wants_qual() const { return min_qual_milli != 0 || trim_qual_milli != 0 || mask_qual != 0 || read_stats == 1; } // the ingest carries quality bytes
+        bool qual_behind_trim() const { return use_qual() || mask_qual != 0 || read_stats == 1; } // the trim stage gathers the trimmed reads' quality bytes
     };
     // (operator+=: a block's outcome added to a running total, count by count)
     struct TrimOutcome { // drprg_hip_read_trim_info
@@ -257,6 +264,23 @@ public:
     void base_mask_device(const ReadFilter& f, const uint8_t* d_qual, uint32_t bias, const uint64_t* d_offsets, const uint8_t* d_rev, uint64_t n_reads,
         uint64_t n_bases, uint8_t* d_text, uint32_t* d_words, const uint64_t* d_npos, uint64_t n_npos, uint64_t* d_npos_out, uint64_t npos_cap, uint64_t res[8],
         hipStream_t stream);
+    // Read statistics (drprg_hip_set_read_stats): two snapshots of dev::RS_WORDS words, kept in device memory per Mapper, zeroed by
+    // reset_coverage(true), added to by every block that is counted: STATS_RAW the block as it arrived, STATS_PREPARED what it hands on to
+    // mapping.  read_stats: the snapshot, read back (synchronises; RS_MIN_LEN is ~0 without a read: the caller folds the devices first).
+    // check_read_stats: what the kernels refused since the reset, thrown (synchronises; map_host_filtered looks per block, the other
+    // paths leave it to the end of the pass).  count_host_block: a host block copied in and counted into the snapshots of hb.stats_which,
+    // nothing else (the block the depth cap cuts, as the file held it); waits.
+    enum { STATS_RAW = 0, STATS_PREPARED = 1 };
+    void read_stats(int which, uint64_t out[dev::RS_WORDS]);
+    void check_read_stats();
+    void count_host_block(const HostBatch& hb);
+    // The kernels alone on the caller's device buffers (drprg_hip_read_stats_device): the bases as for adapter_trim_device, the quality
+    // bytes as for base_mask_device or null (no quality section is filled), d_flags one byte per read (0: not counted) or null, take: only
+    // reads below it count.  out: one snapshot; res[0]: first bad quality byte + 1, or 0; res[1]: the offsets do not ascend from 0 to
+    // n_bases.  Synchronises `stream`.
+    void read_stats_device(const uint8_t* d_text, const uint32_t* d_words, const uint64_t* d_npos, uint64_t n_npos, const uint8_t* d_qual, uint32_t bias,
+        const uint64_t* d_offsets, const uint8_t* d_rev, uint64_t n_reads, uint64_t n_bases, const uint8_t* d_flags, uint64_t take, uint64_t out[dev::RS_WORDS],
+        uint64_t res[2], hipStream_t stream);
     // Reads that stay in HBM (off by default).  keep_reads(max_bytes > 0): from now on map_host_async copies every block into
     // device memory of its own instead of a staging set and leaves it there -- at most max_bytes of it; one byte more and
     // everything kept is dropped and the staging sets are back.  kept_complete(): every read mapped since keep_reads() /
@@ -613,6 +637,27 @@ private:
         uint64_t n_reads, uint64_t n_bases, uint8_t* d_bases, bool packed, const uint64_t* d_npos, uint64_t n_npos, hipStream_t stream);
     // the list of a packed batch behind the mask, n_list positions, into fs.m_npos from the bitmap (queued on `stream`)
     void emit_mask_list(FilterScratch& fs, uint64_t n_bases, uint64_t n_list, hipStream_t stream);
+    // read statistics: the two snapshots' accumulators (allocated with the first block that is counted), the per-read words of
+    // read_stats.hip, a packed block's bitmap, the quality bytes of a block that goes through map_host_async (two buffers in turn, as the
+    // staging sets), the reads of blocks without a base (counted here: such a block is never copied) and the error words' pinned mirror
+    struct StatsState {
+        DeviceBuffer<unsigned long long> acc[2], gcv, esum;
+        DeviceBuffer<uint16_t> nbits;
+        DeviceBuffer<uint8_t> qual[2];
+        int qual_next = 0;
+        uint64_t empty_reads[2] = { 0, 0 };
+        PinnedBuffer<unsigned long long> h_err;
+        hipStream_t last = nullptr; // the stream the scratch was last used on: another one waits for it first
+    };
+    StatsState stats_;
+    StatsState stats_api_; // read_stats_device's own
+    // queues the count of `b` into st.acc[which] on `stream` (d_qual null: without the quality sections)
+    void run_read_stats(StatsState& st, int which, const DeviceBatch& b, const uint8_t* d_qual, uint32_t bias, const uint8_t* d_rev, const uint8_t* d_flags,
+        uint64_t take, hipStream_t stream);
+    // the block's quality bytes into one of stats_.qual, queued on `stream`
+    const uint8_t* stats_qual_in(const HostBatch& hb, hipStream_t stream);
+    // map_host's and map_host_async's hook: block `b` of `hb`, which is on the device once `stream` gets there, counted as hb.stats_which says
+    void count_unfiltered(const HostBatch& hb, const DeviceBatch& b, const uint8_t* d_qual, const uint8_t* d_rev, hipStream_t stream);
     FilterScratch filter_api_; // read_filter_device's and read_trim_device's own (as bam_api_)
     BamScratch bam_api_; // pack_bam_on_device's own (the caller's stream is not ordered with the context's)
     uint64_t bam_blocks_ = 0;

@@ -30,6 +30,7 @@
 #include "adapter_args.h"
 #include "decoy_args.h"
 #include "mask_args.h"
+#include "qc_args.h"
 #include "poly_args.h"
 
 namespace {
@@ -67,6 +68,7 @@ struct Args {
     uint32_t trim_qual_milli = 0, trim_window = 0;
     uint32_t mask_qual = 0; // --mask-qual Q: base masking (include/drprg_hip.h "base masking"); 0 = not set
     drprg::AdapterArgs adapters; // --adapter SEQ, --adapter-error E, --adapter-min-overlap O (include/drprg_hip.h "adapter trimming")
+    drprg::QcArgs qc; // --qc-json FILE, --qc-no-qual (include/drprg_hip.h "read statistics")
     drprg::PolyArgs poly; // --poly-tail LETTERS, --poly-min-len M, --min-complexity P (include/drprg_hip.h "poly tails", "read complexity")
     drprg::DecoyArgs decoy; // --decoy FASTA, --decoy-k K, --decoy-min-frac F, --decoy-min-kmers M (include/drprg_hip.h "decoy screen")
     std::string outdir = "pandora", vcf_refs;
@@ -89,7 +91,7 @@ void usage()
         "                   [--dedup] [--min-read-len L] [--max-read-len L] [--min-read-qual Q]\n"
         "                   [--trim-front N] [--trim-tail N] [--trim-qual Q [--trim-window W]]\n"
         "                   [--adapter SEQ]... [--adapter-error E] [--adapter-min-overlap O] [--adapter-indels] [--front-adapter SEQ]...\n"
-        "                   [--poly-tail LETTERS [--poly-min-len M]] [--min-complexity P]\n"
+        "                   [--poly-tail LETTERS [--poly-min-len M]] [--min-complexity P] [--qc-json FILE [--qc-no-qual]]\n"
         "                   [--mask-qual Q] [--decoy FASTA]... [--decoy-k K] [--decoy-min-frac F] [--decoy-min-kmers M]\n"
         "                   [--vcf-refs FASTA] [-t N] [-w W] [-k K] [-c N] [-I] [-K] [-e RATE] [--max-diff N] <prg> <reads>\n"
         "  pandora discover [same mapping options] <prg> <query.tsv>\n"
@@ -134,6 +136,7 @@ void usage()
         "                The read keeps its length, its place in the depth arithmetic and its mean quality; only the k-mers that hold a masked\n"
         "                base stop existing.  Needs qualities: FASTA, or a BAM record without them, is an error under it.  A threshold on what the\n"
         "                basecaller claims: at Nanopore qualities a Q of 10 or more leaves few 15-mers.  Default: off.\n"
+        "  %s"
         "  --decoy FASTA (up to 8 times; plain or .gz), --decoy-k K (9 to 31, default 31), --decoy-min-frac F (in (0, 1], default 0.5),\n"
         "                --decoy-min-kmers M (default 1): a read is dropped as a contaminant when at least M of its k-mers, and at least the\n"
         "                fraction F of its k-mers without a letter other than ACGT, are k-mers of the decoy files in either orientation -- on\n"
@@ -141,7 +144,8 @@ void usage()
         "                build's own rule (k-mer containment, as bbduk ref=); sized for mitochondrion, NTM genomes, phiX, not a human genome.\n"
         "  <reads>: FASTA or FASTQ, plain or gzip; or BAM (secondary and supplementary records are skipped, reverse-strand records are\n"
         "           reverse-complemented, alignments are ignored, qualities are looked at by --min-read-qual, --trim-qual and --mask-qual alone)\n"
-        "environment: DRPRG_HIP_DEVICE selects the GPU (default 0); DRPRG_HIP_DEVICES=0,1,.. maps on several GPUs of the node\n");
+        "environment: DRPRG_HIP_DEVICE selects the GPU (default 0); DRPRG_HIP_DEVICES=0,1,.. maps on several GPUs of the node\n",
+        drprg::QcArgs::usage());
 }
 
 Args parse(int argc, char** argv)
@@ -249,6 +253,8 @@ Args parse(int argc, char** argv)
             const std::string e = a.decoy.set_kmers(need(i));
             if (!e.empty()) die(e, 2);
         }
+        else if (s == "--qc-json") a.qc.json = need(i);
+        else if (s == "--qc-no-qual") a.qc.no_qual = true;
         else if (s == "--dedup") a.dedup = true;
         else if (s == "-o" || s == "--outdir") a.outdir = need(i);
         else if (s == "--vcf-refs") a.vcf_refs = need(i);
@@ -277,6 +283,7 @@ Args parse(int argc, char** argv)
     if (const std::string e = a.adapters.check(); !e.empty()) die(e, 2);
     if (const std::string e = a.decoy.check(); !e.empty()) die(e, 2);
     if (const std::string e = a.poly.check(); !e.empty()) die(e, 2);
+    if (const std::string e = a.qc.check(); !e.empty()) die(e, 2);
     if (const char* d = std::getenv("DRPRG_HIP_DEVICE")) a.device = std::atoi(d);
     return a;
 }
@@ -325,6 +332,7 @@ drprg_hip_ctx* open_ctx(const Args& a)
     if (int rc = drprg_hip_set_read_trim(ctx, a.trim_front, a.trim_tail, a.trim_qual_milli, a.trim_window)) die(drprg_hip_last_error(ctx), -rc);
     if (int rc = drprg_hip_set_base_mask(ctx, a.mask_qual)) die(drprg_hip_last_error(ctx), -rc);
     if (int rc = a.poly.set_on(ctx, drprg_hip_set_poly_trim, drprg_hip_set_min_complexity)) die(drprg_hip_last_error(ctx), -rc);
+    if (int rc = drprg_hip_set_read_stats(ctx, a.qc.mode())) die(drprg_hip_last_error(ctx), -rc);
     if (a.adapters.any()) {
         if (int rc = a.adapters.set_on(ctx, drprg_hip_set_adapters, drprg_hip_set_adapters2)) die(drprg_hip_last_error(ctx), -rc);
     }
@@ -472,6 +480,14 @@ void report_filter(drprg_hip_ctx* ctx, const Args& a)
         (unsigned long long)fi[4], (unsigned long long)fi[5], (unsigned long long)fi[6], (unsigned long long)fi[7]);
 }
 
+// --qc-json: the report of the mapping pass (behind --dedup and --subsample-covg, whose counts it carries), and -v's two lines
+void report_qc(drprg_hip_ctx* ctx, const Args& a, const std::string& sample)
+{
+    if (!a.qc.any()) return;
+    if (int rc = drprg_hip_write_qc_json(ctx, a.qc.json.c_str(), sample.c_str())) die(std::string("--qc-json: ") + drprg_hip_last_error(ctx), -rc);
+    if (a.verbose) a.qc.report(ctx, [](const char* line) { std::printf("[pandora-hip] %s\n", line); });
+}
+
 const char* COVERAGE_CACHE = ".drprg_hip_coverage";
 
 int cmd_map(const Args& a)
@@ -484,7 +500,8 @@ int cmd_map(const Args& a)
     // pass left its coverage vector there, take it instead of streaming the reads again
     const std::string cache = a.outdir + "/discover/" + COVERAGE_CACHE;
     uint64_t cached[8];
-    if (drprg_hip_load_coverage(ctx, cache.c_str(), run_tag(a, a.positional[1]).c_str(), cached) == 0) {
+    // (--qc-json describes a pass over the reads: with it the pass is made, whatever discover left)
+    if (!a.qc.any() && drprg_hip_load_coverage(ctx, cache.c_str(), run_tag(a, a.positional[1]).c_str(), cached) == 0) {
         std::printf("[pandora-hip] coverage of this PRG and these reads taken from %s (reads=%llu bases=%llu hits=%llu): no second mapping pass\n",
             cache.c_str(), (unsigned long long)cached[0], (unsigned long long)cached[1], (unsigned long long)cached[3]);
     } else {
@@ -496,6 +513,7 @@ int cmd_map(const Args& a)
         report_cap(ctx, a);
         report_bam(ctx, a);
         report_filter(ctx, a);
+        report_qc(ctx, a, "sample");
     }
     const std::string vcf = a.outdir + "/pandora_genotyped.vcf";
     if (int rc = drprg_hip_genotype(ctx, a.vcf_refs.empty() ? nullptr : a.vcf_refs.c_str(), vcf.c_str(), "sample"))
@@ -529,6 +547,7 @@ int cmd_discover(const Args& a)
     report_cap(ctx, a);
     report_bam(ctx, a);
     report_filter(ctx, a);
+    report_qc(ctx, a, sample);
     // The mapping half of discover is the same kernels as `map`; its products are (1) the candidate regions -- stretches of each
     // locus' called consensus that the reads do not support --, (2) the novel variants a host-side pile-up of
     // the reads finds in them, and (3) the coverage vector, kept for the `map` call drprg issues next on the unchanged PRG.

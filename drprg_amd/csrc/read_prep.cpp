@@ -63,7 +63,10 @@ void Mapper::map_host(const HostBatch& hb)
     sync();
     HIPCHK(hipSetDevice(device_));
     if (hb.offsets[0] != 0) throw Error(DRPRG_EINVAL, "offsets[0] must be 0");
-    map(copy_to_stage(hb, stage_sync_, stream_, stream_), nullptr, nullptr, stream_, false);
+    const DeviceBatch b = copy_to_stage(hb, stage_sync_, stream_, stream_);
+    if (hb.stats_which) // (no prep setting: the block is counted where it lies, in front of the map)
+        count_unfiltered(hb, b, hb.stats_mode == 1 ? stats_qual_in(hb, stream_) : nullptr, hb.bam && hb.reverse ? stage_sync_.d_reverse.data() : nullptr, stream_);
+    map(b, nullptr, nullptr, stream_, false);
     HIPCHK(hipStreamSynchronize(stream_)); // the staging buffers are reused by the next call
 }
 
@@ -167,6 +170,8 @@ void Mapper::map_host_async(const HostBatch& hb)
     if (hb.offsets[0] != 0) throw Error(DRPRG_EINVAL, "offsets[0] must be 0");
     if (hb.n_bases() == 0) { // only empty reads: nothing to copy, nothing to keep, nothing to map (the counters still see them)
         count_unmapped(n_reads, keeping);
+        for (int w = 0; w < 2; ++w)
+            if (hb.stats_which >> w & 1) stats_.empty_reads[w] += n_reads;
         return;
     }
     // under keep_reads the block goes into device memory of its own and stays there; else into a staging set
@@ -180,8 +185,10 @@ void Mapper::map_host_async(const HostBatch& hb)
     if (own && !kept_copied_) kept_copied_.create(false);
     const hipEvent_t copied = own ? kept_copied_ : st->copied;
     const DeviceBatch b = own ? copy_block_in(hb, st, own->bases, own->offsets, own->npos, cs, stream_) : copy_to_stage(hb, *st, cs, stream_);
+    const uint8_t* const d_stats_qual = hb.stats_which && hb.stats_mode == 1 ? stats_qual_in(hb, cs) : nullptr; // (beside the block, in front of `copied`)
     HIPCHK(hipEventRecord(copied, cs));
     HIPCHK(hipStreamWaitEvent(stream_, copied, 0));
+    if (hb.stats_which) count_unfiltered(hb, b, d_stats_qual, hb.bam && hb.reverse ? st->d_reverse.data() : nullptr, stream_); // (no wait: queued in front of the map)
     if (own) {
         resident_.add(b, n_reads);
         map_resident_block(b);
@@ -555,6 +562,129 @@ void Mapper::base_mask_device(const ReadFilter& f, const uint8_t* d_qual, uint32
     HIPCHK(hipStreamSynchronize(stream));
 }
 
+// ---- read statistics -----------------------------------------------------------------------------------------------------------------
+void Mapper::run_read_stats(StatsState& st, int which, const DeviceBatch& b, const uint8_t* d_qual, uint32_t bias, const uint8_t* d_rev, const uint8_t* d_flags,
+    uint64_t take, hipStream_t stream)
+{
+    if (b.n_reads == 0) return;
+    if (b.n_bases >= dev::RS_MAX_BASES) throw Error(DRPRG_EOVERFLOW, "read statistics: a block of 2^32 bases or more");
+    if (st.last && st.last != stream) HIPCHK(hipStreamSynchronize(st.last)); // (the scratch below is shared: one stream at a time)
+    st.last = stream;
+    if (!st.acc[which]) {
+        st.acc[which].alloc(dev::RS_DEV_WORDS);
+        HIPCHK(dev::launch_read_stats_clear(st.acc[which].data(), stream));
+    }
+    grow(st.gcv, b.n_reads);
+    if (d_qual) grow(st.esum, b.n_reads);
+    dev::ReadStatsArgs a {};
+    if (b.packed) {
+        a.words = reinterpret_cast<const uint32_t*>(b.d_bases);
+        if (b.n_npos) { // the position list as a bitmap, as adapter_points makes it
+            const uint64_t n16 = (b.n_bases + 15) / 16 + 8;
+            grow(st.nbits, n16);
+            HIPCHK(hipMemsetAsync(st.nbits.data(), 0, n16 * sizeof(uint16_t), stream));
+            HIPCHK(dev::launch_mark_npos(b.d_npos, b.n_npos, b.n_bases, st.nbits.data(), stream));
+            a.nbits = st.nbits.data();
+        }
+    } else a.text = b.d_bases;
+    a.qual = d_qual; a.bias = bias; a.offsets = b.d_offsets; a.rev = d_rev; a.flags = d_flags; a.n_reads = b.n_reads; a.n_bases = b.n_bases; a.take = take;
+    a.gcv = st.gcv.data(); a.esum = st.esum.data(); a.acc = st.acc[which].data();
+    HIPCHK(dev::launch_read_stats(a, stream));
+}
+
+const uint8_t* Mapper::stats_qual_in(const HostBatch& hb, hipStream_t stream)
+{
+    if (!hb.qual) throw Error(DRPRG_EINVAL, "--qc-json: the reads came without base qualities");
+    DeviceBuffer<uint8_t>& q = stats_.qual[stats_.qual_next];
+    stats_.qual_next ^= 1; // (two in turn: the block that used this one two calls ago is complete, as with the staging sets)
+    const uint64_t n = hb.n_bases();
+    grow(q, n + 64);
+    HIPCHK(hipMemcpyAsync(q.data(), hb.qual, n, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemsetAsync(q.data() + n, 0, 64, stream));
+    return q.data();
+}
+
+void Mapper::count_unfiltered(const HostBatch& hb, const DeviceBatch& b, const uint8_t* d_qual, const uint8_t* d_rev, hipStream_t stream)
+{
+    for (int w = 0; w < 2; ++w) {
+        if (!(hb.stats_which >> w & 1)) continue;
+        if (b.n_bases == 0) stats_.empty_reads[w] += b.n_reads;
+        else run_read_stats(stats_, w, b, d_qual, hb.qual_bias, d_rev, nullptr, b.n_reads, stream);
+    }
+}
+
+void Mapper::count_host_block(const HostBatch& hb)
+{
+    if (hb.n_reads == 0 || !hb.stats_which) return;
+    sync();
+    HIPCHK(hipSetDevice(device_));
+    if (hb.offsets[0] != 0) throw Error(DRPRG_EINVAL, "offsets[0] must be 0");
+    if (hb.n_bases() == 0) {
+        for (int w = 0; w < 2; ++w)
+            if (hb.stats_which >> w & 1) stats_.empty_reads[w] += hb.n_reads;
+        return;
+    }
+    const DeviceBatch b = copy_to_stage(hb, stage_sync_, stream_, stream_);
+    count_unfiltered(hb, b, hb.stats_mode == 1 ? stats_qual_in(hb, stream_) : nullptr, hb.bam && hb.reverse ? stage_sync_.d_reverse.data() : nullptr, stream_);
+    HIPCHK(hipStreamSynchronize(stream_));
+}
+
+void Mapper::read_stats(int which, uint64_t out[dev::RS_WORDS])
+{
+    sync();
+    HIPCHK(hipSetDevice(device_));
+    for (uint32_t i = 0; i < dev::RS_WORDS; ++i) out[i] = 0;
+    out[dev::RS_MIN_LEN] = ~0ull;
+    if (stats_.acc[which]) {
+        if (copy_stream_) HIPCHK(hipStreamSynchronize(copy_stream_));
+        HIPCHK(hipStreamSynchronize(stream_));
+        HIPCHK(hipMemcpy(out, stats_.acc[which].data(), dev::RS_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    }
+    if (const uint64_t n = stats_.empty_reads[which]) { // reads of blocks that held no base
+        out[dev::RS_READS] += n;
+        out[dev::RS_LEN_READS] += n;
+        out[dev::RS_MIN_LEN] = 0;
+    }
+}
+
+void Mapper::check_read_stats()
+{
+    sync();
+    HIPCHK(hipSetDevice(device_));
+    if (copy_stream_) HIPCHK(hipStreamSynchronize(copy_stream_));
+    HIPCHK(hipStreamSynchronize(stream_));
+    for (int w = 0; w < 2; ++w) {
+        if (!stats_.acc[w]) continue;
+        unsigned long long e[2] = { 0, 0 };
+        HIPCHK(hipMemcpy(e, stats_.acc[w].data() + dev::RS_DEV_BAD_AT, sizeof e, hipMemcpyDeviceToHost));
+        if (e[1]) throw Error(DRPRG_EINVAL, "read statistics: a block's offsets do not ascend to its number of bases");
+        if (e[0] != ~0ull) throw Error(DRPRG_EFORMAT, "a base quality outside 0..93 (quality byte " + std::to_string(e[0] - 1) + " of an ingest block; FASTQ: bytes 33..126, BAM: bytes 0..93)");
+    }
+}
+
+void Mapper::read_stats_device(const uint8_t* d_text, const uint32_t* d_words, const uint64_t* d_npos, uint64_t n_npos, const uint8_t* d_qual, uint32_t bias,
+    const uint64_t* d_offsets, const uint8_t* d_rev, uint64_t n_reads, uint64_t n_bases, const uint8_t* d_flags, uint64_t take, uint64_t out[dev::RS_WORDS],
+    uint64_t res[2], hipStream_t stream)
+{
+    for (uint32_t i = 0; i < dev::RS_WORDS; ++i) out[i] = 0;
+    res[0] = res[1] = 0;
+    if (n_reads == 0) return;
+    stream = device_entry(stream, !d_offsets || (n_bases && !d_text && !d_words) || (n_npos && !d_npos), n_reads);
+    StatsState& st = stats_api_;
+    if (!st.acc[0]) st.acc[0].alloc(dev::RS_DEV_WORDS);
+    if (!st.h_err) st.h_err.alloc(dev::RS_DEV_WORDS);
+    HIPCHK(dev::launch_read_stats_clear(st.acc[0].data(), stream));
+    const DeviceBatch b { d_words ? reinterpret_cast<const uint8_t*>(d_words) : d_text, d_offsets, n_reads, n_bases, d_words != nullptr, d_npos, n_npos };
+    run_read_stats(st, 0, b, d_qual, bias, d_rev, d_flags, take, stream);
+    HIPCHK(hipMemcpyAsync(st.h_err.data(), st.acc[0].data(), dev::RS_DEV_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    const unsigned long long* h = st.h_err.data();
+    for (uint32_t i = 0; i < dev::RS_WORDS; ++i) out[i] = h[i];
+    if (out[dev::RS_MIN_LEN] == ~0ull) out[dev::RS_MIN_LEN] = 0;
+    res[0] = h[dev::RS_DEV_BAD_AT] == ~0ull ? 0 : h[dev::RS_DEV_BAD_AT];
+    res[1] = h[dev::RS_DEV_OFFSETS];
+}
+
 // ---- a host block behind the filter: map_host_filtered and its steps ---------------------------------------------------------------------
 // what the trim stage and the filter say alike about a quality byte out of range (at: the byte's index + 1)
 static Error bad_quality_error(uint64_t at, uint64_t n_bases, uint32_t bias)
@@ -760,11 +890,16 @@ void Mapper::map_host_filtered(const HostBatch& hb, const ReadFilter& f, uint64_
     bool keeping = resident_.active();
     if (n_bases == 0) { // (the counters still see them)
         only_empty_reads(n_reads, f, keeping, o);
+        if (f.read_stats) {
+            stats_.empty_reads[STATS_RAW] += n_reads;
+            stats_.empty_reads[STATS_PREPARED] += o.reads_kept;
+        }
         return;
     }
     if (f.trim_qual_milli && !hb.qual) throw Error(DRPRG_EINVAL, "--trim-qual: the reads came without base qualities");
     if (f.mask_qual && !hb.qual) throw Error(DRPRG_EINVAL, "--mask-qual: the reads came without base qualities");
     if (f.use_qual() && !hb.qual) throw Error(DRPRG_EINVAL, "--min-read-qual: the reads came without base qualities");
+    if (f.read_stats == 1 && !hb.qual) throw Error(DRPRG_EINVAL, "--qc-json: the reads came without base qualities (--qc-no-qual reports without them)");
     if (n_reads > dev::MAX_BATCH_READS) throw Error(DRPRG_EOVERFLOW, "at most " + std::to_string(dev::MAX_BATCH_READS) + " reads per batch");
     // 1. copy in: the block into a staging set, its quality bytes beside it
     const hipStream_t cs = copy_stream();
@@ -780,16 +915,34 @@ void Mapper::map_host_filtered(const HostBatch& hb, const ReadFilter& f, uint64_
     }
     const uint8_t* d_qual = fs.d_qual.data();
     uint32_t trim_err = 0;
+    // the raw snapshot: the block as the file held it, queued in front of the trim stage; what it refuses arrives with the next read-back
+    const uint8_t* const d_stats_rev = hb.bam && hb.reverse ? st.d_reverse.data() : nullptr;
+    if (f.read_stats) {
+        run_read_stats(stats_, STATS_RAW, src, f.read_stats == 1 ? d_qual : nullptr, hb.qual_bias, d_stats_rev, nullptr, n_reads, cs);
+        if (!stats_.h_err) stats_.h_err.alloc(2);
+        HIPCHK(hipMemcpyAsync(stats_.h_err.data(), stats_.acc[STATS_RAW].data() + dev::RS_DEV_BAD_AT, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, cs));
+    }
+    const auto raw_refusals = [&]() { // (behind a wait for the copy stream)
+        if (!f.read_stats) return;
+        if (stats_.h_err[1]) throw Error(DRPRG_EINVAL, "read statistics: the block's offsets do not ascend to its number of bases");
+        if (stats_.h_err[0] != ~0ull) throw bad_quality_error(stats_.h_err[0], n_bases, hb.qual_bias);
+    };
     // 2. trim, 3. mask, 4. filter, 5. the depth cap
     if (f.trims() && !trim_block(hb, f, st, src, d_qual, trim_err, o)) { // reads of no bases are left: nothing to map
         hand_back_stage();
+        raw_refusals();
         only_empty_reads(n_reads, f, keeping, o);
+        if (f.read_stats) stats_.empty_reads[STATS_PREPARED] += o.reads_kept;
         return;
     }
     if (f.mask_qual) mask_block(hb, f, st, src, d_qual);
     filter_block(hb, f, fs, src, d_qual, trim_err, o);
+    raw_refusals();
     if (f.mask_qual) mask_done(hb, st, src, o); // (the block's list is the one behind the mask before the block is placed)
     const KeptPart k = cut_at_cap(fs, n_reads, cap_need, o);
+    // the prepared snapshot: exactly what the block hands on -- the filter's flags below the cap's cut, on the block before it is compacted
+    if (f.read_stats)
+        run_read_stats(stats_, STATS_PREPARED, src, f.read_stats == 1 ? d_qual : nullptr, hb.qual_bias, d_stats_rev, fs.d_flag.data(), k.take, cs);
     o.mapped_reads = k.n_reads;
     o.mapped_bases = k.n_bases;
     if (k.n_bases == 0) { // nothing of the block is left, or empty reads only

@@ -384,6 +384,65 @@ class Context:
                                                stream), self._h)
         return tuple(int(x) for x in out)
 
+    # ---- read statistics (include/drprg_hip.h: drprg_hip_set_read_stats) -----------------------
+    @staticmethod
+    def read_stats_layout():
+        """the snapshot's layout as the library holds it (csrc/read_stats_words.h): words, the sections' offsets and sizes"""
+        out = (C.c_uint64 * 13)()
+        _check(lib.drprg_hip_read_stats_layout(out))
+        names = ("words", "len_reads", "len_bases", "cyc_base", "cyc_qsum", "qual_hist", "readq_hist", "gc_hist", "len_bins", "cycles", "cols", "quals", "gc_bins")
+        lay = dict(zip(names, (int(x) for x in out)))
+        assert lay["words"] == int(lib.drprg_hip_read_stats_words())
+        return lay
+
+    @classmethod
+    def read_stats_dict(cls, words):
+        """a snapshot's words as a dict of numpy arrays (views of `words`): reads, bases, min_len, max_len, len_reads, len_bases,
+        cyc_base [cycles + 1, 5] (A, C, G, T, U), cyc_qsum, qual_hist, readq_hist, gc_hist, and the flat `words`"""
+        lay = cls.read_stats_layout()
+        w = np.asarray(words, dtype=np.uint64)
+        ncyc = lay["cycles"] + 1
+        return {
+            "words": w, "reads": int(w[0]), "bases": int(w[1]), "min_len": int(w[2]), "max_len": int(w[3]),
+            "len_reads": w[lay["len_reads"]:lay["len_reads"] + lay["len_bins"]], "len_bases": w[lay["len_bases"]:lay["len_bases"] + lay["len_bins"]],
+            "cyc_base": w[lay["cyc_base"]:lay["cyc_base"] + ncyc * lay["cols"]].reshape(ncyc, lay["cols"]),
+            "cyc_qsum": w[lay["cyc_qsum"]:lay["cyc_qsum"] + ncyc], "qual_hist": w[lay["qual_hist"]:lay["qual_hist"] + lay["quals"]],
+            "readq_hist": w[lay["readq_hist"]:lay["readq_hist"] + lay["quals"]], "gc_hist": w[lay["gc_hist"]:lay["gc_hist"] + lay["gc_bins"]],
+        }
+
+    def set_read_stats(self, mode=1):
+        """from the next map_fastx on, every ingest block is counted on the device into the raw and the prepared snapshot: mode 1 with
+        qualities (FASTA is an error then), 2 without the three quality sections, 0 off"""
+        _check(lib.drprg_hip_set_read_stats(self._h, int(mode)), self._h)
+
+    def read_stats_info(self, which=0, n_words=None):
+        """the snapshot (0 raw, 1 prepared) as read_stats_dict gives it; n_words: the size of the buffer handed to the library"""
+        n = int(lib.drprg_hip_read_stats_words()) if n_words is None else int(n_words)
+        out = np.zeros(max(n, 1), dtype=np.uint64)
+        _check(lib.drprg_hip_read_stats_info(self._h, int(which), out.ctypes.data, n), self._h)
+        return self.read_stats_dict(out)
+
+    def read_stats_prepared_is_raw(self):
+        rc = lib.drprg_hip_read_stats_prepared_is_raw(self._h)
+        _check(min(rc, 0), self._h)
+        return rc == 1
+
+    def read_stats_device(self, d_text, d_words, d_npos, n_npos, d_qual, qual_bias, d_offsets, d_rev, n_reads, n_bases, d_flags=None, take=None, n_words=None,
+                          stream=None):
+        """the statistics kernels alone on device buffers (addresses as integers): the bases as text (d_words None) or packed words (d_text
+        None) with their ascending position list; d_qual None: no quality section; d_rev, d_flags may be None; take: only reads below it
+        count (None: all).  Returns the snapshot as read_stats_dict gives it; raises -84 for a quality byte out of range, -22 for offsets
+        that do not ascend to n_bases or a buffer (n_words) that is too small"""
+        n = int(lib.drprg_hip_read_stats_words()) if n_words is None else int(n_words)
+        out = np.zeros(max(n, 1), dtype=np.uint64)
+        _check(lib.drprg_hip_read_stats_device(self._h, d_text, d_words, d_npos, int(n_npos), d_qual, int(qual_bias), d_offsets, d_rev, int(n_reads), int(n_bases),
+                                               d_flags, int(n_reads if take is None else take), out.ctypes.data, n, stream), self._h)
+        return self.read_stats_dict(out)
+
+    def write_qc_json(self, path, sample=""):
+        """the report --qc-json writes: both snapshots and every stage's counters, as JSON"""
+        _check(lib.drprg_hip_write_qc_json(self._h, os.fsencode(path), sample.encode()), self._h)
+
     # ---- base masking (include/drprg_hip.h: drprg_hip_set_base_mask) ---------------------------
     def set_base_mask(self, min_qual=0):
         """from the next map_fastx on, every base whose Phred quality is below min_qual (a whole number, 1..93) becomes an unknown base on

@@ -667,6 +667,64 @@ int drprg_hip_set_min_complexity(drprg_hip_ctx* ctx, uint32_t percent);
 int drprg_hip_complexity_info(drprg_hip_ctx* ctx, uint64_t out[4]);
 int drprg_hip_complexity_device(drprg_hip_ctx* ctx, const void* d_text, const void* d_words, const void* d_npos, uint64_t n_npos, const void* d_offsets,
     uint64_t n_reads, uint64_t n_bases, void* d_diff, void* d_flags, uint64_t out[2], void* hip_stream);
+/* ---- Read statistics: the QC record of a sample (--qc-json), counted on the device as the reads arrive.  THIS BUILD'S OWN RULE: the sums
+ * fastp, NanoStat and nanoq report, before and after preparation.  Statistics only: no pass or fail verdict, no duplication estimate, no
+ * adapter guess.
+ *   Setting, per context: mode 0 (off, the default), 1 (with qualities), 2 (without the three quality sections: --qc-no-qual).
+ *   Two snapshots.  RAW: every read of every ingest block of drprg_hip_map_fastx as the file holds it, in front of the trim stage (BAM: read
+ *   orientation, secondary and supplementary records skipped, as the ingest does).  PREPARED: exactly the reads and bases the block hands on
+ *   to mapping: behind the crops, the quality trim, both adapter sides, the tail cut, the mask (a masked base is an unknown base), the read
+ *   filter, the complexity test, the decoy verdict and the depth cap's cut; a read trimmed to nothing that is kept is a read of 0 bases.  It
+ *   lies IN FRONT OF drprg_hip_dedup and drprg_hip_subsample, which work on the resident sample without qualities and keep counts of their
+ *   own.  When no prep setting and no depth cap is active the prepared snapshot is the raw one by definition and is not counted a second
+ *   time (drprg_hip_read_stats_prepared_is_raw).  Under a depth cap the ingest stops at the block that reaches it: the raw snapshot
+ *   holds that block whole and nothing behind it.
+ *   The rule, under the comparison of "poly tails": case-insensitive; every byte not in ACGTacgt, a listed position of a packed block and
+ *   a masked base are the one unknown base U.  A snapshot is drprg_hip_read_stats_words() u64 words; drprg_hip_read_stats_layout gives
+ *   out[0..12] = words, the offsets of len_reads, len_bases, cyc_base, cyc_qsum, qual_hist, readq_hist, gc_hist, then B, C, 5, 94, 101:
+ *     [0] reads, [1] bases, [2] shortest read (0 without a read), [3] longest read.
+ *     len_reads[B], len_bases[B], B = 2432: reads per length bin, and the exact sum of their lengths.  The bin of L is L for L < 1024;
+ *       otherwise, with e = floor(log2 L) in 10..31, 1024 + (e - 10) * 64 + ((L >> (e - 6)) & 63): exact below 1024, within 1/64 above.
+ *       N50 (N90) is taken on the host: the bins walked downwards over len_bases until ceil(bases / 2) (ceil(9 bases / 10)) are reached;
+ *       the bin's lowest length is reported.
+ *     cyc_base[C + 1][5], cyc_qsum[C + 1], C = 512: for position p of a read, in read orientation, the bases A, C, G, T, U and the sum of
+ *       the Phred values; entry C takes every p >= 512.  The sample's base totals are the column sums.
+ *     qual_hist[94]: bases per Phred value.
+ *     readq_hist[94]: a read of L >= 1 bases falls into the largest q with sum(E[qual_i]) <= E[q] * L in 64-bit integers, E the read
+ *       filter's table round(2^31 * 10^(-q / 10)): the quality of the read's MEAN ERROR PROBABILITY, what --min-read-qual judges, not the
+ *       mean of its Phred values.  q = 0 always holds.  Reads of no bases are not counted.
+ *     gc_hist[101]: a read with V >= 1 bases of ACGT falls into floor(100 * (G + C) / V); reads without one are not counted.
+ *   Every word is an integer sum over independent reads and positions: bit-exact whatever the thread count, the block boundaries, the
+ *   devices and the input form (FASTQ, .gz, BAM; ASCII or packed transport).
+ *   Qualities: the FASTQ byte - 33, or BAM's QUAL byte; base p of a reverse-strand BAM record of L bases has quality byte L - 1 - p; a byte
+ *   outside 0..93 fails the run (-EFORMAT, -84).  Mode 1 needs them: a FASTA record, or a BAM record whose QUAL starts with 0xFF, fails
+ *   drprg_hip_map_fastx with -EINVAL and a text that names --qc-json (another quality setting, when one is set, is named first).  Under
+ *   mode 2 no quality byte is parsed, copied or moved on the statistics' account, qual_hist, readq_hist and cyc_qsum stay zero, and every
+ *   input is served.  drprg_hip_map_host* and drprg_hip_map_device* carry no qualities: they return -EINVAL while mode 1 is set, and under
+ *   mode 2 their reads are simply not counted.  A block is shorter than 2^32 bases (-EOVERFLOW otherwise).
+ *   With only this setting on, coverage, every counter and the resident sample are those of a run without it; the kernels are queued beside
+ *   the block's other work and add no wait per block.  With mode 0 nothing of this exists: no launch, no allocation, no quality byte.
+ *   drprg_hip_set_read_stats: applies from the next drprg_hip_map_fastx, on every device of the context; a reset keeps the setting and
+ *     zeroes both snapshots.  -EINVAL for another mode.
+ *   drprg_hip_read_stats_info: which = 0 raw, 1 prepared; the devices' snapshots folded, read back once.  -EINVAL when n_words is below
+ *     drprg_hip_read_stats_words().
+ *   drprg_hip_read_stats_device: the kernels alone on caller-owned device buffers; one snapshot into out.  The bases in the two forms and
+ *     under the address, padding and stream rules of drprg_hip_base_mask_device (d_npos only read); d_qual with qual_bias and d_rev as
+ *     there, or d_qual NULL: the quality sections stay zero.  d_flags: u8[n_reads], 0 for a read that is not counted, or NULL; take: only
+ *     reads below it are counted (n_reads: all).  n_reads == 0: a snapshot of zeros, no pointer is looked at.  -EFORMAT for a quality byte
+ *     outside 0..93, the text naming it; -EINVAL when the offsets do not ascend from 0 to n_bases or n_words is too small.
+ *   drprg_hip_write_qc_json: the report both executables write for --qc-json: sample, settings, both snapshots (totals, N50, N90, base
+ *     totals, non-empty length bins as [lowest length, reads, bases], per-cycle arrays cut at the longest read, the histograms) and, under
+ *     "stages", the words of every stage's *_info entry in their order, with drprg_hip_dedup's and drprg_hip_subsample's four outputs. */
+uint64_t drprg_hip_read_stats_words(void);
+int drprg_hip_read_stats_layout(uint64_t out[13]);
+int drprg_hip_set_read_stats(drprg_hip_ctx* ctx, int mode);
+int drprg_hip_read_stats_info(drprg_hip_ctx* ctx, int which, uint64_t* out, uint64_t n_words);
+int drprg_hip_read_stats_prepared_is_raw(drprg_hip_ctx* ctx); /* 1: yes, 0: no; negative: error */
+int drprg_hip_read_stats_device(drprg_hip_ctx* ctx, const void* d_text, const void* d_words, const void* d_npos, uint64_t n_npos, const void* d_qual,
+    uint32_t qual_bias, const void* d_offsets, const void* d_rev, uint64_t n_reads, uint64_t n_bases, const void* d_flags, uint64_t take, uint64_t* out,
+    uint64_t n_words, void* hip_stream);
+int drprg_hip_write_qc_json(drprg_hip_ctx* ctx, const char* path, const char* sample);
 /* The read selection drprg_hip_discover_reads uses when the reads are resident, on its own: for every device of the context, in order,
  * every kept read in which a k-mer of `anchors` STARTS (anchors: n_anchors k-mers of A bases, 2 bits per base, A 0 C 1 G 2 T 3, first base
  * in the high bits; any order, duplicates allowed).  A block's reads are one base stream: read r of a block is returned iff for some p with
