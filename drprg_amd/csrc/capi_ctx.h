@@ -46,6 +46,11 @@ struct SampleState {
     bool fastx_unordered = false;
     bool needs_reset = false; // reduce_devices failed half way: the devices' vectors are in no defined state
     Selection subsample, dedup; // drprg_hip_subsample, drprg_hip_dedup
+    // mate overlap: drprg_hip_begin_mates was called (the files mapped since are side 2); the last drprg_hip_pair_overlap's twelve counts
+    // and its chosen shift per source pair
+    bool mates_begun = false, pair_done = false;
+    uint64_t pair_counts[12] = {};
+    std::vector<int32_t> pair_shifts;
     // What the read filter has counted: added to by the submitters of drprg_hip_map_fastx, one per device, under filter_mu.  The blocks'
     // outcomes summed: drprg_hip_read_filter_info, and in .trim / .adapter / .front drprg_hip_read_trim_info,
     // drprg_hip_adapter_trim_info and drprg_hip_front_adapter_info, in .mask drprg_hip_base_mask_info, in .decoy drprg_hip_decoy_info, in
@@ -75,6 +80,7 @@ struct drprg_hip_ctx {
     // drprg_hip_set_poly_trim and drprg_hip_set_min_complexity ride in it too
     drprg::Mapper::ReadFilter read_filter;
     std::mutex filter_mu; // guards sample.filter_counts
+    drprg::Mapper::PairSetting pair; // drprg_hip_set_pair_overlap
     // ---- results of the last calls: a reset keeps them ----
     uint32_t ginfo[4] = { 0, 0, 0, 0 };
     std::vector<drprg::VcfRecord> last_records; // of the last drprg_hip_genotype (drprg_hip_genotype_alleles)

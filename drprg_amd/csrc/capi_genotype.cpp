@@ -85,8 +85,12 @@ int drprg_hip_discover_reads(drprg_hip_ctx* ctx, const char* reads_path, const c
     }
     // the reads of this very file are in HBM (drprg_hip_keep_reads): the device picks the few that hold an anchor k-mer
     ResidentReads resident;
-    ctx->last_discover_resident = reads_resident(ctx, reads_path);
+    // (a paired sample is two files: the resident reads stand for both, reads_path for side 1 alone)
+    ctx->last_discover_resident = reads_resident(ctx, ctx->sample.mates_begun ? nullptr : reads_path);
     // (the pass over the file knows nothing of the read filter: rather than pile up reads the mapping never saw, say so)
+    if (!ctx->last_discover_resident && ctx->sample.mates_begun)
+        throw Error(DRPRG_ENODATA, "discover: the sample was mapped from two mate files (drprg_hip_begin_mates) and its reads are not resident in device memory; a "
+                                   "pass over the file would pile up the first file's reads alone, uncut (raise DRPRG_HIP_KEEP_READS_GB)");
     if (!ctx->last_discover_resident && (ctx->sample.filter_counts.adapter.reads_cut || ctx->sample.filter_counts.front.reads_cut))
         throw Error(DRPRG_ENODATA, "discover: adapter trimming cut bases off reads of this sample and the cut reads are not resident in device memory; a pass "
                                    "over the file would pile up reads with their adapters (raise DRPRG_HIP_KEEP_READS_GB, or cut the file first)");

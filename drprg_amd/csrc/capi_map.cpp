@@ -362,6 +362,10 @@ int drprg_hip_set_threads(drprg_hip_ctx* ctx, int threads)
 // These entry points carry no qualities: while a filter is set they refuse, rather than map unfiltered reads without saying so.
 static void refuse_unfiltered(const drprg_hip_ctx* ctx, const char* entry)
 {
+    if (ctx->pair.on())
+        throw Error(DRPRG_EINVAL, std::string(entry) + ": a mate-overlap setting is on (drprg_hip_set_pair_overlap) and the sides are numbered in "
+                                                      "drprg_hip_map_fastx; this entry would map reads that have no mate (clear it with "
+                                                      "drprg_hip_set_pair_overlap(ctx, 0, 0, 0))");
     if (ctx->read_filter.decoy())
         throw Error(DRPRG_EINVAL, std::string(entry) + ": a decoy set is loaded (drprg_hip_set_decoy) and the screen runs in drprg_hip_map_fastx; this entry "
                                                       "would map the reads unscreened (clear it with drprg_hip_set_decoy(ctx, NULL, 0, 0, 0, 0))");

@@ -447,6 +447,8 @@ int drprg_hip_write_qc_json(drprg_hip_ctx* ctx, const char* path, const char* sa
     stage("max_covg", drprg_hip_max_covg_info, 4);
     const Selection& dd = ctx->sample.dedup;
     const Selection& ss = ctx->sample.subsample;
+    if (ctx->sample.pair_done) // (only when the stage ran: a report without --mate stays byte for byte what it was)
+        r.stages.emplace_back("pair_overlap", std::vector<uint64_t>(ctx->sample.pair_counts, ctx->sample.pair_counts + 12));
     r.stages.emplace_back("dedup", dd.done ? std::vector<uint64_t>(dd.counts, dd.counts + 4) : std::vector<uint64_t>());
     r.stages.emplace_back("subsample", ss.done ? std::vector<uint64_t>(ss.counts, ss.counts + 4) : std::vector<uint64_t>());
     const std::string text = qc_json(r);
@@ -705,6 +707,92 @@ int drprg_hip_dedup_keys_device(drprg_hip_ctx* ctx, const void* d_words, const v
     Mapper& m = need_mapper(ctx);
     m.dedup_keys_device((const uint32_t*)d_words, (const uint64_t*)d_offsets, n_reads, n_bases, (const uint64_t*)d_npos, n_npos, (unsigned long long*)d_keys,
         (hipStream_t)hip_stream);
+    API_END(ctx)
+}
+
+// ---- mate overlap (the rule: include/drprg_hip.h "mate overlap") -----------------------------------------------------------------
+int drprg_hip_set_pair_overlap(drprg_hip_ctx* ctx, uint32_t min_overlap, uint32_t error_milli, int clip)
+{
+    API_BEGIN(ctx)
+    if (min_overlap == 0 && error_milli == 0 && !clip) {
+        ctx->pair = Mapper::PairSetting {};
+        for (Mapper* m : mappers_of(ctx)) m->pair_record(false);
+        return DRPRG_OK;
+    }
+    if (min_overlap < 8 || min_overlap > dev::PO_MAX_LEN) throw Error(DRPRG_EINVAL, "mate overlap: the smallest overlap is a whole number in 8 .. 1024");
+    if (error_milli > 250) throw Error(DRPRG_EINVAL, "mate overlap: the share of differing columns is at most 0.25 (250 thousandths)");
+    ctx->pair = Mapper::PairSetting { min_overlap, error_milli, clip != 0 };
+    for (Mapper* m : mappers_of(ctx)) m->pair_record(true); // (from the next block on the resident set numbers its reads by side)
+    API_END(ctx)
+}
+
+int drprg_hip_begin_mates(drprg_hip_ctx* ctx)
+{
+    API_BEGIN(ctx)
+    Mapper& m = need_mapper(ctx);
+    if (!ctx->pair.on()) throw Error(DRPRG_EINVAL, "drprg_hip_begin_mates: no mate-overlap setting (drprg_hip_set_pair_overlap)");
+    refuse_several_devices(ctx, "drprg_hip_begin_mates");
+    m.begin_mates();
+    ctx->sample.mates_begun = true;
+    API_END(ctx)
+}
+
+int drprg_hip_pair_overlap(drprg_hip_ctx* ctx, uint64_t out[12])
+{
+    API_BEGIN(ctx)
+    if (!out) throw Error(DRPRG_EINVAL, "null output");
+    Mapper& m = need_mapper(ctx);
+    if (!ctx->pair.on()) throw Error(DRPRG_EINVAL, "drprg_hip_pair_overlap: no mate-overlap setting (drprg_hip_set_pair_overlap)");
+    refuse_several_devices(ctx, "drprg_hip_pair_overlap");
+    if (ctx->max_covg < 0xFFFFFFFFull)
+        throw Error(DRPRG_EINVAL, "drprg_hip_pair_overlap: a depth cap is set (drprg_hip_set_max_covg); the prefix cap would take side 1 alone, and a pair "
+                                  "needs both of its mates");
+    refuse_unordered(ctx, m, "drprg_hip_pair_overlap");
+    std::vector<int32_t> shifts;
+    uint64_t counts[dev::PO_WORDS];
+    m.pair_overlap_kept(ctx->pair, shifts, counts);
+    SampleState& s = ctx->sample;
+    s.pair_done = true;
+    s.pair_shifts = std::move(shifts);
+    for (int i = 0; i < dev::PO_WORDS; ++i) out[i] = s.pair_counts[i] = counts[i];
+    if (counts[dev::PO_BASES_KEPT] != counts[dev::PO_BASES_BEFORE]) { // the context now stands for the cut reads
+        s.host_coverage_valid = false;
+        s.total_bases = counts[dev::PO_BASES_KEPT];
+    }
+    API_END(ctx)
+}
+
+int drprg_hip_pair_overlap_shifts(drprg_hip_ctx* ctx, int32_t* d, uint64_t n)
+{
+    API_BEGIN(ctx)
+    const SampleState& s = ctx->sample;
+    if (!s.pair_done) throw Error(DRPRG_EINVAL, "drprg_hip_pair_overlap_shifts: no drprg_hip_pair_overlap call since the last reset");
+    if (n != s.pair_shifts.size())
+        throw Error(DRPRG_EINVAL, "drprg_hip_pair_overlap_shifts: the sample held " + std::to_string(s.pair_shifts.size()) + " pairs, not " + std::to_string(n));
+    if (n && !d) throw Error(DRPRG_EINVAL, "null output");
+    if (n) std::memcpy(d, s.pair_shifts.data(), n * sizeof(int32_t));
+    API_END(ctx)
+}
+
+int drprg_hip_pair_overlap_info(drprg_hip_ctx* ctx, uint64_t out[12])
+{
+    API_BEGIN(ctx)
+    if (!out) throw Error(DRPRG_EINVAL, "null output");
+    for (int i = 0; i < 12; ++i) out[i] = ctx->sample.pair_counts[i]; // (all zero before the stage has run)
+    API_END(ctx)
+}
+
+int drprg_hip_pair_overlap_device(drprg_hip_ctx* ctx, const void* d_words_a, const void* d_offsets_a, uint64_t n_bases_a, const void* d_npos_a, uint64_t n_npos_a,
+    const void* d_words_b, const void* d_offsets_b, uint64_t n_bases_b, const void* d_npos_b, uint64_t n_npos_b, uint64_t n_pairs, void* d_shift, void* d_keep_a,
+    void* d_keep_b, uint64_t out[12], void* hip_stream)
+{
+    API_BEGIN(ctx)
+    Mapper& m = need_mapper(ctx);
+    if (!out) throw Error(DRPRG_EINVAL, "null output");
+    static_assert(dev::PO_WORDS == 12, "drprg_hip_pair_overlap_device writes twelve counts");
+    const Mapper::PairSide a { (const uint32_t*)d_words_a, (const uint64_t*)d_offsets_a, n_bases_a, (const uint64_t*)d_npos_a, n_npos_a };
+    const Mapper::PairSide b { (const uint32_t*)d_words_b, (const uint64_t*)d_offsets_b, n_bases_b, (const uint64_t*)d_npos_b, n_npos_b };
+    m.pair_overlap_device(ctx->pair, a, b, n_pairs, (int32_t*)d_shift, (uint64_t*)d_keep_a, (uint64_t*)d_keep_b, out, (hipStream_t)hip_stream);
     API_END(ctx)
 }
 

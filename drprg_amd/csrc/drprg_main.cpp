@@ -23,6 +23,7 @@
 #include "decoy_args.h"
 #include "mask_args.h"
 #include "poly_args.h"
+#include "pair_args.h"
 #include "qc_args.h"
 
 namespace {
@@ -118,6 +119,7 @@ void usage()
         "              [--adapter SEQ]... [--adapter-error E] [--adapter-min-overlap O] [--adapter-indels] [--front-adapter SEQ]...\n"
         "              [--poly-tail LETTERS [--poly-min-len M]] [--min-complexity P] [--qc-json FILE [--qc-no-qual]]\n"
         "              [--mask-qual Q] [--decoy FASTA]... [--decoy-k K] [--decoy-min-frac F] [--decoy-min-kmers M]\n"
+        "              [--mate FILE [--pair-min-overlap O] [--pair-error E] [--pair-clip-overlap]]\n"
         "--poly-tail LETTERS (letters of ACGT, e.g. G or ACGT), --poly-min-len M (2 to 255, default 10): every read loses its longest suffix of\n"
         "              at least M bases that begins with one of the letters and holds at most min(n / 8, 5) other bases -- the tails two-colour\n"
         "              instruments (NextSeq, NovaSeq) leave when a cluster goes dark, which carry HIGH qualities.  On the device, behind --trim-*\n"
@@ -155,9 +157,9 @@ void usage()
         "--dedup: every read that is identical to a read before it in the file (same length, same bases case-insensitively, non-ACGT bases\n"
         "              at the same places; forward strand only) is dropped on the device, in front of --subsample-covg, discover and\n"
         "              genotyping; needs the sample resident in device memory (DRPRG_HIP_KEEP_READS_GB, default 32), fails if it is not.\n"
-        "%s"
+        "%s%s"
         "MI355X-native hot path; -p/-m/-M (external tools) are accepted and not needed: novel variants update the PRG in process.\n",
-        drprg::QcArgs::usage());
+        drprg::PairArgs::usage(), drprg::QcArgs::usage());
 }
 
 } // namespace
@@ -202,6 +204,7 @@ int main(int argc, char** argv)
     uint32_t trim_qual_milli = 0, trim_window = 0;
     uint32_t mask_qual = 0; // --mask-qual Q: base masking (include/drprg_hip.h "base masking"); 0 = not set
     drprg::AdapterArgs adapters; // --adapter SEQ, --adapter-error E, --adapter-min-overlap O (include/drprg_hip.h "adapter trimming")
+    drprg::PairArgs pair; // --mate FILE, --pair-min-overlap O, --pair-error E, --pair-clip-overlap (include/drprg_hip.h "mate overlap")
     drprg::QcArgs qc; // --qc-json FILE, --qc-no-qual (include/drprg_hip.h "read statistics")
     drprg::PolyArgs poly; // --poly-tail LETTERS, --poly-min-len M, --min-complexity P (include/drprg_hip.h "poly tails", "read complexity")
     drprg::DecoyArgs decoy; // --decoy FASTA, --decoy-k K, --decoy-min-frac F, --decoy-min-kmers M (include/drprg_hip.h "decoy screen")
@@ -252,6 +255,15 @@ int main(int argc, char** argv)
         else if (a == "--qc-json") qc.json = need(i);
         else if (a == "--qc-no-qual") qc.no_qual = true;
         else if (a == "--dedup") dedup = true;
+        else if (a == "--mate") pair.mate = need(i);
+        else if (a == "--pair-clip-overlap") pair.clip = true;
+        else if (a == "--pair-min-overlap") {
+            const std::string e = pair.set_overlap(need(i));
+            if (!e.empty()) die(e, 2);
+        } else if (a == "--pair-error") {
+            const std::string e = pair.set_error(need(i));
+            if (!e.empty()) die(e, 2);
+        }
         else if (a == "--subsample-covg") {
             char* end = nullptr;
             const char* v = need(i);
@@ -343,12 +355,14 @@ int main(int argc, char** argv)
     if (const std::string e = decoy.check(); !e.empty()) die(e, 2);
     if (const std::string e = poly.check(); !e.empty()) die(e, 2);
     if (const std::string e = qc.check(); !e.empty()) die(e, 2);
+    if (const std::string e = pair.check(); !e.empty()) die(e, 2);
     if (index.empty() || input.empty()) {
         usage();
         return 2;
     }
     if (illumina && !maf_given) ao.maf = 0.1f; // default_value_if("is_illumina", .., "0.1"), src/minor.rs:26-33
     if (!exists(input)) die(input + " does not exist");
+    if (pair.any() && !exists(pair.mate)) die(pair.mate + " does not exist");
     bool named_index = false;
     index = resolve_index(index, &named_index);
     // An index found by species name is a downloaded one: its dr.prg.k*.w*.idx and kmer_prgs/ are the real pandora's files.  If
@@ -409,13 +423,19 @@ int main(int argc, char** argv)
     if (const char* e = std::getenv("DRPRG_HIP_KEEP_READS_GB")) keep_gb = std::atof(e);
     if (keep_gb > 0)
         if (int rc = drprg_hip_keep_reads(ctx, (uint64_t)(keep_gb * 1e9))) die(drprg_hip_last_error(ctx), -rc);
-    if (subsample || dedup) drprg_hip_set_ordered_ingest(ctx, 1); // (both number the reads in file order)
+    if (subsample || dedup || pair.any()) drprg_hip_set_ordered_ingest(ctx, 1); // (all three number the reads in file order)
+    if (pair.any() && !(keep_gb > 0)) die("--mate needs the reads resident in device memory: DRPRG_HIP_KEEP_READS_GB=0 switches that off");
+    if (int rc = pair.set_on(ctx)) die(drprg_hip_last_error(ctx), -rc); // (this context alone: a second pass maps the resident reads, which are cut already)
     if (dedup && !(keep_gb > 0)) die("--dedup needs the reads resident in device memory: DRPRG_HIP_KEEP_READS_GB=0 switches that off");
     if (subsample && !(keep_gb > 0)) die("--subsample-covg needs the reads resident in device memory: DRPRG_HIP_KEEP_READS_GB=0 switches that off");
     if (verbose && std::getenv("DRPRG_HIP_T0")) std::fprintf(stderr, "[drprg-hip +%.3fs] main() entered\n", at_main);
     if (verbose) std::fprintf(stderr, "[drprg-hip +%.3fs] mapping %s against %s (k=%d w=%d) on device %d\n", since_start(), input.c_str(), index.c_str(), k, w, device);
     // discover + map share ONE pass over the reads (the reference runs two, /root/reference/src/predict.rs:248-302)
     if (int rc = drprg_hip_map_fastx(ctx, input.c_str())) die(drprg_hip_last_error(ctx), -rc);
+    if (pair.any()) { // the second mates, in the same pass: side 2 of the sample
+        if (int rc = drprg_hip_begin_mates(ctx)) die(std::string("--mate: ") + drprg_hip_last_error(ctx), -rc);
+        if (int rc = drprg_hip_map_fastx(ctx, pair.mate.c_str())) die(drprg_hip_last_error(ctx), -rc);
+    }
     if (verbose) std::fprintf(stderr, "[drprg-hip +%.3fs] reads mapped\n", since_start());
     if (verbose && (trim_front || trim_tail || trim_qual_milli)) {
         uint64_t ti[8] = {};
@@ -465,6 +485,11 @@ int main(int argc, char** argv)
                                  "reads_kept=%llu bases_kept=%llu (T=%llu)\n", since_start(), (unsigned long long)fi[0], (unsigned long long)fi[1],
                 (unsigned long long)fi[2], (unsigned long long)fi[3], (unsigned long long)fi[4], (unsigned long long)fi[5], (unsigned long long)fi[6],
                 (unsigned long long)fi[7]);
+    }
+    if (pair.any()) { // read-through adapters cut by mate overlap on the resident sample (include/drprg_hip.h "mate overlap"); never a silent unpaired run
+        uint64_t out[12] = {};
+        if (int rc = drprg_hip_pair_overlap(ctx, out)) die(std::string("--mate: ") + drprg_hip_last_error(ctx), -rc);
+        if (verbose) drprg::PairArgs::report(out, [](const char* line) { std::fprintf(stderr, "[drprg-hip +%.3fs] %s\n", since_start(), line); });
     }
     if (dedup) { // exact duplicates dropped from the resident sample (include/drprg_hip.h "duplicate reads"); never a silent full run
         uint64_t out[4] = { 0, 0, 0, 0 };
@@ -525,6 +550,7 @@ int main(int argc, char** argv)
                 // the reads again, against the updated index: from HBM if the first context kept them all, else from the file
                 const int from_hbm = drprg_hip_map_resident(next, ctx);
                 if (from_hbm != 0 && from_hbm != -61 /* ENODATA */) die(drprg_hip_last_error(next), -from_hbm);
+                if (from_hbm != 0 && pair.any()) die("--mate: the cut reads are no longer resident in device memory for the second pass", 61);
                 drprg_hip_close(ctx);
                 ctx = next;
                 if (from_hbm != 0 && decoy.any()) // (the file again: it is screened again)

@@ -422,6 +422,42 @@ hipError_t launch_dedup_keys(const DedupBatch& b, unsigned long long* key, uint3
 hipError_t launch_dedup_loc(const DedupBatch& b, uint64_t first, uint64_t n, DedupLoc* loc, uint32_t* err, hipStream_t stream);
 hipError_t launch_dedup_select(const DedupSelect& s, hipStream_t stream);
 
+// pair_overlap.hip: read-through adapters cut by mate overlap (the rule: include/drprg_hip.h "mate overlap").  The n reads of the sample
+// (n < 2^32) are numbered as dedup numbers them, side 1 in [0, n1) and side 2 behind it; loc as launch_dedup_loc fills it (zero for a read
+// that lies in no block; every block's words and bitmap must live until launch_pair_overlap is done).
+// launch_pair_numbers: the source numbers of one block's reads, out[j] = base + i for the j-th read i that stays (flag / rank: the verdict
+// and its exclusive scan, reads at or above `take` do not stay; flag null: every read stays and rank is not looked at).
+// launch_pair_mates: src1 / src2 the ascending source numbers of the reads of either side that lie in blocks (m1, m2 of them), res1 / res2
+// their resident numbers; mate (u32[n], filled with ~0u by the caller) receives, for both reads of every source number that both lists
+// hold, the resident number of the other.
+// launch_pair_overlap: shift[i] (i < n1; i32[n1]) = the chosen shift of read i's pair, PO_NO_SHIFT when none qualifies, PO_NOT_JUDGED when
+// the pair is not judged; keep[i] (u64[n]) = the bases read i keeps; counts (PO_WORDS zeroed device words) receive the pair's counts (the
+// caller sets PO_PAIRS and PO_READS).  *err (zeroed by the caller) is set by a mate number that is out of range or on the read's own side.
+constexpr uint32_t PO_MAX_LEN = 1024;
+constexpr int32_t PO_NO_SHIFT = INT32_MIN, PO_NOT_JUDGED = INT32_MIN + 1;
+enum {
+    PO_PAIRS = 0, PO_JUDGED = 1, PO_ORPHANS = 2, PO_TOO_LONG = 3, PO_OVERLAPPING = 4, PO_READ_THROUGH = 5, PO_BASES_CUT = 6, PO_BASES_CLIPPED = 7,
+    PO_READS_EMPTIED = 8, PO_READS = 9, PO_BASES_BEFORE = 10, PO_BASES_KEPT = 11, PO_WORDS = 12
+};
+struct PairOverlapArgs {
+    const DedupLoc* loc;
+    const uint32_t* mate;
+    uint64_t n, n1;
+    uint32_t min_overlap, error_milli, clip;
+    int32_t* shift;
+    uint64_t* keep;
+    unsigned long long* counts;
+    uint32_t* err;
+};
+hipError_t launch_pair_numbers(const uint8_t* flag, const uint32_t* rank, uint64_t n_reads, uint64_t take, uint32_t base, uint64_t out_cap, uint32_t* out, uint32_t* err,
+    hipStream_t stream);
+hipError_t launch_pair_mates(const uint32_t* src1, const uint32_t* res1, uint32_t m1, const uint32_t* src2, const uint32_t* res2, uint32_t m2, uint64_t n, uint32_t* mate,
+    uint32_t* err, hipStream_t stream);
+hipError_t launch_pair_overlap(const PairOverlapArgs& a, hipStream_t stream);
+// noff = the exclusive scan of keep over n_reads + 1 entries (entry n_reads of keep is read, not used): a block's new offsets.  temp:
+// read_trim_temp_bytes(n_reads) bytes.
+hipError_t launch_pair_offsets(const uint64_t* keep, uint64_t n_reads, uint64_t* noff, void* temp, size_t temp_bytes, hipStream_t stream);
+
 // read_qual.hip: the read filter (the rule: include/drprg_hip.h "read filter").  qsum[i] = sum of E[quality] over read i's n_bases-indexed
 // bytes of qual (qual: n_bases + 64 bytes readable; bias 33 or 0), then flag[i] = 1 for the reads the rule keeps, rank[i] = kept reads
 // before i and boff[i] = kept bases before i (n_reads + 1 entries each, entry n_reads the totals: what launch_subsample_tables and the
@@ -569,6 +605,10 @@ uint32_t read_trim_npos_chunks(uint64_t n_npos);
 // timer: around trim_points_kernel alone
 hipError_t launch_read_trim(const ReadTrimArgs& a, const ReadTrimNpos& np, hipStream_t stream, KernelTimer timer = {}, const AdapterEditSets* edit = nullptr);
 hipError_t launch_read_trim_fill(const ReadTrimFill& f, hipStream_t stream);
+// the count alone, for ranges the caller made itself (mate overlap): how many of np's positions lie inside the ranges of f (offsets, begin,
+// end, noff, n_reads, n_bases; nothing else of f is looked at), left in np.chunk_prefix[read_trim_npos_chunks(n_npos)] with the scan
+// launch_read_trim_npos_emit reads.  n_npos >= 1.
+hipError_t launch_read_trim_npos_count(const ReadTrimFill& f, const ReadTrimNpos& np, hipStream_t stream);
 hipError_t launch_read_trim_npos_emit(const ReadTrimFill& f, const ReadTrimNpos& np, uint64_t* out, uint64_t out_cap, hipStream_t stream);
 
 // decoy_screen.hip: the decoy screen (the rule: include/drprg_hip.h "decoy screen").

@@ -319,6 +319,35 @@ public:
     // of no bases.  Synchronises `stream`.
     void dedup_keys_device(const uint32_t* d_words, const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases, const uint64_t* d_npos, uint64_t n_npos,
         unsigned long long* d_keys, hipStream_t stream);
+    // Mate overlap (the rule: include/drprg_hip.h "mate overlap"; pair_overlap.hip).  min_overlap 8 .. PO_MAX_LEN, error_milli 0 .. 250.
+    struct PairSetting {
+        uint32_t min_overlap = 0, error_milli = 0;
+        bool clip = false;
+        bool on() const { return min_overlap != 0; }
+    };
+    // one side of the caller's pairs: a packed batch of n_pairs reads
+    struct PairSide {
+        const uint32_t* d_words;
+        const uint64_t* d_offsets;
+        uint64_t n_bases;
+        const uint64_t* d_npos;
+        uint64_t n_npos;
+    };
+    // The stage on the resident sample.  pair_record(true): from now on every block the resident set takes gets the source numbers of its
+    // reads (their numbers among the reads of their side as the files held them, counted before any stage dropped one); begin_mates(): the
+    // reads mapped from here on are side 2.  pair_overlap_kept: needs kept_complete(), one begin_mates() call and sides of the same size;
+    // mates are found by source number and judged by the rule; no read lost a base: nothing else happens (no compaction, coverage and
+    // counters untouched).  Otherwise every block is compacted by the ranges [0, keep) into a new set and the cut reads are mapped afresh, as
+    // dedup_kept does with its flags.  shifts: per source pair the chosen shift (PO_NO_SHIFT, PO_NOT_JUDGED).  The source numbers are
+    // dropped either way.  A call that fails leaves the sample as it was.
+    void pair_record(bool on) { pair_.record = on; }
+    void begin_mates();
+    void pair_overlap_kept(const PairSetting& set, std::vector<int32_t>& shifts, uint64_t counts[dev::PO_WORDS]);
+    // The two pair kernels alone on the caller's packed batches (drprg_hip_pair_overlap_device): pair s is (read s of a, read s of b).
+    // d_shift[s] the chosen shift (PO_NO_SHIFT, PO_NOT_JUDGED), d_keep_a[s] / d_keep_b[s] the bases either mate keeps, counts the PO_WORDS
+    // counters.  Synchronises `stream`.
+    void pair_overlap_device(const PairSetting& set, const PairSide& a, const PairSide& b, uint64_t n_pairs, int32_t* d_shift, uint64_t* d_keep_a, uint64_t* d_keep_b,
+        uint64_t counts[dev::PO_WORDS], hipStream_t stream);
 
     // this += other, on the device (the other Mapper's vectors are left as they are): peer copy into a scratch buffer + one
     // add kernel, or the add kernel alone when both live on the same device.  Both are synchronised first.
@@ -718,6 +747,7 @@ private:
         // (npos null without any) -- or nothing, when the cap or the device says no
         std::optional<BlockRoom> take_block(uint64_t payload_bytes, uint64_t n_reads, uint64_t n_npos);
         void add(const DeviceBatch& b, uint64_t n_reads) { kept.push_back(b); first.push_back(seen); seen += n_reads; }
+        uint32_t* take_numbers(uint64_t n_reads) { return static_cast<uint32_t*>(arena_take(n_reads * sizeof(uint32_t))); } // (mate overlap: a block's source numbers)
         void count_empty(uint64_t n) { seen += n; }
         // everything but the cap goes; the caller has made sure that nothing on the device reads the blocks any more
         void clear() { *this = ResidentSet { {}, nullptr, 0, cap }; }
@@ -735,6 +765,25 @@ private:
     SubsampleResult resident_sample(const char* what, std::vector<uint8_t>& flags);
     void keep_flagged(const uint8_t* d_flag, const uint32_t* d_rank, const uint64_t* d_boff, uint32_t* d_err, const char* what, SubsampleResult& res,
         std::vector<uint8_t>& flags);
+    // the second half's own tail, which pair_overlap_kept shares: the compaction's error word read back (a set one: the new set is given
+    // up), then the new set in the old one's place, coverage and counters cleared, its blocks mapped
+    void compaction_clean(uint32_t* d_err, const std::string& what);
+    void adopt_kept(ResidentSet& fresh, uint64_t reads_kept);
+    // mate overlap: what the blocks of the resident set were numbered with (src[b]: kept[b]'s source numbers, in the set's arenas)
+    struct PairState {
+        bool record = false;
+        std::vector<const uint32_t*> src;
+        uint64_t seen[2] = { 0, 0 }; // the reads either side's files held
+        int side = 0, begun = 0;     // begin_mates calls
+        size_t block2 = 0;           // side 2's first block
+        uint64_t n1 = 0;             // and first resident number
+        bool spent = false;          // the sample was compacted, or the stage has run: the numbers no longer stand for it
+    };
+    PairState pair_;
+    // the source numbers of a block the resident set has just taken (flag / rank / take: launch_pair_numbers); base: the side's reads in front
+    // of the block.  false: the set had no room for them.  The callers fail the block then (-ENOMEM, naming DRPRG_HIP_KEEP_READS_GB) rather
+    // than stop keeping: the block's own room is taken from the arenas already, and a paired run needs the resident sample anyway
+    bool pair_number_block(uint64_t n_reads, const uint8_t* d_flag, const uint32_t* d_rank, uint64_t src_reads, uint64_t take, uint64_t base, hipStream_t stream);
     struct DedupBlock;
     void dedup_block(const DeviceBatch& kb, DedupBlock& out, unsigned long long* d_count);
     void stop_keeping(); // the resident set given up (over its limit, or the device is full): what map_host_async and map_host_filtered do alike

@@ -30,6 +30,7 @@
 #include "adapter_args.h"
 #include "decoy_args.h"
 #include "mask_args.h"
+#include "pair_args.h"
 #include "qc_args.h"
 #include "poly_args.h"
 
@@ -60,6 +61,7 @@ struct Args {
     uint64_t seed = 1;
     // --dedup: exact duplicate reads dropped from the resident sample (include/drprg_hip.h "duplicate reads")
     bool dedup = false;
+    drprg::PairArgs pair; // --mate FILE, --pair-min-overlap O, --pair-error E, --pair-clip-overlap (include/drprg_hip.h "mate overlap")
     // --min-read-len L, --max-read-len L, --min-read-qual Q: the read filter (include/drprg_hip.h "read filter"); 0 = not set
     uint64_t min_read_len = 0, max_read_len = 0;
     uint32_t min_read_qual_milli = 0;
@@ -89,6 +91,7 @@ void usage()
         "  pandora index    [-t N] [-w W] [-k K] <prg>\n"
         "  pandora map      [--genotype] [--local] [--gt-conf X] [-v] [-o DIR] [-g SIZE] [--max-covg N | --subsample-covg D [--seed S]]\n"
         "                   [--dedup] [--min-read-len L] [--max-read-len L] [--min-read-qual Q]\n"
+        "                   [--mate FILE [--pair-min-overlap O] [--pair-error E] [--pair-clip-overlap]]\n"
         "                   [--trim-front N] [--trim-tail N] [--trim-qual Q [--trim-window W]]\n"
         "                   [--adapter SEQ]... [--adapter-error E] [--adapter-min-overlap O] [--adapter-indels] [--front-adapter SEQ]...\n"
         "                   [--poly-tail LETTERS [--poly-min-len M]] [--min-complexity P] [--qc-json FILE [--qc-no-qual]]\n"
@@ -137,6 +140,7 @@ void usage()
         "                base stop existing.  Needs qualities: FASTA, or a BAM record without them, is an error under it.  A threshold on what the\n"
         "                basecaller claims: at Nanopore qualities a Q of 10 or more leaves few 15-mers.  Default: off.\n"
         "  %s"
+        "  %s"
         "  --decoy FASTA (up to 8 times; plain or .gz), --decoy-k K (9 to 31, default 31), --decoy-min-frac F (in (0, 1], default 0.5),\n"
         "                --decoy-min-kmers M (default 1): a read is dropped as a contaminant when at least M of its k-mers, and at least the\n"
         "                fraction F of its k-mers without a letter other than ACGT, are k-mers of the decoy files in either orientation -- on\n"
@@ -145,7 +149,7 @@ void usage()
         "  <reads>: FASTA or FASTQ, plain or gzip; or BAM (secondary and supplementary records are skipped, reverse-strand records are\n"
         "           reverse-complemented, alignments are ignored, qualities are looked at by --min-read-qual, --trim-qual and --mask-qual alone)\n"
         "environment: DRPRG_HIP_DEVICE selects the GPU (default 0); DRPRG_HIP_DEVICES=0,1,.. maps on several GPUs of the node\n",
-        drprg::QcArgs::usage());
+        drprg::QcArgs::usage(), drprg::PairArgs::usage());
 }
 
 Args parse(int argc, char** argv)
@@ -256,6 +260,15 @@ Args parse(int argc, char** argv)
         else if (s == "--qc-json") a.qc.json = need(i);
         else if (s == "--qc-no-qual") a.qc.no_qual = true;
         else if (s == "--dedup") a.dedup = true;
+        else if (s == "--mate") a.pair.mate = need(i);
+        else if (s == "--pair-clip-overlap") a.pair.clip = true;
+        else if (s == "--pair-min-overlap") {
+            const std::string e = a.pair.set_overlap(need(i));
+            if (!e.empty()) die(e, 2);
+        } else if (s == "--pair-error") {
+            const std::string e = a.pair.set_error(need(i));
+            if (!e.empty()) die(e, 2);
+        }
         else if (s == "-o" || s == "--outdir") a.outdir = need(i);
         else if (s == "--vcf-refs") a.vcf_refs = need(i);
         else if (s == "--gt-conf") a.gt_conf = std::atof(need(i));
@@ -278,6 +291,8 @@ Args parse(int argc, char** argv)
     if (a.subsample && a.max_covg_given && a.max_covg != 4294967295ull)
         die("--max-covg and --subsample-covg are alternatives (the prefix cap or the random subsample): give one of them", 2);
     if (a.subsample) a.max_covg = 4294967295ull; // the default cap gives way
+    if (const std::string e = a.pair.check(a.max_covg_given ? a.max_covg : ~0ull); !e.empty()) die(e, 2);
+    if (a.pair.any()) a.max_covg = 4294967295ull; // (to --mate as well)
     if (a.max_read_len && a.max_read_len < a.min_read_len) die("--max-read-len is below --min-read-len: no read can pass", 2);
     if (a.trim_window && !a.trim_qual_milli) die("--trim-window belongs to --trim-qual", 2);
     if (const std::string e = a.adapters.check(); !e.empty()) die(e, 2);
@@ -380,6 +395,9 @@ std::string run_tag(const Args& a, const std::string& reads)
         + std::to_string(a.max_diff) + "|g" + std::to_string((unsigned long long)a.genome_size) + "|M" + std::to_string((unsigned long long)a.max_covg)
         + (a.subsample ? "|S" + std::to_string(a.subsample_covg) + "/" + std::to_string((unsigned long long)a.seed) : std::string())
         + (a.dedup ? std::string("|D") : std::string())
+        + (a.pair.any() ? "|" + stamp(a.pair.mate) + "|M" + std::to_string(a.pair.min_overlap) + "/" + std::to_string(a.pair.error_milli) + "/"
+                  + std::to_string((int)a.pair.clip)
+                        : std::string())
         + (a.min_read_len || a.max_read_len || a.min_read_qual_milli ? "|F" + std::to_string((unsigned long long)a.min_read_len) + "/"
                   + std::to_string((unsigned long long)a.max_read_len) + "/" + std::to_string(a.min_read_qual_milli)
                                                                      : std::string())
@@ -397,13 +415,29 @@ void keep_reads(drprg_hip_ctx* ctx, const Args& a)
 {
     double keep_gb = 32;
     if (const char* e = std::getenv("DRPRG_HIP_KEEP_READS_GB")) keep_gb = std::atof(e);
-    if (a.subsample || a.dedup) drprg_hip_set_ordered_ingest(ctx, 1); // (both number the reads in file order)
+    if (a.subsample || a.dedup || a.pair.any()) drprg_hip_set_ordered_ingest(ctx, 1); // (all three number the reads in file order)
     if (keep_gb > 0) {
         if (int rc = drprg_hip_keep_reads(ctx, (uint64_t)(keep_gb * 1e9))) die(drprg_hip_last_error(ctx), -rc);
-    } else if (a.subsample)
+    } else if (a.pair.any())
+        die("--mate needs the reads resident in device memory: DRPRG_HIP_KEEP_READS_GB=0 switches that off");
+    else if (a.subsample)
         die("--subsample-covg needs the reads resident in device memory: DRPRG_HIP_KEEP_READS_GB=0 switches that off");
     else if (a.dedup)
         die("--dedup needs the reads resident in device memory: DRPRG_HIP_KEEP_READS_GB=0 switches that off");
+}
+
+// The mapping pass: the reads, and with --mate the second mates behind them and the overlap stage on the resident pairs, in front of
+// --dedup.  Fails loudly rather than run unpaired.
+void map_reads(drprg_hip_ctx* ctx, const Args& a, const std::string& reads)
+{
+    if (int rc = a.pair.set_on(ctx)) die(drprg_hip_last_error(ctx), -rc);
+    if (int rc = drprg_hip_map_fastx(ctx, reads.c_str())) die(drprg_hip_last_error(ctx), -rc);
+    if (!a.pair.any()) return;
+    if (int rc = drprg_hip_begin_mates(ctx)) die(std::string("--mate: ") + drprg_hip_last_error(ctx), -rc);
+    if (int rc = drprg_hip_map_fastx(ctx, a.pair.mate.c_str())) die(drprg_hip_last_error(ctx), -rc);
+    uint64_t out[12] = {};
+    if (int rc = drprg_hip_pair_overlap(ctx, out)) die(std::string("--mate: ") + drprg_hip_last_error(ctx), -rc);
+    if (a.verbose) drprg::PairArgs::report(out, [](const char* line) { std::printf("[pandora-hip] %s\n", line); });
 }
 
 // --dedup: behind the mapping pass, in front of --subsample-covg.  Fails loudly when the sample is not resident.
@@ -505,8 +539,8 @@ int cmd_map(const Args& a)
         std::printf("[pandora-hip] coverage of this PRG and these reads taken from %s (reads=%llu bases=%llu hits=%llu): no second mapping pass\n",
             cache.c_str(), (unsigned long long)cached[0], (unsigned long long)cached[1], (unsigned long long)cached[3]);
     } else {
-        if (a.subsample || a.dedup) keep_reads(ctx, a);
-        if (int rc = drprg_hip_map_fastx(ctx, a.positional[1].c_str())) die(drprg_hip_last_error(ctx), -rc);
+        if (a.subsample || a.dedup || a.pair.any()) keep_reads(ctx, a);
+        map_reads(ctx, a, a.positional[1]);
         dedup(ctx, a);
         subsample(ctx, a);
         report_counters(ctx, now_s() - t0);
@@ -540,7 +574,7 @@ int cmd_discover(const Args& a)
     // first one left in HBM (up to DRPRG_HIP_KEEP_READS_GB per device, default 32, 0 = read the file again)
     keep_reads(ctx, a);
     double t0 = now_s();
-    if (int rc = drprg_hip_map_fastx(ctx, reads.c_str())) die(drprg_hip_last_error(ctx), -rc);
+    map_reads(ctx, a, reads);
     dedup(ctx, a);
     subsample(ctx, a);
     report_counters(ctx, now_s() - t0);

@@ -172,6 +172,7 @@ void Mapper::map_host_async(const HostBatch& hb)
         count_unmapped(n_reads, keeping);
         for (int w = 0; w < 2; ++w)
             if (hb.stats_which >> w & 1) stats_.empty_reads[w] += n_reads;
+        if (pair_.record) pair_.seen[pair_.side] += n_reads; // (mate overlap: numbered, though they lie in no block)
         return;
     }
     // under keep_reads the block goes into device memory of its own and stays there; else into a staging set
@@ -190,6 +191,11 @@ void Mapper::map_host_async(const HostBatch& hb)
     HIPCHK(hipStreamWaitEvent(stream_, copied, 0));
     if (hb.stats_which) count_unfiltered(hb, b, d_stats_qual, hb.bam && hb.reverse ? st->d_reverse.data() : nullptr, stream_); // (no wait: queued in front of the map)
     if (own) {
+        if (pair_.record) { // mate overlap: a whole block is numbered on from its side's running count
+            if (!pair_number_block(n_reads, nullptr, nullptr, n_reads, ~0ull, pair_.seen[pair_.side], stream_))
+                throw Error(DRPRG_ENOMEM, "mate overlap: no room in the resident set for a block's source numbers (DRPRG_HIP_KEEP_READS_GB raises the limit)");
+            pair_.seen[pair_.side] += n_reads;
+        }
         resident_.add(b, n_reads);
         map_resident_block(b);
     } else map(b, nullptr, nullptr, stream_, true);
@@ -888,6 +894,8 @@ void Mapper::map_host_filtered(const HostBatch& hb, const ReadFilter& f, uint64_
     o.reads_seen = n_reads;
     o.bases_seen = n_bases;
     bool keeping = resident_.active();
+    const uint64_t pair_base = pair_.seen[pair_.side]; // mate overlap: source numbers count the reads the file held, whatever the stages drop
+    if (pair_.record) pair_.seen[pair_.side] += n_reads;
     if (n_bases == 0) { // (the counters still see them)
         only_empty_reads(n_reads, f, keeping, o);
         if (f.read_stats) {
@@ -953,6 +961,11 @@ void Mapper::map_host_filtered(const HostBatch& hb, const ReadFilter& f, uint64_
     // 6. place, 7. map
     const DeviceBatch cur = place_block(fs, src, k, keeping);
     if (keeping) {
+        if (pair_.record) { // the kept reads' numbers: the filter's flags and their scan below the cap's cut, or all of a whole block
+            const bool whole = k.n_reads == n_reads;
+            if (!pair_number_block(k.n_reads, whole ? nullptr : fs.d_flag.data(), fs.d_rank.data(), n_reads, k.take, pair_base, copy_stream_))
+                throw Error(DRPRG_ENOMEM, "mate overlap: no room in the resident set for a block's source numbers (DRPRG_HIP_KEEP_READS_GB raises the limit)");
+        }
         resident_.add(cur, k.n_reads);
         map_resident_block(cur);
     } else map(cur, nullptr, nullptr, stream_, true);

@@ -319,17 +319,23 @@ hipError_t launch_read_trim(const ReadTrimArgs& a, const ReadTrimNpos& np, hipSt
     HIP_TRY(rocprim::exclusive_scan(a.temp, temp_bytes, a.klen, a.noff, (uint64_t)0, (size_t)a.n_reads + 1, rocprim::plus<uint64_t>(), stream));
     const uint32_t* kept_npos = nullptr;
     if (np.n_npos) { // how many listed positions stay: counted before the host looks, so that the block costs one read-back
-        const uint32_t n_chunks = read_trim_npos_chunks(np.n_npos);
         const ReadTrimFill f { a.offsets, a.rev, a.begin, a.end, a.noff, a.n_reads, a.n_bases, ~0ull, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
-        hipLaunchKernelGGL(trim_npos_kernel<false>, dim3(n_chunks), dim3(RT_THREADS), 0, stream, f, np.npos, np.n_npos, np.chunk_count, (const uint32_t*)nullptr,
-            (uint64_t*)nullptr, 0ull);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemsetAsync(np.chunk_count + n_chunks, 0, sizeof(uint32_t), stream));
-        HIP_TRY(exclusive_scan_u32(np.temp, np.temp_bytes, np.chunk_count, np.chunk_prefix, n_chunks + 1, stream));
-        kept_npos = np.chunk_prefix + n_chunks;
+        HIP_TRY(launch_read_trim_npos_count(f, np, stream));
+        kept_npos = np.chunk_prefix + read_trim_npos_chunks(np.n_npos);
     }
     hipLaunchKernelGGL(read_trim_result_kernel, dim3(1), dim3(64), 0, stream, a, kept_npos);
     return hipGetLastError();
+}
+
+hipError_t launch_read_trim_npos_count(const ReadTrimFill& f, const ReadTrimNpos& np, hipStream_t stream)
+{
+    const uint32_t n_chunks = read_trim_npos_chunks(np.n_npos);
+    if (!n_chunks || !f.n_reads) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(trim_npos_kernel<false>, dim3(n_chunks), dim3(RT_THREADS), 0, stream, f, np.npos, np.n_npos, np.chunk_count, (const uint32_t*)nullptr,
+        (uint64_t*)nullptr, 0ull);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemsetAsync(np.chunk_count + n_chunks, 0, sizeof(uint32_t), stream));
+    return exclusive_scan_u32(np.temp, np.temp_bytes, np.chunk_count, np.chunk_prefix, n_chunks + 1, stream);
 }
 
 hipError_t launch_read_trim_fill(const ReadTrimFill& f, hipStream_t stream)

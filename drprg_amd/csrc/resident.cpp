@@ -57,6 +57,9 @@ void Mapper::drop_kept()
         HIPCHK(hipStreamSynchronize(stream_));
     }
     resident_.clear();
+    const bool record = pair_.record;
+    pair_ = PairState {};
+    pair_.record = record;
 }
 
 // The map call on a block of the resident set.  in_keep_call_ is set for as long as it runs and on no other path: map() takes every other
@@ -193,16 +196,28 @@ void Mapper::keep_flagged(const uint8_t* d_flag, const uint32_t* d_rank, const u
             fresh.add(kb, nr);
         }
         fresh.count_empty(res.reads_kept - fresh.seen);
-        uint32_t err = 0;
-        HIPCHK(hipMemcpyAsync(&err, d_err, sizeof err, hipMemcpyDeviceToHost, stream_));
-        HIPCHK(hipStreamSynchronize(stream_)); // (nothing reads the old blocks any more)
-        if (err) throw Error(DRPRG_EIO, std::string(what) + ": the resident blocks' offsets and the selection do not fit each other");
+        compaction_clean(d_err, std::string(what) + ": the resident blocks' offsets and the selection do not fit each other");
     } catch (...) {
         (void)hipStreamSynchronize(stream_); // (nothing writes the new arenas any more when their owners release them)
         flags.clear();
         throw;
     }
+    adopt_kept(fresh, res.reads_kept);
+}
+
+void Mapper::compaction_clean(uint32_t* d_err, const std::string& what)
+{
+    uint32_t err = 0;
+    HIPCHK(hipMemcpyAsync(&err, d_err, sizeof err, hipMemcpyDeviceToHost, stream_));
+    HIPCHK(hipStreamSynchronize(stream_)); // (nothing reads the old blocks any more)
+    if (err) throw Error(DRPRG_EIO, what);
+}
+
+void Mapper::adopt_kept(ResidentSet& fresh, uint64_t reads_kept)
+{
     std::swap(resident_, fresh);
+    pair_.src.clear(); // (mate overlap: the numbers lay in the old arenas and stood for the old blocks)
+    pair_.spent = true;
     // ---- the kept reads mapped afresh ----
     HIPCHK(hipMemsetAsync(d_covg_.data(), 0, d_covg_.bytes(), stream_)); // [coverage | reads per PRG]
     HIPCHK(hipMemsetAsync(d_counters_.data(), 0, d_counters_.bytes(), stream_));
@@ -215,7 +230,7 @@ void Mapper::keep_flagged(const uint8_t* d_flag, const uint32_t* d_rank, const u
     }
     sync();
     HIPCHK(hipStreamSynchronize(stream_));
-    tot_reads_ += res.reads_kept - in_blocks; // (kept empty reads of blocks that hold no base any more)
+    tot_reads_ += reads_kept - in_blocks; // (kept empty reads of blocks that hold no base any more)
 }
 
 void Mapper::compact_room(CompactScratch& cs, bool packed, uint64_t n_kept, uint64_t n_npos)
@@ -367,6 +382,232 @@ void Mapper::dedup_keys_device(const uint32_t* d_words, const uint64_t* d_offset
     HIPCHK(hipMemcpyAsync(&err, d_err.data(), sizeof err, hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
     if (err) throw Error(DRPRG_EINVAL, "duplicate keys: the offsets do not ascend from 0 to n_bases");
+}
+
+// ---- mate overlap on the resident sample (the rule: include/drprg_hip.h "mate overlap") ------------------------------------------------
+bool Mapper::pair_number_block(uint64_t n_reads, const uint8_t* d_flag, const uint32_t* d_rank, uint64_t src_reads, uint64_t take, uint64_t base, hipStream_t stream)
+{
+    uint32_t* const numbers = resident_.take_numbers(n_reads);
+    if (!numbers) return false;
+    // (a side of 2^32 reads or more is refused by the stage: the numbers of such a sample are never looked at)
+    HIPCHK(dev::launch_pair_numbers(d_flag, d_rank, src_reads, take, (uint32_t)base, n_reads, numbers, nullptr, stream));
+    pair_.src.push_back(numbers);
+    return true;
+}
+
+void Mapper::begin_mates()
+{
+    if (!pair_.record) throw Error(DRPRG_EINVAL, "drprg_hip_begin_mates: no mate-overlap setting (drprg_hip_set_pair_overlap)");
+    if (pair_.begun) throw Error(DRPRG_EINVAL, "drprg_hip_begin_mates: called twice for one sample (side 2 has begun already)");
+    sync();
+    pair_.begun = 1;
+    pair_.side = 1;
+    pair_.block2 = resident_.kept.size();
+    pair_.n1 = resident_.seen;
+}
+
+void Mapper::pair_overlap_kept(const PairSetting& set, std::vector<int32_t>& shifts, uint64_t counts[dev::PO_WORDS])
+{
+    std::vector<uint8_t> unused;
+    const SubsampleResult before = resident_sample("mate overlap", unused);
+    if (copy_stream_) HIPCHK(hipStreamSynchronize(copy_stream_)); // (the numbers of filtered blocks were written there)
+    const uint64_t n = before.reads_before, n1 = pair_.n1;
+    const std::vector<DeviceBatch>& old = resident_.kept;
+    if (!set.on()) throw Error(DRPRG_EINVAL, "mate overlap: no setting (drprg_hip_set_pair_overlap)");
+    if (!pair_.begun) throw Error(DRPRG_EINVAL, "mate overlap: drprg_hip_begin_mates was not called: the sample has no second side");
+    if (pair_.spent || pair_.src.size() != old.size())
+        throw Error(DRPRG_EINVAL, "mate overlap: the resident reads are not numbered by side (they were compacted by an earlier stage, or mapped before "
+                                  "drprg_hip_set_pair_overlap)");
+    if (pair_.seen[0] != pair_.seen[1])
+        throw Error(DRPRG_EFORMAT, "mate overlap: the two sides hold different numbers of reads (" + std::to_string(pair_.seen[0]) + " and " +
+                                       std::to_string(pair_.seen[1]) + "): the files are not mates of each other");
+    if (n >= (1ull << 32) || pair_.seen[0] >= (1ull << 32)) throw Error(DRPRG_EOVERFLOW, "mate overlap: 2^32 reads or more in one sample");
+    const uint64_t pairs = pair_.seen[0];
+    shifts.assign(pairs, dev::PO_NOT_JUDGED);
+    for (int i = 0; i < dev::PO_WORDS; ++i) counts[i] = 0;
+    counts[dev::PO_PAIRS] = pairs;
+    counts[dev::PO_READS] = n;
+    counts[dev::PO_BASES_BEFORE] = counts[dev::PO_BASES_KEPT] = before.bases_before;
+    if (n == 0) return;
+    // ---- mates and kept lengths (device scratch of this call) ----
+    uint64_t m[2] = { 0, 0 }, max_reads = 0, max_npos = 0;
+    for (size_t b = 0; b < old.size(); ++b) {
+        if (resident_.first[b] + old[b].n_reads > n || (b < pair_.block2) != (resident_.first[b] < n1))
+            throw Error(DRPRG_EIO, "mate overlap: the resident blocks and the sides do not fit each other");
+        m[b >= pair_.block2] += old[b].n_reads;
+        max_reads = std::max(max_reads, old[b].n_reads);
+        if (old[b].packed) max_npos = std::max(max_npos, old[b].n_npos);
+    }
+    DeviceBuffer<uint32_t> d_src, d_res, d_mate, d_err;
+    DeviceBuffer<int32_t> d_shift;
+    DeviceBuffer<uint64_t> d_keep;
+    DeviceBuffer<dev::DedupLoc> d_loc;
+    DeviceBuffer<unsigned long long> d_counts, d_count;
+    d_src.alloc(m[0] + m[1] + 1); d_res.alloc(m[0] + m[1] + 1); d_mate.alloc(n); d_err.alloc(4); d_shift.alloc(n1 + 1); d_keep.alloc(n + 1); d_loc.alloc(n);
+    d_counts.alloc(dev::PO_WORDS); d_count.alloc(1);
+    HIPCHK(hipMemsetAsync(d_loc.data(), 0, d_loc.bytes(), stream_));
+    HIPCHK(hipMemsetAsync(d_mate.data(), 0xFF, d_mate.bytes(), stream_));
+    HIPCHK(hipMemsetAsync(d_err.data(), 0, d_err.bytes(), stream_));
+    HIPCHK(hipMemsetAsync(d_keep.data(), 0, d_keep.bytes(), stream_));
+    HIPCHK(hipMemsetAsync(d_counts.data(), 0, d_counts.bytes(), stream_));
+    std::vector<DedupBlock> blocks(old.size()); // (the overlap kernel reads every block: the scratch of all of them lives until it is done)
+    uint64_t at = 0;
+    for (size_t b = 0; b < old.size(); ++b) {
+        const uint64_t nr = old[b].n_reads;
+        if (!nr) continue;
+        HIPCHK(hipMemcpyAsync(d_src.data() + at, pair_.src[b], nr * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream_));
+        HIPCHK(dev::launch_pair_numbers(nullptr, nullptr, nr, ~0ull, (uint32_t)resident_.first[b], nr, d_res.data() + at, nullptr, stream_));
+        at += nr;
+        if (!old[b].n_bases) continue;
+        dedup_block(old[b], blocks[b], d_count.data());
+        HIPCHK(dev::launch_dedup_loc(blocks[b].batch, resident_.first[b], n, d_loc.data(), d_err.data(), stream_));
+    }
+    HIPCHK(dev::launch_pair_mates(d_src.data(), d_res.data(), (uint32_t)m[0], d_src.data() + m[0], d_res.data() + m[0], (uint32_t)m[1], n, d_mate.data(), d_err.data(),
+        stream_));
+    dev::PairOverlapArgs args {};
+    args.loc = d_loc.data(); args.mate = d_mate.data(); args.n = n; args.n1 = n1;
+    args.min_overlap = set.min_overlap; args.error_milli = set.error_milli; args.clip = set.clip ? 1 : 0;
+    args.shift = d_shift.data(); args.keep = d_keep.data(); args.counts = d_counts.data(); args.err = d_err.data();
+    HIPCHK(dev::launch_pair_overlap(args, stream_));
+    uint32_t err = 0;
+    unsigned long long got[dev::PO_WORDS];
+    std::vector<int32_t> shift(n1);
+    std::vector<uint32_t> src1(m[0]);
+    std::vector<uint64_t> keep(n);
+    HIPCHK(hipMemcpyAsync(&err, d_err.data(), sizeof err, hipMemcpyDeviceToHost, stream_));
+    HIPCHK(hipMemcpyAsync(got, d_counts.data(), sizeof got, hipMemcpyDeviceToHost, stream_));
+    if (n1) HIPCHK(hipMemcpyAsync(shift.data(), d_shift.data(), n1 * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
+    if (m[0]) HIPCHK(hipMemcpyAsync(src1.data(), d_src.data(), m[0] * sizeof(uint32_t), hipMemcpyDeviceToHost, stream_));
+    HIPCHK(hipMemcpyAsync(keep.data(), d_keep.data(), n * sizeof(uint64_t), hipMemcpyDeviceToHost, stream_));
+    HIPCHK(hipStreamSynchronize(stream_));
+    if (err) throw Error(DRPRG_EIO, "mate overlap: a resident block's offsets do not fit its bases, or its source numbers do not fit the sample");
+    at = 0;
+    for (size_t b = 0; b < pair_.block2 && b < old.size(); ++b)
+        for (uint64_t j = 0; j < old[b].n_reads; ++j, ++at) {
+            if (src1[at] >= pairs) throw Error(DRPRG_EIO, "mate overlap: a source number beyond the side's reads");
+            shifts[src1[at]] = shift[resident_.first[b] + j];
+        }
+    for (int i = 0; i < dev::PO_WORDS; ++i)
+        if (i != dev::PO_PAIRS && i != dev::PO_READS) counts[i] = got[i];
+    if (counts[dev::PO_BASES_KEPT] == counts[dev::PO_BASES_BEFORE]) { // no read lost a base: nothing else happens
+        pair_.src.clear(); // (the numbers are dropped after the stage)
+        pair_.spent = true;
+        return;
+    }
+    // ---- compaction by the ranges [0, keep): a new set under the same cap, as keep_flagged makes one by flags ----
+    DeviceBuffer<uint64_t> d_zero, d_noff, d_start;
+    DeviceBuffer<dev::GatherEntry> d_table;
+    DeviceBuffer<uint32_t> d_ccount, d_cprefix;
+    DeviceBuffer<unsigned char> d_temp, d_ntemp;
+    d_zero.alloc(max_reads + 1); d_noff.alloc(max_reads + 1); d_start.alloc(max_reads + 1); d_table.alloc(max_reads + 1);
+    d_temp.alloc(dev::read_trim_temp_bytes(max_reads));
+    if (max_npos) {
+        const uint64_t chunks = (uint64_t)dev::read_trim_npos_chunks(max_npos) + 1;
+        d_ccount.alloc(chunks); d_cprefix.alloc(chunks); d_ntemp.alloc(dev::scan_temp_bytes((uint32_t)chunks));
+    }
+    HIPCHK(hipMemsetAsync(d_zero.data(), 0, d_zero.bytes(), stream_));
+    uint32_t* const d_cerr = d_err.data() + 1;
+    ResidentSet fresh;
+    fresh.cap = resident_.cap;
+    try {
+        for (size_t b = 0; b < old.size(); ++b) {
+            const DeviceBatch& ob = old[b];
+            const uint64_t nr = ob.n_reads, first = resident_.first[b];
+            uint64_t nb = 0;
+            for (uint64_t j = 0; j < nr; ++j) nb += keep[first + j];
+            if (nb == 0) continue; // (reads of no bases only: numbered below, as map_host_async counts them)
+            const uint64_t payload = ob.packed ? (nb + 15) / 16 * 4 : nb;
+            const uint64_t n_npos = ob.packed ? ob.n_npos : 0;
+            const uint64_t* const d_end = d_keep.data() + first;
+            HIPCHK(dev::launch_pair_offsets(d_end, nr, d_noff.data(), d_temp.data(), d_temp.size(), stream_));
+            dev::ReadTrimFill tf { ob.d_offsets, nullptr, d_zero.data(), d_end, d_noff.data(), nr, ob.n_bases, nb, ob.d_bases, nullptr,
+                ob.packed ? d_start.data() : nullptr, ob.packed ? nullptr : d_table.data(), nullptr, d_cerr };
+            dev::ReadTrimNpos np {};
+            uint32_t n_list = 0;
+            if (n_npos) {
+                np = dev::ReadTrimNpos { ob.d_npos, n_npos, d_ccount.data(), d_cprefix.data(), d_ntemp.data(), d_ntemp.size() };
+                HIPCHK(dev::launch_read_trim_npos_count(tf, np, stream_));
+                HIPCHK(hipMemcpyAsync(&n_list, d_cprefix.data() + dev::read_trim_npos_chunks(n_npos), sizeof n_list, hipMemcpyDeviceToHost, stream_));
+                HIPCHK(hipStreamSynchronize(stream_));
+            }
+            const std::optional<BlockRoom> room = fresh.take_block(payload, nr, n_list);
+            if (!room) throw Error(DRPRG_ENOMEM, "mate overlap: no device memory for the cut reads beside the resident sample");
+            fresh.count_empty(first - fresh.seen); // (reads in front of the block that lie in no block)
+            HIPCHK(hipMemsetAsync(room->bases + payload, 0, 64, stream_));
+            HIPCHK(dev::launch_read_trim_fill(tf, stream_));
+            if (ob.packed) {
+                const dev::SubsampleBlock sb { ob.d_bases, ob.d_offsets, nr, ob.n_bases, 0, nullptr, nullptr, nullptr, nr, nb };
+                HIPCHK(dev::launch_subsample_pack(sb, d_noff.data(), d_start.data(), reinterpret_cast<uint32_t*>(room->bases), d_cerr, stream_));
+                if (n_list) HIPCHK(dev::launch_read_trim_npos_emit(tf, np, room->npos, n_list, stream_));
+            } else HIPCHK(dev::launch_gather_reads(d_table.data(), (uint32_t)nr, room->bases, stream_));
+            HIPCHK(hipMemcpyAsync(room->offsets, d_noff.data(), (nr + 1) * sizeof(uint64_t), hipMemcpyDeviceToDevice, stream_));
+            fresh.add(DeviceBatch { room->bases, room->offsets, nr, nb, ob.packed, n_list ? room->npos : nullptr, n_list }, nr);
+        }
+        fresh.count_empty(n - fresh.seen);
+        compaction_clean(d_cerr, "mate overlap: the resident blocks' offsets and the kept lengths do not fit each other");
+    } catch (...) {
+        (void)hipStreamSynchronize(stream_); // (nothing writes the new arenas any more when their owners release them)
+        throw;
+    }
+    adopt_kept(fresh, n);
+}
+
+void Mapper::pair_overlap_device(const PairSetting& set, const PairSide& a, const PairSide& b, uint64_t n_pairs, int32_t* d_shift, uint64_t* d_keep_a, uint64_t* d_keep_b,
+    uint64_t counts[dev::PO_WORDS], hipStream_t stream)
+{
+    for (int i = 0; i < dev::PO_WORDS; ++i) counts[i] = 0;
+    if (n_pairs == 0) return;
+    HIPCHK(hipSetDevice(device_));
+    if (!stream) stream = stream_;
+    if (!set.on()) throw Error(DRPRG_EINVAL, "mate overlap: no setting (drprg_hip_set_pair_overlap)");
+    if (!a.d_offsets || !b.d_offsets || !d_shift || !d_keep_a || !d_keep_b || (a.n_bases && !a.d_words) || (b.n_bases && !b.d_words) || (a.n_npos && !a.d_npos) ||
+        (b.n_npos && !b.d_npos))
+        throw Error(DRPRG_EINVAL, "null device pointer");
+    if (n_pairs >= (1ull << 31)) throw Error(DRPRG_EOVERFLOW, "mate overlap: 2^32 reads or more in one call");
+    const uint64_t n = 2 * n_pairs;
+    const PairSide* side[2] = { &a, &b };
+    DeviceBuffer<uint16_t> d_bits[2];
+    DeviceBuffer<uint32_t> d_err, d_src, d_res2, d_mate;
+    DeviceBuffer<uint64_t> d_keep;
+    DeviceBuffer<dev::DedupLoc> d_loc;
+    DeviceBuffer<unsigned long long> d_counts;
+    d_err.alloc(1); d_src.alloc(n_pairs); d_res2.alloc(n_pairs); d_mate.alloc(n); d_keep.alloc(n); d_loc.alloc(n); d_counts.alloc(dev::PO_WORDS);
+    HIPCHK(hipMemsetAsync(d_err.data(), 0, d_err.bytes(), stream));
+    HIPCHK(hipMemsetAsync(d_loc.data(), 0, d_loc.bytes(), stream));
+    HIPCHK(hipMemsetAsync(d_mate.data(), 0xFF, d_mate.bytes(), stream));
+    HIPCHK(hipMemsetAsync(d_keep.data(), 0, d_keep.bytes(), stream));
+    HIPCHK(hipMemsetAsync(d_counts.data(), 0, d_counts.bytes(), stream));
+    for (int s = 0; s < 2; ++s) {
+        const PairSide& p = *side[s];
+        const uint64_t n_words = (p.n_bases + 15) / 16;
+        if (p.n_npos) {
+            d_bits[s].alloc(n_words + 8);
+            HIPCHK(hipMemsetAsync(d_bits[s].data(), 0, d_bits[s].bytes(), stream));
+            HIPCHK(dev::launch_mark_npos(p.d_npos, p.n_npos, p.n_bases, d_bits[s].data(), stream));
+        }
+        const dev::DedupBatch batch { p.d_words, p.n_npos ? d_bits[s].data() : nullptr, p.d_offsets, n_pairs, p.n_bases };
+        HIPCHK(dev::launch_dedup_loc(batch, s * n_pairs, n, d_loc.data(), d_err.data(), stream));
+    }
+    // every read has the source number of its place, and side 2's resident numbers follow side 1's
+    HIPCHK(dev::launch_pair_numbers(nullptr, nullptr, n_pairs, ~0ull, 0, n_pairs, d_src.data(), d_err.data(), stream));
+    HIPCHK(dev::launch_pair_numbers(nullptr, nullptr, n_pairs, ~0ull, (uint32_t)n_pairs, n_pairs, d_res2.data(), d_err.data(), stream));
+    HIPCHK(dev::launch_pair_mates(d_src.data(), d_src.data(), (uint32_t)n_pairs, d_src.data(), d_res2.data(), (uint32_t)n_pairs, n, d_mate.data(), d_err.data(), stream));
+    dev::PairOverlapArgs args {};
+    args.loc = d_loc.data(); args.mate = d_mate.data(); args.n = n; args.n1 = n_pairs;
+    args.min_overlap = set.min_overlap; args.error_milli = set.error_milli; args.clip = set.clip ? 1 : 0;
+    args.shift = d_shift; args.keep = d_keep.data(); args.counts = d_counts.data(); args.err = d_err.data();
+    HIPCHK(dev::launch_pair_overlap(args, stream));
+    HIPCHK(hipMemcpyAsync(d_keep_a, d_keep.data(), n_pairs * sizeof(uint64_t), hipMemcpyDeviceToDevice, stream));
+    HIPCHK(hipMemcpyAsync(d_keep_b, d_keep.data() + n_pairs, n_pairs * sizeof(uint64_t), hipMemcpyDeviceToDevice, stream));
+    uint32_t err = 0;
+    unsigned long long got[dev::PO_WORDS];
+    HIPCHK(hipMemcpyAsync(&err, d_err.data(), sizeof err, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(got, d_counts.data(), sizeof got, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    if (err) throw Error(DRPRG_EINVAL, "mate overlap: the offsets of a side do not ascend inside its n_bases");
+    for (int i = 0; i < dev::PO_WORDS; ++i) counts[i] = got[i];
+    counts[dev::PO_PAIRS] = n_pairs;
+    counts[dev::PO_READS] = n;
 }
 
 void Mapper::select_reads_with_anchors(std::vector<uint64_t> anchors, uint32_t A, std::vector<uint8_t>& bases, std::vector<uint64_t>& offsets,

@@ -232,6 +232,49 @@ class Context:
         d_keys (u64 per read)"""
         _check(lib.drprg_hip_dedup_keys_device(self._h, d_words, d_offsets, int(n_reads), int(n_bases), d_npos, int(n_npos), d_keys, stream), self._h)
 
+    # ---- mate overlap (include/drprg_hip.h: drprg_hip_set_pair_overlap) --------------------------
+    PAIR_COUNTS = ("pairs", "pairs_judged", "orphans", "pairs_too_long", "pairs_overlapping", "pairs_read_through", "bases_cut", "bases_clipped",
+                   "reads_emptied", "reads", "bases_before", "bases_kept")
+
+    def set_pair_overlap(self, min_overlap=30, error=0.05, clip=False):
+        """the mate-overlap setting: the smallest overlap (8 .. 1024 columns with both bases known), the largest share of differing columns
+        (0 .. 0.25, at most three places: error_milli below raises ValueError otherwise), and whether the second mate is clipped to what the first does not cover; min_overlap=0 clears it"""
+        if not min_overlap:
+            _check(lib.drprg_hip_set_pair_overlap(self._h, 0, 0, 0), self._h)
+        else:
+            _check(lib.drprg_hip_set_pair_overlap(self._h, int(min_overlap), self.error_milli(error), 1 if clip else 0), self._h)
+
+    def begin_mates(self):
+        """the files mapped from here on are side 2 of the sample's pairs"""
+        _check(lib.drprg_hip_begin_mates(self._h), self._h)
+
+    def pair_overlap(self):
+        """cuts read-through adapters and (with clip) the second mate's share of the overlap off the resident pairs and maps the cut reads
+        afresh (nothing happens when no read loses a base); returns the twelve counts"""
+        out = (C.c_uint64 * 12)()
+        _check(lib.drprg_hip_pair_overlap(self._h, out), self._h)
+        return dict(zip(self.PAIR_COUNTS, (int(v) for v in out)))
+
+    def pair_overlap_shifts(self, n_pairs):
+        """per source pair the shift the last pair_overlap() chose (-2^31: none qualified, -2^31 + 1: not judged)"""
+        d = np.zeros(int(n_pairs), dtype=np.int32)
+        _check(lib.drprg_hip_pair_overlap_shifts(self._h, _ptr(d), d.size), self._h)
+        return d
+
+    def pair_overlap_info(self):
+        out = (C.c_uint64 * 12)()
+        _check(lib.drprg_hip_pair_overlap_info(self._h, out), self._h)
+        return dict(zip(self.PAIR_COUNTS, (int(v) for v in out)))
+
+    def pair_overlap_device(self, side_a, side_b, n_pairs, d_shift, d_keep_a, d_keep_b, stream=None):
+        """the overlap kernel alone on two packed batches of n_pairs reads in device memory; a side is (d_words, d_offsets, n_bases,
+        d_npos or None, n_npos), addresses as integers.  d_shift: i32 per pair, d_keep_a / d_keep_b: u64 per pair.  Returns the twelve counts"""
+        out = (C.c_uint64 * 12)()
+        (wa, oa, ba, pa, na), (wb, ob, bb, pb, nb) = side_a, side_b
+        _check(lib.drprg_hip_pair_overlap_device(self._h, wa, oa, int(ba), pa, int(na), wb, ob, int(bb), pb, int(nb), int(n_pairs), d_shift, d_keep_a,
+                                                 d_keep_b, out, stream), self._h)
+        return dict(zip(self.PAIR_COUNTS, (int(v) for v in out)))
+
     # ---- read filter (include/drprg_hip.h: drprg_hip_set_read_filter) ---------------------------
     @staticmethod
     def qual_milli(min_qual):

@@ -367,6 +367,67 @@ int drprg_hip_dedup(drprg_hip_ctx* ctx, uint32_t key_bits, uint64_t out[4]);
 int drprg_hip_dedup_flags(drprg_hip_ctx* ctx, uint8_t* flags, uint64_t n);
 int drprg_hip_dedup_keys_device(drprg_hip_ctx* ctx, const void* d_words, const void* d_offsets, uint64_t n_reads, uint64_t n_bases, const void* d_npos,
     uint64_t n_npos, void* d_keys, void* hip_stream);
+/* ---- Mate overlap: read-through adapters cut off paired reads by the overlap of the two mates, on the resident sample.  THIS BUILD'S OWN
+ * RULE, stated from memory of fastp's overlap analysis (its default for paired reads); nothing in pandora or drprg pins it.  It is the one
+ * adapter removal that needs no adapter sequence: an insert shorter than the read shows itself in the mates.
+ *   Sides and numbers.  Reads mapped before drprg_hip_begin_mates are side 1, reads mapped after it side 2.  A read's SOURCE NUMBER is its
+ *   number among the reads of its side as the files held them, counted before any ingest-time stage dropped anything (reads seen, not reads
+ *   kept).  Pair s is (read s of side 1, read s of side 2).  Sides that hold different numbers of reads are an error (-84; the text gives
+ *   both counts).
+ *   Who is judged.  A mate is PRESENT if it is in the resident sample with at least one base after the ingest-time stages.  A pair is judged
+ *   iff both mates are present and neither is longer than PO_MAX_LEN = 1024 bases.  Otherwise every present mate passes unchanged, counted as
+ *   an orphan (the partner was dropped or has no bases) or under pairs_too_long.  Nothing is ever dropped because its mate was: pandora maps
+ *   reads singly, and a good orphan is still coverage.
+ *   Comparison.  Letters are those of the packed form, case-insensitive; any other byte, any BAM code other than A, C, G, T and any base
+ *   --mask-qual masked is the unknown base.  For mates a (side 1, La bases) and b (side 2, Lb bases) let B[j] = complement(b[Lb-1-j]);
+ *   unknown stays unknown.  For every shift d in -(Lb-1) .. La-1 the columns are i = max(0,d) .. min(La, Lb+d)-1, and column i pairs a[i]
+ *   with B[i-d].  c(d) is the number of columns where both bases are known, x(d) the number of those where the letters differ; a column with
+ *   an unknown base on either side is neither a match nor a difference.
+ *   Qualifying and choosing.  d qualifies iff c(d) >= O and 1000 x(d) <= e c(d), in integers; O (min_overlap) is a whole number in 8 .. 1024
+ *   (the executables' default: 30), e (error_milli) 1000 times a decimal in [0, 0.25] with at most three places (default 0.05: e = 50).  The
+ *   chosen shift has the largest c; among equals the smallest x; among equals the largest d.  No shift qualifies: the pair is unchanged.
+ *   Cuts.  Both are prefixes; no base is rewritten and qualities are not needed.  With I = Lb + d (the insert from a's first base to B's
+ *   last): a keeps its first min(La, I) bases and b its first min(Lb, I) -- the read-through cut.  With clip set, a keeps min(La, I) and b
+ *   keeps max(0, I - La): every column of the molecule then counts once, and a's base stands where the mates differ.  A read cut to nothing
+ *   stays a read of no bases, as everywhere else.
+ *   Order.  The stage runs on the resident sample, behind the mapping pass and so behind every ingest-time stage, which judge and cut each
+ *   mate alone as before; it runs in front of drprg_hip_dedup and drprg_hip_subsample.  The kept reads are compacted and mapped afresh: the
+ *   context is then that of a file holding side 1's reads and then side 2's, cut by the rule (fastp -i -I | cat | dedupe | rasusa | drprg),
+ *   whatever -t, the block boundaries and the input form.
+ *   Limits.  A pair from a tandem repeat can qualify at a shift that is not its true one; largest-c keeps the cut smallest then.  Behind
+ *   --trim-front or a 5' adapter cut, b loses the columns a no longer has.  Interleaved files, BAM mate flags, merging mates into one read,
+ *   quality-weighted correction, pair-aware dedup and contexts over several devices are not served.  No claim about real samples is made.
+ *   drprg_hip_set_pair_overlap(ctx, min_overlap, error_milli, clip): the setting; all zero: off.  -EINVAL outside the ranges above.  While
+ *     it is on, every block the resident set takes from drprg_hip_map_fastx is numbered by side (u32 per read, in the resident arenas), and
+ *     drprg_hip_map_host* / drprg_hip_map_device* return -EINVAL.  Off, nothing of this exists: no numbers, no launch, no wait.
+ *   drprg_hip_begin_mates(ctx): the files mapped from here on are side 2.  -EINVAL without the setting, over several devices, or when
+ *     called twice for one sample.  From here on drprg_hip_discover_reads takes its reads from device memory and returns -ENODATA (-61)
+ *     when they are not there (a pass over `reads_path` would see side 1 alone, uncut).
+ *   drprg_hip_pair_overlap(ctx, out): the stage.  out[0..11] = pairs, pairs_judged, orphans (present reads without a present partner),
+ *     pairs_too_long, pairs_overlapping (judged pairs with a chosen shift), pairs_read_through (of those, pairs in which the read-through
+ *     cut took a base), bases_cut (by the read-through cut), bases_clipped (the further bases clip took off b), reads_emptied, reads (of the
+ *     resident sample), bases_before, bases_kept.  No read lost a base: nothing else happens (no compaction, no fresh mapping; coverage and
+ *     counters untouched).  -EINVAL without the setting, over several devices, while a depth cap is set (the prefix cap would take side 1
+ *     alone), for a sample whose blocks arrived unordered (drprg_hip_set_ordered_ingest), without a drprg_hip_begin_mates call, and for a
+ *     sample an earlier drprg_hip_pair_overlap, drprg_hip_dedup or drprg_hip_subsample has compacted; -ENODATA (-61) unless the sample is
+ *     resident; -84 for sides of different sizes; -EOVERFLOW for 2^32 reads or more.  A refused or failed call leaves the context as it was.
+ *     The source numbers are dropped after the stage: a following drprg_hip_dedup or drprg_hip_subsample numbers the reads from 0 as ever.
+ *   drprg_hip_pair_overlap_shifts(ctx, d, n): per source pair the shift the last drprg_hip_pair_overlap chose, INT32_MIN when none
+ *     qualified, INT32_MIN + 1 when the pair was not judged.  -EINVAL unless n is that call's out[0].
+ *   drprg_hip_pair_overlap_info(ctx, out): the twelve counts of the last drprg_hip_pair_overlap since the last reset (all zero: none).
+ *   drprg_hip_pair_overlap_device: the two pair kernels alone on two caller-owned packed batches of n_pairs reads each (pair s: read s of
+ *     either), under the stream rule of the other device entries.  A side is d_words (u32[ceil(n_bases / 16)]), d_offsets (u64[n_pairs + 1],
+ *     ascending inside n_bases; -EINVAL otherwise) and d_npos, the n_npos positions of its unknown bases in any order (may be NULL when
+ *     n_npos is 0).  d_shift: i32[n_pairs]; d_keep_a, d_keep_b: u64[n_pairs], the bases either mate keeps; out: the twelve counts.  A mate
+ *     of no bases is not present.  -EINVAL without the setting; -EOVERFLOW for 2^31 pairs or more. */
+int drprg_hip_set_pair_overlap(drprg_hip_ctx* ctx, uint32_t min_overlap, uint32_t error_milli, int clip);
+int drprg_hip_begin_mates(drprg_hip_ctx* ctx);
+int drprg_hip_pair_overlap(drprg_hip_ctx* ctx, uint64_t out[12]);
+int drprg_hip_pair_overlap_shifts(drprg_hip_ctx* ctx, int32_t* d, uint64_t n);
+int drprg_hip_pair_overlap_info(drprg_hip_ctx* ctx, uint64_t out[12]);
+int drprg_hip_pair_overlap_device(drprg_hip_ctx* ctx, const void* d_words_a, const void* d_offsets_a, uint64_t n_bases_a, const void* d_npos_a, uint64_t n_npos_a,
+    const void* d_words_b, const void* d_offsets_b, uint64_t n_bases_b, const void* d_npos_b, uint64_t n_npos_b, uint64_t n_pairs, void* d_shift, void* d_keep_a,
+    void* d_keep_b, uint64_t out[12], void* hip_stream);
 /* ---- Read filter: reads dropped by length and mean quality on the device, as they arrive.  THIS BUILD'S OWN RULE, stated from memory of
  * what the filters nanopore workflows run in front of drprg compute (nanoq, chopper -q Q -l L, filtlong); neither pandora nor drprg has one.
  *   Settings, per context: min_len (0: no lower bound), max_len (0: no upper bound), min_qual_milli = Q * 1000 (0: no quality test).
@@ -463,8 +524,9 @@ int drprg_hip_read_trim_device(drprg_hip_ctx* ctx, const void* d_qual, uint32_t 
  *   from every adapter letter.  A window never reaches past y, so never into the next read.
  *   Cut.  The read is cut at the smallest matching p over all adapters: end = x + p.  A read cut to nothing stays a read of no bases, as
  *   with trimming; nothing is dropped or reordered.  This plain rule compares at a fixed start with substitutions only; the indel rule below
- *   (drprg_hip_set_adapters2) adds insertions, deletions and 5' adapters.  Still missing under either: anchored adapters, pair-overlap
- *   detection (fastp's default for paired reads), and indels inside an adapter that the read's end cuts short.
+ *   (drprg_hip_set_adapters2) adds insertions, deletions and 5' adapters.  Still missing under either: anchored adapters and indels
+ *   inside an adapter that the read's end cuts short.  Pair-overlap detection (fastp's default for paired reads) is a stage of its own on the
+ *   resident sample: "mate overlap" above.
  *   Invariance.  Leftmost is a minimum: the result is bit-identical whatever the launch geometry, the thread count and the input form.
  *   Adapter trimming runs inside the trim stage of drprg_hip_map_fastx, so everything "read trimming" says about what lies behind it holds:
  *   the read filter, the depth cap, the resident set, drprg_hip_dedup, drprg_hip_subsample, discover and the genotyper see cut reads.  It
