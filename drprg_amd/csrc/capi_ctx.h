@@ -51,6 +51,9 @@ struct SampleState {
     bool mates_begun = false, pair_done = false;
     uint64_t pair_counts[12] = {};
     std::vector<int32_t> pair_shifts;
+    // duplicate pairs: the last drprg_hip_dedup_pairs (its flags; counts is not used), and its forty words: eight counts, 32 levels
+    Selection pair_dedup;
+    uint64_t pair_dedup_words[40] = {};
     // What the read filter has counted: added to by the submitters of drprg_hip_map_fastx, one per device, under filter_mu.  The blocks'
     // outcomes summed: drprg_hip_read_filter_info, and in .trim / .adapter / .front drprg_hip_read_trim_info,
     // drprg_hip_adapter_trim_info and drprg_hip_front_adapter_info, in .mask drprg_hip_base_mask_info, in .decoy drprg_hip_decoy_info, in
@@ -81,6 +84,7 @@ struct drprg_hip_ctx {
     drprg::Mapper::ReadFilter read_filter;
     std::mutex filter_mu; // guards sample.filter_counts
     drprg::Mapper::PairSetting pair; // drprg_hip_set_pair_overlap
+    bool dedup_pairs = false;        // drprg_hip_set_dedup_pairs
     // ---- results of the last calls: a reset keeps them ----
     uint32_t ginfo[4] = { 0, 0, 0, 0 };
     std::vector<drprg::VcfRecord> last_records; // of the last drprg_hip_genotype (drprg_hip_genotype_alleles)

@@ -449,6 +449,8 @@ int drprg_hip_write_qc_json(drprg_hip_ctx* ctx, const char* path, const char* sa
     const Selection& ss = ctx->sample.subsample;
     if (ctx->sample.pair_done) // (only when the stage ran: a report without --mate stays byte for byte what it was)
         r.stages.emplace_back("pair_overlap", std::vector<uint64_t>(ctx->sample.pair_counts, ctx->sample.pair_counts + 12));
+    if (ctx->sample.pair_dedup.done) // (likewise: the eight counts, then the 32 duplication levels)
+        r.stages.emplace_back("pair_dedup", std::vector<uint64_t>(ctx->sample.pair_dedup_words, ctx->sample.pair_dedup_words + 40));
     r.stages.emplace_back("dedup", dd.done ? std::vector<uint64_t>(dd.counts, dd.counts + 4) : std::vector<uint64_t>());
     r.stages.emplace_back("subsample", ss.done ? std::vector<uint64_t>(ss.counts, ss.counts + 4) : std::vector<uint64_t>());
     const std::string text = qc_json(r);
@@ -717,6 +719,8 @@ int drprg_hip_set_pair_overlap(drprg_hip_ctx* ctx, uint32_t min_overlap, uint32_
     if (min_overlap == 0 && error_milli == 0 && !clip) {
         ctx->pair = Mapper::PairSetting {};
         for (Mapper* m : mappers_of(ctx)) m->pair_record(false);
+        ctx->dedup_pairs = false; // (duplicate pairs: without mates there are no pairs)
+        for (Mapper* m : mappers_of(ctx)) m->pair_dedup_record(false);
         return DRPRG_OK;
     }
     if (min_overlap < 8 || min_overlap > dev::PO_MAX_LEN) throw Error(DRPRG_EINVAL, "mate overlap: the smallest overlap is a whole number in 8 .. 1024");
@@ -793,6 +797,67 @@ int drprg_hip_pair_overlap_device(drprg_hip_ctx* ctx, const void* d_words_a, con
     const Mapper::PairSide a { (const uint32_t*)d_words_a, (const uint64_t*)d_offsets_a, n_bases_a, (const uint64_t*)d_npos_a, n_npos_a };
     const Mapper::PairSide b { (const uint32_t*)d_words_b, (const uint64_t*)d_offsets_b, n_bases_b, (const uint64_t*)d_npos_b, n_npos_b };
     m.pair_overlap_device(ctx->pair, a, b, n_pairs, (int32_t*)d_shift, (uint64_t*)d_keep_a, (uint64_t*)d_keep_b, out, (hipStream_t)hip_stream);
+    API_END(ctx)
+}
+
+// ---- duplicate pairs (the rule: include/drprg_hip.h "duplicate pairs") --------------------------------------------------------------
+int drprg_hip_set_dedup_pairs(drprg_hip_ctx* ctx, int on)
+{
+    API_BEGIN(ctx)
+    if (on && !ctx->pair.on()) throw Error(DRPRG_EINVAL, "drprg_hip_set_dedup_pairs: no mate-overlap setting (drprg_hip_set_pair_overlap): without mates there are no pairs");
+    ctx->dedup_pairs = on != 0;
+    for (Mapper* m : mappers_of(ctx)) m->pair_dedup_record(on != 0);
+    API_END(ctx)
+}
+
+int drprg_hip_dedup_pairs(drprg_hip_ctx* ctx, uint32_t key_bits, uint64_t out[8])
+{
+    API_BEGIN(ctx)
+    if (!out) throw Error(DRPRG_EINVAL, "null output");
+    Mapper& m = need_mapper(ctx);
+    if (key_bits < 1 || key_bits > 64) throw Error(DRPRG_EINVAL, "drprg_hip_dedup_pairs: key_bits must be 1..64");
+    refuse_several_devices(ctx, "drprg_hip_dedup_pairs");
+    if (!ctx->dedup_pairs) throw Error(DRPRG_EINVAL, "drprg_hip_dedup_pairs: the stage is not switched on (drprg_hip_set_dedup_pairs, before drprg_hip_pair_overlap)");
+    if (m.kept_complete() && !ctx->sample.pair_done)
+        throw Error(DRPRG_EINVAL, "drprg_hip_dedup_pairs: no drprg_hip_pair_overlap call on this sample: its reads are not paired");
+    refuse_unordered(ctx, m, "drprg_hip_dedup_pairs");
+    std::vector<uint8_t> flags;
+    uint64_t counts[8], levels[32];
+    const Mapper::SubsampleResult r = m.dedup_pairs_kept(key_bits, flags, counts, levels);
+    SampleState& s = ctx->sample;
+    uint64_t four[4];
+    record_selection(ctx, s.pair_dedup, r, flags, four);
+    for (int i = 0; i < 8; ++i) out[i] = s.pair_dedup_words[i] = counts[i];
+    for (int i = 0; i < 32; ++i) s.pair_dedup_words[8 + i] = levels[i];
+    API_END(ctx)
+}
+
+int drprg_hip_dedup_pairs_flags(drprg_hip_ctx* ctx, uint8_t* flags, uint64_t n)
+{
+    API_BEGIN(ctx)
+    copy_selection_flags(ctx->sample.pair_dedup, "drprg_hip_dedup_pairs", flags, n);
+    API_END(ctx)
+}
+
+int drprg_hip_dedup_pairs_info(drprg_hip_ctx* ctx, uint64_t out[40])
+{
+    API_BEGIN(ctx)
+    if (!out) throw Error(DRPRG_EINVAL, "null output");
+    for (int i = 0; i < 40; ++i) out[i] = ctx->sample.pair_dedup_words[i]; // (all zero before the stage has run)
+    API_END(ctx)
+}
+
+int drprg_hip_dedup_pairs_device(drprg_hip_ctx* ctx, const void* d_words_a, const void* d_offsets_a, uint64_t n_bases_a, const void* d_npos_a, uint64_t n_npos_a,
+    const void* d_words_b, const void* d_offsets_b, uint64_t n_bases_b, const void* d_npos_b, uint64_t n_npos_b, uint64_t n_pairs, uint32_t key_bits, void* d_keys,
+    void* d_keep, void* d_copies, uint64_t out[40], void* hip_stream)
+{
+    API_BEGIN(ctx)
+    Mapper& m = need_mapper(ctx);
+    if (!out) throw Error(DRPRG_EINVAL, "null output");
+    static_assert(dev::PD_WORDS == 40, "drprg_hip_dedup_pairs_device writes forty words");
+    const Mapper::PairSide a { (const uint32_t*)d_words_a, (const uint64_t*)d_offsets_a, n_bases_a, (const uint64_t*)d_npos_a, n_npos_a };
+    const Mapper::PairSide b { (const uint32_t*)d_words_b, (const uint64_t*)d_offsets_b, n_bases_b, (const uint64_t*)d_npos_b, n_npos_b };
+    m.dedup_pairs_device(a, b, n_pairs, key_bits, (uint64_t*)d_keys, (uint8_t*)d_keep, (uint32_t*)d_copies, out, (hipStream_t)hip_stream);
     API_END(ctx)
 }
 

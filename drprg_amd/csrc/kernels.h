@@ -458,6 +458,40 @@ hipError_t launch_pair_overlap(const PairOverlapArgs& a, hipStream_t stream);
 // read_trim_temp_bytes(n_reads) bytes.
 hipError_t launch_pair_offsets(const uint64_t* keep, uint64_t n_reads, uint64_t* noff, void* temp, size_t temp_bytes, hipStream_t stream);
 
+// pair_dedup.hip: duplicate pairs (the rule: include/drprg_hip.h "duplicate pairs").  The n resident reads (n < 2^32) are numbered as
+// launch_pair_overlap numbers them (side 1 in [0, n1)); loc as launch_dedup_loc fills it and rkey as launch_dedup_keys does (both n
+// entries; every block's words and bitmap must live until the call is done).  srcno[i]: the source pair of resident read i (~0u: the read
+// lies in no block and belongs to no unit), mate[i]: the resident number of its mate (~0u: none); pairs: the source pairs (1 <= pairs < 2^32).
+// launch_pair_dedup leaves ukey[s] = U, keep[s] = 0 for a duplicate unit and 1 for every other, copies[s] = the copies of a kept unit
+// with bases and 0 for every other (pairs entries each); flag[i] = 0 for every read with bases of a duplicate unit, rank / boff as
+// launch_dedup_select leaves them (n + 1 entries, as flag32 and klen); out: PD_WORDS device words, of which it writes PD_WITH_BASES,
+// PD_BOTH, PD_DROPPED and the 32 levels behind PD_LEVELS (the caller sets the rest).  unit: 2 pairs entries, skey / skey_sorted / idx /
+// idx_sorted / root: pairs entries, ubases: pairs bytes, changed: PD_ROUNDS + 1 words -- scratch; temp: subsample_scan_temp_bytes(max(n,
+// pairs)) bytes.  *err (zeroed by the caller) is set by any index out of range, by mates that do not name each other, and by links that
+// have not reached their class's first unit after PD_ROUNDS rounds; nothing is written out of bounds then.
+constexpr int PD_ROUNDS = 32;
+enum { PD_UNITS = 0, PD_WITH_BASES = 1, PD_BOTH = 2, PD_DROPPED = 3, PD_READS_BEFORE = 4, PD_BASES_BEFORE = 5, PD_READS_KEPT = 6, PD_BASES_KEPT = 7, PD_LEVELS = 8, PD_WORDS = 40 };
+struct PairDedupArgs {
+    uint64_t n, n1, pairs;
+    uint32_t key_bits;
+    const DedupLoc* loc;
+    const unsigned long long* rkey;
+    const uint32_t *srcno, *mate;
+    uint32_t* unit;
+    uint64_t *ukey, *skey, *skey_sorted;
+    uint32_t *idx, *idx_sorted, *root, *copies;
+    uint8_t *ubases, *keep, *flag;
+    uint32_t *flag32, *rank;
+    uint64_t *klen, *boff;
+    unsigned long long* out;
+    uint32_t *changed, *err;
+    void* temp;
+    size_t temp_bytes;
+};
+hipError_t launch_pair_dedup(const PairDedupArgs& a, hipStream_t stream);
+// srcno[res[k]] = src[k] for the m reads of one list (launch_pair_mates' lists; srcno: n entries, filled with ~0u by the caller)
+hipError_t launch_pair_source_numbers(const uint32_t* src, const uint32_t* res, uint32_t m, uint64_t n, uint32_t* srcno, uint32_t* err, hipStream_t stream);
+
 // read_qual.hip: the read filter (the rule: include/drprg_hip.h "read filter").  qsum[i] = sum of E[quality] over read i's n_bases-indexed
 // bytes of qual (qual: n_bases + 64 bytes readable; bias 33 or 0), then flag[i] = 1 for the reads the rule keeps, rank[i] = kept reads
 // before i and boff[i] = kept bases before i (n_reads + 1 entries each, entry n_reads the totals: what launch_subsample_tables and the

@@ -349,6 +349,24 @@ public:
     void pair_overlap_device(const PairSetting& set, const PairSide& a, const PairSide& b, uint64_t n_pairs, int32_t* d_shift, uint64_t* d_keep_a, uint64_t* d_keep_b,
         uint64_t counts[dev::PO_WORDS], hipStream_t stream);
 
+    // Duplicate pairs dropped from the resident sample (the rule: include/drprg_hip.h "duplicate pairs"; pair_dedup.hip).
+    // pair_dedup_record(true): from now on pair_overlap_kept keeps, as device buffers of pair_, the mate and the source number of every
+    // resident read (the overlap stage drops no read, so the numbers hold through its compaction); off, nothing is kept.  dedup_pairs_kept
+    // needs that record of this very sample -- any other compaction releases it -- and begins as dedup_kept does; no unit dropped: nothing
+    // else happens.  counts: the eight PD_* counts, levels: the 32 duplication levels.  The record is released when the call is done;
+    // a call that fails leaves it, and the sample, as they were.
+    void pair_dedup_record(bool on)
+    {
+        pair_.dedup = on;
+        if (!on) pair_.release_record();
+    }
+    SubsampleResult dedup_pairs_kept(uint32_t key_bits, std::vector<uint8_t>& flags, uint64_t counts[8], uint64_t levels[32]);
+    // The stage's kernels alone on the caller's packed batches (drprg_hip_dedup_pairs_device): unit s is (read s of a, read s of b).
+    // d_keys[s] = U, d_keep[s] = 0 for a duplicate unit, d_copies[s] = the copies of a kept unit with bases, else 0; out: the PD_WORDS
+    // words.  Synchronises `stream`.
+    void dedup_pairs_device(const PairSide& a, const PairSide& b, uint64_t n_pairs, uint32_t key_bits, uint64_t* d_keys, uint8_t* d_keep, uint32_t* d_copies,
+        uint64_t out[dev::PD_WORDS], hipStream_t stream);
+
     // this += other, on the device (the other Mapper's vectors are left as they are): peer copy into a scratch buffer + one
     // add kernel, or the add kernel alone when both live on the same device.  Both are synchronised first.
     void add_vectors_from(Mapper& other);
@@ -778,6 +796,17 @@ private:
         size_t block2 = 0;           // side 2's first block
         uint64_t n1 = 0;             // and first resident number
         bool spent = false;          // the sample was compacted, or the stage has run: the numbers no longer stand for it
+        // duplicate pairs: switched on; what pair_overlap_kept left for it (ready): mate[i] and srcno[i] of resident read i, the source pairs
+        bool dedup = false, ready = false;
+        uint64_t pairs = 0;
+        DeviceBuffer<uint32_t> d_mate, d_srcno;
+        void release_record()
+        {
+            ready = false;
+            pairs = 0;
+            d_mate.reset();
+            d_srcno.reset();
+        }
     };
     PairState pair_;
     // the source numbers of a block the resident set has just taken (flag / rank / take: launch_pair_numbers); base: the side's reads in front

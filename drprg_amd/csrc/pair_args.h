@@ -1,5 +1,5 @@
 // pair_args.h -- --mate FILE, --pair-min-overlap O, --pair-error E and --pair-clip-overlap as both executables take them
-// (include/drprg_hip.h "mate overlap").
+// (include/drprg_hip.h "mate overlap"), and --dedup-pairs behind them (include/drprg_hip.h "duplicate pairs").
 #pragma once
 #include "../../include/drprg_hip.h"
 #include <cstdio>
@@ -12,6 +12,7 @@ struct PairArgs {
     std::string mate; // --mate FILE: empty = not set
     uint32_t min_overlap = 30, error_milli = 50;
     bool clip = false, overlap_given = false, error_given = false;
+    bool dedup_pairs = false; // --dedup-pairs
     bool any() const { return !mate.empty(); }
     // each returns what is wrong with its value (a usage error: exit 2), or nothing
     std::string set_overlap(const char* v)
@@ -45,8 +46,11 @@ struct PairArgs {
         return std::string();
     }
     // what is wrong with the options together, max_covg being the depth cap the run would set (>= 4294967295: none)
-    std::string check(uint64_t max_covg = ~0ull) const
+    std::string check(uint64_t max_covg = ~0ull, bool dedup = false) const
     {
+        if (mate.empty() && dedup_pairs) return "--dedup-pairs belongs to --mate: without the second mates there are no pairs (--dedup judges every read alone)";
+        if (dedup_pairs && dedup)
+            return "--dedup-pairs and --dedup are alternatives: --dedup would drop one mate of a pair and keep the other (give --dedup-pairs for paired reads)";
         if (mate.empty() && overlap_given) return "--pair-min-overlap belongs to --mate";
         if (mate.empty() && error_given) return "--pair-error belongs to --mate";
         if (mate.empty() && clip) return "--pair-clip-overlap belongs to --mate";
@@ -55,7 +59,12 @@ struct PairArgs {
                    "(--subsample-covg cuts a paired sample to a depth)";
         return std::string();
     }
-    int set_on(drprg_hip_ctx* ctx) const { return any() ? drprg_hip_set_pair_overlap(ctx, min_overlap, error_milli, clip ? 1 : 0) : 0; }
+    int set_on(drprg_hip_ctx* ctx) const
+    {
+        if (!any()) return 0;
+        if (int rc = drprg_hip_set_pair_overlap(ctx, min_overlap, error_milli, clip ? 1 : 0)) return rc;
+        return dedup_pairs ? drprg_hip_set_dedup_pairs(ctx, 1) : 0; // (off: the entry is never called)
+    }
     static const char* usage()
     {
         return "--mate FILE [--pair-min-overlap O] [--pair-error E] [--pair-clip-overlap]: FILE holds the second mates of the reads of -i, in the same\n"
@@ -64,7 +73,13 @@ struct PairArgs {
                "              30, of which at most the share E differ, default 0.05 -- gives the insert: bases beyond it are adapter read-through and\n"
                "              are cut off both mates.  No adapter sequence is needed.  --pair-clip-overlap also cuts the second mate down to what\n"
                "              the first does not cover, so that every base of the molecule counts once.  A read whose mate an earlier stage dropped\n"
-               "              passes unchanged.  Runs in front of --dedup and --subsample-covg; needs the reads resident (DRPRG_HIP_KEEP_READS_GB).\n";
+               "              passes unchanged.  Runs in front of --dedup and --subsample-covg; needs the reads resident (DRPRG_HIP_KEEP_READS_GB).\n"
+               "  --dedup-pairs (beside --mate, instead of --dedup): behind the overlap stage and in front of --subsample-covg every pair whose two mates\n"
+               "              are both identical to the mates of a pair before it in the files -- same lengths, same letters without case, unknown bases\n"
+               "              at the same places; a mate that was dropped or emptied counts as no bases, so an orphan is judged against orphans -- is\n"
+               "              dropped, both mates or neither, on the device.  Two fragments that merely start at the same base keep both their pairs,\n"
+               "              where --dedup would drop the second one's first mate.  -v prints the duplication rate, --qc-json the duplication levels.\n"
+               "              Forward orientation and exact identity only; no optical-distance rule.\n";
     }
     // -v: the twelve counts as one line, through `say`
     template <typename Say> static void report(const uint64_t c[12], Say&& say)
@@ -74,6 +89,16 @@ struct PairArgs {
                                          "bases_cut=%llu bases_clipped=%llu reads_emptied=%llu reads=%llu bases_before=%llu bases_kept=%llu",
             (unsigned long long)c[0], (unsigned long long)c[1], (unsigned long long)c[2], (unsigned long long)c[3], (unsigned long long)c[4], (unsigned long long)c[5],
             (unsigned long long)c[6], (unsigned long long)c[7], (unsigned long long)c[8], (unsigned long long)c[9], (unsigned long long)c[10], (unsigned long long)c[11]);
+        say(line);
+    }
+    // -v: the eight counts of --dedup-pairs and the duplication rate as one line, through `say`
+    template <typename Say> static void report_dedup(const uint64_t c[8], Say&& say)
+    {
+        char line[512];
+        std::snprintf(line, sizeof line, "pair dedup: units=%llu units_with_bases=%llu units_both_mates=%llu units_dropped=%llu reads_before=%llu bases_before=%llu "
+                                         "reads_kept=%llu bases_kept=%llu duplication_rate=%.6f",
+            (unsigned long long)c[0], (unsigned long long)c[1], (unsigned long long)c[2], (unsigned long long)c[3], (unsigned long long)c[4], (unsigned long long)c[5],
+            (unsigned long long)c[6], (unsigned long long)c[7], c[1] ? (double)c[3] / (double)c[1] : 0.0);
         say(line);
     }
 };

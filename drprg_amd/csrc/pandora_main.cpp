@@ -91,7 +91,7 @@ void usage()
         "  pandora index    [-t N] [-w W] [-k K] <prg>\n"
         "  pandora map      [--genotype] [--local] [--gt-conf X] [-v] [-o DIR] [-g SIZE] [--max-covg N | --subsample-covg D [--seed S]]\n"
         "                   [--dedup] [--min-read-len L] [--max-read-len L] [--min-read-qual Q]\n"
-        "                   [--mate FILE [--pair-min-overlap O] [--pair-error E] [--pair-clip-overlap]]\n"
+        "                   [--mate FILE [--pair-min-overlap O] [--pair-error E] [--pair-clip-overlap] [--dedup-pairs]]\n"
         "                   [--trim-front N] [--trim-tail N] [--trim-qual Q [--trim-window W]]\n"
         "                   [--adapter SEQ]... [--adapter-error E] [--adapter-min-overlap O] [--adapter-indels] [--front-adapter SEQ]...\n"
         "                   [--poly-tail LETTERS [--poly-min-len M]] [--min-complexity P] [--qc-json FILE [--qc-no-qual]]\n"
@@ -262,6 +262,7 @@ Args parse(int argc, char** argv)
         else if (s == "--dedup") a.dedup = true;
         else if (s == "--mate") a.pair.mate = need(i);
         else if (s == "--pair-clip-overlap") a.pair.clip = true;
+        else if (s == "--dedup-pairs") a.pair.dedup_pairs = true;
         else if (s == "--pair-min-overlap") {
             const std::string e = a.pair.set_overlap(need(i));
             if (!e.empty()) die(e, 2);
@@ -291,7 +292,7 @@ Args parse(int argc, char** argv)
     if (a.subsample && a.max_covg_given && a.max_covg != 4294967295ull)
         die("--max-covg and --subsample-covg are alternatives (the prefix cap or the random subsample): give one of them", 2);
     if (a.subsample) a.max_covg = 4294967295ull; // the default cap gives way
-    if (const std::string e = a.pair.check(a.max_covg_given ? a.max_covg : ~0ull); !e.empty()) die(e, 2);
+    if (const std::string e = a.pair.check(a.max_covg_given ? a.max_covg : ~0ull, a.dedup); !e.empty()) die(e, 2);
     if (a.pair.any()) a.max_covg = 4294967295ull; // (to --mate as well)
     if (a.max_read_len && a.max_read_len < a.min_read_len) die("--max-read-len is below --min-read-len: no read can pass", 2);
     if (a.trim_window && !a.trim_qual_milli) die("--trim-window belongs to --trim-qual", 2);
@@ -396,7 +397,7 @@ std::string run_tag(const Args& a, const std::string& reads)
         + (a.subsample ? "|S" + std::to_string(a.subsample_covg) + "/" + std::to_string((unsigned long long)a.seed) : std::string())
         + (a.dedup ? std::string("|D") : std::string())
         + (a.pair.any() ? "|" + stamp(a.pair.mate) + "|M" + std::to_string(a.pair.min_overlap) + "/" + std::to_string(a.pair.error_milli) + "/"
-                  + std::to_string((int)a.pair.clip)
+                  + std::to_string((int)a.pair.clip) + (a.pair.dedup_pairs ? "/P" : "")
                         : std::string())
         + (a.min_read_len || a.max_read_len || a.min_read_qual_milli ? "|F" + std::to_string((unsigned long long)a.min_read_len) + "/"
                   + std::to_string((unsigned long long)a.max_read_len) + "/" + std::to_string(a.min_read_qual_milli)
@@ -438,6 +439,10 @@ void map_reads(drprg_hip_ctx* ctx, const Args& a, const std::string& reads)
     uint64_t out[12] = {};
     if (int rc = drprg_hip_pair_overlap(ctx, out)) die(std::string("--mate: ") + drprg_hip_last_error(ctx), -rc);
     if (a.verbose) drprg::PairArgs::report(out, [](const char* line) { std::printf("[pandora-hip] %s\n", line); });
+    if (!a.pair.dedup_pairs) return;
+    uint64_t dd[8] = {};
+    if (int rc = drprg_hip_dedup_pairs(ctx, 64, dd)) die(std::string("--dedup-pairs: ") + drprg_hip_last_error(ctx), -rc);
+    if (a.verbose) drprg::PairArgs::report_dedup(dd, [](const char* line) { std::printf("[pandora-hip] %s\n", line); });
 }
 
 // --dedup: behind the mapping pass, in front of --subsample-covg.  Fails loudly when the sample is not resident.

@@ -25,8 +25,8 @@ struct QcArgs {
                "              length histogram with N50 and N90, per-cycle base composition and quality, base and read quality histograms and GC, of\n"
                "              the reads as the file holds them (raw) and as they are handed to mapping (prepared: behind every --trim-*, --adapter,\n"
                "              --poly-tail, --mask-qual, --min/max-read-*, --min-complexity, --decoy and --max-covg; in front of --dedup and\n"
-               "              --subsample-covg), with every stage's counters.  Statistics only: no verdict, no duplication estimate, no adapter\n"
-               "              guess.  Needs qualities (FASTA is an error) unless --qc-no-qual leaves the three quality sections out.\n";
+               "              --subsample-covg), with every stage's counters.  Statistics only: no verdict, no adapter guess (duplication\n"
+               "              levels: --dedup-pairs).  Needs qualities (FASTA is an error) unless --qc-no-qual leaves the three quality sections out.\n";
     }
     // -v: one line per snapshot, through `say` (a printf-like function of the executable with its own prefix)
     template <typename Say> void report(drprg_hip_ctx* ctx, Say&& say) const

@@ -57,9 +57,10 @@ void Mapper::drop_kept()
         HIPCHK(hipStreamSynchronize(stream_));
     }
     resident_.clear();
-    const bool record = pair_.record;
+    const bool record = pair_.record, dedup = pair_.dedup;
     pair_ = PairState {};
     pair_.record = record;
+    pair_.dedup = dedup;
 }
 
 // The map call on a block of the resident set.  in_keep_call_ is set for as long as it runs and on no other path: map() takes every other
@@ -218,6 +219,7 @@ void Mapper::adopt_kept(ResidentSet& fresh, uint64_t reads_kept)
     std::swap(resident_, fresh);
     pair_.src.clear(); // (mate overlap: the numbers lay in the old arenas and stood for the old blocks)
     pair_.spent = true;
+    pair_.release_record(); // (duplicate pairs: pair_overlap_kept, whose compaction keeps every read's number, hands its record over behind this call)
     // ---- the kept reads mapped afresh ----
     HIPCHK(hipMemsetAsync(d_covg_.data(), 0, d_covg_.bytes(), stream_)); // [coverage | reads per PRG]
     HIPCHK(hipMemsetAsync(d_counters_.data(), 0, d_counters_.bytes(), stream_));
@@ -464,6 +466,19 @@ void Mapper::pair_overlap_kept(const PairSetting& set, std::vector<int32_t>& shi
     }
     HIPCHK(dev::launch_pair_mates(d_src.data(), d_res.data(), (uint32_t)m[0], d_src.data() + m[0], d_res.data() + m[0], (uint32_t)m[1], n, d_mate.data(), d_err.data(),
         stream_));
+    DeviceBuffer<uint32_t> d_srcno; // duplicate pairs: the source number of every resident read, kept with d_mate when that stage is switched on
+    if (pair_.dedup) {
+        d_srcno.alloc(n);
+        HIPCHK(hipMemsetAsync(d_srcno.data(), 0xFF, d_srcno.bytes(), stream_));
+        HIPCHK(dev::launch_pair_source_numbers(d_src.data(), d_res.data(), (uint32_t)(m[0] + m[1]), n, d_srcno.data(), d_err.data(), stream_));
+    }
+    const auto hand_over = [&] {
+        if (!pair_.dedup) return;
+        pair_.d_mate = std::move(d_mate);
+        pair_.d_srcno = std::move(d_srcno);
+        pair_.pairs = pairs;
+        pair_.ready = true;
+    };
     dev::PairOverlapArgs args {};
     args.loc = d_loc.data(); args.mate = d_mate.data(); args.n = n; args.n1 = n1;
     args.min_overlap = set.min_overlap; args.error_milli = set.error_milli; args.clip = set.clip ? 1 : 0;
@@ -492,6 +507,7 @@ void Mapper::pair_overlap_kept(const PairSetting& set, std::vector<int32_t>& shi
     if (counts[dev::PO_BASES_KEPT] == counts[dev::PO_BASES_BEFORE]) { // no read lost a base: nothing else happens
         pair_.src.clear(); // (the numbers are dropped after the stage)
         pair_.spent = true;
+        hand_over();
         return;
     }
     // ---- compaction by the ranges [0, keep): a new set under the same cap, as keep_flagged makes one by flags ----
@@ -550,6 +566,7 @@ void Mapper::pair_overlap_kept(const PairSetting& set, std::vector<int32_t>& shi
         throw;
     }
     adopt_kept(fresh, n);
+    hand_over();
 }
 
 void Mapper::pair_overlap_device(const PairSetting& set, const PairSide& a, const PairSide& b, uint64_t n_pairs, int32_t* d_shift, uint64_t* d_keep_a, uint64_t* d_keep_b,
@@ -608,6 +625,153 @@ void Mapper::pair_overlap_device(const PairSetting& set, const PairSide& a, cons
     for (int i = 0; i < dev::PO_WORDS; ++i) counts[i] = got[i];
     counts[dev::PO_PAIRS] = n_pairs;
     counts[dev::PO_READS] = n;
+}
+
+// ---- duplicate pairs on the resident sample (the rule: include/drprg_hip.h "duplicate pairs") -------------------------------------------
+namespace {
+// the scratch of one launch_pair_dedup call over n reads and `pairs` units; what the caller owns itself stays null in `a`
+struct PairDedupScratch {
+    DeviceBuffer<uint64_t> skey, skey_sorted, klen, boff;
+    DeviceBuffer<uint32_t> unit, idx, idx_sorted, root, flag32, rank, changed;
+    DeviceBuffer<uint8_t> ubases, flag;
+    DeviceBuffer<unsigned long long> out;
+    DeviceBuffer<unsigned char> temp;
+    void alloc(uint64_t n, uint64_t pairs, dev::PairDedupArgs& a)
+    {
+        skey.alloc(pairs); skey_sorted.alloc(pairs); klen.alloc(n + 1); boff.alloc(n + 1);
+        unit.alloc(2 * pairs); idx.alloc(pairs); idx_sorted.alloc(pairs); root.alloc(pairs); flag32.alloc(n + 1); rank.alloc(n + 1);
+        changed.alloc(dev::PD_ROUNDS + 1); ubases.alloc(pairs); flag.alloc(n); out.alloc(dev::PD_WORDS);
+        temp.alloc(dev::subsample_scan_temp_bytes(std::max(n, pairs)));
+        a.unit = unit.data(); a.skey = skey.data(); a.skey_sorted = skey_sorted.data(); a.idx = idx.data(); a.idx_sorted = idx_sorted.data();
+        a.root = root.data(); a.ubases = ubases.data(); a.flag = flag.data(); a.flag32 = flag32.data(); a.rank = rank.data(); a.klen = klen.data();
+        a.boff = boff.data(); a.out = out.data(); a.changed = changed.data(); a.temp = temp.data(); a.temp_bytes = temp.size();
+    }
+};
+} // namespace
+
+Mapper::SubsampleResult Mapper::dedup_pairs_kept(uint32_t key_bits, std::vector<uint8_t>& flags, uint64_t counts[8], uint64_t levels[32])
+{
+    if (key_bits < 1 || key_bits > 64) throw Error(DRPRG_EINVAL, "duplicate pairs: key_bits must be 1..64");
+    SubsampleResult res = resident_sample("duplicate pairs", flags);
+    if (!pair_.dedup) throw Error(DRPRG_EINVAL, "duplicate pairs: the stage is not switched on (drprg_hip_set_dedup_pairs, before drprg_hip_pair_overlap)");
+    const uint64_t n = res.reads_before, n1 = pair_.n1;
+    if (!pair_.ready || pair_.d_mate.size() != n || pair_.d_srcno.size() != n)
+        throw Error(DRPRG_EINVAL, "duplicate pairs: the resident reads are not paired (no drprg_hip_pair_overlap call on this sample, or it has been compacted "
+                                  "since by drprg_hip_dedup, drprg_hip_subsample or an earlier drprg_hip_dedup_pairs)");
+    const uint64_t pairs = pair_.pairs;
+    if (n >= (1ull << 32) || pairs >= (1ull << 32)) throw Error(DRPRG_EOVERFLOW, "duplicate pairs: 2^32 reads or pairs or more in one sample");
+    for (int i = 0; i < 8; ++i) counts[i] = 0;
+    for (int i = 0; i < 32; ++i) levels[i] = 0;
+    counts[dev::PD_UNITS] = pairs;
+    counts[dev::PD_READS_BEFORE] = counts[dev::PD_READS_KEPT] = n;
+    counts[dev::PD_BASES_BEFORE] = counts[dev::PD_BASES_KEPT] = res.bases_before;
+    if (n == 0 || pairs == 0) {
+        pair_.release_record();
+        return res;
+    }
+    // ---- selection (device scratch of this call) ----
+    DeviceBuffer<uint64_t> d_rkey, d_ukey;
+    DeviceBuffer<uint32_t> d_copies, d_err;
+    DeviceBuffer<uint8_t> d_keep;
+    DeviceBuffer<dev::DedupLoc> d_loc;
+    DeviceBuffer<unsigned long long> d_count;
+    PairDedupScratch scratch;
+    dev::PairDedupArgs args {};
+    d_rkey.alloc(n); d_ukey.alloc(pairs); d_copies.alloc(pairs); d_err.alloc(4); d_keep.alloc(pairs); d_loc.alloc(n); d_count.alloc(1);
+    scratch.alloc(n, pairs, args);
+    HIPCHK(hipMemsetAsync(d_rkey.data(), 0, d_rkey.bytes(), stream_));
+    HIPCHK(hipMemsetAsync(d_loc.data(), 0, d_loc.bytes(), stream_));
+    HIPCHK(hipMemsetAsync(d_err.data(), 0, d_err.bytes(), stream_));
+    std::vector<DedupBlock> blocks(resident_.kept.size()); // (the exact check reads every block: the scratch of all of them lives until it is done)
+    for (size_t b = 0; b < resident_.kept.size(); ++b) {
+        if (!resident_.kept[b].n_reads || !resident_.kept[b].n_bases) continue;
+        if (resident_.first[b] + resident_.kept[b].n_reads > n) throw Error(DRPRG_EIO, "duplicate pairs: the resident blocks hold more reads than the sample");
+        dedup_block(resident_.kept[b], blocks[b], d_count.data());
+        HIPCHK(dev::launch_dedup_keys(blocks[b].batch, reinterpret_cast<unsigned long long*>(d_rkey.data()) + resident_.first[b], d_err.data(), stream_));
+        HIPCHK(dev::launch_dedup_loc(blocks[b].batch, resident_.first[b], n, d_loc.data(), d_err.data(), stream_));
+    }
+    args.n = n; args.n1 = n1; args.pairs = pairs; args.key_bits = key_bits; args.loc = d_loc.data();
+    args.rkey = reinterpret_cast<const unsigned long long*>(d_rkey.data()); args.srcno = pair_.d_srcno.data(); args.mate = pair_.d_mate.data();
+    args.ukey = d_ukey.data(); args.copies = d_copies.data(); args.keep = d_keep.data(); args.err = d_err.data();
+    HIPCHK(dev::launch_pair_dedup(args, stream_));
+    uint32_t err = 0, kept = 0;
+    unsigned long long got[dev::PD_WORDS];
+    HIPCHK(hipMemcpyAsync(&err, d_err.data(), sizeof err, hipMemcpyDeviceToHost, stream_));
+    HIPCHK(hipMemcpyAsync(&kept, args.rank + n, sizeof kept, hipMemcpyDeviceToHost, stream_));
+    HIPCHK(hipMemcpyAsync(got, args.out, sizeof got, hipMemcpyDeviceToHost, stream_));
+    HIPCHK(hipStreamSynchronize(stream_));
+    if (err) throw Error(DRPRG_EIO, "duplicate pairs: a resident block's offsets do not fit its bases, or the pairing does not fit the sample");
+    counts[dev::PD_WITH_BASES] = got[dev::PD_WITH_BASES];
+    counts[dev::PD_BOTH] = got[dev::PD_BOTH];
+    counts[dev::PD_DROPPED] = got[dev::PD_DROPPED];
+    for (int i = 0; i < 32; ++i) levels[i] = got[dev::PD_LEVELS + i];
+    if (kept != n) keep_flagged(args.flag, args.rank, args.boff, d_err.data() + 1, "duplicate pairs", res, flags); // (else no read dropped: nothing else happens)
+    counts[dev::PD_READS_KEPT] = res.reads_kept;
+    counts[dev::PD_BASES_KEPT] = res.bases_kept;
+    pair_.release_record();
+    return res;
+}
+
+void Mapper::dedup_pairs_device(const PairSide& a, const PairSide& b, uint64_t n_pairs, uint32_t key_bits, uint64_t* d_keys, uint8_t* d_keep, uint32_t* d_copies,
+    uint64_t out[dev::PD_WORDS], hipStream_t stream)
+{
+    for (int i = 0; i < dev::PD_WORDS; ++i) out[i] = 0;
+    if (key_bits < 1 || key_bits > 64) throw Error(DRPRG_EINVAL, "duplicate pairs: key_bits must be 1..64");
+    if (n_pairs == 0) return;
+    HIPCHK(hipSetDevice(device_));
+    if (!stream) stream = stream_;
+    if (!a.d_offsets || !b.d_offsets || !d_keys || !d_keep || !d_copies || (a.n_bases && !a.d_words) || (b.n_bases && !b.d_words) || (a.n_npos && !a.d_npos) ||
+        (b.n_npos && !b.d_npos))
+        throw Error(DRPRG_EINVAL, "null device pointer");
+    if (n_pairs >= (1ull << 31)) throw Error(DRPRG_EOVERFLOW, "duplicate pairs: 2^32 reads or more in one call");
+    const uint64_t n = 2 * n_pairs;
+    const PairSide* side[2] = { &a, &b };
+    DeviceBuffer<uint16_t> d_bits[2];
+    DeviceBuffer<uint32_t> d_err, d_srcno, d_mate;
+    DeviceBuffer<uint64_t> d_rkey;
+    DeviceBuffer<dev::DedupLoc> d_loc;
+    PairDedupScratch scratch;
+    dev::PairDedupArgs args {};
+    d_err.alloc(1); d_srcno.alloc(n); d_mate.alloc(n); d_rkey.alloc(n); d_loc.alloc(n);
+    scratch.alloc(n, n_pairs, args);
+    HIPCHK(hipMemsetAsync(d_err.data(), 0, d_err.bytes(), stream));
+    HIPCHK(hipMemsetAsync(d_loc.data(), 0, d_loc.bytes(), stream));
+    HIPCHK(hipMemsetAsync(d_rkey.data(), 0, d_rkey.bytes(), stream));
+    for (int s = 0; s < 2; ++s) {
+        const PairSide& p = *side[s];
+        const uint64_t n_words = (p.n_bases + 15) / 16;
+        if (p.n_npos) {
+            d_bits[s].alloc(n_words + 8);
+            HIPCHK(hipMemsetAsync(d_bits[s].data(), 0, d_bits[s].bytes(), stream));
+            HIPCHK(dev::launch_mark_npos(p.d_npos, p.n_npos, p.n_bases, d_bits[s].data(), stream));
+        }
+        const dev::DedupBatch batch { p.d_words, p.n_npos ? d_bits[s].data() : nullptr, p.d_offsets, n_pairs, p.n_bases };
+        HIPCHK(dev::launch_dedup_keys(batch, reinterpret_cast<unsigned long long*>(d_rkey.data()) + s * n_pairs, d_err.data(), stream));
+        HIPCHK(dev::launch_dedup_loc(batch, s * n_pairs, n, d_loc.data(), d_err.data(), stream));
+        // every read has the source number of its place, and its mate is the read at that place of the other side
+        HIPCHK(dev::launch_pair_numbers(nullptr, nullptr, n_pairs, ~0ull, 0, n_pairs, d_srcno.data() + s * n_pairs, d_err.data(), stream));
+        HIPCHK(dev::launch_pair_numbers(nullptr, nullptr, n_pairs, ~0ull, (uint32_t)((1 - s) * n_pairs), n_pairs, d_mate.data() + s * n_pairs, d_err.data(), stream));
+    }
+    args.n = n; args.n1 = n_pairs; args.pairs = n_pairs; args.key_bits = key_bits; args.loc = d_loc.data();
+    args.rkey = reinterpret_cast<const unsigned long long*>(d_rkey.data()); args.srcno = d_srcno.data(); args.mate = d_mate.data();
+    args.ukey = d_keys; args.copies = d_copies; args.keep = d_keep; args.err = d_err.data();
+    HIPCHK(dev::launch_pair_dedup(args, stream));
+    uint32_t err = 0, kept = 0;
+    uint64_t bases[2] = { 0, 0 };
+    unsigned long long got[dev::PD_WORDS];
+    HIPCHK(hipMemcpyAsync(&err, d_err.data(), sizeof err, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(&kept, args.rank + n, sizeof kept, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(&bases[1], args.boff + n, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(got, args.out, sizeof got, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    if (err) throw Error(DRPRG_EINVAL, "duplicate pairs: the offsets of a side do not ascend from 0 to its n_bases");
+    bases[0] = a.n_bases + b.n_bases;
+    for (int i = 0; i < dev::PD_WORDS; ++i) out[i] = got[i];
+    out[dev::PD_UNITS] = n_pairs;
+    out[dev::PD_READS_BEFORE] = n;
+    out[dev::PD_BASES_BEFORE] = bases[0];
+    out[dev::PD_READS_KEPT] = kept;
+    out[dev::PD_BASES_KEPT] = bases[1];
 }
 
 void Mapper::select_reads_with_anchors(std::vector<uint64_t> anchors, uint32_t A, std::vector<uint8_t>& bases, std::vector<uint64_t>& offsets,

@@ -275,6 +275,45 @@ class Context:
                                                  d_keep_b, out, stream), self._h)
         return dict(zip(self.PAIR_COUNTS, (int(v) for v in out)))
 
+    # ---- duplicate pairs (include/drprg_hip.h: drprg_hip_set_dedup_pairs) ------------------------
+    PAIR_DEDUP_COUNTS = ("units", "units_with_bases", "units_both_mates", "units_dropped", "reads_before", "bases_before", "reads_kept", "bases_kept")
+
+    def set_dedup_pairs(self, on=True):
+        """switches pair dedup on (before pair_overlap(), which then keeps the pairing of the resident reads) or off"""
+        _check(lib.drprg_hip_set_dedup_pairs(self._h, 1 if on else 0), self._h)
+
+    def dedup_pairs(self, key_bits=64):
+        """drops every resident pair (or orphan) that is identical, mate by mate, to one before it and maps the kept reads afresh (nothing
+        happens when no unit is dropped); returns the eight counts"""
+        out = (C.c_uint64 * 8)()
+        _check(lib.drprg_hip_dedup_pairs(self._h, int(key_bits), out), self._h)
+        return dict(zip(self.PAIR_DEDUP_COUNTS, (int(v) for v in out)))
+
+    def dedup_pairs_flags(self, n_reads):
+        """one byte per read of the sample as the last dedup_pairs() found it, 1 = kept (n_reads: how many it held)"""
+        flags = np.zeros(int(n_reads), dtype=np.uint8)
+        _check(lib.drprg_hip_dedup_pairs_flags(self._h, _ptr(flags), flags.size), self._h)
+        return flags
+
+    def dedup_pairs_info(self):
+        """the eight counts of the last dedup_pairs() and, under "levels", the 32 duplication levels"""
+        out = (C.c_uint64 * 40)()
+        _check(lib.drprg_hip_dedup_pairs_info(self._h, out), self._h)
+        d = dict(zip(self.PAIR_DEDUP_COUNTS, (int(v) for v in out[:8])))
+        d["levels"] = [int(v) for v in out[8:40]]
+        return d
+
+    def dedup_pairs_device(self, side_a, side_b, n_pairs, key_bits, d_keys, d_keep, d_copies, stream=None):
+        """the stage's kernels alone on two packed batches of n_pairs reads in device memory; a side is (d_words, d_offsets, n_bases,
+        d_npos or None, n_npos), addresses as integers.  d_keys: u64, d_keep: u8, d_copies: u32 per pair.  Returns the eight counts and "levels" """
+        out = (C.c_uint64 * 40)()
+        (wa, oa, ba, pa, na), (wb, ob, bb, pb, nb) = side_a, side_b
+        _check(lib.drprg_hip_dedup_pairs_device(self._h, wa, oa, int(ba), pa, int(na), wb, ob, int(bb), pb, int(nb), int(n_pairs), int(key_bits), d_keys,
+                                                d_keep, d_copies, out, stream), self._h)
+        d = dict(zip(self.PAIR_DEDUP_COUNTS, (int(v) for v in out[:8])))
+        d["levels"] = [int(v) for v in out[8:40]]
+        return d
+
     # ---- read filter (include/drprg_hip.h: drprg_hip_set_read_filter) ---------------------------
     @staticmethod
     def qual_milli(min_qual):

@@ -396,7 +396,8 @@ int drprg_hip_dedup_keys_device(drprg_hip_ctx* ctx, const void* d_words, const v
  *   whatever -t, the block boundaries and the input form.
  *   Limits.  A pair from a tandem repeat can qualify at a shift that is not its true one; largest-c keeps the cut smallest then.  Behind
  *   --trim-front or a 5' adapter cut, b loses the columns a no longer has.  Interleaved files, BAM mate flags, merging mates into one read,
- *   quality-weighted correction, pair-aware dedup and contexts over several devices are not served.  No claim about real samples is made.
+ *   quality-weighted correction and contexts over several devices are not served (pair-aware dedup: "duplicate pairs" below).  No claim
+ *   about real samples is made.
  *   drprg_hip_set_pair_overlap(ctx, min_overlap, error_milli, clip): the setting; all zero: off.  -EINVAL outside the ranges above.  While
  *     it is on, every block the resident set takes from drprg_hip_map_fastx is numbered by side (u32 per read, in the resident arenas), and
  *     drprg_hip_map_host* / drprg_hip_map_device* return -EINVAL.  Off, nothing of this exists: no numbers, no launch, no wait.
@@ -428,6 +429,57 @@ int drprg_hip_pair_overlap_info(drprg_hip_ctx* ctx, uint64_t out[12]);
 int drprg_hip_pair_overlap_device(drprg_hip_ctx* ctx, const void* d_words_a, const void* d_offsets_a, uint64_t n_bases_a, const void* d_npos_a, uint64_t n_npos_a,
     const void* d_words_b, const void* d_offsets_b, uint64_t n_bases_b, const void* d_npos_b, uint64_t n_npos_b, uint64_t n_pairs, void* d_shift, void* d_keep_a,
     void* d_keep_b, uint64_t out[12], void* hip_stream);
+/* ---- Duplicate pairs: exact duplicate read PAIRS dropped from the resident sample, behind "mate overlap".  THIS BUILD'S OWN RULE (what
+ * fastp -i -I --dedup, clumpify dedupe on pairs and Picard do in front of drprg: they judge the pair); nothing in pandora or drprg pins it.
+ * "duplicate reads" judges every read alone, and two different fragments that start at the same base of the same strand have identical
+ * first mates: only their second mates tell them apart.
+ *   Units.  Source pair s is the pair of "mate overlap": read s of side 1 and read s of side 2, counted as the files held them.  A_s is the
+ *   side-1 read of pair s as it lies in the resident sample when drprg_hip_pair_overlap is done, B_s the side-2 read: both behind every
+ *   ingest-time stage, the read-through cut and the clip.  A read that is not in the resident sample (an ingest-time stage dropped it) and
+ *   a read of no bases are the same thing: the empty read e.  An orphan is therefore the unit (a, e) or (e, b), and a pair whose second
+ *   mate the clip emptied is (a, e) too: it carries the same bases as that orphan and is treated as it.
+ *   Identity.  Two units are identical iff A_h is identical to A_s and B_h to B_s by the identity of "duplicate reads": the same length,
+ *   masked bases at the same places, the same letters elsewhere, case-insensitively, forward strand only.  e is identical to e and to
+ *   nothing else.  (a, b) and (b, a) are different units.
+ *   Selection.  Unit s is a duplicate iff at least one of A_s, B_s has bases and some h < s is identical to it.  Every read with bases of
+ *   a duplicate unit is dropped: both mates go, or neither.  A read of no bases is always kept, as under "duplicate reads".  Kept reads
+ *   stay where they were: side 1 in file order, then side 2.
+ *   Copies and levels.  Identity is an equivalence relation; a kept unit with bases is the first of its class, and its copies are the
+ *   size of that class.  levels[c-1], c = 1 .. 31, is the number of kept units with exactly c copies, levels[31] the number with 32 or more.
+ *   The key (part of the statement, never of the decision).  With ka, kb the content keys of "duplicate reads" (0 for e), fin and G as
+ *   there: U = fin(ka + G) + fin(kb + 2G) in 64-bit unsigned arithmetic.  The two constants keep (a, b) and (b, a) apart.  Equal keys
+ *   decide nothing.  Identity does.
+ *   Invariance.  The result depends on the two files' reads and the settings alone: not on -t, on the block boundaries of either side, on
+ *   the input form (ASCII, packed, BAM), or on key_bits.
+ *   Limits.  Forward orientation only: the same fragment sequenced from the other strand arrives as (b, a) and is not found.  Exact
+ *   identity only: one sequencing error in either mate keeps a copy.  There is no optical-distance rule.  Interleaved files, BAM mate
+ *   flags and contexts over several devices are not served, as for "mate overlap".
+ *   drprg_hip_set_dedup_pairs(ctx, on): the switch; set it before drprg_hip_pair_overlap.  While it is on, that call keeps the mate and
+ *     the source number of every resident read in device memory (8 bytes per read) until this stage, a reset or another compaction
+ *     releases them.  Off, nothing is kept and nothing is launched.  -EINVAL without a mate-overlap setting; switching that off switches
+ *     this off too.
+ *   drprg_hip_dedup_pairs(ctx, key_bits, out): the stage (csrc/pair_dedup.hip).  out[0..7] = units (source pairs), units with bases, units
+ *     with both mates (both have bases), units dropped, reads before, bases before, reads kept, bases kept.  key_bits as for
+ *     drprg_hip_dedup.  No unit dropped: nothing else happens.  Otherwise the kept reads are compacted and mapped afresh as
+ *     drprg_hip_dedup does it, and a following drprg_hip_subsample numbers the kept reads from 0.  -EINVAL for key_bits outside 1..64,
+ *     for a context over several devices, without the switch, without a drprg_hip_pair_overlap call on this sample, and for a sample
+ *     that drprg_hip_dedup, drprg_hip_subsample or an earlier drprg_hip_dedup_pairs has compacted since (the stage releases its record
+ *     when it is done, so a second call on one sample is refused); -ENODATA (-61) unless the sample is resident; -EOVERFLOW for 2^32
+ *     reads or pairs or more.  A refused or failed call leaves the context as it was.
+ *   drprg_hip_dedup_pairs_flags(ctx, flags, n): one byte per resident read, numbered before the call: 1 kept, 0 dropped; all ones when
+ *     nothing was dropped.  -EINVAL unless n is that call's out[4].
+ *   drprg_hip_dedup_pairs_info(ctx, out): the eight counts, then the 32 levels, of the last call since the last reset (all zero: none).
+ *   drprg_hip_dedup_pairs_device: the stage's kernels alone on two caller-owned packed batches of n_pairs reads each (unit s: read s of
+ *     either), the sides given as in drprg_hip_pair_overlap_device, under the stream rule of the other device entries.  d_keys:
+ *     u64[n_pairs], U; d_keep: u8[n_pairs], 0 for a duplicate unit; d_copies: u32[n_pairs], the copies of a kept unit with bases, else 0;
+ *     out: the eight counts (reads: 2 n_pairs), then the 32 levels.  Needs no setting.  -EOVERFLOW for 2^31 pairs or more. */
+int drprg_hip_set_dedup_pairs(drprg_hip_ctx* ctx, int on);
+int drprg_hip_dedup_pairs(drprg_hip_ctx* ctx, uint32_t key_bits, uint64_t out[8]);
+int drprg_hip_dedup_pairs_flags(drprg_hip_ctx* ctx, uint8_t* flags, uint64_t n);
+int drprg_hip_dedup_pairs_info(drprg_hip_ctx* ctx, uint64_t out[40]);
+int drprg_hip_dedup_pairs_device(drprg_hip_ctx* ctx, const void* d_words_a, const void* d_offsets_a, uint64_t n_bases_a, const void* d_npos_a, uint64_t n_npos_a,
+    const void* d_words_b, const void* d_offsets_b, uint64_t n_bases_b, const void* d_npos_b, uint64_t n_npos_b, uint64_t n_pairs, uint32_t key_bits, void* d_keys,
+    void* d_keep, void* d_copies, uint64_t out[40], void* hip_stream);
 /* ---- Read filter: reads dropped by length and mean quality on the device, as they arrive.  THIS BUILD'S OWN RULE, stated from memory of
  * what the filters nanopore workflows run in front of drprg compute (nanoq, chopper -q Q -l L, filtlong); neither pandora nor drprg has one.
  *   Settings, per context: min_len (0: no lower bound), max_len (0: no upper bound), min_qual_milli = Q * 1000 (0: no quality test).
@@ -730,8 +782,8 @@ int drprg_hip_complexity_info(drprg_hip_ctx* ctx, uint64_t out[4]);
 int drprg_hip_complexity_device(drprg_hip_ctx* ctx, const void* d_text, const void* d_words, const void* d_npos, uint64_t n_npos, const void* d_offsets,
     uint64_t n_reads, uint64_t n_bases, void* d_diff, void* d_flags, uint64_t out[2], void* hip_stream);
 /* ---- Read statistics: the QC record of a sample (--qc-json), counted on the device as the reads arrive.  THIS BUILD'S OWN RULE: the sums
- * fastp, NanoStat and nanoq report, before and after preparation.  Statistics only: no pass or fail verdict, no duplication estimate, no
- * adapter guess.
+ * fastp, NanoStat and nanoq report, before and after preparation.  Statistics only: no pass or fail verdict, no adapter guess (the
+ * duplication levels of a paired sample: "duplicate pairs" above, the report's "pair_dedup" entry).
  *   Setting, per context: mode 0 (off, the default), 1 (with qualities), 2 (without the three quality sections: --qc-no-qual).
  *   Two snapshots.  RAW: every read of every ingest block of drprg_hip_map_fastx as the file holds it, in front of the trim stage (BAM: read
  *   orientation, secondary and supplementary records skipped, as the ingest does).  PREPARED: exactly the reads and bases the block hands on
