@@ -10,7 +10,7 @@ HIPFLAGS := $(CXXFLAGS) --offload-arch=$(ARCH)
 SRC  := drprg_amd/csrc
 OBJD := build/obj
 HOST_SRCS := prg.cpp kmergraph.cpp index.cpp fastx.cpp genotype.cpp params.cpp denovo.cpp mapper.cpp read_prep.cpp resident.cpp capi.cpp capi_map.cpp capi_prep.cpp capi_reduce.cpp capi_genotype.cpp capi_tools.cpp vcfio.cpp bcfout.cpp annotate.cpp report_json.cpp qc_json.cpp ingest.cpp pgunzip.cpp rccl_dyn.cpp pack.cpp switches.cpp bam.cpp
-HIP_SRCS := read_stats.hip sketch_probe.hip sketch_wave.hip sketch_filter.hip candidates.hip read_cluster.hip cluster.hip anchor_scan.hip packed.hip covg_cut.hip bam_pack.hip subsample.hip read_qual.hip dedup.hip read_trim.hip adapter_trim.hip adapter_edit.hip decoy_screen.hip base_mask.hip poly_tail.hip read_complexity.hip pair_overlap.hip pair_dedup.hip
+HIP_SRCS := read_stats.hip sketch_probe.hip sketch_wave.hip sketch_filter.hip candidates.hip read_cluster.hip cluster.hip anchor_scan.hip packed.hip covg_cut.hip bam_pack.hip subsample.hip read_qual.hip dedup.hip read_trim.hip adapter_trim.hip adapter_edit.hip decoy_screen.hip base_mask.hip poly_tail.hip read_complexity.hip pair_overlap.hip pair_merge.hip pair_dedup.hip
 LIB  := drprg_amd/lib/libdrprg_hip.so
 OBJS := $(addprefix $(OBJD)/,$(HOST_SRCS:.cpp=.o)) $(addprefix $(OBJD)/,$(HIP_SRCS:.hip=.o))
 BIN  := drprg_amd/bin/pandora

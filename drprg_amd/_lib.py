@@ -106,6 +106,11 @@ SIGNATURES = {
     "drprg_hip_pair_overlap_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "drprg_hip_pair_overlap_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
                                                 C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "drprg_hip_set_pair_merge": (C.c_int, [C.c_void_p, C.c_int]),
+    "drprg_hip_pair_merge_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "drprg_hip_pair_merge_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
+                                              C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                              C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]),
     "drprg_hip_set_dedup_pairs": (C.c_int, [C.c_void_p, C.c_int]),
     "drprg_hip_dedup_pairs": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]),
     "drprg_hip_dedup_pairs_flags": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),

@@ -27,6 +27,7 @@ namespace dev {
 constexpr int BM_THREADS = 256;
 constexpr uint32_t BM_LANE_BASES = 64;
 constexpr uint32_t BM_TILE = BM_THREADS * BM_LANE_BASES; // 16384 bases per workgroup
+static_assert(BM_TILE == BASE_MASK_TILE, "kernels.h states the tile that other files count chunks by");
 constexpr uint32_t BM_MAX_QUAL = 93;
 
 uint32_t base_mask_tiles(uint64_t n_bases) { return (uint32_t)((n_bases + BM_TILE - 1) / BM_TILE); }

@@ -51,6 +51,9 @@ struct SampleState {
     bool mates_begun = false, pair_done = false;
     uint64_t pair_counts[12] = {};
     std::vector<int32_t> pair_shifts;
+    // mate merging: that call merged (drprg_hip_set_pair_merge was on), and its eight counts
+    bool pair_merge_done = false;
+    uint64_t pair_merge_counts[8] = {};
     // duplicate pairs: the last drprg_hip_dedup_pairs (its flags; counts is not used), and its forty words: eight counts, 32 levels
     Selection pair_dedup;
     uint64_t pair_dedup_words[40] = {};

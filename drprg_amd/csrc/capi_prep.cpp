@@ -449,6 +449,8 @@ int drprg_hip_write_qc_json(drprg_hip_ctx* ctx, const char* path, const char* sa
     const Selection& ss = ctx->sample.subsample;
     if (ctx->sample.pair_done) // (only when the stage ran: a report without --mate stays byte for byte what it was)
         r.stages.emplace_back("pair_overlap", std::vector<uint64_t>(ctx->sample.pair_counts, ctx->sample.pair_counts + 12));
+    if (ctx->sample.pair_merge_done) // (likewise: only when the stage ran with the switch on)
+        r.stages.emplace_back("pair_merge", std::vector<uint64_t>(ctx->sample.pair_merge_counts, ctx->sample.pair_merge_counts + 8));
     if (ctx->sample.pair_dedup.done) // (likewise: the eight counts, then the 32 duplication levels)
         r.stages.emplace_back("pair_dedup", std::vector<uint64_t>(ctx->sample.pair_dedup_words, ctx->sample.pair_dedup_words + 40));
     r.stages.emplace_back("dedup", dd.done ? std::vector<uint64_t>(dd.counts, dd.counts + 4) : std::vector<uint64_t>());
@@ -725,7 +727,8 @@ int drprg_hip_set_pair_overlap(drprg_hip_ctx* ctx, uint32_t min_overlap, uint32_
     }
     if (min_overlap < 8 || min_overlap > dev::PO_MAX_LEN) throw Error(DRPRG_EINVAL, "mate overlap: the smallest overlap is a whole number in 8 .. 1024");
     if (error_milli > 250) throw Error(DRPRG_EINVAL, "mate overlap: the share of differing columns is at most 0.25 (250 thousandths)");
-    ctx->pair = Mapper::PairSetting { min_overlap, error_milli, clip != 0 };
+    if (clip && ctx->pair.merge) throw Error(DRPRG_EINVAL, "mate overlap: mate merging is on (drprg_hip_set_pair_merge), and merging subsumes the clip");
+    ctx->pair = Mapper::PairSetting { min_overlap, error_milli, clip != 0, ctx->pair.merge };
     for (Mapper* m : mappers_of(ctx)) m->pair_record(true); // (from the next block on the resident set numbers its reads by side)
     API_END(ctx)
 }
@@ -753,12 +756,14 @@ int drprg_hip_pair_overlap(drprg_hip_ctx* ctx, uint64_t out[12])
                                   "needs both of its mates");
     refuse_unordered(ctx, m, "drprg_hip_pair_overlap");
     std::vector<int32_t> shifts;
-    uint64_t counts[dev::PO_WORDS];
-    m.pair_overlap_kept(ctx->pair, shifts, counts);
+    uint64_t counts[dev::PO_WORDS], merged[dev::PM_WORDS];
+    m.pair_overlap_kept(ctx->pair, shifts, counts, ctx->pair.merge ? merged : nullptr);
     SampleState& s = ctx->sample;
     s.pair_done = true;
     s.pair_shifts = std::move(shifts);
     for (int i = 0; i < dev::PO_WORDS; ++i) out[i] = s.pair_counts[i] = counts[i];
+    s.pair_merge_done = ctx->pair.merge;
+    for (int i = 0; i < dev::PM_WORDS; ++i) s.pair_merge_counts[i] = ctx->pair.merge ? merged[i] : 0;
     if (counts[dev::PO_BASES_KEPT] != counts[dev::PO_BASES_BEFORE]) { // the context now stands for the cut reads
         s.host_coverage_valid = false;
         s.total_bases = counts[dev::PO_BASES_KEPT];
@@ -797,6 +802,39 @@ int drprg_hip_pair_overlap_device(drprg_hip_ctx* ctx, const void* d_words_a, con
     const Mapper::PairSide a { (const uint32_t*)d_words_a, (const uint64_t*)d_offsets_a, n_bases_a, (const uint64_t*)d_npos_a, n_npos_a };
     const Mapper::PairSide b { (const uint32_t*)d_words_b, (const uint64_t*)d_offsets_b, n_bases_b, (const uint64_t*)d_npos_b, n_npos_b };
     m.pair_overlap_device(ctx->pair, a, b, n_pairs, (int32_t*)d_shift, (uint64_t*)d_keep_a, (uint64_t*)d_keep_b, out, (hipStream_t)hip_stream);
+    API_END(ctx)
+}
+
+// ---- mate merging (the rule: include/drprg_hip.h "mate merging") -------------------------------------------------------------------
+int drprg_hip_set_pair_merge(drprg_hip_ctx* ctx, int on)
+{
+    API_BEGIN(ctx)
+    if (on && !ctx->pair.on()) throw Error(DRPRG_EINVAL, "drprg_hip_set_pair_merge: no mate-overlap setting (drprg_hip_set_pair_overlap): without mates there is nothing to merge");
+    if (on && ctx->pair.clip) throw Error(DRPRG_EINVAL, "drprg_hip_set_pair_merge: the mate-overlap setting clips, and merging subsumes the clip");
+    ctx->pair.merge = on != 0;
+    API_END(ctx)
+}
+
+int drprg_hip_pair_merge_info(drprg_hip_ctx* ctx, uint64_t out[8])
+{
+    API_BEGIN(ctx)
+    if (!out) throw Error(DRPRG_EINVAL, "null output");
+    static_assert(dev::PM_WORDS == 8, "drprg_hip_pair_merge_info writes eight counts");
+    for (int i = 0; i < 8; ++i) out[i] = ctx->sample.pair_merge_counts[i]; // (all zero before the stage has merged)
+    API_END(ctx)
+}
+
+int drprg_hip_pair_merge_device(drprg_hip_ctx* ctx, const void* d_words_a, const void* d_offsets_a, uint64_t n_bases_a, const void* d_npos_a, uint64_t n_npos_a,
+    const void* d_words_b, const void* d_offsets_b, uint64_t n_bases_b, const void* d_npos_b, uint64_t n_npos_b, uint64_t n_pairs, void* d_shift, void* d_out_offsets,
+    void* d_out_words, uint64_t cap_words, void* d_out_npos, uint64_t cap_npos, uint64_t* n_out_npos, uint64_t out12[12], uint64_t out8[8], void* hip_stream)
+{
+    API_BEGIN(ctx)
+    Mapper& m = need_mapper(ctx);
+    if (!out12 || !out8 || !n_out_npos) throw Error(DRPRG_EINVAL, "null output");
+    const Mapper::PairSide a { (const uint32_t*)d_words_a, (const uint64_t*)d_offsets_a, n_bases_a, (const uint64_t*)d_npos_a, n_npos_a };
+    const Mapper::PairSide b { (const uint32_t*)d_words_b, (const uint64_t*)d_offsets_b, n_bases_b, (const uint64_t*)d_npos_b, n_npos_b };
+    m.pair_merge_device(ctx->pair, a, b, n_pairs, (int32_t*)d_shift, (uint64_t*)d_out_offsets, (uint32_t*)d_out_words, cap_words, (uint64_t*)d_out_npos, cap_npos,
+        n_out_npos, out12, out8, (hipStream_t)hip_stream);
     API_END(ctx)
 }
 

@@ -119,7 +119,7 @@ void usage()
         "              [--adapter SEQ]... [--adapter-error E] [--adapter-min-overlap O] [--adapter-indels] [--front-adapter SEQ]...\n"
         "              [--poly-tail LETTERS [--poly-min-len M]] [--min-complexity P] [--qc-json FILE [--qc-no-qual]]\n"
         "              [--mask-qual Q] [--decoy FASTA]... [--decoy-k K] [--decoy-min-frac F] [--decoy-min-kmers M]\n"
-        "              [--mate FILE [--pair-min-overlap O] [--pair-error E] [--pair-clip-overlap] [--dedup-pairs]]\n"
+        "              [--mate FILE [--pair-min-overlap O] [--pair-error E] [--pair-clip-overlap | --pair-merge] [--dedup-pairs]]\n"
         "--poly-tail LETTERS (letters of ACGT, e.g. G or ACGT), --poly-min-len M (2 to 255, default 10): every read loses its longest suffix of\n"
         "              at least M bases that begins with one of the letters and holds at most min(n / 8, 5) other bases -- the tails two-colour\n"
         "              instruments (NextSeq, NovaSeq) leave when a cluster goes dark, which carry HIGH qualities.  On the device, behind --trim-*\n"
@@ -257,6 +257,7 @@ int main(int argc, char** argv)
         else if (a == "--dedup") dedup = true;
         else if (a == "--mate") pair.mate = need(i);
         else if (a == "--pair-clip-overlap") pair.clip = true;
+        else if (a == "--pair-merge") pair.merge = true;
         else if (a == "--dedup-pairs") pair.dedup_pairs = true;
         else if (a == "--pair-min-overlap") {
             const std::string e = pair.set_overlap(need(i));
@@ -491,6 +492,11 @@ int main(int argc, char** argv)
         uint64_t out[12] = {};
         if (int rc = drprg_hip_pair_overlap(ctx, out)) die(std::string("--mate: ") + drprg_hip_last_error(ctx), -rc);
         if (verbose) drprg::PairArgs::report(out, [](const char* line) { std::fprintf(stderr, "[drprg-hip +%.3fs] %s\n", since_start(), line); });
+        if (pair.merge && verbose) { // (include/drprg_hip.h "mate merging")
+            uint64_t mg[8] = {};
+            if (int rc = drprg_hip_pair_merge_info(ctx, mg)) die(std::string("--pair-merge: ") + drprg_hip_last_error(ctx), -rc);
+            drprg::PairArgs::report_merge(mg, [](const char* line) { std::fprintf(stderr, "[drprg-hip +%.3fs] %s\n", since_start(), line); });
+        }
     }
     if (pair.dedup_pairs) { // duplicate pairs dropped from the resident sample (include/drprg_hip.h "duplicate pairs")
         uint64_t out[8] = {};

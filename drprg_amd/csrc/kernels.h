@@ -433,6 +433,8 @@ hipError_t launch_dedup_select(const DedupSelect& s, hipStream_t stream);
 // launch_pair_overlap: shift[i] (i < n1; i32[n1]) = the chosen shift of read i's pair, PO_NO_SHIFT when none qualifies, PO_NOT_JUDGED when
 // the pair is not judged; keep[i] (u64[n]) = the bases read i keeps; counts (PO_WORDS zeroed device words) receive the pair's counts (the
 // caller sets PO_PAIRS and PO_READS).  *err (zeroed by the caller) is set by a mate number that is out of range or on the read's own side.
+// merge (mate merging, pair_merge.hip; not beside clip): the counts are the clip's, every b of a pair with a chosen shift counts as
+// emptied, and keep[] holds the NEW lengths: the insert for such a pair's a, 0 for its b.
 constexpr uint32_t PO_MAX_LEN = 1024;
 constexpr int32_t PO_NO_SHIFT = INT32_MIN, PO_NOT_JUDGED = INT32_MIN + 1;
 enum {
@@ -443,7 +445,7 @@ struct PairOverlapArgs {
     const DedupLoc* loc;
     const uint32_t* mate;
     uint64_t n, n1;
-    uint32_t min_overlap, error_milli, clip;
+    uint32_t min_overlap, error_milli, clip, merge;
     int32_t* shift;
     uint64_t* keep;
     unsigned long long* counts;
@@ -457,6 +459,42 @@ hipError_t launch_pair_overlap(const PairOverlapArgs& a, hipStream_t stream);
 // noff = the exclusive scan of keep over n_reads + 1 entries (entry n_reads of keep is read, not used): a block's new offsets.  temp:
 // read_trim_temp_bytes(n_reads) bytes.
 hipError_t launch_pair_offsets(const uint64_t* keep, uint64_t n_reads, uint64_t* noff, void* temp, size_t temp_bytes, hipStream_t stream);
+
+// pair_merge.hip: overlapping mates merged into one read (the rule: include/drprg_hip.h "mate merging").  Behind launch_pair_overlap with
+// merge set, on the same loc, mate, n, n1 and its shift[].  One launch places the side-1 reads [first, first + n_reads) at the base offsets
+// noff[0 .. n_reads] of one destination of new_bases bases (noff from launch_pair_offsets over keep + first): every pair with a chosen shift as
+// its merged read M; with `all` set every other read too, as the first noff[j + 1] - noff[j] bases it holds.  The destination is packed
+// (words: ZEROED u32[ceil(new_bases / 16)] and what the caller wants behind them; nbits: the bitmap of M's unknown bases as
+// launch_mark_npos lays it out, ZEROED u16[ceil(new_bases / 16) + 8], 8-byte aligned) or text (upper-case ACGT and N; `all` must be 0:
+// the bytes of the other reads are the caller's to copy).  An unknown base of M carries letter 3 in the words, as an N does.  counts:
+// PM_WORDS device words (zeroed by the caller once; launches add, PM_LONGEST is a maximum).  *err is set when shift, mate, loc and noff do
+// not fit each other; such a read writes nothing, and nothing is written out of bounds.
+enum { PM_MERGED = 0, PM_BOTH = 1, PM_AGREE = 2, PM_DISAGREE = 3, PM_FILLED = 4, PM_UNKNOWN_BOTH = 5, PM_BASES = 6, PM_LONGEST = 7, PM_WORDS = 8 };
+struct PairMergeArgs {
+    const DedupLoc* loc;
+    const uint32_t* mate;
+    const int32_t* shift;
+    uint64_t n, n1, first, n_reads;
+    const uint64_t* noff;
+    uint64_t new_bases;
+    uint32_t* words;
+    uint16_t* nbits;
+    uint8_t* text;
+    uint32_t all;
+    unsigned long long* counts;
+    uint32_t* err;
+};
+hipError_t launch_pair_merge(const PairMergeArgs& a, hipStream_t stream);
+// len[i] = keep[i] for a side-1 read i with a chosen shift, else 0 (n1 entries and one zero behind them: what launch_pair_offsets scans
+// for a batch in which an unmerged pair is a read of no bases)
+hipError_t launch_pair_merge_lengths(const int32_t* shift, const uint64_t* keep, uint64_t n1, uint64_t* len, hipStream_t stream);
+// ASCII blocks: table[j] copies the bytes of the block's read j (first + j of the sample) to noff[j] -- keep[first + j] of them, none for
+// a read with a chosen shift, whose room the merge kernel fills.  *err as launch_read_trim_fill sets it.
+hipError_t launch_pair_merge_table(const uint8_t* bases, const uint64_t* offsets, uint64_t n_reads, uint64_t n_bases, uint64_t first, uint64_t n1, const int32_t* shift,
+    const uint64_t* keep, const uint64_t* noff, uint64_t new_bases, GatherEntry* table, uint32_t* err, hipStream_t stream);
+// the set bits of a bitmap below n_bases: per 16 384 bases into chunk_count (base_mask_tiles(n_bases) words: what launch_base_mask_emit
+// scans) and all of them ADDED to *total
+hipError_t launch_pair_merge_bits_count(const uint16_t* nbits, uint64_t n_bases, uint32_t* chunk_count, unsigned long long* total, hipStream_t stream);
 
 // pair_dedup.hip: duplicate pairs (the rule: include/drprg_hip.h "duplicate pairs").  The n resident reads (n < 2^32) are numbered as
 // launch_pair_overlap numbers them (side 1 in [0, n1)); loc as launch_dedup_loc fills it and rkey as launch_dedup_keys does (both n
@@ -717,6 +755,7 @@ struct BaseMaskArgs {
     uint32_t *read_flag, *chunk_count;
     unsigned long long* work;
 };
+constexpr uint32_t BASE_MASK_TILE = 16384; // the bases under one entry of chunk_count: one workgroup of launch_base_mask and of its emit
 uint32_t base_mask_tiles(uint64_t n_bases);
 // timer: around base_mask_kernel
 hipError_t launch_base_mask(const BaseMaskArgs& a, hipStream_t stream, KernelTimer timer = {});

@@ -323,6 +323,7 @@ public:
     struct PairSetting {
         uint32_t min_overlap = 0, error_milli = 0;
         bool clip = false;
+        bool merge = false; // mate merging (drprg_hip_set_pair_merge; never beside clip)
         bool on() const { return min_overlap != 0; }
     };
     // one side of the caller's pairs: a packed batch of n_pairs reads
@@ -342,12 +343,20 @@ public:
     // dropped either way.  A call that fails leaves the sample as it was.
     void pair_record(bool on) { pair_.record = on; }
     void begin_mates();
-    void pair_overlap_kept(const PairSetting& set, std::vector<int32_t>& shifts, uint64_t counts[dev::PO_WORDS]);
+    // set.merge (the rule: include/drprg_hip.h "mate merging"; pair_merge.hip): every pair with a chosen shift becomes its merged read in a's
+    // place and a read of no bases in b's; no pair has a chosen shift: nothing else happens.  merged: the PM_WORDS counts (null without merge).
+    void pair_overlap_kept(const PairSetting& set, std::vector<int32_t>& shifts, uint64_t counts[dev::PO_WORDS], uint64_t* merged = nullptr);
     // The two pair kernels alone on the caller's packed batches (drprg_hip_pair_overlap_device): pair s is (read s of a, read s of b).
     // d_shift[s] the chosen shift (PO_NO_SHIFT, PO_NOT_JUDGED), d_keep_a[s] / d_keep_b[s] the bases either mate keeps, counts the PO_WORDS
     // counters.  Synchronises `stream`.
     void pair_overlap_device(const PairSetting& set, const PairSide& a, const PairSide& b, uint64_t n_pairs, int32_t* d_shift, uint64_t* d_keep_a, uint64_t* d_keep_b,
         uint64_t counts[dev::PO_WORDS], hipStream_t stream);
+    // The overlap kernel and the merge kernel alone on the caller's packed batches (drprg_hip_pair_merge_device): a packed batch of n_pairs
+    // reads, the merged read of a pair with a chosen shift and a read of no bases for every other.  d_out_offsets: u64[n_pairs + 1];
+    // d_out_words / d_out_npos: room for cap_words words and cap_npos positions (too little: DRPRG_EOVERFLOW, nothing is written beyond
+    // them); *n_out_npos: the length of the ascending list.  Synchronises `stream`.
+    void pair_merge_device(const PairSetting& set, const PairSide& a, const PairSide& b, uint64_t n_pairs, int32_t* d_shift, uint64_t* d_out_offsets, uint32_t* d_out_words,
+        uint64_t cap_words, uint64_t* d_out_npos, uint64_t cap_npos, uint64_t* n_out_npos, uint64_t counts[dev::PO_WORDS], uint64_t merged[dev::PM_WORDS], hipStream_t stream);
 
     // Duplicate pairs dropped from the resident sample (the rule: include/drprg_hip.h "duplicate pairs"; pair_dedup.hip).
     // pair_dedup_record(true): from now on pair_overlap_kept keeps, as device buffers of pair_, the mate and the source number of every
@@ -765,6 +774,7 @@ private:
         // (npos null without any) -- or nothing, when the cap or the device says no
         std::optional<BlockRoom> take_block(uint64_t payload_bytes, uint64_t n_reads, uint64_t n_npos);
         void add(const DeviceBatch& b, uint64_t n_reads) { kept.push_back(b); first.push_back(seen); seen += n_reads; }
+        uint64_t* take_list(uint64_t n_npos) { return static_cast<uint64_t*>(arena_take(n_npos * sizeof(uint64_t))); } // (mate merging: a block's list, sized behind its words)
         uint32_t* take_numbers(uint64_t n_reads) { return static_cast<uint32_t*>(arena_take(n_reads * sizeof(uint32_t))); } // (mate overlap: a block's source numbers)
         void count_empty(uint64_t n) { seen += n; }
         // everything but the cap goes; the caller has made sure that nothing on the device reads the blocks any more

@@ -1,5 +1,6 @@
 // pair_args.h -- --mate FILE, --pair-min-overlap O, --pair-error E and --pair-clip-overlap as both executables take them
-// (include/drprg_hip.h "mate overlap"), and --dedup-pairs behind them (include/drprg_hip.h "duplicate pairs").
+// (include/drprg_hip.h "mate overlap"), --pair-merge beside them (include/drprg_hip.h "mate merging") and --dedup-pairs behind them
+// (include/drprg_hip.h "duplicate pairs").
 #pragma once
 #include "../../include/drprg_hip.h"
 #include <cstdio>
@@ -13,6 +14,7 @@ struct PairArgs {
     uint32_t min_overlap = 30, error_milli = 50;
     bool clip = false, overlap_given = false, error_given = false;
     bool dedup_pairs = false; // --dedup-pairs
+    bool merge = false;       // --pair-merge
     bool any() const { return !mate.empty(); }
     // each returns what is wrong with its value (a usage error: exit 2), or nothing
     std::string set_overlap(const char* v)
@@ -54,6 +56,8 @@ struct PairArgs {
         if (mate.empty() && overlap_given) return "--pair-min-overlap belongs to --mate";
         if (mate.empty() && error_given) return "--pair-error belongs to --mate";
         if (mate.empty() && clip) return "--pair-clip-overlap belongs to --mate";
+        if (mate.empty() && merge) return "--pair-merge belongs to --mate: without the second mates there is nothing to merge";
+        if (merge && clip) return "--pair-merge and --pair-clip-overlap are alternatives: merging subsumes the clip";
         if (!mate.empty() && max_covg < 0xFFFFFFFFull)
             return "--mate and --max-covg are alternatives: the prefix cap would take the first file alone, and a pair needs both of its mates "
                    "(--subsample-covg cuts a paired sample to a depth)";
@@ -63,6 +67,8 @@ struct PairArgs {
     {
         if (!any()) return 0;
         if (int rc = drprg_hip_set_pair_overlap(ctx, min_overlap, error_milli, clip ? 1 : 0)) return rc;
+        if (merge) // (off: the entry is never called)
+            if (int rc = drprg_hip_set_pair_merge(ctx, 1)) return rc;
         return dedup_pairs ? drprg_hip_set_dedup_pairs(ctx, 1) : 0; // (off: the entry is never called)
     }
     static const char* usage()
@@ -74,6 +80,9 @@ struct PairArgs {
                "              are cut off both mates.  No adapter sequence is needed.  --pair-clip-overlap also cuts the second mate down to what\n"
                "              the first does not cover, so that every base of the molecule counts once.  A read whose mate an earlier stage dropped\n"
                "              passes unchanged.  Runs in front of --dedup and --subsample-covg; needs the reads resident (DRPRG_HIP_KEEP_READS_GB).\n"
+               "  --pair-merge (beside --mate, instead of --pair-clip-overlap): every pair with such a shift becomes ONE read, the insert from the first\n"
+               "              mate's first base to the second mate's last, in the first file's place; the second mate stays as a read of no bases.  Where\n"
+               "              both mates read a column and disagree the base becomes unknown (N); a known base fills an unknown one.  No quality is used.\n"
                "  --dedup-pairs (beside --mate, instead of --dedup): behind the overlap stage and in front of --subsample-covg every pair whose two mates\n"
                "              are both identical to the mates of a pair before it in the files -- same lengths, same letters without case, unknown bases\n"
                "              at the same places; a mate that was dropped or emptied counts as no bases, so an orphan is judged against orphans -- is\n"
@@ -89,6 +98,16 @@ struct PairArgs {
                                          "bases_cut=%llu bases_clipped=%llu reads_emptied=%llu reads=%llu bases_before=%llu bases_kept=%llu",
             (unsigned long long)c[0], (unsigned long long)c[1], (unsigned long long)c[2], (unsigned long long)c[3], (unsigned long long)c[4], (unsigned long long)c[5],
             (unsigned long long)c[6], (unsigned long long)c[7], (unsigned long long)c[8], (unsigned long long)c[9], (unsigned long long)c[10], (unsigned long long)c[11]);
+        say(line);
+    }
+    // -v: the eight counts of --pair-merge as one line, through `say`
+    template <typename Say> static void report_merge(const uint64_t c[8], Say&& say)
+    {
+        char line[512];
+        std::snprintf(line, sizeof line, "mate merging: pairs_merged=%llu columns_both=%llu columns_agreeing=%llu columns_disagreeing=%llu columns_filled=%llu "
+                                         "columns_unknown=%llu bases_merged=%llu longest_merged=%llu",
+            (unsigned long long)c[0], (unsigned long long)c[1], (unsigned long long)c[2], (unsigned long long)c[3], (unsigned long long)c[4], (unsigned long long)c[5],
+            (unsigned long long)c[6], (unsigned long long)c[7]);
         say(line);
     }
     // -v: the eight counts of --dedup-pairs and the duplication rate as one line, through `say`

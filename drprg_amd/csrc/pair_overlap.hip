@@ -8,7 +8,8 @@
 // Overlap.  pair_overlap_kernel: one wave per PAIR, that is per side-1 read: it judges the pair when the mate is present, else it passes its
 // read on (an orphan, a read of no bases); pair_side2_kernel, one thread per side-2 read, passes on the side-2 reads no wave writes.  The
 // waves of a workgroup share nothing but the twelve counters, so they meet at two barriers only (the counters zeroed, the counters added);
-// between the stages of one pair a wave waits for its own LDS writes alone.  A judged pair is staged once in LDS:
+// between the stages of one pair a wave waits for its own LDS writes alone.  A judged pair is staged once in LDS (pair_stage.h, which
+// pair_merge.hip stages its pairs with too):
 // a's read-aligned 16-base words with a mask of its known bases (one bit per base, at the even bit of its letter: the same funnel shift
 // moves letters and mask), and B = the reverse complement of b in the same form (b's words staged first, then every word of B is one
 // window of b taken backwards: a bit reversal, the two bits of every letter swapped back, the complement an XOR).  Bases outside a read
@@ -25,6 +26,7 @@
 // Every index that comes from device data (mate numbers, where a read lies) is what the caller built from its own blocks; a mate number
 // that is out of range or on the read's own side sets the error word and the read passes unchanged.
 #include "device_common.h"
+#include "pair_stage.h"
 #include <rocprim/device/device_scan.hpp>
 
 namespace drprg {
@@ -32,45 +34,6 @@ namespace dev {
 
 constexpr int PO_THREADS = 256;
 constexpr int PO_WAVES = PO_THREADS / 64;
-constexpr uint32_t PO_ROW = PO_MAX_LEN / 16 + 4; // words of one staged row: 64 of a mate, zero words around them
-enum { PO_A = 0, PO_KA = 1, PO_B = 2, PO_KB = 3, PO_T = 4, PO_KT = 5, PO_ROWS = 6 };
-
-// bit t of m (m < 2^16) -> bit 2t
-__device__ inline uint32_t po_even(uint32_t m)
-{
-    m = (m | m << 8) & 0x00FF00FFu;
-    m = (m | m << 4) & 0x0F0F0F0Fu;
-    m = (m | m << 2) & 0x33333333u;
-    m = (m | m << 1) & 0x55555555u;
-    return m;
-}
-
-// bits [shift, shift + 32) of hi:lo (shift: 0..30): one v_alignbit_b32, where the 64-bit shift is two slower instructions
-__device__ inline uint32_t po_funnel(uint32_t lo, uint32_t hi, uint32_t shift) { return __builtin_amdgcn_alignbit(hi, lo, shift); }
-
-// word j of the read at l (16 j < l.len): its letters (those behind the read's end are not defined) and the mask of its known bases.  The
-// second batch word is touched only when the bases reach into it, as dd_read_word does.
-__device__ inline void po_read_word(const DedupLoc& l, uint32_t j, uint32_t& letters, uint32_t& known)
-{
-    const uint64_t at = l.start + 16ull * j;
-    const uint32_t n = (uint32_t)(l.len - 16ull * j < 16 ? l.len - 16ull * j : 16);
-    const uint64_t w = at >> 4;
-    const uint32_t phase = (uint32_t)(at & 15u);
-    const bool two = phase + n > 16;
-    const uint32_t lo = l.words[w], hi = two ? l.words[w + 1] : 0u;
-    const uint32_t mlo = l.bits ? l.bits[w] : 0u, mhi = l.bits && two ? l.bits[w + 1] : 0u;
-    letters = po_funnel(lo, hi, 2 * phase);
-    const uint32_t m = ((mhi << 16 | mlo) >> phase) & 0xFFFFu;
-    known = po_even(~m & (n < 16 ? (1u << n) - 1u : 0xFFFFu));
-}
-
-// a wave's own LDS writes before its reads of what other lanes wrote: no other wave touches its rows
-__device__ __forceinline__ void po_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 __global__ __launch_bounds__(PO_THREADS) void pair_overlap_kernel(PairOverlapArgs a)
 {
@@ -106,34 +69,8 @@ __global__ __launch_bounds__(PO_THREADS) void pair_overlap_kernel(PairOverlapArg
         }
     }
     const uint32_t La = judged ? (uint32_t)me.len : 0, Lb = judged ? (uint32_t)other.len : 0;
-    const uint32_t nwa = (La + 15) >> 4, nwb = (Lb + 15) >> 4;
 
-    // ---- a and b as they lie (b one word up: the windows of B reach 15 bases in front of it) ----
-    if (judged) {
-        for (uint32_t k = lane; k < PO_ROW; k += 64) {
-            uint32_t v = 0, m = 0, bv = 0, bm = 0;
-            if (k < nwa) po_read_word(me, k, v, m);
-            if (k >= 1 && k - 1 < nwb) po_read_word(other, k - 1, bv, bm);
-            s[PO_A][k] = v; s[PO_KA][k] = m;
-            s[PO_T][k] = bv; s[PO_KT][k] = bm;
-        }
-    }
-    po_wave_sync();
-    // ---- B[16 k + f] = complement(b[Lb - 1 - 16 k - f]): the window of b that ends at p = Lb - 1 - 16 k, backwards ----
-    if (judged) {
-        for (uint32_t k = lane; k < PO_ROW; k += 64) {
-            uint32_t v = 0, m = 0;
-            if (k < nwb) {
-                const uint32_t at = Lb - 16 * k; // (p - 15) + 16: where the window starts in the row (1 .. 1024)
-                const uint32_t w = at >> 4, sh = 2 * (at & 15u);
-                v = __brev(po_funnel(s[PO_T][w], s[PO_T][w + 1], sh));
-                v = (((v >> 1) & 0x55555555u) | ((v & 0x55555555u) << 1)) ^ 0xAAAAAAAAu; // letters: A 0, C 1, T 2, G 3 -- the complement flips bit 1
-                m = __brev(po_funnel(s[PO_KT][w], s[PO_KT][w + 1], sh)) >> 1;
-            }
-            s[PO_B][k] = v; s[PO_KB][k] = m;
-        }
-    }
-    po_wave_sync();
+    po_stage_rows(s, me, other, judged, lane); // (pair_stage.h)
     // ---- the shifts ----
     unsigned long long best = 0;
     if (judged) {
@@ -191,12 +128,16 @@ __global__ __launch_bounds__(PO_THREADS) void pair_overlap_kernel(PairOverlapArg
                 const uint32_t ins = (uint32_t)((int32_t)Lb + shift); // 1 .. La + Lb - 1
                 ka = min(La, ins);
                 const uint32_t rtb = min(Lb, ins);
-                kb = a.clip ? (ins > La ? ins - La : 0u) : rtb;
+                kb = a.clip || a.merge ? (ins > La ? ins - La : 0u) : rtb;
                 atomicAdd(&s_cnt[PO_OVERLAPPING], 1ull);
                 if (ka < La || rtb < Lb) atomicAdd(&s_cnt[PO_READ_THROUGH], 1ull);
                 if (La - ka + Lb - rtb) atomicAdd(&s_cnt[PO_BASES_CUT], (unsigned long long)(La - ka + Lb - rtb));
                 if (rtb - kb) atomicAdd(&s_cnt[PO_BASES_CLIPPED], (unsigned long long)(rtb - kb));
-                if (kb == 0) atomicAdd(&s_cnt[PO_READS_EMPTIED], 1ull); // (ka >= 1: ins >= 1)
+                if (kb == 0 || a.merge) atomicAdd(&s_cnt[PO_READS_EMPTIED], 1ull); // (ka >= 1: ins >= 1)
+                if (a.merge) { // mate merging: the clip's counts; a's place takes the merged read of `ins` bases (pair_merge.hip), b none
+                    ka = ins;
+                    kb = 0;
+                }
             }
             a.keep[i] = ka;
             a.keep[mt] = kb;

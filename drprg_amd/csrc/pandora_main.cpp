@@ -91,7 +91,7 @@ void usage()
         "  pandora index    [-t N] [-w W] [-k K] <prg>\n"
         "  pandora map      [--genotype] [--local] [--gt-conf X] [-v] [-o DIR] [-g SIZE] [--max-covg N | --subsample-covg D [--seed S]]\n"
         "                   [--dedup] [--min-read-len L] [--max-read-len L] [--min-read-qual Q]\n"
-        "                   [--mate FILE [--pair-min-overlap O] [--pair-error E] [--pair-clip-overlap] [--dedup-pairs]]\n"
+        "                   [--mate FILE [--pair-min-overlap O] [--pair-error E] [--pair-clip-overlap | --pair-merge] [--dedup-pairs]]\n"
         "                   [--trim-front N] [--trim-tail N] [--trim-qual Q [--trim-window W]]\n"
         "                   [--adapter SEQ]... [--adapter-error E] [--adapter-min-overlap O] [--adapter-indels] [--front-adapter SEQ]...\n"
         "                   [--poly-tail LETTERS [--poly-min-len M]] [--min-complexity P] [--qc-json FILE [--qc-no-qual]]\n"
@@ -262,6 +262,7 @@ Args parse(int argc, char** argv)
         else if (s == "--dedup") a.dedup = true;
         else if (s == "--mate") a.pair.mate = need(i);
         else if (s == "--pair-clip-overlap") a.pair.clip = true;
+        else if (s == "--pair-merge") a.pair.merge = true;
         else if (s == "--dedup-pairs") a.pair.dedup_pairs = true;
         else if (s == "--pair-min-overlap") {
             const std::string e = a.pair.set_overlap(need(i));
@@ -397,7 +398,7 @@ std::string run_tag(const Args& a, const std::string& reads)
         + (a.subsample ? "|S" + std::to_string(a.subsample_covg) + "/" + std::to_string((unsigned long long)a.seed) : std::string())
         + (a.dedup ? std::string("|D") : std::string())
         + (a.pair.any() ? "|" + stamp(a.pair.mate) + "|M" + std::to_string(a.pair.min_overlap) + "/" + std::to_string(a.pair.error_milli) + "/"
-                  + std::to_string((int)a.pair.clip) + (a.pair.dedup_pairs ? "/P" : "")
+                  + std::to_string((int)a.pair.clip) + (a.pair.merge ? "/G" : "") + (a.pair.dedup_pairs ? "/P" : "")
                         : std::string())
         + (a.min_read_len || a.max_read_len || a.min_read_qual_milli ? "|F" + std::to_string((unsigned long long)a.min_read_len) + "/"
                   + std::to_string((unsigned long long)a.max_read_len) + "/" + std::to_string(a.min_read_qual_milli)
@@ -439,6 +440,11 @@ void map_reads(drprg_hip_ctx* ctx, const Args& a, const std::string& reads)
     uint64_t out[12] = {};
     if (int rc = drprg_hip_pair_overlap(ctx, out)) die(std::string("--mate: ") + drprg_hip_last_error(ctx), -rc);
     if (a.verbose) drprg::PairArgs::report(out, [](const char* line) { std::printf("[pandora-hip] %s\n", line); });
+    if (a.pair.merge && a.verbose) {
+        uint64_t mg[8] = {};
+        if (int rc = drprg_hip_pair_merge_info(ctx, mg)) die(std::string("--pair-merge: ") + drprg_hip_last_error(ctx), -rc);
+        drprg::PairArgs::report_merge(mg, [](const char* line) { std::printf("[pandora-hip] %s\n", line); });
+    }
     if (!a.pair.dedup_pairs) return;
     uint64_t dd[8] = {};
     if (int rc = drprg_hip_dedup_pairs(ctx, 64, dd)) die(std::string("--dedup-pairs: ") + drprg_hip_last_error(ctx), -rc);

@@ -26,7 +26,7 @@ struct QcArgs {
                "              the reads as the file holds them (raw) and as they are handed to mapping (prepared: behind every --trim-*, --adapter,\n"
                "              --poly-tail, --mask-qual, --min/max-read-*, --min-complexity, --decoy and --max-covg; in front of --dedup and\n"
                "              --subsample-covg), with every stage's counters.  Statistics only: no verdict, no adapter guess (duplication\n"
-               "              levels: --dedup-pairs).  Needs qualities (FASTA is an error) unless --qc-no-qual leaves the three quality sections out.\n";
+               "              levels: --dedup-pairs; merged pairs: --pair-merge).  Needs qualities (FASTA is an error) unless --qc-no-qual leaves the three quality sections out.\n";
     }
     // -v: one line per snapshot, through `say` (a printf-like function of the executable with its own prefix)
     template <typename Say> void report(drprg_hip_ctx* ctx, Say&& say) const

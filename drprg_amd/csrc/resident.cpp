@@ -408,8 +408,11 @@ void Mapper::begin_mates()
     pair_.n1 = resident_.seen;
 }
 
-void Mapper::pair_overlap_kept(const PairSetting& set, std::vector<int32_t>& shifts, uint64_t counts[dev::PO_WORDS])
+void Mapper::pair_overlap_kept(const PairSetting& set, std::vector<int32_t>& shifts, uint64_t counts[dev::PO_WORDS], uint64_t* merged)
 {
+    if (set.merge && (set.clip || !merged)) throw Error(DRPRG_EINVAL, "mate merging: not beside the clip (drprg_hip_set_pair_merge)");
+    if (merged)
+        for (int i = 0; i < dev::PM_WORDS; ++i) merged[i] = 0;
     std::vector<uint8_t> unused;
     const SubsampleResult before = resident_sample("mate overlap", unused);
     if (copy_stream_) HIPCHK(hipStreamSynchronize(copy_stream_)); // (the numbers of filtered blocks were written there)
@@ -481,7 +484,7 @@ void Mapper::pair_overlap_kept(const PairSetting& set, std::vector<int32_t>& shi
     };
     dev::PairOverlapArgs args {};
     args.loc = d_loc.data(); args.mate = d_mate.data(); args.n = n; args.n1 = n1;
-    args.min_overlap = set.min_overlap; args.error_milli = set.error_milli; args.clip = set.clip ? 1 : 0;
+    args.min_overlap = set.min_overlap; args.error_milli = set.error_milli; args.clip = set.clip ? 1 : 0; args.merge = set.merge ? 1 : 0;
     args.shift = d_shift.data(); args.keep = d_keep.data(); args.counts = d_counts.data(); args.err = d_err.data();
     HIPCHK(dev::launch_pair_overlap(args, stream_));
     uint32_t err = 0;
@@ -504,7 +507,8 @@ void Mapper::pair_overlap_kept(const PairSetting& set, std::vector<int32_t>& shi
         }
     for (int i = 0; i < dev::PO_WORDS; ++i)
         if (i != dev::PO_PAIRS && i != dev::PO_READS) counts[i] = got[i];
-    if (counts[dev::PO_BASES_KEPT] == counts[dev::PO_BASES_BEFORE]) { // no read lost a base: nothing else happens
+    // no read lost a base (every merged pair loses the columns both mates covered): nothing else happens
+    if (counts[dev::PO_BASES_KEPT] == counts[dev::PO_BASES_BEFORE]) {
         pair_.src.clear(); // (the numbers are dropped after the stage)
         pair_.spent = true;
         hand_over();
@@ -523,8 +527,60 @@ void Mapper::pair_overlap_kept(const PairSetting& set, std::vector<int32_t>& shi
     }
     HIPCHK(hipMemsetAsync(d_zero.data(), 0, d_zero.bytes(), stream_));
     uint32_t* const d_cerr = d_err.data() + 1;
+    // mate merging: one side-1 block laid out by the new lengths in d_noff (pair_merge.hip).  A packed block is written whole by the merge
+    // kernel into zeroed words -- every merged read, and every other read's kept bases -- with the unknown bases of all of them in a bitmap
+    // that becomes the block's ascending list; an ASCII block has its other reads copied byte for byte and its merged reads written as text
+    DeviceBuffer<uint16_t> d_mbits;
+    DeviceBuffer<uint32_t> d_mcount, d_mprefix;
+    DeviceBuffer<unsigned char> d_mtemp;
+    DeviceBuffer<unsigned long long> d_mwords;
+    if (set.merge) {
+        d_mwords.alloc(dev::PM_WORDS + 1);
+        HIPCHK(hipMemsetAsync(d_mwords.data(), 0, d_mwords.bytes(), stream_));
+    }
     ResidentSet fresh;
     fresh.cap = resident_.cap;
+    const auto merge_block = [&](size_t b, uint64_t nb) {
+        const DeviceBatch& ob = old[b];
+        const uint64_t nr = ob.n_reads, first = resident_.first[b];
+        const uint64_t n_words = (nb + 15) / 16, payload = ob.packed ? n_words * 4 : nb;
+        const std::optional<BlockRoom> room = fresh.take_block(payload, nr, 0);
+        if (!room) throw Error(DRPRG_ENOMEM, "mate merging: no device memory for the merged reads beside the resident sample");
+        dev::PairMergeArgs m {};
+        m.loc = d_loc.data(); m.mate = d_mate.data(); m.shift = d_shift.data(); m.n = n; m.n1 = n1; m.first = first; m.n_reads = nr;
+        m.noff = d_noff.data(); m.new_bases = nb; m.counts = d_mwords.data(); m.err = d_cerr;
+        uint64_t* list = nullptr;
+        unsigned long long n_list = 0;
+        if (ob.packed) {
+            const uint64_t chunks = (uint64_t)dev::base_mask_tiles(nb) + 1;
+            grow(d_mbits, (n_words + 8 + 3) / 4 * 4);
+            grow(d_mcount, chunks);
+            grow(d_mprefix, chunks);
+            grow(d_mtemp, dev::scan_temp_bytes((uint32_t)chunks));
+            unsigned long long* const d_listed = d_mwords.data() + dev::PM_WORDS;
+            HIPCHK(hipMemsetAsync(d_mbits.data(), 0, (n_words + 8) * sizeof(uint16_t), stream_));
+            HIPCHK(hipMemsetAsync(d_listed, 0, sizeof(unsigned long long), stream_));
+            HIPCHK(hipMemsetAsync(room->bases, 0, payload + 64, stream_));
+            m.words = reinterpret_cast<uint32_t*>(room->bases); m.nbits = d_mbits.data(); m.all = 1;
+            HIPCHK(dev::launch_pair_merge(m, stream_));
+            HIPCHK(dev::launch_pair_merge_bits_count(d_mbits.data(), nb, d_mcount.data(), d_listed, stream_));
+            HIPCHK(hipMemcpyAsync(&n_list, d_listed, sizeof n_list, hipMemcpyDeviceToHost, stream_));
+            HIPCHK(hipStreamSynchronize(stream_));
+            if (n_list) {
+                if (!(list = fresh.take_list(n_list))) throw Error(DRPRG_ENOMEM, "mate merging: no device memory for the merged reads beside the resident sample");
+                HIPCHK(dev::launch_base_mask_emit(d_mbits.data(), nb, d_mcount.data(), d_mprefix.data(), d_mtemp.data(), d_mtemp.size(), list, n_list, stream_));
+            }
+        } else {
+            HIPCHK(hipMemsetAsync(room->bases + payload, 0, 64, stream_));
+            HIPCHK(dev::launch_pair_merge_table(ob.d_bases, ob.d_offsets, nr, ob.n_bases, first, n1, d_shift.data(), d_keep.data(), d_noff.data(), nb, d_table.data(), d_cerr,
+                stream_));
+            HIPCHK(dev::launch_gather_reads(d_table.data(), (uint32_t)nr, room->bases, stream_));
+            m.text = room->bases;
+            HIPCHK(dev::launch_pair_merge(m, stream_));
+        }
+        HIPCHK(hipMemcpyAsync(room->offsets, d_noff.data(), (nr + 1) * sizeof(uint64_t), hipMemcpyDeviceToDevice, stream_));
+        fresh.add(DeviceBatch { room->bases, room->offsets, nr, nb, ob.packed, list, (uint64_t)n_list }, nr);
+    };
     try {
         for (size_t b = 0; b < old.size(); ++b) {
             const DeviceBatch& ob = old[b];
@@ -536,6 +592,11 @@ void Mapper::pair_overlap_kept(const PairSetting& set, std::vector<int32_t>& shi
             const uint64_t n_npos = ob.packed ? ob.n_npos : 0;
             const uint64_t* const d_end = d_keep.data() + first;
             HIPCHK(dev::launch_pair_offsets(d_end, nr, d_noff.data(), d_temp.data(), d_temp.size(), stream_));
+            if (set.merge && first < n1) { // a side-1 block under mate merging: the merged reads are written, not copied
+                fresh.count_empty(first - fresh.seen);
+                merge_block(b, nb);
+                continue;
+            }
             dev::ReadTrimFill tf { ob.d_offsets, nullptr, d_zero.data(), d_end, d_noff.data(), nr, ob.n_bases, nb, ob.d_bases, nullptr,
                 ob.packed ? d_start.data() : nullptr, ob.packed ? nullptr : d_table.data(), nullptr, d_cerr };
             dev::ReadTrimNpos np {};
@@ -560,7 +621,13 @@ void Mapper::pair_overlap_kept(const PairSetting& set, std::vector<int32_t>& shi
             fresh.add(DeviceBatch { room->bases, room->offsets, nr, nb, ob.packed, n_list ? room->npos : nullptr, n_list }, nr);
         }
         fresh.count_empty(n - fresh.seen);
-        compaction_clean(d_cerr, "mate overlap: the resident blocks' offsets and the kept lengths do not fit each other");
+        if (set.merge) {
+            unsigned long long mw[dev::PM_WORDS];
+            HIPCHK(hipMemcpyAsync(mw, d_mwords.data(), sizeof mw, hipMemcpyDeviceToHost, stream_)); // (compaction_clean waits for it)
+            compaction_clean(d_cerr, "mate merging: the resident blocks' offsets, the shifts and the new lengths do not fit each other");
+            for (int i = 0; i < dev::PM_WORDS; ++i) merged[i] = mw[i];
+        } else
+            compaction_clean(d_cerr, "mate overlap: the resident blocks' offsets and the kept lengths do not fit each other");
     } catch (...) {
         (void)hipStreamSynchronize(stream_); // (nothing writes the new arenas any more when their owners release them)
         throw;
@@ -569,6 +636,55 @@ void Mapper::pair_overlap_kept(const PairSetting& set, std::vector<int32_t>& shi
     hand_over();
 }
 
+namespace {
+// what one call of the pair kernels on the caller's batches owns, up to and including launch_pair_overlap
+struct PairDeviceRun {
+    DeviceBuffer<uint16_t> d_bits[2];
+    DeviceBuffer<uint32_t> d_err, d_src, d_res2, d_mate;
+    DeviceBuffer<uint64_t> d_keep;
+    DeviceBuffer<dev::DedupLoc> d_loc;
+    DeviceBuffer<unsigned long long> d_counts;
+};
+
+void pair_device_launch(PairDeviceRun& r, const Mapper::PairSetting& set, const Mapper::PairSide& a, const Mapper::PairSide& b, uint64_t n_pairs, int32_t* d_shift,
+    hipStream_t stream)
+{
+    if (!set.on()) throw Error(DRPRG_EINVAL, "mate overlap: no setting (drprg_hip_set_pair_overlap)");
+    if (!a.d_offsets || !b.d_offsets || !d_shift || (a.n_bases && !a.d_words) || (b.n_bases && !b.d_words) || (a.n_npos && !a.d_npos) || (b.n_npos && !b.d_npos))
+        throw Error(DRPRG_EINVAL, "null device pointer");
+    if (n_pairs >= (1ull << 31)) throw Error(DRPRG_EOVERFLOW, "mate overlap: 2^32 reads or more in one call");
+    const uint64_t n = 2 * n_pairs;
+    const Mapper::PairSide* side[2] = { &a, &b };
+    r.d_err.alloc(2); r.d_src.alloc(n_pairs); r.d_res2.alloc(n_pairs); r.d_mate.alloc(n); r.d_keep.alloc(n + 1); r.d_loc.alloc(n); r.d_counts.alloc(dev::PO_WORDS + dev::PM_WORDS + 1);
+    HIPCHK(hipMemsetAsync(r.d_err.data(), 0, r.d_err.bytes(), stream));
+    HIPCHK(hipMemsetAsync(r.d_loc.data(), 0, r.d_loc.bytes(), stream));
+    HIPCHK(hipMemsetAsync(r.d_mate.data(), 0xFF, r.d_mate.bytes(), stream));
+    HIPCHK(hipMemsetAsync(r.d_keep.data(), 0, r.d_keep.bytes(), stream));
+    HIPCHK(hipMemsetAsync(r.d_counts.data(), 0, r.d_counts.bytes(), stream));
+    for (int s = 0; s < 2; ++s) {
+        const Mapper::PairSide& p = *side[s];
+        const uint64_t n_words = (p.n_bases + 15) / 16;
+        if (p.n_npos) {
+            r.d_bits[s].alloc(n_words + 8);
+            HIPCHK(hipMemsetAsync(r.d_bits[s].data(), 0, r.d_bits[s].bytes(), stream));
+            HIPCHK(dev::launch_mark_npos(p.d_npos, p.n_npos, p.n_bases, r.d_bits[s].data(), stream));
+        }
+        const dev::DedupBatch batch { p.d_words, p.n_npos ? r.d_bits[s].data() : nullptr, p.d_offsets, n_pairs, p.n_bases };
+        HIPCHK(dev::launch_dedup_loc(batch, s * n_pairs, n, r.d_loc.data(), r.d_err.data(), stream));
+    }
+    // every read has the source number of its place, and side 2's resident numbers follow side 1's
+    HIPCHK(dev::launch_pair_numbers(nullptr, nullptr, n_pairs, ~0ull, 0, n_pairs, r.d_src.data(), r.d_err.data(), stream));
+    HIPCHK(dev::launch_pair_numbers(nullptr, nullptr, n_pairs, ~0ull, (uint32_t)n_pairs, n_pairs, r.d_res2.data(), r.d_err.data(), stream));
+    HIPCHK(dev::launch_pair_mates(r.d_src.data(), r.d_src.data(), (uint32_t)n_pairs, r.d_src.data(), r.d_res2.data(), (uint32_t)n_pairs, n, r.d_mate.data(), r.d_err.data(),
+        stream));
+    dev::PairOverlapArgs args {};
+    args.loc = r.d_loc.data(); args.mate = r.d_mate.data(); args.n = n; args.n1 = n_pairs;
+    args.min_overlap = set.min_overlap; args.error_milli = set.error_milli; args.clip = set.clip ? 1 : 0; args.merge = set.merge ? 1 : 0;
+    args.shift = d_shift; args.keep = r.d_keep.data(); args.counts = r.d_counts.data(); args.err = r.d_err.data();
+    HIPCHK(dev::launch_pair_overlap(args, stream));
+}
+} // namespace
+
 void Mapper::pair_overlap_device(const PairSetting& set, const PairSide& a, const PairSide& b, uint64_t n_pairs, int32_t* d_shift, uint64_t* d_keep_a, uint64_t* d_keep_b,
     uint64_t counts[dev::PO_WORDS], hipStream_t stream)
 {
@@ -576,55 +692,89 @@ void Mapper::pair_overlap_device(const PairSetting& set, const PairSide& a, cons
     if (n_pairs == 0) return;
     HIPCHK(hipSetDevice(device_));
     if (!stream) stream = stream_;
-    if (!set.on()) throw Error(DRPRG_EINVAL, "mate overlap: no setting (drprg_hip_set_pair_overlap)");
-    if (!a.d_offsets || !b.d_offsets || !d_shift || !d_keep_a || !d_keep_b || (a.n_bases && !a.d_words) || (b.n_bases && !b.d_words) || (a.n_npos && !a.d_npos) ||
-        (b.n_npos && !b.d_npos))
-        throw Error(DRPRG_EINVAL, "null device pointer");
-    if (n_pairs >= (1ull << 31)) throw Error(DRPRG_EOVERFLOW, "mate overlap: 2^32 reads or more in one call");
+    if (!d_keep_a || !d_keep_b) throw Error(DRPRG_EINVAL, "null device pointer");
+    PairDeviceRun r;
+    PairSetting plain = set;
+    plain.merge = false; // (this entry states the cut: the kept lengths are those of the reads as they lie)
+    pair_device_launch(r, plain, a, b, n_pairs, d_shift, stream);
     const uint64_t n = 2 * n_pairs;
-    const PairSide* side[2] = { &a, &b };
-    DeviceBuffer<uint16_t> d_bits[2];
-    DeviceBuffer<uint32_t> d_err, d_src, d_res2, d_mate;
-    DeviceBuffer<uint64_t> d_keep;
-    DeviceBuffer<dev::DedupLoc> d_loc;
-    DeviceBuffer<unsigned long long> d_counts;
-    d_err.alloc(1); d_src.alloc(n_pairs); d_res2.alloc(n_pairs); d_mate.alloc(n); d_keep.alloc(n); d_loc.alloc(n); d_counts.alloc(dev::PO_WORDS);
-    HIPCHK(hipMemsetAsync(d_err.data(), 0, d_err.bytes(), stream));
-    HIPCHK(hipMemsetAsync(d_loc.data(), 0, d_loc.bytes(), stream));
-    HIPCHK(hipMemsetAsync(d_mate.data(), 0xFF, d_mate.bytes(), stream));
-    HIPCHK(hipMemsetAsync(d_keep.data(), 0, d_keep.bytes(), stream));
-    HIPCHK(hipMemsetAsync(d_counts.data(), 0, d_counts.bytes(), stream));
-    for (int s = 0; s < 2; ++s) {
-        const PairSide& p = *side[s];
-        const uint64_t n_words = (p.n_bases + 15) / 16;
-        if (p.n_npos) {
-            d_bits[s].alloc(n_words + 8);
-            HIPCHK(hipMemsetAsync(d_bits[s].data(), 0, d_bits[s].bytes(), stream));
-            HIPCHK(dev::launch_mark_npos(p.d_npos, p.n_npos, p.n_bases, d_bits[s].data(), stream));
-        }
-        const dev::DedupBatch batch { p.d_words, p.n_npos ? d_bits[s].data() : nullptr, p.d_offsets, n_pairs, p.n_bases };
-        HIPCHK(dev::launch_dedup_loc(batch, s * n_pairs, n, d_loc.data(), d_err.data(), stream));
-    }
-    // every read has the source number of its place, and side 2's resident numbers follow side 1's
-    HIPCHK(dev::launch_pair_numbers(nullptr, nullptr, n_pairs, ~0ull, 0, n_pairs, d_src.data(), d_err.data(), stream));
-    HIPCHK(dev::launch_pair_numbers(nullptr, nullptr, n_pairs, ~0ull, (uint32_t)n_pairs, n_pairs, d_res2.data(), d_err.data(), stream));
-    HIPCHK(dev::launch_pair_mates(d_src.data(), d_src.data(), (uint32_t)n_pairs, d_src.data(), d_res2.data(), (uint32_t)n_pairs, n, d_mate.data(), d_err.data(), stream));
-    dev::PairOverlapArgs args {};
-    args.loc = d_loc.data(); args.mate = d_mate.data(); args.n = n; args.n1 = n_pairs;
-    args.min_overlap = set.min_overlap; args.error_milli = set.error_milli; args.clip = set.clip ? 1 : 0;
-    args.shift = d_shift; args.keep = d_keep.data(); args.counts = d_counts.data(); args.err = d_err.data();
-    HIPCHK(dev::launch_pair_overlap(args, stream));
-    HIPCHK(hipMemcpyAsync(d_keep_a, d_keep.data(), n_pairs * sizeof(uint64_t), hipMemcpyDeviceToDevice, stream));
-    HIPCHK(hipMemcpyAsync(d_keep_b, d_keep.data() + n_pairs, n_pairs * sizeof(uint64_t), hipMemcpyDeviceToDevice, stream));
+    HIPCHK(hipMemcpyAsync(d_keep_a, r.d_keep.data(), n_pairs * sizeof(uint64_t), hipMemcpyDeviceToDevice, stream));
+    HIPCHK(hipMemcpyAsync(d_keep_b, r.d_keep.data() + n_pairs, n_pairs * sizeof(uint64_t), hipMemcpyDeviceToDevice, stream));
     uint32_t err = 0;
     unsigned long long got[dev::PO_WORDS];
-    HIPCHK(hipMemcpyAsync(&err, d_err.data(), sizeof err, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipMemcpyAsync(got, d_counts.data(), sizeof got, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(&err, r.d_err.data(), sizeof err, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(got, r.d_counts.data(), sizeof got, hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
     if (err) throw Error(DRPRG_EINVAL, "mate overlap: the offsets of a side do not ascend inside its n_bases");
     for (int i = 0; i < dev::PO_WORDS; ++i) counts[i] = got[i];
     counts[dev::PO_PAIRS] = n_pairs;
     counts[dev::PO_READS] = n;
+}
+
+void Mapper::pair_merge_device(const PairSetting& set, const PairSide& a, const PairSide& b, uint64_t n_pairs, int32_t* d_shift, uint64_t* d_out_offsets, uint32_t* d_out_words,
+    uint64_t cap_words, uint64_t* d_out_npos, uint64_t cap_npos, uint64_t* n_out_npos, uint64_t counts[dev::PO_WORDS], uint64_t merged[dev::PM_WORDS], hipStream_t stream)
+{
+    for (int i = 0; i < dev::PO_WORDS; ++i) counts[i] = 0;
+    for (int i = 0; i < dev::PM_WORDS; ++i) merged[i] = 0;
+    *n_out_npos = 0;
+    if (n_pairs == 0) return;
+    HIPCHK(hipSetDevice(device_));
+    if (!stream) stream = stream_;
+    if (!set.merge) throw Error(DRPRG_EINVAL, "mate merging: the stage is not switched on (drprg_hip_set_pair_merge)");
+    if (!d_out_offsets || (cap_words && !d_out_words) || (cap_npos && !d_out_npos)) throw Error(DRPRG_EINVAL, "null device pointer");
+    PairDeviceRun r;
+    pair_device_launch(r, set, a, b, n_pairs, d_shift, stream);
+    const uint64_t n = 2 * n_pairs;
+    // the merged batch's offsets: the new length of every merged a, nothing for any other pair
+    DeviceBuffer<uint64_t> d_len;
+    DeviceBuffer<unsigned char> d_temp;
+    d_len.alloc(n_pairs + 1);
+    d_temp.alloc(dev::read_trim_temp_bytes(n_pairs));
+    HIPCHK(dev::launch_pair_merge_lengths(d_shift, r.d_keep.data(), n_pairs, d_len.data(), stream));
+    HIPCHK(dev::launch_pair_offsets(d_len.data(), n_pairs, d_out_offsets, d_temp.data(), d_temp.size(), stream));
+    uint32_t err = 0;
+    uint64_t nb = 0;
+    unsigned long long got[dev::PO_WORDS + dev::PM_WORDS + 1];
+    HIPCHK(hipMemcpyAsync(&err, r.d_err.data(), sizeof err, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(&nb, d_out_offsets + n_pairs, sizeof nb, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    if (err) throw Error(DRPRG_EINVAL, "mate overlap: the offsets of a side do not ascend inside its n_bases");
+    const uint64_t n_words = (nb + 15) / 16;
+    if (n_words > cap_words) throw Error(DRPRG_EOVERFLOW, "mate merging: the merged reads take " + std::to_string(n_words) + " words, the caller gave room for " +
+                                                          std::to_string(cap_words));
+    DeviceBuffer<uint16_t> d_obits;
+    DeviceBuffer<uint32_t> d_ccount, d_cprefix;
+    DeviceBuffer<unsigned char> d_ntemp;
+    unsigned long long* const d_listed = r.d_counts.data() + dev::PO_WORDS + dev::PM_WORDS;
+    if (nb) {
+        const uint64_t chunks = (uint64_t)dev::base_mask_tiles(nb) + 1;
+        d_obits.alloc((n_words + 8 + 3) / 4 * 4);
+        d_ccount.alloc(chunks); d_cprefix.alloc(chunks); d_ntemp.alloc(dev::scan_temp_bytes((uint32_t)chunks));
+        HIPCHK(hipMemsetAsync(d_obits.data(), 0, d_obits.bytes(), stream));
+        HIPCHK(hipMemsetAsync(d_out_words, 0, n_words * sizeof(uint32_t), stream));
+        dev::PairMergeArgs m {};
+        m.loc = r.d_loc.data(); m.mate = r.d_mate.data(); m.shift = d_shift; m.n = n; m.n1 = n_pairs; m.first = 0; m.n_reads = n_pairs;
+        m.noff = d_out_offsets; m.new_bases = nb; m.words = d_out_words; m.nbits = d_obits.data(); m.text = nullptr; m.all = 0;
+        m.counts = r.d_counts.data() + dev::PO_WORDS; m.err = r.d_err.data() + 1;
+        HIPCHK(dev::launch_pair_merge(m, stream));
+        HIPCHK(dev::launch_pair_merge_bits_count(d_obits.data(), nb, d_ccount.data(), d_listed, stream));
+    }
+    HIPCHK(hipMemcpyAsync(&err, r.d_err.data() + 1, sizeof err, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(got, r.d_counts.data(), sizeof got, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    if (err) throw Error(DRPRG_EIO, "mate merging: the shifts, the mates and the merged batch's offsets do not fit each other");
+    const uint64_t listed = got[dev::PO_WORDS + dev::PM_WORDS];
+    if (listed > cap_npos) throw Error(DRPRG_EOVERFLOW, "mate merging: the merged reads hold " + std::to_string(listed) + " unknown bases, the caller gave room for " +
+                                                        std::to_string(cap_npos));
+    if (listed) {
+        HIPCHK(dev::launch_base_mask_emit(d_obits.data(), nb, d_ccount.data(), d_cprefix.data(), d_ntemp.data(), d_ntemp.size(), d_out_npos, listed, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+    }
+    *n_out_npos = listed;
+    for (int i = 0; i < dev::PO_WORDS; ++i) counts[i] = got[i];
+    counts[dev::PO_PAIRS] = n_pairs;
+    counts[dev::PO_READS] = n;
+    for (int i = 0; i < dev::PM_WORDS; ++i) merged[i] = got[dev::PO_WORDS + i];
 }
 
 // ---- duplicate pairs on the resident sample (the rule: include/drprg_hip.h "duplicate pairs") -------------------------------------------

@@ -275,6 +275,31 @@ class Context:
                                                  d_keep_b, out, stream), self._h)
         return dict(zip(self.PAIR_COUNTS, (int(v) for v in out)))
 
+    # ---- mate merging (include/drprg_hip.h: drprg_hip_set_pair_merge) ----------------------------
+    PAIR_MERGE_COUNTS = ("pairs_merged", "columns_both", "columns_agreeing", "columns_disagreeing", "columns_filled", "columns_unknown", "bases_merged",
+                         "longest_merged")
+
+    def set_pair_merge(self, on=True):
+        """switches mate merging on (behind set_pair_overlap() without clip: pair_overlap() then merges every pair with a chosen shift into
+        one read) or off"""
+        _check(lib.drprg_hip_set_pair_merge(self._h, 1 if on else 0), self._h)
+
+    def pair_merge_info(self):
+        """the eight counts of the last pair_overlap() that merged"""
+        out = (C.c_uint64 * 8)()
+        _check(lib.drprg_hip_pair_merge_info(self._h, out), self._h)
+        return dict(zip(self.PAIR_MERGE_COUNTS, (int(v) for v in out)))
+
+    def pair_merge_device(self, side_a, side_b, n_pairs, d_shift, d_out_offsets, d_out_words, cap_words, d_out_npos, cap_npos, stream=None):
+        """the overlap and the merge kernel alone on two packed batches of n_pairs reads in device memory, the sides as pair_overlap_device
+        takes them.  d_shift: i32 per pair; the merged batch: d_out_offsets (u64[n_pairs + 1]), d_out_words (room for cap_words u32),
+        d_out_npos (room for cap_npos u64, ascending).  Returns (the twelve counts, the eight counts, the length of the list)"""
+        out12, out8, n_list = (C.c_uint64 * 12)(), (C.c_uint64 * 8)(), C.c_uint64(0)
+        (wa, oa, ba, pa, na), (wb, ob, bb, pb, nb) = side_a, side_b
+        _check(lib.drprg_hip_pair_merge_device(self._h, wa, oa, int(ba), pa, int(na), wb, ob, int(bb), pb, int(nb), int(n_pairs), d_shift, d_out_offsets,
+                                               d_out_words, int(cap_words), d_out_npos, int(cap_npos), C.byref(n_list), out12, out8, stream), self._h)
+        return (dict(zip(self.PAIR_COUNTS, (int(v) for v in out12))), dict(zip(self.PAIR_MERGE_COUNTS, (int(v) for v in out8))), int(n_list.value))
+
     # ---- duplicate pairs (include/drprg_hip.h: drprg_hip_set_dedup_pairs) ------------------------
     PAIR_DEDUP_COUNTS = ("units", "units_with_bases", "units_both_mates", "units_dropped", "reads_before", "bases_before", "reads_kept", "bases_kept")
 

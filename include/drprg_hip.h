@@ -395,10 +395,12 @@ int drprg_hip_dedup_keys_device(drprg_hip_ctx* ctx, const void* d_words, const v
  *   context is then that of a file holding side 1's reads and then side 2's, cut by the rule (fastp -i -I | cat | dedupe | rasusa | drprg),
  *   whatever -t, the block boundaries and the input form.
  *   Limits.  A pair from a tandem repeat can qualify at a shift that is not its true one; largest-c keeps the cut smallest then.  Behind
- *   --trim-front or a 5' adapter cut, b loses the columns a no longer has.  Interleaved files, BAM mate flags, merging mates into one read,
- *   quality-weighted correction and contexts over several devices are not served (pair-aware dedup: "duplicate pairs" below).  No claim
+ *   --trim-front or a 5' adapter cut, b loses the columns a no longer has.  Interleaved files, BAM mate flags, quality-weighted
+ *   correction and contexts over several devices are not served (merging mates into one read: "mate merging" below; pair-aware dedup:
+ *   "duplicate pairs" below).  No claim
  *   about real samples is made.
- *   drprg_hip_set_pair_overlap(ctx, min_overlap, error_milli, clip): the setting; all zero: off.  -EINVAL outside the ranges above.  While
+ *   drprg_hip_set_pair_overlap(ctx, min_overlap, error_milli, clip): the setting; all zero: off.  -EINVAL outside the ranges above, and with clip
+ *     set while mate merging is on ("mate merging" below).  While
  *     it is on, every block the resident set takes from drprg_hip_map_fastx is numbered by side (u32 per read, in the resident arenas), and
  *     drprg_hip_map_host* / drprg_hip_map_device* return -EINVAL.  Off, nothing of this exists: no numbers, no launch, no wait.
  *   drprg_hip_begin_mates(ctx): the files mapped from here on are side 2.  -EINVAL without the setting, over several devices, or when
@@ -429,6 +431,48 @@ int drprg_hip_pair_overlap_info(drprg_hip_ctx* ctx, uint64_t out[12]);
 int drprg_hip_pair_overlap_device(drprg_hip_ctx* ctx, const void* d_words_a, const void* d_offsets_a, uint64_t n_bases_a, const void* d_npos_a, uint64_t n_npos_a,
     const void* d_words_b, const void* d_offsets_b, uint64_t n_bases_b, const void* d_npos_b, uint64_t n_npos_b, uint64_t n_pairs, void* d_shift, void* d_keep_a,
     void* d_keep_b, uint64_t out[12], void* hip_stream);
+/* ---- Mate merging: overlapping mates merged into one read on the resident sample, inside the "mate overlap" stage.  THIS BUILD'S OWN
+ * RULE (what fastp -m, PEAR, FLASH and bbmerge are run for); nothing in pandora or drprg pins it.  Everything is in the terms of "mate
+ * overlap": a, b, La, Lb, B[j] = complement(b[Lb-1-j]), the chosen shift d, I = Lb + d (1 <= I <= La + Lb - 1).
+ *   Who is merged.  A judged pair with a chosen shift.  Every other pair -- no shift qualifies, an orphan, a mate longer than 1024 bases --
+ *   passes exactly as under "mate overlap" alone.
+ *   The merged read M has I bases, in a's orientation.  Position p (0 <= p < I) is covered by a iff p < La and by B iff p >= d; the
+ *   qualifying overlap guarantees that one of them holds.  M[p] is: the base of the one mate that covers p; where both cover p -- both
+ *   known and the same letter: that letter; both known and different: the unknown base; exactly one known: the known one; both unknown:
+ *   unknown.  The bases of a at p >= I and the bases of B in front of a's first base are read-through adapter and fall away, as in the
+ *   read-through cut.  No quality is looked at: a disagreement makes the column unknown, it is never decided.
+ *   How M is written.  Upper-case ACGT and N in a block of text; letters and an entry of the unknown list in a packed block (an unknown
+ *   base carries letter 3 there, as an N does).  Every merged read is rewritten whole; every other read keeps its bytes.
+ *   Where M goes.  M takes a's place in side 1 and b stays in side 2 as a read of no bases: the sample's read count does not change and
+ *   nothing is renumbered.  "duplicate pairs" behind the stage sees the unit (M, e), by its own definition of an empty mate.  The context
+ *   afterwards is that of a file holding side 1 with every merged a replaced by M, then side 2 with every merged b empty, whatever -t,
+ *   the block boundaries and the input form.
+ *   Counts.  The twelve counts of "mate overlap" keep their meaning: bases_cut is unchanged; bases_clipped is the number of columns both
+ *   mates covered, min(La,I) + min(Lb,I) - I, which is the clip's figure; reads_emptied counts every merged b; bases_kept is the sum of
+ *   the new lengths.  The eight counts of this stage: pairs_merged, columns_both (columns both mates covered), columns_agreeing,
+ *   columns_disagreeing (made unknown), columns_filled (one known base of two), columns_unknown (unknown in both), bases_merged (the
+ *   bases of the merged reads), longest_merged.  The four column kinds add up to columns_both.
+ *   Limits.  A column with a disagreement costs every k-mer that holds it (up to k of them; 15 at k = 15), and with e = 50 a merged read
+ *   can carry up to 5 % such columns.  A tandem repeat can merge at a wrong shift, as it can be cut at one.  Qualities in the resident
+ *   sample, quality-weighted choice of a base, interleaved input, BAM mate flags and several devices are not served.  No claim about real
+ *   samples is made.
+ *   drprg_hip_set_pair_merge(ctx, on): the switch.  -EINVAL without a mate-overlap setting or while that setting clips (merging subsumes
+ *     the clip); while the switch is on, drprg_hip_set_pair_overlap with clip set is -EINVAL too, and switching the setting off switches
+ *     this off.  A refused call leaves the context as it was.  On, drprg_hip_pair_overlap merges (csrc/pair_merge.hip): no pair has a
+ *     chosen shift: nothing else happens.  Off, nothing of this exists: no launch, no allocation, no wait.
+ *   drprg_hip_pair_merge_info(ctx, out): the eight counts of the last drprg_hip_pair_overlap that merged, since the last reset (all
+ *     zero: none).
+ *   drprg_hip_pair_merge_device: the overlap kernel, then the merge kernel, alone on two caller-owned packed sides given as in
+ *     drprg_hip_pair_overlap_device, under the same stream rule.  d_shift: i32[n_pairs].  The merged reads come back as one packed batch
+ *     of n_pairs reads in which an unmerged pair is a read of no bases: d_out_offsets (u64[n_pairs + 1]), d_out_words (room for cap_words
+ *     words; the bits behind the last base of the last word are clear), d_out_npos (room for cap_npos positions) with *n_out_npos, the
+ *     length of the list, ASCENDING.  out12: the twelve counts, out8: the eight.  -EINVAL without the switch; -EOVERFLOW when the words
+ *     or the list need more room than given (nothing is written beyond it) and for 2^31 pairs or more. */
+int drprg_hip_set_pair_merge(drprg_hip_ctx* ctx, int on);
+int drprg_hip_pair_merge_info(drprg_hip_ctx* ctx, uint64_t out[8]);
+int drprg_hip_pair_merge_device(drprg_hip_ctx* ctx, const void* d_words_a, const void* d_offsets_a, uint64_t n_bases_a, const void* d_npos_a, uint64_t n_npos_a,
+    const void* d_words_b, const void* d_offsets_b, uint64_t n_bases_b, const void* d_npos_b, uint64_t n_npos_b, uint64_t n_pairs, void* d_shift, void* d_out_offsets,
+    void* d_out_words, uint64_t cap_words, void* d_out_npos, uint64_t cap_npos, uint64_t* n_out_npos, uint64_t out12[12], uint64_t out8[8], void* hip_stream);
 /* ---- Duplicate pairs: exact duplicate read PAIRS dropped from the resident sample, behind "mate overlap".  THIS BUILD'S OWN RULE (what
  * fastp -i -I --dedup, clumpify dedupe on pairs and Picard do in front of drprg: they judge the pair); nothing in pandora or drprg pins it.
  * "duplicate reads" judges every read alone, and two different fragments that start at the same base of the same strand have identical
